@@ -2,6 +2,7 @@
 """bench.py -- env-steps/s of the batched F110Env.step path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs B] [--agents A]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one f110_step over all B envs of this rank (every car: single-track
 RK4, 1080-beam ray march, noise, iTTC, (GJK + opponent ray cast for A>1), lap
@@ -9,6 +10,12 @@ logic, autoreset).  Default workload: BASELINE.json configs[2] = 65536 envs x 1
 agent per GPU on example_map (the config the metric's target is quoted on; N>1 is
 configs[4], independent shards, no collective on the step path).  Actions and all
 state are resident in HBM before the timed region.  Prints ONE JSON line (rank 0).
+
+A plain run does only what the headline needs: set-up, reset, W warm-up steps, K
+timed steps (`value`, `ms_per_step`), the outputs of the last timed step if
+--dump-outputs is given, the JSON line.  --full adds everything else the line
+can carry: the `sustained` and `steady_state` regions, the scan kernel's
+`roofline` from hipEvents on sampled timed steps and the `cpu_baseline`.
 """
 import argparse
 import json
@@ -243,6 +250,49 @@ def timed_steps(ranks, step_fn, K):
     return ranks.max_over_ranks(time.perf_counter() - t0, own)
 
 
+DUMP_BYTES = 60 << 20   # what --dump-outputs may write in all (under 64 MB)
+
+
+def step_outputs(result, bitmaps=None):
+    """name -> tensor [B, ...] of what one step hands its caller: (obs, reward, done, info) of F110VecEnv.step, and the
+    bird's-eye bitmaps when they are drawn in the loop."""
+    obs, reward, done, info = result
+    out = {'obs_' + k: v for k, v in obs.items() if k != 'ego_idx'}
+    out['reward'], out['done'] = reward, done
+    out.update(('info_' + k, v) for k, v in info.items())
+    if bitmaps is not None:
+        out['bitmaps'] = bitmaps
+    return out
+
+
+def sample_outputs(outputs, budget=DUMP_BYTES):
+    """Host copies of `outputs` as float32 (float32 and uint8 tensors) or float64 (everything else, integers and flags
+    exactly), all at the same env rows: every env if they fit in `budget` bytes, else a fixed seeded sample of envs
+    (sorted), as many as fit."""
+    import torch
+    B = next(iter(outputs.values())).shape[0]
+
+    def wide(t):
+        return torch.float32 if t.dtype in (torch.float32, torch.uint8) else torch.float64
+    per_env = sum(t[0].numel() * (4 if wide(t) == torch.float32 else 8) for t in outputs.values())
+    n = min(B, budget // per_env)
+    rows = None
+    if n < B:
+        rows = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    res = {}
+    for name, t in outputs.items():
+        if rows is not None:
+            t = t.index_select(0, torch.as_tensor(rows, device=t.device))
+        res[name] = t.to(wide(t)).cpu().numpy()
+    return res
+
+
+def write_outputs(dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def rank_workload(rank, B, A, pool=16):
     """Each rank owns an independent shard of envs: its own spawn jitter (seed 2025+rank)
     and action stream (seed 777+rank); SURVEY 8(d)."""
@@ -346,24 +396,40 @@ def main(argv=None):
                     help='EXTRA untimed steps before reset + warmup (an idle MI355X needs ~25 ms of load to reach its '
                          'clocks: tools/step_ramp.py).  0 (default): the protocol is exactly W warm-up + K timed steps; '
                          'the effect of the clock ramp is reported separately as `sustained`')
-    ap.add_argument('--sustained', type=int, default=200,
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: `sustained` and `steady_state` (200 steps each unless '
+                         'set), the scan kernel\'s `roofline` from hipEvents and the `cpu_baseline`; off by default')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step handed its caller (obs, reward, done, info; '
+                         'the bitmaps with --bitmap) to DIR/<name>.npy as float32 / float64, rank 0 only; at most 60 MiB in '
+                         'all: every env, or a fixed seeded sample of envs (the same rows in every file)')
+    ap.add_argument('--sustained', type=int, default=None,
                     help='after the timed region, time this many further steps (clocks up, cars scattered) and report '
-                         'them as `sustained` beside `value` (0 = skip); never part of `value`')
-    ap.add_argument('--steady-state', type=int, default=200,
+                         'them as `sustained` beside `value` (0 = skip; default 200 with --full, else 0); never part of `value`')
+    ap.add_argument('--steady-state', type=int, default=None,
                     help='after `sustained`, stagger the envs over 1 024 noise rows (the regime of a long-running batch) and time '
-                         'this many steps; reported as `steady_state` beside `value` (0 = skip); never part of `value`')
+                         'this many steps; reported as `steady_state` beside `value` (0 = skip; default 200 with --full, else 0); '
+                         'never part of `value`')
     ap.add_argument('--repeats', type=int, default=1,
                     help='R > 1: after the protocol region (which alone gives `value`), R - 1 further timed regions of K steps '
                          'each; the median of all R is reported beside it as `median_of_repeats` (SURVEY 8d: median of 5)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no `cpu_baseline`')
     ap.add_argument('--no-scan-events', action='store_true',
-                    help='do not bracket the scan kernel with hipEvents (roofline becomes null)')
+                    help='with --full: do not bracket the scan kernel with hipEvents (roofline becomes null)')
     ap.add_argument('--scan-events-every', type=int, default=4,
-                    help='hipEvent pairs ride on the scan dispatch of every Nth TIMED step (a dispatch with events costs '
-                         'the stream ~10 us of idle time around it); 1 = every step')
+                    help='with --full: hipEvent pairs ride on the scan dispatch of every Nth TIMED step (a dispatch with events '
+                         'costs the stream ~10 us of idle time around it); 1 = every step')
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    for name in ('sustained', 'steady_state'):
+        if getattr(args, name) is None:
+            setattr(args, name, 200 if args.full else 0)
+    # the roofline's hipEvents and the CPU oracle's timing are --full's alone
+    args.scan_events = args.full and not args.no_scan_events
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
     # N > 1 without a launcher (the driver's `python3 bench.py --gpus N` form): start the ranks ourselves, BEFORE
     # torch is imported or any HIP call is made in this process
     if args.gpus > 1 and 'RANK' not in os.environ:
@@ -397,8 +463,9 @@ def main(argv=None):
     # host-side preparation first (~0.1 s of NumPy), so that everything the GPU does before the timed region -- map
     # pipeline, uploads, reset, warm-up -- follows back to back instead of being separated from it by an idle stretch
     poses_np, acts_np = rank_workload(rank, B, A, POOL)
+    # (the lookup counters feed the roofline only; bound without f110_profile_begin they would count on every step)
     env = F110VecEnv(B, map=workload.EXAMPLE_MAP, map_ext='.png', num_agents=A, timestep=0.01, seed=12345,
-                     device=local_rank, autoreset=True, count_lookups=True)
+                     device=local_rank, autoreset=True, count_lookups=args.scan_events)
     poses = torch.as_tensor(poses_np, device=dev)
     acts = torch.as_tensor(acts_np, device=dev)  # resident in HBM before the timed region
     # The first ~30 steps after an idle period run up to 15 % slower (0.80 -> 0.69 ms) whatever the env state
@@ -414,7 +481,8 @@ def main(argv=None):
     for k in range(W):
         env.step(acts[k % POOL])
     lookups = env.eng.t['lookups']
-    lookups.zero_()
+    if lookups is not None:
+        lookups.zero_()
     if args.policy == 'pure_pursuit':
         # secondary mode: the reference's waypoint follower runs on the GPU in front of every step
         rl = workload.load_waypoints(workload.RACELINE)
@@ -422,9 +490,11 @@ def main(argv=None):
         step_fn = lambda k: env.step(env.pure_pursuit(wp, 0.82461887897713965, 1.375))  # noqa: E731
         for k in range(W):
             step_fn(k)
-        lookups.zero_()
+        if lookups is not None:
+            lookups.zero_()
     else:
         step_fn = lambda k: env.step(acts[(W + k) % POOL])  # noqa: E731
+    imgs = None
     if args.bitmap != 'none':
         from red_gym_amd.lidar import LidarBitmap
         to_img = LidarBitmap(1080, bg_color='black', draw_mode=args.bitmap, device=local_rank)
@@ -435,18 +505,22 @@ def main(argv=None):
             obs = inner(k)[0]
             to_img(obs['scans'][:, 0], out=imgs)
         step_fn(0)
-        lookups.zero_()
+        if lookups is not None:
+            lookups.zero_()
     NEVER = 1 << 30  # a sampling period no run reaches: the measurement aid active, no step instrumented
-    if not args.no_scan_events:
+    if args.scan_events:
         env.eng.profile_begin(K, every=max(1, args.scan_events_every))  # hipEvent pairs + lookup counting on every Nth timed scan launch
-    else:
-        env.eng.profile_begin(1, every=NEVER)
     elapsed = timed_steps(ranks, step_fn, K)
     per_rank = list(ranks.last_per_rank)                                      # every rank's own elapsed seconds
-    scan_prof = env.eng.profile_end()                                         # the sampled launches of the K timed steps only
-    if args.no_scan_events:
-        scan_prof = None
-    tot_lookups = int(lookups.to(torch.int64).sum().item())                  # ... and their table reads
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the step's outputs are views of the engine's buffers: copied out before any further step overwrites them
+        # (env._result() is what env.step returned for the last timed step)
+        dumped = sample_outputs(step_outputs(env._result(), imgs))
+    scan_prof = None
+    if args.scan_events:
+        scan_prof = env.eng.profile_end()                                     # the sampled launches of the K timed steps only
+    tot_lookups = int(lookups.to(torch.int64).sum().item()) if lookups is not None else 0   # ... and their table reads
     repeats = None
     if args.repeats > 1:
         env.eng.profile_begin(1, every=NEVER)
@@ -494,7 +568,7 @@ def main(argv=None):
     if rank == 0:
         value = world * B * K / elapsed
         roof = None
-        if not args.no_scan_events:
+        if args.scan_events:
             scan_ms, n_launch = scan_prof
             cars = B * A
             # SURVEY 8(d) byte model, per car-step: L*4 + 1080*4 + 72
@@ -545,10 +619,12 @@ def main(argv=None):
                'roofline': roof, 'sustained': sustained, 'steady_state': steady}
         if repeats:
             out['median_of_repeats'] = repeats
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(A)
     env.close()
     ranks.close()
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     if rank == 0:
         print(json.dumps(out), flush=True)
 

@@ -21,7 +21,7 @@ def test_bench_with_a_forced_one_rank_rccl_group():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT', 'F110_BENCH_BACKEND')}
     env.update(F110_BENCH_FORCE_GROUP='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--envs', '4096', '--steps', '10',
-                        '--warmup', '3', '--sustained', '0', '--no-cpu-baseline', '--repeats', '3'],
+                        '--warmup', '3', '--full', '--sustained', '0', '--no-cpu-baseline', '--repeats', '3'],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]

@@ -5,7 +5,6 @@ import json
 import os
 
 import numpy as np
-import pytest
 
 from oracle import bitmap as ob
 
@@ -115,12 +114,11 @@ def test_point_grid_oracle_equals_the_reference_dataset(golden):
 def test_reference_dataset_files_have_the_format_the_writer_targets():
     """The reference ships datasets its recorder wrote (f1tenth_gym/examples/lidar_datasets/*.npz): key 'data',
     uint8 [N,256,256], values {0, 1} -- the format LidarDatasetWriter.save reproduces (checked on the GPU against
-    g12).  Dev container only: the reference tree does not exist on the GPU box."""
+    g12).  The first three of those files, unchanged, are stored under tests/golden/lidar_datasets/."""
     import glob
-    files = sorted(glob.glob('/root/reference/f1tenth_gym/examples/lidar_datasets/*.npz'))
-    if not files:
-        pytest.skip('reference tree not present')
-    for f in files[:3]:
+    files = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'lidar_datasets', '*.npz')))
+    assert len(files) == 3
+    for f in files:
         d = np.load(f, allow_pickle=False)   # plain arrays: nothing is unpickled
         assert d.files == ['data']
         a = d['data']

@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 export TMPDIR=/tmp
 cd /tmp
 O=$ROOT/gpurun_out/prof_r05_default
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o bench -- python3 $ROOT/bench.py --no-cpu-baseline --sustained 0 --steady-state 0 > $O.json 2> $O.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline --sustained 0 --steady-state 0 > $O.json 2> $O.err
 python3 - <<PY
 import csv,glob,json
 f=glob.glob('$O/**/*kernel_trace.csv',recursive=True)[0]
