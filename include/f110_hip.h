@@ -26,9 +26,9 @@
  *   - there is no f110_get_state / f110_set_state: the whole simulation state lives in the CALLER-owned
  *     buffers of the f110_buffers struct, bound once with f110_bind, so reading, checkpointing or overwriting the state is
  *     an ordinary access to the caller's own memory between steps (F110VecEnv.state_dict / load_state_dict).
- *   - tuning knobs read from the environment at first use (sweeps only; the defaults are the measured optimum):
- *     F110_WPC = 1|2|4|8 wavefronts per car in the scan kernel; F110_STAGES = "cars:log2waves,..." wave -> car
- *     stage list of a scan launch ("*" = the remaining cars), see launch_scan in csrc/f110_step.hip.
+ *   - two test hooks are read from the environment: F110_SCAN_STORES = plain|stream (which store instantiation of
+ *     the scan kernel a step launches) and F110_BM_GRID = <n> (workgroups of a bitmap launch); results do not
+ *     depend on them.
  *   - all arithmetic that decides an index, a collision or a lap toggle is
  *     IEEE fp64 in the reference's operation order (no FMA contraction).
  */
@@ -276,8 +276,8 @@ int f110_pack_env(f110_handle *h, int32_t env, double *out_dev, void *stream);
 
 /* Tuning / test hook: how a scan launch maps wavefronts to cars, as "cars:lg,cars:lg,..." in launch order with one
  * "*" for the remaining cars: a car of a stage gets 2^lg wavefronts (lg = 0..3; several short-lived waves per car pay
- * for small batches and at the end of a launch).  NULL or "" restores the built-in choice (or the F110_STAGES
- * environment variable).  A malformed list (syntax, lg > 3, two "*", more than 6 stages, more cars than the handle
+ * for small batches and at the end of a launch).  NULL or "" restores the built-in choice (scan_stage_list in
+ * csrc/f110_step.hip).  A malformed list (syntax, lg > 3, two "*", more than 6 stages, more cars than the handle
  * has) is refused with F110_E_INVALID and changes nothing.  Results do not depend on it. */
 int f110_set_scan_stages(f110_handle *h, const char *spec);
 

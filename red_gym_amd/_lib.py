@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('F110_LIB') or os.path.join(_HERE, 'libf110_hip.so')  # F110_LIB: kernel-variant sweeps
+LIB_PATH = os.environ.get('F110_LIB') or os.path.join(_HERE, 'libf110_hip.so')  # F110_LIB: another build (tools/build_variant.sh)
 
 F110_MAX_AGENTS = 32
 F110_MAX_NOISE_SLOTS = 64
@@ -137,8 +137,6 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in SYMBOLS.items():
-        if os.environ.get('F110_LIB_OLDER') == '1' and not hasattr(lib, name):
-            continue             # A/B runs against a library built from an earlier tree (tools/sweep.py): newer entry points are absent
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.argtypes = argtypes
         fn.restype = C.c_int

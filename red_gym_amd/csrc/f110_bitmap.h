@@ -22,19 +22,10 @@
 namespace f110 {
 
 enum { BM_FILL = 0, BM_POLYGON = 1, BM_RAYS = 2 };
-#ifndef F110_BM_THREADS
-#define F110_BM_THREADS 512
-#endif
-constexpr int BM_THREADS = F110_BM_THREADS;
+constexpr int BM_THREADS = 512; // per image (256 or 384: ~7 % slower, profiles/r05_bitmap.txt)
 constexpr int BM_MAX_T = 2048;
 constexpr int BM_PER_MAX = (BM_MAX_T + BM_THREADS - 1) / BM_THREADS;
 constexpr int BM_XY_SHIFT = 16;
-constexpr int BM_TL = 10;
-#if defined(F110_BM_TIMELINE)
-#define BM_STAMP(i) do { if (tid == 0) s_tl[i] = wall_clock64(); } while (0)
-#else
-#define BM_STAMP(i) do { } while (0)
-#endif
 
 struct BitmapArgs {
     const void *scans;       // [n, stride] f32 or f64
@@ -49,7 +40,6 @@ struct BitmapArgs {
     unsigned char *out;      // [n, rows, cols(, channels)]
     int S;                   // words per bit-plane row (cols/32 rounded up, made odd)
     int qcap;                // segment records held in LDS at a time (bm_queue_cap)
-    unsigned long long *tl;  // diagnostics (-DF110_BM_TIMELINE): [n][BM_TL] clock stamps of thread 0 at the stage boundaries
 };
 
 // One segment / polygon edge, ready to be walked item by item (32 bytes, two ds_read_b128):
@@ -64,21 +54,10 @@ struct alignas(16) EdgeRec {
     long long x, dx;     // crossing at row ya and its per-row increment
 };
 
-// Segments drawn straight from the points (no record): both ends inside the image and at most this many items.
-#ifndef F110_BM_DIRECT
-#define F110_BM_DIRECT 8
-#endif
-constexpr int BM_DIRECT = F110_BM_DIRECT;
-#ifndef F110_BM_X
-#define F110_BM_X 0   // experiments only (tools/build_variant.sh): 1 = no segments drawn, 2 = no parity pass, 4 = no points
-#endif
-#ifndef F110_BM_PRIO
-#define F110_BM_PRIO 1
-#endif
-#ifndef F110_BM_MIN_SHARE
-#define F110_BM_MIN_SHARE 1
-#endif
-constexpr int BM_MIN_SHARE = F110_BM_MIN_SHARE; // items per thread of the record path's walk, at least
+// Segments drawn straight from the points (no record): both ends inside the image and at most this many items (97 % of a
+// lidar polygon's edges, profiles/r05_bitmap.txt).
+constexpr int BM_DIRECT = 8;
+constexpr int BM_MIN_SHARE = 1; // items per thread of the record path's walk, at least
 
 // LDS of one image (byte offsets, each on a 16-byte boundary):
 //   recs  EdgeRec[qcap]   records of the queued segments of one round (later the 2 KB grey-level table)
@@ -296,9 +275,6 @@ __device__ inline int bm_find(const int *start, int n, int j)
 }
 
 typedef unsigned bm_v4u __attribute__((ext_vector_type(4)));
-#ifndef F110_BM_NT
-#define F110_BM_NT 1
-#endif
 // One 16-byte store of the output image (written once, never read back by this kernel).  STREAM: the wave's
 // lanes write consecutive 16-byte pieces (whole lines per instruction) -> non-temporal; lane-strided pieces
 // are left to the L2 to merge (measured: non-temporal partial lines cost 2.6x on the 3-channel path).
@@ -306,7 +282,7 @@ template <bool STREAM>
 __device__ inline void bm_store16(void *p, unsigned a, unsigned b, unsigned c, unsigned d)
 {
     const bm_v4u v = {a, b, c, d};
-    if (STREAM && F110_BM_NT) __builtin_nontemporal_store(v, reinterpret_cast<bm_v4u *>(p));
+    if (STREAM) __builtin_nontemporal_store(v, reinterpret_cast<bm_v4u *>(p));
     else *reinterpret_cast<bm_v4u *>(p) = v;
 }
 
@@ -434,9 +410,6 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
     unsigned *stage = reinterpret_cast<unsigned *>(s_raw + lay.stage);
     const int stage_words = (a.is_f64 ? 2 : 1) * ((T + 63) & ~63); // of one of the two buffers
 
-#if defined(F110_BM_TIMELINE)
-    __shared__ unsigned long long s_tl[BM_TL];
-#endif
     const int cx = rows / 2, cy = cols / 2; // lidar.py:75: center = (dims[0]//2, dims[1]//2), used as (x, y)
     if (tid0 < 64) s_fdx[tid0] = (tid0 & 7) ? ((tid0 >> 3) << BM_XY_SHIFT) / (tid0 & 7) : 0;
 
@@ -456,12 +429,12 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
                 const double2 c = make_double2(a.cosv[k], a.sinv[k]);
                 beams[k] = (unsigned short)b;
                 cs[k] = c;
-                if (!(F110_BM_X & 4)) pts[k] = bm_point_at(a.scale, bm_range(a, blockIdx.x, b), c.x, c.y, cx, cy); // (round 0: image g)
+                pts[k] = bm_point_at(a.scale, bm_range(a, blockIdx.x, b), c.x, c.y, cx, cy); // (round 0: image g)
             }
         }
         bm_barrier(); // (beams staged)
         const int img1 = bm_image_of(blockIdx.x, 1, gridDim.x, a.n);
-        if (img1 < a.n && !(F110_BM_X & 4)) (void)bm_prefetch(a, img1, beams, stage + stage_words, tid0);
+        if (img1 < a.n) (void)bm_prefetch(a, img1, beams, stage + stage_words, tid0);
     }
     int it = 0;
     // (!AHEAD: one image per workgroup, the launch has a workgroup per image -- the loop is left after one pass, and the
@@ -472,22 +445,15 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
     // then recomputed per image instead of being carried in registers around the whole loop -- the kernel has 64)
     int tid = tid0;
     asm volatile("" : "+v"(tid));
-#if F110_BM_PRIO
     // The CU's arbiter serves the oldest wave first: of the three workgroups that share a CU for the whole launch, the one
     // dispatched first would draw its images a third faster than the last.  The user priority goes round instead.
     if (AHEAD) {
         const int turn = ((int)(blockIdx.x * 3u / gridDim.x) + it) % 3;
         if (turn == 0) __builtin_amdgcn_s_setprio(2); else if (turn == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
     }
-#endif
-#if defined(F110_BM_TIMELINE)
-    if (tid < BM_TL) s_tl[tid] = 0;
-    bm_barrier();
-#endif
-    BM_STAMP(0);
     const int img_next = AHEAD ? bm_image_of(blockIdx.x, it + 1, gridDim.x, a.n) : a.n, img_next2 = AHEAD ? bm_image_of(blockIdx.x, it + 2, gridDim.x, a.n) : a.n;
     if (!AHEAD)
-        for (int k = tid; k < ((F110_BM_X & 4) ? 0 : T); k += BM_THREADS) pts[k] = bm_point(a, img, k, cx, cy);
+        for (int k = tid; k < T; k += BM_THREADS) pts[k] = bm_point(a, img, k, cx, cy);
     // zero both planes (contiguous, each on a 16-byte boundary: 16 bytes per store)
     {
         uint4 *z4 = reinterpret_cast<uint4 *>(parp);
@@ -496,7 +462,6 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
     }
     if (tid < 2) s_nq[tid] = 0;
     bm_barrier();
-    BM_STAMP(1); // planes zeroed (the points were made before the previous image's stores)
     if (a.draw_center && mode != BM_FILL && tid < 25) {
         // lidar.py:98-100: centre marker in the draw colour (FILL clears it after the fill, below)
         const int x = cx - 2 + tid % 5, y = cy - 2 + tid / 5;
@@ -509,7 +474,7 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
     // BM_DIRECT items is drawn here and now, from registers: Bresenham pixels by LineIterator's recurrence, crossings by
     // the 16.16 increment (32 bits suffice: x stays between the two end points).  Everything else -- long edges, edges that
     // need clipLine's 64-bit arithmetic, every ray -- is queued for the record path below, where threads share items, not segments.
-    for (int i0 = 0; i0 < ((F110_BM_X & 1) ? 0 : T); i0 += BM_THREADS) {
+    for (int i0 = 0; i0 < T; i0 += BM_THREADS) {
         const int i = i0 + tid;
         const bool valid = i < T;
         int2 p0 = make_int2(0, 0), p1 = p0;
@@ -565,12 +530,11 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
     }
     bm_barrier();
 
-    BM_STAMP(2); // direct pass done
     // ---- the ranges of the image after the next, into the buffer the previous image's were read from, issued by the
     // upper waves, which have nothing to do while the first waves set the records up; then wait for the loads issued
     // an image ago (everything but the ones just issued)
     if (AHEAD && tid >= BM_THREADS / 2) {
-        const int issued = (img_next2 < a.n && !(F110_BM_X & 4)) ? bm_prefetch(a, img_next2, beams, stage + (it & 1) * stage_words, tid) : 0;
+        const int issued = img_next2 < a.n ? bm_prefetch(a, img_next2, beams, stage + (it & 1) * stage_words, tid) : 0;
         bm_wait_vm(issued);
     }
     // ---- record path: rounds of at most qcap queued segments -- records, prefix of their item counts, item walk
@@ -605,7 +569,6 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
                 if (tid == 63) start[nr] = incl;
             }
             bm_barrier();
-            BM_STAMP(3); // records + prefix
             total = start[nr];
         } else {
             // (separate loops, so that a wave runs the long form only if it holds such a segment)
@@ -621,7 +584,6 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
                 }
             }
             bm_barrier();
-            BM_STAMP(3); // records
             // thread t owns records t*per .. t*per + per - 1
             const int per = (nr + BM_THREADS - 1) / BM_THREADS;
             int cnt[BM_PER_MAX], local = 0;
@@ -641,7 +603,6 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
             bm_barrier();
         }
 
-        BM_STAMP(4); // prefix
         // walk the items: every thread takes a contiguous share of all records' pixels / crossings / marker pixels
         // (at least BM_MIN_SHARE of them: finding its place costs a thread more than a few items do)
         {
@@ -700,7 +661,6 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
         bm_barrier();
     }
 
-    BM_STAMP(5); // walk
     const int ch = a.channels;
     const size_t img_bytes = (size_t)rows * cols * ch;
     unsigned char *dst = a.out + (size_t)img * img_bytes;
@@ -708,7 +668,7 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
     const bool use_tab = ch == 1 && (cols & 15) == 0; // (the layout reserves the table's 2 KB)
     uint2 *tab = reinterpret_cast<uint2 *>(recs); // (the records are dead from here on)
     if (use_tab && tid < 256) tab[tid] = make_uint2(bm_expand4((unsigned)tid & 15u, cols2), bm_expand4((unsigned)tid >> 4, cols2));
-    if (mode == BM_FILL && !(F110_BM_X & 2)) {
+    if (mode == BM_FILL) {
         // ---- inside = crossing on the pixel, or an odd number of crossings strictly left of it; then the centre marker
         // (a row per thread; with rows for half of the threads only, two threads per row: the second takes the words from
         // S0 on, its carry = the row's carry bit ^ the parity of the crossings in the words before)
@@ -741,17 +701,15 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
     }
     bm_barrier();
 
-    BM_STAMP(6); // parity
     // ---- the next image's points (this image's are dead since the last record round; no store of this image is in
     // flight yet, so waiting for the ranges waits for nothing else)
     if (AHEAD && img_next < a.n) {
 #pragma unroll
         for (int q = 0; q < BM_PER_MAX; q++) {
             const int k = tid + q * BM_THREADS;
-            if (k < T && !(F110_BM_X & 4)) { const double2 c = cs[k]; pts[k] = bm_point_at(a.scale, bm_staged_range(a, stage + ((it + 1) & 1) * stage_words, k), c.x, c.y, cx, cy); }
+            if (k < T) { const double2 c = cs[k]; pts[k] = bm_point_at(a.scale, bm_staged_range(a, stage + ((it + 1) & 1) * stage_words, k), c.x, c.y, cx, cy); }
         }
     }
-    BM_STAMP(8); // next points
     // ---- stream the image out: grey levels and channels are expanded here (the only HBM write)
     // One channel: 8 pixel bits -> 8 grey bytes through a 256-entry table (2 KB, in the segment records' place: they are
     // dead after the walk), built by the first 256 threads.  Two ds_read_b64 per 16-byte store replace the twelve VALU
@@ -831,11 +789,6 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
             dst[o] = c == 3 ? (unsigned char)255 : (unsigned char)(bit ? a.draw : a.bg);
         }
     }
-#if defined(F110_BM_TIMELINE)
-    bm_barrier();
-    BM_STAMP(7); // stores issued
-    if (tid == 0 && a.tl) for (int i = 0; i < BM_TL; i++) a.tl[(size_t)img * BM_TL + i] = s_tl[i];
-#endif
     if (!AHEAD) break;
     bm_barrier(); // the planes, the records' place (grey-level table) and the points are the next image's from here
     img = img_next; it++;

@@ -290,59 +290,13 @@ extern "C" int f110_bitmap_render(f110_bitmap *b, const void *scans, int32_t sca
     a.idx = b->d_idx; a.cosv = b->d_cos; a.sinv = b->d_sin; a.T = b->cfg.target_beam_count;
     a.rows = b->cfg.rows; a.cols = b->cfg.cols; a.channels = b->cfg.channels; a.mode = b->cfg.draw_mode;
     a.bg = b->cfg.bg_value; a.draw = b->cfg.draw_value; a.draw_center = b->cfg.draw_center;
-    a.scale = b->cfg.scaling_factor; a.out = out; a.S = b->S; a.qcap = bm_queue_cap(a.T, a.mode); a.tl = nullptr;
-#if defined(F110_BM_TIMELINE)
-    // diagnostics build only: every launch is followed by a synchronisation and a table of the stage times on stderr
-    static unsigned long long *tl = nullptr; static size_t tl_n = 0;
-    if (tl_n < (size_t)n) { if (tl) (void)hipFree(tl); HIP_TRY(hipMalloc((void **)&tl, (size_t)n * BM_TL * 8)); tl_n = (size_t)n; }
-    a.tl = tl;
-#endif
-    const char *grid_env = getenv("F110_BM_GRID"); // sweeps and tests only: workgroups of the launch (read per call)
+    a.scale = b->cfg.scaling_factor; a.out = out; a.S = b->S; a.qcap = bm_queue_cap(a.T, a.mode);
+    const char *grid_env = getenv("F110_BM_GRID"); // test hook (test_gpu_bitmap.py): workgroups of the launch (read per call)
     // fetch-ahead shape: as many workgroups as the device runs at once, each looping over images; else one per image
     const int64_t grid = !bm_fetch_ahead(a.mode, a.channels) ? n : std::min<int64_t>(n, grid_env && atoi(grid_env) > 0 ? atoi(grid_env) : b->resident[a.is_f64]);
     void *params[1] = {(void *)&a};
     HIP_TRY(hipLaunchKernel(bitmap_fn(b->lds[a.is_f64], a.mode, a.channels), dim3((unsigned)grid), dim3(BM_THREADS), params, b->lds[a.is_f64], (hipStream_t)stream));
     HIP_TRY(hipGetLastError());
-#if defined(F110_BM_TIMELINE)
-    {
-        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-        std::vector<unsigned long long> h((size_t)n * BM_TL);
-        HIP_TRY(hipMemcpy(h.data(), tl, h.size() * 8, hipMemcpyDeviceToHost));
-        static const char *names[] = {"zero", "direct pass", "records", "prefix", "walk", "parity", "next points", "store issue"};
-        double sum[8] = {0}; unsigned long long t0 = ~0ull, t1 = 0;
-        for (int64_t i = 0; i < n; i++) {
-            const unsigned long long *s = &h[(size_t)i * BM_TL];
-            unsigned long long prev = s[0];
-            static const int order[8] = {1, 2, 3, 4, 5, 6, 8, 7};
-            for (int j = 0; j < 8; j++) { const int k = order[j]; if (s[k]) { sum[j] += (double)(s[k] - prev); prev = s[k]; } }
-            t0 = std::min(t0, s[0]); t1 = std::max(t1, s[7]);
-        }
-        fprintf(stderr, "bitmap timeline (%lld images, 100 MHz ticks -> us): launch %.1f us;", (long long)n, (t1 - t0) / 100.0);
-        for (int j = 0; j < 8; j++) fprintf(stderr, " %s %.2f", names[j], sum[j] / n / 100.0);
-        // between a workgroup's images (last stamp of one -> first stamp of the next) and a workgroup's life (first stamp of
-        // its first image -> last stamp of its last one); workgroup g draws bm_image_of(g, round, grid, n)
-        double gap = 0, life = 0, life_min = 1e30, life_max = 0, first = 0, first_max = 0; long long gaps = 0;
-        const bool ahead = bm_fetch_ahead(a.mode, a.channels);
-        for (int64_t g = 0; g < grid; g++) {
-            int64_t prev = g, last = g;
-            for (int it = 1; ahead; it++) {
-                const int64_t i = bm_image_of((int)g, it, (int)grid, (int)n);
-                if (i >= n) break;
-                gap += (double)(h[(size_t)i * BM_TL] - h[(size_t)prev * BM_TL + 7]); gaps++;
-                prev = last = i;
-            }
-            const double l = (double)(h[(size_t)last * BM_TL + 7] - h[(size_t)g * BM_TL]), f = (double)(h[(size_t)g * BM_TL] - t0);
-            life += l; life_min = std::min(life_min, l); life_max = std::max(life_max, l); first += f; first_max = std::max(first_max, f);
-        }
-        if (gaps) fprintf(stderr, " | between images %.2f (grid %lld)", gap / gaps / 100.0, (long long)grid);
-        if (const char *dump = getenv("F110_BM_TL_DUMP")) { // raw stamps for offline analysis
-            if (FILE *f = fopen(dump, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-        }
-        const double gn = (double)grid;
-        fprintf(stderr, " | workgroup life mean %.1f min %.1f max %.1f, first stamp after launch start mean %.1f max %.1f", life / gn / 100.0, life_min / 100.0, life_max / 100.0, first / gn / 100.0, first_max / 100.0);
-        fprintf(stderr, "\n");
-    }
-#endif
     return F110_OK;
 }
 

@@ -22,7 +22,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <string>
 #include <utility>
 #include <vector>
 
@@ -63,6 +62,9 @@ struct DeviceScope {
     HIP_TRY(dev_scope_.err)
 
 
+// one stage of a scan launch's wave -> car mapping: `cars` cars (< 0: "*", the remaining cars) at 2^lg waves each
+struct StageSpec { int cars, lg; };
+
 struct f110_handle {
     f110_config cfg;
     // Vehicle parameters, [slots][1 + A]: per params slot (the `params` one reference env was constructed with) entry 0 =
@@ -79,7 +81,7 @@ struct f110_handle {
     // Bumped whenever a later f110_step would enqueue different kernels or by-value arguments than an earlier one
     // (a table re-allocated, another scan instantiation selected, buffers re-bound): f110_launch_epoch.
     int64_t epoch = 0;
-    std::string stages;               // f110_set_scan_stages override ("" = F110_STAGES or the built-in choice)
+    std::vector<StageSpec> stages;    // f110_set_scan_stages override, parsed (empty: the built-in choice, scan_stage_list)
     f110_buffers bufs;
     // device tables owned by the handle
     double *d_scan_angles = nullptr, *d_beam_cosines = nullptr, *d_side = nullptr;

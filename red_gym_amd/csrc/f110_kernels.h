@@ -1,9 +1,10 @@
 // f110_kernels.h -- the kernels of one batched env step on gfx950, in launch order:
 //   dynamics_kernel   (lane per car)        RaceCar.update_pose minus the scan (+ reset)
 //   scan_kernel       (wave per car)        ScanSimulator2D.scan + noise + iTTC
-//   opp_setup_kernel  (4 lanes per car pair) \ RaceCar.ray_cast_agents, only when A > 1
-//   opp_apply_kernel  (wave per car)         /
 //   env_kernel        (lane per env)        GJK, collision flags, iTTC state update, lap timing, done, autoreset
+// and, when A > 1, in place of env_kernel:
+//   post_scan_kernel  (lane per env | 4 lanes per car pair)  env_kernel's work beside opp_setup_body \ RaceCar.ray_cast_agents
+//   opp_apply_kernel  (wave per car)                                                                  /
 // plus small function-level kernels used by the parity entry points.
 #pragma once
 #include "f110_device.h"
@@ -45,16 +46,9 @@ enum { BT_LUT_CODE, BT_CELLS_FAR, BT_LUT_RANK, BT_DT, BT_NOISE_BEAM, BT_CS_TABLE
 #define F110_BCHK(ok, table, errp) do { } while (0)
 #define F110_BOUNDS_ONLY(...)
 #endif
-constexpr int TL_MAX_WAVES = 8; // (diagnostics builds: per-wave stamps of a workgroup)
-#ifndef F110_SCAN_WAVES
-#define F110_SCAN_WAVES 2
-#endif
-#ifndef F110_REFILL_MIN_IDLE
-#define F110_REFILL_MIN_IDLE 44
-#endif
-constexpr int SCAN_WAVES = F110_SCAN_WAVES;   // cars per workgroup (one wavefront each)
+constexpr int SCAN_WAVES = 2;   // cars per workgroup, one wavefront each (one-car workgroups: profiles/r05_one_wave_groups.txt)
 constexpr int SCAN_THREADS = SCAN_WAVES * WAVE;
-constexpr int REFILL_MIN_IDLE = F110_REFILL_MIN_IDLE; // refill the wave's beam slots once this many lanes idle
+constexpr int REFILL_MIN_IDLE = 44; // refill the wave's beam slots once this many lanes idle (32 .. 56 swept: profiles/r05_scan_budget.txt)
 
 // Cell table.  Each map cell stores, as a u16, the BYTE OFFSET of its distance inside the LDS copy of the LUT:
 // 8 * (k + 1), k = RANK of the cell's exact squared distance d2 (in cells, to the nearest obstacle) among the distinct d2
@@ -74,10 +68,7 @@ constexpr int REFILL_MIN_IDLE = F110_REFILL_MIN_IDLE; // refill the wave's beam 
 // (Round 5 tried to have the address unit form an equivalent layout -- a swizzled structured descriptor, index = row, offset =
 // 2 * column, the descriptor's range check as the row clamp: two VALU instructions instead of six -- and it is exact and 26 %
 // slower: an `idxen` load merges at most two lanes per access, profiles/r05_swizzle_probe.txt.)
-#ifndef F110_LUT_LDS
-#define F110_LUT_LDS 1024
-#endif
-constexpr int LUT_LDS = F110_LUT_LDS;                   // LDS LUT slots
+constexpr int LUT_LDS = 1024;                           // LDS LUT slots
 constexpr unsigned SLOT_OOB = 0, SLOT_FAR = LUT_LDS - 1; // slot 0: dt[-1,-1]; slots 1 .. LUT_LDS-2: ranks 0 .. LDS_RANKS-1; last: far marker
 constexpr unsigned LDS_RANKS = LUT_LDS - 2;
 constexpr unsigned OFF_FAR = 8 * SLOT_FAR;
@@ -362,20 +353,10 @@ __device__ inline void march_ident_pow2_fast(const MapView &m, double &x, double
         "s_add_u32 %[nl], %[nl], %[na]\n\t"
         "v_fma_f64 v[60:61], %[rinv], %[x], %[nox]\n\t"
         "v_fma_f64 v[62:63], %[rinv], %[y], %[noy]\n\t"
-#if defined(F110_X_NOMAGIC) // timing experiment
-        "v_floor_f64 v[60:61], v[60:61]\n\t"
-        "v_floor_f64 v[62:63], v[62:63]\n\t"
-        "v_cvt_i32_f64 v60, v[60:61]\n\t"
-        "v_cvt_i32_f64 v62, v[62:63]\n\t"
-#else
         "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 2\n\t"      // f64 rounding: toward -inf
         "v_add_f64 v[60:61], v[60:61], %[magic]\n\t"
         "v_add_f64 v[62:63], v[62:63], %[magic]\n\t"
         "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 0\n\t"      // back to nearest-even
-#endif
-#if defined(F110_X_PAD)
-        "v_mov_b32 v61, v61\n\tv_mov_b32 v61, v61\n\tv_mov_b32 v61, v61\n\t"
-#endif
         "v_med3_i32 v62, v62, -1, %[H]\n\t"
         "v_ashrrev_i32 v61, 3, v60\n\t"
         "v_lshl_add_u32 v62, v62, 4, %[rb]\n\t"
@@ -496,10 +477,10 @@ struct ScanArgs {
     int car_base;           // first car (a shard whose env blocks sit on maps of different kinds -- resolution a power
                             // of two or not, origin rotated or not -- is scanned block by block, each with its own instantiation)
     int agents;             // A (cars of one env are consecutive)
-    int wpc;                // wavefronts per car (power of two): small batches split a car's beams over
-                            // several waves so that the chip is still filled; chunk position p goes to wave p % wpc
+    int wpc;                // unused (the waves per car come from the stage list below); kept so that the fields behind
+                            // it keep their offsets in the argument block
     // Wave -> (car, part) mapping: consecutive STAGES of cars, stage s giving each of its stage_cars[s] cars
-    // 2^stage_log2w[s] waves (launch_scan explains the choice).  Read through `rare`, not held in registers.
+    // 2^stage_log2w[s] waves (scan_stage_list explains the choice).  Read through `rare`, not held in registers.
     int n_stages;
     int stage_cars[8];          // SCAN_MAX_STAGES
     int stage_log2w[8];         // each 0..SCAN_MAX_LOG2W
@@ -541,8 +522,6 @@ struct ScanArgs {
     float *out_f32;              // [N,nb] or NULL
     double *out_f64;             // [N,nb] or NULL
     uint32_t *lookups;           // [N] or NULL (accumulated)
-    unsigned long long *timeline; // diagnostics (builds with -DF110_TIMELINE only, tools/timeline.py): per wave
-                                  // {start, rays started, end} in 100 MHz ticks and (car << 8 | part); else NULL
 };
 
 // One wavefront per car.  Lanes own rays; a finished ray idles (its lookups return 0.0) until at least REFILL_MIN_IDLE lanes are idle, then every idle
@@ -564,11 +543,9 @@ static_assert(sizeof(ScanArgs) <= 4096, "kernarg segment size");
 
 // SM 0: ScanSimulator2D.scan(pose, None); 1: the scan of a step (noise, iTTC flag; env_kernel follows); 2: the same with
 // ordinary instead of streaming stores for the fp32 scan (launches of more than ~300 000 cars, see emit).
+constexpr int SCAN_MIN_WAVES = 8; // waves per SIMD: the kernel is held to their 80-SGPR budget (see the wave -> car mapping)
 template <bool IDENT, bool POW2, int SM>
-#ifndef F110_SCAN_MIN_WAVES
-#define F110_SCAN_MIN_WAVES 8
-#endif
-__global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel(ScanArgs a)
+__global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(ScanArgs a)
 {
     constexpr bool STEP = SM >= 1;
     // ONE LDS object, the LUT first: march_ident_pow2 addresses the LUT by the cell codes alone, i.e. the LUT sits at LDS
@@ -582,9 +559,6 @@ __global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel
     const ScanArgs *rare = (const ScanArgs *)__builtin_amdgcn_kernarg_segment_ptr();
 #else
     const ScanArgs *rare = &a; // host pass of the single-source compile: never executed
-#endif
-#if defined(F110_TIMELINE)
-    __shared__ volatile unsigned long long s_tl[TL_MAX_WAVES][2]; // stamps wait in LDS, not in registers, for the end of the wave
 #endif
     const int nb = a.scan.nb;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -626,9 +600,6 @@ __global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel
     }
     static_assert(MAX_CHUNKS <= WAVE, "one pass of one wave stages the chunk table");
     if ((int)threadIdx.x < ((nb + 63) >> 6)) s_chunk0[threadIdx.x] = a.chunk_beam0[threadIdx.x];
-#if defined(F110_TIMELINE)
-    { unsigned long long t = wall_clock64(); asm volatile("" : "+v"(t)); if (lane == 0) s_tl[wave][0] = t; }
-#endif
     __syncthreads();
     MapView mv;
     mv.init(md);
@@ -715,13 +686,6 @@ __global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel
     // The first table read of every beam is at the car itself (:129): done once.
     double d0 = dist_lookup<IDENT, POW2>(mv, s_lut, px, py);
     if (__builtin_expect(is_far_marker(d0), 0)) d0 = dist_lookup_far<IDENT, POW2>(mv, px, py); // (wave-uniform: every lane reads the car's own cell)
-#if defined(F110_TIMELINE)
-    { unsigned long long t = wall_clock64(); asm volatile("" : "+v"(t)); if (lane == 0) s_tl[wave][1] = t; }
-#endif
-#if defined(F110_TIMELINE)
-    unsigned tl_wit = 0, tl_wit_dry = 0; // march iterations of the wave so far / when its queue ran dry
-    unsigned tl_refills = 0, tl_phases = 0; // refill phases in which beams were taken / passes of the outer loop
-#endif
     unsigned nlook = (unsigned)nbl; // the reference reads the table once per beam before marching
     if (!(d0 > eps && d0 <= max_range)) {
         for (int k = lane; k < nbl; k += WAVE) {
@@ -743,9 +707,6 @@ __global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel
         const unsigned long long T0 = t0_ok ? (unsigned long long)(t0w * 1099511627776.0) : 0ull;
         const unsigned guard2 = t0_ok ? 859u : 0xffffffffu;
 
-#if defined(F110_TIMELINE)
-        bool tl_dry = false;
-#endif
         // (wave-uniform) may this car's rays take the fast march?  Every look-up lies within max_range of the car.
         bool fast = false;
         if (IDENT) {
@@ -778,10 +739,6 @@ __global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel
             // ---- refill phase: idle lanes finish their beam and take the next one ----
             const unsigned long long idle = vote(!active);
             const int nidle = __popcll(idle);
-#if defined(F110_TIMELINE)
-            tl_phases++;
-            if (next < nbl) tl_refills++;
-#endif
             if (!active) {
                 // all independent loads first (one memory round trip).  The noise entry is fetched
                 // for the beam being TAKEN and carried in registers until the beam is finished: idle lanes take
@@ -798,11 +755,7 @@ __global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel
                 F110_BCHK((unsigned)b < (unsigned)nb, BT_NOISE_BEAM, rare->dev_err);
                 if ((unsigned)b >= (unsigned)nb) b = 0;
 #endif
-#if defined(F110_X_NONOISE) // timing experiment: the upper bound of what the noise gather costs (results invalid)
-                const double nsv = 0.0;
-#else
                 const double nsv = STEP ? *reinterpret_cast<const double *>(reinterpret_cast<const char *>(ns) + (size_t)((unsigned)b * 8u)) : 0.0;
-#endif
                 const double nzv = nz;
                 int ti = beam_theta_index(T0, t0w, b, a.scan, guard2);
 #if defined(F110_BOUNDS)
@@ -829,13 +782,7 @@ __global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel
             // ---- march phase: the rays that are still marching step, under their own EXEC mask (a finished ray issues no
             // look-up and keeps its total), until enough lanes are idle again or, once no beams are left, the wave has drained ----
             const int go = next < nbl ? WAVE - REFILL_MIN_IDLE : 0; // keep marching while nact > go
-#if defined(F110_DRAIN_PRIO)
-            if (go == 0) __builtin_amdgcn_s_setprio(F110_DRAIN_PRIO); // experiment: a draining wave ends on its longest ray's dependent chain
-#endif
-#if defined(F110_TIMELINE)
-            if (go == 0 && !tl_dry) { unsigned long long t = wall_clock64(); asm volatile("" : "+v"(t)); if (lane == 0) s_tl[wave][1] = t; tl_dry = true; tl_wit_dry = tl_wit; }
-#endif
-#if !defined(F110_TIMELINE) && !defined(F110_BOUNDS)
+#if !defined(F110_BOUNDS)
             if (IDENT && POW2) {
                 unsigned long long am = vote(active);
                 if (fast) march_ident_pow2_fast(mv, x, y, total, d, c, s, eps, max_range, am, go, nlook, nact);
@@ -866,9 +813,6 @@ __global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel
             }
 #endif
             do {
-#if defined(F110_TIMELINE)
-                tl_wit++;
-#endif
                 nlook += (unsigned)nact;
                 if (active) {
                     d = dist_lookup<IDENT, POW2>(mv, s_lut, x, y);
@@ -884,18 +828,6 @@ __global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel
     const ScanArgs *ra = rare;
     asm volatile("" : "+s"(ra));
     if (ra->lookups && lane == 0) atomicAdd(&ra->lookups[car], nlook);
-#if defined(F110_TIMELINE)
-    unsigned long long tl_end = wall_clock64();
-    asm volatile("" : "+v"(tl_end));
-    if (ra->timeline && lane == 0) {
-        unsigned long long *tl = ra->timeline + (size_t)wid * 4;
-        // {start, queue ran dry (or first rays), end}; car << 8 | part | wpc << 40 | iterations after the queue ran dry << 44
-        // (time stamps are 100 MHz ticks: their top 16 bits are free; they carry the wave's march iterations and its refills)
-        tl[0] = s_tl[wave][0] | ((unsigned long long)min(tl_wit, 0xffffu) << 48); tl[1] = s_tl[wave][1] | ((unsigned long long)min(tl_phases, 0xffffu) << 48);
-        tl[2] = tl_end | ((unsigned long long)min(tl_refills, 0xffffu) << 48);
-        tl[3] = ((unsigned long long)car << 8) | (unsigned)part | ((unsigned long long)wpc << 40) | ((unsigned long long)min(tl_wit - tl_wit_dry, 0xfffffu) << 44);
-    }
-#endif
 
     // ---- iTTC result: the flag only; env_kernel zeroes the state (base_classes.py:241-250)
     // once every wave of the car is done.  Plain store: all writers store the same 1.
@@ -907,11 +839,11 @@ __global__ __launch_bounds__(SCAN_THREADS, F110_SCAN_MIN_WAVES) void scan_kernel
 // ------------------------------------------------------------------ opponents (A > 1)
 // RaceCar.ray_cast_agents (base_classes.py:204-225) -> ray_cast (laser_models.py:319-346): the car's CURRENT pose (yaw
 // already zeroed by an iTTC hit, :245) against the other cars' post-integration snapshot poses.
-// Two kernels behind the scan:
-//   opp_setup_kernel, FOUR LANES PER (car, opponent) PAIR (lane c = corner c = edge c of the opponent's quad): every lane
-//     takes one corner through the arctan2 / arg-min of get_blocked_view_indices (:283-315) and one edge through what
-//     get_range (:250-280) computes from the pose and two corners alone; span, angular hull and the beam intervals worth
-//     visiting come from quad-wide min / max;
+// Two stages behind the scan:
+//   opp_setup_body (in post_scan_kernel, beside the env bookkeeping), FOUR LANES PER (car, opponent) PAIR (lane c = corner
+//     c = edge c of the opponent's quad): every lane takes one corner through the arctan2 / arg-min of
+//     get_blocked_view_indices (:283-315) and one edge through what get_range (:250-280) computes from the pose and two
+//     corners alone; span, angular hull and the beam intervals worth visiting come from quad-wide min / max;
 //   opp_apply_kernel, a group of OPP_GROUP lanes per car (a whole wave as built): the pair is staged in LDS by vector loads
 //     (no chain of dependent scalar loads at the head of the wave) and the lanes share the beams of the intervals.  Per
 //     beam the front-facing edges are tested with get_range's own conditions (:271-274), decided without dividing; the
@@ -982,7 +914,7 @@ struct OppPairRegs {
     int n_front, pad;
 };
 constexpr int OPP_MAX_IV = 3;
-// what opp_setup_kernel leaves for opp_apply_kernel
+// what opp_setup_body leaves for opp_apply_kernel
 struct OppPair {
     OppPairRegs r;
     // Disjoint, ascending beam intervals [iv[2k], iv[2k+1]] inside the reference's span [lo, hi] that hold every beam
@@ -1191,14 +1123,7 @@ __device__ inline void opp_setup_body(const OppArgs &a, int t)
     out.n_iv = n_iv; out.total = total;
 }
 
-#if defined(F110_UNIT_STEP)
-static __global__ __launch_bounds__(128) void opp_setup_kernel(OppArgs a) { opp_setup_body(a, blockIdx.x * blockDim.x + threadIdx.x); }
-#endif
-
-#ifndef F110_OPP_GROUP
-#define F110_OPP_GROUP 64
-#endif
-constexpr int OPP_GROUP = F110_OPP_GROUP; // lanes per car in opp_apply_kernel (measured at 32 768 cars: 8 lanes 52 us, 16: 33, 32: 27, 64: 23)
+constexpr int OPP_GROUP = 64; // lanes per car in opp_apply_kernel (measured at 32 768 cars: 8 lanes 52 us, 16: 33, 32: 27, 64: 23)
 constexpr int OPP_GROUP_MAX = 256; // a pair with more beams than this is walked by the whole wave, not by its group
 
 #if defined(F110_UNIT_STEP)

@@ -58,51 +58,25 @@ static int launch_scan_t(MapKind kind, const ScanArgs &a, const Sink &k, hipEven
     int waves = 0;
     for (int i = 0; i < a.n_stages; i++) waves += a.stage_cars[i] << a.stage_log2w[i];
     const dim3 grid(a.wg_single ? waves : (waves + SCAN_WAVES - 1) / SCAN_WAVES), block(a.wg_single ? WAVE : SCAN_THREADS);
-    // sweeps only: F110_SCAN_PAD_LDS=<bytes> of unused dynamic LDS per workgroup caps the workgroups per CU (160 KiB / (8.6 KiB + pad)),
-    // i.e. emulates a lower occupancy without touching the kernel
-    static const unsigned pad_lds = getenv("F110_SCAN_PAD_LDS") ? (unsigned)atoi(getenv("F110_SCAN_PAD_LDS")) : 0u;
     const void *f = kind.ident && kind.pow2 ? (const void *)&scan_kernel<true, true, SM>
                   : kind.ident              ? (const void *)&scan_kernel<true, false, SM>
                   : kind.pow2               ? (const void *)&scan_kernel<false, true, SM>
                                         : (const void *)&scan_kernel<false, false, SM>;
-    return emit(k, f, grid, block, pad_lds, a, ev0, ev1);
+    return emit(k, f, grid, block, 0, a, ev0, ev1);
 }
 
 // Waves per car.  Measured on MI355X (profiles/r01g, r01i): a wave's lifetime is bounded
 // below by its longest ray (~50 us), so splitting a car's beams over several waves only
 // pays while the chip is nearly empty: scan time at 256 / 1024 cars 76 -> 49 us and
 // 87 -> 65 us with 8 waves per car, but 121 -> 143 us at 4096 cars (prologues and the
-// shorter queues' tails eat the extra parallelism).  F110_WPC overrides the choice.
+// shorter queues' tails eat the extra parallelism).
 static int waves_per_car(int n_cars, int num_beams)
 {
-    static const char *env = getenv("F110_WPC");
-    int wpc = env ? atoi(env) : (n_cars <= 1024 ? 8 : (n_cars <= 2048 ? 4 : 1));
-    if (wpc != 2 && wpc != 4 && wpc != 8) wpc = 1;
+    int wpc = n_cars <= 1024 ? 8 : (n_cars <= 2048 ? 4 : 1);
     const int nch = (num_beams + 63) / 64;
     while (wpc > 1 && wpc > nch) wpc /= 2;
     return wpc;
 }
-
-#if defined(F110_TIMELINE)
-// diagnostics build only (tools/timeline.py): per-wave time stamps of the last scan / car-group launch
-static unsigned long long *g_timeline = nullptr;
-static const size_t TIMELINE_WAVES = (size_t)1 << 20;
-static unsigned long long *timeline_buffer()
-{
-    if (!g_timeline && hipMalloc((void **)&g_timeline, TIMELINE_WAVES * 4 * sizeof(unsigned long long)) != hipSuccess) g_timeline = nullptr;
-    if (g_timeline) (void)hipMemset(g_timeline, 0, TIMELINE_WAVES * 4 * sizeof(unsigned long long));
-    return g_timeline;
-}
-extern "C" int f110_debug_timeline(unsigned long long *out_host, int64_t n_waves)
-{
-    if (!g_timeline || !out_host || n_waves < 0 || (size_t)n_waves > TIMELINE_WAVES) return F110_E_INVALID;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out_host, g_timeline, (size_t)n_waves * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return F110_OK;
-}
-#endif
-
-struct StageSpec { int cars, lg; }; // cars < 0: "*", the remaining cars
 
 // "cars:log2waves,..." with at most one "*": strict syntax (f110_set_scan_stages refuses what this refuses)
 static bool parse_stage_spec(const char *p, std::vector<StageSpec> &spec, const char **why)
@@ -148,6 +122,47 @@ static int check_scan_args(const ScanArgs &a, const char *who)
     return F110_OK;
 }
 
+// The wave -> car mapping of a scan launch of n_cars cars: a list of stages (cars, log2 waves per car), from the
+// f110_set_scan_stages override or, without one, the built-in choice.
+// Drain of a launch: workgroups are dispatched in index order and nothing follows the last ones,
+// so the chip empties over one wave lifetime (about half of it lost: ~5 % at 65 536 cars -- the gap
+// that two half-size launches from two processes close by overlapping).  The last cars therefore
+// run as 4 short waves each ("*:0,2048:2" for big launches of one agent per env).
+// Measured (profiles/r01j): 65 536 cars 0.702 -> 0.672 ms for any tail of 1 000 .. 2 048 cars (it has to
+// cover the last of the slowest cars), 32 768: 0.380 -> 0.368, 16 384: 0.225 -> 0.218, 8 192: neutral,
+// 4 096: 0.126 -> 0.105 with half of the cars split; graded tails (halves, quarters, eighths) and graded
+// heads changed nothing.
+// (Measured and dropped in round 2, profiles/r02_multicar_waves_sweep.txt: stages that give one wave K = 2, 4, 8
+// consecutive cars to march back to back, so that a wave drains once per K cars -- 0.705 ms at best against
+// 0.664 ms: the leaner refill of one car per wave and the finer-grained launch win.)
+static std::vector<StageSpec> scan_stage_list(const std::vector<StageSpec> &override_spec, int n_cars, int agents, int num_beams)
+{
+    std::vector<StageSpec> spec = override_spec;
+    if (spec.empty()) {
+        const int wpc = waves_per_car(n_cars, num_beams), nch = (num_beams + 63) / 64;
+        // split cars (a small launch) or a short scan (fewer than 8 chunks of 64 beams): one stage
+        if (wpc > 1 || nch < 8) return {{n_cars, wpc >= 8 ? 3 : wpc >= 4 ? 2 : wpc >= 2 ? 1 : 0}};
+        // (envs of several agents: 4 096 -- 16 384 x 2: scan 0.396 -> 0.388 ms, 32 768 x 2: 0.697 -> 0.672; 8 192 x 4: flat;
+        // one agent: 4 096 is 1 % worse than 2 048 at 65 536 cars and 2.5 % worse at 32 768; profiles/r04_scan_stores.txt N)
+        const int tail = std::min(agents >= 2 ? 4096 : 2048, n_cars / 2);
+        spec = {{-1, 0}, {tail, 2}};
+    }
+    int fixed = 0;
+    for (StageSpec &x : spec) if (x.cars >= 0) { x.cars -= x.cars % SCAN_WAVES; fixed += x.cars; }
+    // a list written for the step's car count may not fit a function-level scan of fewer poses: whole cars then
+    if (fixed > n_cars) { spec = {{-1, 0}}; fixed = 0; }
+    bool star = false;
+    for (StageSpec &x : spec) if (x.cars < 0 && !star) { x.cars = n_cars - fixed; star = true; }
+    if (!star) spec.push_back({n_cars - fixed, 0});
+    std::vector<StageSpec> stv;
+    for (const StageSpec &x : spec) if (x.cars > 0) stv.push_back(x);
+    // a workgroup never mixes two stages: every stage's wave count is a multiple of SCAN_WAVES
+    for (size_t i = 0; i + 1 < stv.size(); i++)
+        if ((stv[i].cars << stv[i].lg) % SCAN_WAVES) return {{n_cars, 0}};
+    if (stv.size() > (size_t)SCAN_MAX_STAGES) return {{n_cars, 0}};
+    return stv;
+}
+
 static int launch_scan(f110_handle *h, const ScanArgs &a_in, const Sink &st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
                        const MapKind *kind_or_null = nullptr)
 {
@@ -155,68 +170,23 @@ static int launch_scan(f110_handle *h, const ScanArgs &a_in, const Sink &st, hip
     int rc_args = check_scan_args(a_in, "scan launch");
     if (rc_args) return rc_args;
     ScanArgs a = a_in;
-    a.wpc = waves_per_car(a.n_cars, a.scan.nb);
-    // Drain of a launch: workgroups are dispatched in index order and nothing follows the last ones,
-    // so the chip empties over one wave lifetime (about half of it lost: ~5 % at 65 536 cars -- the gap
-    // that two half-size launches from two processes close by overlapping).  The last cars therefore
-    // run as 4 short waves each: the wave -> car mapping is a list of stages (cars, log2 waves per car).
-    // Measured (profiles/r01j): 65 536 cars 0.702 -> 0.672 ms for any tail of 1 000 .. 2 048 cars (it has to
-    // cover the last of the slowest cars), 32 768: 0.380 -> 0.368, 16 384: 0.225 -> 0.218, 8 192: neutral,
-    // 4 096: 0.126 -> 0.105 with half of the cars split; graded tails (halves, quarters, eighths) and graded
-    // heads changed nothing.  F110_STAGES="cars:log2waves,..." with one "*" for the remaining cars overrides
-    // the choice below (e.g. "*:0,2048:2" is the default for big launches).
-    // (Measured and dropped in round 2, profiles/r02_multicar_waves_sweep.txt: stages that give one wave K = 2, 4, 8
-    // consecutive cars to march back to back, so that a wave drains once per K cars -- 0.705 ms at best against
-    // 0.664 ms: the leaner refill of one car per wave and the finer-grained launch win.)
-    static const char *stages_env0 = getenv("F110_STAGES");
-    const char *stages_env = h->stages.empty() ? stages_env0 : h->stages.c_str();
-    const int nch = (a.scan.nb + 63) / 64;
-    int lg_all = a.wpc >= 8 ? 3 : a.wpc >= 4 ? 2 : a.wpc >= 2 ? 1 : 0;
-    typedef StageSpec St;
-    std::vector<St> stv;
-    if (h->stages.empty() && (lg_all > 0 || nch < 8)) stv.push_back({a.n_cars, lg_all});
-    else {
-        std::vector<St> spec;
-        const char *why = nullptr;
-        if (!stages_env || !parse_stage_spec(stages_env, spec, &why)) { // (a malformed F110_STAGES: the built-in choice)
-            // (envs of several agents: 4 096 -- 16 384 x 2: scan 0.396 -> 0.388 ms, 32 768 x 2: 0.697 -> 0.672; 8 192 x 4: flat;
-            // one agent: 4 096 is 1 % worse than 2 048 at 65 536 cars and 2.5 % worse at 32 768; profiles/r04_scan_stores.txt N)
-            const int tail = std::min(a.agents >= 2 ? 4096 : 2048, a.n_cars / 2);
-            spec = {{-1, 0}, {tail, 2}};
-        }
-        int fixed = 0;
-        for (auto &x : spec) if (x.cars >= 0) { x.cars -= x.cars % SCAN_WAVES; fixed += x.cars; }
-        // a list written for the step's car count may not fit a function-level scan of fewer poses: whole cars then
-        if (fixed > a.n_cars) { spec = {{-1, 0}}; fixed = 0; }
-        bool star = false;
-        for (auto &x : spec) if (x.cars < 0 && !star) { x.cars = a.n_cars - fixed; star = true; }
-        if (!star) spec.push_back({a.n_cars - fixed, 0});
-        for (auto &x : spec) if (x.cars > 0) stv.push_back(x);
-        // a workgroup never mixes two stages: every stage's wave count is a multiple of SCAN_WAVES
-        for (size_t i = 0; i + 1 < stv.size(); i++) {
-            const int w = stv[i].cars << stv[i].lg;
-            if (w % SCAN_WAVES) { stv.assign(1, {a.n_cars, 0}); break; }
-        }
-    }
-    if (stv.size() > (size_t)SCAN_MAX_STAGES) stv.assign(1, {a.n_cars, 0});
+    const std::vector<StageSpec> stv = scan_stage_list(h->stages, a.n_cars, a.agents, a.scan.nb);
     a.n_stages = (int)stv.size();
     // what the kernel assumes about the stage list, checked here where a mistake costs an error code instead of a
     // wave -> car mapping that runs off the argument block
     if (a.n_stages < 1 || a.n_stages > SCAN_MAX_STAGES) return fail(F110_E_INVALID, "scan launch: %d stages (1..%d)", a.n_stages, SCAN_MAX_STAGES);
     {
         long long cars = 0;
-        for (const St &x : stv) {
+        for (const StageSpec &x : stv) {
             if (x.cars < 0 || x.lg < 0 || x.lg > SCAN_MAX_LOG2W) return fail(F110_E_INVALID, "scan launch: stage (%d cars, 2^%d waves per car) out of range", x.cars, x.lg);
             cars += x.cars;
         }
         if (cars != a.n_cars) return fail(F110_E_INVALID, "scan launch: the stages cover %lld cars, the launch has %d", cars, a.n_cars);
     }
     for (int i = 0; i < 8; i++) { a.stage_cars[i] = i < a.n_stages ? stv[i].cars : 0; a.stage_log2w[i] = i < a.n_stages ? stv[i].lg : 0; }
-#if defined(F110_TIMELINE)
-    a.timeline = timeline_buffer();
-#endif
     // the step's scan with streaming stores, except in very large launches (profiles/r04_scan_stores.txt L);
-    // F110_SCAN_STORES=plain|stream overrides (A/B runs)
+    // F110_SCAN_STORES=plain|stream overrides: test_plain_store_instantiation_matches_streaming reaches scan_kernel<.., 2>,
+    // which no test size does otherwise, through it
     static const char *stores_env = getenv("F110_SCAN_STORES");
     const bool plain = stores_env ? strcmp(stores_env, "plain") == 0 : a.n_cars > 327680;
     return !a.state ? launch_scan_t<0>(kind, a, st, ev0, ev1) : plain ? launch_scan_t<2>(kind, a, st, ev0, ev1) : launch_scan_t<1>(kind, a, st, ev0, ev1);
@@ -251,8 +221,7 @@ static void sample_lookups(const f110_handle *h, bool sampled_step, ScanArgs &s)
 // The step of every env: dynamics_kernel -> scan_kernel -> env_kernel, or for A > 1 -> post_scan_kernel (env bookkeeping and
 // the opponents' set-up side by side) -> opp_apply_kernel.  (Two other
 // forms -- a scan that also closes the step of a one-agent env, and a workgroup per car with a shared beam queue -- were
-// built, held to ==, measured slower at every size and removed: tools/variants/car_group_and_closing_scan.patch,
-// profiles/r03_step_forms.txt.)
+// built, held to ==, measured slower at every size and removed: profiles/r03_step_forms.txt.)
 static int run_step(f110_handle *h, const double *actions, int reset_only, const Sink &st)
 {
     const f110_config &c = h->cfg;
@@ -500,8 +469,8 @@ extern "C" int f110_graph_info(f110_graph *g, int32_t *nodes, const char *dot_pa
 extern "C" int f110_set_scan_stages(f110_handle *h, const char *spec)
 {
     if (!h) return fail(F110_E_INVALID, "f110_set_scan_stages: null handle");
+    std::vector<StageSpec> parsed;
     if (spec && *spec) {
-        std::vector<StageSpec> parsed;
         const char *why = nullptr;
         if (!parse_stage_spec(spec, parsed, &why)) return fail(F110_E_INVALID, "f110_set_scan_stages: \"%s\": %s", spec, why);
         long long fixed = 0;
@@ -509,7 +478,7 @@ extern "C" int f110_set_scan_stages(f110_handle *h, const char *spec)
         if (fixed > (long long)h->cfg.num_envs * h->cfg.num_agents)
             return fail(F110_E_INVALID, "f110_set_scan_stages: \"%s\" names %lld cars, the handle has %d", spec, fixed, h->cfg.num_envs * h->cfg.num_agents);
     }
-    h->stages = spec ? spec : "";
+    h->stages = std::move(parsed);
     h->epoch++;
     return F110_OK;
 }
