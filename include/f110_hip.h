@@ -284,7 +284,8 @@ int f110_set_scan_stages(f110_handle *h, const char *spec);
 /* hipGraph support.  f110_step only enqueues kernels (no allocation, no synchronisation), so it can be captured
  * into a HIP graph and replayed.  A capture freezes the kernel selection and the by-value launch arguments; the
  * calls that change them -- f110_bind, f110_set_tables, every map install, f110_assign_maps / _params / _noise, a
- * re-allocation of the noise table -- bump the handle's launch epoch.  A graph captured at epoch e is valid while
+ * re-allocation of the noise table, a successful f110_pure_pursuit_prepare (it frees and re-allocates the grid that a
+ * captured f110_pure_pursuit reads) -- bump the handle's launch epoch.  A graph captured at epoch e is valid while
  * f110_launch_epoch still reports e; after that it must be re-captured (F110VecEnv.step_graph does so itself). */
 /* Launch order of the step's scan (performance only; no reference counterpart): order_dev = dev int32 [num_envs * num_agents], a
  * PERMUTATION of the car indices (the caller's responsibility: a wrong array scans some cars twice and others not at all), or NULL
@@ -335,7 +336,9 @@ int f110_profile_end(f110_handle *h, double *scan_ms_total, int32_t *launches);
  * (65 536 cars on the 783-point example raceline: see profiles/r05_planner.txt); poses outside the grid, NaN poses and
  * cells with more than 30 candidates take every segment -- the results are the same in every case (tests: `==` both
  * kernels and oracle/planner.py).  A cold path (copies the raceline to the host, synchronises); call it again when the raceline's
- * VALUES change.  Reference: examples/waypoint_follow.py:15-47 (nearest point), :183-217 (plan). */
+ * VALUES change: f110_pure_pursuit matches the grid by pointer and M alone (pass h = NULL to plan without it).  A failed call
+ * (e.g. M > 65 535, a grid beyond 16 M cells) leaves the handle without a grid.
+ * Reference: examples/waypoint_follow.py:15-47 (nearest point), :183-217 (plan). */
 int f110_pure_pursuit_prepare(f110_handle *h, const double *waypoints, int32_t M, double cell, double margin, void *stream);
 int f110_pure_pursuit(f110_handle *h, const double *waypoints, int32_t M, double lookahead, double vgain,
                       double wheelbase, double max_reacquire, const double *state, int32_t n,

@@ -38,13 +38,16 @@ static int32_t *single_track_offsets(int dev, int M)
 
 // Builds the grid of candidate lists for one raceline (dev [M,3]) in the handle: a cold path (the raceline is copied to the host,
 // ~0.1 s for the 783-point example raceline).  The caller promises to call it again when the raceline's values change; the pointer
-// and M are what f110_pure_pursuit matches.  cell: edge of a grid cell in metres (0: 0.25); margin: how far around the raceline's
-// bounding box the grid reaches (0: 3 m) -- poses beyond it are planned by the exhaustive search.
+// and M are what f110_pure_pursuit matches (red_gym_amd.Engine passes the handle only for the very tensor it prepared, unchanged,
+// and NULL otherwise).  A successful call replaces the grid's memory and moves the launch epoch; a failed one leaves no grid.
+// cell: edge of a grid cell in metres (0: 0.25); margin: how far around the raceline's bounding box the grid reaches (0: 3 m) --
+// poses beyond it are planned by the exhaustive search.
 extern "C" int f110_pure_pursuit_prepare(f110_handle *h, const double *waypoints, int32_t M, double cell, double margin, void *stream)
 {
-    if (!h || !waypoints) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: null argument");
+    if (!h) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: null argument");
     if (int rc = check_device(h, "f110_pure_pursuit_prepare")) return rc;
     h->plan_ok = false;
+    if (!waypoints) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: null argument");
     if (M < 2 || M > 65535) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: M=%d waypoints (2..65535)", M);
     if (!(cell >= 0) || !(margin >= 0) || !std::isfinite(cell) || !std::isfinite(margin)) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: bad cell / margin");
     if (cell == 0) cell = 0.25;
@@ -102,6 +105,7 @@ extern "C" int f110_pure_pursuit_prepare(f110_handle *h, const double *waypoints
     }
     ON_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize()); // an enqueued plan may still read the previous grid
+    h->epoch++; // a captured launch of the grid kernel takes the grid's pointers by value: they are freed below
     if (h->d_plan_count) { (void)hipFree(h->d_plan_count); h->d_plan_count = nullptr; }
     if (h->d_plan_cand) { (void)hipFree(h->d_plan_cand); h->d_plan_cand = nullptr; }
     HIP_TRY(hipMalloc((void **)&h->d_plan_count, cells));

@@ -159,6 +159,9 @@ class Engine(object):
         self._noise_per_env = self._noise_on and noise_source == 'per_env'
         self._noise_rows, self._noise_floor, self._noise_prefetched = 0, 0, False
         self._in_capture = False  # a stream capture is recording step(): no noise work (it was done in front of the capture)
+        # planner grid (Engine._plan_grid): the prepared raceline tensor, its version, (pointer, version, M) while the handle
+        # holds a grid for it (None: none, or its prepare failed), and the last tensor seen once (tensor, version)
+        self._plan_tensor, self._plan_version, self._plan_key, self._plan_seen = None, -1, None, None
         self.scan_reorder = True  # keep the scan's launch order sorted by noise row (Engine._reorder_scan); False: car order
         self.env_noise_assign = None
         self.noise_tables = []
@@ -551,31 +554,49 @@ class Engine(object):
     def pure_pursuit(self, waypoints, lookahead, vgain, wheelbase=0.17145 + 0.15875, max_reacquire=20.,
                      state=None, out=None, prepare=True):
         """waypoints: [M,3] (x, y, speed) device tensor; returns actions [B,A,2] (steer, speed)
-        planned from the current state -- feed it straight to step().  prepare: a raceline tensor that is planned on
-        a second time (same storage, unchanged since: torch's version counter) is prepared once (f110_pure_pursuit_prepare:
-        a grid of candidate segments, ~0.1 s on the host) and from then on planned with one lane per car."""
+        planned from the current state -- feed it straight to step().  prepare: the same raceline tensor OBJECT planned
+        on a second time with its version counter unchanged is prepared once (f110_pure_pursuit_prepare: a grid of
+        candidate segments, ~0.1 s on the host) and from then on planned with one lane per car; every other call -- another
+        tensor (even one at the same address), a bumped version, prepare=False, a call inside a stream capture, a raceline
+        whose grid could not be built -- runs the exhaustive wave-per-car kernel, which reads the raceline's values as they
+        are when it runs (a captured policy therefore plans on whatever the static raceline holds at replay time).  An edit
+        that bypasses the version counter (through `.data`, a raw kernel, a pointer held elsewhere) is not noticed: plan
+        such a raceline with prepare=False, or pass a new tensor.  Anything else (NumPy, another device or dtype) is
+        converted on every call and never prepared."""
         st = self.t['state'] if state is None else self._dev64(state, (-1, 7))
         n = st.numel() // 7
         if out is None:
             out = torch.empty((n, 2), dtype=torch.float64, device=self.device)
+        use_grid = False
         if not (torch.is_tensor(waypoints) and waypoints.device == self.device and waypoints.dtype == torch.float64
                 and waypoints.is_contiguous()):
             waypoints = self._dev64(waypoints, (-1, 3))
         elif prepare and not self._in_capture and 2 <= waypoints.shape[0] <= 65535:
-            key = (waypoints.data_ptr(), waypoints._version, waypoints.shape[0])
-            if getattr(self, '_plan_seen', None) == key and getattr(self, '_plan_key', None) != key:
-                _lib.check(self.lib.f110_pure_pursuit_prepare(self._h, _ptr(waypoints), waypoints.shape[0], 0.0, 0.0, self._stream()))
-                self._plan_key = key
-            elif getattr(self, '_plan_key', None) is not None and self._plan_key != key and self._plan_key[0] == key[0]:
-                # same storage, new values: the prepared grid is stale -- forget it (prepared again on the next call)
-                _lib.check(self.lib.f110_pure_pursuit_prepare(self._h, _ptr(waypoints), waypoints.shape[0], 0.0, 0.0, self._stream()))
-                self._plan_key = key
-            self._plan_seen = key
-        _lib.check(self.lib.f110_pure_pursuit(self._h, _ptr(waypoints), waypoints.shape[0], float(lookahead),
+            use_grid = self._plan_grid(waypoints)
+        _lib.check(self.lib.f110_pure_pursuit(self._h if use_grid else None, _ptr(waypoints), waypoints.shape[0], float(lookahead),
                                               float(vgain), float(wheelbase), float(max_reacquire), _ptr(st), n,
                                               _ptr(out), self._stream()))
         self._keep_wp = waypoints
         return out.view(self.B, self.A, 2) if state is None else out
+
+    def _plan_grid(self, waypoints):
+        """True when the handle holds a grid built from exactly this tensor at its current version.  The prepared
+        tensor is kept alive (its address cannot be handed to another tensor) and matched by identity, not by address;
+        a second use of the last tensor seen prepares it.  A prepare that fails (e.g. a grid beyond 16 M cells) is
+        remembered for that tensor and version: the exhaustive kernel plans it, and the prepare is not tried again."""
+        v = waypoints._version
+        if waypoints is self._plan_tensor and v == self._plan_version:
+            return self._plan_key is not None
+        seen = self._plan_seen
+        if seen is None or seen[0] is not waypoints or seen[1] != v:
+            self._plan_seen = (waypoints, v)
+            return False
+        self._plan_seen = None
+        self._plan_tensor, self._plan_version, self._plan_key = waypoints, v, None
+        rc = self.lib.f110_pure_pursuit_prepare(self._h, _ptr(waypoints), waypoints.shape[0], 0.0, 0.0, self._stream())
+        if rc == 0:
+            self._plan_key = (waypoints.data_ptr(), v, waypoints.shape[0])
+        return self._plan_key is not None
 
     @on_own_device
     def pure_pursuit_tracks(self, tracks, track_of_car, lookahead, vgain, wheelbase=0.17145 + 0.15875, max_reacquire=20.,

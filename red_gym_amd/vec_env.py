@@ -220,9 +220,11 @@ class F110VecEnv(object):
     def pure_pursuit(self, waypoints, lookahead, vgain, wheelbase=0.17145 + 0.15875, prepare=True):
         """Batched pure-pursuit actions for the current poses (examples/waypoint_follow.py planner
         on the GPU); waypoints [M,3] = (x, y, speed).  A device tensor that is planned on repeatedly is prepared once
-        (Engine.pure_pursuit) and then costs one lane per car."""
+        (Engine.pure_pursuit) and then costs one lane per car.  A NumPy array (or a tensor on another device) is copied
+        to the device on every call and never prepared: its in-place edits could not be detected."""
         if not torch.is_tensor(waypoints) or waypoints.device != self.device:
             waypoints = torch.as_tensor(np.ascontiguousarray(waypoints, dtype=np.float64), device=self.device)
+            prepare = False
         return self.eng.pure_pursuit(waypoints, lookahead, vgain, wheelbase, prepare=prepare)
 
     def raceline_slots(self, waypoint_sets, assign):
@@ -246,12 +248,14 @@ class F110VecEnv(object):
         """Pure-pursuit actions when blocks of envs drive on different tracks (randomize_tracks): waypoint_sets[k]
         is the raceline [M_k,3] = (x, y, speed) of slot k, assign the int array [num_envs] of slots.  One planner
         launch for all of them (the packed racelines are cached while the same objects are passed)."""
-        # (the packed form is rebuilt when another list, other raceline objects or another assignment is passed; a raceline
-        # edited IN PLACE is not noticed -- build a new TrackSet with raceline_slots for that)
-        key = (tuple((id(w), tuple(getattr(w, 'shape', ()))) for w in waypoint_sets), np.asarray(assign).tobytes())
-        if getattr(self, '_pp_tracks_key', None) != key:
-            self._pp_tracks = self.raceline_slots(waypoint_sets, assign)
-            self._pp_tracks_key = key
+        # (the packed form is rebuilt unless the very same raceline objects -- held here, so that their ids cannot be
+        # handed to new ones -- and the same assignment are passed; a raceline edited IN PLACE is not noticed -- build a
+        # new TrackSet with raceline_slots for that)
+        lines, assign_bytes = list(waypoint_sets), np.asarray(assign).tobytes()
+        src = getattr(self, '_pp_tracks_src', None)
+        if src is None or src[1] != assign_bytes or len(src[0]) != len(lines) or any(a is not b for a, b in zip(src[0], lines)):
+            self._pp_tracks = self.raceline_slots(lines, assign)
+            self._pp_tracks_src = (lines, assign_bytes)
         ts, of_car = self._pp_tracks
         return self.eng.pure_pursuit_tracks(ts, of_car, lookahead, vgain, wheelbase)
 
