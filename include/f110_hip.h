@@ -170,7 +170,8 @@ int f110_track_mask(const double *pts_dev, int32_t n_pts, int32_t closed, int32_
  * with an even car count; otherwise (a map per env) it runs one wave per workgroup, each staging its own map's table:
  * same bits, ~24 % fewer env-steps/s at 65 536 cars (profiles/r05_map_per_env.txt).  Maps of different kinds ("resolution is a power of two",
  * "origin unrotated") may be mixed: the shard is then scanned block by block, each run of envs with the instantiation
- * its own maps allow (one more launch per change of kind along the env index). */
+ * its own maps allow (one more launch per change of kind along the env index).  An install that fails leaves its slot
+ * as it was: the old map stays in place, and the envs assigned to the slot keep scanning it. */
 int f110_set_map_slot_occupancy(f110_handle *h, int32_t slot, const uint8_t *free_mask_host, int32_t height, int32_t width,
                                 double resolution, double orig_x, double orig_y, double orig_c, double orig_s);
 int f110_set_map_slot_occupancy_dev(f110_handle *h, int32_t slot, const uint8_t *free_mask_dev, int32_t height,

@@ -106,13 +106,12 @@ extern "C" int f110_pure_pursuit_prepare(f110_handle *h, const double *waypoints
     ON_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize()); // an enqueued plan may still read the previous grid
     h->epoch++; // a captured launch of the grid kernel takes the grid's pointers by value: they are freed below
-    if (h->d_plan_count) { (void)hipFree(h->d_plan_count); h->d_plan_count = nullptr; }
-    if (h->d_plan_cand) { (void)hipFree(h->d_plan_cand); h->d_plan_cand = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->d_plan_count, cells));
-    HIP_TRY(hipMalloc((void **)&h->d_plan_cand, cells * PG_CAP * sizeof(uint16_t)));
-    HIP_TRY(hipMemcpy(h->d_plan_count, count.data(), cells, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_plan_cand, cand.data(), cells * PG_CAP * sizeof(uint16_t), hipMemcpyHostToDevice));
-    g.count = h->d_plan_count; g.cand = h->d_plan_cand;
+    DevBuf<uint8_t> d_count;
+    DevBuf<uint16_t> d_cand;
+    HIP_TRY(d_count.upload(count.data(), cells));
+    HIP_TRY(d_cand.upload(cand.data(), cells * PG_CAP));
+    h->d_plan_count = std::move(d_count); h->d_plan_cand = std::move(d_cand);
+    g.count = h->d_plan_count.get(); g.cand = h->d_plan_cand.get();
     h->plan_grid = g; h->plan_wp = waypoints; h->plan_M = M; h->plan_ok = true;
     return F110_OK;
 }
@@ -215,8 +214,8 @@ static const void *bitmap_fn(size_t lds, int mode, int channels)
 
 struct f110_bitmap {
     f110_bitmap_config cfg;
-    int32_t *d_idx = nullptr;
-    double *d_cos = nullptr, *d_sin = nullptr;
+    DevBuf<int32_t> d_idx;
+    DevBuf<double> d_cos, d_sin;
     int S = 0;
     size_t lds[2] = {0, 0};  // dynamic LDS of a launch on fp32 / fp64 scans (the ranges' staging buffers differ)
     int resident[2] = {0, 0}; // workgroups of bitmap_kernel the device runs at once (the launch's grid: a workgroup loops over images)
@@ -226,9 +225,6 @@ extern "C" void f110_bitmap_destroy(f110_bitmap *b)
 {
     if (!b) return;
     DeviceScope on_dev(b->cfg.device);
-    if (b->d_idx) (void)hipFree(b->d_idx);
-    if (b->d_cos) (void)hipFree(b->d_cos);
-    if (b->d_sin) (void)hipFree(b->d_sin);
     delete b;
 }
 
@@ -256,12 +252,9 @@ extern "C" int f110_bitmap_create(const f110_bitmap_config *cfg, const int32_t *
     b->cfg = *cfg; b->S = S; b->lds[1] = lds; b->lds[0] = bitmap_lds_bytes(T, cfg->rows, S, cfg->draw_mode, cfg->channels, 0);
     DeviceScope on_dev(cfg->device);
     if (on_dev.err != hipSuccess) { delete b; return fail(F110_E_HIP, "hipSetDevice(%d) failed", cfg->device); }
-    hipError_t e = hipMalloc((void **)&b->d_idx, T * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_cos, T * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_sin, T * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(b->d_idx, indices, T * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b->d_cos, cosines, T * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b->d_sin, sines, T * sizeof(double), hipMemcpyHostToDevice);
+    hipError_t e = b->d_idx.upload(indices, T);
+    if (e == hipSuccess) e = b->d_cos.upload(cosines, T);
+    if (e == hipSuccess) e = b->d_sin.upload(sines, T);
     if (e == hipSuccess && lds > 64 * 1024)
         e = hipFuncSetAttribute(bitmap_fn(lds, cfg->draw_mode, cfg->channels), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess) {
@@ -291,7 +284,7 @@ extern "C" int f110_bitmap_render(f110_bitmap *b, const void *scans, int32_t sca
     if (int rc = check_current_device(b->cfg.device, "f110_bitmap_render")) return rc;
     BitmapArgs a;
     a.scans = scans; a.is_f64 = scans_f64 != 0; a.stride = stride; a.n = (int)n;
-    a.idx = b->d_idx; a.cosv = b->d_cos; a.sinv = b->d_sin; a.T = b->cfg.target_beam_count;
+    a.idx = b->d_idx.get(); a.cosv = b->d_cos.get(); a.sinv = b->d_sin.get(); a.T = b->cfg.target_beam_count;
     a.rows = b->cfg.rows; a.cols = b->cfg.cols; a.channels = b->cfg.channels; a.mode = b->cfg.draw_mode;
     a.bg = b->cfg.bg_value; a.draw = b->cfg.draw_value; a.draw_center = b->cfg.draw_center;
     a.scale = b->cfg.scaling_factor; a.out = out; a.S = b->S; a.qcap = bm_queue_cap(a.T, a.mode);
@@ -315,7 +308,7 @@ extern "C" int f110_bitmap_points(f110_bitmap *b, const void *scans, int32_t sca
     BitmapArgs a;
     memset(&a, 0, sizeof(a));
     a.scans = scans; a.is_f64 = scans_f64 != 0; a.stride = stride; a.n = (int)n;
-    a.idx = b->d_idx; a.cosv = b->d_cos; a.sinv = b->d_sin; a.T = b->cfg.target_beam_count;
+    a.idx = b->d_idx.get(); a.cosv = b->d_cos.get(); a.sinv = b->d_sin.get(); a.T = b->cfg.target_beam_count;
     a.rows = b->cfg.rows; a.cols = b->cfg.cols; a.scale = b->cfg.scaling_factor;
     const long long items = (long long)n * a.T;
     hipLaunchKernelGGL(bitmap_points_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, points);

@@ -132,13 +132,6 @@ static void default_tables(const f110_config &c, std::vector<double> &sines, std
     }
 }
 
-int upload(double **dst, const double *src, size_t n)
-{
-    if (!*dst) HIP_TRY(hipMalloc((void **)dst, n * sizeof(double)));
-    HIP_TRY(hipMemcpy(*dst, src, n * sizeof(double), hipMemcpyHostToDevice));
-    return F110_OK;
-}
-
 // Order in which a car's beams are handed to idle lanes: chunks of 64 angularly
 // adjacent beams (adjacent rays sample neighbouring cells, which keeps a wave's gathers
 // on few cache lines), the chunks sorted so that rays along the car's longitudinal axis
@@ -159,8 +152,8 @@ static int set_beam_order(f110_handle *h)
     std::vector<uint16_t> chunk0;
     for (auto &k : key) chunk0.push_back((uint16_t)k.second);
     if (nchunks > nfull) chunk0.push_back((uint16_t)(64 * nfull));
-    if (!h->d_chunk0) HIP_TRY(hipMalloc((void **)&h->d_chunk0, MAX_CHUNKS * sizeof(uint16_t)));
-    HIP_TRY(hipMemcpy(h->d_chunk0, chunk0.data(), chunk0.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    if (!h->d_chunk0.get()) HIP_TRY(h->d_chunk0.alloc(MAX_CHUNKS));
+    HIP_TRY(hipMemcpy(h->d_chunk0.get(), chunk0.data(), chunk0.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return F110_OK;
 }
 
@@ -170,8 +163,7 @@ static int upload_beam_cs(f110_handle *h, const double *scan_angles)
     const int n = h->cfg.num_beams;
     std::vector<double2> cs(n);
     for (int i = 0; i < n; i++) { cs[i].x = std::cos(scan_angles[i]); cs[i].y = std::sin(scan_angles[i]); }
-    if (!h->d_beam_cs) HIP_TRY(hipMalloc((void **)&h->d_beam_cs, n * sizeof(double2)));
-    HIP_TRY(hipMemcpy(h->d_beam_cs, cs.data(), n * sizeof(double2), hipMemcpyHostToDevice));
+    HIP_TRY(h->d_beam_cs.upload(cs.data(), n));
     return F110_OK;
 }
 
@@ -182,10 +174,14 @@ static int alloc_opp_pairs(f110_handle *h)
 {
     if (h->cfg.num_agents < 2) return F110_OK;
     const size_t n = (size_t)h->cfg.num_envs * h->cfg.num_agents * (h->cfg.num_agents - 1);
-    HIP_TRY(hipMalloc((void **)&h->d_opp_pairs, n * sizeof(OppPair)));
-    HIP_TRY(hipMemset(h->d_opp_pairs, 0, n * sizeof(OppPair)));
-    HIP_TRY(hipMalloc((void **)&h->d_was_pending, (size_t)h->cfg.num_envs));
-    HIP_TRY(hipMemset(h->d_was_pending, 0, (size_t)h->cfg.num_envs));
+    DevBuf<OppPair> pairs;
+    DevBuf<uint8_t> was_pending;
+    HIP_TRY(pairs.alloc(n));
+    HIP_TRY(hipMemset(pairs.get(), 0, n * sizeof(OppPair)));
+    HIP_TRY(was_pending.alloc((size_t)h->cfg.num_envs));
+    HIP_TRY(hipMemset(was_pending.get(), 0, (size_t)h->cfg.num_envs));
+    h->d_opp_pairs = std::move(pairs);
+    h->d_was_pending = std::move(was_pending);
     return F110_OK;
 }
 
@@ -208,11 +204,17 @@ static int upload_cs(f110_handle *h)
     const int n = td * reps;
     std::vector<double2> cs(n);
     for (int i = 0; i < n; i++) { cs[i].x = h->h_cosines[i % td]; cs[i].y = h->h_sines[i % td]; }
-    if (h->d_cs && h->cs_len != n) { (void)hipFree(h->d_cs); h->d_cs = nullptr; }
-    if (!h->d_cs) HIP_TRY(hipMalloc((void **)&h->d_cs, n * sizeof(double2)));
-    HIP_TRY(hipMemcpy(h->d_cs, cs.data(), n * sizeof(double2), hipMemcpyHostToDevice));
-    h->cs_len = n;
+    HIP_TRY(h->d_cs.upload(cs.data(), n));
     return F110_OK;
+}
+
+// the beam tables a handle starts with
+static int upload_beam_tables(f110_handle *h, const std::vector<double> &ang, const std::vector<double> &bcos, const std::vector<double> &side)
+{
+    HIP_TRY(h->d_scan_angles.upload(ang.data(), ang.size()));
+    HIP_TRY(h->d_beam_cosines.upload(bcos.data(), bcos.size()));
+    HIP_TRY(h->d_side.upload(side.data(), side.size()));
+    return upload_beam_cs(h, ang.data());
 }
 
 extern "C" int f110_create(const f110_config *cfg, f110_handle **out)
@@ -260,10 +262,7 @@ extern "C" int f110_create(const f110_config *cfg, f110_handle **out)
     h->h_cosines = c;
     h->h_side = side;
     set_side_max(h);
-    if ((rc = upload_cs(h)) ||
-        (rc = upload(&h->d_scan_angles, ang.data(), ang.size())) || (rc = upload_beam_cs(h, ang.data())) ||
-        (rc = upload(&h->d_beam_cosines, bcos.data(), bcos.size())) ||
-        (rc = upload(&h->d_side, side.data(), side.size())) || (rc = noise_init(h)) || (rc = set_beam_order(h)) || (rc = upload_params(h)) || (rc = alloc_opp_pairs(h))) {
+    if ((rc = upload_cs(h)) || (rc = upload_beam_tables(h, ang, bcos, side)) || (rc = noise_init(h)) || (rc = set_beam_order(h)) || (rc = upload_params(h)) || (rc = alloc_opp_pairs(h))) {
         f110_destroy(h);
         return rc;
     }
@@ -276,22 +275,7 @@ extern "C" void f110_destroy(f110_handle *h)
     if (!h) return;
     DeviceScope on_dev(h->cfg.device);
     (void)hipDeviceSynchronize();
-    void *ptrs[] = {h->d_cs, h->d_beam_cs, h->d_noise, h->d_noise_desc, h->d_noise_gen, h->d_env_noise, h->d_scan_angles, h->d_beam_cosines,
-                    h->d_side, h->d_chunk0, h->d_params, h->d_env_params, h->d_opp_pairs, h->d_was_pending, h->d_maps, h->d_env_map, h->d_err};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (auto &r : h->retired) { (void)hipFree(r.ptr); (void)hipEventDestroy(r.ev); }
-    if (h->noise_ev) (void)hipEventDestroy(h->noise_ev);
-    if (h->order_ev) (void)hipEventDestroy(h->order_ev);
-    if (h->d_marks) (void)hipFree(h->d_marks);
-    for (void *q : {(void *)h->d_plan_count, (void *)h->d_plan_cand, (void *)h->d_pcg_tab, (void *)h->d_env_gen, (void *)h->d_env_seed, (void *)h->d_env_rows, (void *)h->d_env_ident})
-        if (q) (void)hipFree(q);
-    if (h->noise_stream) (void)hipStreamDestroy(h->noise_stream);
-    for (auto &sl : h->slots)
-        for (void *p : {(void *)sl.d_cells, (void *)sl.d_cells_far, (void *)sl.d_lut, (void *)sl.d_lut_lds, (void *)sl.d_dt})
-            if (p) (void)hipFree(p);
-    for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
-    delete h;
+    delete h; // (its owners free what it holds)
 }
 
 static int upload_params(f110_handle *h)
@@ -299,13 +283,11 @@ static int upload_params(f110_handle *h)
     const int A1 = h->cfg.num_agents + 1;
     // enqueued steps may still read the table
     HIP_TRY(hipDeviceSynchronize());
-    if (h->d_params_slots < h->param_slots) {
-        if (h->d_params) { (void)hipFree(h->d_params); h->d_params = nullptr; }
-        HIP_TRY(hipMalloc((void **)&h->d_params, sizeof(Params) * (size_t)h->param_slots * A1));
-        h->d_params_slots = h->param_slots;
+    if (h->d_params.size() < (size_t)h->param_slots * A1) {
+        HIP_TRY(h->d_params.alloc((size_t)h->param_slots * A1));
         h->epoch++; // the kernels take the pointer by value
     }
-    HIP_TRY(hipMemcpy(h->d_params, h->h_params.data(), sizeof(Params) * (size_t)h->param_slots * A1, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_params.get(), h->h_params.data(), sizeof(Params) * (size_t)h->param_slots * A1, hipMemcpyHostToDevice));
     return F110_OK;
 }
 
@@ -382,8 +364,7 @@ extern "C" int f110_assign_params(f110_handle *h, const int32_t *slot_of_env)
         }
     ON_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize());
-    if (!h->d_env_params) HIP_TRY(hipMalloc((void **)&h->d_env_params, sizeof(int32_t) * B));
-    HIP_TRY(hipMemcpy(h->d_env_params, m.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice));
+    HIP_TRY(h->d_env_params.upload(m.data(), B));
     h->multi_params = multi;
     h->epoch++;
     return F110_OK;
@@ -399,11 +380,14 @@ extern "C" int f110_set_tables(f110_handle *h, const double *sines, const double
     if (sines) h->h_sines.assign(sines, sines + h->cfg.theta_dis);
     if (cosines) h->h_cosines.assign(cosines, cosines + h->cfg.theta_dis);
     if ((sines || cosines) && (rc = upload_cs(h))) return rc;
-    if (ang && ((rc = upload(&h->d_scan_angles, ang, h->cfg.num_beams)) || (rc = upload_beam_cs(h, ang)))) return rc;
-    if (bcos && (rc = upload(&h->d_beam_cosines, bcos, h->cfg.num_beams))) return rc;
+    if (ang) {
+        HIP_TRY(h->d_scan_angles.upload(ang, h->cfg.num_beams));
+        if ((rc = upload_beam_cs(h, ang))) return rc;
+    }
+    if (bcos) HIP_TRY(h->d_beam_cosines.upload(bcos, h->cfg.num_beams));
     h->epoch++;
     if (side) {
-        if ((rc = upload(&h->d_side, side, h->cfg.num_beams))) return rc;
+        HIP_TRY(h->d_side.upload(side, h->cfg.num_beams));
         h->h_side.assign(side, side + h->cfg.num_beams);
         set_side_max(h);
     }
@@ -417,7 +401,7 @@ extern "C" int f110_bounds_selftest(f110_handle *h)
 {
     if (!h) return fail(F110_E_INVALID, "f110_bounds_selftest: null handle");
     ON_DEVICE(h->cfg.device);
-    hipLaunchKernelGGL(bounds_selftest_kernel, dim3(1), dim3(1), 0, nullptr, h->d_err, 7, 7);
+    hipLaunchKernelGGL(bounds_selftest_kernel, dim3(1), dim3(1), 0, nullptr, h->d_err.get(), 7, 7);
     HIP_TRY(hipGetLastError());
     return F110_OK;
 }
@@ -428,8 +412,8 @@ extern "C" int f110_device_errors(f110_handle *h, uint32_t *flags)
     if (!h || !flags) return fail(F110_E_INVALID, "f110_device_errors: null argument");
     ON_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(flags, h->d_err, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (*flags) HIP_TRY(hipMemset(h->d_err, 0, sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(flags, h->d_err.get(), sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (*flags) HIP_TRY(hipMemset(h->d_err.get(), 0, sizeof(uint32_t)));
     return F110_OK;
 }
 

@@ -62,6 +62,47 @@ struct DeviceScope {
     HIP_TRY(dev_scope_.err)
 
 
+// Owners of what the library allocates.  Every device buffer, event, stream and graph lives in one of these and is released by
+// its destructor; a table is replaced by building the new one in a local owner and moving it in, which frees the old one.
+template <typename T> class DevBuf { // device memory of size() elements of T
+    T *p_ = nullptr;
+    size_t n_ = 0;
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+    DevBuf &operator=(DevBuf o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); return *this; } // (o takes the old memory along)
+    ~DevBuf() { if (p_) (void)hipFree(p_); }
+    T *get() const { return p_; }
+    size_t size() const { return n_; }
+    hipError_t alloc(size_t n) // new memory first: a failure leaves what is held
+    {
+        T *p = nullptr;
+        const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+        if (e == hipSuccess) { std::swap(p_, p); n_ = n; if (p) (void)hipFree(p); }
+        return e;
+    }
+    hipError_t upload(const T *src, size_t n) // (re)allocates when n differs from size()
+    {
+        const hipError_t e = n == n_ && p_ ? hipSuccess : alloc(n);
+        return e == hipSuccess ? hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice) : e;
+    }
+};
+
+template <typename H, hipError_t (*Destroy)(H)> class HipOwner { // an event, stream or graph
+    H h_ = nullptr;
+public:
+    HipOwner() = default;
+    HipOwner(HipOwner &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+    HipOwner &operator=(HipOwner o) noexcept { std::swap(h_, o.h_); return *this; }
+    ~HipOwner() { if (h_) (void)Destroy(h_); }
+    H get() const { return h_; }
+    H *put() { *this = HipOwner(); return &h_; } // for the call that creates it: what was held is released first
+};
+using Event = HipOwner<hipEvent_t, hipEventDestroy>;
+using Stream = HipOwner<hipStream_t, hipStreamDestroy>;
+using Graph = HipOwner<hipGraph_t, hipGraphDestroy>;
+using GraphExec = HipOwner<hipGraphExec_t, hipGraphExecDestroy>;
+
 // one stage of a scan launch's wave -> car mapping: `cars` cars (< 0: "*", the remaining cars) at 2^lg waves each
 struct StageSpec { int cars, lg; };
 
@@ -71,12 +112,11 @@ struct f110_handle {
     // Simulator.params (GJK vertices, base_classes.py:542), entry 1 + i = RaceCar.params of agent i
     std::vector<Params> h_params;
     int param_slots = 1;
-    Params *d_params = nullptr;
-    int d_params_slots = 0;           // slots the device allocation holds
-    int32_t *d_env_params = nullptr;  // dev [B] params slot of every env; passed to the kernels only when `multi_params`
+    DevBuf<Params> d_params;          // [slots the allocation holds][1 + A]
+    DevBuf<int32_t> d_env_params;     // dev [B] params slot of every env; passed to the kernels only when `multi_params`
     bool multi_params = false;
-    OppPair *d_opp_pairs = nullptr;   // [N, A-1] opponent ray-cast scratch (never allocated in f110_step)
-    uint8_t *d_was_pending = nullptr; // [B] pending_reset as the step's first kernel found it
+    DevBuf<OppPair> d_opp_pairs;      // [N, A-1] opponent ray-cast scratch (never allocated in f110_step)
+    DevBuf<uint8_t> d_was_pending;    // [B] pending_reset as the step's first kernel found it
     bool has_map = false, bound = false;
     // Bumped whenever a later f110_step would enqueue different kernels or by-value arguments than an earlier one
     // (a table re-allocated, another scan instantiation selected, buffers re-bound): f110_launch_epoch.
@@ -84,20 +124,19 @@ struct f110_handle {
     std::vector<StageSpec> stages;    // f110_set_scan_stages override, parsed (empty: the built-in choice, scan_stage_list)
     f110_buffers bufs;
     // device tables owned by the handle
-    double *d_scan_angles = nullptr, *d_beam_cosines = nullptr, *d_side = nullptr;
-    uint16_t *d_chunk0 = nullptr;
-    double2 *d_cs = nullptr;          // interleaved {cos, sin} LUT (repeated, see upload_cs)
-    int cs_len = 0;
-    double2 *d_beam_cs = nullptr;     // {cos, sin}(scan_angles) for the opponent ray cast
+    DevBuf<double> d_scan_angles, d_beam_cosines, d_side;
+    DevBuf<uint16_t> d_chunk0;
+    DevBuf<double2> d_cs;             // interleaved {cos, sin} LUT (repeated, see upload_cs)
+    DevBuf<double2> d_beam_cs;        // {cos, sin}(scan_angles) for the opponent ray cast
     std::vector<double> h_sines, h_cosines;
     // Lidar noise (f110_noise.h): [noise_slots][cap][nb] noise rows, rows lo .. hi-1 present; the kernels
     // find it through d_noise_desc, whose address never changes
-    double *d_noise = nullptr;        // [noise_slots][noise_cap][num_beams] noise rows (a ring per slot)
+    DevBuf<double> d_noise;           // [noise_slots][noise_cap][num_beams] noise rows (a ring per slot)
     double side_max = 0.0;            // largest finite side distance (the scan's pre-test for iTTC candidates)
     long long noise_cap = 0, noise_lo = 0, noise_hi = 0; // cap: rows per slot (a power of two); noise off: cap 1, hi = "infinity"
     int noise_slots = 1;
     bool noise_on = false;
-    NoiseDesc *d_noise_desc = nullptr;
+    DevBuf<NoiseDesc> d_noise_desc;
     struct NoiseSlot {
         int kind = 0;                 // 0 unset (zeros), 1 host-fed table, 2 generator
         std::vector<double> rows;     // host-fed: [T, nb]
@@ -105,73 +144,57 @@ struct f110_handle {
         NoiseGen seed;                // generator: the stream at row 0
     };
     NoiseSlot nslots[F110_MAX_NOISE_SLOTS];
-    NoiseGen *d_noise_gen = nullptr;  // [F110_MAX_NOISE_SLOTS] device generator states
-    int32_t *d_env_noise = nullptr;   // dev [B] noise slot of every env; passed only when `multi_noise`
+    DevBuf<NoiseGen> d_noise_gen;     // [F110_MAX_NOISE_SLOTS] device generator states
+    DevBuf<int32_t> d_env_noise;      // dev [B] noise slot of every env; passed only when `multi_noise`
     bool multi_noise = false;
-    hipStream_t noise_stream = nullptr; // the generator runs here, beside the caller's stream (f110_noise_prefetch)
-    hipEvent_t noise_ev = nullptr;
+    Stream noise_stream;              // the generator runs here, beside the caller's stream (f110_noise_prefetch)
+    Event noise_ev;
     long long noise_pending_hi = 0;   // rows a prefetch in flight on noise_stream will have produced (0: none in flight)
     // Ordering of the side stream behind the caller's: recorded on the caller's stream whenever the floor is raised (the steps
     // enqueued so far may still read the rows below it, whose ring places the next prefetch recycles) and whenever a generator
     // kernel is enqueued there (it reads and writes the same generator states); the next prefetch waits for it.
-    hipEvent_t order_ev = nullptr;
+    Event order_ev;
     bool order_ev_set = false;
     // prepared raceline of f110_pure_pursuit (f110_pure_pursuit_prepare): grid of candidate lists (f110_planner.h PlanGrid)
     const double *plan_wp = nullptr; int plan_M = 0; bool plan_ok = false;
     PlanGrid plan_grid;
-    uint8_t *d_plan_count = nullptr; uint16_t *d_plan_cand = nullptr;
-    u128 *d_pcg_tab = nullptr;        // [2][65] powers and partial sums of the LCG multiplier (f110_noise.h NoiseGenArgs::pcg_tab)
+    DevBuf<uint8_t> d_plan_count; DevBuf<uint16_t> d_plan_cand;
+    DevBuf<u128> d_pcg_tab;           // [2][65] powers and partial sums of the LCG multiplier (f110_noise.h NoiseGenArgs::pcg_tab)
     const int32_t *scan_order = nullptr; // launch order of the step's scan (f110_set_scan_order; caller-owned device array) or NULL
     // per-env noise (f110_set_noise_per_env): every env its own generator and ONE row, produced in front of every step's scan
     bool per_env_noise = false;
-    NoiseGen *d_env_gen = nullptr, *d_env_seed = nullptr;   // [num_envs]
-    double *d_env_rows = nullptr;                           // [num_envs][num_beams]
-    int32_t *d_env_ident = nullptr;                         // [num_envs] env -> slot = env
-    NoiseMark *d_marks = nullptr;     // [noise_slots][marks_cap] generator state at every 64th row (f110_noise.h NoiseMark)
+    DevBuf<NoiseGen> d_env_gen, d_env_seed;   // [num_envs]
+    DevBuf<double> d_env_rows;                // [num_envs][num_beams]
+    DevBuf<int32_t> d_env_ident;              // [num_envs] env -> slot = env
+    DevBuf<NoiseMark> d_marks;        // [noise_slots][marks_cap] generator state at every 64th row (f110_noise.h NoiseMark)
     long long marks_cap = 0;
     int marks_slots = 0;
-    struct Retired { void *ptr; hipEvent_t ev; };
-    std::vector<Retired> retired;     // old noise tables, freed once the work that may read them has drained
-    uint32_t *d_err = nullptr;        // device error word (f110_device_errors)
+    DevBuf<uint32_t> d_err;           // device error word (f110_device_errors)
     std::vector<double> h_side;       // side distances (host copy of d_side)
     // Maps.  Slot 0 is "the" map of the reference's API; further slots let blocks of envs of one shard run on
     // different maps (one handle standing in for many F110Env instances with their own map each).
     struct MapSlot {
-        uint16_t *d_cells = nullptr, *d_cells_far = nullptr;
-        double *d_lut = nullptr, *d_lut_lds = nullptr, *d_dt = nullptr;
+        DevBuf<uint16_t> d_cells, d_cells_far;
+        DevBuf<double> d_lut, d_lut_lds, d_dt;
         MapDev dev;                   // host copy of d_maps[slot]
         bool used = false, ident = false, pow2 = false;
     };
     MapSlot slots[F110_MAX_MAPS];
-    MapDev *d_maps = nullptr;         // dev [F110_MAX_MAPS] descriptors read by scan_kernel
-    int32_t *d_env_map = nullptr;     // dev [B] slot of every env; only passed to the kernel when `multi`
+    DevBuf<MapDev> d_maps;            // dev [F110_MAX_MAPS] descriptors read by scan_kernel
+    DevBuf<int32_t> d_env_map;        // dev [B] slot of every env; only passed to the kernel when `multi`
     std::vector<int32_t> h_env_map;   // host copy (all 0 until f110_assign_maps)
     bool multi = false;
     bool wg_single = false;           // some neighbouring cars stand on different maps: the scan runs one wave per workgroup
     bool ident = false, pow2 = false; // AND over the used slots: selects the scan_kernel instantiation
     double theta_inc = 0;
     // measurement aid (f110_profile_begin/end)
-    std::vector<hipEvent_t> prof_ev; // pairs: [2*i] before, [2*i+1] after the scan launch
+    std::vector<Event> prof_ev;      // pairs: [2*i] before, [2*i+1] after the scan launch
     int prof_n = 0, prof_every = 1, prof_seq = 0; // events ride on every prof_every-th step's scan launch (the middle one of
                                                   // each run of prof_every steps: on a clock ramp the samples' mean is then the steps' mean)
     bool prof_on = false;
 };
 
-struct DevTemp { // frees its device scratch on every exit path
-    std::vector<void *> ptrs;
-    ~DevTemp() { for (void *p : ptrs) if (p) (void)hipFree(p); }
-    template <typename T> hipError_t alloc(T **out, size_t n)
-    {
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, n * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(p);
-        *out = static_cast<T *>(p);
-        return e;
-    }
-};
-
 // helpers defined in f110_handle.hip / f110_noise_abi.hip and used elsewhere
 int check_current_device(int dev, const char *who);
 int check_device(const f110_handle *h, const char *who);
-int upload(double **dst, const double *src, size_t n);
 int noise_init(f110_handle *h);

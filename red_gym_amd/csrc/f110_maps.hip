@@ -2,28 +2,34 @@
 #define F110_UNIT_MAPS
 #include "f110_internal.h"
 
-// Publishes the device tables of a freshly built map in slot `slot` (both pipelines end here).
-static int finish_map(f110_handle *h, int slot, int H, int W, int Hp, size_t n_tiled, double res, double ox, double oy, double oc,
-                      double os, double oob, unsigned lut_len)
+// Both pipelines end here.  `ns` holds the complete tables of the new map; until the descriptor is on the device nothing of the
+// slot has changed, so a failed install leaves the slot, its descriptor and the handle's flags as they were.  Then the slot takes
+// the new tables over (its old ones are freed: the pipelines synchronised the device before building), with new flags and epoch.
+static int commit_map(f110_handle *h, int slot, f110_handle::MapSlot &&ns, int H, int W, double res, double ox, double oy, double oc,
+                      double os, double oob)
 {
-    f110_handle::MapSlot &sl = h->slots[slot];
-    MapDev &m = sl.dev;
-    m.cells = sl.d_cells; m.cells_far = sl.d_cells_far; m.lut = sl.d_lut; m.lut_lds = sl.d_lut_lds; m.dt = sl.d_dt;
-    m.H = H; m.W = W; m.strip_bytes = (unsigned)Hp * 16u; m.cells_bytes = (unsigned)(n_tiled * sizeof(uint16_t)); m.res = res; m.rinv = 1.0 / res;
+    MapDev &m = ns.dev;
+    memset(&m, 0, sizeof(m));
+    m.cells = ns.d_cells.get(); m.cells_far = ns.d_cells_far.get(); m.lut = ns.d_lut.get(); m.lut_lds = ns.d_lut_lds.get(); m.dt = ns.d_dt.get();
+    m.H = H; m.W = W; m.strip_bytes = (unsigned)map_rows_padded(H) * 16u; m.cells_bytes = (unsigned)(ns.d_cells.size() * sizeof(uint16_t));
+    m.res = res; m.rinv = 1.0 / res;
     m.ox = ox; m.oy = oy; m.oc = oc; m.os = os;
     m.wres = W * res; // width * resolution (laser_models.py:79)
     m.hres = H * res;
     m.oob = oob;      // dt[-1, -1]
-    m.lut_len = lut_len;
+    m.lut_len = (unsigned)ns.d_lut.size();
     int e = 0;
-    sl.pow2 = std::frexp(res, &e) == 0.5;
-    sl.ident = (oc == 1.0 && os == 0.0);
-    sl.used = true;
-    if (!h->d_maps) {
-        HIP_TRY(hipMalloc((void **)&h->d_maps, sizeof(MapDev) * F110_MAX_MAPS));
-        HIP_TRY(hipMemset(h->d_maps, 0, sizeof(MapDev) * F110_MAX_MAPS));
+    ns.pow2 = std::frexp(res, &e) == 0.5;
+    ns.ident = (oc == 1.0 && os == 0.0);
+    ns.used = true;
+    if (!h->d_maps.get()) {
+        DevBuf<MapDev> maps;
+        HIP_TRY(maps.alloc(F110_MAX_MAPS));
+        HIP_TRY(hipMemset(maps.get(), 0, sizeof(MapDev) * F110_MAX_MAPS));
+        h->d_maps = std::move(maps);
     }
-    HIP_TRY(hipMemcpy(h->d_maps + slot, &m, sizeof(MapDev), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_maps.get() + slot, &m, sizeof(MapDev), hipMemcpyHostToDevice));
+    h->slots[slot] = std::move(ns);
     h->ident = h->pow2 = true;
     for (const auto &u : h->slots)
         if (u.used) { h->ident = h->ident && u.ident; h->pow2 = h->pow2 && u.pow2; }
@@ -38,7 +44,6 @@ static int finish_map(f110_handle *h, int slot, int H, int W, int Hp, size_t n_t
 static int install_map(f110_handle *h, int slot, const double *dt, const uint32_t *d2_or_null, int H, int W, double res,
                        double ox, double oy, double oc, double os)
 {
-    f110_handle::MapSlot &sl = h->slots[slot];
     const size_t n = (size_t)H * W;
     // padded table (one border cell on every side), 8-column strips: see MapDev
     const int Hp = map_rows_padded(H);
@@ -78,26 +83,17 @@ static int install_map(f110_handle *h, int slot, const double *dt, const uint32_
     }
     ON_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize()); // the previous map may still be in use by enqueued steps
-    if (sl.d_cells) { (void)hipFree(sl.d_cells); sl.d_cells = nullptr; }
-    if (sl.d_cells_far) { (void)hipFree(sl.d_cells_far); sl.d_cells_far = nullptr; }
-    if (sl.d_dt) { (void)hipFree(sl.d_dt); sl.d_dt = nullptr; }
-    if (sl.d_lut) { (void)hipFree(sl.d_lut); sl.d_lut = nullptr; } // its length depends on the map
-    sl.used = false;
-    h->has_map = h->slots[0].used;
-    HIP_TRY(hipMalloc((void **)&sl.d_cells, n_tiled * sizeof(uint16_t)));
-    HIP_TRY(hipMalloc((void **)&sl.d_dt, n * sizeof(double)));
-    HIP_TRY(hipMemcpy(sl.d_cells, cells.data(), n_tiled * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void **)&sl.d_cells_far, n_tiled * sizeof(uint16_t)));
-    HIP_TRY(hipMemcpy(sl.d_cells_far, cells_far.data(), n_tiled * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sl.d_dt, dt, n * sizeof(double), hipMemcpyHostToDevice));
-    int rc = upload(&sl.d_lut, lut.data(), lut.size());
-    if (rc) return rc;
+    f110_handle::MapSlot ns;
+    HIP_TRY(ns.d_cells.upload(cells.data(), n_tiled));
+    HIP_TRY(ns.d_cells_far.upload(cells_far.data(), n_tiled));
+    HIP_TRY(ns.d_dt.upload(dt, n));
+    HIP_TRY(ns.d_lut.upload(lut.data(), lut.size()));
     std::vector<double> lut_lds(LUT_LDS);
     lut_lds[SLOT_OOB] = dt[n - 1];    // dt[-1, -1]: what code 0 (the border: a look-up outside the map) reads
     std::copy(lut.begin(), lut.begin() + LDS_RANKS, lut_lds.begin() + 1);
     lut_lds[SLOT_FAR] = -0.0;         // the far marker (OFF_FAR cells take the second table): see MapDev
-    if ((rc = upload(&sl.d_lut_lds, lut_lds.data(), lut_lds.size()))) return rc;
-    return finish_map(h, slot, H, W, Hp, n_tiled, res, ox, oy, oc, os, dt[n - 1], (unsigned)lut.size());
+    HIP_TRY(ns.d_lut_lds.upload(lut_lds.data(), lut_lds.size()));
+    return commit_map(h, slot, std::move(ns), H, W, res, ox, oy, oc, os, dt[n - 1]);
 }
 
 // ---------------------------------------------------------------- map pipeline on the device
@@ -127,10 +123,9 @@ extern "C" int f110_edt_squared_dev(const uint8_t *mask_dev, int32_t H, int32_t 
     if (!mask_dev || !d2_dev) return fail(F110_E_INVALID, "f110_edt_squared_dev: null pointer");
     int rc = check_edt_size(H, W, "f110_edt_squared_dev");
     if (rc) return rc;
-    DevTemp tmp;
-    unsigned *g = nullptr;
-    HIP_TRY(tmp.alloc(&g, (size_t)H * W));
-    if ((rc = edt_squared_device(mask_dev, H, W, d2_dev, g, nullptr, (hipStream_t)stream))) return rc;
+    DevBuf<unsigned> g;
+    HIP_TRY(g.alloc((size_t)H * W));
+    if ((rc = edt_squared_device(mask_dev, H, W, d2_dev, g.get(), nullptr, (hipStream_t)stream))) return rc;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); // the scratch is freed on return
     return F110_OK;
 }
@@ -139,62 +134,55 @@ extern "C" int f110_edt_squared_dev(const uint8_t *mask_dev, int32_t H, int32_t 
 static int install_map_occupancy_dev(f110_handle *h, int slot, const uint8_t *mask_dev, int H, int W, double res, double ox,
                                      double oy, double oc, double os)
 {
-    f110_handle::MapSlot &sl = h->slots[slot];
     const size_t n = (size_t)H * W;
     const int Hp = map_rows_padded(H);
     const size_t n_tiled = map_cells(H, W);
     ON_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize()); // the previous map may still be in use by enqueued steps
     hipStream_t st = nullptr;
-    DevTemp tmp;
-    unsigned *g = nullptr, *d2 = nullptr, *maxv = nullptr, *bits = nullptr, *prefix = nullptr, *sums = nullptr;
-    HIP_TRY(tmp.alloc(&g, n));
-    HIP_TRY(tmp.alloc(&d2, n));
-    HIP_TRY(tmp.alloc(&maxv, 2));
-    HIP_TRY(hipMemsetAsync(maxv, 0, 2 * sizeof(unsigned), st));
-    int rc = edt_squared_device(mask_dev, H, W, d2, g, maxv, st);
+    DevBuf<unsigned> g, d2, maxv, bits, prefix, sums; // scratch
+    HIP_TRY(g.alloc(n));
+    HIP_TRY(d2.alloc(n));
+    HIP_TRY(maxv.alloc(2));
+    HIP_TRY(hipMemsetAsync(maxv.get(), 0, 2 * sizeof(unsigned), st));
+    int rc = edt_squared_device(mask_dev, H, W, d2.get(), g.get(), maxv.get(), st);
     if (rc) return rc;
     unsigned max_d2 = 0;
-    HIP_TRY(hipMemcpy(&max_d2, maxv, sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&max_d2, maxv.get(), sizeof(unsigned), hipMemcpyDeviceToHost));
     // ranks of the distinct d2 values: presence bitmap + exclusive prefix of its popcounts
     const int n_words = (int)(((size_t)max_d2 + 32) / 32);
     const int n_blocks = (n_words + SCAN_BLOCK_WORDS - 1) / SCAN_BLOCK_WORDS;
-    HIP_TRY(tmp.alloc(&bits, (size_t)n_words));
-    HIP_TRY(tmp.alloc(&prefix, (size_t)n_words));
-    HIP_TRY(tmp.alloc(&sums, (size_t)n_blocks));
-    HIP_TRY(hipMemsetAsync(bits, 0, (size_t)n_words * sizeof(unsigned), st));
-    hipLaunchKernelGGL(d2_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d2, n, bits);
-    hipLaunchKernelGGL(rank_block_sums_kernel, dim3(n_blocks), dim3(256), 0, st, bits, n_words, sums);
-    hipLaunchKernelGGL(rank_scan_sums_kernel, dim3(1), dim3(64), 0, st, sums, n_blocks, maxv + 1);
-    hipLaunchKernelGGL(rank_word_prefix_kernel, dim3(n_blocks), dim3(256), 0, st, bits, n_words, sums, prefix);
+    HIP_TRY(bits.alloc((size_t)n_words));
+    HIP_TRY(prefix.alloc((size_t)n_words));
+    HIP_TRY(sums.alloc((size_t)n_blocks));
+    HIP_TRY(hipMemsetAsync(bits.get(), 0, (size_t)n_words * sizeof(unsigned), st));
+    hipLaunchKernelGGL(d2_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d2.get(), n, bits.get());
+    hipLaunchKernelGGL(rank_block_sums_kernel, dim3(n_blocks), dim3(256), 0, st, bits.get(), n_words, sums.get());
+    hipLaunchKernelGGL(rank_scan_sums_kernel, dim3(1), dim3(64), 0, st, sums.get(), n_blocks, maxv.get() + 1);
+    hipLaunchKernelGGL(rank_word_prefix_kernel, dim3(n_blocks), dim3(256), 0, st, bits.get(), n_words, sums.get(), prefix.get());
     HIP_TRY(hipGetLastError());
-    // the handle's tables
-    if (sl.d_cells) { (void)hipFree(sl.d_cells); sl.d_cells = nullptr; }
-    if (sl.d_cells_far) { (void)hipFree(sl.d_cells_far); sl.d_cells_far = nullptr; }
-    if (sl.d_dt) { (void)hipFree(sl.d_dt); sl.d_dt = nullptr; }
-    if (sl.d_lut) { (void)hipFree(sl.d_lut); sl.d_lut = nullptr; }
-    sl.used = false;
-    h->has_map = h->slots[0].used;
-    HIP_TRY(hipMalloc((void **)&sl.d_cells, n_tiled * sizeof(uint16_t)));
-    HIP_TRY(hipMalloc((void **)&sl.d_cells_far, n_tiled * sizeof(uint16_t)));
-    HIP_TRY(hipMalloc((void **)&sl.d_dt, n * sizeof(double)));
+    // the new map's tables
+    f110_handle::MapSlot ns;
+    HIP_TRY(ns.d_cells.alloc(n_tiled));
+    HIP_TRY(ns.d_cells_far.alloc(n_tiled));
+    HIP_TRY(ns.d_dt.alloc(n));
     const unsigned n_lut = CODE_ESC; // ranks 0..65534 are encodable; unused slots stay 0.0
-    HIP_TRY(hipMalloc((void **)&sl.d_lut, (size_t)n_lut * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(sl.d_lut, 0, (size_t)n_lut * sizeof(double), st));
-    hipLaunchKernelGGL(map_fill_border_kernel, dim3((unsigned)((n_tiled + 255) / 256)), dim3(256), 0, st, sl.d_cells, sl.d_cells_far, n_tiled);
-    hipLaunchKernelGGL(map_encode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d2, H, W, Hp, bits, prefix, res, sl.d_cells,
-                       sl.d_cells_far, sl.d_dt);
-    hipLaunchKernelGGL(map_lut_kernel, dim3((n_words + 255) / 256), dim3(256), 0, st, bits, n_words, prefix, res, sl.d_lut, n_lut);
+    HIP_TRY(ns.d_lut.alloc(n_lut));
+    HIP_TRY(hipMemsetAsync(ns.d_lut.get(), 0, (size_t)n_lut * sizeof(double), st));
+    hipLaunchKernelGGL(map_fill_border_kernel, dim3((unsigned)((n_tiled + 255) / 256)), dim3(256), 0, st, ns.d_cells.get(), ns.d_cells_far.get(), n_tiled);
+    hipLaunchKernelGGL(map_encode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d2.get(), H, W, Hp, bits.get(), prefix.get(), res,
+                       ns.d_cells.get(), ns.d_cells_far.get(), ns.d_dt.get());
+    hipLaunchKernelGGL(map_lut_kernel, dim3((n_words + 255) / 256), dim3(256), 0, st, bits.get(), n_words, prefix.get(), res, ns.d_lut.get(), n_lut);
     HIP_TRY(hipGetLastError());
     // LDS image of the LUT: its first slots, with the two special ones (see MapDev)
     std::vector<double> lut_lds(LUT_LDS);
     double oob = 0;
-    HIP_TRY(hipMemcpy(lut_lds.data() + 1, sl.d_lut, LDS_RANKS * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&oob, sl.d_dt + (n - 1), sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lut_lds.data() + 1, ns.d_lut.get(), LDS_RANKS * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&oob, ns.d_dt.get() + (n - 1), sizeof(double), hipMemcpyDeviceToHost));
     lut_lds[SLOT_OOB] = oob;
     lut_lds[SLOT_FAR] = -0.0;
-    if ((rc = upload(&sl.d_lut_lds, lut_lds.data(), lut_lds.size()))) return rc;
-    return finish_map(h, slot, H, W, Hp, n_tiled, res, ox, oy, oc, os, oob, n_lut);
+    HIP_TRY(ns.d_lut_lds.upload(lut_lds.data(), lut_lds.size()));
+    return commit_map(h, slot, std::move(ns), H, W, res, ox, oy, oc, os, oob);
 }
 
 
@@ -234,11 +222,9 @@ extern "C" int f110_set_map_slot_occupancy(f110_handle *h, int32_t slot, const u
     const size_t n = (size_t)H * W;
     if (!memchr(mask, 0, n)) return fail(F110_E_INVALID, "f110_set_map_occupancy: map has no occupied cell");
     ON_DEVICE(h->cfg.device);
-    DevTemp tmp;
-    uint8_t *mask_dev = nullptr;
-    HIP_TRY(tmp.alloc(&mask_dev, n));
-    HIP_TRY(hipMemcpy(mask_dev, mask, n, hipMemcpyHostToDevice));
-    return install_map_occupancy_dev(h, slot, mask_dev, H, W, res, ox, oy, oc, os);
+    DevBuf<uint8_t> mask_dev;
+    HIP_TRY(mask_dev.upload(mask, n));
+    return install_map_occupancy_dev(h, slot, mask_dev.get(), H, W, res, ox, oy, oc, os);
 }
 
 extern "C" int f110_set_map_slot_occupancy_dev(f110_handle *h, int32_t slot, const uint8_t *mask_dev, int32_t H, int32_t W,
@@ -279,7 +265,7 @@ extern "C" int f110_get_map_slot_dt(f110_handle *h, int32_t slot, double *out)
     const f110_handle::MapSlot &sl = h->slots[slot];
     if (!sl.used) return fail(F110_E_NOMAP, "Map is not set for scan simulator.");
     ON_DEVICE(h->cfg.device);
-    HIP_TRY(hipMemcpy(out, sl.d_dt, (size_t)sl.dev.H * sl.dev.W * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, sl.d_dt.get(), (size_t)sl.dev.H * sl.dev.W * sizeof(double), hipMemcpyDeviceToHost));
     return F110_OK;
 }
 
@@ -309,8 +295,7 @@ extern "C" int f110_assign_maps(f110_handle *h, const int32_t *map_of_env)
                 if (m[(c + j) / A] != m[c / A]) { single = true; break; }
     ON_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize()); // enqueued steps may still read the table
-    if (!h->d_env_map) HIP_TRY(hipMalloc((void **)&h->d_env_map, sizeof(int32_t) * B));
-    HIP_TRY(hipMemcpy(h->d_env_map, m.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice));
+    HIP_TRY(h->d_env_map.upload(m.data(), B));
     h->h_env_map = m;
     h->multi = multi;
     h->wg_single = single;

@@ -12,17 +12,6 @@ static long long pow2_at_least(long long n)
     return c;
 }
 
-static void noise_reap(f110_handle *h, bool all)
-{
-    for (size_t i = 0; i < h->retired.size();) {
-        if (all || hipEventQuery(h->retired[i].ev) == hipSuccess) {
-            (void)hipFree(h->retired[i].ptr);
-            (void)hipEventDestroy(h->retired[i].ev);
-            h->retired.erase(h->retired.begin() + i);
-        } else i++;
-    }
-}
-
 // rows every active slot can serve
 static void noise_recompute_hi(f110_handle *h)
 {
@@ -41,16 +30,16 @@ static int noise_publish(f110_handle *h, hipStream_t st)
 {
     NoiseDesc d;
     if (h->per_env_noise) { // one row per env, produced on demand: every row counter is "in the table"
-        d.base = h->d_env_rows; d.cap = 1; d.mask = 0; d.lo = 0; d.hi = 0x7fffffff; d.slots = h->cfg.num_envs; d.pad = 0;
-        hipLaunchKernelGGL(noise_publish_kernel, dim3(1), dim3(1), 0, st, h->d_noise_desc, d);
+        d.base = h->d_env_rows.get(); d.cap = 1; d.mask = 0; d.lo = 0; d.hi = 0x7fffffff; d.slots = h->cfg.num_envs; d.pad = 0;
+        hipLaunchKernelGGL(noise_publish_kernel, dim3(1), dim3(1), 0, st, h->d_noise_desc.get(), d);
         HIP_TRY(hipGetLastError());
         return F110_OK;
     }
-    d.base = h->d_noise; d.cap = (int)h->noise_cap; d.mask = (int)(h->noise_cap - 1);
+    d.base = h->d_noise.get(); d.cap = (int)h->noise_cap; d.mask = (int)(h->noise_cap - 1);
     d.lo = h->noise_on ? (int)std::min(h->noise_lo, (long long)0x7fffffff) : 0;
     d.slots = h->noise_slots; d.pad = 0;
     d.hi = h->noise_on ? (int)std::min(h->noise_hi, (long long)0x7fffffff) : 0x7fffffff; // noise off: every row is the row of zeros
-    hipLaunchKernelGGL(noise_publish_kernel, dim3(1), dim3(1), 0, st, h->d_noise_desc, d);
+    hipLaunchKernelGGL(noise_publish_kernel, dim3(1), dim3(1), 0, st, h->d_noise_desc.get(), d);
     HIP_TRY(hipGetLastError());
     return F110_OK;
 }
@@ -72,25 +61,23 @@ static int noise_resize(f110_handle *h, int slots, long long cap)
     const int nb = h->cfg.num_beams;
     if ((long long)slots * cap >= 0x7fffffffll) return fail(F110_E_INVALID, "noise table: %d slots x %lld rows exceed 2^31 rows", slots, cap);
     HIP_TRY(hipDeviceSynchronize());
-    noise_reap(h, true);
-    double *nt = nullptr;
+    DevBuf<double> nt;
     const size_t total = (size_t)slots * (size_t)cap;
-    HIP_TRY(hipMalloc((void **)&nt, total * nb * sizeof(double)));
+    HIP_TRY(nt.alloc(total * nb));
     {
         const long long items = (long long)total * nb;
         hipLaunchKernelGGL(noise_fill_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, nullptr, (const double *)nullptr,
-                           (long long)total, nb, nt, 0, (long long)total, (long long)0x7fffffffffffffffll);
+                           (long long)total, nb, nt.get(), 0, (long long)total, (long long)0x7fffffffffffffffll);
     }
-    if (h->d_noise && h->noise_on && h->noise_hi > h->noise_lo) {
+    if (h->d_noise.get() && h->noise_on && h->noise_hi > h->noise_lo) {
         const int ms = std::min(slots, h->noise_slots);
         const long long items = (h->noise_hi - h->noise_lo) * nb * ms;
-        hipLaunchKernelGGL(noise_move_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, nullptr, h->d_noise, h->noise_cap,
-                           h->noise_cap - 1, nt, cap, cap - 1, ms, h->noise_lo, h->noise_hi, nb);
+        hipLaunchKernelGGL(noise_move_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, nullptr, h->d_noise.get(), h->noise_cap,
+                           h->noise_cap - 1, nt.get(), cap, cap - 1, ms, h->noise_lo, h->noise_hi, nb);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    if (h->d_noise) (void)hipFree(h->d_noise);
-    h->d_noise = nt;
+    h->d_noise = std::move(nt);
     h->noise_cap = cap;
     h->noise_slots = slots;
     h->epoch++; // the scan takes the table's base and size by value (ScanArgs::noise_base): a re-allocation is a new launch
@@ -99,22 +86,21 @@ static int noise_resize(f110_handle *h, int slots, long long cap)
 
 int noise_init(f110_handle *h)
 {
-    HIP_TRY(hipMalloc((void **)&h->d_noise_desc, sizeof(NoiseDesc)));
-    HIP_TRY(hipMalloc((void **)&h->d_noise_gen, sizeof(NoiseGen) * F110_MAX_NOISE_SLOTS));
-    HIP_TRY(hipMemset(h->d_noise_gen, 0, sizeof(NoiseGen) * F110_MAX_NOISE_SLOTS));
-    HIP_TRY(hipMalloc((void **)&h->d_err, sizeof(uint32_t)));
-    HIP_TRY(hipMemset(h->d_err, 0, sizeof(uint32_t)));
-    HIP_TRY(hipStreamCreateWithFlags(&h->noise_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&h->noise_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
+    HIP_TRY(h->d_noise_desc.alloc(1));
+    HIP_TRY(h->d_noise_gen.alloc(F110_MAX_NOISE_SLOTS));
+    HIP_TRY(hipMemset(h->d_noise_gen.get(), 0, sizeof(NoiseGen) * F110_MAX_NOISE_SLOTS));
+    HIP_TRY(h->d_err.alloc(1));
+    HIP_TRY(hipMemset(h->d_err.get(), 0, sizeof(uint32_t)));
+    HIP_TRY(hipStreamCreateWithFlags(h->noise_stream.put(), hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(h->noise_ev.put(), hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(h->order_ev.put(), hipEventDisableTiming));
     {   // M^j and 1 + M + ... + M^(j-1), j = 0 .. 64 (mod 2^128)
         typedef unsigned __int128 u128h;
         const u128h M = ((u128h)0x2360ED051FC65DA4ull << 64) | (u128h)0x4385DF649FCCF645ull;
         u128h tab[130];
         u128h pw = 1, sm = 0;
         for (int j = 0; j <= 64; j++) { tab[j] = pw; tab[65 + j] = sm; sm = sm * M + 1; pw *= M; }
-        HIP_TRY(hipMalloc((void **)&h->d_pcg_tab, sizeof(tab)));
-        HIP_TRY(hipMemcpy(h->d_pcg_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+        HIP_TRY(h->d_pcg_tab.upload(tab, 130));
     }
     return noise_resize(h, 1, 1); // noise off: one row of zeros
 }
@@ -123,7 +109,7 @@ int noise_init(f110_handle *h)
 static int noise_absorb_pending(f110_handle *h, hipStream_t st)
 {
     if (!h->noise_pending_hi) return F110_OK;
-    HIP_TRY(hipStreamWaitEvent(st, h->noise_ev, 0));
+    HIP_TRY(hipStreamWaitEvent(st, h->noise_ev.get(), 0));
     for (int sl = 0; sl < h->noise_slots; sl++)
         if (h->nslots[sl].kind == 2) h->nslots[sl].T = std::max(h->nslots[sl].T, h->noise_pending_hi);
     h->noise_pending_hi = 0;
@@ -142,18 +128,17 @@ static bool noise_has_generators(const f110_handle *h)
 static int noise_marks_reserve(f110_handle *h, long long rows)
 {
     const long long need = rows / NOISE_MARK_ROWS + 2;
-    if (h->d_marks && h->marks_slots == h->noise_slots && need <= h->marks_cap) return F110_OK;
+    if (h->d_marks.get() && h->marks_slots == h->noise_slots && need <= h->marks_cap) return F110_OK;
     long long cap = std::max<long long>(h->marks_cap, 1 << 12);
     while (cap < need) cap <<= 1;
     HIP_TRY(hipDeviceSynchronize());
-    NoiseMark *nm = nullptr;
-    HIP_TRY(hipMalloc((void **)&nm, sizeof(NoiseMark) * (size_t)cap * (size_t)h->noise_slots));
-    HIP_TRY(hipMemset(nm, 0, sizeof(NoiseMark) * (size_t)cap * (size_t)h->noise_slots));
-    if (h->d_marks && h->marks_cap > 0)
+    DevBuf<NoiseMark> nm;
+    HIP_TRY(nm.alloc((size_t)cap * (size_t)h->noise_slots));
+    HIP_TRY(hipMemset(nm.get(), 0, sizeof(NoiseMark) * (size_t)cap * (size_t)h->noise_slots));
+    if (h->d_marks.get() && h->marks_cap > 0)
         for (int sl = 0; sl < std::min(h->marks_slots, h->noise_slots); sl++)
-            HIP_TRY(hipMemcpy(nm + (size_t)sl * cap, h->d_marks + (size_t)sl * h->marks_cap, sizeof(NoiseMark) * (size_t)h->marks_cap, hipMemcpyDeviceToDevice));
-    if (h->d_marks) (void)hipFree(h->d_marks);
-    h->d_marks = nm; h->marks_cap = cap; h->marks_slots = h->noise_slots;
+            HIP_TRY(hipMemcpy(nm.get() + (size_t)sl * cap, h->d_marks.get() + (size_t)sl * h->marks_cap, sizeof(NoiseMark) * (size_t)h->marks_cap, hipMemcpyDeviceToDevice));
+    h->d_marks = std::move(nm); h->marks_cap = cap; h->marks_slots = h->noise_slots;
     return F110_OK;
 }
 
@@ -168,8 +153,8 @@ static int noise_launch_generator(f110_handle *h, long long r1, hipStream_t st)
     if (rc) return rc;
     NoiseGenArgs g;
     memset(&g, 0, sizeof(g));
-    g.gen = h->d_noise_gen; g.base = h->d_noise; g.mask = h->noise_cap - 1; g.cap = h->noise_cap; g.lo = h->noise_lo;
-    g.nb = h->cfg.num_beams; g.marks = h->d_marks; g.marks_cap = h->marks_cap; g.redo = 0; g.chunk0 = 0; g.pcg_tab = h->d_pcg_tab;
+    g.gen = h->d_noise_gen.get(); g.base = h->d_noise.get(); g.mask = h->noise_cap - 1; g.cap = h->noise_cap; g.lo = h->noise_lo;
+    g.nb = h->cfg.num_beams; g.marks = h->d_marks.get(); g.marks_cap = h->marks_cap; g.redo = 0; g.chunk0 = 0; g.pcg_tab = h->d_pcg_tab.get();
     for (long long r = (have / NOISE_MARK_ROWS + 1) * NOISE_MARK_ROWS; ; r += NOISE_MARK_ROWS) {
         g.r1 = std::min(r, r1);
         hipLaunchKernelGGL(noise_rows_kernel, dim3(h->noise_slots), dim3(64), 0, st, g);
@@ -186,8 +171,8 @@ static int noise_redo_rows(f110_handle *h, long long lo, long long hi, hipStream
     if (hi <= lo) return F110_OK;
     NoiseGenArgs g;
     memset(&g, 0, sizeof(g));
-    g.gen = h->d_noise_gen; g.base = h->d_noise; g.mask = h->noise_cap - 1; g.cap = h->noise_cap; g.lo = lo; g.r1 = hi;
-    g.nb = h->cfg.num_beams; g.marks = h->d_marks; g.marks_cap = h->marks_cap; g.redo = 1; g.chunk0 = lo / NOISE_MARK_ROWS; g.pcg_tab = h->d_pcg_tab;
+    g.gen = h->d_noise_gen.get(); g.base = h->d_noise.get(); g.mask = h->noise_cap - 1; g.cap = h->noise_cap; g.lo = lo; g.r1 = hi;
+    g.nb = h->cfg.num_beams; g.marks = h->d_marks.get(); g.marks_cap = h->marks_cap; g.redo = 1; g.chunk0 = lo / NOISE_MARK_ROWS; g.pcg_tab = h->d_pcg_tab.get();
     const long long chunks = (hi + NOISE_MARK_ROWS - 1) / NOISE_MARK_ROWS - g.chunk0;
     for (long long c0 = 0; c0 < chunks; c0 += 32768) { // (grid.y <= 65535)
         NoiseGenArgs gg = g;
@@ -201,14 +186,14 @@ static int noise_redo_rows(f110_handle *h, long long lo, long long hi, hipStream
 // every generator slot restarts at row 0 (its seed state); rows below the floor will be skipped, not stored
 static int noise_restart_generators(f110_handle *h)
 {
-    HIP_TRY(hipStreamSynchronize(h->noise_stream));
+    HIP_TRY(hipStreamSynchronize(h->noise_stream.get()));
     h->noise_pending_hi = 0;
     HIP_TRY(hipDeviceSynchronize());
     for (int sl = 0; sl < h->noise_slots; sl++) {
         auto &ns = h->nslots[sl];
         if (ns.kind != 2) continue;
         ns.T = 0;
-        HIP_TRY(hipMemcpy(h->d_noise_gen + sl, &ns.seed, sizeof(NoiseGen), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h->d_noise_gen.get() + sl, &ns.seed, sizeof(NoiseGen), hipMemcpyHostToDevice));
     }
     noise_recompute_hi(h);
     return F110_OK;
@@ -238,11 +223,11 @@ extern "C" int f110_set_noise_slot(f110_handle *h, int32_t slot, const double *t
     ON_DEVICE(h->cfg.device);
     const int nb = h->cfg.num_beams;
     if (h->noise_lo > 0) { h->noise_lo = 0; if ((rc = noise_restart_generators(h))) return rc; } // host-fed rows start at 0
-    HIP_TRY(hipStreamSynchronize(h->noise_stream));
+    HIP_TRY(hipStreamSynchronize(h->noise_stream.get()));
     HIP_TRY(hipDeviceSynchronize());
     auto &ns = h->nslots[slot];
     ns.kind = 1;
-    HIP_TRY(hipMemset(h->d_noise_gen + slot, 0, sizeof(NoiseGen))); // (the slot may have held a generator)
+    HIP_TRY(hipMemset(h->d_noise_gen.get() + slot, 0, sizeof(NoiseGen))); // (the slot may have held a generator)
     ns.rows.assign(tbl, tbl + (size_t)T * nb);
     ns.T = T;
     const int slots = std::max(h->noise_slots, slot + 1);
@@ -254,13 +239,11 @@ extern "C" int f110_set_noise_slot(f110_handle *h, int32_t slot, const double *t
         if ((rc = noise_resize(h, slots, std::max(cap, (long long)2)))) return rc;
     }
     {   // stage the rows on the device and place them in the slot's ring
-        DevTemp tmp;
-        double *stage = nullptr;
-        HIP_TRY(tmp.alloc(&stage, (size_t)T * nb));
-        HIP_TRY(hipMemcpy(stage, tbl, (size_t)T * nb * sizeof(double), hipMemcpyHostToDevice));
+        DevBuf<double> stage;
+        HIP_TRY(stage.upload(tbl, (size_t)T * nb));
         const long long items = (long long)T * nb;
-        hipLaunchKernelGGL(noise_fill_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, nullptr, (const double *)stage,
-                           (long long)T, nb, h->d_noise, slot, h->noise_cap, h->noise_cap - 1);
+        hipLaunchKernelGGL(noise_fill_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, nullptr, (const double *)stage.get(),
+                           (long long)T, nb, h->d_noise.get(), slot, h->noise_cap, h->noise_cap - 1);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
     }
@@ -276,11 +259,11 @@ extern "C" int f110_set_noise_table(f110_handle *h, const double *tbl, int64_t T
     // noise off: every slot forgets its table / generator
     ON_DEVICE(h->cfg.device);
     leave_per_env_noise(h);
-    HIP_TRY(hipStreamSynchronize(h->noise_stream));
+    HIP_TRY(hipStreamSynchronize(h->noise_stream.get()));
     h->noise_pending_hi = 0;
     for (auto &ns : h->nslots) { ns.kind = 0; ns.rows.clear(); ns.rows.shrink_to_fit(); ns.T = 0; }
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(h->d_noise_gen, 0, sizeof(NoiseGen) * F110_MAX_NOISE_SLOTS));
+    HIP_TRY(hipMemset(h->d_noise_gen.get(), 0, sizeof(NoiseGen) * F110_MAX_NOISE_SLOTS));
     h->noise_on = false; h->noise_lo = 0; h->noise_hi = 0;
     if (h->multi_noise) { h->multi_noise = false; h->epoch++; }
     return noise_resize(h, 1, 1);
@@ -294,7 +277,7 @@ extern "C" int f110_set_noise_generator(f110_handle *h, int32_t slot, const uint
     if (!(pcg64[2] & 1ull)) return fail(F110_E_INVALID, "f110_set_noise_generator: the PCG64 increment must be odd");
     ON_DEVICE(h->cfg.device);
     leave_per_env_noise(h);
-    HIP_TRY(hipStreamSynchronize(h->noise_stream));
+    HIP_TRY(hipStreamSynchronize(h->noise_stream.get()));
     HIP_TRY(hipDeviceSynchronize());
     auto &ns = h->nslots[slot];
     ns.kind = 2;
@@ -344,20 +327,23 @@ extern "C" int f110_set_noise_per_env(f110_handle *h, const uint64_t *pcg64, dou
         g.std = std_dev; g.rows = 0; g.on = 1;
     }
     ON_DEVICE(h->cfg.device);
-    HIP_TRY(hipStreamSynchronize(h->noise_stream));
+    HIP_TRY(hipStreamSynchronize(h->noise_stream.get()));
     HIP_TRY(hipDeviceSynchronize());
-    if (!h->d_env_gen) {
-        HIP_TRY(hipMalloc((void **)&h->d_env_gen, sizeof(NoiseGen) * (size_t)B));
-        HIP_TRY(hipMalloc((void **)&h->d_env_seed, sizeof(NoiseGen) * (size_t)B));
-        HIP_TRY(hipMalloc((void **)&h->d_env_rows, sizeof(double) * (size_t)B * nb));
-        HIP_TRY(hipMalloc((void **)&h->d_env_ident, sizeof(int32_t) * (size_t)B));
+    if (!h->d_env_gen.get()) { // all four buffers, or none
+        DevBuf<NoiseGen> gen, seed;
+        DevBuf<double> rows;
+        DevBuf<int32_t> ident;
         std::vector<int32_t> id((size_t)B);
         for (int e = 0; e < B; e++) id[(size_t)e] = e;
-        HIP_TRY(hipMemcpy(h->d_env_ident, id.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice));
+        HIP_TRY(gen.alloc((size_t)B));
+        HIP_TRY(seed.alloc((size_t)B));
+        HIP_TRY(rows.alloc((size_t)B * nb));
+        HIP_TRY(ident.upload(id.data(), (size_t)B));
+        h->d_env_gen = std::move(gen); h->d_env_seed = std::move(seed); h->d_env_rows = std::move(rows); h->d_env_ident = std::move(ident);
     }
-    HIP_TRY(hipMemcpy(h->d_env_seed, seeds.data(), sizeof(NoiseGen) * (size_t)B, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_env_gen, seeds.data(), sizeof(NoiseGen) * (size_t)B, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(h->d_env_rows, 0, sizeof(double) * (size_t)B * nb));
+    HIP_TRY(hipMemcpy(h->d_env_seed.get(), seeds.data(), sizeof(NoiseGen) * (size_t)B, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_env_gen.get(), seeds.data(), sizeof(NoiseGen) * (size_t)B, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(h->d_env_rows.get(), 0, sizeof(double) * (size_t)B * nb));
     h->per_env_noise = true;
     h->noise_on = true;
     h->epoch++;
@@ -379,9 +365,9 @@ extern "C" int f110_noise_prefetch(f110_handle *h, int64_t rows)
     // The generator appends rows have .. r1-1 into ring places whose previous tenants lie below the floor.  Steps that were
     // enqueued BEFORE the floor was raised may still read those tenants, and a generator kernel enqueued on the caller's
     // stream (f110_noise_ensure) works on the same generator states: both recorded `order_ev` there, and this launch waits for it.
-    if (h->order_ev_set) { HIP_TRY(hipStreamWaitEvent(h->noise_stream, h->order_ev, 0)); h->order_ev_set = false; }
-    if (int rc = noise_launch_generator(h, r1, h->noise_stream)) return rc;
-    HIP_TRY(hipEventRecord(h->noise_ev, h->noise_stream));
+    if (h->order_ev_set) { HIP_TRY(hipStreamWaitEvent(h->noise_stream.get(), h->order_ev.get(), 0)); h->order_ev_set = false; }
+    if (int rc = noise_launch_generator(h, r1, h->noise_stream.get())) return rc;
+    HIP_TRY(hipEventRecord(h->noise_ev.get(), h->noise_stream.get()));
     h->noise_pending_hi = r1;
     return F110_OK;
 }
@@ -392,7 +378,6 @@ extern "C" int f110_noise_ensure(f110_handle *h, int64_t rows, void *stream)
     if (h->per_env_noise || !h->noise_on || rows <= h->noise_hi) return F110_OK; // (per-env rows are produced by the step itself)
     if (int rc = check_device(h, "f110_noise_ensure")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    noise_reap(h, false);
     int rc = noise_absorb_pending(h, st);
     if (rc) return rc;
     if (rows <= h->noise_hi) return F110_OK;
@@ -408,7 +393,7 @@ extern "C" int f110_noise_ensure(f110_handle *h, int64_t rows, void *stream)
         if (h->nslots[sl].kind == 2) h->nslots[sl].T = r1;
     noise_recompute_hi(h);
     if ((rc = noise_publish(h, st))) return rc;
-    HIP_TRY(hipEventRecord(h->order_ev, st)); // the next prefetch (side stream) runs behind this generator launch
+    HIP_TRY(hipEventRecord(h->order_ev.get(), st)); // the next prefetch (side stream) runs behind this generator launch
     h->order_ev_set = true;
     return F110_OK;
 }
@@ -425,7 +410,7 @@ extern "C" int f110_noise_set_floor(f110_handle *h, int64_t lo, void *stream)
         h->noise_lo = lo;
         if (int rc = noise_publish(h, (hipStream_t)stream)) return rc;
         // the steps enqueued so far may read rows below the new floor: the prefetch that recycles their places waits for them
-        HIP_TRY(hipEventRecord(h->order_ev, (hipStream_t)stream));
+        HIP_TRY(hipEventRecord(h->order_ev.get(), (hipStream_t)stream));
         h->order_ev_set = true;
         return F110_OK;
     }
@@ -442,7 +427,7 @@ extern "C" int f110_noise_set_floor(f110_handle *h, int64_t lo, void *stream)
     h->noise_lo = lo;
     if ((rc = noise_redo_rows(h, lo, std::min(old_lo, h->noise_hi), st))) return rc;
     if ((rc = noise_publish(h, st))) return rc;
-    HIP_TRY(hipEventRecord(h->order_ev, st));
+    HIP_TRY(hipEventRecord(h->order_ev.get(), st));
     h->order_ev_set = true;
     return F110_OK;
 }
@@ -454,11 +439,7 @@ extern "C" int f110_noise_info(f110_handle *h, int64_t *lo, int64_t *hi, int64_t
     if (hi) *hi = h->noise_on ? h->noise_hi : 0; // (rows a prefetch is still producing are not counted: f110_noise_ensure makes them readable)
     if (cap) *cap = h->noise_cap;
     if (slots) *slots = h->noise_slots;
-    if (bytes) {
-        long long b = (long long)h->noise_slots * h->noise_cap * h->cfg.num_beams * (long long)sizeof(double);
-        noise_reap(h, false);
-        *bytes = b * (1 + (long long)h->retired.size());
-    }
+    if (bytes) *bytes = (long long)h->noise_slots * h->noise_cap * h->cfg.num_beams * (long long)sizeof(double);
     return F110_OK;
 }
 
@@ -468,7 +449,7 @@ extern "C" int f110_noise_read(f110_handle *h, int32_t slot, int64_t row0, int64
     if (rc) return rc;
     if (!out || n_rows < 0) return fail(F110_E_INVALID, "f110_noise_read: bad arguments");
     ON_DEVICE(h->cfg.device);
-    HIP_TRY(hipStreamSynchronize(h->noise_stream));
+    HIP_TRY(hipStreamSynchronize(h->noise_stream.get()));
     HIP_TRY(hipDeviceSynchronize());
     const long long hi = h->noise_on ? std::max(h->noise_hi, h->noise_pending_hi) : 0;
     if (slot >= h->noise_slots || row0 < h->noise_lo || row0 + n_rows > hi)
@@ -476,7 +457,7 @@ extern "C" int f110_noise_read(f110_handle *h, int32_t slot, int64_t row0, int64
                     (long long)(row0 + n_rows - 1), slot, h->noise_lo, hi - 1, h->noise_slots);
     const int nb = h->cfg.num_beams;
     for (long long r = row0; r < row0 + n_rows; r++)
-        HIP_TRY(hipMemcpy(out + (size_t)(r - row0) * nb, h->d_noise + ((size_t)slot * h->noise_cap + (size_t)(r & (h->noise_cap - 1))) * nb,
+        HIP_TRY(hipMemcpy(out + (size_t)(r - row0) * nb, h->d_noise.get() + ((size_t)slot * h->noise_cap + (size_t)(r & (h->noise_cap - 1))) * nb,
                           (size_t)nb * sizeof(double), hipMemcpyDeviceToHost));
     return F110_OK;
 }
@@ -497,8 +478,7 @@ extern "C" int f110_assign_noise(f110_handle *h, const int32_t *slot_of_env)
         }
     ON_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize());
-    if (!h->d_env_noise) HIP_TRY(hipMalloc((void **)&h->d_env_noise, sizeof(int32_t) * B));
-    HIP_TRY(hipMemcpy(h->d_env_noise, m.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice));
+    HIP_TRY(h->d_env_noise.upload(m.data(), B));
     h->multi_noise = multi;
     h->epoch++;
     return F110_OK;

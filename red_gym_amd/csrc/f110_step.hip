@@ -43,7 +43,7 @@ static ScanDev scan_dev(const f110_handle *h)
 {
     ScanDev s;
     s.nb = h->cfg.num_beams; s.theta_dis = h->cfg.theta_dis; s.fov = h->cfg.fov; s.eps = h->cfg.eps;
-    s.max_range = h->cfg.max_range; s.inc = h->theta_inc; s.inc_fx = (unsigned long long)std::llround(h->theta_inc * 1099511627776.0); s.cs_len = h->cs_len; s.cs = h->d_cs;
+    s.max_range = h->cfg.max_range; s.inc = h->theta_inc; s.inc_fx = (unsigned long long)std::llround(h->theta_inc * 1099511627776.0); s.cs_len = (int)h->d_cs.size(); s.cs = h->d_cs.get();
     return s;
 }
 
@@ -196,16 +196,16 @@ static void fill_scan_args(const f110_handle *h, ScanArgs &s, int reset_only)
 {
     const f110_config &c = h->cfg;
     const f110_buffers &b = h->bufs;
-    s.maps = h->d_maps; s.env_map = h->multi ? h->d_env_map : nullptr; s.scan = scan_dev(h); s.n_cars = c.num_envs * c.num_agents; s.agents = c.num_agents;
+    s.maps = h->d_maps.get(); s.env_map = h->multi ? h->d_env_map.get() : nullptr; s.scan = scan_dev(h); s.n_cars = c.num_envs * c.num_agents; s.agents = c.num_agents;
     s.pose_src = b.state; s.pose_stride = 7; s.yaw_off = 4;
-    s.state = b.state; s.noise_step = b.noise_step; s.chunk_beam0 = h->d_chunk0;
-    s.side = h->d_side; s.side_max = h->side_max;
-    s.noise_base = h->d_noise; s.noise_cap = (int)h->noise_cap; s.noise_mask = (int)(h->noise_cap - 1); s.noise_slots = h->noise_slots;
-    s.env_noise = h->multi_noise ? h->d_env_noise : nullptr; s.dev_err = h->d_err;
+    s.state = b.state; s.noise_step = b.noise_step; s.chunk_beam0 = h->d_chunk0.get();
+    s.side = h->d_side.get(); s.side_max = h->side_max;
+    s.noise_base = h->d_noise.get(); s.noise_cap = (int)h->noise_cap; s.noise_mask = (int)(h->noise_cap - 1); s.noise_slots = h->noise_slots;
+    s.env_noise = h->multi_noise ? h->d_env_noise.get() : nullptr; s.dev_err = h->d_err.get();
     s.order = (h->scan_order && !h->multi) ? h->scan_order : nullptr; // (a workgroup stages one LUT: car order when maps differ)
     s.wg_single = h->multi && h->wg_single; s.n_maps = F110_MAX_MAPS;
-    if (h->per_env_noise) { s.noise_base = h->d_env_rows; s.noise_cap = 1; s.noise_mask = 0; s.noise_slots = c.num_envs; s.env_noise = h->d_env_ident; }
-    s.beam_cosines = h->d_beam_cosines; s.ttc_thresh = c.ttc_thresh;
+    if (h->per_env_noise) { s.noise_base = h->d_env_rows.get(); s.noise_cap = 1; s.noise_mask = 0; s.noise_slots = c.num_envs; s.env_noise = h->d_env_ident.get(); }
+    s.beam_cosines = h->d_beam_cosines.get(); s.ttc_thresh = c.ttc_thresh;
     s.in_collision = b.in_collision; s.pending_reset = b.pending_reset; s.reset_only = reset_only;
     s.out_f32 = b.scans; s.out_f64 = b.scans_f64; s.lookups = b.lookups;
 }
@@ -228,15 +228,15 @@ static int run_step(f110_handle *h, const double *actions, int reset_only, const
     const f110_buffers &b = h->bufs;
     const int N = c.num_envs * c.num_agents;
     const bool prof = h->prof_on && !st.record && (h->prof_seq++ % h->prof_every) == h->prof_every / 2 && (size_t)(2 * h->prof_n + 1) < h->prof_ev.size();
-    hipEvent_t ev0 = prof ? h->prof_ev[2 * h->prof_n] : nullptr, ev1 = prof ? h->prof_ev[2 * h->prof_n + 1] : nullptr;
+    hipEvent_t ev0 = prof ? h->prof_ev[2 * h->prof_n].get() : nullptr, ev1 = prof ? h->prof_ev[2 * h->prof_n + 1].get() : nullptr;
     int rc;
 
     if (h->per_env_noise) {
         // the row every env's scan is about to add (row `pending ? 0 : noise_step`), from the env's own generator
         NoiseGenArgs g;
         memset(&g, 0, sizeof(g));
-        g.gen = h->d_env_gen; g.seeds = h->d_env_seed; g.base = h->d_env_rows; g.mask = 0; g.cap = 1; g.nb = c.num_beams;
-        g.pcg_tab = h->d_pcg_tab; g.env_row = b.noise_step; g.env_row_stride = c.num_agents; g.n_env = c.num_envs;
+        g.gen = h->d_env_gen.get(); g.seeds = h->d_env_seed.get(); g.base = h->d_env_rows.get(); g.mask = 0; g.cap = 1; g.nb = c.num_beams;
+        g.pcg_tab = h->d_pcg_tab.get(); g.env_row = b.noise_step; g.env_row_stride = c.num_agents; g.n_env = c.num_envs;
         g.reset_only = reset_only; g.env_pending = b.pending_reset;
         if ((rc = emit(st, (const void *)&noise_rows_kernel, dim3((c.num_envs + 3) / 4), dim3(256), 0, g))) return rc;
     }
@@ -244,7 +244,7 @@ static int run_step(f110_handle *h, const double *actions, int reset_only, const
         DynArgs d;
         d.n_cars = N; d.agents = c.num_agents; d.state = b.state; d.steer_buf = b.steer_buf; d.steer_cnt = b.steer_cnt;
         d.noise_step = b.noise_step; d.actions = actions; d.spawn = b.spawn; d.pending_reset = b.pending_reset;
-        d.was_pending = h->d_was_pending; d.reset_only = reset_only; d.pose_snap = b.pose_snap; d.in_collision = b.in_collision; d.params = h->d_params; d.env_params = h->multi_params ? h->d_env_params : nullptr; d.param_slots = h->param_slots; d.dev_err = h->d_err; d.noise = h->d_noise_desc;
+        d.was_pending = h->d_was_pending.get(); d.reset_only = reset_only; d.pose_snap = b.pose_snap; d.in_collision = b.in_collision; d.params = h->d_params.get(); d.env_params = h->multi_params ? h->d_env_params.get() : nullptr; d.param_slots = h->param_slots; d.dev_err = h->d_err.get(); d.noise = h->d_noise_desc.get();
         d.time_step = c.timestep; d.integrator = c.integrator;
         if ((rc = emit(st, (const void *)&dynamics_kernel, dim3((N + 255) / 256), dim3(256), 0, d))) return rc;
     }
@@ -282,7 +282,7 @@ static int run_step(f110_handle *h, const double *actions, int reset_only, const
     e.in_collision = b.in_collision; e.collisions = b.collisions; e.collision_idx = b.collision_idx;
     e.start_rot = b.start_rot; e.near_start = b.near_start; e.toggles = b.toggles; e.lap_counts = b.lap_counts;
     e.lap_times = b.lap_times; e.current_time = b.current_time; e.pending_reset = b.pending_reset; e.done = b.done; e.checkpoint_done = b.checkpoint_done;
-    e.time_step = c.timestep; e.params = h->d_params; e.env_params = h->multi_params ? h->d_env_params : nullptr; e.param_slots = h->param_slots; e.dev_err = h->d_err;
+    e.time_step = c.timestep; e.params = h->d_params.get(); e.env_params = h->multi_params ? h->d_env_params.get() : nullptr; e.param_slots = h->param_slots; e.dev_err = h->d_err.get();
     const int env_blocks = (c.num_envs + 127) / 128;
     if (c.num_agents == 1) return emit(st, (const void *)&env_kernel<true>, dim3(env_blocks), dim3(128), 0, e);
 
@@ -292,9 +292,9 @@ static int run_step(f110_handle *h, const double *actions, int reset_only, const
     ps.e = e; ps.env_blocks = env_blocks;
     OppArgs &o = ps.o;
     o.n_cars = N; o.agents = c.num_agents; o.nb = c.num_beams; o.state = b.state; o.pose_snap = b.pose_snap;
-    o.in_collision = b.in_collision; o.scan_angles = h->d_scan_angles; o.beam_cs = h->d_beam_cs; o.params = h->d_params; o.env_params = h->multi_params ? h->d_env_params : nullptr;
-    o.pending_reset = h->d_was_pending; o.reset_only = reset_only; o.scans32 = b.scans; o.scans64 = b.scans_f64;
-    o.pairs = h->d_opp_pairs; o.param_slots = h->param_slots; o.dev_err = h->d_err;
+    o.in_collision = b.in_collision; o.scan_angles = h->d_scan_angles.get(); o.beam_cs = h->d_beam_cs.get(); o.params = h->d_params.get(); o.env_params = h->multi_params ? h->d_env_params.get() : nullptr;
+    o.pending_reset = h->d_was_pending.get(); o.reset_only = reset_only; o.scans32 = b.scans; o.scans64 = b.scans_f64;
+    o.pairs = h->d_opp_pairs.get(); o.param_slots = h->param_slots; o.dev_err = h->d_err.get();
     const int npairs = N * (c.num_agents - 1);
     if ((rc = emit(st, (const void *)&post_scan_kernel, dim3(env_blocks + (4 * npairs + 127) / 128), dim3(128), 0, ps))) return rc; // four lanes per pair
     return emit(st, (const void *)&opp_apply_kernel, dim3((int)(((long long)OPP_GROUP * N + 255) / 256)), dim3(256), 0, ps.o); // OPP_GROUP lanes per car
@@ -376,9 +376,9 @@ extern "C" int f110_pack_env(f110_handle *h, int32_t env, double *out_dev, void 
 // ---------------------------------------------------------------- the step as a HIP graph built by the library
 struct f110_graph {
     f110_handle *h = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipStream_t cap = nullptr;
+    Stream cap;                         // (members are destroyed in reverse order: the executable first, this stream last)
+    Graph graph;
+    GraphExec exec;
     int64_t epoch = 0;
     int nodes = 0;
     std::vector<KernelLaunch> launches; // node argument blocks must outlive hipGraphAddKernelNode only, kept for clarity
@@ -388,9 +388,6 @@ extern "C" void f110_graph_destroy(f110_graph *g)
 {
     if (!g) return;
     DeviceScope on_dev(g->h ? g->h->cfg.device : 0);
-    if (g->exec) (void)hipGraphExecDestroy(g->exec);
-    if (g->graph) (void)hipGraphDestroy(g->graph);
-    if (g->cap) (void)hipStreamDestroy(g->cap);
     delete g;
 }
 
@@ -410,7 +407,7 @@ extern "C" int f110_graph_create(f110_handle *h, const double *actions, int32_t 
     if (how == F110_GRAPH_NODES) {
         rc = run_step(h, actions, 0, make_sink(h, nullptr, &g->launches));
         if (!rc) {
-            e = hipGraphCreate(&g->graph, 0);
+            e = hipGraphCreate(g->graph.put(), 0);
             hipGraphNode_t prev = nullptr;
             for (size_t i = 0; e == hipSuccess && i < g->launches.size(); i++) {
                 KernelLaunch &l = g->launches[i];
@@ -420,23 +417,23 @@ extern "C" int f110_graph_create(f110_handle *h, const double *actions, int32_t 
                 np.func = const_cast<void *>(l.func); np.gridDim = l.grid; np.blockDim = l.block; np.sharedMemBytes = l.shmem;
                 np.kernelParams = params; np.extra = nullptr;
                 hipGraphNode_t node = nullptr;
-                e = hipGraphAddKernelNode(&node, g->graph, prev ? &prev : nullptr, prev ? 1 : 0, &np); // a chain: each kernel reads what the one before wrote
+                e = hipGraphAddKernelNode(&node, g->graph.get(), prev ? &prev : nullptr, prev ? 1 : 0, &np); // a chain: each kernel reads what the one before wrote
                 prev = node;
             }
             g->nodes = (int)g->launches.size();
         }
     } else {
-        e = hipStreamCreateWithFlags(&g->cap, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipStreamBeginCapture(g->cap, hipStreamCaptureModeThreadLocal);
+        e = hipStreamCreateWithFlags(g->cap.put(), hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamBeginCapture(g->cap.get(), hipStreamCaptureModeThreadLocal);
         if (e == hipSuccess) {
-            rc = run_step(h, actions, 0, make_sink(h, g->cap));
-            e = hipStreamEndCapture(g->cap, &g->graph);
+            rc = run_step(h, actions, 0, make_sink(h, g->cap.get()));
+            e = hipStreamEndCapture(g->cap.get(), g->graph.put());
             size_t n = 0;
-            if (e == hipSuccess && hipGraphGetNodes(g->graph, nullptr, &n) == hipSuccess) g->nodes = (int)n;
+            if (e == hipSuccess && hipGraphGetNodes(g->graph.get(), nullptr, &n) == hipSuccess) g->nodes = (int)n;
         }
     }
     h->prof_on = prof;
-    if (!rc && e == hipSuccess) e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
+    if (!rc && e == hipSuccess) e = hipGraphInstantiate(g->exec.put(), g->graph.get(), nullptr, nullptr, 0);
     if (rc || e != hipSuccess) {
         if (!rc) rc = fail(F110_E_HIP, "f110_graph_create: %s", hipGetErrorString(e));
         f110_graph_destroy(g);
@@ -448,13 +445,13 @@ extern "C" int f110_graph_create(f110_handle *h, const double *actions, int32_t 
 
 extern "C" int f110_graph_launch(f110_graph *g, void *stream)
 {
-    if (!g || !g->exec) return fail(F110_E_INVALID, "f110_graph_launch: null graph");
+    if (!g || !g->exec.get()) return fail(F110_E_INVALID, "f110_graph_launch: null graph");
     if (g->epoch != g->h->epoch)
         return fail(F110_E_INVALID, "f110_graph_launch: the graph is stale (a table, map, binding or launch setting of the handle "
                                     "changed since f110_graph_create: f110_launch_epoch moved from %lld to %lld); create it again",
                     (long long)g->epoch, (long long)g->h->epoch);
     if (int rc = check_device(g->h, "f110_graph_launch")) return rc;
-    HIP_TRY(hipGraphLaunch(g->exec, (hipStream_t)stream));
+    HIP_TRY(hipGraphLaunch(g->exec.get(), (hipStream_t)stream));
     return F110_OK;
 }
 
@@ -462,7 +459,7 @@ extern "C" int f110_graph_info(f110_graph *g, int32_t *nodes, const char *dot_pa
 {
     if (!g) return fail(F110_E_INVALID, "f110_graph_info: null graph");
     if (nodes) *nodes = g->nodes;
-    if (dot_path && *dot_path) HIP_TRY(hipGraphDebugDotPrint(g->graph, dot_path, 0));
+    if (dot_path && *dot_path) HIP_TRY(hipGraphDebugDotPrint(g->graph.get(), dot_path, 0));
     return F110_OK;
 }
 
@@ -502,7 +499,6 @@ extern "C" int f110_launch_epoch(f110_handle *h, int64_t *epoch)
 // ---------------------------------------------------------------- measurement aid
 static void prof_clear(f110_handle *h)
 {
-    for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
     h->prof_ev.clear();
     h->prof_n = 0;
     h->prof_on = false;
@@ -522,7 +518,7 @@ extern "C" int f110_profile_begin(f110_handle *h, int32_t max_launches)
     prof_clear(h);
     h->prof_seq = 0;
     h->prof_ev.resize((size_t)2 * max_launches);
-    for (auto &e : h->prof_ev) HIP_TRY(hipEventCreate(&e));
+    for (auto &e : h->prof_ev) HIP_TRY(hipEventCreate(e.put()));
     h->prof_on = true;
     return F110_OK;
 }
@@ -532,10 +528,10 @@ extern "C" int f110_profile_end(f110_handle *h, double *ms_total, int32_t *launc
     if (!h || !ms_total || !launches) return fail(F110_E_INVALID, "f110_profile_end: null argument");
     if (!h->prof_on) return fail(F110_E_INVALID, "f110_profile_end: f110_profile_begin has not been called");
     double tot = 0;
-    if (h->prof_n > 0) HIP_TRY(hipEventSynchronize(h->prof_ev[2 * h->prof_n - 1]));
+    if (h->prof_n > 0) HIP_TRY(hipEventSynchronize(h->prof_ev[2 * h->prof_n - 1].get()));
     for (int i = 0; i < h->prof_n; i++) {
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, h->prof_ev[2 * i], h->prof_ev[2 * i + 1]));
+        HIP_TRY(hipEventElapsedTime(&ms, h->prof_ev[2 * i].get(), h->prof_ev[2 * i + 1].get()));
         tot += ms;
     }
     *ms_total = tot;
@@ -555,9 +551,9 @@ extern "C" int f110_scan(f110_handle *h, const double *poses, int32_t n, double 
     if (int rc = check_device(h, "f110_scan")) return rc;
     ScanArgs s;
     memset(&s, 0, sizeof(s));
-    s.maps = h->d_maps; s.n_maps = F110_MAX_MAPS; s.scan = scan_dev(h); s.n_cars = n; s.agents = 1;
+    s.maps = h->d_maps.get(); s.n_maps = F110_MAX_MAPS; s.scan = scan_dev(h); s.n_cars = n; s.agents = 1;
     s.pose_src = poses; s.pose_stride = 3; s.yaw_off = 2;
-    s.out_f32 = out32; s.out_f64 = out64; s.lookups = lookups; s.chunk_beam0 = h->d_chunk0;
+    s.out_f32 = out32; s.out_f64 = out64; s.lookups = lookups; s.chunk_beam0 = h->d_chunk0.get();
     Sink k;
     k.st = (hipStream_t)stream;
     return launch_scan(h, s, k);
@@ -573,7 +569,7 @@ extern "C" int f110_update_pose(f110_handle *h, double *state, double *steer_buf
     DynArgs d;
     memset(&d, 0, sizeof(d));
     d.n_cars = n; d.agents = 1; d.state = state; d.steer_buf = steer_buf; d.steer_cnt = steer_cnt; d.actions = actions;
-    d.params = h->d_params; d.param_slots = h->param_slots; d.dev_err = h->d_err; d.time_step = h->cfg.timestep; d.integrator = h->cfg.integrator;
+    d.params = h->d_params.get(); d.param_slots = h->param_slots; d.dev_err = h->d_err.get(); d.time_step = h->cfg.timestep; d.integrator = h->cfg.integrator;
     hipLaunchKernelGGL(dynamics_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d);
     HIP_TRY(hipGetLastError());
     return F110_OK;
@@ -586,7 +582,7 @@ extern "C" int f110_vehicle_dynamics(f110_handle *h, const double *x, const doub
     if (!h || !x || !u || !f || n < 0) return fail(F110_E_INVALID, "f110_vehicle_dynamics: bad arguments");
     if (int rc = check_device(h, "f110_vehicle_dynamics")) return rc;
     hipLaunchKernelGGL(rhs_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, u, n, kinematic,
-                       h->d_params, f);
+                       h->d_params.get(), f);
     HIP_TRY(hipGetLastError());
     return F110_OK;
 }
@@ -631,7 +627,7 @@ extern "C" int f110_check_ttc(f110_handle *h, const double *scans, const double 
     if (!h || !scans || !vel || !hit || n < 0) return fail(F110_E_INVALID, "f110_check_ttc: bad arguments");
     if (int rc = check_device(h, "f110_check_ttc")) return rc;
     hipLaunchKernelGGL(ttc_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, scans, vel, n, h->cfg.num_beams,
-                       h->d_beam_cosines, h->d_side, h->cfg.ttc_thresh, hit);
+                       h->d_beam_cosines.get(), h->d_side.get(), h->cfg.ttc_thresh, hit);
     HIP_TRY(hipGetLastError());
     return F110_OK;
 }
@@ -643,7 +639,7 @@ extern "C" int f110_ray_cast(f110_handle *h, const double *ego, const double *ve
     if (!h || !ego || !verts || !scans || n < 0) return fail(F110_E_INVALID, "f110_ray_cast: bad arguments");
     if (int rc = check_device(h, "f110_ray_cast")) return rc;
     hipLaunchKernelGGL(ray_cast_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, ego, verts, n,
-                       h->cfg.num_beams, h->d_scan_angles, h->d_beam_cs, scans, span);
+                       h->cfg.num_beams, h->d_scan_angles.get(), h->d_beam_cs.get(), scans, span);
     HIP_TRY(hipGetLastError());
     return F110_OK;
 }

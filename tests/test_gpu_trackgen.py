@@ -221,6 +221,58 @@ def test_map_slots_give_env_blocks_their_own_map():
         e.close()
 
 
+def test_reinstalled_maps_replace_assigned_slots_whole():
+    """Maps installed again into slots that envs are assigned to -- slot 0 from a distance table (f110_set_map_dt), slot K from
+    an occupancy mask (f110_set_map_slot_occupancy), twice after the first fill, the map sizes changing each time -- are taken
+    over whole: after every install each block scans and collides exactly like a fresh single-map env on its map."""
+    from red_gym_amd import F110VecEnv, workload, maps
+    from red_gym_amd.engine import edt_squared
+    B, K = 64, 5
+    ex = maps.load_map(workload.EXAMPLE_MAP + '.yaml', '.png')
+    berlin = maps.load_map(maps.builtin_map_yaml('berlin'), '.png')
+    skirk = maps.load_map(maps.builtin_map_yaml('skirk'), '.png')
+
+    def dt_spec(m, theta=0.0):
+        dt = m.resolution * np.sqrt(edt_squared(m.free).astype(np.float64))
+        return (dt, m.resolution, m.orig_x, m.orig_y, float(np.cos(theta)), float(np.sin(theta)))
+
+    def occ_spec(m, free=None, theta=0.0):
+        return (m.free if free is None else free, m.resolution, m.orig_x, m.orig_y, theta)
+
+    rounds = [(dt_spec(berlin), occ_spec(ex)),
+              (dt_spec(ex, theta=0.3), occ_spec(skirk)),
+              (dt_spec(skirk), occ_spec(ex, ex.free[200:-300, 100:-250], theta=0.3))]
+    multi = F110VecEnv(B, map=workload.EXAMPLE_MAP, num_agents=1)
+    assign = np.where(np.arange(B) < B // 2, 0, K)
+    rng = np.random.default_rng(2)
+    poses = np.zeros((B, 1, 3))
+    poses[:, 0, :2] = rng.uniform(-3, 3, (B, 2))
+    poses[:, 0, 2] = rng.uniform(-3, 3, B)
+    acts = workload.action_pool(3, B, 1)
+    for r, (spec0, spec_k) in enumerate(rounds):
+        multi.eng.set_map_dt(*spec0)
+        multi.eng.set_map_occupancy(*spec_k, slot=K)
+        if r == 0:
+            multi.eng.assign_maps(assign)
+        singles = [F110VecEnv(B, map=workload.EXAMPLE_MAP, num_agents=1) for _ in range(2)]
+        singles[0].eng.set_map_dt(*spec0)
+        singles[1].eng.set_map_occupancy(*spec_k)
+        om = multi.reset(poses)[0]
+        outs = [s.reset(poses)[0] for s in singles]
+        for step in range(3):
+            for k, slot in enumerate((0, K)):
+                sel = torch.as_tensor(assign == slot, device=multi.device)
+                assert torch.equal(om['scans'][sel], outs[k]['scans'][sel]), (r, step, slot)
+                assert torch.equal(om['collisions'][sel], outs[k]['collisions'][sel]), (r, step, slot)
+            om = multi.step(acts[step])[0]
+            outs = [s.step(acts[step])[0] for s in singles]
+        assert np.array_equal(multi.eng.get_map_dt(), spec0[0])
+        assert np.array_equal(multi.eng.get_map_dt(slot=K), singles[1].eng.get_map_dt())
+        for s in singles:
+            s.close()
+    multi.close()
+
+
 def test_a_map_per_env_neighbouring_cars_on_different_maps():
     """f110_assign_maps without the block rule: envs take their maps in any pattern (here env e on map e % 4, an odd number of
     envs, slots far beyond the first 64) -- the scan then runs one wave per workgroup, every car staging its own map's table --
