@@ -234,7 +234,8 @@ int f110_assign_noise(f110_handle *h, const int32_t *slot_of_env_host);
  * ONE row per env -- no table to keep ahead of the cars, no floor, no growth: f110_noise_ensure / _prefetch / _set_floor
  * are no-ops in this mode.  A reset restarts the env's stream at its seed; a row counter that does not continue the
  * generator's (a loaded checkpoint) makes the generator run forward from the seed without storing.  Costs one more kernel
- * per step (~1 500 wave-instructions per env).  Setting a table or a slot generator leaves the mode.
+ * per step (~1 500 wave-instructions per env).  Setting a table or a slot generator leaves the mode; an f110_set_noise_*
+ * call that refuses its arguments changes nothing, the mode and the launch epoch included.
  * Reference: f110_env.py:102-105 (`seed` of every env), base_classes.py:117,202, laser_models.py:450-452. */
 int f110_set_noise_per_env(f110_handle *h, const uint64_t *pcg64_state_inc_host, double std_dev);
 int f110_noise_ensure(f110_handle *h, int64_t rows, void *stream);

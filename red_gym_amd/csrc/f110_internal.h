@@ -106,6 +106,59 @@ using GraphExec = HipOwner<hipGraphExec_t, hipGraphExecDestroy>;
 // one stage of a scan launch's wave -> car mapping: `cars` cars (< 0: "*", the remaining cars) at 2^lg waves each
 struct StageSpec { int cars, lg; };
 
+// Where the scan finds a car's noise row: row r of the car's slot is base[(slot * cap + (r & mask)) * num_beams], slot =
+// env_slot[env] (NULL: slot 0).  ScanArgs and the device-resident NoiseDesc both take it from NoiseState::where.
+struct NoiseRows {
+    const double *base;
+    int cap, mask, slots;
+    const int32_t *env_slot;
+};
+
+enum class NoiseKind { unset, host_table, generator }; // unset: the row of zeros
+
+// Lidar noise (f110_noise.h, f110_noise_abi.hip).  Ring mode: [slots][cap][num_beams] rows, rows lo .. hi-1 present, every
+// env on the slot d_env_slot gives it.  Per-env mode (f110_set_noise_per_env): every env its own generator and ONE row,
+// produced in front of every step's scan.
+struct NoiseState {
+    struct Slot {
+        NoiseKind kind = NoiseKind::unset;
+        long long T = 0;              // host table: its rows
+        NoiseGen seed;                // generator: the stream at row 0
+    };
+    DevBuf<double> d_rows;            // [slots][cap][num_beams] noise rows (a ring per slot)
+    long long cap = 0, lo = 0, hi = 0; // cap: rows per slot (a power of two); noise off: cap 1, hi = "infinity"
+    int slots = 1;
+    bool on = false;
+    Slot slot[F110_MAX_NOISE_SLOTS];
+    long long gen_rows = 0;           // rows every generator slot has produced (they all stand at the same row)
+    DevBuf<NoiseDesc> d_desc;         // what the kernels read: its address never changes
+    DevBuf<NoiseGen> d_gen;           // [F110_MAX_NOISE_SLOTS] device generator states
+    DevBuf<int32_t> d_env_slot;       // dev [B] noise slot of every env; passed only when `multi`
+    bool multi = false;
+    Stream stream;                    // the generator runs here, beside the caller's stream (f110_noise_prefetch)
+    Event ev;
+    long long pending_hi = 0;         // rows a prefetch in flight on `stream` will have produced (0: none in flight)
+    // Ordering of the side stream behind the caller's: recorded on the caller's stream whenever the floor is raised (the steps
+    // enqueued so far may still read the rows below it, whose ring places the next prefetch recycles) and whenever a generator
+    // kernel is enqueued there (it reads and writes the same generator states); the next prefetch waits for it.
+    Event order_ev;
+    bool order_ev_set = false;
+    DevBuf<NoiseMark> d_marks;        // [marks_slots][marks_cap] generator state at every 64th row (f110_noise.h NoiseMark)
+    long long marks_cap = 0;
+    int marks_slots = 0;
+    DevBuf<u128> d_pcg_tab;           // [2][65] powers and partial sums of the LCG multiplier (f110_noise.h NoiseGenArgs::pcg_tab)
+    bool per_env = false;
+    DevBuf<NoiseGen> d_env_gen, d_env_seed;   // [num_envs]
+    DevBuf<double> d_env_rows;                // [num_envs][num_beams]
+    DevBuf<int32_t> d_env_ident;              // [num_envs] env -> slot = env
+
+    NoiseRows where(int num_envs) const
+    {
+        if (per_env) return {d_env_rows.get(), 1, 0, num_envs, d_env_ident.get()};
+        return {d_rows.get(), (int)cap, (int)(cap - 1), slots, multi ? d_env_slot.get() : nullptr};
+    }
+};
+
 struct f110_handle {
     f110_config cfg;
     // Vehicle parameters, [slots][1 + A]: per params slot (the `params` one reference env was constructed with) entry 0 =
@@ -129,46 +182,13 @@ struct f110_handle {
     DevBuf<double2> d_cs;             // interleaved {cos, sin} LUT (repeated, see upload_cs)
     DevBuf<double2> d_beam_cs;        // {cos, sin}(scan_angles) for the opponent ray cast
     std::vector<double> h_sines, h_cosines;
-    // Lidar noise (f110_noise.h): [noise_slots][cap][nb] noise rows, rows lo .. hi-1 present; the kernels
-    // find it through d_noise_desc, whose address never changes
-    DevBuf<double> d_noise;           // [noise_slots][noise_cap][num_beams] noise rows (a ring per slot)
     double side_max = 0.0;            // largest finite side distance (the scan's pre-test for iTTC candidates)
-    long long noise_cap = 0, noise_lo = 0, noise_hi = 0; // cap: rows per slot (a power of two); noise off: cap 1, hi = "infinity"
-    int noise_slots = 1;
-    bool noise_on = false;
-    DevBuf<NoiseDesc> d_noise_desc;
-    struct NoiseSlot {
-        int kind = 0;                 // 0 unset (zeros), 1 host-fed table, 2 generator
-        std::vector<double> rows;     // host-fed: [T, nb]
-        long long T = 0;              // rows the slot can serve: host-fed = table length, generator = rows produced
-        NoiseGen seed;                // generator: the stream at row 0
-    };
-    NoiseSlot nslots[F110_MAX_NOISE_SLOTS];
-    DevBuf<NoiseGen> d_noise_gen;     // [F110_MAX_NOISE_SLOTS] device generator states
-    DevBuf<int32_t> d_env_noise;      // dev [B] noise slot of every env; passed only when `multi_noise`
-    bool multi_noise = false;
-    Stream noise_stream;              // the generator runs here, beside the caller's stream (f110_noise_prefetch)
-    Event noise_ev;
-    long long noise_pending_hi = 0;   // rows a prefetch in flight on noise_stream will have produced (0: none in flight)
-    // Ordering of the side stream behind the caller's: recorded on the caller's stream whenever the floor is raised (the steps
-    // enqueued so far may still read the rows below it, whose ring places the next prefetch recycles) and whenever a generator
-    // kernel is enqueued there (it reads and writes the same generator states); the next prefetch waits for it.
-    Event order_ev;
-    bool order_ev_set = false;
+    NoiseState noise;
     // prepared raceline of f110_pure_pursuit (f110_pure_pursuit_prepare): grid of candidate lists (f110_planner.h PlanGrid)
     const double *plan_wp = nullptr; int plan_M = 0; bool plan_ok = false;
     PlanGrid plan_grid;
     DevBuf<uint8_t> d_plan_count; DevBuf<uint16_t> d_plan_cand;
-    DevBuf<u128> d_pcg_tab;           // [2][65] powers and partial sums of the LCG multiplier (f110_noise.h NoiseGenArgs::pcg_tab)
     const int32_t *scan_order = nullptr; // launch order of the step's scan (f110_set_scan_order; caller-owned device array) or NULL
-    // per-env noise (f110_set_noise_per_env): every env its own generator and ONE row, produced in front of every step's scan
-    bool per_env_noise = false;
-    DevBuf<NoiseGen> d_env_gen, d_env_seed;   // [num_envs]
-    DevBuf<double> d_env_rows;                // [num_envs][num_beams]
-    DevBuf<int32_t> d_env_ident;              // [num_envs] env -> slot = env
-    DevBuf<NoiseMark> d_marks;        // [noise_slots][marks_cap] generator state at every 64th row (f110_noise.h NoiseMark)
-    long long marks_cap = 0;
-    int marks_slots = 0;
     DevBuf<uint32_t> d_err;           // device error word (f110_device_errors)
     std::vector<double> h_side;       // side distances (host copy of d_side)
     // Maps.  Slot 0 is "the" map of the reference's API; further slots let blocks of envs of one shard run on

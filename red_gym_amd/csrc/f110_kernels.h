@@ -1284,7 +1284,7 @@ static __global__ __launch_bounds__(256) void dynamics_kernel(DynArgs a)
     a.steer_buf[(size_t)car * 2 + 1] = sb[1];
     a.steer_cnt[car] = sc;
     if (a.in_collision) a.in_collision[car] = 0;
-    // the host keeps the noise table ahead of every car (Engine._ensure_noise); a row outside it is reported, never silent
+    // the host keeps the noise table ahead of every car (Engine.ready_noise); a row outside it is reported, never silent
     if (__builtin_expect(nrow < nlo || nrow >= nhi, 0))
         if (a.dev_err) atomicOr(a.dev_err, DEVERR_NOISE_WINDOW);
     if (a.pose_snap) {

@@ -200,11 +200,11 @@ static void fill_scan_args(const f110_handle *h, ScanArgs &s, int reset_only)
     s.pose_src = b.state; s.pose_stride = 7; s.yaw_off = 4;
     s.state = b.state; s.noise_step = b.noise_step; s.chunk_beam0 = h->d_chunk0.get();
     s.side = h->d_side.get(); s.side_max = h->side_max;
-    s.noise_base = h->d_noise.get(); s.noise_cap = (int)h->noise_cap; s.noise_mask = (int)(h->noise_cap - 1); s.noise_slots = h->noise_slots;
-    s.env_noise = h->multi_noise ? h->d_env_noise.get() : nullptr; s.dev_err = h->d_err.get();
+    const NoiseRows nr = h->noise.where(c.num_envs);
+    s.noise_base = nr.base; s.noise_cap = nr.cap; s.noise_mask = nr.mask; s.noise_slots = nr.slots; s.env_noise = nr.env_slot;
+    s.dev_err = h->d_err.get();
     s.order = (h->scan_order && !h->multi) ? h->scan_order : nullptr; // (a workgroup stages one LUT: car order when maps differ)
     s.wg_single = h->multi && h->wg_single; s.n_maps = F110_MAX_MAPS;
-    if (h->per_env_noise) { s.noise_base = h->d_env_rows.get(); s.noise_cap = 1; s.noise_mask = 0; s.noise_slots = c.num_envs; s.env_noise = h->d_env_ident.get(); }
     s.beam_cosines = h->d_beam_cosines.get(); s.ttc_thresh = c.ttc_thresh;
     s.in_collision = b.in_collision; s.pending_reset = b.pending_reset; s.reset_only = reset_only;
     s.out_f32 = b.scans; s.out_f64 = b.scans_f64; s.lookups = b.lookups;
@@ -231,12 +231,12 @@ static int run_step(f110_handle *h, const double *actions, int reset_only, const
     hipEvent_t ev0 = prof ? h->prof_ev[2 * h->prof_n].get() : nullptr, ev1 = prof ? h->prof_ev[2 * h->prof_n + 1].get() : nullptr;
     int rc;
 
-    if (h->per_env_noise) {
+    if (h->noise.per_env) {
         // the row every env's scan is about to add (row `pending ? 0 : noise_step`), from the env's own generator
         NoiseGenArgs g;
         memset(&g, 0, sizeof(g));
-        g.gen = h->d_env_gen.get(); g.seeds = h->d_env_seed.get(); g.base = h->d_env_rows.get(); g.mask = 0; g.cap = 1; g.nb = c.num_beams;
-        g.pcg_tab = h->d_pcg_tab.get(); g.env_row = b.noise_step; g.env_row_stride = c.num_agents; g.n_env = c.num_envs;
+        g.gen = h->noise.d_env_gen.get(); g.seeds = h->noise.d_env_seed.get(); g.base = h->noise.d_env_rows.get(); g.mask = 0; g.cap = 1; g.nb = c.num_beams;
+        g.pcg_tab = h->noise.d_pcg_tab.get(); g.env_row = b.noise_step; g.env_row_stride = c.num_agents; g.n_env = c.num_envs;
         g.reset_only = reset_only; g.env_pending = b.pending_reset;
         if ((rc = emit(st, (const void *)&noise_rows_kernel, dim3((c.num_envs + 3) / 4), dim3(256), 0, g))) return rc;
     }
@@ -244,7 +244,7 @@ static int run_step(f110_handle *h, const double *actions, int reset_only, const
         DynArgs d;
         d.n_cars = N; d.agents = c.num_agents; d.state = b.state; d.steer_buf = b.steer_buf; d.steer_cnt = b.steer_cnt;
         d.noise_step = b.noise_step; d.actions = actions; d.spawn = b.spawn; d.pending_reset = b.pending_reset;
-        d.was_pending = h->d_was_pending.get(); d.reset_only = reset_only; d.pose_snap = b.pose_snap; d.in_collision = b.in_collision; d.params = h->d_params.get(); d.env_params = h->multi_params ? h->d_env_params.get() : nullptr; d.param_slots = h->param_slots; d.dev_err = h->d_err.get(); d.noise = h->d_noise_desc.get();
+        d.was_pending = h->d_was_pending.get(); d.reset_only = reset_only; d.pose_snap = b.pose_snap; d.in_collision = b.in_collision; d.params = h->d_params.get(); d.env_params = h->multi_params ? h->d_env_params.get() : nullptr; d.param_slots = h->param_slots; d.dev_err = h->d_err.get(); d.noise = h->noise.d_desc.get();
         d.time_step = c.timestep; d.integrator = c.integrator;
         if ((rc = emit(st, (const void *)&dynamics_kernel, dim3((N + 255) / 256), dim3(256), 0, d))) return rc;
     }

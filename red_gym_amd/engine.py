@@ -1,5 +1,6 @@
 """Engine: owns one f110_handle (one GPU), the torch tensors bound to it and the
 host-built tables.  Thin: all compute is in libf110_hip.so."""
+import contextlib
 import ctypes as C
 import os
 
@@ -69,6 +70,13 @@ class NoiseTable(object):
                    for _ in range(steps - self.rows.shape[0])]
             self.rows = np.ascontiguousarray(np.concatenate([self.rows, np.stack(new)], axis=0))
         return self.rows
+
+
+def pcg64_words(seed):
+    """{state_lo, state_hi, inc_lo, inc_hi} of np.random.PCG64(seed).state: the stream np.random.default_rng(seed) starts from."""
+    st = np.random.PCG64(seed).state['state']
+    m64 = (1 << 64) - 1
+    return st['state'] & m64, st['state'] >> 64, st['inc'] & m64, st['inc'] >> 64
 
 
 def _ptr(t):
@@ -154,16 +162,14 @@ class Engine(object):
         self.slot_shapes = {}
         self.host_steps_bound = 0
         self._steps_exact = False
-        self._noise_on = bool(noise_std and noise_std > 0)
-        self._noise_gen = self._noise_on and noise_source == 'device'
-        self._noise_per_env = self._noise_on and noise_source == 'per_env'
+        self.noise_mode = noise_source if noise_std and noise_std > 0 else 'off'   # or 'per_env' for too many seeds: _setup_noise
         self._noise_rows, self._noise_floor, self._noise_prefetched = 0, 0, False
         self._in_capture = False  # a stream capture is recording step(): no noise work (it was done in front of the capture)
         # planner grid (Engine._plan_grid): the prepared raceline tensor, its version, (pointer, version, M) while the handle
         # holds a grid for it (None: none, or its prepare failed), and the last tensor seen once (tensor, version)
         self._plan_tensor, self._plan_version, self._plan_key, self._plan_seen = None, -1, None, None
         self.scan_reorder = True  # keep the scan's launch order sorted by noise row (Engine._reorder_scan); False: car order
-        self.env_noise_assign = None
+        self._reorder_count, self._scan_order, self.env_noise_assign = 0, None, None
         self.noise_tables = []
         if env_params is not None:
             self.set_env_params(env_params)
@@ -201,6 +207,9 @@ class Engine(object):
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    _noise_on = property(lambda self: self.noise_mode != 'off')            # (bench.py and the tests read these two)
+    _noise_per_env = property(lambda self: self.noise_mode == 'per_env')
+
     # ------------------------------------------------------------------ per-env constructor arguments
     def set_env_params(self, env_params):
         """env e drives the vehicle of env_params[e] (a sequence of num_envs dicts): what num_envs reference envs
@@ -223,35 +232,25 @@ class Engine(object):
     def _setup_noise(self, seeds, std):
         """One noise slot per distinct seed (base_classes.py:117,202: all cars of an env draw from default_rng(seed))."""
         uniq = list(dict.fromkeys(seeds))
-        if len(uniq) > _lib.F110_MAX_NOISE_SLOTS and self._noise_gen:
-            self._noise_gen, self._noise_per_env = False, True   # more seeds than the table has slots: every env its own generator
-        if self._noise_per_env:
-            # f110_env.py:102-105: every env its own `seed`; np.random.PCG64(seed).state is the stream default_rng(seed) starts from
-            m64 = (1 << 64) - 1
-            words = np.empty((self.B, 4), dtype=np.uint64)
-            per_seed = {}
-            for e in range(self.B):
-                sd = seeds[e if len(seeds) > 1 else 0]
-                if sd not in per_seed:
-                    st = np.random.PCG64(sd).state['state']
-                    per_seed[sd] = (st['state'] & m64, st['state'] >> 64, st['inc'] & m64, st['inc'] >> 64)
-                words[e] = per_seed[sd]
+        self.noise_seeds, self._noise_std = uniq, std
+        if len(uniq) > _lib.F110_MAX_NOISE_SLOTS and self.noise_mode == 'device':
+            self.noise_mode = 'per_env'   # more seeds than the table has slots: every env its own generator
+        if self.noise_mode == 'per_env':
+            # f110_env.py:102-105: every env its own `seed`
+            per_seed = {sd: pcg64_words(sd) for sd in uniq}
+            words = np.array([per_seed[seeds[e if len(seeds) > 1 else 0]] for e in range(self.B)], dtype=np.uint64)
             _lib.check(self.lib.f110_set_noise_per_env(self._h, _np_ptr(words), std))
-            self.noise_seeds, self._noise_std = uniq, std
             return
         if len(uniq) > _lib.F110_MAX_NOISE_SLOTS:
             raise ValueError("%d distinct seeds; a table of host rows holds %d noise slots (noise_source='per_env' has no limit)"
                              % (len(uniq), _lib.F110_MAX_NOISE_SLOTS))
-        self.noise_seeds, self._noise_std = uniq, std
         for k, sd in enumerate(uniq):
-            if self._noise_gen:
-                st = np.random.PCG64(sd).state['state']  # the stream np.random.default_rng(sd) starts from
-                m64 = (1 << 64) - 1
-                words = (C.c_uint64 * 4)(st['state'] & m64, st['state'] >> 64, st['inc'] & m64, st['inc'] >> 64)
-                _lib.check(self.lib.f110_set_noise_generator(self._h, k, words, std))
+            if self.noise_mode == 'device':
+                words = np.array(pcg64_words(sd), dtype=np.uint64)
+                _lib.check(self.lib.f110_set_noise_generator(self._h, k, _np_ptr(words), std))
             else:
                 self.noise_tables.append(NoiseTable(sd, self.num_beams, std))
-        if not self._noise_gen:
+        if self.noise_mode == 'numpy':
             self._upload_host_noise(64)
         if len(seeds) > 1:
             assign = np.ascontiguousarray([uniq.index(sd) for sd in seeds], dtype=np.int32)
@@ -280,9 +279,9 @@ class Engine(object):
 
     def _noise_to(self, rows):
         """Rows 0 .. rows-1 (above the floor) readable by the steps enqueued from now on."""
-        if self._noise_per_env:
+        if self.noise_mode == 'per_env':
             return
-        if self._noise_gen:
+        if self.noise_mode == 'device':
             _lib.check(self.lib.f110_noise_ensure(self._h, int(rows), self._stream()))
             self._noise_rows = self.noise_info()[1]  # (host-side bookkeeping of the library: no synchronisation)
         elif rows > self._noise_rows:
@@ -290,7 +289,7 @@ class Engine(object):
         self._noise_prefetched = False
 
     def _set_noise_floor(self, lo):
-        if self._noise_gen and lo != self._noise_floor:
+        if self.noise_mode == 'device' and lo != self._noise_floor:
             _lib.check(self.lib.f110_noise_set_floor(self._h, int(lo), self._stream()))
             if lo < self._noise_floor:
                 # the dropped rows are produced again from the generators' marks (in this stream); what was produced stays
@@ -299,7 +298,7 @@ class Engine(object):
             self._noise_floor = int(lo)
 
     @on_own_device
-    def _ensure_noise(self, may_raise_floor=True):
+    def ready_noise(self, may_raise_floor=True):
         """Keeps the noise table ahead of every car without synchronising: host_steps_bound counts steps since the last
         full reset, an upper bound of every car's noise_step.  While the rows produced cover it, nothing happens (but the
         next chunk is started on the library's side stream once half of the current one is used).  When the bound reaches
@@ -308,12 +307,12 @@ class Engine(object):
         the next chunk would not fit the table and cars cannot go back to row 0 by themselves (autoreset off), the floor
         moves up to the slowest car instead of the table growing (a ring of constant size however long the run), and the
         next chunk is produced.  may_raise_floor=False: a reset is about to send cars back to row 0."""
-        if not self._noise_on or self._in_capture or self._noise_per_env:
+        if self.noise_mode in ('off', 'per_env') or self._in_capture:
             return   # (per-env noise: the step produces its own rows)
         self._reorder_scan()
         need = self.host_steps_bound + 2
         if need <= self._noise_rows:
-            if self._noise_gen and not self._noise_prefetched and need + self.NOISE_CHUNK // 2 > self._noise_rows:
+            if self.noise_mode == 'device' and not self._noise_prefetched and need + self.NOISE_CHUNK // 2 > self._noise_rows:
                 _lib.check(self.lib.f110_noise_prefetch(self._h, self._noise_rows + self.NOISE_CHUNK))
                 self._noise_prefetched = True
             return
@@ -323,7 +322,7 @@ class Engine(object):
             mn, mx = (int(v) for v in torch.aminmax(self.t['noise_step']))
             self.host_steps_bound = mx
         target = mx + 2 + self.NOISE_CHUNK
-        if (self._noise_gen and may_raise_floor and not self.autoreset and mn > self._noise_floor
+        if (self.noise_mode == 'device' and may_raise_floor and not self.autoreset and mn > self._noise_floor
                 and target - self._noise_floor > self.noise_info()[2]):
             self._set_noise_floor(mn)
         if mx + 2 > self._noise_rows and self._noise_prefetched:
@@ -342,11 +341,11 @@ class Engine(object):
         (~50 us) keeps it.  Results do not depend on the order.  Nothing to do while every car stands on the same row."""
         if self._steps_exact or self.N < self.REORDER_MIN_CARS or not self.scan_reorder:
             return
-        self._reorder_count = getattr(self, '_reorder_count', 0) + 1
+        self._reorder_count += 1
         if self._reorder_count % self.REORDER_EVERY != 1:
             return
         key = self.t['noise_step'][:, 0]
-        if getattr(self, 'env_noise_assign', None) is not None:
+        if self.env_noise_assign is not None:
             key = key.to(torch.int64) + (self.env_noise_assign.to(torch.int64) << 32)   # (envs of one seed AND one row together)
         idx = torch.argsort(key)
         if self.A > 1:
@@ -354,7 +353,7 @@ class Engine(object):
         # (Measured and dropped: giving every XCD one contiguous EIGHTH of the sorted list, so that its L2 holds an eighth of the
         # rows -- the steady state does not move (103.7 M) and the protocol region loses 4 % (105.2 against 109.4 M): age
         # correlates with what a car's scan costs, and an XCD that is dealt the expensive eighth finishes last.)
-        if getattr(self, '_scan_order', None) is None:
+        if self._scan_order is None:
             self._scan_order = idx.to(torch.int32).contiguous()
             _lib.check(self.lib.f110_set_scan_order(self._h, _ptr(self._scan_order)))
         else:
@@ -454,7 +453,7 @@ class Engine(object):
             self._steps_exact = not self.autoreset
         if self._noise_floor > 0:
             self._set_noise_floor(0)       # cars at row 0 again: the rows below the floor are produced anew
-        self._ensure_noise(may_raise_floor=False)
+        self.ready_noise(may_raise_floor=False)
         _lib.check(self.lib.f110_reset(self._h, _ptr(poses), _ptr(mask), self._stream()))
         self.host_steps_bound += 1
         self._keep = (poses, mask)  # keep inputs alive until the stream has consumed them
@@ -466,10 +465,54 @@ class Engine(object):
             raise ValueError('actions must have shape (%d, %d, 2)' % (self.B, self.A))
         if actions.dtype != torch.float64 or not actions.is_contiguous() or actions.device != self.device:
             actions = actions.to(device=self.device, dtype=torch.float64).contiguous()
-        self._ensure_noise()
+        self.ready_noise()
         _lib.check(self.lib.f110_step(self._h, _ptr(actions), self._stream()))
-        self.host_steps_bound += 1
+        if not self._in_capture:
+            self.host_steps_bound += 1
         self._keep = actions
+
+    # ------------------------------------------------------------------ replayed steps
+    @contextlib.contextmanager
+    def capturing(self):
+        """Wraps a stream capture of step(): no noise work inside (ready_noise() goes in front), the step is not counted."""
+        self._in_capture = True
+        try:
+            yield
+        finally:
+            self._in_capture = False
+
+    def count_step(self):
+        """A replay of a captured step was launched: host_steps_bound follows the cars' noise rows."""
+        self.host_steps_bound += 1
+
+    @on_own_device
+    def load_state(self, sd):
+        """Copies a checkpoint {buffer name: tensor} into the bound buffers; host_steps_bound and the noise table follow."""
+        for k, v in sd.items():
+            self.t[k].copy_(v)
+        self.host_steps_bound = max(self.host_steps_bound, int(self.t['noise_step'].max().item()) + 1)
+        self._steps_exact = False
+        self._set_noise_floor(0)
+
+    def create_graph(self, actions, how='nodes'):
+        """The step as a HIP graph built by the library (f110_graph_create), reading its actions from the tensor `actions`."""
+        g = C.c_void_p()
+        _lib.check(self.lib.f110_graph_create(self._h, _ptr(actions), {'nodes': 0, 'capture': 1}[how], C.byref(g)))
+        return g
+
+    @on_own_device
+    def launch_graph(self, g):
+        _lib.check(self.lib.f110_graph_launch(g, self._stream()))
+        self.count_step()
+
+    def graph_info(self, g, dot_path=None):
+        n = C.c_int32(0)
+        _lib.check(self.lib.f110_graph_info(g, C.byref(n), dot_path.encode() if dot_path else None))
+        return n.value
+
+    def destroy_graph(self, g):
+        torch.cuda.current_stream(self.device).synchronize()  # a graph exec must outlive its last launch
+        self.lib.f110_graph_destroy(g)
 
     # ------------------------------------------------------------------ function-level entry points
     def _dev64(self, a, shape=None):

@@ -66,6 +66,7 @@ class F110VecEnv(object):
         if t['scans_f64'] is not None:
             self._obs['scans_f64'] = t['scans_f64']
         self._reward = torch.full((self.num_envs,), float(timestep), dtype=torch.float64, device=self.device)
+        self._g_actions, self._graphs, self._lg = None, [], None   # capture_step / build_step_graph
 
     def _result(self):
         t = self.eng.t
@@ -111,13 +112,7 @@ class F110VecEnv(object):
         return {k: self.eng.t[k].clone() for k in self._STATE_KEYS if self.eng.t[k] is not None}
 
     def load_state_dict(self, sd):
-        for k, v in sd.items():
-            self.eng.t[k].copy_(v)
-        # the host's upper bound of any car's noise row must cover the restored counters, and the noise table their rows
-        self.eng.host_steps_bound = max(self.eng.host_steps_bound, int(self.eng.t['noise_step'].max().item()) + 1)
-        self.eng._steps_exact = False
-        with torch.cuda.device(self.device):
-            self.eng._set_noise_floor(0)
+        self.eng.load_state(sd)
 
     # ------------------------------------------------------------------ hipGraph replay
     def capture_step(self, policy=None, copies=1):
@@ -127,13 +122,13 @@ class F110VecEnv(object):
         kernel launches replay from one graph launch; `step_graph()` then costs one host call.
         Returns the static action buffer [B,A,2] to write into when no policy is given (it stays the
         same tensor across re-captures)."""
-        if getattr(self, '_g_actions', None) is None:
+        if self._g_actions is None:
             self._g_actions = torch.zeros((self.num_envs, self.num_agents, 2), dtype=torch.float64, device=self.device)
         self._g_policy = policy
-        self.eng._ensure_noise()
+        self.eng.ready_noise()
         # `copies` > 1 captures that many identical graphs, replayed in turn (an experiment: two alternating execs
         # replay no faster than one, profiles/r02_graph_vs_eager.txt)
-        if getattr(self, '_graphs', None):
+        if self._graphs:
             # a replay of the graphs being dropped may still be in flight (f110_set_scan_stages bumps the epoch without
             # synchronising): a graph exec must outlive its last launch
             torch.cuda.current_stream(self.device).synchronize()
@@ -142,17 +137,11 @@ class F110VecEnv(object):
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
             g = torch.cuda.CUDAGraph()
-            self.eng._in_capture = True
-            try:
-                with torch.cuda.stream(side):
-                    with torch.cuda.graph(g, stream=side):
-                        if policy is not None:
-                            policy(self, self._g_actions.view(-1, 2))
-                        self.eng.step(self._g_actions)
-            finally:
-                self.eng._in_capture = False
+            with self.eng.capturing(), torch.cuda.stream(side), torch.cuda.graph(g, stream=side):
+                if policy is not None:
+                    policy(self, self._g_actions.view(-1, 2))
+                self.eng.step(self._g_actions)
             torch.cuda.current_stream(self.device).wait_stream(side)
-            self.eng.host_steps_bound -= 1  # the capture executed nothing: undo its host-side step accounting
             self._graphs.append(g)
         self._g_copies = len(self._graphs)
         # a capture freezes the kernel choice and the by-value arguments (noise table address and length, map
@@ -167,12 +156,12 @@ class F110VecEnv(object):
         randomised) the step is re-captured first, so a replay never reads a freed table."""
         if actions is not None:
             self._g_actions.copy_(self._as_dev(actions, 2))
-        self.eng._ensure_noise()
+        self.eng.ready_noise()
         if self.eng.launch_epoch() != self._g_epoch:
             self.capture_step(self._g_policy, self._g_copies)
         self._graphs[self._g_next].replay()
         self._g_next = (self._g_next + 1) % len(self._graphs)
-        self.eng.host_steps_bound += 1
+        self.eng.count_step()
         return self._result()
 
     # ------------------------------------------------------------------ hipGraph built by the library
@@ -180,41 +169,29 @@ class F110VecEnv(object):
         """The step as a HIP graph built by the library itself (f110_graph_create: 'nodes' = explicit kernel nodes,
         'capture' = a capture on a private non-blocking stream) instead of a torch capture.  Returns the static action
         buffer [B,A,2]; `step_lib_graph()` replays."""
-        import ctypes as C
-        from . import _lib
-        if getattr(self, '_g_actions', None) is None:
+        if self._g_actions is None:
             self._g_actions = torch.zeros((self.num_envs, self.num_agents, 2), dtype=torch.float64, device=self.device)
-        self._drop_lib_graph()
-        self.eng._ensure_noise()
-        g = C.c_void_p()
-        _lib.check(self.eng.lib.f110_graph_create(self.eng._h, C.c_void_p(self._g_actions.data_ptr()),
-                                                  {'nodes': 0, 'capture': 1}[how], C.byref(g)))
-        self._lg, self._lg_how, self._lg_epoch = g, how, self.eng.launch_epoch()
+        self._drop_graph()
+        self.eng.ready_noise()
+        self._lg = self.eng.create_graph(self._g_actions, how)
+        self._lg_how, self._lg_epoch = how, self.eng.launch_epoch()
         return self._g_actions
 
-    def _drop_lib_graph(self):
-        if getattr(self, '_lg', None):
-            torch.cuda.current_stream(self.device).synchronize()  # a graph exec must outlive its last launch
-            self.eng.lib.f110_graph_destroy(self._lg)
+    def _drop_graph(self):
+        if self._lg is not None:
+            self.eng.destroy_graph(self._lg)
             self._lg = None
 
     def lib_graph_info(self, dot_path=None):
-        import ctypes as C
-        from . import _lib
-        n = C.c_int32(0)
-        _lib.check(self.eng.lib.f110_graph_info(self._lg, C.byref(n), dot_path.encode() if dot_path else None))
-        return n.value
+        return self.eng.graph_info(self._lg, dot_path)
 
     def step_lib_graph(self, actions=None):
-        from . import _lib
         if actions is not None:
             self._g_actions.copy_(self._as_dev(actions, 2))
-        self.eng._ensure_noise()
+        self.eng.ready_noise()
         if self.eng.launch_epoch() != self._lg_epoch:
             self.build_step_graph(self._lg_how)
-        with torch.cuda.device(self.device):
-            _lib.check(self.eng.lib.f110_graph_launch(self._lg, self.eng._stream()))
-        self.eng.host_steps_bound += 1
+        self.eng.launch_graph(self._lg)
         return self._result()
 
     def pure_pursuit(self, waypoints, lookahead, vgain, wheelbase=0.17145 + 0.15875, prepare=True):
@@ -303,5 +280,5 @@ class F110VecEnv(object):
         return self.eng.t['state']
 
     def close(self):
-        self._drop_lib_graph()
+        self._drop_graph()
         self.eng.close()

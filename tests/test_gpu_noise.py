@@ -177,6 +177,35 @@ def test_per_env_noise_follows_a_loaded_checkpoint_and_a_masked_reset(assets):
     env.close()
 
 
+def test_a_refused_noise_table_leaves_per_env_noise_alone(assets):
+    """f110_set_noise_slot with a bad table (NULL, T = 0) is refused before it changes anything: the handle stays in per-env
+    mode, the launch epoch does not move, and the next scans are still every env's own NumPy rows.  (The call used to leave
+    per-env mode before it checked its arguments: it reported the error, and every later scan ran without noise.)"""
+    import torch
+    from red_gym_amd import F110VecEnv, _lib
+    B = 4
+    seeds = [11, 12, 13, 11]
+    env = F110VecEnv(B, map=os.path.join(assets, 'example_map'), num_agents=1, seed=seeds, autoreset=False, keep_f64_scans=True,
+                     noise_source='per_env')
+    poses = np.tile(np.array([[[-45.87478769831466, -16.282154624538293, 0.3]]]), (B, 1, 1))   # inside a wall
+    z = torch.zeros((B, 1, 2), dtype=torch.float64, device='cuda')
+    env.reset(poses)
+    for k in range(3):
+        env.step(z)
+    eng = env.eng
+    ep0 = eng.launch_epoch()
+    with torch.cuda.device(eng.device):
+        assert eng.lib.f110_set_noise_slot(eng._h, 0, None, 0) == _lib.E_INVALID
+    assert b'bad table' in eng.lib.f110_last_error()
+    assert eng.launch_epoch() == ep0
+    rows = {s_: np.random.default_rng(s_).normal(0., 0.01, size=(8, 1080)) for s_ in set(seeds)}
+    for k in range(4, 8):                        # the reset's scan is row 0, step k's row k
+        env.step(z)
+        assert np.array_equal(_np(eng.t['scans_f64'])[:, 0], np.stack([rows[s_][k] for s_ in seeds])), k
+    assert eng.device_errors() == 0
+    env.close()
+
+
 def test_update_params_reaches_every_slot_and_one_slot_only(assets):
     """f110_update_params (Simulator.update_params, base_classes.py:507-527) applies to the agent in EVERY env;
     f110_set_params_slot(slot, agent) to that env's agent only; IndexError beyond the agent list."""
@@ -263,7 +292,7 @@ def test_long_run_is_a_ring_of_constant_size(assets):
 def test_prefetch_waits_for_the_steps_enqueued_before_the_floor_moved(assets):
     """the floor of the noise ring is raised from the HOST's step count, and the next prefetch (the library's
     side stream) recycles the ring places of the rows below it -- while steps that were enqueued before may not have run yet
-    (a 65 536-env shard runs hundreds of steps behind its host).  The trace of Engine._ensure_noise, compressed: the stream is
+    (a 65 536-env shard runs hundreds of steps behind its host).  The trace of Engine.ready_noise, compressed: the stream is
     stalled by a sleep kernel, 300 steps are enqueued behind it (rows 1 .. 300), the floor goes to 301 and a prefetch of rows
     1 024 .. 1 279 is started -- ring places 0 .. 255.  Every one of the 300 scans must still be its own NumPy row (the cars sit
     inside a wall: a scan IS its noise row).  Fails on the round-4 library (the side stream did not wait)."""

@@ -233,7 +233,7 @@ def test_per_agent_update_params(assets):
 @pytest.mark.parametrize('source', ['numpy', 'device'])
 def test_noise_table_grows_before_it_is_exhausted(assets, source):
     """A car that keeps driving past the rows the noise table holds: more are there before any car needs them
-    (engine._ensure_noise) -- drawn by NumPy on the host and uploaded, or produced on the device."""
+    (Engine.ready_noise) -- drawn by NumPy on the host and uploaded, or produced on the device."""
     from red_gym_amd.engine import Engine
     import torch
     e = Engine(num_envs=2, num_agents=1, noise_steps=4, keep_f64_scans=True, noise_source=source)

@@ -29,10 +29,8 @@ for B in sizes:
                 try:
                     g = torch.cuda.CUDAGraph(); g.enable_debug_mode()
                     side = torch.cuda.Stream()
-                    with torch.cuda.stream(side):
-                        with torch.cuda.graph(g, stream=side):
-                            env.eng.step(buf)
-                    env.eng.host_steps_bound -= 1
+                    with env.eng.capturing(), torch.cuda.stream(side), torch.cuda.graph(g, stream=side):
+                        env.eng.step(buf)
                     g.debug_dump(os.path.join(dump, 'torch_%d.dot' % B))
                 except Exception as e:  # diagnostics only
                     print('torch dot dump failed:', e)
