@@ -179,7 +179,8 @@ int f110_set_map_slot_occupancy_dev(f110_handle *h, int32_t slot, const uint8_t 
                                     double orig_s);
 int f110_assign_maps(f110_handle *h, const int32_t *map_of_env_host);
 int f110_get_map_slot_dt(f110_handle *h, int32_t slot, double *dt_host_out);
-/* Same, from a precomputed distance table dt = resolution*edt(img) (host, [H*W] fp64). */
+/* Same, from a precomputed distance table dt = resolution*edt(img) (host, [H*W] fp64).  Every map entry refuses
+ * height > 524286 or width >= 2^26: the scan addresses cells with signed 24-bit multiplies. */
 int f110_set_map_dt(f110_handle *h, const double *dt_host, int32_t height, int32_t width,
                     double resolution, double orig_x, double orig_y, double orig_c, double orig_s);
 /* Copies the fp64 distance table the handle holds to the host (tests). */

@@ -149,6 +149,7 @@ static int install_map_occupancy_dev(f110_handle *h, int slot, const uint8_t *ma
     if (rc) return rc;
     unsigned max_d2 = 0;
     HIP_TRY(hipMemcpy(&max_d2, maxv.get(), sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (max_d2 == EDT_NONE) return fail(F110_E_INVALID, "f110_set_map_occupancy_dev: map has no occupied cell"); // (the slot is untouched)
     // ranks of the distinct d2 values: presence bitmap + exclusive prefix of its popcounts
     const int n_words = (int)(((size_t)max_d2 + 32) / 32);
     const int n_blocks = (n_words + SCAN_BLOCK_WORDS - 1) / SCAN_BLOCK_WORDS;
@@ -202,6 +203,9 @@ static int check_map_args(f110_handle *h, const void *p, int H, int W, double re
 {
     if (!h || !p) return fail(F110_E_INVALID, "%s: null argument", who);
     if (H < 1 || W < 1 || (int64_t)(H + 10) * (W + 10) > (int64_t)1 << 30 || H + 10 >= (1 << 20)) return fail(F110_E_INVALID, "%s: bad map size %dx%d", who, H, W);
+    // cell_offset and the march loops multiply (c >> 3) by strip_bytes - 16 as signed 24-bit operands (v_mad_i32_i24)
+    if (16 * (int64_t)map_rows_padded(H) - 16 >= (int64_t)1 << 23 || (W >> 3) >= (1 << 23))
+        return fail(F110_E_INVALID, "%s: map size %dx%d outside the 24-bit strip addressing (height <= 524286, width < 2^26)", who, H, W);
     if (!(res > 0) || !std::isfinite(res)) return fail(F110_E_INVALID, "%s: bad resolution %g", who, res);
     return F110_OK;
 }

@@ -1,0 +1,358 @@
+"""The encoded map tables, read out cell by cell through the scan itself.
+
+Every scan reads the cell table, the LDS image of the LUT, the second (far) table, the global LUT and -- for escape
+cells -- the fp64 table; `get_map_dt()` only returns the last of these.  With eps and max_range above every table value
+the reference's trace_ray (laser_models.py:107-145) returns its first look-up, and the scan kernel takes the same early
+exit (dist_lookup, dist_lookup_far for far cells, emit).  So a car at the centre of cell (r, c) scans to exactly the
+value the encoded tables give that cell, and a car outside the map to the border value dt[-1, -1].
+
+Each map goes through the device pipeline (CUDA mask, host mask) and the host pipeline (set_map_dt(res * edt)); the
+read-out must equal res * sqrt(d2) at every probed cell, and the test asserts which rank tier the probed cells are in.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+import oracle  # noqa: E402  (test infrastructure)
+
+# Rank tiers of a cell (red_gym_amd/csrc/f110_kernels.h, LUT_LDS / LDS_RANKS / CODE_ESC): ranks 0 .. LDS_RANKS-1 are
+# LDS byte offsets, ranks up to CODE_ESC-1 go through the far marker to the global LUT, ranks >= CODE_ESC escape to the
+# fp64 table.  SCAN_BLOCK_WORDS: words of the presence bitmap per rank block (f110_mapgen.h); rank_scan_sums_kernel
+# walks the block sums in chunks of 64.
+LDS_RANKS = 1022
+CODE_ESC = 65535
+SCAN_BLOCK_WORDS = 1024
+PIPELINES = ('device', 'device_host_mask', 'host_dt')
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+@pytest.fixture(scope='module')
+def eng():
+    from red_gym_amd.engine import Engine
+    e = Engine(num_envs=1, num_agents=1, num_beams=2, fov=2 * np.pi, eps=1e12, max_range=1e12, noise_std=0)
+    yield e
+    e.close()
+
+
+def ranks_of(d2):
+    """NumPy rank of every cell among the distinct d2 values of the map (0 always takes rank 0)."""
+    return np.searchsorted(np.unique(np.r_[0, d2.ravel()]), d2)
+
+
+def edt_d2(mask):
+    """Exact squared EDT of a free mask (scipy), checked to be the square of scipy's own distances."""
+    from scipy.ndimage import distance_transform_edt
+    e = distance_transform_edt(mask)
+    d2 = np.rint(e ** 2).astype(np.int64)
+    assert np.array_equal(np.sqrt(d2), e)
+    return d2
+
+
+def cell_poses(res, ox, oy, theta, rows, cols):
+    """Poses at the centres of cells (rows, cols) of a map with origin (ox, oy, theta); rows / cols outside the map
+    give poses outside it."""
+    u = (np.asarray(cols, np.float64) + 0.5) * res
+    v = (np.asarray(rows, np.float64) + 0.5) * res
+    if theta == 0:
+        x, y = ox + u, oy + v
+    else:
+        c, s = float(np.cos(theta)), float(np.sin(theta))
+        x, y = ox + c * u - s * v, oy + s * u + c * v
+    return np.stack([x, y, np.zeros_like(x)], axis=1)
+
+
+def readout(engine, H, W, res, ox, oy, theta, cells=None):
+    """The value the installed tables give each of `cells` ([n, 2] rows / columns; None: every cell, row-major),
+    through the scan's own look-up path."""
+    if cells is None:
+        rows, cols = np.divmod(np.arange(H * W, dtype=np.int64), W)
+    else:
+        cells = np.asarray(cells).reshape(-1, 2)
+        rows, cols = cells[:, 0], cells[:, 1]
+    out = np.empty(len(rows))
+    step = 1 << 21
+    for k in range(0, len(rows), step):
+        got = _np(engine.scan(cell_poses(res, ox, oy, theta, rows[k:k + step], cols[k:k + step])))
+        assert np.array_equal(got[:, 0], got[:, 1])
+        out[k:k + step] = got[:, 0]
+    return out
+
+
+def outside_cells(H, W):
+    """Cells just outside the map on all four sides, its corners and far away."""
+    r, c = np.arange(0, H, max(1, H // 7)), np.arange(0, W, max(1, W // 7))
+    side = [np.stack([np.full_like(c, -1), c], 1), np.stack([np.full_like(c, H), c], 1),
+            np.stack([r, np.full_like(r, -1)], 1), np.stack([r, np.full_like(r, W)], 1)]
+    far = np.array([[-1, -1], [-1, W], [H, -1], [H, W], [-40, W // 2], [H + 40, W // 2], [H // 2, -40], [H // 2, W + 40],
+                    [-10 ** 6, -10 ** 6], [10 ** 6, 10 ** 6]])
+    return np.concatenate(side + [far])
+
+
+def install(engine, how, d2, res, ox, oy, theta):
+    import torch
+    mask = (d2 != 0).astype(np.uint8)
+    if how == 'device':
+        engine.set_map_occupancy(torch.as_tensor(mask, device='cuda'), res, ox, oy, theta)
+    elif how == 'device_host_mask':
+        engine.set_map_occupancy(mask, res, ox, oy, theta)
+    else:
+        engine.set_map_dt(res * np.sqrt(d2.astype(np.float64)), res, ox, oy, float(np.cos(theta)), float(np.sin(theta)))
+
+
+def _assert_cells(got, want, rank, what):
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, '%s: %d cells differ; first at flat index %d (rank %d): %r != %r' % (
+        what, bad.size, bad[0], rank[bad[0]], got[bad[0]], want[bad[0]])
+
+
+def check_map(engine, d2, res, ox=0.0, oy=0.0, theta=0.0, cells=None, n_oracle=1500, seed=0):
+    """Installs the map of squared distances `d2` through every pipeline and reads out `cells` (None: all) and the
+    border; a sample is also pinned to the oracle's scan with the same early exit.  Returns the read-outs."""
+    H, W = d2.shape
+    want_map = res * np.sqrt(d2.astype(np.float64))
+    rank_map = ranks_of(d2)
+    if cells is None:
+        want, rank = want_map.ravel(), rank_map.ravel()
+    else:
+        cells = np.asarray(cells).reshape(-1, 2)
+        want, rank = want_map[cells[:, 0], cells[:, 1]], rank_map[cells[:, 0], cells[:, 1]]
+    out_cells = outside_cells(H, W)
+    got = {}
+    for how in PIPELINES:
+        install(engine, how, d2, res, ox, oy, theta)
+        g = readout(engine, H, W, res, ox, oy, theta, cells)
+        _assert_cells(g, want, rank, '%s %dx%d res %g yaw %g' % (how, H, W, res, theta))
+        border = readout(engine, H, W, res, ox, oy, theta, out_cells)
+        assert np.all(border == want_map[-1, -1]), (how, out_cells[border != want_map[-1, -1]][:5])
+        got[how] = g
+    for how in PIPELINES[1:]:
+        assert np.array_equal(got[how], got[PIPELINES[0]]), how
+    # the read-out trick itself follows the reference: the oracle's scan, same early exit, on a sample
+    rng = np.random.default_rng(seed)
+    sample = np.concatenate([np.stack([rng.integers(0, H, n_oracle), rng.integers(0, W, n_oracle)], 1), out_cells[-10:]])
+    sc = oracle.Scanner(2, 2 * np.pi, eps=1e12, max_range=1e12)
+    sc.set_map_dict({'height': H, 'width': W, 'resolution': res, 'orig_x': ox, 'orig_y': oy,
+                     'orig_c': float(np.cos(theta)), 'orig_s': float(np.sin(theta)), 'dt': np.ascontiguousarray(want_map)})
+    ref = sc.scan_batch(cell_poses(res, ox, oy, theta, sample[:, 0], sample[:, 1]))
+    assert np.array_equal(readout(engine, H, W, res, ox, oy, theta, sample), ref[:, 0])
+    return got
+
+
+# ---------------------------------------------------------------- every rank tier
+def tier_map(N=500):
+    """One obstacle in the corner of an N x N map: d2 = r^2 + c^2, whose distinct values pass CODE_ESC for N = 500."""
+    r, c = np.mgrid[0:N, 0:N]
+    return (r * r + c * c).astype(np.int64)
+
+
+@pytest.mark.parametrize('res,theta', [(2.0 ** -5, 0.0), (0.05, 0.0), (0.05, 0.3)])
+def test_every_rank_tier(eng, res, theta):
+    d2 = tier_map()
+    rank = ranks_of(d2)
+    assert rank.max() + 1 == np.unique(d2).size > CODE_ESC + 1, 'the map must cross both tier boundaries'
+    probes = []
+    for k in (0, 1, LDS_RANKS - 1, LDS_RANKS, LDS_RANKS + 1, CODE_ESC - 1, CODE_ESC, CODE_ESC + 1, int(rank.max())):
+        at = np.argwhere(rank == k)
+        assert at.size, k
+        probes.append(at[0])
+        probes.append(at[-1])
+    probes = np.array(probes)
+    tiers = rank[probes[:, 0], probes[:, 1]]
+    assert (tiers < LDS_RANKS).any() and ((tiers >= LDS_RANKS) & (tiers < CODE_ESC)).any() and (tiers >= CODE_ESC).any()
+    check_map(eng, d2, res, -1.25, 3.5, theta, cells=probes)
+    check_map(eng, d2, res, -1.25, 3.5, theta)
+
+
+# ---------------------------------------------------------------- rank-prefix boundaries of the device pipeline
+def _n_words(H):
+    return (H - 1) ** 2 // 32 + 1          # presence-bitmap words of a wall along row 0: max d2 = (H - 1)^2
+
+
+def _height_below(words):
+    """Tallest H x 8 wall map whose bitmap has at most `words` words."""
+    H = 1
+    while _n_words(H + 1) <= words:
+        H += 1
+    return H
+
+
+def _prefix_heights():
+    hs = []
+    for words in (256, SCAN_BLOCK_WORDS, 64 * SCAN_BLOCK_WORDS):   # a wave of rank_word_prefix, a block, a rank_scan_sums chunk
+        h = _height_below(words)
+        hs += [h, h + 1]
+    return hs + [32768]
+
+
+def test_prefix_heights_straddle_the_boundaries():
+    hs = _prefix_heights()
+    words = [_n_words(h) for h in hs]
+    blocks = [-(-w // SCAN_BLOCK_WORDS) for w in words]
+    assert words[0] <= 256 < words[1] and words[2] <= SCAN_BLOCK_WORDS < words[3]
+    assert blocks[2] == 1 and blocks[3] == 2 and blocks[4] == 64 and blocks[5] == 65
+    assert blocks[6] == 32767
+
+
+@pytest.mark.parametrize('H', _prefix_heights())
+def test_rank_prefix_boundaries(eng, H):
+    """A wall along row 0 of an H x 8 map: d2 = r^2 and the rank of row r is r, below CODE_ESC however large d2 gets, so
+    a wrong block or chunk prefix shows up in the LUT value of every cell above it."""
+    r = np.arange(H, dtype=np.int64)
+    d2 = np.repeat((r * r)[:, None], 8, axis=1)
+    assert np.array_equal(ranks_of(d2)[:, 0], r)
+    if H > LDS_RANKS:
+        assert (ranks_of(d2) >= LDS_RANKS).any()
+    check_map(eng, d2, 0.05, 0.0, 0.0, 0.0, n_oracle=500)
+
+
+# ---------------------------------------------------------------- wide rows (edt_rows_kernel with > 64 KiB of LDS)
+@pytest.mark.parametrize('W,density', [(16385, 0.002), (20000, 0.001), (32768, 0.0005)])
+def test_wide_rows(eng, W, density):
+    rng = np.random.default_rng(W)
+    mask = (rng.random((3, W)) >= density).astype(np.uint8)
+    mask[1, rng.integers(W)] = 0
+    mask[:, 5] = 1
+    check_map(eng, edt_d2(mask), 0.05, 0.0, 0.0, 0.0)
+
+
+# ---------------------------------------------------------------- dense random maps and the shipped maps
+@pytest.mark.parametrize('shape,density,res,theta', [((257, 1031), 0.5, 0.05, 0.0), ((1024, 999), 0.05, 2.0 ** -5, 0.0),
+                                                     ((2000, 2000), 0.002, 0.05, 0.3)])
+def test_dense_random_maps(eng, shape, density, res, theta):
+    rng = np.random.default_rng(shape[0] + shape[1])
+    mask = (rng.random(shape) >= density).astype(np.uint8)
+    mask[0, 0] = 0
+    check_map(eng, edt_d2(mask), res, 2.0, -7.5, theta)
+
+
+@pytest.mark.parametrize('name', ['example', 'berlin', 'skirk', 'vegas'])
+def test_shipped_maps_every_cell(eng, name):
+    from red_gym_amd import maps, workload
+    y = workload.EXAMPLE_MAP + '.yaml' if name == 'example' else maps.builtin_map_yaml(name)
+    m = maps.load_map(y, '.png')
+    theta = float(np.arctan2(m.orig_s, m.orig_c))
+    check_map(eng, edt_d2(m.free), m.resolution, m.orig_x, m.orig_y, theta)
+
+
+# ---------------------------------------------------------------- real scans over far and escape cells
+def open_map(N=2000):
+    """A walled N x N room with four pillars: rays of more than 1 000 cells at resolution 0.01, cells of every tier."""
+    mask = np.ones((N, N), np.uint8)
+    mask[0, :] = mask[-1, :] = mask[:, 0] = mask[:, -1] = 0
+    for r, c in ((500, 600), (1400, 1300), (700, 1500), (1600, 400)):
+        mask[r, c] = 0
+    return edt_d2(mask)
+
+
+@pytest.mark.parametrize('which,res,theta', [('tier', 2.0 ** -5, 0.0), ('tier', 0.05, 0.3), ('open', 0.01, 0.0)])
+def test_scans_over_far_and_escape_cells(which, res, theta):
+    from red_gym_amd.engine import Engine
+    d2 = tier_map() if which == 'tier' else open_map()
+    H, W = d2.shape
+    rank = ranks_of(d2)
+    assert (rank >= CODE_ESC).any() and ((rank >= LDS_RANKS) & (rank < CODE_ESC)).any()
+    ox, oy = -3.0, 1.5
+    rng = np.random.default_rng(H + int(res * 1000))
+    n = 160
+    poses = cell_poses(res, ox, oy, theta, rng.uniform(0, H - 1, n), rng.uniform(0, W - 1, n))
+    poses[:, 2] = rng.uniform(-np.pi, np.pi, n)
+    sc = oracle.Scanner(1080, 2 * np.pi)
+    sc.set_map_dict({'height': H, 'width': W, 'resolution': res, 'orig_x': ox, 'orig_y': oy,
+                     'orig_c': float(np.cos(theta)), 'orig_s': float(np.sin(theta)),
+                     'dt': np.ascontiguousarray(res * np.sqrt(d2.astype(np.float64)))})
+    ref, rlk = sc.scan_batch(poses, return_lookups=True)
+    if which == 'open':
+        assert (ref > 1000 * res).any()      # rays of more than 1 000 cells
+    e = Engine(num_envs=1, num_agents=1, noise_std=0)
+    try:
+        for how in PIPELINES:
+            install(e, how, d2, res, ox, oy, theta)
+            out, lk = e.scan(poses, want_lookups=True)
+            assert np.array_equal(_np(out), ref), how
+            assert np.array_equal(_np(lk).astype(np.int64), rlk), how
+    finally:
+        e.close()
+
+
+# ---------------------------------------------------------------- shape limits and refusals
+def _rows_padded(H):
+    return ((H + 2 + 7) >> 3) << 3        # map_rows_padded (f110_kernels.h)
+
+
+def test_strip_addressing_limits(eng):
+    """cell_offset and the march loops multiply (c >> 3) by 16 * rows_padded - 16 as signed 24-bit operands: taller or
+    wider maps are refused, and the limits themselves read out right."""
+    H_max = 1
+    while 16 * _rows_padded(H_max + 1) - 16 < 1 << 23:
+        H_max += 1
+    assert H_max == 524286
+    W_max = (1 << 26) - 1                 # (W >> 3) < 2^23
+    small = tier_map(40)
+    res = 0.05
+    install(eng, 'host_dt', small, res, 0.0, 0.0, 0.0)
+    before = readout(eng, 40, 40, res, 0.0, 0.0, 0.0)
+    # refusals first: a library without them would go on to scan a mis-addressed table
+    with pytest.raises(ValueError, match='24-bit'):
+        eng.set_map_dt(np.zeros((H_max + 1, 16)), res, 0.0, 0.0)
+    with pytest.raises(ValueError, match='24-bit'):
+        eng.set_map_dt(np.zeros((1, W_max + 1)), res, 0.0, 0.0)
+    with pytest.raises(ValueError, match='24-bit'):
+        eng.set_map_dt(np.zeros((5, W_max + 1)), res, 0.0, 0.0)
+    assert np.array_equal(readout(eng, 40, 40, res, 0.0, 0.0, 0.0), before)
+    # the tallest accepted map: its top rows in all 16 columns (8 .. 15 are the second strip)
+    dt = np.zeros((H_max, 16))
+    dt[-3:] = res * np.sqrt(np.arange(1, 49, dtype=np.float64)).reshape(3, 16)
+    dt[:2] = res * np.sqrt(np.arange(100, 132, dtype=np.float64)).reshape(2, 16)
+    eng.set_map_dt(dt, res, 0.0, 0.0)
+    cells = np.array([(r, c) for r in list(range(H_max - 4, H_max)) + [0, 1, H_max // 2] for c in range(16)])
+    assert np.array_equal(readout(eng, H_max, 16, res, 0.0, 0.0, 0.0, cells), dt[cells[:, 0], cells[:, 1]])
+    del dt
+    # the widest accepted map (np.zeros is lazily zero-filled): its first and last strips
+    dt = np.zeros((1, W_max))
+    dt[0, :24] = res * np.sqrt(np.arange(1, 25, dtype=np.float64))
+    dt[0, -24:] = res * np.sqrt(np.arange(200, 224, dtype=np.float64))
+    eng.set_map_dt(dt, res, 0.0, 0.0)
+    cols = np.r_[np.arange(24), W_max - 24 + np.arange(24), (W_max // 2) & ~7]
+    cells = np.stack([np.zeros_like(cols), cols], 1)
+    assert np.array_equal(readout(eng, 1, W_max, res, 0.0, 0.0, 0.0, cells), dt[0, cols])
+    del dt
+
+
+def test_device_pipeline_refuses_a_mask_without_obstacle(eng):
+    """The raw device entry refuses a mask with no occupied cell and leaves the slot as it was."""
+    import torch
+    from red_gym_amd import _lib
+    d2 = tier_map(64)
+    install(eng, 'device', d2, 0.05, 0.0, 0.0, 0.0)
+    before = readout(eng, 64, 64, 0.05, 0.0, 0.0, 0.0)
+    assert np.array_equal(before, 0.05 * np.sqrt(d2.ravel().astype(np.float64)))
+    free = torch.ones((48, 80), dtype=torch.uint8, device='cuda')
+    rc = eng.lib.f110_set_map_slot_occupancy_dev(eng._h, 0, C.c_void_p(free.data_ptr()), 48, 80, C.c_double(0.05),
+                                                 C.c_double(0.0), C.c_double(0.0), C.c_double(1.0), C.c_double(0.0))
+    assert rc == _lib.E_INVALID
+    assert 'no occupied cell' in eng.lib.f110_last_error().decode()
+    assert np.array_equal(readout(eng, 64, 64, 0.05, 0.0, 0.0, 0.0), before)
+
+
+@pytest.mark.parametrize('shape', [(32769, 1), (1, 32769)])
+def test_edt_size_refusals(eng, shape):
+    import torch
+    from red_gym_amd import _lib
+    H, W = shape
+    mask = np.ones(shape, np.uint8)
+    mask[0, 0] = 0
+    m = torch.as_tensor(mask, device='cuda')
+    d2 = torch.empty(shape, dtype=torch.int32, device='cuda')
+    rc = _lib.load().f110_edt_squared_dev(C.c_void_p(m.data_ptr()), H, W, C.c_void_p(d2.data_ptr()),
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == _lib.E_INVALID and '32768' in _lib.load().f110_last_error().decode()
+    with pytest.raises(ValueError, match='32768'):
+        eng.set_map_occupancy(mask, 0.05, 0.0, 0.0)
+    with pytest.raises(ValueError, match='32768'):
+        eng.set_map_occupancy(m, 0.05, 0.0, 0.0)

@@ -273,7 +273,9 @@ def _edt_dev(mask):
 
 
 @pytest.mark.parametrize('shape,density', [((64, 64), 0.02), ((37, 201), 0.005), ((301, 17), 0.1), ((1, 50), 0.1),
-                                           ((50, 1), 0.1), ((257, 513), 0.0003), ((600, 600), 0.5), ((128, 4100), 0.001)])
+                                           ((50, 1), 0.1), ((257, 513), 0.0003), ((600, 600), 0.5), ((128, 4100), 0.001),
+                                           # rows of more than 64 KiB of LDS (edt_rows_kernel through hipFuncSetAttribute)
+                                           ((3, 16385), 0.002), ((3, 20000), 0.001), ((3, 32768), 0.0005)])
 def test_edt_device_matches_host_and_scipy(shape, density):
     from scipy.ndimage import distance_transform_edt
     rng = np.random.default_rng(shape[0] * 1000 + shape[1])
