@@ -471,7 +471,8 @@ __device__ inline double march_fast_limit(const MapView &m) { return (double)((0
 struct ScanArgs {
     const MapDev *maps;         // dev [K] map descriptors
     const int32_t *env_map;     // dev [B] map of every env, or NULL (all envs on maps[0]); the cars of one
-                                // workgroup share a map (f110_assign_maps checks it): its LUT is staged per group
+                                // workgroup share a map (f110_assign_maps checks it for the pairs 2k, 2k+1 of all
+                                // cars; launch_scan keeps every launch and stage at an even car): its LUT is staged per group
     ScanDev scan;
     int n_cars;             // cars of THIS launch: car_base .. car_base + n_cars - 1
     int car_base;           // first car (a shard whose env blocks sit on maps of different kinds -- resolution a power

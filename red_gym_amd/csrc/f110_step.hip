@@ -156,9 +156,13 @@ static std::vector<StageSpec> scan_stage_list(const std::vector<StageSpec> &over
     if (!star) spec.push_back({n_cars - fixed, 0});
     std::vector<StageSpec> stv;
     for (const StageSpec &x : spec) if (x.cars > 0) stv.push_back(x);
-    // a workgroup never mixes two stages: every stage's wave count is a multiple of SCAN_WAVES
+    // Every stage but the last has a car count that is a multiple of SCAN_WAVES, so that every stage starts at such a car
+    // (and a wave count that is one too: a workgroup never mixes two stages).  The two waves of a workgroup of whole cars
+    // then march cars (2k, 2k+1) of the launch, which is the pair f110_assign_maps checks for a shared map: they stage one
+    // LUT copy between them, half each from their own car's map (scan_kernel).  Only the "*" stage can be odd; a wave count
+    // that is even is not enough (65 cars x 2 waves, then whole cars from car 65: cars 79 and 80 in one workgroup).
     for (size_t i = 0; i + 1 < stv.size(); i++)
-        if ((stv[i].cars << stv[i].lg) % SCAN_WAVES) return {{n_cars, 0}};
+        if (stv[i].cars % SCAN_WAVES) return {{n_cars, 0}};
     if (stv.size() > (size_t)SCAN_MAX_STAGES) return {{n_cars, 0}};
     return stv;
 }
@@ -182,6 +186,16 @@ static int launch_scan(f110_handle *h, const ScanArgs &a_in, const Sink &st, hip
             cars += x.cars;
         }
         if (cars != a.n_cars) return fail(F110_E_INVALID, "scan launch: the stages cover %lld cars, the launch has %d", cars, a.n_cars);
+    }
+    // cars on different maps in two-wave workgroups: f110_assign_maps vouched for the pairs (2k, 2k+1) of ALL cars, so the
+    // launch and each of its stages must start at an even car (a car_base across a kind boundary is even: an odd one sets
+    // wg_single)
+    if (a.env_map && !a.wg_single) {
+        long long c0 = a.car_base;
+        for (const StageSpec &x : stv) {
+            if (c0 % SCAN_WAVES) return fail(F110_E_INVALID, "scan launch: a stage of two-wave workgroups on a map per env starts at car %lld", c0);
+            c0 += x.cars;
+        }
     }
     for (int i = 0; i < 8; i++) { a.stage_cars[i] = i < a.n_stages ? stv[i].cars : 0; a.stage_log2w[i] = i < a.n_stages ? stv[i].lg : 0; }
     // the step's scan with streaming stores, except in very large launches (profiles/r04_scan_stores.txt L);

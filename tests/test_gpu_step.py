@@ -515,7 +515,7 @@ def test_check_done_argument_errors():
         check_done(*(args[:6] + [z((2, 2), torch.int64), args[7]]))
 
 
-@pytest.mark.parametrize('spec', ['*:0', '*:1', '*:3', '8:0,*:2', '6:2,*:0,10:1', '20:3,*:0,4:2'])
+@pytest.mark.parametrize('spec', ['*:0', '*:1', '*:3', '8:0,*:2', '6:2,*:0,10:1', '20:3,*:0,4:2', '*:1,32:0', '*:2,16:0,8:1', '*:3,2:0'])
 @pytest.mark.parametrize('A', [1, 2])
 def test_scan_stage_lists_give_identical_results(assets, spec, A):
     """The wave -> car mapping of a scan launch (one wavefront per car, or 2 / 4 / 8 per car splitting its beam queue,
