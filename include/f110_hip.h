@@ -280,7 +280,7 @@ int f110_pack_env(f110_handle *h, int32_t env, double *out_dev, void *stream);
 /* Tuning / test hook: how a scan launch maps wavefronts to cars, as "cars:lg,cars:lg,..." in launch order with one
  * "*" for the remaining cars: a car of a stage gets 2^lg wavefronts (lg = 0..3; several short-lived waves per car pay
  * for small batches and at the end of a launch).  NULL or "" restores the built-in choice (scan_stage_list in
- * csrc/f110_step.hip).  A malformed list (syntax, lg > 3, two "*", more than 6 stages, more cars than the handle
+ * csrc/f110_scan_plan.h).  A malformed list (syntax, lg > 3, two "*", more than 6 stages, more cars than the handle
  * has) is refused with F110_E_INVALID and changes nothing.  A list that does not fit a launch -- a stage before the last
  * with an odd car count (only "*" can have one), fixed stages of more cars than the launch has -- is replaced by one
  * stage of whole cars for that launch.  Results do not depend on it. */

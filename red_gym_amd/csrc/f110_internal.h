@@ -8,6 +8,7 @@
 //   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, scan -> bitmap, occupancy grid
 #pragma once
 #include "../../include/f110_hip.h"
+#include "f110_scan_plan.h"
 #include "f110_kernels.h"
 #include "f110_planner.h"
 #include "f110_bitmap.h"
@@ -103,9 +104,6 @@ using Stream = HipOwner<hipStream_t, hipStreamDestroy>;
 using Graph = HipOwner<hipGraph_t, hipGraphDestroy>;
 using GraphExec = HipOwner<hipGraphExec_t, hipGraphExecDestroy>;
 
-// one stage of a scan launch's wave -> car mapping: `cars` cars (< 0: "*", the remaining cars) at 2^lg waves each
-struct StageSpec { int cars, lg; };
-
 // Where the scan finds a car's noise row: row r of the car's slot is base[(slot * cap + (r & mask)) * num_beams], slot =
 // env_slot[env] (NULL: slot 0).  ScanArgs and the device-resident NoiseDesc both take it from NoiseState::where.
 struct NoiseRows {
@@ -174,7 +172,7 @@ struct f110_handle {
     // Bumped whenever a later f110_step would enqueue different kernels or by-value arguments than an earlier one
     // (a table re-allocated, another scan instantiation selected, buffers re-bound): f110_launch_epoch.
     int64_t epoch = 0;
-    std::vector<StageSpec> stages;    // f110_set_scan_stages override, parsed (empty: the built-in choice, scan_stage_list)
+    std::vector<StageSpec> stages;    // f110_set_scan_stages override, parsed (empty: the built-in choice, f110_scan_plan.h)
     f110_buffers bufs;
     // device tables owned by the handle
     DevBuf<double> d_scan_angles, d_beam_cosines, d_side;

@@ -9,6 +9,7 @@
 #pragma once
 #include "f110_device.h"
 #include "f110_noise.h"
+#include "f110_scan_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -26,7 +27,6 @@ __device__ inline int med3_i32(int x, int lo, int hi)
 // wave-wide vote straight on the condition mask (HIP's __ballot round-trips through a VGPR)
 __device__ inline unsigned long long vote(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
-constexpr int WAVE = 64;
 // bits of the device error word (f110_device_errors; include/f110_hip.h F110_DEVERR_*)
 constexpr uint32_t DEVERR_NOISE_WINDOW = 1u, DEVERR_BOUNDS = 2u;
 
@@ -46,8 +46,6 @@ enum { BT_LUT_CODE, BT_CELLS_FAR, BT_LUT_RANK, BT_DT, BT_NOISE_BEAM, BT_CS_TABLE
 #define F110_BCHK(ok, table, errp) do { } while (0)
 #define F110_BOUNDS_ONLY(...)
 #endif
-constexpr int SCAN_WAVES = 2;   // cars per workgroup, one wavefront each (one-car workgroups: profiles/r05_one_wave_groups.txt)
-constexpr int SCAN_THREADS = SCAN_WAVES * WAVE;
 constexpr int REFILL_MIN_IDLE = 44; // refill the wave's beam slots once this many lanes idle (32 .. 56 swept: profiles/r05_scan_budget.txt)
 
 // Cell table.  Each map cell stores, as a u16, the BYTE OFFSET of its distance inside the LDS copy of the LUT:
@@ -472,7 +470,7 @@ struct ScanArgs {
     const MapDev *maps;         // dev [K] map descriptors
     const int32_t *env_map;     // dev [B] map of every env, or NULL (all envs on maps[0]); the cars of one
                                 // workgroup share a map (f110_assign_maps checks it for the pairs 2k, 2k+1 of all
-                                // cars; launch_scan keeps every launch and stage at an even car): its LUT is staged per group
+                                // cars; plan_scan keeps every launch and stage at an even car): its LUT is staged per group
     ScanDev scan;
     int n_cars;             // cars of THIS launch: car_base .. car_base + n_cars - 1
     int car_base;           // first car (a shard whose env blocks sit on maps of different kinds -- resolution a power
@@ -481,7 +479,7 @@ struct ScanArgs {
     int wpc;                // unused (the waves per car come from the stage list below); kept so that the fields behind
                             // it keep their offsets in the argument block
     // Wave -> (car, part) mapping: consecutive STAGES of cars, stage s giving each of its stage_cars[s] cars
-    // 2^stage_log2w[s] waves (scan_stage_list explains the choice).  Read through `rare`, not held in registers.
+    // 2^stage_log2w[s] waves (f110_scan_plan.h explains the choice).  Read through `rare`, not held in registers.
     int n_stages;
     int stage_cars[8];          // SCAN_MAX_STAGES
     int stage_log2w[8];         // each 0..SCAN_MAX_LOG2W
@@ -534,8 +532,7 @@ constexpr int MAX_CHUNKS = 64; // beams are handed out in chunks of 64 (num_beam
 
 // scan_kernel re-reads its argument block through the kernarg segment pointer, which is only the same block
 // if ScanArgs is the kernel's ONLY argument, passed by value at offset 0, and trivially copyable (the launch
-// memcpy's it).  The stage list is a fixed array inside it: launch_scan checks the count and the exponents.
-constexpr int SCAN_MAX_STAGES = 8, SCAN_MAX_LOG2W = 3;
+// memcpy's it).  The stage list is a fixed array inside it: plan_scan checks the count and the exponents.
 static_assert(__is_trivially_copyable(ScanArgs), "ScanArgs is copied into the kernarg segment byte for byte");
 static_assert(offsetof(ScanArgs, maps) == 0, "kernarg re-read assumes the argument block starts with ScanArgs");
 static_assert(sizeof(((ScanArgs *)0)->stage_cars) == SCAN_MAX_STAGES * sizeof(int) &&

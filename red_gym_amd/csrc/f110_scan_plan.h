@@ -1,0 +1,167 @@
+// f110_scan_plan.h -- the launch plan of a scan: which cars each scan_kernel launch marches, with which instantiation, stage
+// list and grid.  Plain C++17 without HIP (tests/test_scan_plan_cpu.py compiles it for the host); f110_step.hip emits it.
+#pragma once
+#include "../../include/f110_hip.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+int fail(int code, const char *fmt, ...);
+
+namespace f110 {
+
+constexpr int WAVE = 64;
+constexpr int SCAN_WAVES = 2;   // cars per workgroup, one wavefront each (one-car workgroups: profiles/r05_one_wave_groups.txt)
+constexpr int SCAN_THREADS = SCAN_WAVES * WAVE;
+constexpr int SCAN_MAX_STAGES = 8, SCAN_MAX_LOG2W = 3;
+
+// one stage of a scan launch's wave -> car mapping: `cars` cars (< 0: "*", the remaining cars) at 2^lg waves each
+struct StageSpec { int cars, lg; };
+
+// "cars:log2waves,..." with at most one "*": strict syntax (f110_set_scan_stages refuses what this refuses)
+inline bool parse_stage_spec(const char *p, std::vector<StageSpec> &spec, const char **why)
+{
+    spec.clear();
+    int stars = 0;
+    if (!p || !*p) { *why = "empty"; return false; }
+    for (;;) {
+        int cars = -1, lg = 0;
+        if (*p == '*') { p++; stars++; }
+        else if (*p >= '0' && *p <= '9') {
+            long v = strtol(p, (char **)&p, 10);
+            if (v > 0x3fffffff) { *why = "car count too large"; return false; }
+            cars = (int)v;
+        } else { *why = "expected a car count or *"; return false; }
+        if (*p == ':') {
+            p++;
+            if (!(*p >= '0' && *p <= '9')) { *why = "expected log2(waves per car) after ':'"; return false; }
+            long v = strtol(p, (char **)&p, 10);
+            if (v > SCAN_MAX_LOG2W) { *why = "log2(waves per car) above 3"; return false; }
+            lg = (int)v;
+        }
+        spec.push_back({cars, lg});
+        if (*p == ',') { p++; continue; }
+        if (*p) { *why = "unexpected character"; return false; }
+        break;
+    }
+    if (stars > 1) { *why = "more than one *"; return false; }
+    if (spec.size() > 6) { *why = "more than 6 stages"; return false; }
+    return true;
+}
+
+// The wave -> car mapping of a scan launch of n_cars cars: a list of stages (cars, log2 waves per car), from the
+// f110_set_scan_stages override or, without one, the built-in choice.
+// Drain of a launch: workgroups are dispatched in index order and nothing follows the last ones,
+// so the chip empties over one wave lifetime (about half of it lost: ~5 % at 65 536 cars -- the gap
+// that two half-size launches from two processes close by overlapping).  The last cars therefore
+// run as 4 short waves each ("*:0,2048:2" for big launches of one agent per env).
+// Measured (profiles/r01j): 65 536 cars 0.702 -> 0.672 ms for any tail of 1 000 .. 2 048 cars (it has to
+// cover the last of the slowest cars), 32 768: 0.380 -> 0.368, 16 384: 0.225 -> 0.218, 8 192: neutral,
+// 4 096: 0.126 -> 0.105 with half of the cars split; graded tails (halves, quarters, eighths) and graded
+// heads changed nothing.
+// (Measured and dropped in round 2, profiles/r02_multicar_waves_sweep.txt: stages that give one wave K = 2, 4, 8
+// consecutive cars to march back to back, so that a wave drains once per K cars -- 0.705 ms at best against
+// 0.664 ms: the leaner refill of one car per wave and the finer-grained launch win.)
+inline std::vector<StageSpec> scan_stage_list(const std::vector<StageSpec> &override_spec, int n_cars, int agents, int num_beams)
+{
+    std::vector<StageSpec> spec = override_spec;
+    if (spec.empty()) {
+        // Waves per car.  Measured on MI355X (profiles/r01g, r01i): a wave's lifetime is bounded
+        // below by its longest ray (~50 us), so splitting a car's beams over several waves only
+        // pays while the chip is nearly empty: scan time at 256 / 1024 cars 76 -> 49 us and
+        // 87 -> 65 us with 8 waves per car, but 121 -> 143 us at 4096 cars (prologues and the
+        // shorter queues' tails eat the extra parallelism).
+        int wpc = n_cars <= 1024 ? 8 : (n_cars <= 2048 ? 4 : 1);
+        const int nch = (num_beams + 63) / 64;
+        while (wpc > 1 && wpc > nch) wpc /= 2;
+        // split cars (a small launch) or a short scan (fewer than 8 chunks of 64 beams): one stage
+        if (wpc > 1 || nch < 8) return {{n_cars, wpc >= 8 ? 3 : wpc >= 4 ? 2 : wpc >= 2 ? 1 : 0}};
+        // (envs of several agents: 4 096 -- 16 384 x 2: scan 0.396 -> 0.388 ms, 32 768 x 2: 0.697 -> 0.672; 8 192 x 4: flat;
+        // one agent: 4 096 is 1 % worse than 2 048 at 65 536 cars and 2.5 % worse at 32 768; profiles/r04_scan_stores.txt N)
+        const int tail = std::min(agents >= 2 ? 4096 : 2048, n_cars / 2);
+        spec = {{-1, 0}, {tail, 2}};
+    }
+    int fixed = 0;
+    for (StageSpec &x : spec) if (x.cars >= 0) { x.cars -= x.cars % SCAN_WAVES; fixed += x.cars; }
+    // a list written for the step's car count may not fit a function-level scan of fewer poses: whole cars then
+    if (fixed > n_cars) { spec = {{-1, 0}}; fixed = 0; }
+    bool star = false;
+    for (StageSpec &x : spec) if (x.cars < 0 && !star) { x.cars = n_cars - fixed; star = true; }
+    if (!star) spec.push_back({n_cars - fixed, 0});
+    std::vector<StageSpec> stv;
+    for (const StageSpec &x : spec) if (x.cars > 0) stv.push_back(x);
+    // Every stage but the last has a car count that is a multiple of SCAN_WAVES, so that every stage starts at such a car
+    // (and a wave count that is one too: a workgroup never mixes two stages).  The two waves of a workgroup of whole cars
+    // then march cars (2k, 2k+1) of the launch, which is the pair f110_assign_maps checks for a shared map: they stage one
+    // LUT copy between them, half each from their own car's map (scan_kernel).  Only the "*" stage can be odd; a wave count
+    // that is even is not enough (65 cars x 2 waves, then whole cars from car 65: cars 79 and 80 in one workgroup).
+    for (size_t i = 0; i + 1 < stv.size(); i++)
+        if (stv[i].cars % SCAN_WAVES) return {{n_cars, 0}};
+    if (stv.size() > (size_t)SCAN_MAX_STAGES) return {{n_cars, 0}};
+    return stv;
+}
+
+struct ScanPlanIn {
+    int n_cars, agents, num_beams;      // of the whole scan: the shard's cars, or f110_scan's poses (one agent each)
+    const std::vector<StageSpec> *stages; // f110_set_scan_stages override (empty: the built-in choice)
+    bool step;                          // the step's scan (else f110_scan's)
+    const char *stores;                 // F110_SCAN_STORES: "plain", anything else (streaming stores) or NULL (unset)
+    bool multi, wg_single;              // the scan reads a map per env; neighbouring cars on different maps (f110_assign_maps)
+    int kind;                           // AND over the used map slots of their kinds (ScanLaunch::kind)
+};
+
+struct ScanLaunch {
+    int car_base, n_cars;
+    int kind;                           // scan_kernel's IDENT | POW2 << 1 (origin unrotated / resolution 2^k on all its maps)
+    int sm;                             // scan_kernel's SM: 0 f110_scan, 1 the step's, 2 the step's with plain stores
+    int n_stages, stage_cars[SCAN_MAX_STAGES], stage_log2w[SCAN_MAX_STAGES]; // as in ScanArgs
+    int grid, block;
+    bool wg_single, order, events;      // workgroups of one wave; f110_set_scan_order applies (not on a map per env: a
+                                        // workgroup stages one LUT); carries the event pair
+};
+
+// The launches of one scan in launch order, or an error code (message through fail) where they would break what scan_kernel
+// assumes of its stage list.  env_kind(env), the kind of an env's map, is called only when the scan is split.
+template <typename EnvKind>
+int plan_scan(const ScanPlanIn &in, EnvKind env_kind, std::vector<ScanLaunch> &out)
+{
+    // env blocks on maps of different kinds: one launch per run of envs of one kind, so that a single map with an odd
+    // resolution or a rotated origin does not put every car on the general instantiation
+    const bool split = in.multi && in.kind != 3;
+    const int num_envs = in.n_cars / in.agents;
+    out.clear();
+    for (int e0 = 0, e1 = num_envs; e0 < num_envs; e0 = e1) {
+        ScanLaunch l = {};
+        l.kind = split ? env_kind(e0) : in.kind;
+        if (split)
+            for (e1 = e0 + 1; e1 < num_envs && env_kind(e1) == l.kind; e1++) {}
+        l.car_base = e0 * in.agents; l.n_cars = (e1 - e0) * in.agents;
+        l.wg_single = in.multi && in.wg_single; l.order = in.step && !in.multi; l.events = in.step && e0 == 0;
+        const std::vector<StageSpec> stv = scan_stage_list(*in.stages, l.n_cars, in.agents, in.num_beams);
+        // what the kernel assumes about the stage list, checked here where a mistake costs an error code instead of a
+        // wave -> car mapping that runs off the argument block
+        if (stv.size() < 1 || stv.size() > (size_t)SCAN_MAX_STAGES) return fail(F110_E_INVALID, "scan launch: %d stages (1..%d)", (int)stv.size(), SCAN_MAX_STAGES);
+        // cars on different maps in two-wave workgroups: f110_assign_maps vouched for the pairs (2k, 2k+1) of ALL cars, so the
+        // launch and each of its stages must start at an even car (a car_base across a kind boundary is even: an odd one sets
+        // wg_single)
+        long long cars = 0, waves = 0;
+        for (const StageSpec &x : stv) {
+            if (x.cars < 0 || x.lg < 0 || x.lg > SCAN_MAX_LOG2W) return fail(F110_E_INVALID, "scan launch: stage (%d cars, 2^%d waves per car) out of range", x.cars, x.lg);
+            if (in.multi && !l.wg_single && (l.car_base + cars) % SCAN_WAVES) return fail(F110_E_INVALID, "scan launch: a stage of two-wave workgroups on a map per env starts at car %lld", l.car_base + cars);
+            l.stage_cars[l.n_stages] = x.cars; l.stage_log2w[l.n_stages++] = x.lg;
+            cars += x.cars; waves += x.cars << x.lg;
+        }
+        if (cars != l.n_cars) return fail(F110_E_INVALID, "scan launch: the stages cover %lld cars, the launch has %d", cars, l.n_cars);
+        // the step's scan with streaming stores, except in very large launches (profiles/r04_scan_stores.txt L)
+        const bool plain = in.stores ? strcmp(in.stores, "plain") == 0 : l.n_cars > 327680;
+        l.sm = !in.step ? 0 : plain ? 2 : 1;
+        l.grid = (int)(l.wg_single ? waves : (waves + SCAN_WAVES - 1) / SCAN_WAVES);
+        l.block = l.wg_single ? WAVE : SCAN_THREADS;
+        out.push_back(l);
+    }
+    return F110_OK;
+}
+
+} // namespace f110

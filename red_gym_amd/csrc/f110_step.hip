@@ -37,76 +37,19 @@ static int emit(const Sink &k, const void *func, dim3 grid, dim3 block, unsigned
     return F110_OK;
 }
 
-static Sink make_sink(f110_handle *h, hipStream_t st, std::vector<KernelLaunch> *record = nullptr);
-
-static ScanDev scan_dev(const f110_handle *h)
+// The argument block every scan launch starts from: n_cars cars of `agents` agents each at pose_src (x, y at 0 and 1, yaw at
+// yaw_off, pose_stride apart) and the outputs.  The step's scan adds its buffers, the plan each launch's cars and stages.
+static ScanArgs scan_args(const f110_handle *h, int n_cars, int agents, const double *pose_src, int pose_stride, int yaw_off,
+                          float *out_f32, double *out_f64, uint32_t *lookups)
 {
-    ScanDev s;
-    s.nb = h->cfg.num_beams; s.theta_dis = h->cfg.theta_dis; s.fov = h->cfg.fov; s.eps = h->cfg.eps;
-    s.max_range = h->cfg.max_range; s.inc = h->theta_inc; s.inc_fx = (unsigned long long)std::llround(h->theta_inc * 1099511627776.0); s.cs_len = (int)h->d_cs.size(); s.cs = h->d_cs.get();
+    ScanArgs s;
+    memset(&s, 0, sizeof(s));
+    ScanDev &d = s.scan;
+    d.nb = h->cfg.num_beams; d.theta_dis = h->cfg.theta_dis; d.fov = h->cfg.fov; d.eps = h->cfg.eps;
+    d.max_range = h->cfg.max_range; d.inc = h->theta_inc; d.inc_fx = (unsigned long long)std::llround(h->theta_inc * 1099511627776.0); d.cs_len = (int)h->d_cs.size(); d.cs = h->d_cs.get();
+    s.maps = h->d_maps.get(); s.n_maps = F110_MAX_MAPS; s.n_cars = n_cars; s.agents = agents; s.chunk_beam0 = h->d_chunk0.get();
+    s.pose_src = pose_src; s.pose_stride = pose_stride; s.yaw_off = yaw_off; s.out_f32 = out_f32; s.out_f64 = out_f64; s.lookups = lookups;
     return s;
-}
-
-// ev0 / ev1 (measurement aid, may be null): start / stop events attached to the dispatch itself, which costs
-// less than bracketing the launch with two hipEventRecord calls (those add two barrier packets to the queue)
-// which scan instantiation a launch may use: origin unrotated / resolution a power of two for EVERY map its cars touch
-struct MapKind { bool ident, pow2; };
-
-template <int SM>
-static int launch_scan_t(MapKind kind, const ScanArgs &a, const Sink &k, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr)
-{
-    int waves = 0;
-    for (int i = 0; i < a.n_stages; i++) waves += a.stage_cars[i] << a.stage_log2w[i];
-    const dim3 grid(a.wg_single ? waves : (waves + SCAN_WAVES - 1) / SCAN_WAVES), block(a.wg_single ? WAVE : SCAN_THREADS);
-    const void *f = kind.ident && kind.pow2 ? (const void *)&scan_kernel<true, true, SM>
-                  : kind.ident              ? (const void *)&scan_kernel<true, false, SM>
-                  : kind.pow2               ? (const void *)&scan_kernel<false, true, SM>
-                                        : (const void *)&scan_kernel<false, false, SM>;
-    return emit(k, f, grid, block, 0, a, ev0, ev1);
-}
-
-// Waves per car.  Measured on MI355X (profiles/r01g, r01i): a wave's lifetime is bounded
-// below by its longest ray (~50 us), so splitting a car's beams over several waves only
-// pays while the chip is nearly empty: scan time at 256 / 1024 cars 76 -> 49 us and
-// 87 -> 65 us with 8 waves per car, but 121 -> 143 us at 4096 cars (prologues and the
-// shorter queues' tails eat the extra parallelism).
-static int waves_per_car(int n_cars, int num_beams)
-{
-    int wpc = n_cars <= 1024 ? 8 : (n_cars <= 2048 ? 4 : 1);
-    const int nch = (num_beams + 63) / 64;
-    while (wpc > 1 && wpc > nch) wpc /= 2;
-    return wpc;
-}
-
-// "cars:log2waves,..." with at most one "*": strict syntax (f110_set_scan_stages refuses what this refuses)
-static bool parse_stage_spec(const char *p, std::vector<StageSpec> &spec, const char **why)
-{
-    spec.clear();
-    int stars = 0;
-    if (!p || !*p) { *why = "empty"; return false; }
-    for (;;) {
-        int cars = -1, lg = 0;
-        if (*p == '*') { p++; stars++; }
-        else if (*p >= '0' && *p <= '9') {
-            long v = strtol(p, (char **)&p, 10);
-            if (v > 0x3fffffff) { *why = "car count too large"; return false; }
-            cars = (int)v;
-        } else { *why = "expected a car count or *"; return false; }
-        if (*p == ':') {
-            p++;
-            if (!(*p >= '0' && *p <= '9')) { *why = "expected log2(waves per car) after ':'"; return false; }
-            long v = strtol(p, (char **)&p, 10);
-            if (v > SCAN_MAX_LOG2W) { *why = "log2(waves per car) above 3"; return false; }
-            lg = (int)v;
-        }
-        spec.push_back({cars, lg});
-        if (*p == ',') { p++; continue; }
-        if (*p) { *why = "unexpected character"; return false; }
-        break;
-    }
-    if (stars > 1) { *why = "more than one *"; return false; }
-    if (spec.size() > 6) { *why = "more than 6 stages"; return false; }
-    return true;
 }
 
 // Every pointer a scan launch dereferences without a test of its own, checked on the host: a null here is an error
@@ -122,114 +65,35 @@ static int check_scan_args(const ScanArgs &a, const char *who)
     return F110_OK;
 }
 
-// The wave -> car mapping of a scan launch of n_cars cars: a list of stages (cars, log2 waves per car), from the
-// f110_set_scan_stages override or, without one, the built-in choice.
-// Drain of a launch: workgroups are dispatched in index order and nothing follows the last ones,
-// so the chip empties over one wave lifetime (about half of it lost: ~5 % at 65 536 cars -- the gap
-// that two half-size launches from two processes close by overlapping).  The last cars therefore
-// run as 4 short waves each ("*:0,2048:2" for big launches of one agent per env).
-// Measured (profiles/r01j): 65 536 cars 0.702 -> 0.672 ms for any tail of 1 000 .. 2 048 cars (it has to
-// cover the last of the slowest cars), 32 768: 0.380 -> 0.368, 16 384: 0.225 -> 0.218, 8 192: neutral,
-// 4 096: 0.126 -> 0.105 with half of the cars split; graded tails (halves, quarters, eighths) and graded
-// heads changed nothing.
-// (Measured and dropped in round 2, profiles/r02_multicar_waves_sweep.txt: stages that give one wave K = 2, 4, 8
-// consecutive cars to march back to back, so that a wave drains once per K cars -- 0.705 ms at best against
-// 0.664 ms: the leaner refill of one car per wave and the finer-grained launch win.)
-static std::vector<StageSpec> scan_stage_list(const std::vector<StageSpec> &override_spec, int n_cars, int agents, int num_beams)
-{
-    std::vector<StageSpec> spec = override_spec;
-    if (spec.empty()) {
-        const int wpc = waves_per_car(n_cars, num_beams), nch = (num_beams + 63) / 64;
-        // split cars (a small launch) or a short scan (fewer than 8 chunks of 64 beams): one stage
-        if (wpc > 1 || nch < 8) return {{n_cars, wpc >= 8 ? 3 : wpc >= 4 ? 2 : wpc >= 2 ? 1 : 0}};
-        // (envs of several agents: 4 096 -- 16 384 x 2: scan 0.396 -> 0.388 ms, 32 768 x 2: 0.697 -> 0.672; 8 192 x 4: flat;
-        // one agent: 4 096 is 1 % worse than 2 048 at 65 536 cars and 2.5 % worse at 32 768; profiles/r04_scan_stores.txt N)
-        const int tail = std::min(agents >= 2 ? 4096 : 2048, n_cars / 2);
-        spec = {{-1, 0}, {tail, 2}};
-    }
-    int fixed = 0;
-    for (StageSpec &x : spec) if (x.cars >= 0) { x.cars -= x.cars % SCAN_WAVES; fixed += x.cars; }
-    // a list written for the step's car count may not fit a function-level scan of fewer poses: whole cars then
-    if (fixed > n_cars) { spec = {{-1, 0}}; fixed = 0; }
-    bool star = false;
-    for (StageSpec &x : spec) if (x.cars < 0 && !star) { x.cars = n_cars - fixed; star = true; }
-    if (!star) spec.push_back({n_cars - fixed, 0});
-    std::vector<StageSpec> stv;
-    for (const StageSpec &x : spec) if (x.cars > 0) stv.push_back(x);
-    // Every stage but the last has a car count that is a multiple of SCAN_WAVES, so that every stage starts at such a car
-    // (and a wave count that is one too: a workgroup never mixes two stages).  The two waves of a workgroup of whole cars
-    // then march cars (2k, 2k+1) of the launch, which is the pair f110_assign_maps checks for a shared map: they stage one
-    // LUT copy between them, half each from their own car's map (scan_kernel).  Only the "*" stage can be odd; a wave count
-    // that is even is not enough (65 cars x 2 waves, then whole cars from car 65: cars 79 and 80 in one workgroup).
-    for (size_t i = 0; i + 1 < stv.size(); i++)
-        if (stv[i].cars % SCAN_WAVES) return {{n_cars, 0}};
-    if (stv.size() > (size_t)SCAN_MAX_STAGES) return {{n_cars, 0}};
-    return stv;
-}
+// scan_kernel<IDENT, POW2, SM> by [SM][IDENT | POW2 << 1]
+#define SCAN_KERNELS(SM) {(const void *)&scan_kernel<false, false, SM>, (const void *)&scan_kernel<true, false, SM>, \
+                          (const void *)&scan_kernel<false, true, SM>, (const void *)&scan_kernel<true, true, SM>}
+static const void *const scan_kernels[3][4] = {SCAN_KERNELS(0), SCAN_KERNELS(1), SCAN_KERNELS(2)};
 
-static int launch_scan(f110_handle *h, const ScanArgs &a_in, const Sink &st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                       const MapKind *kind_or_null = nullptr)
+// The scan of `a` -- the step's when a.state is set, else f110_scan's -- as f110_scan_plan.h plans it.  ev0 / ev1 (measurement
+// aid, may be null) ride on the step's first launch: start / stop events attached to the dispatch itself, which costs less than
+// bracketing the launch with two hipEventRecord calls (those add two barrier packets to the queue).
+static int run_scan(const f110_handle *h, const ScanArgs &a, const Sink &k, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr)
 {
-    const MapKind kind = kind_or_null ? *kind_or_null : MapKind{h->ident, h->pow2};
-    int rc_args = check_scan_args(a_in, "scan launch");
-    if (rc_args) return rc_args;
-    ScanArgs a = a_in;
-    const std::vector<StageSpec> stv = scan_stage_list(h->stages, a.n_cars, a.agents, a.scan.nb);
-    a.n_stages = (int)stv.size();
-    // what the kernel assumes about the stage list, checked here where a mistake costs an error code instead of a
-    // wave -> car mapping that runs off the argument block
-    if (a.n_stages < 1 || a.n_stages > SCAN_MAX_STAGES) return fail(F110_E_INVALID, "scan launch: %d stages (1..%d)", a.n_stages, SCAN_MAX_STAGES);
-    {
-        long long cars = 0;
-        for (const StageSpec &x : stv) {
-            if (x.cars < 0 || x.lg < 0 || x.lg > SCAN_MAX_LOG2W) return fail(F110_E_INVALID, "scan launch: stage (%d cars, 2^%d waves per car) out of range", x.cars, x.lg);
-            cars += x.cars;
-        }
-        if (cars != a.n_cars) return fail(F110_E_INVALID, "scan launch: the stages cover %lld cars, the launch has %d", cars, a.n_cars);
-    }
-    // cars on different maps in two-wave workgroups: f110_assign_maps vouched for the pairs (2k, 2k+1) of ALL cars, so the
-    // launch and each of its stages must start at an even car (a car_base across a kind boundary is even: an odd one sets
-    // wg_single)
-    if (a.env_map && !a.wg_single) {
-        long long c0 = a.car_base;
-        for (const StageSpec &x : stv) {
-            if (c0 % SCAN_WAVES) return fail(F110_E_INVALID, "scan launch: a stage of two-wave workgroups on a map per env starts at car %lld", c0);
-            c0 += x.cars;
-        }
-    }
-    for (int i = 0; i < 8; i++) { a.stage_cars[i] = i < a.n_stages ? stv[i].cars : 0; a.stage_log2w[i] = i < a.n_stages ? stv[i].lg : 0; }
-    // the step's scan with streaming stores, except in very large launches (profiles/r04_scan_stores.txt L);
-    // F110_SCAN_STORES=plain|stream overrides: test_plain_store_instantiation_matches_streaming reaches scan_kernel<.., 2>,
-    // which no test size does otherwise, through it
+    if (int rc = check_scan_args(a, "scan launch")) return rc;
+    // F110_SCAN_STORES=plain|stream overrides the plan's choice of stores: test_plain_store_instantiation_matches_streaming
+    // reaches scan_kernel<.., 2>, which no test size does otherwise, through it
     static const char *stores_env = getenv("F110_SCAN_STORES");
-    const bool plain = stores_env ? strcmp(stores_env, "plain") == 0 : a.n_cars > 327680;
-    return !a.state ? launch_scan_t<0>(kind, a, st, ev0, ev1) : plain ? launch_scan_t<2>(kind, a, st, ev0, ev1) : launch_scan_t<1>(kind, a, st, ev0, ev1);
-}
-
-static void fill_scan_args(const f110_handle *h, ScanArgs &s, int reset_only)
-{
-    const f110_config &c = h->cfg;
-    const f110_buffers &b = h->bufs;
-    s.maps = h->d_maps.get(); s.env_map = h->multi ? h->d_env_map.get() : nullptr; s.scan = scan_dev(h); s.n_cars = c.num_envs * c.num_agents; s.agents = c.num_agents;
-    s.pose_src = b.state; s.pose_stride = 7; s.yaw_off = 4;
-    s.state = b.state; s.noise_step = b.noise_step; s.chunk_beam0 = h->d_chunk0.get();
-    s.side = h->d_side.get(); s.side_max = h->side_max;
-    const NoiseRows nr = h->noise.where(c.num_envs);
-    s.noise_base = nr.base; s.noise_cap = nr.cap; s.noise_mask = nr.mask; s.noise_slots = nr.slots; s.env_noise = nr.env_slot;
-    s.dev_err = h->d_err.get();
-    s.order = (h->scan_order && !h->multi) ? h->scan_order : nullptr; // (a workgroup stages one LUT: car order when maps differ)
-    s.wg_single = h->multi && h->wg_single; s.n_maps = F110_MAX_MAPS;
-    s.beam_cosines = h->d_beam_cosines.get(); s.ttc_thresh = c.ttc_thresh;
-    s.in_collision = b.in_collision; s.pending_reset = b.pending_reset; s.reset_only = reset_only;
-    s.out_f32 = b.scans; s.out_f64 = b.scans_f64; s.lookups = b.lookups;
-}
-
-// Instrumentation follows the measurement aid's sampling: while f110_profile_begin is active, the per-car lookup counters
-// are only fed by the steps that also carry the event pair (an atomic per wave costs 2.5 % of a 65 536-env step,
-// profiles/r03_event_cost.txt), so bytes and time of the roofline come from the same launches.
-static void sample_lookups(const f110_handle *h, bool sampled_step, ScanArgs &s)
-{
-    if (h->prof_on && !sampled_step) s.lookups = nullptr;
+    ScanPlanIn in;
+    in.n_cars = a.n_cars; in.agents = a.agents; in.num_beams = a.scan.nb; in.stages = &h->stages; in.step = a.state != nullptr;
+    in.stores = stores_env; in.multi = a.env_map != nullptr; in.wg_single = h->wg_single; in.kind = h->ident | h->pow2 << 1;
+    std::vector<ScanLaunch> plan;
+    if (int rc = plan_scan(in, [h](int env) { const f110_handle::MapSlot &m = h->slots[h->h_env_map[env]]; return m.ident | m.pow2 << 1; }, plan))
+        return rc;
+    for (const ScanLaunch &l : plan) {
+        ScanArgs s = a;
+        s.car_base = l.car_base; s.n_cars = l.n_cars; s.wg_single = l.wg_single; s.order = l.order ? h->scan_order : nullptr;
+        s.n_stages = l.n_stages; memcpy(s.stage_cars, l.stage_cars, sizeof(s.stage_cars)); memcpy(s.stage_log2w, l.stage_log2w, sizeof(s.stage_log2w));
+        if (int rc = emit(k, scan_kernels[l.sm][l.kind], dim3(l.grid), dim3(l.block), 0, s, l.events ? ev0 : nullptr,
+                          l.events ? ev1 : nullptr))
+            return rc;
+    }
+    return F110_OK;
 }
 
 // The step of every env: dynamics_kernel -> scan_kernel -> env_kernel, or for A > 1 -> post_scan_kernel (env bookkeeping and
@@ -265,27 +129,19 @@ static int run_step(f110_handle *h, const double *actions, int reset_only, const
 
     // the scan (the launch the measurement aid brackets)
     {
-        ScanArgs s;
-        memset(&s, 0, sizeof(s));
-        fill_scan_args(h, s, reset_only);
-        sample_lookups(h, prof, s);
-        if (h->multi && !(h->ident && h->pow2)) {
-            // env blocks on maps of different kinds: one launch per run of envs of one kind, so that a single map with an
-            // odd resolution or a rotated origin does not put every car on the general instantiation
-            int e0 = 0;
-            rc = F110_OK;
-            while (e0 < c.num_envs && !rc) {
-                const f110_handle::MapSlot &s0 = h->slots[h->h_env_map[e0]];
-                int e1 = e0 + 1;
-                while (e1 < c.num_envs && h->slots[h->h_env_map[e1]].ident == s0.ident && h->slots[h->h_env_map[e1]].pow2 == s0.pow2) e1++;
-                ScanArgs sub = s;
-                sub.car_base = e0 * c.num_agents;
-                sub.n_cars = (e1 - e0) * c.num_agents;
-                const MapKind kind{s0.ident, s0.pow2};
-                rc = launch_scan(h, sub, st, e0 == 0 ? ev0 : nullptr, e0 == 0 ? ev1 : nullptr, &kind);
-                e0 = e1;
-            }
-        } else rc = launch_scan(h, s, st, ev0, ev1);
+        // Instrumentation follows the measurement aid's sampling: while f110_profile_begin is active, the per-car lookup
+        // counters are only fed by the steps that also carry the event pair (an atomic per wave costs 2.5 % of a 65 536-env
+        // step, profiles/r03_event_cost.txt), so bytes and time of the roofline come from the same launches.
+        ScanArgs s = scan_args(h, N, c.num_agents, b.state, 7, 4, b.scans, b.scans_f64, h->prof_on && !prof ? nullptr : b.lookups);
+        s.env_map = h->multi ? h->d_env_map.get() : nullptr;
+        s.state = b.state; s.noise_step = b.noise_step;
+        s.side = h->d_side.get(); s.side_max = h->side_max;
+        const NoiseRows nr = h->noise.where(c.num_envs);
+        s.noise_base = nr.base; s.noise_cap = nr.cap; s.noise_mask = nr.mask; s.noise_slots = nr.slots; s.env_noise = nr.env_slot;
+        s.dev_err = h->d_err.get();
+        s.beam_cosines = h->d_beam_cosines.get(); s.ttc_thresh = c.ttc_thresh;
+        s.in_collision = b.in_collision; s.pending_reset = b.pending_reset; s.reset_only = reset_only;
+        rc = run_scan(h, s, st, ev0, ev1);
     }
     if (rc) return rc;
     if (prof) h->prof_n++;
@@ -312,14 +168,6 @@ static int run_step(f110_handle *h, const double *actions, int reset_only, const
     const int npairs = N * (c.num_agents - 1);
     if ((rc = emit(st, (const void *)&post_scan_kernel, dim3(env_blocks + (4 * npairs + 127) / 128), dim3(128), 0, ps))) return rc; // four lanes per pair
     return emit(st, (const void *)&opp_apply_kernel, dim3((int)(((long long)OPP_GROUP * N + 255) / 256)), dim3(256), 0, ps.o); // OPP_GROUP lanes per car
-}
-
-static Sink make_sink(f110_handle *h, hipStream_t st, std::vector<KernelLaunch> *record)
-{
-    Sink k;
-    (void)h;
-    k.st = st; k.record = record;
-    return k;
 }
 
 static int check_ready(f110_handle *h, const char *who, bool launches_on_callers_stream = true)
@@ -353,7 +201,7 @@ extern "C" int f110_reset(f110_handle *h, const double *poses, const uint8_t *ma
                        c.num_agents, h->bufs.spawn, h->bufs.pending_reset);
     HIP_TRY(hipGetLastError());
     // the zero-action step of F110Env.reset; actions are not read for pending envs
-    return run_step(h, nullptr, 1, make_sink(h, st));
+    return run_step(h, nullptr, 1, Sink{st});
 }
 
 extern "C" int f110_step(f110_handle *h, const double *actions, void *stream)
@@ -361,7 +209,7 @@ extern "C" int f110_step(f110_handle *h, const double *actions, void *stream)
     int rc = check_ready(h, "f110_step");
     if (rc) return rc;
     if (!actions) return fail(F110_E_INVALID, "f110_step: null actions");
-    return run_step(h, actions, 0, make_sink(h, (hipStream_t)stream));
+    return run_step(h, actions, 0, Sink{(hipStream_t)stream});
 }
 
 // ---------------------------------------------------------------- one env's observation in one buffer
@@ -419,7 +267,7 @@ extern "C" int f110_graph_create(f110_handle *h, const double *actions, int32_t 
     h->prof_on = false; // events cannot ride on graph nodes
     hipError_t e = hipSuccess;
     if (how == F110_GRAPH_NODES) {
-        rc = run_step(h, actions, 0, make_sink(h, nullptr, &g->launches));
+        rc = run_step(h, actions, 0, Sink{nullptr, &g->launches});
         if (!rc) {
             e = hipGraphCreate(g->graph.put(), 0);
             hipGraphNode_t prev = nullptr;
@@ -440,7 +288,7 @@ extern "C" int f110_graph_create(f110_handle *h, const double *actions, int32_t 
         e = hipStreamCreateWithFlags(g->cap.put(), hipStreamNonBlocking);
         if (e == hipSuccess) e = hipStreamBeginCapture(g->cap.get(), hipStreamCaptureModeThreadLocal);
         if (e == hipSuccess) {
-            rc = run_step(h, actions, 0, make_sink(h, g->cap.get()));
+            rc = run_step(h, actions, 0, Sink{g->cap.get()});
             e = hipStreamEndCapture(g->cap.get(), g->graph.put());
             size_t n = 0;
             if (e == hipSuccess && hipGraphGetNodes(g->graph.get(), nullptr, &n) == hipSuccess) g->nodes = (int)n;
@@ -563,99 +411,83 @@ extern "C" int f110_scan(f110_handle *h, const double *poses, int32_t n, double 
     if (n == 0) return F110_OK;
     if (!poses || (!out64 && !out32)) return fail(F110_E_INVALID, "f110_scan: null pose or output pointer");
     if (int rc = check_device(h, "f110_scan")) return rc;
-    ScanArgs s;
-    memset(&s, 0, sizeof(s));
-    s.maps = h->d_maps.get(); s.n_maps = F110_MAX_MAPS; s.scan = scan_dev(h); s.n_cars = n; s.agents = 1;
-    s.pose_src = poses; s.pose_stride = 3; s.yaw_off = 2;
-    s.out_f32 = out32; s.out_f64 = out64; s.lookups = lookups; s.chunk_beam0 = h->d_chunk0.get();
-    Sink k;
-    k.st = (hipStream_t)stream;
-    return launch_scan(h, s, k);
+    return run_scan(h, scan_args(h, n, 1, poses, 3, 2, out32, out64, lookups), Sink{(hipStream_t)stream});
+}
+
+// The function-level entry points but f110_scan and f110_check_done: n == 0 does nothing, a null pointer or a bad count is
+// F110_E_INVALID, the caller's current device must be the handle's; then `launch` enqueues the kernel on the caller's stream.
+template <typename Launch>
+static int launch_entry_point(f110_handle *h, int n, bool args_ok, const char *who, Launch launch)
+{
+    if (h && n == 0) return F110_OK;
+    if (!h || !args_ok || n < 0) return fail(F110_E_INVALID, "%s: bad arguments", who);
+    if (int rc = check_device(h, who)) return rc;
+    launch();
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
 }
 
 extern "C" int f110_update_pose(f110_handle *h, double *state, double *steer_buf, int32_t *steer_cnt,
                                 const double *actions, int32_t n, void *stream)
 {
-    if (h && n == 0) return F110_OK;
-    if (!h || !state || !steer_buf || !steer_cnt || !actions || n < 0)
-        return fail(F110_E_INVALID, "f110_update_pose: bad arguments");
-    if (int rc = check_device(h, "f110_update_pose")) return rc;
-    DynArgs d;
-    memset(&d, 0, sizeof(d));
-    d.n_cars = n; d.agents = 1; d.state = state; d.steer_buf = steer_buf; d.steer_cnt = steer_cnt; d.actions = actions;
-    d.params = h->d_params.get(); d.param_slots = h->param_slots; d.dev_err = h->d_err.get(); d.time_step = h->cfg.timestep; d.integrator = h->cfg.integrator;
-    hipLaunchKernelGGL(dynamics_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d);
-    HIP_TRY(hipGetLastError());
-    return F110_OK;
+    return launch_entry_point(h, n, state && steer_buf && steer_cnt && actions, "f110_update_pose", [&] {
+        DynArgs d;
+        memset(&d, 0, sizeof(d));
+        d.n_cars = n; d.agents = 1; d.state = state; d.steer_buf = steer_buf; d.steer_cnt = steer_cnt; d.actions = actions;
+        d.params = h->d_params.get(); d.param_slots = h->param_slots; d.dev_err = h->d_err.get(); d.time_step = h->cfg.timestep; d.integrator = h->cfg.integrator;
+        hipLaunchKernelGGL(dynamics_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d);
+    });
 }
 
 extern "C" int f110_vehicle_dynamics(f110_handle *h, const double *x, const double *u, int32_t n, int32_t kinematic,
                                      double *f, void *stream)
 {
-    if (h && n == 0) return F110_OK;
-    if (!h || !x || !u || !f || n < 0) return fail(F110_E_INVALID, "f110_vehicle_dynamics: bad arguments");
-    if (int rc = check_device(h, "f110_vehicle_dynamics")) return rc;
-    hipLaunchKernelGGL(rhs_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, u, n, kinematic,
-                       h->d_params.get(), f);
-    HIP_TRY(hipGetLastError());
-    return F110_OK;
+    return launch_entry_point(h, n, x && u && f, "f110_vehicle_dynamics", [&] {
+        hipLaunchKernelGGL(rhs_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, u, n, kinematic,
+                           h->d_params.get(), f);
+    });
 }
 
 extern "C" int f110_get_vertices(f110_handle *h, const double *poses, int32_t n, double *verts, void *stream)
 {
-    if (h && n == 0) return F110_OK;
-    if (!h || !poses || !verts || n < 0) return fail(F110_E_INVALID, "f110_get_vertices: bad arguments");
-    if (int rc = check_device(h, "f110_get_vertices")) return rc;
-    hipLaunchKernelGGL(vertices_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, poses, n,
-                       h->h_params[0].v[P_LENGTH], h->h_params[0].v[P_WIDTH], verts);
-    HIP_TRY(hipGetLastError());
-    return F110_OK;
+    return launch_entry_point(h, n, poses && verts, "f110_get_vertices", [&] {
+        hipLaunchKernelGGL(vertices_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, poses, n,
+                           h->h_params[0].v[P_LENGTH], h->h_params[0].v[P_WIDTH], verts);
+    });
 }
 
 extern "C" int f110_gjk_pairs(f110_handle *h, const double *va, const double *vb, int32_t n, uint8_t *hit, void *stream)
 {
-    if (h && n == 0) return F110_OK;
-    if (!h || !va || !vb || !hit || n < 0) return fail(F110_E_INVALID, "f110_gjk_pairs: bad arguments");
-    if (int rc = check_device(h, "f110_gjk_pairs")) return rc;
-    hipLaunchKernelGGL(gjk_pairs_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, va, vb, n, hit);
-    HIP_TRY(hipGetLastError());
-    return F110_OK;
+    return launch_entry_point(h, n, va && vb && hit, "f110_gjk_pairs", [&] {
+        hipLaunchKernelGGL(gjk_pairs_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, va, vb, n, hit);
+    });
 }
 
 extern "C" int f110_collision_multiple(f110_handle *h, const double *verts, int32_t n, int32_t A, uint8_t *col,
                                        int32_t *cidx, void *stream)
 {
-    if (h && n == 0) return F110_OK;
-    if (!h || !verts || !col || !cidx || n < 0 || A < 1) return fail(F110_E_INVALID, "f110_collision_multiple: bad arguments");
-    if (int rc = check_device(h, "f110_collision_multiple")) return rc;
-    hipLaunchKernelGGL(collision_multiple_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, verts, n, A,
-                       col, cidx);
-    HIP_TRY(hipGetLastError());
-    return F110_OK;
+    return launch_entry_point(h, n, verts && col && cidx && A >= 1, "f110_collision_multiple", [&] {
+        hipLaunchKernelGGL(collision_multiple_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, verts, n, A,
+                           col, cidx);
+    });
 }
 
 extern "C" int f110_check_ttc(f110_handle *h, const double *scans, const double *vel, int32_t n, uint8_t *hit,
                               void *stream)
 {
-    if (h && n == 0) return F110_OK;
-    if (!h || !scans || !vel || !hit || n < 0) return fail(F110_E_INVALID, "f110_check_ttc: bad arguments");
-    if (int rc = check_device(h, "f110_check_ttc")) return rc;
-    hipLaunchKernelGGL(ttc_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, scans, vel, n, h->cfg.num_beams,
-                       h->d_beam_cosines.get(), h->d_side.get(), h->cfg.ttc_thresh, hit);
-    HIP_TRY(hipGetLastError());
-    return F110_OK;
+    return launch_entry_point(h, n, scans && vel && hit, "f110_check_ttc", [&] {
+        hipLaunchKernelGGL(ttc_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, scans, vel, n, h->cfg.num_beams,
+                           h->d_beam_cosines.get(), h->d_side.get(), h->cfg.ttc_thresh, hit);
+    });
 }
 
 extern "C" int f110_ray_cast(f110_handle *h, const double *ego, const double *verts, int32_t n, double *scans,
                              int32_t *span, void *stream)
 {
-    if (h && n == 0) return F110_OK;
-    if (!h || !ego || !verts || !scans || n < 0) return fail(F110_E_INVALID, "f110_ray_cast: bad arguments");
-    if (int rc = check_device(h, "f110_ray_cast")) return rc;
-    hipLaunchKernelGGL(ray_cast_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, ego, verts, n,
-                       h->cfg.num_beams, h->d_scan_angles.get(), h->d_beam_cs.get(), scans, span);
-    HIP_TRY(hipGetLastError());
-    return F110_OK;
+    return launch_entry_point(h, n, ego && verts && scans, "f110_ray_cast", [&] {
+        hipLaunchKernelGGL(ray_cast_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, ego, verts, n,
+                           h->cfg.num_beams, h->d_scan_angles.get(), h->d_beam_cs.get(), scans, span);
+    });
 }
 
 extern "C" int f110_check_done(f110_handle *h, const double *poses, const double *start_poses, const double *start_rot,
