@@ -268,14 +268,30 @@ __device__ inline bool gjk_collision(const double v1[4][2], const double v2[4][2
 }
 
 // ---------------------------------------------------------------- opponent ray cast
-// laser_models.py:250-280 with v3 = (cos(beam_theta+pi/2), sin(beam_theta+pi/2)) precomputed
+// The reference's beam normal (cos, sin)(fl(fl(yaw + angle) + pi/2)) (laser_models.py:336, :262), for the rare borderline
+// beam.  Not inlined: the argument reduction's registers would otherwise stay reserved around the beam loops.
+__device__ __attribute__((noinline)) double2 ref_beam_normal(double yaw, double angle)
+{
+    double s, c;
+    sincos((yaw + angle) + F110_PI / 2., &s, &c);
+    return make_double2(c, s);
+}
+
+// A pass condition of get_range (denom == 0, d2 = 0 or d2 = 1) that holds within this fraction of the vectors' size:
+// a normal a few ulps (1e-16) from the reference's may decide it differently (ray_cast_wave).
+#define F110_RAY_BORDER 1e-14
+
+// laser_models.py:250-280 with v3 = (cos(beam_theta+pi/2), sin(beam_theta+pi/2)) precomputed; border is set when the
+// answer rests on the last ulps of v3
 __device__ inline double get_range(double ox, double oy, double v3x, double v3y, double vax,
-                                   double vay, double vbx, double vby)
+                                   double vay, double vbx, double vby, bool &border)
 {
     double v1x = ox - vax, v1y = oy - vay;
     double v2x = vbx - vax, v2y = vby - vay;
     double denom = v2x * v3x + v2y * v3y;
     double distance = __builtin_inf();
+    const double v1n = fabs(v1x) + fabs(v1y), v2n = fabs(v2x) + fabs(v2y);
+    border = border || fabs(denom) <= F110_RAY_BORDER * v2n;
     if (fabs(denom) > 0.0) {
         // d1 = cross/denom >= 0, 0 <= d2 = dot/denom <= 1 (:271-274) decided without dividing:
         // the sign of an IEEE quotient is the sign product, and fl(q) <= 1 <=> q <= 1.
@@ -285,6 +301,7 @@ __device__ inline double get_range(double ox, double oy, double v3x, double v3y,
         const bool d1_ok = (cr == 0.0) || ((cr > 0.0) == dpos);
         const bool d2_ge0 = (dt == 0.0) || ((dt > 0.0) == dpos);
         const bool d2_le1 = dpos ? (dt <= denom) : (dt >= denom);
+        border = border || fabs(dt) <= F110_RAY_BORDER * v1n || fabs(dt - denom) <= F110_RAY_BORDER * (v1n + v2n);
         if (d1_ok && d2_ge0 && d2_le1) distance = cr / denom;
     } else {
         // are_collinear(o, va, vb) :233-247
@@ -304,10 +321,11 @@ __device__ inline double get_range(double ox, double oy, double v3x, double v3y,
 // increasing beam-angle table (base_classes.py:131-132): fl(scan_angles[i] - a) is monotone
 // in i, so |.| falls while negative and rises once positive -- the minimum sits at the last
 // entry <= a or its successor.  A linear estimate lands within a step or two of it; the two
-// loops make the result independent of the estimate.  NaN -> nb (caller bails out).
+// loops make the result independent of the estimate.  NaN -> 0: np.argmin of an all-NaN array (the corner angle of a
+// zero-length vector, the ego centre exactly on an opponent's corner, laser_models.py:293-313).
 __device__ inline int argmin_abs_diff_sorted(const double *__restrict__ scan_angles, int nb, double a)
 {
-    if (!(a == a)) return nb;
+    if (!(a == a)) return 0;
     const double sa0 = scan_angles[0];
     const double inv_incr = (double)(nb - 1) / (scan_angles[nb - 1] - sa0);
     double est = (a - sa0) * inv_incr;
@@ -357,7 +375,8 @@ __device__ inline void blocked_view_indices(double px, double py, double pyaw, c
 // the angle-addition identity from one per-car sincos and a {cos, sin}(scan_angle) table
 // instead of a per-beam fp64 sincos: same ~1e-16 accuracy class as the libm-vs-NumPy
 // difference the tolerance already covers, at a tenth of the instructions (an opponent
-// directly behind the car blocks the whole 2*pi scan, i.e. all 1080 beams).
+// directly behind the car blocks the whole 2*pi scan, i.e. all 1080 beams).  Where those ulps decide a beam (get_range's
+// border: a silhouette corner, an edge along the beam) it is decided again with the reference's own normal.
 __device__ inline void ray_cast_wave(double px, double py, double pyaw, const double verts[4][2],
                                      const double *__restrict__ scan_angles, const double2 *__restrict__ beam_cs,
                                      int nb, int lane, double *scan64, float *scan32, int *span_out)
@@ -365,18 +384,26 @@ __device__ inline void ray_cast_wave(double px, double py, double pyaw, const do
     int min_ind, max_ind;
     blocked_view_indices(px, py, pyaw, verts, scan_angles, nb, lane, min_ind, max_ind);
     if (span_out && lane == 0) { span_out[0] = min_ind; span_out[1] = max_ind; }
-    if (min_ind > nb - 1 || max_ind > nb - 1) return; // only reachable with NaN inputs
+    if (min_ind > nb - 1 || max_ind > nb - 1) return; // (not reachable: the indices are in [0, nb))
     const double A = pyaw + F110_PI / 2.;
     const double cA = cos(A), sA = sin(A);
     for (int i = min_ind + lane; i <= max_ind; i += 64) {
         const double2 cs = beam_cs[i];
         const double v3x = cA * cs.x - sA * cs.y, v3y = sA * cs.x + cA * cs.y;
-        double best = __builtin_inf();
+        double best, nx = v3x, ny = v3y;
+#pragma unroll 1
+        for (int pass = 0;; pass++) {
+            bool border = false;
+            best = __builtin_inf();
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            int jn = (j + 1) & 3;
-            double r = get_range(px, py, v3x, v3y, verts[j][0], verts[j][1], verts[jn][0], verts[jn][1]);
-            if (r < best) best = r;
+            for (int j = 0; j < 4; j++) {
+                int jn = (j + 1) & 3;
+                double r = get_range(px, py, nx, ny, verts[j][0], verts[j][1], verts[jn][0], verts[jn][1], border);
+                if (r < best) best = r;
+            }
+            if (!border || pass) break;
+            const double2 n = ref_beam_normal(pyaw, scan_angles[i]);
+            nx = n.x; ny = n.y;
         }
         if (scan64) { double cur = scan64[i]; if (best < cur) scan64[i] = best; }
         if (scan32) { float cur = scan32[i]; float b32 = (float)best; if (b32 < cur) scan32[i] = b32; }

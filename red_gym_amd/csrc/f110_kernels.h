@@ -896,6 +896,11 @@ __device__ inline bool frac_less(double n1, double d1, double n2, double d2)
     return __builtin_fma(n1, d2, -p1) < __builtin_fma(n2, d1, -p2);
 }
 
+// A beam whose pass condition (denom == 0, d2 = 0 or d2 = 1) holds within this fraction of the vectors' size: the
+// angle-addition normal (a few ulps from the reference's) may decide it differently, so it is decided again with the
+// reference's own normal.  Far above those ulps (1e-16), and rare: silhouette corners, contacts, edges along a beam.
+constexpr double OPP_BORDER = 1e-14;
+
 // One beam of the ray cast against one opponent: get_range over the four edges (see the section comment), then the
 // in-place minimum (laser_models.py:343-344) on the fp64 and / or fp32 scan.
 struct OppPairRegs {
@@ -909,6 +914,8 @@ struct OppPairRegs {
     // quad (overlapping cars) no edge faces it: n_front = 4, every edge takes the full test.
     double v1x[4], v1y[4], v2x[4], v2y[4], cr[4];
     double ax[4], ay[4], bx[4], by[4];
+    double yaw;                                   // the car's yaw: the reference's own beam normal for borderline beams
+    double border_t;                              // OPP_BORDER x the largest |v1|_1 + |v2|_1 of the four edges
     int n_front, pad;
 };
 constexpr int OPP_MAX_IV = 3;
@@ -926,35 +933,28 @@ struct OppPair {
     int n_iv, total, iv[2 * OPP_MAX_IV]; // total = beams in the intervals (0: nothing to do)
 };
 
-__device__ inline void opp_test_beam(const OppPairRegs *o, const double2 *__restrict__ beam_cs, int i, float *s32, double *s64)
+// get_range over the four edges for the beam normal (v3x, v3y); border: a pass condition or the collinear branch rests on
+// the last ulps of the normal (opp_test_beam)
+// (all: every edge takes the full test, as in the reference -- at a borderline beam the front-facing edge may miss by
+// rounding where the back-facing one through the same corner hits)
+__device__ inline double opp_beam_range(const OppPairRegs *o, double v3x, double v3y, bool behind, bool all, bool &border)
 {
-    // (callers pass 0 <= i < num_beams: checked there, and reported by the bounds-checked build)
-    // (*o lives in LDS: its fields are read where they are used, edge by edge, so that few of them are live at a time and
-    // the kernel keeps 8 waves per SIMD -- its time is memory latency, which only more waves hide)
-    const double2 cs = beam_cs[i];
-    const double cA = o->cA, sA = o->sA;
-    const double v3x = cA * cs.x - sA * cs.y, v3y = sA * cs.x + cA * cs.y;
-    // v3 is the ray's unit normal (laser_models.py:262): |q . v3| is the distance of the opponent's centre
-    // from the ray's line.  Beyond the padded half diagonal no edge can be crossed (every get_range would return inf).
-    const double qx = o->qx, qy = o->qy, reach = o->reach;
-    if (!(fabs(qx * v3x + qy * v3y) <= reach)) return;
-    // The ray's direction is (v3y, -v3x).  If the whole bounding circle lies BEHIND the car along it, every edge
-    // point has a negative ray parameter: get_range rejects it (d1 >= 0, :271) -- unless an edge is exactly
-    // parallel to the ray (denom == 0: the collinear branch answers whatever the direction, :275-280).
-    const bool behind = qx * v3y - qy * v3x < -reach;
     bool has = false;
     double bn = 0.0, bd = 1.0;          // the nearest hit so far as a fraction cross / denom (signed, as get_range divides them)
     double direct = __builtin_inf();    // distances the collinear branch produced
-    const int n_front = o->n_front;
+    const int n_front = all ? 4 : o->n_front;
+    const double bt = o->border_t;
 #pragma unroll 1
     for (int e = 0; e < 4; e++) {
         const double denom = o->v2x[e] * v3x + o->v2y[e] * v3y;          // :266
+        border = border || fabs(denom) <= bt;
         if (fabs(denom) > 0.0) {
             if (behind || e >= n_front) continue;
             // d1 = cross / denom >= 0, 0 <= d2 = dot / denom <= 1 (:271-274) decided without dividing:
             // the sign of an IEEE quotient is the sign product, and fl(q) <= 1 <=> q <= 1.
             const double cr = o->cr[e];
             const double dt = o->v1x[e] * v3x + o->v1y[e] * v3y;       // :268
+            border = border || fabs(dt) <= bt || fabs(dt - denom) <= bt;
             const bool dpos = denom > 0.0;
             const bool d1_ok = (cr == 0.0) || ((cr > 0.0) == dpos);
             const bool d2_ge0 = (dt == 0.0) || ((dt > 0.0) == dpos);
@@ -978,6 +978,38 @@ __device__ inline void opp_test_beam(const OppPairRegs *o, const double2 *__rest
     }
     double best = direct;
     if (has) { const double q = bn / bd; if (q < best) best = q; }   // :273 distance = d1
+    return best;
+}
+
+__device__ inline void opp_test_beam(const OppPairRegs *o, const double2 *__restrict__ beam_cs,
+                                     const double *__restrict__ scan_angles, int i, float *s32, double *s64)
+{
+    // (callers pass 0 <= i < num_beams: checked there, and reported by the bounds-checked build)
+    // (*o lives in LDS: its fields are read where they are used, edge by edge, so that few of them are live at a time and
+    // the kernel keeps 8 waves per SIMD -- its time is memory latency, which only more waves hide)
+    const double2 cs = beam_cs[i];
+    const double cA = o->cA, sA = o->sA;
+    const double v3x = cA * cs.x - sA * cs.y, v3y = sA * cs.x + cA * cs.y;
+    // v3 is the ray's unit normal (laser_models.py:262): |q . v3| is the distance of the opponent's centre
+    // from the ray's line.  Beyond the padded half diagonal no edge can be crossed (every get_range would return inf).
+    const double qx = o->qx, qy = o->qy, reach = o->reach;
+    if (!(fabs(qx * v3x + qy * v3y) <= reach)) return;
+    // The ray's direction is (v3y, -v3x).  If the whole bounding circle lies BEHIND the car along it, every edge
+    // point has a negative ray parameter: get_range rejects it (d1 >= 0, :271) -- unless an edge is exactly
+    // parallel to the ray (denom == 0: the collinear branch answers whatever the direction, :275-280).
+    const bool behind = qx * v3y - qy * v3x < -reach;
+    // The angle-addition normal is within a few ulps of the reference's; where that decides the beam (a silhouette corner,
+    // an edge parallel to the beam) the beam is decided again with the reference's own normal
+    // cos / sin(fl(fl(yaw + angle) + pi/2)) (:336, :262).  (One copy of the edge loop: a second one costs registers.)
+    double nx = v3x, ny = v3y, best;
+#pragma unroll 1
+    for (int pass = 0;; pass++) {
+        bool border = false;
+        best = opp_beam_range(o, nx, ny, behind, pass != 0, border);
+        if (!border || pass) break;
+        const double2 n = ref_beam_normal(o->yaw, scan_angles[i]);
+        nx = n.x; ny = n.y;
+    }
     if (best < __builtin_inf()) {
         if (s64) { double *s = s64 + i; if (best < *s) *s = best; }
         if (s32) { float *s = s32 + i; const float b32 = (float)best; if (b32 < *s) *s = b32; }
@@ -1046,9 +1078,13 @@ __device__ inline void opp_setup_body(const OppArgs &a, int t)
         neg_max = t2 > neg_max ? t2 : neg_max; pos_min = t3 < pos_min ? t3 : pos_min;
         nan_any = nan_any || (__shfl_xor((int)nan_any, off) != 0);
     }
-    const bool valid = !(lo > a.nb - 1 || hi > a.nb - 1 || nan_any); // (invalid only with NaN inputs; quad-uniform)
+    // a NaN corner angle (0 / 0 with the ego centre exactly on a corner, or NaN inputs) takes np.argmin's index 0 and
+    // leaves the hull undefined: every beam of the span is tested (with NaN inputs the pre-test rejects every beam, see
+    // DESIGN.md section 3)
+    const bool valid = !(lo > a.nb - 1 || hi > a.nb - 1); // (quad-uniform)
     // this lane's edge: what get_range computes from the pose and the two corners alone; front-facing edges first
     int n_front;
+    double border_t;
     {
         const double v1x = px - cx, v1y = py - cy;     // laser_models.py:258
         const double v2x = nx - cx, v2y = ny - cy;     // :259
@@ -1070,12 +1106,22 @@ __device__ inline void opp_setup_body(const OppArgs &a, int t)
         out.r.v1x[pos] = v1x; out.r.v1y[pos] = v1y; out.r.v2x[pos] = v2x; out.r.v2y[pos] = v2y;
         out.r.cr[pos] = cr;
         out.r.ax[pos] = cx; out.r.ay[pos] = cy; out.r.bx[pos] = nx; out.r.by[pos] = ny;
+        border_t = fabs(v1x) + fabs(v1y) + fabs(v2x) + fabs(v2y);
+    }
+#pragma unroll
+    for (int off = 1; off <= 2; off <<= 1) {
+        const double o_t = __shfl_xor(border_t, off);
+        border_t = o_t > border_t ? o_t : border_t;
     }
     if (c != 0) return;
     out.r.n_front = n_front; out.r.pad = 0;
-    // cos / sin(yaw + pi/2) = (-sin, cos)(yaw): within an ulp of the reference's cos(fl(fl(yaw + angle) + pi/2)) route, like
-    // the angle-addition form it feeds (f110_device.h, ray_cast_wave)
-    out.r.px = px; out.r.py = py; out.r.cA = -ey; out.r.sA = ex;
+    // cos / sin(fl(yaw + pi/2)) as ray_cast_wave forms them (f110_device.h), NOT (-sin, cos)(yaw): at yaw == 0 that is
+    // (-0, 1), a beam at exactly 0 rad gets a normal of exactly (0, 1) and an edge parallel to it denom == 0 -- the collinear
+    // branch, which the reference (cos(0 + 0 + pi/2) = 6.1e-17) never takes
+    double sA, cA;
+    sincos(pyaw + F110_PI / 2., &sA, &cA);
+    out.r.px = px; out.r.py = py; out.r.cA = cA; out.r.sA = sA; out.r.yaw = pyaw;
+    out.r.border_t = OPP_BORDER * border_t;
     const double mx = 0.5 * (verts[0][0] + verts[2][0]), my = 0.5 * (verts[0][1] + verts[2][1]);
     const double ddx = verts[0][0] - verts[2][0], ddy = verts[0][1] - verts[2][1];
     const double qx = mx - px, qy = my - py;
@@ -1088,7 +1134,7 @@ __device__ inline void opp_setup_body(const OppArgs &a, int t)
         const double sa0 = a.scan_angles[0];
         const double incr = (a.scan_angles[a.nb - 1] - sa0) / (double)(a.nb - 1);
         // the car inside the opponent's bounding circle (the hull may be anything), NaNs, a degenerate beam table: every beam
-        const bool all = !(qn > reach * 1.000001) || !(reach < __builtin_inf()) || !(incr > 0.0);
+        const bool all = nan_any || !(qn > reach * 1.000001) || !(reach < __builtin_inf()) || !(incr > 0.0);
         if (all || !(bmax - bmin > F110_PI)) {
             // the hull is the arc from the lowest to the highest corner angle: [lo, hi] itself (hull + pi lies outside it)
             iv[0] = lo; iv[1] = hi; n_iv = 1;
@@ -1155,7 +1201,7 @@ static __global__ __launch_bounds__(256, 8) void opp_apply_kernel(OppArgs a)
             for (int tt = sub; tt < total; tt += OPP_GROUP) {
                 const int i = opp_iv_beam(pr->iv, n_iv, tt);
                 F110_BCHK(i >= 0 && i < a.nb, BT_OPP_BEAM, a.dev_err);
-                if (i >= 0 && i < a.nb) opp_test_beam(&pr->r, a.beam_cs, i, s32, s64);
+                if (i >= 0 && i < a.nb) opp_test_beam(&pr->r, a.beam_cs, a.scan_angles, i, s32, s64);
             }
         }
         unsigned long long todo = __builtin_amdgcn_ballot_w64(longlist && sub == 0);
@@ -1169,7 +1215,7 @@ static __global__ __launch_bounds__(256, 8) void opp_apply_kernel(OppArgs a)
             double *w64 = a.scans64 ? a.scans64 + (size_t)wcar * a.nb : nullptr;
             for (int tt = lane; tt < wtotal; tt += WAVE) {
                 const int i = opp_iv_beam(wp->iv, wn, tt);
-                if (i >= 0 && i < a.nb) opp_test_beam(&wp->r, a.beam_cs, i, w32, w64);
+                if (i >= 0 && i < a.nb) opp_test_beam(&wp->r, a.beam_cs, a.scan_angles, i, w32, w64);
             }
         }
         __builtin_amdgcn_wave_barrier(); // the LDS copies are overwritten by the next opponent's
