@@ -129,12 +129,28 @@ int f110_update_params(f110_handle *h, const double *params18_host, int32_t agen
  *     f110_set_params_slot changes one slot -- agent_idx < 0: as at construction (Simulator copy + every agent), else only
  *     RaceCar.params of that agent (Simulator.update_params on that env, :507-527); a slot beyond the current count extends
  *     the table with copies of slot 0.  f110_update_params (above) keeps applying to every slot.  f110_assign_params: host
- *     int32 [num_envs], NULL = all envs on slot 0.  The beam tables (scan angles, cosines, side distances) stay per handle:
- *     in the reference they are class-level statics fixed by the FIRST RaceCar a process constructs (base_classes.py:116-156).
+ *     int32 [num_envs], NULL = all envs on slot 0.  The beam tables (scan angles, cosines, side distances) are per handle
+ *     by default: in the reference they are class-level statics fixed by the FIRST RaceCar a process constructs
+ *     (base_classes.py:116-156), so envs created in one process share env 0's.  The side distances -- the only one of the
+ *     three that depends on the vehicle -- can be given per params slot instead (f110_set_side_distance_slots below):
+ *     num_envs independently constructed envs, each with the table of its own `params`.
  *   noise slot = one seed: see f110_set_noise_generator / f110_set_noise_slot / f110_assign_noise below. */
 int f110_set_params_slots(f110_handle *h, const double *params_host, int32_t n_slots);
 int f110_set_params_slot(f110_handle *h, int32_t slot, const double *params18_host, int32_t agent_idx);
 int f110_assign_params(f110_handle *h, const int32_t *slot_of_env_host);
+/* Side distances of the iTTC test (base_classes.py:116-156, laser_models.py:189-217) per VEHICLE: side_host = [n_slots,
+ * num_beams] fp64, one table per params slot; the scan of env e tests its beams against row slot_of_env[e] (the table
+ * f110_assign_params installed; all envs on row 0 when none is).  Any values are legal, as for f110_set_tables (negative,
+ * infinite, NaN).  NULL / n_slots == 0 removes the tables: the handle is back on the one table of f110_set_tables, which
+ * is kept beside them and never changed by this call.  Device memory: n_slots x num_beams x 8 B (4 096 vehicles of 1 080
+ * beams: 35 MB).  A successful install or removal moves the launch epoch.
+ * While tables are installed every params slot has one and no other exists: n_slots must equal the handle's current params
+ * slot count (F110_E_INVALID otherwise); f110_set_params_slots with another slot count is refused (F110_E_INVALID: remove
+ * the side tables first); f110_set_params_slot on a slot beyond the count extends the side tables with copies of row 0, as
+ * it does for the params.  f110_update_params and f110_set_params_slot on an existing slot leave the side tables alone: in
+ * the reference they are fixed at construction (base_classes.py:158-169 only replaces self.params).  A refused call
+ * changes nothing, the launch epoch included. */
+int f110_set_side_distance_slots(f110_handle *h, const double *side_host, int32_t n_slots);
 
 /* Optional: replace the library's libm-computed tables by the caller's
  * (numpy-computed, as in the reference).  sines/cosines: [theta_dis]
@@ -288,7 +304,7 @@ int f110_set_scan_stages(f110_handle *h, const char *spec);
 
 /* hipGraph support.  f110_step only enqueues kernels (no allocation, no synchronisation), so it can be captured
  * into a HIP graph and replayed.  A capture freezes the kernel selection and the by-value launch arguments; the
- * calls that change them -- f110_bind, f110_set_tables, every map install, f110_assign_maps / _params / _noise, a
+ * calls that change them -- f110_bind, f110_set_tables, f110_set_side_distance_slots, every map install, f110_assign_maps / _params / _noise, a
  * re-allocation of the noise table, a successful f110_pure_pursuit_prepare (it frees and re-allocates the grid that a
  * captured f110_pure_pursuit reads) -- bump the handle's launch epoch.  A graph captured at epoch e is valid while
  * f110_launch_epoch still reports e; after that it must be re-captured (F110VecEnv.step_graph does so itself). */
@@ -390,6 +406,11 @@ int f110_collision_multiple(f110_handle *h, const double *verts, int32_t n, int3
 /* check_ttc_jit (laser_models.py:189-217): scans [n,num_beams], vel [n] -> hit[n] */
 int f110_check_ttc(f110_handle *h, const double *scans, const double *vel, int32_t n, uint8_t *hit,
                    void *stream);
+/* The same for n rows with the side table of params slot slot_of_row[r] each (dev int32 [n]; f110_set_side_distance_slots;
+ * F110_E_INVALID when no tables are installed).  A slot outside the installed tables reads row 0 (reported through the
+ * device error word in the bounds-checked build). */
+int f110_check_ttc_slots(f110_handle *h, const double *scans, const double *vel, const int32_t *slot_of_row, int32_t n,
+                         uint8_t *hit, void *stream);
 /* ray_cast (laser_models.py:319-346): scans [n,num_beams] modified in place by one
  * opponent quad each; span [n,2] = get_blocked_view_indices (may be NULL). */
 int f110_ray_cast(f110_handle *h, const double *ego_poses, const double *opp_verts, int32_t n,

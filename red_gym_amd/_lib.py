@@ -66,6 +66,7 @@ SYMBOLS = {
     'f110_set_params_slots': [_VP, _VP, _I32],
     'f110_set_params_slot': [_VP, _I32, _VP, _I32],
     'f110_assign_params': [_VP, _VP],
+    'f110_set_side_distance_slots': [_VP, _VP, _I32],
     'f110_set_noise_table': [_VP, _VP, _I64],
     'f110_set_noise_slot': [_VP, _I32, _VP, _I64],
     'f110_set_noise_generator': [_VP, _I32, _VP, _D],
@@ -103,6 +104,7 @@ SYMBOLS = {
     'f110_gjk_pairs': [_VP, _VP, _VP, _I32, _VP, _VP],
     'f110_collision_multiple': [_VP, _VP, _I32, _I32, _VP, _VP, _VP],
     'f110_check_ttc': [_VP, _VP, _VP, _I32, _VP, _VP],
+    'f110_check_ttc_slots': [_VP, _VP, _VP, _VP, _I32, _VP, _VP],
     'f110_ray_cast': [_VP, _VP, _VP, _I32, _VP, _VP, _VP],
     'f110_check_done': [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_bitmap_create': [C.POINTER(BitmapConfig), _VP, _VP, _VP, C.POINTER(_VP)],

@@ -187,12 +187,12 @@ static int alloc_opp_pairs(f110_handle *h)
 
 // The scan reads a beam's side distance only where the iTTC test could fire: scan value below (largest side distance +
 // the candidate margin).  Non-finite entries can never make a candidate (the reference's comparison is false for them).
-static void set_side_max(f110_handle *h)
+static double largest_finite(const double *v, size_t n, double m = 0.0)
 {
-    double m = 0.0;
-    for (double v : h->h_side) if (std::isfinite(v) && v > m) m = v;
-    h->side_max = m;
+    for (size_t i = 0; i < n; i++) if (std::isfinite(v[i]) && v[i] > m) m = v[i];
+    return m;
 }
+static void set_side_max(f110_handle *h) { h->side_max = largest_finite(h->h_side.data(), h->h_side.size()); }
 
 // (Re)builds the interleaved {cos, sin} device table from the host copies.
 static int upload_cs(f110_handle *h)
@@ -317,6 +317,9 @@ extern "C" int f110_set_params_slots(f110_handle *h, const double *params, int32
     if (n_slots < 1 || n_slots > h->cfg.num_envs) return fail(F110_E_INDEX, "f110_set_params_slots: %d slots (1..num_envs = %d)", n_slots, h->cfg.num_envs);
     for (int sl = 0; sl < n_slots; sl++)
         if (int rc = check_params18(params + (size_t)sl * P_COUNT, "f110_set_params_slots")) return rc;
+    if (h->side_n_slots && n_slots != h->param_slots) // (every params slot has its side table, and only those)
+        return fail(F110_E_INVALID, "f110_set_params_slots: %d slots, but side-distance tables are installed for %d: remove the side "
+                    "tables first (f110_set_side_distance_slots(h, NULL, 0))", n_slots, h->side_n_slots);
     ON_DEVICE(h->cfg.device);
     const int A1 = h->cfg.num_agents + 1;
     h->h_params.resize((size_t)n_slots * A1);
@@ -336,6 +339,18 @@ extern "C" int f110_set_params_slot(f110_handle *h, int32_t slot, const double *
     if (int rc = check_params18(p, "f110_set_params_slot")) return rc;
     ON_DEVICE(h->cfg.device);
     const int A1 = h->cfg.num_agents + 1;
+    if (slot >= h->param_slots && h->side_n_slots) { // ... and so do their side tables (built first: a failure changes nothing)
+        const size_t nb = (size_t)h->cfg.num_beams, old_n = (size_t)h->side_n_slots;
+        DevBuf<double> grown;
+        HIP_TRY(grown.alloc((size_t)(slot + 1) * nb));
+        HIP_TRY(hipDeviceSynchronize()); // enqueued steps may still read the table being replaced
+        HIP_TRY(hipMemcpy(grown.get(), h->d_side_slots.get(), old_n * nb * sizeof(double), hipMemcpyDeviceToDevice));
+        for (size_t sl = old_n; sl <= (size_t)slot; sl++)
+            HIP_TRY(hipMemcpy(grown.get() + sl * nb, h->h_side_slot0.data(), nb * sizeof(double), hipMemcpyHostToDevice));
+        h->d_side_slots = std::move(grown);
+        h->side_n_slots = slot + 1;
+        h->epoch++; // the scan takes the pointer by value
+    }
     if (slot >= h->param_slots) { // new slots start as copies of slot 0
         h->h_params.resize((size_t)(slot + 1) * A1);
         for (int sl = h->param_slots; sl <= slot; sl++)
@@ -392,6 +407,37 @@ extern "C" int f110_set_tables(f110_handle *h, const double *sines, const double
         set_side_max(h);
     }
     return rc;
+}
+
+// Side distances per params slot: see include/f110_hip.h.  Installed tables always cover exactly the handle's params slots
+// (checked here; f110_set_params_slots / f110_set_params_slot keep it so), hence every env's slot has a row.
+extern "C" int f110_set_side_distance_slots(f110_handle *h, const double *side, int32_t n_slots)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_set_side_distance_slots: null handle");
+    if (n_slots < 0) return fail(F110_E_INVALID, "f110_set_side_distance_slots: %d slots", n_slots);
+    ON_DEVICE(h->cfg.device);
+    if (!side || n_slots == 0) { // back on the one table of f110_set_tables
+        if (!h->side_n_slots) return F110_OK;
+        HIP_TRY(hipDeviceSynchronize()); // enqueued steps may still read the tables
+        h->d_side_slots = DevBuf<double>();
+        h->h_side_slot0.clear();
+        h->side_n_slots = 0;
+        h->epoch++;
+        return F110_OK;
+    }
+    if (n_slots != h->param_slots)
+        return fail(F110_E_INVALID, "f110_set_side_distance_slots: %d tables for %d params slots (one table per slot: "
+                    "f110_set_params_slots first)", n_slots, h->param_slots);
+    const size_t nb = (size_t)h->cfg.num_beams;
+    DevBuf<double> fresh;
+    HIP_TRY(fresh.upload(side, (size_t)n_slots * nb));
+    HIP_TRY(hipDeviceSynchronize());
+    h->d_side_slots = std::move(fresh);
+    h->h_side_slot0.assign(side, side + nb);
+    h->side_n_slots = n_slots;
+    h->side_slots_max = largest_finite(side, (size_t)n_slots * nb);
+    h->epoch++; // the scan takes the pointer by value
+    return F110_OK;
 }
 
 #if defined(F110_BOUNDS)

@@ -189,6 +189,12 @@ struct f110_handle {
     const int32_t *scan_order = nullptr; // launch order of the step's scan (f110_set_scan_order; caller-owned device array) or NULL
     DevBuf<uint32_t> d_err;           // device error word (f110_device_errors)
     std::vector<double> h_side;       // side distances (host copy of d_side)
+    // Side distances per params slot (f110_set_side_distance_slots), while installed: side_n_slots == param_slots at all
+    // times, so the slot of every env (d_env_params) has a row.  0: the scan reads d_side for every car.
+    DevBuf<double> d_side_slots;      // [side_n_slots][num_beams]
+    int side_n_slots = 0;
+    std::vector<double> h_side_slot0; // host copy of row 0 (new slots start as copies of it, like their params)
+    double side_slots_max = 0.0;      // largest finite value over all installed rows (ScanArgs::side_max while installed)
     // Maps.  Slot 0 is "the" map of the reference's API; further slots let blocks of envs of one shard run on
     // different maps (one handle standing in for many F110Env instances with their own map each).
     struct MapSlot {

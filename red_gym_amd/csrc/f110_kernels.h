@@ -37,7 +37,7 @@ constexpr uint32_t DEVERR_NOISE_WINDOW = 1u, DEVERR_BOUNDS = 2u;
 // device error word (f110_device_errors) and the access is redirected to a valid element, so the run goes on and the
 // report names the table.  The whole -m gpu suite is run against this build once per round (profiles/r04_bounds_build.txt).
 enum { BT_LUT_CODE, BT_CELLS_FAR, BT_LUT_RANK, BT_DT, BT_NOISE_BEAM, BT_CS_TABLE, BT_CHUNK_ORDER, BT_MAP_SLOT, BT_NOISE_SLOT,
-       BT_PARAMS_SLOT, BT_SCAN_STORE, BT_OPP_BEAM, BT_STAGE_LIST, BT_SELFTEST };
+       BT_PARAMS_SLOT, BT_SCAN_STORE, BT_OPP_BEAM, BT_STAGE_LIST, BT_SELFTEST, BT_SIDE_SLOT };
 #if defined(F110_BOUNDS)
 #define F110_BCHK(ok, table, errp) \
     do { if (!(ok)) { uint32_t *e_ = (errp); if (e_) atomicOr(e_, DEVERR_BOUNDS | (1u << (8 + (table)))); } } while (0)
@@ -517,6 +517,12 @@ struct ScanArgs {
     // different maps (f110_assign_maps with a map per env); 0: SCAN_WAVES cars per workgroup share one LUT copy.
     int wg_single;
     int n_maps;             // slots of `maps` (bounds build)
+    // Side distances per VEHICLE (f110_set_side_distance_slots), or NULL = the handle's one table `side`: [side_n_slots][nb], the
+    // car's row is that of its env's params slot (env_params[env], NULL: slot 0).  Both belong to the rarely needed arguments:
+    // read through the kernarg pointer inside the iTTC candidate branch only; side_max then spans every installed row.
+    const double *side_slots;
+    const int32_t *env_params;
+    int side_n_slots;       // rows of side_slots (bounds build)
     // outputs
     float *out_f32;              // [N,nb] or NULL
     double *out_f64;             // [N,nb] or NULL
@@ -671,7 +677,20 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
         if (__builtin_expect(v < side_pre, 0)) {
             const ScanArgs *ra = rare;
             asm volatile("" : "+s"(ra)); // re-read the rarely needed arguments here instead of holding them in SGPRs
-            const double sd = v - ra->side[i];
+            const double *side = ra->side;
+            if (const double *const rows = ra->side_slots) {
+                // the table of the car's own vehicle: row `params slot of its env` (wave-uniform: scalar loads and one scalar
+                // division for A > 1, paid by candidates only -- the env index is not kept in a register across the march)
+                const int ag = ra->agents;
+                const int32_t *const ep = ra->env_params;
+                int sl = ep ? ep[ag == 1 ? car : car / ag] : 0;
+#if defined(F110_BOUNDS)
+                F110_BCHK((unsigned)sl < (unsigned)ra->side_n_slots, BT_SIDE_SLOT, ra->dev_err);
+                if ((unsigned)sl >= (unsigned)ra->side_n_slots) sl = 0;
+#endif
+                side = rows + (size_t)(unsigned)sl * (size_t)(unsigned)nb;
+            }
+            const double sd = v - side[i];
             if (fabs(sd) < cand) {
                 const double proj_vel = vel * ra->beam_cosines[i];
                 const double ttc = sd / proj_vel;
@@ -1628,11 +1647,20 @@ static __global__ void collision_multiple_kernel(const double *verts, int n, int
 
 // check_ttc_jit (laser_models.py:189-217): wave per scan
 #if defined(F110_UNIT_STEP)
+// slot_of_row (f110_check_ttc_slots): row r is tested against row slot_of_row[r] of side_distances [n_slots][nb]; NULL: the one table
 static __global__ void ttc_kernel(const double *scans, const double *vel, int n, int nb, const double *beam_cosines,
-                           const double *side_distances, double thresh, uint8_t *hit)
+                           const double *side_distances, double thresh, uint8_t *hit, const int32_t *slot_of_row, int n_slots,
+                           uint32_t *dev_err)
 {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n) return;
+    if (slot_of_row) {
+        int sl = slot_of_row[row]; // (the caller's device array: a slot outside the table reads slot 0; reported in the bounds build)
+        F110_BCHK((unsigned)sl < (unsigned)n_slots, BT_SIDE_SLOT, dev_err);
+        if ((unsigned)sl >= (unsigned)n_slots) sl = 0;
+        (void)dev_err;
+        side_distances += (size_t)sl * nb;
+    }
     const double v = vel[row];
     bool h = false;
     if (v != 0.0) {

@@ -136,6 +136,10 @@ static int run_step(f110_handle *h, const double *actions, int reset_only, const
         s.env_map = h->multi ? h->d_env_map.get() : nullptr;
         s.state = b.state; s.noise_step = b.noise_step;
         s.side = h->d_side.get(); s.side_max = h->side_max;
+        if (h->side_n_slots) { // every car against its own vehicle's table; the pre-filter's bound then spans all of them
+            s.side_slots = h->d_side_slots.get(); s.side_n_slots = h->side_n_slots; s.side_max = h->side_slots_max;
+            s.env_params = h->multi_params ? h->d_env_params.get() : nullptr;
+        }
         const NoiseRows nr = h->noise.where(c.num_envs);
         s.noise_base = nr.base; s.noise_cap = nr.cap; s.noise_mask = nr.mask; s.noise_slots = nr.slots; s.env_noise = nr.env_slot;
         s.dev_err = h->d_err.get();
@@ -477,7 +481,20 @@ extern "C" int f110_check_ttc(f110_handle *h, const double *scans, const double 
 {
     return launch_entry_point(h, n, scans && vel && hit, "f110_check_ttc", [&] {
         hipLaunchKernelGGL(ttc_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, scans, vel, n, h->cfg.num_beams,
-                           h->d_beam_cosines.get(), h->d_side.get(), h->cfg.ttc_thresh, hit);
+                           h->d_beam_cosines.get(), h->d_side.get(), h->cfg.ttc_thresh, hit, (const int32_t *)nullptr, 0,
+                           (uint32_t *)nullptr);
+    });
+}
+
+extern "C" int f110_check_ttc_slots(f110_handle *h, const double *scans, const double *vel, const int32_t *slot_of_row,
+                                    int32_t n, uint8_t *hit, void *stream)
+{
+    if (h && !h->side_n_slots)
+        return fail(F110_E_INVALID, "f110_check_ttc_slots: no side-distance tables installed (f110_set_side_distance_slots)");
+    return launch_entry_point(h, n, scans && vel && slot_of_row && hit, "f110_check_ttc_slots", [&] {
+        hipLaunchKernelGGL(ttc_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, scans, vel, n, h->cfg.num_beams,
+                           h->d_beam_cosines.get(), h->d_side_slots.get(), h->cfg.ttc_thresh, hit, slot_of_row,
+                           h->side_n_slots, h->d_err.get());
     });
 }
 

@@ -106,14 +106,21 @@ class Engine(object):
     def __init__(self, num_envs=1, num_agents=1, params=None, seed=12345, fov=2 * np.pi, timestep=0.01,
                  integrator=1, ego_idx=0, num_beams=1080, eps=0.0001, theta_dis=2000, max_range=30.0,
                  ttc_thresh=0.005, device=0, autoreset=False, noise_std=0.01, noise_steps=0,
-                 keep_f64_scans=False, count_lookups=False, noise_source='device'):
+                 keep_f64_scans=False, count_lookups=False, noise_source='device', side_distances='shared'):
         """`params`: one dict (every env, f110_env.py:125-128) or a sequence of num_envs dicts (env e constructed with
         params[e]); `seed`: one int (:102-105) or a sequence of num_envs ints.
         `noise_source`: 'device' (rows produced on the GPU, kept once per distinct seed in a table that runs ahead of the
         cars: at most F110_MAX_NOISE_SLOTS distinct seeds), 'per_env' (every env its own generator, its row produced by the
         step itself: any number of seeds -- chosen by itself when 'device' is asked for more distinct seeds than the table
         holds) or 'numpy' (NumPy draws on the host, rows uploaded);
-        `noise_steps`: rows to have ready at construction (0: the first step asks for them)."""
+        `noise_steps`: rows to have ready at construction (0: the first step asks for them).
+        `side_distances`: which outline the iTTC wall test of an env uses (base_classes.py:116-156, laser_models.py:189-217).
+        'shared' (default): ONE table per handle, from env 0's params -- what reference envs created in one process share
+        through RaceCar's class-level statics; 'per_env': every env the table of its own `params` (one per distinct params
+        slot, built by beam_tables and installed with f110_set_side_distance_slots) -- what num_envs independently
+        constructed envs, each in its own process, would have.  With a single `params` dict the two are the same.  Scan angles
+        and beam cosines depend on fov / num_beams alone and stay per handle; update_params leaves the tables alone in both
+        modes, as the reference does after construction (:158-169)."""
         if not torch.cuda.is_available():
             raise RuntimeError('red_gym_amd needs a HIP device (torch.cuda.is_available() is False); '
                                'there is no CPU path.')
@@ -121,6 +128,10 @@ class Engine(object):
             noise_source = 'per_env'   # (the cars of an env share its seed and therefore its rows)
         if noise_source not in ('device', 'numpy', 'per_env'):
             raise ValueError("noise_source must be 'device', 'per_env' or 'numpy'")
+        if side_distances not in ('shared', 'per_env'):
+            raise ValueError("side_distances must be 'shared' or 'per_env'")
+        self.side_distances_mode = side_distances
+        self.env_params_assign, self._side_slots = None, None   # params slot of every env; [slots, num_beams] while installed
         self.lib = _lib.load()
         env_params = None
         if params is not None and not isinstance(params, dict):
@@ -213,9 +224,12 @@ class Engine(object):
     # ------------------------------------------------------------------ per-env constructor arguments
     def set_env_params(self, env_params):
         """env e drives the vehicle of env_params[e] (a sequence of num_envs dicts): what num_envs reference envs
-        constructed with their own `params` would do.  Equal dicts share a params slot."""
+        constructed with their own `params` would do.  Equal dicts share a params slot.  side_distances='per_env': every
+        slot also gets the side distances of its own vehicle."""
         if len(env_params) != self.B:
             raise ValueError('one params dict per env (%d), got %d' % (self.B, len(env_params)))
+        if self._side_slots is not None:   # (the library keeps one side table per params slot: off while the slots change)
+            self.set_side_distance_slots(None)
         vecs = np.stack([params_vec(p) for p in env_params])
         uniq, inv = np.unique(vecs, axis=0, return_inverse=True)
         # slot 0 must be env 0's (the handle's constructor params: beam tables, defaults)
@@ -228,6 +242,31 @@ class Engine(object):
         _lib.check(self.lib.f110_set_params_slots(self._h, _np_ptr(table), table.shape[0]))
         _lib.check(self.lib.f110_assign_params(self._h, _np_ptr(assign) if table.shape[0] > 1 else None))
         self.env_params_assign = assign
+        if self.side_distances_mode == 'per_env' and table.shape[0] > 1:
+            slot_params = [dict(zip(_lib.PARAM_KEYS, row)) for row in table]
+            self.set_side_distance_slots(np.stack([beam_tables(self.num_beams, self.fov, p)[2] for p in slot_params]))
+
+    def set_side_distance_slots(self, side=None):
+        """f110_set_side_distance_slots: `side` [params slots, num_beams], one side-distance table per params slot (any
+        values), or None: back on the handle's one table.  ValueError when the row count is not the handle's slot count."""
+        if side is None:
+            _lib.check(self.lib.f110_set_side_distance_slots(self._h, None, 0))
+            self._side_slots = None
+            return
+        side = np.ascontiguousarray(side, dtype=np.float64)
+        if side.ndim != 2 or side.shape[1] != self.num_beams:
+            raise ValueError('side tables must have shape (params slots, %d), got %s' % (self.num_beams, side.shape))
+        _lib.check(self.lib.f110_set_side_distance_slots(self._h, _np_ptr(side), side.shape[0]))
+        self._side_slots = side
+
+    def side_distances_of(self, env):
+        """The side-distance table (NumPy [num_beams]) the iTTC test of env `env`'s scan uses: the handle's one table
+        ('shared', or a single vehicle), or the table of the env's own params slot ('per_env')."""
+        if not 0 <= int(env) < self.B:
+            raise IndexError('env %d outside 0..%d' % (env, self.B - 1))
+        if self._side_slots is None:
+            return self.side_distances
+        return self._side_slots[self.env_params_assign[int(env)]]
 
     def _setup_noise(self, seeds, std):
         """One noise slot per distinct seed (base_classes.py:117,202: all cars of an env draw from default_rng(seed))."""
@@ -432,7 +471,8 @@ class Engine(object):
         return out
 
     def update_params(self, params, agent_idx=-1):
-        """base_classes.py:507-527: all agents (agent_idx < 0) or one agent of every env."""
+        """base_classes.py:507-527: all agents (agent_idx < 0) or one agent of every env.  The side distances stay as they
+        are in either mode: the reference fixes them at construction (:116-156) and update_params only replaces the params."""
         pv = params_vec(params)
         _lib.check(self.lib.f110_update_params(self._h, _np_ptr(pv), int(agent_idx)))
         if agent_idx < 0:
@@ -581,6 +621,18 @@ class Engine(object):
         scans, vel = self._dev64(scans, (-1, self.num_beams)), self._dev64(vel, (-1,))
         hit = torch.zeros((scans.shape[0],), dtype=torch.uint8, device=self.device)
         _lib.check(self.lib.f110_check_ttc(self._h, _ptr(scans), _ptr(vel), scans.shape[0], _ptr(hit), self._stream()))
+        return hit
+
+    @on_own_device
+    def check_ttc_slots(self, scans, vel, slot_of_row):
+        """check_ttc for every row with the installed side table of params slot slot_of_row[r] (f110_check_ttc_slots)."""
+        scans, vel = self._dev64(scans, (-1, self.num_beams)), self._dev64(vel, (-1,))
+        slots = torch.as_tensor(np.ascontiguousarray(slot_of_row, dtype=np.int32)).to(device=self.device).contiguous()
+        if slots.shape != (scans.shape[0],):
+            raise ValueError('one slot per row (%d), got shape %s' % (scans.shape[0], tuple(slots.shape)))
+        hit = torch.zeros((scans.shape[0],), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.f110_check_ttc_slots(self._h, _ptr(scans), _ptr(vel), _ptr(slots), scans.shape[0], _ptr(hit),
+                                                 self._stream()))
         return hit
 
     @on_own_device

@@ -30,14 +30,16 @@ class F110VecEnv(object):
     def __init__(self, num_envs, map=None, map_ext='.png', params=None, num_agents=2, timestep=0.01,
                  ego_idx=0, integrator=Integrator.RK4, fov=2 * np.pi, seed=12345, device=0, autoreset=True,
                  num_beams=1080, noise_std=0.01, noise_steps=0, keep_f64_scans=False, count_lookups=False,
-                 noise_source='device', **_ignored):
+                 noise_source='device', side_distances='shared', **_ignored):
         """The reference's constructor keywords (f110_env.py:100-157) plus the batch: `params` and `seed` may each be ONE
         value for every env, or a sequence of num_envs values -- env e is then what `F110Env(params=params[e],
         seed=seed[e])` would be (equal values share a slot on the device; more than 64 distinct seeds switch the device noise to
-        one generator per env, `noise_source='per_env'`).  The scan's beam tables and side distances are built ONCE, from env 0's
-        params -- what reference envs created in one process share through RaceCar's class-level statics (base_classes.py:116-156),
-        not what independently started processes would have: an env whose `width` / `lf` / `lr` differ still uses env 0's side
-        distances for its iTTC test."""
+        one generator per env, `noise_source='per_env'`).  The scan angles and beam cosines depend on fov / num_beams alone and are
+        built once.  `side_distances` chooses the car outline of each env's iTTC wall test (a function of `width`, `lf`, `lr`):
+        'shared' (default) builds ONE table from env 0's params -- what reference envs created in one process share through
+        RaceCar's class-level statics (base_classes.py:116-156); 'per_env' gives every env the table of its own params -- what
+        num_envs independently constructed envs (one process each) would have, e.g. when vehicle geometry is randomised per
+        env.  With a single `params` dict the two are the same."""
         self.num_envs, self.num_agents = int(num_envs), int(num_agents)
         self.map_name, self.map_ext = map, map_ext
         self.map_path = resolve_map_path(map)
@@ -47,7 +49,8 @@ class F110VecEnv(object):
                           seed=seed, fov=fov,
                           timestep=timestep, integrator=integrator, ego_idx=ego_idx, num_beams=num_beams,
                           device=device, autoreset=autoreset, noise_std=noise_std, noise_steps=noise_steps,
-                          keep_f64_scans=keep_f64_scans, count_lookups=count_lookups, noise_source=noise_source)
+                          keep_f64_scans=keep_f64_scans, count_lookups=count_lookups, noise_source=noise_source,
+                          side_distances=side_distances)
         self.eng.set_map(self.map_path, self.map_ext)
         self.device = self.eng.device
         t = self.eng.t
