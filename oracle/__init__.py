@@ -278,6 +278,21 @@ class Env(object):
         lib().orc_sim_step(self._ptr, _p(action), _p(self.scans))
         return self.observe(False)
 
+    def update_params(self, params, index=-1):
+        """F110Env.update_params (f110_env.py:362-373): RaceCar.params of every agent (index < 0) or of one;
+        Simulator.params (the GJK quads) and the beam tables stay as constructed."""
+        pv = params_vec(params)
+        if lib().orc_env_update_params(self._ptr, _p(pv), C.c_int(index)) != 0:
+            raise IndexError('Index given is out of bounds for list of agents.')
+
+    def update_map(self, map_path, map_ext):
+        """F110Env.update_map (f110_env.py:349-360)."""
+        self._map = load_map(map_path, map_ext)
+        m = self._map
+        self._cmap = _Map(m['height'], m['width'], m['resolution'], m['orig_x'], m['orig_y'],
+                          m['orig_c'], m['orig_s'], _p(m['dt']))
+        lib().orc_env_set_map(self._ptr, C.byref(self._cmap))
+
     def set_state(self, agent, state, steer_buffer=(0., 0.), steer_count=2, noise_step=0):
         state, sb = _f64(state), _f64(steer_buffer)
         lib().orc_env_set_state(self._ptr, C.c_int(agent), _p(state), _p(sb), C.c_int(steer_count),
@@ -289,7 +304,9 @@ class Env(object):
         col, idx, lt, lc, tg = (np.empty(A) for _ in range(5))
         ct, lk = C.c_double(0), C.c_int64(0)
         lib().orc_env_get(self._ptr, _p(st), _p(col), _p(idx), _p(lt), _p(lc), _p(tg), C.byref(ct), C.byref(lk))
-        return {'scans': self.scans.copy(), 'state': st, 'collisions': col, 'collision_idx': idx,
+        sp = np.empty((A, 3))
+        lib().orc_env_get_scan_poses(self._ptr, _p(sp))
+        return {'scans': self.scans.copy(), 'state': st, 'scan_poses': sp, 'collisions': col, 'collision_idx': idx,
                 'lap_times': lt, 'lap_counts': lc, 'toggles': tg, 'current_time': ct.value,
                 'lookups': lk.value, 'done': done}
 

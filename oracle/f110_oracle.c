@@ -623,7 +623,8 @@ int orc_collision_quads(const double *a, const double *b)
 typedef struct {
     int num_agents, ego_idx, integrator;
     double time_step;
-    double params[P_COUNT];
+    double params[P_COUNT];     /* Simulator.params (:477): the GJK quads (:542); update_params never touches it */
+    double car_params[ORC_MAX_AGENTS][P_COUNT]; /* RaceCar.params (:84,:169): dynamics, and the size a car gives its opponents (:221) */
     double ttc_thresh; /* base_classes.py:113 */
     orc_scan_cfg scan;
     orc_map map;
@@ -633,6 +634,7 @@ typedef struct {
     orc_car cars[ORC_MAX_AGENTS];
     double collisions[ORC_MAX_AGENTS];
     double collision_idx[ORC_MAX_AGENTS];
+    double scan_poses[ORC_MAX_AGENTS][3]; /* Simulator.agent_poses (:567): where the last scans were taken, before the iTTC zeroing */
     /* F110Env members (f110_env.py:160-187) */
     double start_xs[ORC_MAX_AGENTS], start_ys[ORC_MAX_AGENTS], start_thetas[ORC_MAX_AGENTS];
     double start_rot[2][2];
@@ -656,6 +658,7 @@ void orc_env_init(orc_env *e, int num_agents, int ego_idx, int integrator, doubl
     e->integrator = integrator;
     e->time_step = time_step;
     memcpy(e->params, params18, sizeof(double) * P_COUNT);
+    for (int i = 0; i < ORC_MAX_AGENTS; i++) memcpy(e->car_params[i], params18, sizeof(double) * P_COUNT);
     e->ttc_thresh = 0.005;
     e->scan = *scan;
     e->map = *map;
@@ -668,6 +671,19 @@ void orc_env_init(orc_env *e, int num_agents, int ego_idx, int integrator, doubl
     e->start_rot[0][0] = 1; e->start_rot[1][1] = 1;
 }
 
+/* Simulator.update_params (base_classes.py:507-527): every agent (agent_idx < 0) or one; Simulator.params stays.
+ * Returns 0, or -1 for an index beyond the agent list (the reference's IndexError). */
+int orc_env_update_params(orc_env *e, const double *params18, int agent_idx)
+{
+    if (agent_idx >= e->num_agents) return -1;
+    for (int i = 0; i < e->num_agents; i++)
+        if (agent_idx < 0 || agent_idx == i) memcpy(e->car_params[i], params18, sizeof(double) * P_COUNT);
+    return 0;
+}
+
+/* F110Env.update_map (f110_env.py:349-360): the scan simulator's map, nothing else */
+void orc_env_set_map(orc_env *e, const orc_map *map) { e->map = *map; }
+
 /* Simulator.step (base_classes.py:546-605).  scans: [num_agents, num_beams] out. */
 void orc_sim_step(orc_env *e, const double *control_inputs /*[A,2]*/, double *scans)
 {
@@ -678,7 +694,7 @@ void orc_sim_step(orc_env *e, const double *control_inputs /*[A,2]*/, double *sc
     for (int i = 0; i < A; i++) {
         orc_car *car = &e->cars[i];
         orc_car_update_pose(car, control_inputs[2 * i], control_inputs[2 * i + 1],
-                            e->params, e->time_step, e->integrator);
+                            e->car_params[i], e->time_step, e->integrator);
         double pose[3] = {car->state[0], car->state[1], car->state[4]};
         double *scan = scans + (size_t)i * nb;
         orc_get_scan(pose, &e->scan, &e->map, scan, NULL, &e->lookups);
@@ -688,6 +704,7 @@ void orc_sim_step(orc_env *e, const double *control_inputs /*[A,2]*/, double *sc
         }
         car->noise_step++;
         agent_poses[i][0] = pose[0]; agent_poses[i][1] = pose[1]; agent_poses[i][2] = pose[2];
+        memcpy(e->scan_poses[i], pose, sizeof(pose));
     }
     /* :570 check_collision (:529-543) */
     for (int i = 0; i < A; i++)
@@ -707,7 +724,9 @@ void orc_sim_step(orc_env *e, const double *control_inputs /*[A,2]*/, double *sc
         double pose[3] = {car->state[0], car->state[1], car->state[4]};
         for (int j = 0; j < A; j++) {
             if (j == i) continue;
-            orc_ray_cast(pose, scan, e->scan_angles, nb, verts[j]);
+            double opp[4][2]; /* :221 the opponent's quad in the size of car i's OWN params */
+            orc_get_vertices(agent_poses[j], e->car_params[i][P_LENGTH], e->car_params[i][P_WIDTH], opp);
+            orc_ray_cast(pose, scan, e->scan_angles, nb, opp);
         }
         if (car->in_collision)
             e->collisions[i] = 1.;
@@ -794,6 +813,11 @@ void orc_env_get(const orc_env *e, double *states /*[A,7]*/, double *collisions,
     }
     *current_time = e->current_time;
     if (lookups) *lookups = e->lookups;
+}
+
+void orc_env_get_scan_poses(const orc_env *e, double *poses /*[A,3]*/)
+{
+    memcpy(poses, e->scan_poses, sizeof(double) * 3 * e->num_agents);
 }
 
 void orc_env_set_state(orc_env *e, int agent, const double state[7], const double steer_buffer[2],

@@ -15,6 +15,9 @@ Fixtures:
   g6_raycast.npz   ray_cast, get_blocked_view_indices
   g7_sim.npz       Simulator.step trajectories (1 and 2 agents)
   g8_env.npz       F110Env 2-lap closed loop with the reference's pure-pursuit caller
+  g9 ... g12       make_golden_r2.py; g13_raycast_edges.npz  make_golden_r3.py
+  g14_<case>.npz   make_golden_configs.py: F110Env runs at off-default configurations (3 / 4 agents, other ego_idx, Euler,
+                   other timesteps, maps, fov, seed and vehicles, update_params / update_map, resets, the class statics)
 """
 import importlib.util
 import os
