@@ -381,6 +381,60 @@ int f110_pure_pursuit_tracks(f110_handle *h, const double *waypoints, const int3
                              double vgain, double wheelbase, double max_reacquire, const double *state, int32_t n,
                              double *actions, double *workspace, int32_t boxes_valid, void *stream);
 
+/* Progress along the raceline: per car the Frenet pose on its raceline and the metres driven since its reset, from the
+ * state the step left (no reference counterpart as a function; the nearest point is examples/waypoint_follow.py:16-47,
+ * the consumer the reference's own RL loop, src/SAL.py:233-236, which pays for metres moved).
+ * A raceline is M >= 2 points (x, y); its segments are i = 0 .. M-2 as nearest_point_on_trajectory sees them (the closing
+ * segment from the last point back to the first is not searched).  The caller computes the tables on the HOST (NumPy in
+ * red_gym_amd/progress.py) and the library uploads them -- the device takes no sqrt of a segment and no atan2:
+ *   len[i] = sqrt(dx*dx + dy*dy), cum = [0, cumsum(len)], psi[i] = atan2(dy, dx), lap_length = cum[M-1] + |first - last|.
+ * Per car and f110_progress_update, fp64 without contraction, (px, py, yaw) = state[car, (0, 1, 4)]:
+ *   1. (seg, t, dist) = the reference's nearest point: first minimum over the segments in ascending order
+ *   2. s = cum[seg] + t * len[seg]
+ *   3. d = dist with the sign of cross = dx*(py - y0) - dy*(px - x0), >= 0 -> +dist: left of the line is positive
+ *   4. heading_error = yaw - psi[seg]; if > pi: -= 2 pi; if <= -pi: += 2 pi (one pass each)
+ *   5. the env was reset by the last step that stepped it, or the car has not been seen (seen[car] == 0): delta = 0,
+ *      progress = 0; else delta = s - s_prev; if >= L/2: -= L; if < -L/2: += L; progress += delta.  Then s_prev = s, seen = 1.
+ *   6. px or py not finite: s, d, heading_error, delta = NaN, seg = 0; progress and s_prev stay (and seen goes to 0 when 5.
+ *      asked for a restart, which the next finite pose then takes).
+ * "Reset by its last step" is read off the env's clock: f110_buffers.current_time[env] == timestep exactly, which holds
+ * after the step that reset the env (f110_reset, masked or not, and autoreset alike) and after no other, since every
+ * further step adds the time step.  So the update after the step in which an env reports done still sees the terminal
+ * pose and pays that step's delta, and the update after the NEXT step starts the new episode at 0; an env a masked
+ * f110_reset left alone is not restarted; two updates without a step between give delta = 0 the second time.
+ * f110_progress_install: host arrays; waypoints [total,2] = the K racelines back to back, offsets [K+1] (offsets[0] = 0,
+ * offsets[K] = total), len / cum / psi [total] (raceline k's at offsets[k]; the last len / psi entry of a raceline is
+ * unused), lap_length [K], raceline_of_env [num_envs] or NULL (all envs on raceline 0).  The handle keeps its OWN device
+ * copy of all of it (nothing of the caller's is retained or matched later).  grid != 0 and K == 1 with at most 65 535
+ * points: the search runs over the planner's grid of candidate lists (see f110_pure_pursuit_prepare; cell 0.25 m, margin
+ * 3 m, same escapes to every segment); otherwise over every segment of the car's raceline -- the same results.
+ * Refused with F110_E_INVALID, nothing installed and the previous tracker kept: fewer than 2 points, a zero-length
+ * segment, a non-finite coordinate or table entry, a lap length that is not positive, a raceline index outside 0..K-1
+ * (f110_progress_validate is that check alone: no handle, no device).  K = 0 or waypoints = NULL removes the tracker.
+ * A cold path (allocates, synchronises); install and removal move the launch epoch.
+ * f110_progress_bind: the caller-owned outputs, dev, one element per car (N = num_envs * num_agents); progress, s_prev
+ * and seen are state carried from update to update (zero them to start; checkpoint them with the step's buffers).
+ * f110_progress_update: one kernel on `stream`, no allocation, no synchronisation (capturable behind f110_step).
+ * F110_E_INVALID without a tracker, F110_E_UNBOUND before f110_progress_bind or f110_bind. */
+typedef struct {
+    double *s;             /* [N] arc length of the projection on the car's raceline, 0 .. cum[M-1] */
+    double *d;             /* [N] lateral offset, left positive */
+    double *heading_error; /* [N] yaw relative to the segment, (-pi, pi] */
+    double *delta;         /* [N] metres along the raceline since the previous update (0 at a restart) */
+    double *progress;      /* [N] sum of delta since the car's reset */
+    double *s_prev;        /* [N] s of the previous update */
+    int32_t *seg;          /* [N] nearest segment */
+    uint8_t *seen;         /* [N] 1 once the car has been placed */
+} f110_progress_buffers;
+int f110_progress_validate(const double *waypoints_host, const int32_t *offsets_host, int32_t K, const double *len_host,
+                           const double *cum_host, const double *psi_host, const double *lap_length_host,
+                           const int32_t *raceline_of_env_host, int32_t num_envs);
+int f110_progress_install(f110_handle *h, const double *waypoints_host, const int32_t *offsets_host, int32_t K,
+                          const double *len_host, const double *cum_host, const double *psi_host,
+                          const double *lap_length_host, const int32_t *raceline_of_env_host, int32_t grid);
+int f110_progress_bind(f110_handle *h, const f110_progress_buffers *bufs);
+int f110_progress_update(f110_handle *h, void *stream);
+
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).
  * scans_f32 / lookups may be NULL; lookups [n] is overwritten-by-accumulation like

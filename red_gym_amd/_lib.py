@@ -44,6 +44,14 @@ class Buffers(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in BUFFER_FIELDS]
 
 
+# f110_progress_buffers: the progress tracker's caller-owned outputs, one element per car
+PROGRESS_FIELDS = ['s', 'd', 'heading_error', 'delta', 'progress', 's_prev', 'seg', 'seen']
+
+
+class ProgressBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in PROGRESS_FIELDS]
+
+
 # every symbol include/f110_hip.h declares: name -> argtypes (restype int unless noted)
 _VP, _I32, _I64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -94,6 +102,10 @@ SYMBOLS = {
     'f110_pure_pursuit_prepare': [_VP, _VP, _I32, _D, _D, _VP],
     'f110_pure_pursuit_workspace': [_I32, _I32],
     'f110_pure_pursuit_tracks': [_VP, _VP, _VP, _VP, _I32, _VP, _D, _D, _D, _D, _VP, _I32, _VP, _VP, _I32, _VP],
+    'f110_progress_validate': [_VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _I32],
+    'f110_progress_install': [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _I32],
+    'f110_progress_bind': [_VP, C.POINTER(ProgressBuffers)],
+    'f110_progress_update': [_VP, _VP],
     'f110_profile_begin': [_VP, _I32],
     'f110_profile_every': [_VP, _I32],
     'f110_profile_end': [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32)],

@@ -36,53 +36,41 @@ static int32_t *single_track_offsets(int dev, int M)
     return d.hdr;
 }
 
-// Builds the grid of candidate lists for one raceline (dev [M,3]) in the handle: a cold path (the raceline is copied to the host,
-// ~0.1 s for the 783-point example raceline).  The caller promises to call it again when the raceline's values change; the pointer
-// and M are what f110_pure_pursuit matches (red_gym_amd.Engine passes the handle only for the very tensor it prepared, unchanged,
-// and NULL otherwise).  A successful call replaces the grid's memory and moves the launch epoch; a failed one leaves no grid.
-// cell: edge of a grid cell in metres (0: 0.25); margin: how far around the raceline's bounding box the grid reaches (0: 3 m) --
-// poses beyond it are planned by the exhaustive search.
-extern "C" int f110_pure_pursuit_prepare(f110_handle *h, const double *waypoints, int32_t M, double cell, double margin, void *stream)
+// Host half of a raceline's grid of candidate lists (f110_planner.h PlanGrid): the points are (wp[stride * i], wp[stride * i + 1]),
+// i < M; `g` gets the geometry and the degenerate flag, `count` / `cand` the tables to upload (g.count / g.cand stay unset).
+// cell: edge of a grid cell in metres; margin: how far around the raceline's bounding box the grid reaches.  Shared by the
+// planner's prepare and the progress tracker's install, so that both search the same lists.
+static int build_plan_grid(const char *who, const double *wp, int stride, int M, double cell, double margin, PlanGrid &g,
+                           std::vector<uint8_t> &count, std::vector<uint16_t> &cand)
 {
-    if (!h) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: null argument");
-    if (int rc = check_device(h, "f110_pure_pursuit_prepare")) return rc;
-    h->plan_ok = false;
-    if (!waypoints) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: null argument");
-    if (M < 2 || M > 65535) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: M=%d waypoints (2..65535)", M);
-    if (!(cell >= 0) || !(margin >= 0) || !std::isfinite(cell) || !std::isfinite(margin)) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: bad cell / margin");
-    if (cell == 0) cell = 0.25;
-    if (margin == 0) margin = 3.0;
-    std::vector<double> wp((size_t)M * 3);
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipMemcpy(wp.data(), waypoints, wp.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t st = (size_t)stride;
     const int nseg = M - 1;
     double xl = 1e300, xh = -1e300, yl = 1e300, yh = -1e300;
     bool finite = true, degenerate = false;
     for (int i = 0; i < M; i++) {
-        const double x = wp[3 * (size_t)i], y = wp[3 * (size_t)i + 1];
+        const double x = wp[st * (size_t)i], y = wp[st * (size_t)i + 1];
         finite = finite && std::isfinite(x) && std::isfinite(y);
         xl = std::min(xl, x); xh = std::max(xh, x); yl = std::min(yl, y); yh = std::max(yh, y);
     }
-    if (!finite) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: the raceline has non-finite points");
+    if (!finite) return fail(F110_E_INVALID, "%s: the raceline has non-finite points", who);
     for (int i = 0; i < nseg; i++) {
-        const double dx = wp[3 * (size_t)i + 3] - wp[3 * (size_t)i], dy = wp[3 * (size_t)i + 4] - wp[3 * (size_t)i + 1];
+        const double dx = wp[st * (size_t)(i + 1)] - wp[st * (size_t)i], dy = wp[st * (size_t)(i + 1) + 1] - wp[st * (size_t)i + 1];
         if (dx * dx + dy * dy == 0.0) degenerate = true;
     }
-    PlanGrid g;
     memset(&g, 0, sizeof(g));
     g.x0 = xl - margin; g.y0 = yl - margin; g.inv_cell = 1.0 / cell;
     const double gw = std::ceil((xh + margin - g.x0) / cell), gh = std::ceil((yh + margin - g.y0) / cell);
-    if (!(gw >= 1 && gh >= 1) || gw * gh > 16.0e6) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: grid of %.0f x %.0f cells (choose a larger cell)", gw, gh);
+    if (!(gw >= 1 && gh >= 1) || gw * gh > 16.0e6) return fail(F110_E_INVALID, "%s: grid of %.0f x %.0f cells (choose a larger cell)", who, gw, gh);
     g.gw = (int)gw; g.gh = (int)gh; g.degenerate = degenerate ? 1 : 0;
     const size_t cells = (size_t)g.gw * g.gh;
-    std::vector<uint8_t> count(cells, 0);
-    std::vector<uint16_t> cand(cells * PG_CAP, 0);
+    count.assign(cells, 0);
+    cand.assign(cells * PG_CAP, 0);
     if (!degenerate) {
         // segments bucketed by a coarse grid first, so that a cell only looks at the segments that can matter
         const double hd = 0.5 * cell * std::sqrt(2.0);
         auto seg_dist = [&](int i, double px, double py) {
-            const double x0 = wp[3 * (size_t)i], y0 = wp[3 * (size_t)i + 1];
-            const double dx = wp[3 * (size_t)i + 3] - x0, dy = wp[3 * (size_t)i + 4] - y0;
+            const double x0 = wp[st * (size_t)i], y0 = wp[st * (size_t)i + 1];
+            const double dx = wp[st * (size_t)(i + 1)] - x0, dy = wp[st * (size_t)(i + 1) + 1] - y0;
             const double l2 = dx * dx + dy * dy;
             double t = ((px - x0) * dx + (py - y0) * dy) / l2;
             t = t < 0.0 ? 0.0 : t; t = t > 1.0 ? 1.0 : t;
@@ -103,6 +91,33 @@ extern "C" int f110_pure_pursuit_prepare(f110_handle *h, const double *waypoints
                 count[c] = n > (unsigned)PG_CAP ? (uint8_t)PG_ALL : (uint8_t)n;
             }
     }
+    return F110_OK;
+}
+
+// Builds the grid of candidate lists for one raceline (dev [M,3]) in the handle: a cold path (the raceline is copied to the host,
+// ~0.1 s for the 783-point example raceline).  The caller promises to call it again when the raceline's values change; the pointer
+// and M are what f110_pure_pursuit matches (red_gym_amd.Engine passes the handle only for the very tensor it prepared, unchanged,
+// and NULL otherwise).  A successful call replaces the grid's memory and moves the launch epoch; a failed one leaves no grid.
+// cell: edge of a grid cell in metres (0: 0.25); margin: how far around the raceline's bounding box the grid reaches (0: 3 m) --
+// poses beyond it are planned by the exhaustive search.
+extern "C" int f110_pure_pursuit_prepare(f110_handle *h, const double *waypoints, int32_t M, double cell, double margin, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: null argument");
+    if (int rc = check_device(h, "f110_pure_pursuit_prepare")) return rc;
+    h->plan_ok = false;
+    if (!waypoints) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: null argument");
+    if (M < 2 || M > 65535) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: M=%d waypoints (2..65535)", M);
+    if (!(cell >= 0) || !(margin >= 0) || !std::isfinite(cell) || !std::isfinite(margin)) return fail(F110_E_INVALID, "f110_pure_pursuit_prepare: bad cell / margin");
+    if (cell == 0) cell = 0.25;
+    if (margin == 0) margin = 3.0;
+    std::vector<double> wp((size_t)M * 3);
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(wp.data(), waypoints, wp.size() * sizeof(double), hipMemcpyDeviceToHost));
+    PlanGrid g;
+    std::vector<uint8_t> count;
+    std::vector<uint16_t> cand;
+    if (int rc = build_plan_grid("f110_pure_pursuit_prepare", wp.data(), 3, M, cell, margin, g, count, cand)) return rc;
+    const size_t cells = (size_t)g.gw * g.gh;
     ON_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize()); // an enqueued plan may still read the previous grid
     h->epoch++; // a captured launch of the grid kernel takes the grid's pointers by value: they are freed below
@@ -201,6 +216,121 @@ extern "C" int f110_pure_pursuit_tracks(f110_handle *h, const double *waypoints,
     a.t = t; a.track_of_car = track_of_car; a.lookahead = lookahead; a.vgain = vgain; a.wheelbase = wheelbase;
     a.max_reacquire = max_reacquire; a.state = state; a.n = n; a.actions = actions;
     hipLaunchKernelGGL(pure_pursuit_tracks_kernel, dim3((n + PPG_WAVES - 1) / PPG_WAVES), dim3(PPG_WAVES * 64), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+// ---------------------------------------------------------------- progress along the raceline
+// What install refuses, on host arrays alone (no handle, no device): the all-or-nothing rule of the map installs.
+extern "C" int f110_progress_validate(const double *waypoints, const int32_t *offsets, int32_t K, const double *len, const double *cum,
+                                      const double *psi, const double *lap_length, const int32_t *raceline_of_env, int32_t num_envs)
+{
+    const char *who = "f110_progress_validate";
+    if (K < 1) return fail(F110_E_INVALID, "%s: K=%d racelines (at least 1)", who, K);
+    if (!waypoints || !offsets || !len || !cum || !psi || !lap_length) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (num_envs < 0 || (raceline_of_env && num_envs < 1)) return fail(F110_E_INVALID, "%s: num_envs=%d", who, num_envs);
+    if (offsets[0] != 0) return fail(F110_E_INVALID, "%s: offsets[0] must be 0", who);
+    for (int k = 0; k < K; k++) {
+        const int64_t m = (int64_t)offsets[k + 1] - offsets[k];
+        if (m < 2 || m > 0x3fffffff) return fail(F110_E_INVALID, "%s: raceline %d has %lld points (at least 2)", who, k, (long long)m);
+        const size_t o = (size_t)offsets[k];
+        for (int64_t i = 0; i < m; i++) {
+            if (!std::isfinite(waypoints[2 * (o + i)]) || !std::isfinite(waypoints[2 * (o + i) + 1]))
+                return fail(F110_E_INVALID, "%s: raceline %d has a non-finite point (row %lld)", who, k, (long long)i);
+            if (!std::isfinite(cum[o + i])) return fail(F110_E_INVALID, "%s: raceline %d: cum[%lld] is not finite", who, k, (long long)i);
+        }
+        for (int64_t i = 0; i + 1 < m; i++) {
+            const double dx = waypoints[2 * (o + i + 1)] - waypoints[2 * (o + i)], dy = waypoints[2 * (o + i + 1) + 1] - waypoints[2 * (o + i) + 1];
+            if (dx * dx + dy * dy == 0.0 || !(len[o + i] > 0.0))
+                return fail(F110_E_INVALID, "%s: raceline %d has a zero-length segment (%lld)", who, k, (long long)i);
+            if (!std::isfinite(len[o + i]) || !std::isfinite(psi[o + i]))
+                return fail(F110_E_INVALID, "%s: raceline %d: len / psi of segment %lld is not finite", who, k, (long long)i);
+        }
+        if (!(lap_length[k] > 0.0) || !std::isfinite(lap_length[k]))
+            return fail(F110_E_INVALID, "%s: raceline %d has lap length %g (must be positive and finite)", who, k, lap_length[k]);
+    }
+    if (raceline_of_env)
+        for (int e = 0; e < num_envs; e++)
+            if (raceline_of_env[e] < 0 || raceline_of_env[e] >= K)
+                return fail(F110_E_INVALID, "%s: env %d on raceline %d (0..%d)", who, e, raceline_of_env[e], K - 1);
+    return F110_OK;
+}
+
+extern "C" int f110_progress_install(f110_handle *h, const double *waypoints, const int32_t *offsets, int32_t K, const double *len,
+                                     const double *cum, const double *psi, const double *lap_length, const int32_t *raceline_of_env,
+                                     int32_t grid)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_progress_install: null handle");
+    f110_handle::Progress &p = h->progress;
+    if (K == 0 || !waypoints) { // removes the tracker
+        if (!p.on) return F110_OK;
+        ON_DEVICE(h->cfg.device);
+        HIP_TRY(hipDeviceSynchronize()); // an enqueued update may still read the tables
+        const f110_progress_buffers bufs = p.bufs;
+        const bool bound = p.bound;
+        p = f110_handle::Progress();
+        p.bufs = bufs; p.bound = bound;
+        h->epoch++;
+        return F110_OK;
+    }
+    if (int rc = f110_progress_validate(waypoints, offsets, K, len, cum, psi, lap_length, raceline_of_env, h->cfg.num_envs)) return rc;
+    if (!(h->cfg.timestep > 0.0)) return fail(F110_E_INVALID, "f110_progress_install: the handle's timestep is %g (an env's reset is read off its clock: it must be positive)", h->cfg.timestep);
+    const size_t total = (size_t)offsets[K];
+    f110_handle::Progress n;
+    n.K = K;
+    // one raceline: the planner's grid of candidate lists (a raceline it cannot hold is searched segment by segment: same results)
+    std::vector<uint8_t> count;
+    std::vector<uint16_t> cand;
+    if (grid && K == 1 && total <= 65535 && build_plan_grid("f110_progress_install", waypoints, 2, (int)total, 0.25, 3.0, n.grid, count, cand) == F110_OK)
+        n.use_grid = true;
+    ON_DEVICE(h->cfg.device);
+    HIP_TRY(n.d_xy.upload(waypoints, total * 2));
+    HIP_TRY(n.d_len.upload(len, total));
+    HIP_TRY(n.d_cum.upload(cum, total));
+    HIP_TRY(n.d_psi.upload(psi, total));
+    HIP_TRY(n.d_lap.upload(lap_length, (size_t)K));
+    HIP_TRY(n.d_offsets.upload(offsets, (size_t)K + 1));
+    if (raceline_of_env) HIP_TRY(n.d_env.upload(raceline_of_env, (size_t)h->cfg.num_envs));
+    if (n.use_grid) {
+        HIP_TRY(n.d_count.upload(count.data(), count.size()));
+        HIP_TRY(n.d_cand.upload(cand.data(), cand.size()));
+        n.grid.count = n.d_count.get(); n.grid.cand = n.d_cand.get();
+    }
+    HIP_TRY(hipDeviceSynchronize()); // an enqueued update may still read the tables that are replaced
+    n.bufs = p.bufs; n.bound = p.bound; n.on = true;
+    p = std::move(n);
+    h->epoch++; // a captured update takes the tables' pointers by value
+    return F110_OK;
+}
+
+extern "C" int f110_progress_bind(f110_handle *h, const f110_progress_buffers *b)
+{
+    if (!h || !b) return fail(F110_E_INVALID, "f110_progress_bind: null argument");
+    if (!b->s || !b->d || !b->heading_error || !b->delta || !b->progress || !b->s_prev || !b->seg || !b->seen)
+        return fail(F110_E_INVALID, "f110_progress_bind: a buffer is NULL (all eight are required)");
+    h->progress.bufs = *b;
+    h->progress.bound = true;
+    h->epoch++;
+    return F110_OK;
+}
+
+extern "C" int f110_progress_update(f110_handle *h, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_progress_update: null handle");
+    const f110_handle::Progress &p = h->progress;
+    if (!p.on) return fail(F110_E_INVALID, "f110_progress_update: no tracker is installed (f110_progress_install)");
+    if (!p.bound) return fail(F110_E_UNBOUND, "f110_progress_update: f110_progress_bind has not been called");
+    if (!h->bound) return fail(F110_E_UNBOUND, "f110_progress_update: f110_bind has not been called");
+    if (int rc = check_device(h, "f110_progress_update")) return rc;
+    ProgressArgs a;
+    memset(&a, 0, sizeof(a));
+    a.state = h->bufs.state; a.n = h->cfg.num_envs * h->cfg.num_agents; a.agents = h->cfg.num_agents;
+    a.xy = p.d_xy.get(); a.len = p.d_len.get(); a.cum = p.d_cum.get(); a.psi = p.d_psi.get(); a.lap = p.d_lap.get();
+    a.offsets = p.d_offsets.get(); a.raceline_of_env = p.d_env.get(); a.K = p.K; a.use_grid = p.use_grid ? 1 : 0; a.g = p.grid;
+    a.current_time = h->bufs.current_time; a.timestep = h->cfg.timestep;
+    a.s = p.bufs.s; a.d = p.bufs.d; a.heading_error = p.bufs.heading_error; a.delta = p.bufs.delta; a.progress = p.bufs.progress;
+    a.s_prev = p.bufs.s_prev; a.seg = p.bufs.seg; a.seen = p.bufs.seen; a.dev_err = h->d_err.get();
+    hipLaunchKernelGGL(progress_kernel, dim3((a.n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return F110_OK;
 }

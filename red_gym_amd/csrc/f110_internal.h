@@ -5,12 +5,13 @@
 //   f110_maps.hip       map installation (host table / occupancy mask -> cell codes, LUTs), device EDT, track mask
 //   f110_noise_abi.hip  lidar noise: slots, ring, generators, per-env mode
 //   f110_step.hip       launch policy of the scan, the step, hipGraphs, measurement aid, function-level entry points
-//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, scan -> bitmap, occupancy grid
+//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, progress tracker, scan -> bitmap, occupancy grid
 #pragma once
 #include "../../include/f110_hip.h"
 #include "f110_scan_plan.h"
 #include "f110_kernels.h"
 #include "f110_planner.h"
+#include "f110_progress.h"
 #include "f110_bitmap.h"
 #include "f110_mapgen.h"
 
@@ -186,6 +187,17 @@ struct f110_handle {
     const double *plan_wp = nullptr; int plan_M = 0; bool plan_ok = false;
     PlanGrid plan_grid;
     DevBuf<uint8_t> d_plan_count; DevBuf<uint16_t> d_plan_cand;
+    // progress tracker (f110_progress_install / _bind / _update, f110_consumers.hip): its own device copy of the racelines and
+    // their host-built tables, the grid of candidate lists of a single raceline, and the caller's output buffers
+    struct Progress {
+        bool on = false, bound = false, use_grid = false;
+        int K = 0;
+        DevBuf<double> d_xy, d_len, d_cum, d_psi, d_lap;
+        DevBuf<int32_t> d_offsets, d_env;   // d_env: [B] raceline of every env (empty: all on raceline 0)
+        PlanGrid grid;
+        DevBuf<uint8_t> d_count; DevBuf<uint16_t> d_cand;
+        f110_progress_buffers bufs;
+    } progress;
     const int32_t *scan_order = nullptr; // launch order of the step's scan (f110_set_scan_order; caller-owned device array) or NULL
     DevBuf<uint32_t> d_err;           // device error word (f110_device_errors)
     std::vector<double> h_side;       // side distances (host copy of d_side)

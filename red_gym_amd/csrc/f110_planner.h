@@ -34,6 +34,20 @@ __device__ inline bool seg_circle(double sx, double sy, double ex, double ey, do
     return true;
 }
 
+// nearest_point_on_trajectory (waypoint_follow.py:31-46) for ONE segment (x0, y0) -> (x1, y1): the clipped parameter t of the
+// projection of (px, py) and its distance.  The one text of the expression for the lane-per-car searches
+// (pure_pursuit_grid_kernel here, progress_kernel in f110_progress.h).
+__device__ inline double seg_nearest(double px, double py, double x0, double y0, double x1, double y1, double &t)
+{
+    const double dx = x1 - x0, dy = y1 - y0;
+    const double l2 = dx * dx + dy * dy;
+    t = ((px - x0) * dx + (py - y0) * dy) / l2;
+    t = t < 0.0 ? 0.0 : t;
+    t = t > 1.0 ? 1.0 : t;
+    const double qx = px - (x0 + t * dx), qy = py - (y0 + t * dy);
+    return sqrt(qx * qx + qy * qy);
+}
+
 // One WAVEFRONT per car (round 2; round 1 ran one lane per car, every lane walking all M - 1 segments: 128 us for
 // 65 536 cars on the 783-point example raceline).  The 64 lanes evaluate 64 consecutive segments at once, and whole
 // 64-segment blocks are skipped when their bounding box is farther from the car than a distance already found --
@@ -274,14 +288,8 @@ static __global__ __launch_bounds__(256) void pure_pursuit_grid_kernel(PlanArgs 
         double best = __builtin_inf(), best_t = 0;
         int best_i = 0;
         auto consider = [&](int i) {
-            const double x0 = wp[3 * i], y0 = wp[3 * i + 1];
-            const double dx = wp[3 * i + 3] - x0, dy = wp[3 * i + 4] - y0;
-            const double l2 = dx * dx + dy * dy;
-            double t = ((px - x0) * dx + (py - y0) * dy) / l2;
-            t = t < 0.0 ? 0.0 : t;
-            t = t > 1.0 ? 1.0 : t;
-            const double qx = px - (x0 + t * dx), qy = py - (y0 + t * dy);
-            const double d = sqrt(qx * qx + qy * qy);
+            double t;
+            const double d = seg_nearest(px, py, wp[3 * i], wp[3 * i + 1], wp[3 * i + 3], wp[3 * i + 4], t);
             if (d < best) { best = d; best_i = i; best_t = t; }
         };
         const double fx = floor((px - g.x0) * g.inv_cell), fy = floor((py - g.y0) * g.inv_cell);

@@ -182,6 +182,7 @@ class Engine(object):
         self.scan_reorder = True  # keep the scan's launch order sorted by noise row (Engine._reorder_scan); False: car order
         self._reorder_count, self._scan_order, self.env_noise_assign = 0, None, None
         self.noise_tables = []
+        self.p, self.progress_lines, self.lap_length = None, None, None   # progress tracker (set_progress)
         if env_params is not None:
             self.set_env_params(env_params)
         if self._noise_on:
@@ -709,6 +710,53 @@ class Engine(object):
         tracks.boxes_valid = True
         self._keep_tracks = (tracks, track_of_car)
         return out.view(self.B, self.A, 2) if state is None else out
+
+    # ------------------------------------------------------------------ progress along the raceline
+    _PROGRESS_DTYPES = {'s': torch.float64, 'd': torch.float64, 'heading_error': torch.float64, 'delta': torch.float64,
+                        'progress': torch.float64, 's_prev': torch.float64, 'seg': torch.int32, 'seen': torch.uint8}
+
+    def set_progress(self, racelines, raceline_of_env=None, grid=True):
+        """Installs the progress tracker (f110_progress_install): `racelines` one [M, >= 2] array (columns 0, 1 = x, y) or a
+        sequence of K of them, `raceline_of_env` int array [num_envs] (None: every env on raceline 0); None removes it.
+        The tables are computed here with NumPy (red_gym_amd.progress) and the handle keeps its own device copy of
+        everything.  The outputs live in self.p (tensors [B, A]: s, d, heading_error, delta, progress, s_prev, seg, seen);
+        an install starts every car anew (seen = 0).  grid=False searches every segment even for a single raceline (the
+        results are the same).  ValueError for what the library refuses: a zero-length segment, fewer than 2 points,
+        non-finite coordinates, a raceline index outside 0..K-1."""
+        from .progress import PackedRacelines
+        if racelines is None:
+            _lib.check(self.lib.f110_progress_install(self._h, None, None, 0, None, None, None, None, None, 0))
+            self.progress_lines, self.lap_length = None, None
+            return
+        if torch.is_tensor(racelines) or (isinstance(racelines, np.ndarray) and racelines.ndim == 2):
+            racelines = [racelines]
+        pk = PackedRacelines(racelines)
+        assign = None
+        if raceline_of_env is not None:
+            assign = np.ascontiguousarray(raceline_of_env, dtype=np.int32)
+            if assign.shape != (self.B,):
+                raise ValueError('raceline_of_env must have one entry per env (%d), got shape %s' % (self.B, assign.shape))
+        _lib.check(self.lib.f110_progress_install(self._h, _np_ptr(pk.xy), _np_ptr(pk.offsets), pk.K, _np_ptr(pk.len),
+                                                  _np_ptr(pk.cum), _np_ptr(pk.psi), _np_ptr(pk.lap_length),
+                                                  _np_ptr(assign) if assign is not None else None, int(bool(grid))))
+        if getattr(self, 'p', None) is None:
+            self.p = {k: torch.zeros((self.B, self.A), dtype=dt, device=self.device) for k, dt in self._PROGRESS_DTYPES.items()}
+            bufs = _lib.ProgressBuffers()
+            for name in _lib.PROGRESS_FIELDS:
+                setattr(bufs, name, self.p[name].data_ptr())
+            torch.cuda.synchronize(self.device)
+            _lib.check(self.lib.f110_progress_bind(self._h, C.byref(bufs)))
+        else:
+            self.p['seen'].zero_()
+        self.progress_lines = pk
+        lap = pk.lap_length[assign] if assign is not None else np.full(self.B, pk.lap_length[0])
+        self.lap_length = torch.as_tensor(lap, device=self.device)
+
+    @on_own_device
+    def progress_update(self):
+        """Enqueues the tracker's kernel on the current stream for the state as the last step left it (f110_progress_update:
+        no allocation, no synchronisation -- it can be captured behind step())."""
+        _lib.check(self.lib.f110_progress_update(self._h, self._stream()))
 
     @on_own_device
     def pack_env(self, env=0):

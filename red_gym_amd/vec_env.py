@@ -70,12 +70,17 @@ class F110VecEnv(object):
             self._obs['scans_f64'] = t['scans_f64']
         self._reward = torch.full((self.num_envs,), float(timestep), dtype=torch.float64, device=self.device)
         self._g_actions, self._graphs, self._lg = None, [], None   # capture_step / build_step_graph
+        self._tracking = False                                      # track_progress
 
     def _result(self):
         t = self.eng.t
         done = t['done']  # bool tensor written by env_kernel (no per-step torch kernels here)
         info = {'checkpoint_done': t['checkpoint_done'], 'collision_idx': t['collision_idx'],
                 'current_time': t['current_time'], 'toggles': t['toggles']}
+        if self._tracking:
+            p = self.eng.p
+            info.update(frenet_s=p['s'], frenet_d=p['d'], heading_error=p['heading_error'], progress=p['progress'],
+                        progress_delta=p['delta'], lap_length=self.eng.lap_length)
         return self._obs, self._reward, done, info
 
     def _as_dev(self, a, last):
@@ -97,12 +102,45 @@ class F110VecEnv(object):
         except ValueError:
             raise ValueError('Number of poses for reset does not match number of agents.')
         self.eng.reset(poses, mask)
+        if self._tracking:
+            self.eng.progress_update()
         return self._result()
 
     def step(self, actions):
         """actions [B,A,2] = (steer, speed) per car (f110_env.py:261-302)."""
         self.eng.step(self._as_dev(actions, 2))
+        if self._tracking:
+            self.eng.progress_update()
         return self._result()
+
+    # ------------------------------------------------------------------ progress along the raceline
+    def track_progress(self, racelines, assign=None):
+        """Switches the progress tracker on: `racelines` one [M, >= 2] array (columns 0, 1 = x, y; a planner's [M,3]
+        waypoints fit) or a list of K of them with `assign` [num_envs] = the raceline of every env (the form
+        raceline_slots takes, e.g. the slots of randomize_tracks with the tracks' centre lines).  From then on reset, step,
+        step_graph and step_lib_graph leave the tracker updated for the step they ran, and `info` also holds frenet_s
+        (metres along the raceline), frenet_d (lateral offset, left positive), heading_error, progress (metres driven
+        since the car's reset), progress_delta (this step's share; combine it into a reward as you like) -- views [B, A],
+        no copies -- and lap_length [B].  A reset (masked, whole batch or autoreset) restarts the car's progress at 0 in the
+        step that performs it.  None switches tracking off: no launch, no info key, no state_dict key remains."""
+        if racelines is None:
+            if self._tracking:
+                self.eng.set_progress(None)
+            self._tracking = False
+            return
+        if isinstance(racelines, (list, tuple)):
+            if assign is None and len(racelines) > 1:
+                raise ValueError('a list of racelines needs assign [num_envs]')
+            if assign is not None:
+                assign = np.asarray(assign)
+                if assign.shape != (self.num_envs,) or assign.min() < 0 or assign.max() >= len(racelines):
+                    raise ValueError('assign must hold one raceline index (0..%d) per env' % (len(racelines) - 1))
+        elif assign is not None:
+            raise ValueError('assign goes with a list of racelines')
+        self.eng.set_progress(racelines, assign)
+        self._tracking = True
+
+    _PROGRESS_KEYS = ('progress', 's_prev', 'seen')
 
     # ------------------------------------------------------------------ checkpoint / resume
     _STATE_KEYS = ('state', 'steer_buf', 'steer_cnt', 'noise_step', 'spawn', 'start_rot', 'near_start', 'toggles',
@@ -112,10 +150,21 @@ class F110VecEnv(object):
     def state_dict(self):
         """Everything a step depends on lives in the caller-owned tensors bound to the handle
         (f110_buffers): a copy of them is a complete checkpoint of all B envs."""
-        return {k: self.eng.t[k].clone() for k in self._STATE_KEYS if self.eng.t[k] is not None}
+        sd = {k: self.eng.t[k].clone() for k in self._STATE_KEYS if self.eng.t[k] is not None}
+        if self._tracking:
+            sd.update({k: self.eng.p[k].clone() for k in self._PROGRESS_KEYS})
+        return sd
 
     def load_state_dict(self, sd):
-        self.eng.load_state(sd)
+        """While tracking is on the checkpoint's progress, s_prev and seen are restored with it; one taken without them
+        starts every car's progress anew."""
+        self.eng.load_state({k: v for k, v in sd.items() if k not in self._PROGRESS_KEYS})
+        if self._tracking:
+            if all(k in sd for k in self._PROGRESS_KEYS):
+                for k in self._PROGRESS_KEYS:
+                    self.eng.p[k].copy_(sd[k])
+            else:
+                self.eng.p['seen'].zero_()
 
     # ------------------------------------------------------------------ hipGraph replay
     def capture_step(self, policy=None, copies=1):
@@ -144,6 +193,8 @@ class F110VecEnv(object):
                 if policy is not None:
                     policy(self, self._g_actions.view(-1, 2))
                 self.eng.step(self._g_actions)
+                if self._tracking:
+                    self.eng.progress_update()
             torch.cuda.current_stream(self.device).wait_stream(side)
             self._graphs.append(g)
         self._g_copies = len(self._graphs)
@@ -195,6 +246,8 @@ class F110VecEnv(object):
         if self.eng.launch_epoch() != self._lg_epoch:
             self.build_step_graph(self._lg_how)
         self.eng.launch_graph(self._lg)
+        if self._tracking:
+            self.eng.progress_update()   # behind the graph launch, on the same stream
         return self._result()
 
     def pure_pursuit(self, waypoints, lookahead, vgain, wheelbase=0.17145 + 0.15875, prepare=True):
