@@ -435,6 +435,64 @@ int f110_progress_install(f110_handle *h, const double *waypoints_host, const in
 int f110_progress_bind(f110_handle *h, const f110_progress_buffers *bufs);
 int f110_progress_update(f110_handle *h, void *stream);
 
+/* Reward shaping: per env the three bitmap reward terms of the reference's RL consumer, SACF110Env._calculate_rewards
+ * (src/SAL.py:219-250), from the FILL bitmap of the env's PREVIOUS step's scan and the pose the step left.  The reference
+ * restated with its quirks; fp64 without contraction.  (x, y) = state[env, agent, (0, 1)], img = bitmap[env] [rows, cols],
+ * (x0, y0) = prev_xy[env]:
+ *   pixel       px = clip(trunc(origin_x + x * scale), 0, clip_max), py likewise (_world_to_pixel, :139-142; trunc toward
+ *               zero like Python's int(); equal to the reference's for every finite x, however large)
+ *   collision   collided = 1 if any of the (2n+1)^2 - 1 neighbours (px + dx, py + dy), |dx|, |dy| <= n = neighborhood, the
+ *               centre excluded, with 0 <= px + dx < cols and 0 <= py + dy < rows has img[py + dy, px + dx] == 255
+ *               (detect_collison, :766-790; with a black-background FILL image 255 is the FILLED region: the reference's
+ *               behaviour, kept); collision_term = collided ? w_collision : 0.0
+ *   progress    progress_term = sqrt(dx*dx + dy*dy) * w_progress, dx = x - x0, dy = y - y0
+ *   centering   car_x = trunc(x), car_y = trunc(y): metres truncated, NOT pixels (the reference's quirk, :239-243).  Outside
+ *               the image: reward = -1.  Otherwise left = car_x, walk left while left >= 0 and img[car_y, left] == 255, then
+ *               left += 1; right = car_x, walk right while right < cols and img[car_y, right] == 255, then right -= 1;
+ *               left >= right (the car's pixel is not 255, or a one-pixel run): reward = -1; else dist = |car_x - (left +
+ *               right) / 2.0| and reward = max(0.0, 1.0 - dist / max_lane_halfwidth) (centerline_reward, :879-935);
+ *               centering_term = reward * w_centering
+ *   total       ((0.0 + progress_term) + collision_term) + centering_term  (sum() over the reference's dict; its lap term
+ *               tests a key the env never produces and is not built)
+ *   x or y not finite: the four outputs are NaN, collided = 0 and prev_xy[env] stays.
+ * Episode logic of f110_shaping_update, read off the env's clock like the progress tracker's: (1) current_time[env] ==
+ * timestep exactly (the env was reset by its last step: f110_reset, masked or not, or autoreset): all four outputs 0,
+ * collided 0, prev_xy = (x, y) -- the reference's reset() pays nothing and stores the reset pose; idempotent.  (2) else
+ * current_time[env] == t_seen[env]: the env has not stepped since its previous update (a masked reset left it alone):
+ * nothing of it is written.  (3) else the terms above (t_seen[env] < 0, "no update yet": with (x0, y0) = (x, y)); then
+ * prev_xy = (x, y), t_seen = current_time.  The step in which an env reports done is paid with its terminal pose.
+ * The caller renders the new scan's bitmap INTO THE SAME buffer after the update, on the same stream.
+ * f110_shaping_validate: host only.  F110_E_INVALID for rows or cols < 1, agent outside 0..num_agents-1, neighborhood < 0,
+ * clip_max < 0, a scalar that is not finite, max_lane_halfwidth <= 0.
+ * f110_shaping_install: cfg NULL removes the shaper; a refused cfg installs nothing and keeps what was there.  Install and
+ * removal move the launch epoch.  f110_shaping_bind: the caller-owned buffers, dev (all required; binding moves the epoch).
+ * f110_shaping_update: one kernel on `stream`, no allocation, no synchronisation (capturable behind f110_step).
+ * F110_E_INVALID without a shaper, F110_E_UNBOUND before f110_shaping_bind or f110_bind. */
+typedef struct {
+    int32_t rows, cols;         /* the bitmap's output_image_dims (256, 256) */
+    int32_t agent;              /* whose pose is read (0: SAL reads index 0) */
+    int32_t neighborhood;       /* n of detect_collison (1) */
+    int32_t clip_max;           /* upper clip of _world_to_pixel (255, whatever the image size: the reference's constant) */
+    double scale;               /* map_scale, pixels per metre (10.0) */
+    double origin_x, origin_y;  /* map_origin (128, 128) */
+    double max_lane_halfwidth;  /* centerline_reward's normaliser (50) */
+    double w_collision, w_progress, w_centering; /* -100.0, 10.0, 2.0 */
+} f110_shaping_config;
+typedef struct {
+    const uint8_t *bitmap;      /* [B, rows, cols] in: the image of the previous step's scan */
+    double *collision_term;     /* [B] */
+    double *progress_term;      /* [B] */
+    double *centering_term;     /* [B] */
+    double *total;              /* [B] */
+    uint8_t *collided;          /* [B] */
+    double *prev_xy;            /* [B,2] state: position at the env's previous update */
+    double *t_seen;             /* [B] state: current_time at the env's previous update; start at -1 (no clock is negative) */
+} f110_shaping_buffers;
+int f110_shaping_validate(const f110_shaping_config *cfg, int32_t num_agents);
+int f110_shaping_install(f110_handle *h, const f110_shaping_config *cfg);
+int f110_shaping_bind(f110_handle *h, const f110_shaping_buffers *bufs);
+int f110_shaping_update(f110_handle *h, void *stream);
+
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).
  * scans_f32 / lookups may be NULL; lookups [n] is overwritten-by-accumulation like
@@ -481,6 +539,13 @@ int f110_check_done(f110_handle *h, const double *poses, const double *start_pos
                     const double *current_time, const uint8_t *collisions, int32_t n, int32_t num_agents,
                     int32_t ego_idx, uint8_t *near_start, int32_t *toggles, int32_t *lap_counts, double *lap_times,
                     uint8_t *done, uint8_t *checkpoint_done, void *stream);
+/* The reward terms of f110_shaping_update without its episode logic, stateless (no handle; cfg host, cfg->agent is not
+ * read): n images bitmaps [n, rows, cols], positions xy [n,2] and prev_xy [n,2] -> collision_term, progress_term,
+ * centering_term, total [n] and collided [n] (SACF110Env._calculate_rewards on last_obs['lidar_bitmap'] = bitmaps[i],
+ * prev_position = prev_xy[i] and the new pose xy[i]).  Launches on the calling thread's current device. */
+int f110_shaping_terms(const f110_shaping_config *cfg, const uint8_t *bitmaps, const double *xy, const double *prev_xy,
+                       int32_t n, double *collision_term, double *progress_term, double *centering_term, double *total,
+                       uint8_t *collided, void *stream);
 
 /* ---- scan -> bird's-eye bitmap (the first consumer of the step's scans) ----
  * Replaces weap_util/weap_util/lidar.py:105-154 `lidar_to_bitmap` (same body in src/SAL.py:274-395

@@ -52,6 +52,21 @@ class ProgressBuffers(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in PROGRESS_FIELDS]
 
 
+# f110_shaping_config / f110_shaping_buffers: the reward shaper's options and its caller-owned buffers
+class ShapingConfig(C.Structure):
+    _fields_ = [('rows', C.c_int32), ('cols', C.c_int32), ('agent', C.c_int32), ('neighborhood', C.c_int32),
+                ('clip_max', C.c_int32), ('scale', C.c_double), ('origin_x', C.c_double), ('origin_y', C.c_double),
+                ('max_lane_halfwidth', C.c_double), ('w_collision', C.c_double), ('w_progress', C.c_double),
+                ('w_centering', C.c_double)]
+
+
+SHAPING_FIELDS = ['bitmap', 'collision_term', 'progress_term', 'centering_term', 'total', 'collided', 'prev_xy', 't_seen']
+
+
+class ShapingBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in SHAPING_FIELDS]
+
+
 # every symbol include/f110_hip.h declares: name -> argtypes (restype int unless noted)
 _VP, _I32, _I64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -106,6 +121,11 @@ SYMBOLS = {
     'f110_progress_install': [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _I32],
     'f110_progress_bind': [_VP, C.POINTER(ProgressBuffers)],
     'f110_progress_update': [_VP, _VP],
+    'f110_shaping_validate': [C.POINTER(ShapingConfig), _I32],
+    'f110_shaping_install': [_VP, C.POINTER(ShapingConfig)],
+    'f110_shaping_bind': [_VP, C.POINTER(ShapingBuffers)],
+    'f110_shaping_update': [_VP, _VP],
+    'f110_shaping_terms': [C.POINTER(ShapingConfig), _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],
     'f110_profile_every': [_VP, _I32],
     'f110_profile_end': [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32)],

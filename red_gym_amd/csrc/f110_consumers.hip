@@ -335,6 +335,97 @@ extern "C" int f110_progress_update(f110_handle *h, void *stream)
     return F110_OK;
 }
 
+// ---------------------------------------------------------------- reward shaping
+// What install refuses, on the struct alone (no handle, no device).
+extern "C" int f110_shaping_validate(const f110_shaping_config *cfg, int32_t num_agents)
+{
+    const char *who = "f110_shaping_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    if (cfg->rows < 1 || cfg->cols < 1) return fail(F110_E_INVALID, "%s: image of %d x %d pixels", who, cfg->rows, cfg->cols);
+    if (cfg->agent < 0 || cfg->agent >= num_agents) return fail(F110_E_INVALID, "%s: agent %d (0..%d)", who, cfg->agent, num_agents - 1);
+    if (cfg->neighborhood < 0) return fail(F110_E_INVALID, "%s: neighborhood %d is negative", who, cfg->neighborhood);
+    if (cfg->clip_max < 0) return fail(F110_E_INVALID, "%s: clip_max %d is negative", who, cfg->clip_max);
+    const double scalars[] = {cfg->scale, cfg->origin_x, cfg->origin_y, cfg->max_lane_halfwidth, cfg->w_collision, cfg->w_progress, cfg->w_centering};
+    for (double v : scalars)
+        if (!std::isfinite(v)) return fail(F110_E_INVALID, "%s: a scalar of the config is not finite", who);
+    if (!(cfg->max_lane_halfwidth > 0.0)) return fail(F110_E_INVALID, "%s: max_lane_halfwidth %g must be positive", who, cfg->max_lane_halfwidth);
+    return F110_OK;
+}
+
+extern "C" int f110_shaping_install(f110_handle *h, const f110_shaping_config *cfg)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_shaping_install: null handle");
+    f110_handle::Shaping &s = h->shaping;
+    if (!cfg) { // removes the shaper
+        if (!s.on) return F110_OK;
+        s.on = false;
+        h->epoch++;
+        return F110_OK;
+    }
+    if (int rc = f110_shaping_validate(cfg, h->cfg.num_agents)) return rc;
+    if (!(h->cfg.timestep > 0.0)) return fail(F110_E_INVALID, "f110_shaping_install: the handle's timestep is %g (an env's reset is read off its clock: it must be positive)", h->cfg.timestep);
+    s.cfg = *cfg; // by value in every launch: nothing on the device to replace
+    s.on = true;
+    h->epoch++;
+    return F110_OK;
+}
+
+extern "C" int f110_shaping_bind(f110_handle *h, const f110_shaping_buffers *b)
+{
+    if (!h || !b) return fail(F110_E_INVALID, "f110_shaping_bind: null argument");
+    if (!b->bitmap || !b->collision_term || !b->progress_term || !b->centering_term || !b->total || !b->collided || !b->prev_xy || !b->t_seen)
+        return fail(F110_E_INVALID, "f110_shaping_bind: a buffer is NULL (all eight are required)");
+    h->shaping.bufs = *b;
+    h->shaping.bound = true;
+    h->epoch++;
+    return F110_OK;
+}
+
+static int launch_shaping(const ShapingArgs &a, hipStream_t stream)
+{
+    if (a.n == 0) return F110_OK;
+    hipLaunchKernelGGL(shaping_kernel, dim3((a.n + SHAPING_WAVES - 1) / SHAPING_WAVES), dim3(64 * SHAPING_WAVES), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_shaping_update(f110_handle *h, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_shaping_update: null handle");
+    const f110_handle::Shaping &s = h->shaping;
+    if (!s.on) return fail(F110_E_INVALID, "f110_shaping_update: no shaper is installed (f110_shaping_install)");
+    if (!s.bound) return fail(F110_E_UNBOUND, "f110_shaping_update: f110_shaping_bind has not been called");
+    if (!h->bound) return fail(F110_E_UNBOUND, "f110_shaping_update: f110_bind has not been called");
+    if (int rc = check_device(h, "f110_shaping_update")) return rc;
+    ShapingArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cfg = s.cfg; a.bitmap = s.bufs.bitmap; a.n = h->cfg.num_envs;
+    a.xy = h->bufs.state + 7 * (size_t)s.cfg.agent; a.xy_stride = 7LL * h->cfg.num_agents;
+    a.current_time = h->bufs.current_time; a.timestep = h->cfg.timestep;
+    a.prev_in = s.bufs.prev_xy; a.prev_out = s.bufs.prev_xy; a.t_seen = s.bufs.t_seen;
+    a.collision_term = s.bufs.collision_term; a.progress_term = s.bufs.progress_term; a.centering_term = s.bufs.centering_term;
+    a.total = s.bufs.total; a.collided = s.bufs.collided; a.dev_err = h->d_err.get();
+    return launch_shaping(a, (hipStream_t)stream);
+}
+
+extern "C" int f110_shaping_terms(const f110_shaping_config *cfg, const uint8_t *bitmaps, const double *xy, const double *prev_xy,
+                                  int32_t n, double *collision_term, double *progress_term, double *centering_term, double *total,
+                                  uint8_t *collided, void *stream)
+{
+    if (!cfg) return fail(F110_E_INVALID, "f110_shaping_terms: null config");
+    f110_shaping_config c = *cfg;
+    c.agent = 0;
+    if (int rc = f110_shaping_validate(&c, 1)) return rc;
+    if (n < 0 || !bitmaps || !xy || !prev_xy || !collision_term || !progress_term || !centering_term || !total || !collided)
+        return fail(F110_E_INVALID, "f110_shaping_terms: bad arguments");
+    ShapingArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cfg = c; a.bitmap = bitmaps; a.n = n; a.xy = xy; a.xy_stride = 2; a.prev_in = prev_xy;
+    a.collision_term = collision_term; a.progress_term = progress_term; a.centering_term = centering_term; a.total = total;
+    a.collided = collided;
+    return launch_shaping(a, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- scan -> bitmap
 static const void *bitmap_fn(size_t lds, int mode, int channels)
 {

@@ -5,13 +5,15 @@
 //   f110_maps.hip       map installation (host table / occupancy mask -> cell codes, LUTs), device EDT, track mask
 //   f110_noise_abi.hip  lidar noise: slots, ring, generators, per-env mode
 //   f110_step.hip       launch policy of the scan, the step, hipGraphs, measurement aid, function-level entry points
-//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, progress tracker, scan -> bitmap, occupancy grid
+//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, progress tracker, reward shaper, scan -> bitmap,
+//                       occupancy grid
 #pragma once
 #include "../../include/f110_hip.h"
 #include "f110_scan_plan.h"
 #include "f110_kernels.h"
 #include "f110_planner.h"
 #include "f110_progress.h"
+#include "f110_shaping.h"
 #include "f110_bitmap.h"
 #include "f110_mapgen.h"
 
@@ -198,6 +200,12 @@ struct f110_handle {
         DevBuf<uint8_t> d_count; DevBuf<uint16_t> d_cand;
         f110_progress_buffers bufs;
     } progress;
+    // reward shaper (f110_shaping_install / _bind / _update, f110_consumers.hip): the configuration and the caller's buffers
+    struct Shaping {
+        bool on = false, bound = false;
+        f110_shaping_config cfg;
+        f110_shaping_buffers bufs;
+    } shaping;
     const int32_t *scan_order = nullptr; // launch order of the step's scan (f110_set_scan_order; caller-owned device array) or NULL
     DevBuf<uint32_t> d_err;           // device error word (f110_device_errors)
     std::vector<double> h_side;       // side distances (host copy of d_side)

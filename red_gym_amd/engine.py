@@ -183,6 +183,7 @@ class Engine(object):
         self._reorder_count, self._scan_order, self.env_noise_assign = 0, None, None
         self.noise_tables = []
         self.p, self.progress_lines, self.lap_length = None, None, None   # progress tracker (set_progress)
+        self.s, self.shaping_cfg = None, None                             # reward shaper (set_shaping)
         if env_params is not None:
             self.set_env_params(env_params)
         if self._noise_on:
@@ -757,6 +758,42 @@ class Engine(object):
         """Enqueues the tracker's kernel on the current stream for the state as the last step left it (f110_progress_update:
         no allocation, no synchronisation -- it can be captured behind step())."""
         _lib.check(self.lib.f110_progress_update(self._h, self._stream()))
+
+    # ------------------------------------------------------------------ reward shaping
+    _SHAPING_DTYPES = {'collision_term': torch.float64, 'progress_term': torch.float64, 'centering_term': torch.float64,
+                       'total': torch.float64, 'collided': torch.uint8, 't_seen': torch.float64}
+
+    def set_shaping(self, cfg):
+        """Installs the reward shaper (f110_shaping_install): `cfg` a dict of red_gym_amd.shaping.DEFAULTS' keys (missing ones
+        take SAL's numbers), or None to remove it.  The buffers live in self.s: bitmap [B, rows, cols] uint8 (the caller
+        renders every step's scan into it AFTER shaping_update), collision_term, progress_term, centering_term, total [B]
+        fp64, collided [B] uint8 and the state prev_xy [B, 2], t_seen [B].  An install starts the shaper anew (t_seen = -1:
+        the first update takes its previous position from its own pose).  ValueError for what the library refuses."""
+        from .shaping import make_config
+        if cfg is None:
+            _lib.check(self.lib.f110_shaping_install(self._h, None))
+            self.shaping_cfg = None
+            return
+        c = make_config(**cfg)
+        _lib.check(self.lib.f110_shaping_install(self._h, C.byref(c)))
+        with torch.cuda.device(self.device):
+            if self.s is None or tuple(self.s['bitmap'].shape[1:]) != (c.rows, c.cols):
+                self.s = {k: torch.zeros((self.B,), dtype=dt, device=self.device) for k, dt in self._SHAPING_DTYPES.items()}
+                self.s['prev_xy'] = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)
+                self.s['bitmap'] = torch.zeros((self.B, c.rows, c.cols), dtype=torch.uint8, device=self.device)
+                bufs = _lib.ShapingBuffers()
+                for name in _lib.SHAPING_FIELDS:
+                    setattr(bufs, name, self.s[name].data_ptr())
+                torch.cuda.synchronize(self.device)
+                _lib.check(self.lib.f110_shaping_bind(self._h, C.byref(bufs)))
+            self.s['t_seen'].fill_(-1.0)
+        self.shaping_cfg = c
+
+    @on_own_device
+    def shaping_update(self):
+        """Enqueues the shaper's kernel on the current stream: the rewards of the step just made, from self.s['bitmap'] as the
+        previous step left it (f110_shaping_update: no allocation, no synchronisation -- capturable behind step())."""
+        _lib.check(self.lib.f110_shaping_update(self._h, self._stream()))
 
     @on_own_device
     def pack_env(self, env=0):

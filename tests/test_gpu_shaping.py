@@ -1,0 +1,246 @@
+"""Reward shaper on the GPU (csrc/f110_shaping.h): every output `==` the reference's recorded results (g16) and the NumPy
+checker of tests/shaping_cases.py."""
+import os
+
+import numpy as np
+import pytest
+
+import shaping_cases as sc
+
+pytestmark = pytest.mark.gpu
+
+TLAD, VGAIN = 0.82461887897713965, 1.375
+OUT_KEYS = sc.TERMS + ('collided',)
+
+
+def _env(assets, B, A=1, **kw):
+    from red_gym_amd import F110VecEnv
+    return F110VecEnv(B, map=os.path.join(assets, 'example_map'), map_ext='.png', num_agents=A, **kw)
+
+
+def _waypoints(env):
+    import torch
+    from red_gym_amd import workload
+    rl = workload.load_waypoints(workload.RACELINE)
+    return torch.as_tensor(np.ascontiguousarray(rl[:, [1, 2, 5]]), device=env.device)
+
+
+def _outputs(reward, info):
+    import torch
+    torch.cuda.synchronize()
+    return {'total': reward.cpu().numpy().copy(), 'collision_term': info['reward_collision'].cpu().numpy(),
+            'progress_term': info['reward_progress'].cpu().numpy(), 'centering_term': info['reward_centering'].cpu().numpy(),
+            'collided': info['bitmap_collided'].cpu().numpy()}
+
+
+def _assert_same(got, want, what):
+    bad = {k: int((~sc.same(got[k], want[k])).sum()) for k in OUT_KEYS}
+    print(what, 'differing elements:', bad)
+    assert not any(bad.values()), (what, bad)
+
+
+def test_kernel_equals_the_reference_on_g16(golden):
+    """The function-level kernel on every case of g16, every image size: the four terms and collided `==` what the
+    reference's own _calculate_rewards returned."""
+    import torch
+    from red_gym_amd import shaping
+    g = golden('g16_shaping.npz')
+    for gi, grp in enumerate(sc.GROUPS):
+        imgs = sc.unpack_images(g, grp)
+        m = np.flatnonzero(g['group'] == gi)
+        dev_imgs = torch.as_tensor(imgs[g['img'][m]], device='cuda')
+        out = shaping.reward_terms(dev_imgs, torch.as_tensor(g['xy'][m], device='cuda'), torch.as_tensor(g['prev'][m], device='cuda'))
+        got = {k: v.cpu().numpy() for k, v in out.items()}
+        _assert_same(got, {k: g[k][m] for k in OUT_KEYS}, 'g16 group %s (%d x %d, %d cases)' % ((grp,) + imgs.shape[1:] + (m.size,)))
+        assert m.size > 500
+    # other options than SAL's: a wider neighbourhood, another scale / origin / clip / weights, against the checker
+    imgs = sc.unpack_images(g, 'b')
+    m = np.flatnonzero(g['group'] == 1)[:1500]
+    cfg = sc.config(rows=75, cols=100, neighborhood=3, clip_max=99, scale=2.5, origin_x=50.0, origin_y=37.0, max_lane_halfwidth=20.0,
+                    w_collision=-7.0, w_progress=3.0, w_centering=0.5)
+    out = shaping.reward_terms(torch.as_tensor(imgs[g['img'][m]], device='cuda'), torch.as_tensor(g['xy'][m], device='cuda'),
+                               torch.as_tensor(g['prev'][m], device='cuda'), **{k: v for k, v in cfg.items() if k != 'agent'})
+    want = [sc.reward_terms(imgs[g['img'][i]], g['xy'][i, 0], g['xy'][i, 1], g['prev'][i, 0], g['prev'][i, 1], cfg) for i in m]
+    _assert_same({k: v.cpu().numpy() for k, v in out.items()}, {k: np.array([w[k] for w in want]) for k in OUT_KEYS}, 'other options')
+    assert 0.02 < np.mean([w['collided'] for w in want]) < 0.98
+
+
+def test_closed_loop_equals_checker_through_resets(assets):
+    """256 envs with lidar noise, planner actions (a quarter of the envs spawned across the track and driven straight at
+    the wall), 200 steps with autoreset and a masked reset of half the envs: each step's outputs `==` the checker fed the
+    previous step's info['lidar_bitmap'] and the poses copied to the host."""
+    import torch
+    from red_gym_amd import workload
+    B = 256
+    env = _env(assets, B, autoreset=True)
+    assert env.eng._noise_on
+    wp = _waypoints(env)
+    env.shape_rewards()
+    ck = sc.ShapingChecker(B, env.timestep)
+    spawn = workload.spawn_poses(B, 1)
+    crash = np.arange(B) % 4 == 1
+    spawn[crash, 0, 2] += np.pi / 2
+    crash_dev = torch.as_tensor(crash, device=env.device)
+    _, reward, _, info = env.reset(spawn)
+    prev_img = np.zeros((B, 256, 256), np.uint8)
+
+    def check(reward, info, what):
+        nonlocal prev_img
+        got = _outputs(reward, info)
+        xy = env.state[:, 0, :2].cpu().numpy()
+        clock = info['current_time'].cpu().numpy()
+        want = ck.update(prev_img, xy, clock)
+        _assert_same(got, want, what)
+        assert np.array_equal(env.eng.s['prev_xy'].cpu().numpy(), ck.prev_xy)
+        prev_img = info['lidar_bitmap'].cpu().numpy().copy()
+        return got, clock
+    got, _ = check(reward, info, 'reset')
+    assert all((got[k] == 0).all() for k in OUT_KEYS) and reward.shape == (B,) and info['lidar_bitmap'].shape == (B, 256, 256)
+    assert prev_img.max() == 255 and set(np.unique(prev_img)) == {0, 255}
+    resets = 0
+    clock = info['current_time'].cpu().numpy()
+    for k in range(200):
+        if k == 100:
+            mask = (np.arange(B) % 2 == 0).astype(np.uint8)
+            before, clock_before = got, clock
+            _, reward, _, info = env.reset(spawn, torch.as_tensor(mask))
+            got, clock = check(reward, info, 'masked reset')
+            hit = mask.astype(bool)
+            assert (clock[hit] == env.timestep).all() and all((got[key][hit] == 0).all() for key in OUT_KEYS)
+            # left alone: outside the mask with its clock standing still (the call also performs a pending autoreset)
+            alone = ~hit & (clock == clock_before)
+            print('masked reset: %d envs reset by the mask, %d left alone, %d others reset as pending'
+                  % (hit.sum(), alone.sum(), (~hit & ~alone).sum()))
+            assert alone.any() and (clock[~hit & ~alone] == env.timestep).all()    # outside the mask: stood still, or its pending reset
+            for key in OUT_KEYS:                                   # the envs left alone keep every value bit for bit
+                assert np.array_equal(got[key][alone], before[key][alone], equal_nan=True), key
+            continue
+        acts = env.pure_pursuit(wp, TLAD, VGAIN)
+        acts[:, 0, 0] = torch.where(crash_dev, 0.0, acts[:, 0, 0])
+        acts[:, 0, 1] = torch.where(crash_dev, 8.0, acts[:, 0, 1])
+        _, reward, _, info = env.step(acts)
+        got, clock = check(reward, info, 'step %d' % k)
+        resets += int((clock == env.timestep).sum())
+    print('autoresets:', resets)
+    assert resets > 0, 'no autoreset happened'
+    assert (got['progress_term'] > 0).any() and np.isfinite(got['total']).all()
+    assert env.eng.device_errors() == 0
+    env.close()
+
+
+def _run(env, stepper, pool, sd, lo, hi):
+    import torch
+    env.load_state_dict(sd)
+    outs = []
+    for k in range(lo, hi):
+        _, reward, _, info = stepper(pool[k])
+        o = {key: info[key].clone() for key in ('reward_collision', 'reward_progress', 'reward_centering', 'bitmap_collided')}
+        o['total'], o['bitmap_sum'] = reward.clone(), info['lidar_bitmap'].sum(dtype=torch.int64)
+        if 'progress' in info:
+            o['progress'] = info['progress'].clone()
+        outs.append(o)
+    torch.cuda.synchronize()
+    return outs
+
+
+def _equal_runs(a, b, what):
+    import torch
+    for k, (x, y) in enumerate(zip(a, b)):
+        for key in x:
+            assert torch.equal(torch.nan_to_num(x[key].double(), nan=-12345.0), torch.nan_to_num(y[key].double(), nan=-12345.0)), (what, k, key)
+
+
+@pytest.mark.parametrize('tracking', [False, True])
+def test_graphs_and_checkpoint_equal_eager(assets, tracking):
+    """capture_step + step_graph and build_step_graph + step_lib_graph `==` the eager step for 20 steps (also with the
+    progress tracker on at once); a state_dict round trip resumes `==` the uninterrupted run."""
+    from red_gym_amd import workload
+    B, A = 64, 2
+    env = _env(assets, B, A, autoreset=True)
+    if tracking:
+        env.track_progress(_waypoints(env))
+    env.shape_rewards()
+    env.reset(workload.spawn_poses(B, A))
+    pool = workload.action_pool(34, B, A)
+    for k in range(4):
+        env.step(pool[k])
+    sd = env.state_dict()
+    assert {'prev_xy', 't_seen', 'lidar_bitmap'} <= set(sd)
+    eager = _run(env, env.step, pool, sd, 4, 24)
+    env.capture_step()
+    _equal_runs(eager, _run(env, env.step_graph, pool, sd, 4, 24), 'step_graph')
+    env.build_step_graph()
+    _equal_runs(eager, _run(env, env.step_lib_graph, pool, sd, 4, 24), 'step_lib_graph')
+    # checkpoint in the middle of a run: 10 steps, save, 10 more; restore and repeat the last 10
+    first = _run(env, env.step, pool, sd, 4, 14)
+    mid = env.state_dict()
+    rest = _run(env, env.step, pool, mid, 14, 24)
+    _equal_runs(eager, first + rest, 'uninterrupted')
+    _equal_runs(rest, _run(env, env.step, pool, mid, 14, 24), 'resumed')
+    assert float(eager[-1]['reward_progress'].max()) > 0.0
+    # a checkpoint taken without the shaper's state restarts it: no progress is paid by the first update
+    plain = {k: v for k, v in mid.items() if k not in ('prev_xy', 't_seen', 'lidar_bitmap')}
+    o = _run(env, env.step, pool, plain, 14, 15)[0]
+    assert float(o['reward_progress'].abs().max()) == 0.0
+    assert env.eng.device_errors() == 0
+    env.close()
+
+
+def test_the_step_itself_is_unchanged_and_switching_off_removes_everything(assets):
+    import torch
+    from red_gym_amd import workload
+    B, A = 32, 2
+    pool = workload.action_pool(12, B, A)
+    runs = []
+    for on in (False, True):
+        env = _env(assets, B, A, autoreset=True)
+        if on:
+            env.shape_rewards()
+        res = [env.reset(workload.spawn_poses(B, A))] + [env.step(pool[k]) for k in range(12)]
+        obs, reward, done, info = res[-1]
+        torch.cuda.synchronize()
+        snap = {'done': done.clone(), **{'obs_' + k: v.clone() for k, v in obs.items() if torch.is_tensor(v)},
+                **{'info_' + k: v.clone() for k, v in info.items() if torch.is_tensor(v)}}
+        runs.append((snap, set(info), set(env.state_dict())))
+        if on:
+            assert reward is not env._reward and reward.shape == (B,)
+            env.shape_rewards(False)
+            obs, reward, done, info = env.step(pool[0])
+            assert set(info) == runs[0][1] and set(env.state_dict()) == runs[0][2]
+            assert reward is env._reward and torch.equal(reward, torch.full((B,), env.timestep, dtype=torch.float64, device=env.device))
+            with pytest.raises(ValueError):
+                env.eng.shaping_update()                            # F110_E_INVALID: no shaper
+        else:
+            assert reward is env._reward
+        assert env.eng.device_errors() == 0
+        env.close()
+    (off, keys_off, sd_off), (on_, keys_on, sd_on) = runs
+    assert keys_on - keys_off == {'reward_collision', 'reward_progress', 'reward_centering', 'bitmap_collided', 'lidar_bitmap'}
+    assert sd_on - sd_off == {'prev_xy', 't_seen', 'lidar_bitmap'}
+    for k in off:
+        assert torch.equal(off[k], on_[k]), k
+
+
+def test_pose_that_is_not_finite(assets):
+    """x or y NaN / inf: the four terms are NaN, collided is 0, prev_xy stays; the other envs are paid normally."""
+    import torch
+    from red_gym_amd import workload
+    B = 64
+    env = _env(assets, B, autoreset=False)
+    env.shape_rewards()
+    env.reset(workload.spawn_poses(B, 1))
+    env.step(torch.zeros((B, 1, 2), dtype=torch.float64, device=env.device))
+    prev = env.eng.s['prev_xy'].clone()
+    env.state[0::4, 0, 0] = float('nan')
+    env.state[1::4, 0, 1] = float('inf')
+    env.eng.t['current_time'] += 1.0                               # "stepped": the clocks moved
+    env.eng.shaping_update()
+    torch.cuda.synchronize()
+    s = env.eng.s
+    bad = (torch.arange(B, device=env.device) % 4) < 2
+    for k in ('collision_term', 'progress_term', 'centering_term', 'total'):
+        assert torch.isnan(s[k][bad]).all() and torch.isfinite(s[k][~bad]).all(), k
+    assert (s['collided'][bad] == 0).all() and torch.equal(s['prev_xy'][bad], prev[bad])
+    assert torch.equal(s['prev_xy'][~bad], env.state[~bad, 0, :2])
+    assert env.eng.device_errors() == 0
+    env.close()
