@@ -1,0 +1,51 @@
+"""What the step's consumers share.  A consumer is a kernel enqueued behind every step that adds keys to `info`: the progress
+tracker (progress.py) and the reward shaper (shaping.py).  The Engine owns one object of each; F110VecEnv loops over the pair."""
+import ctypes as C
+import weakref
+
+import torch
+
+from . import _lib
+
+
+class Consumer(object):
+    """Nothing is allocated before the first install().  A subclass names its entry points (NAME: f110_<NAME>_bind / _update)
+    and gives INFO (`info` key -> buffer name), STATE (state_dict key -> buffer name), install(), remove() and restart().
+    `buf` holds its tensors by name, `info` the views that join the step's `info` while it is `on`."""
+    reward = None   # the reward [B] the consumer pays (None: the env's constant stays)
+
+    def __init__(self, eng):
+        self.eng = weakref.proxy(eng)   # (the Engine owns this object: a strong reference would keep both alive until a GC cycle)
+        self.on, self.buf, self.info = False, None, {}
+        self._update = getattr(eng.lib, 'f110_%s_update' % self.NAME)
+
+    def _bind(self, buf, struct):
+        """The tensors `buf` become the buffers the kernel writes: one struct of pointers, handed to the library once."""
+        ptrs = struct()
+        for name, _ in struct._fields_:
+            setattr(ptrs, name, buf[name].data_ptr())
+        torch.cuda.synchronize(self.eng.device)
+        _lib.check(getattr(self.eng.lib, 'f110_%s_bind' % self.NAME)(self.eng._h, C.byref(ptrs)))
+        self.buf, self.info = buf, {k: buf[name] for k, name in self.INFO.items()}
+
+    def kernel(self):
+        """Enqueues the consumer's kernel on the current stream for the state as the last step left it (no allocation, no
+        synchronisation -- it can be captured behind step()).  ValueError from the library while nothing is installed."""
+        with torch.cuda.device(self.eng.device):
+            _lib.check(self._update(self.eng._h, self.eng._stream()))
+
+    update = kernel   # what follows every step
+
+    def state(self):
+        return {k: self.buf[name].clone() for k, name in self.STATE.items()}
+
+    def load(self, sd):
+        """Restores state() from a checkpoint that holds this consumer's keys with fitting shapes; any other restarts it."""
+        if all(k in sd and sd[k].shape == self.buf[name].shape for k, name in self.STATE.items()):
+            for k, name in self.STATE.items():
+                self.buf[name].copy_(sd[k])
+        else:
+            self.restart()
+
+    def close(self):
+        pass

@@ -117,17 +117,13 @@ extern "C" int f110_pure_pursuit_prepare(f110_handle *h, const double *waypoints
     std::vector<uint8_t> count;
     std::vector<uint16_t> cand;
     if (int rc = build_plan_grid("f110_pure_pursuit_prepare", wp.data(), 3, M, cell, margin, g, count, cand)) return rc;
-    const size_t cells = (size_t)g.gw * g.gh;
     ON_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize()); // an enqueued plan may still read the previous grid
     h->epoch++; // a captured launch of the grid kernel takes the grid's pointers by value: they are freed below
-    DevBuf<uint8_t> d_count;
-    DevBuf<uint16_t> d_cand;
-    HIP_TRY(d_count.upload(count.data(), cells));
-    HIP_TRY(d_cand.upload(cand.data(), cells * PG_CAP));
-    h->d_plan_count = std::move(d_count); h->d_plan_cand = std::move(d_cand);
-    g.count = h->d_plan_count.get(); g.cand = h->d_plan_cand.get();
-    h->plan_grid = g; h->plan_wp = waypoints; h->plan_M = M; h->plan_ok = true;
+    PlanGridDev n;
+    HIP_TRY(n.upload(g, count, cand));
+    h->plan = std::move(n);
+    h->plan_wp = waypoints; h->plan_M = M; h->plan_ok = true;
     return F110_OK;
 }
 
@@ -141,12 +137,12 @@ extern "C" int f110_pure_pursuit(f110_handle *h, const double *waypoints, int32_
     if (h) if (int rc = check_device(h, "f110_pure_pursuit")) return rc;
     if (!waypoints || !state || !actions) return fail(F110_E_INVALID, "f110_pure_pursuit: null pointer");
     if (M < 2) return fail(F110_E_INVALID, "f110_pure_pursuit: M=%d waypoints (a raceline has at least 2)", M);
+    PlanArgs a;
+    a.waypoints = waypoints; a.M = M; a.lookahead = lookahead; a.vgain = vgain; a.wheelbase = wheelbase;
+    a.max_reacquire = max_reacquire; a.state = state; a.n = n; a.actions = actions;
     if (h && h->plan_ok && h->plan_wp == waypoints && h->plan_M == M) {
         // a prepared raceline: one lane per car over the grid's candidate lists
-        PlanArgs a;
-        a.waypoints = waypoints; a.M = M; a.lookahead = lookahead; a.vgain = vgain; a.wheelbase = wheelbase;
-        a.max_reacquire = max_reacquire; a.state = state; a.n = n; a.actions = actions;
-        hipLaunchKernelGGL(pure_pursuit_grid_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, h->plan_grid);
+        hipLaunchKernelGGL(pure_pursuit_grid_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, h->plan.g);
         HIP_TRY(hipGetLastError());
         return F110_OK;
     }
@@ -170,9 +166,6 @@ extern "C" int f110_pure_pursuit(f110_handle *h, const double *waypoints, int32_
         HIP_TRY(hipGetLastError());
         return F110_OK;
     }
-    PlanArgs a;
-    a.waypoints = waypoints; a.M = M; a.lookahead = lookahead; a.vgain = vgain; a.wheelbase = wheelbase;
-    a.max_reacquire = max_reacquire; a.state = state; a.n = n; a.actions = actions;
     if (smem > 64 * 1024 && smem > dl.pp_attr) { // raised once per device and size, not on every call (nor inside a captured policy)
         HIP_TRY(hipFuncSetAttribute((const void *)pure_pursuit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         device_lds(dev).pp_attr = smem;
@@ -218,6 +211,23 @@ extern "C" int f110_pure_pursuit_tracks(f110_handle *h, const double *waypoints,
     hipLaunchKernelGGL(pure_pursuit_tracks_kernel, dim3((n + PPG_WAVES - 1) / PPG_WAVES), dim3(PPG_WAVES * 64), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return F110_OK;
+}
+
+// ---------------------------------------------------------------- what the tracker and the shaper share
+// Both read an env's reset off its clock (current_time == timestep): their installs refuse a handle whose clock cannot tell.
+static int clock_usable(const f110_handle *h, const char *who)
+{
+    return h->cfg.timestep > 0.0 ? F110_OK : fail(F110_E_INVALID, "%s: the handle's timestep is %g (an env's reset is read off its clock: it must be positive)", who, h->cfg.timestep);
+}
+
+// The opening of f110_progress_update / f110_shaping_update (`who`): `what` is installed and bound (f110_<family>_install /
+// _bind), the handle is bound and its device is the caller's current one.
+static int update_ready(const f110_handle *h, const char *who, const char *what, const char *family, bool on, bool bound)
+{
+    if (!on) return fail(F110_E_INVALID, "%s: no %s is installed (f110_%s_install)", who, what, family);
+    if (!bound) return fail(F110_E_UNBOUND, "%s: f110_%s_bind has not been called", who, family);
+    if (!h->bound) return fail(F110_E_UNBOUND, "%s: f110_bind has not been called", who);
+    return check_device(h, who);
 }
 
 // ---------------------------------------------------------------- progress along the raceline
@@ -274,14 +284,15 @@ extern "C" int f110_progress_install(f110_handle *h, const double *waypoints, co
         return F110_OK;
     }
     if (int rc = f110_progress_validate(waypoints, offsets, K, len, cum, psi, lap_length, raceline_of_env, h->cfg.num_envs)) return rc;
-    if (!(h->cfg.timestep > 0.0)) return fail(F110_E_INVALID, "f110_progress_install: the handle's timestep is %g (an env's reset is read off its clock: it must be positive)", h->cfg.timestep);
+    if (int rc = clock_usable(h, "f110_progress_install")) return rc;
     const size_t total = (size_t)offsets[K];
     f110_handle::Progress n;
     n.K = K;
     // one raceline: the planner's grid of candidate lists (a raceline it cannot hold is searched segment by segment: same results)
+    PlanGrid g;
     std::vector<uint8_t> count;
     std::vector<uint16_t> cand;
-    if (grid && K == 1 && total <= 65535 && build_plan_grid("f110_progress_install", waypoints, 2, (int)total, 0.25, 3.0, n.grid, count, cand) == F110_OK)
+    if (grid && K == 1 && total <= 65535 && build_plan_grid("f110_progress_install", waypoints, 2, (int)total, 0.25, 3.0, g, count, cand) == F110_OK)
         n.use_grid = true;
     ON_DEVICE(h->cfg.device);
     HIP_TRY(n.d_xy.upload(waypoints, total * 2));
@@ -291,11 +302,7 @@ extern "C" int f110_progress_install(f110_handle *h, const double *waypoints, co
     HIP_TRY(n.d_lap.upload(lap_length, (size_t)K));
     HIP_TRY(n.d_offsets.upload(offsets, (size_t)K + 1));
     if (raceline_of_env) HIP_TRY(n.d_env.upload(raceline_of_env, (size_t)h->cfg.num_envs));
-    if (n.use_grid) {
-        HIP_TRY(n.d_count.upload(count.data(), count.size()));
-        HIP_TRY(n.d_cand.upload(cand.data(), cand.size()));
-        n.grid.count = n.d_count.get(); n.grid.cand = n.d_cand.get();
-    }
+    if (n.use_grid) HIP_TRY(n.grid.upload(g, count, cand));
     HIP_TRY(hipDeviceSynchronize()); // an enqueued update may still read the tables that are replaced
     n.bufs = p.bufs; n.bound = p.bound; n.on = true;
     p = std::move(n);
@@ -318,15 +325,12 @@ extern "C" int f110_progress_update(f110_handle *h, void *stream)
 {
     if (!h) return fail(F110_E_INVALID, "f110_progress_update: null handle");
     const f110_handle::Progress &p = h->progress;
-    if (!p.on) return fail(F110_E_INVALID, "f110_progress_update: no tracker is installed (f110_progress_install)");
-    if (!p.bound) return fail(F110_E_UNBOUND, "f110_progress_update: f110_progress_bind has not been called");
-    if (!h->bound) return fail(F110_E_UNBOUND, "f110_progress_update: f110_bind has not been called");
-    if (int rc = check_device(h, "f110_progress_update")) return rc;
+    if (int rc = update_ready(h, "f110_progress_update", "tracker", "progress", p.on, p.bound)) return rc;
     ProgressArgs a;
     memset(&a, 0, sizeof(a));
     a.state = h->bufs.state; a.n = h->cfg.num_envs * h->cfg.num_agents; a.agents = h->cfg.num_agents;
     a.xy = p.d_xy.get(); a.len = p.d_len.get(); a.cum = p.d_cum.get(); a.psi = p.d_psi.get(); a.lap = p.d_lap.get();
-    a.offsets = p.d_offsets.get(); a.raceline_of_env = p.d_env.get(); a.K = p.K; a.use_grid = p.use_grid ? 1 : 0; a.g = p.grid;
+    a.offsets = p.d_offsets.get(); a.raceline_of_env = p.d_env.get(); a.K = p.K; a.use_grid = p.use_grid ? 1 : 0; a.g = p.grid.g;
     a.current_time = h->bufs.current_time; a.timestep = h->cfg.timestep;
     a.s = p.bufs.s; a.d = p.bufs.d; a.heading_error = p.bufs.heading_error; a.delta = p.bufs.delta; a.progress = p.bufs.progress;
     a.s_prev = p.bufs.s_prev; a.seg = p.bufs.seg; a.seen = p.bufs.seen; a.dev_err = h->d_err.get();
@@ -363,7 +367,7 @@ extern "C" int f110_shaping_install(f110_handle *h, const f110_shaping_config *c
         return F110_OK;
     }
     if (int rc = f110_shaping_validate(cfg, h->cfg.num_agents)) return rc;
-    if (!(h->cfg.timestep > 0.0)) return fail(F110_E_INVALID, "f110_shaping_install: the handle's timestep is %g (an env's reset is read off its clock: it must be positive)", h->cfg.timestep);
+    if (int rc = clock_usable(h, "f110_shaping_install")) return rc;
     s.cfg = *cfg; // by value in every launch: nothing on the device to replace
     s.on = true;
     h->epoch++;
@@ -393,10 +397,7 @@ extern "C" int f110_shaping_update(f110_handle *h, void *stream)
 {
     if (!h) return fail(F110_E_INVALID, "f110_shaping_update: null handle");
     const f110_handle::Shaping &s = h->shaping;
-    if (!s.on) return fail(F110_E_INVALID, "f110_shaping_update: no shaper is installed (f110_shaping_install)");
-    if (!s.bound) return fail(F110_E_UNBOUND, "f110_shaping_update: f110_shaping_bind has not been called");
-    if (!h->bound) return fail(F110_E_UNBOUND, "f110_shaping_update: f110_bind has not been called");
-    if (int rc = check_device(h, "f110_shaping_update")) return rc;
+    if (int rc = update_ready(h, "f110_shaping_update", "shaper", "shaping", s.on, s.bound)) return rc;
     ShapingArgs a;
     memset(&a, 0, sizeof(a));
     a.cfg = s.cfg; a.bitmap = s.bufs.bitmap; a.n = h->cfg.num_envs;

@@ -107,6 +107,21 @@ using Stream = HipOwner<hipStream_t, hipStreamDestroy>;
 using Graph = HipOwner<hipGraph_t, hipGraphDestroy>;
 using GraphExec = HipOwner<hipGraphExec_t, hipGraphExecDestroy>;
 
+// A raceline's grid of candidate lists on the device (f110_planner.h PlanGrid; built on the host by build_plan_grid,
+// f110_consumers.hip): the geometry, whose count / cand point into the two tables it owns.  The planner's prepared raceline
+// and the progress tracker each hold one.
+struct PlanGridDev {
+    PlanGrid g;
+    DevBuf<uint8_t> d_count; DevBuf<uint16_t> d_cand;
+    hipError_t upload(const PlanGrid &geometry, const std::vector<uint8_t> &count, const std::vector<uint16_t> &cand)
+    {
+        hipError_t e = d_count.upload(count.data(), count.size());
+        if (e == hipSuccess) e = d_cand.upload(cand.data(), cand.size());
+        g = geometry; g.count = d_count.get(); g.cand = d_cand.get();
+        return e;
+    }
+};
+
 // Where the scan finds a car's noise row: row r of the car's slot is base[(slot * cap + (r & mask)) * num_beams], slot =
 // env_slot[env] (NULL: slot 0).  ScanArgs and the device-resident NoiseDesc both take it from NoiseState::where.
 struct NoiseRows {
@@ -185,10 +200,9 @@ struct f110_handle {
     std::vector<double> h_sines, h_cosines;
     double side_max = 0.0;            // largest finite side distance (the scan's pre-test for iTTC candidates)
     NoiseState noise;
-    // prepared raceline of f110_pure_pursuit (f110_pure_pursuit_prepare): grid of candidate lists (f110_planner.h PlanGrid)
+    // prepared raceline of f110_pure_pursuit (f110_pure_pursuit_prepare) and its grid of candidate lists
     const double *plan_wp = nullptr; int plan_M = 0; bool plan_ok = false;
-    PlanGrid plan_grid;
-    DevBuf<uint8_t> d_plan_count; DevBuf<uint16_t> d_plan_cand;
+    PlanGridDev plan;
     // progress tracker (f110_progress_install / _bind / _update, f110_consumers.hip): its own device copy of the racelines and
     // their host-built tables, the grid of candidate lists of a single raceline, and the caller's output buffers
     struct Progress {
@@ -196,8 +210,7 @@ struct f110_handle {
         int K = 0;
         DevBuf<double> d_xy, d_len, d_cum, d_psi, d_lap;
         DevBuf<int32_t> d_offsets, d_env;   // d_env: [B] raceline of every env (empty: all on raceline 0)
-        PlanGrid grid;
-        DevBuf<uint8_t> d_count; DevBuf<uint16_t> d_cand;
+        PlanGridDev grid;
         f110_progress_buffers bufs;
     } progress;
     // reward shaper (f110_shaping_install / _bind / _update, f110_consumers.hip): the configuration and the caller's buffers

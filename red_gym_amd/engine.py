@@ -10,6 +10,8 @@ import torch
 from . import _lib
 from .base_classes import integrator_code
 from .maps import load_map
+from .progress import ProgressTracker
+from .shaping import RewardShaper
 
 # f110_env.py:128
 DEFAULT_PARAMS = {'mu': 1.0489, 'C_Sf': 4.718, 'C_Sr': 5.4562, 'lf': 0.15875, 'lr': 0.17145, 'h': 0.074,
@@ -133,6 +135,8 @@ class Engine(object):
         self.side_distances_mode = side_distances
         self.env_params_assign, self._side_slots = None, None   # params slot of every env; [slots, num_beams] while installed
         self.lib = _lib.load()
+        # the step's consumers (consumer.py), in the order their kernels follow a step; nothing is allocated until an install
+        self.tracker, self.shaper = ProgressTracker(self), RewardShaper(self)
         env_params = None
         if params is not None and not isinstance(params, dict):
             env_params = [dict(p) for p in params]
@@ -182,8 +186,6 @@ class Engine(object):
         self.scan_reorder = True  # keep the scan's launch order sorted by noise row (Engine._reorder_scan); False: car order
         self._reorder_count, self._scan_order, self.env_noise_assign = 0, None, None
         self.noise_tables = []
-        self.p, self.progress_lines, self.lap_length = None, None, None   # progress tracker (set_progress)
-        self.s, self.shaping_cfg = None, None                             # reward shaper (set_shaping)
         if env_params is not None:
             self.set_env_params(env_params)
         if self._noise_on:
@@ -422,7 +424,6 @@ class Engine(object):
         """Map from an occupancy mask (nonzero = free, row 0 = bottom row, as after laser_models.py:399-404).
         A CUDA uint8 tensor stays on the device: EDT, cell codes, LUT and the fp64 table are built there (~1 ms),
         so a generated track can be installed every episode."""
-        import torch
         oc, os_ = float(np.cos(orig_theta)), float(np.sin(orig_theta))
         if torch.is_tensor(free) and free.is_cuda:
             f = free.to(device=self.device, dtype=torch.uint8).contiguous()
@@ -712,89 +713,6 @@ class Engine(object):
         self._keep_tracks = (tracks, track_of_car)
         return out.view(self.B, self.A, 2) if state is None else out
 
-    # ------------------------------------------------------------------ progress along the raceline
-    _PROGRESS_DTYPES = {'s': torch.float64, 'd': torch.float64, 'heading_error': torch.float64, 'delta': torch.float64,
-                        'progress': torch.float64, 's_prev': torch.float64, 'seg': torch.int32, 'seen': torch.uint8}
-
-    def set_progress(self, racelines, raceline_of_env=None, grid=True):
-        """Installs the progress tracker (f110_progress_install): `racelines` one [M, >= 2] array (columns 0, 1 = x, y) or a
-        sequence of K of them, `raceline_of_env` int array [num_envs] (None: every env on raceline 0); None removes it.
-        The tables are computed here with NumPy (red_gym_amd.progress) and the handle keeps its own device copy of
-        everything.  The outputs live in self.p (tensors [B, A]: s, d, heading_error, delta, progress, s_prev, seg, seen);
-        an install starts every car anew (seen = 0).  grid=False searches every segment even for a single raceline (the
-        results are the same).  ValueError for what the library refuses: a zero-length segment, fewer than 2 points,
-        non-finite coordinates, a raceline index outside 0..K-1."""
-        from .progress import PackedRacelines
-        if racelines is None:
-            _lib.check(self.lib.f110_progress_install(self._h, None, None, 0, None, None, None, None, None, 0))
-            self.progress_lines, self.lap_length = None, None
-            return
-        if torch.is_tensor(racelines) or (isinstance(racelines, np.ndarray) and racelines.ndim == 2):
-            racelines = [racelines]
-        pk = PackedRacelines(racelines)
-        assign = None
-        if raceline_of_env is not None:
-            assign = np.ascontiguousarray(raceline_of_env, dtype=np.int32)
-            if assign.shape != (self.B,):
-                raise ValueError('raceline_of_env must have one entry per env (%d), got shape %s' % (self.B, assign.shape))
-        _lib.check(self.lib.f110_progress_install(self._h, _np_ptr(pk.xy), _np_ptr(pk.offsets), pk.K, _np_ptr(pk.len),
-                                                  _np_ptr(pk.cum), _np_ptr(pk.psi), _np_ptr(pk.lap_length),
-                                                  _np_ptr(assign) if assign is not None else None, int(bool(grid))))
-        if getattr(self, 'p', None) is None:
-            self.p = {k: torch.zeros((self.B, self.A), dtype=dt, device=self.device) for k, dt in self._PROGRESS_DTYPES.items()}
-            bufs = _lib.ProgressBuffers()
-            for name in _lib.PROGRESS_FIELDS:
-                setattr(bufs, name, self.p[name].data_ptr())
-            torch.cuda.synchronize(self.device)
-            _lib.check(self.lib.f110_progress_bind(self._h, C.byref(bufs)))
-        else:
-            self.p['seen'].zero_()
-        self.progress_lines = pk
-        lap = pk.lap_length[assign] if assign is not None else np.full(self.B, pk.lap_length[0])
-        self.lap_length = torch.as_tensor(lap, device=self.device)
-
-    @on_own_device
-    def progress_update(self):
-        """Enqueues the tracker's kernel on the current stream for the state as the last step left it (f110_progress_update:
-        no allocation, no synchronisation -- it can be captured behind step())."""
-        _lib.check(self.lib.f110_progress_update(self._h, self._stream()))
-
-    # ------------------------------------------------------------------ reward shaping
-    _SHAPING_DTYPES = {'collision_term': torch.float64, 'progress_term': torch.float64, 'centering_term': torch.float64,
-                       'total': torch.float64, 'collided': torch.uint8, 't_seen': torch.float64}
-
-    def set_shaping(self, cfg):
-        """Installs the reward shaper (f110_shaping_install): `cfg` a dict of red_gym_amd.shaping.DEFAULTS' keys (missing ones
-        take SAL's numbers), or None to remove it.  The buffers live in self.s: bitmap [B, rows, cols] uint8 (the caller
-        renders every step's scan into it AFTER shaping_update), collision_term, progress_term, centering_term, total [B]
-        fp64, collided [B] uint8 and the state prev_xy [B, 2], t_seen [B].  An install starts the shaper anew (t_seen = -1:
-        the first update takes its previous position from its own pose).  ValueError for what the library refuses."""
-        from .shaping import make_config
-        if cfg is None:
-            _lib.check(self.lib.f110_shaping_install(self._h, None))
-            self.shaping_cfg = None
-            return
-        c = make_config(**cfg)
-        _lib.check(self.lib.f110_shaping_install(self._h, C.byref(c)))
-        with torch.cuda.device(self.device):
-            if self.s is None or tuple(self.s['bitmap'].shape[1:]) != (c.rows, c.cols):
-                self.s = {k: torch.zeros((self.B,), dtype=dt, device=self.device) for k, dt in self._SHAPING_DTYPES.items()}
-                self.s['prev_xy'] = torch.zeros((self.B, 2), dtype=torch.float64, device=self.device)
-                self.s['bitmap'] = torch.zeros((self.B, c.rows, c.cols), dtype=torch.uint8, device=self.device)
-                bufs = _lib.ShapingBuffers()
-                for name in _lib.SHAPING_FIELDS:
-                    setattr(bufs, name, self.s[name].data_ptr())
-                torch.cuda.synchronize(self.device)
-                _lib.check(self.lib.f110_shaping_bind(self._h, C.byref(bufs)))
-            self.s['t_seen'].fill_(-1.0)
-        self.shaping_cfg = c
-
-    @on_own_device
-    def shaping_update(self):
-        """Enqueues the shaper's kernel on the current stream: the rewards of the step just made, from self.s['bitmap'] as the
-        previous step left it (f110_shaping_update: no allocation, no synchronisation -- capturable behind step())."""
-        _lib.check(self.lib.f110_shaping_update(self._h, self._stream()))
-
     @on_own_device
     def pack_env(self, env=0):
         """Env `env`'s observation as ONE pinned host fp64 row (f110_pack_env + one device -> host copy + a stream
@@ -832,6 +750,8 @@ class Engine(object):
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:
+            self.tracker.close()
+            self.shaper.close()
             torch.cuda.synchronize(self.device)
             flags = self.device_errors() if os.environ.get('F110_CHECK_DEVICE_ERRORS') == '1' else 0
             self.lib.f110_destroy(self._h)

@@ -1,8 +1,14 @@
 """Host side of the progress tracker (csrc/f110_progress.h): the per-raceline tables the kernel looks up.
 
 They are computed here with NumPy and uploaded (tables come from the host), so the device never takes
-the sqrt of a segment or an atan2 and the tests can demand `==` of a NumPy checker for every output."""
+the sqrt of a segment or an atan2 and the tests can demand `==` of a NumPy checker for every output.  ProgressTracker is the Engine's side of it."""
+import ctypes as C
+
 import numpy as np
+import torch
+
+from . import _lib
+from .consumer import Consumer
 
 
 def raceline_xy(raceline):
@@ -52,3 +58,52 @@ class PackedRacelines(object):
             o, m = int(self.offsets[k]), a.shape[0]
             self.len[o:o + m - 1], self.cum[o:o + m], self.psi[o:o + m - 1] = length, cum, psi
             self.lap_length[k] = L
+
+
+class ProgressTracker(Consumer):
+    """The progress tracker of one Engine (f110_progress_install / _bind / _update).  The outputs live in `buf` (tensors [B, A]:
+    s, d, heading_error, delta, progress, s_prev, seg, seen), allocated and bound by the first install and kept from then on;
+    `lap_length` is the tensor [B] of every env's lap length."""
+    NAME = 'progress'
+    INFO = {'frenet_s': 's', 'frenet_d': 'd', 'heading_error': 'heading_error', 'progress': 'progress', 'progress_delta': 'delta'}
+    STATE = {'progress': 'progress', 's_prev': 's_prev', 'seen': 'seen'}
+    DTYPES = {'s': torch.float64, 'd': torch.float64, 'heading_error': torch.float64, 'delta': torch.float64,
+              'progress': torch.float64, 's_prev': torch.float64, 'seg': torch.int32, 'seen': torch.uint8}
+    lap_length = None
+
+    def install(self, racelines, raceline_of_env=None, grid=True):
+        """`racelines` one [M, >= 2] array (columns 0, 1 = x, y) or a sequence of K of them, `raceline_of_env` int array
+        [num_envs] (None: every env on raceline 0).  The tables are computed here with NumPy and the handle keeps its own
+        device copy of everything; an install starts every car anew.  grid=False searches every segment even for a single
+        raceline (the results are the same).  ValueError for what the library refuses: a zero-length segment, fewer than 2
+        points, non-finite coordinates, a raceline index outside 0..K-1."""
+        eng = self.eng
+        if torch.is_tensor(racelines) or (isinstance(racelines, np.ndarray) and racelines.ndim == 2):
+            racelines = [racelines]
+        pk = PackedRacelines(racelines)
+        assign = None
+        if raceline_of_env is not None:
+            assign = np.ascontiguousarray(raceline_of_env, dtype=np.int32)
+            if assign.shape != (eng.B,):
+                raise ValueError('raceline_of_env must have one entry per env (%d), got shape %s' % (eng.B, assign.shape))
+        xy, offsets, *tables = [a.ctypes.data_as(C.c_void_p) if a is not None else None
+                                for a in (pk.xy, pk.offsets, pk.len, pk.cum, pk.psi, pk.lap_length, assign)]
+        _lib.check(eng.lib.f110_progress_install(eng._h, xy, offsets, pk.K, *tables, int(bool(grid))))
+        if self.buf is None:
+            self._bind({k: torch.zeros((eng.B, eng.A), dtype=dt, device=eng.device) for k, dt in self.DTYPES.items()},
+                       _lib.ProgressBuffers)
+        else:
+            self.restart()
+        lap = pk.lap_length[assign] if assign is not None else np.full(eng.B, pk.lap_length[0])
+        self.lap_length = self.info['lap_length'] = torch.as_tensor(lap, device=eng.device)
+        self.on = True
+
+    def remove(self):
+        """No launch, no info key, no state_dict key remains; the buffers stay for the next install."""
+        if self.on:
+            _lib.check(self.eng.lib.f110_progress_install(self.eng._h, None, None, 0, None, None, None, None, None, 0))
+        self.on = False
+
+    def restart(self):
+        """Every car's progress starts anew with the next update."""
+        self.buf['seen'].zero_()

@@ -70,36 +70,26 @@ class F110VecEnv(object):
             self._obs['scans_f64'] = t['scans_f64']
         self._reward = torch.full((self.num_envs,), float(timestep), dtype=torch.float64, device=self.device)
         self._g_actions, self._graphs, self._lg = None, [], None   # capture_step / build_step_graph
-        self._tracking = False                                      # track_progress
-        self._shaping, self._to_img = False, None                   # shape_rewards
+        self.consumers = (self.eng.tracker, self.eng.shaper)        # track_progress, shape_rewards: the ones that are `on` run
 
     def _result(self):
         t = self.eng.t
         done = t['done']  # bool tensor written by env_kernel (no per-step torch kernels here)
         info = {'checkpoint_done': t['checkpoint_done'], 'collision_idx': t['collision_idx'],
                 'current_time': t['current_time'], 'toggles': t['toggles']}
-        if self._tracking:
-            p = self.eng.p
-            info.update(frenet_s=p['s'], frenet_d=p['d'], heading_error=p['heading_error'], progress=p['progress'],
-                        progress_delta=p['delta'], lap_length=self.eng.lap_length)
-        if self._shaping:
-            sh = self.eng.s
-            info.update(reward_collision=sh['collision_term'], reward_progress=sh['progress_term'],
-                        reward_centering=sh['centering_term'], bitmap_collided=sh['collided'], lidar_bitmap=sh['bitmap'])
-            return self._obs, sh['total'], done, info
-        return self._obs, self._reward, done, info
+        reward = None
+        for c in self.consumers:
+            if c.on:
+                info.update(c.info)
+                if reward is None:
+                    reward = c.reward
+        return self._obs, self._reward if reward is None else reward, done, info
 
-    def _consumers(self):
-        """What follows every step on the same stream: the progress tracker, then the reward shaper -- its kernel reads the
-        bitmap buffer while it still holds the PREVIOUS step's image, then the new scan is rendered into the same buffer."""
-        if self._tracking:
-            self.eng.progress_update()
-        if self._shaping:
-            self.eng.shaping_update()
-            self._render_bitmap()
-
-    def _render_bitmap(self):
-        self._to_img(self._obs['scans'][:, self.eng.shaping_cfg.agent], out=self.eng.s['bitmap'])
+    def _after_step(self):
+        """What follows every step on the same stream: the progress tracker's update, then the reward shaper's."""
+        for c in self.consumers:
+            if c.on:
+                c.update()
 
     def _as_dev(self, a, last):
         if not torch.is_tensor(a):
@@ -120,13 +110,13 @@ class F110VecEnv(object):
         except ValueError:
             raise ValueError('Number of poses for reset does not match number of agents.')
         self.eng.reset(poses, mask)
-        self._consumers()
+        self._after_step()
         return self._result()
 
     def step(self, actions):
         """actions [B,A,2] = (steer, speed) per car (f110_env.py:261-302)."""
         self.eng.step(self._as_dev(actions, 2))
-        self._consumers()
+        self._after_step()
         return self._result()
 
     # ------------------------------------------------------------------ progress along the raceline
@@ -140,23 +130,22 @@ class F110VecEnv(object):
         no copies -- and lap_length [B].  A reset (masked, whole batch or autoreset) restarts the car's progress at 0 in the
         step that performs it.  None switches tracking off: no launch, no info key, no state_dict key remains."""
         if racelines is None:
-            if self._tracking:
-                self.eng.set_progress(None)
-            self._tracking = False
+            self.eng.tracker.remove()
             return
         if isinstance(racelines, (list, tuple)):
             if assign is None and len(racelines) > 1:
                 raise ValueError('a list of racelines needs assign [num_envs]')
             if assign is not None:
-                assign = np.asarray(assign)
-                if assign.shape != (self.num_envs,) or assign.min() < 0 or assign.max() >= len(racelines):
-                    raise ValueError('assign must hold one raceline index (0..%d) per env' % (len(racelines) - 1))
+                assign = self._raceline_of_env(assign, len(racelines))
         elif assign is not None:
             raise ValueError('assign goes with a list of racelines')
-        self.eng.set_progress(racelines, assign)
-        self._tracking = True
+        self.eng.tracker.install(racelines, assign)
 
-    _PROGRESS_KEYS = ('progress', 's_prev', 'seen')
+    def _raceline_of_env(self, assign, K):
+        assign = np.asarray(assign)
+        if assign.shape != (self.num_envs,) or assign.min() < 0 or assign.max() >= K:
+            raise ValueError('assign must hold one raceline index (0..%d) per env' % (K - 1))
+        return assign
 
     # ------------------------------------------------------------------ reward shaping
     def shape_rewards(self, enable=True, **cfg):
@@ -173,26 +162,10 @@ class F110VecEnv(object):
         shape_rewards(False) switches it off: no launch, no info key, no state_dict key remains and the reward is the
         constant again.  Switched on in the middle of a run, the first update pays no progress and reads the image of the
         scans as they stand."""
-        if not enable:
-            if self._shaping:
-                self.eng.set_shaping(None)
-            self._shaping = False
-            if self._to_img is not None:
-                self._to_img.close()
-                self._to_img = None
-            return
-        from .lidar import LidarBitmap
-        from .shaping import make_config
-        c = make_config(**cfg)
-        self.eng.set_shaping(cfg)
-        if self._to_img is not None:
-            self._to_img.close()
-        self._to_img = LidarBitmap(self.eng.num_beams, bg_color='black', draw_mode='FILL', output_image_dims=(c.rows, c.cols),
-                                   device=self.eng.device_index)
-        self._shaping = True
-        self._render_bitmap()
-
-    _SHAPING_KEYS = {'prev_xy': 'prev_xy', 't_seen': 't_seen', 'lidar_bitmap': 'bitmap'}   # state_dict key -> Engine.s key
+        if enable:
+            self.eng.shaper.install(**cfg)
+        else:
+            self.eng.shaper.remove()
 
     # ------------------------------------------------------------------ checkpoint / resume
     _STATE_KEYS = ('state', 'steer_buf', 'steer_cnt', 'noise_step', 'spawn', 'start_rot', 'near_start', 'toggles',
@@ -203,30 +176,20 @@ class F110VecEnv(object):
         """Everything a step depends on lives in the caller-owned tensors bound to the handle
         (f110_buffers): a copy of them is a complete checkpoint of all B envs."""
         sd = {k: self.eng.t[k].clone() for k in self._STATE_KEYS if self.eng.t[k] is not None}
-        if self._tracking:
-            sd.update({k: self.eng.p[k].clone() for k in self._PROGRESS_KEYS})
-        if self._shaping:
-            sd.update({k: self.eng.s[name].clone() for k, name in self._SHAPING_KEYS.items()})
+        for c in self.consumers:
+            if c.on:
+                sd.update(c.state())
         return sd
 
     def load_state_dict(self, sd):
         """While tracking is on the checkpoint's progress, s_prev and seen are restored with it; one taken without them
         starts every car's progress anew.  Likewise the shaper's prev_xy, t_seen and bitmap while shaping is on; without
         them the shaper restarts: the next update pays no progress and reads the image of the restored scans."""
-        self.eng.load_state({k: v for k, v in sd.items() if k not in self._PROGRESS_KEYS and k not in self._SHAPING_KEYS})
-        if self._tracking:
-            if all(k in sd for k in self._PROGRESS_KEYS):
-                for k in self._PROGRESS_KEYS:
-                    self.eng.p[k].copy_(sd[k])
-            else:
-                self.eng.p['seen'].zero_()
-        if self._shaping:
-            if all(k in sd and sd[k].shape == self.eng.s[name].shape for k, name in self._SHAPING_KEYS.items()):
-                for k, name in self._SHAPING_KEYS.items():
-                    self.eng.s[name].copy_(sd[k])
-            else:
-                self.eng.s['t_seen'].fill_(-1.0)
-                self._render_bitmap()
+        theirs = {k for c in self.consumers for k in c.STATE}
+        self.eng.load_state({k: v for k, v in sd.items() if k not in theirs})
+        for c in self.consumers:
+            if c.on:
+                c.load(sd)
 
     # ------------------------------------------------------------------ hipGraph replay
     def capture_step(self, policy=None, copies=1):
@@ -236,8 +199,7 @@ class F110VecEnv(object):
         kernel launches replay from one graph launch; `step_graph()` then costs one host call.
         Returns the static action buffer [B,A,2] to write into when no policy is given (it stays the
         same tensor across re-captures)."""
-        if self._g_actions is None:
-            self._g_actions = torch.zeros((self.num_envs, self.num_agents, 2), dtype=torch.float64, device=self.device)
+        self._static_actions()
         self._g_policy = policy
         self.eng.ready_noise()
         # `copies` > 1 captures that many identical graphs, replayed in turn (an experiment: two alternating execs
@@ -255,7 +217,7 @@ class F110VecEnv(object):
                 if policy is not None:
                     policy(self, self._g_actions.view(-1, 2))
                 self.eng.step(self._g_actions)
-                self._consumers()
+                self._after_step()
             torch.cuda.current_stream(self.device).wait_stream(side)
             self._graphs.append(g)
         self._g_copies = len(self._graphs)
@@ -263,6 +225,11 @@ class F110VecEnv(object):
         # template flags, env -> map table): it is valid for this launch epoch only
         self._g_epoch = self.eng.launch_epoch()
         return self._g_actions
+
+    def _static_actions(self):
+        """The action buffer the replayed steps read: allocated once, shared by both kinds of graph."""
+        if self._g_actions is None:
+            self._g_actions = torch.zeros((self.num_envs, self.num_agents, 2), dtype=torch.float64, device=self.device)
 
     def step_graph(self, actions=None):
         """Replays the captured step.  With `actions` they are copied into the static buffer first; cheaper is to
@@ -284,8 +251,7 @@ class F110VecEnv(object):
         """The step as a HIP graph built by the library itself (f110_graph_create: 'nodes' = explicit kernel nodes,
         'capture' = a capture on a private non-blocking stream) instead of a torch capture.  Returns the static action
         buffer [B,A,2]; `step_lib_graph()` replays."""
-        if self._g_actions is None:
-            self._g_actions = torch.zeros((self.num_envs, self.num_agents, 2), dtype=torch.float64, device=self.device)
+        self._static_actions()
         self._drop_graph()
         self.eng.ready_noise()
         self._lg = self.eng.create_graph(self._g_actions, how)
@@ -307,7 +273,7 @@ class F110VecEnv(object):
         if self.eng.launch_epoch() != self._lg_epoch:
             self.build_step_graph(self._lg_how)
         self.eng.launch_graph(self._lg)
-        self._consumers()                # behind the graph launch, on the same stream
+        self._after_step()               # behind the graph launch, on the same stream
         return self._result()
 
     def pure_pursuit(self, waypoints, lookahead, vgain, wheelbase=0.17145 + 0.15875, prepare=True):
@@ -325,9 +291,7 @@ class F110VecEnv(object):
         slots of randomize_tracks) for pure_pursuit_tracks: the planner's counterpart of f110_assign_maps.  Returns
         (TrackSet, int32 device tensor [num_envs * num_agents])."""
         from .engine import TrackSet
-        assign = np.asarray(assign)
-        if assign.shape != (self.num_envs,) or assign.min() < 0 or assign.max() >= len(waypoint_sets):
-            raise ValueError('assign must hold one raceline index (0..%d) per env' % (len(waypoint_sets) - 1))
+        assign = self._raceline_of_env(assign, len(waypoint_sets))
         ts = TrackSet(waypoint_sets, self.device)
         of_car = torch.as_tensor(np.repeat(assign.astype(np.int32), self.num_agents), device=self.device)
         return ts, of_car
@@ -397,7 +361,4 @@ class F110VecEnv(object):
 
     def close(self):
         self._drop_graph()
-        if self._to_img is not None:
-            self._to_img.close()
-            self._to_img = None
         self.eng.close()

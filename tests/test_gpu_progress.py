@@ -30,7 +30,7 @@ def _place(eng, poses, clock=0.5):
 def _read(eng):
     import torch
     torch.cuda.synchronize()
-    p = eng.p
+    p = eng.tracker.buf
     return {'seg': p['seg'].cpu().numpy().reshape(-1), 's': p['s'].cpu().numpy().reshape(-1), 'd': p['d'].cpu().numpy().reshape(-1),
             'heading_error': p['heading_error'].cpu().numpy().reshape(-1), 'delta': p['delta'].cpu().numpy().reshape(-1),
             'progress': p['progress'].cpu().numpy().reshape(-1)}
@@ -63,27 +63,27 @@ def test_frenet_pose_equals_checker_on_262144_poses(golden):
     B, A = 65536, 4
     poses, _ = _big_pose_set(golden, ck, B * A)
     eng = _engine(B, A)
-    eng.set_progress(pc.example_raceline())
+    eng.tracker.install(pc.example_raceline())
     of_car = np.zeros(B * A, dtype=int)
     trk = pc.ProgressCheckerMany([ck], of_car)
     _place(eng, poses)
-    eng.progress_update()
+    eng.tracker.update()
     grid1 = _read(eng)
     _same(grid1, trk.update(poses, np.zeros(B * A, dtype=bool)), what='grid, first update')
     moved = np.roll(poses, 1, axis=0)
     _place(eng, moved)
-    eng.progress_update()
+    eng.tracker.update()
     grid2 = _read(eng)
     _same(grid2, trk.update(moved, np.zeros(B * A, dtype=bool)), what='grid, second update')
     assert np.abs(grid2['delta']).max() > 1.0
-    eng.progress_update()                                          # twice after one step
+    eng.tracker.update()                                           # twice after one step
     again = _read(eng)
     assert (again['delta'] == 0).all() and np.array_equal(again['progress'], grid2['progress'])
     _same(again, grid2, keys=('seg', 's', 'd', 'heading_error'), what='repeated update')
     # exhaustive search, K = 1
-    eng.set_progress([pc.example_raceline()], np.zeros(B, dtype=np.int32), grid=False)
+    eng.tracker.install([pc.example_raceline()], np.zeros(B, dtype=np.int32), grid=False)
     _place(eng, poses)
-    eng.progress_update()
+    eng.tracker.update()
     _same(_read(eng), grid1, what='exhaustive against grid')
     assert eng.device_errors() == 0
     eng.close()
@@ -101,9 +101,9 @@ def test_g15_poses_equal_the_reference(golden):
     poses[:n, :2] = P
     poses[n:, :2] = P[0]
     eng = _engine(B, 1)
-    eng.set_progress(pc.example_raceline())
+    eng.tracker.install(pc.example_raceline())
     _place(eng, poses)
-    eng.progress_update()
+    eng.tracker.update()
     out = _read(eng)
     eng.close()
     s_ref = ck.cum[g['i']] + g['t'] * ck.len[g['i']]
@@ -211,14 +211,14 @@ def test_autoreset_masked_reset_and_the_seam(assets):
     for line in (pc.circle_raceline(), pc.stadium_raceline()):
         c = pc.FrenetChecker(line)
         eng = _engine(2, 1)
-        eng.set_progress(line)
+        eng.tracker.install(line)
         t2 = pc.ProgressCheckerMany([c], [0, 0])
         a = c.line.xy[0] + 0.3 * c.line.seg[0]                     # just behind the start
         b = c.line.xy[-2] + 0.6 * c.line.seg[-1]                   # on the last segment
         seq = [np.array([[a[0], a[1], 0.1], [b[0], b[1], 0.2]]), np.array([[b[0], b[1], 0.1], [a[0], a[1], 0.2]])]
         for q in seq:
             _place(eng, q)
-            eng.progress_update()
+            eng.tracker.update()
             got, want = _read(eng), t2.update(q, [False, False])
             _same(got, want, what='seam')
         assert got['delta'][0] < 0 < got['delta'][1] and abs(got['delta'][0]) < 0.5 * c.L
@@ -275,7 +275,7 @@ def test_eager_torch_graph_and_library_graph_agree(assets):
     assert env.lib_graph_info() == nodes_off
     env.step_graph(pool[1])                                        # re-captured without the update (the epoch moved)
     with pytest.raises(ValueError):
-        env.eng.progress_update()                                  # F110_E_INVALID: no tracker
+        env.eng.tracker.update()                                   # F110_E_INVALID: no tracker
     assert env.eng.device_errors() == 0
     env.close()
 
@@ -290,9 +290,9 @@ def test_several_racelines_and_random_tracks(assets):
     of_car = np.repeat(assign, A)
     rng = np.random.default_rng(77)
     eng = _engine(B, A)
-    eng.set_progress(lines, assign)
+    eng.tracker.install(lines, assign)
     trk = pc.ProgressCheckerMany(cks, of_car)
-    assert np.array_equal(eng.lap_length.cpu().numpy(), np.array([cks[k].L for k in assign]))
+    assert np.array_equal(eng.tracker.lap_length.cpu().numpy(), np.array([cks[k].L for k in assign]))
     for step in range(3):
         xy = np.zeros((B * A, 2))
         for k in range(3):
@@ -301,14 +301,14 @@ def test_several_racelines_and_random_tracks(assets):
         poses = np.concatenate([xy, rng.uniform(0, 2 * np.pi, (B * A, 1))], axis=1)
         clock = np.where(rng.uniform(size=B) < 0.25, eng.timestep, 0.37)   # a quarter of the envs "just reset"
         _place(eng, poses, clock)
-        eng.progress_update()
+        eng.tracker.update()
         _same(_read(eng), trk.update(poses, np.repeat(clock == eng.timestep, A)), what='K = 3, update %d' % step)
     assert eng.device_errors() == 0
     eng.close()
     with pytest.raises(ValueError):
         e2 = _engine(4, 1)
         try:
-            e2.set_progress([lines[0], np.array([[0., 0.], [1., 0.], [1., 0.]])], [0, 1, 0, 1])   # zero-length segment
+            e2.tracker.install([lines[0], np.array([[0., 0.], [1., 0.], [1., 0.]])], [0, 1, 0, 1])   # zero-length segment
         finally:
             e2.close()
     env = _example_env(assets, 8, 1, autoreset=False)
@@ -320,7 +320,7 @@ def test_several_racelines_and_random_tracks(assets):
         xy = np.stack([pc.scattered_poses(tracks[k].waypoints[:, :2], 1, 3.0, 500 + 8 * step + e)[0] for e, k in enumerate(slots)])
         poses = np.concatenate([xy, rng.uniform(0, 2 * np.pi, (8, 1))], axis=1)
         _place(env.eng, poses)
-        env.eng.progress_update()
+        env.eng.tracker.update()
         _same(_read(env.eng), trk.update(poses, np.zeros(8, dtype=bool)), what='random tracks, update %d' % step)
     env.close()
 
@@ -331,7 +331,7 @@ def test_pose_that_is_not_finite():
     xy = ck.line.xy
     n = 256
     eng = _engine(n, 1)
-    eng.set_progress(pc.example_raceline())
+    eng.tracker.install(pc.example_raceline())
     trk = pc.ProgressCheckerMany([ck], np.zeros(n, dtype=int))
     base = np.concatenate([xy[np.arange(n) * 3], np.full((n, 1), 1.0)], axis=1)
     seq = [base.copy(), base.copy(), base.copy(), base.copy()]
@@ -343,7 +343,7 @@ def test_pose_that_is_not_finite():
     seq[3][:, :2] = xy[np.arange(n) * 3 + 4]
     for k, q in enumerate(seq):
         _place(eng, q)
-        eng.progress_update()
+        eng.tracker.update()
         got = _read(eng)
         _same(got, trk.update(q, np.zeros(n, dtype=bool)), what='update %d' % k)
         if k == 1:

@@ -91,7 +91,7 @@ def test_closed_loop_equals_checker_through_resets(assets):
         clock = info['current_time'].cpu().numpy()
         want = ck.update(prev_img, xy, clock)
         _assert_same(got, want, what)
-        assert np.array_equal(env.eng.s['prev_xy'].cpu().numpy(), ck.prev_xy)
+        assert np.array_equal(env.eng.shaper.buf['prev_xy'].cpu().numpy(), ck.prev_xy)
         prev_img = info['lidar_bitmap'].cpu().numpy().copy()
         return got, clock
     got, _ = check(reward, info, 'reset')
@@ -209,7 +209,7 @@ def test_the_step_itself_is_unchanged_and_switching_off_removes_everything(asset
             assert set(info) == runs[0][1] and set(env.state_dict()) == runs[0][2]
             assert reward is env._reward and torch.equal(reward, torch.full((B,), env.timestep, dtype=torch.float64, device=env.device))
             with pytest.raises(ValueError):
-                env.eng.shaping_update()                            # F110_E_INVALID: no shaper
+                env.eng.shaper.kernel()                             # F110_E_INVALID: no shaper
         else:
             assert reward is env._reward
         assert env.eng.device_errors() == 0
@@ -230,13 +230,13 @@ def test_pose_that_is_not_finite(assets):
     env.shape_rewards()
     env.reset(workload.spawn_poses(B, 1))
     env.step(torch.zeros((B, 1, 2), dtype=torch.float64, device=env.device))
-    prev = env.eng.s['prev_xy'].clone()
+    prev = env.eng.shaper.buf['prev_xy'].clone()
     env.state[0::4, 0, 0] = float('nan')
     env.state[1::4, 0, 1] = float('inf')
     env.eng.t['current_time'] += 1.0                               # "stepped": the clocks moved
-    env.eng.shaping_update()
+    env.eng.shaper.kernel()
     torch.cuda.synchronize()
-    s = env.eng.s
+    s = env.eng.shaper.buf
     bad = (torch.arange(B, device=env.device) % 4) < 2
     for k in ('collision_term', 'progress_term', 'centering_term', 'total'):
         assert torch.isnan(s[k][bad]).all() and torch.isfinite(s[k][~bad]).all(), k

@@ -39,13 +39,13 @@ def kernels():
     out = torch.empty((B, 2), dtype=torch.float64, device=env.device)
     res = {}
     res['planner grid kernel'] = timed(lambda: env.eng.pure_pursuit(wp, TLAD, VGAIN, out=out))
-    env.eng.set_progress(wp_np)
-    res['tracker, grid (1 raceline)'] = timed(env.eng.progress_update)
-    env.eng.set_progress([wp_np], np.zeros(B, dtype=np.int32), grid=False)
-    res['tracker, every segment, K = 1'] = timed(env.eng.progress_update)
-    env.eng.set_progress([wp_np] * 8, np.arange(B, dtype=np.int32) % 8, grid=False)
-    res['tracker, every segment, K = 8'] = timed(env.eng.progress_update)
-    env.eng.set_progress(None)
+    env.eng.tracker.install(wp_np)
+    res['tracker, grid (1 raceline)'] = timed(env.eng.tracker.update)
+    env.eng.tracker.install([wp_np], np.zeros(B, dtype=np.int32), grid=False)
+    res['tracker, every segment, K = 1'] = timed(env.eng.tracker.update)
+    env.eng.tracker.install([wp_np] * 8, np.arange(B, dtype=np.int32) % 8, grid=False)
+    res['tracker, every segment, K = 8'] = timed(env.eng.tracker.update)
+    env.eng.tracker.remove()
     return res
 
 

@@ -54,12 +54,12 @@ for _ in range(3):
 
 def update_stepped():
     env.eng.t['current_time'].add_(env.timestep)   # (the kernel skips an env whose clock stands still; the add is ~2 us)
-    env.eng.shaping_update()
+    env.eng.shaper.kernel()
 
 
 a = report('(a) ', {'reward kernel alone (+ clock add)': update_stepped,
                     'clock add alone': lambda: env.eng.t['current_time'].add_(env.timestep)})
-b = report('(b) ', {'FILL render alone': env._render_bitmap})
+b = report('(b) ', {'FILL render alone': env.eng.shaper.render})
 env.shape_rewards(False)
 to_img = LidarBitmap(1080, bg_color='black', draw_mode='FILL')
 imgs = torch.empty((B, 256, 256), dtype=torch.uint8, device=env.device)
