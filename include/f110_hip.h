@@ -272,6 +272,7 @@ int f110_noise_read(f110_handle *h, int32_t slot, int64_t row0, int64_t n_rows, 
  * of range; bits 8.. name the table (csrc/f110_kernels.h BOUNDS_*). */
 #define F110_DEVERR_NOISE_WINDOW 0x1u
 #define F110_DEVERR_BOUNDS 0x2u
+#define F110_DEVERR_QP_LIMIT 0x4u /* the path follower's active-set walk reached its step limit (see f110_pathfollow_act) */
 int f110_device_errors(f110_handle *h, uint32_t *flags_out);
 
 int f110_bind(f110_handle *h, const f110_buffers *bufs);
@@ -493,6 +494,58 @@ int f110_shaping_install(f110_handle *h, const f110_shaping_config *cfg);
 int f110_shaping_bind(f110_handle *h, const f110_shaping_buffers *bufs);
 int f110_shaping_update(f110_handle *h, void *stream);
 
+/* Path actions: the action side of the reference's RL consumer, SACF110Env.step (src/SAL.py).  Per env, for car `agent`:
+ *   decode   compute_vectors_with_angle_clamp (:585-608) on the raw action [16] = 8 rows of 2: rows are normalised by
+ *            (norm + 1e-8), row 0 is ignored (the first increment is (1, 0)), each further heading follows the row's atan2
+ *            by at most max_diff_deg per row (Python's floor-modulo wrap); _calculate_global_path (:157-181) from the point
+ *            car_length ahead of the pose, increments of vector_length rotated by the yaw; that start point is dropped: 8 points.
+ *   mpc      MPC_controller (:615-739): chord lengths `dists`, scipy's not-a-knot CubicSpline per coordinate, reference states
+ *            ref_traj[i] = (x, y, vx, vy) at s = min(desired_velocity * (i * timestep), dists[7]), i = 0 .. horizon, the
+ *            derivative rescaled to desired_velocity (0 where its norm is <= 1e-3), and the FIRST of the reference's QPs (the
+ *            only one whose result it uses, :206-207): x_0 = (path[0], vx, vy) -- the path's first point, not the pose --
+ *            double integrator, cost sum_{k<horizon} (x_k - ref_k)'Q(x_k - ref_k) + u_k'R u_k + terminal P, -1 <= u <= 1.  Q, R,
+ *            P diagonal: one strictly convex box QP per axis, solved exactly by a primal active-set walk over host-built
+ *            inverses for every set of free variables (csrc/f110_pathfollow.h).  mpc_accel = u_0 of the two axes.
+ *   convert  MPC_converter (:741-764) with current_steer = 0: steer = clip(wrap(atan2(ay, ax)), +-max_steer), speed =
+ *            clip(ax, -1, 1), written as (steer, speed) of car `agent`.
+ * State: path_points [B,8,2], path_index [B] (< 0: no path) and t_seen [B].  f110_pathfollow_act decodes a new path for the
+ * envs with path_index < 0 or >= replan_at (path_replanned = 1, path_index = 0) and computes the action of every env.  The
+ * reference waits for index 16 on a path of 8 points and raises IndexError at index 8; replan_at (1..8, default 8) decodes
+ * the new path where it would raise.  Its pending_action is never set and is not built.  f110_pathfollow_update, behind the
+ * step: _update_path_index (:252-259), path_index += 1 if |pos - path[path_index]| < dist_threshold; episode logic read off
+ * the env's clock as for the shaper: current_time == timestep exactly (reset by its last step): path_index = -1; current_time
+ * == t_seen (a masked reset left it alone): untouched.
+ * f110_pathfollow_validate: host only.  F110_E_INVALID for agent outside 0..num_agents-1, horizon or replan_at outside 1..8,
+ * a weight of R <= 0, a weight of Q or P < 0, a scalar that is not finite, vector_length or timestep <= 0.
+ * f110_pathfollow_install: cfg NULL removes the follower; a refused cfg installs nothing.  It builds and uploads the QP's
+ * tables (cold path, synchronises).  Install, removal and bind move the launch epoch.  _act and _update: one kernel each on
+ * `stream`, no allocation, no synchronisation (capturable).  raw_actions dev [B,16]; actions_out dev [B, num_agents, 2]:
+ * only car `agent`'s pair is written. */
+typedef struct {
+    int32_t agent;              /* whose pose is read and whose action is written (0) */
+    int32_t replan_at;          /* a new path is decoded at this waypoint index (8) */
+    int32_t horizon;            /* horizon_length (5), 1..8 */
+    int32_t reserved;
+    double car_length, vector_length; /* 0.3, 0.5 */
+    double max_diff_deg;        /* 10 */
+    double dist_threshold;      /* DIST_THRESHOLD (0.2) */
+    double desired_velocity, timestep; /* MPC_PARAMS: 2.0, 0.1 */
+    double q[4], r[2], p[4];    /* diagonals of state_cost (1, 1, .1, .1), input_cost (.1, .1), terminal_cost (10, 10, 1, 1) */
+    double max_steer;           /* 0.4189 */
+} f110_pathfollow_config;
+typedef struct {
+    double *path_points;        /* [B,8,2] state */
+    int32_t *path_index;        /* [B] state; start at -1 */
+    uint8_t *path_replanned;    /* [B] the last act decoded a new path */
+    double *mpc_accel;          /* [B,2] */
+    double *t_seen;             /* [B] state: current_time at the env's previous update; start at -1 */
+} f110_pathfollow_buffers;
+int f110_pathfollow_validate(const f110_pathfollow_config *cfg, int32_t num_agents);
+int f110_pathfollow_install(f110_handle *h, const f110_pathfollow_config *cfg);
+int f110_pathfollow_bind(f110_handle *h, const f110_pathfollow_buffers *bufs);
+int f110_pathfollow_act(f110_handle *h, const double *raw_actions, double *actions_out, void *stream);
+int f110_pathfollow_update(f110_handle *h, void *stream);
+
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).
  * scans_f32 / lookups may be NULL; lookups [n] is overwritten-by-accumulation like
@@ -546,6 +599,19 @@ int f110_check_done(f110_handle *h, const double *poses, const double *start_pos
 int f110_shaping_terms(const f110_shaping_config *cfg, const uint8_t *bitmaps, const double *xy, const double *prev_xy,
                        int32_t n, double *collision_term, double *progress_term, double *centering_term, double *total,
                        uint8_t *collided, void *stream);
+/* The follower's two halves for n independent cases, stateless, no episode logic (no handle; cfg host, cfg->agent is not read;
+ * all arrays dev).  f110_pathfollow_decode: raw actions [n,16] and poses [n,3] = (x, y, yaw) -> paths [n,8,2].
+ * f110_pathfollow_mpc: paths [n,8,2] and velocities [n,2] = (vx, vy) -> dists [n,8], ref_traj [n, horizon + 1, 4], accel [n,2],
+ * actions [n,2] = (steer, speed) and qp_steps [n,2] (steps of the two active-set walks; may be NULL); dev_err (may be NULL): a
+ * device word that gets F110_DEVERR_QP_LIMIT OR-ed in.  It builds the QP's tables, waits for the kernel and frees them.
+ * f110_pathfollow_advance: _update_path_index for paths [n,8,2], index [n] (0..7; any other is copied) and positions xy [n,2]
+ * -> index_out [n]. */
+int f110_pathfollow_decode(const f110_pathfollow_config *cfg, const double *raw_actions, const double *poses, int32_t n,
+                           double *paths, void *stream);
+int f110_pathfollow_mpc(const f110_pathfollow_config *cfg, const double *paths, const double *vels, int32_t n, double *dists,
+                        double *ref_traj, double *accel, double *actions, int32_t *qp_steps, uint32_t *dev_err, void *stream);
+int f110_pathfollow_advance(const f110_pathfollow_config *cfg, const double *paths, const int32_t *index, const double *xy,
+                            int32_t n, int32_t *index_out, void *stream);
 
 /* ---- scan -> bird's-eye bitmap (the first consumer of the step's scans) ----
  * Replaces weap_util/weap_util/lidar.py:105-154 `lidar_to_bitmap` (same body in src/SAL.py:274-395

@@ -67,6 +67,21 @@ class ShapingBuffers(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in SHAPING_FIELDS]
 
 
+# f110_pathfollow_config / f110_pathfollow_buffers: the path follower's options and its caller-owned buffers
+class PathFollowConfig(C.Structure):
+    _fields_ = [('agent', C.c_int32), ('replan_at', C.c_int32), ('horizon', C.c_int32), ('reserved', C.c_int32),
+                ('car_length', C.c_double), ('vector_length', C.c_double), ('max_diff_deg', C.c_double),
+                ('dist_threshold', C.c_double), ('desired_velocity', C.c_double), ('timestep', C.c_double),
+                ('q', C.c_double * 4), ('r', C.c_double * 2), ('p', C.c_double * 4), ('max_steer', C.c_double)]
+
+
+PATHFOLLOW_FIELDS = ['path_points', 'path_index', 'path_replanned', 'mpc_accel', 't_seen']
+
+
+class PathFollowBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in PATHFOLLOW_FIELDS]
+
+
 # every symbol include/f110_hip.h declares: name -> argtypes (restype int unless noted)
 _VP, _I32, _I64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -126,6 +141,14 @@ SYMBOLS = {
     'f110_shaping_bind': [_VP, C.POINTER(ShapingBuffers)],
     'f110_shaping_update': [_VP, _VP],
     'f110_shaping_terms': [C.POINTER(ShapingConfig), _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_pathfollow_validate': [C.POINTER(PathFollowConfig), _I32],
+    'f110_pathfollow_install': [_VP, C.POINTER(PathFollowConfig)],
+    'f110_pathfollow_bind': [_VP, C.POINTER(PathFollowBuffers)],
+    'f110_pathfollow_act': [_VP, _VP, _VP, _VP],
+    'f110_pathfollow_update': [_VP, _VP],
+    'f110_pathfollow_decode': [C.POINTER(PathFollowConfig), _VP, _VP, _I32, _VP, _VP],
+    'f110_pathfollow_mpc': [C.POINTER(PathFollowConfig), _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_pathfollow_advance': [C.POINTER(PathFollowConfig), _VP, _VP, _VP, _I32, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],
     'f110_profile_every': [_VP, _I32],
     'f110_profile_end': [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32)],

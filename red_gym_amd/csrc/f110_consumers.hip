@@ -427,6 +427,205 @@ extern "C" int f110_shaping_terms(const f110_shaping_config *cfg, const uint8_t 
     return launch_shaping(a, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- path actions
+// What install refuses, on the struct alone (no handle, no device).
+extern "C" int f110_pathfollow_validate(const f110_pathfollow_config *cfg, int32_t num_agents)
+{
+    const char *who = "f110_pathfollow_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    if (cfg->agent < 0 || cfg->agent >= num_agents) return fail(F110_E_INVALID, "%s: agent %d (0..%d)", who, cfg->agent, num_agents - 1);
+    if (cfg->horizon < 1 || cfg->horizon > PF_MAX_H) return fail(F110_E_INVALID, "%s: horizon %d (1..%d)", who, cfg->horizon, PF_MAX_H);
+    if (cfg->replan_at < 1 || cfg->replan_at > PF_POINTS) return fail(F110_E_INVALID, "%s: replan_at %d (1..%d)", who, cfg->replan_at, PF_POINTS);
+    const double scalars[] = {cfg->car_length, cfg->vector_length, cfg->max_diff_deg, cfg->dist_threshold, cfg->desired_velocity,
+                              cfg->timestep, cfg->max_steer, cfg->q[0], cfg->q[1], cfg->q[2], cfg->q[3], cfg->r[0], cfg->r[1],
+                              cfg->p[0], cfg->p[1], cfg->p[2], cfg->p[3]};
+    for (double v : scalars)
+        if (!std::isfinite(v)) return fail(F110_E_INVALID, "%s: a scalar of the config is not finite", who);
+    for (int i = 0; i < 2; i++)
+        if (!(cfg->r[i] > 0.0)) return fail(F110_E_INVALID, "%s: input weight r[%d] = %g must be positive (the QP must be strictly convex)", who, i, cfg->r[i]);
+    for (int i = 0; i < 4; i++)
+        if (cfg->q[i] < 0.0 || cfg->p[i] < 0.0) return fail(F110_E_INVALID, "%s: state weight q[%d] = %g / p[%d] = %g is negative", who, i, cfg->q[i], i, cfg->p[i]);
+    if (!(cfg->vector_length > 0.0)) return fail(F110_E_INVALID, "%s: vector_length %g must be positive (the spline's knots are the chord lengths)", who, cfg->vector_length);
+    if (!(cfg->timestep > 0.0)) return fail(F110_E_INVALID, "%s: timestep %g must be positive", who, cfg->timestep);
+    return F110_OK;
+}
+
+// The table of pathfollow_table_doubles(horizon) the act kernel reads: per axis the Hessian (halved) of the QP, H = sum_k wp_k
+// a_k a_k' + wv_k b_k b_k' + r I over k = 1 .. horizon with a_k[j] = dt^2 (k - j - 1/2), b_k[j] = dt for j < k, and for every set
+// of free variables the inverse of its restriction (Gauss-Jordan with partial pivoting; the matrix is positive definite).
+static int pathfollow_tables(const f110_pathfollow_config &c, std::vector<double> &tab)
+{
+    const int H = c.horizon, HH = H * H;
+    const double dt = c.timestep;
+    tab.assign(pathfollow_table_doubles(H), 0.0);
+    for (int ax = 0; ax < 2; ax++) {
+        double *Hm = tab.data() + (size_t)ax * HH;
+        for (int k = 1; k <= H; k++) {
+            const double wp = k < H ? c.q[ax] : c.p[ax], wv = k < H ? c.q[2 + ax] : c.p[2 + ax];
+            for (int i = 0; i < k; i++)
+                for (int j = 0; j < k; j++)
+                    Hm[i * H + j] += wp * (dt * dt * (k - i - 0.5)) * (dt * dt * (k - j - 0.5)) + wv * dt * dt;
+        }
+        for (int i = 0; i < H; i++) Hm[i * H + i] += c.r[ax];
+        for (unsigned set = 1; set < (1u << H); set++) {
+            int id[PF_MAX_H], m = 0;
+            for (int i = 0; i < H; i++) if ((set >> i) & 1u) id[m++] = i;
+            double aug[PF_MAX_H][2 * PF_MAX_H];
+            for (int i = 0; i < m; i++)
+                for (int j = 0; j < m; j++) { aug[i][j] = Hm[id[i] * H + id[j]]; aug[i][m + j] = i == j ? 1.0 : 0.0; }
+            for (int col = 0; col < m; col++) {
+                int piv = col;
+                for (int i = col + 1; i < m; i++) if (std::fabs(aug[i][col]) > std::fabs(aug[piv][col])) piv = i;
+                if (!(std::fabs(aug[piv][col]) > 0.0)) return fail(F110_E_INVALID, "f110_pathfollow: the QP's Hessian is singular");
+                for (int j = 0; j < 2 * m; j++) std::swap(aug[col][j], aug[piv][j]);
+                const double d = aug[col][col];
+                for (int j = 0; j < 2 * m; j++) aug[col][j] /= d;
+                for (int i = 0; i < m; i++) {
+                    if (i == col) continue;
+                    const double fct = aug[i][col];
+                    for (int j = 0; j < 2 * m; j++) aug[i][j] -= fct * aug[col][j];
+                }
+            }
+            double *Z = tab.data() + (size_t)2 * HH + ((size_t)ax * ((size_t)1 << H) + set) * HH;
+            for (int i = 0; i < m; i++)
+                for (int j = 0; j < m; j++) Z[id[i] * H + id[j]] = 0.5 * (aug[i][m + j] + aug[j][m + i]);
+        }
+    }
+    return F110_OK;
+}
+
+extern "C" int f110_pathfollow_install(f110_handle *h, const f110_pathfollow_config *cfg)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_pathfollow_install: null handle");
+    f110_handle::PathFollow &p = h->follow;
+    if (!cfg) { // removes the follower (the table stays for the next install: an enqueued act may still read it)
+        if (!p.on) return F110_OK;
+        p.on = false;
+        h->epoch++;
+        return F110_OK;
+    }
+    if (int rc = f110_pathfollow_validate(cfg, h->cfg.num_agents)) return rc;
+    if (int rc = clock_usable(h, "f110_pathfollow_install")) return rc;
+    std::vector<double> tab;
+    if (int rc = pathfollow_tables(*cfg, tab)) return rc;
+    ON_DEVICE(h->cfg.device);
+    DevBuf<double> n;
+    HIP_TRY(n.upload(tab.data(), tab.size()));
+    HIP_TRY(hipDeviceSynchronize()); // an enqueued act may still read the table that is replaced
+    p.d_qp = std::move(n);
+    p.cfg = *cfg;
+    p.on = true;
+    h->epoch++; // a captured act takes the table's pointer and the configuration by value
+    return F110_OK;
+}
+
+extern "C" int f110_pathfollow_bind(f110_handle *h, const f110_pathfollow_buffers *b)
+{
+    if (!h || !b) return fail(F110_E_INVALID, "f110_pathfollow_bind: null argument");
+    if (!b->path_points || !b->path_index || !b->path_replanned || !b->mpc_accel || !b->t_seen)
+        return fail(F110_E_INVALID, "f110_pathfollow_bind: a buffer is NULL (all five are required)");
+    h->follow.bufs = *b;
+    h->follow.bound = true;
+    h->epoch++;
+    return F110_OK;
+}
+
+static int launch_pathfollow_act(const PathFollowArgs &a, hipStream_t stream)
+{
+    if (a.n == 0) return F110_OK;
+    hipLaunchKernelGGL(pathfollow_act_kernel, dim3((unsigned)((2LL * a.n + 255) / 256)), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+static int launch_pathfollow_advance(const PathAdvanceArgs &a, hipStream_t stream)
+{
+    if (a.n == 0) return F110_OK;
+    hipLaunchKernelGGL(pathfollow_advance_kernel, dim3((a.n + 255) / 256), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_pathfollow_act(f110_handle *h, const double *raw_actions, double *actions_out, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_pathfollow_act: null handle");
+    const f110_handle::PathFollow &p = h->follow;
+    if (int rc = update_ready(h, "f110_pathfollow_act", "path follower", "pathfollow", p.on, p.bound)) return rc;
+    if (!raw_actions || !actions_out) return fail(F110_E_INVALID, "f110_pathfollow_act: null pointer");
+    PathFollowArgs a;
+    memset(&a, 0, sizeof(a));
+    const long long A = h->cfg.num_agents;
+    a.cfg = p.cfg; a.n = h->cfg.num_envs; a.raw = raw_actions;
+    a.pose = h->bufs.state + 7 * (size_t)p.cfg.agent; a.pose_stride = 7 * A; a.th_off = 4;
+    a.vel = h->bufs.state + 7 * (size_t)p.cfg.agent + 3; a.vel_stride = 7 * A; a.has_vy = 0; // linear_vels_y is always 0
+    a.path = p.bufs.path_points; a.index = p.bufs.path_index; a.replanned = p.bufs.path_replanned; a.qp = p.d_qp.get();
+    a.accel = p.bufs.mpc_accel; a.actions = actions_out + 2 * (size_t)p.cfg.agent; a.act_stride = 2 * A;
+    a.dev_err = h->d_err.get();
+    return launch_pathfollow_act(a, (hipStream_t)stream);
+}
+
+extern "C" int f110_pathfollow_update(f110_handle *h, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_pathfollow_update: null handle");
+    const f110_handle::PathFollow &p = h->follow;
+    if (int rc = update_ready(h, "f110_pathfollow_update", "path follower", "pathfollow", p.on, p.bound)) return rc;
+    PathAdvanceArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cfg = p.cfg; a.n = h->cfg.num_envs;
+    a.xy = h->bufs.state + 7 * (size_t)p.cfg.agent; a.xy_stride = 7LL * h->cfg.num_agents;
+    a.path = p.bufs.path_points; a.index_in = p.bufs.path_index; a.index_out = p.bufs.path_index;
+    a.current_time = h->bufs.current_time; a.timestep = h->cfg.timestep; a.t_seen = p.bufs.t_seen; a.dev_err = h->d_err.get();
+    return launch_pathfollow_advance(a, (hipStream_t)stream);
+}
+
+static int pathfollow_stateless(const f110_pathfollow_config *cfg, f110_pathfollow_config &c, const char *who)
+{
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    c = *cfg;
+    c.agent = 0;
+    return f110_pathfollow_validate(&c, 1);
+}
+
+extern "C" int f110_pathfollow_decode(const f110_pathfollow_config *cfg, const double *raw_actions, const double *poses, int32_t n,
+                                      double *paths, void *stream)
+{
+    PathFollowArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = pathfollow_stateless(cfg, a.cfg, "f110_pathfollow_decode")) return rc;
+    if (n < 0 || !raw_actions || !poses || !paths) return fail(F110_E_INVALID, "f110_pathfollow_decode: bad arguments");
+    a.n = n; a.raw = raw_actions; a.pose = poses; a.pose_stride = 3; a.th_off = 2; a.path = paths;
+    return launch_pathfollow_act(a, (hipStream_t)stream);
+}
+
+extern "C" int f110_pathfollow_mpc(const f110_pathfollow_config *cfg, const double *paths, const double *vels, int32_t n, double *dists,
+                                   double *ref_traj, double *accel, double *actions, int32_t *qp_steps, uint32_t *dev_err, void *stream)
+{
+    PathFollowArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = pathfollow_stateless(cfg, a.cfg, "f110_pathfollow_mpc")) return rc;
+    if (n < 0 || !paths || !vels || !dists || !ref_traj || !accel || !actions) return fail(F110_E_INVALID, "f110_pathfollow_mpc: bad arguments");
+    std::vector<double> tab;
+    if (int rc = pathfollow_tables(a.cfg, tab)) return rc;
+    DevBuf<double> d_qp;
+    HIP_TRY(d_qp.upload(tab.data(), tab.size()));
+    a.n = n; a.path = const_cast<double *>(paths); a.vel = vels; a.vel_stride = 2; a.has_vy = 1; a.qp = d_qp.get();
+    a.dists = dists; a.ref_traj = ref_traj; a.accel = accel; a.actions = actions; a.act_stride = 2; a.qp_steps = qp_steps; a.dev_err = dev_err;
+    if (int rc = launch_pathfollow_act(a, (hipStream_t)stream)) return rc;
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); // the table is freed on return
+    return F110_OK;
+}
+
+extern "C" int f110_pathfollow_advance(const f110_pathfollow_config *cfg, const double *paths, const int32_t *index, const double *xy,
+                                       int32_t n, int32_t *index_out, void *stream)
+{
+    PathAdvanceArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = pathfollow_stateless(cfg, a.cfg, "f110_pathfollow_advance")) return rc;
+    if (n < 0 || !paths || !index || !xy || !index_out) return fail(F110_E_INVALID, "f110_pathfollow_advance: bad arguments");
+    a.n = n; a.xy = xy; a.xy_stride = 2; a.path = paths; a.index_in = index; a.index_out = index_out;
+    return launch_pathfollow_advance(a, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- scan -> bitmap
 static const void *bitmap_fn(size_t lds, int mode, int channels)
 {

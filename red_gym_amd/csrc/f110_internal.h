@@ -5,7 +5,7 @@
 //   f110_maps.hip       map installation (host table / occupancy mask -> cell codes, LUTs), device EDT, track mask
 //   f110_noise_abi.hip  lidar noise: slots, ring, generators, per-env mode
 //   f110_step.hip       launch policy of the scan, the step, hipGraphs, measurement aid, function-level entry points
-//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, progress tracker, reward shaper, scan -> bitmap,
+//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, progress tracker, reward shaper, path follower, scan -> bitmap,
 //                       occupancy grid
 #pragma once
 #include "../../include/f110_hip.h"
@@ -14,6 +14,7 @@
 #include "f110_planner.h"
 #include "f110_progress.h"
 #include "f110_shaping.h"
+#include "f110_pathfollow.h"
 #include "f110_bitmap.h"
 #include "f110_mapgen.h"
 
@@ -219,6 +220,14 @@ struct f110_handle {
         f110_shaping_config cfg;
         f110_shaping_buffers bufs;
     } shaping;
+    // path follower (f110_pathfollow_install / _bind / _act / _update, f110_consumers.hip): the configuration, the QP's host-built
+    // tables (f110_pathfollow.h) and the caller's buffers
+    struct PathFollow {
+        bool on = false, bound = false;
+        f110_pathfollow_config cfg;
+        DevBuf<double> d_qp;
+        f110_pathfollow_buffers bufs;
+    } follow;
     const int32_t *scan_order = nullptr; // launch order of the step's scan (f110_set_scan_order; caller-owned device array) or NULL
     DevBuf<uint32_t> d_err;           // device error word (f110_device_errors)
     std::vector<double> h_side;       // side distances (host copy of d_side)

@@ -12,6 +12,7 @@ from .base_classes import integrator_code
 from .maps import load_map
 from .progress import ProgressTracker
 from .shaping import RewardShaper
+from .pathfollow import PathFollower
 
 # f110_env.py:128
 DEFAULT_PARAMS = {'mu': 1.0489, 'C_Sf': 4.718, 'C_Sr': 5.4562, 'lf': 0.15875, 'lr': 0.17145, 'h': 0.074,
@@ -136,7 +137,7 @@ class Engine(object):
         self.env_params_assign, self._side_slots = None, None   # params slot of every env; [slots, num_beams] while installed
         self.lib = _lib.load()
         # the step's consumers (consumer.py), in the order their kernels follow a step; nothing is allocated until an install
-        self.tracker, self.shaper = ProgressTracker(self), RewardShaper(self)
+        self.tracker, self.shaper, self.follower = ProgressTracker(self), RewardShaper(self), PathFollower(self)
         env_params = None
         if params is not None and not isinstance(params, dict):
             env_params = [dict(p) for p in params]
@@ -752,6 +753,7 @@ class Engine(object):
         if getattr(self, '_h', None) is not None and self._h:
             self.tracker.close()
             self.shaper.close()
+            self.follower.close()
             torch.cuda.synchronize(self.device)
             flags = self.device_errors() if os.environ.get('F110_CHECK_DEVICE_ERRORS') == '1' else 0
             self.lib.f110_destroy(self._h)

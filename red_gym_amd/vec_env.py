@@ -70,7 +70,7 @@ class F110VecEnv(object):
             self._obs['scans_f64'] = t['scans_f64']
         self._reward = torch.full((self.num_envs,), float(timestep), dtype=torch.float64, device=self.device)
         self._g_actions, self._graphs, self._lg = None, [], None   # capture_step / build_step_graph
-        self.consumers = (self.eng.tracker, self.eng.shaper)        # track_progress, shape_rewards: the ones that are `on` run
+        self.consumers = (self.eng.tracker, self.eng.shaper, self.eng.follower)   # track_progress, shape_rewards, follow_paths: the ones that are `on` run
 
     def _result(self):
         t = self.eng.t
@@ -86,7 +86,7 @@ class F110VecEnv(object):
         return self._obs, self._reward if reward is None else reward, done, info
 
     def _after_step(self):
-        """What follows every step on the same stream: the progress tracker's update, then the reward shaper's."""
+        """What follows every step on the same stream: the progress tracker's update, the reward shaper's, the path follower's."""
         for c in self.consumers:
             if c.on:
                 c.update()
@@ -166,6 +166,42 @@ class F110VecEnv(object):
             self.eng.shaper.install(**cfg)
         else:
             self.eng.shaper.remove()
+
+    # ------------------------------------------------------------------ path actions
+    def follow_paths(self, enable=True, **cfg):
+        """Switches the path follower on: the action side of the reference's RL consumer (src/SAL.py, SACF110Env.step) for
+        every env on the GPU.  `cfg`: options of red_gym_amd.pathfollow.DEFAULTS (agent, car_length, vector_length,
+        max_diff_deg, dist_threshold, replan_at, desired_velocity, timestep, horizon, q, r, p, max_steer; SAL's numbers where
+        absent).  From then on path_actions(raw_actions) turns the policy's [B, 16] numbers into (steer, speed) of car
+        `agent`, and reset, step, step_graph and step_lib_graph run the follower's update behind the step: the waypoint index
+        follows the new pose (_update_path_index), and an env that was reset (masked, whole batch or autoreset) loses its
+        path and decodes a new one at its next path_actions.  `info` also holds path_points [B, 8, 2] fp64, path_index [B]
+        int32 (< 0: no path), path_replanned [B] uint8 (the last path_actions decoded a new path) and mpc_accel [B, 2] fp64
+        -- views, no copies.  The reference's pending_action (never set) is left out, and where it would raise IndexError
+        (its path has 8 points, it replans at index 16) a new path is decoded: replan_at, default 8.
+        follow_paths(False) switches it off: no launch, no info key, no state_dict key remains."""
+        if enable:
+            self.eng.follower.install(**cfg)
+        else:
+            self.eng.follower.remove()
+
+    def path_actions(self, raw_actions, out=None):
+        """The follower's actions [B, A, 2] for the policy's raw_actions [B, 16] (device tensor) at the current poses and
+        velocities: one kernel on the current stream, no synchronisation.  With `out` ([B, A, 2] or its [B * A, 2] view)
+        only car `agent`'s pairs are written and the others stay as they are; without it a new tensor is returned whose
+        other entries are 0.  Usable as the policy of capture_step -- `lambda env, out: env.path_actions(raw, out=out)` with
+        `raw` a tensor that is refilled in place -- and in front of step_lib_graph, writing into the static action buffer.
+        ValueError while the follower is off."""
+        if not self.eng.follower.on:
+            raise ValueError('path_actions: the path follower is off (follow_paths())')
+        if out is None:
+            out = torch.zeros((self.num_envs, self.num_agents, 2), dtype=torch.float64, device=self.device)
+        if not torch.is_tensor(raw_actions):
+            raw_actions = torch.as_tensor(np.ascontiguousarray(raw_actions, dtype=np.float64))
+        if raw_actions.dtype != torch.float64 or raw_actions.device != self.device or not raw_actions.is_contiguous():
+            raw_actions = raw_actions.to(device=self.device, dtype=torch.float64).contiguous()
+        self.eng.follower.act(raw_actions, out)
+        return out.view(self.num_envs, self.num_agents, 2)
 
     # ------------------------------------------------------------------ checkpoint / resume
     _STATE_KEYS = ('state', 'steer_buf', 'steer_cnt', 'noise_step', 'spawn', 'start_rot', 'near_start', 'toggles',
