@@ -546,6 +546,60 @@ int f110_pathfollow_bind(f110_handle *h, const f110_pathfollow_buffers *bufs);
 int f110_pathfollow_act(f110_handle *h, const double *raw_actions, double *actions_out, void *stream);
 int f110_pathfollow_update(f110_handle *h, void *stream);
 
+/* Replay buffer: the ReplayBuffer of the reference's RL consumer (src/SAL.py:447-463) and the push of its training loop
+ * (:996-1001), on the device behind the reward shaper.  A ring of T = steps step slots for all B envs; FIFO by step slot like
+ * the reference's deque(maxlen).  Push number c (c = count, an int64 that lives on the device and is advanced by a one-lane
+ * kernel behind the push, so that a captured push replays correctly: no slot ever crosses the ABI by value) writes
+ *   frame slot c % (T + 1)   the shaper's bitmap as the step left it, bit-packed: a row of cols pixels is words = ceil(cols /
+ *                            64) uint64, bit k of word w = (pixel[64 w + k] == 255), tail bits 0 -- np.packbits(row == 255,
+ *                            bitorder='little') padded with zeros to 8 * words bytes.  Frames are stored once: T step slots
+ *                            own T + 1 frame slots, the transition of push c is (frame c - 1, frame c)
+ *   step slot c % T          action = action_in[env] (fp32 [action_dim]), reward = the shaper's total (fp64), done (uint8) and
+ *                            valid (uint8); last_valid[env] = the same valid.
+ * valid = 0 (never sampled) when (1) current_time[env] == timestep exactly: the step was the env's reset (f110_reset, masked
+ * or not, or autoreset) -- terminal frame and spawn frame are no transition; (2) current_time[env] == t_seen[env]: the env was
+ * not stepped by the call; (3) c <= chain_start[0]: there is no previous frame (chain_start starts at 0; the caller sets it to
+ * count after restoring a checkpoint).  The terminal step itself (done = 1) is valid, its next frame the terminal observation.
+ * A transition is named by index = step slot * B + env.
+ * f110_replay_validate: host only; `shaping` = the shaper's configuration, NULL = shaping is off.  F110_E_INVALID for shaping
+ * off, steps < 2, action_dim < 1, rows or cols above 16384, a ring whose byte sizes overflow.
+ * f110_replay_install: behind an installed shaper (whose rows / cols the ring takes); cfg NULL removes it.  An install needs
+ * a new f110_replay_bind.  f110_shaping_install(NULL), or one with another image size, removes the buffer too.  Install,
+ * removal and bind move the launch epoch.
+ * f110_replay_update: the push, two kernels on `stream` behind f110_shaping_update and the render of the new bitmap; no
+ * allocation, no synchronisation (capturable).
+ * f110_replay_draw: n indices uniform over the valid transitions, no synchronisation.  Attempt k < F110_REPLAY_TRIES of draw j
+ * (j counts from first_draw) takes z = splitmix64(seed + 0x9E3779B97F4A7C15 * (1 + j * F110_REPLAY_TRIES + k)) and the candidate
+ * mulhi64(z, stored * B), stored = min(count, T); candidate / B = age (0: the newest push), candidate % B = env; the first
+ * candidate whose valid is set wins.  None: indices[j] = -1 and ok[j] = 0.
+ * f110_replay_gather: for n indices (dev int64) s = frame before, ns = frame after, unpacked to uint8 [n, rows, cols] (as_f32
+ * = 0) or to fp32 [n, 1, rows, cols] = pixel * (float)scale; a [n, action_dim] fp32, r [n] fp64, d [n], ok [n] uint8.  An index
+ * outside 0 .. T * B - 1 (-1 included) or of an invalid transition yields zeros in every output and ok = 0. */
+#define F110_REPLAY_TRIES 64
+typedef struct {
+    int32_t steps;              /* T: step slots of the ring (capacity in transitions / num_envs), at least 2 */
+    int32_t action_dim;         /* values of the stored action (16: SAL's raw action) */
+} f110_replay_config;
+typedef struct {
+    uint64_t *frames;           /* [T + 1, B, rows, words] */
+    float *actions;             /* [T, B, action_dim] */
+    double *rewards;            /* [T, B] */
+    uint8_t *dones;             /* [T, B] */
+    uint8_t *valid;             /* [T, B]; start at 0 */
+    int64_t *count;             /* [1] pushes made; start at 0 */
+    int64_t *chain_start;       /* [1] the push that has no previous frame; start at 0 */
+    double *t_seen;             /* [B] current_time at the env's previous push; start at -1 */
+    uint8_t *last_valid;        /* [B] valid of the push just made */
+    const float *action_in;     /* [B, action_dim] in: what the next push stores */
+} f110_replay_buffers;
+int f110_replay_validate(const f110_replay_config *cfg, const f110_shaping_config *shaping, int32_t num_envs);
+int f110_replay_install(f110_handle *h, const f110_replay_config *cfg);
+int f110_replay_bind(f110_handle *h, const f110_replay_buffers *bufs);
+int f110_replay_update(f110_handle *h, void *stream);
+int f110_replay_draw(f110_handle *h, uint64_t seed, uint64_t first_draw, int32_t n, int64_t *indices, uint8_t *ok, void *stream);
+int f110_replay_gather(f110_handle *h, const int64_t *indices, int32_t n, void *s, void *ns, int32_t as_f32, double scale,
+                       float *a, double *r, uint8_t *d, uint8_t *ok, void *stream);
+
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).
  * scans_f32 / lookups may be NULL; lookups [n] is overwritten-by-accumulation like
@@ -612,6 +666,10 @@ int f110_pathfollow_mpc(const f110_pathfollow_config *cfg, const double *paths, 
                         double *ref_traj, double *accel, double *actions, int32_t *qp_steps, uint32_t *dev_err, void *stream);
 int f110_pathfollow_advance(const f110_pathfollow_config *cfg, const double *paths, const int32_t *index, const double *xy,
                             int32_t n, int32_t *index_out, void *stream);
+/* The replay buffer's frame format, stateless (no handle; all arrays dev, 16-byte aligned; rows, cols 1..16384): n images
+ * bitmaps [n, rows, cols] uint8 -> packed [n, rows, words] uint64 (bit = pixel == 255) and back (0 / 255). */
+int f110_replay_pack(const uint8_t *bitmaps, int64_t n, int32_t rows, int32_t cols, uint64_t *packed, void *stream);
+int f110_replay_unpack(const uint64_t *packed, int64_t n, int32_t rows, int32_t cols, uint8_t *bitmaps, void *stream);
 
 /* ---- scan -> bird's-eye bitmap (the first consumer of the step's scans) ----
  * Replaces weap_util/weap_util/lidar.py:105-154 `lidar_to_bitmap` (same body in src/SAL.py:274-395

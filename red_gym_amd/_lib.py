@@ -82,6 +82,19 @@ class PathFollowBuffers(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in PATHFOLLOW_FIELDS]
 
 
+# f110_replay_config / f110_replay_buffers: the replay buffer's options and its caller-owned ring
+class ReplayConfig(C.Structure):
+    _fields_ = [('steps', C.c_int32), ('action_dim', C.c_int32)]
+
+
+REPLAY_FIELDS = ['frames', 'actions', 'rewards', 'dones', 'valid', 'count', 'chain_start', 't_seen', 'last_valid', 'action_in']
+F110_REPLAY_TRIES = 64
+
+
+class ReplayBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in REPLAY_FIELDS]
+
+
 # every symbol include/f110_hip.h declares: name -> argtypes (restype int unless noted)
 _VP, _I32, _I64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -149,6 +162,14 @@ SYMBOLS = {
     'f110_pathfollow_decode': [C.POINTER(PathFollowConfig), _VP, _VP, _I32, _VP, _VP],
     'f110_pathfollow_mpc': [C.POINTER(PathFollowConfig), _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_pathfollow_advance': [C.POINTER(PathFollowConfig), _VP, _VP, _VP, _I32, _VP, _VP],
+    'f110_replay_validate': [C.POINTER(ReplayConfig), C.POINTER(ShapingConfig), _I32],
+    'f110_replay_install': [_VP, C.POINTER(ReplayConfig)],
+    'f110_replay_bind': [_VP, C.POINTER(ReplayBuffers)],
+    'f110_replay_update': [_VP, _VP],
+    'f110_replay_draw': [_VP, C.c_uint64, C.c_uint64, _I32, _VP, _VP, _VP],
+    'f110_replay_gather': [_VP, _VP, _I32, _VP, _VP, _I32, _D, _VP, _VP, _VP, _VP, _VP],
+    'f110_replay_pack': [_VP, _I64, _I32, _I32, _VP, _VP],
+    'f110_replay_unpack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],
     'f110_profile_every': [_VP, _I32],
     'f110_profile_end': [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int32)],

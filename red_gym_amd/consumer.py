@@ -1,5 +1,6 @@
 """What the step's consumers share.  A consumer is a kernel enqueued behind every step that adds keys to `info`: the progress
-tracker (progress.py) and the reward shaper (shaping.py).  The Engine owns one object of each; F110VecEnv loops over the pair."""
+tracker (progress.py), the reward shaper (shaping.py), the path follower (pathfollow.py) and the replay buffer (replay.py).  The
+Engine owns one object of each; F110VecEnv loops over them."""
 import ctypes as C
 import weakref
 
@@ -46,6 +47,10 @@ class Consumer(object):
                 self.buf[name].copy_(sd[k])
         else:
             self.restart()
+
+    def on_load_state_dict(self, sd):
+        """What F110VecEnv.load_state_dict asks of a consumer that is `on`."""
+        self.load(sd)
 
     def close(self):
         pass

@@ -363,11 +363,13 @@ extern "C" int f110_shaping_install(f110_handle *h, const f110_shaping_config *c
     if (!cfg) { // removes the shaper
         if (!s.on) return F110_OK;
         s.on = false;
+        h->replay.on = false; // the replay buffer records the shaper's image and reward: it goes with it
         h->epoch++;
         return F110_OK;
     }
     if (int rc = f110_shaping_validate(cfg, h->cfg.num_agents)) return rc;
     if (int rc = clock_usable(h, "f110_shaping_install")) return rc;
+    if (h->replay.on && (cfg->rows != h->replay.rows || cfg->cols != h->replay.cols)) h->replay.on = false; // (its ring holds the old size)
     s.cfg = *cfg; // by value in every launch: nothing on the device to replace
     s.on = true;
     h->epoch++;
@@ -624,6 +626,157 @@ extern "C" int f110_pathfollow_advance(const f110_pathfollow_config *cfg, const 
     if (n < 0 || !paths || !index || !xy || !index_out) return fail(F110_E_INVALID, "f110_pathfollow_advance: bad arguments");
     a.n = n; a.xy = xy; a.xy_stride = 2; a.path = paths; a.index_in = index; a.index_out = index_out;
     return launch_pathfollow_advance(a, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------- replay buffer
+// What install refuses, on the structs alone (no handle, no device).  `shaping`: the installed shaper's configuration, NULL = off.
+extern "C" int f110_replay_validate(const f110_replay_config *cfg, const f110_shaping_config *shaping, int32_t num_envs)
+{
+    const char *who = "f110_replay_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    if (!shaping) return fail(F110_E_INVALID, "%s: reward shaping is off (the buffer records the shaper's bitmap and reward: f110_shaping_install)", who);
+    if (shaping->rows < 1 || shaping->cols < 1 || shaping->rows > REPLAY_MAX_DIM || shaping->cols > REPLAY_MAX_DIM)
+        return fail(F110_E_INVALID, "%s: image of %d x %d pixels (1..%d)", who, shaping->rows, shaping->cols, REPLAY_MAX_DIM);
+    if (cfg->steps < 2) return fail(F110_E_INVALID, "%s: %d step slots (at least 2)", who, cfg->steps);
+    if (cfg->action_dim < 1) return fail(F110_E_INVALID, "%s: action_dim %d (at least 1)", who, cfg->action_dim);
+    if (num_envs < 1) return fail(F110_E_INVALID, "%s: num_envs=%d", who, num_envs);
+    // every size the kernels form, in bytes, stays below 2^62
+    const long double lim = 4611686018427387904.0L;
+    const long double cells = ((long double)cfg->steps + 1.0L) * (long double)num_envs;
+    const long double frame = (long double)shaping->rows * (long double)replay_words(shaping->cols) * 8.0L;
+    if (cells * frame >= lim || cells * (long double)cfg->action_dim * 4.0L >= lim || cells * 8.0L >= lim)
+        return fail(F110_E_INVALID, "%s: a ring of %d steps x %d envs (frames of %d x %d, %d action values) overflows", who, cfg->steps, num_envs,
+                    shaping->rows, shaping->cols, cfg->action_dim);
+    return F110_OK;
+}
+
+extern "C" int f110_replay_install(f110_handle *h, const f110_replay_config *cfg)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_replay_install: null handle");
+    f110_handle::Replay &r = h->replay;
+    if (!cfg) { // removes the buffer (the ring is the caller's)
+        if (!r.on) return F110_OK;
+        r.on = false; r.bound = false;
+        h->epoch++;
+        return F110_OK;
+    }
+    if (int rc = f110_replay_validate(cfg, h->shaping.on ? &h->shaping.cfg : nullptr, h->cfg.num_envs)) return rc;
+    if (int rc = clock_usable(h, "f110_replay_install")) return rc;
+    r.cfg = *cfg; r.rows = h->shaping.cfg.rows; r.cols = h->shaping.cfg.cols;
+    r.on = true; r.bound = false; // the ring's shape may have changed: bind again
+    h->epoch++;
+    return F110_OK;
+}
+
+extern "C" int f110_replay_bind(f110_handle *h, const f110_replay_buffers *b)
+{
+    if (!h || !b) return fail(F110_E_INVALID, "f110_replay_bind: null argument");
+    if (!b->frames || !b->actions || !b->rewards || !b->dones || !b->valid || !b->count || !b->chain_start || !b->t_seen || !b->last_valid || !b->action_in)
+        return fail(F110_E_INVALID, "f110_replay_bind: a buffer is NULL (all ten are required)");
+    if ((uintptr_t)b->frames % 16) return fail(F110_E_INVALID, "f110_replay_bind: frames must be 16-byte aligned");
+    h->replay.bufs = *b;
+    h->replay.bound = true;
+    h->epoch++;
+    return F110_OK;
+}
+
+// `who` may run: the buffer is installed and bound, and the shaper it records still draws images of the ring's size
+static int replay_ready(const f110_handle *h, const char *who, ReplayRing &g)
+{
+    const f110_handle::Replay &r = h->replay;
+    if (int rc = update_ready(h, who, "replay buffer", "replay", r.on, r.bound)) return rc;
+    const f110_handle::Shaping &s = h->shaping;
+    if (!s.on || !s.bound || s.cfg.rows != r.rows || s.cfg.cols != r.cols)
+        return fail(F110_E_INVALID, "%s: the shaper is off or draws another image size than the ring holds (install the buffer again)", who);
+    memset(&g, 0, sizeof(g));
+    g.frames = r.bufs.frames; g.actions = r.bufs.actions; g.rewards = r.bufs.rewards; g.dones = r.bufs.dones; g.valid = r.bufs.valid;
+    g.count = (long long *)r.bufs.count; g.steps = r.cfg.steps; g.n_envs = h->cfg.num_envs; g.rows = r.rows; g.cols = r.cols;
+    g.action_dim = r.cfg.action_dim; g.dev_err = h->d_err.get();
+    return F110_OK;
+}
+
+extern "C" int f110_replay_update(f110_handle *h, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_replay_update: null handle");
+    ReplayPushArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = replay_ready(h, "f110_replay_update", a.ring)) return rc;
+    const f110_handle::Replay &r = h->replay;
+    if ((uintptr_t)h->shaping.bufs.bitmap % 16) return fail(F110_E_INVALID, "f110_replay_update: the shaper's bitmap must be 16-byte aligned");
+    a.bitmap = h->shaping.bufs.bitmap; a.action_in = r.bufs.action_in; a.total = h->shaping.bufs.total; a.done = (const uint8_t *)h->bufs.done;
+    a.current_time = h->bufs.current_time; a.timestep = h->cfg.timestep; a.chain_start = (const long long *)r.bufs.chain_start;
+    a.t_seen = r.bufs.t_seen; a.last_valid = r.bufs.last_valid;
+    hipLaunchKernelGGL(replay_push_kernel, dim3((unsigned)a.ring.n_envs), dim3(REPLAY_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(replay_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a.ring.count);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_replay_draw(f110_handle *h, uint64_t seed, uint64_t first_draw, int32_t n, int64_t *indices, uint8_t *ok, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_replay_draw: null handle");
+    ReplayDrawArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = replay_ready(h, "f110_replay_draw", a.ring)) return rc;
+    if (n < 0 || !indices || !ok) return fail(F110_E_INVALID, "f110_replay_draw: bad arguments");
+    if (n == 0) return F110_OK;
+    a.seed = seed; a.first = first_draw; a.n = n; a.idx = (long long *)indices; a.ok = ok;
+    hipLaunchKernelGGL(replay_draw_kernel, dim3((unsigned)((n + REPLAY_THREADS - 1) / REPLAY_THREADS)), dim3(REPLAY_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_replay_gather(f110_handle *h, const int64_t *indices, int32_t n, void *s, void *ns, int32_t as_f32, double scale,
+                                  float *a_out, double *r_out, uint8_t *d_out, uint8_t *ok, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_replay_gather: null handle");
+    ReplayGatherArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = replay_ready(h, "f110_replay_gather", a.ring)) return rc;
+    if (n < 0 || !indices || !s || !ns || !a_out || !r_out || !d_out || !ok) return fail(F110_E_INVALID, "f110_replay_gather: bad arguments");
+    if ((uintptr_t)s % 16 || (uintptr_t)ns % 16) return fail(F110_E_INVALID, "f110_replay_gather: s and ns must be 16-byte aligned");
+    if (n == 0) return F110_OK;
+    a.idx = (const long long *)indices; a.n = n;
+    if (as_f32) { a.s32 = (float *)s; a.ns32 = (float *)ns; a.on = 255.0f * (float)scale; }
+    else { a.s8 = (uint8_t *)s; a.ns8 = (uint8_t *)ns; }
+    a.a = a_out; a.r = r_out; a.d = d_out; a.ok = ok;
+    hipLaunchKernelGGL(replay_gather_kernel, dim3((unsigned)n, (unsigned)((a.ring.rows + REPLAY_ROWS - 1) / REPLAY_ROWS), 2), dim3(REPLAY_THREADS), 0,
+                       (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+static int replay_pack_args(const char *who, const void *in, const void *out, int64_t n, int32_t rows, int32_t cols)
+{
+    if (n < 0 || n > 0x7fffffff || rows < 1 || cols < 1 || rows > REPLAY_MAX_DIM || cols > REPLAY_MAX_DIM)
+        return fail(F110_E_INVALID, "%s: n=%lld images of %d x %d pixels (1..%d)", who, (long long)n, rows, cols, REPLAY_MAX_DIM);
+    if (n > 0 && (!in || !out)) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if ((uintptr_t)in % 16 || (uintptr_t)out % 16) return fail(F110_E_INVALID, "%s: both arrays must be 16-byte aligned", who);
+    return F110_OK;
+}
+
+extern "C" int f110_replay_pack(const uint8_t *bitmaps, int64_t n, int32_t rows, int32_t cols, uint64_t *packed, void *stream)
+{
+    if (int rc = replay_pack_args("f110_replay_pack", bitmaps, packed, n, rows, cols)) return rc;
+    if (n == 0) return F110_OK;
+    ReplayPackArgs a;
+    a.bitmaps = bitmaps; a.packed = packed; a.rows = rows; a.cols = cols;
+    hipLaunchKernelGGL(replay_pack_kernel, dim3((unsigned)n), dim3(REPLAY_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_replay_unpack(const uint64_t *packed, int64_t n, int32_t rows, int32_t cols, uint8_t *bitmaps, void *stream)
+{
+    if (int rc = replay_pack_args("f110_replay_unpack", packed, bitmaps, n, rows, cols)) return rc;
+    if (n == 0) return F110_OK;
+    ReplayPackArgs a;
+    a.bitmaps = nullptr; a.packed = const_cast<uint64_t *>(packed); a.rows = rows; a.cols = cols;
+    hipLaunchKernelGGL(replay_unpack_kernel, dim3((unsigned)n, (unsigned)((rows + REPLAY_ROWS - 1) / REPLAY_ROWS)), dim3(REPLAY_THREADS), 0,
+                       (hipStream_t)stream, a, bitmaps);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
 }
 
 // ---------------------------------------------------------------- scan -> bitmap

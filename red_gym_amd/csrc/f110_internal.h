@@ -5,7 +5,7 @@
 //   f110_maps.hip       map installation (host table / occupancy mask -> cell codes, LUTs), device EDT, track mask
 //   f110_noise_abi.hip  lidar noise: slots, ring, generators, per-env mode
 //   f110_step.hip       launch policy of the scan, the step, hipGraphs, measurement aid, function-level entry points
-//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, progress tracker, reward shaper, path follower, scan -> bitmap,
+//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, progress tracker, reward shaper, path follower, replay buffer, scan -> bitmap,
 //                       occupancy grid
 #pragma once
 #include "../../include/f110_hip.h"
@@ -15,6 +15,7 @@
 #include "f110_progress.h"
 #include "f110_shaping.h"
 #include "f110_pathfollow.h"
+#include "f110_replay.h"
 #include "f110_bitmap.h"
 #include "f110_mapgen.h"
 
@@ -228,6 +229,14 @@ struct f110_handle {
         DevBuf<double> d_qp;
         f110_pathfollow_buffers bufs;
     } follow;
+    // replay buffer (f110_replay_install / _bind / _update / _draw / _gather, f110_consumers.hip): the configuration, the image
+    // size of the shaper it was installed behind, and the caller's ring
+    struct Replay {
+        bool on = false, bound = false;
+        f110_replay_config cfg;
+        int rows = 0, cols = 0;
+        f110_replay_buffers bufs;
+    } replay;
     const int32_t *scan_order = nullptr; // launch order of the step's scan (f110_set_scan_order; caller-owned device array) or NULL
     DevBuf<uint32_t> d_err;           // device error word (f110_device_errors)
     std::vector<double> h_side;       // side distances (host copy of d_side)

@@ -1,0 +1,299 @@
+// f110_replay.h -- the replay buffer of the reference's RL consumer (src/SAL.py:447-463 ReplayBuffer, pushed at :1000) on the
+// device: a ring of T step slots behind the shaper.  A FILL image has two values, so a frame is kept as bits -- a row of
+// `cols` pixels is ceil(cols / 64) 64-bit words, bit k of word w = (pixel[64 w + k] == 255), np.packbits(bitorder='little') --
+// and once: next_obs of step t is obs of step t + 1, so T step slots own T + 1 frame slots.  Push number c (the device-side
+// counter `count`) writes frame slot c % (T + 1) and step slot c % T; its transition is (frame c - 1, action, reward, frame c,
+// done).  Nothing here takes a slot by value from the host: every kernel reads `count`, so a captured push replays correctly.
+//   replay_push_kernel     one workgroup per env: 16 pixels per lane in one 16-byte load, reduced to 16 bits in registers, one
+//                          2-byte store per lane -- a wave reads 1 KiB and writes 128 B, both contiguous
+//   replay_advance_kernel  one lane: count += 1, behind the push
+//   replay_draw_kernel     one lane per draw: splitmix64 candidates over the stored transitions, the first valid one wins
+//   replay_gather_kernel   one wave per (sample, frame, 4 rows): bits back to uint8 (4 pixels = one 4-byte store per lane) or fp32
+#pragma once
+#include "f110_kernels.h"
+#include "f110_pathfollow.h"
+
+namespace f110 {
+
+constexpr int BT_REPLAY = BT_PATHFOLLOW + 1; // bounds-checked build: a slot the replay kernels derive from `count`, a drawn index
+constexpr int REPLAY_THREADS = 256;
+constexpr int REPLAY_ROWS = 16;              // rows of a frame one workgroup of the gather unpacks (4 per wave)
+constexpr int REPLAY_MAX_DIM = 16384;        // rows, cols: the kernels count a frame's 16-pixel chunks in 32 bits
+
+__host__ __device__ inline int replay_words(int cols) { return (cols + 63) >> 6; }
+
+// 4 pixels -> 4 bits, bit i = (byte i == 255): a byte is 255 iff its low 7 bits carry into bit 7 and bit 7 is set; the four
+// bits 7 are gathered by one multiply (exponents 8 i + 7 (j + 1) are pairwise distinct: no carries, bits 28..31 = byte 0..3).
+__device__ inline unsigned replay_bits4(unsigned x)
+{
+    const unsigned m = ((x & 0x7f7f7f7fu) + 0x01010101u) & x & 0x80808080u;
+    return ((m >> 7) * 0x10204080u) >> 28;
+}
+__device__ inline unsigned replay_bits16(uint4 v)
+{
+    return replay_bits4(v.x) | (replay_bits4(v.y) << 4) | (replay_bits4(v.z) << 8) | (replay_bits4(v.w) << 12);
+}
+
+// One image [rows, cols] -> [rows, words] as 16-bit pieces, by the `nthr` threads of a workgroup.  Piece u = row * ch + c holds
+// pixels 16 c .. 16 c + 15 of its row (ch = 4 * words; pieces beyond the row are the zero padding).  `img` is 16-byte aligned.
+__device__ inline void replay_pack_image(const uint8_t *__restrict__ img, int rows, int cols, uint16_t *__restrict__ out, int tid, int nthr)
+{
+    const int ch = 4 * replay_words(cols);
+    const int units = rows * ch;
+    if ((cols & 15) == 0) {
+        // rows are whole 16-byte pieces: four independent aligned loads in flight per lane
+        const int full = cols >> 4;
+        const bool dense = full == ch;            // cols a multiple of 64: piece u is bytes 16 u .. of the image
+        for (int u0 = tid; u0 < units; u0 += 4 * nthr) {
+            uint4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int u = u0 + j * nthr;
+                v[j] = make_uint4(0u, 0u, 0u, 0u);
+                if (u < units) {
+                    if (dense) v[j] = *reinterpret_cast<const uint4 *>(img + 16 * (size_t)u);
+                    else {
+                        const int r = u / ch, c = u - r * ch;
+                        if (c < full) v[j] = *reinterpret_cast<const uint4 *>(img + (size_t)r * (size_t)cols + 16 * (size_t)c);
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int u = u0 + j * nthr;
+                if (u < units) out[u] = (uint16_t)replay_bits16(v[j]);
+            }
+        }
+        return;
+    }
+    // a row's byte length is no multiple of 16: its rows start anywhere, whole pieces are read as 16 bytes of alignment 1 and
+    // the row's last piece byte by byte under a mask
+    for (int u = tid; u < units; u += nthr) {
+        const int r = u / ch, c = u - r * ch, col0 = 16 * c;
+        const uint8_t *p = img + (size_t)r * (size_t)cols + (size_t)col0;
+        unsigned bits = 0;
+        if (col0 + 16 <= cols) {
+            uint4 v;
+            __builtin_memcpy(&v, p, 16);
+            bits = replay_bits16(v);
+        } else {
+            for (int k = 0; k < 16 && col0 + k < cols; k++) bits |= (unsigned)(p[k] == 255) << k;
+        }
+        out[u] = (uint16_t)bits;
+    }
+}
+
+// One packed row (NULL: a row of zeros) -> cols pixels of 0 / 255 (uint8) or 0 / `on` (fp32), by the 64 lanes of a wave.  With
+// cols a multiple of 4 a lane writes 4 pixels at once (their bits share a word): 4 bytes, or 16 as fp32.
+__device__ inline void replay_unpack_row(const uint64_t *__restrict__ prow, int cols, uint8_t *__restrict__ orow, int lane)
+{
+    if ((cols & 3) == 0) {
+        for (int c0 = 4 * lane; c0 < cols; c0 += 256) {
+            const unsigned b = prow ? (unsigned)(prow[c0 >> 6] >> (c0 & 63)) & 15u : 0u;
+            // bit i -> byte i (exponents i + 7 j are pairwise distinct: no carries), times 255
+            *reinterpret_cast<unsigned *>(orow + c0) = ((b * 0x00204081u) & 0x01010101u) * 255u;
+        }
+        return;
+    }
+    for (int c = lane; c < cols; c += 64)
+        orow[c] = prow && ((prow[c >> 6] >> (c & 63)) & 1ull) ? (uint8_t)255 : (uint8_t)0;
+}
+__device__ inline void replay_unpack_row(const uint64_t *__restrict__ prow, int cols, float *__restrict__ orow, int lane, float on)
+{
+    if ((cols & 3) == 0) {
+        for (int c0 = 4 * lane; c0 < cols; c0 += 256) {
+            const unsigned b = prow ? (unsigned)(prow[c0 >> 6] >> (c0 & 63)) & 15u : 0u;
+            *reinterpret_cast<float4 *>(orow + c0) = make_float4(b & 1u ? on : 0.0f, b & 2u ? on : 0.0f, b & 4u ? on : 0.0f, b & 8u ? on : 0.0f);
+        }
+        return;
+    }
+    for (int c = lane; c < cols; c += 64)
+        orow[c] = prow && ((prow[c >> 6] >> (c & 63)) & 1ull) ? on : 0.0f;
+}
+
+__device__ inline unsigned long long replay_splitmix64(unsigned long long z)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+struct ReplayRing {                 // what the three kernels share
+    uint64_t *frames;               // [steps + 1, n_envs, rows, words]
+    float *actions;                 // [steps, n_envs, action_dim]
+    double *rewards;                // [steps, n_envs]
+    uint8_t *dones, *valid;         // [steps, n_envs]
+    long long *count;               // [1] pushes made
+    long long steps;
+    int n_envs, rows, cols, action_dim;
+    uint32_t *dev_err;
+    __device__ size_t frame_words() const { return (size_t)rows * (size_t)replay_words(cols); }
+    __device__ uint64_t *frame(long long fs, int env) const { return frames + ((size_t)fs * (size_t)n_envs + (size_t)env) * frame_words(); }
+};
+
+struct ReplayPushArgs {
+    ReplayRing ring;
+    const uint8_t *bitmap;          // [n_envs, rows, cols] the shaper's image of the scan the step returned
+    const float *action_in;         // [n_envs, action_dim]
+    const double *total;            // [n_envs] the shaper's reward
+    const uint8_t *done;            // [n_envs]
+    const double *current_time;     // [n_envs]
+    double timestep;
+    const long long *chain_start;   // [1] the push number that has no previous frame (install, load_state_dict)
+    double *t_seen;                 // [n_envs] clock at the env's previous push (< 0: none)
+    uint8_t *last_valid;            // [n_envs] valid as this push decided it
+};
+
+struct ReplayDrawArgs {
+    ReplayRing ring;
+    unsigned long long seed, first; // draw j of this launch is draw number first + j of the stream `seed`
+    int n;
+    long long *idx;                 // [n] step slot * n_envs + env, or -1
+    uint8_t *ok;                    // [n]
+};
+
+struct ReplayGatherArgs {
+    ReplayRing ring;
+    const long long *idx;           // [n]
+    int n;
+    uint8_t *s8, *ns8;              // [n, rows, cols], or
+    float *s32, *ns32;              // [n, 1, rows, cols] = pixel * scale
+    float on;                       // 255.0f * scale
+    float *a;                       // [n, action_dim]
+    double *r;                      // [n]
+    uint8_t *d, *ok;                // [n]
+};
+
+struct ReplayPackArgs {
+    const uint8_t *bitmaps;         // [n, rows, cols]
+    uint64_t *packed;               // [n, rows, words]
+    int rows, cols;
+};
+
+#if defined(F110_UNIT_CONSUMERS)
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_push_kernel(ReplayPushArgs a)
+{
+    const ReplayRing &g = a.ring;
+    const int env = blockIdx.x, tid = threadIdx.x;
+    const long long count = *g.count;
+    F110_BCHK(count >= 0, BT_REPLAY, g.dev_err);
+    if (count < 0) return;
+    const long long fs = count % (g.steps + 1), ss = count % g.steps;
+    F110_BCHK(fs >= 0 && fs <= g.steps && ss >= 0 && ss < g.steps, BT_REPLAY, g.dev_err);
+    replay_pack_image(a.bitmap + (size_t)env * (size_t)g.rows * (size_t)g.cols, g.rows, g.cols,
+                      reinterpret_cast<uint16_t *>(g.frame(fs, env)), tid, REPLAY_THREADS);
+    const size_t cell = (size_t)ss * (size_t)g.n_envs + (size_t)env;
+    for (int k = tid; k < g.action_dim; k += REPLAY_THREADS)
+        g.actions[cell * (size_t)g.action_dim + (size_t)k] = a.action_in[(size_t)env * (size_t)g.action_dim + (size_t)k];
+    if (tid == 0) {
+        // the clock idiom of f110_shaping.h: an env's clock reads exactly `timestep` iff the last step that touched it was
+        // its reset (terminal frame -> spawn frame is no transition); a clock that stands still was not stepped by the call
+        const double now = a.current_time[env], seen = a.t_seen[env];
+        const uint8_t v = count > *a.chain_start && now != a.timestep && now != seen ? 1 : 0;
+        g.rewards[cell] = a.total[env];
+        g.dones[cell] = a.done[env] != 0 ? 1 : 0;
+        g.valid[cell] = v;
+        a.last_valid[env] = v;
+        a.t_seen[env] = now;
+    }
+}
+
+static __global__ void replay_advance_kernel(long long *count)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) *count += 1;
+}
+
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_draw_kernel(ReplayDrawArgs a)
+{
+    const ReplayRing &g = a.ring;
+    const int i = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (i >= a.n) return;
+    const long long count = *g.count;
+    const long long stored = count < 0 ? 0 : (count < g.steps ? count : g.steps);
+    const unsigned long long total = (unsigned long long)stored * (unsigned long long)g.n_envs;
+    long long pick = -1;
+    if (total > 0) {
+        const unsigned long long j = a.first + (unsigned long long)i;
+        for (int k = 0; k < F110_REPLAY_TRIES; k++) {
+            const unsigned long long z = replay_splitmix64(a.seed + 0x9E3779B97F4A7C15ull * (1ull + j * (unsigned long long)F110_REPLAY_TRIES + (unsigned long long)k));
+            const unsigned long long cand = __umul64hi(z, total);
+            const long long age = (long long)(cand / (unsigned long long)g.n_envs), env = (long long)(cand % (unsigned long long)g.n_envs);
+            const long long slot = (count - 1 - age) % g.steps;
+            F110_BCHK(age < stored && slot >= 0 && slot < g.steps, BT_REPLAY, g.dev_err);
+            const long long id = slot * g.n_envs + env;
+            if (g.valid[id]) { pick = id; break; }
+        }
+    }
+    a.idx[i] = pick;
+    a.ok[i] = pick >= 0 ? 1 : 0;
+}
+
+// grid (n, ceil(rows / REPLAY_ROWS), 2): z = 0 the transition's frame before (s), z = 1 its frame after (ns)
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_gather_kernel(ReplayGatherArgs a)
+{
+    const ReplayRing &g = a.ring;
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long id = a.idx[i], count = *g.count;
+    bool ok = id >= 0 && id < g.steps * g.n_envs && count >= 1;
+    long long c = 0;
+    int env = 0;
+    if (ok) {
+        const long long slot = id / g.n_envs;
+        env = (int)(id - slot * g.n_envs);
+        ok = slot <= count - 1 && g.valid[id] != 0;
+        if (ok) {
+            c = count - 1 - (count - 1 - slot) % g.steps;   // the newest push that went to this step slot
+            F110_BCHK(c >= 1 && c % g.steps == slot, BT_REPLAY, g.dev_err);
+            ok = c >= 1;                                    // (push 0 has no previous frame and is never valid)
+        }
+    }
+    const uint64_t *frame = nullptr;
+    if (ok) {
+        const long long fs = (blockIdx.z ? c : c - 1) % (g.steps + 1);
+        F110_BCHK(fs >= 0 && fs <= g.steps, BT_REPLAY, g.dev_err);
+        frame = g.frame(fs, env);
+    }
+    const int W = replay_words(g.cols);
+    const size_t img = (size_t)i * (size_t)g.rows * (size_t)g.cols;
+    uint8_t *o8 = blockIdx.z ? a.ns8 : a.s8;
+    float *o32 = blockIdx.z ? a.ns32 : a.s32;
+    for (int rr = 0; rr < REPLAY_ROWS / 4; rr++) {
+        const int row = blockIdx.y * REPLAY_ROWS + wave * (REPLAY_ROWS / 4) + rr;
+        if (row >= g.rows) break;
+        const uint64_t *prow = frame ? frame + (size_t)row * (size_t)W : nullptr;
+        if (o8) replay_unpack_row(prow, g.cols, o8 + img + (size_t)row * (size_t)g.cols, lane);
+        else replay_unpack_row(prow, g.cols, o32 + img + (size_t)row * (size_t)g.cols, lane, a.on);
+    }
+    if (blockIdx.y == 0 && blockIdx.z == 0) {
+        for (int k = tid; k < g.action_dim; k += REPLAY_THREADS)
+            a.a[(size_t)i * (size_t)g.action_dim + (size_t)k] = ok ? g.actions[(size_t)id * (size_t)g.action_dim + (size_t)k] : 0.0f;
+        if (tid == 0) {
+            a.r[i] = ok ? g.rewards[id] : 0.0;
+            a.d[i] = ok ? g.dones[id] : (uint8_t)0;
+            a.ok[i] = ok ? 1 : 0;
+        }
+    }
+}
+
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_pack_kernel(ReplayPackArgs a)
+{
+    const size_t i = blockIdx.x;
+    replay_pack_image(a.bitmaps + i * (size_t)a.rows * (size_t)a.cols, a.rows, a.cols,
+                      reinterpret_cast<uint16_t *>(a.packed + i * (size_t)a.rows * (size_t)replay_words(a.cols)), threadIdx.x, REPLAY_THREADS);
+}
+
+// grid (n, ceil(rows / REPLAY_ROWS))
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_unpack_kernel(ReplayPackArgs a, uint8_t *out)
+{
+    const size_t i = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = replay_words(a.cols);
+    for (int rr = 0; rr < REPLAY_ROWS / 4; rr++) {
+        const int row = blockIdx.y * REPLAY_ROWS + wave * (REPLAY_ROWS / 4) + rr;
+        if (row >= a.rows) break;
+        replay_unpack_row(a.packed + (i * (size_t)a.rows + (size_t)row) * (size_t)W, a.cols,
+                          out + (i * (size_t)a.rows + (size_t)row) * (size_t)a.cols, lane);
+    }
+}
+#endif
+
+} // namespace f110

@@ -1,0 +1,201 @@
+"""Host side of the replay buffer (csrc/f110_replay.h): the ReplayBuffer of the reference's RL consumer (src/SAL.py:447-463)
+and the `replay_buffer.push(obs, action, reward, next_obs, done)` of its training loop (:996-1001), kept on the device behind
+the reward shaper.  A FILL image has two values, so a frame is stored as bits (8 KiB instead of 64 for 256 x 256), and once:
+next_obs of step t is obs of step t + 1.  DEFAULTS are SAL's numbers (capacity 1 000 000 transitions, the raw action's 16
+values).  There is no CPU path: frames are packed, drawn and unpacked by libf110_hip.so's replay kernels."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .consumer import Consumer
+
+DEFAULTS = dict(capacity=1000000, steps=None, action_dim=16)
+TRIES = _lib.F110_REPLAY_TRIES
+
+
+def make_config(num_envs=1, **cfg):
+    """An f110_replay_config from keyword options; the missing ones take DEFAULTS.  `capacity` counts transitions as the
+    reference's does: steps = capacity // num_envs step slots, unless `steps` says so itself."""
+    unknown = set(cfg) - set(DEFAULTS)
+    if unknown:
+        raise TypeError('unknown replay option(s): %s' % ', '.join(sorted(unknown)))
+    c = _lib.ReplayConfig()
+    steps = cfg.get('steps')
+    if steps is None:
+        capacity = cfg.get('capacity')
+        steps = int(DEFAULTS['capacity'] if capacity is None else capacity) // max(int(num_envs), 1)
+    c.steps = max(min(int(steps), 2 ** 31 - 1), -1)
+    c.action_dim = max(min(int(cfg.get('action_dim', DEFAULTS['action_dim'])), 2 ** 31 - 1), -1)
+    return c
+
+
+def validate(num_envs=1, shaping=None, **cfg):
+    """f110_replay_validate (host only, no device): ValueError for what an install would refuse.  `shaping`: the options of the
+    shaper the buffer records (a dict for red_gym_amd.shaping.make_config), None = shaping is off."""
+    from .shaping import make_config as shaping_config
+    sc = None if shaping is None else C.byref(shaping_config(**shaping))
+    _lib.check(_lib.load().f110_replay_validate(C.byref(make_config(num_envs, **cfg)), sc, int(num_envs)))
+
+
+def words(cols):
+    return (int(cols) + 63) // 64
+
+
+def pack_bitmaps(bitmaps):
+    """f110_replay_pack: [n, rows, cols] uint8 device tensor -> [n, rows, ceil(cols / 64)] int64 (the bits of uint64 words: bit
+    k of word w = (pixel[64 w + k] == 255), tail bits 0)."""
+    lib = _lib.load()
+    n, rows, cols = bitmaps.shape
+    dev = bitmaps.device
+    src = bitmaps.to(torch.uint8).contiguous()
+    out = torch.empty((n, rows, words(cols)), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.f110_replay_pack(src.data_ptr(), n, rows, cols, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        torch.cuda.current_stream(dev).synchronize()   # the contiguous copy above may be a temporary
+    return out
+
+
+def unpack_bitmaps(packed, cols):
+    """f110_replay_unpack: [n, rows, ceil(cols / 64)] int64 device tensor -> [n, rows, cols] uint8 of 0 / 255."""
+    lib = _lib.load()
+    n, rows, w = packed.shape
+    if w != words(cols):
+        raise ValueError('%d words per row do not hold %d pixels' % (w, cols))
+    dev = packed.device
+    src = packed.to(torch.int64).contiguous()
+    out = torch.empty((n, rows, int(cols)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.f110_replay_unpack(src.data_ptr(), n, rows, int(cols), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        torch.cuda.current_stream(dev).synchronize()
+    return out
+
+
+class ReplayBuffer(Consumer):
+    """The replay buffer of one Engine (f110_replay_install / _bind / _update / _draw / _gather).  The ring lives in `buf`:
+    frames [T + 1, B, rows, words] int64 (bit-packed), actions [T, B, action_dim] fp32, rewards [T, B] fp64, dones and valid
+    [T, B] uint8, count and chain_start [1] int64, t_seen [B] fp64, last_valid [B] uint8 and action_in [B, action_dim] fp32 (what
+    the next push stores: F110VecEnv.replay_action).  A transition is named by index = step slot * B + env.  The ring is no part
+    of state_dict(): save() / load() hand it over explicitly."""
+    NAME = 'replay'
+    INFO = {'replay_count': 'count', 'replay_valid': 'last_valid'}
+    STATE = {}
+    RING = ('frames', 'actions', 'rewards', 'dones', 'valid', 'count', 'chain_start', 't_seen')
+    cfg, rows, cols, _draws = None, 0, 0, 0
+
+    steps = property(lambda self: self.cfg.steps)
+    action_dim = property(lambda self: self.cfg.action_dim)
+
+    def install(self, **cfg):
+        """`cfg`: options of DEFAULTS.  An install allocates a new, empty ring for the image size of the shaper as it is
+        installed now.  TypeError for an unknown option, ValueError for what the library refuses (the shaper is off)."""
+        eng = self.eng
+        c = make_config(eng.B, **cfg)
+        _lib.check(eng.lib.f110_replay_install(eng._h, C.byref(c)))
+        rows, cols = eng.shaper.cfg.rows, eng.shaper.cfg.cols
+        T, B, ad = c.steps, eng.B, c.action_dim
+        self.buf, self.info = None, {}          # (the old ring goes before the new one is allocated)
+        try:
+            with torch.cuda.device(eng.device):
+                z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=eng.device)  # noqa: E731
+                buf = {'frames': z((T + 1, B, rows, words(cols)), torch.int64), 'actions': z((T, B, ad), torch.float32),
+                       'rewards': z((T, B), torch.float64), 'dones': z((T, B), torch.uint8), 'valid': z((T, B), torch.uint8),
+                       'count': z((1,), torch.int64), 'chain_start': z((1,), torch.int64), 't_seen': z((B,), torch.float64),
+                       'last_valid': z((B,), torch.uint8), 'action_in': z((B, ad), torch.float32)}
+                buf['t_seen'].fill_(-1.0)
+                self._bind(buf, _lib.ReplayBuffers)
+        except Exception:
+            eng.lib.f110_replay_install(eng._h, None)
+            self.on = False
+            raise
+        self.cfg, self.rows, self.cols, self.on, self._draws = c, rows, cols, True, 0
+
+    def remove(self):
+        """No launch, no info key remains and the ring is freed."""
+        if self.on:
+            _lib.check(self.eng.lib.f110_replay_install(self.eng._h, None))
+            torch.cuda.synchronize(self.eng.device)   # an enqueued push may still write the ring
+        self.cfg, self.on, self.buf, self.info = None, False, None, {}
+
+    def restart(self):
+        """Breaks the chain of frames: the next push stores a frame and an invalid transition; what is stored stays."""
+        self.buf['chain_start'].copy_(self.buf['count'])
+        self.buf['t_seen'].fill_(-1.0)
+
+    def on_load_state_dict(self, sd):
+        self.restart()
+
+    def save(self):
+        """The ring and its counter as a dict of new tensors (gigabytes at the reference's capacity)."""
+        return {k: self.buf[k].clone() for k in self.RING}
+
+    def load(self, d):
+        """Restores what save() returned into a ring of the same shape; ValueError otherwise.  The chain of frames is restored
+        with it: if the envs are not in the state they had at save(), call restart() (load_state_dict does)."""
+        for k in self.RING:
+            if k not in d or tuple(d[k].shape) != tuple(self.buf[k].shape):
+                raise ValueError('replay: the saved ring does not fit (%s)' % k)
+        for k in self.RING:
+            self.buf[k].copy_(d[k])
+
+    def __len__(self):
+        """Valid transitions held (one small reduction and one synchronisation: not for the step path)."""
+        return int(self.buf['valid'].sum().item()) if self.on else 0
+
+    def _seed(self, seed):
+        if seed is None:
+            seed = self.eng.seed
+            if seed is None:
+                seed = 0
+        return int(seed) & (2 ** 64 - 1)
+
+    def draw(self, n, seed=None):
+        """f110_replay_draw: (indices [n] int64, ok [n] uint8) of n draws, no synchronisation.  The draw counter moves on by n."""
+        eng = self.eng
+        idx = torch.empty((int(n),), dtype=torch.int64, device=eng.device)
+        ok = torch.empty((int(n),), dtype=torch.uint8, device=eng.device)
+        with torch.cuda.device(eng.device):
+            _lib.check(eng.lib.f110_replay_draw(eng._h, self._seed(seed), self._draws & (2 ** 64 - 1), int(n), idx.data_ptr(), ok.data_ptr(),
+                                                eng._stream()))
+        self._draws += int(n)
+        return idx, ok
+
+    def sample_at(self, indices, dtype=torch.uint8, scale=1.0):
+        """f110_replay_gather for the transitions `indices` [n] (step slot * B + env; -1 or an invalid one: zeros and ok = 0).
+        Returns (s, a, r, ns, d, ok): s and ns uint8 [n, rows, cols], or with dtype=torch.float32 fp32 [n, 1, rows, cols] =
+        pixel * scale; a [n, action_dim] fp32, r [n] fp64, d [n] and ok [n] uint8.  Device tensors, no synchronisation."""
+        if not self.on:
+            raise ValueError('replay: the buffer is off (record_replay())')
+        if dtype not in (torch.uint8, torch.float32):
+            raise ValueError('replay: dtype must be torch.uint8 or torch.float32')
+        eng = self.eng
+        idx = torch.as_tensor(indices).to(device=eng.device, dtype=torch.int64).contiguous().reshape(-1)
+        n = idx.shape[0]
+        f32 = dtype == torch.float32
+        shape = (n, 1, self.rows, self.cols) if f32 else (n, self.rows, self.cols)
+        s, ns = torch.empty(shape, dtype=dtype, device=eng.device), torch.empty(shape, dtype=dtype, device=eng.device)
+        a = torch.empty((n, self.cfg.action_dim), dtype=torch.float32, device=eng.device)
+        r = torch.empty((n,), dtype=torch.float64, device=eng.device)
+        d, ok = torch.empty((n,), dtype=torch.uint8, device=eng.device), torch.empty((n,), dtype=torch.uint8, device=eng.device)
+        with torch.cuda.device(eng.device):
+            _lib.check(eng.lib.f110_replay_gather(eng._h, idx.data_ptr(), n, s.data_ptr(), ns.data_ptr(), int(f32), float(scale),
+                                                  a.data_ptr(), r.data_ptr(), d.data_ptr(), ok.data_ptr(), eng._stream()))
+        self._keep = idx   # (kept until the next call: the stream may not have read it yet)
+        return s, a, r, ns, d, ok
+
+    def sample(self, batch_size, seed=None, dtype=torch.uint8, scale=1.0):
+        """batch_size transitions drawn uniformly over the valid ones, as sample_at returns them.  `seed` defaults to the
+        env's; the host keeps the draw counter, so two calls never reuse draws.  A draw that found no valid transition in TRIES
+        attempts (an empty buffer is one case) has ok = 0 and zeros."""
+        if not self.on:
+            raise ValueError('replay: the buffer is off (record_replay())')
+        idx, _ = self.draw(batch_size, seed)
+        return self.sample_at(idx, dtype, scale)
+
+    def bytes_held(self):
+        return sum(self.buf[k].numel() * self.buf[k].element_size() for k in ('frames', 'actions', 'rewards', 'dones', 'valid'))
+
+    def bytes_raw(self):
+        """What the same transitions cost as the reference stores them: two raw uint8 images, the action, reward and done."""
+        T, B = self.cfg.steps, self.eng.B
+        return T * B * (2 * self.rows * self.cols + 4 * self.cfg.action_dim + 8 + 1)

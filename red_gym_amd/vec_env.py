@@ -70,7 +70,8 @@ class F110VecEnv(object):
             self._obs['scans_f64'] = t['scans_f64']
         self._reward = torch.full((self.num_envs,), float(timestep), dtype=torch.float64, device=self.device)
         self._g_actions, self._graphs, self._lg = None, [], None   # capture_step / build_step_graph
-        self.consumers = (self.eng.tracker, self.eng.shaper, self.eng.follower)   # track_progress, shape_rewards, follow_paths: the ones that are `on` run
+        # track_progress, shape_rewards, follow_paths, record_replay: the ones that are `on` run, in this order
+        self.consumers = (self.eng.tracker, self.eng.shaper, self.eng.follower, self.eng.replay)
 
     def _result(self):
         t = self.eng.t
@@ -86,7 +87,8 @@ class F110VecEnv(object):
         return self._obs, self._reward if reward is None else reward, done, info
 
     def _after_step(self):
-        """What follows every step on the same stream: the progress tracker's update, the reward shaper's, the path follower's."""
+        """What follows every step on the same stream: the progress tracker's update, the reward shaper's, the path follower's,
+        the replay buffer's push."""
         for c in self.consumers:
             if c.on:
                 c.update()
@@ -161,11 +163,15 @@ class F110VecEnv(object):
         A reset (masked, whole batch or autoreset) pays 0 in the step that performs it and restarts from the reset pose.
         shape_rewards(False) switches it off: no launch, no info key, no state_dict key remains and the reward is the
         constant again.  Switched on in the middle of a run, the first update pays no progress and reads the image of the
-        scans as they stand."""
+        scans as they stand.  The replay buffer records the shaper's image and reward: switching the shaper off, or installing it
+        again with another image size, while record_replay() is on removes the replay buffer too (its ring is freed)."""
         if enable:
             self.eng.shaper.install(**cfg)
         else:
             self.eng.shaper.remove()
+        rp, sh = self.eng.replay, self.eng.shaper
+        if rp.on and (not sh.on or (sh.cfg.rows, sh.cfg.cols) != (rp.rows, rp.cols)):
+            rp.remove()
 
     # ------------------------------------------------------------------ path actions
     def follow_paths(self, enable=True, **cfg):
@@ -201,7 +207,46 @@ class F110VecEnv(object):
         if raw_actions.dtype != torch.float64 or raw_actions.device != self.device or not raw_actions.is_contiguous():
             raw_actions = raw_actions.to(device=self.device, dtype=torch.float64).contiguous()
         self.eng.follower.act(raw_actions, out)
+        rp = self.eng.replay
+        if rp.on and rp.action_dim == raw_actions.shape[1]:
+            rp.buf['action_in'].copy_(raw_actions)   # what the next push stores (one capturable copy)
         return out.view(self.num_envs, self.num_agents, 2)
+
+    # ------------------------------------------------------------------ replay buffer
+    def record_replay(self, capacity=None, steps=None, action_dim=16):
+        """Switches the replay buffer on: the ReplayBuffer of the reference's RL consumer (src/SAL.py:447-463) and the push of
+        its training loop (:996-1001) on the GPU.  `capacity` counts transitions as the reference's does: the ring has steps =
+        capacity // num_envs step slots for all envs (or give `steps` itself; at least 2).  From then on reset, step, step_graph
+        and step_lib_graph push behind the shaper: the transition of env e at step t is (F[t-1, e], a[t, e], r[t, e], F[t, e],
+        done[t, e]) with F the shaper's lidar_bitmap as the step left it (stored bit-packed and once: 1/16 of the raw bytes), a =
+        replay_action as it stands at the push, r the shaper's total reward.  A transition is invalid and never sampled when
+        the step was the env's reset (masked, whole batch or autoreset: terminal frame and spawn frame are no transition),
+        when the env was not stepped by the call, or when there is no previous frame (the first push after this call or after
+        load_state_dict).  The terminal step itself is valid.  Eviction is FIFO by step, like the reference's deque.  `info`
+        also holds replay_count [1] int64 (pushes made) and replay_valid [B] uint8 (the push just made) -- views.  The ring is
+        not part of state_dict().  env.replay.sample(batch_size) returns (s, a, r, ns, d, ok) on the device.
+        record_replay(None) or record_replay(False) switches it off and frees the ring: no launch, no allocation, no info key
+        remains.  ValueError while shape_rewards() is off; switching the shaper off, or installing it again with another image
+        size, removes the buffer too."""
+        if not capacity and steps is None:
+            self.eng.replay.remove()
+            return
+        if not self.eng.shaper.on:
+            raise ValueError('record_replay: the reward shaper is off (shape_rewards())')
+        self.eng.replay.install(capacity=None if capacity is True else capacity, steps=steps, action_dim=action_dim)
+
+    @property
+    def replay(self):
+        """The Engine's ReplayBuffer (sample, sample_at, len(), save, load)."""
+        return self.eng.replay
+
+    @property
+    def replay_action(self):
+        """[B, action_dim] fp32: what the next push stores as the action.  path_actions(raw) fills it while the buffer is on
+        (when action_dim is raw's width); users of another policy write into it themselves."""
+        if not self.eng.replay.on:
+            raise ValueError('replay_action: the replay buffer is off (record_replay())')
+        return self.eng.replay.buf['action_in']
 
     # ------------------------------------------------------------------ checkpoint / resume
     _STATE_KEYS = ('state', 'steer_buf', 'steer_cnt', 'noise_step', 'spawn', 'start_rot', 'near_start', 'toggles',
@@ -220,12 +265,13 @@ class F110VecEnv(object):
     def load_state_dict(self, sd):
         """While tracking is on the checkpoint's progress, s_prev and seen are restored with it; one taken without them
         starts every car's progress anew.  Likewise the shaper's prev_xy, t_seen and bitmap while shaping is on; without
-        them the shaper restarts: the next update pays no progress and reads the image of the restored scans."""
+        them the shaper restarts: the next update pays no progress and reads the image of the restored scans.  The replay
+        buffer's ring is no part of a checkpoint: what it holds stays, and the next push stores a frame and an invalid transition."""
         theirs = {k for c in self.consumers for k in c.STATE}
         self.eng.load_state({k: v for k, v in sd.items() if k not in theirs})
         for c in self.consumers:
             if c.on:
-                c.load(sd)
+                c.on_load_state_dict(sd)
 
     # ------------------------------------------------------------------ hipGraph replay
     def capture_step(self, policy=None, copies=1):
