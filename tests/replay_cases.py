@@ -49,6 +49,79 @@ def edge_images(rows, cols):
     return np.stack(out)
 
 
+def random_images(rows, cols, n=7, seed=0):
+    """n images of arbitrary bytes, 30 % of the pixels 255; every image holds 254 and 127 where it has the room (neither is a
+    set bit)."""
+    rng = np.random.default_rng([rows, cols, n, seed])
+    a = rng.integers(0, 256, (n, rows, cols)).astype(np.uint8)
+    a[rng.uniform(size=a.shape) < 0.3] = 255
+    flat = a.reshape(n, -1)
+    if flat.shape[1] >= 2:
+        flat[:, flat.shape[1] // 2] = 254
+        flat[:, flat.shape[1] // 2 - 1] = 127
+    return a
+
+
+# ---------------------------------------------------------------------------------------------- the code paths a size selects
+REPLAY_THREADS, REPLAY_ROWS = 256, 16      # csrc/f110_replay.h
+
+# every path of replay_pack_image / replay_unpack_row / the gather grid, see paths() and test_replay_cpu.py
+SHAPES = [(3, 64), (75, 64), (5, 128), (75, 320),                                                       # dense
+          (17, 16), (33, 48), (16, 96), (224, 224), (20, 272),                                          # aligned
+          (84, 84), (1, 17), (15, 15), (10, 65), (12, 255), (9, 257), (31, 260), (7, 513), (40, 1028)]  # bytewise
+
+
+def paths(rows, cols):
+    """What csrc/f110_replay.h does with an image of rows x cols, restated from its arithmetic.  pack: the branch of
+    replay_pack_image ('dense': cols a multiple of 64, 'aligned': of 16, 'bytewise': the rest), the passes of its loop over the
+    rows * 4 * words 16-bit pieces (a workgroup takes 4 * 256 per pass in the first two branches, 256 in the third) and whether
+    the last pass is a partial one; unpack: the form of replay_unpack_row ('vec4': cols a multiple of 4, 4 pixels per lane and
+    256 per pass; 'scalar': 64 per pass) and its passes; row_blocks: the gather's and the unpack's grid.y."""
+    units = rows * 4 * words(cols)
+    if cols % 16 == 0:
+        branch, per_pass = ('dense' if cols % 64 == 0 else 'aligned'), 4 * REPLAY_THREADS
+    else:
+        branch, per_pass = 'bytewise', REPLAY_THREADS
+    form, per_row_pass = ('vec4', 4 * 64) if cols % 4 == 0 else ('scalar', 64)
+    return dict(pack=branch, pack_passes=-(-units // per_pass), pack_last_partial=units % per_pass != 0, unpack=form,
+                unpack_passes=-(-cols // per_row_pass), row_blocks=-(-rows // REPLAY_ROWS))
+
+
+# the sizes the ring itself is run at (tests/test_gpu_replay.py): every pack branch and both unpack forms with one pass and with
+# several, the row counts around a gather block
+RING_SHAPES = [(3, 64), (75, 320), (17, 16), (16, 96), (224, 224), (20, 272), (84, 84), (1, 17), (15, 15), (10, 65), (9, 257), (40, 1028)]
+
+
+def scripted_pushes(rows, cols, B, T, action_dim, timestep):
+    """The inputs of 2 T + 3 pushes the test writes itself (B >= 5), a list of dicts: frame [B, rows, cols] uint8 (40 % of the
+    pixels 255, the rest arbitrary bytes; another one per env and push), action [B, action_dim] fp32 (arange-distinct over push,
+    env and component), reward [B] fp64, done [B] uint8 and clock [B] fp64.  Every clock advances by `timestep` per push, but env
+    1 stands still at push 3 (not stepped: invalid) and env 2 reads exactly `timestep` at push 5 (its reset: invalid) after its
+    done at push 4; env 4 is done at push 1 and env 0 at push 2 T + 1."""
+    rng = np.random.default_rng([rows, cols, B, T, action_dim])
+    clock = 0.37 + 0.11 * np.arange(B)
+    out = []
+    for k in range(2 * T + 3):
+        frame = rng.integers(0, 255, (B, rows, cols)).astype(np.uint8)
+        frame[rng.uniform(size=frame.shape) < 0.4] = 255
+        step = np.full(B, float(timestep))
+        if k == 3:
+            step[1] = 0.0
+        clock = clock + step
+        if k == 5:
+            clock[2] = float(timestep)
+        done = np.zeros(B, np.uint8)
+        done[[e for e, at in ((2, 4), (4, 1), (0, 2 * T + 1)) if at == k]] = 1
+        action = (np.arange(B * action_dim).reshape(B, action_dim) + 10000.0 * k).astype(np.float32)
+        out.append(dict(frame=frame, action=action, reward=rng.normal(size=B) * 10.0 ** rng.integers(-3, 4, B), done=done, clock=clock.copy()))
+    return out
+
+
+def binary(frame):
+    """What a stored frame reads back as: 255 where the pixel is 255, 0 elsewhere."""
+    return np.where(np.asarray(frame) == 255, 255, 0).astype(np.uint8)
+
+
 def splitmix64(z):
     z &= M64
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64

@@ -23,12 +23,15 @@ def _packed_u64(t):
     return np.ascontiguousarray(_np(t)).view(np.uint64)
 
 
-@pytest.mark.parametrize('rows,cols,group', [(256, 256, 'a'), (75, 100, 'b'), (40, 300, 'c'), (3, 1, None)])
+@pytest.mark.parametrize('rows,cols,group', [(256, 256, 'a'), (75, 100, 'b'), (40, 300, 'c'), (3, 1, None)] + [s + (None,) for s in rc.SHAPES])
 def test_pack_and_unpack_equal_numpy(golden, rows, cols, group):
-    """f110_replay_pack / _unpack `==` np.packbits(bitorder='little') on 5 FILL images of g16 and on the edge images."""
+    """f110_replay_pack / _unpack `==` np.packbits(bitorder='little') on 5 FILL images of g16, on the edge images and on 7
+    images of arbitrary bytes (a batch that is neither one image nor a multiple of 4), at the sizes of g16 and at every size of
+    rc.SHAPES: each branch of replay_pack_image and each form of replay_unpack_row with one pass and with several."""
     import torch
     from red_gym_amd import replay
-    batches = [rc.edge_images(rows, cols)]
+    batches = [rc.edge_images(rows, cols), rc.random_images(rows, cols)]
+    assert batches[1].shape[0] == 7
     if group is not None:
         imgs = sc.unpack_images(golden('g16_shaping.npz'), group)
         assert imgs.shape[1:] == (rows, cols)
@@ -58,8 +61,9 @@ def _assert_batch(got, want, what):
 def test_closed_loop_equals_mirror_through_resets(assets, rows, cols):
     """6 envs (every fourth spawned across the track and driven at the wall), T = 4, 60 steps with autoreset, random raw
     actions through path_actions and a masked reset of half the envs in the middle: after every step replay_valid `==` the
-    mirror's decision, every 7 steps sample_at(all T * B indices) `==` the mirror.  (Time step 0.025 s: from a standing start
-    a car needs about a second to reach the wall across the track, and the run has 60 steps.)"""
+    mirror's decision, every 7 steps sample_at(all T * B indices) `==` the mirror -- and what is compared there holds something:
+    every stored s has pixels of both values, and s != ns for at least half of the valid transitions.  (Time step 0.025 s: from
+    a standing start a car needs about a second to reach the wall across the track, and the run has 60 steps.)"""
     import torch
     from red_gym_amd import workload
     B, T, AD = 6, 4, 16
@@ -105,8 +109,15 @@ def test_closed_loop_equals_mirror_through_resets(assets, rows, cols):
             autoresets += int((clock == env.timestep).sum())
             assert not valid[clock == env.timestep].any()
         if k % 7 == 6 or k == 59:
-            _assert_batch(env.replay.sample_at(all_idx), mirror.at(range(T * B)), 'after step %d' % k)
+            want = mirror.at(range(T * B))
+            _assert_batch(env.replay.sample_at(all_idx), want, 'after step %d' % k)
             assert len(env.replay) == len(mirror)
+            # what is compared holds something: every stored s has both values, and most transitions change the image
+            held = np.flatnonzero(want[5])
+            moved = sum(bool((want[0][i] != want[3][i]).any()) for i in held)
+            both = sum(bool((want[0][i] == 0).any() and (want[0][i] == 255).any()) for i in held)
+            print('after step %d: %d valid, s != ns in %d, s holds 0 and 255 in %d' % (k, held.size, moved, both))
+            assert held.size > 0 and 2 * moved >= held.size and both == held.size
             checks += 1
     print('autoresets: %d, pushes: %d, valid held: %d, terminal transitions held: %d'
           % (autoresets, mirror.count, len(mirror), int(mirror.at(range(T * B))[4].sum())))
@@ -302,5 +313,148 @@ def test_switching_off_save_load_and_checkpoints(assets):
     assert len(env.replay) == n_before - int(_np(saved['valid'])[7 % 4].sum())       # only the evicted step slot's are gone
     _, _, _, info = env.step(pool[7])
     assert _np(info['replay_valid']).any()
+    assert env.eng.device_errors() == 0
+    env.close()
+
+
+@pytest.mark.parametrize('rows,cols,action_dim', [s + (16,) for s in rc.RING_SHAPES] + [(3, 64, 300)])
+def test_ring_equals_mirror_on_scripted_frames(assets, rows, cols, action_dim):
+    """The push itself (env.eng.replay.kernel()) on inputs the test writes into the buffers it reads -- the shaper's bitmap and
+    total, the engine's clock and done, replay_action -- at the sizes of rc.RING_SHAPES: 5 envs, T = 3, 2 T + 3 pushes of
+    rc.scripted_pushes (frames of arbitrary bytes that differ per env and push, a clock that stands still, a reset, terminal
+    steps).  After every push last_valid, the counter and sample_at(all T * B indices) as uint8 and as fp32 at scales 1 and
+    1 / 255 `==` the mirror.  action_dim = 300 runs the action loops of push and gather beyond one pass of the workgroup."""
+    import torch
+    B, T = 5, 3
+    env = _env(assets, B, autoreset=True)
+    env.shape_rewards(rows=rows, cols=cols)
+    env.record_replay(steps=T, action_dim=action_dim)
+    rp, sh, t = env.replay, env.eng.shaper.buf, env.eng.t
+    assert tuple(sh['bitmap'].shape) == (B, rows, cols) and tuple(env.replay_action.shape) == (B, action_dim)
+    mirror = rc.Mirror(T, B, rows, cols, action_dim, env.timestep)
+    pushes = rc.scripted_pushes(rows, cols, B, T, action_dim, env.timestep)
+    assert len(pushes) == 2 * T + 3
+    all_idx = torch.arange(T * B, device=env.device)
+    prev, invalid, terminal = None, 0, 0
+    for k, q in enumerate(pushes):
+        frame = rc.binary(q['frame'])
+        assert all((frame[e] == 0).any() and (frame[e] == 255).any() for e in range(B))
+        assert prev is None or all((frame[e] != prev[e]).any() for e in range(B))
+        prev = frame
+        sh['bitmap'].copy_(torch.as_tensor(q['frame']))
+        sh['total'].copy_(torch.as_tensor(q['reward']))
+        t['current_time'].copy_(torch.as_tensor(q['clock']))
+        t['done'].copy_(torch.as_tensor(q['done'].astype(bool)))
+        env.replay_action.copy_(torch.as_tensor(q['action']))
+        rp.kernel()
+        torch.cuda.synchronize()
+        valid = mirror.push(frame, q['action'], q['reward'], q['done'], q['clock'])
+        assert np.array_equal(_np(rp.buf['last_valid']), valid), (k, _np(rp.buf['last_valid']), valid)
+        assert int(rp.buf['count']) == mirror.count
+        if k:
+            invalid += int((valid == 0).sum())
+            terminal += int((valid & q['done']).sum())
+        want = mirror.at(range(T * B))
+        _assert_batch(rp.sample_at(all_idx), want, '%d x %d, push %d, uint8' % (rows, cols, k))
+        for scale in (1.0, 1.0 / 255.0):
+            on = np.float32(255.0) * np.float32(scale)
+            got = rp.sample_at(all_idx, dtype=torch.float32, scale=scale)
+            assert got[0].shape == got[3].shape == (T * B, 1, rows, cols) and got[0].dtype == torch.float32
+            want32 = tuple(np.where(w == 255, on, np.float32(0.0)).astype(np.float32)[:, None] if i in (0, 3) else w for i, w in enumerate(want))
+            _assert_batch(got, want32, '%d x %d, push %d, fp32 * %g' % (rows, cols, k, scale))
+    assert invalid >= 1 and terminal >= 1 and len(mirror) == len(rp) > 0
+    assert np.array_equal(_np(rp.buf['valid']), mirror.valid_array())
+    assert env.eng.device_errors() == 0
+    env.close()
+
+
+def _draw_direct(env, seed, first, n):
+    """f110_replay_draw itself (the wrapper keeps its own draw counter) into arrays longer than the launch has lanes: what lies
+    beyond the n draws must stay as it was."""
+    import torch
+    from red_gym_amd import _lib
+    eng = env.eng
+    m = (n + 255) // 256 * 256 + 300
+    idx = torch.full((m,), -7, dtype=torch.int64, device=env.device)
+    ok = torch.full((m,), 9, dtype=torch.uint8, device=env.device)
+    with torch.cuda.device(env.device):
+        _lib.check(eng.lib.f110_replay_draw(eng._h, seed, first, n, idx.data_ptr(), ok.data_ptr(), eng._stream()))
+    torch.cuda.synchronize()
+    idx, ok = _np(idx), _np(ok)
+    assert (idx[n:] == -7).all() and (ok[n:] == 9).all(), 'the draw wrote beyond its n = %d outputs' % n
+    return idx[:n], ok[:n]
+
+
+def test_draw_at_every_launch_shape_and_a_wrapping_draw_number(assets):
+    """n = 1, 255, 257 and 1000 draws (a partial last workgroup, several workgroups) on DRAW_CASE's pattern, from draw number 0
+    and from 2 ** 64 - 3, where the draw number wraps inside the launch: `==` the checker, nothing written beyond n."""
+    import torch
+    c = rc.DRAW_CASE
+    env, _ = _filled_env(assets, B=c['B'], T=c['T'], steps=c['count'] - 1, rows=40, cols=30)
+    pattern = rc.draw_case_valid()
+    env.replay.buf['valid'].copy_(torch.as_tensor(pattern))
+    assert int(env.replay.buf['count']) == c['count']
+    for first in (0, 2 ** 64 - 3):
+        for n in (1, 255, 257, 1000):
+            idx, ok = _draw_direct(env, c['seed'], first, n)
+            want_idx, want_ok, _ = rc.draw(pattern, c['count'], c['seed'], first, n)
+            assert np.array_equal(idx, want_idx) and np.array_equal(ok, want_ok), (first, n)
+            assert pattern[idx[idx >= 0] // c['B'], idx[idx >= 0] % c['B']].all()
+    # the draws either side of the wrap are those of draw numbers 2 ** 64 - 3 .. 2 ** 64 - 1 and 0 ..: another stream than 0 ..
+    assert np.array_equal(_draw_direct(env, c['seed'], 2 ** 64 - 3, 257)[0][3:], _draw_direct(env, c['seed'], 0, 254)[0])
+    assert env.eng.device_errors() == 0
+    env.close()
+
+
+@pytest.mark.parametrize('start', [2 ** 31 - 3, 2 ** 40 + 1])
+def test_counter_beyond_32_bits(assets, start):
+    """A ring of T = 4, B = 6 whose counter starts at 2 ** 31 - 3 (the run crosses 2 ** 31) and at 2 ** 40 + 1 (save(), edit
+    count and chain_start, load()), 2 T + 3 pushes through the eager step and through step_graph: replay_count, replay_valid,
+    sample_at(all T * B indices) and draw(257) `==` the mirror started at the same count after every push.  A kernel or a
+    binding that kept 32 bits of `count` would report another replay_count and take other slots."""
+    import torch
+    from red_gym_amd import workload
+    B, T, AD = 6, 4, 16
+    env = _env(assets, B, autoreset=True)
+    env.shape_rewards()
+    env.reset(workload.spawn_poses(B, 1))
+    pool = workload.action_pool(3 + 2 * T + 3, B, 1)
+    for k in range(3):
+        env.step(pool[k])
+    sd = env.state_dict()
+    env.record_replay(steps=T, action_dim=AD)
+    rp = env.replay
+    blank = rp.save()
+    blank['count'].fill_(start)
+    blank['chain_start'].fill_(start)
+    all_idx = torch.arange(T * B, device=env.device)
+    for how in ('eager', 'step_graph'):
+        env.load_state_dict(sd)
+        rp.load(blank)
+        assert int(rp.buf['count']) == start and len(rp) == 0
+        mirror = rc.Mirror(T, B, 256, 256, AD, env.timestep)
+        mirror.count = mirror.chain_start = start
+        if how == 'step_graph':
+            env.capture_step()
+        stepper = env.step if how == 'eager' else env.step_graph
+        for k in range(2 * T + 3):
+            action = (np.arange(B * AD).reshape(B, AD) + 1000.0 * k).astype(np.float32)
+            env.replay_action.copy_(torch.as_tensor(action))
+            _, reward, done, info = stepper(pool[3 + k])
+            torch.cuda.synchronize()
+            valid = mirror.push(_np(info['lidar_bitmap']), action, _np(reward), _np(done), _np(info['current_time']))
+            assert np.array_equal(_np(info['replay_valid']), valid), (how, k)
+            assert int(info['replay_count']) == mirror.count == start + k + 1
+            assert not valid.any() if k == 0 else valid.any()
+            _assert_batch(rp.sample_at(all_idx), mirror.at(range(T * B)), '%s from %d, push %d' % (how, start, k))
+            first = rp._draws
+            idx, ok = rp.draw(257, seed=5)
+            want_idx, want_ok, _ = rc.draw(mirror.valid_array(), mirror.count, 5, first, 257)
+            assert np.array_equal(_np(idx), want_idx) and np.array_equal(_np(ok), want_ok), (how, k)
+            assert want_ok.all() == (k > 0)
+        idx, ok = _draw_direct(env, 5, 2 ** 64 - 3, 257)
+        want_idx, want_ok, _ = rc.draw(mirror.valid_array(), mirror.count, 5, 2 ** 64 - 3, 257)
+        assert np.array_equal(idx, want_idx) and np.array_equal(ok, want_ok) and want_ok.all()
+        assert len(rp) == len(mirror) > 2 * B and mirror.count > 2 ** 31
     assert env.eng.device_errors() == 0
     env.close()

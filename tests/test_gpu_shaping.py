@@ -244,3 +244,64 @@ def test_pose_that_is_not_finite(assets):
     assert torch.equal(s['prev_xy'][~bad], env.state[~bad, 0, :2])
     assert env.eng.device_errors() == 0
     env.close()
+
+
+@pytest.mark.parametrize('B', [5, 7])
+def test_batches_that_do_not_fill_a_workgroup(assets, golden, B):
+    """shaping_kernel runs four envs per workgroup: with 5 and 7 envs the last workgroup has waves without an env.  The
+    function-level kernel on B cases of g16 `==` the reference's recorded results, and a 20-step closed loop of B envs `==` the
+    checker after every step."""
+    import torch
+    from red_gym_amd import shaping, workload
+    g = golden('g16_shaping.npz')
+    imgs = sc.unpack_images(g, 'b')
+    m = np.flatnonzero(g['group'] == 1)
+    m = m[::m.size // B][:B]
+    assert m.size == B
+    out = shaping.reward_terms(torch.as_tensor(imgs[g['img'][m]], device='cuda'), torch.as_tensor(g['xy'][m], device='cuda'),
+                               torch.as_tensor(g['prev'][m], device='cuda'))
+    _assert_same({k: v.cpu().numpy() for k, v in out.items()}, {k: g[k][m] for k in OUT_KEYS}, 'g16, %d cases' % B)
+    env = _env(assets, B, autoreset=True)
+    wp = _waypoints(env)
+    env.shape_rewards()
+    ck = sc.ShapingChecker(B, env.timestep)
+    _, reward, _, info = env.reset(workload.spawn_poses(B, 1))
+    prev_img = np.zeros((B, 256, 256), np.uint8)
+    for k in range(21):
+        if k:
+            _, reward, _, info = env.step(env.pure_pursuit(wp, TLAD, VGAIN))
+        got = _outputs(reward, info)
+        want = ck.update(prev_img, env.state[:, 0, :2].cpu().numpy(), info['current_time'].cpu().numpy())
+        _assert_same(got, want, '%d envs, step %d' % (B, k))
+        assert np.array_equal(env.eng.shaper.buf['prev_xy'].cpu().numpy(), ck.prev_xy)
+        prev_img = info['lidar_bitmap'].cpu().numpy().copy()
+        assert prev_img.shape == (B, 256, 256) and all(im.max() == 255 and im.min() == 0 for im in prev_img)
+    assert (got['progress_term'] > 0).any() and np.isfinite(got['total']).all()
+    assert env.eng.device_errors() == 0
+    env.close()
+
+
+@pytest.mark.parametrize('rows,cols', [(12, 40), (10, 64), (10, 65), (11, 600)])
+def test_kernel_equals_the_checker_at_other_image_sizes(rows, cols):
+    """The hand-built images and designed poses of tests/shaping_cases.py at rows narrower than one 64-pixel chunk, of exactly
+    one, of one and a pixel, and of 600 pixels (a third pass of the centering row's 256-pixel loop): 366 cases each (no multiple
+    of 4), every output `==` the checker."""
+    import torch
+    from red_gym_amd import shaping
+    cfg = sc.config(rows=rows, cols=cols, clip_max=max(rows, cols) - 1, scale=2.0, origin_x=cols / 2.0, origin_y=rows / 2.0,
+                    max_lane_halfwidth=cols / 4.0, neighborhood=1 + rows % 2)
+    imgs = sc.hand_images(rows, cols)
+    n = 61 * imgs.shape[0]
+    poses = sc.designed_poses(rows, cols, n, rows * cols, cfg)
+    pick = np.arange(n) % imgs.shape[0]
+    want = [sc.reward_terms(imgs[pick[k]], poses[k, 0], poses[k, 1], poses[k, 2], poses[k, 3], cfg) for k in range(n)]
+    out = shaping.reward_terms(torch.as_tensor(imgs[pick], device='cuda'), torch.as_tensor(poses[:, :2], device='cuda'),
+                               torch.as_tensor(poses[:, 2:], device='cuda'), **{k: v for k, v in cfg.items() if k != 'agent'})
+    _assert_same({k: v.cpu().numpy() for k, v in out.items()}, {k: np.array([w[k] for w in want]) for k in OUT_KEYS}, '%d x %d' % (rows, cols))
+    # the cases reach the branches: both collision results, a run found (reward in (0, 1) and clamped to 0) and none (-1)
+    hit = np.array([w['collided'] for w in want])
+    reward = np.array([w['centering_term'] for w in want]) / cfg['w_centering']
+    assert 0.1 < hit.mean() < 0.9 and ((reward > 0) & (reward < 1)).mean() > 0.1 and (reward == 0).mean() > 0.05 and (reward == -1).mean() > 0.1
+    if cols > 512:
+        assert sum(1 for k in range(n) if poses[k, 0] >= 512 and reward[k] > -1) >= 10    # runs found in the row's third pass
+    assert n % 4 != 0

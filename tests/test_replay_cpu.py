@@ -93,3 +93,94 @@ def test_redraw_finds_a_transition_for_every_draw_of_the_gpu_test():
     a = rc.draw(valid, c['count'], c['seed'], 0, c['n'])[0]
     b = rc.draw(valid, c['count'], c['seed'], c['n'], c['n'])[0]
     assert not np.array_equal(a, b) and len(set(a.tolist())) > 15
+
+
+def test_shape_table_covers_every_size_selected_path():
+    """SHAPES (what the GPU tests run) against paths(), the header's arithmetic restated: every pack branch with one pass and
+    with several whose last is partial, both unpack forms with one pass and with at least two, the rows either side of a gather
+    block (REPLAY_ROWS = 16) and several blocks."""
+    assert len(set(rc.SHAPES)) == len(rc.SHAPES)
+    p = {s: rc.paths(*s) for s in rc.SHAPES}
+    for branch in ('dense', 'aligned', 'bytewise'):
+        mine = [v for v in p.values() if v['pack'] == branch]
+        assert any(v['pack_passes'] == 1 for v in mine), branch
+        assert any(v['pack_passes'] > 1 and v['pack_last_partial'] for v in mine), branch
+    for form in ('vec4', 'scalar'):
+        mine = [v for v in p.values() if v['unpack'] == form]
+        assert any(v['unpack_passes'] == 1 for v in mine) and any(v['unpack_passes'] >= 2 for v in mine), form
+    rows = {r for r, _ in rc.SHAPES}
+    assert {1, 15, 16, 17} <= rows and max(rows) > 32
+    assert {p[s]['row_blocks'] for s in ((15, 15), (16, 96), (17, 16), (33, 48))} == {1, 2, 3}
+    # paths() on sizes worked out by hand from csrc/f110_replay.h
+    assert rc.paths(256, 256) == dict(pack='dense', pack_passes=4, pack_last_partial=False, unpack='vec4', unpack_passes=1, row_blocks=16)
+    assert rc.paths(224, 224) == dict(pack='aligned', pack_passes=4, pack_last_partial=True, unpack='vec4', unpack_passes=1, row_blocks=14)
+    assert rc.paths(75, 320) == dict(pack='dense', pack_passes=2, pack_last_partial=True, unpack='vec4', unpack_passes=2, row_blocks=5)
+    assert rc.paths(9, 257) == dict(pack='bytewise', pack_passes=1, pack_last_partial=True, unpack='scalar', unpack_passes=5, row_blocks=1)
+    assert rc.paths(84, 84) == dict(pack='bytewise', pack_passes=3, pack_last_partial=True, unpack='vec4', unpack_passes=1, row_blocks=6)
+    assert rc.paths(40, 1028)['unpack_passes'] == 5 and rc.paths(20, 272)['pack'] == 'aligned' and rc.paths(20, 272)['unpack_passes'] == 2
+
+
+def test_scripted_pushes_exercise_the_ring():
+    """The ring's run on frames the test writes (test_gpu_replay.py), on the mirror alone: its sizes cover every pack branch and
+    both unpack forms with one pass and with several, every frame holds both values, no env repeats a frame, and the ring comes
+    to hold invalid transitions (a clock that stands still, a reset) and terminal ones."""
+    assert set(rc.RING_SHAPES) <= set(rc.SHAPES) and {(224, 224), (20, 272), (84, 84), (9, 257), (40, 1028)} <= set(rc.RING_SHAPES)
+    p = [rc.paths(*s) for s in rc.RING_SHAPES]
+    assert {(v['pack'], v['pack_passes'] > 1) for v in p} == {(b, m) for b in ('dense', 'aligned', 'bytewise') for m in (False, True)}
+    assert {(v['unpack'], v['unpack_passes'] > 1) for v in p} == {(f, m) for f in ('vec4', 'scalar') for m in (False, True)}
+    assert {1, 15, 16, 17} <= {r for r, _ in rc.RING_SHAPES}
+    B, T, dt = 5, 3, 0.01
+    for rows, cols in rc.RING_SHAPES:
+        m = rc.Mirror(T, B, rows, cols, 16, dt)
+        pushes = rc.scripted_pushes(rows, cols, B, T, 16, dt)
+        assert len(pushes) == 2 * T + 3
+        prev, invalid, terminal = None, 0, 0
+        for k, q in enumerate(pushes):
+            f = rc.binary(q['frame'])
+            assert all((f[e] == 0).any() and (f[e] == 255).any() for e in range(B))
+            assert prev is None or all((f[e] != prev[e]).any() for e in range(B))
+            v = m.push(f, q['action'], q['reward'], q['done'], q['clock'])
+            assert not v.any() if k == 0 else v.sum() >= B - 1
+            if k:
+                invalid += int((v == 0).sum())
+                terminal += int((v & q['done']).sum())
+            prev = f
+        assert invalid == 2 and terminal == 3 and m.count == 2 * T + 3
+        assert all(((q['frame'] != 0) & (q['frame'] != 255)).any() for q in pushes)   # raw bytes: only 255 is a set bit
+    a = np.stack([q['action'] for q in rc.scripted_pushes(3, 64, B, T, 300, dt)])
+    assert a.dtype == np.float32 and np.unique(a).size == a.size                  # arange-distinct, exact in fp32
+
+
+@pytest.mark.parametrize('rows,cols', rc.SHAPES)
+def test_pack_round_trip_at_every_shape(rows, cols):
+    for imgs in (rc.edge_images(rows, cols), rc.random_images(rows, cols)):
+        p = rc.pack(imgs)
+        assert p.shape == (imgs.shape[0], rows, rc.words(cols))
+        assert np.array_equal(rc.unpack(p, cols), np.where(imgs == 255, 255, 0).astype(np.uint8))
+        # the padding bits of a row's last word are 0
+        if cols % 64:
+            assert not (p[:, :, -1] >> np.uint64(cols % 64)).any()
+    r = rc.random_images(rows, cols)
+    assert r.shape[0] == 7 and all((im == 254).any() and (im == 127).any() and (im == 255).any() for im in r)
+    assert 0.2 < (r == 255).mean() < 0.4
+
+
+def test_draw_is_uniform_over_the_valid_transitions():
+    """sample() promises a uniform draw over the valid transitions.  The GPU's draw `==` this checker bit for bit
+    (test_gpu_replay.py), so the distribution is checked here: 20 000 draws on DRAW_CASE's pattern, Pearson's statistic over its
+    26 valid transitions inside the central 99.8 % of chi-square with 25 degrees of freedom (8.65 .. 52.62)."""
+    from scipy.stats import chi2
+    c = rc.DRAW_CASE
+    valid = rc.draw_case_valid()
+    n = 20000
+    idx, ok, _ = rc.draw(valid, c['count'], c['seed'], 0, n)
+    assert (ok == 1).all()
+    hist = np.bincount(idx, minlength=valid.size).reshape(valid.shape)
+    assert not hist[valid == 0].any()                                             # no invalid index is drawn
+    k = int(valid.sum())
+    assert k == 26
+    expected = n / k
+    stat = float(((hist[valid == 1] - expected) ** 2 / expected).sum())
+    lo, hi = chi2.ppf(0.001, k - 1), chi2.ppf(0.999, k - 1)
+    print('Pearson statistic %.2f over %d cells, bounds %.2f .. %.2f' % (stat, k, lo, hi))
+    assert lo < stat < hi
