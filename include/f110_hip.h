@@ -599,6 +599,45 @@ int f110_replay_update(f110_handle *h, void *stream);
 int f110_replay_draw(f110_handle *h, uint64_t seed, uint64_t first_draw, int32_t n, int64_t *indices, uint8_t *ok, void *stream);
 int f110_replay_gather(f110_handle *h, const int64_t *indices, int32_t n, void *s, void *ns, int32_t as_f32, double scale,
                        float *a, double *r, uint8_t *d, uint8_t *ok, void *stream);
+/* f110_replay_locate: where the gather would read.  For n indices (dev int64) the rows of the frame tensor, viewed as
+ * [(T + 1) * B, rows, words], that hold the transition's frame before (s_frame [n]) and its frame after (ns_frame [n], both dev
+ * int64); -1 for both where the gather writes zeros.  It reads count on the device like every replay kernel (capturable). */
+int f110_replay_locate(f110_handle *h, const int64_t *indices, int32_t n, int64_t *s_frame, int64_t *ns_frame, void *stream);
+
+/* First convolution of the policy from bits: the nn.Conv2d(1, C, kernel, stride) that opens the reference's Actor and Critic
+ * (src/SAL.py:397, 429) on an image of two values, forward and backward, stateless (no handle; cfg host; all arrays dev; launches
+ * on the calling thread's current device, no allocation, no synchronisation).  `on` is what a set pixel is worth: 1 for
+ * FloatTensor(state) / 255 (:510), 255 for the raw images of update() (:536).  Output size as nn.Conv2d without padding: OH =
+ * (rows - kernel) / stride + 1, OW likewise.
+ * frames: [n_frames, rows, ceil(cols / 64)] uint64 in the replay ring's format (bit k of word w = pixel 64 w + k), 8-byte
+ * aligned; the _u8 entry reads uint8 images [n_frames, rows, cols] instead, a pixel set iff it == 255, thresholded on the fly.
+ * index: NULL (sample i reads frame i; n <= n_frames) or dev int64 [n]: the frame of sample i; an entry outside 0 .. n_frames
+ * - 1 (-1 is the conventional one) reads a frame of zeros and is never dereferenced; repeats are allowed.
+ * weight [channels, 1, kernel, kernel] fp32 (finite), bias [channels] fp32 or NULL (= zeros), out [n, channels, OH, OW] fp32.
+ * Numerics, in fp32: acc = 0; for the taps ky major, kx minor: acc = acc + w[c][ky][kx] if the tap's pixel is set; out = (acc *
+ * on) + bias[c], two roundings; then out < 0 ? 0 : out if relu.  The output is a function of the bits alone.
+ * f110_bitconv_backward: from grad_out [n, channels, OH, OW] fp32 and the same frames / index, grad_weight[c][ky][kx] = on *
+ * sum over samples and outputs of grad_out * bit and grad_bias[c] = sum of grad_out (NULL: skipped); fp32 sums in an order fixed
+ * by the shape and n (no atomics: two calls give the same bits), through `workspace` (16-byte aligned) of
+ * f110_bitconv_workspace bytes (0 for an invalid configuration or n < 1).  With relu the caller has already zeroed grad_out
+ * where out is 0.  There is no gradient with respect to the image.
+ * f110_bitconv_validate: host only.  F110_E_INVALID for kernel outside 1..8 (a window is one 64-bit mask), stride outside
+ * 1..kernel, channels outside 1..64, rows or cols below kernel or above 16384, a non-finite `on`. */
+typedef struct {
+    int32_t rows, cols;         /* the image */
+    int32_t kernel, stride;     /* square window, 1..8; stride 1..kernel */
+    int32_t channels;           /* output channels, 1..64 */
+    int32_t relu;               /* nonzero: max(out, 0) */
+    float on;                   /* the value of a set pixel */
+} f110_bitconv_config;
+int f110_bitconv_validate(const f110_bitconv_config *cfg);
+int64_t f110_bitconv_workspace(const f110_bitconv_config *cfg, int64_t n);
+int f110_bitconv_forward(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
+                         const float *weight, const float *bias, float *out, void *stream);
+int f110_bitconv_forward_u8(const f110_bitconv_config *cfg, const uint8_t *images, int64_t n_frames, const int64_t *index, int64_t n,
+                            const float *weight, const float *bias, float *out, void *stream);
+int f110_bitconv_backward(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
+                          const float *grad_out, float *grad_weight, float *grad_bias, float *workspace, void *stream);
 
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).

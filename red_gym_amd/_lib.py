@@ -95,6 +95,12 @@ class ReplayBuffers(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in REPLAY_FIELDS]
 
 
+# f110_bitconv_config: the first convolution computed from bits (stateless)
+class BitconvConfig(C.Structure):
+    _fields_ = [('rows', C.c_int32), ('cols', C.c_int32), ('kernel', C.c_int32), ('stride', C.c_int32),
+                ('channels', C.c_int32), ('relu', C.c_int32), ('on', C.c_float)]
+
+
 # every symbol include/f110_hip.h declares: name -> argtypes (restype int unless noted)
 _VP, _I32, _I64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -168,6 +174,12 @@ SYMBOLS = {
     'f110_replay_update': [_VP, _VP],
     'f110_replay_draw': [_VP, C.c_uint64, C.c_uint64, _I32, _VP, _VP, _VP],
     'f110_replay_gather': [_VP, _VP, _I32, _VP, _VP, _I32, _D, _VP, _VP, _VP, _VP, _VP],
+    'f110_replay_locate': [_VP, _VP, _I32, _VP, _VP, _VP],
+    'f110_bitconv_validate': [C.POINTER(BitconvConfig)],
+    'f110_bitconv_workspace': [C.POINTER(BitconvConfig), _I64],
+    'f110_bitconv_forward': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP],
+    'f110_bitconv_forward_u8': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP],
+    'f110_bitconv_backward': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP],
     'f110_replay_pack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_replay_unpack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],
@@ -220,6 +232,7 @@ def load():
         fn.restype = C.c_int
     lib.f110_last_error.restype = C.c_char_p
     lib.f110_pure_pursuit_workspace.restype = C.c_int64
+    lib.f110_bitconv_workspace.restype = C.c_int64
     lib.f110_pack_env_size.restype = C.c_int64
     lib.f110_destroy.restype = None
     lib.f110_bitmap_destroy.restype = None

@@ -747,6 +747,19 @@ extern "C" int f110_replay_gather(f110_handle *h, const int64_t *indices, int32_
     return F110_OK;
 }
 
+extern "C" int f110_replay_locate(f110_handle *h, const int64_t *indices, int32_t n, int64_t *s_frame, int64_t *ns_frame, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_replay_locate: null handle");
+    ReplayRing g;
+    if (int rc = replay_ready(h, "f110_replay_locate", g)) return rc;
+    if (n < 0 || !indices || !s_frame || !ns_frame) return fail(F110_E_INVALID, "f110_replay_locate: bad arguments");
+    if (n == 0) return F110_OK;
+    hipLaunchKernelGGL(replay_locate_kernel, dim3((unsigned)((n + REPLAY_THREADS - 1) / REPLAY_THREADS)), dim3(REPLAY_THREADS), 0, (hipStream_t)stream,
+                       g, (const long long *)indices, n, (long long *)s_frame, (long long *)ns_frame);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
 static int replay_pack_args(const char *who, const void *in, const void *out, int64_t n, int32_t rows, int32_t cols)
 {
     if (n < 0 || n > 0x7fffffff || rows < 1 || cols < 1 || rows > REPLAY_MAX_DIM || cols > REPLAY_MAX_DIM)
@@ -775,6 +788,114 @@ extern "C" int f110_replay_unpack(const uint64_t *packed, int64_t n, int32_t row
     a.bitmaps = nullptr; a.packed = const_cast<uint64_t *>(packed); a.rows = rows; a.cols = cols;
     hipLaunchKernelGGL(replay_unpack_kernel, dim3((unsigned)n, (unsigned)((rows + REPLAY_ROWS - 1) / REPLAY_ROWS)), dim3(REPLAY_THREADS), 0,
                        (hipStream_t)stream, a, bitmaps);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+// ---------------------------------------------------------------- first convolution from bits
+// What the entry points refuse, on the struct alone (no device).
+extern "C" int f110_bitconv_validate(const f110_bitconv_config *cfg)
+{
+    const char *who = "f110_bitconv_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    if (cfg->kernel < 1 || cfg->kernel > BC_MAX_K) return fail(F110_E_INVALID, "%s: kernel %d (1..%d: a window is one 64-bit mask)", who, cfg->kernel, BC_MAX_K);
+    if (cfg->stride < 1 || cfg->stride > cfg->kernel) return fail(F110_E_INVALID, "%s: stride %d (1..kernel = %d)", who, cfg->stride, cfg->kernel);
+    if (cfg->channels < 1 || cfg->channels > 64) return fail(F110_E_INVALID, "%s: %d channels (1..64)", who, cfg->channels);
+    if (cfg->rows < cfg->kernel || cfg->cols < cfg->kernel || cfg->rows > REPLAY_MAX_DIM || cfg->cols > REPLAY_MAX_DIM)
+        return fail(F110_E_INVALID, "%s: image of %d x %d pixels (kernel = %d .. %d)", who, cfg->rows, cfg->cols, cfg->kernel, REPLAY_MAX_DIM);
+    if (!std::isfinite(cfg->on)) return fail(F110_E_INVALID, "%s: `on` is not finite", who);
+    return F110_OK;
+}
+
+// the launch geometry of a validated configuration
+static void bitconv_geometry(const f110_bitconv_config &c, BitconvArgs &a)
+{
+    a.cfg = c;
+    a.OH = (c.rows - c.kernel) / c.stride + 1; a.OW = (c.cols - c.kernel) / c.stride + 1;
+    a.W = replay_words(c.cols);
+    a.tiles_x = (a.OW + BC_TX - 1) / BC_TX; a.tiles_y = (a.OH + BC_TY - 1) / BC_TY;
+}
+
+static int bitconv_partials(const BitconvArgs &a, int64_t n)
+{
+    const int64_t tiles = n * a.tiles_x * a.tiles_y;
+    return (int)std::min<int64_t>(tiles, BC_MAX_PARTIALS);
+}
+
+extern "C" int64_t f110_bitconv_workspace(const f110_bitconv_config *cfg, int64_t n)
+{
+    if (n < 1 || f110_bitconv_validate(cfg) != F110_OK) return 0;
+    BitconvArgs a;
+    bitconv_geometry(*cfg, a);
+    return (int64_t)bitconv_partials(a, n) * cfg->channels * (cfg->kernel * cfg->kernel + 1) * (int64_t)sizeof(float);
+}
+
+#define BITCONV_BY_KERNEL(K, LAUNCH) \
+    switch (K) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; case 4: LAUNCH(4); break; \
+                 case 5: LAUNCH(5); break; case 6: LAUNCH(6); break; case 7: LAUNCH(7); break; default: LAUNCH(8); break; }
+
+static int bitconv_forward(const char *who, const f110_bitconv_config *cfg, const void *src, bool u8, int64_t n_frames, const int64_t *index,
+                           int64_t n, const float *weight, const float *bias, float *out, hipStream_t stream)
+{
+    if (int rc = f110_bitconv_validate(cfg)) return rc;
+    if (n < 0 || n_frames < 0) return fail(F110_E_INVALID, "%s: n=%lld samples of %lld frames", who, (long long)n, (long long)n_frames);
+    if (n == 0) return F110_OK;
+    if (!weight || !out || (n_frames > 0 && !src)) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (!index && n > n_frames) return fail(F110_E_INVALID, "%s: %lld samples of %lld frames without an index", who, (long long)n, (long long)n_frames);
+    if (!u8 && (uintptr_t)src % 8) return fail(F110_E_INVALID, "%s: frames must be 8-byte aligned", who);
+    BitconvArgs a;
+    memset(&a, 0, sizeof(a));
+    bitconv_geometry(*cfg, a);
+    if (u8) a.images = (const uint8_t *)src; else a.frames = (const uint64_t *)src;
+    a.n_frames = n_frames; a.index = (const long long *)index; a.n = n;
+    // a launch has fewer than 2^32 threads: images go in groups of at most 2^23 workgroups
+    const int64_t per = (int64_t)a.tiles_x * a.tiles_y, group = std::max<int64_t>(1, ((int64_t)1 << 23) / per);
+    for (int64_t first = 0; first < n; first += group) {
+        a.first = first;
+        const unsigned grid = (unsigned)(std::min(group, n - first) * per);
+#define BITCONV_FWD(K) do { if (u8) hipLaunchKernelGGL((bitconv_forward_kernel<K, true>), dim3(grid), dim3(BC_THREADS), 0, stream, a, weight, bias, out); \
+                            else hipLaunchKernelGGL((bitconv_forward_kernel<K, false>), dim3(grid), dim3(BC_THREADS), 0, stream, a, weight, bias, out); } while (0)
+        BITCONV_BY_KERNEL(cfg->kernel, BITCONV_FWD)
+#undef BITCONV_FWD
+        HIP_TRY(hipGetLastError());
+    }
+    return F110_OK;
+}
+
+extern "C" int f110_bitconv_forward(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
+                                    const float *weight, const float *bias, float *out, void *stream)
+{
+    return bitconv_forward("f110_bitconv_forward", cfg, frames, false, n_frames, index, n, weight, bias, out, (hipStream_t)stream);
+}
+
+extern "C" int f110_bitconv_forward_u8(const f110_bitconv_config *cfg, const uint8_t *images, int64_t n_frames, const int64_t *index, int64_t n,
+                                       const float *weight, const float *bias, float *out, void *stream)
+{
+    return bitconv_forward("f110_bitconv_forward_u8", cfg, images, true, n_frames, index, n, weight, bias, out, (hipStream_t)stream);
+}
+
+extern "C" int f110_bitconv_backward(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
+                                     const float *grad_out, float *grad_weight, float *grad_bias, float *workspace, void *stream)
+{
+    const char *who = "f110_bitconv_backward";
+    if (int rc = f110_bitconv_validate(cfg)) return rc;
+    if (n < 1 || n_frames < 0) return fail(F110_E_INVALID, "%s: n=%lld samples of %lld frames", who, (long long)n, (long long)n_frames);
+    if (!grad_out || !grad_weight || !workspace || (n_frames > 0 && !frames)) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (!index && n > n_frames) return fail(F110_E_INVALID, "%s: %lld samples of %lld frames without an index", who, (long long)n, (long long)n_frames);
+    if ((uintptr_t)frames % 8 || (uintptr_t)workspace % 16) return fail(F110_E_INVALID, "%s: frames must be 8-byte and the workspace 16-byte aligned", who);
+    BitconvArgs a;
+    memset(&a, 0, sizeof(a));
+    bitconv_geometry(*cfg, a);
+    a.frames = frames; a.n_frames = n_frames; a.index = (const long long *)index; a.n = n; a.grad_out = grad_out; a.ws = workspace;
+    a.G = bitconv_partials(a, n);
+    const dim3 grid((unsigned)a.G, (unsigned)((cfg->channels + BC_CHUNK - 1) / BC_CHUNK));
+#define BITCONV_BWD(K) hipLaunchKernelGGL((bitconv_backward_kernel<K>), grid, dim3(BC_THREADS), 0, (hipStream_t)stream, a)
+    BITCONV_BY_KERNEL(cfg->kernel, BITCONV_BWD)
+#undef BITCONV_BWD
+    HIP_TRY(hipGetLastError());
+    const int nw = cfg->channels * cfg->kernel * cfg->kernel;
+    hipLaunchKernelGGL(bitconv_reduce_kernel, dim3((unsigned)((nw + cfg->channels + BC_THREADS - 1) / BC_THREADS)), dim3(BC_THREADS), 0, (hipStream_t)stream,
+                       (const float *)workspace, a.G, nw, cfg->channels, cfg->on, grad_weight, grad_bias);
     HIP_TRY(hipGetLastError());
     return F110_OK;
 }

@@ -9,6 +9,7 @@
 //   replay_advance_kernel  one lane: count += 1, behind the push
 //   replay_draw_kernel     one lane per draw: splitmix64 candidates over the stored transitions, the first valid one wins
 //   replay_gather_kernel   one wave per (sample, frame, 4 rows): bits back to uint8 (4 pixels = one 4-byte store per lane) or fp32
+//   replay_locate_kernel   one lane per index: where the gather would read, for consumers that read the bits themselves (f110_bitconv.h)
 #pragma once
 #include "f110_kernels.h"
 #include "f110_pathfollow.h"
@@ -131,6 +132,28 @@ struct ReplayRing {                 // what the three kernels share
     __device__ uint64_t *frame(long long fs, int env) const { return frames + ((size_t)fs * (size_t)n_envs + (size_t)env) * frame_words(); }
 };
 
+// Transition `id` (step slot * n_envs + env) of the ring as `count` stands: false for an index outside the ring, a slot no push
+// has reached or an invalid transition; else `c` = the newest push that went to its step slot (its frames are c - 1 and c) and
+// `env`.  The addressing the gather and the locate share.
+__device__ inline bool replay_resolve(const ReplayRing &g, long long id, long long &c, int &env)
+{
+    const long long count = *g.count;
+    bool ok = id >= 0 && id < g.steps * g.n_envs && count >= 1;
+    c = 0;
+    env = 0;
+    if (ok) {
+        const long long slot = id / g.n_envs;
+        env = (int)(id - slot * g.n_envs);
+        ok = slot <= count - 1 && g.valid[id] != 0;
+        if (ok) {
+            c = count - 1 - (count - 1 - slot) % g.steps;   // the newest push that went to this step slot
+            F110_BCHK(c >= 1 && c % g.steps == slot, BT_REPLAY, g.dev_err);
+            ok = c >= 1;                                    // (push 0 has no previous frame and is never valid)
+        }
+    }
+    return ok;
+}
+
 struct ReplayPushArgs {
     ReplayRing ring;
     const uint8_t *bitmap;          // [n_envs, rows, cols] the shaper's image of the scan the step returned
@@ -233,20 +256,10 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_gather_kernel(Re
 {
     const ReplayRing &g = a.ring;
     const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long id = a.idx[i], count = *g.count;
-    bool ok = id >= 0 && id < g.steps * g.n_envs && count >= 1;
+    const long long id = a.idx[i];
     long long c = 0;
     int env = 0;
-    if (ok) {
-        const long long slot = id / g.n_envs;
-        env = (int)(id - slot * g.n_envs);
-        ok = slot <= count - 1 && g.valid[id] != 0;
-        if (ok) {
-            c = count - 1 - (count - 1 - slot) % g.steps;   // the newest push that went to this step slot
-            F110_BCHK(c >= 1 && c % g.steps == slot, BT_REPLAY, g.dev_err);
-            ok = c >= 1;                                    // (push 0 has no previous frame and is never valid)
-        }
-    }
+    const bool ok = replay_resolve(g, id, c, env);
     const uint64_t *frame = nullptr;
     if (ok) {
         const long long fs = (blockIdx.z ? c : c - 1) % (g.steps + 1);
@@ -273,6 +286,19 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_gather_kernel(Re
             a.ok[i] = ok ? 1 : 0;
         }
     }
+}
+
+// one lane per index: the rows of the frame tensor viewed as [(steps + 1) * n_envs, rows, words] that hold the transition's frame
+// before and its frame after, -1 for both where the gather would write zeros
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_locate_kernel(ReplayRing g, const long long *idx, int n, long long *s_frame, long long *ns_frame)
+{
+    const int i = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (i >= n) return;
+    long long c = 0;
+    int env = 0;
+    const bool ok = replay_resolve(g, idx[i], c, env);
+    s_frame[i] = ok ? ((c - 1) % (g.steps + 1)) * g.n_envs + env : -1;
+    ns_frame[i] = ok ? (c % (g.steps + 1)) * g.n_envs + env : -1;
 }
 
 static __global__ __launch_bounds__(REPLAY_THREADS) void replay_pack_kernel(ReplayPackArgs a)

@@ -72,7 +72,7 @@ def unpack_bitmaps(packed, cols):
 
 
 class ReplayBuffer(Consumer):
-    """The replay buffer of one Engine (f110_replay_install / _bind / _update / _draw / _gather).  The ring lives in `buf`:
+    """The replay buffer of one Engine (f110_replay_install / _bind / _update / _draw / _gather / _locate).  The ring lives in `buf`:
     frames [T + 1, B, rows, words] int64 (bit-packed), actions [T, B, action_dim] fp32, rewards [T, B] fp64, dones and valid
     [T, B] uint8, count and chain_start [1] int64, t_seen [B] fp64, last_valid [B] uint8 and action_in [B, action_dim] fp32 (what
     the next push stores: F110VecEnv.replay_action).  A transition is named by index = step slot * B + env.  The ring is no part
@@ -191,6 +191,38 @@ class ReplayBuffer(Consumer):
             raise ValueError('replay: the buffer is off (record_replay())')
         idx, _ = self.draw(batch_size, seed)
         return self.sample_at(idx, dtype, scale)
+
+    def frames_at(self, indices):
+        """The transitions `indices` [n] without unpacking an image, for consumers that read bits (red_gym_amd.bitconv).
+        Returns (frames, s_idx, ns_idx, a, r, d, ok): frames is the ring's frame tensor viewed as [(T + 1) * B, rows, words]
+        int64 (a view, no copy: it changes with the next push), s_idx and ns_idx [n] int64 its rows that hold the frame before
+        and the frame after (f110_replay_locate; -1 for both where sample_at gives zeros), and a, r, d, ok exactly what
+        sample_at(indices) returns.  Device tensors, no synchronisation."""
+        if not self.on:
+            raise ValueError('replay: the buffer is off (record_replay())')
+        eng = self.eng
+        idx = torch.as_tensor(indices).to(device=eng.device, dtype=torch.int64).contiguous().reshape(-1)
+        n = idx.shape[0]
+        s_idx = torch.empty((n,), dtype=torch.int64, device=eng.device)
+        ns_idx = torch.empty((n,), dtype=torch.int64, device=eng.device)
+        with torch.cuda.device(eng.device):
+            _lib.check(eng.lib.f110_replay_locate(eng._h, idx.data_ptr(), n, s_idx.data_ptr(), ns_idx.data_ptr(), eng._stream()))
+        self._keep = idx
+        T, B = self.cfg.steps, eng.B
+        found = s_idx >= 0
+        at = torch.where(found, idx, torch.zeros_like(idx))
+        a = torch.where(found[:, None], self.buf['actions'].view(T * B, -1)[at], torch.zeros((), dtype=torch.float32, device=eng.device))
+        r = torch.where(found, self.buf['rewards'].view(-1)[at], torch.zeros((), dtype=torch.float64, device=eng.device))
+        d = torch.where(found, self.buf['dones'].view(-1)[at], torch.zeros((), dtype=torch.uint8, device=eng.device))
+        frames = self.buf['frames'].view((T + 1) * B, self.rows, words(self.cols))
+        return frames, s_idx, ns_idx, a, r, d, found.to(torch.uint8)
+
+    def sample_frames(self, batch_size, seed=None):
+        """batch_size transitions drawn as sample() draws them (the same draw counter), returned as frames_at returns them."""
+        if not self.on:
+            raise ValueError('replay: the buffer is off (record_replay())')
+        idx, _ = self.draw(batch_size, seed)
+        return self.frames_at(idx)
 
     def bytes_held(self):
         return sum(self.buf[k].numel() * self.buf[k].element_size() for k in ('frames', 'actions', 'rewards', 'dones', 'valid'))
