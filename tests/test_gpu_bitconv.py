@@ -1,6 +1,7 @@
 """Bit convolution on the GPU (csrc/f110_bitconv.h): the forward pass `==` the checker of tests/bitconv_cases.py bit for bit, the
-backward pass inside the bound of an fp32 sum around the checker's fp64 gradients, and the closed loop from the env's bitmap and
-the replay ring's frames to features."""
+backward pass inside the bound of an fp32 sum around the checker's fp64 gradients and `==` the exact sums where grad_out is made
+of small integers, both at every shape-selected path (bc.paths), and the closed loop from the env's bitmap and the replay ring's
+frames to features."""
 import ctypes as C
 import os
 
@@ -29,7 +30,10 @@ def _packed(imgs):
 
 
 def _differing(got, want):
-    return int((bc.bit_patterns(_np(got)) != bc.bit_patterns(want)).sum())
+    """The elements of got (a device tensor, or an array already on the host) whose 32-bit patterns are not want's."""
+    got = got if isinstance(got, np.ndarray) else _np(got)
+    assert got.shape == want.shape
+    return int((bc.bit_patterns(got) != bc.bit_patterns(want)).sum())
 
 
 _forward_cache = {}
@@ -111,8 +115,9 @@ def test_uint8_entry_and_index(rows, cols, kernel, stride, channels):
         assert torch.equal(got[2], got[3])                                                         # the repeated rows
 
 
-def _raw_backward(frames, n_frames, index, n, cfg, g, with_bias=True):
-    """f110_bitconv_backward itself, into arrays with a margin that must stay as it was."""
+def _raw_backward(frames, n_frames, index, n, cfg, g, with_bias=True, ws_fill=-7.0):
+    """f110_bitconv_backward itself, into arrays with a margin that must stay as it was; the workspace starts as `ws_fill` (NaN:
+    a partial that is read without having been written shows in the result)."""
     import torch
     from red_gym_amd import _lib
     lib = _lib.load()
@@ -120,24 +125,21 @@ def _raw_backward(frames, n_frames, index, n, cfg, g, with_bias=True):
     gw = torch.full((cfg.channels * kk + 64,), -7.0, dtype=torch.float32, device='cuda')
     gb = torch.full((cfg.channels + 64,), -7.0, dtype=torch.float32, device='cuda')
     nbytes = lib.f110_bitconv_workspace(C.byref(cfg), n)
-    ws = torch.full((nbytes // 4 + 64,), -7.0, dtype=torch.float32, device='cuda')
+    ws = torch.full((nbytes // 4 + 64,), ws_fill, dtype=torch.float32, device='cuda')
     _lib.check(lib.f110_bitconv_backward(C.byref(cfg), frames.data_ptr(), n_frames, None if index is None else index.data_ptr(), n, g.data_ptr(),
                                          gw.data_ptr(), gb.data_ptr() if with_bias else None, ws.data_ptr(), torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    assert (_np(gw)[cfg.channels * kk:] == -7.0).all() and (_np(gb)[cfg.channels:] == -7.0).all() and (_np(ws)[nbytes // 4:] == -7.0).all()
+    margin = _np(ws)[nbytes // 4:]
+    assert (_np(gw)[cfg.channels * kk:] == -7.0).all() and (_np(gb)[cfg.channels:] == -7.0).all()
+    assert margin.size == 64 and (np.isnan(margin) if np.isnan(ws_fill) else margin == ws_fill).all()
     if not with_bias:
         assert (_np(gb) == -7.0).all()
     return _np(gw)[:cfg.channels * kk].reshape(cfg.channels, 1, cfg.kernel, cfg.kernel).copy(), _np(gb)[:cfg.channels].copy()
 
 
-@pytest.mark.parametrize('n', bc.BACKWARD_N)
-@pytest.mark.parametrize('rows,cols,kernel,stride,channels', bc.BACKWARD_CASES)
-def test_backward_within_the_bound_of_an_fp32_sum(rows, cols, kernel, stride, channels, n):
-    """grad_weight and grad_bias against the checker's fp64 gradients: |d grad_weight| <= gamma_(M + 1) |on| sum |grad_out bit|,
-    |d grad_bias| <= gamma_M sum |grad_out|, M = n OH OW; two calls give the same bits; without grad_bias nothing is written
-    there; and with an index that holds -1 and repeats."""
+def _backward_within_the_bound(rows, cols, kernel, stride, channels, n):
     from red_gym_amd import bitconv
-    imgs = bc.many_images(rows, cols, n)
+    imgs = bc.many_images(rows, cols, max(n, 3))[:n]
     oh, ow = bc.out_size(rows, cols, kernel, stride)
     rng = np.random.default_rng([rows, cols, n])
     g = (rng.normal(size=(n, channels, oh, ow)) * 10.0 ** rng.integers(-2, 2, (n, channels, 1, 1))).astype(np.float32)
@@ -166,6 +168,166 @@ def test_backward_within_the_bound_of_an_fp32_sum(rows, cols, kernel, stride, ch
     want_w, want_b, _, _ = bc.gradients(picked, gi, kernel, stride, 1.0)
     bound_w, bound_b = bc.grad_bounds(picked, gi, kernel, stride, 1.0)
     assert (np.abs(gw - want_w) <= bound_w).all() and (np.abs(gb - want_b) <= bound_b).all()
+
+
+@pytest.mark.parametrize('n', bc.BACKWARD_N)
+@pytest.mark.parametrize('rows,cols,kernel,stride,channels', bc.BACKWARD_CASES)
+def test_backward_within_the_bound_of_an_fp32_sum(rows, cols, kernel, stride, channels, n):
+    """grad_weight and grad_bias against the checker's fp64 gradients: |d grad_weight| <= gamma_(M + 1) |on| sum |grad_out bit|,
+    |d grad_bias| <= gamma_M sum |grad_out|, M = n OH OW; two calls give the same bits; without grad_bias nothing is written
+    there; and with an index that holds -1 and repeats."""
+    _backward_within_the_bound(rows, cols, kernel, stride, channels, n)
+
+
+@pytest.mark.parametrize('rows,cols,kernel,stride,channels,n', bc.BACKWARD_SHAPES)
+def test_backward_within_the_bound_at_every_path(rows, cols, kernel, stride, channels, n):
+    """The same test, bound and two-calls-give-the-same-bits check at the shapes of bc.BACKWARD_SHAPES: every kernel size, one to
+    four chunks of channels, and workgroups that walk one, two and three tiles."""
+    _backward_within_the_bound(rows, cols, kernel, stride, channels, n)
+
+
+def _raw_forward(src, n_frames, index, n, cfg, w, b):
+    """f110_bitconv_forward (int64 frames) or f110_bitconv_forward_u8 (uint8 images) itself, into an array of -7 with a margin
+    before and after it that must stay as it was -> the output on the host."""
+    import torch
+    from red_gym_amd import _lib
+    lib = _lib.load()
+    oh, ow = bc.out_size(cfg.rows, cfg.cols, cfg.kernel, cfg.stride)
+    size = n * cfg.channels * oh * ow
+    buf = torch.full((size + 128,), -7.0, dtype=torch.float32, device='cuda')
+    fn = lib.f110_bitconv_forward_u8 if src.dtype == torch.uint8 else lib.f110_bitconv_forward
+    _lib.check(fn(C.byref(cfg), src.data_ptr(), n_frames, None if index is None else index.data_ptr(), n, w.data_ptr(),
+                  None if b is None else b.data_ptr(), buf.data_ptr() + 64 * 4, torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    host = _np(buf)
+    assert (host[:64] == -7.0).all() and (host[64 + size:] == -7.0).all()
+    return host[64:64 + size].reshape(n, cfg.channels, oh, ow)
+
+
+FORWARD_VARIANTS = ((255.0, True, True), (1.0 / 255.0, False, False))      # (on, relu, bias); the cross product runs on bc.CASES
+
+
+@pytest.mark.parametrize('rows,cols,kernel,stride,channels', bc.SHAPES)
+def test_forward_equals_checker_at_every_path(rows, cols, kernel, stride, channels):
+    """Both entries `==` the checker as raw bit patterns at the shapes of bc.SHAPES (every kernel size, both branches of the mask,
+    the largest LDS footprint, full and partial tiles, the tail word, more than 16 channels on several tiles): the three images
+    of bc.images and rc.edge_images (single pixels at columns 0, 63, 64 and cols - 1), on = 255 with relu and bias, on = 1 / 255
+    without either, and an index with -1, a repeat and an entry beyond the frames; the output's margins stay as they were."""
+    from red_gym_amd import bitconv
+    w, b = bc.params(kernel, channels, seed=3)
+    wd, bd = _dev(w), _dev(b)
+    batches = (('abc', bc.images(rows, cols)), ('edge', rc.edge_images(rows, cols)))
+    total = 0
+    for name, imgs in batches:
+        srcs = (('packed', _packed(imgs)), ('uint8', _dev(imgs)))
+        for on, relu, bias in FORWARD_VARIANTS:
+            want = bc.forward(imgs, w, b if bias else None, stride, on, relu)
+            cfg = bitconv.make_config(rows, cols, kernel, stride, channels, on, relu)
+            for entry, src in srcs:
+                got = _raw_forward(src, len(imgs), None, len(imgs), cfg, wd, bd if bias else None)
+                bad = _differing(got, want)
+                print('%d x %d k%d s%d c%d %s %s on=%g relu=%s bias=%s: %d of %d elements differ' % (rows, cols, kernel, stride, channels, name, entry, on, relu, bias, bad, want.size))
+                total += bad
+            if name == 'abc':
+                assert (want[0] != want[1]).any() and (want[0] != want[2]).any()
+                assert not relu or channels < 5 or ((want == 0).any() and (want > 0).any())
+            elif not relu:      # the pixel at (row 0, column 0) is under window (0, 0); the arbitrary image is no other one
+                assert (want[2] != want[0]).any() and (want[-1] != want[0]).any() and (want[-1] != want[1]).any()
+    imgs = batches[0][1]
+    index = np.array([1, -1, 0, 0, len(imgs) + 5, 2], np.int64)
+    want = bc.forward(bc.pick(imgs, index), w, b, stride, 1.0, False)
+    assert (want[0] != want[2]).any() and (want[2] != want[1]).any() and (want[1] == want[4]).all() and (want[1] == want[5]).all()
+    cfg = bitconv.make_config(rows, cols, kernel, stride, channels, 1.0, False)
+    for src in (_packed(imgs), _dev(imgs)):
+        total += _differing(_raw_forward(src, len(imgs), _dev(index), len(index), cfg, wd, bd), want)
+    assert total == 0
+
+
+@pytest.mark.parametrize('rows,cols,kernel,stride,channels,n', bc.BACKWARD_SHAPES)
+def test_backward_exact_on_integer_gradients(rows, cols, kernel, stride, channels, n):
+    """grad_out of integers in [-4, 4] with n OH OW 4 < 2^24 (bc.exact_sums asserts it before anything runs here): every fp32
+    partial sum is an integer below 2^24, exact in any order and under any tiling, so grad_bias must `==` the sum and
+    grad_weight `==` fp32(sum) * fp32(on) -- every (sample, pixel, channel, tap) term present once, in its own place.  With
+    on in {1, 255, 1 / 255}, with and without grad_bias, with and without an index (-1, beyond the frames, repeats), and on a
+    workspace of NaN once per case."""
+    from red_gym_amd import bitconv
+    oh, ow = bc.out_size(rows, cols, kernel, stride)
+    frames5 = bc.many_images(rows, cols, bc.EXACT_FRAMES)
+    g = bc.exact_grad_out(n, channels, oh, ow)
+    gd = _dev(g)
+    bad = 0
+    for with_index in (False, True):
+        idx = bc.exact_index(n, with_index)
+        picked = bc.pick(frames5, idx)
+        sums = bc.exact_sums(picked, g, kernel, stride)
+        assert bc.holds_something(sums)
+        frames, n_frames, index = (_packed(frames5), bc.EXACT_FRAMES, _dev(idx)) if with_index else (_packed(picked), n, None)
+        for on in bc.EXACT_ONS:
+            want_w, want_b = bc.exact_gradients(sums, on)
+            cfg = bitconv.make_config(rows, cols, kernel, stride, channels, on)
+            for with_bias in (True, False):
+                gw, gb = _raw_backward(frames, n_frames, index, n, cfg, gd, with_bias=with_bias,
+                                       ws_fill=float('nan') if on == 255.0 and with_bias else -7.0)
+                dw, db = int((gw != want_w).sum()), int((gb != want_b).sum()) if with_bias else 0
+                print('%d x %d k%d s%d c%d n=%d index=%s on=%g bias=%s: %d of %d weights and %d of %d biases differ' % (
+                      rows, cols, kernel, stride, channels, n, with_index, on, with_bias, dw, want_w.size, db, want_b.size))
+                bad += dw + db
+    assert bad == 0
+
+
+def test_autograd_exact_beyond_one_chunk():
+    """conv_bits(...).backward() at 33 channels and kernel 7 (the wrapper sizes the workspace of three chunks): integer grad_out,
+    on = 1, no relu, from uint8 images and from packed frames with an index; weight.grad and bias.grad `==` the exact sums."""
+    from red_gym_amd.bitconv import conv_bits
+    rows, cols, kernel, stride, channels, n = 20, 400, 7, 5, 33, 4
+    assert (rows, cols, kernel, stride, channels) in [s[:5] for s in bc.BACKWARD_SHAPES]
+    oh, ow = bc.out_size(rows, cols, kernel, stride)
+    frames5 = bc.many_images(rows, cols, bc.EXACT_FRAMES)
+    idx = np.array([2, -1, 0, bc.EXACT_FRAMES - 1], np.int64)                  # two random frames, an empty sample, the all-set frame
+    picked = bc.pick(frames5, idx)
+    g = bc.exact_grad_out(n, channels, oh, ow)
+    sums = bc.exact_sums(picked, g, kernel, stride)
+    assert bc.holds_something(sums)
+    want_w, want_b = bc.exact_gradients(sums, 1.0)
+    w, b = bc.params(kernel, channels, seed=5)
+    out32 = bc.forward(picked, w, b, stride, 1.0, False)
+    for src, kw in ((_dev(picked), {}), (_packed(frames5), dict(cols=cols, index=_dev(idx)))):
+        wd, bd = _dev(w).requires_grad_(), _dev(b).requires_grad_()
+        out = conv_bits(src, wd, bd, stride=stride, on=1.0, relu=False, **kw)
+        assert _differing(out, out32) == 0
+        out.backward(_dev(g))
+        assert wd.grad.shape == wd.shape and (_np(wd.grad) == want_w).all() and (_np(bd.grad) == want_b).all()
+
+
+def test_forward_in_two_launches():
+    """2^23 + 3 samples of one tile each: bitconv_forward launches 2^23 workgroups and then 3 more from a.first = 2^23.  8 x 8
+    images, kernel 8, stride 8, one channel; an index over five packed frames (random, all-set, empty) with -1 entries, the last
+    three samples on three different frames; every output `==` the checker's for its frame."""
+    import torch
+    from red_gym_amd import _lib, bitconv
+    n = (1 << 23) + 3
+    assert bc.paths(8, 8, 8, 8, 1, n)['launches'] == 2 and bc.paths(8, 8, 8, 8, 1, n)['group'] == n - 3
+    rnd = rc.random_images(8, 8, n=3, seed=23)
+    imgs = np.stack([rnd[0], np.full((8, 8), 255, np.uint8), rnd[1], np.zeros((8, 8), np.uint8), rnd[2]])
+    w, b = bc.params(8, 1, seed=4)
+    want = bc.forward(np.concatenate([imgs, np.zeros((1, 8, 8), np.uint8)]), w, b, 8, 1.0, False)[:, 0, 0, 0]
+    assert len(set(bc.bit_patterns(want[:5]).tolist())) == 5 and want[5] == want[3]
+    idx = np.random.default_rng(23).integers(0, 5, n).astype(np.int64)
+    idx[5::1001] = -1
+    idx[-3:] = [0, 1, 2]
+    assert (idx[:-3] == -1).sum() > 8000 and all((idx[:-3] == f).sum() > 1000000 for f in range(5))
+    index, frames, wd, bd = _dev(idx), _packed(imgs), _dev(w), _dev(b)
+    buf = torch.full((n + 64,), -7.0, dtype=torch.float32, device='cuda')
+    cfg = bitconv.make_config(8, 8, 8, 8, 1, 1.0)
+    _lib.check(_lib.load().f110_bitconv_forward(C.byref(cfg), frames.data_ptr(), 5, index.data_ptr(), n, wd.data_ptr(), bd.data_ptr(),
+                                                buf.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    gathered = _dev(want)[torch.where(index < 0, 5, index)]
+    assert bool((buf[n:] == -7.0).all())
+    wrong = int((buf[:n].view(torch.int32) != gathered.view(torch.int32)).sum())
+    print('%d of %d outputs differ; the last three: %s, wanted %s' % (wrong, n, _np(buf[n - 3:n]), want[idx[-3:]]))
+    assert wrong == 0 and torch.equal(buf[:n].view(torch.int32), gathered.view(torch.int32))
+    assert np.array_equal(bc.bit_patterns(_np(buf[n - 16:n])), bc.bit_patterns(want[np.where(idx[-16:] < 0, 5, idx[-16:])]))
 
 
 @pytest.mark.parametrize('rows,cols,kernel,stride,channels', bc.BACKWARD_CASES)
