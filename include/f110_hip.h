@@ -516,7 +516,8 @@ int f110_shaping_update(f110_handle *h, void *stream);
  * the env's clock as for the shaper: current_time == timestep exactly (reset by its last step): path_index = -1; current_time
  * == t_seen (a masked reset left it alone): untouched.
  * f110_pathfollow_validate: host only.  F110_E_INVALID for agent outside 0..num_agents-1, horizon or replan_at outside 1..8,
- * a weight of R <= 0, a weight of Q or P < 0, a scalar that is not finite, vector_length or timestep <= 0.
+ * a weight of R <= 0, a weight of Q or P < 0, a scalar that is not finite, vector_length or timestep <= 0, max_diff_deg,
+ * max_steer or dist_threshold < 0 (car_length and desired_velocity may be negative).
  * f110_pathfollow_install: cfg NULL removes the follower; a refused cfg installs nothing.  It builds and uploads the QP's
  * tables (cold path, synchronises).  Install, removal and bind move the launch epoch.  _act and _update: one kernel each on
  * `stream`, no allocation, no synchronisation (capturable).  raw_actions dev [B,16]; actions_out dev [B, num_agents, 2]:

@@ -449,6 +449,11 @@ extern "C" int f110_pathfollow_validate(const f110_pathfollow_config *cfg, int32
         if (cfg->q[i] < 0.0 || cfg->p[i] < 0.0) return fail(F110_E_INVALID, "%s: state weight q[%d] = %g / p[%d] = %g is negative", who, i, cfg->q[i], i, cfg->p[i]);
     if (!(cfg->vector_length > 0.0)) return fail(F110_E_INVALID, "%s: vector_length %g must be positive (the spline's knots are the chord lengths)", who, cfg->vector_length);
     if (!(cfg->timestep > 0.0)) return fail(F110_E_INVALID, "%s: timestep %g must be positive", who, cfg->timestep);
+    // limits of a clip and a distance: negative, the kernel's selects and the reference's np.clip (lower bound above upper) disagree.
+    // car_length and desired_velocity may be negative (a point behind the axle, a path followed backwards from its first point).
+    if (cfg->max_diff_deg < 0.0 || cfg->max_steer < 0.0 || cfg->dist_threshold < 0.0)
+        return fail(F110_E_INVALID, "%s: max_diff_deg %g, max_steer %g and dist_threshold %g must not be negative", who, cfg->max_diff_deg,
+                    cfg->max_steer, cfg->dist_threshold);
     return F110_OK;
 }
 

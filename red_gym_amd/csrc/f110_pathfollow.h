@@ -13,6 +13,10 @@
 // PF_TOL_U outside a bound is clamped onto it and counts as feasible; a multiplier within PF_TOL_G * max(1, |f|_inf) of zero
 // counts as having the right sign (the variable stays bound) -- both change u by far less than the 1e-9 the tests allow.
 // fp64; sin / cos / atan2 / fmod are the device library's: the tests allow 1e-9 * max(1, |value|).
+// Non-finite inputs (a diverged policy's NaN action, a NaN or infinite velocity) stay in their env: the points from the first
+// non-finite row on, or the env's acceleration and action, come out non-finite; no index is formed from such a value (the spline
+// piece is a count of comparisons, the free set a bit mask), the walk ends at PF_QP_LIMIT at the latest and may raise
+// DEVERR_QP_LIMIT, and no other env changes by a bit -- the lane exchanges never leave the env's own pair of lanes.
 #pragma once
 #include "f110_kernels.h"
 #include "f110_shaping.h"

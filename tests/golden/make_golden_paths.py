@@ -38,8 +38,12 @@ def _raise(*a, **k):
     raise _Stop()
 
 
-def controller_frame(sal, path, vx, vy):
+def controller_frame(sal, path, vx, vy, cfg=None):
+    """(dists, ref_traj) of MPC_controller with SAL's MPC_PARAMS, or with the options of a tests/path_cases.py config."""
     p = sal.SACF110Env.MPC_PARAMS
+    if cfg is not None:
+        p = dict(p, desired_velocity=cfg['desired_velocity'], timestep=cfg['timestep'], horizon_length=cfg['horizon'],
+                 state_cost=np.diag(cfg['q']), input_cost=np.diag(cfg['r']), terminal_cost=np.diag(cfg['p']))
     try:
         sal.MPC_controller(path=path, desiredVelocity=p['desired_velocity'], timeStep=p['timestep'], totalSteps=p['total_steps'],
                            horizonLength=p['horizon_length'], stateCost=p['state_cost'], inputCost=p['input_cost'],

@@ -73,8 +73,7 @@ def test_g17_through_the_function_level_entries(golden):
             f.writelines('%-28s %.3g\n' % kv for kv in sorted(WORST.items()))
 
 
-@pytest.mark.parametrize('cfg', [dict(), dict(horizon=1, r=(0.02, 0.3)), dict(horizon=3, q=(2.0, 0.5, 0.0, 0.3), r=(0.05, 0.2), p=(4.0, 20.0, 0.5, 2.0)),
-                                 dict(horizon=8, timestep=0.05, desired_velocity=3.0, p=(30.0, 30.0, 3.0, 3.0))])
+@pytest.mark.parametrize('cfg', pc.QP_CONFIGS)              # every horizon 1..8; the first four are the first tests' own
 def test_qp_equals_the_enumerators_optimum(golden, cfg):
     from red_gym_amd import pathfollow
     g = golden('g17_paths.npz')
@@ -119,7 +118,10 @@ def _snapshot(env):
     return {k: b[k].cpu().numpy().copy() for k in ('path_points', 'path_index', 'path_replanned', 'mpc_accel')}
 
 
-@pytest.mark.parametrize('B,A,agent,cfg,steps', [(65, 1, 0, dict(dist_threshold=1.29, replan_at=2), 70), (33, 2, 1, dict(), 30)])
+# the third: short chords and a fast reference, so that the end clamp and the late spline pieces run through act (has_vy = 0, the
+# engine's strides)
+@pytest.mark.parametrize('B,A,agent,cfg,steps', [(65, 1, 0, dict(dist_threshold=1.29, replan_at=2), 70), (33, 2, 1, dict(), 30),
+                                                 (33, 1, 0, dict(vector_length=0.25, desired_velocity=4.7, horizon=8, replan_at=3, dist_threshold=1.29), 20)])
 def test_closed_loop_equals_checker_through_resets(assets, B, A, agent, cfg, steps):
     """Seeded raw actions that change every step; the checker is fed the device's poses and velocities step by step.  A quarter
     of the envs of the first configuration is spawned across the track and driven at the wall (the follower's action is
@@ -309,3 +311,176 @@ def test_indices_stay_in_bounds(assets, golden):
     assert int(i.min()) >= -1 and int(i.max()) <= 3
     assert env.eng.device_errors() == 0
     env.close()
+
+
+# ---------------------------------------------------------------- off the defaults (tests/path_cases.py: CONFIGS and the case families)
+def _mpc(paths, vels, **cfg):
+    """mpc_controls in the chunks of _chunks: dict of NumPy arrays, `errors` or-ed."""
+    from red_gym_amd import pathfollow
+    H = pc.config(**cfg)['horizon']
+    n = paths.shape[0]
+    out = dict(dists=np.zeros((n, 8)), ref_traj=np.zeros((n, H + 1, 4)), accel=np.zeros((n, 2)), actions=np.zeros((n, 2)),
+               qp_steps=np.zeros((n, 2), dtype=np.int32), errors=0)
+    for m in _chunks(n):
+        o = pathfollow.mpc_controls(_dev(paths[m]), _dev(vels[m]), **cfg)
+        for k in out:
+            if k == 'errors':
+                out[k] |= o[k]
+            else:
+                out[k][m] = o[k].cpu().numpy()
+    return out
+
+
+def _decode(raw, poses, **cfg):
+    from red_gym_amd import pathfollow
+    out = np.zeros((raw.shape[0], 8, 2))
+    for m in _chunks(raw.shape[0]):
+        out[m] = pathfollow.decode_paths(_dev(raw[m]), _dev(poses[m]), **cfg).cpu().numpy()
+    return out
+
+
+@pytest.mark.parametrize('name', list(pc.CONFIGS))
+def test_g19_through_the_function_level_entries(golden, name):
+    g = golden('g19_path_configs.npz')
+    cfg = pc.CONFIGS[name]['cfg']
+    raw, poses, vels = pc.g19_inputs(name)
+    rec = {k: g['%s/%s' % (name, k)] for k in ('paths', 'dists', 'ref_traj', 'conv_out')}
+    _close(name + ' paths', _decode(raw, poses, **cfg), rec['paths'])
+    out = _mpc(rec['paths'], vels, **cfg)
+    assert out['errors'] == 0
+    _close(name + ' dists', out['dists'], rec['dists'])
+    _close(name + ' ref_traj', out['ref_traj'], rec['ref_traj'])
+    _close(name + ' (steer, speed)', out['actions'], rec['conv_out'])
+
+
+def _same_steps(what, steps, info):
+    """Where the transcribed walk's step counts do not hang on rounding (path_cases.step_stable) the device takes as many steps:
+    the same faces in the same order.  (u is never compared with the transcription, only with the enumerator.)"""
+    m = info['stable']
+    print('%s: %d of %d walks step-stable; device steps == transcription on %d of them' % (what, m.sum(), m.size, (steps[m] == info['steps'][m]).sum()))
+    assert np.array_equal(steps[m], info['steps'][m])
+
+
+@pytest.mark.parametrize('name', ['bound2', 'bound5', 'bound8'])
+def test_optimum_on_the_edge_of_a_bound(name):
+    """No cycling and no wrong face at the walk's tolerances: the unconstrained optimum or a multiplier within 0, 1e-13, 1e-11, 1e-8
+    of a bound, either side."""
+    f = pc.family(name)
+    H = f['cfg']['horizon']
+    out = _mpc(f['paths'], f['vels'], horizon=H)
+    err = np.abs(out['accel'] - f['info']['u'][:, :, 0]).max()
+    agree = (out['qp_steps'] == f['info']['steps']).mean()
+    print('%s: %d cases, largest |u_0 - u*_0| = %.3g, steps <= %d (%.0f %% as the transcribed walk)' % (name, f['paths'].shape[0], err, out['qp_steps'].max(), 100 * agree))
+    WORST[name] = err
+    assert err <= 1e-9 and out['errors'] == 0
+    assert out['qp_steps'].min() >= 1 and out['qp_steps'].max() <= 4 * H + 2
+    _same_steps(name, out['qp_steps'], f['info'])
+
+
+def test_weights_at_the_edge_of_validate():
+    """r = 1e-6 with q = p = 0 (a diagonal Hessian) and r = 1e-6 with p = 1e4 at horizon 8 (condition ~ 1e9): the device is allowed
+    max(1e-9, 16 * e_ref), e_ref the enumerator's own fp64-against-longdouble difference (tests/path_cases.py stiff_cases; 16 for
+    the device's table inversion and order of sums).  `errors` is the whole device error word of the call: no step limit reached,
+    and in the bounds-checked build no index reported."""
+    dg = pc.family('diagonal')
+    out = _mpc(dg['paths'], dg['vels'], **pc.EDGE_DIAGONAL)
+    assert out['errors'] == 0 and np.array_equal(out['accel'], dg['info']['u'][:, :, 0]) and (out['qp_steps'] == 1).all()
+    st = pc.family('stiff')
+    out = _mpc(st['paths'], st['vels'], **pc.EDGE_STIFF)
+    tol = max(1e-9, 16 * st['e_ref'])
+    err = np.abs(out['accel'] - st['want']).max()
+    print('stiff: e_ref %.3g, allowed %.3g, device %.3g; steps <= %d (transcribed walk <= %d)' % (st['e_ref'], tol, err, out['qp_steps'].max(), st['info']['steps'].max()))
+    WORST['stiff'] = err
+    assert out['errors'] == 0 and err <= tol
+    assert out['qp_steps'].min() >= 1 and out['qp_steps'].max() <= 4 * 8 + 2
+    _same_steps('stiff', out['qp_steps'], st['info'])
+    # the order of the releases: cases on which releasing the first wrong-signed multiplier instead of the worst takes another
+    # number of steps to the same optimum
+    ro = pc.family('release_order')
+    out = _mpc(ro['paths'], ro['vels'], **pc.EDGE_STIFF)
+    err = np.abs(out['accel'] - ro['info']['u'][:, :, 0]).max()
+    print('release order: %d cases, device %.3g; worst-first steps %s, first-first %s, device %s'
+          % (ro['paths'].shape[0], err, ro['info']['steps'][ro['tells']].tolist(), ro['first'][ro['tells']].tolist(), out['qp_steps'][ro['tells']].tolist()))
+    WORST['release order'] = err
+    assert out['errors'] == 0 and err <= tol and ro['tells'].sum() >= 6
+    _same_steps('release order', out['qp_steps'], ro['info'])
+
+
+def test_nonuniform_chords_and_a_stationary_point():
+    """mpc_controls takes any path: chords in ratios of 1 : 4 and 4 : 1 (the elimination has no pivoting), against the dense solve of
+    reference_states; and a path that turns back on itself, with a reference state on the spline's stationary point: rv = (0, 0)."""
+    paths = pc.nonuniform_paths(pc.g17_paths())
+    for cfg in (dict(horizon=8), dict(horizon=8, desired_velocity=4.7)):   # the second: pieces 4..6 and the clamp, the far not-a-knot row's slopes themselves
+        c = pc.config(**cfg)
+        vels = pc.built_cases(paths, c, 2120)
+        out = _mpc(paths, vels, **cfg)
+        x, ref = pc.reference_states(paths, c)
+        assert out['errors'] == 0 and all(np.isfinite(out[k]).all() for k in ('dists', 'ref_traj', 'accel', 'actions'))
+        _close('non-uniform dists', out['dists'], x)
+        _close('non-uniform ref_traj', out['ref_traj'], ref)
+        _close('non-uniform accel', out['accel'], pc.mpc_accel(paths, vels, c)[0])
+    paths, c, k = pc.stationary_case()
+    cfg = {key: c[key] for key in ('desired_velocity', 'timestep', 'horizon')}
+    vels = np.array([[1.0, 0.0], [0.0, -0.5]])
+    out = _mpc(paths, vels, **cfg)
+    x, ref = pc.reference_states(paths, c)
+    assert out['errors'] == 0 and all(np.isfinite(out[key]).all() for key in ('dists', 'ref_traj', 'accel', 'actions'))
+    assert (out['ref_traj'][:, k, 2:] == 0.0).all()
+    _close('stationary ref_traj', out['ref_traj'], ref)
+    _close('stationary accel', out['accel'], pc.mpc_accel(paths, vels, c)[0])
+
+
+def test_exact_directions_and_negative_lengths():
+    """Rows exactly behind the car, (-a, +0.0) and (-a, -0.0), zero rows and poses beyond 2 pi: the wrap's argument is exactly 0 or
+    2 pi and the turn direction is the checker's.  And the two options validate lets be negative."""
+    raw, poses = pc.exact_direction_cases()
+    want = pc.decode(raw, poses)
+    got = _decode(raw, poses)
+    _close('exact directions', got, want)
+    # the direction of the turn, read off the paths: the sign of the cross product of neighbouring chords
+    def turns(p):
+        d = np.diff(np.concatenate([np.zeros((p.shape[0], 1, 2)), p], axis=1), axis=1)[:, 1:]
+        cross = d[:, :-1, 0] * d[:, 1:, 1] - d[:, :-1, 1] * d[:, 1:, 0]
+        return np.sign(np.where(np.abs(cross) > 1e-6, cross, 0.0))
+    assert np.array_equal(turns(got), turns(want)) and (turns(want) < 0).any()
+    g = pc.g17_paths()[:65]
+    cfg = dict(car_length=-0.3, desired_velocity=-2.0)
+    raw, poses, vels = pc.designed_raw(65, 2300), pc.designed_poses(65, 2301), pc.designed_vels(65, 2302)
+    _close('negative car_length', _decode(raw, poses, **cfg), pc.decode(raw, poses, pc.config(**cfg)))
+    out = _mpc(g, vels, **cfg)
+    x, ref = pc.reference_states(g, pc.config(**cfg))
+    assert out['errors'] == 0
+    _close('negative velocity ref_traj', out['ref_traj'], ref)
+    _close('negative velocity accel', out['accel'], pc.mpc_accel(g, vels, pc.config(**cfg))[0])
+
+
+def test_nonfinite_inputs_stay_in_their_env():
+    """A diverged policy: NaN raw actions in envs 7 and 64 of 130, NaN / inf velocities in envs 8 and 65.  Every other env's outputs
+    are `==` to the same batch without them (the lane exchange never crosses envs), the walks end within the step limit and the
+    error word holds at most DEVERR_QP_LIMIT -- in the bounds-checked build too: every index comes from bit masks and selects."""
+    from red_gym_amd import pathfollow
+    n = 130
+    raw, poses, vels = pc.designed_raw(n, 2400), pc.designed_poses(n, 2401), pc.designed_vels(n, 2402)
+    clean_paths = pathfollow.decode_paths(_dev(raw), _dev(poses)).cpu().numpy()
+    bad_raw = raw.copy()
+    bad_raw[7, 5], bad_raw[64] = np.nan, np.nan
+    paths = pathfollow.decode_paths(_dev(bad_raw), _dev(poses)).cpu().numpy()
+    others = np.ones(n, dtype=bool)
+    others[[7, 64]] = False
+    assert np.array_equal(paths[others], clean_paths[others])
+    # the points in front of the first NaN row are untouched (row 0 of the action is never read), the others are NaN
+    assert np.array_equal(paths[7, :2], clean_paths[7, :2]) and np.isnan(paths[7, 2:]).all()
+    assert np.array_equal(paths[64, :1], clean_paths[64, :1]) and np.isnan(paths[64, 1:]).all()
+    for H in (5, 8):
+        clean = pathfollow.mpc_controls(_dev(clean_paths), _dev(vels), horizon=H)
+        assert clean['errors'] == 0
+        bad_vels = vels.copy()
+        bad_vels[8, 0], bad_vels[65] = np.nan, (np.inf, -np.inf)
+        out = pathfollow.mpc_controls(_dev(paths), _dev(bad_vels), horizon=H)     # NaN paths in 7 and 64, non-finite velocities in 8 and 65
+        others[[8, 65]] = False
+        for k in ('dists', 'ref_traj', 'accel', 'actions', 'qp_steps'):
+            assert np.array_equal(out[k].cpu().numpy()[others], clean[k].cpu().numpy()[others]), k
+        steps = out['qp_steps'].cpu().numpy()
+        print('H = %d: steps of the non-finite envs %s, error word %d' % (H, steps[~others].tolist(), out['errors']))
+        assert steps.min() >= 1 and steps.max() <= pc.QP_LIMIT
+        assert out['errors'] & ~pc.DEVERR_QP_LIMIT == 0
