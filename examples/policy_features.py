@@ -1,15 +1,17 @@
-"""Closed loop of shaper + path follower + replay buffer in which the policy's first layer reads bits: acting on the env's uint8
-lidar_bitmap and learning from the ring's packed frames without an fp32 image ever existing.
+"""Closed loop of shaper + path follower + replay buffer in which the policy's stem reads bits: acting on the env's uint8
+lidar_bitmap through conv1 + relu + conv2 in one kernel, and learning from the ring's packed frames through the same module with
+grad on, without an fp32 image ever existing.
     python examples/policy_features.py [envs] [steps]
 The reference's Actor opens with nn.Conv2d(1, 16, kernel_size=8, stride=4) (src/SAL.py:397) on FloatTensor(state) / 255 (:510) when
 it acts and on the raw 0 / 255 images when it learns (:536).  BitConv2d shares that layer's parameters and computes it from bits;
-a linear head on the features stands in for the rest of the network."""
+BitConvStem does the same for the pair conv1, conv2 = nn.Conv2d(16, 32, kernel_size=4, stride=2) (:398) that both networks continue
+with, fused when it acts.  A linear head on the features stands in for the rest of the network."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from red_gym_amd import F110VecEnv, workload
-from red_gym_amd.bitconv import BitConv2d
+from red_gym_amd.bitconv import BitConv2d, BitConvStem
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 STEPS = int(sys.argv[2]) if len(sys.argv) > 2 else 40
@@ -21,11 +23,13 @@ torch.manual_seed(0)
 conv1 = torch.nn.Conv2d(1, 16, kernel_size=8, stride=4).to(env.device)          # the reference's Actor.conv1
 act_layer = BitConv2d.from_conv(conv1, on=1.0, relu=True)                      # select_action: state / 255
 learn_layer = BitConv2d.from_conv(conv1, on=255.0, relu=True, cols=env.eng.shaper.cfg.cols)   # update: the raw 0 / 255 floats
-head = torch.nn.Linear(16, 16).to(env.device).double()
+conv2 = torch.nn.Conv2d(16, 32, kernel_size=4, stride=2).to(env.device)         # the reference's Actor.conv2
+stem = BitConvStem.from_convs(conv1, conv2, on=1.0, cols=env.eng.shaper.cfg.cols)   # relu(conv2(relu(conv1(x)))), the same four tensors
+head = torch.nn.Linear(32, 16).to(env.device).double()
 obs, reward, done, info = env.reset(torch.as_tensor(workload.spawn_poses(B, 1), device=env.device))
 for k in range(STEPS):
     with torch.no_grad():
-        feats = act_layer(info['lidar_bitmap'])                                    # [B, 16, 63, 63] from uint8, no fp32 image
+        feats = stem(info['lidar_bitmap'])                                         # [B, 32, 30, 30]: fused, conv1's [B, 16, 63, 63] is never written
         raw = torch.tanh(head(feats.mean(dim=(2, 3)).double()))
     obs, reward, done, info = env.step(env.path_actions(raw))
 print('acting: lidar_bitmap %s %s -> features %s %s' % (tuple(info['lidar_bitmap'].shape), info['lidar_bitmap'].dtype, tuple(feats.shape), feats.dtype))
@@ -36,6 +40,9 @@ loss = ((f_s.mean(dim=(1, 2, 3)) - r.float()) ** 2).mean() + f_ns.mean()
 loss.backward()
 print('learning: frames %s %s (a view of the ring), %d of %d draws valid -> features %s, grad weight %s, grad bias %s'
       % (tuple(frames.shape), frames.dtype, int(ok.sum()), n, tuple(f_s.shape), tuple(conv1.weight.grad.shape), tuple(conv1.bias.grad.shape)))
+f2 = stem(frames, index=s_idx)                                                     # grad on: conv_bits -> F.conv2d -> relu, differentiable
+f2.mean().backward()
+print('stem: acting features %s (no grad_fn: %s), learning features %s, grad conv2.weight %s' % (tuple(feats.shape), feats.grad_fn is None, tuple(f2.shape), tuple(conv2.weight.grad.shape)))
 rows, cols = env.eng.shaper.cfg.rows, env.eng.shaper.cfg.cols
 print('bytes not moved: acting %.1f MB per step (the fp32 copy of %d bitmaps, written and read again), learning %.1f MB per batch '
       '(two fp32 images per transition, written and read again)' % (2 * B * rows * cols * 4 / 1e6, B, 2 * 2 * n * rows * cols * 4 / 1e6))

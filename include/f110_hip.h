@@ -640,6 +640,39 @@ int f110_bitconv_forward_u8(const f110_bitconv_config *cfg, const uint8_t *image
 int f110_bitconv_backward(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
                           const float *grad_out, float *grad_weight, float *grad_bias, float *workspace, void *stream);
 
+/* Policy stem for acting: relu(conv2(relu(conv1(x)))) of the reference's Actor and Critic (src/SAL.py:397-398, 405-406, 429-430,
+ * 436-437; conv2 = nn.Conv2d(16, 32, kernel_size=4, stride=2)) from bits in one kernel.  The first layer's activations never
+ * reach memory: `out` [n, channels2, OH2, OW2] fp32 is all that is written, OH2 = (OH1 - kernel2) / stride2 + 1 on the first
+ * layer's OH1 = (rows - kernel) / stride + 1, OW2 likewise.  Stateless, forward only (learning keeps f110_bitconv_forward and
+ * _backward with the framework's second layer); cfg host, all arrays dev; launches on `stream` of the calling thread's current
+ * device, no allocation, no synchronisation, no atomics.  frames / images / index / n_frames / n as for f110_bitconv_forward and
+ * f110_bitconv_forward_u8; w1 [channels, 1, kernel, kernel], b1 [channels] or NULL, w2 [channels2, channels, kernel2, kernel2],
+ * b2 [channels2] or NULL, all fp32 and finite.  F110_E_INVALID for a null frames, w1, w2 or out with n > 0; n == 0 does nothing.
+ * Numerics.  Layer 1 is the contract of f110_bitconv_forward unchanged, with `on`, b1 (or NULL) and `relu`; call its result a1
+ * [channels, OH1, OW1].  Layer 2 in fp32: acc = 0; for ci major, then ky, then kx minor: acc = fmaf(w2[co][ci][ky][kx],
+ * a1[ci][stride2 oy + ky][stride2 ox + kx], acc), one rounding per step; out = acc + b2[co] (+ 0.0f for NULL); then out < 0 ? 0
+ * : out if relu2.  The output is a function of the bits and the four parameter tensors alone: two calls give the same bits, and
+ * a sample's result depends neither on n nor on its place in the batch.
+ * f110_bitconv2_validate: host only.  F110_E_INVALID for what f110_bitconv_validate refuses in the first layer's fields, for
+ * channels outside 1..16, kernel2 outside 1..4, stride2 outside 1..kernel2, channels2 outside 1..64, for OH1 or OW1 below
+ * kernel2, and for a first layer's output wider than 64 (OW1 > 64: the kernel works on whole rows of it and has no halo in x;
+ * any number of rows is accepted). */
+typedef struct {
+    int32_t rows, cols;         /* the image */
+    int32_t kernel, stride;     /* layer 1, as f110_bitconv_config */
+    int32_t channels;           /* layer 1 output channels, 1..16 */
+    int32_t relu;               /* between the layers */
+    float on;                   /* the value of a set pixel */
+    int32_t kernel2, stride2;   /* layer 2: kernel2 1..4, stride2 1..kernel2 */
+    int32_t channels2;          /* 1..64 */
+    int32_t relu2;              /* nonzero: max(out, 0) */
+} f110_bitconv2_config;
+int f110_bitconv2_validate(const f110_bitconv2_config *cfg);
+int f110_bitconv2_forward(const f110_bitconv2_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
+                          const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream);
+int f110_bitconv2_forward_u8(const f110_bitconv2_config *cfg, const uint8_t *images, int64_t n_frames, const int64_t *index, int64_t n,
+                             const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream);
+
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).
  * scans_f32 / lookups may be NULL; lookups [n] is overwritten-by-accumulation like

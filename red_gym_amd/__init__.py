@@ -17,7 +17,7 @@ def __getattr__(name):
     if name in ('lidar_to_bitmap', 'LidarBitmap', 'scan_occupancy'):
         from . import lidar
         return getattr(lidar, name)
-    if name in ('conv_bits', 'BitConv2d'):
+    if name in ('conv_bits', 'BitConv2d', 'conv_bits2', 'BitConvStem'):
         from . import bitconv
         return getattr(bitconv, name)
     raise AttributeError(name)

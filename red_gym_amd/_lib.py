@@ -101,6 +101,13 @@ class BitconvConfig(C.Structure):
                 ('channels', C.c_int32), ('relu', C.c_int32), ('on', C.c_float)]
 
 
+# f110_bitconv2_config: the policy stem (conv1 + relu + conv2) from bits, forward only (stateless)
+class Bitconv2Config(C.Structure):
+    _fields_ = [('rows', C.c_int32), ('cols', C.c_int32), ('kernel', C.c_int32), ('stride', C.c_int32),
+                ('channels', C.c_int32), ('relu', C.c_int32), ('on', C.c_float),
+                ('kernel2', C.c_int32), ('stride2', C.c_int32), ('channels2', C.c_int32), ('relu2', C.c_int32)]
+
+
 # every symbol include/f110_hip.h declares: name -> argtypes (restype int unless noted)
 _VP, _I32, _I64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -180,6 +187,9 @@ SYMBOLS = {
     'f110_bitconv_forward': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP],
     'f110_bitconv_forward_u8': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP],
     'f110_bitconv_backward': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP],
+    'f110_bitconv2_validate': [C.POINTER(Bitconv2Config)],
+    'f110_bitconv2_forward': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_bitconv2_forward_u8': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_replay_pack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_replay_unpack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],

@@ -11,6 +11,7 @@ import torch
 from . import _lib
 
 MAX_KERNEL, MAX_CHANNELS = 8, 64
+MAX_KERNEL2, MAX_STEM_CHANNELS, MAX_STEM_WIDTH = 4, 16, 64     # conv_bits2: kernel2, the first layer's channels and output width
 
 
 def make_config(rows, cols, kernel, stride=1, channels=1, on=1.0, relu=False):
@@ -35,6 +36,34 @@ def validate(rows, cols, kernel, stride=1, channels=1, on=1.0, relu=False):
 
 def output_size(rows, cols, kernel, stride):
     return (rows - kernel) // stride + 1, (cols - kernel) // stride + 1
+
+
+def make_config2(rows, cols, kernel, stride, channels, kernel2, stride2, channels2, on=1.0, relu1=True, relu2=True):
+    """An f110_bitconv2_config, clamped like make_config."""
+    c = _lib.Bitconv2Config()
+    clamp = lambda v: max(min(int(v), 2 ** 31 - 1), -2 ** 31)  # noqa: E731
+    c.rows, c.cols, c.kernel, c.stride, c.channels = clamp(rows), clamp(cols), clamp(kernel), clamp(stride), clamp(channels)
+    c.kernel2, c.stride2, c.channels2 = clamp(kernel2), clamp(stride2), clamp(channels2)
+    c.relu, c.relu2 = (1 if relu1 else 0), (1 if relu2 else 0)
+    c.on = float(on)
+    return c
+
+
+def validate2(rows, cols, kernel, stride, channels, kernel2, stride2, channels2, on=1.0, relu1=True, relu2=True):
+    """f110_bitconv2_validate (host only, no device): ValueError for what the fused stem refuses -- everything validate()
+    refuses in the first layer, more than 16 first-layer channels, kernel2 outside 1..4, stride2 outside 1..kernel2, channels2
+    outside 1..64, a first-layer output smaller than kernel2 or wider than 64."""
+    on = float(on)
+    if math.isfinite(on) and abs(on) > 3.4028234663852886e38:
+        raise ValueError('bitconv: `on` = %g is not finite in fp32' % on)
+    c = make_config2(rows, cols, kernel, stride, channels, kernel2, stride2, channels2, on, relu1, relu2)
+    _lib.check(_lib.load().f110_bitconv2_validate(C.byref(c)))
+    return c
+
+
+def output_size2(rows, cols, kernel, stride, kernel2, stride2):
+    oh, ow = output_size(rows, cols, kernel, stride)
+    return (oh - kernel2) // stride2 + 1, (ow - kernel2) // stride2 + 1
 
 
 def _stream(dev):
@@ -129,6 +158,72 @@ def conv_bits(frames, weight, bias=None, stride=1, on=1.0, relu=False, index=Non
     return _ConvBits.apply(frames.contiguous(), weight, bias, index, cfg, n, u8)
 
 
+def _frames_kind(who, frames, cols):
+    """(u8, rows, cols) of `frames` for `who`, with conv_bits' checks."""
+    if frames.dim() != 3:
+        raise ValueError('%s: frames must be [m, rows, words] int64 or [m, rows, cols] uint8, not %s' % (who, tuple(frames.shape)))
+    rows = int(frames.shape[1])
+    if frames.dtype == torch.uint8:
+        if cols is not None and int(cols) != frames.shape[2]:
+            raise ValueError('%s: cols=%d but the uint8 images have %d columns' % (who, int(cols), frames.shape[2]))
+        return True, rows, int(frames.shape[2])
+    if frames.dtype == torch.int64:
+        if cols is None:
+            raise ValueError('%s: packed frames need cols=' % who)
+        cols = int(cols)
+        if cols < 1 or frames.shape[2] != (cols + 63) // 64:
+            raise ValueError('%s: %d words per row do not hold %d pixels' % (who, frames.shape[2], cols))
+        return False, rows, cols
+    raise ValueError('%s: frames must be int64 (packed) or uint8, not %s' % (who, frames.dtype))
+
+
+def conv_bits2(frames, w1, b1, w2, b2, stride1=1, stride2=1, on=1.0, relu1=True, relu2=True, index=None, cols=None):
+    """conv2(relu(conv1(frames))) of the reference's Actor / Critic in one kernel (csrc/f110_bitconv2.h), for acting: the first
+    layer's activations stay in LDS, only the second layer's output is written.
+    frames, index, cols, on: as conv_bits.  w1 [C1, 1, k1, k1] and b1 [C1] or None: the first layer, as conv_bits' weight and
+    bias (C1 <= 16, and its output at most 64 wide); w2 [C2, C1, k2, k2] fp32 and b2 [C2] or None on the frames' device (k2 <= 4,
+    C2 <= 64); relu1 between the layers, relu2 on the output.
+    Inference only: the returned [n, C2, OH2, OW2] fp32 tensor has no grad_fn whatever the parameters require (training goes
+    through conv_bits and torch's conv2d: BitConvStem chooses).  Always the fused kernel, on the caller's current stream,
+    without synchronising.  Numerics: the first layer exactly as conv_bits, the second acc = fma(w2[co][ci][ky][kx], a1, acc)
+    for ci major, ky, kx minor from 0, + b2 -- a function of the bits and the four tensors alone (include/f110_hip.h).
+    ValueError for what f110_bitconv2_validate refuses and for a dtype / shape mismatch."""
+    who = 'conv_bits2'
+    if not torch.is_tensor(frames) or not torch.is_tensor(w1) or not torch.is_tensor(w2):
+        raise ValueError('%s: frames, w1 and w2 must be tensors' % who)
+    if not frames.is_cuda or w1.device != frames.device or w2.device != frames.device:
+        raise ValueError('%s: frames, w1 and w2 must be on the same GPU' % who)
+    if w1.dtype != torch.float32 or w1.dim() != 4 or w1.shape[1] != 1 or w1.shape[2] != w1.shape[3]:
+        raise ValueError('%s: w1 must be fp32 [C1, 1, k1, k1], not %s %s' % (who, w1.dtype, tuple(w1.shape)))
+    c1, k1 = int(w1.shape[0]), int(w1.shape[2])
+    if w2.dtype != torch.float32 or w2.dim() != 4 or w2.shape[1] != c1 or w2.shape[2] != w2.shape[3]:
+        raise ValueError('%s: w2 must be fp32 [C2, %d, k2, k2], not %s %s' % (who, c1, w2.dtype, tuple(w2.shape)))
+    c2, k2 = int(w2.shape[0]), int(w2.shape[2])
+    for name, b, ch in (('b1', b1, c1), ('b2', b2, c2)):
+        if b is not None and (not torch.is_tensor(b) or b.dtype != torch.float32 or tuple(b.shape) != (ch,) or b.device != frames.device):
+            raise ValueError('%s: %s must be fp32 [%d] on the frames\' device' % (who, name, ch))
+    u8, rows, cols = _frames_kind(who, frames, cols)
+    cfg = validate2(rows, cols, k1, stride1, c1, k2, stride2, c2, on, relu1, relu2)
+    if index is not None:
+        if not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 1 or index.device != frames.device:
+            raise ValueError('%s: index must be an int64 vector on the frames\' device' % who)
+        index = index.contiguous()
+        n = int(index.shape[0])
+    else:
+        n = int(frames.shape[0])
+    lib = _lib.load()
+    dev = frames.device
+    frames = frames.contiguous()
+    tensors = [None if t is None else t.detach().contiguous() for t in (w1, b1, w2, b2)]
+    oh2, ow2 = output_size2(rows, cols, k1, stride1, k2, stride2)
+    out = torch.empty((n, c2, oh2, ow2), dtype=torch.float32, device=dev)
+    fn = lib.f110_bitconv2_forward_u8 if u8 else lib.f110_bitconv2_forward
+    with torch.cuda.device(dev):
+        _lib.check(fn(C.byref(cfg), frames.data_ptr(), frames.shape[0], None if index is None else index.data_ptr(), n,
+                      *[None if t is None else t.data_ptr() for t in tensors], out.data_ptr(), _stream(dev)))
+    return out
+
+
 class BitConv2d(torch.nn.Module):
     """nn.Conv2d(1, out_channels, kernel_size, stride) on two-valued images, computed by conv_bits.  Its parameters have the
     names and shapes of nn.Conv2d's (weight [C, 1, k, k], bias [C]), so state dicts pass between the two in both directions.
@@ -171,3 +266,63 @@ class BitConv2d(torch.nn.Module):
 
     def extra_repr(self):
         return '1, %d, kernel_size=%d, stride=%d, on=%g, relu=%s' % (self.weight.shape[0], self.kernel_size, self.stride, self.on, self.relu)
+
+
+def _plain_conv2(who, conv2, in_channels):
+    """(kernel, stride) of an nn.Conv2d(in_channels, C2, k2, stride2) that the stem can run; ValueError otherwise."""
+    pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)  # noqa: E731
+    if not isinstance(conv2, torch.nn.Conv2d):
+        raise ValueError('%s: conv2 is not an nn.Conv2d' % who)
+    if conv2.in_channels != in_channels:
+        raise ValueError('%s: conv2.in_channels = %d but conv1 has %d output channels' % (who, conv2.in_channels, in_channels))
+    if conv2.groups != 1 or pair(conv2.dilation) != (1, 1) or isinstance(conv2.padding, str) or pair(conv2.padding) != (0, 0):
+        raise ValueError('%s: padding, dilation and groups are not supported in conv2' % who)
+    ks, st = pair(conv2.kernel_size), pair(conv2.stride)
+    if ks[0] != ks[1] or st[0] != st[1]:
+        raise ValueError('%s: conv2\'s kernel and stride must be square' % who)
+    return ks[0], st[0]
+
+
+class BitConvStem(torch.nn.Module):
+    """relu(conv2(relu(conv1(frames)))): the two layers the reference's Actor and Critic open with, on two-valued images.
+    Submodules conv1 (a BitConv2d) and conv2 (an nn.Conv2d), so a state dict has the reference's keys conv1.weight, conv1.bias,
+    conv2.weight, conv2.bias.  forward(frames, index=None) takes one of two paths: while torch.is_grad_enabled() and one of the
+    four parameters requires grad, conv_bits(relu=True) -> F.conv2d -> relu, differentiable as before; otherwise (acting, the
+    no_grad block of an update) conv_bits2, the fused kernel, whose result has no grad_fn.  The two paths agree to fp32
+    rounding, not bit for bit: torch picks conv2's summation order on the first, the second adds in the order of the contract
+    (include/f110_hip.h)."""
+
+    def __init__(self, channels1=16, kernel1=8, stride1=4, channels2=32, kernel2=4, stride2=2, on=1.0, cols=None, device=None):
+        super().__init__()
+        self.conv1 = BitConv2d(channels1, kernel1, stride1, on=on, relu=True, cols=cols, device=device)
+        self.conv2 = torch.nn.Conv2d(int(channels1), int(channels2), int(kernel2), int(stride2), device=device)
+        self._check()
+
+    def _check(self):
+        k2, s2 = _plain_conv2('BitConvStem', self.conv2, self.conv1.weight.shape[0])
+        k1 = self.conv1.kernel_size
+        big = k1 + self.conv1.stride * (k2 - 1)                                   # the smallest image with one output
+        validate2(big, big, k1, self.conv1.stride, self.conv1.weight.shape[0], k2, s2, self.conv2.out_channels, self.conv1.on)
+
+    @classmethod
+    def from_convs(cls, conv1, conv2, on=1.0, cols=None):
+        """A stem that shares the parameters of an nn.Conv2d pair (the same tensors: training one trains the other).  ValueError
+        where BitConv2d.from_conv raises for conv1, and for a conv2 with padding, dilation, groups, a non-square kernel or stride,
+        or in_channels != conv1.out_channels, or sizes the fused kernel refuses."""
+        first = BitConv2d.from_conv(conv1, on=on, relu=True, cols=cols)
+        _plain_conv2('BitConvStem.from_convs', conv2, conv1.out_channels)
+        m = cls.__new__(cls)
+        torch.nn.Module.__init__(m)
+        m.conv1, m.conv2 = first, conv2
+        m._check()
+        return m
+
+    def forward(self, frames, index=None):
+        c1, c2 = self.conv1, self.conv2
+        cols = None if frames.dtype == torch.uint8 else c1.cols
+        params = (c1.weight, c1.bias, c2.weight, c2.bias)
+        if torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in params):
+            a1 = conv_bits(frames, c1.weight, c1.bias, stride=c1.stride, on=c1.on, relu=True, index=index, cols=cols)
+            return torch.relu(torch.nn.functional.conv2d(a1, c2.weight, c2.bias, stride=c2.stride))
+        return conv_bits2(frames, c1.weight, c1.bias, c2.weight, c2.bias, stride1=c1.stride, stride2=c2.stride[0], on=c1.on,
+                          relu1=True, relu2=True, index=index, cols=cols)

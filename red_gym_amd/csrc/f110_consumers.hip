@@ -905,6 +905,91 @@ extern "C" int f110_bitconv_backward(const f110_bitconv_config *cfg, const uint6
     return F110_OK;
 }
 
+// ---------------------------------------------------------------- policy stem: conv1 + relu + conv2 from bits
+static f110_bitconv_config bitconv2_layer1_config(const f110_bitconv2_config &c)
+{
+    f110_bitconv_config l1;
+    l1.rows = c.rows; l1.cols = c.cols; l1.kernel = c.kernel; l1.stride = c.stride; l1.channels = c.channels; l1.relu = c.relu; l1.on = c.on;
+    return l1;
+}
+
+extern "C" int f110_bitconv2_validate(const f110_bitconv2_config *cfg)
+{
+    const char *who = "f110_bitconv2_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    const f110_bitconv_config l1 = bitconv2_layer1_config(*cfg);
+    if (int rc = f110_bitconv_validate(&l1)) return rc;
+    if (cfg->channels > BC2_MAX_C1) return fail(F110_E_INVALID, "%s: %d channels in the first layer (1..%d)", who, cfg->channels, BC2_MAX_C1);
+    if (cfg->kernel2 < 1 || cfg->kernel2 > BC2_MAX_K2) return fail(F110_E_INVALID, "%s: kernel2 %d (1..%d)", who, cfg->kernel2, BC2_MAX_K2);
+    if (cfg->stride2 < 1 || cfg->stride2 > cfg->kernel2) return fail(F110_E_INVALID, "%s: stride2 %d (1..kernel2 = %d)", who, cfg->stride2, cfg->kernel2);
+    if (cfg->channels2 < 1 || cfg->channels2 > BC2_MAX_C2) return fail(F110_E_INVALID, "%s: %d channels in the second layer (1..%d)", who, cfg->channels2, BC2_MAX_C2);
+    const int oh1 = (cfg->rows - cfg->kernel) / cfg->stride + 1, ow1 = (cfg->cols - cfg->kernel) / cfg->stride + 1;
+    if (ow1 > BC2_MAX_OW1) return fail(F110_E_INVALID, "%s: the first layer's output is %d wide (at most %d: a band is whole rows)", who, ow1, BC2_MAX_OW1);
+    if (oh1 < cfg->kernel2 || ow1 < cfg->kernel2)
+        return fail(F110_E_INVALID, "%s: the first layer's output of %d x %d is smaller than kernel2 = %d", who, oh1, ow1, cfg->kernel2);
+    return F110_OK;
+}
+
+// LDS bytes of a workgroup whose bands have `br` output rows; the offsets of koff and a1 in it
+static size_t bitconv2_lds(const f110_bitconv2_config &c, int br, int xw, int ksteps, int *koff_off, int *a1_off)
+{
+    const int nr1 = (br - 1) * c.stride2 + c.kernel2, img_rows = (nr1 - 1) * c.stride + c.kernel;
+    const size_t words = (size_t)img_rows * BC_LWORDS * sizeof(uint64_t), koff = (size_t)BC2_KSTEPS * 4 * sizeof(int);
+    if (koff_off) *koff_off = (int)words;
+    if (a1_off) *a1_off = (int)(words + koff);
+    return words + koff + (size_t)c.channels * nr1 * xw * sizeof(float);
+}
+
+// the launch geometry of a validated configuration (restated by tests/bitconv2_cases.py paths2)
+static size_t bitconv2_geometry(const f110_bitconv2_config &c, Bitconv2Args &a)
+{
+    memset(&a, 0, sizeof(a));
+    bitconv_geometry(bitconv2_layer1_config(c), a.l1);
+    a.k2 = c.kernel2; a.s2 = c.stride2; a.C2 = c.channels2; a.relu2 = c.relu2;
+    a.OH2 = (a.l1.OH - a.k2) / a.s2 + 1; a.OW2 = (a.l1.OW - a.k2) / a.s2 + 1;
+    a.XW = (a.OW2 - 1) * a.s2 + a.k2;
+    a.ktot = c.channels * a.k2 * a.k2; a.ksteps = (a.ktot + 3) / 4;
+    a.BR = 1;
+    while (a.BR < a.OH2 && bitconv2_lds(c, a.BR + 1, a.XW, a.ksteps, nullptr, nullptr) <= (size_t)BC2_LDS_BYTES) a.BR++;
+    a.bands = (a.OH2 + a.BR - 1) / a.BR;
+    a.NR1 = (a.BR - 1) * a.s2 + a.k2;
+    return bitconv2_lds(c, a.BR, a.XW, a.ksteps, &a.koff_off, &a.a1_off);
+}
+
+static int bitconv2_forward(const char *who, const f110_bitconv2_config *cfg, const void *src, bool u8, int64_t n_frames, const int64_t *index,
+                            int64_t n, const float *w1, const float *b1, const float *w2, const float *b2, float *out, hipStream_t stream)
+{
+    if (int rc = f110_bitconv2_validate(cfg)) return rc;
+    if (n < 0 || n_frames < 0) return fail(F110_E_INVALID, "%s: n=%lld samples of %lld frames", who, (long long)n, (long long)n_frames);
+    if (n == 0) return F110_OK;
+    if (!w1 || !w2 || !out || !src) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (!index && n > n_frames) return fail(F110_E_INVALID, "%s: %lld samples of %lld frames without an index", who, (long long)n, (long long)n_frames);
+    if (!u8 && (uintptr_t)src % 8) return fail(F110_E_INVALID, "%s: frames must be 8-byte aligned", who);
+    Bitconv2Args a;
+    const size_t lds = bitconv2_geometry(*cfg, a);
+    if (u8) a.l1.images = (const uint8_t *)src; else a.l1.frames = (const uint64_t *)src;
+    a.u8 = u8 ? 1 : 0;
+    a.l1.n_frames = n_frames; a.l1.index = (const long long *)index; a.l1.n = n;
+    a.items = (long long)n * a.bands;
+    // (a workgroup walks items grid apart, so one launch serves any n; its LDS stays below the 64 KiB every kernel may ask for)
+    const unsigned grid = (unsigned)std::min<long long>(a.items, BC2_MAX_GRID);
+    hipLaunchKernelGGL(bitconv2_forward_kernel, dim3(grid), dim3(BC_THREADS), lds, stream, a, w1, b1, w2, b2, out);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_bitconv2_forward(const f110_bitconv2_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
+                                     const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream)
+{
+    return bitconv2_forward("f110_bitconv2_forward", cfg, frames, false, n_frames, index, n, w1, b1, w2, b2, out, (hipStream_t)stream);
+}
+
+extern "C" int f110_bitconv2_forward_u8(const f110_bitconv2_config *cfg, const uint8_t *images, int64_t n_frames, const int64_t *index, int64_t n,
+                                        const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream)
+{
+    return bitconv2_forward("f110_bitconv2_forward_u8", cfg, images, true, n_frames, index, n, w1, b1, w2, b2, out, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- scan -> bitmap
 static const void *bitmap_fn(size_t lds, int mode, int channels)
 {

@@ -1,0 +1,377 @@
+"""The fused policy stem on the GPU (csrc/f110_bitconv2.h): conv_bits2 `==` the checker of tests/bitconv2_cases.py as raw 32-bit
+patterns at every shape-selected path (b2.paths2), the same activations as the unfused layer, index, batch independence, margins,
+no intermediate in memory, the module's two paths, graph replay and the closed loop from the env's bitmap and the ring's frames."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import bitconv2_cases as b2
+import bitconv_cases as bc
+import replay_cases as rc
+import shaping_cases as sc
+
+pytestmark = pytest.mark.gpu
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _dev(a):
+    import torch
+    return None if a is None else torch.as_tensor(np.ascontiguousarray(a), device='cuda')
+
+
+def _packed(imgs):
+    import torch
+    return torch.as_tensor(rc.pack(imgs).view(np.int64), device='cuda')
+
+
+def _differing(got, want):
+    got = got if isinstance(got, np.ndarray) else _np(got)
+    assert got.shape == want.shape
+    return int((bc.bit_patterns(got) != bc.bit_patterns(want)).sum())
+
+
+_acc_cache = {}
+
+
+def _want(case, name, imgs, P, on, relu1, relu2, with_b1, with_b2):
+    """The checker's output; the fma chain is computed once per (case, batch, on, relu1, b1) and left unchanged."""
+    rows, cols, k1, s1, c1, k2, s2, c2 = case
+    w1, b1, w2, bb = P
+    key = (case, name, on, relu1, with_b1)
+    if key not in _acc_cache:
+        acc = b2.accumulate2(bc.forward(imgs, w1, b1 if with_b1 else None, s1, on, relu1), w2, s2)
+        acc.setflags(write=False)
+        _acc_cache[key] = acc
+    return b2.finish2(_acc_cache[key], bb if with_b2 else None, relu2)
+
+
+def _stem(src, P, case, on=1.0, relu1=True, relu2=True, with_b1=True, with_b2=True, index=None):
+    from red_gym_amd.bitconv import conv_bits2
+    w1, b1, w2, bb = P
+    return conv_bits2(src, w1, b1 if with_b1 else None, w2, bb if with_b2 else None, stride1=case[3], stride2=case[6], on=on,
+                      relu1=relu1, relu2=relu2, index=index, cols=case[1])
+
+
+@pytest.mark.parametrize('case', b2.CASES2)
+def test_forward_equals_checker(golden, case):
+    """Both entries `==` the checker as raw bit patterns on three images (arbitrary bytes, all set, empty) under b2.VARIANTS (every
+    `on`, relu1 and relu2 both ways, each bias present and NULL); SAL's shape also on the five fullest two-valued FILL images of g16."""
+    rows, cols, k1, s1, c1, k2, s2, c2 = case
+    host = b2.params2(k1, c1, k2, c2)
+    P = tuple(_dev(x) for x in host)
+    batches = [('abc', b2.images2(rows, cols), b2.VARIANTS)]
+    if case == b2.SAL:
+        imgs = sc.unpack_images(golden('g16_shaping.npz'), 'a')
+        filled = (imgs.reshape(imgs.shape[0], -1) == 255).sum(axis=1)
+        filled = np.where(filled == 256 * 256, -1, filled)
+        fill = imgs[np.argsort(-filled, kind='stable')[:5]]
+        assert fill.shape == (5, 256, 256) and all((im == 255).any() and (im == 0).any() for im in fill)
+        batches.append(('fill', fill, b2.VARIANTS[:1]))
+    total = 0
+    for name, imgs, variants in batches:
+        srcs = (('packed', _packed(imgs)), ('uint8', _dev(imgs)))
+        for on, relu1, relu2, wb1, wb2 in variants:
+            want = _want(case, name, imgs, host, on, relu1, relu2, wb1, wb2)
+            for entry, src in srcs:
+                got = _stem(src, P, case, on, relu1, relu2, wb1, wb2)
+                assert tuple(got.shape) == want.shape and got.grad_fn is None
+                bad = _differing(got, want)
+                print('%s %s %s on=%g relu=%s/%s bias=%s/%s: %d of %d elements differ' % (case, name, entry, on, relu1, relu2, wb1, wb2, bad, want.size))
+                total += bad
+            if name == 'abc':
+                assert (want[0] != want[1]).any() and (want[0] != want[2]).any()
+                if not relu2 and c2 * want.shape[2] * want.shape[3] >= 8:
+                    assert (want < 0).any() and (want > 0).any()
+    assert total == 0
+
+
+@pytest.mark.parametrize('case', (b2.CASES2[3], b2.CASES2[1]))
+def test_same_activations_as_the_unfused_layer(case):
+    """With w2 an identity selector (k2 = 1, s2 = 1, C2 = C1, w2[c][c] = 1, no bias, no relu2) the stem's output channel c is
+    conv_bits' own channel c, bit for bit; one channel at a time as well."""
+    import torch
+    from red_gym_amd.bitconv import conv_bits, conv_bits2
+    rows, cols, k1, s1, c1 = case[:5]
+    w1, b1 = (_dev(x) for x in bc.params(k1, c1, seed=6))
+    imgs = _dev(b2.images2(rows, cols))
+    for on, relu1 in ((255.0, True), (1.0, False)):
+        a1 = conv_bits(imgs, w1, b1, stride=s1, on=on, relu=relu1)
+        eye = torch.eye(c1, device='cuda').reshape(c1, c1, 1, 1).contiguous()
+        got = conv_bits2(imgs, w1, b1, eye, None, stride1=s1, stride2=1, on=on, relu1=relu1, relu2=False)
+        assert torch.equal(got.view(torch.int32), a1.view(torch.int32)) and (a1 != 0).any()
+        for c in range(c1):
+            one = conv_bits2(imgs, w1, b1, eye[c:c + 1].contiguous(), None, stride1=s1, stride2=1, on=on, relu1=relu1, relu2=False)
+            assert torch.equal(one[:, 0].view(torch.int32), a1[:, c].view(torch.int32))
+
+
+@pytest.mark.parametrize('case', (b2.CASES2[1], b2.CASES2[3]))
+def test_index_and_batch_independence(case):
+    """index [2, -1, 0, 0, m + 5]: -1 and out of range give the empty frame's output, repeats are equal; a sample inside a batch
+    of 67 equals the sample alone."""
+    import torch
+    rows, cols, k1, s1, c1, k2, s2, c2 = case
+    host = b2.params2(k1, c1, k2, c2, seed=1)
+    P = tuple(_dev(x) for x in host)
+    imgs = b2.images2(rows, cols)
+    full = _stem(_dev(imgs), P, case)
+    empty = _stem(_dev(np.zeros((1, rows, cols), np.uint8)), P, case)
+    assert _differing(full, b2.forward2(imgs, host[0], host[1], s1, 1.0, True, host[2], host[3], s2, True)) == 0
+    index = _dev(np.array([2, -1, 0, 0, imgs.shape[0] + 5], np.int64))
+    for src in (_packed(imgs), _dev(imgs)):
+        got = _stem(src, P, case, index=index)
+        assert got.shape[0] == 5 and torch.equal(got[0], full[2]) and torch.equal(got[2], full[0]) and torch.equal(got[2], got[3])
+        assert torch.equal(got[1], empty[0]) and torch.equal(got[4], empty[0]) and not torch.equal(got[0], got[2])
+    many = rc.random_images(rows, cols, n=67, seed=3)
+    batch = _stem(_dev(many), P, case)
+    for i in (0, 31, 66):
+        alone = _stem(_dev(many[i:i + 1]), P, case)
+        assert torch.equal(batch[i], alone[0])
+    assert not torch.equal(batch[0], batch[66])
+
+
+def _raw_forward2(src, n_frames, index, n, cfg, P, sentinel=-7.0):
+    """f110_bitconv2_forward / _u8 itself into an array of `sentinel` with guard rows before and after -> the output on the host."""
+    import torch
+    from red_gym_amd import _lib, bitconv
+    lib = _lib.load()
+    oh2, ow2 = bitconv.output_size2(cfg.rows, cfg.cols, cfg.kernel, cfg.stride, cfg.kernel2, cfg.stride2)
+    size = n * cfg.channels2 * oh2 * ow2
+    buf = torch.full((size + 128,), sentinel, dtype=torch.float32, device='cuda')
+    fn = lib.f110_bitconv2_forward_u8 if src.dtype == torch.uint8 else lib.f110_bitconv2_forward
+    _lib.check(fn(C.byref(cfg), src.data_ptr(), n_frames, None if index is None else index.data_ptr(), n,
+                  *[None if t is None else t.data_ptr() for t in P], buf.data_ptr() + 64 * 4, torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    host = _np(buf)
+    assert (host[:64] == sentinel).all() and (host[64 + size:] == sentinel).all()
+    return host[64:64 + size].reshape(n, cfg.channels2, oh2, ow2)
+
+
+@pytest.mark.parametrize('case', b2.CASES2)
+def test_margins_through_the_raw_abi(case):
+    """The guards around `out` stay as they were and no element of `out` keeps the sentinel (relu2 off, so 0 is no hiding place
+    and the sentinel -7 would have to be computed), from both entries; n == 0 writes nothing and null pointers are refused."""
+    from red_gym_amd import _lib, bitconv
+    rows, cols, k1, s1, c1, k2, s2, c2 = case
+    host = b2.params2(k1, c1, k2, c2, seed=2)
+    P = tuple(_dev(x) for x in host)
+    imgs = b2.images2(rows, cols)
+    cfg = bitconv.make_config2(rows, cols, k1, s1, c1, k2, s2, c2, 1.0, True, False)
+    want = b2.forward2(imgs, host[0], host[1], s1, 1.0, True, host[2], host[3], s2, False)
+    assert (want != -7.0).all()
+    for src in (_packed(imgs), _dev(imgs)):
+        got = _raw_forward2(src, 3, None, 3, cfg, P)
+        assert (got != -7.0).all() and _differing(got, want) == 0
+        assert (_raw_forward2(src, 3, None, 0, cfg, P).size == 0)
+    lib = _lib.load()
+    src = _packed(imgs)
+    ptrs = [src.data_ptr(), P[0].data_ptr(), P[2].data_ptr(), P[3].data_ptr()]
+    for hole in range(4):
+        frames, w1, w2, out = [None if i == hole else p for i, p in enumerate(ptrs)]
+        assert lib.f110_bitconv2_forward(C.byref(cfg), frames, 3, None, 3, w1, None, w2, None, out, None) == _lib.E_INVALID
+
+
+def test_more_items_than_workgroups():
+    """b2.LOOP_N samples of one band each on b2.BC2_MAX_GRID workgroups: each walks two or three; through an index over three
+    packed frames with -1 entries; every output `==` the checker's for its frame."""
+    import torch
+    case, n = b2.LOOP_CASE, b2.LOOP_N
+    rows, cols, k1, s1, c1, k2, s2, c2 = case
+    host = b2.params2(k1, c1, k2, c2, seed=4)
+    P = tuple(_dev(x) for x in host)
+    imgs = b2.images2(rows, cols)
+    imgs[2] = rc.random_images(rows, cols, n=1, seed=8)[0]                     # (random, all set, random; -1 reads the empty one)
+    want = b2.forward2(np.concatenate([imgs, np.zeros((1, rows, cols), np.uint8)]), host[0], host[1], s1, 1.0, True, host[2], host[3], s2, False)
+    assert all((want[i] != want[j]).any() for i in range(4) for j in range(i))
+    idx = np.random.default_rng(4).integers(0, 3, n).astype(np.int64)
+    idx[7::101] = -1
+    idx[-3:] = [0, 1, 2]
+    got = _stem(_packed(imgs), P, case, relu2=False, index=_dev(idx))
+    gathered = _dev(want)[_dev(np.where(idx < 0, 3, idx))]
+    assert got.shape == gathered.shape and torch.equal(got.view(torch.int32), gathered.view(torch.int32))
+
+
+def test_no_intermediate_in_memory():
+    """SAL's shape on 64 uint8 bitmaps: the peak allocated above the starting level during conv_bits2 stays below the output's
+    7.4 MB + 1 MiB, less than the 16.3 MB of the first layer's activations alone; the composed path's peak exceeds those 16.3 MB,
+    so the measure can see them."""
+    import torch
+    import torch.nn.functional as F
+    from red_gym_amd.bitconv import conv_bits, conv_bits2
+    rows, cols, k1, s1, c1, k2, s2, c2 = b2.SAL
+    w1, b1, w2, bb = (_dev(x) for x in b2.params2(k1, c1, k2, c2))
+    imgs = _dev(rc.random_images(rows, cols, n=64, seed=2))
+    out_bytes, a1_bytes = 64 * 32 * 30 * 30 * 4, 64 * 16 * 63 * 63 * 4
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    out = conv_bits2(imgs, w1, b1, w2, bb, stride1=s1, stride2=s2)
+    torch.cuda.synchronize()
+    fused = torch.cuda.max_memory_allocated() - base
+    del out
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    out = torch.relu_(F.conv2d(conv_bits(imgs, w1, b1, stride=s1, relu=True), w2, bb, stride=s2))
+    torch.cuda.synchronize()
+    composed = torch.cuda.max_memory_allocated() - base
+    print('peak bytes above the start: fused %d, composed %d (out %d, a1 %d)' % (fused, composed, out_bytes, a1_bytes))
+    assert out_bytes <= fused < out_bytes + (1 << 20) < a1_bytes < composed
+
+
+def test_module_two_paths():
+    """BitConvStem.from_convs shares the four tensors; state dicts pass to an nn.Conv2d pair and back; under no_grad the output
+    `==` the checker; with grad on it has a grad_fn, lies within gamma(257) sum |w2 a1| + ulp of the checker's fp64 conv2, and
+    backward() fills the four grads with those of the hand-composed conv_bits -> F.conv2d -> relu on clones."""
+    import torch
+    import torch.nn.functional as F
+    from red_gym_amd.bitconv import BitConvStem, conv_bits
+    torch.manual_seed(5)
+    conv1, conv2 = torch.nn.Conv2d(1, 16, 8, 4).cuda(), torch.nn.Conv2d(16, 32, 4, 2).cuda()
+    stem = BitConvStem.from_convs(conv1, conv2, on=1.0, cols=256)
+    mine = (stem.conv1.weight, stem.conv1.bias, stem.conv2.weight, stem.conv2.bias)
+    theirs = (conv1.weight, conv1.bias, conv2.weight, conv2.bias)
+    assert all(a.data_ptr() == b.data_ptr() for a, b in zip(mine, theirs))
+    assert sorted(stem.state_dict()) == ['conv1.bias', 'conv1.weight', 'conv2.bias', 'conv2.weight']
+    fresh = BitConvStem(cols=256).cuda()
+    fresh.load_state_dict({'conv1.' + k: v for k, v in conv1.state_dict().items()} | {'conv2.' + k: v for k, v in conv2.state_dict().items()})
+    back1, back2 = torch.nn.Conv2d(1, 16, 8, 4).cuda(), torch.nn.Conv2d(16, 32, 4, 2).cuda()
+    back1.load_state_dict(fresh.conv1.state_dict())
+    back2.load_state_dict(fresh.conv2.state_dict())
+    assert torch.equal(back1.weight, conv1.weight) and torch.equal(back2.weight, conv2.weight) and torch.equal(back2.bias, conv2.bias)
+    imgs = b2.images2(256, 256)
+    host = tuple(_np(p) for p in theirs)
+    want = b2.forward2(imgs, host[0], host[1], 4, 1.0, True, host[2], host[3], 2, True)
+    with torch.no_grad():
+        got = stem(_dev(imgs))
+        assert got.grad_fn is None and _differing(got, want) == 0
+        assert _differing(fresh(_packed(imgs)), want) == 0
+    out = stem(_dev(imgs))
+    assert out.grad_fn is not None
+    a1 = bc.forward(imgs, host[0], host[1], 4, 1.0, True)
+    ref, mag = b2.conv2_fp64(a1, host[2], host[3], 2)
+    bound = bc.gamma(257) * mag + np.abs(ref) * bc.U
+    err = np.abs(_np(out).astype(np.float64) - np.maximum(ref, 0.0))
+    print('grad path: worst error / bound %.4f' % float((err / np.maximum(bound, 1e-300)).max()))
+    assert (err <= bound).all()
+    g = torch.randn_like(out)
+    clones = [p.detach().clone().requires_grad_() for p in theirs]
+    # both sides run torch's conv2d backward: it is held to its deterministic kernels, and has chosen them, before either runs
+    was = torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark
+    torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = True, False
+    try:
+        warm = [p.detach().clone().requires_grad_() for p in theirs]
+        torch.relu(F.conv2d(conv_bits(_dev(imgs), warm[0], warm[1], stride=4, relu=True), warm[2], warm[3], stride=2)).backward(g)
+        stem(_dev(imgs)).backward(g)
+        hand = torch.relu(F.conv2d(conv_bits(_dev(imgs), clones[0], clones[1], stride=4, relu=True), clones[2], clones[3], stride=2))
+        hand.backward(g)
+    finally:
+        torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = was
+    for name, p, q in zip(('conv1.weight', 'conv1.bias', 'conv2.weight', 'conv2.bias'), theirs, clones):
+        assert p.grad is not None and p.grad.shape == p.shape and bool((p.grad != 0).any())
+        print('%s.grad: largest difference from the hand-composed path %.3g' % (name, float((p.grad - q.grad).abs().max())))
+    for p, q in zip(theirs, clones):
+        assert torch.equal(p.grad, q.grad)
+    # frozen parameters take the fused path even with grad enabled
+    for p in theirs:
+        p.requires_grad_(False)
+    assert stem(_dev(imgs)).grad_fn is None and _differing(stem(_dev(imgs)), want) == 0
+    for bad2 in (torch.nn.Conv2d(16, 32, 4, 2, padding=1), torch.nn.Conv2d(16, 32, 4, 2, dilation=2), torch.nn.Conv2d(16, 32, 4, 2, groups=4),
+                 torch.nn.Conv2d(16, 32, (4, 3), 2), torch.nn.Conv2d(16, 32, 4, (2, 1)), torch.nn.Conv2d(8, 32, 4, 2), torch.nn.Conv2d(16, 32, 5, 2)):
+        with pytest.raises(ValueError):
+            BitConvStem.from_convs(conv1, bad2.cuda())
+    for bad1 in (torch.nn.Conv2d(3, 16, 8, 4), torch.nn.Conv2d(1, 16, 8, 4, padding=2), torch.nn.Conv2d(1, 32, 8, 4)):
+        with pytest.raises(ValueError):
+            BitConvStem.from_convs(bad1.cuda(), conv2)
+
+
+def test_refuses_mismatched_tensors():
+    import torch
+    from red_gym_amd.bitconv import conv_bits2
+    w1, b1, w2, bb = (_dev(x) for x in b2.params2(8, 16, 4, 32))
+    f = _packed(b2.images2(256, 256))
+    for args, kw in (((f, w1, b1, w2, bb), dict(stride1=4, stride2=2)),                          # packed frames without cols
+                     ((f, w1, b1, w2, bb), dict(stride1=4, stride2=2, cols=100)),
+                     ((f.float(), w1, b1, w2, bb), dict(stride1=4, stride2=2, cols=256)),
+                     ((f, w1, b1, w2.double(), bb), dict(stride1=4, stride2=2, cols=256)),
+                     ((f, w1, b1, w2[:, :8].contiguous(), bb), dict(stride1=4, stride2=2, cols=256)),  # C1 mismatch
+                     ((f, w1, b1, w2[:, :, :, :3], bb), dict(stride1=4, stride2=2, cols=256)),   # not square
+                     ((f, w1, b1, w2, bb[:3]), dict(stride1=4, stride2=2, cols=256)),
+                     ((f, w1, b1[:3], w2, bb), dict(stride1=4, stride2=2, cols=256)),
+                     ((f, w1, b1, w2, bb), dict(stride1=4, stride2=5, cols=256)),                # what validate2 refuses
+                     ((f, w1, b1, w2, bb), dict(stride1=3, stride2=2, cols=256)),                # OW1 = 83
+                     ((f, w1, b1, w2.cpu(), bb), dict(stride1=4, stride2=2, cols=256)),
+                     ((f, w1, b1, w2, bb), dict(stride1=4, stride2=2, cols=256, index=torch.zeros(3, dtype=torch.int32, device='cuda')))):
+        with pytest.raises(ValueError):
+            conv_bits2(*args, **kw)
+
+
+def test_graph_replay():
+    """conv_bits2 captured in a torch.cuda.graph on one stream replays twice, the input frames refilled in place between the
+    replays; each replay equals the eager result."""
+    import torch
+    case = b2.CASES2[1]
+    rows, cols, k1, s1, c1, k2, s2, c2 = case
+    P = tuple(_dev(x) for x in b2.params2(k1, c1, k2, c2, seed=7))
+    fills = [rc.random_images(rows, cols, n=4, seed=s) for s in (1, 2)]
+    eager = [_stem(_dev(f), P, case) for f in fills]
+    assert not torch.equal(eager[0], eager[1])
+    frames = _dev(np.zeros_like(fills[0]))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        _stem(frames, P, case)                                     # (warm-up outside the capture)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = _stem(frames, P, case)
+    for f, want in zip(fills, eager):
+        frames.copy_(_dev(f))
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, want)
+
+
+def test_closed_loop_from_bitmap_and_ring_to_features(assets):
+    """64 envs with shaper, path follower and replay ring, 20 steps: the stem under no_grad on info['lidar_bitmap'] and on
+    env.replay.sample_frames(32) `==` the checker on the images the env returned; the device error word stays clean."""
+    import torch
+    from red_gym_amd import F110VecEnv, workload
+    from red_gym_amd.bitconv import BitConvStem
+    B, AD, rows, cols = 64, 16, 75, 100
+    env = F110VecEnv(B, map=os.path.join(assets, 'example_map'), map_ext='.png', num_agents=1, autoreset=True, timestep=0.025)
+    env.shape_rewards(rows=rows, cols=cols)
+    env.follow_paths()
+    env.record_replay(capacity=4 * B, action_dim=AD)
+    torch.manual_seed(3)
+    stem = BitConvStem(16, 8, 4, 32, 4, 2, on=1.0, cols=cols).cuda()
+    host = tuple(_np(p) for p in (stem.conv1.weight, stem.conv1.bias, stem.conv2.weight, stem.conv2.bias))
+
+    def checker(imgs):
+        return b2.forward2(imgs, host[0], host[1], 4, 1.0, True, host[2], host[3], 2, True)
+
+    rng = np.random.default_rng(18)
+    env.reset(workload.spawn_poses(B, 1))
+    checked = 0
+    for k in range(20):
+        acts = env.path_actions(torch.as_tensor(rng.uniform(-1.0, 1.0, (B, AD)), device=env.device))
+        _, _, _, info = env.step(acts)
+        if k in (9, 19):
+            with torch.no_grad():
+                feats = stem(info['lidar_bitmap'])
+            bitmap = _np(info['lidar_bitmap'])
+            assert feats.shape == (B, 32, 7, 11) and feats.grad_fn is None and _differing(feats, checker(bitmap)) == 0
+            assert 2 * sum(bool((im == 255).any() and (im == 0).any()) for im in bitmap) >= B
+            checked += 1
+    first = env.replay._draws
+    frames, s_idx, ns_idx, a, r, d, ok = env.replay.sample_frames(32, seed=5)
+    s2 = env.replay.sample_at(torch.as_tensor(_np(env.replay._keep), device=env.device))
+    assert env.replay._draws == first + 32 and int(ok.sum()) > 0
+    with torch.no_grad():
+        fs, fns = stem(frames, index=s_idx), stem(frames, index=ns_idx)
+    assert _differing(fs, checker(_np(s2[0]))) == 0 and _differing(fns, checker(_np(s2[3]))) == 0
+    assert checked == 2 and env.eng.device_errors() == 0
+    env.close()
