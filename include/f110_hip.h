@@ -673,6 +673,53 @@ int f110_bitconv2_forward(const f110_bitconv2_config *cfg, const uint64_t *frame
 int f110_bitconv2_forward_u8(const f110_bitconv2_config *cfg, const uint8_t *images, int64_t n_frames, const int64_t *index, int64_t n,
                              const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream);
 
+/* Policy head: the end of the reference's Actor.forward and Actor.sample (src/SAL.py:410-421) -- fc_mean and fc_log_std on the
+ * features h of fc1, clamp(-20, 2), exp, rsample, tanh and the squashed-Gaussian log_prob summed over the action -- forward in one
+ * kernel, and a backward without atomics.  Stateless (no handle; cfg host; all arrays dev); launches on `stream` of the calling
+ * thread's current device, no allocation, no synchronisation.
+ * h [n, K] fp32 (K = in_features), w_mean [A, K], b_mean [A] or NULL, w_log_std [A, K], b_log_std [A] or NULL (A = action_dim),
+ * eps [n, A] fp32 (the standard normal draws of rsample) or NULL (the reference's evaluate=True).
+ * Outputs: pre [n, 2A] fp32, required (columns 0 .. A - 1 the mean's pre-activations, A .. 2A - 1 the log_std's before the clamp);
+ * action [n, A] and log_prob [n], fp64 when out_fp64 is nonzero, else fp32, rounded once.  log_prob must be NULL exactly when eps
+ * is NULL.  n == 0 does nothing; F110_E_INVALID, not a launch, for a null h, w_mean, w_log_std, pre or action with n > 0, for n
+ * outside 0 .. 2^24, for what f110_policyhead_validate refuses, and for a wrong device: a required pointer that is not memory of the
+ * calling thread's current device (host memory included), or a non-null `stream` of another device (both entry points).
+ * Numerics.  Pre-activations in fp32, bit for bit: for row j of w_mean, then of w_log_std: acc = 0; for k ascending: acc =
+ * fmaf(w[j][k], h[b][k], acc), one rounding per step; pre = acc + bias[j] (+ 0.0f for NULL).  The tail in fp64, from the fp32 pre
+ * and eps widened exactly: ls = min(max(pre_ls, -20), 2); std = exp(ls); x = mean + std * eps; y = tanh(x) = the action;
+ * log_prob[b] = the sum over j ascending, from 0, of ((-(eps * eps) / 2 - ls) - log(2 pi) / 2) - log((1.0 - y * y) + 1e-6).
+ * With eps NULL: y = tanh(mean), no log_prob.  -(eps * eps) / 2 is what Normal.log_prob(x_t) means; the reference evaluates ((x_t -
+ * mean) / std)^2 on the rounded x_t in fp32, which loses every digit when std is small (a log_prob off by 1.15 at log_std near
+ * -19.9): a deliberate difference.  A row's result depends neither on n nor on its place in the batch; two calls give the same bits.
+ * f110_policyhead_backward: from grad_action [n, A] (required) and grad_log_prob [n] or NULL, both of the width out_fp64 names,
+ * and h, pre, eps and the weights of the forward call; it recomputes the tail from pre and eps and reads no other forward output.
+ * grad_log_prob must be NULL when eps is.  In fp64: g_x = g_y (1 - y y) + g_lp * (2 y (1 - y y) / ((1 - y y) + 1e-6)); g_mean =
+ * g_x; g_ls = g_x std eps - g_lp where -20 <= pre_ls <= 2 (torch's clamp gradient, bounds included) and 0 elsewhere and with eps
+ * NULL; grad_pre [n, 2A] fp32 or NULL is a gradient that arrives at pre itself (through the mean, or through the caller's clamp of
+ * the log_std, whose mask the caller has applied) and is added to g_mean and g_ls in fp64; each sum rounded once to fp32: g_pre
+ * [n, 2A], kept in the workspace.  Then in fp32: grad_h[b][k]: acc = 0; for j ascending
+ * over the 2A columns of g_pre (w = w_mean's rows, then w_log_std's): acc = fmaf(w[j][k], g_pre[b][j], acc).  grad_w[j][k] in two
+ * stages: for each slice of F110_POLICYHEAD_SLICE_ROWS consecutive rows, acc = 0; for b ascending: acc = fmaf(g_pre[b][j], h[b][k],
+ * acc); then the slices are added in ascending order from 0.  grad_b[j] likewise with acc = acc + g_pre[b][j].  No atomics: the
+ * result is a function of the inputs alone, whatever the device.  Every gradient output may be NULL (skipped).  `workspace`: 16-byte
+ * aligned, f110_policyhead_workspace bytes (0 for an invalid configuration or n outside 1 .. 2^24); it need not be initialised.
+ * f110_policyhead_validate: host only.  F110_E_INVALID for in_features outside 1..4096 and action_dim outside 1..32. */
+#define F110_POLICYHEAD_SLICE_ROWS 256
+typedef struct {
+    int32_t in_features;        /* K, 1..4096 (SAL: 512) */
+    int32_t action_dim;         /* A, 1..32 (SAL: 16) */
+    int32_t out_fp64;           /* nonzero: action, log_prob and their gradients are double, else float */
+} f110_policyhead_config;
+int f110_policyhead_validate(const f110_policyhead_config *cfg);
+int64_t f110_policyhead_workspace(const f110_policyhead_config *cfg, int64_t n);
+int f110_policyhead_forward(const f110_policyhead_config *cfg, const float *h, int64_t n, const float *w_mean, const float *b_mean,
+                            const float *w_log_std, const float *b_log_std, const float *eps, float *pre, void *action, void *log_prob,
+                            void *stream);
+int f110_policyhead_backward(const f110_policyhead_config *cfg, const float *h, int64_t n, const float *w_mean, const float *w_log_std,
+                             const float *pre, const float *eps, const void *grad_action, const void *grad_log_prob, const float *grad_pre,
+                             float *grad_h, float *grad_w_mean, float *grad_b_mean, float *grad_w_log_std, float *grad_b_log_std, float *workspace,
+                             void *stream);
+
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).
  * scans_f32 / lookups may be NULL; lookups [n] is overwritten-by-accumulation like

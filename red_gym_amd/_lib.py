@@ -108,6 +108,13 @@ class Bitconv2Config(C.Structure):
                 ('kernel2', C.c_int32), ('stride2', C.c_int32), ('channels2', C.c_int32), ('relu2', C.c_int32)]
 
 
+# f110_policyhead_config: the policy head (fc_mean, fc_log_std and the sampling tail; stateless)
+class PolicyheadConfig(C.Structure):
+    _fields_ = [('in_features', C.c_int32), ('action_dim', C.c_int32), ('out_fp64', C.c_int32)]
+
+
+F110_POLICYHEAD_SLICE_ROWS = 256
+
 # every symbol include/f110_hip.h declares: name -> argtypes (restype int unless noted)
 _VP, _I32, _I64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -190,6 +197,10 @@ SYMBOLS = {
     'f110_bitconv2_validate': [C.POINTER(Bitconv2Config)],
     'f110_bitconv2_forward': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_bitconv2_forward_u8': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_policyhead_validate': [C.POINTER(PolicyheadConfig)],
+    'f110_policyhead_workspace': [C.POINTER(PolicyheadConfig), _I64],
+    'f110_policyhead_forward': [C.POINTER(PolicyheadConfig), _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_policyhead_backward': [C.POINTER(PolicyheadConfig), _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_replay_pack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_replay_unpack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],
@@ -243,6 +254,7 @@ def load():
     lib.f110_last_error.restype = C.c_char_p
     lib.f110_pure_pursuit_workspace.restype = C.c_int64
     lib.f110_bitconv_workspace.restype = C.c_int64
+    lib.f110_policyhead_workspace.restype = C.c_int64
     lib.f110_pack_env_size.restype = C.c_int64
     lib.f110_destroy.restype = None
     lib.f110_bitmap_destroy.restype = None

@@ -990,6 +990,129 @@ extern "C" int f110_bitconv2_forward_u8(const f110_bitconv2_config *cfg, const u
     return bitconv2_forward("f110_bitconv2_forward_u8", cfg, images, true, n_frames, index, n, w1, b1, w2, b2, out, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- policy head: fc_mean, fc_log_std and the sampling tail
+extern "C" int f110_policyhead_validate(const f110_policyhead_config *cfg)
+{
+    const char *who = "f110_policyhead_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    if (cfg->in_features < 1 || cfg->in_features > PH_MAX_K) return fail(F110_E_INVALID, "%s: in_features %d (1..%d)", who, cfg->in_features, PH_MAX_K);
+    if (cfg->action_dim < 1 || cfg->action_dim > PH_MAX_A) return fail(F110_E_INVALID, "%s: action_dim %d (1..%d)", who, cfg->action_dim, PH_MAX_A);
+    return F110_OK;
+}
+
+// the launch geometry of a validated configuration (restated by tests/policyhead_cases.py paths)
+static void policyhead_geometry(const f110_policyhead_config &c, int64_t n, PolicyheadArgs &a)
+{
+    memset(&a, 0, sizeof(a));
+    a.K = c.in_features; a.A = c.action_dim; a.T = (a.A + 15) / 16; a.out_fp64 = c.out_fp64 ? 1 : 0;
+    a.kc = std::min(PH_LDS_BYTES / (128 * a.T), (a.K + 63) / 64 * 64);
+    a.chunks = (a.K + a.kc - 1) / a.kc;
+    a.n = n; a.tiles = (n + PH_ROWS - 1) / PH_ROWS;
+    a.slices = (int)((n + PH_SLICE - 1) / PH_SLICE);
+}
+
+// floats of g_pre in the workspace: [n, 2A], rounded up so that the partial sums behind it start 16-byte aligned
+static int64_t policyhead_gpre_floats(const f110_policyhead_config &c, int64_t n) { return (n * 2 * c.action_dim + 3) / 4 * 4; }
+
+extern "C" int64_t f110_policyhead_workspace(const f110_policyhead_config *cfg, int64_t n)
+{
+    if (n < 1 || n > PH_MAX_ROWS || f110_policyhead_validate(cfg) != F110_OK) return 0;
+    const int64_t slices = (n + PH_SLICE - 1) / PH_SLICE;
+    return (policyhead_gpre_floats(*cfg, n) + slices * 2 * cfg->action_dim * (cfg->in_features + 1)) * (int64_t)sizeof(float);
+}
+
+// The stateless entry points launch on the calling thread's current device: every required pointer must be memory of that device
+// and a stream given must belong to it.  A mismatch is refused here, before any launch (host-side queries only, no synchronisation).
+struct PolicyheadPtr { const char *name; const void *p; };
+static int policyhead_check_device(const char *who, hipStream_t stream, std::initializer_list<PolicyheadPtr> ptrs)
+{
+    int cur = -1;
+    HIP_TRY(hipGetDevice(&cur));
+    if (stream) {
+        hipDevice_t sdev = -1;
+        if (hipStreamGetDevice(stream, &sdev) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(F110_E_INVALID, "%s: `stream` is not a stream of this process", who);
+        }
+        if ((int)sdev != cur) return fail(F110_E_INVALID, "%s: `stream` belongs to device %d but the calling thread's current device is %d", who, (int)sdev, cur);
+    }
+    for (const PolicyheadPtr &q : ptrs) {
+        hipPointerAttribute_t at;
+        memset(&at, 0, sizeof(at));
+        const hipError_t e = hipPointerGetAttributes(&at, q.p);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged))
+            return fail(F110_E_INVALID, "%s: `%s` is not device memory", who, q.name);
+        if (at.device != cur) return fail(F110_E_INVALID, "%s: `%s` lives on device %d but the calling thread's current device is %d", who, q.name, at.device, cur);
+    }
+    return F110_OK;
+}
+
+extern "C" int f110_policyhead_forward(const f110_policyhead_config *cfg, const float *h, int64_t n, const float *w_mean, const float *b_mean,
+                                       const float *w_log_std, const float *b_log_std, const float *eps, float *pre, void *action, void *log_prob,
+                                       void *stream)
+{
+    const char *who = "f110_policyhead_forward";
+    if (int rc = f110_policyhead_validate(cfg)) return rc;
+    if (n < 0 || n > PH_MAX_ROWS) return fail(F110_E_INVALID, "%s: n=%lld rows (0..%lld)", who, (long long)n, (long long)PH_MAX_ROWS);
+    if (n == 0) return F110_OK;
+    if (!h || !w_mean || !w_log_std || !pre || !action) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if ((eps == nullptr) != (log_prob == nullptr)) return fail(F110_E_INVALID, "%s: log_prob must be NULL exactly when eps is NULL", who);
+    if (int rc = policyhead_check_device(who, (hipStream_t)stream, {{"h", h}, {"w_mean", w_mean}, {"w_log_std", w_log_std}, {"pre", pre}, {"action", action}})) return rc;
+    PolicyheadArgs a;
+    policyhead_geometry(*cfg, n, a);
+    a.h = h; a.w_mean = w_mean; a.b_mean = b_mean; a.w_log_std = w_log_std; a.b_log_std = b_log_std; a.eps = eps;
+    a.pre = pre; a.action = action; a.log_prob = log_prob;
+    // (a workgroup walks tiles grid apart, so one launch serves any n; its LDS stays within the 64 KiB every kernel may ask for)
+    const unsigned grid = (unsigned)std::min<long long>(a.tiles, PH_MAX_GRID);
+    const size_t lds = (size_t)128 * a.T * a.kc;
+#define POLICYHEAD_FWD(T, F64) hipLaunchKernelGGL((policyhead_forward_kernel<T, F64>), dim3(grid), dim3(PH_THREADS), lds, (hipStream_t)stream, a)
+    if (a.T == 1) { if (a.out_fp64) POLICYHEAD_FWD(1, true); else POLICYHEAD_FWD(1, false); }
+    else { if (a.out_fp64) POLICYHEAD_FWD(2, true); else POLICYHEAD_FWD(2, false); }
+#undef POLICYHEAD_FWD
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_policyhead_backward(const f110_policyhead_config *cfg, const float *h, int64_t n, const float *w_mean, const float *w_log_std,
+                                        const float *pre, const float *eps, const void *grad_action, const void *grad_log_prob, const float *grad_pre,
+                                        float *grad_h, float *grad_w_mean, float *grad_b_mean, float *grad_w_log_std, float *grad_b_log_std, float *workspace,
+                                        void *stream)
+{
+    const char *who = "f110_policyhead_backward";
+    if (int rc = f110_policyhead_validate(cfg)) return rc;
+    if (n < 0 || n > PH_MAX_ROWS) return fail(F110_E_INVALID, "%s: n=%lld rows (0..%lld)", who, (long long)n, (long long)PH_MAX_ROWS);
+    if (n == 0) return F110_OK;
+    if (!h || !w_mean || !w_log_std || !pre || !grad_action || !workspace) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (!eps && grad_log_prob) return fail(F110_E_INVALID, "%s: grad_log_prob without eps (no log_prob was produced)", who);
+    if ((uintptr_t)workspace % 16) return fail(F110_E_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    if (int rc = policyhead_check_device(who, (hipStream_t)stream, {{"h", h}, {"w_mean", w_mean}, {"w_log_std", w_log_std}, {"pre", pre},
+                                                                    {"grad_action", grad_action}, {"workspace", workspace}})) return rc;
+    PolicyheadArgs a;
+    policyhead_geometry(*cfg, n, a);
+    a.h = h; a.w_mean = w_mean; a.w_log_std = w_log_std; a.eps = eps; a.pre = const_cast<float *>(pre);
+    a.grad_action = grad_action; a.grad_log_prob = grad_log_prob; a.grad_pre = grad_pre;
+    a.gpre = workspace; a.partial = workspace + policyhead_gpre_floats(*cfg, n);
+    a.grad_h = grad_h; a.grad_w_mean = grad_w_mean; a.grad_b_mean = grad_b_mean; a.grad_w_log_std = grad_w_log_std; a.grad_b_log_std = grad_b_log_std;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((n * a.A + PH_THREADS - 1) / PH_THREADS);
+    if (a.out_fp64) hipLaunchKernelGGL(policyhead_gpre_kernel<true>, dim3(blocks), dim3(PH_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(policyhead_gpre_kernel<false>, dim3(blocks), dim3(PH_THREADS), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    if (grad_h) {
+        hipLaunchKernelGGL(policyhead_gradh_kernel, dim3((unsigned)((n + PH_GH_ROWS - 1) / PH_GH_ROWS), (unsigned)((a.K + PH_THREADS - 1) / PH_THREADS)),
+                           dim3(PH_THREADS), 0, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (grad_w_mean || grad_b_mean || grad_w_log_std || grad_b_log_std) {
+        hipLaunchKernelGGL(policyhead_gradw_kernel, dim3((unsigned)a.slices, (unsigned)((a.K + 63) / 64 + 1)), dim3(64), 0, s, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(policyhead_reduce_kernel, dim3((unsigned)((2 * a.A * (a.K + 1) + PH_THREADS - 1) / PH_THREADS)), dim3(PH_THREADS), 0, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return F110_OK;
+}
+
 // ---------------------------------------------------------------- scan -> bitmap
 static const void *bitmap_fn(size_t lds, int mode, int channels)
 {

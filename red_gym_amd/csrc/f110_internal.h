@@ -5,7 +5,7 @@
 //   f110_maps.hip       map installation (host table / occupancy mask -> cell codes, LUTs), device EDT, track mask
 //   f110_noise_abi.hip  lidar noise: slots, ring, generators, per-env mode
 //   f110_step.hip       launch policy of the scan, the step, hipGraphs, measurement aid, function-level entry points
-//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, progress tracker, reward shaper, path follower, replay buffer, bit convolution, policy stem, scan -> bitmap,
+//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, progress tracker, reward shaper, path follower, replay buffer, bit convolution, policy stem, policy head, scan -> bitmap,
 //                       occupancy grid
 #pragma once
 #include "../../include/f110_hip.h"
@@ -18,6 +18,7 @@
 #include "f110_replay.h"
 #include "f110_bitconv.h"
 #include "f110_bitconv2.h"
+#include "f110_policyhead.h"
 #include "f110_bitmap.h"
 #include "f110_mapgen.h"
 

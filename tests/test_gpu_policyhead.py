@@ -1,0 +1,532 @@
+"""The policy head on the GPU (csrc/f110_policyhead.h): `pre` `==` the checker of tests/policyhead_cases.py as raw 32-bit patterns
+at every shape-selected path (ph.paths), action and log_prob within the tail bounds, margins, batch independence, repeatability; the
+backward pass against the fp64 reference built from the kernel's own `pre`, two exact cases; the module; and the closed loop from the
+env's bitmap to the step, eager and through a captured graph."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import bitconv_cases as bc
+import policyhead_cases as ph
+
+pytestmark = pytest.mark.gpu
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _dev(a):
+    import torch
+    return None if a is None else torch.as_tensor(np.ascontiguousarray(a), device='cuda')
+
+
+def _bits(a):
+    return bc.bit_patterns(a if isinstance(a, np.ndarray) else _np(a))
+
+
+_pre_cache = {}
+
+
+def _case(shape, with_bias):
+    """(host inputs, the checker's pre) of a shape, computed once and left unchanged."""
+    key = (shape, with_bias)
+    if key not in _pre_cache:
+        h, wm, bm, wl, bl, eps = ph.inputs(*shape)
+        if not with_bias:
+            bm = bl = None
+        pre = ph.pre_activations(h, wm, bm, wl, bl)
+        pre.setflags(write=False)
+        _pre_cache[key] = ((h, wm, bm, wl, bl, eps), pre)
+    return _pre_cache[key]
+
+
+def _check_tail(got_action, got_lp, pre, eps, fp32, what):
+    t = ph.tail(pre, eps)
+    act_b, lp_b = ph.tail_bounds(pre, eps, out_fp32=fp32)
+    err = np.abs(_np(got_action).astype(np.float64) - t['y'])
+    print('%s: worst action error / bound %.3g' % (what, float((err / np.maximum(act_b, 1e-300)).max())))
+    assert (err <= act_b).all(), what
+    if eps is None:
+        assert got_lp is None
+        return
+    err = np.abs(_np(got_lp).astype(np.float64) - t['log_prob'])
+    print('%s: worst log_prob error / bound %.3g (largest bound %.3g)' % (what, float((err / np.maximum(lp_b, 1e-300)).max()), float(lp_b.max())))
+    assert (err <= lp_b).all(), what
+
+
+@pytest.mark.parametrize('shape', ph.FORWARD_SHAPES)
+def test_forward_equals_checker(shape):
+    """Sampling and eps=None, with and without biases, both dtypes: pre `==` the checker as raw bit patterns, action and log_prob
+    within the tail bounds, mean and log_std the view and the clamp of pre; two calls give the same bits.  With biases the rows at
+    and beyond both clamps and the saturated rows are there."""
+    import torch
+    from red_gym_amd.policyhead import sample_actions
+    n, K, A = shape
+    for with_bias in (True, False):
+        host, pre = _case(shape, with_bias)
+        h, wm, bm, wl, bl, eps = (_dev(x) for x in host)
+        if with_bias and A >= 4 and n >= 4:
+            t = ph.tail(pre, host[5])
+            assert {-20.0, 2.0, -25.0, 3.0} <= set(pre[n // 2, A:].tolist()) and (np.abs(t['y'][n // 3]) == 1.0).any()
+        for e_dev, e_host in ((eps, host[5]), (None, None)):
+            for dtype in (torch.float64, torch.float32):
+                what = '%s bias=%s %s %s' % (shape, with_bias, 'sampling' if e_host is not None else 'evaluate', dtype)
+                action, lp, mean, ls = sample_actions(h, wm, bm, wl, bl, eps=e_dev, dtype=dtype)
+                assert action.dtype == dtype and tuple(action.shape) == (n, A) and (lp is None) == (e_host is None)
+                assert lp is None or (lp.dtype == dtype and tuple(lp.shape) == (n,))
+                got = _np(mean._base)                                  # (mean is a view of the kernel's pre [n, 2A])
+                assert got.shape == pre.shape and mean.data_ptr() == mean._base.data_ptr()
+                bad = int((_bits(got) != _bits(pre)).sum()) + int((_bits(_np(ls)) != _bits(np.clip(pre[:, A:], np.float32(-20.0), np.float32(2.0)))).sum())
+                print('%s: %d of %d pre-activations differ' % (what, bad, got.size))
+                assert bad == 0, what
+                _check_tail(action, lp, pre, e_host, dtype == torch.float32, what)
+                again = sample_actions(h, wm, bm, wl, bl, eps=e_dev, dtype=dtype)
+                assert torch.equal(again[0], action) and (lp is None or torch.equal(again[1], lp)) and torch.equal(again[2], mean)
+
+
+def _raw_forward(host, n, K, A, fp64, sampling, sentinel=-7.0):
+    """f110_policyhead_forward itself into arrays of `sentinel` with guards before and after -> (pre, action, log_prob) on the host."""
+    import torch
+    from red_gym_amd import _lib, policyhead
+    lib = _lib.load()
+    cfg = policyhead.make_config(K, A, fp64)
+    h, wm, bm, wl, bl, eps = (_dev(x) for x in host)
+    dt = torch.float64 if fp64 else torch.float32
+    G = 64
+    bufs = [torch.full((n * 2 * A + 2 * G,), sentinel, dtype=torch.float32, device='cuda'), torch.full((n * A + 2 * G,), sentinel, dtype=dt, device='cuda'),
+            torch.full((n + 2 * G,), sentinel, dtype=dt, device='cuda')]
+    ptr = [b.data_ptr() + G * b.element_size() for b in bufs]
+    _lib.check(lib.f110_policyhead_forward(C.byref(cfg), h.data_ptr(), n, wm.data_ptr(), None if bm is None else bm.data_ptr(), wl.data_ptr(),
+                                           None if bl is None else bl.data_ptr(), eps.data_ptr() if sampling else None, ptr[0], ptr[1],
+                                           ptr[2] if sampling else None, torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    out = []
+    for b, size in zip(bufs, (n * 2 * A, n * A, n)):
+        a = _np(b)
+        assert (a[:G] == sentinel).all() and (a[G + size:] == sentinel).all()
+        out.append(a[G:G + size])
+    return out[0].reshape(n, 2 * A), out[1].reshape(n, A), out[2]
+
+
+@pytest.mark.parametrize('shape', [s for s in ph.FORWARD_SHAPES if s[0] <= 100])
+def test_margins_through_the_raw_abi(shape):
+    """The guards around pre, action and log_prob stay as they were and no element keeps the sentinel (-7 cannot be a tanh, and
+    no pre-activation or log_prob of these inputs equals it); without eps log_prob is not touched at all."""
+    n, K, A = shape
+    host, pre = _case(shape, True)
+    assert (pre != -7.0).all()
+    for fp64 in (True, False):
+        p, a, lp = _raw_forward(host, n, K, A, fp64, True)
+        assert (_bits(p) == _bits(pre)).all() and (a != -7.0).all() and (lp != -7.0).all()
+        p, a, lp = _raw_forward(host, n, K, A, fp64, False)
+        assert (_bits(p) == _bits(pre)).all() and (a != -7.0).all() and (lp == -7.0).all()
+
+
+def test_wrong_device_is_refused():
+    """F110_E_INVALID, not a launch: host memory (pageable and pinned) in the place of each required pointer, and, where the machine
+    has a second GPU, a tensor and a stream of that one; the outputs keep their fill."""
+    import torch
+    from red_gym_amd import _lib, policyhead
+    lib = _lib.load()
+    n, K, A = 5, 100, 3
+    cfg = policyhead.make_config(K, A, True)
+    h, wm, bm, wl, bl, eps = (_dev(x) for x in ph.inputs(n, K, A))
+    pre = torch.full((n, 2 * A), -7.0, dtype=torch.float32, device='cuda')
+    act, lp = torch.full((n, A), -7.0, dtype=torch.float64, device='cuda'), torch.full((n,), -7.0, dtype=torch.float64, device='cuda')
+
+    def forward(ptrs, stream=None):
+        return lib.f110_policyhead_forward(C.byref(cfg), ptrs[0], n, ptrs[1], bm.data_ptr(), ptrs[2], bl.data_ptr(), eps.data_ptr(), ptrs[3], ptrs[4],
+                                           lp.data_ptr(), stream)
+
+    good = [h.data_ptr(), wm.data_ptr(), wl.data_ptr(), pre.data_ptr(), act.data_ptr()]
+    pageable = np.zeros(n * K, np.float64)
+    pinned = torch.zeros(n * K, dtype=torch.float64).pin_memory()
+    others = [('pageable', pageable.ctypes.data), ('pinned', pinned.data_ptr())]
+    if torch.cuda.device_count() > 1:
+        far = torch.zeros(n * K, dtype=torch.float64, device='cuda:1')
+        others.append(('cuda:1', far.data_ptr()))
+        assert forward(good, torch.cuda.Stream(device='cuda:1').cuda_stream) == _lib.E_INVALID and b'stream' in lib.f110_last_error()
+    for what, bad in others:
+        for hole, name in enumerate(('h', 'w_mean', 'w_log_std', 'pre', 'action')):
+            ptrs = list(good)
+            ptrs[hole] = bad
+            assert forward(ptrs) == _lib.E_INVALID, (what, name)
+            assert ('`%s`' % name).encode() in lib.f110_last_error(), (what, name)
+    ws = torch.zeros(policyhead.workspace_bytes(K, A, n) // 4, dtype=torch.float32, device='cuda')
+    ga = torch.ones((n, A), dtype=torch.float64, device='cuda')
+    for what, bad in others:
+        for hole in range(6):
+            q = [h.data_ptr(), wm.data_ptr(), wl.data_ptr(), pre.data_ptr(), ga.data_ptr(), ws.data_ptr()]
+            q[hole] = bad - bad % 16
+            rc = lib.f110_policyhead_backward(C.byref(cfg), q[0], n, q[1], q[2], q[3], eps.data_ptr(), q[4], None, None, None, None, None, None, None, q[5], None)
+            assert rc == _lib.E_INVALID, (what, hole)
+    torch.cuda.synchronize()
+    assert bool((pre == -7.0).all()) and bool((act == -7.0).all()) and bool((lp == -7.0).all())
+    assert forward(good, torch.cuda.current_stream().cuda_stream) == 0 and forward(good, torch.cuda.Stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    assert bool((pre != -7.0).all()) and bool((act != -7.0).all())
+
+
+def test_rows_do_not_depend_on_the_batch():
+    """A row's pre, action and log_prob are the same bits alone, in a batch of 131 and at another place of a batch of 4099."""
+    import torch
+    from red_gym_amd.policyhead import sample_actions
+    K, A = 515, 17
+    host = ph.inputs(131, K, A, seed=3)
+    h, wm, bm, wl, bl, eps = (_dev(x) for x in host)
+    full = sample_actions(h, wm, bm, wl, bl, eps=eps)
+    for i in (0, 15, 16, 64, 130):
+        one = sample_actions(h[i:i + 1].contiguous(), wm, bm, wl, bl, eps=eps[i:i + 1].contiguous())
+        for a, b in zip(full, one):
+            assert torch.equal(a[i:i + 1], b)
+    big_h, big_e = torch.zeros((4099, K), device='cuda'), torch.zeros((4099, A), device='cuda')
+    perm = torch.randperm(4099, device='cuda', generator=torch.Generator('cuda').manual_seed(1))[:131]
+    big_h[perm], big_e[perm] = h, eps
+    big = sample_actions(big_h, wm, bm, wl, bl, eps=big_e)
+    for a, b in zip(full, big):
+        assert torch.equal(a, b[perm])
+    assert not torch.equal(full[0][0], full[0][1])
+
+
+def test_out_is_written_in_place_and_mismatches_are_refused():
+    import torch
+    from red_gym_amd.policyhead import sample_actions
+    n, K, A = 33, 5, 15
+    h, wm, bm, wl, bl, eps = (_dev(x) for x in ph.inputs(n, K, A))
+    want = sample_actions(h, wm, bm, wl, bl, eps=eps)
+    raw = torch.full((n, A), 9.0, dtype=torch.float64, device='cuda')
+    got = sample_actions(h, wm.requires_grad_(), bm, wl, bl, eps=eps, out=raw)
+    assert got[0].data_ptr() == raw.data_ptr() and torch.equal(raw, want[0]) and torch.equal(got[1], want[1])
+    assert got[0].grad_fn is None and got[1].grad_fn is None and not raw.requires_grad
+    wm = wm.detach()
+    raw32 = torch.empty((n, A), dtype=torch.float32, device='cuda')
+    assert sample_actions(h, wm, bm, wl, bl, eps=None, dtype=torch.float32, out=raw32)[0].data_ptr() == raw32.data_ptr()
+    for args, kw in (((h.double(), wm, bm, wl, bl), {}), ((h, wm.double(), bm, wl, bl), {}), ((h, wm[:, :4].contiguous(), bm, wl, bl), {}),
+                     ((h, wm, bm, wl[:3], bl), {}), ((h, wm, bm[:3], wl, bl), {}), ((h, wm, bm, wl, bl.double()), {}),
+                     ((h, wm, bm, wl, bl), dict(eps=eps[:5])), ((h, wm, bm, wl, bl), dict(eps=eps.double())),
+                     ((h, wm, bm, wl, bl), dict(eps=eps, dtype=torch.float16)), ((h, wm, bm, wl, bl), dict(eps=eps, out=raw32)),
+                     ((h, wm, bm, wl, bl), dict(eps=eps, out=raw[:5])), ((h.cpu(), wm, bm, wl, bl), {}), ((h, wm.cpu(), bm, wl, bl), {}),
+                     ((h, wm, bm, wl, bl), dict(eps=eps.cpu())), ((h[0], wm, bm, wl, bl), {}),
+                     ((torch.zeros((2, 4097), device='cuda'), torch.zeros((2, 4097), device='cuda'), None, torch.zeros((2, 4097), device='cuda'), None), {}),
+                     ((torch.zeros((2, 8), device='cuda'), torch.zeros((33, 8), device='cuda'), None, torch.zeros((33, 8), device='cuda'), None), {})):
+        with pytest.raises(ValueError):
+            sample_actions(*args, **kw)
+    empty = sample_actions(h[:0], wm, bm, wl, bl, eps=eps[:0])
+    assert tuple(empty[0].shape) == (0, A) and tuple(empty[1].shape) == (0,)
+
+
+def _raw_backward(host, pre, g_y, g_lp, fp64, sampling, fill=float('nan'), skip=(), g_in=None):
+    """f110_policyhead_backward itself from a workspace of `fill` -> dict of host arrays (outputs named in `skip` are passed as NULL)."""
+    import torch
+    from red_gym_amd import _lib, policyhead
+    lib = _lib.load()
+    h, wm, bm, wl, bl, eps = (_dev(x) for x in host)
+    n, K = h.shape
+    A = wm.shape[0]
+    cfg = policyhead.make_config(K, A, fp64)
+    dt = torch.float64 if fp64 else torch.float32
+    ga, glp = _dev(g_y).to(dt), None if g_lp is None else _dev(g_lp).to(dt)
+    gin = None if g_in is None else _dev(g_in)
+    nbytes = policyhead.workspace_bytes(K, A, n)
+    G = 64
+    ws = torch.full((nbytes // 4 + 2 * G,), fill, dtype=torch.float32, device='cuda')
+    outs = {k: torch.full(s, 7.0, dtype=torch.float32, device='cuda')
+            for k, s in (('grad_h', (n, K)), ('grad_w_mean', (A, K)), ('grad_b_mean', (A,)), ('grad_w_log_std', (A, K)), ('grad_b_log_std', (A,)))}
+    p = {k: (None if k in skip else v.data_ptr()) for k, v in outs.items()}
+    _lib.check(lib.f110_policyhead_backward(C.byref(cfg), h.data_ptr(), n, wm.data_ptr(), wl.data_ptr(), _dev(pre).data_ptr(),
+                                            eps.data_ptr() if sampling else None, ga.data_ptr(), None if glp is None else glp.data_ptr(),
+                                            None if gin is None else gin.data_ptr(),
+                                            p['grad_h'], p['grad_w_mean'], p['grad_b_mean'], p['grad_w_log_std'], p['grad_b_log_std'],
+                                            ws.data_ptr() + 4 * G, torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    w = _np(ws)
+    guard = np.float32(fill)
+    same = (lambda a: np.isnan(a).all()) if np.isnan(guard) else (lambda a: (a == guard).all())
+    assert same(w[:G]) and same(w[G + nbytes // 4:])
+    res = {k: _np(v) for k, v in outs.items()}
+    for k in skip:
+        assert (res[k] == 7.0).all()
+    res['g_pre'] = w[G:G + n * 2 * A].reshape(n, 2 * A)
+    return res
+
+
+def _check_grads(res, host, pre, g_y, g_lp, sampling, what, g_in=None):
+    h, wm, bm, wl, bl, eps = host
+    A = wm.shape[0]
+    g, gb = ph.g_pre(pre, eps if sampling else None, g_y, g_lp, g_in)
+    want = ph.gradients(h, wm, wl, g, gb)
+    got = {'g_pre': res['g_pre'], 'grad_h': res['grad_h'], 'grad_w': np.concatenate([res['grad_w_mean'], res['grad_w_log_std']]),
+           'grad_b': np.concatenate([res['grad_b_mean'], res['grad_b_log_std']])}
+    want['g_pre'] = (g, gb)
+    for k, (ref, bound) in want.items():
+        assert np.isfinite(got[k]).all(), (what, k)
+        err = np.abs(got[k].astype(np.float64) - ref)
+        ulp = bc.U * np.abs(ref)                                  # the final rounding of the fp32 result
+        print('%s %s: worst error / bound %.3g' % (what, k, float((err / np.maximum(bound + ulp, 1e-300)).max())))
+        assert (err <= bound + ulp).all(), (what, k)
+    assert (got['grad_h'] != 0).any() and (got['grad_w'][:A] != 0).any() and (got['grad_b'][:A] != 0).any()
+    if sampling:
+        assert (got['grad_w'][A:] != 0).any() or h.shape[0] == 1
+    else:
+        assert g_in is not None or ((got['g_pre'][:, A:] == 0).all() and (got['grad_w'][A:] == 0).all() and (got['grad_b'][A:] == 0).all())
+
+
+@pytest.mark.parametrize('shape', ph.BACKWARD_SHAPES)
+def test_backward_within_bounds_and_repeatable(shape):
+    """All gradients within their bounds of the fp64 reference built from the kernel's own pre, from a workspace of NaN; a second
+    call from a workspace of another fill gives the same bits; sampling and eps=None, fp64 and fp32 gradients; NULL outputs are
+    skipped and the others unchanged by that."""
+    from red_gym_amd.policyhead import sample_actions
+    n, K, A = shape
+    host = ph.inputs(n, K, A, seed=5, special=n > 1)
+    h, wm, bm, wl, bl, eps = (_dev(x) for x in host)
+    pre = _np(sample_actions(h, wm, bm, wl, bl, eps=eps)[2]._base)               # the kernel's own pre
+    assert (_bits(pre) == _bits(ph.pre_activations(*host[:5]))).all()
+    if n > 1:
+        assert (pre[:, A:] > 2.0).any() and (pre[:, A:] < -20.0).any() and ((pre[:, A:] == 2.0) | (pre[:, A:] == -20.0)).any() or A < 4
+    rng = np.random.default_rng([n, K, A])
+    g_y, g_lp = rng.normal(size=(n, A)), rng.normal(size=n)
+    for fp64 in (True, False):
+        gy, glp = (g_y, g_lp) if fp64 else (g_y.astype(np.float32).astype(np.float64), g_lp.astype(np.float32).astype(np.float64))
+        first = _raw_backward(host, pre, gy, glp, fp64, True)
+        _check_grads(first, host, pre, gy, glp, True, '%s fp64=%s sampling' % (shape, fp64))
+        second = _raw_backward(host, pre, gy, glp, fp64, True, fill=3.0e38)
+        assert all((_bits(first[k]) == _bits(second[k])).all() for k in first)
+    g_in = rng.normal(size=(n, 2 * A)).astype(np.float32)                      # a gradient arriving at pre itself joins g_pre
+    for sampling, glp in ((True, g_lp), (False, None)):
+        _check_grads(_raw_backward(host, pre, g_y, glp, True, sampling, g_in=g_in), host, pre, g_y, glp, sampling,
+                     '%s grad_pre sampling=%s' % (shape, sampling), g_in=g_in)
+    ev = _raw_backward(host, pre, g_y, None, True, False)
+    _check_grads(ev, host, pre, g_y, None, False, '%s evaluate' % (shape,))
+    part = _raw_backward(host, pre, g_y, g_lp, True, True, skip=('grad_h', 'grad_b_mean', 'grad_w_log_std'))
+    full = _raw_backward(host, pre, g_y, g_lp, True, True)
+    assert all((_bits(part[k]) == _bits(full[k])).all() for k in ('grad_w_mean', 'grad_b_log_std', 'g_pre'))
+    only_h = _raw_backward(host, pre, g_y, g_lp, True, True, skip=('grad_w_mean', 'grad_b_mean', 'grad_w_log_std', 'grad_b_log_std'))
+    assert (_bits(only_h['grad_h']) == _bits(full['grad_h'])).all()
+
+
+@pytest.mark.parametrize('shape', [(2 * ph.R + 3, 70, 17), (ph.R + 1, 33, 3)])
+def test_backward_exact_weight_sums(shape):
+    """Zero weights and biases, eps = 0, small-integer h, grad_action and grad_log_prob: pre = 0, y = 0, so g_pre = [g_y | -g_lp]
+    exactly, and grad_w and grad_b must `==` the integer sums (every partial sum stays below 2^24): no term lost, doubled or
+    misplaced, in either stage."""
+    n, K, A = shape
+    rng = np.random.default_rng([n, K, A, 1])
+    h = rng.integers(0, 8, (n, K)).astype(np.float32)
+    g_y, g_lp = rng.integers(-4, 5, (n, A)).astype(np.float64), rng.integers(-4, 5, n).astype(np.float64)
+    host = (h, np.zeros((A, K), np.float32), None, np.zeros((A, K), np.float32), None, np.zeros((n, A), np.float32))
+    pre = np.zeros((n, 2 * A), np.float32)
+    res = _raw_backward(host, pre, g_y, g_lp, True, True)
+    g = np.concatenate([g_y, np.repeat(-g_lp[:, None], A, axis=1)], axis=1)
+    assert np.array_equal(res['g_pre'].astype(np.float64), g)
+    gw, gb = g.T @ h.astype(np.float64), g.sum(axis=0)
+    assert (np.abs(g).T @ h).max() < 2 ** 24
+    assert np.array_equal(np.concatenate([res['grad_w_mean'], res['grad_w_log_std']]).astype(np.float64), gw)
+    assert np.array_equal(np.concatenate([res['grad_b_mean'], res['grad_b_log_std']]).astype(np.float64), gb)
+    assert (res['grad_h'] == 0).all()
+    assert len({tuple(r) for r in gw.tolist()}) > A and (gw != 0).any(axis=1).all()      # rows differ: a misplaced one would show
+
+
+@pytest.mark.parametrize('shape', [(37, 300, 17), (3, 70, 32)])
+def test_backward_exact_grad_h(shape):
+    """h = 0, integer weights, zero biases, eps = 0: pre = 0 again, g_pre = [g_y | -g_lp], and grad_h must `==` g_pre @ W."""
+    n, K, A = shape
+    rng = np.random.default_rng([n, K, A, 2])
+    wm, wl = rng.integers(-8, 9, (2, A, K)).astype(np.float32)
+    g_y, g_lp = rng.integers(-4, 5, (n, A)).astype(np.float64), rng.integers(-4, 5, n).astype(np.float64)
+    host = (np.zeros((n, K), np.float32), wm, None, wl, None, np.zeros((n, A), np.float32))
+    res = _raw_backward(host, np.zeros((n, 2 * A), np.float32), g_y, g_lp, True, True)
+    g = np.concatenate([g_y, np.repeat(-g_lp[:, None], A, axis=1)], axis=1)
+    want = g @ np.concatenate([wm, wl]).astype(np.float64)
+    assert np.array_equal(res['grad_h'].astype(np.float64), want) and (want != 0).any()
+    assert (res['grad_w_mean'] == 0).all() and (res['grad_w_log_std'] == 0).all()
+    assert np.array_equal(res['grad_b_mean'].astype(np.float64), g_y.sum(axis=0))
+
+
+def _g20_bound_check(golden, run):
+    """sample_actions (through `run`) on g20's inputs against the recording, within the bound of test_policyhead_cpu's pin."""
+    g = golden('g20_head.npz')
+    R, A = ph.GROUP_ROWS, 16
+    pinned = 0
+    for gi, name in enumerate(ph.GROUPS):
+        rows = slice(gi * R, (gi + 1) * R)
+        wm, bm, wl, bl = ph.group_weights(g, gi)
+        h, eps = g['h'][rows], g['eps'][rows]
+        action, lp, mean, ls = run(h, wm, bm, wl, bl, eps)
+        pre = ph.pre_activations(h, wm, bm, wl, bl)
+        assert (_bits(_np(mean)) == _bits(pre[:, :A])).all()
+        dpre, dy, dlp = ph.reference_bounds(h, wm, bm, wl, bl, eps, pre)
+        own_a, own_l = ph.tail_bounds(pre, eps)
+        pin_a, pin_l = dy <= 1e-3, dlp <= 1e-3
+        err_a = np.abs(_np(action) - g['action'][rows].astype(np.float64))
+        err_l = np.abs(_np(lp) - g['log_prob'][rows].astype(np.float64))
+        print('%-16s action %5.1f %% value-pinned, log_prob %5.1f %%' % (name, 100 * pin_a.mean(), 100 * pin_l.mean()))
+        assert (err_a[pin_a] <= (dy + own_a)[pin_a]).all() and (err_l[pin_l] <= (dlp + own_l)[pin_l]).all()
+        fin = np.isfinite(dlp)                                           # (the coarse pin of test_policyhead_cpu: every finite bound holds)
+        assert (err_l[fin] <= (dlp + own_l)[fin]).all()
+        sat = np.abs(g['action'][rows]) == 1.0
+        assert (np.abs(_np(action)[sat]) >= 1.0 - 2.0 ** -24).all()
+        pinned += int(pin_a.sum()) + int(pin_l.sum())
+    assert pinned > 0
+
+
+def test_module(golden):
+    """from_linears shares the tensors (an optimiser step on one is seen by the other); the state-dict keys are the reference's;
+    sample_actions on g20's inputs is within the fp32 bound of the recording; act leaves no grad_fn and writes `out`; forward
+    returns (mean, log_std); an update-shaped use fills every .grad."""
+    import torch
+    from red_gym_amd.policyhead import PolicyHead
+    torch.manual_seed(9)
+    fc_mean, fc_log_std = torch.nn.Linear(512, 16).cuda(), torch.nn.Linear(512, 16).cuda()
+    head = PolicyHead.from_linears(fc_mean, fc_log_std)
+    assert head.fc_mean.weight.data_ptr() == fc_mean.weight.data_ptr() and head.fc_log_std.bias.data_ptr() == fc_log_std.bias.data_ptr()
+    keys = [k for k in golden('g20_head.npz')['keys'] if k.startswith('fc_mean') or k.startswith('fc_log_std')]
+    assert sorted(head.state_dict()) == sorted(keys) and len(keys) == 4
+    fresh = PolicyHead(512, 16).cuda()
+    fresh.load_state_dict(head.state_dict())
+    assert torch.equal(fresh.fc_mean.weight, fc_mean.weight)
+    for bad in ((torch.nn.Linear(512, 16), torch.nn.Linear(512, 8)), (torch.nn.Linear(512, 33), torch.nn.Linear(512, 33)),
+                (torch.nn.Conv2d(1, 1, 1), torch.nn.Linear(512, 16))):
+        with pytest.raises(ValueError):
+            PolicyHead.from_linears(*bad)
+    with pytest.raises(ValueError):
+        PolicyHead(4097, 16)
+
+    def run(h, wm, bm, wl, bl, eps):
+        m = PolicyHead(512, 16).cuda()
+        m.load_state_dict({'fc_mean.weight': _dev(wm), 'fc_mean.bias': _dev(bm), 'fc_log_std.weight': _dev(wl), 'fc_log_std.bias': _dev(bl)})
+        with torch.no_grad():
+            return m.sample(_dev(h), eps=_dev(eps))
+    _g20_bound_check(golden, run)
+
+    h = torch.randn((64, 512), device='cuda').relu_()
+    raw = torch.zeros((64, 16), dtype=torch.float64, device='cuda')
+    a = head.act(h, out=raw, generator=torch.Generator('cuda').manual_seed(4))
+    assert a.grad_fn is None and a.data_ptr() == raw.data_ptr() and bool((raw.abs() <= 1).all()) and bool((raw != 0).any())
+    b = head.act(h, evaluate=True)
+    mean, ls = head(h)
+    assert b.grad_fn is None and b.dtype == torch.float64 and torch.equal(b, torch.tanh(mean.double()))
+    assert mean.grad_fn is not None and ls.grad_fn is not None and bool(((ls >= -20) & (ls <= 2)).all())
+    with torch.no_grad():
+        assert head(h)[0].grad_fn is None
+    gen = torch.Generator('cuda').manual_seed(4)
+    eps = torch.randn((64, 16), dtype=torch.float32, device='cuda', generator=gen)
+    assert torch.equal(head.sample(h, eps=eps)[0].detach(), raw)                    # (the draws are torch's)
+    # update-shaped: (alpha * logp - q(new_a)).mean().backward() through a critic head, the features require grad too
+    q = torch.nn.Linear(16, 1).cuda().double()
+    hh = h.clone().requires_grad_()
+    new_a, logp, _, _ = head.sample(hh, eps=eps)
+    assert new_a.grad_fn is not None and logp.grad_fn is not None
+    (0.2 * logp - q(new_a)[:, 0]).mean().backward()
+    params = [fc_mean.weight, fc_mean.bias, fc_log_std.weight, fc_log_std.bias]
+    for p in params + [hh]:
+        assert p.grad is not None and p.grad.shape == p.shape and bool(torch.isfinite(p.grad).all()) and bool((p.grad != 0).any())
+    # against torch's own autograd of the same formula in fp64
+    ref = [p.detach().double().requires_grad_() for p in params + [hh]]
+    mean64, ls64 = ref[4] @ ref[0].T + ref[1], torch.clamp(ref[4] @ ref[2].T + ref[3], -20, 2)
+    y = torch.tanh(mean64 + ls64.exp() * eps.double())
+    lp64 = (-(eps.double() ** 2) / 2 - ls64 - ph.HALF_LOG_2PI - torch.log(1.0 - y * y + 1e-6)).sum(1)
+    (0.2 * lp64 - q(y)[:, 0]).mean().backward()
+    for name, p, r in zip(('fc_mean.weight', 'fc_mean.bias', 'fc_log_std.weight', 'fc_log_std.bias', 'h'), params + [hh], ref):
+        err = float((p.grad.double() - r.grad).abs().max())
+        scale = float(r.grad.abs().max())
+        print('%s.grad: largest difference from fp64 autograd %.3g (largest entry %.3g)' % (name, err, scale))
+        # the reference here starts from fp64 pre-activations; the kernel's fp32 ones differ by up to gamma_514 (sum |w| |h| + |b|),
+        # about 3e-5 * 5, the tail's derivatives with respect to them are of order one, and an entry adds up to 64 such terms of
+        # like sign at worst: a few times 1.5e-4 of the largest entry, where a lost or doubled term would change it by its own size
+        assert err <= 1e-3 * scale
+    # a regulariser on mean and log_std alone (forward(h)), and one mixed with the sample: gradients reach every parameter and h
+    for mixed in (False, True):
+        for p in params + [hh]:
+            p.grad = None
+        if mixed:
+            a2, lp2, m2, s2 = head.sample(hh, eps=eps)
+            loss = (0.2 * lp2 - a2.sum(1)).mean() + (m2.double() ** 2).mean() + 0.01 * s2.double().sum()
+        else:
+            m2, s2 = head(hh)
+            loss = (m2.double() ** 2).mean() + 0.01 * s2.double().sum()
+        loss.backward()
+        ref = [p.detach().double().requires_grad_() for p in params + [hh]]
+        mean64, ls64 = ref[4] @ ref[0].T + ref[1], torch.clamp(ref[4] @ ref[2].T + ref[3], -20, 2)
+        want = (mean64 ** 2).mean() + 0.01 * ls64.sum()
+        if mixed:
+            y = torch.tanh(mean64 + ls64.exp() * eps.double())
+            want = want + (0.2 * (-(eps.double() ** 2) / 2 - ls64 - ph.HALF_LOG_2PI - torch.log(1.0 - y * y + 1e-6)).sum(1) - y.sum(1)).mean()
+        want.backward()
+        for name, p, r in zip(('fc_mean.weight', 'fc_mean.bias', 'fc_log_std.weight', 'fc_log_std.bias', 'h'), params + [hh], ref):
+            err, scale = float((p.grad.double() - r.grad).abs().max()), float(r.grad.abs().max())
+            print('regulariser (mixed=%s) %s.grad: largest difference from fp64 autograd %.3g (largest entry %.3g)' % (mixed, name, err, scale))
+            assert scale > 0 and err <= 1e-3 * scale                       # (the bound reasoned above)
+    # an optimiser step through the head is seen by the Actor's layers
+    before = fc_mean.weight.detach().clone()
+    torch.optim.SGD(head.parameters(), lr=0.1).step()
+    assert not torch.equal(fc_mean.weight, before) and head.fc_mean.weight.data_ptr() == fc_mean.weight.data_ptr()
+
+
+def test_closed_loop_eager_and_graph(assets):
+    """64 envs with shaper, follower and ring: stem -> conv3 -> fc1 -> PolicyHead.sample(out=raw) -> path_actions -> step, eager and
+    with the step captured (the follower reads `raw` inside the graph): raw and the step's outputs `==` between the two, and every
+    step's action within bound of the checker fed the same h and eps."""
+    import torch
+    from red_gym_amd import F110VecEnv, workload
+    from red_gym_amd.bitconv import BitConvStem
+    from red_gym_amd.policyhead import PolicyHead
+    B, AD, rows, cols, STEPS = 64, 16, 75, 100, 12
+    env = F110VecEnv(B, map=os.path.join(assets, 'example_map'), map_ext='.png', num_agents=1, autoreset=True, timestep=0.025)
+    env.shape_rewards(rows=rows, cols=cols)
+    env.follow_paths()
+    env.record_replay(capacity=4 * B, action_dim=AD)
+    torch.manual_seed(11)
+    stem = BitConvStem(16, 8, 4, 32, 4, 2, on=1.0, cols=cols).cuda()
+    conv3, fc1 = torch.nn.Conv2d(32, 32, 3, 1).cuda(), torch.nn.Linear(32 * 5 * 9, 512).cuda()
+    head = PolicyHead(512, AD).cuda()
+    with torch.no_grad():
+        head.fc_mean.weight.mul_(20.0)                                # (actions that use the whole range, so that paths differ)
+    host = tuple(_np(p) for p in (head.fc_mean.weight, head.fc_mean.bias, head.fc_log_std.weight, head.fc_log_std.bias))
+    eps_pool = torch.randn((STEPS, B, AD), device='cuda', generator=torch.Generator('cuda').manual_seed(2))
+    raw = torch.zeros((B, AD), dtype=torch.float64, device='cuda')
+    env.reset(workload.spawn_poses(B, 1))
+    for k in range(3):
+        env.step(env.path_actions(torch.zeros_like(raw)))
+    sd = env.state_dict()
+
+    def run(graph):
+        env.load_state_dict(sd)
+        _, _, _, info = env.step(env.path_actions(torch.zeros_like(raw))) if not graph else (None, None, None, None)
+        if graph:
+            raw.zero_()
+            _, _, _, info = env.step_graph()
+        outs = []
+        for k in range(STEPS):
+            with torch.no_grad():
+                h = torch.relu(fc1(torch.relu(conv3(stem(info['lidar_bitmap']))).flatten(1)))
+                a, lp, _, _ = head.sample(h, eps=eps_pool[k], out=raw)
+            assert a.data_ptr() == raw.data_ptr()
+            if graph:
+                _, rew, done, info = env.step_graph()
+            else:
+                _, rew, done, info = env.step(env.path_actions(raw))
+            outs.append(dict(h=h.clone(), raw=raw.clone(), lp=lp.clone(), state=env.state.clone(), reward=rew.clone(), done=done.clone(),
+                             bitmap=info['lidar_bitmap'].clone(), path=info['path_points'].clone(), stored=env.replay_action.clone()))
+        torch.cuda.synchronize()
+        return outs
+
+    eager = run(False)
+    env.capture_step(policy=lambda e, out: e.path_actions(raw, out=out))
+    graph = run(True)
+    for k, (x, y) in enumerate(zip(eager, graph)):
+        for key in x:
+            assert torch.equal(x[key], y[key]), (k, key)
+    assert not torch.equal(eager[0]['raw'], eager[-1]['raw']) and not torch.equal(eager[0]['state'], eager[-1]['state'])
+    for k, o in enumerate(eager):
+        h, eps = _np(o['h']), _np(eps_pool[k])
+        pre = ph.pre_activations(h, *host)
+        act_b, lp_b = ph.tail_bounds(pre, eps)
+        t = ph.tail(pre, eps)
+        assert (np.abs(_np(o['raw']) - t['y']) <= act_b).all() and (np.abs(_np(o['lp']) - t['log_prob']) <= lp_b).all(), k
+        assert torch.equal(o['stored'], o['raw'].float())
+    assert env.eng.device_errors() == 0
+    env.close()
