@@ -263,6 +263,22 @@ def load():
     return lib
 
 
+def clamp(v):
+    """int(v) clamped into int32: an out-of-range size reaches the library's validate, which can name it."""
+    return max(min(int(v), 2 ** 31 - 1), -2 ** 31)
+
+
+def ptr(t):
+    """data_ptr() of a tensor, NULL for None."""
+    return None if t is None else t.data_ptr()
+
+
+def stream(dev):
+    """The raw handle of the caller's current stream on `dev`."""
+    import torch
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
 def check(rc):
     """Maps C error codes to the exceptions the reference raises for the same
     conditions (ValueError base_classes.py:619 / laser_models.py:446, IndexError :527)."""

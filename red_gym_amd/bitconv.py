@@ -14,22 +14,31 @@ MAX_KERNEL, MAX_CHANNELS = 8, 64
 MAX_KERNEL2, MAX_STEM_CHANNELS, MAX_STEM_WIDTH = 4, 16, 64     # conv_bits2: kernel2, the first layer's channels and output width
 
 
-def make_config(rows, cols, kernel, stride=1, channels=1, on=1.0, relu=False):
-    """An f110_bitconv_config; out-of-range integers are clamped into int32 so that validate() can name them."""
-    c = _lib.BitconvConfig()
-    clamp = lambda v: max(min(int(v), 2 ** 31 - 1), -2 ** 31)  # noqa: E731
+def _first_layer(c, rows, cols, kernel, stride, channels, on, relu):
+    """The fields the two configs share, into `c`."""
+    clamp = _lib.clamp
     c.rows, c.cols, c.kernel, c.stride, c.channels = clamp(rows), clamp(cols), clamp(kernel), clamp(stride), clamp(channels)
     c.relu = 1 if relu else 0
     c.on = float(on)
     return c
 
 
-def validate(rows, cols, kernel, stride=1, channels=1, on=1.0, relu=False):
-    """f110_bitconv_validate (host only, no device): ValueError for what the kernels refuse."""
+def _finite_fp32(on):
+    """float(on); ValueError for a finite value that fp32 cannot hold (inf and nan are f110_bitconv_validate's to name)."""
     on = float(on)
     if math.isfinite(on) and abs(on) > 3.4028234663852886e38:
         raise ValueError('bitconv: `on` = %g is not finite in fp32' % on)
-    c = make_config(rows, cols, kernel, stride, channels, on, relu)
+    return on
+
+
+def make_config(rows, cols, kernel, stride=1, channels=1, on=1.0, relu=False):
+    """An f110_bitconv_config; out-of-range integers are clamped into int32 so that validate() can name them."""
+    return _first_layer(_lib.BitconvConfig(), rows, cols, kernel, stride, channels, on, relu)
+
+
+def validate(rows, cols, kernel, stride=1, channels=1, on=1.0, relu=False):
+    """f110_bitconv_validate (host only, no device): ValueError for what the kernels refuse."""
+    c = make_config(rows, cols, kernel, stride, channels, _finite_fp32(on), relu)
     _lib.check(_lib.load().f110_bitconv_validate(C.byref(c)))
     return c
 
@@ -40,12 +49,9 @@ def output_size(rows, cols, kernel, stride):
 
 def make_config2(rows, cols, kernel, stride, channels, kernel2, stride2, channels2, on=1.0, relu1=True, relu2=True):
     """An f110_bitconv2_config, clamped like make_config."""
-    c = _lib.Bitconv2Config()
-    clamp = lambda v: max(min(int(v), 2 ** 31 - 1), -2 ** 31)  # noqa: E731
-    c.rows, c.cols, c.kernel, c.stride, c.channels = clamp(rows), clamp(cols), clamp(kernel), clamp(stride), clamp(channels)
-    c.kernel2, c.stride2, c.channels2 = clamp(kernel2), clamp(stride2), clamp(channels2)
-    c.relu, c.relu2 = (1 if relu1 else 0), (1 if relu2 else 0)
-    c.on = float(on)
+    c = _first_layer(_lib.Bitconv2Config(), rows, cols, kernel, stride, channels, on, relu1)
+    c.kernel2, c.stride2, c.channels2 = _lib.clamp(kernel2), _lib.clamp(stride2), _lib.clamp(channels2)
+    c.relu2 = 1 if relu2 else 0
     return c
 
 
@@ -53,10 +59,7 @@ def validate2(rows, cols, kernel, stride, channels, kernel2, stride2, channels2,
     """f110_bitconv2_validate (host only, no device): ValueError for what the fused stem refuses -- everything validate()
     refuses in the first layer, more than 16 first-layer channels, kernel2 outside 1..4, stride2 outside 1..kernel2, channels2
     outside 1..64, a first-layer output smaller than kernel2 or wider than 64."""
-    on = float(on)
-    if math.isfinite(on) and abs(on) > 3.4028234663852886e38:
-        raise ValueError('bitconv: `on` = %g is not finite in fp32' % on)
-    c = make_config2(rows, cols, kernel, stride, channels, kernel2, stride2, channels2, on, relu1, relu2)
+    c = make_config2(rows, cols, kernel, stride, channels, kernel2, stride2, channels2, _finite_fp32(on), relu1, relu2)
     _lib.check(_lib.load().f110_bitconv2_validate(C.byref(c)))
     return c
 
@@ -64,10 +67,6 @@ def validate2(rows, cols, kernel, stride, channels, kernel2, stride2, channels2,
 def output_size2(rows, cols, kernel, stride, kernel2, stride2):
     oh, ow = output_size(rows, cols, kernel, stride)
     return (oh - kernel2) // stride2 + 1, (ow - kernel2) // stride2 + 1
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 class _ConvBits(torch.autograd.Function):
@@ -81,8 +80,8 @@ class _ConvBits(torch.autograd.Function):
         b = None if bias is None else bias.detach().contiguous()
         fn = lib.f110_bitconv_forward_u8 if u8 else lib.f110_bitconv_forward
         with torch.cuda.device(dev):
-            _lib.check(fn(C.byref(cfg), frames.data_ptr(), frames.shape[0], None if index is None else index.data_ptr(), n,
-                          w.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr(), _stream(dev)))
+            _lib.check(fn(C.byref(cfg), frames.data_ptr(), frames.shape[0], _lib.ptr(index), n, w.data_ptr(), _lib.ptr(b), out.data_ptr(),
+                          _lib.stream(dev)))
         ctx.cfg, ctx.n, ctx.u8, ctx.has_bias = cfg, n, u8, bias is not None
         ctx.save_for_backward(frames, index, out if cfg.relu else None)
         return out
@@ -106,8 +105,8 @@ class _ConvBits(torch.autograd.Function):
         assert nbytes >= 4 * cfg.channels * (kk + 1)
         ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.f110_bitconv_backward(C.byref(cfg), frames.data_ptr(), frames.shape[0], None if index is None else index.data_ptr(), n,
-                                                 g.data_ptr(), gw.data_ptr(), None if gb is None else gb.data_ptr(), ws.data_ptr(), _stream(dev)))
+            _lib.check(lib.f110_bitconv_backward(C.byref(cfg), frames.data_ptr(), frames.shape[0], _lib.ptr(index), n, g.data_ptr(), gw.data_ptr(),
+                                                 _lib.ptr(gb), ws.data_ptr(), _lib.stream(dev)))
         return None, (gw if ctx.needs_input_grad[1] else None), gb, None, None, None, None
 
 
@@ -125,41 +124,19 @@ def conv_bits(frames, weight, bias=None, stride=1, on=1.0, relu=False, index=Non
         raise ValueError('conv_bits: frames and weight must be tensors')
     if not frames.is_cuda or weight.device != frames.device:
         raise ValueError('conv_bits: frames and weight must be on the same GPU')
-    if frames.dim() != 3:
-        raise ValueError('conv_bits: frames must be [m, rows, words] int64 or [m, rows, cols] uint8, not %s' % (tuple(frames.shape),))
     if weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[1] != 1 or weight.shape[2] != weight.shape[3]:
         raise ValueError('conv_bits: weight must be fp32 [C, 1, k, k], not %s %s' % (weight.dtype, tuple(weight.shape)))
     ch, k = int(weight.shape[0]), int(weight.shape[2])
     if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (ch,) or bias.device != frames.device):
         raise ValueError('conv_bits: bias must be fp32 [%d] on the frames\' device' % ch)
-    rows = int(frames.shape[1])
-    if frames.dtype == torch.uint8:
-        u8 = True
-        if cols is not None and int(cols) != frames.shape[2]:
-            raise ValueError('conv_bits: cols=%d but the uint8 images have %d columns' % (int(cols), frames.shape[2]))
-        cols = int(frames.shape[2])
-    elif frames.dtype == torch.int64:
-        u8 = False
-        if cols is None:
-            raise ValueError('conv_bits: packed frames need cols=')
-        cols = int(cols)
-        if cols < 1 or frames.shape[2] != (cols + 63) // 64:
-            raise ValueError('conv_bits: %d words per row do not hold %d pixels' % (frames.shape[2], cols))
-    else:
-        raise ValueError('conv_bits: frames must be int64 (packed) or uint8, not %s' % frames.dtype)
+    u8, rows, cols = _frames_kind('conv_bits', frames, cols)
     cfg = validate(rows, cols, k, stride, ch, on, relu)
-    if index is not None:
-        if not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 1 or index.device != frames.device:
-            raise ValueError('conv_bits: index must be an int64 vector on the frames\' device')
-        index = index.contiguous()
-        n = int(index.shape[0])
-    else:
-        n = int(frames.shape[0])
+    index, n = _index_arg('conv_bits', index, frames)
     return _ConvBits.apply(frames.contiguous(), weight, bias, index, cfg, n, u8)
 
 
 def _frames_kind(who, frames, cols):
-    """(u8, rows, cols) of `frames` for `who`, with conv_bits' checks."""
+    """(u8, rows, cols) of `frames` for `who`: the checks of both entry points."""
     if frames.dim() != 3:
         raise ValueError('%s: frames must be [m, rows, words] int64 or [m, rows, cols] uint8, not %s' % (who, tuple(frames.shape)))
     rows = int(frames.shape[1])
@@ -175,6 +152,15 @@ def _frames_kind(who, frames, cols):
             raise ValueError('%s: %d words per row do not hold %d pixels' % (who, frames.shape[2], cols))
         return False, rows, cols
     raise ValueError('%s: frames must be int64 (packed) or uint8, not %s' % (who, frames.dtype))
+
+
+def _index_arg(who, index, frames):
+    """(index, n) for `who`: the index made contiguous and its length, or None and the number of frames."""
+    if index is None:
+        return None, int(frames.shape[0])
+    if not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 1 or index.device != frames.device:
+        raise ValueError('%s: index must be an int64 vector on the frames\' device' % who)
+    return index.contiguous(), int(index.shape[0])
 
 
 def conv_bits2(frames, w1, b1, w2, b2, stride1=1, stride2=1, on=1.0, relu1=True, relu2=True, index=None, cols=None):
@@ -204,13 +190,7 @@ def conv_bits2(frames, w1, b1, w2, b2, stride1=1, stride2=1, on=1.0, relu1=True,
             raise ValueError('%s: %s must be fp32 [%d] on the frames\' device' % (who, name, ch))
     u8, rows, cols = _frames_kind(who, frames, cols)
     cfg = validate2(rows, cols, k1, stride1, c1, k2, stride2, c2, on, relu1, relu2)
-    if index is not None:
-        if not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 1 or index.device != frames.device:
-            raise ValueError('%s: index must be an int64 vector on the frames\' device' % who)
-        index = index.contiguous()
-        n = int(index.shape[0])
-    else:
-        n = int(frames.shape[0])
+    index, n = _index_arg(who, index, frames)
     lib = _lib.load()
     dev = frames.device
     frames = frames.contiguous()
@@ -219,9 +199,26 @@ def conv_bits2(frames, w1, b1, w2, b2, stride1=1, stride2=1, on=1.0, relu1=True,
     out = torch.empty((n, c2, oh2, ow2), dtype=torch.float32, device=dev)
     fn = lib.f110_bitconv2_forward_u8 if u8 else lib.f110_bitconv2_forward
     with torch.cuda.device(dev):
-        _lib.check(fn(C.byref(cfg), frames.data_ptr(), frames.shape[0], None if index is None else index.data_ptr(), n,
-                      *[None if t is None else t.data_ptr() for t in tensors], out.data_ptr(), _stream(dev)))
+        _lib.check(fn(C.byref(cfg), frames.data_ptr(), frames.shape[0], _lib.ptr(index), n, *[_lib.ptr(t) for t in tensors], out.data_ptr(),
+                      _lib.stream(dev)))
     return out
+
+
+def _plain_conv(who, conv, name, in_channels, wrong_in):
+    """(kernel, stride) of an nn.Conv2d with `in_channels` inputs, a square kernel and stride, no padding, dilation or groups;
+    ValueError from `who` otherwise.  name: what the messages call the layer ('' for the only one); wrong_in: the sentence for
+    another in_channels, with one %d for it."""
+    pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)  # noqa: E731
+    if not isinstance(conv, torch.nn.Conv2d):
+        raise ValueError('%s: %s an nn.Conv2d' % (who, name + ' is not' if name else 'not'))
+    if conv.in_channels != in_channels:
+        raise ValueError('%s: %s' % (who, wrong_in % conv.in_channels))
+    if conv.groups != 1 or pair(conv.dilation) != (1, 1) or isinstance(conv.padding, str) or pair(conv.padding) != (0, 0):
+        raise ValueError('%s: padding, dilation and groups are not supported%s' % (who, ' in ' + name if name else ''))
+    ks, st = pair(conv.kernel_size), pair(conv.stride)
+    if ks[0] != ks[1] or st[0] != st[1]:
+        raise ValueError('%s: %skernel and stride must be square' % (who, name + '\'s ' if name else ''))
+    return ks[0], st[0]
 
 
 class BitConv2d(torch.nn.Module):
@@ -242,22 +239,13 @@ class BitConv2d(torch.nn.Module):
     def from_conv(cls, conv, on=1.0, relu=False, cols=None):
         """A BitConv2d that shares the parameters of `conv` (the same tensors: training one trains the other).  ValueError
         unless it is an nn.Conv2d(1, C, k, stride) with a square kernel and stride, no padding, dilation or groups."""
-        pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)  # noqa: E731
-        if not isinstance(conv, torch.nn.Conv2d):
-            raise ValueError('BitConv2d.from_conv: not an nn.Conv2d')
-        if conv.in_channels != 1:
-            raise ValueError('BitConv2d.from_conv: in_channels = %d (a bitmap has one channel)' % conv.in_channels)
-        if conv.groups != 1 or pair(conv.dilation) != (1, 1) or isinstance(conv.padding, str) or pair(conv.padding) != (0, 0):
-            raise ValueError('BitConv2d.from_conv: padding, dilation and groups are not supported')
-        ks, st = pair(conv.kernel_size), pair(conv.stride)
-        if ks[0] != ks[1] or st[0] != st[1]:
-            raise ValueError('BitConv2d.from_conv: kernel and stride must be square')
-        validate(ks[0], ks[0], ks[0], st[0], conv.out_channels, on)
+        k, s = _plain_conv('BitConv2d.from_conv', conv, '', 1, 'in_channels = %d (a bitmap has one channel)')
+        validate(k, k, k, s, conv.out_channels, on)
         m = cls.__new__(cls)
         torch.nn.Module.__init__(m)
         m.weight = conv.weight
         m.register_parameter('bias', conv.bias)
-        m.kernel_size, m.stride, m.on, m.relu, m.cols = ks[0], st[0], float(on), bool(relu), cols
+        m.kernel_size, m.stride, m.on, m.relu, m.cols = k, s, float(on), bool(relu), cols
         return m
 
     def forward(self, frames, index=None):
@@ -270,17 +258,7 @@ class BitConv2d(torch.nn.Module):
 
 def _plain_conv2(who, conv2, in_channels):
     """(kernel, stride) of an nn.Conv2d(in_channels, C2, k2, stride2) that the stem can run; ValueError otherwise."""
-    pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)  # noqa: E731
-    if not isinstance(conv2, torch.nn.Conv2d):
-        raise ValueError('%s: conv2 is not an nn.Conv2d' % who)
-    if conv2.in_channels != in_channels:
-        raise ValueError('%s: conv2.in_channels = %d but conv1 has %d output channels' % (who, conv2.in_channels, in_channels))
-    if conv2.groups != 1 or pair(conv2.dilation) != (1, 1) or isinstance(conv2.padding, str) or pair(conv2.padding) != (0, 0):
-        raise ValueError('%s: padding, dilation and groups are not supported in conv2' % who)
-    ks, st = pair(conv2.kernel_size), pair(conv2.stride)
-    if ks[0] != ks[1] or st[0] != st[1]:
-        raise ValueError('%s: conv2\'s kernel and stride must be square' % who)
-    return ks[0], st[0]
+    return _plain_conv(who, conv2, 'conv2', in_channels, 'conv2.in_channels = %%d but conv1 has %d output channels' % in_channels)
 
 
 class BitConvStem(torch.nn.Module):

@@ -1,9 +1,9 @@
 """Builds the gfx950 shared library of the step path in-tree:
     python -m red_gym_amd.build [--force]
 hipcc cross-compiles without a GPU; the resulting libf110_hip.so is git-ignored
-but travels with the tree to the GPU box.  The library is five translation units
-(csrc/f110_internal.h lists them): they are compiled in parallel, each only when it or
-a header it includes has changed, and linked into the one .so."""
+but travels with the tree to the GPU box.  The library is the translation units of UNITS
+(csrc/f110_internal.h says what each holds): they are compiled in parallel, each only when
+it or a header has changed, and linked into the one .so."""
 import glob
 import os
 import subprocess
@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-UNITS = ['f110_handle', 'f110_maps', 'f110_noise_abi', 'f110_step', 'f110_consumers']
+UNITS = ['f110_handle', 'f110_maps', 'f110_noise_abi', 'f110_step', 'f110_consumers', 'f110_policy_abi', 'f110_bitmap_abi']
 HEADERS = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + [os.path.join(os.path.dirname(HERE), 'include', 'f110_hip.h')]
 LIB = os.path.join(HERE, 'libf110_hip.so')
 OBJ_DIR = os.path.join(HERE, 'build')
@@ -41,7 +41,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, obj_dir=OBJ_DIR):
         if verbose:
             print(' '.join(cmd))
         subprocess.run(cmd, check=True)
-    with ThreadPoolExecutor(max_workers=min(5, os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(UNITS), 16)) as ex:
         list(ex.map(run, jobs))
     run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib] + [os.path.join(obj_dir, u + '.o') for u in UNITS])
     return lib

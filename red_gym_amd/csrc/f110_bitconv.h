@@ -11,6 +11,8 @@
 //   bitconv_reduce_kernel    stage 2: the G partials of every element summed in a fixed order, times `on`
 // Forward numerics (the contract of include/f110_hip.h): acc = 0; taps ky major, kx minor: acc = fma(w, bit, acc) with bit 0.0 or
 // 1.0 -- w * bit is exact, so this is acc + w for a set tap and acc for a clear one, rounded once per tap; out = (acc * on) + bias.
+// Includes f110_replay.h for the frame format it reads: replay_bits16 (16 pixels -> 16 bits) here, replay_words and REPLAY_MAX_DIM
+// in the host checks of f110_policy_abi.hip.
 #pragma once
 #include "f110_replay.h"
 
@@ -112,7 +114,7 @@ __device__ inline uint64_t bitconv_mask(const uint64_t *lds, const BitconvTile &
     return m;
 }
 
-#if defined(F110_UNIT_CONSUMERS)
+#if defined(F110_UNIT_POLICY)
 // grid: (images of this launch) * tiles_y * tiles_x; weight [C, K, K], bias [C] or NULL, out [n, C, OH, OW]
 template <int K, bool U8>
 static __global__ __launch_bounds__(BC_THREADS) void bitconv_forward_kernel(BitconvArgs a, const float *__restrict__ weight, const float *__restrict__ bias,

@@ -362,7 +362,7 @@ __device__ inline int2 bm_point(const BitmapArgs &a, int img, int k, int cx, int
 }
 
 // function-level view of the point stage (f110_bitmap_points): out [n, T, 2] int32 (x, y)
-#if defined(F110_UNIT_CONSUMERS)
+#if defined(F110_UNIT_BITMAP)
 static __global__ __launch_bounds__(256) void bitmap_points_kernel(BitmapArgs a, int *out)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -374,7 +374,7 @@ static __global__ __launch_bounds__(256) void bitmap_points_kernel(BitmapArgs a,
 }
 #endif
 
-#if defined(F110_UNIT_CONSUMERS)
+#if defined(F110_UNIT_BITMAP)
 // The image workgroup g draws in round `it` of a launch of `grid` workgroups; a value >= n: none (and none in later rounds).
 // (Rotating the rounds' slots, so that a workgroup sees every kind of image, changes nothing: the spread of the workgroups'
 // lives -- 620 to 980 us in one launch -- follows their dispatch order, not their images; profiles/r05_bitmap.txt.)
@@ -805,7 +805,7 @@ struct OccArgs {
     unsigned char *out;        // [n, grid, grid]
 };
 
-#if defined(F110_UNIT_CONSUMERS)
+#if defined(F110_UNIT_BITMAP)
 static __global__ __launch_bounds__(BM_THREADS) void occupancy_kernel(OccArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];

@@ -5,8 +5,10 @@
 //   f110_maps.hip       map installation (host table / occupancy mask -> cell codes, LUTs), device EDT, track mask
 //   f110_noise_abi.hip  lidar noise: slots, ring, generators, per-env mode
 //   f110_step.hip       launch policy of the scan, the step, hipGraphs, measurement aid, function-level entry points
-//   f110_consumers.hip  the callers either side of the step: pure-pursuit planner, progress tracker, reward shaper, path follower, replay buffer, bit convolution, policy stem, policy head, scan -> bitmap,
-//                       occupancy grid
+//   f110_consumers.hip  the callers either side of the step, on the handle: pure-pursuit planner, progress tracker, reward shaper,
+//                       path follower, replay buffer
+//   f110_policy_abi.hip the policy, stateless: bit convolution, policy stem, policy head
+//   f110_bitmap_abi.hip the scan's consumers with no handle: scan -> bitmap (its own f110_bitmap object), occupancy grid
 #pragma once
 #include "../../include/f110_hip.h"
 #include "f110_scan_plan.h"

@@ -37,7 +37,13 @@ constexpr uint32_t DEVERR_NOISE_WINDOW = 1u, DEVERR_BOUNDS = 2u;
 // device error word (f110_device_errors) and the access is redirected to a valid element, so the run goes on and the
 // report names the table.  The whole -m gpu suite is run against this build once per round (profiles/r04_bounds_build.txt).
 enum { BT_LUT_CODE, BT_CELLS_FAR, BT_LUT_RANK, BT_DT, BT_NOISE_BEAM, BT_CS_TABLE, BT_CHUNK_ORDER, BT_MAP_SLOT, BT_NOISE_SLOT,
-       BT_PARAMS_SLOT, BT_SCAN_STORE, BT_OPP_BEAM, BT_STAGE_LIST, BT_SELFTEST, BT_SIDE_SLOT };
+       BT_PARAMS_SLOT, BT_SCAN_STORE, BT_OPP_BEAM, BT_STAGE_LIST, BT_SELFTEST, BT_SIDE_SLOT,
+       // the step's consumers (every header here includes this one and takes its tag from this list: a new family appends)
+       BT_PROGRESS,   // an index of the tracker (raceline slot, grid cell, candidate, segment)
+       BT_SHAPING,    // a pixel index of the shaper (px, py, car_x, car_y, a neighbour)
+       BT_PATHFOLLOW, // an index of the follower (waypoint index, free set, spline piece)
+       BT_REPLAY };   // a slot the replay kernels derive from `count`, a drawn index
+static_assert(BT_PROGRESS == 15 && BT_REPLAY == 18, "the tags are bits of the device error word (8 + BT_*): the ABI fixes their values");
 #if defined(F110_BOUNDS)
 #define F110_BCHK(ok, table, errp) \
     do { if (!(ok)) { uint32_t *e_ = (errp); if (e_) atomicOr(e_, DEVERR_BOUNDS | (1u << (8 + (table)))); } } while (0)

@@ -19,13 +19,11 @@
 // DEVERR_QP_LIMIT, and no other env changes by a bit -- the lane exchanges never leave the env's own pair of lanes.
 #pragma once
 #include "f110_kernels.h"
-#include "f110_shaping.h"
 
 #pragma clang fp contract(off)
 
 namespace f110 {
 
-constexpr int BT_PATHFOLLOW = BT_SHAPING + 1; // bounds-checked build: an index of the follower (waypoint index, free set, spline piece)
 constexpr uint32_t DEVERR_QP_LIMIT = 4u;
 constexpr int PF_POINTS = 8;                  // points of a path = rows of the raw action
 constexpr int PF_MAX_H = 8;                   // longest horizon (variables of one QP)

@@ -1,0 +1,319 @@
+// f110_policy_abi.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_internal.h for the units.
+#define F110_UNIT_POLICY
+#include "f110_internal.h"
+
+// ---------------------------------------------------------------- first convolution from bits
+// What the entry points refuse, on the struct alone (no device).
+extern "C" int f110_bitconv_validate(const f110_bitconv_config *cfg)
+{
+    const char *who = "f110_bitconv_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    if (cfg->kernel < 1 || cfg->kernel > BC_MAX_K) return fail(F110_E_INVALID, "%s: kernel %d (1..%d: a window is one 64-bit mask)", who, cfg->kernel, BC_MAX_K);
+    if (cfg->stride < 1 || cfg->stride > cfg->kernel) return fail(F110_E_INVALID, "%s: stride %d (1..kernel = %d)", who, cfg->stride, cfg->kernel);
+    if (cfg->channels < 1 || cfg->channels > 64) return fail(F110_E_INVALID, "%s: %d channels (1..64)", who, cfg->channels);
+    if (cfg->rows < cfg->kernel || cfg->cols < cfg->kernel || cfg->rows > REPLAY_MAX_DIM || cfg->cols > REPLAY_MAX_DIM)
+        return fail(F110_E_INVALID, "%s: image of %d x %d pixels (kernel = %d .. %d)", who, cfg->rows, cfg->cols, cfg->kernel, REPLAY_MAX_DIM);
+    if (!std::isfinite(cfg->on)) return fail(F110_E_INVALID, "%s: `on` is not finite", who);
+    return F110_OK;
+}
+
+// the launch geometry of a validated configuration
+static void bitconv_geometry(const f110_bitconv_config &c, BitconvArgs &a)
+{
+    a.cfg = c;
+    a.OH = (c.rows - c.kernel) / c.stride + 1; a.OW = (c.cols - c.kernel) / c.stride + 1;
+    a.W = replay_words(c.cols);
+    a.tiles_x = (a.OW + BC_TX - 1) / BC_TX; a.tiles_y = (a.OH + BC_TY - 1) / BC_TY;
+}
+
+static int bitconv_partials(const BitconvArgs &a, int64_t n)
+{
+    const int64_t tiles = n * a.tiles_x * a.tiles_y;
+    return (int)std::min<int64_t>(tiles, BC_MAX_PARTIALS);
+}
+
+extern "C" int64_t f110_bitconv_workspace(const f110_bitconv_config *cfg, int64_t n)
+{
+    if (n < 1 || f110_bitconv_validate(cfg) != F110_OK) return 0;
+    BitconvArgs a;
+    bitconv_geometry(*cfg, a);
+    return (int64_t)bitconv_partials(a, n) * cfg->channels * (cfg->kernel * cfg->kernel + 1) * (int64_t)sizeof(float);
+}
+
+#define BITCONV_BY_KERNEL(K, LAUNCH) \
+    switch (K) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; case 4: LAUNCH(4); break; \
+                 case 5: LAUNCH(5); break; case 6: LAUNCH(6); break; case 7: LAUNCH(7); break; default: LAUNCH(8); break; }
+
+static int bitconv_forward(const char *who, const f110_bitconv_config *cfg, const void *src, bool u8, int64_t n_frames, const int64_t *index,
+                           int64_t n, const float *weight, const float *bias, float *out, hipStream_t stream)
+{
+    if (int rc = f110_bitconv_validate(cfg)) return rc;
+    if (n < 0 || n_frames < 0) return fail(F110_E_INVALID, "%s: n=%lld samples of %lld frames", who, (long long)n, (long long)n_frames);
+    if (n == 0) return F110_OK;
+    if (!weight || !out || (n_frames > 0 && !src)) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (!index && n > n_frames) return fail(F110_E_INVALID, "%s: %lld samples of %lld frames without an index", who, (long long)n, (long long)n_frames);
+    if (!u8 && (uintptr_t)src % 8) return fail(F110_E_INVALID, "%s: frames must be 8-byte aligned", who);
+    BitconvArgs a;
+    memset(&a, 0, sizeof(a));
+    bitconv_geometry(*cfg, a);
+    if (u8) a.images = (const uint8_t *)src; else a.frames = (const uint64_t *)src;
+    a.n_frames = n_frames; a.index = (const long long *)index; a.n = n;
+    // a launch has fewer than 2^32 threads: images go in groups of at most 2^23 workgroups
+    const int64_t per = (int64_t)a.tiles_x * a.tiles_y, group = std::max<int64_t>(1, ((int64_t)1 << 23) / per);
+    for (int64_t first = 0; first < n; first += group) {
+        a.first = first;
+        const unsigned grid = (unsigned)(std::min(group, n - first) * per);
+#define BITCONV_FWD(K) do { if (u8) hipLaunchKernelGGL((bitconv_forward_kernel<K, true>), dim3(grid), dim3(BC_THREADS), 0, stream, a, weight, bias, out); \
+                            else hipLaunchKernelGGL((bitconv_forward_kernel<K, false>), dim3(grid), dim3(BC_THREADS), 0, stream, a, weight, bias, out); } while (0)
+        BITCONV_BY_KERNEL(cfg->kernel, BITCONV_FWD)
+#undef BITCONV_FWD
+        HIP_TRY(hipGetLastError());
+    }
+    return F110_OK;
+}
+
+extern "C" int f110_bitconv_forward(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
+                                    const float *weight, const float *bias, float *out, void *stream)
+{
+    return bitconv_forward("f110_bitconv_forward", cfg, frames, false, n_frames, index, n, weight, bias, out, (hipStream_t)stream);
+}
+
+extern "C" int f110_bitconv_forward_u8(const f110_bitconv_config *cfg, const uint8_t *images, int64_t n_frames, const int64_t *index, int64_t n,
+                                       const float *weight, const float *bias, float *out, void *stream)
+{
+    return bitconv_forward("f110_bitconv_forward_u8", cfg, images, true, n_frames, index, n, weight, bias, out, (hipStream_t)stream);
+}
+
+extern "C" int f110_bitconv_backward(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
+                                     const float *grad_out, float *grad_weight, float *grad_bias, float *workspace, void *stream)
+{
+    const char *who = "f110_bitconv_backward";
+    if (int rc = f110_bitconv_validate(cfg)) return rc;
+    if (n < 1 || n_frames < 0) return fail(F110_E_INVALID, "%s: n=%lld samples of %lld frames", who, (long long)n, (long long)n_frames);
+    if (!grad_out || !grad_weight || !workspace || (n_frames > 0 && !frames)) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (!index && n > n_frames) return fail(F110_E_INVALID, "%s: %lld samples of %lld frames without an index", who, (long long)n, (long long)n_frames);
+    if ((uintptr_t)frames % 8 || (uintptr_t)workspace % 16) return fail(F110_E_INVALID, "%s: frames must be 8-byte and the workspace 16-byte aligned", who);
+    BitconvArgs a;
+    memset(&a, 0, sizeof(a));
+    bitconv_geometry(*cfg, a);
+    a.frames = frames; a.n_frames = n_frames; a.index = (const long long *)index; a.n = n; a.grad_out = grad_out; a.ws = workspace;
+    a.G = bitconv_partials(a, n);
+    const dim3 grid((unsigned)a.G, (unsigned)((cfg->channels + BC_CHUNK - 1) / BC_CHUNK));
+#define BITCONV_BWD(K) hipLaunchKernelGGL((bitconv_backward_kernel<K>), grid, dim3(BC_THREADS), 0, (hipStream_t)stream, a)
+    BITCONV_BY_KERNEL(cfg->kernel, BITCONV_BWD)
+#undef BITCONV_BWD
+    HIP_TRY(hipGetLastError());
+    const int nw = cfg->channels * cfg->kernel * cfg->kernel;
+    hipLaunchKernelGGL(bitconv_reduce_kernel, dim3((unsigned)((nw + cfg->channels + BC_THREADS - 1) / BC_THREADS)), dim3(BC_THREADS), 0, (hipStream_t)stream,
+                       (const float *)workspace, a.G, nw, cfg->channels, cfg->on, grad_weight, grad_bias);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+// ---------------------------------------------------------------- policy stem: conv1 + relu + conv2 from bits
+static f110_bitconv_config bitconv2_layer1_config(const f110_bitconv2_config &c)
+{
+    f110_bitconv_config l1;
+    l1.rows = c.rows; l1.cols = c.cols; l1.kernel = c.kernel; l1.stride = c.stride; l1.channels = c.channels; l1.relu = c.relu; l1.on = c.on;
+    return l1;
+}
+
+extern "C" int f110_bitconv2_validate(const f110_bitconv2_config *cfg)
+{
+    const char *who = "f110_bitconv2_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    const f110_bitconv_config l1 = bitconv2_layer1_config(*cfg);
+    if (int rc = f110_bitconv_validate(&l1)) return rc;
+    if (cfg->channels > BC2_MAX_C1) return fail(F110_E_INVALID, "%s: %d channels in the first layer (1..%d)", who, cfg->channels, BC2_MAX_C1);
+    if (cfg->kernel2 < 1 || cfg->kernel2 > BC2_MAX_K2) return fail(F110_E_INVALID, "%s: kernel2 %d (1..%d)", who, cfg->kernel2, BC2_MAX_K2);
+    if (cfg->stride2 < 1 || cfg->stride2 > cfg->kernel2) return fail(F110_E_INVALID, "%s: stride2 %d (1..kernel2 = %d)", who, cfg->stride2, cfg->kernel2);
+    if (cfg->channels2 < 1 || cfg->channels2 > BC2_MAX_C2) return fail(F110_E_INVALID, "%s: %d channels in the second layer (1..%d)", who, cfg->channels2, BC2_MAX_C2);
+    const int oh1 = (cfg->rows - cfg->kernel) / cfg->stride + 1, ow1 = (cfg->cols - cfg->kernel) / cfg->stride + 1;
+    if (ow1 > BC2_MAX_OW1) return fail(F110_E_INVALID, "%s: the first layer's output is %d wide (at most %d: a band is whole rows)", who, ow1, BC2_MAX_OW1);
+    if (oh1 < cfg->kernel2 || ow1 < cfg->kernel2)
+        return fail(F110_E_INVALID, "%s: the first layer's output of %d x %d is smaller than kernel2 = %d", who, oh1, ow1, cfg->kernel2);
+    return F110_OK;
+}
+
+// LDS bytes of a workgroup whose bands have `br` output rows; the offsets of koff and a1 in it
+static size_t bitconv2_lds(const f110_bitconv2_config &c, int br, int xw, int ksteps, int *koff_off, int *a1_off)
+{
+    const int nr1 = (br - 1) * c.stride2 + c.kernel2, img_rows = (nr1 - 1) * c.stride + c.kernel;
+    const size_t words = (size_t)img_rows * BC_LWORDS * sizeof(uint64_t), koff = (size_t)BC2_KSTEPS * 4 * sizeof(int);
+    if (koff_off) *koff_off = (int)words;
+    if (a1_off) *a1_off = (int)(words + koff);
+    return words + koff + (size_t)c.channels * nr1 * xw * sizeof(float);
+}
+
+// the launch geometry of a validated configuration (restated by tests/bitconv2_cases.py paths2)
+static size_t bitconv2_geometry(const f110_bitconv2_config &c, Bitconv2Args &a)
+{
+    memset(&a, 0, sizeof(a));
+    bitconv_geometry(bitconv2_layer1_config(c), a.l1);
+    a.k2 = c.kernel2; a.s2 = c.stride2; a.C2 = c.channels2; a.relu2 = c.relu2;
+    a.OH2 = (a.l1.OH - a.k2) / a.s2 + 1; a.OW2 = (a.l1.OW - a.k2) / a.s2 + 1;
+    a.XW = (a.OW2 - 1) * a.s2 + a.k2;
+    a.ktot = c.channels * a.k2 * a.k2; a.ksteps = (a.ktot + 3) / 4;
+    a.BR = 1;
+    while (a.BR < a.OH2 && bitconv2_lds(c, a.BR + 1, a.XW, a.ksteps, nullptr, nullptr) <= (size_t)BC2_LDS_BYTES) a.BR++;
+    a.bands = (a.OH2 + a.BR - 1) / a.BR;
+    a.NR1 = (a.BR - 1) * a.s2 + a.k2;
+    return bitconv2_lds(c, a.BR, a.XW, a.ksteps, &a.koff_off, &a.a1_off);
+}
+
+static int bitconv2_forward(const char *who, const f110_bitconv2_config *cfg, const void *src, bool u8, int64_t n_frames, const int64_t *index,
+                            int64_t n, const float *w1, const float *b1, const float *w2, const float *b2, float *out, hipStream_t stream)
+{
+    if (int rc = f110_bitconv2_validate(cfg)) return rc;
+    if (n < 0 || n_frames < 0) return fail(F110_E_INVALID, "%s: n=%lld samples of %lld frames", who, (long long)n, (long long)n_frames);
+    if (n == 0) return F110_OK;
+    if (!w1 || !w2 || !out || !src) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (!index && n > n_frames) return fail(F110_E_INVALID, "%s: %lld samples of %lld frames without an index", who, (long long)n, (long long)n_frames);
+    if (!u8 && (uintptr_t)src % 8) return fail(F110_E_INVALID, "%s: frames must be 8-byte aligned", who);
+    Bitconv2Args a;
+    const size_t lds = bitconv2_geometry(*cfg, a);
+    if (u8) a.l1.images = (const uint8_t *)src; else a.l1.frames = (const uint64_t *)src;
+    a.u8 = u8 ? 1 : 0;
+    a.l1.n_frames = n_frames; a.l1.index = (const long long *)index; a.l1.n = n;
+    a.items = (long long)n * a.bands;
+    // (a workgroup walks items grid apart, so one launch serves any n; its LDS stays below the 64 KiB every kernel may ask for)
+    const unsigned grid = (unsigned)std::min<long long>(a.items, BC2_MAX_GRID);
+    hipLaunchKernelGGL(bitconv2_forward_kernel, dim3(grid), dim3(BC_THREADS), lds, stream, a, w1, b1, w2, b2, out);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_bitconv2_forward(const f110_bitconv2_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
+                                     const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream)
+{
+    return bitconv2_forward("f110_bitconv2_forward", cfg, frames, false, n_frames, index, n, w1, b1, w2, b2, out, (hipStream_t)stream);
+}
+
+extern "C" int f110_bitconv2_forward_u8(const f110_bitconv2_config *cfg, const uint8_t *images, int64_t n_frames, const int64_t *index, int64_t n,
+                                        const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream)
+{
+    return bitconv2_forward("f110_bitconv2_forward_u8", cfg, images, true, n_frames, index, n, w1, b1, w2, b2, out, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------- policy head: fc_mean, fc_log_std and the sampling tail
+extern "C" int f110_policyhead_validate(const f110_policyhead_config *cfg)
+{
+    const char *who = "f110_policyhead_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    if (cfg->in_features < 1 || cfg->in_features > PH_MAX_K) return fail(F110_E_INVALID, "%s: in_features %d (1..%d)", who, cfg->in_features, PH_MAX_K);
+    if (cfg->action_dim < 1 || cfg->action_dim > PH_MAX_A) return fail(F110_E_INVALID, "%s: action_dim %d (1..%d)", who, cfg->action_dim, PH_MAX_A);
+    return F110_OK;
+}
+
+// the launch geometry of a validated configuration (restated by tests/policyhead_cases.py paths)
+static void policyhead_geometry(const f110_policyhead_config &c, int64_t n, PolicyheadArgs &a)
+{
+    memset(&a, 0, sizeof(a));
+    a.K = c.in_features; a.A = c.action_dim; a.T = (a.A + 15) / 16; a.out_fp64 = c.out_fp64 ? 1 : 0;
+    a.kc = std::min(PH_LDS_BYTES / (128 * a.T), (a.K + 63) / 64 * 64);
+    a.chunks = (a.K + a.kc - 1) / a.kc;
+    a.n = n; a.tiles = (n + PH_ROWS - 1) / PH_ROWS;
+    a.slices = (int)((n + PH_SLICE - 1) / PH_SLICE);
+}
+
+// floats of g_pre in the workspace: [n, 2A], rounded up so that the partial sums behind it start 16-byte aligned
+static int64_t policyhead_gpre_floats(const f110_policyhead_config &c, int64_t n) { return (n * 2 * c.action_dim + 3) / 4 * 4; }
+
+extern "C" int64_t f110_policyhead_workspace(const f110_policyhead_config *cfg, int64_t n)
+{
+    if (n < 1 || n > PH_MAX_ROWS || f110_policyhead_validate(cfg) != F110_OK) return 0;
+    const int64_t slices = (n + PH_SLICE - 1) / PH_SLICE;
+    return (policyhead_gpre_floats(*cfg, n) + slices * 2 * cfg->action_dim * (cfg->in_features + 1)) * (int64_t)sizeof(float);
+}
+
+// The stateless entry points launch on the calling thread's current device: every required pointer must be memory of that device
+// and a stream given must belong to it.  A mismatch is refused here, before any launch (host-side queries only, no synchronisation).
+struct PolicyheadPtr { const char *name; const void *p; };
+static int policyhead_check_device(const char *who, hipStream_t stream, std::initializer_list<PolicyheadPtr> ptrs)
+{
+    int cur = -1;
+    HIP_TRY(hipGetDevice(&cur));
+    if (stream) {
+        hipDevice_t sdev = -1;
+        if (hipStreamGetDevice(stream, &sdev) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(F110_E_INVALID, "%s: `stream` is not a stream of this process", who);
+        }
+        if ((int)sdev != cur) return fail(F110_E_INVALID, "%s: `stream` belongs to device %d but the calling thread's current device is %d", who, (int)sdev, cur);
+    }
+    for (const PolicyheadPtr &q : ptrs) {
+        hipPointerAttribute_t at;
+        memset(&at, 0, sizeof(at));
+        const hipError_t e = hipPointerGetAttributes(&at, q.p);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged))
+            return fail(F110_E_INVALID, "%s: `%s` is not device memory", who, q.name);
+        if (at.device != cur) return fail(F110_E_INVALID, "%s: `%s` lives on device %d but the calling thread's current device is %d", who, q.name, at.device, cur);
+    }
+    return F110_OK;
+}
+
+extern "C" int f110_policyhead_forward(const f110_policyhead_config *cfg, const float *h, int64_t n, const float *w_mean, const float *b_mean,
+                                       const float *w_log_std, const float *b_log_std, const float *eps, float *pre, void *action, void *log_prob,
+                                       void *stream)
+{
+    const char *who = "f110_policyhead_forward";
+    if (int rc = f110_policyhead_validate(cfg)) return rc;
+    if (n < 0 || n > PH_MAX_ROWS) return fail(F110_E_INVALID, "%s: n=%lld rows (0..%lld)", who, (long long)n, (long long)PH_MAX_ROWS);
+    if (n == 0) return F110_OK;
+    if (!h || !w_mean || !w_log_std || !pre || !action) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if ((eps == nullptr) != (log_prob == nullptr)) return fail(F110_E_INVALID, "%s: log_prob must be NULL exactly when eps is NULL", who);
+    if (int rc = policyhead_check_device(who, (hipStream_t)stream, {{"h", h}, {"w_mean", w_mean}, {"w_log_std", w_log_std}, {"pre", pre}, {"action", action}})) return rc;
+    PolicyheadArgs a;
+    policyhead_geometry(*cfg, n, a);
+    a.h = h; a.w_mean = w_mean; a.b_mean = b_mean; a.w_log_std = w_log_std; a.b_log_std = b_log_std; a.eps = eps;
+    a.pre = pre; a.action = action; a.log_prob = log_prob;
+    // (a workgroup walks tiles grid apart, so one launch serves any n; its LDS stays within the 64 KiB every kernel may ask for)
+    const unsigned grid = (unsigned)std::min<long long>(a.tiles, PH_MAX_GRID);
+    const size_t lds = (size_t)128 * a.T * a.kc;
+#define POLICYHEAD_FWD(T, F64) hipLaunchKernelGGL((policyhead_forward_kernel<T, F64>), dim3(grid), dim3(PH_THREADS), lds, (hipStream_t)stream, a)
+    if (a.T == 1) { if (a.out_fp64) POLICYHEAD_FWD(1, true); else POLICYHEAD_FWD(1, false); }
+    else { if (a.out_fp64) POLICYHEAD_FWD(2, true); else POLICYHEAD_FWD(2, false); }
+#undef POLICYHEAD_FWD
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_policyhead_backward(const f110_policyhead_config *cfg, const float *h, int64_t n, const float *w_mean, const float *w_log_std,
+                                        const float *pre, const float *eps, const void *grad_action, const void *grad_log_prob, const float *grad_pre,
+                                        float *grad_h, float *grad_w_mean, float *grad_b_mean, float *grad_w_log_std, float *grad_b_log_std, float *workspace,
+                                        void *stream)
+{
+    const char *who = "f110_policyhead_backward";
+    if (int rc = f110_policyhead_validate(cfg)) return rc;
+    if (n < 0 || n > PH_MAX_ROWS) return fail(F110_E_INVALID, "%s: n=%lld rows (0..%lld)", who, (long long)n, (long long)PH_MAX_ROWS);
+    if (n == 0) return F110_OK;
+    if (!h || !w_mean || !w_log_std || !pre || !grad_action || !workspace) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (!eps && grad_log_prob) return fail(F110_E_INVALID, "%s: grad_log_prob without eps (no log_prob was produced)", who);
+    if ((uintptr_t)workspace % 16) return fail(F110_E_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    if (int rc = policyhead_check_device(who, (hipStream_t)stream, {{"h", h}, {"w_mean", w_mean}, {"w_log_std", w_log_std}, {"pre", pre},
+                                                                    {"grad_action", grad_action}, {"workspace", workspace}})) return rc;
+    PolicyheadArgs a;
+    policyhead_geometry(*cfg, n, a);
+    a.h = h; a.w_mean = w_mean; a.w_log_std = w_log_std; a.eps = eps; a.pre = const_cast<float *>(pre);
+    a.grad_action = grad_action; a.grad_log_prob = grad_log_prob; a.grad_pre = grad_pre;
+    a.gpre = workspace; a.partial = workspace + policyhead_gpre_floats(*cfg, n);
+    a.grad_h = grad_h; a.grad_w_mean = grad_w_mean; a.grad_b_mean = grad_b_mean; a.grad_w_log_std = grad_w_log_std; a.grad_b_log_std = grad_b_log_std;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((n * a.A + PH_THREADS - 1) / PH_THREADS);
+    if (a.out_fp64) hipLaunchKernelGGL(policyhead_gpre_kernel<true>, dim3(blocks), dim3(PH_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(policyhead_gpre_kernel<false>, dim3(blocks), dim3(PH_THREADS), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    if (grad_h) {
+        hipLaunchKernelGGL(policyhead_gradh_kernel, dim3((unsigned)((n + PH_GH_ROWS - 1) / PH_GH_ROWS), (unsigned)((a.K + PH_THREADS - 1) / PH_THREADS)),
+                           dim3(PH_THREADS), 0, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (grad_w_mean || grad_b_mean || grad_w_log_std || grad_b_log_std) {
+        hipLaunchKernelGGL(policyhead_gradw_kernel, dim3((unsigned)a.slices, (unsigned)((a.K + 63) / 64 + 1)), dim3(64), 0, s, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(policyhead_reduce_kernel, dim3((unsigned)((2 * a.A * (a.K + 1) + PH_THREADS - 1) / PH_THREADS)), dim3(PH_THREADS), 0, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return F110_OK;
+}

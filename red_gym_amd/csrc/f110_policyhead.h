@@ -18,8 +18,10 @@
 // XORed with 4 (row & 15), which spreads the 16 rows a read touches over all banks.  Columns past K are zeros: fma(0, 0, acc).
 // Numerics (the contract of include/f110_hip.h): the MFMA is a k-ordered fmaf chain through C.
 #pragma once
-#include "f110_replay.h"
+#include "../../include/f110_hip.h" // F110_POLICYHEAD_SLICE_ROWS
 
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 #include <type_traits>
 
 namespace f110 {
@@ -102,7 +104,7 @@ __device__ inline void policyhead_stage(const PolicyheadArgs &a, float *lw, int 
     }
 }
 
-#if defined(F110_UNIT_CONSUMERS)
+#if defined(F110_UNIT_POLICY)
 // grid: min(tiles, PH_MAX_GRID); dynamic LDS of 128 T kc bytes
 template <int T, bool F64>
 static __global__ __launch_bounds__(PH_THREADS) void policyhead_forward_kernel(PolicyheadArgs a)

@@ -11,8 +11,6 @@
 
 namespace f110 {
 
-constexpr int BT_PROGRESS = BT_SIDE_SLOT + 1; // bounds-checked build: an index of the tracker (raceline slot, grid cell, candidate, segment)
-
 struct ProgressArgs {
     const double *state;            // [n,7]: x, y, yaw = columns 0, 1, 4
     int n, agents;

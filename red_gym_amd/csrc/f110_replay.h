@@ -12,11 +12,9 @@
 //   replay_locate_kernel   one lane per index: where the gather would read, for consumers that read the bits themselves (f110_bitconv.h)
 #pragma once
 #include "f110_kernels.h"
-#include "f110_pathfollow.h"
 
 namespace f110 {
 
-constexpr int BT_REPLAY = BT_PATHFOLLOW + 1; // bounds-checked build: a slot the replay kernels derive from `count`, a drawn index
 constexpr int REPLAY_THREADS = 256;
 constexpr int REPLAY_ROWS = 16;              // rows of a frame one workgroup of the gather unpacks (4 per wave)
 constexpr int REPLAY_MAX_DIM = 16384;        // rows, cols: the kernels count a frame's 16-pixel chunks in 32 bits

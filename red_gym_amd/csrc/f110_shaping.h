@@ -8,14 +8,12 @@
 // fp64, plain mul/add in the order DESIGN.md section 3 fixes; the tests demand `==` of a NumPy checker for every output.
 #pragma once
 #include "f110_kernels.h"
-#include "f110_progress.h"
 
 #pragma clang fp contract(off)
 
 namespace f110 {
 
-constexpr int BT_SHAPING = BT_PROGRESS + 1; // bounds-checked build: a pixel index of the shaper (px, py, car_x, car_y, a neighbour)
-constexpr int SHAPING_WAVES = 4;            // envs (= waves) per workgroup
+constexpr int SHAPING_WAVES = 4; // envs (= waves) per workgroup
 
 struct ShapingArgs {
     f110_shaping_config cfg;

@@ -16,8 +16,7 @@ LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
 def make_config(in_features, action_dim, out_fp64=True):
     """An f110_policyhead_config; out-of-range integers are clamped into int32 so that validate() can name them."""
     c = _lib.PolicyheadConfig()
-    clamp = lambda v: max(min(int(v), 2 ** 31 - 1), -2 ** 31)  # noqa: E731
-    c.in_features, c.action_dim, c.out_fp64 = clamp(in_features), clamp(action_dim), 1 if out_fp64 else 0
+    c.in_features, c.action_dim, c.out_fp64 = _lib.clamp(in_features), _lib.clamp(action_dim), 1 if out_fp64 else 0
     return c
 
 
@@ -34,12 +33,7 @@ def workspace_bytes(in_features, action_dim, n):
     return int(_lib.load().f110_policyhead_workspace(C.byref(c), int(n)))
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+_ptr = _lib.ptr
 
 
 class _SampleActions(torch.autograd.Function):
@@ -55,7 +49,7 @@ class _SampleActions(torch.autograd.Function):
         log_prob = None if eps is None else torch.empty((n,), dtype=dt, device=dev)
         with torch.cuda.device(dev):
             _lib.check(lib.f110_policyhead_forward(C.byref(cfg), tensors[0].data_ptr(), n, *[_ptr(t) for t in tensors[1:]], pre.data_ptr(),
-                                                   action.data_ptr(), _ptr(log_prob), _stream(dev)))
+                                                   action.data_ptr(), _ptr(log_prob), _lib.stream(dev)))
         ctx.cfg, ctx.n, ctx.has_bias = cfg, n, (b_mean is not None, b_log_std is not None)
         ctx.save_for_backward(tensors[0], tensors[1], tensors[3], tensors[5], pre)
         ctx.set_materialize_grads(False)
@@ -93,7 +87,7 @@ class _SampleActions(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check(lib.f110_policyhead_backward(C.byref(cfg), h.data_ptr(), n, w_mean.data_ptr(), w_log_std.data_ptr(), pre.data_ptr(), _ptr(eps),
                                                     ga.data_ptr(), _ptr(glp), _ptr(gp), _ptr(gh), _ptr(gwm), _ptr(gbm), _ptr(gwl), _ptr(gbl), ws.data_ptr(),
-                                                    _stream(dev)))
+                                                    _lib.stream(dev)))
         return gh, gwm, gbm, gwl, gbl, None, None, None
 
 

@@ -81,7 +81,7 @@ def test_shape_tables_reach_every_path():
     k = _header_constants()
     assert [k[n] for n in ('BC_TX', 'BC_TY', 'BC_MAX_K', 'BC_LROWS', 'BC_LWORDS', 'BC_CHUNK', 'BC_MAX_PARTIALS')] == \
         [bc.BC_TX, bc.BC_TY, bc.BC_MAX_K, bc.BC_LROWS, bc.BC_LWORDS, bc.BC_CHUNK, bc.BC_MAX_PARTIALS]
-    src = open(os.path.join(ROOT, 'red_gym_amd', 'csrc', 'f110_consumers.hip')).read()
+    src = open(os.path.join(ROOT, 'red_gym_amd', 'csrc', 'f110_policy_abi.hip')).read()
     assert re.search(r'\(int64_t\)\s*1\s*<<\s*23\)\s*/\s*per\b', src) and bc.FORWARD_GROUP == 1 << 23
     # the validated range by brute force: every kernel, every stride, every count of outputs of a row of up to three tiles
     widest = offs = 0
