@@ -58,7 +58,7 @@ print('learning: frames %s %s (a view of the ring), %d of %d draws valid -> feat
 f2 = stem(frames, index=s_idx)                                                     # grad on: conv_bits -> F.conv2d -> relu, differentiable
 f2.mean().backward()
 new_a, logp, mean, log_std = head.sample(features(frames, index=s_idx))             # one sample with gradients, as update() takes (:564)
-(0.2 * logp - new_a.sum(dim=1)).mean().backward()                                 # (the critics are not part of this example)
+(0.2 * logp - new_a.sum(dim=1)).mean().backward()                                 # (the critics: examples/sac_update.py)
 print('head: actions %s %s, log_prob %s, grad fc_mean.weight %s, grad fc1.weight %s'
       % (tuple(new_a.shape), new_a.dtype, tuple(logp.shape), tuple(head.fc_mean.weight.grad.shape), tuple(fc1.weight.grad.shape)))
 print('stem: acting features %s (no grad_fn: %s), learning features %s, grad conv2.weight %s' % (tuple(feats.shape), feats.grad_fn is None, tuple(f2.shape), tuple(conv2.weight.grad.shape)))

@@ -720,6 +720,61 @@ int f110_policyhead_backward(const f110_policyhead_config *cfg, const float *h, 
                              float *grad_h, float *grad_w_mean, float *grad_b_mean, float *grad_w_log_std, float *grad_b_log_std, float *workspace,
                              void *stream);
 
+/* Critic head: what the reference's twin critics do behind the feature part of fc1 (src/SAL.py:440-442 and :546-549) -- the action
+ * columns of fc1, its bias, ReLU, fc2, the min over the two critics and the TD target -- forward in one kernel, and a backward without
+ * atomics, for C = 1 or 2 critics at once.  fc1(cat([f, a])) = f @ W[:, :F].T + a @ W[:, F:].T + b: the first term is the caller's
+ * GEMM and arrives as `pre`; the concatenated input never exists.  Stateless (no handle; cfg and the two pointer structs host; all
+ * arrays dev); launches on `stream` of the calling thread's current device, no allocation, no synchronisation.
+ * Per critic c < C (f110_qhead_critics): pre[c] [n, H] fp32, the feature part of fc1 without bias; w_act[c] the action columns of
+ * fc1.weight, [H, A] fp32 with a row stride of cfg->ld elements (a view into the [H, F + A] weight with ld = F + A; no alignment
+ * of its rows is assumed); b1[c] [H] or NULL; w2[c] [H]; b2[c] [1] or NULL.  Shared: action [n, A], double when action_fp64 is
+ * nonzero, else float; a double is rounded to fp32 once on load.
+ * Outputs: q [C, n] fp32, required; qmin [n] fp32 or NULL; target [n] fp32 or NULL.  A target needs reward [n] fp64, done [n] uint8
+ * and next_log_prob [n] of the action's width, and gamma and alpha finite.  n == 0 does nothing; F110_E_INVALID, not a launch, for
+ * what f110_qhead_validate refuses, n outside 0 .. 2^24, a null p, action, q or pre, w_act or w2 of a critic c < C, a target without
+ * all three of its inputs, and a wrong device as f110_policyhead_forward refuses it.
+ * Numerics, fp32, bit for bit, for row b and hidden unit j: acc = 0; for a ascending: acc = fmaf(w_act[j][a], (float)action[b][a],
+ * acc); z = (pre[b][j] + acc) + b1[j] (+ 0.0f for NULL); h = z > 0 ? z : 0.  q[b]: 64 partial sums s_l = 0; for j = l, l + 64, ...
+ * ascending while j < H: s_l = fmaf(w2[j], h_j, s_l); a tree: for m = 32, 16, 8, 4, 2, 1: s_l = s_l + s_{l + m} for l < m; q = s_0 +
+ * b2 (+ 0.0f for NULL).  qmin = q[0] < q[1] ? q[0] : q[1] (C = 1: q[0]).  The target in fp64 from values widened exactly, every
+ * operation rounded on its own, in the reference's order: tq = qmin - alpha * next_log_prob; tv = reward + ((1.0 - done) * gamma) *
+ * tq; rounded once to fp32.  A row's result depends neither on n nor on its place in the batch; two calls give the same bits.
+ * f110_qhead_backward: from the forward's inputs, its output q, grad_q [C, n] fp32 or NULL and grad_qmin [n] fp32 or NULL (a missing
+ * one counts as 0); it recomputes z with the same chain, so the ReLU's mask is the forward's.  G_c[b] = grad_q[c][b] + grad_qmin[b] *
+ * m_c[b], m_c = 1 where q_c < q_other, 0.5 where they are equal, 0 where greater (torch's rule for minimum; C = 1: 1).  g_z = z > 0 ?
+ * G_c * w2[j] : 0, which is grad_pre[c] [n, H].  grad_w_act[c][j][a], grad_b1[c][j], grad_w2[c][j], grad_b2[c] in two stages: for each
+ * slice of F110_QHEAD_SLICE_ROWS consecutive rows acc = 0; for b ascending: acc = fmaf(g_z, (float)action[b][a], acc), acc = acc +
+ * g_z, acc = fmaf(G_c, h, acc), acc = acc + G_c respectively; then acc = 0 and the slices are added in ascending order.  grad_w_act
+ * is written with the row stride ld, and nothing between its rows is touched.  grad_action[b][a], of the action's width: per critic
+ * the 64 partial sums s_l = fmaf(g_z[j], w_act[j][a], s_l) over j = l, l + 64, ... and the tree as in q; then acc = 0; for c
+ * ascending: acc = acc + that.  No atomics.  Every gradient output may be NULL (skipped).  `workspace`: 16-byte aligned,
+ * f110_qhead_workspace bytes (0 for an invalid configuration or n outside 1 .. 2^24), required when a parameter gradient is asked
+ * for; it need not be initialised.
+ * f110_qhead_validate: host only.  F110_E_INVALID for hidden outside 1..4096, action_dim outside 1..32, critics outside 1..2 and
+ * ld below action_dim. */
+#define F110_QHEAD_SLICE_ROWS 256
+typedef struct {
+    int32_t hidden;             /* H, 1..4096 (SAL: 512) */
+    int32_t action_dim;         /* A, 1..32 (SAL: 16) */
+    int32_t critics;            /* C, 1..2 */
+    int32_t ld;                 /* row stride of w_act and grad_w_act in elements, >= A */
+    int32_t action_fp64;        /* nonzero: action, next_log_prob and grad_action are double, else float */
+} f110_qhead_config;
+typedef struct {                /* entries c >= C are not read */
+    const float *pre[2], *w_act[2], *b1[2], *w2[2], *b2[2];
+} f110_qhead_critics;
+typedef struct {
+    float *grad_pre[2], *grad_w_act[2], *grad_b1[2], *grad_w2[2], *grad_b2[2];
+} f110_qhead_grads;
+int f110_qhead_validate(const f110_qhead_config *cfg);
+int64_t f110_qhead_workspace(const f110_qhead_config *cfg, int64_t n);
+int f110_qhead_forward(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const double *reward,
+                       const uint8_t *done, const void *next_log_prob, double gamma, double alpha, float *q, float *qmin, float *target,
+                       void *stream);
+int f110_qhead_backward(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const float *q,
+                        const float *grad_q, const float *grad_qmin, const f110_qhead_grads *g, void *grad_action, float *workspace,
+                        void *stream);
+
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).
  * scans_f32 / lookups may be NULL; lookups [n] is overwritten-by-accumulation like

@@ -23,4 +23,7 @@ def __getattr__(name):
     if name in ('sample_actions', 'PolicyHead'):
         from . import policyhead
         return getattr(policyhead, name)
+    if name in ('twin_q', 'td_target', 'QHead'):
+        from . import qhead
+        return getattr(qhead, name)
     raise AttributeError(name)

@@ -115,6 +115,26 @@ class PolicyheadConfig(C.Structure):
 
 F110_POLICYHEAD_SLICE_ROWS = 256
 
+
+# f110_qhead_config, f110_qhead_critics, f110_qhead_grads: the critic head (the twin Q tail and the TD target; stateless)
+class QheadConfig(C.Structure):
+    _fields_ = [('hidden', C.c_int32), ('action_dim', C.c_int32), ('critics', C.c_int32), ('ld', C.c_int32), ('action_fp64', C.c_int32)]
+
+
+QHEAD_CRITIC_FIELDS = ['pre', 'w_act', 'b1', 'w2', 'b2']
+QHEAD_GRAD_FIELDS = ['grad_pre', 'grad_w_act', 'grad_b1', 'grad_w2', 'grad_b2']
+
+
+class QheadCritics(C.Structure):
+    _fields_ = [(name, C.c_void_p * 2) for name in QHEAD_CRITIC_FIELDS]
+
+
+class QheadGrads(C.Structure):
+    _fields_ = [(name, C.c_void_p * 2) for name in QHEAD_GRAD_FIELDS]
+
+
+F110_QHEAD_SLICE_ROWS = 256
+
 # every symbol include/f110_hip.h declares: name -> argtypes (restype int unless noted)
 _VP, _I32, _I64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -201,6 +221,10 @@ SYMBOLS = {
     'f110_policyhead_workspace': [C.POINTER(PolicyheadConfig), _I64],
     'f110_policyhead_forward': [C.POINTER(PolicyheadConfig), _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_policyhead_backward': [C.POINTER(PolicyheadConfig), _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_qhead_validate': [C.POINTER(QheadConfig)],
+    'f110_qhead_workspace': [C.POINTER(QheadConfig), _I64],
+    'f110_qhead_forward': [C.POINTER(QheadConfig), C.POINTER(QheadCritics), _VP, _I64, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP],
+    'f110_qhead_backward': [C.POINTER(QheadConfig), C.POINTER(QheadCritics), _VP, _I64, _VP, _VP, _VP, C.POINTER(QheadGrads), _VP, _VP, _VP],
     'f110_replay_pack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_replay_unpack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],
@@ -255,6 +279,7 @@ def load():
     lib.f110_pure_pursuit_workspace.restype = C.c_int64
     lib.f110_bitconv_workspace.restype = C.c_int64
     lib.f110_policyhead_workspace.restype = C.c_int64
+    lib.f110_qhead_workspace.restype = C.c_int64
     lib.f110_pack_env_size.restype = C.c_int64
     lib.f110_destroy.restype = None
     lib.f110_bitmap_destroy.restype = None

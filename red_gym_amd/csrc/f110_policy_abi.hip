@@ -229,7 +229,7 @@ extern "C" int64_t f110_policyhead_workspace(const f110_policyhead_config *cfg, 
 // The stateless entry points launch on the calling thread's current device: every required pointer must be memory of that device
 // and a stream given must belong to it.  A mismatch is refused here, before any launch (host-side queries only, no synchronisation).
 struct PolicyheadPtr { const char *name; const void *p; };
-static int policyhead_check_device(const char *who, hipStream_t stream, std::initializer_list<PolicyheadPtr> ptrs)
+static int policyhead_check_device(const char *who, hipStream_t stream, const std::vector<PolicyheadPtr> &ptrs)
 {
     int cur = -1;
     HIP_TRY(hipGetDevice(&cur));
@@ -313,6 +313,119 @@ extern "C" int f110_policyhead_backward(const f110_policyhead_config *cfg, const
         hipLaunchKernelGGL(policyhead_gradw_kernel, dim3((unsigned)a.slices, (unsigned)((a.K + 63) / 64 + 1)), dim3(64), 0, s, a);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(policyhead_reduce_kernel, dim3((unsigned)((2 * a.A * (a.K + 1) + PH_THREADS - 1) / PH_THREADS)), dim3(PH_THREADS), 0, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return F110_OK;
+}
+
+// ---------------------------------------------------------------- critic head: the twin Q tail and the TD target
+extern "C" int f110_qhead_validate(const f110_qhead_config *cfg)
+{
+    const char *who = "f110_qhead_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    if (cfg->hidden < 1 || cfg->hidden > QH_MAX_H) return fail(F110_E_INVALID, "%s: hidden %d (1..%d)", who, cfg->hidden, QH_MAX_H);
+    if (cfg->action_dim < 1 || cfg->action_dim > QH_MAX_A) return fail(F110_E_INVALID, "%s: action_dim %d (1..%d)", who, cfg->action_dim, QH_MAX_A);
+    if (cfg->critics < 1 || cfg->critics > QH_MAX_C) return fail(F110_E_INVALID, "%s: %d critics (1..%d)", who, cfg->critics, QH_MAX_C);
+    if (cfg->ld < cfg->action_dim) return fail(F110_E_INVALID, "%s: ld %d is below action_dim %d", who, cfg->ld, cfg->action_dim);
+    return F110_OK;
+}
+
+// the launch geometry of a validated configuration (restated by tests/qhead_cases.py paths)
+static size_t qhead_geometry(const f110_qhead_config &c, int64_t n, int rows_per_tile, QheadArgs &a)
+{
+    memset(&a, 0, sizeof(a));
+    a.H = c.hidden; a.A = c.action_dim; a.C = c.critics; a.ld = c.ld; a.act_fp64 = c.action_fp64 ? 1 : 0;
+    a.hc = std::min((QH_LDS_BYTES / 4 - a.A) / (a.A + 2) / 64 * 64, (a.H + 63) / 64 * 64);
+    a.chunks = (a.H + a.hc - 1) / a.hc;
+    a.n = n; a.tiles = (n + rows_per_tile - 1) / rows_per_tile;
+    a.slices = (int)((n + QH_SLICE - 1) / QH_SLICE);
+    return ((size_t)a.A * (a.hc + 1) + 2 * (size_t)a.hc) * sizeof(float);
+}
+
+extern "C" int64_t f110_qhead_workspace(const f110_qhead_config *cfg, int64_t n)
+{
+    if (n < 1 || n > QH_MAX_ROWS || f110_qhead_validate(cfg) != F110_OK) return 0;
+    const int64_t slices = (n + QH_SLICE - 1) / QH_SLICE;
+    const int64_t floats = cfg->critics * slices * (int64_t)qhead_partial_floats(cfg->hidden, cfg->action_dim);
+    return (floats + 3) / 4 * 4 * (int64_t)sizeof(float);
+}
+
+// what both entry points ask of the critics' arrays; the pointers that must be device memory are appended to `ptrs`
+static int qhead_critics(const char *who, const f110_qhead_config *cfg, const f110_qhead_critics *p, QheadArgs &a, std::vector<PolicyheadPtr> &ptrs)
+{
+    static const char *names[3][QH_MAX_C] = {{"pre[0]", "pre[1]"}, {"w_act[0]", "w_act[1]"}, {"w2[0]", "w2[1]"}};
+    for (int c = 0; c < cfg->critics; c++) {
+        if (!p->pre[c] || !p->w_act[c] || !p->w2[c]) return fail(F110_E_INVALID, "%s: null pre, w_act or w2 of critic %d", who, c);
+        a.pre[c] = p->pre[c]; a.w_act[c] = p->w_act[c]; a.b1[c] = p->b1[c]; a.w2[c] = p->w2[c]; a.b2[c] = p->b2[c];
+        ptrs.push_back({names[0][c], p->pre[c]}); ptrs.push_back({names[1][c], p->w_act[c]}); ptrs.push_back({names[2][c], p->w2[c]});
+    }
+    return F110_OK;
+}
+
+extern "C" int f110_qhead_forward(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const double *reward,
+                                  const uint8_t *done, const void *next_log_prob, double gamma, double alpha, float *q, float *qmin, float *target,
+                                  void *stream)
+{
+    const char *who = "f110_qhead_forward";
+    if (int rc = f110_qhead_validate(cfg)) return rc;
+    if (n < 0 || n > QH_MAX_ROWS) return fail(F110_E_INVALID, "%s: n=%lld rows (0..%lld)", who, (long long)n, (long long)QH_MAX_ROWS);
+    if (n == 0) return F110_OK;
+    if (!p || !action || !q) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (target && (!reward || !done || !next_log_prob)) return fail(F110_E_INVALID, "%s: a target needs reward, done and next_log_prob", who);
+    if (target && (!std::isfinite(gamma) || !std::isfinite(alpha))) return fail(F110_E_INVALID, "%s: gamma or alpha is not finite", who);
+    QheadArgs a;
+    const size_t lds = qhead_geometry(*cfg, n, QH_ROWS, a);
+    std::vector<PolicyheadPtr> ptrs = {{"action", action}, {"q", q}};
+    if (int rc = qhead_critics(who, cfg, p, a, ptrs)) return rc;
+    if (target) { ptrs.push_back({"reward", reward}); ptrs.push_back({"done", done}); ptrs.push_back({"next_log_prob", next_log_prob}); ptrs.push_back({"target", target}); }
+    if (int rc = policyhead_check_device(who, (hipStream_t)stream, ptrs)) return rc;
+    a.action = action; a.q = q; a.qmin = qmin; a.target = target;
+    if (target) { a.reward = reward; a.done = done; a.nlp = next_log_prob; a.gamma = gamma; a.alpha = alpha; }
+    // (a workgroup walks tiles grid apart, so one launch serves any n; its LDS stays within the 64 KiB every kernel may ask for)
+    const unsigned grid = (unsigned)std::min<long long>(a.tiles, QH_MAX_GRID);
+    hipLaunchKernelGGL(qhead_forward_kernel, dim3(grid), dim3(QH_THREADS), lds, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_qhead_backward(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const float *q,
+                                   const float *grad_q, const float *grad_qmin, const f110_qhead_grads *g, void *grad_action, float *workspace,
+                                   void *stream)
+{
+    const char *who = "f110_qhead_backward";
+    if (int rc = f110_qhead_validate(cfg)) return rc;
+    if (n < 0 || n > QH_MAX_ROWS) return fail(F110_E_INVALID, "%s: n=%lld rows (0..%lld)", who, (long long)n, (long long)QH_MAX_ROWS);
+    if (n == 0) return F110_OK;
+    if (!p || !action || !q || !g) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if ((uintptr_t)workspace % 16) return fail(F110_E_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    QheadArgs a;
+    const size_t lds = qhead_geometry(*cfg, n, QH_BROWS, a);
+    std::vector<PolicyheadPtr> ptrs = {{"action", action}, {"q", q}};
+    if (int rc = qhead_critics(who, cfg, p, a, ptrs)) return rc;
+    bool rows = grad_action != nullptr, params = false;
+    for (int c = 0; c < a.C; c++) {
+        a.grad_pre[c] = g->grad_pre[c]; a.grad_w_act[c] = g->grad_w_act[c]; a.grad_b1[c] = g->grad_b1[c]; a.grad_w2[c] = g->grad_w2[c]; a.grad_b2[c] = g->grad_b2[c];
+        rows = rows || a.grad_pre[c];
+        params = params || a.grad_w_act[c] || a.grad_b1[c] || a.grad_w2[c] || a.grad_b2[c];
+    }
+    if (params && !workspace) return fail(F110_E_INVALID, "%s: parameter gradients need the workspace", who);
+    if (params) ptrs.push_back({"workspace", workspace});
+    if (int rc = policyhead_check_device(who, (hipStream_t)stream, ptrs)) return rc;
+    a.action = action; a.q_in = q; a.grad_q = grad_q; a.grad_qmin = grad_qmin; a.grad_action = grad_action; a.partial = workspace;
+    hipStream_t s = (hipStream_t)stream;
+    if (rows) {
+        const unsigned grid = (unsigned)std::min<long long>(a.tiles, QH_MAX_GRID);
+        if (a.A <= 16) hipLaunchKernelGGL(qhead_rows_kernel<16>, dim3(grid), dim3(QH_THREADS), lds, s, a);
+        else hipLaunchKernelGGL(qhead_rows_kernel<32>, dim3(grid), dim3(QH_THREADS), lds, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (params) {
+        const dim3 grid((unsigned)a.slices, (unsigned)((a.H + QH_THREADS - 1) / QH_THREADS), (unsigned)a.C);
+        if (a.A <= 16) hipLaunchKernelGGL(qhead_gradw_kernel<16>, grid, dim3(QH_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(qhead_gradw_kernel<32>, grid, dim3(QH_THREADS), 0, s, a);
+        HIP_TRY(hipGetLastError());
+        const unsigned blocks = (unsigned)((qhead_partial_floats(a.H, a.A) + QH_THREADS - 1) / QH_THREADS);
+        hipLaunchKernelGGL(qhead_reduce_kernel, dim3(blocks, (unsigned)a.C), dim3(QH_THREADS), 0, s, a);
         HIP_TRY(hipGetLastError());
     }
     return F110_OK;
