@@ -269,7 +269,7 @@ int f110_noise_read(f110_handle *h, int32_t slot, int64_t row0, int64_t n_rows, 
  * being silent.  Synchronises the device, returns the word and clears it.  F110_DEVERR_NOISE_WINDOW: a car's noise row
  * was not in the table (f110_noise_ensure not called, or the floor above a live car).  F110_DEVERR_BOUNDS: only in the
  * bounds-checked debug build of the library (-DF110_BOUNDS, tools/build_variant.sh): an index into a device table was out
- * of range; bits 8.. name the table (csrc/f110_kernels.h BOUNDS_*). */
+ * of range; bits 8.. name the table (csrc/f110_bounds.h BT_*). */
 #define F110_DEVERR_NOISE_WINDOW 0x1u
 #define F110_DEVERR_BOUNDS 0x2u
 #define F110_DEVERR_QP_LIMIT 0x4u /* the path follower's active-set walk reached its step limit (see f110_pathfollow_act) */

@@ -2,7 +2,7 @@
     python -m red_gym_amd.build [--force]
 hipcc cross-compiles without a GPU; the resulting libf110_hip.so is git-ignored
 but travels with the tree to the GPU box.  The library is the translation units of UNITS
-(csrc/f110_internal.h says what each holds): they are compiled in parallel, each only when
+(csrc/f110_common.h says what each holds): they are compiled in parallel, each only when
 it or a header has changed, and linked into the one .so."""
 import glob
 import os

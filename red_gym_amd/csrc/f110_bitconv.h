@@ -11,10 +11,13 @@
 //   bitconv_reduce_kernel    stage 2: the G partials of every element summed in a fixed order, times `on`
 // Forward numerics (the contract of include/f110_hip.h): acc = 0; taps ky major, kx minor: acc = fma(w, bit, acc) with bit 0.0 or
 // 1.0 -- w * bit is exact, so this is acc + w for a set tap and acc for a clear one, rounded once per tap; out = (acc * on) + bias.
-// Includes f110_replay.h for the frame format it reads: replay_bits16 (16 pixels -> 16 bits) here, replay_words and REPLAY_MAX_DIM
+// Includes f110_replay_bits.h for the frame format it reads: replay_bits16 (16 pixels -> 16 bits) here, replay_words and REPLAY_MAX_DIM
 // in the host checks of f110_policy_abi.hip.
 #pragma once
-#include "f110_replay.h"
+#include "../../include/f110_hip.h" // f110_bitconv_config
+#include "f110_replay_bits.h"
+
+#pragma clang fp contract(off)
 
 namespace f110 {
 
@@ -114,7 +117,6 @@ __device__ inline uint64_t bitconv_mask(const uint64_t *lds, const BitconvTile &
     return m;
 }
 
-#if defined(F110_UNIT_POLICY)
 // grid: (images of this launch) * tiles_y * tiles_x; weight [C, K, K], bias [C] or NULL, out [n, C, OH, OW]
 template <int K, bool U8>
 static __global__ __launch_bounds__(BC_THREADS) void bitconv_forward_kernel(BitconvArgs a, const float *__restrict__ weight, const float *__restrict__ bias,
@@ -241,6 +243,5 @@ static __global__ __launch_bounds__(BC_THREADS) void bitconv_reduce_kernel(const
     if (is_w) grad_weight[o] = v * on;
     else if (grad_bias) grad_bias[o - nw] = v;
 }
-#endif
 
 } // namespace f110

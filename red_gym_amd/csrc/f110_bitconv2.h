@@ -18,7 +18,9 @@
 // acc) for k = (ci major, ky, kx minor) from acc = 0; the padding terms are fma(0, 0, acc); out = acc + bias2, relu2.
 #pragma once
 #include "f110_bitconv.h"
-#include "f110_kernels.h" // F110_BOUNDS_ONLY
+#include "f110_bounds.h" // F110_BOUNDS_ONLY
+
+#pragma clang fp contract(off)
 
 namespace f110 {
 
@@ -102,7 +104,6 @@ __device__ inline void bitconv2_mma(const float *a1, const int *koff, const floa
     }
 }
 
-#if defined(F110_UNIT_POLICY)
 // grid: min(items, BC2_MAX_GRID); dynamic LDS of a.a1_off + 4 C1 NR1 XW bytes.  w1 [C1, K, K], w2 [C2, C1, k2, k2], b1 / b2 or
 // NULL, out [n, C2, OH2, OW2]
 static __global__ __launch_bounds__(BC_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void bitconv2_forward_kernel(Bitconv2Args a, const float *__restrict__ w1, const float *__restrict__ b1,
@@ -201,6 +202,5 @@ static __global__ __launch_bounds__(BC_THREADS) __attribute__((amdgpu_waves_per_
         // written after the barrier behind the staging)
     }
 }
-#endif
 
 } // namespace f110

@@ -362,7 +362,6 @@ __device__ inline int2 bm_point(const BitmapArgs &a, int img, int k, int cx, int
 }
 
 // function-level view of the point stage (f110_bitmap_points): out [n, T, 2] int32 (x, y)
-#if defined(F110_UNIT_BITMAP)
 static __global__ __launch_bounds__(256) void bitmap_points_kernel(BitmapArgs a, int *out)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -372,9 +371,7 @@ static __global__ __launch_bounds__(256) void bitmap_points_kernel(BitmapArgs a,
     out[2 * i] = p.x;
     out[2 * i + 1] = p.y;
 }
-#endif
 
-#if defined(F110_UNIT_BITMAP)
 // The image workgroup g draws in round `it` of a launch of `grid` workgroups; a value >= n: none (and none in later rounds).
 // (Rotating the rounds' slots, so that a workgroup sees every kind of image, changes nothing: the spread of the workgroups'
 // lives -- 620 to 980 us in one launch -- follows their dispatch order, not their images; profiles/r05_bitmap.txt.)
@@ -794,7 +791,6 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
     img = img_next; it++;
     } while (img < a.n);
 }
-#endif
 
 // ---- f1tenth_gym/examples/lidar.py:212-244: point-occupancy grid (one workgroup per scan)
 struct OccArgs {
@@ -805,7 +801,6 @@ struct OccArgs {
     unsigned char *out;        // [n, grid, grid]
 };
 
-#if defined(F110_UNIT_BITMAP)
 static __global__ __launch_bounds__(BM_THREADS) void occupancy_kernel(OccArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -840,6 +835,5 @@ static __global__ __launch_bounds__(BM_THREADS) void occupancy_kernel(OccArgs a)
         for (int p = tid; p < G * G; p += BM_THREADS) dst[p] = (unsigned char)((bits[p >> 5] >> (p & 31)) & 1u);
     }
 }
-#endif
 
 } // namespace f110

@@ -1,6 +1,6 @@
-// f110_bitmap_abi.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_internal.h for the units.
-#define F110_UNIT_BITMAP
-#include "f110_internal.h"
+// f110_bitmap_abi.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_common.h for the units.
+#include "f110_common.h"
+#include "f110_bitmap.h"
 
 // ---------------------------------------------------------------- scan -> bitmap
 static const void *bitmap_fn(size_t lds, int mode, int channels)

@@ -1,6 +1,10 @@
-// f110_consumers.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_internal.h for the units.
-#define F110_UNIT_CONSUMERS
-#include "f110_internal.h"
+// f110_consumers.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_common.h for the units.
+#include "f110_handle.h"
+#include "f110_planner.h"
+#include "f110_progress.h"
+#include "f110_shaping.h"
+#include "f110_pathfollow.h"
+#include "f110_replay.h"
 
 // ---------------------------------------------------------------- planner
 // per device: the LDS a workgroup may use (queried once), the dynamic-LDS attribute already granted to
@@ -36,7 +40,7 @@ static int32_t *single_track_offsets(int dev, int M)
     return d.hdr;
 }
 
-// Host half of a raceline's grid of candidate lists (f110_planner.h PlanGrid): the points are (wp[stride * i], wp[stride * i + 1]),
+// Host half of a raceline's grid of candidate lists (f110_plangrid.h PlanGrid): the points are (wp[stride * i], wp[stride * i + 1]),
 // i < M; `g` gets the geometry and the degenerate flag, `count` / `cand` the tables to upload (g.count / g.cand stay unset).
 // cell: edge of a grid cell in metres; margin: how far around the raceline's bounding box the grid reaches.  Shared by the
 // planner's prepare and the progress tracker's install, so that both search the same lists.

@@ -410,4 +410,16 @@ __device__ inline void ray_cast_wave(double px, double py, double pyaw, const do
     }
 }
 
+// clamp x to [lo, hi] in one instruction (the compiler only forms v_med3_i32 when it can
+// prove lo <= hi, which it cannot for a runtime map size)
+__device__ inline int med3_i32(int x, int lo, int hi)
+{
+    int r;
+    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(lo), "s"(hi));
+    return r;
+}
+
+// wave-wide vote straight on the condition mask (HIP's __ballot round-trips through a VGPR)
+__device__ inline unsigned long long vote(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 } // namespace f110

@@ -1,121 +1,16 @@
-// f110_internal.h -- what the translation units of libf110_hip.so share: the handle, the error plumbing and the few helpers
-// that cross a unit's border.  The kernels live in headers as `static __global__` functions: a unit instantiates the ones it
-// launches.  Units (red_gym_amd/build.py compiles them in parallel and links them into the one library):
-//   f110_handle.hip     handle life cycle, host tables, vehicle parameters, buffers, device error word, host EDT
-//   f110_maps.hip       map installation (host table / occupancy mask -> cell codes, LUTs), device EDT, track mask
-//   f110_noise_abi.hip  lidar noise: slots, ring, generators, per-env mode
-//   f110_step.hip       launch policy of the scan, the step, hipGraphs, measurement aid, function-level entry points
-//   f110_consumers.hip  the callers either side of the step, on the handle: pure-pursuit planner, progress tracker, reward shaper,
-//                       path follower, replay buffer
-//   f110_policy_abi.hip the policy and the critics' tail, stateless: bit convolution, policy stem, policy head, critic head
-//   f110_bitmap_abi.hip the scan's consumers with no handle: scan -> bitmap (its own f110_bitmap object), occupancy grid
+// f110_handle.h -- the handle (f110_handle) with the state of every family that lives on it, and the few helpers that cross a
+// unit's border.  It includes the headers whose TYPES the handle stores, none that defines a kernel.
 #pragma once
-#include "../../include/f110_hip.h"
-#include "f110_scan_plan.h"
-#include "f110_kernels.h"
-#include "f110_planner.h"
-#include "f110_progress.h"
-#include "f110_shaping.h"
-#include "f110_pathfollow.h"
-#include "f110_replay.h"
-#include "f110_bitconv.h"
-#include "f110_bitconv2.h"
-#include "f110_policyhead.h"
-#include "f110_qhead.h"
-#include "f110_bitmap.h"
-#include "f110_mapgen.h"
+#include "f110_common.h"
+#include "f110_device.h"    // Params
+#include "f110_map.h"       // MapDev
+#include "f110_noise.h"     // NoiseDesc, NoiseGen, NoiseMark, u128
+#include "f110_plangrid.h"  // PlanGrid
+#include "f110_scan_plan.h" // StageSpec
 
-#include <hip/hip_ext.h>
+namespace f110 { struct OppPair; } // f110_opponents.h: the handle only holds the buffer (alloc_opp_pairs, f110_step.hip, sizes it)
 
-#include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <new>
-#include <utility>
-#include <vector>
-
-using namespace f110;
-
-int fail(int code, const char *fmt, ...);
-
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(F110_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-// Makes `dev` the calling thread's current device for the scope of one library call and restores the caller's own
-// afterwards: a process that drives several GPUs (or several handles on different GPUs) keeps ITS current device across
-// every call.  f110_step / f110_reset and the function-level entry points do not switch -- they launch on the caller's
-// stream, which belongs to the caller's current device -- they check (check_device) and refuse a mismatch.
-struct DeviceScope {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceScope(int dev)
-    {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != dev) {
-            err = hipSetDevice(dev);
-            switched = err == hipSuccess;
-        }
-    }
-    ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-    DeviceScope(const DeviceScope &) = delete;
-    DeviceScope &operator=(const DeviceScope &) = delete;
-};
-#define ON_DEVICE(dev)            \
-    DeviceScope dev_scope_(dev);  \
-    HIP_TRY(dev_scope_.err)
-
-
-// Owners of what the library allocates.  Every device buffer, event, stream and graph lives in one of these and is released by
-// its destructor; a table is replaced by building the new one in a local owner and moving it in, which frees the old one.
-template <typename T> class DevBuf { // device memory of size() elements of T
-    T *p_ = nullptr;
-    size_t n_ = 0;
-public:
-    DevBuf() = default;
-    DevBuf(DevBuf &&o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
-    DevBuf &operator=(DevBuf o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); return *this; } // (o takes the old memory along)
-    ~DevBuf() { if (p_) (void)hipFree(p_); }
-    T *get() const { return p_; }
-    size_t size() const { return n_; }
-    hipError_t alloc(size_t n) // new memory first: a failure leaves what is held
-    {
-        T *p = nullptr;
-        const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
-        if (e == hipSuccess) { std::swap(p_, p); n_ = n; if (p) (void)hipFree(p); }
-        return e;
-    }
-    hipError_t upload(const T *src, size_t n) // (re)allocates when n differs from size()
-    {
-        const hipError_t e = n == n_ && p_ ? hipSuccess : alloc(n);
-        return e == hipSuccess ? hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice) : e;
-    }
-};
-
-template <typename H, hipError_t (*Destroy)(H)> class HipOwner { // an event, stream or graph
-    H h_ = nullptr;
-public:
-    HipOwner() = default;
-    HipOwner(HipOwner &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
-    HipOwner &operator=(HipOwner o) noexcept { std::swap(h_, o.h_); return *this; }
-    ~HipOwner() { if (h_) (void)Destroy(h_); }
-    H get() const { return h_; }
-    H *put() { *this = HipOwner(); return &h_; } // for the call that creates it: what was held is released first
-};
-using Event = HipOwner<hipEvent_t, hipEventDestroy>;
-using Stream = HipOwner<hipStream_t, hipStreamDestroy>;
-using Graph = HipOwner<hipGraph_t, hipGraphDestroy>;
-using GraphExec = HipOwner<hipGraphExec_t, hipGraphExecDestroy>;
-
-// A raceline's grid of candidate lists on the device (f110_planner.h PlanGrid; built on the host by build_plan_grid,
+// A raceline's grid of candidate lists on the device (f110_plangrid.h PlanGrid; built on the host by build_plan_grid,
 // f110_consumers.hip): the geometry, whose count / cand point into the two tables it owns.  The planner's prepared raceline
 // and the progress tracker each hold one.
 struct PlanGridDev {
@@ -170,7 +65,7 @@ struct NoiseState {
     DevBuf<NoiseMark> d_marks;        // [marks_slots][marks_cap] generator state at every 64th row (f110_noise.h NoiseMark)
     long long marks_cap = 0;
     int marks_slots = 0;
-    DevBuf<u128> d_pcg_tab;           // [2][65] powers and partial sums of the LCG multiplier (f110_noise.h NoiseGenArgs::pcg_tab)
+    DevBuf<u128> d_pcg_tab;           // [2][65] powers and partial sums of the LCG multiplier (f110_noise_kernels.h NoiseGenArgs::pcg_tab)
     bool per_env = false;
     DevBuf<NoiseGen> d_env_gen, d_env_seed;   // [num_envs]
     DevBuf<double> d_env_rows;                // [num_envs][num_beams]
@@ -192,7 +87,7 @@ struct f110_handle {
     DevBuf<Params> d_params;          // [slots the allocation holds][1 + A]
     DevBuf<int32_t> d_env_params;     // dev [B] params slot of every env; passed to the kernels only when `multi_params`
     bool multi_params = false;
-    DevBuf<OppPair> d_opp_pairs;      // [N, A-1] opponent ray-cast scratch (never allocated in f110_step)
+    DevBuf<OppPair> d_opp_pairs;      // [N, A-1] opponent ray-cast scratch (alloc_opp_pairs at f110_create; the entry point f110_step() never allocates)
     DevBuf<uint8_t> d_was_pending;    // [B] pending_reset as the step's first kernel found it
     bool has_map = false, bound = false;
     // Bumped whenever a later f110_step would enqueue different kernels or by-value arguments than an earlier one
@@ -275,7 +170,7 @@ struct f110_handle {
     bool prof_on = false;
 };
 
-// helpers defined in f110_handle.hip / f110_noise_abi.hip and used elsewhere
-int check_current_device(int dev, const char *who);
+// helpers defined in f110_handle.hip / f110_noise_abi.hip / f110_step.hip and used elsewhere
 int check_device(const f110_handle *h, const char *who);
 int noise_init(f110_handle *h);
+int alloc_opp_pairs(f110_handle *h);

@@ -1,5 +1,6 @@
-// f110_handle.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_internal.h for the units.
-#include "f110_internal.h"
+// f110_handle.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_common.h for the units.
+#include "f110_handle.h"
+#include "f110_bounds.h" // F110_BCHK, BT_SELFTEST for bounds_selftest_kernel below
 
 static thread_local char g_err[512] = "";
 
@@ -168,22 +169,6 @@ static int upload_beam_cs(f110_handle *h, const double *scan_angles)
 }
 
 static int upload_params(f110_handle *h);
-
-// scratch of the opponent ray cast: allocated here, never in f110_step
-static int alloc_opp_pairs(f110_handle *h)
-{
-    if (h->cfg.num_agents < 2) return F110_OK;
-    const size_t n = (size_t)h->cfg.num_envs * h->cfg.num_agents * (h->cfg.num_agents - 1);
-    DevBuf<OppPair> pairs;
-    DevBuf<uint8_t> was_pending;
-    HIP_TRY(pairs.alloc(n));
-    HIP_TRY(hipMemset(pairs.get(), 0, n * sizeof(OppPair)));
-    HIP_TRY(was_pending.alloc((size_t)h->cfg.num_envs));
-    HIP_TRY(hipMemset(was_pending.get(), 0, (size_t)h->cfg.num_envs));
-    h->d_opp_pairs = std::move(pairs);
-    h->d_was_pending = std::move(was_pending);
-    return F110_OK;
-}
 
 // The scan reads a beam's side distance only where the iTTC test could fire: scan value below (largest side distance +
 // the candidate margin).  Non-finite entries can never make a candidate (the reference's comparison is false for them).

@@ -1,0 +1,55 @@
+// f110_map.h -- the cell-table format of a map, shared by the host code that builds the tables (f110_maps.hip), the device
+// pipeline that builds them (f110_mapgen.h) and the scan that reads them (f110_scan.h).  No kernels.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#pragma clang fp contract(off)
+
+namespace f110 {
+
+// Cell table.  Each map cell stores, as a u16, the BYTE OFFSET of its distance inside the LDS copy of the LUT:
+// 8 * (k + 1), k = RANK of the cell's exact squared distance d2 (in cells, to the nearest obstacle) among the distinct d2
+// values of the map, for k < LDS_RANKS = 1022 (squared distances are sums of two squares, so that reaches d2 ~ 3 900 =
+// 62 cells); OFF_FAR for larger ranks and for cells of a user table that are not resolution*sqrt(int) -- those re-read a
+// second table (u16 rank, 65535 = "use the fp64 table") in a rarely taken branch.
+// The table has a one-cell BORDER on every side holding code 0, and LDS slot 0 holds dt[-1,-1]: the reference's
+// out-of-bounds read (laser_models.py:80-81,:103) becomes an ordinary lookup of a clamped index -- no bounds compare, no
+// select in the march loop (the loaded value addresses the ds_read directly).
+// The far marker's LDS slot holds -0.0: as a distance it is an exact no-op (total += -0.0, x += -0.0 * c) that ends the ray's
+// march (-0.0 > eps is false); the wave looks at the sign of its parked lanes' last distance once per refill, not once per look-up.
+// Layout: 8-column strips, map cell (r, c), r in -1..H, c in -1..W, at [(c >> 3) + 1][r + 1][c & 7] (arithmetic
+// shift: the left border column is the last column of strip 0), so one 128-B cache line holds an 8x8-cell block.  The 64 rays of a wave sample neighbouring
+// points, so a gather touches fewer lines than with a row-major table (which measured
+// ~40 L1 accesses per 64-lane gather and made the kernel L1-tag-rate bound), and the byte
+// offset is two shift-adds and one multiply-add: (c >> 3) * (strip_bytes - 16) + (c << 1) + (r << 4) + strip_bytes + 16.
+// (Round 5 tried to have the address unit form an equivalent layout -- a swizzled structured descriptor, index = row, offset =
+// 2 * column, the descriptor's range check as the row clamp: two VALU instructions instead of six -- and it is exact and 26 %
+// slower: an `idxen` load merges at most two lanes per access, profiles/r05_swizzle_probe.txt.)
+constexpr int LUT_LDS = 1024;                           // LDS LUT slots
+constexpr unsigned SLOT_OOB = 0, SLOT_FAR = LUT_LDS - 1; // slot 0: dt[-1,-1]; slots 1 .. LUT_LDS-2: ranks 0 .. LDS_RANKS-1; last: far marker
+constexpr unsigned LDS_RANKS = LUT_LDS - 2;
+constexpr unsigned OFF_FAR = 8 * SLOT_FAR;
+constexpr unsigned CODE_ESC = 65535;                    // second table: read the fp64 table instead
+__host__ __device__ inline unsigned cell_code(unsigned rank) { return rank < LDS_RANKS ? 8u * (rank + 1u) : OFF_FAR; }
+// geometry of the padded strip table
+__host__ __device__ inline int map_rows_padded(int H) { return ((H + 2 + 7) >> 3) << 3; }
+__host__ __device__ inline size_t map_cells(int H, int W) { return (size_t)((W >> 3) + 2) * map_rows_padded(H) * 8; } // strip 0 only holds the left border column
+// element index of map cell (r, c), -1 <= r <= H, -1 <= c <= W
+__host__ __device__ inline size_t cell_elem(int r, int c, int Hp) { return ((size_t)((c >> 3) + 1) * Hp + (size_t)(r + 1)) * 8 + (size_t)(c & 7); }
+
+struct MapDev {
+    const uint16_t *cells;  // padded strips [(W >> 3) + 2][Hp][8] of LDS byte offsets
+    const uint16_t *cells_far; // same layout: rank (<= 65534) of the cells marked OFF_FAR, 65535 = fp64 table
+    unsigned cells_bytes;
+    unsigned strip_bytes;   // Hp * 16, Hp = H + 2 rounded up to a multiple of 8
+    const double *lut;      // [lut_len <= 65535] resolution*sqrt(d2_k), indexed by rank k
+    const double *lut_lds;  // [LUT_LDS] image staged in LDS: dt[-1,-1], lut[0..LDS_RANKS-1], -0.0
+    const double *dt;       // [H*W] exact fp64 distance table (escape path, rarely touched)
+    int H, W;
+    double res, rinv, ox, oy, oc, os, wres, hres, oob; // oob = dt[H-1][W-1]
+    unsigned lut_len;       // entries of lut
+};
+
+} // namespace f110

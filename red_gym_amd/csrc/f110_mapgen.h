@@ -5,7 +5,7 @@
 // Integer arithmetic throughout: d2 is exact, and resolution*sqrt(d2) (IEEE sqrt and multiply) reproduces
 // scipy.ndimage.distance_transform_edt bit for bit like the host pipeline it replaces.
 #pragma once
-#include "f110_kernels.h"
+#include "f110_map.h"
 
 #pragma clang fp contract(off)
 
@@ -14,7 +14,6 @@ namespace f110 {
 constexpr unsigned EDT_NONE = 0xffffffffu; // column without any occupied cell
 
 // Pass 1, one lane per column (coalesced across x): g = distance along the column to the nearest zero cell.
-#if defined(F110_UNIT_MAPS)
 static __global__ __launch_bounds__(256) void edt_columns_kernel(const uint8_t *mask, int H, int W, unsigned *g)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -33,12 +32,10 @@ static __global__ __launch_bounds__(256) void edt_columns_kernel(const uint8_t *
         g[i] = d < up ? d : up;
     }
 }
-#endif
 
 // Pass 2, one workgroup per row with the row's g^2 in LDS: d2(x) = min over x' of (x - x')^2 + g(x')^2, searched
 // outwards from x and stopped as soon as dx^2 alone reaches the best value -- O(distance) LDS reads per cell,
 // exact, no lower-envelope bookkeeping (the sequential formulation of the host code).
-#if defined(F110_UNIT_MAPS)
 static __global__ __launch_bounds__(256) void edt_rows_kernel(const unsigned *g, int H, int W, unsigned *d2, unsigned *max_d2)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -75,10 +72,8 @@ static __global__ __launch_bounds__(256) void edt_rows_kernel(const unsigned *g,
         if ((threadIdx.x & 63) == 0) atomicMax(max_d2, local_max);
     }
 }
-#endif
 
 // presence bitmap of the distinct d2 values
-#if defined(F110_UNIT_MAPS)
 static __global__ __launch_bounds__(256) void d2_mark_kernel(const unsigned *d2, size_t n, unsigned *bits)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -87,11 +82,9 @@ static __global__ __launch_bounds__(256) void d2_mark_kernel(const unsigned *d2,
     const unsigned m = 1u << (v & 31);
     if (!(bits[v >> 5] & m)) atomicOr(&bits[v >> 5], m); // most values are already marked: read before the atomic
 }
-#endif
 
 // exclusive prefix of per-word popcounts, three small kernels (1024 words per block)
 constexpr int SCAN_BLOCK_WORDS = 1024;
-#if defined(F110_UNIT_MAPS)
 static __global__ __launch_bounds__(256) void rank_block_sums_kernel(const unsigned *bits, int n_words, unsigned *block_sums)
 {
     __shared__ unsigned s_part[4];
@@ -105,9 +98,7 @@ static __global__ __launch_bounds__(256) void rank_block_sums_kernel(const unsig
     __syncthreads();
     if (threadIdx.x == 0) block_sums[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
 }
-#endif
 
-#if defined(F110_UNIT_MAPS)
 static __global__ __launch_bounds__(64) void rank_scan_sums_kernel(unsigned *block_sums, int n_blocks, unsigned *total)
 {
     // one wave, sequential over chunks of 64: n_blocks is small (words / 1024)
@@ -125,9 +116,7 @@ static __global__ __launch_bounds__(64) void rank_scan_sums_kernel(unsigned *blo
     }
     if (threadIdx.x == 0) *total = run;
 }
-#endif
 
-#if defined(F110_UNIT_MAPS)
 static __global__ __launch_bounds__(256) void rank_word_prefix_kernel(const unsigned *bits, int n_words, const unsigned *block_sums,
                                                                unsigned *word_prefix)
 {
@@ -152,7 +141,6 @@ static __global__ __launch_bounds__(256) void rank_word_prefix_kernel(const unsi
         run += c[k];
     }
 }
-#endif
 
 __device__ inline unsigned d2_rank(const unsigned *bits, const unsigned *word_prefix, unsigned v)
 {
@@ -160,7 +148,6 @@ __device__ inline unsigned d2_rank(const unsigned *bits, const unsigned *word_pr
 }
 
 // cell codes (strip layout with border, see MapDev), second rank table and the fp64 distance table
-#if defined(F110_UNIT_MAPS)
 static __global__ __launch_bounds__(256) void map_encode_kernel(const unsigned *d2, int H, int W, int Hp, const unsigned *bits,
                                                          const unsigned *word_prefix, double res, uint16_t *cells,
                                                          uint16_t *cells_far, double *dt)
@@ -174,9 +161,7 @@ static __global__ __launch_bounds__(256) void map_encode_kernel(const unsigned *
     cells_far[t] = (uint16_t)(rank < CODE_ESC ? rank : CODE_ESC);
     dt[i] = res * sqrt((double)v);
 }
-#endif
 
-#if defined(F110_UNIT_MAPS)
 static __global__ __launch_bounds__(256) void map_fill_border_kernel(uint16_t *cells, uint16_t *cells_far, size_t n)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -184,10 +169,8 @@ static __global__ __launch_bounds__(256) void map_fill_border_kernel(uint16_t *c
     cells[i] = 0; // the border and the padding: code 0 = LDS slot 0 = dt[-1, -1]
     cells_far[i] = 0;
 }
-#endif
 
 // lut[rank] = resolution * sqrt(d2) for every distinct d2 with rank < n_lut
-#if defined(F110_UNIT_MAPS)
 static __global__ __launch_bounds__(256) void map_lut_kernel(const unsigned *bits, int n_words, const unsigned *word_prefix, double res,
                                                       double *lut, unsigned n_lut)
 {
@@ -200,7 +183,6 @@ static __global__ __launch_bounds__(256) void map_lut_kernel(const unsigned *bit
         lut[rank++] = res * sqrt((double)((unsigned)w * 32u + (unsigned)bit));
     }
 }
-#endif
 
 
 // ---- track walls from a centre line (red_gym_amd/trackgen.py): pixel (ix, iy) is a wall (0) iff the
@@ -211,7 +193,6 @@ static __global__ __launch_bounds__(256) void map_lut_kernel(const unsigned *bit
 struct TrackSeg { double ax, ay, ex, ey, inv_l2; };
 constexpr int TRACK_CHUNK = 256;
 
-#if defined(F110_UNIT_MAPS)
 static __global__ __launch_bounds__(256) void track_mask_kernel(const double *pts, int n_pts, int closed, int H, int W, double x0,
                                                          double y0, double pixel, double offset, double half_stroke,
                                                          uint8_t *mask)
@@ -246,6 +227,5 @@ static __global__ __launch_bounds__(256) void track_mask_kernel(const double *pt
     }
     if (ix < W && iy < H) mask[(size_t)iy * W + ix] = fabs(sqrt(best) - offset) <= half_stroke ? 0 : 1;
 }
-#endif
 
 } // namespace f110

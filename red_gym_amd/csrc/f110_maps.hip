@@ -1,6 +1,6 @@
-// f110_maps.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_internal.h for the units.
-#define F110_UNIT_MAPS
-#include "f110_internal.h"
+// f110_maps.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_common.h for the units.
+#include "f110_handle.h"
+#include "f110_mapgen.h"
 
 // Both pipelines end here.  `ns` holds the complete tables of the new map; until the descriptor is on the device nothing of the
 // slot has changed, so a failed install leaves the slot, its descriptor and the handle's flags as they were.  Then the slot takes

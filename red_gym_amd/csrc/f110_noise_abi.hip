@@ -1,6 +1,6 @@
-// f110_noise_abi.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_internal.h for the units.
-#define F110_UNIT_NOISE
-#include "f110_internal.h"
+// f110_noise_abi.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_common.h for the units.
+#include "f110_handle.h"
+#include "f110_noise_kernels.h"
 
 // ---------------------------------------------------------------- lidar noise (f110_noise.h)
 __global__ void noise_publish_kernel(NoiseDesc *dst, NoiseDesc d) { *dst = d; }

@@ -18,7 +18,9 @@
 // piece is a count of comparisons, the free set a bit mask), the walk ends at PF_QP_LIMIT at the latest and may raise
 // DEVERR_QP_LIMIT, and no other env changes by a bit -- the lane exchanges never leave the env's own pair of lanes.
 #pragma once
-#include "f110_kernels.h"
+#include "../../include/f110_hip.h" // f110_pathfollow_config
+#include "f110_bounds.h"
+#include "f110_device.h"
 
 #pragma clang fp contract(off)
 
@@ -79,7 +81,6 @@ __device__ inline double pf_floor_mod(double a, double m)
     return r;
 }
 
-#if defined(F110_UNIT_CONSUMERS)
 static __global__ __launch_bounds__(256) void pathfollow_act_kernel(PathFollowArgs a)
 {
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -337,6 +338,5 @@ static __global__ __launch_bounds__(256) void pathfollow_advance_kernel(PathAdva
     }
     a.index_out[env] = idx;
 }
-#endif
 
 } // namespace f110

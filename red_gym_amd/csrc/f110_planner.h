@@ -4,6 +4,7 @@
 // section 2); checked against oracle/planner.py in the tests.
 #pragma once
 #include "f110_device.h"
+#include "f110_plangrid.h"
 
 #pragma clang fp contract(off)
 
@@ -95,7 +96,6 @@ __host__ __device__ inline size_t pure_pursuit_lds_bytes(int M)
     return ((size_t)M * 3 + (size_t)nblk * 4) * sizeof(double);
 }
 
-#if defined(F110_UNIT_CONSUMERS)
 static __global__ __launch_bounds__(PP_WAVES * 64) void pure_pursuit_kernel(PlanArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double s_wp[]; // [M,3] waypoints, then [nblk,4] block boxes
@@ -247,7 +247,6 @@ static __global__ __launch_bounds__(PP_WAVES * 64) void pure_pursuit_kernel(Plan
         }
     }
 }
-#endif
 
 // ------------------------------------------------------------------ one LANE per car behind a grid of candidate lists (round 5)
 // The wave-per-car kernel above prunes 64-segment blocks by their boxes, but it still spends a whole wavefront, a copy of the
@@ -262,17 +261,7 @@ static __global__ __launch_bounds__(PP_WAVES * 64) void pure_pursuit_kernel(Plan
 // holds (a pose equally far from a long stretch of the raceline), a pose outside the grid and a NaN pose take every
 // segment, in the same lane: the same results, slower, and rare.  The look-ahead point (:49-129) is searched segment by
 // segment from the nearest one, as the reference does.
-constexpr int PG_CAP = 30;            // candidates a cell's list holds
-constexpr unsigned PG_ALL = 255;      // count value: take every segment
-struct PlanGrid {
-    double x0, y0, inv_cell;          // cell (ix, iy) covers x0 + ix / inv_cell ...
-    int gw, gh;
-    const uint8_t *count;             // [gh * gw]
-    const uint16_t *cand;             // [gh * gw][PG_CAP] ascending segment indices
-    int degenerate;                   // the raceline has a zero-length segment: plan() answers (0, 4.0) for every pose
-};
 
-#if defined(F110_UNIT_CONSUMERS)
 static __global__ __launch_bounds__(256) void pure_pursuit_grid_kernel(PlanArgs a, PlanGrid g)
 {
     const int car = blockIdx.x * blockDim.x + threadIdx.x;
@@ -345,7 +334,6 @@ static __global__ __launch_bounds__(256) void pure_pursuit_grid_kernel(PlanArgs 
     a.actions[(size_t)car * 2] = steer;
     a.actions[(size_t)car * 2 + 1] = speed;
 }
-#endif
 
 // ------------------------------------------------------------------ many tracks / racelines of any length
 // The kernel above stages ONE raceline in LDS (<= 6 400 points).  The reference loads any CSV
@@ -365,7 +353,6 @@ struct TrackSet {
 __device__ inline size_t track_box_row(const TrackSet &t, int k) { return (size_t)(t.offsets[k] >> 6) + (size_t)k; }
 
 // one wave per (raceline, 64-segment block): grid (ceil(max_blocks / 4), K), 256 threads
-#if defined(F110_UNIT_CONSUMERS)
 static __global__ __launch_bounds__(256) void track_boxes_kernel(TrackSet t)
 {
     const int k = blockIdx.y;
@@ -386,7 +373,6 @@ static __global__ __launch_bounds__(256) void track_boxes_kernel(TrackSet t)
         bx[0] = xl; bx[1] = xh; bx[2] = yl; bx[3] = yh; bx[4] = any_deg ? 1.0 : 0.0;
     }
 }
-#endif
 
 struct PlanTracksArgs {
     TrackSet t;
@@ -399,7 +385,6 @@ struct PlanTracksArgs {
 
 constexpr int PPG_WAVES = 4;
 
-#if defined(F110_UNIT_CONSUMERS)
 static __global__ __launch_bounds__(PPG_WAVES * 64) void pure_pursuit_tracks_kernel(PlanTracksArgs a)
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -533,6 +518,5 @@ static __global__ __launch_bounds__(PPG_WAVES * 64) void pure_pursuit_tracks_ker
         a.actions[(size_t)car * 2 + 1] = speed;
     }
 }
-#endif
 
 } // namespace f110

@@ -1,6 +1,9 @@
-// f110_policy_abi.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_internal.h for the units.
-#define F110_UNIT_POLICY
-#include "f110_internal.h"
+// f110_policy_abi.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_common.h for the units.
+#include "f110_common.h"
+#include "f110_bitconv.h"
+#include "f110_bitconv2.h"
+#include "f110_policyhead.h"
+#include "f110_qhead.h"
 
 // ---------------------------------------------------------------- first convolution from bits
 // What the entry points refuse, on the struct alone (no device).
@@ -226,33 +229,6 @@ extern "C" int64_t f110_policyhead_workspace(const f110_policyhead_config *cfg, 
     return (policyhead_gpre_floats(*cfg, n) + slices * 2 * cfg->action_dim * (cfg->in_features + 1)) * (int64_t)sizeof(float);
 }
 
-// The stateless entry points launch on the calling thread's current device: every required pointer must be memory of that device
-// and a stream given must belong to it.  A mismatch is refused here, before any launch (host-side queries only, no synchronisation).
-struct PolicyheadPtr { const char *name; const void *p; };
-static int policyhead_check_device(const char *who, hipStream_t stream, const std::vector<PolicyheadPtr> &ptrs)
-{
-    int cur = -1;
-    HIP_TRY(hipGetDevice(&cur));
-    if (stream) {
-        hipDevice_t sdev = -1;
-        if (hipStreamGetDevice(stream, &sdev) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(F110_E_INVALID, "%s: `stream` is not a stream of this process", who);
-        }
-        if ((int)sdev != cur) return fail(F110_E_INVALID, "%s: `stream` belongs to device %d but the calling thread's current device is %d", who, (int)sdev, cur);
-    }
-    for (const PolicyheadPtr &q : ptrs) {
-        hipPointerAttribute_t at;
-        memset(&at, 0, sizeof(at));
-        const hipError_t e = hipPointerGetAttributes(&at, q.p);
-        if (e != hipSuccess) (void)hipGetLastError();
-        if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged))
-            return fail(F110_E_INVALID, "%s: `%s` is not device memory", who, q.name);
-        if (at.device != cur) return fail(F110_E_INVALID, "%s: `%s` lives on device %d but the calling thread's current device is %d", who, q.name, at.device, cur);
-    }
-    return F110_OK;
-}
-
 extern "C" int f110_policyhead_forward(const f110_policyhead_config *cfg, const float *h, int64_t n, const float *w_mean, const float *b_mean,
                                        const float *w_log_std, const float *b_log_std, const float *eps, float *pre, void *action, void *log_prob,
                                        void *stream)
@@ -263,7 +239,7 @@ extern "C" int f110_policyhead_forward(const f110_policyhead_config *cfg, const 
     if (n == 0) return F110_OK;
     if (!h || !w_mean || !w_log_std || !pre || !action) return fail(F110_E_INVALID, "%s: null pointer", who);
     if ((eps == nullptr) != (log_prob == nullptr)) return fail(F110_E_INVALID, "%s: log_prob must be NULL exactly when eps is NULL", who);
-    if (int rc = policyhead_check_device(who, (hipStream_t)stream, {{"h", h}, {"w_mean", w_mean}, {"w_log_std", w_log_std}, {"pre", pre}, {"action", action}})) return rc;
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, {{"h", h}, {"w_mean", w_mean}, {"w_log_std", w_log_std}, {"pre", pre}, {"action", action}})) return rc;
     PolicyheadArgs a;
     policyhead_geometry(*cfg, n, a);
     a.h = h; a.w_mean = w_mean; a.b_mean = b_mean; a.w_log_std = w_log_std; a.b_log_std = b_log_std; a.eps = eps;
@@ -291,7 +267,7 @@ extern "C" int f110_policyhead_backward(const f110_policyhead_config *cfg, const
     if (!h || !w_mean || !w_log_std || !pre || !grad_action || !workspace) return fail(F110_E_INVALID, "%s: null pointer", who);
     if (!eps && grad_log_prob) return fail(F110_E_INVALID, "%s: grad_log_prob without eps (no log_prob was produced)", who);
     if ((uintptr_t)workspace % 16) return fail(F110_E_INVALID, "%s: the workspace must be 16-byte aligned", who);
-    if (int rc = policyhead_check_device(who, (hipStream_t)stream, {{"h", h}, {"w_mean", w_mean}, {"w_log_std", w_log_std}, {"pre", pre},
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, {{"h", h}, {"w_mean", w_mean}, {"w_log_std", w_log_std}, {"pre", pre},
                                                                     {"grad_action", grad_action}, {"workspace", workspace}})) return rc;
     PolicyheadArgs a;
     policyhead_geometry(*cfg, n, a);
@@ -351,7 +327,7 @@ extern "C" int64_t f110_qhead_workspace(const f110_qhead_config *cfg, int64_t n)
 }
 
 // what both entry points ask of the critics' arrays; the pointers that must be device memory are appended to `ptrs`
-static int qhead_critics(const char *who, const f110_qhead_config *cfg, const f110_qhead_critics *p, QheadArgs &a, std::vector<PolicyheadPtr> &ptrs)
+static int qhead_critics(const char *who, const f110_qhead_config *cfg, const f110_qhead_critics *p, QheadArgs &a, std::vector<DevicePtr> &ptrs)
 {
     static const char *names[3][QH_MAX_C] = {{"pre[0]", "pre[1]"}, {"w_act[0]", "w_act[1]"}, {"w2[0]", "w2[1]"}};
     for (int c = 0; c < cfg->critics; c++) {
@@ -375,10 +351,10 @@ extern "C" int f110_qhead_forward(const f110_qhead_config *cfg, const f110_qhead
     if (target && (!std::isfinite(gamma) || !std::isfinite(alpha))) return fail(F110_E_INVALID, "%s: gamma or alpha is not finite", who);
     QheadArgs a;
     const size_t lds = qhead_geometry(*cfg, n, QH_ROWS, a);
-    std::vector<PolicyheadPtr> ptrs = {{"action", action}, {"q", q}};
+    std::vector<DevicePtr> ptrs = {{"action", action}, {"q", q}};
     if (int rc = qhead_critics(who, cfg, p, a, ptrs)) return rc;
     if (target) { ptrs.push_back({"reward", reward}); ptrs.push_back({"done", done}); ptrs.push_back({"next_log_prob", next_log_prob}); ptrs.push_back({"target", target}); }
-    if (int rc = policyhead_check_device(who, (hipStream_t)stream, ptrs)) return rc;
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
     a.action = action; a.q = q; a.qmin = qmin; a.target = target;
     if (target) { a.reward = reward; a.done = done; a.nlp = next_log_prob; a.gamma = gamma; a.alpha = alpha; }
     // (a workgroup walks tiles grid apart, so one launch serves any n; its LDS stays within the 64 KiB every kernel may ask for)
@@ -400,7 +376,7 @@ extern "C" int f110_qhead_backward(const f110_qhead_config *cfg, const f110_qhea
     if ((uintptr_t)workspace % 16) return fail(F110_E_INVALID, "%s: the workspace must be 16-byte aligned", who);
     QheadArgs a;
     const size_t lds = qhead_geometry(*cfg, n, QH_BROWS, a);
-    std::vector<PolicyheadPtr> ptrs = {{"action", action}, {"q", q}};
+    std::vector<DevicePtr> ptrs = {{"action", action}, {"q", q}};
     if (int rc = qhead_critics(who, cfg, p, a, ptrs)) return rc;
     bool rows = grad_action != nullptr, params = false;
     for (int c = 0; c < a.C; c++) {
@@ -410,7 +386,7 @@ extern "C" int f110_qhead_backward(const f110_qhead_config *cfg, const f110_qhea
     }
     if (params && !workspace) return fail(F110_E_INVALID, "%s: parameter gradients need the workspace", who);
     if (params) ptrs.push_back({"workspace", workspace});
-    if (int rc = policyhead_check_device(who, (hipStream_t)stream, ptrs)) return rc;
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
     a.action = action; a.q_in = q; a.grad_q = grad_q; a.grad_qmin = grad_qmin; a.grad_action = grad_action; a.partial = workspace;
     hipStream_t s = (hipStream_t)stream;
     if (rows) {

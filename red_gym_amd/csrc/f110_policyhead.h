@@ -24,6 +24,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#pragma clang fp contract(off)
+
 namespace f110 {
 
 constexpr int PH_THREADS = 256;
@@ -104,7 +106,6 @@ __device__ inline void policyhead_stage(const PolicyheadArgs &a, float *lw, int 
     }
 }
 
-#if defined(F110_UNIT_POLICY)
 // grid: min(tiles, PH_MAX_GRID); dynamic LDS of 128 T kc bytes
 template <int T, bool F64>
 static __global__ __launch_bounds__(PH_THREADS) void policyhead_forward_kernel(PolicyheadArgs a)
@@ -323,6 +324,5 @@ static __global__ __launch_bounds__(PH_THREADS) void policyhead_reduce_kernel(Po
         if (gb) gb[jj] = acc;
     }
 }
-#endif
 
 } // namespace f110

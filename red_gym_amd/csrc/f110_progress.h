@@ -4,7 +4,8 @@
 // the HOST computed with NumPy (red_gym_amd/progress.py): the device evaluates neither the sqrt of a segment nor an atan2.
 // fp64, plain mul/add in the order DESIGN.md section 3 fixes; the tests demand `==` of a NumPy checker for every output.
 #pragma once
-#include "f110_kernels.h"
+#include "f110_bounds.h"
+#include "f110_device.h"
 #include "f110_planner.h"
 
 #pragma clang fp contract(off)
@@ -30,7 +31,6 @@ struct ProgressArgs {
     uint32_t *dev_err;
 };
 
-#if defined(F110_UNIT_CONSUMERS)
 static __global__ __launch_bounds__(256) void progress_kernel(ProgressArgs a)
 {
     const int car = blockIdx.x * blockDim.x + threadIdx.x;
@@ -111,6 +111,5 @@ static __global__ __launch_bounds__(256) void progress_kernel(ProgressArgs a)
     }
     a.s[car] = s; a.d[car] = d; a.heading_error[car] = e; a.delta[car] = delta; a.seg[car] = seg;
 }
-#endif
 
 } // namespace f110

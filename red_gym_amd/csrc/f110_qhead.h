@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#pragma clang fp contract(off)
+
 namespace f110 {
 
 constexpr int QH_THREADS = 256;
@@ -53,7 +55,6 @@ struct QheadArgs {
 // floats of one (critic, slice) in the workspace: grad_w_act [H][A], grad_b1 [H], grad_w2 [H], grad_b2
 __host__ __device__ inline size_t qhead_partial_floats(int H, int A) { return (size_t)H * (size_t)(A + 2) + 1; }
 
-#if defined(F110_UNIT_POLICY)
 // Units j0 .. j0 + hc - 1 of critic c in LDS; units past H are zeros.
 __device__ inline void qhead_stage(const QheadArgs &a, float *lw, int c, int j0, int tid)
 {
@@ -381,6 +382,5 @@ static __global__ __launch_bounds__(QH_THREADS) void qhead_reduce_kernel(QheadAr
         a.grad_b2[c][0] = acc;
     }
 }
-#endif
 
 } // namespace f110

@@ -11,27 +11,16 @@
 //   replay_gather_kernel   one wave per (sample, frame, 4 rows): bits back to uint8 (4 pixels = one 4-byte store per lane) or fp32
 //   replay_locate_kernel   one lane per index: where the gather would read, for consumers that read the bits themselves (f110_bitconv.h)
 #pragma once
-#include "f110_kernels.h"
+#include "../../include/f110_hip.h" // F110_REPLAY_TRIES
+#include "f110_bounds.h"
+#include "f110_replay_bits.h"
+
+#pragma clang fp contract(off)
 
 namespace f110 {
 
 constexpr int REPLAY_THREADS = 256;
 constexpr int REPLAY_ROWS = 16;              // rows of a frame one workgroup of the gather unpacks (4 per wave)
-constexpr int REPLAY_MAX_DIM = 16384;        // rows, cols: the kernels count a frame's 16-pixel chunks in 32 bits
-
-__host__ __device__ inline int replay_words(int cols) { return (cols + 63) >> 6; }
-
-// 4 pixels -> 4 bits, bit i = (byte i == 255): a byte is 255 iff its low 7 bits carry into bit 7 and bit 7 is set; the four
-// bits 7 are gathered by one multiply (exponents 8 i + 7 (j + 1) are pairwise distinct: no carries, bits 28..31 = byte 0..3).
-__device__ inline unsigned replay_bits4(unsigned x)
-{
-    const unsigned m = ((x & 0x7f7f7f7fu) + 0x01010101u) & x & 0x80808080u;
-    return ((m >> 7) * 0x10204080u) >> 28;
-}
-__device__ inline unsigned replay_bits16(uint4 v)
-{
-    return replay_bits4(v.x) | (replay_bits4(v.y) << 4) | (replay_bits4(v.z) << 8) | (replay_bits4(v.w) << 12);
-}
 
 // One image [rows, cols] -> [rows, words] as 16-bit pieces, by the `nthr` threads of a workgroup.  Piece u = row * ch + c holds
 // pixels 16 c .. 16 c + 15 of its row (ch = 4 * words; pieces beyond the row are the zero padding).  `img` is 16-byte aligned.
@@ -191,7 +180,6 @@ struct ReplayPackArgs {
     int rows, cols;
 };
 
-#if defined(F110_UNIT_CONSUMERS)
 static __global__ __launch_bounds__(REPLAY_THREADS) void replay_push_kernel(ReplayPushArgs a)
 {
     const ReplayRing &g = a.ring;
@@ -318,6 +306,5 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_unpack_kernel(Re
                           out + (i * (size_t)a.rows + (size_t)row) * (size_t)a.cols, lane);
     }
 }
-#endif
 
 } // namespace f110

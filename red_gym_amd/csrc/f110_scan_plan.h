@@ -16,6 +16,7 @@ constexpr int WAVE = 64;
 constexpr int SCAN_WAVES = 2;   // cars per workgroup, one wavefront each (one-car workgroups: profiles/r05_one_wave_groups.txt)
 constexpr int SCAN_THREADS = SCAN_WAVES * WAVE;
 constexpr int SCAN_MAX_STAGES = 8, SCAN_MAX_LOG2W = 3;
+constexpr int MAX_CHUNKS = 64; // beams are handed out in chunks of 64 (num_beams <= 4096)
 
 // one stage of a scan launch's wave -> car mapping: `cars` cars (< 0: "*", the remaining cars) at 2^lg waves each
 struct StageSpec { int cars, lg; };

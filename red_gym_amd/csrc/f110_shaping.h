@@ -7,7 +7,9 @@
 // depends on another.  The neighbours of the collision test are read by the first lanes and reduced by a ballot.
 // fp64, plain mul/add in the order DESIGN.md section 3 fixes; the tests demand `==` of a NumPy checker for every output.
 #pragma once
-#include "f110_kernels.h"
+#include "../../include/f110_hip.h" // f110_shaping_config
+#include "f110_bounds.h"
+#include "f110_device.h"
 
 #pragma clang fp contract(off)
 
@@ -43,7 +45,6 @@ __device__ inline int shaping_pixel(double origin, double v, double scale, int c
     return (int)p;
 }
 
-#if defined(F110_UNIT_CONSUMERS)
 static __global__ __launch_bounds__(64 * SHAPING_WAVES) void shaping_kernel(ShapingArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -151,6 +152,5 @@ static __global__ __launch_bounds__(64 * SHAPING_WAVES) void shaping_kernel(Shap
         if (a.t_seen) a.t_seen[env] = a.current_time[env];
     }
 }
-#endif
 
 } // namespace f110

@@ -1,7 +1,34 @@
-// f110_step.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_internal.h for the units.
-#define F110_UNIT_STEP
-#define F110_UNIT_NOISE  // (the per-env noise rows are produced by a launch of the step)
-#include "f110_internal.h"
+// f110_step.hip -- part of the C ABI (include/f110_hip.h) over the gfx950 kernels; see f110_common.h for the units.
+// The kernels of one batched env step on gfx950, in launch order:
+//   dynamics_kernel   (lane per car)        RaceCar.update_pose minus the scan (+ reset)
+//   scan_kernel       (wave per car)        ScanSimulator2D.scan + noise + iTTC
+//   env_kernel        (lane per env)        GJK, collision flags, iTTC state update, lap timing, done, autoreset
+// and, when A > 1, in place of env_kernel:
+//   post_scan_kernel  (lane per env | 4 lanes per car pair)  env_kernel's work beside opp_setup_body \ RaceCar.ray_cast_agents
+//   opp_apply_kernel  (wave per car)                                                                  /
+// plus small function-level kernels used by the parity entry points.
+#include "f110_handle.h"
+#include "f110_scan.h"
+#include "f110_env.h"
+#include "f110_mirrors.h"
+#include "f110_noise_kernels.h" // (the per-env noise rows are produced by a launch of the step)
+
+// scratch of the opponent ray cast: allocated when the handle is created (f110_create, f110_handle.hip), never by the entry point f110_step().  It lives in this
+// unit because OppPair does (f110_opponents.h, beside opp_apply_kernel)
+int alloc_opp_pairs(f110_handle *h)
+{
+    if (h->cfg.num_agents < 2) return F110_OK;
+    const size_t n = (size_t)h->cfg.num_envs * h->cfg.num_agents * (h->cfg.num_agents - 1);
+    DevBuf<OppPair> pairs;
+    DevBuf<uint8_t> was_pending;
+    HIP_TRY(pairs.alloc(n));
+    HIP_TRY(hipMemset(pairs.get(), 0, n * sizeof(OppPair)));
+    HIP_TRY(was_pending.alloc((size_t)h->cfg.num_envs));
+    HIP_TRY(hipMemset(was_pending.get(), 0, (size_t)h->cfg.num_envs));
+    h->d_opp_pairs = std::move(pairs);
+    h->d_was_pending = std::move(was_pending);
+    return F110_OK;
+}
 
 // ---------------------------------------------------------------- launches
 // Every kernel of the step path goes through emit(): launched at once on a stream (eager, or inside somebody's stream

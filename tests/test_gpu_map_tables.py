@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 import oracle  # noqa: E402  (test infrastructure)
 
-# Rank tiers of a cell (red_gym_amd/csrc/f110_kernels.h, LUT_LDS / LDS_RANKS / CODE_ESC): ranks 0 .. LDS_RANKS-1 are
+# Rank tiers of a cell (red_gym_amd/csrc/f110_map.h, LUT_LDS / LDS_RANKS / CODE_ESC): ranks 0 .. LDS_RANKS-1 are
 # LDS byte offsets, ranks up to CODE_ESC-1 go through the far marker to the global LUT, ranks >= CODE_ESC escape to the
 # fp64 table.  SCAN_BLOCK_WORDS: words of the presence bitmap per rank block (f110_mapgen.h); rank_scan_sums_kernel
 # walks the block sums in chunks of 64.
@@ -282,7 +282,7 @@ def test_scans_over_far_and_escape_cells(which, res, theta):
 
 # ---------------------------------------------------------------- shape limits and refusals
 def _rows_padded(H):
-    return ((H + 2 + 7) >> 3) << 3        # map_rows_padded (f110_kernels.h)
+    return ((H + 2 + 7) >> 3) << 3        # map_rows_padded (f110_map.h)
 
 
 def test_strip_addressing_limits(eng):
