@@ -463,6 +463,9 @@ int f110_progress_update(f110_handle *h, void *stream);
  * nothing of it is written.  (3) else the terms above (t_seen[env] < 0, "no update yet": with (x0, y0) = (x, y)); then
  * prev_xy = (x, y), t_seen = current_time.  The step in which an env reports done is paid with its terminal pose.
  * The caller renders the new scan's bitmap INTO THE SAME buffer after the update, on the same stream.
+ * The image is bound in one of two forms, with the same results: bytes (bitmap, f110_bitmap_render's output) or bits (bitmap_bits,
+ * f110_bitmap_render_bits' output = the replay ring's frame format: [B, rows, ceil(cols / 64)] uint64, bit k of word w of a row =
+ * (pixel[64 w + k] == 255), bits beyond cols 0).  f110_shaping_bind: exactly one of the two is not NULL, else F110_E_INVALID.
  * f110_shaping_validate: host only.  F110_E_INVALID for rows or cols < 1, agent outside 0..num_agents-1, neighborhood < 0,
  * clip_max < 0, a scalar that is not finite, max_lane_halfwidth <= 0.
  * f110_shaping_install: cfg NULL removes the shaper; a refused cfg installs nothing and keeps what was there.  Install and
@@ -480,7 +483,7 @@ typedef struct {
     double w_collision, w_progress, w_centering; /* -100.0, 10.0, 2.0 */
 } f110_shaping_config;
 typedef struct {
-    const uint8_t *bitmap;      /* [B, rows, cols] in: the image of the previous step's scan */
+    const uint8_t *bitmap;      /* [B, rows, cols] in: the image of the previous step's scan (NULL: bitmap_bits is bound) */
     double *collision_term;     /* [B] */
     double *progress_term;      /* [B] */
     double *centering_term;     /* [B] */
@@ -488,6 +491,7 @@ typedef struct {
     uint8_t *collided;          /* [B] */
     double *prev_xy;            /* [B,2] state: position at the env's previous update */
     double *t_seen;             /* [B] state: current_time at the env's previous update; start at -1 (no clock is negative) */
+    const uint64_t *bitmap_bits; /* [B, rows, ceil(cols / 64)] in: the same image as bits, 16-byte aligned (NULL: bitmap is bound) */
 } f110_shaping_buffers;
 int f110_shaping_validate(const f110_shaping_config *cfg, int32_t num_agents);
 int f110_shaping_install(f110_handle *h, const f110_shaping_config *cfg);
@@ -568,7 +572,8 @@ int f110_pathfollow_update(f110_handle *h, void *stream);
  * a new f110_replay_bind.  f110_shaping_install(NULL), or one with another image size, removes the buffer too.  Install,
  * removal and bind move the launch epoch.
  * f110_replay_update: the push, two kernels on `stream` behind f110_shaping_update and the render of the new bitmap; no
- * allocation, no synchronisation (capturable).
+ * allocation, no synchronisation (capturable).  Behind a shaper bound to bitmap_bits the frame is copied as it is (it is the
+ * ring's format); installing the shaper again with the same image size in the other form keeps the buffer.
  * f110_replay_draw: n indices uniform over the valid transitions, no synchronisation.  Attempt k < F110_REPLAY_TRIES of draw j
  * (j counts from first_draw) takes z = splitmix64(seed + 0x9E3779B97F4A7C15 * (1 + j * F110_REPLAY_TRIES + k)) and the candidate
  * mulhi64(z, stored * B), stored = min(count, T); candidate / B = age (0: the newest push), candidate % B = env; the first
@@ -828,6 +833,10 @@ int f110_check_done(f110_handle *h, const double *poses, const double *start_pos
 int f110_shaping_terms(const f110_shaping_config *cfg, const uint8_t *bitmaps, const double *xy, const double *prev_xy,
                        int32_t n, double *collision_term, double *progress_term, double *centering_term, double *total,
                        uint8_t *collided, void *stream);
+/* The same from images held as bits: packed [n, rows, ceil(cols / 64)] uint64 (f110_replay_pack's, f110_bitmap_render_bits'). */
+int f110_shaping_terms_bits(const f110_shaping_config *cfg, const uint64_t *packed, const double *xy, const double *prev_xy,
+                            int32_t n, double *collision_term, double *progress_term, double *centering_term, double *total,
+                            uint8_t *collided, void *stream);
 /* The follower's two halves for n independent cases, stateless, no episode logic (no handle; cfg host, cfg->agent is not read;
  * all arrays dev).  f110_pathfollow_decode: raw actions [n,16] and poses [n,3] = (x, y, yaw) -> paths [n,8,2].
  * f110_pathfollow_mpc: paths [n,8,2] and velocities [n,2] = (vx, vy) -> dists [n,8], ref_traj [n, horizon + 1, 4], accel [n,2],
@@ -875,6 +884,14 @@ void f110_bitmap_destroy(f110_bitmap *b);
  * Enqueued on `stream`; no allocation, no synchronisation. */
 int f110_bitmap_render(f110_bitmap *b, const void *scans, int32_t scans_f64, int64_t n, int64_t stride,
                        uint8_t *out, void *stream);
+/* The same images as one bit per pixel: out dev uint64 [n, rows, words], words = ceil(cols / 64), 16-byte aligned.  Bit k of
+ * word w of row y is set iff f110_bitmap_render would write draw_value at (y, 64 w + k) -- the centre marker of a FILL image is
+ * background: 0 -- and bits at columns >= cols are 0.  All three draw modes; `channels` plays no part.  The kernel is
+ * f110_bitmap_render's up to its last phase, which stores the 1-bit image it drew instead of expanding it to grey bytes.  With
+ * bg_value 0 and draw_value 255 this is the replay ring's frame format (f110_replay_pack of the byte image).  Enqueued on
+ * `stream`; no allocation, no synchronisation. */
+int f110_bitmap_render_bits(f110_bitmap *b, const void *scans, int32_t scans_f64, int64_t n, int64_t stride,
+                            uint64_t *out, void *stream);
 /* Function-level view of the renderer's first stage (parity tests): the integer points the reference computes
  * at lidar.py:63-73 and hands to cv2.fillPoly / polylines / line -- points dev int32 [n, T, 2] = (x, y) of
  * np.rint(center + scaling_factor * scan[indices] * {cos, sin}(angles)).astype(int), center = (rows//2, cols//2). */

@@ -60,7 +60,7 @@ class ShapingConfig(C.Structure):
                 ('w_centering', C.c_double)]
 
 
-SHAPING_FIELDS = ['bitmap', 'collision_term', 'progress_term', 'centering_term', 'total', 'collided', 'prev_xy', 't_seen']
+SHAPING_FIELDS = ['bitmap', 'collision_term', 'progress_term', 'centering_term', 'total', 'collided', 'prev_xy', 't_seen', 'bitmap_bits']
 
 
 class ShapingBuffers(C.Structure):
@@ -194,6 +194,7 @@ SYMBOLS = {
     'f110_shaping_bind': [_VP, C.POINTER(ShapingBuffers)],
     'f110_shaping_update': [_VP, _VP],
     'f110_shaping_terms': [C.POINTER(ShapingConfig), _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_shaping_terms_bits': [C.POINTER(ShapingConfig), _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_pathfollow_validate': [C.POINTER(PathFollowConfig), _I32],
     'f110_pathfollow_install': [_VP, C.POINTER(PathFollowConfig)],
     'f110_pathfollow_bind': [_VP, C.POINTER(PathFollowBuffers)],
@@ -243,6 +244,7 @@ SYMBOLS = {
     'f110_bitmap_create': [C.POINTER(BitmapConfig), _VP, _VP, _VP, C.POINTER(_VP)],
     'f110_bitmap_destroy': [_VP],
     'f110_bitmap_render': [_VP, _VP, _I32, _I64, _I64, _VP, _VP],
+    'f110_bitmap_render_bits': [_VP, _VP, _I32, _I64, _I64, _VP, _VP],
     'f110_bitmap_points': [_VP, _VP, _I32, _I64, _I64, _VP, _VP],
     'f110_scan_occupancy': [_VP, _I32, _I64, _I64, _I32, _VP, _VP, _D, _D, _D, _I32, _VP, _VP],
 }

@@ -20,11 +20,13 @@ class Consumer(object):
         self.on, self.buf, self.info = False, None, {}
         self._update = getattr(eng.lib, 'f110_%s_update' % self.NAME)
 
-    def _bind(self, buf, struct):
-        """The tensors `buf` become the buffers the kernel writes: one struct of pointers, handed to the library once."""
+    def _bind(self, buf, struct, fields=None):
+        """The tensors `buf` become the buffers the kernel writes: one struct of pointers, handed to the library once.
+        `fields`: struct field -> name in `buf` where the two differ, None for a field that stays NULL."""
         ptrs = struct()
         for name, _ in struct._fields_:
-            setattr(ptrs, name, buf[name].data_ptr())
+            key = (fields or {}).get(name, name)
+            setattr(ptrs, name, None if key is None else buf[key].data_ptr())
         torch.cuda.synchronize(self.eng.device)
         _lib.check(getattr(self.eng.lib, 'f110_%s_bind' % self.NAME)(self.eng._h, C.byref(ptrs)))
         self.buf, self.info = buf, {k: buf[name] for k, name in self.INFO.items()}
@@ -47,6 +49,10 @@ class Consumer(object):
                 self.buf[name].copy_(sd[k])
         else:
             self.restart()
+
+    def state_keys(self):
+        """Every state_dict key that is this consumer's, whether it would load it or not."""
+        return set(self.STATE)
 
     def on_load_state_dict(self, sd):
         """What F110VecEnv.load_state_dict asks of a consumer that is `on`."""

@@ -37,7 +37,8 @@ struct BitmapArgs {
     int T;
     int rows, cols, channels, mode, bg, draw, draw_center;
     double scale;
-    unsigned char *out;      // [n, rows, cols(, channels)]
+    unsigned char *out;      // [n, rows, cols(, channels)], or
+    unsigned long long *out_bits; // [n, rows, ceil(cols / 64)]: the 1-bit image itself (f110_bitmap_render_bits); NULL: grey bytes
     int S;                   // words per bit-plane row (cols/32 rounded up, made odd)
     int qcap;                // segment records held in LDS at a time (bm_queue_cap)
 };
@@ -285,6 +286,16 @@ __device__ inline void bm_store16(void *p, unsigned a, unsigned b, unsigned c, u
     if (STREAM) __builtin_nontemporal_store(v, reinterpret_cast<bm_v4u *>(p));
     else *reinterpret_cast<bm_v4u *>(p) = v;
 }
+
+// The 16-byte stores of the bits form (f110_bitmap_render_bits): cached -- the shaper, the replay push and the policy's stem read
+// the bits right after, and the step was measured in this form.  -DF110_BM_BITS_STREAM=1 builds the non-temporal variant: the
+// render alone is 0.2-2.7 % faster with it, the consumers behind it are not measured yet (tools/time_bits.py --variant,
+// profiles/r15_bitmap_bits.txt).
+#if defined(F110_BM_BITS_STREAM) && F110_BM_BITS_STREAM
+constexpr bool BM_BITS_STREAM = true;
+#else
+constexpr bool BM_BITS_STREAM = false;
+#endif
 
 // 4 pixel bits -> 4 bytes, each bg (bit 0) or draw (bit 1); cols = bg | draw << 8
 __device__ inline unsigned bm_expand4(unsigned nib, unsigned cols2)
@@ -662,7 +673,8 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
     const size_t img_bytes = (size_t)rows * cols * ch;
     unsigned char *dst = a.out + (size_t)img * img_bytes;
     const unsigned cols2 = ((unsigned)a.bg & 255u) | ((unsigned)a.draw & 255u) << 8;
-    const bool use_tab = ch == 1 && (cols & 15) == 0; // (the layout reserves the table's 2 KB)
+    const bool as_bits = a.out_bits != nullptr;       // (launch-uniform: the bit plane goes out as it is, no grey levels)
+    const bool use_tab = !as_bits && ch == 1 && (cols & 15) == 0; // (the layout reserves the table's 2 KB)
     uint2 *tab = reinterpret_cast<uint2 *>(recs); // (the records are dead from here on)
     if (use_tab && tid < 256) tab[tid] = make_uint2(bm_expand4((unsigned)tid & 15u, cols2), bm_expand4((unsigned)tid >> 4, cols2));
     if (mode == BM_FILL) {
@@ -707,6 +719,32 @@ static __global__ __launch_bounds__(BM_THREADS) __attribute__((amdgpu_waves_per_
             if (k < T) { const double2 c = cs[k]; pts[k] = bm_point_at(a.scale, bm_staged_range(a, stage + ((it + 1) & 1) * stage_words, k), c.x, c.y, cx, cy); }
         }
     }
+    // ---- bits form: the plane's valid words go out as they are, 1/8 of the bytes of the one-channel image.  A row of the
+    // output is ceil(cols / 64) 64-bit words = U 32-bit ones, of which the plane holds W (its pitch S is W or W + 1: the
+    // padding word never leaves LDS); the parity pass fills a row's last word to its end, so the tail beyond `cols` is masked
+    // here, and with W odd the upper half of the row's last 64-bit word is written as 0.
+    if (as_bits) {
+        const int W = (cols + 31) >> 5, U = 2 * ((cols + 63) >> 6);
+        unsigned *dst32 = reinterpret_cast<unsigned *>(a.out_bits) + (size_t)img * (size_t)rows * (size_t)U;
+        if ((cols & 127) == 0) {
+            // (rows of whole 16-byte pieces, W == U and no tail: the wave's lanes write consecutive pieces)
+            const int cpr = cols >> 7, chunks = rows * cpr;
+            for (int c = tid; c < chunks; c += BM_THREADS) {
+                const int y = c / cpr, h = c - y * cpr;
+                const unsigned *src = anyp + __mul24(y, S) + 4 * h;
+                bm_store16<BM_BITS_STREAM>(dst32 + 4 * (size_t)c, src[0], src[1], src[2], src[3]);
+            }
+        } else {
+            const unsigned tail = (cols & 31) ? (1u << (cols & 31)) - 1u : ~0u;
+            const int units = rows * U;
+            for (int u = tid; u < units; u += BM_THREADS) {
+                const int y = u / U, w = u - y * U;
+                unsigned v = w < W ? anyp[__mul24(y, S) + w] : 0u;
+                if (w == W - 1) v &= tail;
+                dst32[u] = v;
+            }
+        }
+    } else
     // ---- stream the image out: grey levels and channels are expanded here (the only HBM write)
     // One channel: 8 pixel bits -> 8 grey bytes through a 256-entry table (2 KB, in the segment records' place: they are
     // dead after the walk), built by the first 256 threads.  Two ds_read_b64 per 16-byte store replace the twelve VALU

@@ -70,21 +70,22 @@ extern "C" int f110_bitmap_create(const f110_bitmap_config *cfg, const int32_t *
     return F110_OK;
 }
 
-extern "C" int f110_bitmap_render(f110_bitmap *b, const void *scans, int32_t scans_f64, int64_t n, int64_t stride,
-                                  uint8_t *out, void *stream)
+// f110_bitmap_render and f110_bitmap_render_bits (`who`): exactly one of `out` / `out_bits` is the launch's output
+static int bitmap_launch(const char *who, f110_bitmap *b, const void *scans, int32_t scans_f64, int64_t n, int64_t stride,
+                         uint8_t *out, uint64_t *out_bits, void *stream)
 {
-    if (!b || n < 0) return fail(F110_E_INVALID, "f110_bitmap_render: bad arguments");
+    if (!b || n < 0) return fail(F110_E_INVALID, "%s: bad arguments", who);
     if (n == 0) return F110_OK;
-    if (!scans || !out) return fail(F110_E_INVALID, "f110_bitmap_render: null pointer");
-    if (stride < b->cfg.num_beams || n > 0x7fffffff) return fail(F110_E_INVALID, "f110_bitmap_render: stride %lld < num_beams or n too large", (long long)stride);
-    if ((uintptr_t)out % 16) return fail(F110_E_INVALID, "f110_bitmap_render: out must be 16-byte aligned");
-    if (int rc = check_current_device(b->cfg.device, "f110_bitmap_render")) return rc;
+    if (!scans || (!out && !out_bits)) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (stride < b->cfg.num_beams || n > 0x7fffffff) return fail(F110_E_INVALID, "%s: stride %lld < num_beams or n too large", who, (long long)stride);
+    if (((uintptr_t)out | (uintptr_t)out_bits) % 16) return fail(F110_E_INVALID, "%s: out must be 16-byte aligned", who);
+    if (int rc = check_current_device(b->cfg.device, who)) return rc;
     BitmapArgs a;
     a.scans = scans; a.is_f64 = scans_f64 != 0; a.stride = stride; a.n = (int)n;
     a.idx = b->d_idx.get(); a.cosv = b->d_cos.get(); a.sinv = b->d_sin.get(); a.T = b->cfg.target_beam_count;
     a.rows = b->cfg.rows; a.cols = b->cfg.cols; a.channels = b->cfg.channels; a.mode = b->cfg.draw_mode;
     a.bg = b->cfg.bg_value; a.draw = b->cfg.draw_value; a.draw_center = b->cfg.draw_center;
-    a.scale = b->cfg.scaling_factor; a.out = out; a.S = b->S; a.qcap = bm_queue_cap(a.T, a.mode);
+    a.scale = b->cfg.scaling_factor; a.out = out; a.out_bits = (unsigned long long *)out_bits; a.S = b->S; a.qcap = bm_queue_cap(a.T, a.mode);
     const char *grid_env = getenv("F110_BM_GRID"); // test hook (test_gpu_bitmap.py): workgroups of the launch (read per call)
     // fetch-ahead shape: as many workgroups as the device runs at once, each looping over images; else one per image
     const int64_t grid = !bm_fetch_ahead(a.mode, a.channels) ? n : std::min<int64_t>(n, grid_env && atoi(grid_env) > 0 ? atoi(grid_env) : b->resident[a.is_f64]);
@@ -92,6 +93,18 @@ extern "C" int f110_bitmap_render(f110_bitmap *b, const void *scans, int32_t sca
     HIP_TRY(hipLaunchKernel(bitmap_fn(b->lds[a.is_f64], a.mode, a.channels), dim3((unsigned)grid), dim3(BM_THREADS), params, b->lds[a.is_f64], (hipStream_t)stream));
     HIP_TRY(hipGetLastError());
     return F110_OK;
+}
+
+extern "C" int f110_bitmap_render(f110_bitmap *b, const void *scans, int32_t scans_f64, int64_t n, int64_t stride,
+                                  uint8_t *out, void *stream)
+{
+    return bitmap_launch("f110_bitmap_render", b, scans, scans_f64, n, stride, out, nullptr, stream);
+}
+
+extern "C" int f110_bitmap_render_bits(f110_bitmap *b, const void *scans, int32_t scans_f64, int64_t n, int64_t stride,
+                                       uint64_t *out, void *stream)
+{
+    return bitmap_launch("f110_bitmap_render_bits", b, scans, scans_f64, n, stride, nullptr, out, stream);
 }
 
 extern "C" int f110_bitmap_points(f110_bitmap *b, const void *scans, int32_t scans_f64, int64_t n, int64_t stride,

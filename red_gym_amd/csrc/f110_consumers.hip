@@ -383,8 +383,10 @@ extern "C" int f110_shaping_install(f110_handle *h, const f110_shaping_config *c
 extern "C" int f110_shaping_bind(f110_handle *h, const f110_shaping_buffers *b)
 {
     if (!h || !b) return fail(F110_E_INVALID, "f110_shaping_bind: null argument");
-    if (!b->bitmap || !b->collision_term || !b->progress_term || !b->centering_term || !b->total || !b->collided || !b->prev_xy || !b->t_seen)
-        return fail(F110_E_INVALID, "f110_shaping_bind: a buffer is NULL (all eight are required)");
+    if (!b->collision_term || !b->progress_term || !b->centering_term || !b->total || !b->collided || !b->prev_xy || !b->t_seen)
+        return fail(F110_E_INVALID, "f110_shaping_bind: a buffer is NULL (the seven behind the image are required)");
+    if ((b->bitmap != nullptr) == (b->bitmap_bits != nullptr))
+        return fail(F110_E_INVALID, "f110_shaping_bind: exactly one of bitmap and bitmap_bits is bound");
     h->shaping.bufs = *b;
     h->shaping.bound = true;
     h->epoch++;
@@ -394,7 +396,9 @@ extern "C" int f110_shaping_bind(f110_handle *h, const f110_shaping_buffers *b)
 static int launch_shaping(const ShapingArgs &a, hipStream_t stream)
 {
     if (a.n == 0) return F110_OK;
-    hipLaunchKernelGGL(shaping_kernel, dim3((a.n + SHAPING_WAVES - 1) / SHAPING_WAVES), dim3(64 * SHAPING_WAVES), 0, stream, a);
+    const dim3 grid((a.n + SHAPING_WAVES - 1) / SHAPING_WAVES), block(64 * SHAPING_WAVES);
+    if (a.bitmap_bits) hipLaunchKernelGGL(shaping_kernel<true>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(shaping_kernel<false>, grid, block, 0, stream, a);
     HIP_TRY(hipGetLastError());
     return F110_OK;
 }
@@ -406,7 +410,7 @@ extern "C" int f110_shaping_update(f110_handle *h, void *stream)
     if (int rc = update_ready(h, "f110_shaping_update", "shaper", "shaping", s.on, s.bound)) return rc;
     ShapingArgs a;
     memset(&a, 0, sizeof(a));
-    a.cfg = s.cfg; a.bitmap = s.bufs.bitmap; a.n = h->cfg.num_envs;
+    a.cfg = s.cfg; a.bitmap = s.bufs.bitmap; a.bitmap_bits = s.bufs.bitmap_bits; a.n = h->cfg.num_envs;
     a.xy = h->bufs.state + 7 * (size_t)s.cfg.agent; a.xy_stride = 7LL * h->cfg.num_agents;
     a.current_time = h->bufs.current_time; a.timestep = h->cfg.timestep;
     a.prev_in = s.bufs.prev_xy; a.prev_out = s.bufs.prev_xy; a.t_seen = s.bufs.t_seen;
@@ -415,22 +419,39 @@ extern "C" int f110_shaping_update(f110_handle *h, void *stream)
     return launch_shaping(a, (hipStream_t)stream);
 }
 
+// f110_shaping_terms and f110_shaping_terms_bits (`who`): exactly one of `bitmaps` / `packed` is the images
+static int shaping_terms(const char *who, const f110_shaping_config *cfg, const uint8_t *bitmaps, const uint64_t *packed, const double *xy,
+                         const double *prev_xy, int32_t n, double *collision_term, double *progress_term, double *centering_term,
+                         double *total, uint8_t *collided, void *stream)
+{
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    f110_shaping_config c = *cfg;
+    c.agent = 0;
+    if (int rc = f110_shaping_validate(&c, 1)) return rc;
+    if (n < 0 || (!bitmaps && !packed) || !xy || !prev_xy || !collision_term || !progress_term || !centering_term || !total || !collided)
+        return fail(F110_E_INVALID, "%s: bad arguments", who);
+    ShapingArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cfg = c; a.bitmap = bitmaps; a.bitmap_bits = packed; a.n = n; a.xy = xy; a.xy_stride = 2; a.prev_in = prev_xy;
+    a.collision_term = collision_term; a.progress_term = progress_term; a.centering_term = centering_term; a.total = total;
+    a.collided = collided;
+    return launch_shaping(a, (hipStream_t)stream);
+}
+
 extern "C" int f110_shaping_terms(const f110_shaping_config *cfg, const uint8_t *bitmaps, const double *xy, const double *prev_xy,
                                   int32_t n, double *collision_term, double *progress_term, double *centering_term, double *total,
                                   uint8_t *collided, void *stream)
 {
-    if (!cfg) return fail(F110_E_INVALID, "f110_shaping_terms: null config");
-    f110_shaping_config c = *cfg;
-    c.agent = 0;
-    if (int rc = f110_shaping_validate(&c, 1)) return rc;
-    if (n < 0 || !bitmaps || !xy || !prev_xy || !collision_term || !progress_term || !centering_term || !total || !collided)
-        return fail(F110_E_INVALID, "f110_shaping_terms: bad arguments");
-    ShapingArgs a;
-    memset(&a, 0, sizeof(a));
-    a.cfg = c; a.bitmap = bitmaps; a.n = n; a.xy = xy; a.xy_stride = 2; a.prev_in = prev_xy;
-    a.collision_term = collision_term; a.progress_term = progress_term; a.centering_term = centering_term; a.total = total;
-    a.collided = collided;
-    return launch_shaping(a, (hipStream_t)stream);
+    return shaping_terms("f110_shaping_terms", cfg, bitmaps, nullptr, xy, prev_xy, n, collision_term, progress_term, centering_term, total,
+                         collided, stream);
+}
+
+extern "C" int f110_shaping_terms_bits(const f110_shaping_config *cfg, const uint64_t *packed, const double *xy, const double *prev_xy,
+                                       int32_t n, double *collision_term, double *progress_term, double *centering_term, double *total,
+                                       uint8_t *collided, void *stream)
+{
+    return shaping_terms("f110_shaping_terms_bits", cfg, nullptr, packed, xy, prev_xy, n, collision_term, progress_term, centering_term,
+                         total, collided, stream);
 }
 
 // ---------------------------------------------------------------- path actions
@@ -711,8 +732,9 @@ extern "C" int f110_replay_update(f110_handle *h, void *stream)
     memset(&a, 0, sizeof(a));
     if (int rc = replay_ready(h, "f110_replay_update", a.ring)) return rc;
     const f110_handle::Replay &r = h->replay;
-    if ((uintptr_t)h->shaping.bufs.bitmap % 16) return fail(F110_E_INVALID, "f110_replay_update: the shaper's bitmap must be 16-byte aligned");
-    a.bitmap = h->shaping.bufs.bitmap; a.action_in = r.bufs.action_in; a.total = h->shaping.bufs.total; a.done = (const uint8_t *)h->bufs.done;
+    if (((uintptr_t)h->shaping.bufs.bitmap | (uintptr_t)h->shaping.bufs.bitmap_bits) % 16)
+        return fail(F110_E_INVALID, "f110_replay_update: the shaper's bitmap must be 16-byte aligned");
+    a.bitmap = h->shaping.bufs.bitmap; a.bitmap_bits = h->shaping.bufs.bitmap_bits; a.action_in = r.bufs.action_in; a.total = h->shaping.bufs.total; a.done = (const uint8_t *)h->bufs.done;
     a.current_time = h->bufs.current_time; a.timestep = h->cfg.timestep; a.chain_start = (const long long *)r.bufs.chain_start;
     a.t_seen = r.bufs.t_seen; a.last_valid = r.bufs.last_valid;
     hipLaunchKernelGGL(replay_push_kernel, dim3((unsigned)a.ring.n_envs), dim3(REPLAY_THREADS), 0, (hipStream_t)stream, a);

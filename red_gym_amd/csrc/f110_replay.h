@@ -5,7 +5,8 @@
 // counter `count`) writes frame slot c % (T + 1) and step slot c % T; its transition is (frame c - 1, action, reward, frame c,
 // done).  Nothing here takes a slot by value from the host: every kernel reads `count`, so a captured push replays correctly.
 //   replay_push_kernel     one workgroup per env: 16 pixels per lane in one 16-byte load, reduced to 16 bits in registers, one
-//                          2-byte store per lane -- a wave reads 1 KiB and writes 128 B, both contiguous
+//                          2-byte store per lane -- a wave reads 1 KiB and writes 128 B, both contiguous; behind a shaper that
+//                          holds its image as bits already (f110_bitmap_render_bits) the frame is copied, 16 bytes per lane
 //   replay_advance_kernel  one lane: count += 1, behind the push
 //   replay_draw_kernel     one lane per draw: splitmix64 candidates over the stored transitions, the first valid one wins
 //   replay_gather_kernel   one wave per (sample, frame, 4 rows): bits back to uint8 (4 pixels = one 4-byte store per lane) or fp32
@@ -141,9 +142,25 @@ __device__ inline bool replay_resolve(const ReplayRing &g, long long id, long lo
     return ok;
 }
 
+// One frame in the ring's format [rows * words] copied as it is, by the `nthr` threads of a workgroup: 16 bytes per access where
+// both frames start on a 16-byte boundary (`pairs`: an even word count, the arrays themselves are aligned), else 8.
+__device__ inline void replay_copy_frame(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, size_t n_words, int tid, int nthr)
+{
+    if ((n_words & 1) == 0) {
+        const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
+        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
+        const size_t n4 = n_words >> 1;
+#pragma unroll 4
+        for (size_t i = (size_t)tid; i < n4; i += (size_t)nthr) d4[i] = s4[i];   // (restrict: the unrolled loads go out together)
+        return;
+    }
+    for (size_t i = (size_t)tid; i < n_words; i += (size_t)nthr) dst[i] = src[i];
+}
+
 struct ReplayPushArgs {
     ReplayRing ring;
-    const uint8_t *bitmap;          // [n_envs, rows, cols] the shaper's image of the scan the step returned
+    const uint8_t *bitmap;          // [n_envs, rows, cols] the shaper's image of the scan the step returned, or (exactly one of the two)
+    const uint64_t *bitmap_bits;    // [n_envs, rows, words] the same image in the ring's own format
     const float *action_in;         // [n_envs, action_dim]
     const double *total;            // [n_envs] the shaper's reward
     const uint8_t *done;            // [n_envs]
@@ -189,8 +206,11 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_push_kernel(Repl
     if (count < 0) return;
     const long long fs = count % (g.steps + 1), ss = count % g.steps;
     F110_BCHK(fs >= 0 && fs <= g.steps && ss >= 0 && ss < g.steps, BT_REPLAY, g.dev_err);
-    replay_pack_image(a.bitmap + (size_t)env * (size_t)g.rows * (size_t)g.cols, g.rows, g.cols,
-                      reinterpret_cast<uint16_t *>(g.frame(fs, env)), tid, REPLAY_THREADS);
+    if (a.bitmap_bits)
+        replay_copy_frame(a.bitmap_bits + (size_t)env * g.frame_words(), g.frame(fs, env), g.frame_words(), tid, REPLAY_THREADS);
+    else
+        replay_pack_image(a.bitmap + (size_t)env * (size_t)g.rows * (size_t)g.cols, g.rows, g.cols,
+                          reinterpret_cast<uint16_t *>(g.frame(fs, env)), tid, REPLAY_THREADS);
     const size_t cell = (size_t)ss * (size_t)g.n_envs + (size_t)env;
     for (int k = tid; k < g.action_dim; k += REPLAY_THREADS)
         g.actions[cell * (size_t)g.action_dim + (size_t)k] = a.action_in[(size_t)env * (size_t)g.action_dim + (size_t)k];

@@ -5,6 +5,8 @@
 // centering term is loaded once, 64 pixels per load, a ballot of "pixel != 255" turns each 64-pixel chunk into a mask, and the
 // ends of the run of 255 around the car come from count-leading / count-trailing zeros on those masks -- no pixel load
 // depends on another.  The neighbours of the collision test are read by the first lanes and reduced by a ballot.
+// The image is bytes, or the renderer's bits (f110_bitmap_render_bits: bit k of word w of a row = pixel 64 w + k is 255): then the
+// mask of a 64-pixel chunk is the complemented word -- no byte loads, no ballot -- and a neighbour is one bit.
 // fp64, plain mul/add in the order DESIGN.md section 3 fixes; the tests demand `==` of a NumPy checker for every output.
 #pragma once
 #include "../../include/f110_hip.h" // f110_shaping_config
@@ -19,7 +21,8 @@ constexpr int SHAPING_WAVES = 4; // envs (= waves) per workgroup
 
 struct ShapingArgs {
     f110_shaping_config cfg;
-    const uint8_t *bitmap;       // [n, rows, cols] the image of the PREVIOUS step's scan
+    const uint8_t *bitmap;       // [n, rows, cols] the image of the PREVIOUS step's scan, or (exactly one of the two)
+    const uint64_t *bitmap_bits; // [n, rows, ceil(cols / 64)] the same image as bits
     const double *xy;            // pose of env e: (xy[e * xy_stride], xy[e * xy_stride + 1]) -- state + 7 * agent with stride 7 * A, or [n,2]
     long long xy_stride;
     int n;
@@ -45,6 +48,23 @@ __device__ inline int shaping_pixel(double origin, double v, double scale, int c
     return (int)p;
 }
 
+// The "not 255" mask `m` of columns b0 .. b0 + 63 of the centering row, folded into the two ends of the run around car_x.
+__device__ inline void shaping_run_ends(unsigned long long m, int b0, int car_x, int cols, int &stop_l, int &stop_r)
+{
+    if (b0 <= car_x) {
+        const int k = car_x - b0;                 // columns b0 .. car_x of this chunk
+        const unsigned long long ml = k >= 63 ? m : m & ((2ull << k) - 1ull);
+        if (ml) stop_l = b0 + 63 - __builtin_clzll(ml);
+    }
+    if (b0 + 63 >= car_x && stop_r == cols) {
+        const int k = car_x - b0;                 // columns car_x .. b0 + 63 of this chunk
+        const unsigned long long mr = k <= 0 ? m : m & (~0ull << k);
+        if (mr) stop_r = b0 + __builtin_ctzll(mr);
+    }
+}
+
+// BITS: the image is a.bitmap_bits (else a.bitmap)
+template <bool BITS>
 static __global__ __launch_bounds__(64 * SHAPING_WAVES) void shaping_kernel(ShapingArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -75,7 +95,9 @@ static __global__ __launch_bounds__(64 * SHAPING_WAVES) void shaping_kernel(Shap
     int hit = 0;
     const bool finite = __builtin_isfinite(x) && __builtin_isfinite(y);
     if (finite) {
-        const uint8_t *__restrict__ img = a.bitmap + (size_t)env * (size_t)c.rows * (size_t)c.cols;
+        const int words = (c.cols + 63) >> 6;
+        const uint8_t *__restrict__ img = BITS ? nullptr : a.bitmap + (size_t)env * (size_t)c.rows * (size_t)c.cols;
+        const uint64_t *__restrict__ bits = BITS ? a.bitmap_bits + (size_t)env * (size_t)c.rows * (size_t)words : nullptr;
         // collision (detect_collison): any neighbour of (px, py) inside the image equal to 255, the centre excluded.  Only
         // the part of the (2n+1)^2 window that lies inside the image is visited, so the trip count is bounded by the image.
         const int px = shaping_pixel(c.origin_x, x, c.scale, c.clip_max), py = shaping_pixel(c.origin_y, y, c.scale, c.clip_max);
@@ -92,7 +114,10 @@ static __global__ __launch_bounds__(64 * SHAPING_WAVES) void shaping_kernel(Shap
                 if (i < cells) {
                     const long long ny = wy0 + i / ww, nx = wx0 + i % ww;
                     F110_BCHK(nx >= 0 && nx < c.cols && ny >= 0 && ny < c.rows, BT_SHAPING, a.dev_err);
-                    h = !(nx == px && ny == py) && img[(size_t)ny * (size_t)c.cols + (size_t)nx] == 255;
+                    F110_BCHK(!BITS || (nx >> 6) < words, BT_SHAPING, a.dev_err);
+                    const bool on = BITS ? ((bits[(size_t)ny * (size_t)words + (size_t)(nx >> 6)] >> (nx & 63)) & 1ull) != 0ull
+                                         : img[(size_t)ny * (size_t)c.cols + (size_t)nx] == 255;
+                    h = !(nx == px && ny == py) && on;
                 }
                 if (vote(h) != 0ull) { hit = 1; break; }
             }
@@ -107,31 +132,35 @@ static __global__ __launch_bounds__(64 * SHAPING_WAVES) void shaping_kernel(Shap
         if (x > -1.0 && x < (double)c.cols && y > -1.0 && y < (double)c.rows) {
             const int car_x = (int)x, car_y = (int)y;
             F110_BCHK(car_x >= 0 && car_x < c.cols && car_y >= 0 && car_y < c.rows, BT_SHAPING, a.dev_err);
-            const uint8_t *__restrict__ row = img + (size_t)car_y * (size_t)c.cols;
             // stop_l: the last column <= car_x that is not 255 (-1: none); stop_r: the first column >= car_x that is not 255
             // (cols: none).  The reference's walks end there: left = stop_l + 1, right = stop_r - 1.
             int stop_l = -1, stop_r = c.cols;
-            for (int c0 = 0; c0 < c.cols; c0 += 256) {          // four independent 64-pixel loads in flight
-                uint8_t v[4];
+            if (BITS) {
+                const uint64_t *__restrict__ row = bits + (size_t)car_y * (size_t)words;
+                for (int w0 = 0; w0 < words; w0 += 4) {           // four independent loads in flight, the same in every lane
+                    uint64_t v[4];
 #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int col = c0 + 64 * j + lane;
-                    v[j] = col < c.cols ? row[col] : (uint8_t)0;   // beyond the row: not 255, the walk stops at the edge
+                    for (int j = 0; j < 4; j++) v[j] = w0 + j < words ? row[w0 + j] : 0ull;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const int b0 = 64 * (w0 + j);
+                        if (b0 >= c.cols) break;
+                        // beyond the row: not 255, the walk stops at the edge
+                        const unsigned long long m = ~v[j] | (c.cols - b0 < 64 ? ~0ull << (c.cols - b0) : 0ull);
+                        shaping_run_ends(m, b0, car_x, c.cols, stop_l, stop_r);
+                    }
                 }
+            } else {
+                const uint8_t *__restrict__ row = img + (size_t)car_y * (size_t)c.cols;
+                for (int c0 = 0; c0 < c.cols; c0 += 256) {          // four independent 64-pixel loads in flight
+                    uint8_t v[4];
 #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int b0 = c0 + 64 * j;
-                    const unsigned long long m = vote(v[j] != 255);
-                    if (b0 <= car_x) {
-                        const int k = car_x - b0;                 // columns b0 .. car_x of this chunk
-                        const unsigned long long ml = k >= 63 ? m : m & ((2ull << k) - 1ull);
-                        if (ml) stop_l = b0 + 63 - __builtin_clzll(ml);
+                    for (int j = 0; j < 4; j++) {
+                        const int col = c0 + 64 * j + lane;
+                        v[j] = col < c.cols ? row[col] : (uint8_t)0;   // beyond the row: not 255, the walk stops at the edge
                     }
-                    if (b0 + 63 >= car_x && stop_r == c.cols) {
-                        const int k = car_x - b0;                 // columns car_x .. b0 + 63 of this chunk
-                        const unsigned long long mr = k <= 0 ? m : m & (~0ull << k);
-                        if (mr) stop_r = b0 + __builtin_ctzll(mr);
-                    }
+#pragma unroll
+                    for (int j = 0; j < 4; j++) shaping_run_ends(vote(v[j] != 255), c0 + 64 * j, car_x, c.cols, stop_l, stop_r);
                 }
             }
             stop_r = stop_r > c.cols ? c.cols : stop_r;          // (a virtual column beyond the row stands for the edge)

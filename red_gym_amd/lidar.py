@@ -65,11 +65,10 @@ class LidarBitmap:
                                                C.byref(h)))
         self.h = h
 
-    def __call__(self, scans, out=None):
-        """scans: [N, num_beams] (or [num_beams]) float32 / float64 tensor on the renderer's device."""
+    def _batch(self, scans):
+        """The argument handling __call__ and bits share: (scans as given, the [n, num_beams] batch the kernel reads, single)."""
         if not torch.is_tensor(scans):
             scans = torch.as_tensor(np.asarray(scans, dtype=np.float64), device=self.device)
-        single = scans.dim() == 1
         s = scans.reshape(-1, scans.shape[-1])
         if s.dtype not in (torch.float32, torch.float64):
             s = s.to(torch.float64)
@@ -78,17 +77,34 @@ class LidarBitmap:
         if s.stride(-1) != 1:
             s = s.contiguous()
         assert s.shape[-1] == self.num_beams, 'scan length %d != %d' % (s.shape[-1], self.num_beams)
+        return scans, s, scans.dim() == 1
+
+    def _render(self, entry, scans, out, shape, dtype):
+        scans, s, single = self._batch(scans)
         n = s.shape[0]
-        shape = (n, self.rows, self.cols) + ((self.channels,) if self.channels > 1 else ())
+        shape = (n,) + shape
         if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.uint8 and tuple(out.shape) == shape
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        assert out.is_contiguous() and out.dtype == dtype and tuple(out.shape) == shape
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):  # the library launches on the current device's stream (f110_hip.h, conventions)
-            _lib.check(self.lib.f110_bitmap_render(self.h, s.data_ptr(), int(s.dtype == torch.float64), n,
-                                                   s.stride(0) if n > 1 else self.num_beams, out.data_ptr(), stream))
+            _lib.check(entry(self.h, s.data_ptr(), int(s.dtype == torch.float64), n,
+                             s.stride(0) if n > 1 else self.num_beams, out.data_ptr(), stream))
         out = out.reshape(scans.shape[:-1] + shape[1:]) if not single else out[0]
         return out
+
+    def __call__(self, scans, out=None):
+        """scans: [N, num_beams] (or [num_beams]) float32 / float64 tensor on the renderer's device."""
+        shape = (self.rows, self.cols) + ((self.channels,) if self.channels > 1 else ())
+        return self._render(self.lib.f110_bitmap_render, scans, out, shape, torch.uint8)
+
+    def bits(self, scans, out=None):
+        """The same images as one bit per pixel (f110_bitmap_render_bits): int64 [N, rows, ceil(cols / 64)] device tensor, the
+        bits of uint64 words -- bit k of word w of a row is set iff __call__'s image holds the draw colour at column 64 w + k
+        (the centre marker of a FILL image is background: 0), bits beyond `cols` are 0.  `channels` plays no part.  This is
+        the replay ring's frame format: with bg_color='black' it equals replay.pack_bitmaps(self(scans)), and
+        replay.unpack_bitmaps gives the byte image back."""
+        return self._render(self.lib.f110_bitmap_render_bits, scans, out, (self.rows, (self.cols + 63) // 64), torch.int64)
 
     def points(self, scans):
         """The integer points of lidar.py:63-73 (what the reference passes to the cv2 draw calls):

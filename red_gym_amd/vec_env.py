@@ -163,7 +163,15 @@ class F110VecEnv(object):
         A reset (masked, whole batch or autoreset) pays 0 in the step that performs it and restarts from the reset pose.
         shape_rewards(False) switches it off: no launch, no info key, no state_dict key remains and the reward is the
         constant again.  Switched on in the middle of a run, the first update pays no progress and reads the image of the
-        scans as they stand.  The replay buffer records the shaper's image and reward: switching the shaper off, or installing it
+        scans as they stand.
+        image='bits' (default 'bytes') keeps the bitmap as one bit per pixel from the renderer on: reset, step, step_graph and
+        step_lib_graph then run the bits forms of the render, the shaper and the replay push, with the same rewards and the same
+        ring, and `info` and state_dict() hold lidar_bitmap_bits [B, rows, ceil(cols / 64)] int64 instead of lidar_bitmap -- the
+        bits of uint64 words, bit k of word w of a row = (pixel[64 w + k] == 255), bits beyond cols 0: the replay ring's frame
+        format, which bitconv.BitConvStem(..., cols=cols) and conv_bits read as they are, and which
+        replay.unpack_bitmaps(info['lidar_bitmap_bits'], cols) turns back into the byte image.  load_state_dict takes a
+        checkpoint of either form in either mode.  Installing the shaper again in the other form at the same image size
+        restarts the shaper and keeps the replay buffer.  The replay buffer records the shaper's image and reward: switching the shaper off, or installing it
         again with another image size, while record_replay() is on removes the replay buffer too (its ring is freed)."""
         if enable:
             self.eng.shaper.install(**cfg)
@@ -218,7 +226,8 @@ class F110VecEnv(object):
         its training loop (:996-1001) on the GPU.  `capacity` counts transitions as the reference's does: the ring has steps =
         capacity // num_envs step slots for all envs (or give `steps` itself; at least 2).  From then on reset, step, step_graph
         and step_lib_graph push behind the shaper: the transition of env e at step t is (F[t-1, e], a[t, e], r[t, e], F[t, e],
-        done[t, e]) with F the shaper's lidar_bitmap as the step left it (stored bit-packed and once: 1/16 of the raw bytes), a =
+        done[t, e]) with F the shaper's lidar_bitmap as the step left it (stored bit-packed and once: 1/16 of the raw bytes; behind
+        shape_rewards(image='bits') the shaper's bits are copied as they are), a =
         replay_action as it stands at the push, r the shaper's total reward.  A transition is invalid and never sampled when
         the step was the env's reset (masked, whole batch or autoreset: terminal frame and spawn frame are no transition),
         when the env was not stepped by the call, or when there is no previous frame (the first push after this call or after
@@ -267,7 +276,7 @@ class F110VecEnv(object):
         starts every car's progress anew.  Likewise the shaper's prev_xy, t_seen and bitmap while shaping is on; without
         them the shaper restarts: the next update pays no progress and reads the image of the restored scans.  The replay
         buffer's ring is no part of a checkpoint: what it holds stays, and the next push stores a frame and an invalid transition."""
-        theirs = {k for c in self.consumers for k in c.STATE}
+        theirs = {k for c in self.consumers for k in c.state_keys()}
         self.eng.load_state({k: v for k, v in sd.items() if k not in theirs})
         for c in self.consumers:
             if c.on:
