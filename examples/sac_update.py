@@ -1,14 +1,15 @@
-"""One complete SACAgent.update (src/SAL.py:521-580) from the replay ring on the GPU, in the reference's order and with
-torch.optim.Adam:
+"""One complete SACAgent.update (src/SAL.py:521-580) from the replay ring on the GPU, in the reference's order, the parameter update
+included (SacAdam: Adam and the soft update of the target critics in one pass per network):
     python examples/sac_update.py [envs] [steps] [batch]
     sample_frames -> BitConvStem (conv1 + conv2 from the ring's bits) -> conv3 -> fc1 + PolicyHead   (the actor)
                                                                           -> twin_q / td_target         (the critics' fc1, fc2, min, target)
-    -> the two critic losses, the actor loss, the soft update of the target critics.
+    -> the two critic losses, the actor loss; SacAdam.step() per network, which also moves the target critics (:575-578).
 The critics never see cat([features, action]) (:440): the feature part of fc1 is one GEMM on the view fc1.weight[:, :F], and one
 kernel does the action part, bias, ReLU, fc2, the min over the twin critics and the TD target, reading the policy head's fp64 action
 and log_prob and the ring's fp64 reward and uint8 done as they are.  A random policy fills the ring first.  The two critic losses
 are summed for one backward pass (their parameters are disjoint, so each critic gets the gradient the reference's two passes give
-it), which runs the shared backward kernels once."""
+it), which runs the shared backward kernels once.  A target critic moves in the pass that updates its critic, before the actor's loss
+where the reference moves it after: the actor's loss reads the critics, never the targets, so the update computes the same."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,6 +17,7 @@ import torch
 import torch.nn.functional as F
 from red_gym_amd import F110VecEnv, workload
 from red_gym_amd.bitconv import BitConvStem
+from red_gym_amd.optim import SacAdam
 from red_gym_amd.policyhead import PolicyHead
 from red_gym_amd.qhead import QHead, td_target, twin_q
 
@@ -72,8 +74,8 @@ critics = [Critic(width).to(dev) for _ in range(2)]
 targets = [Critic(width).to(dev) for _ in range(2)]
 for t, c in zip(targets, critics):
     t.load_state_dict(c.state_dict())
-actor_opt = torch.optim.Adam(actor.parameters(), lr=LR)
-critic_opts = [torch.optim.Adam(c.parameters(), lr=LR) for c in critics]
+actor_opt = SacAdam(actor, lr=LR)
+critic_opts = [SacAdam(c, lr=LR, targets=t, tau=TAU) for c, t in zip(critics, targets)]
 
 
 def heads(nets):
@@ -91,16 +93,13 @@ def update():
         opt.zero_grad()
     (c_losses[0] + c_losses[1]).backward()
     for opt in critic_opts:
-        opt.step()
+        opt.step()                                                           # :556-562 and, in the same pass, :575-578
     new_a, logp = actor.sample(frames, s_idx)                                 # :564-568
     _, qn = twin_q([c.trunk(frames, s_idx) for c in critics], new_a, *heads(critics))
     a_loss = (ALPHA * logp - qn).mean()
     actor_opt.zero_grad()
     a_loss.backward()
     actor_opt.step()
-    with torch.no_grad():                                                    # :575-578: tp = tau p + (1 - tau) tp
-        for t, c in zip(targets, critics):
-            torch._foreach_lerp_(list(t.parameters()), list(c.parameters()), TAU)
     return a_loss.item(), c_losses[0].item(), c_losses[1].item()
 
 

@@ -780,6 +780,57 @@ int f110_qhead_backward(const f110_qhead_config *cfg, const f110_qhead_critics *
                         const float *grad_q, const float *grad_qmin, const f110_qhead_grads *g, void *grad_action, float *workspace,
                         void *stream);
 
+/* Parameter update: Adam with the reference's defaults (src/SAL.py:487-492: weight_decay 0, no amsgrad, no maximize) and the soft
+ * update of a target network (:575-578), over up to F110_ADAM_MAX_TENSORS tensors per call in ONE pass: p, g, m, v read once, p, m, v
+ * written once, and the target moved from the new p in the same pass.  Stateless but for the caller's f110_adam_state on the device
+ * (cfg and table host, every array dev); launches on `stream` of the calling thread's current device, no allocation, no
+ * synchronisation.  The table is copied into the kernel's arguments, so it may change from call to call (a fresh .grad buffer) and a
+ * captured call keeps the addresses it was captured with.  More tensors than F110_ADAM_MAX_TENSORS: further calls with advance = 0.
+ * f110_adam_step: per tensor p, g, m, v [n] fp32 and, with cfg->with_target nonzero, target [n] fp32 (else ignored).  With
+ * cfg->advance nonzero the call begins a step: a one-wave launch in front advances the state (t += 1; pow1 *= beta1; pow2 *= beta2,
+ * one fp64 multiplication each; k2 = float(sqrt(1 - pow2)), a = float(lr / (1 - pow1)), formed in fp64 with a correctly rounded
+ * division and square root and rounded to fp32 once).  With advance zero the call belongs to the step begun before it and reads the
+ * same k2 and a; `lr` is then unused.  `lr` is a host scalar of the call: a captured step replays the lr it was captured with.  A
+ * fresh state is t = 0, pow1 = pow2 = 1.0 (k2 and a are outputs); a resumed one t = step, pow = beta ** step.  n_tensors == 0 with
+ * advance nonzero only advances the state.
+ * Numerics, fp32, bit for bit, every line one correctly rounded operation (fmaf fused, division and square root correctly rounded,
+ * denormals kept, nothing contracted), with c1 = float(1 - beta1), c2 = float(1 - beta2), b2 = float(beta2), e = float(eps), tau_f =
+ * float(tau), each formed in fp64 and rounded once:
+ *   d = g - m;  m' = fmaf(c1, d, m);  t1 = g * g;  t2 = t1 * c2;  v' = fmaf(b2, v, t2);  s = sqrt(v');  r = s / k2;  den = r + e;
+ *   q = m' / den;  p' = fmaf(-a, q, p);  and with a target: u = p' - tp;  tp' = fmaf(tau_f, u, tp).
+ * f110_soft_update: the last line alone with p for p' on p and target of every tensor (g, m, v ignored); p is not written.
+ * An element's result depends on nothing but its own inputs and the state; tensors whose pointers are all 16-byte aligned take 16-byte
+ * accesses, any other (a view at an odd element offset) 4-byte ones, with the same result.  No element outside [0, n) is touched.
+ * F110_E_INVALID, before any launch, naming the culprit: a null cfg, table (with n_tensors > 0) or state; n_tensors outside 0 ..
+ * F110_ADAM_MAX_TENSORS; a tensor with n < 0 or n > 2^31; with n > 0: a null p, m or v (Adam), a null g (Adam), a null target (target
+ * modes), target == p, a pointer that is not 4-byte aligned; beta1 or beta2 outside [0, 1); eps <= 0 or not finite; lr or tau not
+ * finite; tau outside [0, 1]; and a wrong device as f110_policyhead_forward refuses it (p and target of every tensor and the state).
+ * f110_adam_validate: the checks on cfg alone, host only.  f110_adam_state_bytes: sizeof(f110_adam_state). */
+#define F110_ADAM_CHUNK 4096        /* elements of one tensor a workgroup updates */
+#define F110_ADAM_MAX_TENSORS 64    /* tensors of one call: 64 entries of 48 bytes fit a kernel's 4 KiB of arguments */
+typedef struct {
+    double beta1, beta2, eps;       /* SAL: 0.9, 0.999, 1e-8 */
+    double tau;                     /* of the target update, read when with_target is nonzero (SAL: 0.005) */
+    int32_t with_target;            /* nonzero: Adam plus target */
+    int32_t advance;                /* nonzero: the call begins a step and advances the state first */
+} f110_adam_config;
+typedef struct {
+    float *p;
+    const float *g;
+    float *m, *v, *target;
+    int64_t n;
+} f110_adam_tensor;
+typedef struct {                    /* on the device; 32 bytes */
+    int64_t t;                      /* steps taken */
+    double pow1, pow2;              /* beta1 ** t, beta2 ** t as running products */
+    float k2, a;                    /* of step t: float(sqrt(1 - pow2)), float(lr / (1 - pow1)) */
+} f110_adam_state;
+int f110_adam_validate(const f110_adam_config *cfg);
+int64_t f110_adam_state_bytes(void);
+int f110_adam_step(const f110_adam_config *cfg, const f110_adam_tensor *table, int32_t n_tensors, f110_adam_state *state, double lr,
+                   void *stream);
+int f110_soft_update(const f110_adam_tensor *table, int32_t n_tensors, double tau, void *stream);
+
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).
  * scans_f32 / lookups may be NULL; lookups [n] is overwritten-by-accumulation like

@@ -26,4 +26,7 @@ def __getattr__(name):
     if name in ('twin_q', 'td_target', 'QHead'):
         from . import qhead
         return getattr(qhead, name)
+    if name in ('SacAdam', 'soft_update'):
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(name)

@@ -135,6 +135,24 @@ class QheadGrads(C.Structure):
 
 F110_QHEAD_SLICE_ROWS = 256
 
+
+# f110_adam_config, f110_adam_tensor: the parameter update (Adam and the soft update of the targets); f110_adam_state lives on the device
+class AdamConfig(C.Structure):
+    _fields_ = [('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double), ('tau', C.c_double),
+                ('with_target', C.c_int32), ('advance', C.c_int32)]
+
+
+ADAM_TENSOR_FIELDS = ['p', 'g', 'm', 'v', 'target']
+
+
+class AdamTensor(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ADAM_TENSOR_FIELDS] + [('n', C.c_int64)]
+
+
+F110_ADAM_CHUNK = 4096
+F110_ADAM_MAX_TENSORS = 64
+F110_ADAM_STATE_BYTES = 32          # f110_adam_state: int64 t, double pow1, pow2, float k2, a
+
 # every symbol include/f110_hip.h declares: name -> argtypes (restype int unless noted)
 _VP, _I32, _I64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
@@ -226,6 +244,10 @@ SYMBOLS = {
     'f110_qhead_workspace': [C.POINTER(QheadConfig), _I64],
     'f110_qhead_forward': [C.POINTER(QheadConfig), C.POINTER(QheadCritics), _VP, _I64, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP],
     'f110_qhead_backward': [C.POINTER(QheadConfig), C.POINTER(QheadCritics), _VP, _I64, _VP, _VP, _VP, C.POINTER(QheadGrads), _VP, _VP, _VP],
+    'f110_adam_validate': [C.POINTER(AdamConfig)],
+    'f110_adam_state_bytes': [],
+    'f110_adam_step': [C.POINTER(AdamConfig), C.POINTER(AdamTensor), _I32, _VP, _D, _VP],
+    'f110_soft_update': [C.POINTER(AdamTensor), _I32, _D, _VP],
     'f110_replay_pack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_replay_unpack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],
@@ -282,6 +304,7 @@ def load():
     lib.f110_bitconv_workspace.restype = C.c_int64
     lib.f110_policyhead_workspace.restype = C.c_int64
     lib.f110_qhead_workspace.restype = C.c_int64
+    lib.f110_adam_state_bytes.restype = C.c_int64
     lib.f110_pack_env_size.restype = C.c_int64
     lib.f110_destroy.restype = None
     lib.f110_bitmap_destroy.restype = None

@@ -8,7 +8,8 @@
 //   f110_step.hip       launch policy of the scan, the step, hipGraphs, measurement aid, function-level entry points
 //   f110_consumers.hip  the callers either side of the step, on the handle: pure-pursuit planner, progress tracker, reward shaper,
 //                       path follower, replay buffer
-//   f110_policy_abi.hip the policy and the critics' tail, stateless: bit convolution, policy stem, policy head, critic head
+//   f110_policy_abi.hip the policy and the critics' tail, stateless: bit convolution, policy stem, policy head, critic head, and the
+//                       parameter update (Adam and the soft update of the targets)
 //   f110_bitmap_abi.hip the scan's consumers with no handle: scan -> bitmap (its own f110_bitmap object), occupancy grid
 #pragma once
 #include "../../include/f110_hip.h"

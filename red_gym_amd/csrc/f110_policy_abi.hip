@@ -4,6 +4,7 @@
 #include "f110_bitconv2.h"
 #include "f110_policyhead.h"
 #include "f110_qhead.h"
+#include "f110_adam.h"
 
 // ---------------------------------------------------------------- first convolution from bits
 // What the entry points refuse, on the struct alone (no device).
@@ -404,5 +405,104 @@ extern "C" int f110_qhead_backward(const f110_qhead_config *cfg, const f110_qhea
         hipLaunchKernelGGL(qhead_reduce_kernel, dim3(blocks, (unsigned)a.C), dim3(QH_THREADS), 0, s, a);
         HIP_TRY(hipGetLastError());
     }
+    return F110_OK;
+}
+
+// ---------------------------------------------------------------- parameter update: Adam and the soft update of the targets
+static int adam_scalar_checks(const char *who, const f110_adam_config *cfg, bool target)
+{
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    if (!(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0)) return fail(F110_E_INVALID, "%s: beta1 %g (0 <= beta1 < 1)", who, cfg->beta1);
+    if (!(cfg->beta2 >= 0.0 && cfg->beta2 < 1.0)) return fail(F110_E_INVALID, "%s: beta2 %g (0 <= beta2 < 1)", who, cfg->beta2);
+    if (!std::isfinite(cfg->eps) || !(cfg->eps > 0.0)) return fail(F110_E_INVALID, "%s: eps %g (finite and > 0)", who, cfg->eps);
+    if (target && (!std::isfinite(cfg->tau) || cfg->tau < 0.0 || cfg->tau > 1.0)) return fail(F110_E_INVALID, "%s: tau %g (0 <= tau <= 1)", who, cfg->tau);
+    return F110_OK;
+}
+
+extern "C" int f110_adam_validate(const f110_adam_config *cfg)
+{
+    return adam_scalar_checks("f110_adam_validate", cfg, cfg && cfg->with_target);
+}
+
+extern "C" int64_t f110_adam_state_bytes(void) { return (int64_t)sizeof(f110_adam_state); }
+
+// the checks on the table and the kernel's copy of it -> chunks of the launch in *grid
+static int adam_table(const char *who, const f110_adam_tensor *table, int n_tensors, bool adam, bool target, AdamTable &tab, uint32_t *grid,
+                      std::vector<DevicePtr> &ptrs)
+{
+    if (n_tensors < 0 || n_tensors > AD_MAX_T) return fail(F110_E_INVALID, "%s: n_tensors %d (0..%d a call)", who, n_tensors, AD_MAX_T);
+    if (n_tensors > 0 && !table) return fail(F110_E_INVALID, "%s: null table", who);
+    memset(&tab, 0, sizeof(tab));
+    tab.n_tensors = n_tensors;
+    uint32_t chunks = 0;
+    for (int i = 0; i < n_tensors; i++) {
+        const f110_adam_tensor &t = table[i];
+        if (t.n < 0 || t.n > ((int64_t)1 << 31)) return fail(F110_E_INVALID, "%s: tensor %d: n %lld (0..2^31)", who, i, (long long)t.n);
+        if (t.n > 0) {
+            if (!t.p) return fail(F110_E_INVALID, "%s: tensor %d: null p", who, i);
+            if (adam && !t.m) return fail(F110_E_INVALID, "%s: tensor %d: null m", who, i);
+            if (adam && !t.v) return fail(F110_E_INVALID, "%s: tensor %d: null v", who, i);
+            if (adam && !t.g) return fail(F110_E_INVALID, "%s: tensor %d: null g", who, i);
+            if (target && !t.target) return fail(F110_E_INVALID, "%s: tensor %d: null target", who, i);
+            if (target && t.target == t.p) return fail(F110_E_INVALID, "%s: tensor %d: target == p", who, i);
+            uintptr_t bits = (uintptr_t)t.p;
+            if (adam) bits |= (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v;
+            if (target) bits |= (uintptr_t)t.target;
+            if (bits % 4) return fail(F110_E_INVALID, "%s: tensor %d: a pointer is not 4-byte aligned", who, i);
+            AdamEntry &e = tab.t[i];
+            e.p = t.p; e.n = (uint32_t)t.n; e.vec = bits % 16 == 0;
+            if (adam) { e.g = t.g; e.m = t.m; e.v = t.v; }
+            if (target) e.target = t.target;
+            chunks += (uint32_t)((t.n + AD_CHUNK - 1) / AD_CHUNK);
+            ptrs.push_back({"p", t.p});
+            if (target) ptrs.push_back({"target", t.target});
+        }
+        tab.chunk_end[i] = chunks;      // (at most 64 * 2^19)
+    }
+    *grid = chunks;
+    return F110_OK;
+}
+
+extern "C" int f110_adam_step(const f110_adam_config *cfg, const f110_adam_tensor *table, int32_t n_tensors, f110_adam_state *state, double lr,
+                              void *stream)
+{
+    const char *who = "f110_adam_step";
+    if (int rc = adam_scalar_checks(who, cfg, cfg && cfg->with_target)) return rc;
+    if (!state) return fail(F110_E_INVALID, "%s: null state", who);
+    if ((uintptr_t)state % 8) return fail(F110_E_INVALID, "%s: the state is not 8-byte aligned", who);
+    if (!std::isfinite(lr)) return fail(F110_E_INVALID, "%s: lr is not finite", who);
+    const bool target = cfg->with_target != 0;
+    AdamTable tab;
+    uint32_t grid = 0;
+    std::vector<DevicePtr> ptrs = {{"state", state}};
+    if (int rc = adam_table(who, table, n_tensors, true, target, tab, &grid, ptrs)) return rc;
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
+    tab.c1 = (float)(1.0 - cfg->beta1); tab.c2 = (float)(1.0 - cfg->beta2); tab.b2 = (float)cfg->beta2; tab.eps = (float)cfg->eps;
+    tab.tau = target ? (float)cfg->tau : 0.0f;
+    hipStream_t s = (hipStream_t)stream;
+    if (cfg->advance) {
+        hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, s, state, cfg->beta1, cfg->beta2, lr);
+        HIP_TRY(hipGetLastError());
+    }
+    if (grid == 0) return F110_OK;
+    if (target) hipLaunchKernelGGL((adam_kernel<true, true>), dim3(grid), dim3(AD_THREADS), 0, s, tab, (const AdamState *)state);
+    else hipLaunchKernelGGL((adam_kernel<true, false>), dim3(grid), dim3(AD_THREADS), 0, s, tab, (const AdamState *)state);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_soft_update(const f110_adam_tensor *table, int32_t n_tensors, double tau, void *stream)
+{
+    const char *who = "f110_soft_update";
+    if (!std::isfinite(tau) || tau < 0.0 || tau > 1.0) return fail(F110_E_INVALID, "%s: tau %g (0 <= tau <= 1)", who, tau);
+    AdamTable tab;
+    uint32_t grid = 0;
+    std::vector<DevicePtr> ptrs;
+    if (int rc = adam_table(who, table, n_tensors, false, true, tab, &grid, ptrs)) return rc;
+    if (grid == 0) return F110_OK;
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
+    tab.tau = (float)tau;
+    hipLaunchKernelGGL((adam_kernel<false, true>), dim3(grid), dim3(AD_THREADS), 0, (hipStream_t)stream, tab, (const AdamState *)nullptr);
+    HIP_TRY(hipGetLastError());
     return F110_OK;
 }
