@@ -1,8 +1,8 @@
 """One complete SACAgent.update (src/SAL.py:521-580) from the replay ring on the GPU, in the reference's order, the parameter update
 included (SacAdam: Adam and the soft update of the target critics in one pass per network):
     python examples/sac_update.py [envs] [steps] [batch]
-    sample_frames -> BitConvStem (conv1 + conv2 from the ring's bits) -> conv3 -> fc1 + PolicyHead   (the actor)
-                                                                          -> twin_q / td_target         (the critics' fc1, fc2, min, target)
+    sample_frames -> Trunk (conv1 from the ring's bits, conv2, conv3: featconv) -> fc1 + PolicyHead   (the actor)
+                                                                                 -> twin_q / td_target (the critics' fc1, fc2, min, target)
     -> the two critic losses, the actor loss; SacAdam.step() per network, which also moves the target critics (:575-578).
 The critics never see cat([features, action]) (:440): the feature part of fc1 is one GEMM on the view fc1.weight[:, :F], and one
 kernel does the action part, bias, ReLU, fc2, the min over the twin critics and the TD target, reading the policy head's fp64 action
@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
 from red_gym_amd import F110VecEnv, workload
-from red_gym_amd.bitconv import BitConvStem
+from red_gym_amd.featconv import Trunk
 from red_gym_amd.optim import SacAdam
 from red_gym_amd.policyhead import PolicyHead
 from red_gym_amd.qhead import QHead, td_target, twin_q
@@ -25,6 +25,7 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 STEPS = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 BATCH = int(sys.argv[3]) if len(sys.argv) > 3 else 64
 GAMMA, TAU, ALPHA, LR, AD = 0.99, 0.005, 0.2, 3e-4, 16                         # SACAgent's defaults (:478-480)
+ON = 255.0                                                                     # a set pixel: update() feeds the raw 0 / 255 images (:536)
 env = F110VecEnv(B, map=workload.EXAMPLE_MAP, num_agents=1, autoreset=True)
 env.shape_rewards()
 env.follow_paths()
@@ -33,22 +34,10 @@ dev, cols = env.device, env.eng.shaper.cfg.cols
 torch.manual_seed(0)
 
 
-class Trunk(torch.nn.Module):
-    """conv1, conv2 (from bits, on = 255: update() feeds the raw 0 / 255 images, :536) and conv3 of the reference's Actor and Critic."""
-
-    def __init__(self):
-        super().__init__()
-        self.stem = BitConvStem(16, 8, 4, 32, 4, 2, on=255.0, cols=cols)
-        self.conv3 = torch.nn.Conv2d(32, 32, kernel_size=3, stride=1)
-
-    def forward(self, frames, index):
-        return torch.relu(self.conv3(self.stem(frames, index=index))).flatten(1)
-
-
 class Actor(torch.nn.Module):
     def __init__(self, width):
         super().__init__()
-        self.trunk, self.fc1, self.head = Trunk(), torch.nn.Linear(width, 512), PolicyHead(512, AD)
+        self.trunk, self.fc1, self.head = Trunk(on=ON, cols=cols), torch.nn.Linear(width, 512), PolicyHead(512, AD)
 
     def sample(self, frames, index):
         action, log_prob, _, _ = self.head.sample(torch.relu(self.fc1(self.trunk(frames, index))))
@@ -58,7 +47,7 @@ class Actor(torch.nn.Module):
 class Critic(torch.nn.Module):
     def __init__(self, width):
         super().__init__()
-        self.trunk, self.head = Trunk(), QHead(width, AD, 512)
+        self.trunk, self.head = Trunk(on=ON, cols=cols), QHead(width, AD, 512)
 
 
 gen = torch.Generator(device=dev).manual_seed(0)
@@ -68,7 +57,7 @@ for k in range(STEPS):
     env.step(env.path_actions(raw))
 frames, s_idx, ns_idx, a, r, d, ok = env.replay.sample_frames(BATCH)
 with torch.no_grad():
-    width = Trunk().to(dev)(frames, s_idx).shape[1]
+    width = Trunk(on=ON, cols=cols).to(dev)(frames, s_idx).shape[1]
 actor = Actor(width).to(dev)
 critics = [Critic(width).to(dev) for _ in range(2)]
 targets = [Critic(width).to(dev) for _ in range(2)]
@@ -110,4 +99,5 @@ for k in range(3):
 g = critics[0].head.fc1.weight.grad
 print('critic fc1.weight.grad %s: feature columns filled: %s, action columns filled: %s' % (
     tuple(g.shape), bool((g[:, :width] != 0).any()), bool((g[:, width:] != 0).any())))
-env.close()
+if __name__ == '__main__':                                                   # (tools/time_featconv.py runs this file for its update() and closes the env itself)
+    env.close()

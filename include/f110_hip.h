@@ -678,6 +678,48 @@ int f110_bitconv2_forward(const f110_bitconv2_config *cfg, const uint64_t *frame
 int f110_bitconv2_forward_u8(const f110_bitconv2_config *cfg, const uint8_t *images, int64_t n_frames, const int64_t *index, int64_t n,
                              const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream);
 
+/* Dense convolution of fp32 feature maps, forward and backward: conv2 = nn.Conv2d(16, 32, 4, 2) and conv3 = nn.Conv2d(32, 32, 3, 1)
+ * of the reference's Actor and Critic (src/SAL.py:398-399, 406-407, 430-431, 437-438) with their ReLU, on the fp32 matrix cores.
+ * Stateless (no handle; cfg host; all arrays dev); launches on `stream` of the calling thread's current device, no allocation, no
+ * synchronisation, no atomics.  x [n, in_channels, rows, cols] fp32 NCHW contiguous, weight [out_channels, in_channels, kernel,
+ * kernel] fp32 (finite), bias [out_channels] fp32 or NULL (= zeros), out [n, out_channels, OH, OW] fp32 with OH = (rows - kernel) /
+ * stride + 1, OW likewise: square kernel and stride, no padding, no dilation, no groups.  n == 0 does nothing.
+ * Numerics, forward, in fp32 (the contract of f110_bitconv2's second layer): acc = 0; for ci major, then ky, then kx minor: acc =
+ * fmaf(weight[co][ci][ky][kx], x[ci][stride oy + ky][stride ox + kx], acc), one rounding per step; out = acc + bias[co] (+ 0.0f for
+ * NULL); then out < 0 ? 0 : out if relu.  Two calls give the same bits, and a sample's result depends neither on n nor on its place
+ * in the batch.
+ * f110_featconv_backward: from x, out (the forward's result, read only where relu is set, for the mask), grad_out [n, out_channels,
+ * OH, OW] and weight; each of grad_x [n, in_channels, rows, cols] and the pair grad_weight [as weight] / grad_bias [out_channels]
+ * may be NULL and is then skipped (grad_bias alone may be NULL too).  With g = out > 0 ? grad_out : 0 under relu, else g = grad_out:
+ *   grad_x[n][ci][iy][ix]: acc = 0; for co major, then ky, then kx minor: acc = fmaf(weight[co][ci][ky][kx], g[n][co][(iy - ky) /
+ *   stride][(ix - kx) / stride], acc) over the terms whose output pixel exists (divisible by stride, inside the plane); a missing
+ *   term is fed as fmaf(w, 0, acc), which for finite weights leaves acc (never -0) unchanged.
+ *   grad_weight in two stages.  Stage 1, per sample: P[n][co][ci][ky][kx]: acc = 0; for oy major, ox minor: acc = fmaf(g[n][co][oy]
+ *   [ox], x[n][ci][stride oy + ky][stride ox + kx], acc).  Stage 2: grad_weight = ((P[0] + P[1]) + P[2]) + ..., plain fp32 adds,
+ *   samples ascending.  grad_bias: the same two stages with acc = acc + g[n][co][oy][ox] from 0.
+ * The order depends on the shape and n alone, never on the grid or on timing: two calls give the same bits, and a sample's grad_x
+ * and partials do not depend on the batch around it.  P lives in `workspace` (16-byte aligned, required with grad_weight or
+ * grad_bias) of f110_featconv_workspace bytes = n * out_channels * (in_channels * kernel^2 + 1) * 4 (0 for an invalid configuration,
+ * for n < 1 and where the count does not fit int64): per sample out_channels * in_channels * kernel^2 weight partials, then out_channels bias partials.  That is 2.4 MB for
+ * conv3 at a batch of 64 and 151 MB at 4 096 rows.
+ * f110_featconv_validate: host only.  F110_E_INVALID for kernel outside 1..4, stride outside 1..4, in_channels outside 1..32,
+ * out_channels outside 1..64, in_channels * kernel^2 or out_channels * kernel^2 above 512, rows below kernel, cols below kernel or
+ * above 64 (the kernels work on whole rows and have no halo in x; any number of rows is accepted). */
+typedef struct {
+    int32_t in_channels;        /* 1..32 */
+    int32_t rows, cols;         /* the input planes; cols <= 64 */
+    int32_t out_channels;       /* 1..64 */
+    int32_t kernel, stride;     /* square window 1..4, stride 1..4 */
+    int32_t relu;               /* nonzero: max(out, 0), and its mask in the backward */
+    int32_t reserved;           /* 0 */
+} f110_featconv_config;
+int f110_featconv_validate(const f110_featconv_config *cfg);
+int64_t f110_featconv_workspace(const f110_featconv_config *cfg, int64_t n);
+int f110_featconv_forward(const f110_featconv_config *cfg, const float *x, int64_t n, const float *weight, const float *bias, float *out,
+                          void *stream);
+int f110_featconv_backward(const f110_featconv_config *cfg, const float *x, const float *out, const float *grad_out, int64_t n,
+                           const float *weight, float *grad_x, float *grad_weight, float *grad_bias, float *workspace, void *stream);
+
 /* Policy head: the end of the reference's Actor.forward and Actor.sample (src/SAL.py:410-421) -- fc_mean and fc_log_std on the
  * features h of fc1, clamp(-20, 2), exp, rsample, tanh and the squashed-Gaussian log_prob summed over the action -- forward in one
  * kernel, and a backward without atomics.  Stateless (no handle; cfg host; all arrays dev); launches on `stream` of the calling

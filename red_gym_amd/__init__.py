@@ -20,6 +20,9 @@ def __getattr__(name):
     if name in ('conv_bits', 'BitConv2d', 'conv_bits2', 'BitConvStem'):
         from . import bitconv
         return getattr(bitconv, name)
+    if name in ('conv_feat', 'FeatConv2d', 'Trunk'):
+        from . import featconv
+        return getattr(featconv, name)
     if name in ('sample_actions', 'PolicyHead'):
         from . import policyhead
         return getattr(policyhead, name)

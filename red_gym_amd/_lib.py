@@ -108,6 +108,12 @@ class Bitconv2Config(C.Structure):
                 ('kernel2', C.c_int32), ('stride2', C.c_int32), ('channels2', C.c_int32), ('relu2', C.c_int32)]
 
 
+# f110_featconv_config: a dense convolution of fp32 feature maps, forward and backward (stateless)
+class FeatconvConfig(C.Structure):
+    _fields_ = [('in_channels', C.c_int32), ('rows', C.c_int32), ('cols', C.c_int32), ('out_channels', C.c_int32),
+                ('kernel', C.c_int32), ('stride', C.c_int32), ('relu', C.c_int32), ('reserved', C.c_int32)]
+
+
 # f110_policyhead_config: the policy head (fc_mean, fc_log_std and the sampling tail; stateless)
 class PolicyheadConfig(C.Structure):
     _fields_ = [('in_features', C.c_int32), ('action_dim', C.c_int32), ('out_fp64', C.c_int32)]
@@ -236,6 +242,10 @@ SYMBOLS = {
     'f110_bitconv2_validate': [C.POINTER(Bitconv2Config)],
     'f110_bitconv2_forward': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_bitconv2_forward_u8': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_featconv_validate': [C.POINTER(FeatconvConfig)],
+    'f110_featconv_workspace': [C.POINTER(FeatconvConfig), _I64],
+    'f110_featconv_forward': [C.POINTER(FeatconvConfig), _VP, _I64, _VP, _VP, _VP, _VP],
+    'f110_featconv_backward': [C.POINTER(FeatconvConfig), _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_policyhead_validate': [C.POINTER(PolicyheadConfig)],
     'f110_policyhead_workspace': [C.POINTER(PolicyheadConfig), _I64],
     'f110_policyhead_forward': [C.POINTER(PolicyheadConfig), _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
@@ -302,6 +312,7 @@ def load():
     lib.f110_last_error.restype = C.c_char_p
     lib.f110_pure_pursuit_workspace.restype = C.c_int64
     lib.f110_bitconv_workspace.restype = C.c_int64
+    lib.f110_featconv_workspace.restype = C.c_int64
     lib.f110_policyhead_workspace.restype = C.c_int64
     lib.f110_qhead_workspace.restype = C.c_int64
     lib.f110_adam_state_bytes.restype = C.c_int64
