@@ -11,35 +11,14 @@
 //   bitconv_reduce_kernel    stage 2: the G partials of every element summed in a fixed order, times `on`
 // Forward numerics (the contract of include/f110_hip.h): acc = 0; taps ky major, kx minor: acc = fma(w, bit, acc) with bit 0.0 or
 // 1.0 -- w * bit is exact, so this is acc + w for a set tap and acc for a clear one, rounded once per tap; out = (acc * on) + bias.
-// Includes f110_replay_bits.h for the frame format it reads: replay_bits16 (16 pixels -> 16 bits) here, replay_words and REPLAY_MAX_DIM
-// in the host checks of f110_policy_abi.hip.
+// Limits, BitconvArgs and the host's checks and launch plans are in f110_bitconv_plan.h (f110_bitconv_abi.hip launches them); it
+// includes f110_replay_bits.h for the frame format read here: replay_bits16 (16 pixels -> 16 bits).
 #pragma once
-#include "../../include/f110_hip.h" // f110_bitconv_config
-#include "f110_replay_bits.h"
+#include "f110_bitconv_plan.h"
 
 #pragma clang fp contract(off)
 
 namespace f110 {
-
-constexpr int BC_THREADS = 256;
-constexpr int BC_TX = 64, BC_TY = 4;          // outputs of a tile: one wave per row
-constexpr int BC_MAX_K = 8;                   // kernel * kernel taps fit one 64-bit mask
-constexpr int BC_LROWS = (BC_TY - 1) * BC_MAX_K + BC_MAX_K;   // 32 image rows under a tile at most (stride <= kernel <= 8)
-constexpr int BC_LWORDS = 9;                  // (63 + 63 * 8 + 8) bits from the first word's bit 0: 575 <= 9 * 64
-constexpr int BC_CHUNK = 16;                  // channels one workgroup of the backward pass accumulates
-constexpr int BC_MAX_PARTIALS = 1024;         // G at most
-
-struct BitconvArgs {
-    f110_bitconv_config cfg;
-    const uint64_t *frames;         // [n_frames, rows, W], or
-    const uint8_t *images;          // [n_frames, rows, cols]
-    long long n_frames;
-    const long long *index;         // [n] or NULL
-    long long first, n;             // forward: this launch computes images first .. first + gridDim.x / tiles - 1
-    const float *grad_out;          // backward [n, C, OH, OW]
-    float *ws;                      // backward [G, C, kernel^2] then [G, C]
-    int OH, OW, W, tiles_x, tiles_y, G;
-};
 
 struct BitconvTile {                // what a workgroup knows about its tile
     long long i, src;               // sample, and the frame it reads (-1: a frame of zeros)

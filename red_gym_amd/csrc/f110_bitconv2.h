@@ -24,24 +24,7 @@
 
 namespace f110 {
 
-constexpr int BC2_MAX_K2 = 4, BC2_MAX_C1 = 16, BC2_MAX_C2 = 64, BC2_MAX_OW1 = 64;
-constexpr int BC2_KSTEPS = BC2_MAX_C1 * BC2_MAX_K2 * BC2_MAX_K2 / 4;     // 64 steps of 4 at most
-constexpr int BC2_ACCS = 6;                    // M-tiles a wave accumulates at once
-constexpr int BC2_LDS_BYTES = 64 * 1024;       // of a workgroup: what a kernel may ask for without an attribute; two fit a CU
-constexpr int BC2_MAX_GRID = 2048;             // workgroups of a launch; each walks its share of the items
-
 typedef float bc2_f32x4 __attribute__((ext_vector_type(4)));
-
-struct Bitconv2Args {
-    BitconvArgs l1;                 // the first layer: cfg, frames / images, n_frames, index, n, OH, OW, W
-    int u8;                         // images, not frames
-    int k2, s2, C2, relu2;
-    int OH2, OW2, XW;               // XW: columns of a1 that conv2 reads
-    int BR, bands, NR1;             // output rows of a band, bands of a sample, conv1 rows under a full band
-    int ktot, ksteps;               // C1 k2 k2 and ceil(ktot / 4)
-    int a1_off, koff_off;           // byte offsets into the workgroup's LDS
-    long long items;                // n * bands
-};
 
 // The band as the tile bitconv_stage and bitconv_mask understand: all columns from word 0, the image rows under conv1 rows
 // y1 .. y1 + nr1 - 1.

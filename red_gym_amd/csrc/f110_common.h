@@ -8,12 +8,14 @@
 //   f110_step.hip       launch policy of the scan, the step, hipGraphs, measurement aid, function-level entry points
 //   f110_consumers.hip  the callers either side of the step, on the handle: pure-pursuit planner, progress tracker, reward shaper,
 //                       path follower, replay buffer
-//   f110_policy_abi.hip the policy and the critics' tail, stateless: bit convolution, policy stem, policy head, critic head, and the
-//                       parameter update (Adam and the soft update of the targets)
+//   f110_bitconv_abi.hip the policy's first layers from bits, stateless: bit convolution, policy stem
+//   f110_policy_abi.hip the policy's and the critics' tails, stateless: policy head, critic head, and the parameter update (Adam and
+//                       the soft update of the targets)
 //   f110_featconv_abi.hip the trunk's dense convolutions (conv2, conv3), stateless: forward, grad_x, grad_weight / grad_bias
 //   f110_bitmap_abi.hip the scan's consumers with no handle: scan -> bitmap (its own f110_bitmap object), occupancy grid
 #pragma once
 #include "../../include/f110_hip.h"
+#include "f110_launch.h"
 
 #include <hip/hip_ext.h>
 
@@ -39,6 +41,10 @@ int check_current_device(int dev, const char *who);       // f110_handle.hip
         if (e_ != hipSuccess)                                                                  \
             return fail(F110_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+// One launch as a plan (f110_*_plan.h) describes it; `kernel` in parentheses where its template arguments hold a comma.
+#define F110_LAUNCH(kernel, L, stream, ...) \
+    hipLaunchKernelGGL(kernel, dim3((L).gx, (L).gy, (L).gz), dim3((L).block), (L).lds, stream, __VA_ARGS__)
 
 // Makes `dev` the calling thread's current device for the scope of one library call and restores the caller's own
 // afterwards: a process that drives several GPUs (or several handles on different GPUs) keeps ITS current device across

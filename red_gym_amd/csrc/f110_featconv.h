@@ -31,48 +31,13 @@
 // Workspace: P is n Co (Ci k^2 + 1) floats -- 2.4 MB for conv3 at the update's batch of 64, 151 MB at 4 096 rows.
 #pragma once
 #include "f110_bounds.h" // F110_BOUNDS_ONLY
+#include "f110_featconv_plan.h" // limits, FeatconvGemm, FeatconvArgs; the host's checks and launch plans
 
 #pragma clang fp contract(off)
 
 namespace f110 {
 
-constexpr int FC_MAX_K = 4, FC_MAX_S = 4, FC_MAX_CI = 32, FC_MAX_CO = 64, FC_MAX_KTOT = 512, FC_MAX_W = 64;
-constexpr int FC_THREADS = 256;
-constexpr int FC_CHUNK = 8;                    // steps of 4 in a chunk of K
-constexpr int FC_ACCS = 4;                     // M-tiles a wave accumulates at once
-constexpr int FC_STAGE = 8;                    // planes a lane stages at once: that many loads in flight
-constexpr int FC_ZERO_BYTES = 16;              // zeros in front of the staged data: what a padding term reads (index -1)
-constexpr int FC_LDS_BYTES = 64 * 1024;        // of a workgroup: what a kernel may ask for without an attribute
-constexpr int FC_MAX_GRID = 2048;              // workgroups of a launch in x; each walks its share of the items
-constexpr int FCW_TILES = 8;                   // N-tiles of a workgroup of featconv_gradw_kernel, two per wave
-constexpr int FCW_MAX_MT = FC_MAX_CO / 16;
-
 typedef float fc_f32x4 __attribute__((ext_vector_type(4)));
-
-// One GEMM over planes: the forward (C = Ci planes of x, N = Co) or grad_x (C = Co planes of g, N = Ci).
-struct FeatconvGemm {
-    int C, N;                       // staged planes, output channels
-    int ktot, chunks;               // C k k and ceil(ktot / (4 FC_CHUNK))
-    int PH, PW;                     // the output plane
-    int ms;                         // distance in the planes between the windows of neighbouring output pixels
-    int XW;                         // columns of a staged plane
-    int BR, bands, NR;              // output rows of a band, bands of a sample, staged rows under a full band
-    int planes_off;                 // byte offset of the planes in the workgroup's LDS: koff[32 chunks], FC_ZERO_BYTES of zeros, the planes
-    long long items;                // n * bands
-};
-
-struct FeatconvArgs {
-    int Ci, H, W, Co, k, s, relu, OH, OW;
-    FeatconvGemm g;
-    // stage 1 of grad_weight
-    int wBR, wbands, wNR, wXW, wGP; // output rows of a band, bands, staged rows and columns of x, pixels of a full band
-    int wktot, wNT, wMT;            // Ci k k, its N-tiles, the M-tiles of Co
-    int xs_at;                      // float index of the x planes in the workgroup's LDS: FC_ZERO_BYTES of zeros, g, x
-    long long n;
-    const float *x, *out, *grad_out, *w, *bias;
-    float *dst;                     // out (forward) or grad_x
-    float *P;                       // [n][Co ktot + Co]
-};
 
 // FC_CHUNK steps of K for FC_ACCS M-tiles against one N-tile: acc[j] = mfma(planes at fm[j] + koff[k], b[i], acc[j]), k ascending.
 // A padding term (koff < 0; b is 0 there) multiplies the 0 at planes[-1] by 0.

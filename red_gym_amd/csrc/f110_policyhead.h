@@ -18,7 +18,7 @@
 // XORed with 4 (row & 15), which spreads the 16 rows a read touches over all banks.  Columns past K are zeros: fma(0, 0, acc).
 // Numerics (the contract of include/f110_hip.h): the MFMA is a k-ordered fmaf chain through C.
 #pragma once
-#include "../../include/f110_hip.h" // F110_POLICYHEAD_SLICE_ROWS
+#include "f110_policyhead_plan.h" // limits, PolicyheadArgs; the host's checks and launch plans
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,35 +28,7 @@
 
 namespace f110 {
 
-constexpr int PH_THREADS = 256;
-constexpr int PH_ROWS = 64;                   // rows of a forward tile: 16 per wave
-constexpr int PH_MAX_K = 4096, PH_MAX_A = 32;
-constexpr long long PH_MAX_ROWS = 1ll << 24;      // of a call: every launch stays below 2^31 workgroups and 2^32 threads
-constexpr int PH_LDS_BYTES = 64 * 1024;       // of a workgroup: what a kernel may ask for without an attribute
-constexpr int PH_MAX_GRID = 512;              // workgroups of the forward launch; each walks its share of the tiles
-constexpr int PH_PREFETCH = 64;               // columns of h a lane's loads run ahead of the multiply
-constexpr int PH_GH_ROWS = 16;                // rows of a grad_h workgroup
-constexpr int PH_SLICE = F110_POLICYHEAD_SLICE_ROWS;
-constexpr double PH_HALF_LOG_2PI = 0.91893853320467274178;
-
 typedef float ph_f32x4 __attribute__((ext_vector_type(4)));
-
-struct PolicyheadArgs {
-    int K, A, T;                    // in_features, action_dim, N-tiles per half
-    int kc, chunks;                 // columns of K in LDS at a time, ceil(K / kc)
-    int out_fp64;
-    long long n, tiles;             // rows, ceil(n / PH_ROWS)
-    const float *h, *w_mean, *b_mean, *w_log_std, *b_log_std, *eps;
-    float *pre;                     // [n, 2A]
-    void *action, *log_prob;        // [n, A], [n]: double or float
-    // backward
-    const void *grad_action, *grad_log_prob;
-    const float *grad_pre;          // [n, 2A] or NULL: a gradient that arrives at pre itself
-    float *gpre;                    // workspace [n, 2A]
-    float *partial;                 // workspace [slices, 2A, K + 1]
-    int slices;
-    float *grad_h, *grad_w_mean, *grad_b_mean, *grad_w_log_std, *grad_b_log_std;
-};
 
 // What the tail makes of one element, in fp64 (forward and backward agree on it by construction).
 struct PolicyheadTail {

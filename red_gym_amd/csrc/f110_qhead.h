@@ -15,7 +15,7 @@
 // <= QH_LDS_BYTES (SAL: 36.1 KB), staged once per critic and workgroup; else every tile stages its chunks in turn.
 // Numerics: the contract of include/f110_hip.h; every fused step is an explicit fmaf, every other one a separately rounded operation.
 #pragma once
-#include "../../include/f110_hip.h" // F110_QHEAD_SLICE_ROWS
+#include "f110_qhead_plan.h" // limits, QheadArgs, qhead_partial_floats; the host's checks and launch plans
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,37 +23,6 @@
 #pragma clang fp contract(off)
 
 namespace f110 {
-
-constexpr int QH_THREADS = 256;
-constexpr int QH_RPW = 2;                     // rows of a wave in the forward kernel: an LDS read of w_act feeds two chains
-constexpr int QH_ROWS = 4 * QH_RPW;           // rows of a forward tile
-constexpr int QH_BROWS = 4;                   // rows of a backward tile: one per wave
-constexpr int QH_MAX_H = 4096, QH_MAX_A = 32, QH_MAX_C = 2;
-constexpr long long QH_MAX_ROWS = 1ll << 24;
-constexpr int QH_LDS_BYTES = 64 * 1024;       // of a workgroup: what a kernel may ask for without an attribute
-constexpr int QH_MAX_GRID = 1024;             // workgroups of a row kernel; each walks its share of the tiles
-constexpr int QH_SLICE = F110_QHEAD_SLICE_ROWS;
-
-struct QheadArgs {
-    int H, A, C, ld, act_fp64;
-    int hc, chunks;                 // hidden units in LDS at a time (a multiple of 64), ceil(H / hc)
-    long long n, tiles;             // rows, tiles of the launch
-    int slices;
-    const float *pre[QH_MAX_C], *w_act[QH_MAX_C], *b1[QH_MAX_C], *w2[QH_MAX_C], *b2[QH_MAX_C];
-    const void *action, *nlp;       // [n, A], [n]: double or float
-    const double *reward;
-    const uint8_t *done;
-    double gamma, alpha;
-    float *q, *qmin, *target;       // forward outputs
-    // backward
-    const float *q_in, *grad_q, *grad_qmin;
-    float *grad_pre[QH_MAX_C], *grad_w_act[QH_MAX_C], *grad_b1[QH_MAX_C], *grad_w2[QH_MAX_C], *grad_b2[QH_MAX_C];
-    void *grad_action;
-    float *partial;                 // workspace [C][slices][H (A + 2) + 1]
-};
-
-// floats of one (critic, slice) in the workspace: grad_w_act [H][A], grad_b1 [H], grad_w2 [H], grad_b2
-__host__ __device__ inline size_t qhead_partial_floats(int H, int A) { return (size_t)H * (size_t)(A + 2) + 1; }
 
 // Units j0 .. j0 + hc - 1 of critic c in LDS; units past H are zeros.
 __device__ inline void qhead_stage(const QheadArgs &a, float *lw, int c, int j0, int tid)

@@ -9,6 +9,7 @@ import pytest
 
 import bitconv_cases as bc
 import replay_cases as rc
+from test_launch_plans_cpu import constant, lib as launch_plans  # noqa: F401 (the fixture: the plan headers compiled for the host)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ('f110_bitconv_validate', 'f110_bitconv_workspace', 'f110_bitconv_forward', 'f110_bitconv_forward_u8',
@@ -62,27 +63,15 @@ def test_checker_gradients_against_autograd_in_fp64():
     assert (aw >= np.abs(gw) / on - 1e-9).all() and (ab >= np.abs(gb) - 1e-9).all()
 
 
-def _header_constants():
-    """The BC_ constants of csrc/f110_bitconv.h, read from its text: `NAME = digits` each, BC_LROWS the one expression."""
-    hdr = open(os.path.join(ROOT, 'red_gym_amd', 'csrc', 'f110_bitconv.h')).read()
-    vals = {name: int(re.search(r'\b%s\s*=\s*(\d+)\s*[,;]' % name, hdr).group(1))
-            for name in ('BC_TX', 'BC_TY', 'BC_MAX_K', 'BC_LWORDS', 'BC_CHUNK', 'BC_MAX_PARTIALS')}
-    lrows = re.sub(r'\s', '', re.search(r'\bBC_LROWS\s*=([^;]+);', hdr).group(1))
-    assert lrows == '(BC_TY-1)*BC_MAX_K+BC_MAX_K'
-    vals['BC_LROWS'] = (vals['BC_TY'] - 1) * vals['BC_MAX_K'] + vals['BC_MAX_K']
-    return vals
-
-
-def test_shape_tables_reach_every_path():
+def test_shape_tables_reach_every_path(launch_plans):
     """tests/bitconv_cases.py: paths() restates the header's arithmetic, and the tables the GPU tests run reach every kernel
     size, both branches of the mask, the largest LDS footprint, full and partial tiles, the tail word, every count of channel
     chunks and every kind of walk over the tiles.  Removing a row that is the only one to reach a path fails here."""
     from red_gym_amd import _lib, bitconv
-    k = _header_constants()
-    assert [k[n] for n in ('BC_TX', 'BC_TY', 'BC_MAX_K', 'BC_LROWS', 'BC_LWORDS', 'BC_CHUNK', 'BC_MAX_PARTIALS')] == \
+    # the constants as the compiler sees them in csrc/f110_bitconv_plan.h (the shim of test_launch_plans_cpu.py)
+    assert [constant(launch_plans, n) for n in ('BC_TX', 'BC_TY', 'BC_MAX_K', 'BC_LROWS', 'BC_LWORDS', 'BC_CHUNK', 'BC_MAX_PARTIALS')] == \
         [bc.BC_TX, bc.BC_TY, bc.BC_MAX_K, bc.BC_LROWS, bc.BC_LWORDS, bc.BC_CHUNK, bc.BC_MAX_PARTIALS]
-    src = open(os.path.join(ROOT, 'red_gym_amd', 'csrc', 'f110_policy_abi.hip')).read()
-    assert re.search(r'\(int64_t\)\s*1\s*<<\s*23\)\s*/\s*per\b', src) and bc.FORWARD_GROUP == 1 << 23
+    assert constant(launch_plans, 'BC_FORWARD_GROUP') == bc.FORWARD_GROUP == 1 << 23
     # the validated range by brute force: every kernel, every stride, every count of outputs of a row of up to three tiles
     widest = offs = 0
     for kernel in range(1, bc.BC_MAX_K + 1):
