@@ -1,10 +1,11 @@
 """One complete SACAgent.update (src/SAL.py:521-580) from the replay ring on the GPU, in the reference's order, the parameter update
 included (SacAdam: Adam and the soft update of the target critics in one pass per network):
     python examples/sac_update.py [envs] [steps] [batch]
-    sample_frames -> Trunk (conv1 from the ring's bits, conv2, conv3: featconv) -> fc1 + PolicyHead   (the actor)
-                                                                                 -> twin_q / td_target (the critics' fc1, fc2, min, target)
+    sample_frames -> Trunk (conv1 from the ring's bits, conv2, conv3: featconv) -> Dense (fc1 + ReLU) -> PolicyHead   (the actor)
+                                                                                 -> twin_q / td_target, dense=True (the critics' fc1, fc2, min, target)
     -> the two critic losses, the actor loss; SacAdam.step() per network, which also moves the target critics (:575-578).
-The critics never see cat([features, action]) (:440): the feature part of fc1 is one GEMM on the view fc1.weight[:, :F], and one
+Every fc1 is the dense layer's kernels (red_gym_amd.dense): segments of 784 k's, each a fixed chain, added in a fixed order.
+The critics never see cat([features, action]) (:440): the feature part of fc1 is that layer on the view fc1.weight[:, :F], and one
 kernel does the action part, bias, ReLU, fc2, the min over the twin critics and the TD target, reading the policy head's fp64 action
 and log_prob and the ring's fp64 reward and uint8 done as they are.  A random policy fills the ring first.  The two critic losses
 are summed for one backward pass (their parameters are disjoint, so each critic gets the gradient the reference's two passes give
@@ -16,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
 from red_gym_amd import F110VecEnv, workload
+from red_gym_amd.dense import Dense
 from red_gym_amd.featconv import Trunk
 from red_gym_amd.optim import SacAdam
 from red_gym_amd.policyhead import PolicyHead
@@ -37,17 +39,17 @@ torch.manual_seed(0)
 class Actor(torch.nn.Module):
     def __init__(self, width):
         super().__init__()
-        self.trunk, self.fc1, self.head = Trunk(on=ON, cols=cols), torch.nn.Linear(width, 512), PolicyHead(512, AD)
+        self.trunk, self.fc1, self.head = Trunk(on=ON, cols=cols), Dense(width, 512, relu=True), PolicyHead(512, AD)
 
     def sample(self, frames, index):
-        action, log_prob, _, _ = self.head.sample(torch.relu(self.fc1(self.trunk(frames, index))))
+        action, log_prob, _, _ = self.head.sample(self.fc1(self.trunk(frames, index)))
         return action, log_prob
 
 
 class Critic(torch.nn.Module):
     def __init__(self, width):
         super().__init__()
-        self.trunk, self.head = Trunk(on=ON, cols=cols), QHead(width, AD, 512)
+        self.trunk, self.head = Trunk(on=ON, cols=cols), QHead(width, AD, 512, dense=True)
 
 
 gen = torch.Generator(device=dev).manual_seed(0)
@@ -75,8 +77,8 @@ def update():
     frames, s_idx, ns_idx, a, r, d, ok = env.replay.sample_frames(BATCH)
     with torch.no_grad():                                                    # :544-549
         next_a, next_logp = actor.sample(frames, ns_idx)
-        tv = td_target([t.trunk(frames, ns_idx) for t in targets], next_a, next_logp, r, d, *heads(targets), GAMMA, ALPHA)
-    q, _ = twin_q([c.trunk(frames, s_idx) for c in critics], a, *heads(critics))     # :551-552, a as the ring stores it (fp32)
+        tv = td_target([t.trunk(frames, ns_idx) for t in targets], next_a, next_logp, r, d, *heads(targets), GAMMA, ALPHA, dense=True)
+    q, _ = twin_q([c.trunk(frames, s_idx) for c in critics], a, *heads(critics), dense=True)     # :551-552, a as the ring stores it (fp32)
     c_losses = [F.mse_loss(q[0], tv), F.mse_loss(q[1], tv)]
     for opt in critic_opts:
         opt.zero_grad()
@@ -84,7 +86,7 @@ def update():
     for opt in critic_opts:
         opt.step()                                                           # :556-562 and, in the same pass, :575-578
     new_a, logp = actor.sample(frames, s_idx)                                 # :564-568
-    _, qn = twin_q([c.trunk(frames, s_idx) for c in critics], new_a, *heads(critics))
+    _, qn = twin_q([c.trunk(frames, s_idx) for c in critics], new_a, *heads(critics), dense=True)
     a_loss = (ALPHA * logp - qn).mean()
     actor_opt.zero_grad()
     a_loss.backward()

@@ -720,6 +720,51 @@ int f110_featconv_forward(const f110_featconv_config *cfg, const float *x, int64
 int f110_featconv_backward(const f110_featconv_config *cfg, const float *x, const float *out, const float *grad_out, int64_t n,
                            const float *weight, float *grad_x, float *grad_weight, float *grad_bias, float *workspace, void *stream);
 
+/* Dense layer of fp32 features, forward and backward: fc1 = nn.Linear(32 * 28 * 28, 512) of the reference's Actor and the feature
+ * columns of nn.Linear(32 * 28 * 28 + 16, 512) of its Critic (src/SAL.py:400, 408, 432, 440) with their ReLU, on the fp32 matrix
+ * cores.  Stateless (no handle; cfg host; all arrays dev); launches on `stream` of the calling thread's current device, no
+ * allocation, no synchronisation, no atomics.  x [n, K] fp32 contiguous (K = in_features), weight [H, K] fp32 (H = out_features)
+ * whose rows lie ld >= K elements apart -- a column view of a wider matrix, such as the feature columns of the critics' [H, F + A]
+ * weight; neither its base nor its rows need be 16-byte aligned -- bias [H] fp32 or NULL (= zeros), out [n, H] fp32.  n == 0 does
+ * nothing; F110_E_INVALID, not a launch, for n outside 0 .. 2^24, for a null required pointer with n > 0, for what
+ * f110_dense_validate refuses, and for a wrong device as f110_featconv_forward refuses it.
+ * Numerics, forward, in fp32.  K is cut into segments j = 0 .. ceil(K / S) - 1 of S = segment consecutive k's (the last may be
+ * shorter).  Per segment: acc_j = 0; for k ascending in the segment: acc_j = fmaf(x[r][k], weight[h][k], acc_j), one rounding per
+ * step.  Then sum = acc_0; sum = sum + acc_j for j ascending, plain fp32 adds.  Then out = sum + bias[h] (+ 0.0f for NULL); then
+ * out < 0 ? 0 : out if relu.  (A step padded to a multiple of 4 feeds 0 * 0, which leaves the never negative-zero acc as it is.)
+ * S belongs to the configuration, not to the launch: a row's result depends on x[r], the parameters and S alone -- not on n, on the
+ * row's place in the batch or on the grid -- and two calls give the same bits.  The launch plan either gives every segment a
+ * workgroup of its own, which writes acc_j to `workspace`, and adds them in a second kernel (small n), or lets one workgroup walk
+ * the segments and add in registers (large n); both give the same bits.  f110_dense_workspace: the bytes the FORWARD needs for n
+ * rows: ceil(K / S) * n * H * 4 on the first path, 0 on the second (then `workspace` may be NULL), 0 for an invalid configuration
+ * and for n outside 1 .. 2^24.  The first path is taken where K has more than one segment and ceil(n / 32) * ceil(H / 64) < 256.
+ * The workspace's contents before the call do not matter.
+ * f110_dense_backward: from x, out (the forward's result, read only where relu is set, for the mask), grad_out [n, H] and weight;
+ * each of grad_x [n, K], grad_weight [H, K] with the row stride ld (the elements between the rows are not touched) and grad_bias
+ * [H] may be NULL and is then skipped.  x is read only for grad_weight, weight only for grad_x.  With g = out > 0 ? grad_out : 0
+ * under relu, else g = grad_out:
+ *   grad_x[r][k]: acc = 0; for h ascending: acc = fmaf(g[r][h], weight[h][k], acc).
+ *   grad_weight[h][k]: acc = 0; for r ascending: acc = fmaf(g[r][h], x[r][k], acc).
+ *   grad_bias[h]: acc = 0; for r ascending: acc = acc + g[r][h].
+ * No workspace, no atomics: the order depends on the shape and n alone, two calls give the same bits, and a row's grad_x does not
+ * depend on the batch around it.
+ * f110_dense_validate: host only.  F110_E_INVALID for in_features outside 1 .. 2^20, out_features outside 1 .. 4096, ld below
+ * in_features, segment not a multiple of 4 in 4 .. 4096, and reserved other than 0. */
+typedef struct {
+    int32_t in_features;        /* K, 1 .. 2^20 */
+    int32_t out_features;       /* H, 1 .. 4096 */
+    int32_t ld;                 /* row stride of weight AND grad_weight in elements, >= K */
+    int32_t segment;            /* S: k's per chain, a multiple of 4 in 4 .. 4096 */
+    int32_t relu;               /* nonzero: max(out, 0), and its mask in the backward */
+    int32_t reserved;           /* 0 */
+} f110_dense_config;
+int f110_dense_validate(const f110_dense_config *cfg);
+int64_t f110_dense_workspace(const f110_dense_config *cfg, int64_t n);
+int f110_dense_forward(const f110_dense_config *cfg, const float *x, int64_t n, const float *weight, const float *bias, float *out,
+                       float *workspace, void *stream);
+int f110_dense_backward(const f110_dense_config *cfg, const float *x, const float *out, const float *grad_out, int64_t n,
+                        const float *weight, float *grad_x, float *grad_weight, float *grad_bias, void *stream);
+
 /* Policy head: the end of the reference's Actor.forward and Actor.sample (src/SAL.py:410-421) -- fc_mean and fc_log_std on the
  * features h of fc1, clamp(-20, 2), exp, rsample, tanh and the squashed-Gaussian log_prob summed over the action -- forward in one
  * kernel, and a backward without atomics.  Stateless (no handle; cfg host; all arrays dev); launches on `stream` of the calling

@@ -23,6 +23,9 @@ def __getattr__(name):
     if name in ('conv_feat', 'FeatConv2d', 'Trunk'):
         from . import featconv
         return getattr(featconv, name)
+    if name in ('linear_feat', 'Dense'):
+        from . import dense
+        return getattr(dense, name)
     if name in ('sample_actions', 'PolicyHead'):
         from . import policyhead
         return getattr(policyhead, name)

@@ -114,6 +114,12 @@ class FeatconvConfig(C.Structure):
                 ('kernel', C.c_int32), ('stride', C.c_int32), ('relu', C.c_int32), ('reserved', C.c_int32)]
 
 
+# f110_dense_config: a dense layer (fc1), forward and backward (stateless)
+class DenseConfig(C.Structure):
+    _fields_ = [('in_features', C.c_int32), ('out_features', C.c_int32), ('ld', C.c_int32), ('segment', C.c_int32),
+                ('relu', C.c_int32), ('reserved', C.c_int32)]
+
+
 # f110_policyhead_config: the policy head (fc_mean, fc_log_std and the sampling tail; stateless)
 class PolicyheadConfig(C.Structure):
     _fields_ = [('in_features', C.c_int32), ('action_dim', C.c_int32), ('out_fp64', C.c_int32)]
@@ -246,6 +252,10 @@ SYMBOLS = {
     'f110_featconv_workspace': [C.POINTER(FeatconvConfig), _I64],
     'f110_featconv_forward': [C.POINTER(FeatconvConfig), _VP, _I64, _VP, _VP, _VP, _VP],
     'f110_featconv_backward': [C.POINTER(FeatconvConfig), _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_dense_validate': [C.POINTER(DenseConfig)],
+    'f110_dense_workspace': [C.POINTER(DenseConfig), _I64],
+    'f110_dense_forward': [C.POINTER(DenseConfig), _VP, _I64, _VP, _VP, _VP, _VP, _VP],
+    'f110_dense_backward': [C.POINTER(DenseConfig), _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP],
     'f110_policyhead_validate': [C.POINTER(PolicyheadConfig)],
     'f110_policyhead_workspace': [C.POINTER(PolicyheadConfig), _I64],
     'f110_policyhead_forward': [C.POINTER(PolicyheadConfig), _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
@@ -313,6 +323,7 @@ def load():
     lib.f110_pure_pursuit_workspace.restype = C.c_int64
     lib.f110_bitconv_workspace.restype = C.c_int64
     lib.f110_featconv_workspace.restype = C.c_int64
+    lib.f110_dense_workspace.restype = C.c_int64
     lib.f110_policyhead_workspace.restype = C.c_int64
     lib.f110_qhead_workspace.restype = C.c_int64
     lib.f110_adam_state_bytes.restype = C.c_int64

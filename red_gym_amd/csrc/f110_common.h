@@ -12,6 +12,7 @@
 //   f110_policy_abi.hip the policy's and the critics' tails, stateless: policy head, critic head, and the parameter update (Adam and
 //                       the soft update of the targets)
 //   f110_featconv_abi.hip the trunk's dense convolutions (conv2, conv3), stateless: forward, grad_x, grad_weight / grad_bias
+//   f110_dense_abi.hip  the dense layer fc1, stateless: forward, grad_x, grad_weight, grad_bias
 //   f110_bitmap_abi.hip the scan's consumers with no handle: scan -> bitmap (its own f110_bitmap object), occupancy grid
 #pragma once
 #include "../../include/f110_hip.h"

@@ -2,7 +2,8 @@
 what SACAgent.update makes of two critics (:546-549) -- the action columns of fc1, bias, ReLU, fc2, the min over the twin critics and
 the TD target -- as one forward kernel and a deterministic backward, for one or two critics at once.  fc1(cat([f, a])) = f @ W[:, :F].T
 + a @ W[:, F:].T + b: the first term is one GEMM of the framework on the strided view W[:, :F]; the kernel takes the view W[:, F:] with
-its row stride, so neither the concatenated input nor a copy of the weight ever exists.  The action, next_log_prob, reward and done
+its row stride, so neither the concatenated input nor a copy of the weight ever exists (dense=True: that GEMM and its two backward
+GEMMs are the dense layer's kernels on the same view, red_gym_amd.dense, instead of the framework's).  The action, next_log_prob, reward and done
 arrive as the policy head and the replay ring produce them (fp64 or fp32, fp64, uint8).  There is no CPU path and no torch
 fallback: the kernels of libf110_hip.so do the work."""
 import ctypes as C
@@ -10,6 +11,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from . import dense as _dense
 
 MAX_HIDDEN, MAX_ACTION_DIM, MAX_CRITICS = 4096, 32, 2
 
@@ -64,19 +66,35 @@ def _launch_forward(cfg, pres, w1s, b1s, w2s, b2s, F, action, target_inputs=None
     return q, qmin, target
 
 
+def _feature_pre(feats, w1s, F, A, segment):
+    """pre[c] = feats[c] @ w1s[c][:, :F].T by f110_dense_forward on the view's address with ld = F + A -> (the config, the list)."""
+    H = int(w1s[0].shape[0])
+    cfg = _dense.validate(F, H, F + A, segment)
+    return cfg, [_dense.forward_into(cfg, f, w.data_ptr(), None, torch.empty((int(f.shape[0]), H), dtype=torch.float32, device=f.device))
+                 for f, w in zip(feats, w1s)]
+
+
 class _TwinQ(torch.autograd.Function):
-    """(q [C, n], qmin [n]) of C critics.  Arguments: action, C, then per critic feat, fc1.weight, fc1.bias, fc2.weight, fc2.bias."""
+    """(q [C, n], qmin [n]) of C critics.  Arguments: action, (C, the segment of the dense layer or None for the framework's GEMM), then
+    per critic feat, fc1.weight, fc1.bias, fc2.weight, fc2.bias."""
 
     @staticmethod
-    def forward(ctx, action, nc, *flat):
+    def forward(ctx, action, spec, *flat):
+        nc, segment = spec
         feats, w1s, b1s, w2s, b2s = (list(flat[k::5]) for k in range(5))
         F, A = int(feats[0].shape[1]), int(action.shape[1])
         cfg = validate(int(w1s[0].shape[0]), A, nc, F + A, action.dtype == torch.float64)
         act = action.detach().contiguous()
         w1s = [w.detach() for w in w1s]
         feats = [f.detach() for f in feats]
-        # the feature part of fc1: the framework's GEMM on the strided view W[:, :F] (no copy of the weight)
-        pres = [torch.mm(f, w[:, :F].t()) for f, w in zip(feats, w1s)]
+        ctx.dense = None
+        if segment is not None:
+            # the feature part of fc1 under the dense layer's contract, on the same view
+            feats = [f.contiguous() for f in feats]
+            ctx.dense, pres = _feature_pre(feats, w1s, F, A, segment)
+        else:
+            # the feature part of fc1: the framework's GEMM on the strided view W[:, :F] (no copy of the weight)
+            pres = [torch.mm(f, w[:, :F].t()) for f, w in zip(feats, w1s)]
         b1d, w2d, b2d = ([None if t is None else t.detach().contiguous() for t in ts] for ts in (b1s, w2s, b2s))
         q, qmin, _ = _launch_forward(cfg, pres, w1s, b1d, w2d, b2d, F, act)
         ctx.cfg, ctx.nc, ctx.F = cfg, nc, F
@@ -137,10 +155,15 @@ class _TwinQ(torch.autograd.Function):
         out[0] = ga
         for c in range(nc):
             nf, nw, _, _, _ = need_c[c]
-            if nf:
-                out[2 + 5 * c] = torch.mm(gpre[c], w1s[c][:, :F])
-            if nw:
-                torch.mm(gpre[c].t(), feats[c], out=gw1[c][:, :F])          # into the view: the feature columns of the one gradient
+            if ctx.dense is not None and (nf or nw):
+                # grad_feat, and the feature columns of the one gradient written with its row stride
+                out[2 + 5 * c] = torch.empty_like(feats[c]) if nf else None
+                _dense.backward_into(ctx.dense, feats[c], None, gpre[c], w1s[c].data_ptr(), out[2 + 5 * c], _ptr(gw1[c]), None)
+            elif nf or nw:
+                if nf:
+                    out[2 + 5 * c] = torch.mm(gpre[c], w1s[c][:, :F])
+                if nw:
+                    torch.mm(gpre[c].t(), feats[c], out=gw1[c][:, :F])      # into the view: the feature columns of the one gradient
             out[3 + 5 * c], out[4 + 5 * c], out[5 + 5 * c], out[6 + 5 * c] = gw1[c], gb1[c], gw2[c], gb2[c]
         return tuple(out)
 
@@ -182,7 +205,12 @@ def _flat(feats, fc1s, fc2s):
     return flat
 
 
-def twin_q(feats, action, fc1s, fc2s):
+def _segment(dense, segment):
+    """The _TwinQ spec's second entry: None for the framework's GEMM, else the dense layer's segment."""
+    return None if not dense else int(_dense.DEFAULT_SEGMENT if segment is None else segment)
+
+
+def twin_q(feats, action, fc1s, fc2s, dense=False, segment=None):
     """(q [C, n] fp32, qmin [n] fp32) of C = 1 or 2 critics: q[c] = fc2s[c](relu(fc1s[c](cat([feats[c], action], 1))))[:, 0] and
     qmin = min(q[0], q[1]) (C = 1: q[0]), differentiable in the features, the action and every parameter.
     feats: a list of C fp32 [n, F] tensors, each critic's own flattened conv3 output; action [n, A] fp64 (what the policy head and
@@ -192,16 +220,25 @@ def twin_q(feats, action, fc1s, fc2s):
     [H, F + A] gradient per fc1.weight is allocated; the framework's GEMM writes its feature columns through torch.mm(out=view) and
     the kernel its action columns with the row stride, so no zero-filled full-size temporaries are built and added.  The numerics are
     the contract of include/f110_hip.h; at a tie of the two critics each gets half of qmin's gradient, as torch.minimum gives.
-    ValueError for what f110_qhead_validate refuses and for a dtype, shape, device or contiguity mismatch."""
+    dense=True (opt-in; the default launches what it always did): the three GEMMs on the feature columns are the dense layer's
+    (red_gym_amd.dense, csrc/f110_dense.h) on the same views -- f110_dense_forward on the address of fc1.weight with ld = F + A, no
+    bias and no ReLU, for `pre`; f110_dense_backward for grad_feat and, with the row stride, for the feature columns of the one
+    gradient -- so every number of the critics is under the contract of include/f110_hip.h and a row's q does not depend on the
+    batch around it.  segment: the dense layer's k's per chain (None: dense.DEFAULT_SEGMENT).
+    ValueError for what f110_qhead_validate (and, with dense, f110_dense_validate) refuses and for a dtype, shape, device or
+    contiguity mismatch."""
     nc, F, A = _linears('twin_q', fc1s, fc2s, feats, action)
-    return _TwinQ.apply(action, nc, *_flat(feats, fc1s, fc2s))
+    seg = _segment(dense, segment)
+    if seg is not None:
+        _dense.validate(F, fc1s[0].out_features, F + A, seg)
+    return _TwinQ.apply(action, (nc, seg), *_flat(feats, fc1s, fc2s))
 
 
-def td_target(feats, next_action, next_log_prob, reward, done, fc1s, fc2s, gamma, alpha):
+def td_target(feats, next_action, next_log_prob, reward, done, fc1s, fc2s, gamma, alpha, dense=False, segment=None):
     """tv [n] fp32 of SACAgent.update (src/SAL.py:546-549) under no_grad: tv = reward + (1 - done) * gamma * (min(q1, q2) - alpha *
     next_log_prob), the last two lines in fp64 and rounded once.  feats, fc1s, fc2s as twin_q's, of the TARGET critics on the next
     state; next_action [n, A] and next_log_prob [n] or [n, 1] of one dtype (fp64 or fp32: the policy head's outputs); reward [n] fp64
-    and done [n] uint8 or bool as the ring's sample() returns them.  C GEMMs plus one launch."""
+    and done [n] uint8 or bool as the ring's sample() returns them.  C GEMMs plus one launch; dense, segment: as twin_q's."""
     who = 'td_target'
     nc, F, A = _linears(who, fc1s, fc2s, feats, next_action)
     n, dev = int(next_action.shape[0]), next_action.device
@@ -217,7 +254,11 @@ def td_target(feats, next_action, next_log_prob, reward, done, fc1s, fc2s, gamma
     with torch.no_grad():
         cfg = validate(fc1s[0].out_features, A, nc, F + A, next_action.dtype == torch.float64)
         w1s = [l.weight.detach() for l in fc1s]
-        pres = [torch.mm(f.detach(), w[:, :F].t()) for f, w in zip(feats, w1s)]
+        seg = _segment(dense, segment)
+        if seg is not None:
+            _, pres = _feature_pre([f.detach().contiguous() for f in feats], w1s, F, A, seg)
+        else:
+            pres = [torch.mm(f.detach(), w[:, :F].t()) for f, w in zip(feats, w1s)]
         d = done.detach().reshape(n).contiguous()
         d = d.view(torch.uint8) if d.dtype == torch.bool else d
         inputs = (reward.detach().reshape(n).contiguous(), d, next_log_prob.detach().reshape(n).contiguous(), gamma, alpha)
@@ -228,18 +269,19 @@ def td_target(feats, next_action, next_log_prob, reward, done, fc1s, fc2s, gamma
 
 class QHead(torch.nn.Module):
     """fc1 and fc2 of the reference's Critic (src/SAL.py:432-433) computed by twin_q.  Submodules fc1 = nn.Linear(F + A, H) and fc2 =
-    nn.Linear(H, 1), so a state dict has the reference's keys fc1.weight, fc1.bias, fc2.weight, fc2.bias."""
+    nn.Linear(H, 1), so a state dict has the reference's keys fc1.weight, fc1.bias, fc2.weight, fc2.bias.  dense, segment: as twin_q's."""
 
-    def __init__(self, in_features, action_dim=16, hidden=512, device=None):
+    def __init__(self, in_features, action_dim=16, hidden=512, device=None, dense=False, segment=None):
         super().__init__()
         validate(hidden, action_dim, 1)
+        self.dense, self.segment = bool(dense), segment
         if int(in_features) < 1:
             raise ValueError('QHead: in_features %d' % int(in_features))
         self.fc1 = torch.nn.Linear(int(in_features) + int(action_dim), int(hidden), device=device)
         self.fc2 = torch.nn.Linear(int(hidden), 1, device=device)
 
     @classmethod
-    def from_linears(cls, fc1, fc2):
+    def from_linears(cls, fc1, fc2, dense=False, segment=None):
         """A head that shares the parameters of a Critic's two layers (the same tensors: training one trains the other).  ValueError
         unless both are nn.Linear, fc2 is fc1.out_features -> 1 and f110_qhead_validate accepts the hidden width."""
         who = 'QHead.from_linears'
@@ -251,10 +293,11 @@ class QHead(torch.nn.Module):
         m = cls.__new__(cls)
         torch.nn.Module.__init__(m)
         m.fc1, m.fc2 = fc1, fc2
+        m.dense, m.segment = bool(dense), segment
         return m
 
     def forward(self, feat, action):
         """q [n, 1] fp32 of Critic.forward behind conv3: feat [n, F] fp32 (the flattened features), action [n, A] fp64 or fp32 with F +
         A = fc1.in_features; differentiable."""
-        q, _ = twin_q([feat], action, [self.fc1], [self.fc2])
+        q, _ = twin_q([feat], action, [self.fc1], [self.fc2], dense=self.dense, segment=self.segment)
         return q[0].unsqueeze(1)
