@@ -24,8 +24,14 @@ CASES = [
     (8, 8, 40, 64, 2, 1),       # four N-tiles, Co k^2 large
     (4, 16, 60, 20, 4, 4),      # windows that do not overlap
     (32, 6, 6, 8, 4, 3),        # Ci k^2 = 512; two rows and two columns of x no window reaches
+    # kernel < stride: between two windows lie input pixels that no window reaches (holes()); grad_x is +0 there
+    (3, 9, 11, 5, 1, 2),        # k = 1: every odd row and column is a hole, none is left over at the edge; K = 3 and grad_x's K = 5, one padded chunk each
+    (4, 10, 13, 6, 2, 3),       # one row and column in three a hole, and two of each left over at the edge; the partials' K = 16 is one whole N-tile
+    (2, 12, 14, 4, 3, 4),       # stride 4; grad_x's K = 36 takes two chunks, the partials two N-tiles; one row and three columns left over
+    (5, 8, 9, 3, 1, 4),         # k = 1 under stride 4: three rows in four are holes; three rows left over, no column
 ]
 CONV3, CONV2 = CASES[0], CASES[1]
+GAP_CASES = [c for c in CASES if c[4] < c[5]]
 # the recordings of the reference's own Actor: the row fed as raw 0 / 255 floats, the row fed as / 255 (tests/golden/make_golden_trunk.py)
 GOLDEN = ('g22_trunk.npz', 'g22_trunk_unit.npz')
 
@@ -44,6 +50,17 @@ VARIANTS = ((True, True), (False, False), (True, False), (False, True))
 
 def out_size(h, w, k, s):
     return (h - k) // s + 1, (w - k) // s + 1
+
+
+def holes(h, w, k, s):
+    """(the [h, w] mask of the input pixels no window reaches, the mask of those that lie inside the rectangle the windows span: between
+    two windows, not behind the last one)."""
+    oh, ow = out_size(h, w, k, s)
+    rows = (np.arange(h) % s < k) & (np.arange(h) < (oh - 1) * s + k)
+    cols = (np.arange(w) % s < k) & (np.arange(w) < (ow - 1) * s + k)
+    unreached = ~(rows[:, None] & cols[None, :])
+    inside = (np.arange(h) < (oh - 1) * s + k)[:, None] & (np.arange(w) < (ow - 1) * s + k)[None, :]
+    return unreached, unreached & inside
 
 
 def gemm_lds(ktot, planes, nr, xw):

@@ -155,7 +155,9 @@ def test_checkers_within_twice_gamma_mag_of_the_reference(golden, name):
 
 def test_every_case_selects_what_it_claims():
     P = {c: fc.paths(*c) for c in fc.CASES}
-    conv3, conv2, odd, one, pixel, three, four, apart, full = (P[c] for c in fc.CASES)
+    conv3, conv2, odd, one, pixel, three, four, apart, full, gap1, gap2, gap3, gap4 = (P[c] for c in fc.CASES)
+    assert fc.GAP_CASES == fc.CASES[9:] == [(3, 9, 11, 5, 1, 2), (4, 10, 13, 6, 2, 3), (2, 12, 14, 4, 3, 4), (5, 8, 9, 3, 1, 4)]
+    assert all(c[4] >= c[5] for c in fc.CASES[:9])
     for p in P.values():
         assert max(p['lds'], p['gx_lds'], p['gw_lds']) <= fc.FC_LDS_BYTES and p['xw'] <= 64 and p['gx_xw'] <= 67
     assert (conv3['oh'], conv3['ow'], conv3['ktot'], conv3['chunks'], conv3['NT'], conv3['br'], conv3['bands']) == (28, 28, 288, 9, 2, 14, 2)
@@ -174,6 +176,27 @@ def test_every_case_selects_what_it_claims():
     assert four['NT'] == 4 and four['gw_MT'] == 4 and four['gx_ktot'] == 256 and four['gx_bands'] == 2 and four['gw_bands'] == 2 and four['jobs'] == 20
     assert apart['gx_dilated'] and apart['NT'] == 2 and apart['gx_bands'] == 2 and (apart['unused_rows'], apart['unused_cols']) == (0, 0)
     assert (full['ktot'], full['chunks'], full['gw_NT'], full['gw_groups'], full['gw_idle_waves']) == (512, 16, 32, 4, 0) and (full['unused_rows'], full['unused_cols']) == (2, 2)
+    # kernel < stride: grad_x runs over a dilated g whose taps leave pixels between the windows untouched; every one of them is one
+    # band, one padded chunk forward and a partial M- and N-tile, so what differs is the stride, the gaps and K
+    for c, p in zip(fc.GAP_CASES, (gap1, gap2, gap3, gap4)):
+        ci, h, w, co, k, s = c
+        assert k < s and p['gx_dilated'] and p['kpad'] and p['gx_kpad'] and p['partial_m'] and p['partial_n'] and p['gx_partial_m'] and p['gx_partial_n']
+        assert (p['bands'], p['gx_bands'], p['gw_bands'], p['chunks']) == (1, 1, 1, 1) and p['xw'] == (p['ow'] - 1) * s + k <= w
+        reached = np.zeros((h, w), bool)                              # from the windows themselves
+        for oy in range(p['oh']):
+            for ox in range(p['ow']):
+                reached[s * oy:s * oy + k, s * ox:s * ox + k] = True
+        unreached, inside = fc.holes(h, w, k, s)
+        assert np.array_equal(unreached, ~reached) and inside.sum() > 0 and not (inside & reached).any()
+        assert inside.sum() == (h - p['unused_rows']) * (w - p['unused_cols']) - reached.sum()
+    assert [(int(fc.holes(c[1], c[2], c[4], c[5])[1].sum()), int(fc.holes(c[1], c[2], c[4], c[5])[0].sum())) for c in fc.GAP_CASES] == [(69, 69), (40, 82), (40, 87), (39, 66)]
+    assert all(not fc.holes(c[1], c[2], c[4], c[5])[1].any() for c in fc.CASES[:9])        # k >= s: no pixel between two windows is skipped
+    assert (gap1['oh'], gap1['ow'], gap1['ktot'], gap1['gx_ktot'], gap1['unused_rows'], gap1['unused_cols'], gap1['MT']) == (5, 6, 3, 5, 0, 0, 2)
+    assert (gap2['oh'], gap2['ow'], gap2['ktot'], gap2['gx_ktot'], gap2['unused_rows'], gap2['unused_cols']) == (3, 4, 16, 24, 2, 2)
+    assert (gap2['gw_NT'], gap2['gw_partial_n'], gap2['gw_kpad']) == (1, False, False)
+    assert (gap3['oh'], gap3['ow'], gap3['ktot'], gap3['gx_ktot'], gap3['gx_chunks'], gap3['gw_NT'], gap3['unused_rows'], gap3['unused_cols']) == (3, 3, 18, 36, 2, 2, 1, 3)
+    assert (gap4['oh'], gap4['ow'], gap4['ktot'], gap4['gx_ktot'], gap4['unused_rows'], gap4['unused_cols'], gap4['gw_kpad']) == (2, 3, 5, 3, 3, 0, True)
+    assert {c[5] - c[4] for c in fc.GAP_CASES} == {1, 3} and {c[5] for c in fc.GAP_CASES} == {2, 3, 4} and {c[4] for c in fc.GAP_CASES} == {1, 2, 3}
     # together: one to four N-tiles forward, every instantiation of the partials' kernel, one and several bands with a short last
     # one in all three kernels, padded and whole K in all three, one to four workgroups per sample of partials
     assert {p['NT'] for p in P.values()} == {1, 2, 3, 4} and {p['gw_MT'] for p in P.values()} == {1, 2, 3, 4}

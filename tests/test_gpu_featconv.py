@@ -96,6 +96,23 @@ def test_backward_equals_checker_and_repeats(case):
     assert _differing(x.grad, r['grad_x']) == 0
 
 
+@pytest.mark.parametrize('case', fc.GAP_CASES)
+def test_grad_x_is_plus_zero_where_no_window_reaches(case):
+    """kernel < stride: the input pixels between two windows (fc.holes) get no term; grad_x is +0 there as a bit pattern, through
+    conv_feat and through the raw ABI into a buffer of sentinels, and not zero everywhere else; the whole array `==` the checker."""
+    ci, h, wd, co, k, s = case
+    unreached, inside = fc.holes(h, wd, k, s)
+    assert inside.sum() > 0 and unreached.sum() >= inside.sum() and not unreached.all()
+    r = fc.reference(case, 3, False)
+    assert (bc.bit_patterns(r['grad_x'][:, :, unreached]) == 0).all() and (r['grad_x'][:, :, ~unreached] != 0).any()
+    _, gx, _, _ = _backward(case, r, False)
+    raw = _Raw(case, False)
+    gx_raw = raw.backward(_dev(r['x']), None, _dev(r['grad_out']), _dev(r['w']), 3, want=(True, False, False), with_ws=False)[0].reshape(r['x'].shape)
+    for got in (_np(gx), gx_raw):
+        assert int((bc.bit_patterns(got[:, :, inside]) != 0).sum()) == 0 and int((bc.bit_patterns(got[:, :, unreached]) != 0).sum()) == 0
+        assert _differing(got, r['grad_x']) == 0
+
+
 class _Raw:
     """The two entry points themselves on buffers of SENTINEL with 64 guard floats either side of every output."""
 

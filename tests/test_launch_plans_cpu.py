@@ -485,6 +485,15 @@ def test_qhead_tables(lib, hip):
 def test_featconv_tables(lib, hip):
     for s in fc.CASES:
         assert check_featconv(lib, hip, s, 3)
+    # kernel < stride: the staged width is what the windows span (it skips the gap behind the last one), grad_x stages all of x's
+    # columns plus k - 1, and each is one band in all three kernels
+    assert len(fc.GAP_CASES) == 4 and all(s in fc.CASES for s in fc.GAP_CASES)
+    for s in fc.GAP_CASES:
+        ci, h, wd, co, k, st = s
+        p = check_featconv(lib, hip, s, 3)
+        assert k < st and (p['xw'], p['gw_xw'], p['gx_xw']) == ((p['ow'] - 1) * st + k, (p['ow'] - 1) * st + k, wd + k - 1), s
+        assert (p['bands'], p['gx_bands'], p['gw_bands'], p['gx_ph'], p['gx_pw']) == (1, 1, 1, h, wd), s
+        assert (p['nr'], p['gx_nr'], p['gw_nr']) == ((p['oh'] - 1) * st + k, h + k - 1, (p['oh'] - 1) * st + k), s
     p = check_featconv(lib, hip, fc.LOOP_CASE, fc.LOOP_N)
     assert p['items'] > p['grid'] == fc.FC_MAX_GRID and p['gx_items'] > p['gx_grid'] and fc.LOOP_N > p['gw_grid'] == fc.FC_MAX_GRID
 
