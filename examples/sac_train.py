@@ -1,0 +1,46 @@
+"""The training loop of the reference's RL consumer (main(), src/SAL.py:975-1019) for many envs at once, everything on the GPU:
+    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every]
+    select_action (the policy on the shaper's bitmap) -> path_actions (SAL's action decode and MPC step, which also hands the raw
+    action to the ring) -> step (scan, shaper, the ring's push) -> after update_after steps, every update_every steps, one SACAgent
+    update replayed from a graph: the batch is drawn on the device, the losses stay there.
+The defaults are small, so that it finishes in seconds; the reference's are batch 64, update_after 1000, update_every 50.  The loss
+tensor is read (one synchronisation) only where it is printed.  At the end the actor is saved under the reference's keys, as main()
+saves sac_actor.pth."""
+import os
+import sys
+import tempfile
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from red_gym_amd import F110VecEnv, SACAgent, workload
+
+arg = lambda i, default: int(sys.argv[i]) if len(sys.argv) > i else default  # noqa: E731
+B, STEPS, BATCH, UPDATE_AFTER, UPDATE_EVERY = arg(1, 64), arg(2, 48), arg(3, 64), arg(4, 16), arg(5, 4)
+AD = 16
+env = F110VecEnv(B, map=workload.EXAMPLE_MAP, num_agents=1, autoreset=True)
+env.shape_rewards()
+env.follow_paths()
+env.record_replay(capacity=16 * B, action_dim=AD)
+dev, cfg = env.device, env.eng.shaper.cfg
+torch.manual_seed(0)
+agent = SACAgent(action_dim=AD, rows=cfg.rows, cols=cfg.cols, device=dev)
+raw = torch.zeros((B, AD), dtype=torch.float64, device=dev)                    # the policy's action, written in place
+obs, reward, done, info = env.reset(torch.as_tensor(workload.spawn_poses(B, 1), device=dev))
+total = torch.zeros((B,), dtype=torch.float64, device=dev)
+updates = 0
+for step in range(1, STEPS + 1):
+    agent.select_action(info['lidar_bitmap'], out=raw)
+    obs, reward, done, info = env.step(env.path_actions(raw))
+    total += reward
+    if step > UPDATE_AFTER and step % UPDATE_EVERY == 0:
+        if updates == 0:
+            agent.capture_update(env.replay, BATCH)
+        losses = agent.update_graph()
+        updates += 1
+        if updates % 4 == 1:
+            print('step %3d, update %2d: losses (actor, critic 1, critic 2) %s' % (step, updates, ' '.join('%.6f' % v for v in losses.tolist())))
+print('%d steps of %d envs, %d updates of batch %d, captures %d; %d of %d transitions valid; mean reward per step %.4f' % (
+    STEPS, B, updates, BATCH, agent.captures, len(env.replay), env.replay.steps * B, float(total.mean()) / STEPS))
+path = os.path.join(tempfile.mkdtemp(), 'sac_actor.pth')
+torch.save({k: v.cpu() for k, v in agent.actor_state_dict().items()}, path)
+print('actor saved as %s (%d tensors under the reference\'s keys)' % (path, len(torch.load(path))))
+env.close()

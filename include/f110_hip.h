@@ -609,6 +609,15 @@ int f110_replay_gather(f110_handle *h, const int64_t *indices, int32_t n, void *
  * [(T + 1) * B, rows, words], that hold the transition's frame before (s_frame [n]) and its frame after (ns_frame [n], both dev
  * int64); -1 for both where the gather writes zeros.  It reads count on the device like every replay kernel (capturable). */
 int f110_replay_locate(f110_handle *h, const int64_t *indices, int32_t n, int64_t *s_frame, int64_t *ns_frame, void *stream);
+/* f110_replay_sample: a whole batch in one kernel from a draw counter that lives on the device, so that a captured sample replays
+ * with fresh draws.  counter [1] dev uint64 is the caller's (8-byte aligned; start at 0): draw i of the call is draw number
+ * counter[0] + i of the stream `seed`, drawn exactly as f110_replay_draw draws it with first_draw = counter[0]; indices [n] is what
+ * that draw gives, s_frame and ns_frame [n] what f110_replay_locate gives for it, a [n, action_dim] fp32, r [n] fp64, d [n] and ok
+ * [n] uint8 what f110_replay_gather gives (-1, -1, zeros and ok = 0 where the draw found no valid transition).  A one-lane kernel
+ * behind it adds n to the counter: no lane reads a counter that has moved.  All arrays dev; two launches on `stream`, no
+ * allocation, no synchronisation.  The handle keeps no draw counter: f110_replay_draw's first_draw stays the caller's host value. */
+int f110_replay_sample(f110_handle *h, uint64_t seed, uint64_t *counter, int32_t n, int64_t *indices, int64_t *s_frame, int64_t *ns_frame,
+                       float *a, double *r, uint8_t *d, uint8_t *ok, void *stream);
 
 /* First convolution of the policy from bits: the nn.Conv2d(1, C, kernel, stride) that opens the reference's Actor and Critic
  * (src/SAL.py:397, 429) on an image of two values, forward and backward, stateless (no handle; cfg host; all arrays dev; launches
@@ -917,6 +926,26 @@ int64_t f110_adam_state_bytes(void);
 int f110_adam_step(const f110_adam_config *cfg, const f110_adam_tensor *table, int32_t n_tensors, f110_adam_state *state, double lr,
                    void *stream);
 int f110_soft_update(const f110_adam_tensor *table, int32_t n_tensors, double tau, void *stream);
+
+/* The two losses of SACAgent.update (src/SAL.py:553-554, :568) and their gradients with respect to the arrays given, one launch each,
+ * stateless (all arrays dev, n rows, 1 <= n <= 2^24; launches on `stream` of the calling thread's current device, no allocation, no
+ * synchronisation, no atomics).  Neither knows of autograd: the caller hands the gradients to the layers behind q, log_prob and min_q.
+ * The sum of every loss, over terms t_i in fp64: chain l (0 <= l < 256) S_l = ((0.0 + t_l) + t_{l + 256}) + ... over i = l mod 256
+ * ascending (0.0 for a chain without a term); then for s = 128, 64, .., 1: S_l = S_l + S_{l + s} for every l < s; loss = float(S_0 /
+ * double(n)).  Every + is one fp64 addition, the division one fp64 division, rounded to fp32 once; nothing is contracted.  n alone fixes
+ * the order, whatever the launch's shape.
+ * f110_sac_critic_loss: q1, q2, tv [n] fp32 -> loss [2] fp32 = mean((q_c - tv)^2) with e = double(q_c[i]) - double(tv[i]), t_i = e * e;
+ * grad_q1, grad_q2 [n] fp32 (either may be NULL) = (q_c[i] - tv[i]) * k in fp32, one subtraction and one multiplication, k = float(2.0 /
+ * double(n)).
+ * f110_sac_actor_loss: logp [n] fp64 (logp_fp64 nonzero) or fp32, qn [n] fp32 -> loss [1] fp32 = mean(alpha * logp - qn) with m =
+ * alpha * double(logp[i]), t_i = m - double(qn[i]); grad_logp [n] of logp's type = alpha / double(n) (rounded to fp32 from that for
+ * fp32) and grad_qn [n] fp32 = float(-1.0 / double(n)) (either may be NULL).
+ * Where n is a power of two every gradient equals what autograd gives for F.mse_loss and for (alpha * logp - qn).mean(), bit for bit.
+ * F110_E_INVALID, before any launch: n outside 1 .. 2^24, a null input or loss, alpha not finite, logp or grad_logp not aligned to its
+ * type, and a wrong device as f110_policyhead_forward refuses it. */
+int f110_sac_critic_loss(const float *q1, const float *q2, const float *tv, int64_t n, float *loss, float *grad_q1, float *grad_q2, void *stream);
+int f110_sac_actor_loss(const void *logp, int32_t logp_fp64, const float *qn, double alpha, int64_t n, float *loss, void *grad_logp,
+                        float *grad_qn, void *stream);
 
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).

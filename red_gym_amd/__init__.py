@@ -35,4 +35,10 @@ def __getattr__(name):
     if name in ('SacAdam', 'soft_update'):
         from . import optim
         return getattr(optim, name)
+    if name in ('critic_loss', 'actor_loss'):
+        from . import sacloss
+        return getattr(sacloss, name)
+    if name == 'SACAgent':
+        from .sac import SACAgent
+        return SACAgent
     raise AttributeError(name)

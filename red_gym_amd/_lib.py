@@ -240,6 +240,7 @@ SYMBOLS = {
     'f110_replay_draw': [_VP, C.c_uint64, C.c_uint64, _I32, _VP, _VP, _VP],
     'f110_replay_gather': [_VP, _VP, _I32, _VP, _VP, _I32, _D, _VP, _VP, _VP, _VP, _VP],
     'f110_replay_locate': [_VP, _VP, _I32, _VP, _VP, _VP],
+    'f110_replay_sample': [_VP, C.c_uint64, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_bitconv_validate': [C.POINTER(BitconvConfig)],
     'f110_bitconv_workspace': [C.POINTER(BitconvConfig), _I64],
     'f110_bitconv_forward': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP],
@@ -268,6 +269,8 @@ SYMBOLS = {
     'f110_adam_state_bytes': [],
     'f110_adam_step': [C.POINTER(AdamConfig), C.POINTER(AdamTensor), _I32, _VP, _D, _VP],
     'f110_soft_update': [C.POINTER(AdamTensor), _I32, _D, _VP],
+    'f110_sac_critic_loss': [_VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP],
+    'f110_sac_actor_loss': [_VP, _I32, _VP, _D, _I64, _VP, _VP, _VP, _VP],
     'f110_replay_pack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_replay_unpack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],

@@ -9,8 +9,8 @@
 //   f110_consumers.hip  the callers either side of the step, on the handle: pure-pursuit planner, progress tracker, reward shaper,
 //                       path follower, replay buffer
 //   f110_bitconv_abi.hip the policy's first layers from bits, stateless: bit convolution, policy stem
-//   f110_policy_abi.hip the policy's and the critics' tails, stateless: policy head, critic head, and the parameter update (Adam and
-//                       the soft update of the targets)
+//   f110_policy_abi.hip the policy's and the critics' tails, stateless: policy head, critic head, the parameter update (Adam and
+//                       the soft update of the targets) and the two losses of a SAC update
 //   f110_featconv_abi.hip the trunk's dense convolutions (conv2, conv3), stateless: forward, grad_x, grad_weight / grad_bias
 //   f110_dense_abi.hip  the dense layer fc1, stateless: forward, grad_x, grad_weight, grad_bias
 //   f110_bitmap_abi.hip the scan's consumers with no handle: scan -> bitmap (its own f110_bitmap object), occupancy grid

@@ -791,6 +791,27 @@ extern "C" int f110_replay_locate(f110_handle *h, const int64_t *indices, int32_
     return F110_OK;
 }
 
+extern "C" int f110_replay_sample(f110_handle *h, uint64_t seed, uint64_t *counter, int32_t n, int64_t *indices, int64_t *s_frame, int64_t *ns_frame,
+                                  float *a_out, double *r_out, uint8_t *d_out, uint8_t *ok, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_replay_sample: null handle");
+    ReplaySampleArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = replay_ready(h, "f110_replay_sample", a.ring)) return rc;
+    if (n < 0 || !counter || !indices || !s_frame || !ns_frame || !a_out || !r_out || !d_out || !ok)
+        return fail(F110_E_INVALID, "f110_replay_sample: bad arguments");
+    if ((uintptr_t)counter % 8) return fail(F110_E_INVALID, "f110_replay_sample: the counter is not 8-byte aligned");
+    if (n == 0) return F110_OK;
+    a.seed = seed; a.counter = (const unsigned long long *)counter; a.n = n;
+    a.idx = (long long *)indices; a.s_frame = (long long *)s_frame; a.ns_frame = (long long *)ns_frame;
+    a.a = a_out; a.r = r_out; a.d = d_out; a.ok = ok;
+    hipLaunchKernelGGL(replay_sample_kernel, dim3((unsigned)((n + REPLAY_THREADS - 1) / REPLAY_THREADS)), dim3(REPLAY_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(replay_counter_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long *)counter, (unsigned long long)n);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
 static int replay_pack_args(const char *who, const void *in, const void *out, int64_t n, int32_t rows, int32_t cols)
 {
     if (n < 0 || n > 0x7fffffff || rows < 1 || cols < 1 || rows > REPLAY_MAX_DIM || cols > REPLAY_MAX_DIM)

@@ -3,6 +3,7 @@
 #include "f110_policyhead.h"
 #include "f110_qhead.h"
 #include "f110_adam.h"
+#include "f110_sacloss.h"
 
 // ---------------------------------------------------------------- policy head: fc_mean, fc_log_std and the sampling tail
 extern "C" int f110_policyhead_validate(const f110_policyhead_config *cfg) { return policyhead_check(cfg, "f110_policyhead_validate"); }
@@ -254,6 +255,51 @@ extern "C" int f110_soft_update(const f110_adam_tensor *table, int32_t n_tensors
     if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
     tab.tau = (float)tau;
     hipLaunchKernelGGL((adam_kernel<false, true>), dim3(grid), dim3(AD_THREADS), 0, (hipStream_t)stream, tab, (const AdamState *)nullptr);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+// ---------------------------------------------------------------- the two losses of a SAC update and their gradients
+static int sacloss_rows(const char *who, int64_t n)
+{
+    if (n < 1 || n > SL_MAX_ROWS) return fail(F110_E_INVALID, "%s: n=%lld rows (1..%lld)", who, (long long)n, (long long)SL_MAX_ROWS);
+    return F110_OK;
+}
+
+extern "C" int f110_sac_critic_loss(const float *q1, const float *q2, const float *tv, int64_t n, float *loss, float *grad_q1, float *grad_q2,
+                                    void *stream)
+{
+    const char *who = "f110_sac_critic_loss";
+    if (int rc = sacloss_rows(who, n)) return rc;
+    if (!q1 || !q2 || !tv || !loss) return fail(F110_E_INVALID, "%s: null pointer", who);
+    std::vector<DevicePtr> ptrs = {{"q1", q1}, {"q2", q2}, {"tv", tv}, {"loss", loss}};
+    if (grad_q1) ptrs.push_back({"grad_q1", grad_q1});
+    if (grad_q2) ptrs.push_back({"grad_q2", grad_q2});
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
+    SaclossPlan p = sacloss_plan(n, false, false, 0.0);
+    p.a.q1 = q1; p.a.q2 = q2; p.a.tv = tv; p.a.loss = loss; p.a.grad_q1 = grad_q1; p.a.grad_q2 = grad_q2;
+    F110_LAUNCH(sac_critic_loss_kernel, p.l, (hipStream_t)stream, p.a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_sac_actor_loss(const void *logp, int32_t logp_fp64, const float *qn, double alpha, int64_t n, float *loss, void *grad_logp,
+                                   float *grad_qn, void *stream)
+{
+    const char *who = "f110_sac_actor_loss";
+    if (int rc = sacloss_rows(who, n)) return rc;
+    if (!logp || !qn || !loss) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (!std::isfinite(alpha)) return fail(F110_E_INVALID, "%s: alpha is not finite", who);
+    if ((uintptr_t)logp % (logp_fp64 ? 8 : 4) || (uintptr_t)grad_logp % (logp_fp64 ? 8 : 4))
+        return fail(F110_E_INVALID, "%s: logp or grad_logp is not aligned to its type", who);
+    std::vector<DevicePtr> ptrs = {{"logp", logp}, {"qn", qn}, {"loss", loss}};
+    if (grad_logp) ptrs.push_back({"grad_logp", grad_logp});
+    if (grad_qn) ptrs.push_back({"grad_qn", grad_qn});
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
+    SaclossPlan p = sacloss_plan(n, true, logp_fp64 != 0, alpha);
+    p.a.logp = logp; p.a.qn = qn; p.a.loss = loss; p.a.grad_logp = grad_logp; p.a.grad_qn = grad_qn;
+    if (p.l.inst == 2) F110_LAUNCH(sac_actor_loss_kernel<true>, p.l, (hipStream_t)stream, p.a);
+    else F110_LAUNCH(sac_actor_loss_kernel<false>, p.l, (hipStream_t)stream, p.a);
     HIP_TRY(hipGetLastError());
     return F110_OK;
 }

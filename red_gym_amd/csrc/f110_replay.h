@@ -11,6 +11,9 @@
 //   replay_draw_kernel     one lane per draw: splitmix64 candidates over the stored transitions, the first valid one wins
 //   replay_gather_kernel   one wave per (sample, frame, 4 rows): bits back to uint8 (4 pixels = one 4-byte store per lane) or fp32
 //   replay_locate_kernel   one lane per index: where the gather would read, for consumers that read the bits themselves (f110_bitconv.h)
+//   replay_sample_kernel   one lane per draw: the draw, the locate and the gather's tail in one, from a draw counter that lives on the
+//                          device (the caller's), so that a captured sample replays with fresh draws
+//   replay_counter_advance_kernel  one lane: counter += n, behind the sample
 #pragma once
 #include "../../include/f110_hip.h" // F110_REPLAY_TRIES
 #include "f110_bounds.h"
@@ -179,6 +182,17 @@ struct ReplayDrawArgs {
     uint8_t *ok;                    // [n]
 };
 
+struct ReplaySampleArgs {
+    ReplayRing ring;
+    unsigned long long seed;
+    const unsigned long long *counter; // [1] draws made so far, on the device: draw i of this launch is draw number *counter + i
+    int n;
+    long long *idx, *s_frame, *ns_frame; // [n]
+    float *a;                       // [n, action_dim]
+    double *r;                      // [n]
+    uint8_t *d, *ok;                // [n]
+};
+
 struct ReplayGatherArgs {
     ReplayRing ring;
     const long long *idx;           // [n]
@@ -232,27 +246,31 @@ static __global__ void replay_advance_kernel(long long *count)
     if (threadIdx.x == 0 && blockIdx.x == 0) *count += 1;
 }
 
-static __global__ __launch_bounds__(REPLAY_THREADS) void replay_draw_kernel(ReplayDrawArgs a)
+// Draw number j of the stream `seed` over the ring as `count` stands: the first of F110_REPLAY_TRIES splitmix64 candidates whose
+// transition is valid, or -1.  What the draw and the sample share.
+__device__ inline long long replay_pick(const ReplayRing &g, unsigned long long seed, unsigned long long j)
 {
-    const ReplayRing &g = a.ring;
-    const int i = blockIdx.x * REPLAY_THREADS + threadIdx.x;
-    if (i >= a.n) return;
     const long long count = *g.count;
     const long long stored = count < 0 ? 0 : (count < g.steps ? count : g.steps);
     const unsigned long long total = (unsigned long long)stored * (unsigned long long)g.n_envs;
-    long long pick = -1;
-    if (total > 0) {
-        const unsigned long long j = a.first + (unsigned long long)i;
-        for (int k = 0; k < F110_REPLAY_TRIES; k++) {
-            const unsigned long long z = replay_splitmix64(a.seed + 0x9E3779B97F4A7C15ull * (1ull + j * (unsigned long long)F110_REPLAY_TRIES + (unsigned long long)k));
-            const unsigned long long cand = __umul64hi(z, total);
-            const long long age = (long long)(cand / (unsigned long long)g.n_envs), env = (long long)(cand % (unsigned long long)g.n_envs);
-            const long long slot = (count - 1 - age) % g.steps;
-            F110_BCHK(age < stored && slot >= 0 && slot < g.steps, BT_REPLAY, g.dev_err);
-            const long long id = slot * g.n_envs + env;
-            if (g.valid[id]) { pick = id; break; }
-        }
+    if (total == 0) return -1;
+    for (int k = 0; k < F110_REPLAY_TRIES; k++) {
+        const unsigned long long z = replay_splitmix64(seed + 0x9E3779B97F4A7C15ull * (1ull + j * (unsigned long long)F110_REPLAY_TRIES + (unsigned long long)k));
+        const unsigned long long cand = __umul64hi(z, total);
+        const long long age = (long long)(cand / (unsigned long long)g.n_envs), env = (long long)(cand % (unsigned long long)g.n_envs);
+        const long long slot = (count - 1 - age) % g.steps;
+        F110_BCHK(age < stored && slot >= 0 && slot < g.steps, BT_REPLAY, g.dev_err);
+        const long long id = slot * g.n_envs + env;
+        if (g.valid[id]) return id;
     }
+    return -1;
+}
+
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_draw_kernel(ReplayDrawArgs a)
+{
+    const int i = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (i >= a.n) return;
+    const long long pick = replay_pick(a.ring, a.seed, a.first + (unsigned long long)i);
     a.idx[i] = pick;
     a.ok[i] = pick >= 0 ? 1 : 0;
 }
@@ -305,6 +323,35 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_locate_kernel(Re
     const bool ok = replay_resolve(g, idx[i], c, env);
     s_frame[i] = ok ? ((c - 1) % (g.steps + 1)) * g.n_envs + env : -1;
     ns_frame[i] = ok ? (c % (g.steps + 1)) * g.n_envs + env : -1;
+}
+
+// one lane per draw: draw number *counter + i (replay_pick), where its two frames lie (the locate) and its action, reward and done
+// (the gather's tail); -1, -1 and zeros with ok = 0 where no valid transition was found.  Every lane reads the counter; nothing in
+// this launch writes it (replay_counter_advance_kernel behind it does).
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_sample_kernel(ReplaySampleArgs a)
+{
+    const ReplayRing &g = a.ring;
+    const int i = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (i >= a.n) return;
+    const unsigned long long first = *a.counter;
+    const long long id = replay_pick(g, a.seed, first + (unsigned long long)i);
+    long long c = 0;
+    int env = 0;
+    const bool ok = replay_resolve(g, id, c, env);
+    F110_BCHK(!ok || (id >= 0 && id < g.steps * g.n_envs), BT_REPLAY, g.dev_err);
+    a.idx[i] = id;
+    a.s_frame[i] = ok ? ((c - 1) % (g.steps + 1)) * g.n_envs + env : -1;
+    a.ns_frame[i] = ok ? (c % (g.steps + 1)) * g.n_envs + env : -1;
+    for (int k = 0; k < g.action_dim; k++)
+        a.a[(size_t)i * (size_t)g.action_dim + (size_t)k] = ok ? g.actions[(size_t)id * (size_t)g.action_dim + (size_t)k] : 0.0f;
+    a.r[i] = ok ? g.rewards[id] : 0.0;
+    a.d[i] = ok ? g.dones[id] : (uint8_t)0;
+    a.ok[i] = ok ? 1 : 0;
+}
+
+static __global__ void replay_counter_advance_kernel(unsigned long long *counter, unsigned long long n)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) *counter += n;
 }
 
 static __global__ __launch_bounds__(REPLAY_THREADS) void replay_pack_kernel(ReplayPackArgs a)

@@ -72,7 +72,7 @@ def unpack_bitmaps(packed, cols):
 
 
 class ReplayBuffer(Consumer):
-    """The replay buffer of one Engine (f110_replay_install / _bind / _update / _draw / _gather / _locate).  The ring lives in `buf`:
+    """The replay buffer of one Engine (f110_replay_install / _bind / _update / _draw / _gather / _locate / _sample).  The ring lives in `buf`:
     frames [T + 1, B, rows, words] int64 (bit-packed), actions [T, B, action_dim] fp32, rewards [T, B] fp64, dones and valid
     [T, B] uint8, count and chain_start [1] int64, t_seen [B] fp64, last_valid [B] uint8 and action_in [B, action_dim] fp32 (what
     the next push stores: F110VecEnv.replay_action).  A transition is named by index = step slot * B + env.  The ring is no part
@@ -82,6 +82,7 @@ class ReplayBuffer(Consumer):
     STATE = {}
     RING = ('frames', 'actions', 'rewards', 'dones', 'valid', 'count', 'chain_start', 't_seen')
     cfg, rows, cols, _draws = None, 0, 0, 0
+    generation = 0                  # installs made: a graph captured on the ring of an earlier one holds freed addresses (SACAgent)
 
     steps = property(lambda self: self.cfg.steps)
     action_dim = property(lambda self: self.cfg.action_dim)
@@ -109,6 +110,7 @@ class ReplayBuffer(Consumer):
             self.on = False
             raise
         self.cfg, self.rows, self.cols, self.on, self._draws = c, rows, cols, True, 0
+        self.generation += 1
 
     def remove(self):
         """No launch, no info key remains and the ring is freed."""
@@ -223,6 +225,42 @@ class ReplayBuffer(Consumer):
             raise ValueError('replay: the buffer is off (record_replay())')
         idx, _ = self.draw(batch_size, seed)
         return self.frames_at(idx)
+
+    def sample_frames_dev(self, batch_size, counter, seed=None, out=None):
+        """f110_replay_sample: batch_size transitions drawn from a draw counter that lives on the device, in one kernel.  counter: a
+        [1] int64 tensor on the env's device (the bits of the library's uint64; start it at 0) that the caller owns; the call draws
+        draw numbers counter .. counter + batch_size - 1 of the stream `seed` (default: the env's) exactly as draw() would with
+        that counter, and a one-lane kernel behind it adds batch_size.  Nothing crosses from the host that changes from call to
+        call, so a captured call replays with fresh draws.  The host counter of draw(), sample() and sample_frames() does not move.
+        Returns (frames, s_idx, ns_idx, a, r, d, ok, indices): the first seven what frames_at(indices) returns.  out: a dict with
+        the static tensors 'indices', 's_idx', 'ns_idx' [n] int64, 'a' [n, action_dim] fp32, 'r' [n] fp64, 'd' and 'ok' [n] uint8
+        to write into (sample_out() allocates one); the same tensors are then returned.  Device tensors, no synchronisation."""
+        if not self.on:
+            raise ValueError('replay: the buffer is off (record_replay())')
+        eng, n = self.eng, int(batch_size)
+        if not torch.is_tensor(counter) or counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != torch.device(eng.device):
+            raise ValueError('replay: counter must be a [1] int64 tensor on %s' % (eng.device,))
+        o = self.sample_out(n) if out is None else out
+        shapes = self._sample_shapes(n)
+        for k, (shape, dt) in shapes.items():
+            t = o.get(k)
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != torch.device(eng.device) or not t.is_contiguous():
+                raise ValueError('replay: out[%r] must be a contiguous %s tensor of shape %s on %s' % (k, dt, shape, eng.device))
+        with torch.cuda.device(eng.device):
+            _lib.check(eng.lib.f110_replay_sample(eng._h, self._seed(seed), counter.data_ptr(), n, o['indices'].data_ptr(), o['s_idx'].data_ptr(),
+                                                  o['ns_idx'].data_ptr(), o['a'].data_ptr(), o['r'].data_ptr(), o['d'].data_ptr(), o['ok'].data_ptr(),
+                                                  eng._stream()))
+        T, B = self.cfg.steps, eng.B
+        frames = self.buf['frames'].view((T + 1) * B, self.rows, words(self.cols))
+        return frames, o['s_idx'], o['ns_idx'], o['a'], o['r'], o['d'], o['ok'], o['indices']
+
+    def _sample_shapes(self, n):
+        return {'indices': ((n,), torch.int64), 's_idx': ((n,), torch.int64), 'ns_idx': ((n,), torch.int64),
+                'a': ((n, self.cfg.action_dim), torch.float32), 'r': ((n,), torch.float64), 'd': ((n,), torch.uint8), 'ok': ((n,), torch.uint8)}
+
+    def sample_out(self, batch_size):
+        """The tensors sample_frames_dev writes, newly allocated: what its `out` takes."""
+        return {k: torch.empty(shape, dtype=dt, device=self.eng.device) for k, (shape, dt) in self._sample_shapes(int(batch_size)).items()}
 
     def bytes_held(self):
         return sum(self.buf[k].numel() * self.buf[k].element_size() for k in ('frames', 'actions', 'rewards', 'dones', 'valid'))

@@ -1,0 +1,317 @@
+"""The reference's SACAgent (src/SAL.py:468-580) on the GPU: its five networks on the library's modules (featconv.Trunk from the
+ring's bits, dense.Dense, policyhead.PolicyHead, qhead.QHead with dense=True), three optim.SacAdam and one update that samples on the
+device (ReplayBuffer.sample_frames_dev with the agent's own draw counter), takes both losses from csrc/f110_sacloss.h and never calls
+.item().  Every kernel in it adds in a fixed order, so an update repeats bit for bit and the whole of it -- sample, forward, losses,
+backward, the three optimizer steps with the soft update of the targets -- is captured once in a torch.cuda.graph and replayed:
+K replays equal K eager updates.
+The order is that of examples/sac_update.py: the critics' losses are handed to ONE backward pass (their parameters are disjoint, so
+each critic gets the gradient the reference's two passes give it), and a target critic moves in the step of its critic, in front of the
+actor's loss where the reference moves it behind: that loss reads the critics, never the targets.  As in the reference the actor's
+backward leaves gradients in the critics, which the critics' next zero_grad drops.
+There is no CPU path and no torch fallback: the kernels of libf110_hip.so do the work."""
+import torch
+
+from .dense import Dense
+from .featconv import Trunk
+from .optim import SacAdam
+from .policyhead import PolicyHead, sample_actions
+from .qhead import QHead, td_target, twin_q
+from .sacloss import actor_loss, critic_loss
+
+NETS = ('actor', 'critic1', 'critic2', 'critic1_target', 'critic2_target')      # the reference's order of construction (:486-495)
+OPTIMIZERS = ('actor', 'critic1', 'critic2')
+
+
+def feature_width(rows, cols):
+    """Values behind conv1(8, 4), conv2(4, 2), conv3(3, 1) without padding, 32 channels."""
+    for k, s in ((8, 4), (4, 2), (3, 1)):
+        rows, cols = (rows - k) // s + 1, (cols - k) // s + 1
+    if rows < 1 or cols < 1:
+        raise ValueError('SACAgent: an image of this size leaves no output behind conv3')
+    return 32 * rows * cols
+
+
+def _key(name):
+    """A module's parameter name -> the reference's key."""
+    return name.replace('trunk.', '').replace('head.', '')
+
+
+class Actor(torch.nn.Module):
+    """The reference's Actor (src/SAL.py:390-421): trunk, fc1 + ReLU, fc_mean / fc_log_std and the sampling tail."""
+
+    def __init__(self, trunk, fc1, head):
+        super().__init__()
+        self.trunk, self.fc1, self.head = trunk, fc1, head
+
+    @classmethod
+    def new(cls, width, hidden, action_dim, on, cols, device):
+        return cls(Trunk(on=on, cols=cols, device=device), Dense(width, hidden, relu=True, device=device), PolicyHead(hidden, action_dim, device=device))
+
+    @classmethod
+    def sharing(cls, m, on, cols):
+        """On the tensors of a torch.nn network with the reference's attributes conv1 .. conv3, fc1, fc_mean, fc_log_std."""
+        return cls(Trunk.from_convs(m.conv1, m.conv2, m.conv3, on=on, cols=cols), Dense.from_linear(m.fc1, relu=True),
+                   PolicyHead.from_linears(m.fc_mean, m.fc_log_std))
+
+    def features(self, frames, index=None):
+        return self.fc1(self.trunk(frames, index))
+
+    def sample(self, frames, index=None, eps=None):
+        action, log_prob, _, _ = self.head.sample(self.features(frames, index), eps=eps)
+        return action, log_prob
+
+
+class Critic(torch.nn.Module):
+    """The reference's Critic (src/SAL.py:424-442): trunk, and fc1 + ReLU + fc2 on cat([features, action]) by qhead.twin_q."""
+
+    def __init__(self, trunk, head):
+        super().__init__()
+        self.trunk, self.head = trunk, head
+
+    @classmethod
+    def new(cls, width, hidden, action_dim, on, cols, device):
+        return cls(Trunk(on=on, cols=cols, device=device), QHead(width, action_dim, hidden, device=device, dense=True))
+
+    @classmethod
+    def sharing(cls, m, on, cols):
+        return cls(Trunk.from_convs(m.conv1, m.conv2, m.conv3, on=on, cols=cols), QHead.from_linears(m.fc1, m.fc2, dense=True))
+
+
+def _heads(nets):
+    return [c.head.fc1 for c in nets], [c.head.fc2 for c in nets]
+
+
+class SACAgent:
+    """SACAgent(action_dim, gamma, tau, alpha, actor_lr, critic_lr) with the reference's defaults, for images of rows x cols pixels
+    and fc1 layers `hidden` wide; on: what a set pixel is worth (255.0: update() feeds the raw 0 / 255 images, :536; select_action
+    here sees the same scale, where the reference divides by 255 for acting only).  networks: a dict (or an object with these
+    attributes) of five torch.nn networks 'actor', 'critic1', 'critic2', 'critic1_target', 'critic2_target' with the reference's layers
+    (conv1 .. conv3, fc1, fc_mean / fc_log_std or fc2) whose tensors the agent then shares: training the agent trains them.  Without it
+    the agent builds its own, in the reference's order, the targets loaded from the critics.
+    Attributes: actor, critics [2], targets [2]; actor_opt, critic_opts [2] (SacAdam; a critic's also moves its target); draws, the [1]
+    int64 draw counter on the device; sample, the tensors of the batch the last update drew (sample['indices'] names the transitions)."""
+
+    def __init__(self, action_dim=16, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, rows=256, cols=256, hidden=512,
+                 on=255.0, device='cuda', networks=None):
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise ValueError('SACAgent: device %s: there is no CPU path' % (self.device,))
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.action_dim, self.gamma, self.tau, self.alpha = int(action_dim), float(gamma), float(tau), float(alpha)
+        self.rows, self.cols, self.hidden, self.on = int(rows), int(cols), int(hidden), float(on)
+        self.width = feature_width(self.rows, self.cols)
+        if networks is None:
+            make = lambda cls: cls.new(self.width, self.hidden, self.action_dim, self.on, self.cols, self.device)  # noqa: E731
+            self.actor = make(Actor)
+            self.critics = [make(Critic), make(Critic)]
+            self.targets = [make(Critic), make(Critic)]
+            for t, c in zip(self.targets, self.critics):
+                t.load_state_dict(c.state_dict())
+        else:
+            get = networks.__getitem__ if isinstance(networks, dict) else lambda name: getattr(networks, name)  # noqa: E731
+            self.actor = Actor.sharing(get('actor'), self.on, self.cols)
+            self.critics = [Critic.sharing(get(n), self.on, self.cols) for n in ('critic1', 'critic2')]
+            self.targets = [Critic.sharing(get(n), self.on, self.cols) for n in ('critic1_target', 'critic2_target')]
+        fc1 = self.actor.fc1.weight
+        if tuple(fc1.shape) != (self.hidden, self.width) or self.actor.head.fc_mean.out_features != self.action_dim:
+            raise ValueError('SACAgent: the actor\'s fc1 is %s and its action has %d values; rows, cols, hidden and action_dim say %s and %d'
+                             % (tuple(fc1.shape), self.actor.head.fc_mean.out_features, (self.hidden, self.width), self.action_dim))
+        for p in self.modules()['actor'].parameters():
+            if p.device != self.device:
+                raise ValueError('SACAgent: the networks are on %s, not on %s' % (p.device, self.device))
+        self.actor_opt = SacAdam(self.actor, lr=actor_lr)
+        self.critic_opts = [SacAdam(c, lr=critic_lr, targets=t, tau=self.tau) for c, t in zip(self.critics, self.targets)]
+        self.draws = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self.sample = None
+        # the captured update
+        self._g_losses = torch.zeros((3,), dtype=torch.float32, device=self.device)
+        self._g_key, self._g_replay, self._g_sample, self._g_eps, self._graphs = None, None, None, None, {}
+        self.captures, self.recaptured = 0, False
+
+    # ---- the parts
+    def modules(self):
+        return dict(actor=self.actor, critic1=self.critics[0], critic2=self.critics[1], critic1_target=self.targets[0], critic2_target=self.targets[1])
+
+    def optimizers(self):
+        return dict(actor=self.actor_opt, critic1=self.critic_opts[0], critic2=self.critic_opts[1])
+
+    def zero_grad(self, set_to_none=True):
+        for opt in self.optimizers().values():
+            opt.zero_grad(set_to_none)
+
+    # ---- acting
+    def select_action(self, frames, index=None, evaluate=False, out=None, eps=None):
+        """select_action (src/SAL.py:499-519) for a batch of envs under no_grad -> the fp64 [n, action_dim] action that
+        F110VecEnv.path_actions and replay_action take: tanh(mean) with evaluate, else a sample.  frames: the env's uint8 bitmaps [n,
+        rows, cols] or their bits [m, rows, words] int64 (info['lidar_bitmap'] either way); index: rows of `frames` to act on (None:
+        all).  eps: the [n, action_dim] fp32 draws (None: torch.randn); out: a [n, action_dim] fp64 tensor that receives the action, a
+        static buffer that path_actions or a captured step reads.  A row's action does not depend on the batch around it."""
+        with torch.no_grad():
+            h = self.actor.features(frames, index)
+            if evaluate:
+                head = self.actor.head
+                return sample_actions(h, head.fc_mean.weight, head.fc_mean.bias, head.fc_log_std.weight, head.fc_log_std.bias, eps=None,
+                                      dtype=torch.float64, out=out)[0]
+            return self.actor.head.sample(h, eps=eps, dtype=torch.float64, out=out)[0]
+
+    # ---- learning
+    def _eps(self, eps, n):
+        if eps is None:
+            return None, None
+        if not isinstance(eps, (tuple, list)) or len(eps) != 2:
+            raise ValueError('SACAgent: eps must be (eps_next, eps_new)')
+        for e in eps:
+            if not torch.is_tensor(e) or e.dtype != torch.float32 or tuple(e.shape) != (n, self.action_dim) or e.device != self.device:
+                raise ValueError('SACAgent: eps_next and eps_new must be fp32 [%d, %d] on %s' % (n, self.action_dim, self.device))
+        return eps[0], eps[1]
+
+    def _update(self, frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, losses):
+        """:544-580 on one batch; the three losses go to `losses` [3] (actor, critic1, critic2), which is returned."""
+        actor, critics, targets = self.actor, self.critics, self.targets
+        with torch.no_grad():                                                    # :544-549
+            next_a, next_logp = actor.sample(frames, ns_idx, eps_next)
+            tv = td_target([t.trunk(frames, ns_idx) for t in targets], next_a, next_logp, r, d, *_heads(targets), self.gamma, self.alpha, dense=True)
+        q, _ = twin_q([c.trunk(frames, s_idx) for c in critics], a, *_heads(critics), dense=True)     # :551-552, a as the ring stores it (fp32)
+        grad_q = torch.empty_like(q)
+        critic_loss(q[0], q[1], tv, loss=losses[1:3], grad=grad_q)               # :553-554
+        for opt in self.critic_opts:
+            opt.zero_grad()
+        torch.autograd.backward((q,), (grad_q,))
+        for opt in self.critic_opts:
+            opt.step()                                                           # :556-562 and, in the same pass, :575-578
+        new_a, logp = actor.sample(frames, s_idx, eps_new)                       # :564-568
+        _, qn = twin_q([c.trunk(frames, s_idx) for c in critics], new_a, *_heads(critics), dense=True)
+        _, g_logp, g_qn = actor_loss(logp, qn, self.alpha, loss=losses[0:1])
+        self.actor_opt.zero_grad()
+        torch.autograd.backward((logp, qn), (g_logp, g_qn))
+        self.actor_opt.step()                                                    # :570-572
+        return losses
+
+    def update_batch(self, batch, eps=None):
+        """One update on a batch that is given, not drawn: a dict with 'frames' [m, rows, words] int64, 's_idx' and 'ns_idx' [n] int64
+        rows of it (-1: a zero frame), 'a' [n, action_dim] fp32, 'r' [n] fp64 and 'd' [n] uint8, as ReplayBuffer.sample_frames returns
+        them.  eps = (eps_next, eps_new), fp32 [n, action_dim], replace the two torch.randn draws.  Returns the new [3] fp32 loss tensor
+        (actor, critic1, critic2) on the device; no synchronisation."""
+        n = int(batch['s_idx'].shape[0])
+        eps_next, eps_new = self._eps(eps, n)
+        losses = torch.empty((3,), dtype=torch.float32, device=self.device)
+        return self._update(batch['frames'], batch['s_idx'], batch['ns_idx'], batch['a'], batch['r'], batch['d'], eps_next, eps_new, losses)
+
+    def _check_replay(self, replay):
+        if not replay.on:
+            raise ValueError('SACAgent: the replay buffer is off (record_replay())')
+        if (replay.rows, replay.cols, replay.action_dim) != (self.rows, self.cols, self.action_dim) or replay.eng.device != self.device:
+            raise ValueError('SACAgent: the ring holds %d x %d images and %d action values on %s; the agent takes %d x %d and %d on %s'
+                             % (replay.rows, replay.cols, replay.action_dim, replay.eng.device, self.rows, self.cols, self.action_dim, self.device))
+
+    def update(self, replay, batch_size=64, eps=None, check=False):
+        """SACAgent.update (src/SAL.py:521-580) from the ring `replay` (F110VecEnv.replay): batch_size transitions drawn on the
+        device with the agent's own draw counter, then update_batch.  Returns the [3] loss tensor; nothing synchronises.
+        check=True is the reference's `len(replay_buffer) < batch_size` test (:532): one synchronisation, and with fewer valid
+        transitions in the ring it returns zeros and touches nothing, the draw counter included.  Without it a draw that finds no valid
+        transition (ok = 0: an empty ring, or 64 misses in a sparse one) is a zero transition -- zero frames, action, reward and done --
+        and is learnt from like any other; the caller keeps the ring filled (update_after in examples/sac_train.py)."""
+        self._check_replay(replay)
+        n = int(batch_size)
+        eps_next, eps_new = self._eps(eps, n)
+        if check and len(replay) < n:
+            return torch.zeros((3,), dtype=torch.float32, device=self.device)
+        self.sample = replay.sample_out(n)
+        frames, s_idx, ns_idx, a, r, d, _, _ = replay.sample_frames_dev(n, self.draws, out=self.sample)
+        return self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, torch.empty((3,), dtype=torch.float32, device=self.device))
+
+    # ---- the captured update
+    def _graph_key(self, replay, n):
+        opts = self.optimizers().values()
+        return (id(replay), replay.generation, replay.steps, replay.eng.B, replay._seed(None), n,
+                tuple((o.lr, o.betas, o.eps, o.tau) for o in opts))
+
+    def capture_update(self, replay, batch_size=64, draws=True):
+        """Captures the whole of update(replay, batch_size) -- the sample and the advance of the draw counter, both forward and
+        backward passes, the losses, the three optimizer steps -- in one torch.cuda.graph on a side stream.  A capture executes
+        nothing: no parameter, moment or counter moves.  The batch, the two draws and the losses live in static tensors (the losses:
+        the tensor update_graph returns, the same across re-captures); .grad is dropped inside the capture, so the gradients live in the
+        graph's pool.  draws=True records the two torch.randn calls inside the graph (the framework's graph-safe generator); draws=False
+        captures the variant that reads the static draws update_graph(eps=...) fills.  update_graph captures what it needs by itself;
+        calling this first only moves the cost."""
+        self._check_replay(replay)
+        n, dev = int(batch_size), self.device
+        key = self._graph_key(replay, n)
+        if key != self._g_key:
+            self._graphs = {}
+            self._g_key, self._g_replay = key, replay
+            self._g_sample = replay.sample_out(n)
+            self._g_eps = [torch.zeros((n, self.action_dim), dtype=torch.float32, device=dev) for _ in range(2)]
+        cur = torch.cuda.current_stream(dev)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(cur)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side), torch.cuda.graph(g, stream=side):
+            self.zero_grad(set_to_none=True)
+            frames, s_idx, ns_idx, a, r, d, _, _ = replay.sample_frames_dev(n, self.draws, out=self._g_sample)
+            eps_next, eps_new = (None, None) if draws else self._g_eps
+            self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, self._g_losses)
+        cur.wait_stream(side)
+        self._graphs[bool(draws)] = g
+        self.captures += 1
+        return self._g_losses
+
+    def update_graph(self, eps=None):
+        """Replays the update captured for the ring and batch size of the last capture_update: one host call.  eps = (eps_next,
+        eps_new) are copied into the static draws first; without them the graph draws by itself.  Returns the static [3] loss tensor
+        (read it before the next replay).  The update is captured again first -- `recaptured` says so, `captures` counts -- when the
+        ring was installed anew (its old tensors are freed), or an optimizer's lr, betas, eps or tau, or the env's seed has changed:
+        a captured launch keeps the addresses and scalars it was captured with."""
+        if self._g_key is None:
+            raise ValueError('SACAgent: no update is captured (capture_update(replay, batch_size))')
+        replay, n = self._g_replay, self._g_key[5]
+        draws = eps is None
+        if not draws:
+            eps_next, eps_new = self._eps(eps, n)
+        self.recaptured = not replay.on or self._graph_key(replay, n) != self._g_key
+        if self.recaptured or draws not in self._graphs:
+            self.capture_update(replay, n, draws)
+        if not draws:
+            self._g_eps[0].copy_(eps_next)
+            self._g_eps[1].copy_(eps_new)
+        self.sample = self._g_sample
+        self._graphs[draws].replay()
+        return self._g_losses
+
+    # ---- state
+    def actor_state_dict(self):
+        """The actor under the reference's keys (conv1.weight .. fc_log_std.bias): what main() saves as sac_actor.pth."""
+        return {_key(k): p.detach() for k, p in self.actor.named_parameters()}
+
+    def load_actor_state_dict(self, sd):
+        self._load_net('actor', sd)
+
+    def _load_net(self, name, sd):
+        net = self.modules()[name]
+        own = {_key(k): p.detach() for k, p in net.named_parameters()}
+        if sorted(own) != sorted(sd):
+            raise ValueError('SACAgent: the state of %s has the keys %s, expected %s' % (name, sorted(sd), sorted(own)))
+        with torch.no_grad():
+            for k, v in own.items():
+                if tuple(v.shape) != tuple(sd[k].shape):
+                    raise ValueError('SACAgent: %s of %s has shape %s, expected %s' % (k, name, tuple(sd[k].shape), tuple(v.shape)))
+            for k, v in own.items():
+                v.copy_(sd[k])                                                  # in place: a captured update keeps reading these tensors
+
+    def state_dict(self):
+        """The five networks under the reference's keys, the three optimizers in torch.optim.Adam's format (SacAdam.state_dict) and
+        the draw counter (copies; synchronises)."""
+        sd = {name: {_key(k): p.detach().clone() for k, p in net.named_parameters()} for name, net in self.modules().items()}
+        for name, opt in self.optimizers().items():
+            sd[name + '_optimizer'] = opt.state_dict()
+        sd['draws'] = int(self.draws.item())
+        return sd
+
+    def load_state_dict(self, sd):
+        """Continues from state_dict()'s result, written in place into the agent's own tensors."""
+        for name in NETS:
+            self._load_net(name, sd[name])
+        for name, opt in self.optimizers().items():
+            opt.load_state_dict(sd[name + '_optimizer'])
+        self.draws.fill_(int(sd['draws']))
