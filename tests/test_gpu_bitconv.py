@@ -9,31 +9,11 @@ import numpy as np
 import pytest
 
 import bitconv_cases as bc
+import gpu_checks as gk
 import replay_cases as rc
 import shaping_cases as sc
 
 pytestmark = pytest.mark.gpu
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _dev(a, dtype=None):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a), device='cuda') if dtype is None else torch.as_tensor(np.ascontiguousarray(a), device='cuda').to(dtype)
-
-
-def _packed(imgs):
-    import torch
-    return torch.as_tensor(rc.pack(imgs).view(np.int64), device='cuda')
-
-
-def _differing(got, want):
-    """The elements of got (a device tensor, or an array already on the host) whose 32-bit patterns are not want's."""
-    got = got if isinstance(got, np.ndarray) else _np(got)
-    assert got.shape == want.shape
-    return int((bc.bit_patterns(got) != bc.bit_patterns(want)).sum())
 
 
 _forward_cache = {}
@@ -54,7 +34,7 @@ def test_forward_equals_checker(golden, rows, cols, kernel, stride, channels):
     empty), on in {1, 255, 1 / 255}, relu both ways, bias present and NULL; SAL's shape also on five FILL images of g16."""
     from red_gym_amd.bitconv import conv_bits
     w, b = bc.params(kernel, channels)
-    wd, bd = _dev(w), _dev(b)
+    wd, bd = gk.to_device(w), gk.to_device(b)
     batches = [('abc', bc.images(rows, cols))]
     if (rows, cols) == (256, 256):
         imgs = sc.unpack_images(golden('g16_shaping.npz'), 'a')
@@ -65,14 +45,14 @@ def test_forward_equals_checker(golden, rows, cols, kernel, stride, channels):
         batches.append(('fill', fill))
     total = 0
     for name, imgs in batches:
-        frames = _packed(imgs)
+        frames = gk.packed(imgs)
         for on in bc.ONS:
             for relu in (False, True):
                 for bias, bias_dev in ((b, bd), (None, None)):
                     got = conv_bits(frames, wd, bias_dev, stride=stride, on=on, relu=relu, cols=cols)
                     want = _want((rows, cols, name, on, relu, bias is not None), imgs, w, bias, stride, on, relu)
                     assert tuple(got.shape) == want.shape
-                    bad = _differing(got, want)
+                    bad = gk.differing(got, want)
                     print('%d x %d k%d s%d c%d %s on=%g relu=%s bias=%s: %d of %d elements differ' % (rows, cols, kernel, stride, channels, name, on, relu, bias is not None, bad, want.size))
                     total += bad
     assert total == 0
@@ -90,28 +70,28 @@ def test_uint8_entry_and_index(rows, cols, kernel, stride, channels):
     import torch
     from red_gym_amd.bitconv import conv_bits
     w, b = bc.params(kernel, channels, seed=1)
-    wd, bd = _dev(w), _dev(b)
+    wd, bd = gk.to_device(w), gk.to_device(b)
     imgs = bc.images(rows, cols)
     assert (imgs[0] == 254).any() and (imgs[0] == 255).any()
-    frames = _packed(imgs)
+    frames = gk.packed(imgs)
     for on, relu in ((1.0, False), (255.0, True)):
         a = conv_bits(frames, wd, bd, stride=stride, on=on, relu=relu, cols=cols)
-        u = conv_bits(_dev(imgs), wd, bd, stride=stride, on=on, relu=relu)
-        assert torch.equal(a, u) and _differing(u, bc.forward(imgs, w, b, stride, on, relu)) == 0
+        u = conv_bits(gk.to_device(imgs), wd, bd, stride=stride, on=on, relu=relu)
+        assert torch.equal(a, u) and gk.differing(u, bc.forward(imgs, w, b, stride, on, relu)) == 0
     # an image of 254 everywhere is an empty image; one 255 in it is one set pixel
     almost = np.full((2, rows, cols), 254, np.uint8)
     almost[1, rows // 2, cols // 2] = 255
-    u = conv_bits(_dev(almost), wd, bd, stride=stride)
+    u = conv_bits(gk.to_device(almost), wd, bd, stride=stride)
     empty = bc.forward(np.zeros((1, rows, cols), np.uint8), w, b, stride, 1.0, False)
-    assert _differing(u[:1], empty) == 0 and _differing(u, bc.forward(almost, w, b, stride, 1.0, False)) == 0
+    assert gk.differing(u[:1], empty) == 0 and gk.differing(u, bc.forward(almost, w, b, stride, 1.0, False)) == 0
     assert not torch.equal(u[0], u[1])
     index = [2, -1, 0, 0, imgs.shape[0] + 5]
-    for src in (frames, _dev(imgs)):
-        got = conv_bits(src, wd, bd, stride=stride, index=_dev(np.array(index, np.int64)), cols=cols)
+    for src in (frames, gk.to_device(imgs)):
+        got = conv_bits(src, wd, bd, stride=stride, index=gk.to_device(np.array(index, np.int64)), cols=cols)
         full = bc.forward(imgs, w, b, stride, 1.0, False)
         assert got.shape[0] == 5
-        assert _differing(got[0], full[2]) == 0 and _differing(got[2], full[0]) == 0
-        assert _differing(got[1], empty[0]) == 0 and _differing(got[4], empty[0]) == 0          # -1 and out of range: the empty frame
+        assert gk.differing(got[0], full[2]) == 0 and gk.differing(got[2], full[0]) == 0
+        assert gk.differing(got[1], empty[0]) == 0 and gk.differing(got[4], empty[0]) == 0          # -1 and out of range: the empty frame
         assert torch.equal(got[2], got[3])                                                         # the repeated rows
 
 
@@ -122,19 +102,14 @@ def _raw_backward(frames, n_frames, index, n, cfg, g, with_bias=True, ws_fill=-7
     from red_gym_amd import _lib
     lib = _lib.load()
     kk = cfg.kernel * cfg.kernel
-    gw = torch.full((cfg.channels * kk + 64,), -7.0, dtype=torch.float32, device='cuda')
-    gb = torch.full((cfg.channels + 64,), -7.0, dtype=torch.float32, device='cuda')
-    nbytes = lib.f110_bitconv_workspace(C.byref(cfg), n)
-    ws = torch.full((nbytes // 4 + 64,), ws_fill, dtype=torch.float32, device='cuda')
+    gw, gb = gk.Guarded(cfg.channels * kk, fill=-7.0), gk.Guarded(cfg.channels, fill=-7.0)
+    ws = gk.Guarded(lib.f110_bitconv_workspace(C.byref(cfg), n) // 4, fill=ws_fill)
     _lib.check(lib.f110_bitconv_backward(C.byref(cfg), frames.data_ptr(), n_frames, None if index is None else index.data_ptr(), n, g.data_ptr(),
-                                         gw.data_ptr(), gb.data_ptr() if with_bias else None, ws.data_ptr(), torch.cuda.current_stream().cuda_stream))
+                                         gw.ptr, gb.ptr if with_bias else None, ws.ptr, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    margin = _np(ws)[nbytes // 4:]
-    assert (_np(gw)[cfg.channels * kk:] == -7.0).all() and (_np(gb)[cfg.channels:] == -7.0).all()
-    assert margin.size == 64 and (np.isnan(margin) if np.isnan(ws_fill) else margin == ws_fill).all()
-    if not with_bias:
-        assert (_np(gb) == -7.0).all()
-    return _np(gw)[:cfg.channels * kk].reshape(cfg.channels, 1, cfg.kernel, cfg.kernel).copy(), _np(gb)[:cfg.channels].copy()
+    ws.read()
+    assert with_bias or gb.untouched()
+    return gw.read().reshape(cfg.channels, 1, cfg.kernel, cfg.kernel), gb.read()
 
 
 def _backward_within_the_bound(rows, cols, kernel, stride, channels, n):
@@ -143,7 +118,7 @@ def _backward_within_the_bound(rows, cols, kernel, stride, channels, n):
     oh, ow = bc.out_size(rows, cols, kernel, stride)
     rng = np.random.default_rng([rows, cols, n])
     g = (rng.normal(size=(n, channels, oh, ow)) * 10.0 ** rng.integers(-2, 2, (n, channels, 1, 1))).astype(np.float32)
-    frames, gd = _packed(imgs), _dev(g)
+    frames, gd = gk.packed(imgs), gk.to_device(g)
     for on in (255.0, 1.0 / 255.0):
         cfg = bitconv.make_config(rows, cols, kernel, stride, channels, on)
         gw, gb = _raw_backward(frames, n, None, n, cfg, gd)
@@ -164,7 +139,7 @@ def _backward_within_the_bound(rows, cols, kernel, stride, channels, n):
     picked = np.stack([imgs[i] if 0 <= i < n else np.zeros((rows, cols), np.uint8) for i in index])
     gi = np.ascontiguousarray(g[np.arange(m) % n])
     cfg = bitconv.make_config(rows, cols, kernel, stride, channels, 1.0)
-    gw, gb = _raw_backward(frames, n, _dev(index), m, cfg, _dev(gi))
+    gw, gb = _raw_backward(frames, n, gk.to_device(index), m, cfg, gk.to_device(gi))
     want_w, want_b, _, _ = bc.gradients(picked, gi, kernel, stride, 1.0)
     bound_w, bound_b = bc.grad_bounds(picked, gi, kernel, stride, 1.0)
     assert (np.abs(gw - want_w) <= bound_w).all() and (np.abs(gb - want_b) <= bound_b).all()
@@ -194,14 +169,12 @@ def _raw_forward(src, n_frames, index, n, cfg, w, b):
     lib = _lib.load()
     oh, ow = bc.out_size(cfg.rows, cfg.cols, cfg.kernel, cfg.stride)
     size = n * cfg.channels * oh * ow
-    buf = torch.full((size + 128,), -7.0, dtype=torch.float32, device='cuda')
+    buf = gk.Guarded(size, fill=-7.0)
     fn = lib.f110_bitconv_forward_u8 if src.dtype == torch.uint8 else lib.f110_bitconv_forward
     _lib.check(fn(C.byref(cfg), src.data_ptr(), n_frames, None if index is None else index.data_ptr(), n, w.data_ptr(),
-                  None if b is None else b.data_ptr(), buf.data_ptr() + 64 * 4, torch.cuda.current_stream().cuda_stream))
+                  None if b is None else b.data_ptr(), buf.ptr, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    host = _np(buf)
-    assert (host[:64] == -7.0).all() and (host[64 + size:] == -7.0).all()
-    return host[64:64 + size].reshape(n, cfg.channels, oh, ow)
+    return buf.read().reshape(n, cfg.channels, oh, ow)
 
 
 FORWARD_VARIANTS = ((255.0, True, True), (1.0 / 255.0, False, False))      # (on, relu, bias); the cross product runs on bc.CASES
@@ -215,17 +188,17 @@ def test_forward_equals_checker_at_every_path(rows, cols, kernel, stride, channe
     without either, and an index with -1, a repeat and an entry beyond the frames; the output's margins stay as they were."""
     from red_gym_amd import bitconv
     w, b = bc.params(kernel, channels, seed=3)
-    wd, bd = _dev(w), _dev(b)
+    wd, bd = gk.to_device(w), gk.to_device(b)
     batches = (('abc', bc.images(rows, cols)), ('edge', rc.edge_images(rows, cols)))
     total = 0
     for name, imgs in batches:
-        srcs = (('packed', _packed(imgs)), ('uint8', _dev(imgs)))
+        srcs = (('packed', gk.packed(imgs)), ('uint8', gk.to_device(imgs)))
         for on, relu, bias in FORWARD_VARIANTS:
             want = bc.forward(imgs, w, b if bias else None, stride, on, relu)
             cfg = bitconv.make_config(rows, cols, kernel, stride, channels, on, relu)
             for entry, src in srcs:
                 got = _raw_forward(src, len(imgs), None, len(imgs), cfg, wd, bd if bias else None)
-                bad = _differing(got, want)
+                bad = gk.differing(got, want)
                 print('%d x %d k%d s%d c%d %s %s on=%g relu=%s bias=%s: %d of %d elements differ' % (rows, cols, kernel, stride, channels, name, entry, on, relu, bias, bad, want.size))
                 total += bad
             if name == 'abc':
@@ -238,8 +211,8 @@ def test_forward_equals_checker_at_every_path(rows, cols, kernel, stride, channe
     want = bc.forward(bc.pick(imgs, index), w, b, stride, 1.0, False)
     assert (want[0] != want[2]).any() and (want[2] != want[1]).any() and (want[1] == want[4]).all() and (want[1] == want[5]).all()
     cfg = bitconv.make_config(rows, cols, kernel, stride, channels, 1.0, False)
-    for src in (_packed(imgs), _dev(imgs)):
-        total += _differing(_raw_forward(src, len(imgs), _dev(index), len(index), cfg, wd, bd), want)
+    for src in (gk.packed(imgs), gk.to_device(imgs)):
+        total += gk.differing(_raw_forward(src, len(imgs), gk.to_device(index), len(index), cfg, wd, bd), want)
     assert total == 0
 
 
@@ -254,14 +227,14 @@ def test_backward_exact_on_integer_gradients(rows, cols, kernel, stride, channel
     oh, ow = bc.out_size(rows, cols, kernel, stride)
     frames5 = bc.many_images(rows, cols, bc.EXACT_FRAMES)
     g = bc.exact_grad_out(n, channels, oh, ow)
-    gd = _dev(g)
+    gd = gk.to_device(g)
     bad = 0
     for with_index in (False, True):
         idx = bc.exact_index(n, with_index)
         picked = bc.pick(frames5, idx)
         sums = bc.exact_sums(picked, g, kernel, stride)
         assert bc.holds_something(sums)
-        frames, n_frames, index = (_packed(frames5), bc.EXACT_FRAMES, _dev(idx)) if with_index else (_packed(picked), n, None)
+        frames, n_frames, index = (gk.packed(frames5), bc.EXACT_FRAMES, gk.to_device(idx)) if with_index else (gk.packed(picked), n, None)
         for on in bc.EXACT_ONS:
             want_w, want_b = bc.exact_gradients(sums, on)
             cfg = bitconv.make_config(rows, cols, kernel, stride, channels, on)
@@ -291,12 +264,12 @@ def test_autograd_exact_beyond_one_chunk():
     want_w, want_b = bc.exact_gradients(sums, 1.0)
     w, b = bc.params(kernel, channels, seed=5)
     out32 = bc.forward(picked, w, b, stride, 1.0, False)
-    for src, kw in ((_dev(picked), {}), (_packed(frames5), dict(cols=cols, index=_dev(idx)))):
-        wd, bd = _dev(w).requires_grad_(), _dev(b).requires_grad_()
+    for src, kw in ((gk.to_device(picked), {}), (gk.packed(frames5), dict(cols=cols, index=gk.to_device(idx)))):
+        wd, bd = gk.to_device(w).requires_grad_(), gk.to_device(b).requires_grad_()
         out = conv_bits(src, wd, bd, stride=stride, on=1.0, relu=False, **kw)
-        assert _differing(out, out32) == 0
-        out.backward(_dev(g))
-        assert wd.grad.shape == wd.shape and (_np(wd.grad) == want_w).all() and (_np(bd.grad) == want_b).all()
+        assert gk.differing(out, out32) == 0
+        out.backward(gk.to_device(g))
+        assert wd.grad.shape == wd.shape and (gk.to_host(wd.grad) == want_w).all() and (gk.to_host(bd.grad) == want_b).all()
 
 
 def test_forward_in_two_launches():
@@ -316,18 +289,19 @@ def test_forward_in_two_launches():
     idx[5::1001] = -1
     idx[-3:] = [0, 1, 2]
     assert (idx[:-3] == -1).sum() > 8000 and all((idx[:-3] == f).sum() > 1000000 for f in range(5))
-    index, frames, wd, bd = _dev(idx), _packed(imgs), _dev(w), _dev(b)
-    buf = torch.full((n + 64,), -7.0, dtype=torch.float32, device='cuda')
+    index, frames, wd, bd = gk.to_device(idx), gk.packed(imgs), gk.to_device(w), gk.to_device(b)
+    out = gk.Guarded(n, fill=-7.0)
+    buf = out.data
     cfg = bitconv.make_config(8, 8, 8, 8, 1, 1.0)
     _lib.check(_lib.load().f110_bitconv_forward(C.byref(cfg), frames.data_ptr(), 5, index.data_ptr(), n, wd.data_ptr(), bd.data_ptr(),
-                                                buf.data_ptr(), torch.cuda.current_stream().cuda_stream))
+                                                out.ptr, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    gathered = _dev(want)[torch.where(index < 0, 5, index)]
-    assert bool((buf[n:] == -7.0).all())
-    wrong = int((buf[:n].view(torch.int32) != gathered.view(torch.int32)).sum())
-    print('%d of %d outputs differ; the last three: %s, wanted %s' % (wrong, n, _np(buf[n - 3:n]), want[idx[-3:]]))
-    assert wrong == 0 and torch.equal(buf[:n].view(torch.int32), gathered.view(torch.int32))
-    assert np.array_equal(bc.bit_patterns(_np(buf[n - 16:n])), bc.bit_patterns(want[np.where(idx[-16:] < 0, 5, idx[-16:])]))
+    gathered = gk.to_device(want)[torch.where(index < 0, 5, index)]
+    out.read()
+    wrong = int((buf.view(torch.int32) != gathered.view(torch.int32)).sum())
+    print('%d of %d outputs differ; the last three: %s, wanted %s' % (wrong, n, gk.to_host(buf[n - 3:n]), want[idx[-3:]]))
+    assert wrong == 0 and torch.equal(buf.view(torch.int32), gathered.view(torch.int32))
+    assert np.array_equal(bc.bit_patterns(gk.to_host(buf[n - 16:n])), bc.bit_patterns(want[np.where(idx[-16:] < 0, 5, idx[-16:])]))
 
 
 @pytest.mark.parametrize('rows,cols,kernel,stride,channels', bc.BACKWARD_CASES)
@@ -351,21 +325,21 @@ def test_autograd_with_relu(rows, cols, kernel, stride, channels):
     # the mask is the fp32 output's: it equals the fp64 one unless an output sits within rounding of 0
     assert ((out32 > 0) == (ref.detach().numpy() > 0)).all()
     bound_w, bound_b = bc.grad_bounds(imgs, masked, kernel, stride, on)
-    for src, kw in ((_packed(imgs), dict(cols=cols, index=_dev(np.arange(n, dtype=np.int64)))), (_dev(imgs), {})):
-        wd, bd = _dev(w).requires_grad_(), _dev(b).requires_grad_()
+    for src, kw in ((gk.packed(imgs), dict(cols=cols, index=gk.to_device(np.arange(n, dtype=np.int64)))), (gk.to_device(imgs), {})):
+        wd, bd = gk.to_device(w).requires_grad_(), gk.to_device(b).requires_grad_()
         out = conv_bits(src, wd, bd, stride=stride, on=on, relu=True, **kw)
-        assert out.requires_grad and _differing(out, out32) == 0
-        out.backward(_dev(g))
+        assert out.requires_grad and gk.differing(out, out32) == 0
+        out.backward(gk.to_device(g))
         assert src.grad is None and not src.requires_grad
-        ew, eb = np.abs(_np(wd.grad) - _np(wt.grad)), np.abs(_np(bd.grad) - _np(bt.grad))
+        ew, eb = np.abs(gk.to_host(wd.grad) - gk.to_host(wt.grad)), np.abs(gk.to_host(bd.grad) - gk.to_host(bt.grad))
         print('%d x %d: worst error / bound: weight %.4f, bias %.4f' % (rows, cols, float((ew / bound_w).max()), float((eb / bound_b).max())))
         assert wd.grad.shape == wd.shape and (ew <= bound_w).all() and (eb <= bound_b).all()
     # weight alone: no bias, and a weight that needs no gradient gets none
-    wd = _dev(w).requires_grad_()
-    conv_bits(_packed(imgs), wd, None, stride=stride, on=on, cols=cols).backward(_dev(g))
+    wd = gk.to_device(w).requires_grad_()
+    conv_bits(gk.packed(imgs), wd, None, stride=stride, on=on, cols=cols).backward(gk.to_device(g))
     want_w = bc.gradients(imgs, g, kernel, stride, on)[0]
-    assert (np.abs(_np(wd.grad) - want_w) <= bc.grad_bounds(imgs, g, kernel, stride, on)[0]).all()
-    assert not conv_bits(_packed(imgs), _dev(w), None, stride=stride, cols=cols).requires_grad
+    assert (np.abs(gk.to_host(wd.grad) - want_w) <= bc.grad_bounds(imgs, g, kernel, stride, on)[0]).all()
+    assert not conv_bits(gk.packed(imgs), gk.to_device(w), None, stride=stride, cols=cols).requires_grad
 
 
 def test_module_shares_parameters_and_refuses(golden):
@@ -375,8 +349,8 @@ def test_module_shares_parameters_and_refuses(golden):
     m = BitConv2d.from_conv(conv, on=1.0 / 255.0)
     assert m.weight.data_ptr() == conv.weight.data_ptr() and m.bias.data_ptr() == conv.bias.data_ptr()
     imgs = bc.images(256, 256)
-    out = m(_dev(imgs))
-    assert _differing(out, bc.forward(imgs, _np(conv.weight), _np(conv.bias), 4, 1.0 / 255.0, False)) == 0
+    out = m(gk.to_device(imgs))
+    assert gk.differing(out, bc.forward(imgs, gk.to_host(conv.weight), gk.to_host(conv.bias), 4, 1.0 / 255.0, False)) == 0
     # training the module trains the layer it shares with
     out.sum().backward()
     assert conv.weight.grad is not None and conv.bias.grad is not None and float(conv.bias.grad[0]) == 3 * 63 * 63
@@ -386,12 +360,12 @@ def test_module_shares_parameters_and_refuses(golden):
     back = torch.nn.Conv2d(1, 16, 8, 4).cuda()
     back.load_state_dict(fresh.state_dict())
     assert torch.equal(back.weight, conv.weight) and torch.equal(back.bias, conv.bias)
-    assert torch.equal(fresh(_packed(imgs)), conv_bits(_packed(imgs), conv.weight, conv.bias, stride=4, cols=256))
+    assert torch.equal(fresh(gk.packed(imgs)), conv_bits(gk.packed(imgs), conv.weight, conv.bias, stride=4, cols=256))
     for bad in (torch.nn.Conv2d(3, 16, 8, 4), torch.nn.Conv2d(1, 16, 8, 4, padding=2), torch.nn.Conv2d(1, 16, 8, 4, dilation=2),
                 torch.nn.Conv2d(4, 16, 8, 4, groups=4)):
         with pytest.raises(ValueError):
             BitConv2d.from_conv(bad)
-    w, b, f = conv.weight.detach(), conv.bias.detach(), _packed(imgs)
+    w, b, f = conv.weight.detach(), conv.bias.detach(), gk.packed(imgs)
     for args, kw in (((f, w, b), dict(stride=4)),                                            # packed frames without cols
                      ((f, w, b), dict(stride=4, cols=100)),                                  # words that do not hold cols
                      ((f.float(), w, b), dict(stride=4, cols=256)),                          # a dtype that is neither
@@ -423,7 +397,7 @@ def test_closed_loop_from_bitmap_and_ring_to_features(assets):
     assert env.replay.steps == T
     torch.manual_seed(3)
     layer = BitConv2d(16, 8, 4, on=1.0, relu=True, cols=cols).cuda()
-    w, b = _np(layer.weight), _np(layer.bias)
+    w, b = gk.to_host(layer.weight), gk.to_host(layer.bias)
     spawn = workload.spawn_poses(B, 1)
     crash = np.arange(B) % 4 == 1
     spawn[crash, 0, 2] += np.pi / 2
@@ -435,8 +409,8 @@ def test_closed_loop_from_bitmap_and_ring_to_features(assets):
 
     def check_bitmap(info):
         feats = layer(info['lidar_bitmap'])
-        bitmap = _np(info['lidar_bitmap'])
-        assert feats.shape == (B, 16, 17, 24) and _differing(feats, bc.forward(bitmap, w, b, 4, 1.0, True)) == 0
+        bitmap = gk.to_host(info['lidar_bitmap'])
+        assert feats.shape == (B, 16, 17, 24) and gk.differing(feats, bc.forward(bitmap, w, b, 4, 1.0, True)) == 0
         assert 2 * sum(bool((im == 255).any() and (im == 0).any()) for im in bitmap) >= B
         checks['bitmap'] += 1
 
@@ -448,15 +422,15 @@ def test_closed_loop_from_bitmap_and_ring_to_features(assets):
             assert x.dtype == y.dtype and torch.equal(x, y), what
         fs = conv_bits(frames, layer.weight, layer.bias, stride=4, relu=True, index=s_idx, cols=cols)
         fns = layer(frames, index=ns_idx)
-        s, ns, okn = _np(s), _np(ns), _np(ok)
-        bad = _differing(fs, bc.forward(s, w, b, 4, 1.0, True)) + _differing(fns, bc.forward(ns, w, b, 4, 1.0, True))
+        s, ns, okn = gk.to_host(s), gk.to_host(ns), gk.to_host(ok)
+        bad = gk.differing(fs, bc.forward(s, w, b, 4, 1.0, True)) + gk.differing(fns, bc.forward(ns, w, b, 4, 1.0, True))
         held = np.flatnonzero(okn)
         both = sum(bool((s[i] == 0).any() and (s[i] == 255).any()) for i in held)
         print('%s: %d differing feature elements, %d valid, s holds 0 and 255 in %d' % (what, bad, held.size, both))
         assert bad == 0 and held.size > 0 and 2 * both >= held.size
-        assert ((_np(s_idx) >= 0) == (okn == 1)).all() and ((_np(ns_idx) >= 0) == (okn == 1)).all()
+        assert ((gk.to_host(s_idx) >= 0) == (okn == 1)).all() and ((gk.to_host(ns_idx) >= 0) == (okn == 1)).all()
         for i in np.flatnonzero(okn == 0):
-            assert _differing(fs[i], empty) == 0 and _differing(fns[i], empty) == 0
+            assert gk.differing(fs[i], empty) == 0 and gk.differing(fns[i], empty) == 0
         checks['ring'] += 1
         checks['valid'] += held.size
         checks['invalid'] += int((okn == 0).sum())
@@ -482,12 +456,12 @@ def test_closed_loop_from_bitmap_and_ring_to_features(assets):
     # the same draws as sample(): sample_frames moves the one draw counter
     first = env.replay._draws
     frames, s_idx, ns_idx, a, r, d, ok = env.replay.sample_frames(64, seed=5)
-    drawn = _np(env.replay._keep)
-    want_idx, want_ok, _ = rc.draw(_np(env.replay.buf['valid']), int(env.replay.buf['count']), 5, first, 64)
-    assert np.array_equal(drawn, want_idx) and np.array_equal(_np(ok), want_ok) and env.replay._draws == first + 64
+    drawn = gk.to_host(env.replay._keep)
+    want_idx, want_ok, _ = rc.draw(gk.to_host(env.replay.buf['valid']), int(env.replay.buf['count']), 5, first, 64)
+    assert np.array_equal(drawn, want_idx) and np.array_equal(gk.to_host(ok), want_ok) and env.replay._draws == first + 64
     s2 = env.replay.sample_at(torch.as_tensor(drawn, device=env.device))
     assert torch.equal(a, s2[1]) and torch.equal(r, s2[2]) and torch.equal(d, s2[4]) and torch.equal(ok, s2[5])
-    assert _differing(layer(frames, index=s_idx), bc.forward(_np(s2[0]), w, b, 4, 1.0, True)) == 0
+    assert gk.differing(layer(frames, index=s_idx), bc.forward(gk.to_host(s2[0]), w, b, 4, 1.0, True)) == 0
     print(checks)
     assert checks['bitmap'] >= 5 and checks['ring'] >= 5 and checks['valid'] > 0
     assert env.eng.device_errors() == 0

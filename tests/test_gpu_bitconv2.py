@@ -9,30 +9,11 @@ import pytest
 
 import bitconv2_cases as b2
 import bitconv_cases as bc
+import gpu_checks as gk
 import replay_cases as rc
 import shaping_cases as sc
 
 pytestmark = pytest.mark.gpu
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _dev(a):
-    import torch
-    return None if a is None else torch.as_tensor(np.ascontiguousarray(a), device='cuda')
-
-
-def _packed(imgs):
-    import torch
-    return torch.as_tensor(rc.pack(imgs).view(np.int64), device='cuda')
-
-
-def _differing(got, want):
-    got = got if isinstance(got, np.ndarray) else _np(got)
-    assert got.shape == want.shape
-    return int((bc.bit_patterns(got) != bc.bit_patterns(want)).sum())
 
 
 _acc_cache = {}
@@ -63,7 +44,7 @@ def test_forward_equals_checker(golden, case):
     `on`, relu1 and relu2 both ways, each bias present and NULL); SAL's shape also on the five fullest two-valued FILL images of g16."""
     rows, cols, k1, s1, c1, k2, s2, c2 = case
     host = b2.params2(k1, c1, k2, c2)
-    P = tuple(_dev(x) for x in host)
+    P = tuple(gk.to_device(x) for x in host)
     batches = [('abc', b2.images2(rows, cols), b2.VARIANTS)]
     if case == b2.SAL:
         imgs = sc.unpack_images(golden('g16_shaping.npz'), 'a')
@@ -74,13 +55,13 @@ def test_forward_equals_checker(golden, case):
         batches.append(('fill', fill, b2.VARIANTS[:1]))
     total = 0
     for name, imgs, variants in batches:
-        srcs = (('packed', _packed(imgs)), ('uint8', _dev(imgs)))
+        srcs = (('packed', gk.packed(imgs)), ('uint8', gk.to_device(imgs)))
         for on, relu1, relu2, wb1, wb2 in variants:
             want = _want(case, name, imgs, host, on, relu1, relu2, wb1, wb2)
             for entry, src in srcs:
                 got = _stem(src, P, case, on, relu1, relu2, wb1, wb2)
                 assert tuple(got.shape) == want.shape and got.grad_fn is None
-                bad = _differing(got, want)
+                bad = gk.differing(got, want)
                 print('%s %s %s on=%g relu=%s/%s bias=%s/%s: %d of %d elements differ' % (case, name, entry, on, relu1, relu2, wb1, wb2, bad, want.size))
                 total += bad
             if name == 'abc':
@@ -97,8 +78,8 @@ def test_same_activations_as_the_unfused_layer(case):
     import torch
     from red_gym_amd.bitconv import conv_bits, conv_bits2
     rows, cols, k1, s1, c1 = case[:5]
-    w1, b1 = (_dev(x) for x in bc.params(k1, c1, seed=6))
-    imgs = _dev(b2.images2(rows, cols))
+    w1, b1 = (gk.to_device(x) for x in bc.params(k1, c1, seed=6))
+    imgs = gk.to_device(b2.images2(rows, cols))
     for on, relu1 in ((255.0, True), (1.0, False)):
         a1 = conv_bits(imgs, w1, b1, stride=s1, on=on, relu=relu1)
         eye = torch.eye(c1, device='cuda').reshape(c1, c1, 1, 1).contiguous()
@@ -116,20 +97,20 @@ def test_index_and_batch_independence(case):
     import torch
     rows, cols, k1, s1, c1, k2, s2, c2 = case
     host = b2.params2(k1, c1, k2, c2, seed=1)
-    P = tuple(_dev(x) for x in host)
+    P = tuple(gk.to_device(x) for x in host)
     imgs = b2.images2(rows, cols)
-    full = _stem(_dev(imgs), P, case)
-    empty = _stem(_dev(np.zeros((1, rows, cols), np.uint8)), P, case)
-    assert _differing(full, b2.forward2(imgs, host[0], host[1], s1, 1.0, True, host[2], host[3], s2, True)) == 0
-    index = _dev(np.array([2, -1, 0, 0, imgs.shape[0] + 5], np.int64))
-    for src in (_packed(imgs), _dev(imgs)):
+    full = _stem(gk.to_device(imgs), P, case)
+    empty = _stem(gk.to_device(np.zeros((1, rows, cols), np.uint8)), P, case)
+    assert gk.differing(full, b2.forward2(imgs, host[0], host[1], s1, 1.0, True, host[2], host[3], s2, True)) == 0
+    index = gk.to_device(np.array([2, -1, 0, 0, imgs.shape[0] + 5], np.int64))
+    for src in (gk.packed(imgs), gk.to_device(imgs)):
         got = _stem(src, P, case, index=index)
         assert got.shape[0] == 5 and torch.equal(got[0], full[2]) and torch.equal(got[2], full[0]) and torch.equal(got[2], got[3])
         assert torch.equal(got[1], empty[0]) and torch.equal(got[4], empty[0]) and not torch.equal(got[0], got[2])
     many = rc.random_images(rows, cols, n=67, seed=3)
-    batch = _stem(_dev(many), P, case)
+    batch = _stem(gk.to_device(many), P, case)
     for i in (0, 31, 66):
-        alone = _stem(_dev(many[i:i + 1]), P, case)
+        alone = _stem(gk.to_device(many[i:i + 1]), P, case)
         assert torch.equal(batch[i], alone[0])
     assert not torch.equal(batch[0], batch[66])
 
@@ -141,14 +122,12 @@ def _raw_forward2(src, n_frames, index, n, cfg, P, sentinel=-7.0):
     lib = _lib.load()
     oh2, ow2 = bitconv.output_size2(cfg.rows, cfg.cols, cfg.kernel, cfg.stride, cfg.kernel2, cfg.stride2)
     size = n * cfg.channels2 * oh2 * ow2
-    buf = torch.full((size + 128,), sentinel, dtype=torch.float32, device='cuda')
+    buf = gk.Guarded(size, fill=sentinel)
     fn = lib.f110_bitconv2_forward_u8 if src.dtype == torch.uint8 else lib.f110_bitconv2_forward
     _lib.check(fn(C.byref(cfg), src.data_ptr(), n_frames, None if index is None else index.data_ptr(), n,
-                  *[None if t is None else t.data_ptr() for t in P], buf.data_ptr() + 64 * 4, torch.cuda.current_stream().cuda_stream))
+                  *[None if t is None else t.data_ptr() for t in P], buf.ptr, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    host = _np(buf)
-    assert (host[:64] == sentinel).all() and (host[64 + size:] == sentinel).all()
-    return host[64:64 + size].reshape(n, cfg.channels2, oh2, ow2)
+    return buf.read().reshape(n, cfg.channels2, oh2, ow2)
 
 
 @pytest.mark.parametrize('case', b2.CASES2)
@@ -158,17 +137,17 @@ def test_margins_through_the_raw_abi(case):
     from red_gym_amd import _lib, bitconv
     rows, cols, k1, s1, c1, k2, s2, c2 = case
     host = b2.params2(k1, c1, k2, c2, seed=2)
-    P = tuple(_dev(x) for x in host)
+    P = tuple(gk.to_device(x) for x in host)
     imgs = b2.images2(rows, cols)
     cfg = bitconv.make_config2(rows, cols, k1, s1, c1, k2, s2, c2, 1.0, True, False)
     want = b2.forward2(imgs, host[0], host[1], s1, 1.0, True, host[2], host[3], s2, False)
     assert (want != -7.0).all()
-    for src in (_packed(imgs), _dev(imgs)):
+    for src in (gk.packed(imgs), gk.to_device(imgs)):
         got = _raw_forward2(src, 3, None, 3, cfg, P)
-        assert (got != -7.0).all() and _differing(got, want) == 0
+        assert (got != -7.0).all() and gk.differing(got, want) == 0
         assert (_raw_forward2(src, 3, None, 0, cfg, P).size == 0)
     lib = _lib.load()
-    src = _packed(imgs)
+    src = gk.packed(imgs)
     ptrs = [src.data_ptr(), P[0].data_ptr(), P[2].data_ptr(), P[3].data_ptr()]
     for hole in range(4):
         frames, w1, w2, out = [None if i == hole else p for i, p in enumerate(ptrs)]
@@ -182,7 +161,7 @@ def test_more_items_than_workgroups():
     case, n = b2.LOOP_CASE, b2.LOOP_N
     rows, cols, k1, s1, c1, k2, s2, c2 = case
     host = b2.params2(k1, c1, k2, c2, seed=4)
-    P = tuple(_dev(x) for x in host)
+    P = tuple(gk.to_device(x) for x in host)
     imgs = b2.images2(rows, cols)
     imgs[2] = rc.random_images(rows, cols, n=1, seed=8)[0]                     # (random, all set, random; -1 reads the empty one)
     want = b2.forward2(np.concatenate([imgs, np.zeros((1, rows, cols), np.uint8)]), host[0], host[1], s1, 1.0, True, host[2], host[3], s2, False)
@@ -190,8 +169,8 @@ def test_more_items_than_workgroups():
     idx = np.random.default_rng(4).integers(0, 3, n).astype(np.int64)
     idx[7::101] = -1
     idx[-3:] = [0, 1, 2]
-    got = _stem(_packed(imgs), P, case, relu2=False, index=_dev(idx))
-    gathered = _dev(want)[_dev(np.where(idx < 0, 3, idx))]
+    got = _stem(gk.packed(imgs), P, case, relu2=False, index=gk.to_device(idx))
+    gathered = gk.to_device(want)[gk.to_device(np.where(idx < 0, 3, idx))]
     assert got.shape == gathered.shape and torch.equal(got.view(torch.int32), gathered.view(torch.int32))
 
 
@@ -203,8 +182,8 @@ def test_no_intermediate_in_memory():
     import torch.nn.functional as F
     from red_gym_amd.bitconv import conv_bits, conv_bits2
     rows, cols, k1, s1, c1, k2, s2, c2 = b2.SAL
-    w1, b1, w2, bb = (_dev(x) for x in b2.params2(k1, c1, k2, c2))
-    imgs = _dev(rc.random_images(rows, cols, n=64, seed=2))
+    w1, b1, w2, bb = (gk.to_device(x) for x in b2.params2(k1, c1, k2, c2))
+    imgs = gk.to_device(rc.random_images(rows, cols, n=64, seed=2))
     out_bytes, a1_bytes = 64 * 32 * 30 * 30 * 4, 64 * 16 * 63 * 63 * 4
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
@@ -243,18 +222,18 @@ def test_module_two_paths():
     back2.load_state_dict(fresh.conv2.state_dict())
     assert torch.equal(back1.weight, conv1.weight) and torch.equal(back2.weight, conv2.weight) and torch.equal(back2.bias, conv2.bias)
     imgs = b2.images2(256, 256)
-    host = tuple(_np(p) for p in theirs)
+    host = tuple(gk.to_host(p) for p in theirs)
     want = b2.forward2(imgs, host[0], host[1], 4, 1.0, True, host[2], host[3], 2, True)
     with torch.no_grad():
-        got = stem(_dev(imgs))
-        assert got.grad_fn is None and _differing(got, want) == 0
-        assert _differing(fresh(_packed(imgs)), want) == 0
-    out = stem(_dev(imgs))
+        got = stem(gk.to_device(imgs))
+        assert got.grad_fn is None and gk.differing(got, want) == 0
+        assert gk.differing(fresh(gk.packed(imgs)), want) == 0
+    out = stem(gk.to_device(imgs))
     assert out.grad_fn is not None
     a1 = bc.forward(imgs, host[0], host[1], 4, 1.0, True)
     ref, mag = b2.conv2_fp64(a1, host[2], host[3], 2)
     bound = bc.gamma(257) * mag + np.abs(ref) * bc.U
-    err = np.abs(_np(out).astype(np.float64) - np.maximum(ref, 0.0))
+    err = np.abs(gk.to_host(out).astype(np.float64) - np.maximum(ref, 0.0))
     print('grad path: worst error / bound %.4f' % float((err / np.maximum(bound, 1e-300)).max()))
     assert (err <= bound).all()
     g = torch.randn_like(out)
@@ -264,9 +243,9 @@ def test_module_two_paths():
     torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = True, False
     try:
         warm = [p.detach().clone().requires_grad_() for p in theirs]
-        torch.relu(F.conv2d(conv_bits(_dev(imgs), warm[0], warm[1], stride=4, relu=True), warm[2], warm[3], stride=2)).backward(g)
-        stem(_dev(imgs)).backward(g)
-        hand = torch.relu(F.conv2d(conv_bits(_dev(imgs), clones[0], clones[1], stride=4, relu=True), clones[2], clones[3], stride=2))
+        torch.relu(F.conv2d(conv_bits(gk.to_device(imgs), warm[0], warm[1], stride=4, relu=True), warm[2], warm[3], stride=2)).backward(g)
+        stem(gk.to_device(imgs)).backward(g)
+        hand = torch.relu(F.conv2d(conv_bits(gk.to_device(imgs), clones[0], clones[1], stride=4, relu=True), clones[2], clones[3], stride=2))
         hand.backward(g)
     finally:
         torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = was
@@ -278,7 +257,7 @@ def test_module_two_paths():
     # frozen parameters take the fused path even with grad enabled
     for p in theirs:
         p.requires_grad_(False)
-    assert stem(_dev(imgs)).grad_fn is None and _differing(stem(_dev(imgs)), want) == 0
+    assert stem(gk.to_device(imgs)).grad_fn is None and gk.differing(stem(gk.to_device(imgs)), want) == 0
     for bad2 in (torch.nn.Conv2d(16, 32, 4, 2, padding=1), torch.nn.Conv2d(16, 32, 4, 2, dilation=2), torch.nn.Conv2d(16, 32, 4, 2, groups=4),
                  torch.nn.Conv2d(16, 32, (4, 3), 2), torch.nn.Conv2d(16, 32, 4, (2, 1)), torch.nn.Conv2d(8, 32, 4, 2), torch.nn.Conv2d(16, 32, 5, 2)):
         with pytest.raises(ValueError):
@@ -291,8 +270,8 @@ def test_module_two_paths():
 def test_refuses_mismatched_tensors():
     import torch
     from red_gym_amd.bitconv import conv_bits2
-    w1, b1, w2, bb = (_dev(x) for x in b2.params2(8, 16, 4, 32))
-    f = _packed(b2.images2(256, 256))
+    w1, b1, w2, bb = (gk.to_device(x) for x in b2.params2(8, 16, 4, 32))
+    f = gk.packed(b2.images2(256, 256))
     for args, kw in (((f, w1, b1, w2, bb), dict(stride1=4, stride2=2)),                          # packed frames without cols
                      ((f, w1, b1, w2, bb), dict(stride1=4, stride2=2, cols=100)),
                      ((f.float(), w1, b1, w2, bb), dict(stride1=4, stride2=2, cols=256)),
@@ -315,11 +294,11 @@ def test_graph_replay():
     import torch
     case = b2.CASES2[1]
     rows, cols, k1, s1, c1, k2, s2, c2 = case
-    P = tuple(_dev(x) for x in b2.params2(k1, c1, k2, c2, seed=7))
+    P = tuple(gk.to_device(x) for x in b2.params2(k1, c1, k2, c2, seed=7))
     fills = [rc.random_images(rows, cols, n=4, seed=s) for s in (1, 2)]
-    eager = [_stem(_dev(f), P, case) for f in fills]
+    eager = [_stem(gk.to_device(f), P, case) for f in fills]
     assert not torch.equal(eager[0], eager[1])
-    frames = _dev(np.zeros_like(fills[0]))
+    frames = gk.to_device(np.zeros_like(fills[0]))
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -329,7 +308,7 @@ def test_graph_replay():
     with torch.cuda.graph(graph):
         out = _stem(frames, P, case)
     for f, want in zip(fills, eager):
-        frames.copy_(_dev(f))
+        frames.copy_(gk.to_device(f))
         graph.replay()
         torch.cuda.synchronize()
         assert torch.equal(out, want)
@@ -348,7 +327,7 @@ def test_closed_loop_from_bitmap_and_ring_to_features(assets):
     env.record_replay(capacity=4 * B, action_dim=AD)
     torch.manual_seed(3)
     stem = BitConvStem(16, 8, 4, 32, 4, 2, on=1.0, cols=cols).cuda()
-    host = tuple(_np(p) for p in (stem.conv1.weight, stem.conv1.bias, stem.conv2.weight, stem.conv2.bias))
+    host = tuple(gk.to_host(p) for p in (stem.conv1.weight, stem.conv1.bias, stem.conv2.weight, stem.conv2.bias))
 
     def checker(imgs):
         return b2.forward2(imgs, host[0], host[1], 4, 1.0, True, host[2], host[3], 2, True)
@@ -362,16 +341,16 @@ def test_closed_loop_from_bitmap_and_ring_to_features(assets):
         if k in (9, 19):
             with torch.no_grad():
                 feats = stem(info['lidar_bitmap'])
-            bitmap = _np(info['lidar_bitmap'])
-            assert feats.shape == (B, 32, 7, 11) and feats.grad_fn is None and _differing(feats, checker(bitmap)) == 0
+            bitmap = gk.to_host(info['lidar_bitmap'])
+            assert feats.shape == (B, 32, 7, 11) and feats.grad_fn is None and gk.differing(feats, checker(bitmap)) == 0
             assert 2 * sum(bool((im == 255).any() and (im == 0).any()) for im in bitmap) >= B
             checked += 1
     first = env.replay._draws
     frames, s_idx, ns_idx, a, r, d, ok = env.replay.sample_frames(32, seed=5)
-    s2 = env.replay.sample_at(torch.as_tensor(_np(env.replay._keep), device=env.device))
+    s2 = env.replay.sample_at(torch.as_tensor(gk.to_host(env.replay._keep), device=env.device))
     assert env.replay._draws == first + 32 and int(ok.sum()) > 0
     with torch.no_grad():
         fs, fns = stem(frames, index=s_idx), stem(frames, index=ns_idx)
-    assert _differing(fs, checker(_np(s2[0]))) == 0 and _differing(fns, checker(_np(s2[3]))) == 0
+    assert gk.differing(fs, checker(gk.to_host(s2[0]))) == 0 and gk.differing(fns, checker(gk.to_host(s2[3]))) == 0
     assert checked == 2 and env.eng.device_errors() == 0
     env.close()

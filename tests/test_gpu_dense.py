@@ -6,59 +6,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import bitconv_cases as bc
 import dense_cases as dc
+import gpu_checks as gk
 import qhead_cases as qh
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7.0
-GUARD = 64
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _dev(a):
-    import torch
-    return None if a is None else torch.as_tensor(np.array(a), device='cuda')
-
-
-def _differing(got, want):
-    got = got if isinstance(got, np.ndarray) else _np(got)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    return int((bc.bit_patterns(got) != bc.bit_patterns(want)).sum())
-
-
-class _Guarded:
-    """count floats with GUARD sentinels either side, the first `off` floats past a 16-byte boundary; optionally a [rows, cols]
-    matrix whose rows lie ld apart, with sentinels between the rows."""
-
-    def __init__(self, count, off=0, fill=SENTINEL):
-        import torch
-        self.whole = torch.full((GUARD + off + count + GUARD,), fill, dtype=torch.float32, device='cuda')
-        self.data = self.whole[GUARD + off:GUARD + off + count]
-        assert self.whole.data_ptr() % 16 == 0 and self.data.data_ptr() % 16 == (4 * off) % 16
-        self.count, self.off = count, off
-
-    @classmethod
-    def matrix(cls, rows, cols, ld, off, values=None):
-        m = cls((rows - 1) * ld + cols, off)
-        m.view = m.data.as_strided((rows, cols), (ld, 1))
-        if values is not None:
-            m.view.copy_(_dev(values))
-        return m
-
-    def margins_intact(self, rows=None, cols=None, ld=None):
-        """The guards, and the floats between the rows of a matrix, still hold the sentinel."""
-        w = _np(self.whole)
-        ok = (w[:GUARD + self.off] == SENTINEL).all() and (w[GUARD + self.off + self.count:] == SENTINEL).all()
-        if rows is not None and ld > cols:
-            body = np.full(rows * ld, SENTINEL, np.float32)
-            body[:self.count] = w[GUARD + self.off:GUARD + self.off + self.count]
-            ok = ok and (body.reshape(rows, ld)[:, cols:] == SENTINEL).all()
-        return bool(ok)
 
 
 class _Raw:
@@ -73,24 +27,24 @@ class _Raw:
         self.lib, self._lib, self.dense = _lib.load(), _lib, dense
 
     def weight(self, w):
-        return _Guarded.matrix(self.H, self.K, self.ld, self.off, w)
+        return gk.Guarded.matrix(self.H, self.K, self.ld, self.off, w, fill=SENTINEL)
 
     def forward(self, x, wm, b, n=None):
         """-> out [n, H] as numpy; the workspace is NaN beforehand and the guards of out and the workspace are checked."""
         import torch
         n = self.n if n is None else n
-        out = _Guarded(n * self.H)
+        out = gk.Guarded(n * self.H, fill=SENTINEL)
         nbytes = self.dense.workspace_bytes(self.cfg, n)
         assert nbytes == dc.paths(n, self.K, self.H, self.S)['workspace'] if n else nbytes == 0
-        ws = _Guarded(nbytes // 4) if nbytes else None
-        if ws is not None:
-            ws.data.fill_(float('nan'))
+        ws = gk.Guarded(nbytes // 4, fill=float('nan')) if nbytes else None
         before = wm.whole.clone()
-        self._lib.check(self.lib.f110_dense_forward(C.byref(self.cfg), x.data_ptr(), n, wm.data.data_ptr(), self._lib.ptr(b), out.data.data_ptr(),
-                                                    None if ws is None else ws.data.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        self._lib.check(self.lib.f110_dense_forward(C.byref(self.cfg), x.data_ptr(), n, wm.ptr, self._lib.ptr(b), out.ptr,
+                                                    None if ws is None else ws.ptr, torch.cuda.current_stream().cuda_stream))
         torch.cuda.synchronize()
-        assert out.margins_intact() and (ws is None or ws.margins_intact()) and torch.equal(wm.whole, before)
-        got = _np(out.data).reshape(n, self.H)
+        assert torch.equal(wm.whole, before)
+        if ws is not None:
+            ws.read()
+        got = out.read().reshape(n, self.H)
         assert n == 0 or not (got == SENTINEL).any()
         return got
 
@@ -98,26 +52,25 @@ class _Raw:
         """-> (grad_x [n, K], grad_weight [H, K], grad_bias [H]) as numpy, None for what `want` leaves out; the guards, the floats
         between the rows of grad_weight and the weight itself are checked."""
         import torch
-        gx = _Guarded(self.n * self.K) if want[0] else None
-        gw = _Guarded.matrix(self.H, self.K, self.ld, self.off) if want[1] else None
-        gb = _Guarded(self.H) if want[2] else None
+        gx = gk.Guarded(self.n * self.K, fill=SENTINEL) if want[0] else None
+        gw = gk.Guarded.matrix(self.H, self.K, self.ld, self.off, fill=SENTINEL) if want[1] else None
+        gb = gk.Guarded(self.H, fill=SENTINEL) if want[2] else None
         before = wm.whole.clone()
-        ptr = lambda g: None if g is None else g.data.data_ptr()       # noqa: E731
-        self._lib.check(self.lib.f110_dense_backward(C.byref(self.cfg), x.data_ptr(), self._lib.ptr(out), go.data_ptr(), self.n, wm.data.data_ptr(),
+        ptr = lambda g: None if g is None else g.ptr       # noqa: E731
+        self._lib.check(self.lib.f110_dense_backward(C.byref(self.cfg), x.data_ptr(), self._lib.ptr(out), go.data_ptr(), self.n, wm.ptr,
                                                      ptr(gx), ptr(gw), ptr(gb), torch.cuda.current_stream().cuda_stream))
         torch.cuda.synchronize()
         assert torch.equal(wm.whole, before)
-        assert (gx is None or gx.margins_intact()) and (gb is None or gb.margins_intact()) and (gw is None or gw.margins_intact(self.H, self.K, self.ld))
-        return (None if gx is None else _np(gx.data).reshape(self.n, self.K), None if gw is None else _np(gw.view), None if gb is None else _np(gb.data))
+        return (None if gx is None else gx.read().reshape(self.n, self.K), None if gw is None else gw.read(), None if gb is None else gb.read())
 
 
 def _layer(shape, r, relu, with_bias):
     """linear_feat forward and backward on leaves made from the reference's arrays -> (out, x.grad, w.grad, b.grad)."""
     from red_gym_amd.dense import linear_feat
-    x, w = _dev(r['x']).requires_grad_(), _dev(r['w']).requires_grad_()
-    b = _dev(r['b']).requires_grad_() if with_bias else None
+    x, w = gk.to_device(r['x']).requires_grad_(), gk.to_device(r['w']).requires_grad_()
+    b = gk.to_device(r['b']).requires_grad_() if with_bias else None
     out = linear_feat(x, w, b, relu=relu, segment=shape[3])
-    out.backward(_dev(r['grad_out']))
+    out.backward(gk.to_device(r['grad_out']))
     return out, x.grad, w.grad, None if b is None else b.grad
 
 
@@ -126,14 +79,14 @@ def test_forward_equals_checker(shape):
     """`==` the checker as raw bit patterns under dc.VARIANTS (relu on and off, bias present and NULL); a second call gives the same bits."""
     from red_gym_amd.dense import linear_feat
     r = dc.reference(shape)
-    x, w, b = _dev(r['x']), _dev(r['w']), _dev(r['b'])
+    x, w, b = gk.to_device(r['x']), gk.to_device(r['w']), gk.to_device(r['b'])
     total = 0
     for v in dc.VARIANTS:
         relu, with_bias = v
         got = linear_feat(x, w, b if with_bias else None, relu=relu, segment=shape[3])
         again = linear_feat(x, w, b if with_bias else None, relu=relu, segment=shape[3])
-        assert got.grad_fn is None and _differing(again, _np(got)) == 0
-        bad = _differing(got, r['out'][v])
+        assert got.grad_fn is None and gk.differing(again, gk.to_host(got)) == 0
+        bad = gk.differing(got, r['out'][v])
         print('%s relu=%s bias=%s: %d of %d elements differ' % (shape, relu, with_bias, bad, got.numel()))
         total += bad
     assert total == 0
@@ -145,11 +98,11 @@ def test_backward_equals_checker_and_repeats(shape):
     for v in ((True, True), (False, False)):
         r = dc.reference(shape)
         out, gx, gw, gb = _layer(shape, r, *v)
-        bad = (_differing(out, r['out'][v]), _differing(gx, r['grad_x'][v]), _differing(gw, r['grad_weight'][v]), 0 if gb is None else _differing(gb, r['grad_bias'][v]))
+        bad = (gk.differing(out, r['out'][v]), gk.differing(gx, r['grad_x'][v]), gk.differing(gw, r['grad_weight'][v]), 0 if gb is None else gk.differing(gb, r['grad_bias'][v]))
         print('%s relu=%s bias=%s: differing elements of out, grad_x, grad_weight, grad_bias: %s' % ((shape,) + v + (bad,)))
         assert bad == (0, 0, 0, 0)
         again = _layer(shape, r, *v)
-        assert all(a is None or _differing(a, _np(c)) == 0 for a, c in zip(again, (out, gx, gw, gb)))
+        assert all(a is None or gk.differing(a, gk.to_host(c)) == 0 for a, c in zip(again, (out, gx, gw, gb)))
     n, K, H, S = shape
     if n * H >= 64:
         g = dc.reference(shape)['g'][(True, True)]
@@ -167,27 +120,27 @@ def test_margins_through_the_raw_abi(shape, layout):
     from red_gym_amd import _lib
     n, K, H, S = shape
     r = dc.reference(shape)
-    x, b, go = _dev(r['x']), _dev(r['b']), _dev(r['grad_out'])
+    x, b, go = gk.to_device(r['x']), gk.to_device(r['b']), gk.to_device(r['grad_out'])
     for v in ((True, True), (False, False)):
         relu, with_bias = v
         raw = _Raw(shape, layout, relu)
         wm = raw.weight(r['w'])
         out = raw.forward(x, wm, b if with_bias else None)
-        assert _differing(out, r['out'][v]) == 0
+        assert gk.differing(out, r['out'][v]) == 0
         assert raw.forward(x, wm, None, 0).size == 0
-        o = _dev(r['out'][v]) if relu else None
+        o = gk.to_device(r['out'][v]) if relu else None
         gx, gw, gb = raw.backward(x, o, go, wm)
-        assert (_differing(gx, r['grad_x'][v]), _differing(gw, r['grad_weight'][v]), _differing(gb, r['grad_bias'][v])) == (0, 0, 0)
+        assert (gk.differing(gx, r['grad_x'][v]), gk.differing(gw, r['grad_weight'][v]), gk.differing(gb, r['grad_bias'][v])) == (0, 0, 0)
         for hole in range(3):
             want = tuple(i != hole for i in range(3))
             got = raw.backward(x, o, go, wm, want)
             for i, (a, name) in enumerate(zip(got, ('grad_x', 'grad_weight', 'grad_bias'))):
-                assert (a is None) == (i == hole) and (a is None or _differing(a, r[name][v]) == 0)
+                assert (a is None) == (i == hole) and (a is None or gk.differing(a, r[name][v]) == 0)
     raw = _Raw(shape, layout, False)
     wm = raw.weight(r['w'])
     lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
     keep = torch.empty(max(n * H, n * K, raw.dense.workspace_bytes(raw.cfg, n) // 4) + 8, device='cuda')
-    ptrs = [x.data_ptr(), wm.data.data_ptr(), keep.data_ptr()]
+    ptrs = [x.data_ptr(), wm.ptr, keep.data_ptr()]
     for hole in range(3):
         a = [None if i == hole else p for i, p in enumerate(ptrs)]
         assert lib.f110_dense_forward(C.byref(raw.cfg), a[0], n, a[1], None, a[2], keep.data_ptr(), stream) == _lib.E_INVALID
@@ -214,7 +167,7 @@ def test_a_row_does_not_depend_on_its_batch():
     n, K, H, S = shape
     r = dc.reference(shape)
     v = (True, True)
-    w, b = _dev(r['w']), _dev(r['b'])
+    w, b = gk.to_device(r['w']), gk.to_device(r['b'])
     big_n, at_small, at_big = 2753, 17, 2000
     assert [dc.paths(m, K, H, S)['path'] for m in (1, n, big_n)] == ['split', 'split', 'registers']
     big = dc.tensor((big_n, K), 77)
@@ -223,12 +176,12 @@ def test_a_row_does_not_depend_on_its_batch():
     big_go[at_big] = r['grad_out'][at_small]
     rows = []
     for xs, gos, at in ((r['x'][at_small:at_small + 1], r['grad_out'][at_small:at_small + 1], 0), (r['x'], r['grad_out'], at_small), (big, big_go, at_big)):
-        x = _dev(xs).requires_grad_()
+        x = gk.to_device(xs).requires_grad_()
         out = linear_feat(x, w, b, relu=True, segment=S)
-        gx, = torch.autograd.grad(out, x, _dev(gos))
-        rows.append((_np(out)[at], _np(gx)[at]))
+        gx, = torch.autograd.grad(out, x, gk.to_device(gos))
+        rows.append((gk.to_host(out)[at], gk.to_host(gx)[at]))
     for out, gx in rows:
-        assert _differing(out, r['out'][v][at_small]) == 0 and _differing(gx, r['grad_x'][v][at_small]) == 0
+        assert gk.differing(out, r['out'][v][at_small]) == 0 and gk.differing(gx, r['grad_x'][v][at_small]) == 0
     assert (r['out'][v][at_small] != 0).any() and (r['grad_x'][v][at_small] != 0).any()
 
 
@@ -242,17 +195,17 @@ def test_sal_shape_on_the_critics_view():
     r = dc.reference(dc.SAL, cols=dc.SAL_COLS, variants=((True, True),))
     v = (True, True)
     full = torch.full((H, K + A), SENTINEL, device='cuda')
-    full[:, :K] = _dev(r['w'])
+    full[:, :K] = gk.to_device(r['w'])
     gfull = torch.full((H, K + A), SENTINEL, device='cuda')
     cfg = dense.validate(K, H, K + A, S, True)
-    x, b, go = _dev(r['x']), _dev(r['b']), _dev(r['grad_out'])
+    x, b, go = gk.to_device(r['x']), gk.to_device(r['b']), gk.to_device(r['grad_out'])
     out = dense.forward_into(cfg, x, full.data_ptr(), b, torch.empty((n, H), device='cuda'))
     assert dense.workspace_bytes(cfg, n) == 32 * n * H * 4
-    assert _differing(out, r['out'][v]) == 0
+    assert gk.differing(out, r['out'][v]) == 0
     gx, gb = torch.empty((n, K), device='cuda'), torch.empty((H,), device='cuda')
     dense.backward_into(cfg, x, out, go, full.data_ptr(), gx, gfull.data_ptr(), gb)
-    assert _differing(gx, r['grad_x'][v]) == 0 and _differing(gb, r['grad_bias'][v]) == 0
-    assert _differing(_np(gfull[:, :K])[:, dc.SAL_COLS], r['grad_weight'][v]) == 0
+    assert gk.differing(gx, r['grad_x'][v]) == 0 and gk.differing(gb, r['grad_bias'][v]) == 0
+    assert gk.differing(gk.to_host(gfull[:, :K])[:, dc.SAL_COLS], r['grad_weight'][v]) == 0
     assert bool((gfull[:, K:] == SENTINEL).all()) and bool((full[:, K:] == SENTINEL).all()) and not bool((gfull[:, :K] == SENTINEL).any())
     assert _lib.load().f110_dense_workspace(C.byref(cfg), 4096) == 0
 
@@ -263,14 +216,14 @@ def test_against_the_reference_actor():
     import torch
     from red_gym_amd.dense import linear_feat
     g, x, w, b = dc.golden_inputs()
-    xd, wd, bd = _dev(x).requires_grad_(), _dev(w).requires_grad_(), _dev(b).requires_grad_()
+    xd, wd, bd = gk.to_device(x).requires_grad_(), gk.to_device(w).requires_grad_(), gk.to_device(b).requires_grad_()
     pre = linear_feat(xd, wd, bd, relu=False)
-    assert _differing(pre, dc.forward(x, w, b, dc.DEFAULT_SEGMENT, False)) == 0
+    assert gk.differing(pre, dc.forward(x, w, b, dc.DEFAULT_SEGMENT, False)) == 0
     # the backward on the recording's own forward: relu's mask from the recorded pre-activation
-    rec = _dev(g['pre'])
-    gm = torch.where(rec > 0, _dev(g['cotangent']), torch.zeros_like(rec))
+    rec = gk.to_device(g['pre'])
+    gm = torch.where(rec > 0, gk.to_device(g['cotangent']), torch.zeros_like(rec))
     pre.backward(gm)
-    dc.golden_check(g, x, w, b, _np(pre), _np(xd.grad), _np(wd.grad)[:, g['cols']], _np(bd.grad))
+    dc.golden_check(g, x, w, b, gk.to_host(pre), gk.to_host(xd.grad), gk.to_host(wd.grad)[:, g['cols']], gk.to_host(bd.grad))
 
 
 def _critic_case(n, F, A, H, seed):
@@ -280,13 +233,13 @@ def _critic_case(n, F, A, H, seed):
     for c in range(2):
         l1, l2 = torch.nn.Linear(F + A, H).cuda(), torch.nn.Linear(H, 1).cuda()
         with torch.no_grad():
-            l1.weight.copy_(_dev(dc.tensor((H, F + A), seed + c)))
-            l1.bias.copy_(_dev((0.5 * rng.normal(size=H)).astype(np.float32)))
-            l2.weight.copy_(_dev((rng.normal(size=(1, H)) / np.sqrt(H)).astype(np.float32)))
+            l1.weight.copy_(gk.to_device(dc.tensor((H, F + A), seed + c)))
+            l1.bias.copy_(gk.to_device((0.5 * rng.normal(size=H)).astype(np.float32)))
+            l2.weight.copy_(gk.to_device((rng.normal(size=(1, H)) / np.sqrt(H)).astype(np.float32)))
         fc1s.append(l1)
         fc2s.append(l2)
-        feats.append(_dev(dc.tensor((n, F), seed + 10 + c)).requires_grad_())
-    action = _dev(np.tanh(rng.normal(size=(n, A)))).requires_grad_()
+        feats.append(gk.to_device(dc.tensor((n, F), seed + 10 + c)).requires_grad_())
+    action = gk.to_device(np.tanh(rng.normal(size=(n, A)))).requires_grad_()
     return feats, action, fc1s, fc2s
 
 
@@ -297,30 +250,30 @@ def test_twin_q_dense_equals_the_chained_checkers():
     from red_gym_amd.qhead import QHead, td_target, twin_q
     n, F, A, H, S = 17, 37, 3, 33, 8
     feats, action, fc1s, fc2s = _critic_case(n, F, A, H, 3)
-    W = [_np(l.weight) for l in fc1s]
-    inp = dict(pre=[dc.chains(_np(f), w[:, :F], S) for f, w in zip(feats, W)], w_act=[np.ascontiguousarray(w[:, F:]) for w in W],
-               b1=[_np(l.bias) for l in fc1s], w2=[_np(l.weight).reshape(-1) for l in fc2s], b2=[_np(l.bias) for l in fc2s], action=_np(action),
+    W = [gk.to_host(l.weight) for l in fc1s]
+    inp = dict(pre=[dc.chains(gk.to_host(f), w[:, :F], S) for f, w in zip(feats, W)], w_act=[np.ascontiguousarray(w[:, F:]) for w in W],
+               b1=[gk.to_host(l.bias) for l in fc1s], w2=[gk.to_host(l.weight).reshape(-1) for l in fc2s], b2=[gk.to_host(l.bias) for l in fc2s], action=gk.to_host(action),
                reward=np.linspace(-1.0, 1.0, n), done=(np.arange(n) % 3 == 0).astype(np.uint8), nlp=np.linspace(-5.0, 2.0, n))
     fwd = qh.forward(inp, target=True, gamma=0.99, alpha=0.2)
     rng = np.random.default_rng(5)
     cq, cm = rng.normal(size=(2, n)).astype(np.float32), rng.normal(size=n).astype(np.float32)
     bwd = qh.backward(inp, fwd, cq, cm)
     q, qmin = twin_q(feats, action, fc1s, fc2s, dense=True, segment=S)
-    assert _differing(q, fwd['q']) == 0 and _differing(qmin, fwd['qmin']) == 0
-    ((q * _dev(cq)).sum() + (qmin * _dev(cm)).sum()).backward()
+    assert gk.differing(q, fwd['q']) == 0 and gk.differing(qmin, fwd['qmin']) == 0
+    ((q * gk.to_device(cq)).sum() + (qmin * gk.to_device(cm)).sum()).backward()
     for c in range(2):
-        gw = _np(fc1s[c].weight.grad)
-        assert _differing(np.ascontiguousarray(gw[:, :F]), dc.grad_weight(bwd['grad_pre'][c], _np(feats[c]))) == 0
-        assert _differing(np.ascontiguousarray(gw[:, F:]), bwd['grad_w_act'][c]) == 0
-        assert _differing(feats[c].grad, dc.grad_x(bwd['grad_pre'][c], W[c][:, :F])) == 0
-        assert _differing(fc1s[c].bias.grad, bwd['grad_b1'][c]) == 0 and _differing(_np(fc2s[c].weight.grad).reshape(-1), bwd['grad_w2'][c]) == 0
-        assert _differing(fc2s[c].bias.grad, bwd['grad_b2'][c]) == 0 and (gw[:, :F] != 0).any() and (gw[:, F:] != 0).any()
-    assert np.array_equal(_np(action.grad), bwd['grad_action'].astype(np.float64))
+        gw = gk.to_host(fc1s[c].weight.grad)
+        assert gk.differing(np.ascontiguousarray(gw[:, :F]), dc.grad_weight(bwd['grad_pre'][c], gk.to_host(feats[c]))) == 0
+        assert gk.differing(np.ascontiguousarray(gw[:, F:]), bwd['grad_w_act'][c]) == 0
+        assert gk.differing(feats[c].grad, dc.grad_x(bwd['grad_pre'][c], W[c][:, :F])) == 0
+        assert gk.differing(fc1s[c].bias.grad, bwd['grad_b1'][c]) == 0 and gk.differing(gk.to_host(fc2s[c].weight.grad).reshape(-1), bwd['grad_w2'][c]) == 0
+        assert gk.differing(fc2s[c].bias.grad, bwd['grad_b2'][c]) == 0 and (gw[:, :F] != 0).any() and (gw[:, F:] != 0).any()
+    assert np.array_equal(gk.to_host(action.grad), bwd['grad_action'].astype(np.float64))
     with torch.no_grad():
-        tv = td_target(feats, action, _dev(inp['nlp']), _dev(inp['reward']), _dev(inp['done']), fc1s, fc2s, 0.99, 0.2, dense=True, segment=S)
-        assert _differing(tv, fwd['target']) == 0
+        tv = td_target(feats, action, gk.to_device(inp['nlp']), gk.to_device(inp['reward']), gk.to_device(inp['done']), fc1s, fc2s, 0.99, 0.2, dense=True, segment=S)
+        assert gk.differing(tv, fwd['target']) == 0
         head = QHead.from_linears(fc1s[0], fc2s[0], dense=True, segment=S)
-        assert _differing(head(feats[0], action)[:, 0], fwd['q'][0]) == 0
+        assert gk.differing(head(feats[0], action)[:, 0], fwd['q'][0]) == 0
     with pytest.raises(ValueError):
         twin_q(feats, action, fc1s, fc2s, dense=True, segment=6)
 
@@ -363,9 +316,9 @@ def test_dense_module_shares_tensors_and_keys():
     fresh.load_state_dict(lin.state_dict())
     lin2 = torch.nn.Linear(100, 130).cuda()
     lin2.load_state_dict(fresh.state_dict())
-    x = _dev(dc.tensor((40, 100), 4))
-    want = dc.forward(_np(x), _np(lin.weight), _np(lin.bias), 36, True)
-    assert _differing(m(x), want) == 0 and _differing(fresh(x), want) == 0 and torch.equal(lin2.weight, lin.weight)
+    x = gk.to_device(dc.tensor((40, 100), 4))
+    want = dc.forward(gk.to_host(x), gk.to_host(lin.weight), gk.to_host(lin.bias), 36, True)
+    assert gk.differing(m(x), want) == 0 and gk.differing(fresh(x), want) == 0 and torch.equal(lin2.weight, lin.weight)
     m(x).sum().backward()
     assert lin.weight.grad is not None and lin.bias.grad is not None
     nobias = Dense(8, 4, bias=False).cuda()
@@ -389,7 +342,7 @@ def test_graph_replay():
     from red_gym_amd.dense import linear_feat
     shape = (40, 100, 130, 36)
     fills = [dc.reference(shape, seed=s) for s in (0, 12)]
-    w, b = _dev(fills[0]['w']), _dev(fills[0]['b'])
+    w, b = gk.to_device(fills[0]['w']), gk.to_device(fills[0]['b'])
     v = (True, True)
 
     def run(x, go, wl, bl):
@@ -399,10 +352,10 @@ def test_graph_replay():
 
     eager = []
     for r in fills:
-        eager.append([t.clone() for t in run(_dev(r['x']).requires_grad_(), _dev(r['grad_out']), w.clone().requires_grad_(), b.clone().requires_grad_())])
-    assert _differing(eager[0][0], fills[0]['out'][v]) == 0 and _differing(eager[0][2], fills[0]['grad_weight'][v]) == 0
+        eager.append([t.clone() for t in run(gk.to_device(r['x']).requires_grad_(), gk.to_device(r['grad_out']), w.clone().requires_grad_(), b.clone().requires_grad_())])
+    assert gk.differing(eager[0][0], fills[0]['out'][v]) == 0 and gk.differing(eager[0][2], fills[0]['grad_weight'][v]) == 0
     assert not torch.equal(eager[0][0], eager[1][0])
-    x, go = torch.zeros_like(_dev(fills[0]['x'])).requires_grad_(), torch.zeros_like(_dev(fills[0]['grad_out']))
+    x, go = torch.zeros_like(gk.to_device(fills[0]['x'])).requires_grad_(), torch.zeros_like(gk.to_device(fills[0]['grad_out']))
     wl, bl = w.clone().requires_grad_(), b.clone().requires_grad_()
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -414,8 +367,8 @@ def test_graph_replay():
         outs = run(x, go, wl, bl)
     for r, want in zip(fills, eager):
         with torch.no_grad():
-            x.copy_(_dev(r['x']))
-            go.copy_(_dev(r['grad_out']))
+            x.copy_(gk.to_device(r['x']))
+            go.copy_(gk.to_device(r['grad_out']))
         graph.replay()
         torch.cuda.synchronize()
         assert all(torch.equal(a.view(torch.int32), c.view(torch.int32)) for a, c in zip(outs, want))

@@ -9,26 +9,11 @@ import pytest
 
 import bitconv_cases as bc
 import featconv_cases as fc
-import replay_cases as rc
+import gpu_checks as gk
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7.0
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _dev(a):
-    import torch
-    return None if a is None else torch.as_tensor(np.array(a), device='cuda')
-
-
-def _differing(got, want):
-    got = got if isinstance(got, np.ndarray) else _np(got)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    return int((bc.bit_patterns(got) != bc.bit_patterns(want)).sum())
 
 
 def _conv(case, x, w, b, relu):
@@ -38,10 +23,10 @@ def _conv(case, x, w, b, relu):
 
 def _backward(case, r, relu, with_bias=True):
     """conv_feat forward and backward on leaves made from the reference's arrays -> (out, x.grad, w.grad, b.grad)."""
-    x, w = _dev(r['x']).requires_grad_(), _dev(r['w']).requires_grad_()
-    b = _dev(r['b']).requires_grad_() if with_bias else None
+    x, w = gk.to_device(r['x']).requires_grad_(), gk.to_device(r['w']).requires_grad_()
+    b = gk.to_device(r['b']).requires_grad_() if with_bias else None
     out = _conv(case, x, w, b, relu)
-    out.backward(_dev(r['grad_out']))
+    out.backward(gk.to_device(r['grad_out']))
     return out, x.grad, w.grad, None if b is None else b.grad
 
 
@@ -52,9 +37,9 @@ def test_forward_equals_checker(case):
     for relu, with_bias in fc.VARIANTS:
         r = fc.reference(case, 3, relu)
         want = fc.finish2(r['acc'], r['b'] if with_bias else None, relu)
-        got = _conv(case, _dev(r['x']), _dev(r['w']), _dev(r['b']) if with_bias else None, relu)
+        got = _conv(case, gk.to_device(r['x']), gk.to_device(r['w']), gk.to_device(r['b']) if with_bias else None, relu)
         assert got.grad_fn is None
-        bad = _differing(got, want)
+        bad = gk.differing(got, want)
         print('%s relu=%s bias=%s: %d of %d elements differ' % (case, relu, with_bias, bad, want.size))
         total += bad
         if want[0].size >= 8:
@@ -72,7 +57,7 @@ def test_backward_equals_checker_and_repeats(case):
     for relu in (True, False):
         r = fc.reference(case, 3, relu)
         out, gx, gw, gb = _backward(case, r, relu)
-        bad = [_differing(out, r['out']), _differing(gx, r['grad_x']), _differing(gw, r['grad_weight']), _differing(gb, r['grad_bias'])]
+        bad = [gk.differing(out, r['out']), gk.differing(gx, r['grad_x']), gk.differing(gw, r['grad_weight']), gk.differing(gb, r['grad_bias'])]
         print('%s relu=%s: out, grad_x, grad_weight, grad_bias differ in %s elements' % (case, relu, bad))
         total += sum(bad)
         again = _backward(case, r, relu)
@@ -85,15 +70,15 @@ def test_backward_equals_checker_and_repeats(case):
     nb = fc.finish2(r['acc'], None, True)
     g = fc.masked(nb, r['grad_out'], True)
     out, gx, gw, gb = _backward(case, r, True, with_bias=False)
-    assert gb is None and _differing(out, nb) == 0 and _differing(gx, fc.grad_x(g, r['w'], case[5], case[1], case[2])) == 0
-    assert _differing(gw, fc.reduce(fc.partials(g, r['x'], case[4], case[5])[0])) == 0
+    assert gb is None and gk.differing(out, nb) == 0 and gk.differing(gx, fc.grad_x(g, r['w'], case[5], case[1], case[2])) == 0
+    assert gk.differing(gw, fc.reduce(fc.partials(g, r['x'], case[4], case[5])[0])) == 0
     # only what needs_input_grad asks: weight alone, x alone
-    w = _dev(r['w']).requires_grad_()
-    _conv(case, _dev(r['x']), w, _dev(r['b']), True).backward(_dev(r['grad_out']))
-    assert _differing(w.grad, r['grad_weight']) == 0
-    x = _dev(r['x']).requires_grad_()
-    _conv(case, x, _dev(r['w']), _dev(r['b']), True).backward(_dev(r['grad_out']))
-    assert _differing(x.grad, r['grad_x']) == 0
+    w = gk.to_device(r['w']).requires_grad_()
+    _conv(case, gk.to_device(r['x']), w, gk.to_device(r['b']), True).backward(gk.to_device(r['grad_out']))
+    assert gk.differing(w.grad, r['grad_weight']) == 0
+    x = gk.to_device(r['x']).requires_grad_()
+    _conv(case, x, gk.to_device(r['w']), gk.to_device(r['b']), True).backward(gk.to_device(r['grad_out']))
+    assert gk.differing(x.grad, r['grad_x']) == 0
 
 
 @pytest.mark.parametrize('case', fc.GAP_CASES)
@@ -107,10 +92,10 @@ def test_grad_x_is_plus_zero_where_no_window_reaches(case):
     assert (bc.bit_patterns(r['grad_x'][:, :, unreached]) == 0).all() and (r['grad_x'][:, :, ~unreached] != 0).any()
     _, gx, _, _ = _backward(case, r, False)
     raw = _Raw(case, False)
-    gx_raw = raw.backward(_dev(r['x']), None, _dev(r['grad_out']), _dev(r['w']), 3, want=(True, False, False), with_ws=False)[0].reshape(r['x'].shape)
-    for got in (_np(gx), gx_raw):
+    gx_raw = raw.backward(gk.to_device(r['x']), None, gk.to_device(r['grad_out']), gk.to_device(r['w']), 3, want=(True, False, False), with_ws=False)[0].reshape(r['x'].shape)
+    for got in (gk.to_host(gx), gx_raw):
         assert int((bc.bit_patterns(got[:, :, inside]) != 0).sum()) == 0 and int((bc.bit_patterns(got[:, :, unreached]) != 0).sum()) == 0
-        assert _differing(got, r['grad_x']) == 0
+        assert gk.differing(got, r['grad_x']) == 0
 
 
 class _Raw:
@@ -123,38 +108,28 @@ class _Raw:
         self.case, self.cfg = case, featconv.make_config(ci, h, w, co, k, s, relu)
         self.oh, self.ow = fc.out_size(h, w, k, s)
 
-    def _buf(self, size):
-        import torch
-        return torch.full((size + 128,), SENTINEL, dtype=torch.float32, device='cuda')
-
-    @staticmethod
-    def _body(buf, size):
-        host = _np(buf)
-        assert (host[:64] == SENTINEL).all() and (host[64 + size:] == SENTINEL).all()
-        return host[64:64 + size]
-
     def forward(self, x, w, b, n):
         import torch
         ci, h, wd, co, k, s = self.case
         size = n * co * self.oh * self.ow
-        buf = self._buf(size)
-        self._lib.check(self.lib.f110_featconv_forward(C.byref(self.cfg), x.data_ptr(), n, w.data_ptr(), self._lib.ptr(b), buf.data_ptr() + 256,
+        buf = gk.Guarded(size, fill=SENTINEL)
+        self._lib.check(self.lib.f110_featconv_forward(C.byref(self.cfg), x.data_ptr(), n, w.data_ptr(), self._lib.ptr(b), buf.ptr,
                                                        torch.cuda.current_stream().cuda_stream))
         torch.cuda.synchronize()
-        return self._body(buf, size).reshape(n, co, self.oh, self.ow)
+        return buf.read().reshape(n, co, self.oh, self.ow)
 
     def backward(self, x, out, go, w, n, want=(True, True, True), with_ws=True):
         """-> (grad_x, grad_weight, grad_bias, workspace) on the host, None for an output passed as NULL."""
         import torch
         ci, h, wd, co, k, s = self.case
         sizes = (n * ci * h * wd, co * ci * k * k, co, n * co * (ci * k * k + 1))
-        bufs = [self._buf(z) if on else None for z, on in zip(sizes, tuple(want) + (with_ws,))]
-        ptrs = [None if t is None else t.data_ptr() + 256 for t in bufs]
+        bufs = [gk.Guarded(z, fill=SENTINEL) if on else None for z, on in zip(sizes, tuple(want) + (with_ws,))]
+        ptrs = [None if t is None else t.ptr for t in bufs]
         rc_ = self.lib.f110_featconv_backward(C.byref(self.cfg), self._lib.ptr(x), self._lib.ptr(out), self._lib.ptr(go), n, self._lib.ptr(w), ptrs[0], ptrs[1], ptrs[2],
                                               ptrs[3], torch.cuda.current_stream().cuda_stream)
         self._lib.check(rc_)
         torch.cuda.synchronize()
-        return [None if t is None else self._body(t, z) for t, z in zip(bufs, sizes)]
+        return [None if t is None else t.read() for t in bufs]
 
 
 @pytest.mark.parametrize('case', (fc.CONV3, fc.CASES[2], fc.CASES[6]))
@@ -164,7 +139,7 @@ def test_batch_independence(case):
     import torch
     ci, h, wd, co, k, s = case
     r = fc.reference(case, 3, True)
-    x, w, b, go = (_dev(r[key]) for key in ('x', 'w', 'b', 'grad_out'))
+    x, w, b, go = (gk.to_device(r[key]) for key in ('x', 'w', 'b', 'grad_out'))
     full = _backward(case, r, True)
     two = {key: r[key][:2] for key in ('x', 'grad_out')}
     two.update(w=r['w'], b=r['b'])
@@ -172,12 +147,12 @@ def test_batch_independence(case):
     assert torch.equal(full[0][:2], part[0]) and torch.equal(full[1][:2], part[1]) and not torch.equal(full[0][0], full[0][2])
     raw = _Raw(case, True)
     out = raw.forward(x, w, b, 3)
-    assert _differing(out, r['out']) == 0
+    assert gk.differing(out, r['out']) == 0
     row = co * (ci * k * k + 1)
-    ws3 = raw.backward(x, _dev(out), go, w, 3)[3].reshape(3, row)
-    ws2 = raw.backward(x[:2].contiguous(), _dev(out[:2]), go[:2].contiguous(), w, 2)[3].reshape(2, row)
+    ws3 = raw.backward(x, gk.to_device(out), go, w, 3)[3].reshape(3, row)
+    ws2 = raw.backward(x[:2].contiguous(), gk.to_device(out[:2]), go[:2].contiguous(), w, 2)[3].reshape(2, row)
     assert np.array_equal(bc.bit_patterns(ws3[:2]), bc.bit_patterns(ws2))
-    assert _differing(ws3[:, :co * ci * k * k].reshape(r['P'].shape), r['P']) == 0 and _differing(ws3[:, co * ci * k * k:], r['B']) == 0
+    assert gk.differing(ws3[:, :co * ci * k * k].reshape(r['P'].shape), r['P']) == 0 and gk.differing(ws3[:, co * ci * k * k:], r['B']) == 0
     assert (ws3[0] != ws3[2]).any()
 
 
@@ -192,7 +167,7 @@ def test_against_the_reference_actor(golden, fixture):
         co, ci, k, _ = w.shape
         case = (ci, xin.shape[2], xin.shape[3], co, k, s)
         raw = _Raw(case, True)
-        got = raw.forward(_dev(xin), _dev(w), _dev(b), rows)
+        got = raw.forward(gk.to_device(xin), gk.to_device(w), gk.to_device(b), rows)
 
         def within(what, v, ref, mag, terms):
             err, bound = np.abs(v.astype(np.float64) - ref.astype(np.float64)), 2.0 * fc.gamma(terms) * mag
@@ -201,7 +176,7 @@ def test_against_the_reference_actor(golden, fixture):
 
         within('out', got, out, fc.forward_fp64(xin, w, b, s)[1], ci * k * k + 1)
         gm = fc.masked(out, go, True)
-        gx, gw, gb, _ = raw.backward(_dev(xin), _dev(out), _dev(go), _dev(w), rows)
+        gx, gw, gb, _ = raw.backward(gk.to_device(xin), gk.to_device(out), gk.to_device(go), gk.to_device(w), rows)
         within('grad_input', gx.reshape(xin.shape), g[name + '_grad_input'], fc.grad_x_fp64(gm, w, s, xin.shape[2], xin.shape[3])[1], co * (-(-k // s)) ** 2)
         _, mw, _, mb = fc.grad_w_fp64(gm, xin, k, s)
         pixels = rows * out.shape[2] * out.shape[3]
@@ -218,22 +193,22 @@ def test_margins_through_the_raw_abi(case):
     from red_gym_amd import _lib
     ci, h, wd, co, k, s = case
     r = fc.reference(case, 3, False)
-    x, w, b, go = (_dev(r[key]) for key in ('x', 'w', 'b', 'grad_out'))
+    x, w, b, go = (gk.to_device(r[key]) for key in ('x', 'w', 'b', 'grad_out'))
     raw = _Raw(case, False)
     out = raw.forward(x, w, b, 3)
-    assert (r['out'] != SENTINEL).all() and _differing(out, r['out']) == 0
+    assert (r['out'] != SENTINEL).all() and gk.differing(out, r['out']) == 0
     assert raw.forward(x, w, b, 0).size == 0
     gx, gw, gb, ws = raw.backward(x, None, go, w, 3)
-    assert _differing(gx.reshape(r['x'].shape), r['grad_x']) == 0 and _differing(gw.reshape(r['w'].shape), r['grad_weight']) == 0
-    assert _differing(gb, r['grad_bias']) == 0 and (ws != SENTINEL).all()
+    assert gk.differing(gx.reshape(r['x'].shape), r['grad_x']) == 0 and gk.differing(gw.reshape(r['w'].shape), r['grad_weight']) == 0
+    assert gk.differing(gb, r['grad_bias']) == 0 and (ws != SENTINEL).all()
     gx, gw, gb, ws = raw.backward(x, None, go, w, 3, want=(True, False, False), with_ws=False)
-    assert gw is None and gb is None and ws is None and _differing(gx.reshape(r['x'].shape), r['grad_x']) == 0
+    assert gw is None and gb is None and ws is None and gk.differing(gx.reshape(r['x'].shape), r['grad_x']) == 0
     gx, gw, gb, ws = raw.backward(x, None, go, None, 3, want=(False, True, False))
-    assert gx is None and gb is None and _differing(gw.reshape(r['w'].shape), r['grad_weight']) == 0
+    assert gx is None and gb is None and gk.differing(gw.reshape(r['w'].shape), r['grad_weight']) == 0
     gx, gw, gb, ws = raw.backward(x, None, go, None, 3, want=(False, False, True))
-    assert gx is None and gw is None and _differing(gb, r['grad_bias']) == 0
+    assert gx is None and gw is None and gk.differing(gb, r['grad_bias']) == 0
     lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
-    ptrs = [x.data_ptr(), w.data_ptr(), _dev(out).data_ptr()]
+    ptrs = [x.data_ptr(), w.data_ptr(), gk.to_device(out).data_ptr()]
     for hole in range(3):
         a = [None if i == hole else p for i, p in enumerate(ptrs)]
         assert lib.f110_featconv_forward(C.byref(raw.cfg), a[0], 3, a[1], None, a[2], stream) == _lib.E_INVALID
@@ -254,7 +229,7 @@ def test_more_items_than_workgroups():
     case, n = fc.LOOP_CASE, fc.LOOP_N
     r = fc.reference(case, n, True)
     out, gx, gw, gb = _backward(case, r, True)
-    assert (_differing(out, r['out']), _differing(gx, r['grad_x']), _differing(gw, r['grad_weight']), _differing(gb, r['grad_bias'])) == (0, 0, 0, 0)
+    assert (gk.differing(out, r['out']), gk.differing(gx, r['grad_x']), gk.differing(gw, r['grad_weight']), gk.differing(gb, r['grad_bias'])) == (0, 0, 0, 0)
     assert (r['out'][-1] != r['out'][0]).any() and (r['grad_x'][-1] != 0).any()
 
 
@@ -305,29 +280,29 @@ def test_trunk_acts_and_learns_on_the_same_bits():
     fresh = Trunk(on=on, cols=256).cuda()
     fresh.load_state_dict(dict(zip(keys, theirs)))
     imgs = np.kron(np.random.default_rng(7).random((2, 32, 32)) < 0.5, np.ones((8, 8), bool)).astype(np.uint8) * 255
-    packed = torch.as_tensor(rc.pack(imgs).view(np.int64), device='cuda')
-    index = _dev(np.array([1, -1, 0, 1], np.int64))
+    packed = gk.packed(imgs)
+    index = gk.to_device(np.array([1, -1, 0, 1], np.int64))
     with torch.no_grad():
-        act, act_ring = trunk(_dev(imgs)), fresh(packed, index=index)
-    learn, learn_ring = trunk(_dev(imgs)), fresh(packed, index=index)
+        act, act_ring = trunk(gk.to_device(imgs)), fresh(packed, index=index)
+    learn, learn_ring = trunk(gk.to_device(imgs)), fresh(packed, index=index)
     assert act.grad_fn is None and learn.grad_fn is not None and act.shape == (2, 32 * 28 * 28) and act_ring.shape == (4, 32 * 28 * 28)
     assert torch.equal(act.view(torch.int32), learn.view(torch.int32)) and torch.equal(act_ring.view(torch.int32), learn_ring.view(torch.int32))
     assert torch.equal(act_ring[0], act[1]) and torch.equal(act_ring[2], act[0]) and not torch.equal(act[0], act[1]) and bool((act_ring[1] != act_ring[0]).any())
-    host = tuple(_np(p) for p in theirs)
+    host = tuple(gk.to_host(p) for p in theirs)
     cot = fc.tensor(tuple(act.shape), 9)
     feats, grads, g_a1 = _trunk_checker(imgs, host, on, cot)
-    assert _differing(act, feats) == 0 and (feats > 0).any()
-    learn.backward(_dev(cot))
+    assert gk.differing(act, feats) == 0 and (feats > 0).any()
+    learn.backward(gk.to_device(cot))
     for name, p, want in zip(keys[2:], theirs[2:], grads):
         assert p.grad is not None and (want != 0).any()
-        assert _differing(p.grad, want.reshape(p.shape)) == 0, name
+        assert gk.differing(p.grad, want.reshape(p.shape)) == 0, name
     leaves = [p.detach().clone().requires_grad_() for p in theirs[:2]]
-    conv_bits(_dev(imgs), leaves[0], leaves[1], stride=4, on=on, relu=True).backward(_dev(g_a1))
+    conv_bits(gk.to_device(imgs), leaves[0], leaves[1], stride=4, on=on, relu=True).backward(gk.to_device(g_a1))
     assert torch.equal(c1.weight.grad, leaves[0].grad) and torch.equal(c1.bias.grad, leaves[1].grad) and bool((c1.weight.grad != 0).any())
     # frozen parameters take the acting path even with grad enabled
     for p in theirs:
         p.requires_grad_(False)
-    frozen = trunk(_dev(imgs))
+    frozen = trunk(gk.to_device(imgs))
     assert frozen.grad_fn is None and torch.equal(frozen, act)
 
 
@@ -337,7 +312,7 @@ def test_graph_replay():
     import torch
     case = fc.CASES[2]
     fills = [fc.reference(case, 3, True, seed=s) for s in (11, 12)]
-    w, b = _dev(fills[0]['w']), _dev(fills[0]['b'])
+    w, b = gk.to_device(fills[0]['w']), gk.to_device(fills[0]['b'])
 
     def run(x, go, wl, bl):
         out = _conv(case, x, wl, bl, True)
@@ -346,10 +321,10 @@ def test_graph_replay():
 
     eager = []
     for r in fills:
-        eager.append([t.clone() for t in run(_dev(r['x']).requires_grad_(), _dev(r['grad_out']), w.clone().requires_grad_(), b.clone().requires_grad_())])
-    assert _differing(eager[0][0], fills[0]['out']) == 0 and _differing(eager[0][2], fills[0]['grad_weight']) == 0
+        eager.append([t.clone() for t in run(gk.to_device(r['x']).requires_grad_(), gk.to_device(r['grad_out']), w.clone().requires_grad_(), b.clone().requires_grad_())])
+    assert gk.differing(eager[0][0], fills[0]['out']) == 0 and gk.differing(eager[0][2], fills[0]['grad_weight']) == 0
     assert not torch.equal(eager[0][0], eager[1][0])
-    x, go = torch.zeros_like(_dev(fills[0]['x'])).requires_grad_(), torch.zeros_like(_dev(fills[0]['grad_out']))
+    x, go = torch.zeros_like(gk.to_device(fills[0]['x'])).requires_grad_(), torch.zeros_like(gk.to_device(fills[0]['grad_out']))
     wl, bl = w.clone().requires_grad_(), b.clone().requires_grad_()
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -361,8 +336,8 @@ def test_graph_replay():
         outs = run(x, go, wl, bl)
     for r, want in zip(fills, eager):
         with torch.no_grad():
-            x.copy_(_dev(r['x']))
-            go.copy_(_dev(r['grad_out']))
+            x.copy_(gk.to_device(r['x']))
+            go.copy_(gk.to_device(r['grad_out']))
         graph.replay()
         torch.cuda.synchronize()
         assert all(torch.equal(a.view(torch.int32), c.view(torch.int32)) for a, c in zip(outs, want))

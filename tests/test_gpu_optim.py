@@ -5,31 +5,16 @@ exchange with torch.optim.Adam in both directions and on SAL's critic; and as cl
 import numpy as np
 import pytest
 
-import bitconv_cases as bc
+import gpu_checks as gk
 import optim_cases as oc
 
 pytestmark = pytest.mark.gpu
 
 CANARY = -7.0                                 # fill around every view: no result of these inputs equals it
-GUARD = 8
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _dev(a):
-    import torch
-    return torch.as_tensor(np.array(a), device='cuda')            # (a copy: the cached inputs are read-only)
-
-
-def _same(got, want):
-    got = got if isinstance(got, np.ndarray) else _np(got)
-    return got.shape == np.asarray(want).shape and bool((bc.bit_patterns(got) == bc.bit_patterns(np.asarray(want, got.dtype))).all())
 
 
 def _state_words(opt):
-    return _np(opt._state)
+    return gk.to_host(opt._state)
 
 
 _cache = {}
@@ -53,7 +38,7 @@ def _sizes_case():
 def _run(opt, params, grads):
     for gs in grads:
         for p, g in zip(params, gs):
-            p.grad = None if g is None else _dev(g)
+            p.grad = None if g is None else gk.to_device(g)
         opt.step()
 
 
@@ -61,11 +46,11 @@ def _assert_equal(opt, params, targets, want):
     ps, ms, vs, ts, state = want
     for i, p in enumerate(params):
         m, v = opt.moments(i)
-        assert _same(p, ps[i]), ('p', i)
-        assert _same(m, ms[i]), ('m', i)
-        assert _same(v, vs[i]), ('v', i)
+        assert gk.same(p, ps[i]), ('p', i)
+        assert gk.same(m, ms[i]), ('m', i)
+        assert gk.same(v, vs[i]), ('v', i)
         if targets is not None:
-            assert _same(targets[i], ts[i]), ('target', i)
+            assert gk.same(targets[i], ts[i]), ('target', i)
     assert np.array_equal(_state_words(opt), oc.state_words(state)), (_state_words(opt), oc.state_words(state))
 
 
@@ -75,8 +60,8 @@ def test_every_size_equals_the_checker(with_targets):
     state `==` the checker."""
     from red_gym_amd.optim import SacAdam
     p0, t0, grads, ref = _sizes_case()
-    params = [_dev(p) for p in p0]
-    targets = [_dev(t) for t in t0] if with_targets else None
+    params = [gk.to_device(p) for p in p0]
+    targets = [gk.to_device(t) for t in t0] if with_targets else None
     opt = SacAdam(params, lr=oc.LR, betas=oc.BETAS, eps=oc.EPS, targets=targets, tau=oc.TAU)
     assert opt.device_state()[:3] == (0, 1.0, 1.0)
     _run(opt, params, grads[:5])
@@ -91,7 +76,6 @@ def test_every_size_equals_the_checker(with_targets):
 def test_misaligned_views_between_canaries(which):
     """p, g and the target in turn, and together, a view at element offset 1, 2, 3 of a larger buffer of canaries (so the tensor takes
     the 4-byte path), for 5 and CHUNK + 1 elements, two steps: the results `==` the checker and every canary is unchanged."""
-    import torch
     from red_gym_amd.optim import SacAdam
     rng = np.random.default_rng(2)
     for n in oc.MISALIGNED_SIZES:
@@ -100,21 +84,20 @@ def test_misaligned_views_between_canaries(which):
         want = oc.run([p0], grads, [t0])
         for off in ((0, 1, 2, 3) if which == 'all' else (1, 2, 3)):
             offs = {k: off if which in (k, 'all') else 0 for k in ('p', 'g', 'target')}
-            bufs = {k: torch.full((GUARD + n + GUARD,), CANARY, dtype=torch.float32, device='cuda') for k in offs}
-            view = {k: bufs[k][GUARD + offs[k]:GUARD + offs[k] + n] for k in offs}
+            bufs = {k: gk.Guarded(n, off=offs[k], fill=CANARY) for k in offs}
+            view = {k: bufs[k].data for k in offs}
             assert all(view[k].data_ptr() % 16 == 4 * offs[k] for k in offs)
-            view['p'].copy_(_dev(p0))
-            view['target'].copy_(_dev(t0))
+            view['p'].copy_(gk.to_device(p0))
+            view['target'].copy_(gk.to_device(t0))
             opt = SacAdam([view['p']], lr=oc.LR, betas=oc.BETAS, eps=oc.EPS, targets=[view['target']], tau=oc.TAU)
             for gs in grads:
-                view['g'].copy_(_dev(gs[0]))
+                view['g'].copy_(gk.to_device(gs[0]))
                 view['p'].grad = view['g']
                 opt.step()
             _assert_equal(opt, [view['p']], [view['target']], want)
-            assert _same(view['g'], grads[-1][0])
+            assert gk.same(view['g'], grads[-1][0])
             for k in offs:
-                b = _np(bufs[k])
-                assert (b[:GUARD + offs[k]] == CANARY).all() and (b[GUARD + offs[k] + n:] == CANARY).all(), (which, n, off, k)
+                bufs[k].read()
 
 
 def test_more_tensors_than_one_launch_holds():
@@ -125,7 +108,7 @@ def test_more_tensors_than_one_launch_holds():
     sizes = [1 + i % 7 for i in range(oc.MAX_TENSORS + 3)]
     p0, t0 = [oc.values(rng, n) for n in sizes], [oc.values(rng, n) for n in sizes]
     grads = [[oc.values(rng, n, 3.0) for n in sizes] for _ in range(2)]
-    params, targets = [_dev(p) for p in p0], [_dev(t) for t in t0]
+    params, targets = [gk.to_device(p) for p in p0], [gk.to_device(t) for t in t0]
     opt = SacAdam(params, targets=targets)
     _run(opt, params, grads)
     want = oc.run(p0, grads, t0)
@@ -141,34 +124,34 @@ def test_a_missing_gradient_leaves_the_parameter_and_moves_its_target():
     p0, t0 = [oc.values(rng, n) for n in sizes], [oc.values(rng, n) for n in sizes]
     grads = [[oc.gradients(rng, n) for n in sizes] for _ in range(3)]
     grads[1][1] = grads[2][1] = None                                     # parameter 1 has a gradient at the first step only
-    params, targets = [_dev(p) for p in p0], [_dev(t) for t in t0]
+    params, targets = [gk.to_device(p) for p in p0], [gk.to_device(t) for t in t0]
     opt = SacAdam(params, targets=targets)
     _run(opt, params, grads[:1])
     after_first = [x.clone() for x in (params[1],) + opt.moments(1)]
     target_first = targets[1].clone()
     _run(opt, params, grads[1:])
     for got, was in zip((params[1],) + opt.moments(1), after_first):
-        assert _same(got, _np(was))
-    assert not _same(targets[1], _np(target_first))
+        assert gk.same(got, gk.to_host(was))
+    assert not gk.same(targets[1], gk.to_host(target_first))
     _assert_equal(opt, params, targets, oc.run(p0, grads, t0))
     # no gradient anywhere: nothing is stepped, the counter stands, the targets still move
     before = [t.clone() for t in targets]
     _run(opt, params, [[None] * len(sizes)])
     assert opt.device_state()[0] == 3
     for i, t in enumerate(targets):
-        assert _same(t, oc.lerp(_np(before[i]), _np(params[i])))
+        assert gk.same(t, oc.lerp(gk.to_host(before[i]), gk.to_host(params[i])))
 
 
 def test_soft_update_alone():
     from red_gym_amd.optim import soft_update
     p0, t0, _, _ = _sizes_case()
-    sources, targets = [_dev(p) for p in p0], [_dev(t) for t in t0]
+    sources, targets = [gk.to_device(p) for p in p0], [gk.to_device(t) for t in t0]
     soft_update(targets, sources, oc.TAU)
     for i in range(len(p0)):
-        assert _same(targets[i], oc.lerp(t0[i], p0[i])), i
-        assert _same(sources[i], p0[i]), i
+        assert gk.same(targets[i], oc.lerp(t0[i], p0[i])), i
+        assert gk.same(sources[i], p0[i]), i
     soft_update(targets, sources, 0.0)
-    assert all(_same(targets[i], oc.lerp(t0[i], p0[i])) for i in range(len(p0)))
+    assert all(gk.same(targets[i], oc.lerp(t0[i], p0[i])) for i in range(len(p0)))
     with pytest.raises(ValueError, match='tau'):
         soft_update(targets, sources, 1.5)
 
@@ -216,10 +199,10 @@ def test_captured_step_replays():
     sizes = [3, 257, oc.CHUNK + 1, 2 * oc.CHUNK + 3]
     p0, t0 = [oc.values(rng, n) for n in sizes], [oc.values(rng, n) for n in sizes]
     grads = [[oc.gradients(rng, n) for n in sizes] for _ in range(3)]
-    eager_p, eager_t = [_dev(p) for p in p0], [_dev(t) for t in t0]
+    eager_p, eager_t = [gk.to_device(p) for p in p0], [gk.to_device(t) for t in t0]
     eager = SacAdam(eager_p, targets=eager_t)
     _run(eager, eager_p, grads)                                          # (also the warm-up: the kernels are loaded before the capture)
-    params, targets = [_dev(p) for p in p0], [_dev(t) for t in t0]
+    params, targets = [gk.to_device(p) for p in p0], [gk.to_device(t) for t in t0]
     static = [torch.zeros_like(p) for p in params]
     for p, g in zip(params, static):
         p.grad = g
@@ -233,10 +216,10 @@ def test_captured_step_replays():
             opt.step()
     torch.cuda.current_stream().wait_stream(s)
     torch.cuda.synchronize()
-    assert opt.device_state()[0] == 0 and all(_same(p, p0[i]) for i, p in enumerate(params))    # capturing runs nothing
+    assert opt.device_state()[0] == 0 and all(gk.same(p, p0[i]) for i, p in enumerate(params))    # capturing runs nothing
     for gs in grads:
         for g, new in zip(static, gs):
-            g.copy_(_dev(new))
+            g.copy_(gk.to_device(new))
         graph.replay()
     torch.cuda.synchronize()
     for i in range(len(sizes)):
@@ -255,15 +238,15 @@ def test_state_dict_interchange_with_torch_adam():
     rng = np.random.default_rng(7)
     sizes = [5, 257, oc.CHUNK + 1]
     grads = [[oc.gradients(rng, n) for n in sizes] for _ in range(6)]
-    params = [_dev(oc.values(rng, n)) for n in sizes]
+    params = [gk.to_device(oc.values(rng, n)) for n in sizes]
     adam = torch.optim.Adam(params, lr=oc.LR, betas=oc.BETAS, eps=oc.EPS)
     for gs in grads[:3]:
         for p, g in zip(params, gs):
-            p.grad = _dev(g)
+            p.grad = gk.to_device(g)
         adam.step()
     sd = adam.state_dict()
-    p3 = [_np(p).copy() for p in params]
-    moments = ([_np(sd['state'][i]['exp_avg']).copy() for i in range(3)], [_np(sd['state'][i]['exp_avg_sq']).copy() for i in range(3)])
+    p3 = [gk.to_host(p).copy() for p in params]
+    moments = ([gk.to_host(sd['state'][i]['exp_avg']).copy() for i in range(3)], [gk.to_host(sd['state'][i]['exp_avg_sq']).copy() for i in range(3)])
     opt = SacAdam(params, lr=1.0, betas=(0.5, 0.5), eps=1.0)            # (every hyperparameter comes from the state_dict)
     opt.load_state_dict(sd)
     assert (opt.lr, opt.betas, opt.eps) == (oc.LR, oc.BETAS, oc.EPS)
@@ -280,7 +263,7 @@ def test_state_dict_interchange_with_torch_adam():
     assert fresh.param_groups[0]['lr'] == oc.LR and tuple(fresh.param_groups[0]['betas']) == oc.BETAS
     assert all(torch.equal(fresh.state[p]['exp_avg'], opt.moments(i)[0]) for i, p in enumerate(params))
     for p, g in zip(params, grads[5]):
-        p.grad = _dev(g)
+        p.grad = gk.to_device(g)
     before = [p.clone() for p in params]
     fresh.step()
     assert all(float(fresh.state[p]['step']) == 6.0 for p in params) and all(not torch.equal(p, b) for p, b in zip(params, before))
@@ -305,17 +288,17 @@ def test_sal_critic_once():
     p0 = [oc.values(rng, n, 0.05) for n in ns]
     t0 = [p + oc.values(rng, n, 0.001) for p, n in zip(p0, ns)]
     grads = [[oc.values(rng, n, 0.01) for n in ns]]
-    params = [_dev(p).view(s) for p, s in zip(p0, oc.SAL_CRITIC)]
-    targets = [_dev(t).view(s) for t, s in zip(t0, oc.SAL_CRITIC)]
+    params = [gk.to_device(p).view(s) for p, s in zip(p0, oc.SAL_CRITIC)]
+    targets = [gk.to_device(t).view(s) for t, s in zip(t0, oc.SAL_CRITIC)]
     opt = SacAdam(params, targets=targets)
     for p, g, s in zip(params, grads[0], oc.SAL_CRITIC):
-        p.grad = _dev(g).view(s)
+        p.grad = gk.to_device(g).view(s)
     opt.step()
     ps, ms, vs, ts, state = oc.run(p0, grads, t0)
     for i, s in enumerate(oc.SAL_CRITIC):
         m, v = opt.moments(i)
-        assert _same(params[i], ps[i].reshape(s)) and _same(m, ms[i].reshape(s)) and _same(v, vs[i].reshape(s)), i
-        assert _same(targets[i], ts[i].reshape(s)), i
+        assert gk.same(params[i], ps[i].reshape(s)) and gk.same(m, ms[i].reshape(s)) and gk.same(v, vs[i].reshape(s)), i
+        assert gk.same(targets[i], ts[i].reshape(s)), i
     assert np.array_equal(_state_words(opt), oc.state_words(state))
 
 
@@ -326,19 +309,19 @@ def test_as_close_to_fp64_adam_as_torch_on_the_gpu():
     from red_gym_amd.optim import SacAdam
     p0, _, grads, _ = _sizes_case()
     want = oc.adam64(p0, grads)
-    ours, theirs = [_dev(p) for p in p0], [_dev(p) for p in p0]
+    ours, theirs = [gk.to_device(p) for p in p0], [gk.to_device(p) for p in p0]
     opt = SacAdam(ours, lr=oc.LR, betas=oc.BETAS, eps=oc.EPS)
     ref = torch.optim.Adam(theirs, lr=oc.LR, betas=oc.BETAS, eps=oc.EPS, foreach=False)
     for gs in grads:
         for a, b, g in zip(ours, theirs, gs):
-            a.grad = _dev(g)
-            b.grad = _dev(g)
+            a.grad = gk.to_device(g)
+            b.grad = gk.to_device(g)
         opt.step()
         ref.step()
     for i, n in enumerate(oc.SIZES):
         if n == 0:
             continue
-        e_torch = np.abs(_np(theirs[i]).astype(np.float64) - want[i])
-        e_ours = np.abs(_np(ours[i]).astype(np.float64) - want[i])
+        e_torch = np.abs(gk.to_host(theirs[i]).astype(np.float64) - want[i])
+        e_ours = np.abs(gk.to_host(ours[i]).astype(np.float64) - want[i])
         print('%d elements: max |torch32 - p64| %.3e, max |SacAdam - p64| %.3e' % (n, e_torch.max(), e_ours.max()))
         assert (e_ours <= 2.0 * e_torch.max() + oc.ulp32(want[i])).all(), n

@@ -9,22 +9,10 @@ import numpy as np
 import pytest
 
 import bitconv_cases as bc
+import gpu_checks as gk
 import policyhead_cases as ph
 
 pytestmark = pytest.mark.gpu
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _dev(a):
-    import torch
-    return None if a is None else torch.as_tensor(np.ascontiguousarray(a), device='cuda')
-
-
-def _bits(a):
-    return bc.bit_patterns(a if isinstance(a, np.ndarray) else _np(a))
 
 
 _pre_cache = {}
@@ -46,13 +34,13 @@ def _case(shape, with_bias):
 def _check_tail(got_action, got_lp, pre, eps, fp32, what):
     t = ph.tail(pre, eps)
     act_b, lp_b = ph.tail_bounds(pre, eps, out_fp32=fp32)
-    err = np.abs(_np(got_action).astype(np.float64) - t['y'])
+    err = np.abs(gk.to_host(got_action).astype(np.float64) - t['y'])
     print('%s: worst action error / bound %.3g' % (what, float((err / np.maximum(act_b, 1e-300)).max())))
     assert (err <= act_b).all(), what
     if eps is None:
         assert got_lp is None
         return
-    err = np.abs(_np(got_lp).astype(np.float64) - t['log_prob'])
+    err = np.abs(gk.to_host(got_lp).astype(np.float64) - t['log_prob'])
     print('%s: worst log_prob error / bound %.3g (largest bound %.3g)' % (what, float((err / np.maximum(lp_b, 1e-300)).max()), float(lp_b.max())))
     assert (err <= lp_b).all(), what
 
@@ -67,7 +55,7 @@ def test_forward_equals_checker(shape):
     n, K, A = shape
     for with_bias in (True, False):
         host, pre = _case(shape, with_bias)
-        h, wm, bm, wl, bl, eps = (_dev(x) for x in host)
+        h, wm, bm, wl, bl, eps = (gk.to_device(x) for x in host)
         if with_bias and A >= 4 and n >= 4:
             t = ph.tail(pre, host[5])
             assert {-20.0, 2.0, -25.0, 3.0} <= set(pre[n // 2, A:].tolist()) and (np.abs(t['y'][n // 3]) == 1.0).any()
@@ -77,9 +65,9 @@ def test_forward_equals_checker(shape):
                 action, lp, mean, ls = sample_actions(h, wm, bm, wl, bl, eps=e_dev, dtype=dtype)
                 assert action.dtype == dtype and tuple(action.shape) == (n, A) and (lp is None) == (e_host is None)
                 assert lp is None or (lp.dtype == dtype and tuple(lp.shape) == (n,))
-                got = _np(mean._base)                                  # (mean is a view of the kernel's pre [n, 2A])
+                got = gk.to_host(mean._base)                                  # (mean is a view of the kernel's pre [n, 2A])
                 assert got.shape == pre.shape and mean.data_ptr() == mean._base.data_ptr()
-                bad = int((_bits(got) != _bits(pre)).sum()) + int((_bits(_np(ls)) != _bits(np.clip(pre[:, A:], np.float32(-20.0), np.float32(2.0)))).sum())
+                bad = gk.differing(got, pre) + gk.differing(ls, np.clip(pre[:, A:], np.float32(-20.0), np.float32(2.0)))
                 print('%s: %d of %d pre-activations differ' % (what, bad, got.size))
                 assert bad == 0, what
                 _check_tail(action, lp, pre, e_host, dtype == torch.float32, what)
@@ -93,22 +81,15 @@ def _raw_forward(host, n, K, A, fp64, sampling, sentinel=-7.0):
     from red_gym_amd import _lib, policyhead
     lib = _lib.load()
     cfg = policyhead.make_config(K, A, fp64)
-    h, wm, bm, wl, bl, eps = (_dev(x) for x in host)
+    h, wm, bm, wl, bl, eps = (gk.to_device(x) for x in host)
     dt = torch.float64 if fp64 else torch.float32
-    G = 64
-    bufs = [torch.full((n * 2 * A + 2 * G,), sentinel, dtype=torch.float32, device='cuda'), torch.full((n * A + 2 * G,), sentinel, dtype=dt, device='cuda'),
-            torch.full((n + 2 * G,), sentinel, dtype=dt, device='cuda')]
-    ptr = [b.data_ptr() + G * b.element_size() for b in bufs]
+    bufs = [gk.Guarded(n * 2 * A, fill=sentinel), gk.Guarded(n * A, dtype=dt, fill=sentinel), gk.Guarded(n, dtype=dt, fill=sentinel)]
+    ptr = [b.ptr for b in bufs]
     _lib.check(lib.f110_policyhead_forward(C.byref(cfg), h.data_ptr(), n, wm.data_ptr(), None if bm is None else bm.data_ptr(), wl.data_ptr(),
                                            None if bl is None else bl.data_ptr(), eps.data_ptr() if sampling else None, ptr[0], ptr[1],
                                            ptr[2] if sampling else None, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    out = []
-    for b, size in zip(bufs, (n * 2 * A, n * A, n)):
-        a = _np(b)
-        assert (a[:G] == sentinel).all() and (a[G + size:] == sentinel).all()
-        out.append(a[G:G + size])
-    return out[0].reshape(n, 2 * A), out[1].reshape(n, A), out[2]
+    return bufs[0].read().reshape(n, 2 * A), bufs[1].read().reshape(n, A), bufs[2].read()
 
 
 @pytest.mark.parametrize('shape', [s for s in ph.FORWARD_SHAPES if s[0] <= 100])
@@ -120,9 +101,9 @@ def test_margins_through_the_raw_abi(shape):
     assert (pre != -7.0).all()
     for fp64 in (True, False):
         p, a, lp = _raw_forward(host, n, K, A, fp64, True)
-        assert (_bits(p) == _bits(pre)).all() and (a != -7.0).all() and (lp != -7.0).all()
+        assert gk.same(p, pre) and (a != -7.0).all() and (lp != -7.0).all()
         p, a, lp = _raw_forward(host, n, K, A, fp64, False)
-        assert (_bits(p) == _bits(pre)).all() and (a != -7.0).all() and (lp == -7.0).all()
+        assert gk.same(p, pre) and (a != -7.0).all() and (lp == -7.0).all()
 
 
 def test_wrong_device_is_refused():
@@ -133,7 +114,7 @@ def test_wrong_device_is_refused():
     lib = _lib.load()
     n, K, A = 5, 100, 3
     cfg = policyhead.make_config(K, A, True)
-    h, wm, bm, wl, bl, eps = (_dev(x) for x in ph.inputs(n, K, A))
+    h, wm, bm, wl, bl, eps = (gk.to_device(x) for x in ph.inputs(n, K, A))
     pre = torch.full((n, 2 * A), -7.0, dtype=torch.float32, device='cuda')
     act, lp = torch.full((n, A), -7.0, dtype=torch.float64, device='cuda'), torch.full((n,), -7.0, dtype=torch.float64, device='cuda')
 
@@ -176,7 +157,7 @@ def test_rows_do_not_depend_on_the_batch():
     from red_gym_amd.policyhead import sample_actions
     K, A = 515, 17
     host = ph.inputs(131, K, A, seed=3)
-    h, wm, bm, wl, bl, eps = (_dev(x) for x in host)
+    h, wm, bm, wl, bl, eps = (gk.to_device(x) for x in host)
     full = sample_actions(h, wm, bm, wl, bl, eps=eps)
     for i in (0, 15, 16, 64, 130):
         one = sample_actions(h[i:i + 1].contiguous(), wm, bm, wl, bl, eps=eps[i:i + 1].contiguous())
@@ -195,7 +176,7 @@ def test_out_is_written_in_place_and_mismatches_are_refused():
     import torch
     from red_gym_amd.policyhead import sample_actions
     n, K, A = 33, 5, 15
-    h, wm, bm, wl, bl, eps = (_dev(x) for x in ph.inputs(n, K, A))
+    h, wm, bm, wl, bl, eps = (gk.to_device(x) for x in ph.inputs(n, K, A))
     want = sample_actions(h, wm, bm, wl, bl, eps=eps)
     raw = torch.full((n, A), 9.0, dtype=torch.float64, device='cuda')
     got = sample_actions(h, wm.requires_grad_(), bm, wl, bl, eps=eps, out=raw)
@@ -223,33 +204,26 @@ def _raw_backward(host, pre, g_y, g_lp, fp64, sampling, fill=float('nan'), skip=
     import torch
     from red_gym_amd import _lib, policyhead
     lib = _lib.load()
-    h, wm, bm, wl, bl, eps = (_dev(x) for x in host)
+    h, wm, bm, wl, bl, eps = (gk.to_device(x) for x in host)
     n, K = h.shape
     A = wm.shape[0]
     cfg = policyhead.make_config(K, A, fp64)
     dt = torch.float64 if fp64 else torch.float32
-    ga, glp = _dev(g_y).to(dt), None if g_lp is None else _dev(g_lp).to(dt)
-    gin = None if g_in is None else _dev(g_in)
-    nbytes = policyhead.workspace_bytes(K, A, n)
-    G = 64
-    ws = torch.full((nbytes // 4 + 2 * G,), fill, dtype=torch.float32, device='cuda')
-    outs = {k: torch.full(s, 7.0, dtype=torch.float32, device='cuda')
-            for k, s in (('grad_h', (n, K)), ('grad_w_mean', (A, K)), ('grad_b_mean', (A,)), ('grad_w_log_std', (A, K)), ('grad_b_log_std', (A,)))}
-    p = {k: (None if k in skip else v.data_ptr()) for k, v in outs.items()}
-    _lib.check(lib.f110_policyhead_backward(C.byref(cfg), h.data_ptr(), n, wm.data_ptr(), wl.data_ptr(), _dev(pre).data_ptr(),
+    ga, glp = gk.to_device(g_y).to(dt), None if g_lp is None else gk.to_device(g_lp).to(dt)
+    gin = None if g_in is None else gk.to_device(g_in)
+    ws = gk.Guarded(policyhead.workspace_bytes(K, A, n) // 4, fill=fill)
+    shapes = dict(grad_h=(n, K), grad_w_mean=(A, K), grad_b_mean=(A,), grad_w_log_std=(A, K), grad_b_log_std=(A,))
+    outs = {k: gk.Guarded(int(np.prod(s)), fill=7.0) for k, s in shapes.items()}
+    p = {k: (None if k in skip else v.ptr) for k, v in outs.items()}
+    _lib.check(lib.f110_policyhead_backward(C.byref(cfg), h.data_ptr(), n, wm.data_ptr(), wl.data_ptr(), gk.to_device(pre).data_ptr(),
                                             eps.data_ptr() if sampling else None, ga.data_ptr(), None if glp is None else glp.data_ptr(),
                                             None if gin is None else gin.data_ptr(),
                                             p['grad_h'], p['grad_w_mean'], p['grad_b_mean'], p['grad_w_log_std'], p['grad_b_log_std'],
-                                            ws.data_ptr() + 4 * G, torch.cuda.current_stream().cuda_stream))
+                                            ws.ptr, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    w = _np(ws)
-    guard = np.float32(fill)
-    same = (lambda a: np.isnan(a).all()) if np.isnan(guard) else (lambda a: (a == guard).all())
-    assert same(w[:G]) and same(w[G + nbytes // 4:])
-    res = {k: _np(v) for k, v in outs.items()}
-    for k in skip:
-        assert (res[k] == 7.0).all()
-    res['g_pre'] = w[G:G + n * 2 * A].reshape(n, 2 * A)
+    res = {k: v.read().reshape(shapes[k]) for k, v in outs.items()}
+    assert all(outs[k].untouched() for k in skip)
+    res['g_pre'] = ws.read()[:n * 2 * A].reshape(n, 2 * A)
     return res
 
 
@@ -282,9 +256,9 @@ def test_backward_within_bounds_and_repeatable(shape):
     from red_gym_amd.policyhead import sample_actions
     n, K, A = shape
     host = ph.inputs(n, K, A, seed=5, special=n > 1)
-    h, wm, bm, wl, bl, eps = (_dev(x) for x in host)
-    pre = _np(sample_actions(h, wm, bm, wl, bl, eps=eps)[2]._base)               # the kernel's own pre
-    assert (_bits(pre) == _bits(ph.pre_activations(*host[:5]))).all()
+    h, wm, bm, wl, bl, eps = (gk.to_device(x) for x in host)
+    pre = gk.to_host(sample_actions(h, wm, bm, wl, bl, eps=eps)[2]._base)               # the kernel's own pre
+    assert gk.same(pre, ph.pre_activations(*host[:5]))
     if n > 1:
         assert (pre[:, A:] > 2.0).any() and (pre[:, A:] < -20.0).any() and ((pre[:, A:] == 2.0) | (pre[:, A:] == -20.0)).any() or A < 4
     rng = np.random.default_rng([n, K, A])
@@ -294,7 +268,7 @@ def test_backward_within_bounds_and_repeatable(shape):
         first = _raw_backward(host, pre, gy, glp, fp64, True)
         _check_grads(first, host, pre, gy, glp, True, '%s fp64=%s sampling' % (shape, fp64))
         second = _raw_backward(host, pre, gy, glp, fp64, True, fill=3.0e38)
-        assert all((_bits(first[k]) == _bits(second[k])).all() for k in first)
+        assert all(gk.same(first[k], second[k]) for k in first)
     g_in = rng.normal(size=(n, 2 * A)).astype(np.float32)                      # a gradient arriving at pre itself joins g_pre
     for sampling, glp in ((True, g_lp), (False, None)):
         _check_grads(_raw_backward(host, pre, g_y, glp, True, sampling, g_in=g_in), host, pre, g_y, glp, sampling,
@@ -303,9 +277,9 @@ def test_backward_within_bounds_and_repeatable(shape):
     _check_grads(ev, host, pre, g_y, None, False, '%s evaluate' % (shape,))
     part = _raw_backward(host, pre, g_y, g_lp, True, True, skip=('grad_h', 'grad_b_mean', 'grad_w_log_std'))
     full = _raw_backward(host, pre, g_y, g_lp, True, True)
-    assert all((_bits(part[k]) == _bits(full[k])).all() for k in ('grad_w_mean', 'grad_b_log_std', 'g_pre'))
+    assert all(gk.same(part[k], full[k]) for k in ('grad_w_mean', 'grad_b_log_std', 'g_pre'))
     only_h = _raw_backward(host, pre, g_y, g_lp, True, True, skip=('grad_w_mean', 'grad_b_mean', 'grad_w_log_std', 'grad_b_log_std'))
-    assert (_bits(only_h['grad_h']) == _bits(full['grad_h'])).all()
+    assert gk.same(only_h['grad_h'], full['grad_h'])
 
 
 @pytest.mark.parametrize('shape', [(2 * ph.R + 3, 70, 17), (ph.R + 1, 33, 3)])
@@ -357,18 +331,18 @@ def _g20_bound_check(golden, run):
         h, eps = g['h'][rows], g['eps'][rows]
         action, lp, mean, ls = run(h, wm, bm, wl, bl, eps)
         pre = ph.pre_activations(h, wm, bm, wl, bl)
-        assert (_bits(_np(mean)) == _bits(pre[:, :A])).all()
+        assert gk.same(mean, pre[:, :A])
         dpre, dy, dlp = ph.reference_bounds(h, wm, bm, wl, bl, eps, pre)
         own_a, own_l = ph.tail_bounds(pre, eps)
         pin_a, pin_l = dy <= 1e-3, dlp <= 1e-3
-        err_a = np.abs(_np(action) - g['action'][rows].astype(np.float64))
-        err_l = np.abs(_np(lp) - g['log_prob'][rows].astype(np.float64))
+        err_a = np.abs(gk.to_host(action) - g['action'][rows].astype(np.float64))
+        err_l = np.abs(gk.to_host(lp) - g['log_prob'][rows].astype(np.float64))
         print('%-16s action %5.1f %% value-pinned, log_prob %5.1f %%' % (name, 100 * pin_a.mean(), 100 * pin_l.mean()))
         assert (err_a[pin_a] <= (dy + own_a)[pin_a]).all() and (err_l[pin_l] <= (dlp + own_l)[pin_l]).all()
         fin = np.isfinite(dlp)                                           # (the coarse pin of test_policyhead_cpu: every finite bound holds)
         assert (err_l[fin] <= (dlp + own_l)[fin]).all()
         sat = np.abs(g['action'][rows]) == 1.0
-        assert (np.abs(_np(action)[sat]) >= 1.0 - 2.0 ** -24).all()
+        assert (np.abs(gk.to_host(action)[sat]) >= 1.0 - 2.0 ** -24).all()
         pinned += int(pin_a.sum()) + int(pin_l.sum())
     assert pinned > 0
 
@@ -397,9 +371,9 @@ def test_module(golden):
 
     def run(h, wm, bm, wl, bl, eps):
         m = PolicyHead(512, 16).cuda()
-        m.load_state_dict({'fc_mean.weight': _dev(wm), 'fc_mean.bias': _dev(bm), 'fc_log_std.weight': _dev(wl), 'fc_log_std.bias': _dev(bl)})
+        m.load_state_dict({'fc_mean.weight': gk.to_device(wm), 'fc_mean.bias': gk.to_device(bm), 'fc_log_std.weight': gk.to_device(wl), 'fc_log_std.bias': gk.to_device(bl)})
         with torch.no_grad():
-            return m.sample(_dev(h), eps=_dev(eps))
+            return m.sample(gk.to_device(h), eps=gk.to_device(eps))
     _g20_bound_check(golden, run)
 
     h = torch.randn((64, 512), device='cuda').relu_()
@@ -485,7 +459,7 @@ def test_closed_loop_eager_and_graph(assets):
     head = PolicyHead(512, AD).cuda()
     with torch.no_grad():
         head.fc_mean.weight.mul_(20.0)                                # (actions that use the whole range, so that paths differ)
-    host = tuple(_np(p) for p in (head.fc_mean.weight, head.fc_mean.bias, head.fc_log_std.weight, head.fc_log_std.bias))
+    host = tuple(gk.to_host(p) for p in (head.fc_mean.weight, head.fc_mean.bias, head.fc_log_std.weight, head.fc_log_std.bias))
     eps_pool = torch.randn((STEPS, B, AD), device='cuda', generator=torch.Generator('cuda').manual_seed(2))
     raw = torch.zeros((B, AD), dtype=torch.float64, device='cuda')
     env.reset(workload.spawn_poses(B, 1))
@@ -522,11 +496,11 @@ def test_closed_loop_eager_and_graph(assets):
             assert torch.equal(x[key], y[key]), (k, key)
     assert not torch.equal(eager[0]['raw'], eager[-1]['raw']) and not torch.equal(eager[0]['state'], eager[-1]['state'])
     for k, o in enumerate(eager):
-        h, eps = _np(o['h']), _np(eps_pool[k])
+        h, eps = gk.to_host(o['h']), gk.to_host(eps_pool[k])
         pre = ph.pre_activations(h, *host)
         act_b, lp_b = ph.tail_bounds(pre, eps)
         t = ph.tail(pre, eps)
-        assert (np.abs(_np(o['raw']) - t['y']) <= act_b).all() and (np.abs(_np(o['lp']) - t['log_prob']) <= lp_b).all(), k
+        assert (np.abs(gk.to_host(o['raw']) - t['y']) <= act_b).all() and (np.abs(gk.to_host(o['lp']) - t['log_prob']) <= lp_b).all(), k
         assert torch.equal(o['stored'], o['raw'].float())
     assert env.eng.device_errors() == 0
     env.close()

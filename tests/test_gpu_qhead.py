@@ -8,26 +8,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import bitconv_cases as bc
+import gpu_checks as gk
 import qhead_cases as qc
 
 pytestmark = pytest.mark.gpu
 
 SENT = -7.0                                   # fill of every output and guard: no result of these inputs equals it
-GUARD = 64
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _dev(a):
-    import torch
-    return None if a is None else torch.as_tensor(np.ascontiguousarray(a), device='cuda')
-
-
-def _bits(a):
-    return bc.bit_patterns(a if isinstance(a, np.ndarray) else _np(a))
 
 
 _cache = {}
@@ -73,39 +59,28 @@ class _Raw:
         for c in range(nc):
             block = np.full(self.H * self.ld + off, SENT, np.float32)
             block[off:].reshape(self.H, self.ld)[:, :self.A] = inp['w_act'][c]
-            wb = _dev(block)
-            t = [_dev(inp['pre'][c]), wb, _dev(inp['b1'][c]) if bias else None, _dev(inp['w2'][c]), _dev(inp['b2'][c]) if bias else None]
+            wb = gk.to_device(block)
+            t = [gk.to_device(inp['pre'][c]), wb, gk.to_device(inp['b1'][c]) if bias else None, gk.to_device(inp['w2'][c]), gk.to_device(inp['b2'][c]) if bias else None]
             self.keep.append(t)
             self.wblocks.append(block)
             self.p.pre[c], self.p.w_act[c], self.p.b1[c] = t[0].data_ptr(), wb.data_ptr() + 4 * off, _lib.ptr(t[2])
             self.p.w2[c], self.p.b2[c] = t[3].data_ptr(), _lib.ptr(t[4])
-        self.action = _dev(inp['action']).to(dt)
-        self.nlp, self.reward, self.done = _dev(inp['nlp']).to(dt), _dev(inp['reward']), _dev(inp['done'])
+        self.action = gk.to_device(inp['action']).to(dt)
+        self.nlp, self.reward, self.done = gk.to_device(inp['nlp']).to(dt), gk.to_device(inp['reward']), gk.to_device(inp['done'])
         self.stream = torch.cuda.current_stream().cuda_stream
-
-    def _guarded(self, size, dtype, fill=SENT):
-        import torch
-        return torch.full((size + 2 * GUARD,), fill, dtype=dtype, device='cuda')
-
-    @staticmethod
-    def _inner(buf, size, fill=SENT):
-        a = _np(buf)
-        same = (lambda x: np.isnan(x).all()) if np.isnan(fill) else (lambda x: (x == fill).all())
-        assert same(a[:GUARD]) and same(a[GUARD + size:]), 'a guard was written'
-        return a[GUARD:GUARD + size]
 
     def forward(self, target=True, qmin=True, gamma=0.99, alpha=0.2):
         import torch
         n, nc = self.n, self.nc
-        bufs = [self._guarded(nc * n, torch.float32), self._guarded(n, torch.float32), self._guarded(n, torch.float32)]
-        ptr = [b.data_ptr() + 4 * GUARD for b in bufs]
+        bufs = [gk.Guarded(size, fill=SENT) for size in (nc * n, n, n)]
+        ptr = [b.ptr for b in bufs]
         self._lib.check(self.lib.f110_qhead_forward(C.byref(self.cfg), C.byref(self.p), self.action.data_ptr(), n, self.reward.data_ptr() if target else None,
                                                     self.done.data_ptr() if target else None, self.nlp.data_ptr() if target else None, gamma, alpha,
                                                     ptr[0], ptr[1] if qmin else None, ptr[2] if target else None, self.stream))
         torch.cuda.synchronize()
         for c in range(nc):                                               # the weights, and what lies between their rows, are as they were
-            assert (_bits(_np(self.keep[c][1])) == _bits(self.wblocks[c])).all()
-        return self._inner(bufs[0], nc * n).reshape(nc, n), self._inner(bufs[1], n), self._inner(bufs[2], n)
+            assert gk.same(self.keep[c][1], self.wblocks[c])
+        return bufs[0].read().reshape(nc, n), bufs[1].read(), bufs[2].read()
 
     def backward(self, q, grad_q, grad_qmin, skip=(), ws_fill=float('nan')):
         """f110_qhead_backward from a workspace of `ws_fill` -> dict of host arrays; outputs named in `skip` are passed as NULL.
@@ -115,22 +90,22 @@ class _Raw:
         n, H, A, nc, ld = self.n, self.H, self.A, self.nc, self.ld
         sizes = dict(grad_pre=n * H, grad_w_act=H * ld, grad_b1=H, grad_w2=H, grad_b2=1)
         g = self._lib.QheadGrads()
-        bufs = {k: [self._guarded(s, torch.float32) for _ in range(nc)] for k, s in sizes.items()}
+        bufs = {k: [gk.Guarded(s, fill=SENT) for _ in range(nc)] for k, s in sizes.items()}
         for k in sizes:
             for c in range(nc):
-                getattr(g, k)[c] = None if k in skip else bufs[k][c].data_ptr() + 4 * GUARD
-        ga = self._guarded(n * A, self.dt)
+                getattr(g, k)[c] = None if k in skip else bufs[k][c].ptr
+        ga = gk.Guarded(n * A, dtype=self.dt, fill=SENT)
         nbytes = qhead.workspace_bytes(H, A, nc, n)
         assert nbytes == qc.workspace_bytes(n, H, A, nc)
-        ws = self._guarded(nbytes // 4, torch.float32, ws_fill)
-        qd, gq, gm = _dev(np.ascontiguousarray(q, np.float32)), _dev(grad_q), _dev(grad_qmin)
+        ws = gk.Guarded(nbytes // 4, fill=ws_fill)
+        qd, gq, gm = gk.to_device(np.ascontiguousarray(q, np.float32)), gk.to_device(grad_q), gk.to_device(grad_qmin)
         self._lib.check(self.lib.f110_qhead_backward(C.byref(self.cfg), C.byref(self.p), self.action.data_ptr(), n, qd.data_ptr(), self._lib.ptr(gq),
-                                                     self._lib.ptr(gm), C.byref(g), None if 'grad_action' in skip else ga.data_ptr() + GUARD * ga.element_size(),
-                                                     ws.data_ptr() + 4 * GUARD, self.stream))
+                                                     self._lib.ptr(gm), C.byref(g), None if 'grad_action' in skip else ga.ptr,
+                                                     ws.ptr, self.stream))
         torch.cuda.synchronize()
-        self._inner(ws, nbytes // 4, ws_fill)
-        res = {k: [self._inner(bufs[k][c], s) for c in range(nc)] for k, s in sizes.items()}
-        res['grad_action'] = self._inner(ga, n * A).reshape(n, A)
+        ws.read()
+        res = {k: [b.read() for b in bufs[k]] for k in sizes}
+        res['grad_action'] = ga.read().reshape(n, A)
         res['grad_pre'] = [a.reshape(n, H) for a in res['grad_pre']]
         res['grad_w_act'] = [a.reshape(H, ld) for a in res['grad_w_act']]
         for k in skip:
@@ -153,13 +128,13 @@ def test_forward_equals_checker(shape):
         raw = _Raw(inp, nc, fp64, bias, ld_extra=3 if bias else 0, off=1 if bias else 0)
         q, qmin, tv = raw.forward()
         what = '%s C=%d fp64=%s bias=%s' % (shape, nc, fp64, bias)
-        bad = [int((_bits(a) != _bits(b)).sum()) for a, b in ((q, want['q']), (qmin, want['qmin']), (tv, want['target']))]
+        bad = [gk.differing(a, b) for a, b in ((q, want['q']), (qmin, want['qmin']), (tv, want['target']))]
         print('%s: %d q, %d qmin, %d target values differ' % ((what,) + tuple(bad)))
         assert bad == [0, 0, 0], what
         q2, qmin2, tv2 = raw.forward()
-        assert (_bits(q2) == _bits(q)).all() and (_bits(qmin2) == _bits(qmin)).all() and (_bits(tv2) == _bits(tv)).all()
+        assert gk.same(q2, q) and gk.same(qmin2, qmin) and gk.same(tv2, tv)
         q3, qmin3, tv3 = raw.forward(target=False, qmin=False)
-        assert (_bits(q3) == _bits(q)).all() and (qmin3 == SENT).all() and (tv3 == SENT).all()
+        assert gk.same(q3, q) and (qmin3 == SENT).all() and (tv3 == SENT).all()
     inp, want = _forward_ref(shape, 2, True, True)
     ties, zero_row, z0_row = qc.special_rows(n, H)
     if H >= 4:
@@ -176,7 +151,7 @@ def test_rows_do_not_depend_on_the_batch():
     n, H, A = 131, 515, 17
     inp, want = _forward_ref((n, H, A), 2, True, True, seed=3)
     full = _Raw(inp, 2, True, True).forward()
-    assert (_bits(full[0]) == _bits(want['q'])).all()
+    assert gk.same(full[0], want['q'])
 
     def pick(rows, total=None):
         sub = dict(inp)
@@ -199,10 +174,10 @@ def test_rows_do_not_depend_on_the_batch():
         return sub, None
     for i in (0, 1, 7, 8, 130):
         one = _Raw(pick(np.array([i]))[0], 2, True, True).forward()
-        assert all((_bits(a[..., i:i + 1]) == _bits(b)).all() for a, b in zip(full, one)), i
+        assert all(gk.same(a[..., i:i + 1], b) for a, b in zip(full, one)), i
     sub, perm = pick(np.arange(n), 4099)
     big = _Raw(sub, 2, True, True).forward()
-    assert all((_bits(a) == _bits(b[..., perm])).all() for a, b in zip(full, big))
+    assert all(gk.same(a, b[..., perm]) for a, b in zip(full, big))
     assert full[0][0, 0] != full[0][0, 1]
 
 
@@ -218,14 +193,14 @@ def _compare_backward(res, want, inp, A, what, skip=()):
     for c in range(len(want['grad_pre'])):
         for k in ('grad_pre', 'grad_b1', 'grad_w2', 'grad_b2'):
             if k not in skip:
-                bad['%s[%d]' % (k, c)] = int((_bits(res[k][c].reshape(-1)) != _bits(want[k][c].reshape(-1))).sum())
+                bad['%s[%d]' % (k, c)] = gk.differing(res[k][c].reshape(-1), want[k][c].reshape(-1))
         if 'grad_w_act' not in skip:
             block = res['grad_w_act'][c]
-            bad['grad_w_act[%d]' % c] = int((_bits(block[:, :A]) != _bits(want['grad_w_act'][c])).sum())
+            bad['grad_w_act[%d]' % c] = gk.differing(block[:, :A], want['grad_w_act'][c])
             assert (block[:, A:] == SENT).all(), '%s: the columns between the rows of grad_w_act[%d] were written' % (what, c)
     if 'grad_action' not in skip:
         ga = res['grad_action']
-        bad['grad_action'] = int((_bits(ga.astype(np.float32)) != _bits(want['grad_action'])).sum()) + int((ga.astype(np.float32) != ga).sum())
+        bad['grad_action'] = gk.differing(ga.astype(np.float32), want['grad_action']) + int((ga.astype(np.float32) != ga).sum())
     print('%s: values that differ: %s' % (what, bad))
     assert not any(bad.values()), (what, bad)
 
@@ -254,7 +229,7 @@ def test_backward_equals_checker(shape):
                 assert all(res['grad_pre'][c][r, 0] == np.float32(0.5) * gm[r] for c in range(2)) and gm[r] != 0
         if mode == 'both':
             again = raw.backward(fwd['q'], gq, gm, ws_fill=3.0e38)
-            assert all((_bits(np.asarray(a)) == _bits(np.asarray(b))).all() for k in res for a, b in zip(res[k], again[k]))
+            assert all(gk.same(a, b) for k in res for a, b in zip(res[k], again[k]))
             part = raw.backward(fwd['q'], gq, gm, skip=('grad_pre', 'grad_b1', 'grad_w_act'))
             _compare_backward(part, want, inp, A, '%s NULL grad_pre, grad_b1, grad_w_act' % (shape,), skip=('grad_pre', 'grad_b1', 'grad_w_act'))
             part = raw.backward(fwd['q'], gq, gm, skip=('grad_action', 'grad_w2', 'grad_b2'))
@@ -312,7 +287,7 @@ def test_module_against_the_torch_sequence():
     assert torch.equal(head(feats[0], action), q[0].unsqueeze(1)) and tuple(head(feats[0], action).shape) == (n, 1)
     ref_q, ref_min = _torch_sequence(feats, action, fc1s, fc2s)
     a32 = action.float()
-    side = _np(q[0] < q[1])
+    side = gk.to_host(q[0] < q[1])
     assert 0.1 < side.mean() < 0.9                                         # both sides of the min occur
     dq = []
     for c in range(2):
@@ -321,14 +296,14 @@ def test_module_against_the_torch_sequence():
         z64 = Fn.linear(x.double(), fc1s[c].weight.double(), fc1s[c].bias.double())
         mag = Fn.linear(x.double().abs(), fc1s[c].weight.double().abs(), fc1s[c].bias.double().abs())
         rel = float(((z32.double() - z64).abs() / mag).max())
-        dz = qc.dz_bound(_np(mag), rel, A, gemm_sides=2)
-        bound = qc.q_bound(dz, _np(torch.relu(z64)), _np(fc2s[c].weight.double()).reshape(-1), float(fc2s[c].bias))
-        err = np.abs(_np(q[c]).astype(np.float64) - _np(ref_q[c][:, 0]).astype(np.float64))
+        dz = qc.dz_bound(gk.to_host(mag), rel, A, gemm_sides=2)
+        bound = qc.q_bound(dz, gk.to_host(torch.relu(z64)), gk.to_host(fc2s[c].weight.double()).reshape(-1), float(fc2s[c].bias))
+        err = np.abs(gk.to_host(q[c]).astype(np.float64) - gk.to_host(ref_q[c][:, 0]).astype(np.float64))
         print('critic %d: fc1 relative error %.3g of sum |w||x|; worst q error %.3g, its bound %.3g' % (c, rel, err.max(), bound[err.argmax()]))
         assert (err <= bound).all() and bound.max() < 1e-3
         dq.append(bound)
     dmin = np.maximum(dq[0], dq[1])
-    assert (np.abs(_np(qmin).astype(np.float64) - _np(ref_min[:, 0])) <= dmin).all()
+    assert (np.abs(gk.to_host(qmin).astype(np.float64) - gk.to_host(ref_min[:, 0])) <= dmin).all()
     # the target against the reference's two fp32 lines
     gamma, alpha = 0.99, 0.2
     reward = torch.randn(n, dtype=torch.float64, device='cuda')
@@ -338,10 +313,10 @@ def test_module_against_the_torch_sequence():
     assert tv.dtype == torch.float32 and tuple(tv.shape) == (n,) and tv.grad_fn is None
     tq = ref_min - alpha * nlp.float().unsqueeze(1)
     ref_tv = reward.float().unsqueeze(1) + (1 - done.float().unsqueeze(1)) * gamma * tq
-    tb = qc.target_bound(dmin, _np(qmin), _np(nlp), _np(reward), _np(done), gamma, alpha)
-    err = np.abs(_np(tv).astype(np.float64) - _np(ref_tv[:, 0]))
+    tb = qc.target_bound(dmin, gk.to_host(qmin), gk.to_host(nlp), gk.to_host(reward), gk.to_host(done), gamma, alpha)
+    err = np.abs(gk.to_host(tv).astype(np.float64) - gk.to_host(ref_tv[:, 0]))
     print('target: worst error %.3g, its bound %.3g' % (err.max(), tb[err.argmax()]))
-    assert (err <= tb).all() and set(_np(done).tolist()) == {0, 1}
+    assert (err <= tb).all() and set(gk.to_host(done).tolist()) == {0, 1}
     assert torch.equal(td_target(feats, action, nlp.unsqueeze(1), reward, done.bool(), fc1s, fc2s, gamma, alpha), tv)
     # gradients: a loss that uses q and qmin, features and action require grad
     f_req = [f.clone().requires_grad_() for f in feats]
@@ -450,8 +425,8 @@ def test_g21_on_the_device(golden):
     def run_forward(inp, target):
         q, qmin, tv = _Raw(inp, 2, False, True, ld_extra=5).forward(target=target, gamma=qc.GAMMA, alpha=qc.ALPHA)
         want = qc.forward(inp, fp32_action=True, target=target, gamma=qc.GAMMA, alpha=qc.ALPHA)
-        assert (_bits(q) == _bits(want['q'])).all() and (_bits(qmin) == _bits(want['qmin'])).all()
-        assert not target or (_bits(tv) == _bits(want['target'])).all()
+        assert gk.same(q, want['q']) and gk.same(qmin, want['qmin'])
+        assert not target or gk.same(tv, want['target'])
         return dict(q=q, qmin=qmin, target=tv if target else None)
 
     def run_backward(inp, q, G):

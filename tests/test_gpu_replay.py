@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import gpu_checks as gk
 import replay_cases as rc
 import shaping_cases as sc
 
@@ -15,12 +16,8 @@ def _env(assets, B, A=1, **kw):
     return F110VecEnv(B, map=os.path.join(assets, 'example_map'), map_ext='.png', num_agents=A, **kw)
 
 
-def _np(t):
-    return t.cpu().numpy()
-
-
 def _packed_u64(t):
-    return np.ascontiguousarray(_np(t)).view(np.uint64)
+    return np.ascontiguousarray(gk.to_host(t)).view(np.uint64)
 
 
 @pytest.mark.parametrize('rows,cols,group', [(256, 256, 'a'), (75, 100, 'b'), (40, 300, 'c'), (3, 1, None)] + [s + (None,) for s in rc.SHAPES])
@@ -46,13 +43,13 @@ def test_pack_and_unpack_equal_numpy(golden, rows, cols, group):
         bad = int((_packed_u64(packed) != want).sum())
         print('%d x %d, %d images: %d differing words' % (rows, cols, imgs.shape[0], bad))
         assert bad == 0
-        back = _np(replay.unpack_bitmaps(packed, cols))
+        back = gk.to_host(replay.unpack_bitmaps(packed, cols))
         assert np.array_equal(back, rc.unpack(want, cols)) and np.array_equal(back, np.where(imgs == 255, 255, 0).astype(np.uint8))
 
 
 def _assert_batch(got, want, what):
     names = ('s', 'a', 'r', 'ns', 'd', 'ok')
-    bad = {k: int((_np(g) != w).sum()) for k, g, w in zip(names, got, want)}
+    bad = {k: int((gk.to_host(g) != w).sum()) for k, g, w in zip(names, got, want)}
     print(what, 'differing elements:', bad, 'valid:', int(want[5].sum()))
     assert not any(bad.values()), (what, bad)
 
@@ -85,10 +82,10 @@ def test_closed_loop_equals_mirror_through_resets(assets, rows, cols):
     def pushed(res, what):
         _, reward, done, info = res
         torch.cuda.synchronize()
-        clock = _np(info['current_time'])
-        want = mirror.push(_np(info['lidar_bitmap']), raw.astype(np.float32), _np(reward), _np(done), clock)
+        clock = gk.to_host(info['current_time'])
+        want = mirror.push(gk.to_host(info['lidar_bitmap']), raw.astype(np.float32), gk.to_host(reward), gk.to_host(done), clock)
         assert info['lidar_bitmap'].shape == (B, rows, cols)
-        assert np.array_equal(_np(info['replay_valid']), want), (what, _np(info['replay_valid']), want)
+        assert np.array_equal(gk.to_host(info['replay_valid']), want), (what, gk.to_host(info['replay_valid']), want)
         assert int(info['replay_count']) == mirror.count
         return clock, want
 
@@ -152,12 +149,12 @@ def test_sample_equals_the_checkers_draw(assets):
     rp = env.replay
     B, T = 6, 4
     # (a) the ring as the run left it: every transition of the last T steps is valid
-    valid = _np(rp.buf['valid'])
+    valid = gk.to_host(rp.buf['valid'])
     count = int(rp.buf['count'])
     assert count == 10 and valid.all()
     idx, ok = rp.draw(256, seed=77)
     want_idx, want_ok, _ = rc.draw(valid, count, 77, 0, 256)
-    assert np.array_equal(_np(idx), want_idx) and np.array_equal(_np(ok), want_ok) and want_ok.all()
+    assert np.array_equal(gk.to_host(idx), want_idx) and np.array_equal(gk.to_host(ok), want_ok) and want_ok.all()
     # (b) the synthetic pattern whose redraw condition the CPU suite has checked: a ring of DRAW_CASE's shape
     env.close()
     c = rc.DRAW_CASE
@@ -167,23 +164,23 @@ def test_sample_equals_the_checkers_draw(assets):
     pattern = rc.draw_case_valid()
     rp.buf['valid'].copy_(torch.as_tensor(pattern))
     s, a, r, ns, d, ok = rp.sample(c['n'], seed=c['seed'])
-    first = _np(rp._keep)
+    first = gk.to_host(rp._keep)
     want_idx, want_ok, _ = rc.draw(pattern, c['count'], c['seed'], 0, c['n'])
-    assert np.array_equal(first, want_idx) and _np(ok).all() and want_ok.all()
+    assert np.array_equal(first, want_idx) and gk.to_host(ok).all() and want_ok.all()
     assert pattern[first // c['B'], first % c['B']].all()                            # no drawn index is invalid
     assert s.shape == (c['n'], 256, 256) and s.dtype == torch.uint8 and a.shape == (c['n'], 16) and r.dtype == torch.float64
     # the stored action names its env and step: a[., 0] = 16 env + 1000 k
     slot, e = first // c['B'], first % c['B']
-    assert np.array_equal(_np(a)[:, 0] % 1000, 16.0 * e)
+    assert np.array_equal(gk.to_host(a)[:, 0] % 1000, 16.0 * e)
     rp.sample(c['n'], seed=c['seed'])
-    second = _np(rp._keep)
+    second = gk.to_host(rp._keep)
     assert np.array_equal(second, rc.draw(pattern, c['count'], c['seed'], c['n'], c['n'])[0]) and not np.array_equal(first, second)
     # (c) an empty buffer: every draw reports ok = 0
     env.record_replay(steps=c['T'])
     s, a, r, ns, d, ok = env.replay.sample(64)
-    assert not _np(ok).any() and (_np(env.replay._keep) == -1).all() and not _np(s).any() and not _np(ns).any()
+    assert not gk.to_host(ok).any() and (gk.to_host(env.replay._keep) == -1).all() and not gk.to_host(s).any() and not gk.to_host(ns).any()
     env.step(torch.zeros((c['B'], 1, 2), dtype=torch.float64, device=env.device))     # one frame, no transition yet
-    assert not _np(env.replay.sample(64)[5]).any() and len(env.replay) == 0
+    assert not gk.to_host(env.replay.sample(64)[5]).any() and len(env.replay) == 0
     assert env.eng.device_errors() == 0
     env.close()
 
@@ -199,7 +196,7 @@ def test_fp32_output(assets, rows, cols):
         assert s.shape == ns.shape == (6, 1, rows, cols) and s.dtype == torch.float32
         assert torch.equal(s, (s8.float() * scale).unsqueeze(1)) and torch.equal(ns, (ns8.float() * scale).unsqueeze(1))
         assert torch.equal(a, a8) and torch.equal(r, r8) and torch.equal(d, d8) and torch.equal(ok, ok8)
-    assert _np(ok8).tolist() == [1, 1, 1, 0, 1, 1] and int(s8.max()) == 255 and not _np(s8[3]).any()
+    assert gk.to_host(ok8).tolist() == [1, 1, 1, 0, 1, 1] and int(s8.max()) == 255 and not gk.to_host(s8[3]).any()
     env.close()
 
 
@@ -309,10 +306,10 @@ def test_switching_off_save_load_and_checkpoints(assets):
     env.load_state_dict(sd)
     n_before = len(env.replay)
     _, _, _, info = env.step(pool[6])
-    assert not _np(info['replay_valid']).any()                                       # the chain was broken: a frame, no transition
-    assert len(env.replay) == n_before - int(_np(saved['valid'])[7 % 4].sum())       # only the evicted step slot's are gone
+    assert not gk.to_host(info['replay_valid']).any()                                       # the chain was broken: a frame, no transition
+    assert len(env.replay) == n_before - int(gk.to_host(saved['valid'])[7 % 4].sum())       # only the evicted step slot's are gone
     _, _, _, info = env.step(pool[7])
-    assert _np(info['replay_valid']).any()
+    assert gk.to_host(info['replay_valid']).any()
     assert env.eng.device_errors() == 0
     env.close()
 
@@ -349,7 +346,7 @@ def test_ring_equals_mirror_on_scripted_frames(assets, rows, cols, action_dim):
         rp.kernel()
         torch.cuda.synchronize()
         valid = mirror.push(frame, q['action'], q['reward'], q['done'], q['clock'])
-        assert np.array_equal(_np(rp.buf['last_valid']), valid), (k, _np(rp.buf['last_valid']), valid)
+        assert np.array_equal(gk.to_host(rp.buf['last_valid']), valid), (k, gk.to_host(rp.buf['last_valid']), valid)
         assert int(rp.buf['count']) == mirror.count
         if k:
             invalid += int((valid == 0).sum())
@@ -363,7 +360,7 @@ def test_ring_equals_mirror_on_scripted_frames(assets, rows, cols, action_dim):
             want32 = tuple(np.where(w == 255, on, np.float32(0.0)).astype(np.float32)[:, None] if i in (0, 3) else w for i, w in enumerate(want))
             _assert_batch(got, want32, '%d x %d, push %d, fp32 * %g' % (rows, cols, k, scale))
     assert invalid >= 1 and terminal >= 1 and len(mirror) == len(rp) > 0
-    assert np.array_equal(_np(rp.buf['valid']), mirror.valid_array())
+    assert np.array_equal(gk.to_host(rp.buf['valid']), mirror.valid_array())
     assert env.eng.device_errors() == 0
     env.close()
 
@@ -380,7 +377,7 @@ def _draw_direct(env, seed, first, n):
     with torch.cuda.device(env.device):
         _lib.check(eng.lib.f110_replay_draw(eng._h, seed, first, n, idx.data_ptr(), ok.data_ptr(), eng._stream()))
     torch.cuda.synchronize()
-    idx, ok = _np(idx), _np(ok)
+    idx, ok = gk.to_host(idx), gk.to_host(ok)
     assert (idx[n:] == -7).all() and (ok[n:] == 9).all(), 'the draw wrote beyond its n = %d outputs' % n
     return idx[:n], ok[:n]
 
@@ -442,15 +439,15 @@ def test_counter_beyond_32_bits(assets, start):
             env.replay_action.copy_(torch.as_tensor(action))
             _, reward, done, info = stepper(pool[3 + k])
             torch.cuda.synchronize()
-            valid = mirror.push(_np(info['lidar_bitmap']), action, _np(reward), _np(done), _np(info['current_time']))
-            assert np.array_equal(_np(info['replay_valid']), valid), (how, k)
+            valid = mirror.push(gk.to_host(info['lidar_bitmap']), action, gk.to_host(reward), gk.to_host(done), gk.to_host(info['current_time']))
+            assert np.array_equal(gk.to_host(info['replay_valid']), valid), (how, k)
             assert int(info['replay_count']) == mirror.count == start + k + 1
             assert not valid.any() if k == 0 else valid.any()
             _assert_batch(rp.sample_at(all_idx), mirror.at(range(T * B)), '%s from %d, push %d' % (how, start, k))
             first = rp._draws
             idx, ok = rp.draw(257, seed=5)
             want_idx, want_ok, _ = rc.draw(mirror.valid_array(), mirror.count, 5, first, 257)
-            assert np.array_equal(_np(idx), want_idx) and np.array_equal(_np(ok), want_ok), (how, k)
+            assert np.array_equal(gk.to_host(idx), want_idx) and np.array_equal(gk.to_host(ok), want_ok), (how, k)
             assert want_ok.all() == (k > 0)
         idx, ok = _draw_direct(env, 5, 2 ** 64 - 3, 257)
         want_idx, want_ok, _ = rc.draw(mirror.valid_array(), mirror.count, 5, 2 ** 64 - 3, 257)

@@ -6,54 +6,31 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import gpu_checks as gk
 import sacloss_cases as sl
 
 pytestmark = pytest.mark.gpu
 
-GUARD, SENTINEL = 64, -7.25
+SENTINEL = -7.25
 ALPHA = 0.2
 
 
-class _Guarded:
-    """count elements of `dtype` with GUARD sentinels either side."""
-
-    def __init__(self, count, dtype=None, fill=None):
-        import torch
-        dtype = torch.float32 if dtype is None else dtype
-        self.whole = torch.full((GUARD + count + GUARD,), SENTINEL, dtype=dtype, device='cuda')
-        self.data = self.whole[GUARD:GUARD + count]
-        self.count = count
-        if fill is not None:
-            self.data.copy_(torch.as_tensor(fill))
-
-    ptr = property(lambda self: self.data.data_ptr())
-
-    def read(self):
-        w = self.whole.cpu().numpy()
-        assert (w[:GUARD] == SENTINEL).all() and (w[GUARD + self.count:] == SENTINEL).all(), 'a guard was written'
-        return w[GUARD:GUARD + self.count].copy()
-
-
-def _bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view(np.uint64 if x.dtype == np.float64 else np.uint32)
-
-
-def _same(got, want):
-    return got.dtype == want.dtype and np.array_equal(_bits(got), _bits(want))
+def _exact(got, want):
+    """The same dtype and the same bits (gk.same alone would cast the checker's array to the buffer's dtype)."""
+    return got.dtype == want.dtype and gk.same(got, want)
 
 
 def _critic_raw(q1, q2, tv, grads=(True, True)):
     import torch
     from red_gym_amd import _lib
     n = tv.shape[0]
-    ins = [_Guarded(n, fill=x) for x in (q1, q2, tv)]
-    loss, g1, g2 = _Guarded(2), _Guarded(n), _Guarded(n)
+    ins = [gk.Guarded(n, fill=SENTINEL, values=x) for x in (q1, q2, tv)]
+    loss, g1, g2 = (gk.Guarded(m, fill=SENTINEL) for m in (2, n, n))
     _lib.check(_lib.load().f110_sac_critic_loss(ins[0].ptr, ins[1].ptr, ins[2].ptr, n, loss.ptr, g1.ptr if grads[0] else None,
                                                 g2.ptr if grads[1] else None, _lib.stream(torch.device('cuda', torch.cuda.current_device()))))
     torch.cuda.synchronize()
     for t, x in zip(ins, (q1, q2, tv)):
-        assert _same(t.read(), x), 'an input was written'
+        assert _exact(t.read(), x), 'an input was written'
     return loss.read(), g1.read(), g2.read()
 
 
@@ -63,12 +40,12 @@ def _actor_raw(logp, qn, alpha):
     n = qn.shape[0]
     f64 = logp.dtype == np.float64
     dt = torch.float64 if f64 else torch.float32
-    lp, q = _Guarded(n, dt, fill=logp), _Guarded(n, fill=qn)
-    loss, glp, gqn = _Guarded(1), _Guarded(n, dt), _Guarded(n)
+    lp, q = gk.Guarded(n, dtype=dt, fill=SENTINEL, values=logp), gk.Guarded(n, fill=SENTINEL, values=qn)
+    loss, glp, gqn = gk.Guarded(1, fill=SENTINEL), gk.Guarded(n, dtype=dt, fill=SENTINEL), gk.Guarded(n, fill=SENTINEL)
     _lib.check(_lib.load().f110_sac_actor_loss(lp.ptr, int(f64), q.ptr, alpha, n, loss.ptr, glp.ptr, gqn.ptr,
                                                _lib.stream(torch.device('cuda', torch.cuda.current_device()))))
     torch.cuda.synchronize()
-    assert _same(lp.read(), logp) and _same(q.read(), qn), 'an input was written'
+    assert _exact(lp.read(), logp) and _exact(q.read(), qn), 'an input was written'
     return loss.read(), glp.read(), gqn.read()
 
 
@@ -80,15 +57,15 @@ def test_raw_abi_equals_the_checker(n):
     want = sl.critic(c['q1'], c['q2'], c['tv'])
     got = _critic_raw(c['q1'], c['q2'], c['tv'])
     print('n = %d: critic losses %r (checker %r)' % (n, got[0].tolist(), want[0].tolist()))
-    assert all(_same(g, w) for g, w in zip(got, want))
+    assert all(_exact(g, w) for g, w in zip(got, want))
     only = _critic_raw(c['q1'], c['q2'], c['tv'], grads=(False, True))
-    assert _same(only[0], want[0]) and (only[1] == SENTINEL).all() and _same(only[2], want[2])
+    assert _exact(only[0], want[0]) and (only[1] == SENTINEL).all() and _exact(only[2], want[2])
     for dt in (np.float64, np.float32):
         c = sl.case(n, logp_dtype=dt)
         want = sl.actor(c['logp'], c['qn'], ALPHA)
         got = _actor_raw(c['logp'], c['qn'], ALPHA)
         print('n = %d: actor loss %r (checker %r), log_prob %s' % (n, got[0].tolist(), want[0].tolist(), np.dtype(dt).name))
-        assert all(_same(g, w) for g, w in zip(got, want)), (n, dt)
+        assert all(_exact(g, w) for g, w in zip(got, want)), (n, dt)
 
 
 def test_the_order_of_the_sum():
@@ -97,16 +74,16 @@ def test_the_order_of_the_sum():
     n = 4096
     c = sl.case(n)
     base = _critic_raw(c['q1'], c['q2'], c['tv'])[0]
-    assert _same(base, sl.critic(c['q1'], c['q2'], c['tv'])[0])
+    assert _exact(base, sl.critic(c['q1'], c['q2'], c['tv'])[0])
     for m in (1, 128):
         p = sl.butterfly(n, m)
-        assert _same(_critic_raw(c['q1'][p], c['q2'][p], c['tv'][p])[0], base), m
+        assert _exact(_critic_raw(c['q1'][p], c['q2'][p], c['tv'][p])[0], base), m
     for n in (257, 4097):
         losses = []
         for apart in (False, True):
             k = sl.cancelling(n, apart)
             got, want = _actor_raw(k['logp'], k['qn'], 1.0)[0], sl.actor(k['logp'], k['qn'], 1.0)[0]
-            assert _same(got, want), (n, apart, got, want)
+            assert _exact(got, want), (n, apart, got, want)
             losses.append(got[0])
         assert losses[0] == np.float32(-(n - 2) / n) and losses[1] != losses[0], (n, losses)
 
@@ -119,7 +96,7 @@ def test_wrappers_and_autograd_at_a_power_of_two():
     from red_gym_amd.sacloss import actor_loss, critic_loss
     n = 64
     c = sl.case(n)
-    dev = lambda x: torch.as_tensor(x, device='cuda')  # noqa: E731
+    dev = gk.to_device
     losses = torch.zeros(3, device='cuda')
     q = torch.stack([dev(c['q1']), dev(c['q2'])])
     grad = torch.empty_like(q)
@@ -127,8 +104,8 @@ def test_wrappers_and_autograd_at_a_power_of_two():
     _, glp, gqn = actor_loss(dev(c['logp']), dev(c['qn']), ALPHA, loss=losses[0:1])
     wc, wa = sl.critic(c['q1'], c['q2'], c['tv']), sl.actor(c['logp'], c['qn'], ALPHA)
     assert out.data_ptr() == losses[1:3].data_ptr() and g1.data_ptr() == grad[0].data_ptr()
-    assert _same(losses.cpu().numpy(), np.concatenate([wa[0], wc[0]]))
-    assert _same(grad.cpu().numpy(), np.stack([wc[1], wc[2]])) and _same(glp.cpu().numpy(), wa[1]) and _same(gqn.cpu().numpy(), wa[2])
+    assert _exact(losses.cpu().numpy(), np.concatenate([wa[0], wc[0]]))
+    assert _exact(grad.cpu().numpy(), np.stack([wc[1], wc[2]])) and _exact(glp.cpu().numpy(), wa[1]) and _exact(gqn.cpu().numpy(), wa[2])
     x1, x2 = dev(c['q1']).requires_grad_(), dev(c['q2']).requires_grad_()
     (F.mse_loss(x1, dev(c['tv'])) + F.mse_loss(x2, dev(c['tv']))).backward()
     assert torch.equal(x1.grad, g1) and torch.equal(x2.grad, g2)
@@ -148,7 +125,7 @@ def test_graph_replay_equals_eager():
     from red_gym_amd.sacloss import actor_loss, critic_loss
     n = 257
     fills = [sl.case(n, seed=s) for s in (0, 5)]
-    dev = lambda x: torch.as_tensor(x, device='cuda')  # noqa: E731
+    dev = gk.to_device
 
     def run(t, losses):
         _, g1, g2 = critic_loss(t['q1'], t['q2'], t['tv'], loss=losses[1:3])

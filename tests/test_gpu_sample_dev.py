@@ -6,15 +6,12 @@ import os
 import numpy as np
 import pytest
 
+import gpu_checks as gk
 import replay_cases as rc
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ('s_idx', 'ns_idx', 'a', 'r', 'd', 'ok')
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 def _ring(assets, rows=40, cols=30):
@@ -42,7 +39,7 @@ def _assert_is_frames_at(rp, got, want_idx):
     """got: sample_frames_dev's result; every output but the indices `==` frames_at(indices)."""
     import torch
     frames, idx = got[0], got[7]
-    assert np.array_equal(_np(idx), want_idx)
+    assert np.array_equal(gk.to_host(idx), want_idx)
     want = rp.frames_at(idx)
     assert frames.data_ptr() == want[0].data_ptr() and frames.shape == want[0].shape
     for name, g, w in zip(NAMES, got[1:7], want[1:]):
@@ -60,15 +57,15 @@ def test_two_calls_continue_one_stream_of_draws(assets):
     _assert_is_frames_at(rp, first, rc.draw(pattern, c['count'], c['seed'], 0, 5)[0])
     _assert_is_frames_at(rp, second, rc.draw(pattern, c['count'], c['seed'], 5, 7)[0])
     assert int(counter) == 12
-    assert _np(first[6]).all() and _np(second[6]).all() and (_np(first[1]) >= 0).all() and _np(second[3]).any()
-    idx = np.concatenate([_np(first[7]), _np(second[7])])
+    assert gk.to_host(first[6]).all() and gk.to_host(second[6]).all() and (gk.to_host(first[1]) >= 0).all() and gk.to_host(second[3]).any()
+    idx = np.concatenate([gk.to_host(first[7]), gk.to_host(second[7])])
     assert pattern[idx // c['B'], idx % c['B']].all()                                  # no drawn index is invalid
     # the stored action names its env: a[., 0] = 16 env + 1000 k
-    assert np.array_equal(_np(second[3])[:, 0] % 1000, 16.0 * (_np(second[7]) % c['B']))
+    assert np.array_equal(gk.to_host(second[3])[:, 0] % 1000, 16.0 * (gk.to_host(second[7]) % c['B']))
     # the host counter of draw() has not moved, and draw() does not move the device counter
     assert rp._draws == host_before
     again, _ = rp.draw(5, seed=c['seed'])
-    assert np.array_equal(_np(again), rc.draw(pattern, c['count'], c['seed'], host_before, 5)[0]) and rp._draws == host_before + 5 and int(counter) == 12
+    assert np.array_equal(gk.to_host(again), rc.draw(pattern, c['count'], c['seed'], host_before, 5)[0]) and rp._draws == host_before + 5 and int(counter) == 12
     # out=: the static tensors are written and returned; a counter past 2^63 draws on (the bits of a uint64)
     out = rp.sample_out(7)
     counter.fill_(-3)
@@ -94,10 +91,10 @@ def test_the_empty_ring(assets):
     for t in out.values():
         t.fill_(3)
     frames, s_idx, ns_idx, a, r, d, ok, idx = env.replay.sample_frames_dev(9, counter, out=out)
-    assert (_np(idx) == -1).all() and (_np(s_idx) == -1).all() and (_np(ns_idx) == -1).all()
-    assert not _np(ok).any() and not _np(a).any() and not _np(r).any() and not _np(d).any() and int(counter) == 9
+    assert (gk.to_host(idx) == -1).all() and (gk.to_host(s_idx) == -1).all() and (gk.to_host(ns_idx) == -1).all()
+    assert not gk.to_host(ok).any() and not gk.to_host(a).any() and not gk.to_host(r).any() and not gk.to_host(d).any() and int(counter) == 9
     env.step(torch.zeros((c['B'], 1, 2), dtype=torch.float64, device=env.device))      # one frame, no transition yet
-    assert not _np(env.replay.sample_frames_dev(9, counter)[6]).any() and int(counter) == 18
+    assert not gk.to_host(env.replay.sample_frames_dev(9, counter)[6]).any() and int(counter) == 18
     assert env.eng.device_errors() == 0
     env.close()
 
@@ -119,7 +116,7 @@ def test_a_captured_sample_draws_afresh_at_every_replay(assets):
         got = rp.sample_frames_dev(n, counter, seed=c['seed'], out=out)
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
-    assert int(counter) == 0 and (_np(out['indices']) == -5).all()
+    assert int(counter) == 0 and (gk.to_host(out['indices']) == -5).all()
     batches = []
     for k in range(3):
         graph.replay()
@@ -128,7 +125,7 @@ def test_a_captured_sample_draws_afresh_at_every_replay(assets):
         assert want_ok.all()
         _assert_is_frames_at(rp, got, want_idx)
         assert int(counter) == (k + 1) * n
-        batches.append(_np(out['indices']).copy())
+        batches.append(gk.to_host(out['indices']).copy())
     assert not np.array_equal(batches[0], batches[1]) and not np.array_equal(batches[1], batches[2])
     assert env.eng.device_errors() == 0
     env.close()

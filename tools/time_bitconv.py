@@ -10,11 +10,12 @@ values are printed (their spread is the run-to-run noise).  Its output belongs i
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 import torch.nn.functional as F
 from red_gym_amd import F110VecEnv, workload
 from red_gym_amd.bitconv import conv_bits
+from timing import report
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 SECTIONS = sys.argv[2:] or ['ring', 'u8_4096', 'u8_65536', 'backward']
@@ -22,31 +23,6 @@ ROWS = COLS = 256
 K, STRIDE, CH = 8, 4, 16
 SCALE = 1.0 / 255.0
 T = 3
-
-
-def window(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(name, fns, n=N, warm=5, rounds=3):
-    for fn in fns.values():
-        for _ in range(warm):
-            fn()
-    vals = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():          # alternating
-            vals[k].append(window(fn, n))
-    for k, v in vals.items():
-        print('%-78s median %10.1f us  (%s)  spread %.1f %%' % (name + k, float(np.median(v)), ' '.join('%.1f' % x for x in v),
-              100.0 * (max(v) - min(v)) / float(np.median(v))), flush=True)
-    return {k: float(np.median(v)) for k, v in vals.items()}
 
 
 def filled_env(B):
@@ -95,10 +71,10 @@ if 'ring' in SECTIONS or 'backward' in SECTIONS:
     if 'ring' in SECTIONS:
         assert torch.allclose(ours(), theirs(), rtol=0, atol=1e-4)
         print('---- forward, %d samples of the ring (out: %.2f GB per frame set)' % (n, out_bytes(n) / 1e9))
-        report('ring  ', {'frames_at + conv_bits(s)': ours, 'sample_at(fp32, scale) + F.conv2d(s)   [unpacks s and ns]': theirs,
-                          'frames_at + conv_bits(s) + conv_bits(ns)': ours_both, 'sample_at(fp32, scale) + F.conv2d(s) + F.conv2d(ns)': theirs_both,
-                          'frames_at alone (locate + a, r, d, ok)': lambda: rp.frames_at(idx),
-                          'write of one out tensor alone (fill_)': (lambda o=torch.empty((n, CH, OH, OW), device='cuda'): o.fill_(1.0))})
+        report({'frames_at + conv_bits(s)': ours, 'sample_at(fp32, scale) + F.conv2d(s)   [unpacks s and ns]': theirs,
+                'frames_at + conv_bits(s) + conv_bits(ns)': ours_both, 'sample_at(fp32, scale) + F.conv2d(s) + F.conv2d(ns)': theirs_both,
+                'frames_at alone (locate + a, r, d, ok)': lambda: rp.frames_at(idx),
+                'write of one out tensor alone (fill_)': (lambda o=torch.empty((n, CH, OH, OW), device='cuda'): o.fill_(1.0))}, N, 5, 3, name='ring  ')
 
     if 'backward' in SECTIONS:
         frames, s_idx, _, _, _, _, _ = rp.frames_at(idx)
@@ -122,8 +98,8 @@ if 'ring' in SECTIONS or 'backward' in SECTIONS:
         ref_w, ref_b = theirs_bwd()
         assert torch.allclose(wg.grad, ref_w, rtol=1e-3, atol=1e-2) and torch.allclose(bg.grad, ref_b, rtol=1e-3, atol=1e-2)
         print('---- backward, %d samples (grad_out: %.2f GB)' % (n, out_bytes(n) / 1e9))
-        r = report('bwd   ', {'conv_bits forward + backward': ours_bwd, 'conv_bits forward alone': ours_fwd_only,
-                              'torch: conv2d_weight on the fp32 images + grad_out.sum': theirs_bwd})
+        r = report({'conv_bits forward + backward': ours_bwd, 'conv_bits forward alone': ours_fwd_only,
+                    'torch: conv2d_weight on the fp32 images + grad_out.sum': theirs_bwd}, N, 5, 3, name='bwd   ')
         print('    f110_bitconv_backward alone (difference of the first two): %.1f us' % (r['conv_bits forward + backward'] - r['conv_bits forward alone']), flush=True)
         del s32, g
 
@@ -146,8 +122,8 @@ for sec in SECTIONS:
         assert torch.allclose(out_holder['o'], out_holder['t'], rtol=0, atol=1e-4)
     fill = torch.empty((n, CH, OH, OW), device='cuda')
     print('---- forward, %d envs\' uint8 bitmaps (in: %.2f GB uint8 = %.2f GB as fp32; out: %.2f GB)' % (n, n * ROWS * COLS / 1e9, n * ROWS * COLS * 4 / 1e9, out_bytes(n) / 1e9))
-    r = report('u8    ', {'conv_bits(lidar_bitmap)': ours_u8, '.float().mul_(scale).unsqueeze(1) + F.conv2d': theirs_u8,
-                          'write of out alone (fill_)': lambda: fill.fill_(1.0)})
+    r = report({'conv_bits(lidar_bitmap)': ours_u8, '.float().mul_(scale).unsqueeze(1) + F.conv2d': theirs_u8,
+                'write of out alone (fill_)': lambda: fill.fill_(1.0)}, N, 5, 3, name='u8    ')
     print('    output write share of conv_bits: %.0f %%' % (100.0 * r['write of out alone (fill_)'] / r['conv_bits(lidar_bitmap)']), flush=True)
     del images, fill
     out_holder.clear()

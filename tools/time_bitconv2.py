@@ -10,41 +10,17 @@ values are printed (their spread is the run-to-run noise).  Its output belongs i
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 import torch.nn.functional as F
 from red_gym_amd import F110VecEnv, workload
 from red_gym_amd.bitconv import conv_bits, conv_bits2
+from timing import report
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 SECTIONS = sys.argv[2:] or ['ring', 'u8_4096', 'u8_65536']
 ROWS = COLS = 256
 T = 3
-
-
-def window(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(name, fns, n=N, warm=3, rounds=3):
-    for fn in fns.values():
-        for _ in range(warm):
-            fn()
-    vals = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():          # alternating
-            vals[k].append(window(fn, n))
-    for k, v in vals.items():
-        print('%-70s median %10.1f us  (%s)  spread %.1f %%' % (name + k, float(np.median(v)), ' '.join('%.1f' % x for x in v),
-              100.0 * (max(v) - min(v)) / float(np.median(v))), flush=True)
-    return {k: float(np.median(v)) for k, v in vals.items()}
 
 
 def peak(fn):
@@ -93,8 +69,8 @@ def section(title, n, src, kw):
     print('peak bytes above the start over one call: conv_bits2 %d, conv_bits -> F.conv2d -> relu_ %d' % (peak(fused), peak(parent)), flush=True)
     a1 = conv_bits(src, w1, b1, stride=4, on=1.0, relu=True, **kw)
     fill = torch.empty((n, 32, 30, 30), device='cuda')
-    r = report('', {'conv_bits2': fused, 'conv_bits(relu) -> F.conv2d -> relu_': parent, 'F.conv2d alone on a kept a1': lambda: F.conv2d(a1, w2, b2, stride=2),
-                    'write of out alone (fill_)': lambda: fill.fill_(1.0)}, n=N if n <= 4096 else max(2, N // 4))
+    r = report({'conv_bits2': fused, 'conv_bits(relu) -> F.conv2d -> relu_': parent, 'F.conv2d alone on a kept a1': lambda: F.conv2d(a1, w2, b2, stride=2),
+                'write of out alone (fill_)': lambda: fill.fill_(1.0)}, N if n <= 4096 else max(2, N // 4), 3, 3)
     print('    conv_bits2 / parent path: %.2f' % (r['conv_bits2'] / r['conv_bits(relu) -> F.conv2d -> relu_']), flush=True)
     del a1, fill
     torch.cuda.empty_cache()

@@ -12,10 +12,11 @@ import ctypes as C
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 from red_gym_amd import F110VecEnv, _lib, workload
 from red_gym_amd.lidar import LidarBitmap
+from timing import report
 
 args = sys.argv[1:]
 VARIANT = None
@@ -28,30 +29,6 @@ SIZES = [int(a) for a in args[1:]] or [4096, 65536]
 T = 3            # step slots of the ring
 ROWS = COLS = 256
 FORMS = ('bytes', 'bits')
-
-
-def window(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(name, fns, n=N, warm=10, rounds=5):
-    for fn in fns.values():
-        for _ in range(warm):
-            fn()
-    vals = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():          # alternating
-            vals[k].append(window(fn, n))
-    for k, v in vals.items():
-        print('%-58s median %9.1f us  min %9.1f max %9.1f  (%s)' % (name + k, float(np.median(v)), min(v), max(v), ' '.join('%.1f' % x for x in v)), flush=True)
-    return {k: float(np.median(v)) for k, v in vals.items()}
 
 
 def variant_renderer(path, num_beams, device):
@@ -106,28 +83,28 @@ for B in SIZES:
         scans = b.eng.t['scans'][:, 0]
         renders['bits, non-temporal stores (variant build)'] = lambda: vr.bits(scans, out=spare)
         renders['bits, product build into the same spare buffer'] = lambda: b.eng.shaper._to_img.bits(scans, out=spare)
-    report('(a) render, ', renders)
+    report(renders, N, 10, 5, name='(a) render, ')
     if VARIANT:
         vr.bits(scans, out=spare)
         torch.cuda.synchronize()
         assert torch.equal(spare, b.eng.shaper.buf['bitmap'])
         vr.close()
         del spare
-    report('(b) shaper kernel (+ clock add), ', {image: (lambda e=envs[image]: shaper_kernel(e)) for image in FORMS})
-    report('(c) replay push (+ clock add), ', dict({image: (lambda e=envs[image]: push(e)) for image in FORMS},
-                                                  **{'clock add alone': lambda: tick(a)}))
+    report({image: (lambda e=envs[image]: shaper_kernel(e)) for image in FORMS}, N, 10, 5, name='(b) shaper kernel (+ clock add), ')
+    report(dict({image: (lambda e=envs[image]: push(e)) for image in FORMS},
+               **{'clock add alone': lambda: tick(a)}), N, 10, 5, name='(c) replay push (+ clock add), ')
 
     def eager(env):
         env.step(env.path_actions(raw))
 
-    report('(d) step + shaper + follower + replay, eager, ', {image: (lambda e=envs[image]: eager(e)) for image in FORMS}, n=max(N // 2, 5))
+    report({image: (lambda e=envs[image]: eager(e)) for image in FORMS}, max(N // 2, 5), 10, 5, name='(d) step + shaper + follower + replay, eager, ')
     bufs = {image: envs[image].build_step_graph() for image in FORMS}
 
     def graphed(env, buf):
         env.path_actions(raw, out=buf)
         env.step_lib_graph()
 
-    report('(d) the same through step_lib_graph, ', {image: (lambda e=envs[image], g=bufs[image]: graphed(e, g)) for image in FORMS}, n=max(N // 2, 5))
+    report({image: (lambda e=envs[image], g=bufs[image]: graphed(e, g)) for image in FORMS}, max(N // 2, 5), 10, 5, name='(d) the same through step_lib_graph, ')
     for image in FORMS:
         env = envs[image]
         bm, fr = env.eng.shaper.buf['bitmap'], env.replay.buf['frames']

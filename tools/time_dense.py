@@ -14,41 +14,17 @@ import os
 import sys
 import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 import torch.nn.functional as F
 from red_gym_amd.dense import DEFAULT_SEGMENT, linear_feat, make_config, workspace_bytes
 from red_gym_amd.qhead import twin_q
+from timing import report
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 SECTIONS = sys.argv[2:] or ['layer', 'critics', 'update']
 MFMA_F32_FLOPS = 157.3e12                     # 256 CUs x 4 SIMDs x 64 FLOP / clk at 2.4 GHz: the fp32 matrix-core (= vector) peak
 K, H, A = 32 * 28 * 28, 512, 16
-
-
-def window(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(name, fns, n=N, warm=3, rounds=3):
-    for fn in fns.values():
-        for _ in range(warm):
-            fn()
-    vals = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():          # alternating
-            vals[k].append(window(fn, n))
-    for k, v in vals.items():
-        print('%-72s median %10.1f us  (%s)  spread %.1f %%' % (name + k, float(np.median(v)), ' '.join('%.1f' % x for x in v),
-              100.0 * (max(v) - min(v)) / float(np.median(v))), flush=True)
-    return {k: float(np.median(v)) for k, v in vals.items()}
 
 
 def layer():
@@ -74,7 +50,7 @@ def layer():
         if rows == 64:
             fns['device copy of fc1.weight\'s bytes'] = lambda: dst.copy_(src)
         few = N if rows <= 4096 else max(2, N // 4)
-        r = report('fc1 forward, %5d rows: ' % rows, fns, n=few)
+        r = report(fns, few, 3, 3, name='fc1 forward, %5d rows: ' % rows)
         print('    linear_feat / torch: %.2f' % (r['linear_feat(relu)'] / r['F.linear -> relu_']), flush=True)
         flops = 2.0 * rows * H * K
         floor = flops / MFMA_F32_FLOPS * 1e6
@@ -88,8 +64,8 @@ def layer():
                 xg.grad = wg.grad = bg.grad = None
                 f(xg, wg, bg).backward(go)
             return run
-        r = report('fc1 forward + backward, %5d rows: ' % rows, {'linear_feat(relu)': both(lambda a, c, d: linear_feat(a, c, d, relu=True)),
-                                                               'F.linear -> relu': both(lambda a, c, d: torch.relu(F.linear(a, c, d)))}, n=few)
+        r = report({'linear_feat(relu)': both(lambda a, c, d: linear_feat(a, c, d, relu=True)),
+                  'F.linear -> relu': both(lambda a, c, d: torch.relu(F.linear(a, c, d)))}, few, 3, 3, name='fc1 forward + backward, %5d rows: ' % rows)
         print('    linear_feat / torch: %.2f (three GEMMs: %.0f us at the matrix-core rate)' % (r['linear_feat(relu)'] / r['F.linear -> relu'], 3 * floor), flush=True)
         del x, xg, go
         torch.cuda.empty_cache()
@@ -116,7 +92,7 @@ def critics():
             qd, qt = twin_q(feats, action, fc1s, fc2s, dense=True)[0], twin_q(feats, action, fc1s, fc2s)[0]
         print('critics, %5d rows: largest difference of q between dense=True and dense=False %.3g (q up to %.3g)'
               % (rows, float((qd - qt).abs().max()), float(qt.abs().max())), flush=True)
-        r = report('twin_q forward + backward, %5d rows: ' % rows, {'dense=True': both(True), 'dense=False': both(False)})
+        r = report({'dense=True': both(True), 'dense=False': both(False)}, N, 3, 3, name='twin_q forward + backward, %5d rows: ' % rows)
         print('    dense / default: %.2f' % (r['dense=True'] / r['dense=False']), flush=True)
         del feats
         torch.cuda.empty_cache()

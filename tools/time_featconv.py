@@ -13,41 +13,17 @@ import os
 import sys
 import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 import torch.nn.functional as F
 from red_gym_amd.bitconv import BitConvStem
 from red_gym_amd.featconv import Trunk, conv_feat
+from timing import report
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 SECTIONS = sys.argv[2:] or ['layers', 'trunk', 'update']
 MFMA_F32_FLOPS = 157.3e12                     # 256 CUs x 4 SIMDs x 64 FLOP / clk at 2.4 GHz: the fp32 matrix-core (= vector) peak
 LAYERS = {'conv2': (16, 63, 32, 4, 2, 30), 'conv3': (32, 30, 32, 3, 1, 28)}
-
-
-def window(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(name, fns, n=N, warm=3, rounds=3):
-    for fn in fns.values():
-        for _ in range(warm):
-            fn()
-    vals = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():          # alternating
-            vals[k].append(window(fn, n))
-    for k, v in vals.items():
-        print('%-72s median %10.1f us  (%s)  spread %.1f %%' % (name + k, float(np.median(v)), ' '.join('%.1f' % x for x in v),
-              100.0 * (max(v) - min(v)) / float(np.median(v))), flush=True)
-    return {k: float(np.median(v)) for k, v in vals.items()}
 
 
 def layers():
@@ -72,7 +48,7 @@ def layers():
                 src = torch.empty((rows * (ci * hw * hw + co * ohw * ohw) // 2,), device='cuda')
                 dst = torch.empty_like(src)
                 fns['device copy of its bytes (x read, out written)'] = lambda: dst.copy_(src)
-            r = report('%s forward, %5d rows: ' % (name, rows), fns, n=N if rows <= 4096 else max(2, N // 4))
+            r = report(fns, N if rows <= 4096 else max(2, N // 4), 3, 3, name='%s forward, %5d rows: ' % (name, rows))
             print('    conv_feat / torch: %.2f' % (r['conv_feat(relu)'] / r['F.conv2d -> relu_']), flush=True)
             if rows == 65536:
                 flops = 2.0 * rows * co * ohw * ohw * ci * k * k
@@ -89,9 +65,9 @@ def layers():
                         xg.grad = wg.grad = bg.grad = None
                         f(xg, wg, bg).backward(go)
                     return run
-                r = report('%s forward + backward, %5d rows: ' % (name, rows),
-                           {'conv_feat(relu)': both(lambda a, c, d: conv_feat(a, c, d, stride=s, relu=True)),
-                            'F.conv2d -> relu': both(lambda a, c, d: torch.relu(F.conv2d(a, c, d, stride=s)))})
+                r = report({'conv_feat(relu)': both(lambda a, c, d: conv_feat(a, c, d, stride=s, relu=True)),
+                            'F.conv2d -> relu': both(lambda a, c, d: torch.relu(F.conv2d(a, c, d, stride=s)))},
+                           N, 3, 3, name='%s forward + backward, %5d rows: ' % (name, rows))
                 print('    conv_feat / torch: %.2f' % (r['conv_feat(relu)'] / r['F.conv2d -> relu']), flush=True)
             del x
             torch.cuda.empty_cache()
@@ -131,9 +107,9 @@ def trunk():
                 m.zero_grad(set_to_none=True)
                 m(imgs).backward(go)
             return run
-        r = report('trunk, no grad, %5d uint8 bitmaps: ' % rows, {'featconv.Trunk': acting(new), 'BitConvStem -> nn.Conv2d -> relu': acting(old)})
+        r = report({'featconv.Trunk': acting(new), 'BitConvStem -> nn.Conv2d -> relu': acting(old)}, N, 3, 3, name='trunk, no grad, %5d uint8 bitmaps: ' % rows)
         print('    new / previous: %.2f' % (r['featconv.Trunk'] / r['BitConvStem -> nn.Conv2d -> relu']), flush=True)
-        r = report('trunk, forward + backward, %5d uint8 bitmaps: ' % rows, {'featconv.Trunk': learning(new), 'BitConvStem -> nn.Conv2d -> relu': learning(old)})
+        r = report({'featconv.Trunk': learning(new), 'BitConvStem -> nn.Conv2d -> relu': learning(old)}, N, 3, 3, name='trunk, forward + backward, %5d uint8 bitmaps: ' % rows)
         print('    new / previous: %.2f' % (r['featconv.Trunk'] / r['BitConvStem -> nn.Conv2d -> relu']), flush=True)
 
 

@@ -15,40 +15,17 @@ import ctypes as C
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import torch
 from red_gym_amd import _lib
 from red_gym_amd.optim import SacAdam
+from timing import report
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 CRITIC = [(16, 1, 8, 8), (16,), (32, 16, 4, 4), (32,), (32, 32, 3, 3), (32,), (512, 25104), (512,), (1, 512), (1,)]
 ACTOR = CRITIC[:6] + [(512, 25088), (512,), (16, 512), (16,), (16, 512), (16,)]
 LR, TAU = 3e-4, 0.005
-
-
-def window(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(fns, n, warm=3, rounds=5):
-    for fn in fns.values():
-        for _ in range(warm):
-            fn()
-    vals = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():          # alternating
-            vals[k].append(window(fn, n))
-    for k, v in vals.items():
-        print('%-52s median %9.1f us  (%s)  spread %.1f %%' % (k, float(np.median(v)), ' '.join('%.1f' % x for x in v),
-              100.0 * (max(v) - min(v)) / float(np.median(v))), flush=True)
-    return {k: float(np.median(v)) for k, v in vals.items()}
 
 
 def network(shapes):
@@ -113,9 +90,9 @@ try:
 except Exception as e:                     # (reported, not hidden: the variant is optional by the torch version)
     print('torch Adam (fused=True): not accepted here: %s' % str(e).splitlines()[0], flush=True)
 fns['device copy, reads + writes = %.3f GB' % (2 * src.numel() * 4 / 1e9)] = lambda: dst.copy_(src)
-med = report(fns, N)
+med = report(fns, N, 3, 5)
 for k, v in med.items():
     print('%-52s %.0f GB/s of the single pass\'s bytes' % (k, nbytes / v / 1e3), flush=True)
 print('the advance launches: %.1f us per update by difference' % (med['SacAdam: 3 steps (2 with targets)'] - med['SacAdam, no advance launches']), flush=True)
-report({'the state advance alone, back to back': advance_alone}, 200)
+report({'the state advance alone, back to back': advance_alone}, 200, 3, 5)
 assert all(bool(torch.isfinite(p).all()) for p in critics[0] + targets[0] + actor)

@@ -7,29 +7,13 @@ values are printed.  Results: profiles/r08_pathfollow.txt."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import torch
 from red_gym_amd import F110VecEnv, workload
+from timing import report
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-
-
-def window(fn, n=N):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(name, fn, warm=20, rounds=5):
-    for _ in range(warm):
-        fn()
-    v = [window(fn) for _ in range(rounds)]
-    print('%-64s median %9.1f us  (%s)' % (name, float(np.median(v)), ' '.join('%.1f' % x for x in v)), flush=True)
 
 
 for B in (65536, 4096):
@@ -47,20 +31,20 @@ for B in (65536, 4096):
         idx.fill_(-1)                         # (the fill is ~2 us)
         fo.act(raw, out)
 
-    report('%5d x 1 (a) act, every env decodes (+ index fill)' % B, act_all)
+    report({'%5d x 1 (a) act, every env decodes (+ index fill)' % B: act_all}, N, 20, 5)
     idx.zero_()
-    report('%5d x 1 (a) act, no env decodes' % B, lambda: fo.act(raw, out))
+    report({'%5d x 1 (a) act, no env decodes' % B: lambda: fo.act(raw, out)}, N, 20, 5)
 
     def advance():
         env.eng.t['current_time'].add_(env.timestep)   # (the kernel skips an env whose clock stands still; the add is ~2 us)
         fo.kernel()
 
-    report('%5d x 1 (b) advance (+ clock add)' % B, advance)
+    report({'%5d x 1 (b) advance (+ clock add)' % B: advance}, N, 20, 5)
     env.reset(torch.as_tensor(workload.spawn_poses(B, 1), device=env.device))
     acts = env.path_actions(raw).clone()
-    report('%5d x 1 (c) path_actions + step, follower on' % B, lambda: env.step(env.path_actions(raw, out=out)), rounds=3)
+    report({'%5d x 1 (c) path_actions + step, follower on' % B: lambda: env.step(env.path_actions(raw, out=out))}, N, 20, 3)
     env.follow_paths(False)
-    report('%5d x 1 (c) step, follower off' % B, lambda: env.step(acts), rounds=3)
+    report({'%5d x 1 (c) step, follower off' % B: lambda: env.step(acts)}, N, 20, 3)
     assert env.eng.device_errors() == 0
     env.close()
 print('%d launches per window' % N)

@@ -12,40 +12,16 @@ import math
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 import torch.nn.functional as F
 from red_gym_amd.policyhead import sample_actions
+from timing import report
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 SIZES = [int(a) for a in sys.argv[2:]] or [64, 4096, 65536]
 K, A = 512, 16
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
-
-
-def window(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(fns, n, warm=5, rounds=3):
-    for fn in fns.values():
-        for _ in range(warm):
-            fn()
-    vals = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():          # alternating
-            vals[k].append(window(fn, n))
-    for k, v in vals.items():
-        print('%-64s median %10.1f us  (%s)  spread %.1f %%' % (k, float(np.median(v)), ' '.join('%.1f' % x for x in v),
-              100.0 * (max(v) - min(v)) / float(np.median(v))), flush=True)
-    return {k: float(np.median(v)) for k, v in vals.items()}
 
 
 def torch_head(h, wm, bm, wl, bl, eps):
@@ -98,7 +74,7 @@ for n in SIZES:
     if n == max(SIZES):
         copy = torch.empty_like(h)
         fns['device copy of h (%.0f MB read + as much written)' % (n * K * 4 / 1e6)] = lambda: copy.copy_(h)
-    r = report(fns, launches)
+    r = report(fns, launches, 5, 3)
     print('    sample_actions / torch: forward %.2f, forward + backward %.2f' % (
         r['forward: sample_actions'] / r['forward: torch sequence + .double()'],
         r['forward + backward: sample_actions'] / r['forward + backward: torch sequence']), flush=True)

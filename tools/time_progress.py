@@ -5,9 +5,11 @@ turn) so that the spread is visible.  Results: profiles/r06_progress.txt."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import torch
 from red_gym_amd import F110VecEnv, workload
+from timing import window
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 200
@@ -25,14 +27,7 @@ assert env.eng._plan_key is not None
 def timed(fn, n=N, warm=20):
     for _ in range(warm):
         fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
+    return window(fn, n)
 
 
 def kernels():

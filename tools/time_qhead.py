@@ -17,40 +17,16 @@ values are printed (their spread is the run-to-run noise).  Its output belongs i
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 import torch.nn.functional as Fn
 from red_gym_amd import qhead
+from timing import report
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 SIZES = [int(a) for a in sys.argv[2:]] or [64, 4096, 65536]
 F, A, H = 32 * 28 * 28, 16, 512
 GAMMA, ALPHA = 0.99, 0.2
-
-
-def window(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(fns, n, warm=3, rounds=3):
-    for fn in fns.values():
-        for _ in range(warm):
-            fn()
-    vals = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():          # alternating
-            vals[k].append(window(fn, n))
-    for k, v in vals.items():
-        print('%-72s median %10.1f us  (%s)  spread %.1f %%' % (k, float(np.median(v)), ' '.join('%.1f' % x for x in v),
-              100.0 * (max(v) - min(v)) / float(np.median(v))), flush=True)
-    return {k: float(np.median(v)) for k, v in vals.items()}
 
 
 torch.manual_seed(0)
@@ -112,10 +88,10 @@ for n in SIZES:
     launches = N if n <= 4096 else max(3, N // 40)
     slow = max(3, launches // 10 if n > 64 else launches // 2)
     t = report({'the tail alone, forward: f110_qhead_forward (one launch)': tail_mine,
-                'the tail alone, forward: torch launches behind the GEMM': tail_torch}, launches)
+                'the tail alone, forward: torch launches behind the GEMM': tail_torch}, launches, 3, 3)
     t.update(report({'cat([features, action]) of both critics (the sequence only)': cat_torch,
                      'feature GEMM: torch.mm on the view W[:, :F], both critics': gemm_view,
-                     'feature GEMM: F.linear on the concatenated input, both critics': gemm_cat}, slow))
+                     'feature GEMM: F.linear on the concatenated input, both critics': gemm_cat}, slow, 3, 3))
 
     def fb_mine():
         for p in params:
@@ -129,7 +105,7 @@ for n in SIZES:
         qs, qmin = torch_sequence()
         (Fn.mse_loss(qs[0], tv) + Fn.mse_loss(qs[1], tv) - qmin.mean()).backward()
 
-    t.update(report({'forward + backward, GEMMs included: twin_q': fb_mine, 'forward + backward, GEMMs included: torch sequence': fb_torch}, slow))
+    t.update(report({'forward + backward, GEMMs included: twin_q': fb_mine, 'forward + backward, GEMMs included: torch sequence': fb_torch}, slow, 3, 3))
     # the backward kernels on their own: the same tail behind a 16-wide feature part, where both sides' GEMMs and the cat are negligible
     small = torch.randn((n, 16), device='cuda').relu_()
 
@@ -147,7 +123,7 @@ for n in SIZES:
         (Fn.mse_loss(qs[0], tv) + Fn.mse_loss(qs[1], tv) - torch.min(qs[0], qs[1]).mean()).backward()
 
     t.update(report({'forward + backward at F = 16 (the tail and its backward alone): twin_q': fb_mine_small,
-                     'forward + backward at F = 16: torch sequence': fb_torch_small}, launches))
+                     'forward + backward at F = 16: torch sequence': fb_torch_small}, launches, 3, 3))
     fb_mine()
     g_mine = [l.weight.grad.clone() for l in fc1s]
     fb_torch()
@@ -158,7 +134,7 @@ for n in SIZES:
     if n == max(SIZES):
         both = torch.stack(pres)
         out = torch.empty_like(both)
-        report({'device copy of pre (%.0f MB read + as much written)' % (both.numel() * 4 / 1e6): lambda: out.copy_(both)}, launches)
+        report({'device copy of pre (%.0f MB read + as much written)' % (both.numel() * 4 / 1e6): lambda: out.copy_(both)}, launches, 3, 3)
     keys = list(t)
     print('    kernel / torch: the tail alone %.2f; forward + backward with GEMMs %.2f; forward + backward at F = 16 %.2f' % (
         t[keys[0]] / t[keys[1]], t[keys[5]] / t[keys[6]], t[keys[7]] / t[keys[8]]), flush=True)

@@ -9,38 +9,15 @@ are printed.  Results: profiles/r09_replay.txt."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 from red_gym_amd import F110VecEnv, workload
+from timing import report
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 SIZES = [int(a) for a in sys.argv[2:]] or [65536, 4096]
 T = 3            # step slots: the raw baseline ring costs (T + 1) * B * 64 KiB (17 GB at 65 536 envs)
 ROWS = COLS = 256
-
-
-def window(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(name, fns, n=N, warm=10, rounds=5):
-    for fn in fns.values():
-        for _ in range(warm):
-            fn()
-    vals = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():          # alternating
-            vals[k].append(window(fn, n))
-    for k, v in vals.items():
-        print('%-66s median %9.1f us  (%s)' % (name + k, float(np.median(v)), ' '.join('%.1f' % x for x in v)), flush=True)
-    return {k: float(np.median(v)) for k, v in vals.items()}
 
 
 for B in SIZES:
@@ -69,9 +46,9 @@ for B in SIZES:
         state['k'] += 1
 
     print('---- %d envs x 1, %d x %d, T = %d, %d launches per window' % (B, ROWS, COLS, T, N))
-    a = report('(a) ', {'push: pack kernel + counter (+ clock add)': push, 'torch: copy_ of the raw bitmap into the ring (+ clock add)': torch_push,
-                        'copy_ of 36 KiB per env (reads + writes 72 KiB per env)': lambda: half_b.copy_(half_a),
-                        'clock add alone': lambda: env.eng.t['current_time'].add_(env.timestep)})
+    a = report({'push: pack kernel + counter (+ clock add)': push, 'torch: copy_ of the raw bitmap into the ring (+ clock add)': torch_push,
+                'copy_ of 36 KiB per env (reads + writes 72 KiB per env)': lambda: half_b.copy_(half_a),
+                'clock add alone': lambda: env.eng.t['current_time'].add_(env.timestep)}, N, 10, 5, name='(a) ')
     moved = B * 72 * 1024
     copy_us = a['copy_ of 36 KiB per env (reads + writes 72 KiB per env)']
     bw = moved / (copy_us * 1e-6) / 1e12
@@ -89,9 +66,9 @@ for B in SIZES:
             if f32:
                 s, ns = s.float().mul_(1.0 / 255.0).unsqueeze(1), ns.float().mul_(1.0 / 255.0).unsqueeze(1)
             return s, ns
-        report('(b) n = %4d ' % n, {'draw + gather, uint8': lambda: rp.sample(n), 'draw + gather, fp32 * scale': lambda: rp.sample(n, dtype=torch.float32, scale=1.0 / 255.0),
-                                    'torch: index_select of both frames, uint8': lambda: torch_gather(False),
-                                    'torch: index_select + .float() * scale': lambda: torch_gather(True)}, n=max(N // 2, 5))
+        report({'draw + gather, uint8': lambda: rp.sample(n), 'draw + gather, fp32 * scale': lambda: rp.sample(n, dtype=torch.float32, scale=1.0 / 255.0),
+                'torch: index_select of both frames, uint8': lambda: torch_gather(False),
+                'torch: index_select + .float() * scale': lambda: torch_gather(True)}, max(N // 2, 5), 10, 5, name='(b) n = %4d ' % n)
     print('    bytes held %.1f MB against %.1f MB raw (%.1f x)' % (rp.bytes_held() / 1e6, rp.bytes_raw() / 1e6, rp.bytes_raw() / rp.bytes_held()), flush=True)
     assert env.eng.device_errors() == 0
     del raw_ring, half_a, half_b, packed_like

@@ -6,10 +6,12 @@ hipEvents around `launches` back-to-back calls after a warm-up, one process; the
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import torch
 from red_gym_amd import F110VecEnv, workload
 from red_gym_amd.lidar import LidarBitmap
+from timing import report
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 100
@@ -23,30 +25,6 @@ for _ in range(150):   # spread the cars along the track
 acts = env.pure_pursuit(wp, TLAD, VGAIN).clone()
 
 
-def window(fn, n=N):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us per call
-
-
-def report(name, fns, warm=20, rounds=5):
-    for fn in fns.values():
-        for _ in range(warm):
-            fn()
-    vals = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():          # alternating
-            vals[k].append(window(fn))
-    for k, v in vals.items():
-        print('%-58s median %9.1f us  (%s)' % (name + k, float(np.median(v)), ' '.join('%.1f' % x for x in v)), flush=True)
-    return {k: float(np.median(v)) for k, v in vals.items()}
-
-
 env.shape_rewards()
 for _ in range(3):
     env.step(acts)
@@ -57,9 +35,9 @@ def update_stepped():
     env.eng.shaper.kernel()
 
 
-a = report('(a) ', {'reward kernel alone (+ clock add)': update_stepped,
-                    'clock add alone': lambda: env.eng.t['current_time'].add_(env.timestep)})
-b = report('(b) ', {'FILL render alone': env.eng.shaper.render})
+a = report({'reward kernel alone (+ clock add)': update_stepped,
+            'clock add alone': lambda: env.eng.t['current_time'].add_(env.timestep)}, N, 20, 5, name='(a) ')
+b = report({'FILL render alone': env.eng.shaper.render}, N, 20, 5, name='(b) ')
 env.shape_rewards(False)
 to_img = LidarBitmap(1080, bg_color='black', draw_mode='FILL')
 imgs = torch.empty((B, 256, 256), dtype=torch.uint8, device=env.device)
@@ -70,11 +48,11 @@ def off_step():
     to_img(obs['scans'][:, 0], out=imgs)
 
 
-off = report('(c) ', {'step + render, shaping off': off_step}, rounds=3)
+off = report({'step + render, shaping off': off_step}, N, 20, 3, name='(c) ')
 env.shape_rewards()
-on = report('(c) ', {'step, shaping on': lambda: env.step(acts)}, rounds=3)
+on = report({'step, shaping on': lambda: env.step(acts)}, N, 20, 3, name='(c) ')
 env.shape_rewards(False)
-off2 = report('(c) ', {'step + render, shaping off (again)': off_step}, rounds=3)
+off2 = report({'step + render, shaping off (again)': off_step}, N, 20, 3, name='(c) ')
 print('%d envs x 1, %d launches per window' % (B, N))
 assert env.eng.device_errors() == 0
 env.close()
