@@ -1,4 +1,4 @@
-"""The recorded reference runs of tests/golden/g14_<case>.npz (make_golden_configs.py), for replay through the oracle
+"""The recorded reference runs of tests/golden/g14_<case>.npz (make_golden.py g14_<case>), for replay through the oracle
 (test_oracle_configs.py) and through the C ABI (test_gpu_configs.py).  A plain module, not a conftest.
 
 load_case(golden, name) -> Case(kwargs, poses, actions, expected) plus what a replay needs around them:

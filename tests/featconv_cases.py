@@ -32,7 +32,7 @@ CASES = [
 ]
 CONV3, CONV2 = CASES[0], CASES[1]
 GAP_CASES = [c for c in CASES if c[4] < c[5]]
-# the recordings of the reference's own Actor: the row fed as raw 0 / 255 floats, the row fed as / 255 (tests/golden/make_golden_trunk.py)
+# the recordings of the reference's own Actor: the row fed as raw 0 / 255 floats, the row fed as / 255 (tests/golden/make_golden.py g22)
 GOLDEN = ('g22_trunk.npz', 'g22_trunk_unit.npz')
 
 

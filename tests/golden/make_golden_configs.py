@@ -1,7 +1,6 @@
 """Golden fixtures of the COMPOSED step path at its off-default configurations, generated in the dev container by
-RUNNING THE REFERENCE's own F110Env (imported through ref_loader.load_env(); never shipped, none of its text copied):
-
-    python tests/golden/make_golden_configs.py [A B ...]
+RUNNING THE REFERENCE's own F110Env (reference.load_env(); never shipped, none of its text copied) through make_golden.py,
+rows g14_A ... g14_H:
 
   g14_<case>.npz   one file per case (arrays and JSON strings only), cases A-H below.  Per case: the constructor kwargs,
                    every operation in order (reset poses, step actions, update_params / update_map calls), and after every
@@ -42,19 +41,13 @@ except inside case H, which is about them.  Every case asserts that what it is m
 No trajectory had to be replaced for a rounding-decided flag (none was met: the oracle agrees on every flag of every case).
 """
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
+import reference
+from reference import PARAMS
 
 NB = 1080
-PARAMS = {'mu': 1.0489, 'C_Sf': 4.718, 'C_Sr': 5.4562, 'lf': 0.15875, 'lr': 0.17145, 'h': 0.074,
-          'm': 3.74, 'I': 0.04712, 's_min': -0.4189, 's_max': 0.4189, 'sv_min': -3.2, 'sv_max': 3.2,
-          'v_switch': 7.319, 'a_max': 9.51, 'v_min': -5.0, 'v_max': 20.0, 'width': 0.31, 'length': 0.58}
 START = [0.7, 0.0, 1.37079632679]   # config_example_map.yaml
 
 
@@ -62,9 +55,7 @@ class RefBackend(object):
     """The reference's F110Env; the only place that reads its internals."""
 
     def __init__(self):
-        import ref_loader
-        self.lm, self.dm, self.cm, self.bc, self.fe = ref_loader.load_env()
-        self.ref = ref_loader.REF_ROOT
+        self.lm, self.dm, self.cm, self.bc, self.fe = reference.load_env()
         self._mods = []
         orig = self.bc.ray_cast
 
@@ -80,11 +71,11 @@ class RefBackend(object):
         rc.scan_simulator = rc.scan_angles = rc.cosines = rc.side_distances = None
 
     def map_arg(self, name):
-        return self.ref + '/examples/example_map' if name == 'example_map' else name
+        return reference.path('examples', 'example_map') if name == 'example_map' else name
 
     def map_yaml(self, name):
-        return (self.ref + '/examples/example_map.yaml' if name == 'example_map'
-                else self.ref + '/gym/f110_gym/envs/maps/' + name + '.yaml')
+        return (reference.path('examples', 'example_map.yaml') if name == 'example_map'
+                else reference.path('gym', 'f110_gym', 'envs', 'maps', name + '.yaml'))
 
     def make(self, kw):
         k = dict(kw)
@@ -193,29 +184,19 @@ class Run(object):
                    opp_mod=np.packbits(np.stack([self.rec[r]['opp_mod'] for r in s]), axis=-1))
         for k in ('state', 'scan_pose', 'collisions', 'collision_idx', 'toggles', 'lap_counts', 'lap_times', 'checkpoint_done'):
             out[k] = self.col(k)
-        path = os.path.join(HERE, 'g14_%s.npz' % name)
-        np.savez_compressed(path, **out)
-        kb = os.path.getsize(path) / 1024
+        kb = reference.save('g14_%s.npz' % name, **out) / 1024
         assert kb < 1000, kb
-        print('  wrote g14_%s.npz %.0f KB: %d records, %d with scans, %d opponent-modified beams; %s'
-              % (name, kb, R, len(s), int(sum(self.rec[r]['opp_mod'].sum() for r in s)), notes), flush=True)
+        print('  %d records, %d with scans, %d opponent-modified beams; %s'
+              % (R, len(s), int(sum(self.rec[r]['opp_mod'].sum() for r in s)), notes), flush=True)
 
 
 class Planner(object):
-    """The reference's own pure-pursuit caller (examples/waypoint_follow.py), as make_golden.py loads it."""
+    """The reference's own pure-pursuit caller (examples/waypoint_follow.py), as g7-g9 load it."""
 
-    def __init__(self, ref):
-        import importlib.util
-        from argparse import Namespace
-        import yaml
-        spec = importlib.util.spec_from_file_location('ref_waypoint_follow', ref + '/examples/waypoint_follow.py')
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        with open(ref + '/examples/config_example_map.yaml') as f:
-            conf = Namespace(**yaml.safe_load(f))
-        conf.wpt_path = ref + '/examples/example_waypoints.csv'
+    def __init__(self):
+        mod, conf = reference.load_planner()
         self.p = mod.PurePursuitPlanner(conf, 0.17145 + 0.15875)
-        self.rl = np.loadtxt(conf.wpt_path, delimiter=';', skiprows=3)
+        self.rl = reference.raceline()
 
     def __call__(self, pose, vgain):
         sp, st = self.p.plan(pose[0], pose[1], pose[2], 0.82461887897713965, vgain)
@@ -436,17 +417,7 @@ def case_H(be, plan):
 CASES = {'A': case_A, 'B': case_B, 'C': case_C, 'D': case_D, 'E': case_E, 'F': case_F, 'G': case_G, 'H': case_H}
 
 
-def main(names, be=None):
-    be = be or RefBackend()
-    plan = Planner(be.ref)
-    os.chdir(be.ref + '/examples')
-    for nm in names or sorted(CASES):
-        t = time.time()
-        print('== case', nm, flush=True)
-        be.clear_statics()
-        CASES[nm](be, plan)
-        print('   %.1fs' % (time.time() - t), flush=True)
-
-
-if __name__ == '__main__':
-    main(sys.argv[1:])
+def record(case):
+    be = RefBackend()
+    be.clear_statics()
+    CASES[case](be, Planner())

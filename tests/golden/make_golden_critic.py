@@ -9,38 +9,19 @@ fc1_rel_err = max |z_ref - z_64| / sum |w||x|: the reference's own fc1 output ag
 
 Groups (qhead_cases.GROUPS): images fed as 0 / 1 with critic2_target.fc2.bias shifted so that each side of the min wins half of the
 rows; images as 0 / 255 (what update() feeds, :536) with such a shift; and 0 / 255 with the default initialisation.
-
-    python tests/golden/make_golden_critic.py /path/to/reference
+Run through make_golden.py.
 """
-import os
-import sys
-
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
-
-import make_golden_shaping as mgs  # noqa: E402
-import qhead_cases as qc  # noqa: E402
+import reference
+import qhead_cases as qc
+from reference import StubBuffer
 
 # per group: the value of a set pixel, whether critic2_target.fc2.bias is shifted to balance the min
 MODS = ((1.0, True), (255.0, True), (255.0, False))
 CRITICS = ('critic1_target', 'critic2_target', 'critic1', 'critic2')
 F, A, H = 32 * 28 * 28, 16, 512
-
-
-class StubBuffer:
-    def __init__(self, arrays):
-        self.arrays = arrays
-
-    def __len__(self):
-        return len(self.arrays[0])
-
-    def sample(self, batch_size):
-        assert batch_size == len(self)
-        return self.arrays
 
 
 def round_up_fp16(x):
@@ -88,10 +69,8 @@ def run_update(sal, agent, arrays):
     return seen
 
 
-def main():
-    if len(sys.argv) > 1:
-        mgs.REF_SAL = os.path.join(sys.argv[1], 'src', 'SAL.py')
-    sal = mgs.load_reference_sal()
+def g21_critic():
+    sal = reference.load_sal()
     torch.manual_seed(21)
     torch.set_num_threads(1)
     agent = sal.SACAgent(torch.device('cpu'), action_dim=A)
@@ -176,11 +155,4 @@ def main():
     assert 0.20 <= active_share <= 0.80 and all(0.20 <= m.mean() <= 0.80 for m in active), active_share
     assert near_share <= 0.01, near_share
     assert all(v.dtype in (np.float32, np.float64, np.float16, np.uint8) for k, v in fix.items() if k != 'keys')
-    path = os.path.join(HERE, 'g21_critic.npz')
-    np.savez_compressed(path, **fix)
-    print('wrote', path, os.path.getsize(path), 'bytes')
-    assert os.path.getsize(path) <= 1000000
-
-
-if __name__ == '__main__':
-    main()
+    assert reference.save('g21_critic.npz', **fix) <= 1000000

@@ -6,46 +6,27 @@ a seeded fp32 cotangent on relu(.), fc1's grad_input [2, 25088], bias.grad, bias
 of 128 columns: the 51 MB weight itself is not committed -- tests/test_dense_cpu.py rebuilds it from the seed, by constructing the
 Actor's layers in their order, and checks conv2, conv3 and these columns before it uses it.  The fixture holds data only.
 The generator asserts, per recorded array v, |v - fp64| <= gamma(T) * mag: fp64 and mag = sum |terms| from dense_cases' fp64 sums
-on the recorded inputs, T the number of terms of the sum, bias included.
-
-    python tests/golden/make_golden_dense.py /path/to/reference
+on the recorded inputs, T the number of terms of the sum, bias included.  Run through make_golden.py.
 """
-import os
-import sys
-
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
-
-import bitconv_cases as bc  # noqa: E402
-import dense_cases as dc  # noqa: E402
-import featconv_cases as fc  # noqa: E402
-import make_golden_shaping as mgs  # noqa: E402
+import reference
+import dense_cases as dc
+import featconv_cases as fc
+from reference import within
 
 LIMIT = 1 << 20
 SEED = 22
 COLS = np.arange(128) * 197         # 0 .. 25019
 
 
-def within(name, v, ref, mag, terms):
-    err = np.abs(np.asarray(v, np.float64) - ref)
-    bound = dc.gamma(terms) * mag
-    worst = float((err / np.maximum(bound, 1e-300)).max())
-    print('%-12s T = %6d: worst error / bound %.6f, worst error %.3f u * mag' % (name, terms, worst, float((err / np.maximum(bc.U * mag, 1e-300)).max())))
-    assert (err <= bound).all(), name
-
-
-def main():
-    if len(sys.argv) > 1:
-        mgs.REF_SAL = os.path.join(sys.argv[1], 'src', 'SAL.py')
-    sal = mgs.load_reference_sal()
+def g23_dense():
+    sal = reference.load_sal()
     torch.set_num_threads(1)
     torch.manual_seed(SEED)
     actor = sal.Actor(action_dim=16)
-    rows = [np.load(os.path.join(HERE, name)) for name in fc.GOLDEN]
+    rows = [np.load(reference.fixture(name)) for name in fc.GOLDEN]
     for g in rows:
         assert np.array_equal(g['conv2_weight'], actor.conv2.weight.detach().numpy()) and np.array_equal(g['conv3_weight'], actor.conv3.weight.detach().numpy())
     feat = np.stack([g['conv3_out'].reshape(-1) for g in rows]).astype(np.float32)
@@ -69,11 +50,4 @@ def main():
     within('weight_grad', out['weight_grad_cols'], ref, mag, n)
     ref, mag = dc.grad_bias_fp64(g)
     within('bias_grad', out['bias_grad'], ref, mag, n)
-    path = os.path.join(HERE, 'g23_dense.npz')
-    np.savez_compressed(path, **out)
-    print('wrote', path, os.path.getsize(path), 'bytes')
-    assert os.path.getsize(path) <= LIMIT
-
-
-if __name__ == '__main__':
-    main()
+    assert reference.save('g23_dense.npz', **out) <= LIMIT

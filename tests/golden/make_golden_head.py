@@ -3,30 +3,20 @@ that reach the head, the draws eps of rsample, and what Actor.forward and Actor.
 the head through its branches (policyhead_cases.GROUPS): the default initialisation, fc_mean.weight x 40, fc_log_std.weight x 400
 (high clamp and saturation), fc_log_std.bias + 1.9 (saturation), - 19.9 and - 25 (low clamp).  The fixture holds data only: the
 default head's weights, the per-group fp32 scalars applied to them, inputs, recorded outputs and the Actor's state-dict keys.
-
-    python tests/golden/make_golden_head.py /path/to/reference
+Run through make_golden.py, whose g20 row says which of these arrays follow the host's CPU kernels.
 """
-import os
-import sys
-
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
-
-import make_golden_shaping as mgs  # noqa: E402
-import policyhead_cases as ph  # noqa: E402
+import reference
+import policyhead_cases as ph
 
 # per group: fc_mean.weight *=, fc_log_std.weight *=, fc_log_std.bias +=
 MODS = ((1.0, 1.0, 0.0), (40.0, 1.0, 0.0), (1.0, 400.0, 0.0), (1.0, 1.0, 1.9), (1.0, 1.0, -19.9), (1.0, 1.0, -25.0))
 
 
-def main():
-    if len(sys.argv) > 1:
-        mgs.REF_SAL = os.path.join(sys.argv[1], 'src', 'SAL.py')
-    sal = mgs.load_reference_sal()
+def g20_head():
+    sal = reference.load_sal()
     torch.manual_seed(20)
     torch.set_num_threads(1)
     actor = sal.Actor(action_dim=16)
@@ -75,10 +65,4 @@ def main():
                log_std_scale=np.array([m[1] for m in MODS], np.float32), log_std_shift=np.array([m[2] for m in MODS], np.float32),
                keys=np.array(list(base.keys())))
     assert all(v.dtype == np.float32 for k, v in out.items() if k not in ('seed', 'keys'))
-    path = os.path.join(HERE, 'g20_head.npz')
-    np.savez_compressed(path, **out)
-    print('wrote', path, os.path.getsize(path), 'bytes')
-
-
-if __name__ == '__main__':
-    main()
+    reference.save('g20_head.npz', **out)

@@ -6,35 +6,28 @@ reused with the config's velocity, timestep, horizon and weights) and MPC_conver
 enumerator's optimum of each case.  Every option is one the reference takes as an argument or an attribute: no record comes from
 the NumPy checker.  Per config: path_cases.designed_raw / poses / vels on the config's own seeds, G19_CASES cases.
 
-Dev-container only, like make_golden_paths.py (same loader of src/SAL.py, same BLAS guard).  The fixture holds inputs and
+Run through make_golden.py, like g17 (same loader of src/SAL.py, same BLAS guard).  The fixture holds inputs and
 recorded results only; keys are '<config>/<record>'.
 
 Asserted here, on the reference's values: every case stays at least 1e-6 from the wrap of the clamp, the wrap of the converter
 and the speed > 1e-3 switch of the reference states (the third discontinuity of g17, dist < DIST_THRESHOLD, is not recorded
 here); in the first config every reference state is at least 1e-6 from a knot of the spline, and every spline piece 0..6 and
 the end clamp occur in at least 5 % of the (case, k) pairs.
-
-    python tests/golden/make_golden_path_configs.py
 """
 import os
-import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import make_golden_paths as mgp  # noqa: E402  (through make_golden_shaping: the BLAS kernel is set before NumPy loads)
-from make_golden_paths import mgs  # noqa: E402
+import numpy as np
 
-import numpy as np  # noqa: E402
-
-import path_cases as pc  # noqa: E402
+import reference
+import make_golden_paths as mgp
+import path_cases as pc
 
 MARGIN = 1e-6
 
 
-def main():
-    if not mgs.dot_is_unfused():
-        raise SystemExit('np.dot fuses its multiply-add on this host (BLAS kernel): the fixture would record the host, not the reference')
-    sal = mgs.load_reference_sal()
+def g19_path_configs():
+    reference.require_unfused_dot()
+    sal = reference.load_sal()
     sal.cp.Variable = mgp._raise
     env = sal.SACF110Env.__new__(sal.SACF110Env)
     n = pc.G19_CASES
@@ -86,12 +79,6 @@ def main():
             assert seg.mean() >= 0.9 and not steer.any()
         for key, val in (('increments', inc), ('paths', paths), ('dists', dists), ('ref_traj', ref), ('conv_in', conv_in), ('conv_out', conv_out)):
             store['%s/%s' % (name, key)] = val
-    out = os.path.join(HERE, 'g19_path_configs.npz')
-    np.savez_compressed(out, **store)
-    size = os.path.getsize(out)
-    print('wrote %s: %d configs of %d cases, %d bytes' % (out, len(pc.CONFIGS), n, size))
-    assert size < os.path.getsize(os.path.join(HERE, 'g17_paths.npz'))
-
-
-if __name__ == '__main__':
-    main()
+    size = reference.save('g19_path_configs.npz', **store)
+    print('  %d configs of %d cases' % (len(pc.CONFIGS), n))
+    assert size < os.path.getsize(reference.fixture('g17_paths.npz'))

@@ -2,8 +2,8 @@
 SACF110Env._calculate_global_path (:157-181), _update_path_index (:252-259), MPC_converter (:741-764) and the part of
 MPC_controller (:615-687) in front of its first cvxpy call: `dists` and `ref_traj` -- on the cases of tests/path_cases.py.
 
-Dev-container only, like make_golden_shaping.py, whose loader of src/SAL.py (stand-in modules for cv2, cvxpy, gym, pyglet)
-and BLAS guard (np.linalg.norm is in `dists` and in _update_path_index) are reused.  cvxpy and OSQP are absent here, so the QP's
+Run through make_golden.py, with g16's loader of src/SAL.py (reference.load_sal(): stand-in modules for cv2, cvxpy, gym,
+pyglet) and BLAS guard (np.linalg.norm is in `dists` and in _update_path_index).  cvxpy and OSQP are absent here, so the QP's
 solution cannot be recorded: the stand-in cvxpy's Variable raises a private exception at MPC_controller's first use of it, and
 `ref_traj` and `dists` are read from MPC_controller's frame in the traceback -- everything up to that line is NumPy and scipy.
 The accelerations MPC_converter is recorded on are (a) the optimum the enumerator of tests/path_cases.py finds for the case and
@@ -12,19 +12,14 @@ The accelerations MPC_converter is recorded on are (a) the optimum the enumerato
 The reference has three discontinuities -- the +-pi wrap of the clamp, the wrap of the converter and dist < DIST_THRESHOLD; the
 generator asserts, on the reference's values, that every case stays at least 1e-6 away from each, so that no test needs to
 leave a case out.
-
-    python tests/golden/make_golden_paths.py
 """
 import os
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import make_golden_shaping as mgs  # noqa: E402  (sets the BLAS kernel before NumPy loads, extends sys.path)
+import numpy as np
 
-import numpy as np  # noqa: E402
-
-import path_cases as pc  # noqa: E402
+import reference
+import path_cases as pc
 
 N = 780
 MARGIN = 1e-6
@@ -64,10 +59,9 @@ def away(values, period):
     return np.minimum(r, period - r)
 
 
-def main():
-    if not mgs.dot_is_unfused():
-        raise SystemExit('np.dot fuses its multiply-add on this host (BLAS kernel): the fixture would record the host, not the reference')
-    sal = mgs.load_reference_sal()
+def g17_paths():
+    reference.require_unfused_dot()
+    sal = reference.load_sal()
     sal.cp.Variable = _raise
     env = sal.SACF110Env.__new__(sal.SACF110Env)
     env.car_length, env.vector_length = 0.3, 0.5
@@ -119,13 +113,7 @@ def main():
         print('%-40s %6d (%.1f %%)' % (name, mk.sum(), 100.0 * mk.mean()))
         assert mk.mean() >= 0.05, name
     assert ((index_out == index) | (index_out == index + 1)).all()
-    out = os.path.join(HERE, 'g17_paths.npz')
-    np.savez_compressed(out, raw=raw, poses=poses, vels=vels, increments=inc, paths=paths, dists=dists, ref_traj=ref, index=index,
-                        xy=xy, index_out=index_out, conv_in=conv_in, conv_out=conv_out)
-    size = os.path.getsize(out)
-    print('wrote %s: %d cases, %d converter records, %d bytes' % (out, N, conv_in.shape[0], size))
-    assert size < os.path.getsize(os.path.join(HERE, 'g6_raycast.npz')) // 2
-
-
-if __name__ == '__main__':
-    main()
+    size = reference.save('g17_paths.npz', raw=raw, poses=poses, vels=vels, increments=inc, paths=paths, dists=dists, ref_traj=ref,
+                          index=index, xy=xy, index_out=index_out, conv_in=conv_in, conv_out=conv_out)
+    print('  %d cases, %d converter records' % (N, conv_in.shape[0]))
+    assert size < os.path.getsize(reference.fixture('g6_raycast.npz')) // 2

@@ -2,9 +2,9 @@
 detect_collison (:766-790), distance_from_row_center / centerline_reward (:879-935) and _world_to_pixel (:139-142) -- on the
 images and poses of tests/shaping_cases.py.
 
-Dev-container only, like make_golden_progress.py.  src/SAL.py is loaded by file path with empty stand-in modules for cv2,
-cvxpy, gym (with an Env class and a spaces.Box) and pyglet / pyglet.gl (GL_LINES); the functions recorded here are plain
-Python and NumPy and call none of them.  They run on a bare SACF110Env.__new__ instance whose map_origin, map_scale,
+Run through make_golden.py.  src/SAL.py is loaded by file path (reference.load_sal()) with empty stand-in modules for cv2,
+cvxpy, gym (with an Env class) and pyglet / pyglet.gl (GL_LINES); the functions recorded here are plain Python and NumPy
+and call none of them.  They run on a bare SACF110Env.__new__ instance whose map_origin, map_scale,
 last_obs and prev_position are set by hand.  The fixture holds inputs and recorded results only.
 
 Images: (a) the FILL image (black background, SAL's call at :76-77) of g8's and g10's scans.  cv2 is absent here, so the
@@ -12,61 +12,27 @@ reference's own drawer cannot run: they are drawn by oracle.bitmap, the project'
 image is an INPUT, any 0 / 255 picture serves; (b) hand-built images for the edges of the run search; (c) the sizes 75 x 100
 and 40 x 300, whose widths are not multiples of 64.  0 / 255 images are stored with np.packbits.
 
-np.linalg.norm of the progress term goes through the BLAS's dot, so g15's guard is kept: the BLAS kernel set is pinned
-before NumPy loads, and the generator refuses to run if np.dot still fuses its multiply-add.
-
-    python tests/golden/make_golden_shaping.py
+np.linalg.norm of the progress term goes through the BLAS's dot, so g15's guard is kept: the row runs under
+reference.BLAS_PIN, and the generator refuses to run if np.dot still fuses its multiply-add.
 """
-import importlib.util
 import os
-import sys
-import types
 
-os.environ.setdefault('OPENBLAS_CORETYPE', 'Haswell')   # must precede the first import of numpy
+import numpy as np
 
-import numpy as np  # noqa: E402
+import reference
+import shaping_cases as sc
+from oracle import bitmap as ob
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
-
-import shaping_cases as sc  # noqa: E402
-from oracle import bitmap as ob  # noqa: E402
-
-REF_SAL = '/root/reference/src/SAL.py'
 SIZES = {'a': (256, 256), 'b': (75, 100), 'c': (40, 300)}
 POSES_PER_IMAGE = {'a': 36, 'b': 36, 'c': 48}   # per drawn image
 POSES_PER_HAND_IMAGE = 144
 
 
-def load_reference_sal():
-    for name in ('cv2', 'cvxpy', 'gym', 'pyglet', 'pyglet.gl'):
-        if name not in sys.modules:
-            sys.modules[name] = types.ModuleType(name)
-    gym = sys.modules['gym']
-    if not hasattr(gym, 'Env'):
-        gym.Env = type('Env', (object,), {})
-    sys.modules['pyglet'].gl = sys.modules['pyglet.gl']
-    sys.modules['pyglet.gl'].GL_LINES = 1
-    spec = importlib.util.spec_from_file_location('ref_sal', REF_SAL)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def dot_is_unfused():
-    rng = np.random.default_rng(0)
-    a = rng.uniform(-3, 3, (4096, 2))
-    return all(np.dot(a[k], a[k]) == a[k, 0] * a[k, 0] + a[k, 1] * a[k, 1] for k in range(4096))
-
-
-def main():
-    if not dot_is_unfused():
-        raise SystemExit('np.dot fuses its multiply-add on this host (BLAS kernel): the fixture would record the host, not the reference')
-    sal = load_reference_sal()
-    g8 = np.load(os.path.join(HERE, 'g8_env.npz'))
-    g10 = np.load(os.path.join(HERE, 'g10_bitmap_calls.npz'))
+def g16_shaping():
+    reference.require_unfused_dot()
+    sal = reference.load_sal()
+    g8 = np.load(reference.fixture('g8_env.npz'))
+    g10 = np.load(reference.fixture('g10_bitmap_calls.npz'))
     scans = {'a': np.concatenate([g8['scans'], g10['scans']]), 'b': g8['scans'], 'c': g8['scans'][::3]}
     env = sal.SACF110Env.__new__(sal.SACF110Env)
     env.map_origin, env.map_scale = (128, 128), 10.0
@@ -116,12 +82,6 @@ def main():
     for name, m in cover.items():
         print('%-34s %5d cases (%.1f %%)' % (name, m.sum(), 100.0 * m.mean()))
         assert m.mean() >= 0.05, name
-    out = os.path.join(HERE, 'g16_shaping.npz')
-    np.savez_compressed(out, n_real=np.int64(n_real), **store, **c)
-    size = os.path.getsize(out)
-    print('wrote %s: %d cases (%d real pairs) on %d images, %d bytes' % (out, n, n_real, sum(store['img_' + g].shape[0] for g in sc.GROUPS), size))
-    assert size < os.path.getsize(os.path.join(HERE, 'g6_raycast.npz'))
-
-
-if __name__ == '__main__':
-    main()
+    size = reference.save('g16_shaping.npz', n_real=np.int64(n_real), **store, **c)
+    print('  %d cases (%d real pairs) on %d images' % (n, n_real, sum(store['img_' + g].shape[0] for g in sc.GROUPS)))
+    assert size < os.path.getsize(reference.fixture('g6_raycast.npz'))

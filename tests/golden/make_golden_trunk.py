@@ -10,33 +10,17 @@ file with both rows is 1.3 MB and does not compress further: the gradients are d
 stored twice: conv3's grad_out is `cotangent` reshaped to [1, 32, 28, 28], conv2's grad_out is `conv3_grad_input`.
 The generator asserts, per recorded array v, |v - fp64| <= gamma(T) * mag: fp64 and mag = sum |terms| from featconv_cases' fp64
 sums on the recorded inputs, T the number of terms of the sum, bias included.  torch's default CPU convolution (oneDNN) keeps that
-bound here, so it stays enabled.
-
-    python tests/golden/make_golden_trunk.py /path/to/reference
+bound here, so it stays enabled.  Run through make_golden.py.
 """
-import os
-import sys
-
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
-
-import featconv_cases as fc  # noqa: E402
-import make_golden_shaping as mgs  # noqa: E402
+import reference
+import featconv_cases as fc
+from reference import within
 
 LIMIT = 1 << 20
 FILES = (('g22_trunk.npz', 255.0), ('g22_trunk_unit.npz', 1.0))     # per file: the one recorded row and what a set pixel is worth in it
-
-
-def within(name, v, ref, mag, terms):
-    err = np.abs(np.asarray(v, np.float64) - ref)
-    bound = fc.gamma(terms) * mag
-    worst = float((err / np.maximum(bound, 1e-300)).max())
-    print('%-18s T = %6d: worst error / bound %.4f' % (name, terms, worst))
-    assert (err <= bound).all(), name
 
 
 def record(sal, name, on, blocks):
@@ -86,22 +70,14 @@ def record(sal, name, on, blocks):
         pixels = R * o.shape[2] * o.shape[3]
         within(layer + '_weight_grad', out[layer + '_weight_grad'], gw, mw, pixels)
         within(layer + '_bias_grad', out[layer + '_bias_grad'], gb, mb, pixels)
-    path = os.path.join(HERE, name)
-    np.savez_compressed(path, **out)
-    print('wrote', path, os.path.getsize(path), 'bytes')
-    assert os.path.getsize(path) <= LIMIT
+    assert reference.save(name, **out) <= LIMIT
 
 
-def main():
-    if len(sys.argv) > 1:
-        mgs.REF_SAL = os.path.join(sys.argv[1], 'src', 'SAL.py')
-    sal = mgs.load_reference_sal()
+def g22_trunk():
+    sal = reference.load_sal()
     torch.set_num_threads(1)
     rng = np.random.default_rng(22)
     for name, on in FILES:
         blocks = rng.random((1, 1, 32, 32)) < rng.uniform(0.3, 0.7, (1, 1, 1, 1))
         record(sal, name, on, blocks)
 
-
-if __name__ == '__main__':
-    main()

@@ -7,22 +7,14 @@ pre-hook every parameter's .grad as it stands at its optimizer's step, and every
 The fixture holds the batch (images as bits), both draws, those quantities, and per parameter tensor the fp64 sum and sum of squares
 of its initial value (the check that a rebuild from the seed worked), its gradient's L2 norm, and 256 entries (all of a smaller tensor)
 of the gradient and of the parameter after the update at positions drawn from a seed stored in the file.  Data only.
-
-    python tests/golden/make_golden_update.py /path/to/reference
+Run through make_golden.py.
 """
-import os
-import sys
-
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
-
-import make_golden_shaping as mgs  # noqa: E402
-import update_cases as uc  # noqa: E402
-from make_golden_critic import StubBuffer  # noqa: E402
+import reference
+import update_cases as uc
+from reference import StubBuffer
 
 SEED, DRAW_SEED, POSITION_SEED, ROWS, A, ENTRIES = 24, 2400, 240, 8, 16, 256
 
@@ -77,10 +69,8 @@ def run_update(sal, agent, arrays):
     return seen
 
 
-def main():
-    if len(sys.argv) > 1:
-        mgs.REF_SAL = os.path.join(sys.argv[1], 'src', 'SAL.py')
-    sal = mgs.load_reference_sal()
+def g24_update():
+    sal = reference.load_sal()
     torch.set_num_threads(1)
     torch.manual_seed(SEED)
     agent = sal.SACAgent(torch.device('cpu'), action_dim=A)
@@ -119,11 +109,4 @@ def main():
                 assert fix['%s/%s/grad_norm' % (n, k)] > 0
     assert all(v.dtype in (np.float32, np.float64, np.uint8, np.int64) for v in fix.values())
     print('losses', fix['losses'], 'tv', fix['tv'], 'done', fix['d'])
-    path = os.path.join(HERE, 'g24_update.npz')
-    np.savez_compressed(path, **fix)
-    print('wrote', path, os.path.getsize(path), 'bytes')
-    assert os.path.getsize(path) <= 1000000
-
-
-if __name__ == '__main__':
-    main()
+    assert reference.save('g24_update.npz', **fix) <= 1000000

@@ -1,5 +1,5 @@
 """NumPy restatement of the action side of the reference's RL consumer (src/SAL.py, SACF110Env.step) -- the checker of the path
-follower's tests -- and the designed cases of g17 (tests/golden/make_golden_paths.py records the reference's own results on them).
+follower's tests -- and the designed cases of g17 (tests/golden/make_golden.py g17 records the reference's own results on them).
 
 decode (:585-608), global path (:157-181), chord lengths and the not-a-knot cubic spline of MPC_controller (:615-687; scipy's
 system written out, solved with np.linalg.solve), the first QP (:693-722) as two box QPs solved by ENUMERATION of the 3^H
@@ -370,7 +370,7 @@ def designed_vels(n, seed):
 
 
 # ---------------------------------------------------------------- off-default configurations (g19) and the kernel's case analysis
-# tests/golden/make_golden_path_configs.py records the reference on designed_raw / poses / vels(G19_CASES, seed .. seed + 2) per entry.
+# tests/golden/make_golden.py g19 records the reference on designed_raw / poses / vels(G19_CASES, seed .. seed + 2) per entry.
 G19_CASES = 96
 CONFIGS = {
     'late_pieces': dict(seed=1900, cfg=dict(desired_velocity=4.7, timestep=0.1, horizon=8)),                      # sk = 0.47 k: pieces 0 0 1 2 3 4 5 6, the clamp at k = 8

@@ -1,4 +1,4 @@
-"""Shared by the tests of the opponent ray cast at its edge geometries (g13, tests/golden/make_golden_r3.py):
+"""Shared by the tests of the opponent ray cast at its edge geometries (g13, tests/golden/make_golden.py g13):
 the reference's scans rebuilt from the fixture's modified-beam triplets, and the one place where the reference's
 answer is not a function of its inputs alone.
 

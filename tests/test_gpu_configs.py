@@ -1,5 +1,5 @@
 """The composed step path on the GPU (f110_reset / f110_step through F110VecEnv and the single-env F110Env facade) against
-runs of the REFERENCE at off-default configurations: g14, tests/golden/make_golden_configs.py, cases A-H.
+runs of the REFERENCE at off-default configurations: g14, tests/golden/make_golden.py g14_A ... g14_H.
 
 Each case is ONE env of a batch of five and never env 0; the other envs start from jittered poses and drive seeded random
 actions, so a result leaking from a neighbour shows.  Every record, agent and beam is compared (tests/config_cases.py:

@@ -1,5 +1,5 @@
 """Both GPU implementations of the opponent ray cast at the reference's edge geometries (g13,
-tests/golden/make_golden_r3.py; the oracle is pinned to the same fixture in tests/test_oracle_raycast_edges.py):
+tests/golden/make_golden.py g13; the oracle is pinned to the same fixture in tests/test_oracle_raycast_edges.py):
 
   * the function-level path (ray_cast_wave behind f110_ray_cast / Engine.ray_cast) against g13 itself: spans ==,
     modified-beam sets ==, values <= 1e-9;

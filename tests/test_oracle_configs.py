@@ -1,5 +1,5 @@
 """The oracle's composed path (oracle.Env: Simulator.step, F110Env.step / reset / _check_done, update_params, update_map)
-against runs of the REFERENCE at off-default configurations: g14, tests/golden/make_golden_configs.py, cases A-H.
+against runs of the REFERENCE at off-default configurations: g14, tests/golden/make_golden.py g14_A ... g14_H.
 
 Every record, agent and beam is compared (tests/config_cases.py: compare): every boolean, index, counter, toggle and
 `done` ==; lap_times and current_time ==; state <= 1e-12; scans == where no opponent modified the beam and <= 1e-12 where

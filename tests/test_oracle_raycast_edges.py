@@ -1,5 +1,5 @@
 """The oracle's opponent ray cast (oracle/f110_oracle.c: orc_get_blocked_view_indices, orc_ray_cast) against the
-reference at its edge geometries (g13, tests/golden/make_golden_r3.py): beams at exactly 0 rad with yaw 0, the +-pi
+reference at its edge geometries (g13, tests/golden/make_golden.py g13): beams at exactly 0 rad with yaw 0, the +-pi
 wrap, contacts on an edge's line and on the corners, the ego inside the box, silhouette corners, opponents outside a
 narrow fov, in eight (num_beams, fov) configurations.  This is what makes the oracle a valid referee for the GPU's
 two implementations at these edges (tests/test_gpu_raycast_edges.py).

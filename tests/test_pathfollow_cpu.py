@@ -110,7 +110,7 @@ def test_state_machine_on_a_scripted_clock():
 
 # ---------------------------------------------------------------- off the defaults: g19 and the case families of path_cases
 def test_checker_against_every_record_of_g19(golden):
-    """The reference's records at the off-default configurations (tests/golden/make_golden_path_configs.py)."""
+    """The reference's records at the off-default configurations (tests/golden/make_golden.py g19)."""
     g = golden('g19_path_configs.npz')
     assert {k.split('/')[0] for k in g.files} == set(pc.CONFIGS)
     for name, entry in pc.CONFIGS.items():

@@ -30,7 +30,7 @@ def test_checker_equals_reference_nearest_point(golden, example):
     pins the checker on the reference.  The fixture records the reference under arithmetic without contraction: its dot
     product is np.dot, and the generator pins a BLAS kernel set that does not fuse a 2-element dot (a fusing one returns
     fma(r1, s1, r0 * s0), which moves t in the last place on a third of the poses and flips the tie on waypoint 29 -- a
-    property of a host's BLAS, not of the reference; tests/golden/make_golden_progress.py)."""
+    property of a host's BLAS, not of the reference; tests/golden/make_golden.py g15)."""
     P, g = pc.g15_poses(golden), golden('g15_nearest.npz')
     assert P.shape[0] == g['i'].shape[0] == int(g['n_g8']) + g['poses'].shape[0]
     got = [example.nearest(x, y) for x, y in P]

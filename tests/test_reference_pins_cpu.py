@@ -1,5 +1,5 @@
 """Pins of the "next" rows against fixtures generated from the reference's own code
-(tests/golden/make_golden_r2.py, dev container).  What each fixture pins -- and what stays unpinned -- is said
+(tests/golden/make_golden.py g9 ... g12, where the reference is present).  What each fixture pins -- and what stays unpinned -- is said
 in the test; the OpenCV / shapely / matplotlib rasterisation itself is out of reach (not installed)."""
 import json
 import os

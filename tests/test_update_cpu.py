@@ -1,6 +1,6 @@
 """The mirror of tests/update_cases.py is the reference's update, without a device: MirrorAgent at SAL's shape in fp32 on the CPU with
 one thread, rebuilt from the seed, reproduces every quantity the reference's own SACAgent.update left in g24_update.npz (tests/golden/
-make_golden_update.py) with `==` -- the same torch operations in the same order; the phases compose to the whole update bit for bit;
+make_golden.py g24) with `==` -- the same torch operations in the same order; the phases compose to the whole update bit for bit;
 and the ring's "no transition" row (index -1) is a zero image that adds nothing to conv1.weight's gradient.
 
 Measured where the fixture was generated (profiles/r19_update.txt): every forward quantity, the three losses, all 32 gradients' 256

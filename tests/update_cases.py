@@ -260,7 +260,7 @@ def golden_batch(g):
 
 
 def golden_positions(g, net, key, numel):
-    """The flat positions of the entries the fixture keeps of a tensor (tests/golden/make_golden_update.py's draw)."""
+    """The flat positions of the entries the fixture keeps of a tensor (the draw of g24's generator, tests/golden/make_golden.py g24)."""
     entries = int(g['entries'])
     if numel <= entries:
         return np.arange(numel, dtype=np.int64)
