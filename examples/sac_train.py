@@ -1,9 +1,12 @@
 """The training loop of the reference's RL consumer (main(), src/SAL.py:975-1019) for many envs at once, everything on the GPU:
-    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every]
+    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps]
     select_action (the policy on the shaper's bitmap) -> path_actions (SAL's action decode and MPC step, which also hands the raw
     action to the ring) -> step (scan, shaper, the ring's push) -> after update_after steps, every update_every steps, one SACAgent
-    update replayed from a graph: the batch is drawn on the device, the losses stay there.
-The defaults are small, so that it finishes in seconds; the reference's are batch 64, update_after 1000, update_every 50.  The loss
+    update replayed from a graph: the batch is drawn on the device, the losses stay there.  The episodes are kept on the GPU too
+    (track_episodes: max_steps ends an episode the env never ends, as the reference's `for st in range(max_steps)` does): the
+    `Episode ... Reward=...` lines main() prints come from the log of finished episodes, read where the losses are printed.
+The defaults are small, so that it finishes in seconds; the reference's are batch 64, update_after 1000, update_every 50, max_steps
+2000.  The loss
 tensor is read (one synchronisation) only where it is printed.  At the end the actor is saved under the reference's keys, as main()
 saves sac_actor.pth."""
 import os
@@ -12,21 +15,23 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from red_gym_amd import F110VecEnv, SACAgent, workload
+from red_gym_amd.episodes import REASONS
 
 arg = lambda i, default: int(sys.argv[i]) if len(sys.argv) > i else default  # noqa: E731
-B, STEPS, BATCH, UPDATE_AFTER, UPDATE_EVERY = arg(1, 64), arg(2, 48), arg(3, 64), arg(4, 16), arg(5, 4)
+B, STEPS, BATCH, UPDATE_AFTER, UPDATE_EVERY, MAX_STEPS = arg(1, 64), arg(2, 48), arg(3, 64), arg(4, 16), arg(5, 4), arg(6, 12)
 AD = 16
 env = F110VecEnv(B, map=workload.EXAMPLE_MAP, num_agents=1, autoreset=True)
 env.shape_rewards()
 env.follow_paths()
 env.record_replay(capacity=16 * B, action_dim=AD)
+env.track_episodes(MAX_STEPS + torch.arange(B, dtype=torch.int32) % 4)   # staggered: envs spawned together do not end together
 dev, cfg = env.device, env.eng.shaper.cfg
 torch.manual_seed(0)
 agent = SACAgent(action_dim=AD, rows=cfg.rows, cols=cfg.cols, device=dev)
 raw = torch.zeros((B, AD), dtype=torch.float64, device=dev)                    # the policy's action, written in place
 obs, reward, done, info = env.reset(torch.as_tensor(workload.spawn_poses(B, 1), device=dev))
 total = torch.zeros((B,), dtype=torch.float64, device=dev)
-updates = 0
+updates = printed = 0
 for step in range(1, STEPS + 1):
     agent.select_action(info['lidar_bitmap'], out=raw)
     obs, reward, done, info = env.step(env.path_actions(raw))
@@ -38,8 +43,17 @@ for step in range(1, STEPS + 1):
         updates += 1
         if updates % 4 == 1:
             print('step %3d, update %2d: losses (actor, critic 1, critic 2) %s' % (step, updates, ' '.join('%.6f' % v for v in losses.tolist())))
+            count = int(info['episodes_finished'].item())
+            rec = {k: v.tolist() for k, v in env.episodes.finished(last=min(count - printed, 4)).items()}   # (a few of the new ones)
+            for i in range(len(rec['env'])):
+                print('Episode %d Reward=%.2f  (env %d, %d steps, %s)' % (count - len(rec['env']) + i, rec['ret'][i], rec['env'][i], rec['length'][i],
+                                                                        REASONS[rec['reason'][i]]))
+            printed = count
 print('%d steps of %d envs, %d updates of batch %d, captures %d; %d of %d transitions valid; mean reward per step %.4f' % (
     STEPS, B, updates, BATCH, agent.captures, len(env.replay), env.replay.steps * B, float(total.mean()) / STEPS))
+s = env.episodes.summary(last=100)
+print('episodes: %d finished; the last %d: mean return %.3f, mean length %.1f; done %.0f %%, limit %.0f %%, reset %.0f %%'
+      % (s['count'], s['n'], s['mean_return'], s['mean_length'], 100 * s['done'], 100 * s['limit'], 100 * s['reset']))
 path = os.path.join(tempfile.mkdtemp(), 'sac_actor.pth')
 torch.save({k: v.cpu() for k, v in agent.actor_state_dict().items()}, path)
 print('actor saved as %s (%d tensors under the reference\'s keys)' % (path, len(torch.load(path))))

@@ -619,6 +619,73 @@ int f110_replay_locate(f110_handle *h, const int64_t *indices, int32_t n, int64_
 int f110_replay_sample(f110_handle *h, uint64_t seed, uint64_t *counter, int32_t n, int64_t *indices, int64_t *s_frame, int64_t *ns_frame,
                        float *a, double *r, uint8_t *d, uint8_t *ok, void *stream);
 
+/* Episodes: the episode of the reference's training loop (src/SAL.py:986-1015: `obs = env.reset(); ep_reward = 0; for st in
+ * range(max_steps): ...; ep_reward += reward; if done: break; print(f"Episode {ep} Reward={ep_reward:.2f}")`) for every env, on
+ * the device behind the step: the return and the length of the running episode, a step limit per env, and a log of the finished
+ * episodes.  State per env: ep_return (fp64), ep_length, ep_open, t_seen, truncated; limit[env] is the env's step limit (0: none,
+ * statistics only).  The rules, read off the env's clock as the shaper's are (now = current_time[env]):
+ *   (2) now == t_seen[env]: the env was not stepped since its previous update (a masked reset left it alone): nothing of it is
+ *       written -- the update is idempotent.  Else
+ *   (1) now == timestep exactly: the last step was the env's reset (f110_reset, masked or not, or autoreset), the reference's
+ *       env.reset().  If the episode was still open and ep_length > 0 -- a masked reset cut it -- it is closed with reason RESET
+ *       (its record holds the accumulators as they stood; time and laps are those of the reset step).  Then ep_return = 0,
+ *       ep_length = 0, ep_open = 1, truncated = 0: the reset step pays nothing and counts no step.  Else
+ *   (3) ep_open: ep_return = ep_return + reward[env] (a plain fp64 add in step order), ep_length += 1; reward is the shaper's total
+ *       while a shaper is installed and bound, else the constant `timestep`.  If done[env]: closed with reason DONE; else if
+ *       limit[env] > 0 and ep_length >= limit[env]: closed with reason LIMIT, truncated = 1, and, if the handle runs with autoreset,
+ *       pending_reset[env] = 1 -- the flag the step raises on done: the next step respawns the env at its spawn pose and every
+ *       other consumer sees an ordinary reset.  done is never written; with autoreset off only the flag `truncated` is raised and
+ *       the env keeps stepping.  A closed episode has ep_open = 0.  Else
+ *   (4) a step of a closed episode (autoreset off): the accumulators stay frozen, no second record, until the reset.
+ *   In cases (1), (3) and (4) t_seen = now.
+ * Closing appends one record {env, length, return, reason, time = now, laps = lap_counts of the ego} to a ring of L = cfg.log
+ * records kept as separate arrays.  count [1] (int64, on the device) holds the episodes closed so far; record k of the run lives
+ * in slot k % L, and the records of one update appear in ascending env order (a compaction by wave ballots, LDS and per-workgroup
+ * counts: no atomics, the same slots in every run).  If more than L episodes close in one update only the last L in env order are
+ * written, each to its own slot; count advances by all of them, in a one-wave kernel behind the writes, so that a captured update
+ * replays with fresh slots.
+ * f110_episodes_validate: host only.  F110_E_INVALID for limit < 0 and for log outside 1..2^24.
+ * f110_episodes_install: cfg NULL removes the tracker; a refused cfg installs nothing and keeps what was there.  Install, removal and
+ * bind move the launch epoch.  f110_episodes_bind: the caller-owned arrays, dev; all required but `limit` (NULL: cfg.limit for every
+ * env).  Start with ep_open = 1, t_seen = -1 and zeros elsewhere.  block_counts is scratch of ceil(B / 256) int32.
+ * f110_episodes_update: three kernels on `stream`, no allocation, no synchronisation (capturable behind f110_step and the other
+ * consumers' updates: it reads the shaper's total, and the replay push in front of it sees pending_reset as the step left it).
+ * F110_E_INVALID without a tracker, F110_E_UNBOUND before f110_episodes_bind or f110_bind.
+ * f110_episodes_apply: the same kernels on caller-supplied arrays, no handle: n envs (n = 0: nothing is launched), reward [n] or NULL
+ * (= timestep), done [n], current_time [n], laps NULL (0 is logged) or the laps of env e at laps[e * laps_stride], pending_reset [n]
+ * or NULL (autoreset off); bufs as for the bind, with block_counts of ceil(n / 256) int32.  All arrays dev; launches on the calling
+ * thread's current device.  F110_E_INVALID for a NULL cfg, bufs or required array, a refused cfg, n < 0, timestep <= 0. */
+#define F110_EPISODE_DONE 1  /* the env reported done */
+#define F110_EPISODE_LIMIT 2 /* the step limit was reached (truncated) */
+#define F110_EPISODE_RESET 3 /* a reset cut the running episode */
+typedef struct {
+    int32_t limit;              /* the step limit of every env while no limit array is bound (2000: the reference's max_steps); 0: none */
+    int32_t log;                /* L: records the log holds, 1..2^24 */
+} f110_episodes_config;
+typedef struct {
+    double *ep_return;          /* [B] state: the running episode's return */
+    int32_t *ep_length;         /* [B] state: its steps */
+    uint8_t *ep_open;           /* [B] state: 1 while it runs; start at 1 */
+    double *t_seen;             /* [B] state: current_time at the env's previous update; start at -1 */
+    uint8_t *truncated;         /* [B] state: 1 from the step that hit the limit until the env's reset */
+    const int32_t *limit;       /* [B] in: the step limit of every env, or NULL */
+    int32_t *log_env;           /* [L] */
+    int32_t *log_length;        /* [L] */
+    double *log_return;         /* [L] */
+    uint8_t *log_reason;        /* [L] F110_EPISODE_* */
+    double *log_time;           /* [L] */
+    int32_t *log_laps;          /* [L] */
+    int64_t *count;             /* [1] episodes closed; start at 0 */
+    int32_t *block_counts;      /* [ceil(B / 256)] scratch */
+} f110_episodes_buffers;
+int f110_episodes_validate(const f110_episodes_config *cfg);
+int f110_episodes_install(f110_handle *h, const f110_episodes_config *cfg);
+int f110_episodes_bind(f110_handle *h, const f110_episodes_buffers *bufs);
+int f110_episodes_update(f110_handle *h, void *stream);
+int f110_episodes_apply(const f110_episodes_config *cfg, int32_t n, double timestep, const double *reward, const uint8_t *done,
+                        const double *current_time, const int32_t *laps, int64_t laps_stride, uint8_t *pending_reset,
+                        const f110_episodes_buffers *bufs, void *stream);
+
 /* First convolution of the policy from bits: the nn.Conv2d(1, C, kernel, stride) that opens the reference's Actor and Critic
  * (src/SAL.py:397, 429) on an image of two values, forward and backward, stateless (no handle; cfg host; all arrays dev; launches
  * on the calling thread's current device, no allocation, no synchronisation).  `on` is what a set pixel is worth: 1 for

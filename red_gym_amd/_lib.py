@@ -95,6 +95,21 @@ class ReplayBuffers(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in REPLAY_FIELDS]
 
 
+# f110_episodes_config / f110_episodes_buffers: the episode tracker's options and its caller-owned arrays
+class EpisodesConfig(C.Structure):
+    _fields_ = [('limit', C.c_int32), ('log', C.c_int32)]
+
+
+EPISODES_FIELDS = ['ep_return', 'ep_length', 'ep_open', 't_seen', 'truncated', 'limit', 'log_env', 'log_length', 'log_return',
+                   'log_reason', 'log_time', 'log_laps', 'count', 'block_counts']
+F110_EPISODE_DONE, F110_EPISODE_LIMIT, F110_EPISODE_RESET = 1, 2, 3
+F110_EPISODES_BLOCK = 256           # envs per entry of block_counts
+
+
+class EpisodesBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in EPISODES_FIELDS]
+
+
 # f110_bitconv_config: the first convolution computed from bits (stateless)
 class BitconvConfig(C.Structure):
     _fields_ = [('rows', C.c_int32), ('cols', C.c_int32), ('kernel', C.c_int32), ('stride', C.c_int32),
@@ -241,6 +256,11 @@ SYMBOLS = {
     'f110_replay_gather': [_VP, _VP, _I32, _VP, _VP, _I32, _D, _VP, _VP, _VP, _VP, _VP],
     'f110_replay_locate': [_VP, _VP, _I32, _VP, _VP, _VP],
     'f110_replay_sample': [_VP, C.c_uint64, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_episodes_validate': [C.POINTER(EpisodesConfig)],
+    'f110_episodes_install': [_VP, C.POINTER(EpisodesConfig)],
+    'f110_episodes_bind': [_VP, C.POINTER(EpisodesBuffers)],
+    'f110_episodes_update': [_VP, _VP],
+    'f110_episodes_apply': [C.POINTER(EpisodesConfig), _I32, _D, _VP, _VP, _VP, _VP, _I64, _VP, C.POINTER(EpisodesBuffers), _VP],
     'f110_bitconv_validate': [C.POINTER(BitconvConfig)],
     'f110_bitconv_workspace': [C.POINTER(BitconvConfig), _I64],
     'f110_bitconv_forward': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP],

@@ -1,5 +1,6 @@
 """What the step's consumers share.  A consumer is a kernel enqueued behind every step that adds keys to `info`: the progress
-tracker (progress.py), the reward shaper (shaping.py), the path follower (pathfollow.py) and the replay buffer (replay.py).  The
+tracker (progress.py), the reward shaper (shaping.py), the path follower (pathfollow.py), the replay buffer (replay.py) and the
+episode tracker (episodes.py).  The
 Engine owns one object of each; F110VecEnv loops over them."""
 import ctypes as C
 import weakref

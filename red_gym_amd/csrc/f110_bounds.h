@@ -23,7 +23,8 @@ enum { BT_LUT_CODE, BT_CELLS_FAR, BT_LUT_RANK, BT_DT, BT_NOISE_BEAM, BT_CS_TABLE
        BT_PROGRESS,   // an index of the tracker (raceline slot, grid cell, candidate, segment)
        BT_SHAPING,    // a pixel index of the shaper (px, py, car_x, car_y, a neighbour)
        BT_PATHFOLLOW, // an index of the follower (waypoint index, free set, spline piece)
-       BT_REPLAY };   // a slot the replay kernels derive from `count`, a drawn index
+       BT_REPLAY,     // a slot the replay kernels derive from `count`, a drawn index
+       BT_EPISODES }; // a rank or a slot of the episode log
 static_assert(BT_PROGRESS == 15 && BT_REPLAY == 18, "the tags are bits of the device error word (8 + BT_*): the ABI fixes their values");
 #if defined(F110_BOUNDS)
 #define F110_BCHK(ok, table, errp) \

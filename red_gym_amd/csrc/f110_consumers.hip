@@ -5,6 +5,7 @@
 #include "f110_shaping.h"
 #include "f110_pathfollow.h"
 #include "f110_replay.h"
+#include "f110_episodes.h"
 
 // ---------------------------------------------------------------- planner
 // per device: the LDS a workgroup may use (queried once), the dynamic-LDS attribute already granted to
@@ -224,7 +225,7 @@ static int clock_usable(const f110_handle *h, const char *who)
     return h->cfg.timestep > 0.0 ? F110_OK : fail(F110_E_INVALID, "%s: the handle's timestep is %g (an env's reset is read off its clock: it must be positive)", who, h->cfg.timestep);
 }
 
-// The opening of f110_progress_update / f110_shaping_update (`who`): `what` is installed and bound (f110_<family>_install /
+// The opening of a consumer's update (`who`): `what` is installed and bound (f110_<family>_install /
 // _bind), the handle is bound and its device is the caller's current one.
 static int update_ready(const f110_handle *h, const char *who, const char *what, const char *family, bool on, bool bound)
 {
@@ -810,6 +811,102 @@ extern "C" int f110_replay_sample(f110_handle *h, uint64_t seed, uint64_t *count
     hipLaunchKernelGGL(replay_counter_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long *)counter, (unsigned long long)n);
     HIP_TRY(hipGetLastError());
     return F110_OK;
+}
+
+// ---------------------------------------------------------------- episodes
+// What install refuses, on the struct alone (no handle, no device).
+extern "C" int f110_episodes_validate(const f110_episodes_config *cfg)
+{
+    const char *who = "f110_episodes_validate";
+    if (!cfg) return fail(F110_E_INVALID, "%s: null config", who);
+    if (cfg->limit < 0) return fail(F110_E_INVALID, "%s: step limit %d is negative (0: no limit)", who, cfg->limit);
+    if (cfg->log < 1 || cfg->log > (1 << 24)) return fail(F110_E_INVALID, "%s: a log of %d records (1..%d)", who, cfg->log, 1 << 24);
+    return F110_OK;
+}
+
+extern "C" int f110_episodes_install(f110_handle *h, const f110_episodes_config *cfg)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_episodes_install: null handle");
+    f110_handle::Episodes &e = h->episodes;
+    if (!cfg) { // removes the tracker (the arrays are the caller's)
+        if (!e.on) return F110_OK;
+        e.on = false;
+        h->epoch++;
+        return F110_OK;
+    }
+    if (int rc = f110_episodes_validate(cfg)) return rc;
+    if (int rc = clock_usable(h, "f110_episodes_install")) return rc;
+    if (e.on && e.cfg.log != cfg->log) e.bound = false; // the log's arrays have another length: bind again
+    e.cfg = *cfg; // by value in every launch
+    e.on = true;
+    h->epoch++;
+    return F110_OK;
+}
+
+static bool episodes_buffers_complete(const f110_episodes_buffers *b)
+{
+    return b->ep_return && b->ep_length && b->ep_open && b->t_seen && b->truncated && b->log_env && b->log_length && b->log_return &&
+           b->log_reason && b->log_time && b->log_laps && b->count && b->block_counts;
+}
+
+extern "C" int f110_episodes_bind(f110_handle *h, const f110_episodes_buffers *b)
+{
+    if (!h || !b) return fail(F110_E_INVALID, "f110_episodes_bind: null argument");
+    if (!episodes_buffers_complete(b)) return fail(F110_E_INVALID, "f110_episodes_bind: an array is NULL (all but `limit` are required)");
+    if ((uintptr_t)b->count % 8) return fail(F110_E_INVALID, "f110_episodes_bind: count is not 8-byte aligned");
+    h->episodes.bufs = *b;
+    h->episodes.bound = true;
+    h->epoch++;
+    return F110_OK;
+}
+
+static int launch_episodes(EpisodesArgs &a, const f110_episodes_config &c, const f110_episodes_buffers &b, hipStream_t stream)
+{
+    if (a.n == 0) return F110_OK;
+    a.log = c.log; a.limit_all = c.limit;
+    a.ep_return = b.ep_return; a.ep_length = b.ep_length; a.ep_open = b.ep_open; a.t_seen = b.t_seen; a.truncated = b.truncated;
+    a.limit = b.limit; a.log_env = b.log_env; a.log_length = b.log_length; a.log_return = b.log_return; a.log_reason = b.log_reason;
+    a.log_time = b.log_time; a.log_laps = b.log_laps; a.count = (const long long *)b.count; a.block_counts = b.block_counts;
+    const int blocks = (a.n + EPISODES_THREADS - 1) / EPISODES_THREADS;
+    hipLaunchKernelGGL(episodes_count_kernel, dim3(blocks), dim3(EPISODES_THREADS), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(episodes_update_kernel, dim3(blocks), dim3(EPISODES_THREADS), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(episodes_advance_kernel, dim3(1), dim3(64), 0, stream, (long long *)b.count, (const int32_t *)b.block_counts, blocks);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_episodes_update(f110_handle *h, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "f110_episodes_update: null handle");
+    const f110_handle::Episodes &e = h->episodes;
+    if (int rc = update_ready(h, "f110_episodes_update", "episode tracker", "episodes", e.on, e.bound)) return rc;
+    EpisodesArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = h->cfg.num_envs; a.timestep = h->cfg.timestep;
+    a.reward = h->shaping.on && h->shaping.bound ? h->shaping.bufs.total : nullptr; // follows the shaper being switched on and off
+    a.done = (const uint8_t *)h->bufs.done; a.current_time = h->bufs.current_time;
+    a.laps = h->bufs.lap_counts + h->cfg.ego_idx; a.laps_stride = h->cfg.num_agents;
+    a.pending_reset = h->cfg.autoreset ? h->bufs.pending_reset : nullptr;
+    a.dev_err = h->d_err.get();
+    return launch_episodes(a, e.cfg, e.bufs, (hipStream_t)stream);
+}
+
+extern "C" int f110_episodes_apply(const f110_episodes_config *cfg, int32_t n, double timestep, const double *reward, const uint8_t *done,
+                                   const double *current_time, const int32_t *laps, int64_t laps_stride, uint8_t *pending_reset,
+                                   const f110_episodes_buffers *bufs, void *stream)
+{
+    if (!cfg) return fail(F110_E_INVALID, "f110_episodes_apply: null config");
+    if (int rc = f110_episodes_validate(cfg)) return rc;
+    if (!bufs || !done || !current_time || !episodes_buffers_complete(bufs)) return fail(F110_E_INVALID, "f110_episodes_apply: null pointer");
+    if (n < 0 || !(timestep > 0.0) || laps_stride < 0) return fail(F110_E_INVALID, "f110_episodes_apply: bad arguments (n=%d, timestep=%g)", n, timestep);
+    if ((uintptr_t)bufs->count % 8) return fail(F110_E_INVALID, "f110_episodes_apply: count is not 8-byte aligned");
+    EpisodesArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = n; a.timestep = timestep; a.reward = reward; a.done = done; a.current_time = current_time;
+    a.laps = laps; a.laps_stride = laps_stride; a.pending_reset = pending_reset;
+    return launch_episodes(a, *cfg, *bufs, (hipStream_t)stream);
 }
 
 static int replay_pack_args(const char *who, const void *in, const void *out, int64_t n, int32_t rows, int32_t cols)

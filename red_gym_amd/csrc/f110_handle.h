@@ -138,6 +138,12 @@ struct f110_handle {
         int rows = 0, cols = 0;
         f110_replay_buffers bufs;
     } replay;
+    // episode tracker (f110_episodes_install / _bind / _update, f110_consumers.hip): the configuration and the caller's arrays
+    struct Episodes {
+        bool on = false, bound = false;
+        f110_episodes_config cfg;
+        f110_episodes_buffers bufs;
+    } episodes;
     const int32_t *scan_order = nullptr; // launch order of the step's scan (f110_set_scan_order; caller-owned device array) or NULL
     DevBuf<uint32_t> d_err;           // device error word (f110_device_errors)
     std::vector<double> h_side;       // side distances (host copy of d_side)

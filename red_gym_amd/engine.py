@@ -14,6 +14,7 @@ from .progress import ProgressTracker
 from .shaping import RewardShaper
 from .pathfollow import PathFollower
 from .replay import ReplayBuffer
+from .episodes import EpisodeTracker
 
 # f110_env.py:128
 DEFAULT_PARAMS = {'mu': 1.0489, 'C_Sf': 4.718, 'C_Sr': 5.4562, 'lf': 0.15875, 'lr': 0.17145, 'h': 0.074,
@@ -139,7 +140,8 @@ class Engine(object):
         self.lib = _lib.load()
         # the step's consumers (consumer.py), in the order their kernels follow a step; nothing is allocated until an install
         self.tracker, self.shaper, self.follower = ProgressTracker(self), RewardShaper(self), PathFollower(self)
-        self.replay = ReplayBuffer(self)   # last: its push reads the bitmap the shaper has just rendered
+        self.replay = ReplayBuffer(self)   # behind the shaper: its push reads the bitmap the shaper has just rendered
+        self.episodes = EpisodeTracker(self)   # last: it reads the shaper's reward, and raises pending_reset behind the push
         env_params = None
         if params is not None and not isinstance(params, dict):
             env_params = [dict(p) for p in params]
@@ -757,6 +759,7 @@ class Engine(object):
             self.shaper.close()
             self.follower.close()
             self.replay.close()
+            self.episodes.close()
             torch.cuda.synchronize(self.device)
             flags = self.device_errors() if os.environ.get('F110_CHECK_DEVICE_ERRORS') == '1' else 0
             self.lib.f110_destroy(self._h)

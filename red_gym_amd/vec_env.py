@@ -70,8 +70,8 @@ class F110VecEnv(object):
             self._obs['scans_f64'] = t['scans_f64']
         self._reward = torch.full((self.num_envs,), float(timestep), dtype=torch.float64, device=self.device)
         self._g_actions, self._graphs, self._lg = None, [], None   # capture_step / build_step_graph
-        # track_progress, shape_rewards, follow_paths, record_replay: the ones that are `on` run, in this order
-        self.consumers = (self.eng.tracker, self.eng.shaper, self.eng.follower, self.eng.replay)
+        # track_progress, shape_rewards, follow_paths, record_replay, track_episodes: the ones that are `on` run, in this order
+        self.consumers = (self.eng.tracker, self.eng.shaper, self.eng.follower, self.eng.replay, self.eng.episodes)
 
     def _result(self):
         t = self.eng.t
@@ -88,7 +88,7 @@ class F110VecEnv(object):
 
     def _after_step(self):
         """What follows every step on the same stream: the progress tracker's update, the reward shaper's, the path follower's,
-        the replay buffer's push."""
+        the replay buffer's push, the episode tracker's."""
         for c in self.consumers:
             if c.on:
                 c.update()
@@ -231,7 +231,9 @@ class F110VecEnv(object):
         replay_action as it stands at the push, r the shaper's total reward.  A transition is invalid and never sampled when
         the step was the env's reset (masked, whole batch or autoreset: terminal frame and spawn frame are no transition),
         when the env was not stepped by the call, or when there is no previous frame (the first push after this call or after
-        load_state_dict).  The terminal step itself is valid.  Eviction is FIFO by step, like the reference's deque.  `info`
+        load_state_dict).  The terminal step itself is valid.  With track_episodes() on, the transition of the step that hit the
+        limit is valid and carries d = 0 -- what the reference pushes at st == max_steps - 1 -- and the respawn step behind it is
+        invalid, like every reset.  Eviction is FIFO by step, like the reference's deque.  `info`
         also holds replay_count [1] int64 (pushes made) and replay_valid [B] uint8 (the push just made) -- views.  The ring is
         not part of state_dict().  env.replay.sample(batch_size) returns (s, a, r, ns, d, ok) on the device.
         record_replay(None) or record_replay(False) switches it off and frees the ring: no launch, no allocation, no info key
@@ -256,6 +258,32 @@ class F110VecEnv(object):
         if not self.eng.replay.on:
             raise ValueError('replay_action: the replay buffer is off (record_replay())')
         return self.eng.replay.buf['action_in']
+
+    # ------------------------------------------------------------------ episodes
+    def track_episodes(self, max_steps=2000, log=4096):
+        """Switches the episode tracker on: the episode of the reference's training loop (src/SAL.py:986-1015) for every env on the
+        GPU.  `max_steps` (the reference's 2000): the step limit, one int or an int tensor [B] -- staggered limits keep envs
+        spawned together from ending together; 0: no limit, statistics only.  `log`: the records the log of finished episodes
+        holds (1..2^24).  From then on reset, step, step_graph and step_lib_graph run the tracker behind every other consumer: an
+        episode's return is the sum of the rewards step() returned (the shaper's total while shape_rewards() is on, else the
+        constant time step), added in step order; the reset step pays nothing and counts no step.  An episode closes when the env
+        reports done (DONE), when its length reaches the limit (LIMIT), or when a reset of the user's cuts it (RESET).  At a LIMIT
+        `truncated` is raised -- `done` is never written -- and, with autoreset=True, the env's pending_reset, so that the next step
+        respawns it at its spawn pose exactly as after a done; with autoreset=False the env keeps stepping, its accumulators
+        frozen, until the user resets it.  `info` also holds episode_return [B] fp64, episode_length [B] int32, truncated [B] uint8
+        and episodes_finished [1] int64 -- views, no copies; env.episodes.finished() returns the log, env.episodes.summary() its
+        means.  Switched on in the middle of a run, or restored from a checkpoint without its keys, every env opens a fresh episode
+        and nothing is logged for the one that ran.  track_episodes(None) or track_episodes(False) switches it off: no launch, no
+        info key, no state_dict key remains."""
+        if max_steps is None or max_steps is False:
+            self.eng.episodes.remove()
+            return
+        self.eng.episodes.install(max_steps=max_steps, log=log)
+
+    @property
+    def episodes(self):
+        """The Engine's EpisodeTracker (finished, summary, DONE / LIMIT / RESET)."""
+        return self.eng.episodes
 
     # ------------------------------------------------------------------ checkpoint / resume
     _STATE_KEYS = ('state', 'steer_buf', 'steer_cnt', 'noise_step', 'spawn', 'start_rot', 'near_start', 'toggles',
