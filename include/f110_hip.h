@@ -647,17 +647,18 @@ int f110_replay_sample(f110_handle *h, uint64_t seed, uint64_t *counter, int32_t
  * f110_episodes_validate: host only.  F110_E_INVALID for limit < 0 and for log outside 1..2^24.
  * f110_episodes_install: cfg NULL removes the tracker; a refused cfg installs nothing and keeps what was there.  Install, removal and
  * bind move the launch epoch.  f110_episodes_bind: the caller-owned arrays, dev; all required but `limit` (NULL: cfg.limit for every
- * env).  Start with ep_open = 1, t_seen = -1 and zeros elsewhere.  block_counts is scratch of ceil(B / 256) int32.
+ * env).  Start with ep_open = 1, t_seen = -1 and zeros elsewhere.  block_counts is scratch of ceil(B / F110_EPISODES_BLOCK) int32.
  * f110_episodes_update: three kernels on `stream`, no allocation, no synchronisation (capturable behind f110_step and the other
  * consumers' updates: it reads the shaper's total, and the replay push in front of it sees pending_reset as the step left it).
  * F110_E_INVALID without a tracker, F110_E_UNBOUND before f110_episodes_bind or f110_bind.
  * f110_episodes_apply: the same kernels on caller-supplied arrays, no handle: n envs (n = 0: nothing is launched), reward [n] or NULL
  * (= timestep), done [n], current_time [n], laps NULL (0 is logged) or the laps of env e at laps[e * laps_stride], pending_reset [n]
- * or NULL (autoreset off); bufs as for the bind, with block_counts of ceil(n / 256) int32.  All arrays dev; launches on the calling
+ * or NULL (autoreset off); bufs as for the bind, with block_counts of ceil(n / F110_EPISODES_BLOCK) int32.  All arrays dev; launches on the calling
  * thread's current device.  F110_E_INVALID for a NULL cfg, bufs or required array, a refused cfg, n < 0, timestep <= 0. */
 #define F110_EPISODE_DONE 1  /* the env reported done */
 #define F110_EPISODE_LIMIT 2 /* the step limit was reached (truncated) */
 #define F110_EPISODE_RESET 3 /* a reset cut the running episode */
+#define F110_EPISODES_BLOCK 256 /* envs per entry of block_counts (the kernels' workgroup size) */
 typedef struct {
     int32_t limit;              /* the step limit of every env while no limit array is bound (2000: the reference's max_steps); 0: none */
     int32_t log;                /* L: records the log holds, 1..2^24 */
@@ -676,7 +677,7 @@ typedef struct {
     double *log_time;           /* [L] */
     int32_t *log_laps;          /* [L] */
     int64_t *count;             /* [1] episodes closed; start at 0 */
-    int32_t *block_counts;      /* [ceil(B / 256)] scratch */
+    int32_t *block_counts;      /* [ceil(B / F110_EPISODES_BLOCK)] scratch */
 } f110_episodes_buffers;
 int f110_episodes_validate(const f110_episodes_config *cfg);
 int f110_episodes_install(f110_handle *h, const f110_episodes_config *cfg);

@@ -2,6 +2,11 @@
 
 There is no CPU fallback: if the HIP library is missing or fails to load the
 import raises, and every entry point returning a negative code raises here.
+
+The mirror is three literal tables -- SYMBOLS (+ RESTYPES), STRUCTS and the F110_* / E_* constants -- and
+tests/test_abi_cpu.py checks them whole against the header: every prototype's return and argument types, every
+struct's fields, sizes and offsets (by the C compiler), every constant.  An entry point is added to the header
+and here; that test says where the two differ.
 """
 import ctypes as C
 import os
@@ -103,7 +108,7 @@ class EpisodesConfig(C.Structure):
 EPISODES_FIELDS = ['ep_return', 'ep_length', 'ep_open', 't_seen', 'truncated', 'limit', 'log_env', 'log_length', 'log_return',
                    'log_reason', 'log_time', 'log_laps', 'count', 'block_counts']
 F110_EPISODE_DONE, F110_EPISODE_LIMIT, F110_EPISODE_RESET = 1, 2, 3
-F110_EPISODES_BLOCK = 256           # envs per entry of block_counts
+F110_EPISODES_BLOCK = 256           # envs per entry of block_counts (the header's, which sizes the kernels' workgroups)
 
 
 class EpisodesBuffers(C.Structure):
@@ -180,7 +185,20 @@ F110_ADAM_CHUNK = 4096
 F110_ADAM_MAX_TENSORS = 64
 F110_ADAM_STATE_BYTES = 32          # f110_adam_state: int64 t, double pow1, pow2, float k2, a
 
-# every symbol include/f110_hip.h declares: name -> argtypes (restype int unless noted)
+# every typedef struct of include/f110_hip.h but f110_adam_state (device-resident; F110_ADAM_STATE_BYTES is its size)
+STRUCTS = {
+    'f110_config': Config, 'f110_buffers': Buffers, 'f110_progress_buffers': ProgressBuffers,
+    'f110_shaping_config': ShapingConfig, 'f110_shaping_buffers': ShapingBuffers,
+    'f110_pathfollow_config': PathFollowConfig, 'f110_pathfollow_buffers': PathFollowBuffers,
+    'f110_replay_config': ReplayConfig, 'f110_replay_buffers': ReplayBuffers,
+    'f110_episodes_config': EpisodesConfig, 'f110_episodes_buffers': EpisodesBuffers,
+    'f110_bitconv_config': BitconvConfig, 'f110_bitconv2_config': Bitconv2Config, 'f110_featconv_config': FeatconvConfig,
+    'f110_dense_config': DenseConfig, 'f110_policyhead_config': PolicyheadConfig,
+    'f110_qhead_config': QheadConfig, 'f110_qhead_critics': QheadCritics, 'f110_qhead_grads': QheadGrads,
+    'f110_adam_config': AdamConfig, 'f110_adam_tensor': AdamTensor, 'f110_bitmap_config': BitmapConfig,
+}
+
+# every symbol include/f110_hip.h declares: name -> argtypes; RESTYPES below holds the return types that are not int
 _VP, _I32, _I64, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 SYMBOLS = {
     'f110_create': [C.POINTER(Config), C.POINTER(_VP)],
@@ -313,6 +331,13 @@ SYMBOLS = {
     'f110_bitmap_points': [_VP, _VP, _I32, _I64, _I64, _VP, _VP],
     'f110_scan_occupancy': [_VP, _I32, _I64, _I64, _I32, _VP, _VP, _D, _D, _D, _I32, _VP, _VP],
 }
+RESTYPES = {
+    'f110_last_error': C.c_char_p,
+    'f110_destroy': None, 'f110_graph_destroy': None, 'f110_bitmap_destroy': None,
+    'f110_pack_env_size': _I64, 'f110_adam_state_bytes': _I64,
+    'f110_pure_pursuit_workspace': _I64, 'f110_bitconv_workspace': _I64, 'f110_featconv_workspace': _I64,
+    'f110_dense_workspace': _I64, 'f110_policyhead_workspace': _I64, 'f110_qhead_workspace': _I64,
+}
 
 
 class F110Error(RuntimeError):
@@ -341,19 +366,7 @@ def load():
     for name, argtypes in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.argtypes = argtypes
-        fn.restype = C.c_int
-    lib.f110_last_error.restype = C.c_char_p
-    lib.f110_pure_pursuit_workspace.restype = C.c_int64
-    lib.f110_bitconv_workspace.restype = C.c_int64
-    lib.f110_featconv_workspace.restype = C.c_int64
-    lib.f110_dense_workspace.restype = C.c_int64
-    lib.f110_policyhead_workspace.restype = C.c_int64
-    lib.f110_qhead_workspace.restype = C.c_int64
-    lib.f110_adam_state_bytes.restype = C.c_int64
-    lib.f110_pack_env_size.restype = C.c_int64
-    lib.f110_destroy.restype = None
-    lib.f110_bitmap_destroy.restype = None
-    lib.f110_graph_destroy.restype = None
+        fn.restype = RESTYPES.get(name, C.c_int)
     _lib = lib
     return lib
 

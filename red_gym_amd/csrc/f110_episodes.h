@@ -17,7 +17,7 @@
 // gfx950, hipcc -O3: count 12 VGPRs / 28 SGPRs, update 37 VGPRs / 68 SGPRs, advance 9 VGPRs / 15 SGPRs; LDS 16 / 80 / 0 bytes; no
 // scratch, no spills (tools/kernel_resources.py).  fp64 adds in step order, no contraction.
 #pragma once
-#include "../../include/f110_hip.h" // F110_EPISODE_*
+#include "../../include/f110_hip.h" // F110_EPISODE_*, F110_EPISODES_BLOCK
 #include "f110_bounds.h"
 #include "f110_device.h"
 
@@ -25,7 +25,7 @@
 
 namespace f110 {
 
-constexpr int EPISODES_THREADS = 256;
+constexpr int EPISODES_THREADS = F110_EPISODES_BLOCK; // one entry of the caller's block_counts per workgroup
 constexpr int EPISODES_WAVES = EPISODES_THREADS / 64;
 
 struct EpisodesArgs {

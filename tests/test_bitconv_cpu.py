@@ -1,8 +1,6 @@
 """Bit convolution without a GPU: the checker of tests/bitconv_cases.py against the reference's own operator (torch's conv2d in
-fp64 on the unpacked image), the library's host-only validate entry, and the ABI."""
+fp64 on the unpacked image), and the library's host-only validate entry."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -10,10 +8,6 @@ import pytest
 import bitconv_cases as bc
 import replay_cases as rc
 from test_launch_plans_cpu import constant, lib as launch_plans  # noqa: F401 (the fixture: the plan headers compiled for the host)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ('f110_bitconv_validate', 'f110_bitconv_workspace', 'f110_bitconv_forward', 'f110_bitconv_forward_u8',
-               'f110_bitconv_backward', 'f110_replay_locate')
 
 
 @pytest.mark.parametrize('rows,cols,kernel,stride,channels', bc.CASES + bc.SHAPES)
@@ -193,26 +187,6 @@ def test_validate_accepts_and_refuses():
     assert lib.f110_bitconv_forward_u8(C.byref(c), None, 3, None, -1, None, None, None, None) == _lib.E_INVALID
     assert lib.f110_bitconv_backward(C.byref(c), None, 3, None, 3, None, None, None, None, None) == _lib.E_INVALID
     assert lib.f110_replay_locate(None, None, 0, None, None, None) == _lib.E_INVALID
-
-
-def test_abi_symbols_and_struct_layout():
-    from red_gym_amd import _lib
-    lib = _lib.load()
-    hdr = open(os.path.join(ROOT, 'include', 'f110_hip.h')).read()
-    declared = set(re.findall(r'\b(f110_[a-z0-9_]+)\s*\(', hdr))
-    for name in NEW_SYMBOLS:
-        assert name in declared and name in _lib.SYMBOLS and getattr(lib, name) is not None, name
-    assert lib.f110_bitconv_workspace.restype is C.c_int64
-    body = hdr[hdr.rindex('typedef struct {', 0, hdr.index('} f110_bitconv_config;')):hdr.index('} f110_bitconv_config;')]
-    fields = []
-    for ctype, names in re.findall(r'^\s*(int32_t|float)\s+([a-z_, ]+);', body, re.M):
-        fields += [(n.strip(), C.c_int32 if ctype == 'int32_t' else C.c_float) for n in names.split(',')]
-    assert fields == list(_lib.BitconvConfig._fields_)
-    assert C.sizeof(_lib.BitconvConfig) == 7 * 4
-    # one argument per parameter of the declaration
-    for name in NEW_SYMBOLS:
-        decl = re.search(r'\b%s\s*\(([^;]*)\);' % name, hdr).group(1)
-        assert len(_lib.SYMBOLS[name]) == decl.count(',') + 1, name
 
 
 def test_module_parameters_without_gpu():

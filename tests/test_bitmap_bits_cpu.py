@@ -3,11 +3,11 @@ struct field appended for it, the argument handling of shape_rewards(image=...),
 recorded rewards when it is fed images that went through the bit format."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header
 import bits_cases as bc
 import replay_cases as rc
 import shaping_cases as sc
@@ -23,44 +23,30 @@ def lib():
     return _lib.load()
 
 
-def _header():
-    return open(os.path.join(ROOT, 'include', 'f110_hip.h')).read()
+@pytest.fixture(scope='module')
+def header():
+    return abi_header.read(os.path.join(ROOT, 'include', 'f110_hip.h'))
 
 
-def _declaration(hdr, name):
-    """The parameter list of `int name(...)` in the header, as a list of C declarations."""
-    m = re.search(r'\bint\s+%s\s*\(([^;]*)\)\s*;' % name, hdr)
-    assert m, name
-    return [' '.join(p.split()) for p in m.group(1).split(',')]
-
-
-def test_header_exports_and_mirror_agree_on_the_new_entry_points(lib):
+def test_header_exports_and_mirror_agree_on_the_new_entry_points(lib, header):
     from red_gym_amd import _lib
-    hdr = _header()
     for name, twin in zip(NEW, ('f110_bitmap_render', 'f110_shaping_terms')):
-        assert name in _lib.SYMBOLS and getattr(lib, name) is not None
-        params, twin_params = _declaration(hdr, name), _declaration(hdr, twin)
         # the bits entry takes what its bytes twin takes, but for the image: uint64 words instead of uint8 pixels
-        assert len(params) == len(twin_params) == len(_lib.SYMBOLS[name]) == len(_lib.SYMBOLS[twin])
-        differ = [(p, q) for p, q in zip(params, twin_params) if p != q]
-        assert len(differ) == 1 and 'uint64_t *' in differ[0][0] and 'uint8_t *' in differ[0][1], differ
+        (ret, params), (twin_ret, twin_params) = header[2][name], header[2][twin]
+        assert ret == twin_ret and len(params) == len(twin_params)
+        assert [(p, q) for p, q in zip(params, twin_params) if p != q] == [('uint64*', 'uint8*')]
         assert list(_lib.SYMBOLS[name]) == list(_lib.SYMBOLS[twin])
     # without a renderer / a config both refuse before any HIP call
     assert lib.f110_bitmap_render_bits(None, None, 0, 1, 1080, None, None) == _lib.E_INVALID
     assert lib.f110_shaping_terms_bits(None, None, None, None, 1, None, None, None, None, None, None) == _lib.E_INVALID
 
 
-def test_shaping_buffers_field_is_appended():
+def test_shaping_buffers_field_is_appended(header):
     from red_gym_amd import _lib
-    hdr = _header()
-    body = hdr[:hdr.index('} f110_shaping_buffers;')]
-    body = body[body.rindex('typedef struct {'):]
-    fields = re.findall(r'\*\s*([a-z_0-9]+);', body)
-    assert fields == _lib.SHAPING_FIELDS
+    fields = _lib.SHAPING_FIELDS        # (that they are the header's, with its offsets: tests/test_abi_cpu.py)
     assert fields[-1] == 'bitmap_bits' and fields[0] == 'bitmap' and len(fields) == 9      # appended: the first eight keep their offsets
-    assert C.sizeof(_lib.ShapingBuffers) == 9 * C.sizeof(C.c_void_p)
-    assert _lib.ShapingBuffers.bitmap_bits.offset == 8 * C.sizeof(C.c_void_p)
-    assert re.search(r'const uint64_t \*bitmap_bits;', body)
+    assert [getattr(_lib.ShapingBuffers, f).offset for f in fields] == [i * C.sizeof(C.c_void_p) for i in range(9)]
+    assert header[1]['f110_shaping_buffers'][-1] == ('bitmap_bits', 'uint64*', 0)
 
 
 def test_image_argument_handling(lib):

@@ -5,17 +5,12 @@ other bits; the launch plan (csrc/f110_dense_plan.h) compiled for the host with 
 on a seeded sample and, for what every launch must satisfy, on every accepted configuration of the sample; and the reference pin:
 the checkers against the recording of the reference's own Actor.fc1 (tests/golden/g23_dense.npz)."""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import dense_cases as dc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'red_gym_amd', 'csrc')
+import host_build
 
 
 @pytest.fixture(scope='module')
@@ -124,21 +119,8 @@ KEYS = ('segs chunks mblocks nblocks split gx gy block inst lds sum_blocks sum_b
 
 SHIM = r'''
 #include "f110_dense_plan.h"
-#include <cstdarg>
-#include <cstdio>
 using namespace f110;
 typedef long long ll;
-
-static char g_msg[512];
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_msg, sizeof(g_msg), fmt, ap);
-    va_end(ap);
-    return code;
-}
-extern "C" const char *shim_message() { return g_msg; }
 
 #define C(x) {#x, (ll)x}
 static const struct { const char *name; ll value; } constants[] = {@CONSTANTS@};
@@ -169,21 +151,10 @@ extern "C" int shim_dense(const int *s, ll n, ll *o)
 '''
 
 
-def _compiler():
-    for cxx in ('g++', 'c++', '/opt/rocm/llvm/bin/clang++'):
-        path = shutil.which(cxx)
-        if path:
-            return path
-    raise RuntimeError('no host C++ compiler (g++, c++ or clang++) found')
-
-
 @pytest.fixture(scope='module')
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp('dense_plan')
-    src, so = d / 'shim.cpp', d / 'libdenseplan.so'
-    src.write_text(SHIM.replace('@CONSTANTS@', ', '.join('C(%s)' % c for c in CONSTANTS)))
-    subprocess.run([_compiler(), '-std=c++17', '-O1', '-Wall', '-shared', '-fPIC', '-I', CSRC, '-o', str(so), str(src)], check=True)
-    L = ctypes.CDLL(str(so))
+    L = host_build.build_shim(tmp_path_factory.mktemp('dense_plan'), 'denseplan',
+                              host_build.FAIL_SHIM + SHIM.replace('@CONSTANTS@', ', '.join('C(%s)' % c for c in CONSTANTS)))
     L.shim_message.restype = ctypes.c_char_p
     L.shim_constant.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong)]
     L.shim_dense.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]

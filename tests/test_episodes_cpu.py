@@ -97,13 +97,14 @@ def test_checker_rules_reset_idle_and_closed_episode():
     assert ck2.log_env[3 % 2] == 3 and ck2.log_env[4 % 2] == 4 and (ck2.log_return == DT).all()
 
 
-def test_symbols_exported(lib):
-    for name in ('f110_episodes_validate', 'f110_episodes_install', 'f110_episodes_bind', 'f110_episodes_update', 'f110_episodes_apply'):
-        assert name in _lib.SYMBOLS and getattr(lib, name) is not None
+def test_symbols_exported():
+    """What the package re-exports (the library's own exports and their prototypes: tests/test_abi_cpu.py)."""
     from red_gym_amd import episodes
     assert (episodes.DONE, episodes.LIMIT, episodes.RESET) == (ec.DONE, ec.LIMIT, ec.RESET)
     import red_gym_amd
     assert (red_gym_amd.DONE, red_gym_amd.LIMIT, red_gym_amd.RESET) == (1, 2, 3) and red_gym_amd.EpisodeTracker is episodes.EpisodeTracker
+    # block_counts is sized by the header's constant, one entry per workgroup of the kernels
+    assert [episodes.blocks(n) for n in (1, 256, 257)] == [-(-n // _lib.F110_EPISODES_BLOCK) for n in (1, 256, 257)] == [1, 1, 2]
 
 
 def test_null_arguments_are_refused_without_a_gpu(lib):

@@ -5,9 +5,6 @@ shape tables (test_shape_tables_reach_every_path and its siblings) rest on them:
 and every number both sides define is compared with what the library's own C++ computes -- on the GPU tables, on a seeded sample
 of what the compiled checks accept, and, for the properties every launch must have, on every accepted configuration."""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,11 +12,9 @@ import pytest
 import bitconv2_cases as b2
 import bitconv_cases as bc
 import featconv_cases as fc
+import host_build
 import policyhead_cases as ph
 import qhead_cases as qh
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'red_gym_amd', 'csrc')
 
 CONSTANTS = ('REPLAY_MAX_DIM BC_THREADS BC_TX BC_TY BC_MAX_K BC_LROWS BC_LWORDS BC_CHUNK BC_MAX_PARTIALS BC_FORWARD_GROUP '
              'BC2_MAX_K2 BC2_MAX_C1 BC2_MAX_C2 BC2_MAX_OW1 BC2_KSTEPS BC2_ACCS BC2_LDS_BYTES BC2_MAX_GRID '
@@ -46,21 +41,8 @@ SHIM = r'''
 #include "f110_policyhead_plan.h"
 #include "f110_qhead_plan.h"
 #include "f110_featconv_plan.h"
-#include <cstdarg>
-#include <cstdio>
 using namespace f110;
 typedef long long ll;
-
-static char g_msg[512];
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_msg, sizeof(g_msg), fmt, ap);
-    va_end(ap);
-    return code;
-}
-extern "C" const char *shim_message() { return g_msg; }
 
 #define C(x) {#x, (ll)x}
 static const struct { const char *name; ll value; } constants[] = {@CONSTANTS@};
@@ -263,21 +245,10 @@ extern "C" void shim_sweep_qhead(ll *out)
 '''
 
 
-def _compiler():
-    for cxx in ('g++', 'c++', '/opt/rocm/llvm/bin/clang++'):
-        path = shutil.which(cxx)
-        if path:
-            return path
-    raise RuntimeError('no host C++ compiler (g++, c++ or clang++) found')
-
-
 @pytest.fixture(scope='module')
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp('launch_plans')
-    src, so = d / 'shim.cpp', d / 'liblaunchplans.so'
-    src.write_text(SHIM.replace('@CONSTANTS@', ', '.join('C(%s)' % c for c in CONSTANTS)))
-    subprocess.run([_compiler(), '-std=c++17', '-O1', '-Wall', '-shared', '-fPIC', '-I', CSRC, '-o', str(so), str(src)], check=True)
-    L = ctypes.CDLL(str(so))
+    L = host_build.build_shim(tmp_path_factory.mktemp('launch_plans'), 'launchplans',
+                              host_build.FAIL_SHIM + SHIM.replace('@CONSTANTS@', ', '.join('C(%s)' % c for c in CONSTANTS)))
     L.shim_message.restype = ctypes.c_char_p
     L.shim_half_log_2pi.restype = ctypes.c_double
     ip, lp, ll = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong), ctypes.c_longlong

@@ -81,14 +81,6 @@ def test_validate_accepts_and_refuses():
     assert got == pc.DEFAULTS == pathfollow.DEFAULTS
 
 
-def test_abi_symbols_exist():
-    from red_gym_amd import _lib, build
-    build.build()
-    lib = _lib.load()
-    for name in ('validate', 'install', 'bind', 'act', 'update', 'decode', 'mpc', 'advance'):
-        assert getattr(lib, 'f110_pathfollow_' + name) is not None and 'f110_pathfollow_' + name in _lib.SYMBOLS
-
-
 def test_state_machine_on_a_scripted_clock():
     """Three envs: 0 drives on and reaches its waypoints; 1 is reset; 2 is left alone by a masked reset."""
     dt = 0.01

@@ -10,17 +10,13 @@ checker's (q - tv) * float(2 / n) and the framework's 2 (q - tv) / n each round 
 one denormal step) covers both; alpha / n against alpha * (1 / n) likewise in the dtype of log_prob."""
 import ctypes
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import sacloss_cases as sl
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'red_gym_amd', 'csrc')
 ALPHAS = (0.2, 1.0, 0.013)
 
 
@@ -115,21 +111,9 @@ extern "C" void shim_sacloss(ll n, int actor, int logp_fp64, double alpha, ll *o
 '''
 
 
-def _compiler():
-    for cxx in ('g++', 'c++', '/opt/rocm/llvm/bin/clang++'):
-        path = shutil.which(cxx)
-        if path:
-            return path
-    raise RuntimeError('no host C++ compiler (g++, c++ or clang++) found')
-
-
 @pytest.fixture(scope='module')
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp('sacloss_plan')
-    src, so = d / 'shim.cpp', d / 'libsaclossplan.so'
-    src.write_text(SHIM)
-    subprocess.run([_compiler(), '-std=c++17', '-O1', '-Wall', '-shared', '-fPIC', '-I', CSRC, '-o', str(so), str(src)], check=True)
-    L = ctypes.CDLL(str(so))
+    L = host_build.build_shim(tmp_path_factory.mktemp('sacloss_plan'), 'saclossplan', SHIM)
     L.shim_constant.restype = ctypes.c_longlong
     L.shim_sacloss.argtypes = [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_longlong),
                                ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)]

@@ -4,37 +4,19 @@ launch shape to `==`), so a plan that drifts from the measured launch shapes wou
 launch the plan makes is compared, field by field, with a restatement of its rules in Python."""
 import ctypes
 import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'red_gym_amd', 'csrc')
+import host_build
+
 E_INVALID = -1
 MAX_MAPS = 4096
 ROW = 27   # ints per launch in the shim's output
 
 SHIM = r'''
 #include "f110_scan_plan.h"
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 using namespace f110;
-
-static char g_msg[512];
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_msg, sizeof(g_msg), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-extern "C" const char *shim_message() { return g_msg; }
 
 extern "C" int shim_parse(const char *s, int *out, int cap, const char **why)
 {
@@ -74,22 +56,9 @@ extern "C" int shim_plan(int n_cars, int agents, int nb, const int *spec, int n_
 '''
 
 
-def _compiler():
-    for cxx in ('g++', 'c++', '/opt/rocm/llvm/bin/clang++'):
-        path = shutil.which(cxx)
-        if path:
-            return path
-    raise RuntimeError('no host C++ compiler (g++, c++ or clang++) found')
-
-
 @pytest.fixture(scope='module')
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp('scan_plan')
-    src, so = d / 'shim.cpp', d / 'libscanplan.so'
-    src.write_text(SHIM)
-    subprocess.run([_compiler(), '-std=c++17', '-O1', '-Wall', '-shared', '-fPIC', '-I', CSRC, '-o', str(so), str(src)],
-                   check=True)
-    L = ctypes.CDLL(str(so))
+    L = host_build.build_shim(tmp_path_factory.mktemp('scan_plan'), 'scanplan', host_build.FAIL_SHIM + SHIM)
     L.shim_message.restype = ctypes.c_char_p
     L.shim_parse.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                              ctypes.POINTER(ctypes.c_char_p)]

@@ -3,7 +3,6 @@ readings of "num_envs reference envs" -- one process's class statics / independe
 different collision histories in the scenario used there), the tables Engine builds for a slot against the oracle's, and
 the ABI declarations."""
 import os
-import re
 
 import numpy as np
 
@@ -51,11 +50,7 @@ def test_own_scanner_and_shared_scanner_histories_differ(assets):
 
 def test_header_binding_and_docs_name_the_new_entry_points():
     from red_gym_amd import _lib
-    header = open(os.path.join(ROOT, 'include', 'f110_hip.h')).read()
-    integ = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    integ = open(os.path.join(ROOT, 'INTEGRATION.md')).read()        # (the header against the binding: tests/test_abi_cpu.py)
     for name, nargs in (('f110_set_side_distance_slots', 3), ('f110_check_ttc_slots', 7)):
-        m = re.search(r'int %s\(([^;]*)\);' % name, header)
-        assert m and len(m.group(1).split(',')) == nargs
-        assert len(_lib.SYMBOLS[name]) == nargs
-        assert name in integ
+        assert len(_lib.SYMBOLS[name]) == nargs and name in integ
 
