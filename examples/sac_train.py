@@ -1,5 +1,5 @@
 """The training loop of the reference's RL consumer (main(), src/SAL.py:975-1019) for many envs at once, everything on the GPU:
-    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps]
+    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps] [auto]
     select_action (the policy on the shaper's bitmap) -> path_actions (SAL's action decode and MPC step, which also hands the raw
     action to the ring) -> step (scan, shaper, the ring's push) -> after update_after steps, every update_every steps, one SACAgent
     update replayed from a graph: the batch is drawn on the device, the losses stay there.  The episodes are kept on the GPU too
@@ -7,7 +7,8 @@
     `Episode ... Reward=...` lines main() prints come from the log of finished episodes, read where the losses are printed.
 The defaults are small, so that it finishes in seconds; the reference's are batch 64, update_after 1000, update_every 50, max_steps
 2000.  The loss
-tensor is read (one synchronisation) only where it is printed.  At the end the actor is saved under the reference's keys, as main()
+tensor is read (one synchronisation) only where it is printed.  With a trailing `auto` the temperature is learnt on the device
+(SACAgent(alpha='auto'): its step is part of the replayed graph) and alpha is printed beside the losses.  At the end the actor is saved under the reference's keys, as main()
 saves sac_actor.pth."""
 import os
 import sys
@@ -20,6 +21,7 @@ from red_gym_amd.episodes import REASONS
 arg = lambda i, default: int(sys.argv[i]) if len(sys.argv) > i else default  # noqa: E731
 B, STEPS, BATCH, UPDATE_AFTER, UPDATE_EVERY, MAX_STEPS = arg(1, 64), arg(2, 48), arg(3, 64), arg(4, 16), arg(5, 4), arg(6, 12)
 AD = 16
+AUTO = len(sys.argv) > 7 and sys.argv[7] == 'auto'
 env = F110VecEnv(B, map=workload.EXAMPLE_MAP, num_agents=1, autoreset=True)
 env.shape_rewards()
 env.follow_paths()
@@ -27,7 +29,7 @@ env.record_replay(capacity=16 * B, action_dim=AD)
 env.track_episodes(MAX_STEPS + torch.arange(B, dtype=torch.int32) % 4)   # staggered: envs spawned together do not end together
 dev, cfg = env.device, env.eng.shaper.cfg
 torch.manual_seed(0)
-agent = SACAgent(action_dim=AD, rows=cfg.rows, cols=cfg.cols, device=dev)
+agent = SACAgent(action_dim=AD, rows=cfg.rows, cols=cfg.cols, device=dev, **(dict(alpha='auto') if AUTO else {}))
 raw = torch.zeros((B, AD), dtype=torch.float64, device=dev)                    # the policy's action, written in place
 obs, reward, done, info = env.reset(torch.as_tensor(workload.spawn_poses(B, 1), device=dev))
 total = torch.zeros((B,), dtype=torch.float64, device=dev)
@@ -42,7 +44,8 @@ for step in range(1, STEPS + 1):
         losses = agent.update_graph()
         updates += 1
         if updates % 4 == 1:
-            print('step %3d, update %2d: losses (actor, critic 1, critic 2) %s' % (step, updates, ' '.join('%.6f' % v for v in losses.tolist())))
+            print('step %3d, update %2d: losses (actor, critic 1, critic 2) %s%s' % (step, updates, ' '.join('%.6f' % v for v in losses.tolist()),
+                                                                                      ', alpha %.9f' % agent.alpha.item() if AUTO else ''))
             count = int(info['episodes_finished'].item())
             rec = {k: v.tolist() for k, v in env.episodes.finished(last=min(count - printed, 4)).items()}   # (a few of the new ones)
             for i in range(len(rec['env'])):

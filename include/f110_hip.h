@@ -1015,6 +1015,64 @@ int f110_sac_critic_loss(const float *q1, const float *q2, const float *tv, int6
 int f110_sac_actor_loss(const void *logp, int32_t logp_fp64, const float *qn, double alpha, int64_t n, float *loss, void *grad_logp,
                         float *grad_qn, void *stream);
 
+/* The entropy temperature of SAC, learnt on the device: log_alpha moves by Adam towards a target entropy (the usual default is
+ * -action_dim), and alpha = exp(log_alpha) lives in device memory where the two kernels that consume it read it, so a captured update
+ * replays with a temperature that changes from replay to replay.  (The reference fixes alpha = 0.2, src/SAL.py:479; the by-value
+ * entry points above are that case and are unchanged.)  Stateless but for the caller's f110_temperature_state on the device (cfg host,
+ * logp and state dev); launches on `stream` of the calling thread's current device, no allocation, no synchronisation, no atomics.
+ * f110_temperature_step: ONE launch of ONE 256-thread workgroup on logp [n] fp64 (logp_fp64 nonzero) or fp32, 1 <= n <= 2^24.
+ * Numerics, bit for bit, nothing contracted:
+ *   terms     t_i = double(logp[i]) + target_entropy           one fp64 addition; a fp32 logp is widened exactly
+ *   sum       S_0 in the order of the two losses above: 256 chains over i mod 256 ascending, then the tree 128 .. 1; n alone fixes it
+ *   mean      mean = S_0 / double(n)                            one fp64 division
+ *   loss      loss = float(-(double(log_alpha) * mean))         log_alpha as it stands BEFORE the step; one fp64 multiplication, the
+ *                                                               negation exact, one rounding to fp32
+ *   gradient  grad = float(-mean)                               d loss / d log_alpha
+ *   state     adam advances as f110_adam_step advances its state with advance nonzero: t += 1; pow1 *= beta1; pow2 *= beta2; k2 =
+ *             float(sqrt(1 - pow2)); a = float(lr / (1 - pow1))
+ *   Adam      the lines d .. p' of f110_adam_step's contract on the one element p = log_alpha, g = grad, m, v (c1, c2, b2, e from
+ *             cfg as there), each one correctly rounded fp32 operation, fmaf fused, denormals kept
+ *   alpha     alpha = exp(double(log_alpha'))                   one fp64 exp of the device's library (the one value here that is not
+ *                                                               fixed to the last bit: within an ulp of the correctly rounded one)
+ * Lane 0 forms everything behind the sum and writes the state.  A mean that is not finite is NOT caught: it propagates into loss, grad,
+ * the moments, log_alpha and alpha as it would in any framework's optimizer.  `lr` is a host scalar of the call: a captured step
+ * replays the lr it was captured with.
+ * A fresh state is written by the host: adam = {0, 1.0, 1.0, 0, 0}, alpha = init_alpha exactly, log_alpha = float(log(init_alpha)),
+ * m = v = grad = loss = 0, reserved = 0; the temperature before the first step is the number the user gave, bit for bit.  A resumed
+ * one: adam.t = step, pow = beta ** step.
+ * F110_E_INVALID, before any launch, naming the culprit: a null cfg, logp or state; n outside 1 .. 2^24; beta1 or beta2 outside [0, 1);
+ * eps <= 0 or not finite; lr or target_entropy not finite; logp not aligned to its type; state not 8-byte aligned; and a wrong device
+ * as f110_policyhead_forward refuses it (logp and state).
+ * f110_temperature_validate: the checks on cfg alone, host only.  f110_temperature_state_bytes: sizeof(f110_temperature_state), 64.
+ * f110_qhead_forward_alpha_dev, f110_sac_actor_loss_alpha_dev: f110_qhead_forward and f110_sac_actor_loss -- the same kernels, the same
+ * numerics -- with alpha read from device memory (one fp64 load; typically &state->alpha) instead of passed by value; in the actor loss
+ * grad_logp = alpha / double(n) is then one fp64 division on the device (IEEE: the host's bits).  alpha cannot be checked for
+ * finiteness on the host any more; a null `alpha` (for the critic head: where a target is asked for) and one on a wrong device are
+ * refused, everything else as the by-value entry refuses it.
+ * (The two structs carry a tag: tests/abi_header.py reads the untagged typedefs, whose fields are scalars, arrays and pointers, for
+ * the flat mirror of red_gym_amd/_lib.py; f110_temperature_state nests f110_adam_state by value, so these two are mirrored as
+ * _lib.TEMPERATURE_STRUCTS and tests/test_temperature_cpu.py checks their fields, sizes and offsets by the C compiler.) */
+typedef struct f110_temperature_config {
+    double beta1, beta2, eps;       /* 0.9, 0.999, 1e-8 */
+    double target_entropy;          /* SAC's default: -action_dim */
+} f110_temperature_config;
+typedef struct f110_temperature_state { /* on the device; 64 bytes */
+    f110_adam_state adam;           /* 32 B: t, pow1, pow2, k2, a -- advanced as f110_adam_step advances its state */
+    double alpha;                   /* what the *_alpha_dev entries read */
+    float log_alpha, m, v;          /* the parameter and its Adam moments */
+    float grad, loss;               /* of the last step (outputs) */
+    int32_t reserved;               /* 0 */
+} f110_temperature_state;
+int f110_temperature_validate(const f110_temperature_config *cfg);
+int64_t f110_temperature_state_bytes(void);
+int f110_temperature_step(const f110_temperature_config *cfg, const void *logp, int32_t logp_fp64, int64_t n,
+                          f110_temperature_state *state, double lr, void *stream);
+int f110_qhead_forward_alpha_dev(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const double *reward,
+                                 const uint8_t *done, const void *next_log_prob, double gamma, const double *alpha, float *q, float *qmin,
+                                 float *target, void *stream);
+int f110_sac_actor_loss_alpha_dev(const void *logp, int32_t logp_fp64, const float *qn, const double *alpha, int64_t n, float *loss,
+                                  void *grad_logp, float *grad_qn, void *stream);
+
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).
  * scans_f32 / lookups may be NULL; lookups [n] is overwritten-by-accumulation like

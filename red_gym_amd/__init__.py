@@ -38,6 +38,9 @@ def __getattr__(name):
     if name in ('critic_loss', 'actor_loss'):
         from . import sacloss
         return getattr(sacloss, name)
+    if name == 'Temperature':
+        from .temperature import Temperature
+        return Temperature
     if name in ('EpisodeTracker', 'DONE', 'LIMIT', 'RESET'):
         from . import episodes
         return getattr(episodes, name)

@@ -185,6 +185,25 @@ F110_ADAM_CHUNK = 4096
 F110_ADAM_MAX_TENSORS = 64
 F110_ADAM_STATE_BYTES = 32          # f110_adam_state: int64 t, double pow1, pow2, float k2, a
 
+
+# f110_temperature_config, f110_temperature_state: the entropy temperature learnt on the device.  The state lives on the device and
+# nests f110_adam_state by value; the mirror is here so that temperature.py writes a fresh state through it and reads its offsets.
+class AdamState(C.Structure):
+    _fields_ = [('t', C.c_int64), ('pow1', C.c_double), ('pow2', C.c_double), ('k2', C.c_float), ('a', C.c_float)]
+
+
+class TemperatureConfig(C.Structure):
+    _fields_ = [('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double), ('target_entropy', C.c_double)]
+
+
+class TemperatureState(C.Structure):
+    _fields_ = [('adam', AdamState), ('alpha', C.c_double), ('log_alpha', C.c_float), ('m', C.c_float), ('v', C.c_float),
+                ('grad', C.c_float), ('loss', C.c_float), ('reserved', C.c_int32)]
+
+
+# the header's tagged typedefs (a struct that nests another by value); tests/test_temperature_cpu.py checks them against the compiler
+TEMPERATURE_STRUCTS = {'f110_adam_state': AdamState, 'f110_temperature_config': TemperatureConfig, 'f110_temperature_state': TemperatureState}
+
 # every typedef struct of include/f110_hip.h but f110_adam_state (device-resident; F110_ADAM_STATE_BYTES is its size)
 STRUCTS = {
     'f110_config': Config, 'f110_buffers': Buffers, 'f110_progress_buffers': ProgressBuffers,
@@ -309,6 +328,11 @@ SYMBOLS = {
     'f110_soft_update': [C.POINTER(AdamTensor), _I32, _D, _VP],
     'f110_sac_critic_loss': [_VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP],
     'f110_sac_actor_loss': [_VP, _I32, _VP, _D, _I64, _VP, _VP, _VP, _VP],
+    'f110_temperature_validate': [_VP],
+    'f110_temperature_state_bytes': [],
+    'f110_temperature_step': [_VP, _VP, _I32, _I64, _VP, _D, _VP],
+    'f110_qhead_forward_alpha_dev': [C.POINTER(QheadConfig), C.POINTER(QheadCritics), _VP, _I64, _VP, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP],
+    'f110_sac_actor_loss_alpha_dev': [_VP, _I32, _VP, _VP, _I64, _VP, _VP, _VP, _VP],
     'f110_replay_pack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_replay_unpack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],
@@ -334,7 +358,7 @@ SYMBOLS = {
 RESTYPES = {
     'f110_last_error': C.c_char_p,
     'f110_destroy': None, 'f110_graph_destroy': None, 'f110_bitmap_destroy': None,
-    'f110_pack_env_size': _I64, 'f110_adam_state_bytes': _I64,
+    'f110_pack_env_size': _I64, 'f110_adam_state_bytes': _I64, 'f110_temperature_state_bytes': _I64,
     'f110_pure_pursuit_workspace': _I64, 'f110_bitconv_workspace': _I64, 'f110_featconv_workspace': _I64,
     'f110_dense_workspace': _I64, 'f110_policyhead_workspace': _I64, 'f110_qhead_workspace': _I64,
 }

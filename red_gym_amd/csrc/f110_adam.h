@@ -75,10 +75,9 @@ __device__ inline double adam_sqrt_rn(double x)
     return y;
 }
 
-// grid 1, block 64
-static __global__ void adam_advance_kernel(AdamState *s, double beta1, double beta2, double lr)
+// one lane: the state of step t -> that of step t + 1 (adam_advance_kernel, and the temperature step of f110_temperature.h)
+__device__ inline void adam_advance(AdamState *s, double beta1, double beta2, double lr)
 {
-    if (threadIdx.x != 0) return;
     const double p1 = s->pow1 * beta1, p2 = s->pow2 * beta2;
     const double bc1 = 1.0 - p1, bc2 = 1.0 - p2;
     s->t = s->t + 1;
@@ -86,6 +85,13 @@ static __global__ void adam_advance_kernel(AdamState *s, double beta1, double be
     s->pow2 = p2;
     s->k2 = (float)adam_sqrt_rn(bc2);
     s->a = (float)(lr / bc1);
+}
+
+// grid 1, block 64
+static __global__ void adam_advance_kernel(AdamState *s, double beta1, double beta2, double lr)
+{
+    if (threadIdx.x != 0) return;
+    adam_advance(s, beta1, beta2, lr);
 }
 
 struct AdamConsts { float c1, c2, b2, eps, tau, k2, a; };

@@ -4,6 +4,7 @@
 #include "f110_qhead.h"
 #include "f110_adam.h"
 #include "f110_sacloss.h"
+#include "f110_temperature.h"
 
 // ---------------------------------------------------------------- policy head: fc_mean, fc_log_std and the sampling tail
 extern "C" int f110_policyhead_validate(const f110_policyhead_config *cfg) { return policyhead_check(cfg, "f110_policyhead_validate"); }
@@ -95,28 +96,44 @@ static int qhead_critics(const char *who, const f110_qhead_config *cfg, const f1
     return F110_OK;
 }
 
-extern "C" int f110_qhead_forward(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const double *reward,
-                                  const uint8_t *done, const void *next_log_prob, double gamma, double alpha, float *q, float *qmin, float *target,
-                                  void *stream)
+// both forward entry points; alpha_dev: where the target's alpha is read on the device, NULL: `alpha`
+static int qhead_forward(const char *who, const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n,
+                         const double *reward, const uint8_t *done, const void *next_log_prob, double gamma, double alpha, bool by_pointer,
+                         const double *alpha_dev, float *q, float *qmin, float *target, void *stream)
 {
-    const char *who = "f110_qhead_forward";
     if (int rc = f110_qhead_validate(cfg)) return rc;
     if (n < 0 || n > QH_MAX_ROWS) return fail(F110_E_INVALID, "%s: n=%lld rows (0..%lld)", who, (long long)n, (long long)QH_MAX_ROWS);
     if (n == 0) return F110_OK;
     if (!p || !action || !q) return fail(F110_E_INVALID, "%s: null pointer", who);
     if (target && (!reward || !done || !next_log_prob)) return fail(F110_E_INVALID, "%s: a target needs reward, done and next_log_prob", who);
     if (target && (!std::isfinite(gamma) || !std::isfinite(alpha))) return fail(F110_E_INVALID, "%s: gamma or alpha is not finite", who);
+    if (target && by_pointer && !alpha_dev) return fail(F110_E_INVALID, "%s: null alpha", who);
     QheadForwardPlan plan = qhead_forward_plan(*cfg, n);
     QheadArgs &a = plan.a;
     std::vector<DevicePtr> ptrs = {{"action", action}, {"q", q}};
     if (int rc = qhead_critics(who, cfg, p, a, ptrs)) return rc;
     if (target) { ptrs.push_back({"reward", reward}); ptrs.push_back({"done", done}); ptrs.push_back({"next_log_prob", next_log_prob}); ptrs.push_back({"target", target}); }
+    if (target && by_pointer) ptrs.push_back({"alpha", alpha_dev});
     if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
     a.action = action; a.q = q; a.qmin = qmin; a.target = target;
-    if (target) { a.reward = reward; a.done = done; a.nlp = next_log_prob; a.gamma = gamma; a.alpha = alpha; }
+    if (target) { a.reward = reward; a.done = done; a.nlp = next_log_prob; a.gamma = gamma; a.alpha = alpha; a.alpha_dev = by_pointer ? alpha_dev : nullptr; }
     F110_LAUNCH(qhead_forward_kernel, plan.l, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return F110_OK;
+}
+
+extern "C" int f110_qhead_forward(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const double *reward,
+                                  const uint8_t *done, const void *next_log_prob, double gamma, double alpha, float *q, float *qmin, float *target,
+                                  void *stream)
+{
+    return qhead_forward("f110_qhead_forward", cfg, p, action, n, reward, done, next_log_prob, gamma, alpha, false, nullptr, q, qmin, target, stream);
+}
+
+extern "C" int f110_qhead_forward_alpha_dev(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n,
+                                            const double *reward, const uint8_t *done, const void *next_log_prob, double gamma, const double *alpha,
+                                            float *q, float *qmin, float *target, void *stream)
+{
+    return qhead_forward("f110_qhead_forward_alpha_dev", cfg, p, action, n, reward, done, next_log_prob, gamma, 0.0, true, alpha, q, qmin, target, stream);
 }
 
 extern "C" int f110_qhead_backward(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const float *q,
@@ -283,23 +300,57 @@ extern "C" int f110_sac_critic_loss(const float *q1, const float *q2, const floa
     return F110_OK;
 }
 
-extern "C" int f110_sac_actor_loss(const void *logp, int32_t logp_fp64, const float *qn, double alpha, int64_t n, float *loss, void *grad_logp,
-                                   float *grad_qn, void *stream)
+// both actor-loss entry points; alpha_dev: where alpha is read on the device, NULL: `alpha`
+static int sac_actor_loss(const char *who, const void *logp, int32_t logp_fp64, const float *qn, double alpha, bool by_pointer, const double *alpha_dev,
+                          int64_t n, float *loss, void *grad_logp, float *grad_qn, void *stream)
 {
-    const char *who = "f110_sac_actor_loss";
     if (int rc = sacloss_rows(who, n)) return rc;
     if (!logp || !qn || !loss) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (by_pointer && !alpha_dev) return fail(F110_E_INVALID, "%s: null alpha", who);
     if (!std::isfinite(alpha)) return fail(F110_E_INVALID, "%s: alpha is not finite", who);
     if ((uintptr_t)logp % (logp_fp64 ? 8 : 4) || (uintptr_t)grad_logp % (logp_fp64 ? 8 : 4))
         return fail(F110_E_INVALID, "%s: logp or grad_logp is not aligned to its type", who);
     std::vector<DevicePtr> ptrs = {{"logp", logp}, {"qn", qn}, {"loss", loss}};
     if (grad_logp) ptrs.push_back({"grad_logp", grad_logp});
     if (grad_qn) ptrs.push_back({"grad_qn", grad_qn});
+    if (by_pointer) ptrs.push_back({"alpha", alpha_dev});
     if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
     SaclossPlan p = sacloss_plan(n, true, logp_fp64 != 0, alpha);
     p.a.logp = logp; p.a.qn = qn; p.a.loss = loss; p.a.grad_logp = grad_logp; p.a.grad_qn = grad_qn;
+    p.a.alpha_dev = by_pointer ? alpha_dev : nullptr;
     if (p.l.inst == 2) F110_LAUNCH(sac_actor_loss_kernel<true>, p.l, (hipStream_t)stream, p.a);
     else F110_LAUNCH(sac_actor_loss_kernel<false>, p.l, (hipStream_t)stream, p.a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_sac_actor_loss(const void *logp, int32_t logp_fp64, const float *qn, double alpha, int64_t n, float *loss, void *grad_logp,
+                                   float *grad_qn, void *stream)
+{
+    return sac_actor_loss("f110_sac_actor_loss", logp, logp_fp64, qn, alpha, false, nullptr, n, loss, grad_logp, grad_qn, stream);
+}
+
+extern "C" int f110_sac_actor_loss_alpha_dev(const void *logp, int32_t logp_fp64, const float *qn, const double *alpha, int64_t n, float *loss,
+                                             void *grad_logp, float *grad_qn, void *stream)
+{
+    return sac_actor_loss("f110_sac_actor_loss_alpha_dev", logp, logp_fp64, qn, 0.0, true, alpha, n, loss, grad_logp, grad_qn, stream);
+}
+
+// ---------------------------------------------------------------- the entropy temperature learnt on the device
+extern "C" int f110_temperature_validate(const f110_temperature_config *cfg) { return temperature_check(cfg, "f110_temperature_validate"); }
+
+extern "C" int64_t f110_temperature_state_bytes(void) { return (int64_t)sizeof(f110_temperature_state); }
+
+extern "C" int f110_temperature_step(const f110_temperature_config *cfg, const void *logp, int32_t logp_fp64, int64_t n,
+                                     f110_temperature_state *state, double lr, void *stream)
+{
+    const char *who = "f110_temperature_step";
+    if (int rc = temperature_step_check(who, cfg, logp, logp_fp64, n, state, lr)) return rc;
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, {{"logp", logp}, {"state", state}})) return rc;
+    TemperaturePlan p = temperature_plan(*cfg, n, logp_fp64 != 0, lr);
+    p.a.logp = logp; p.a.state = state;
+    if (p.l.inst) F110_LAUNCH(temperature_step_kernel<true>, p.l, (hipStream_t)stream, p.a);
+    else F110_LAUNCH(temperature_step_kernel<false>, p.l, (hipStream_t)stream, p.a);
     HIP_TRY(hipGetLastError());
     return F110_OK;
 }

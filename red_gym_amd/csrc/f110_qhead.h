@@ -151,7 +151,8 @@ static __global__ __launch_bounds__(QH_THREADS) void qhead_forward_kernel(QheadA
                 if (a.qmin) a.qmin[row] = qm;
                 if (a.target) {
                     const double lp = a.act_fp64 ? reinterpret_cast<const double *>(a.nlp)[row] : (double)reinterpret_cast<const float *>(a.nlp)[row];
-                    const double tq = (double)qm - a.alpha * lp;
+                    const double alpha = a.alpha_dev ? *a.alpha_dev : a.alpha;      // (uniform in the launch)
+                    const double tq = (double)qm - alpha * lp;
                     const double keep = (1.0 - (double)a.done[row]) * a.gamma;
                     a.target[row] = (float)(a.reward[row] + keep * tq);
                 }

@@ -38,6 +38,7 @@ struct QheadArgs {
     float *grad_pre[QH_MAX_C], *grad_w_act[QH_MAX_C], *grad_b1[QH_MAX_C], *grad_w2[QH_MAX_C], *grad_b2[QH_MAX_C];
     void *grad_action;
     float *partial;                 // workspace [C][slices][H (A + 2) + 1]
+    const double *alpha_dev;        // forward, f110_qhead_forward_alpha_dev: the target's alpha is read here; NULL: `alpha` above
 };
 
 // floats of one (critic, slice) in the workspace: grad_w_act [H][A], grad_b1 [H], grad_w2 [H], grad_b2

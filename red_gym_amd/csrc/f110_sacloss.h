@@ -13,6 +13,8 @@
 //   actor:     m = alpha * double(logp[i]);  t_i = m - double(qn[i])
 //              grad_logp[i] = alpha / double(n)                (logp fp64), float(alpha / double(n)) (logp fp32)
 //              grad_qn[i] = float(-1.0 / double(n))
+//              alpha: a launch argument, or (alpha_dev, the learnt temperature of f110_temperature.h) one fp64 load, with alpha / double(n)
+//              then divided on the device: IEEE division, the host's bits
 // Where n is a power of two each gradient is what autograd gives for the framework's expression, bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -64,10 +66,17 @@ template <bool F64> static __global__ __launch_bounds__(SL_THREADS) void sac_act
 {
     __shared__ double s[SL_THREADS];
     const int tid = threadIdx.x;
+    double alpha = a.alpha, glp64 = a.glp64;
+    float glp32 = a.glp32;
+    if (a.alpha_dev) {                                // (uniform in the launch) the host's three lines, on the device's alpha
+        alpha = *a.alpha_dev;
+        glp64 = alpha / (double)a.n;
+        glp32 = (float)glp64;
+    }
     for (long long i = (long long)blockIdx.x * SL_THREADS + tid; i < a.n; i += (long long)gridDim.x * SL_THREADS) {
         if (a.grad_logp) {
-            if (F64) static_cast<double *>(a.grad_logp)[i] = a.glp64;
-            else static_cast<float *>(a.grad_logp)[i] = a.glp32;
+            if (F64) static_cast<double *>(a.grad_logp)[i] = glp64;
+            else static_cast<float *>(a.grad_logp)[i] = glp32;
         }
         if (a.grad_qn) a.grad_qn[i] = a.gqn;
     }
@@ -75,7 +84,7 @@ template <bool F64> static __global__ __launch_bounds__(SL_THREADS) void sac_act
     double c = 0.0;
     for (long long i = tid; i < a.n; i += SL_THREADS) {
         const double lp = F64 ? static_cast<const double *>(a.logp)[i] : (double)static_cast<const float *>(a.logp)[i];
-        const double m = a.alpha * lp;
+        const double m = alpha * lp;
         const double t = m - (double)a.qn[i];
         c = c + t;
     }

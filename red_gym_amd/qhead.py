@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from . import dense as _dense
+from .temperature import alpha_argument
 
 MAX_HIDDEN, MAX_ACTION_DIM, MAX_CRITICS = 4096, 32, 2
 
@@ -61,8 +62,12 @@ def _launch_forward(cfg, pres, w1s, b1s, w2s, b2s, F, action, target_inputs=None
     reward, done, nlp, gamma, alpha = target_inputs if target_inputs is not None else (None, None, None, 0.0, 0.0)
     p = _critics_struct(pres, w1s, b1s, w2s, b2s, F)
     with torch.cuda.device(dev):
-        _lib.check(lib.f110_qhead_forward(C.byref(cfg), C.byref(p), action.data_ptr(), n, _ptr(reward), _ptr(done), _ptr(nlp), float(gamma),
-                                          float(alpha), q.data_ptr(), qmin.data_ptr(), _ptr(target), _lib.stream(dev)))
+        if torch.is_tensor(alpha):                      # the [1] fp64 device tensor td_target has checked
+            _lib.check(lib.f110_qhead_forward_alpha_dev(C.byref(cfg), C.byref(p), action.data_ptr(), n, _ptr(reward), _ptr(done), _ptr(nlp),
+                                                        float(gamma), alpha.data_ptr(), q.data_ptr(), qmin.data_ptr(), _ptr(target), _lib.stream(dev)))
+        else:
+            _lib.check(lib.f110_qhead_forward(C.byref(cfg), C.byref(p), action.data_ptr(), n, _ptr(reward), _ptr(done), _ptr(nlp), float(gamma),
+                                              float(alpha), q.data_ptr(), qmin.data_ptr(), _ptr(target), _lib.stream(dev)))
     return q, qmin, target
 
 
@@ -238,7 +243,9 @@ def td_target(feats, next_action, next_log_prob, reward, done, fc1s, fc2s, gamma
     """tv [n] fp32 of SACAgent.update (src/SAL.py:546-549) under no_grad: tv = reward + (1 - done) * gamma * (min(q1, q2) - alpha *
     next_log_prob), the last two lines in fp64 and rounded once.  feats, fc1s, fc2s as twin_q's, of the TARGET critics on the next
     state; next_action [n, A] and next_log_prob [n] or [n, 1] of one dtype (fp64 or fp32: the policy head's outputs); reward [n] fp64
-    and done [n] uint8 or bool as the ring's sample() returns them.  C GEMMs plus one launch; dense, segment: as twin_q's."""
+    and done [n] uint8 or bool as the ring's sample() returns them.  alpha: a finite number, or a [1] fp64 tensor on the action's
+    device (Temperature.alpha), which the kernel then reads there (f110_qhead_forward_alpha_dev).  C GEMMs plus one launch; dense,
+    segment: as twin_q's."""
     who = 'td_target'
     nc, F, A = _linears(who, fc1s, fc2s, feats, next_action)
     n, dev = int(next_action.shape[0]), next_action.device
@@ -249,7 +256,9 @@ def td_target(feats, next_action, next_log_prob, reward, done, fc1s, fc2s, gamma
     if not torch.is_tensor(done) or done.dtype not in (torch.uint8, torch.bool) or done.numel() != n or done.device != dev:
         raise ValueError('%s: done must be uint8 or bool [%d] on the action\'s device' % (who, n))
     import math
-    if not (math.isfinite(gamma) and math.isfinite(alpha)):
+    if torch.is_tensor(alpha):
+        alpha = alpha_argument(who, alpha, dev)[1]
+    if not (math.isfinite(gamma) and (torch.is_tensor(alpha) or math.isfinite(alpha))):
         raise ValueError('%s: gamma and alpha must be finite' % who)
     with torch.no_grad():
         cfg = validate(fc1s[0].out_features, A, nc, F + A, next_action.dtype == torch.float64)

@@ -17,6 +17,7 @@ from .optim import SacAdam
 from .policyhead import PolicyHead, sample_actions
 from .qhead import QHead, td_target, twin_q
 from .sacloss import actor_loss, critic_loss
+from .temperature import Temperature
 
 NETS = ('actor', 'critic1', 'critic2', 'critic1_target', 'critic2_target')      # the reference's order of construction (:486-495)
 OPTIMIZERS = ('actor', 'critic1', 'critic2')
@@ -88,17 +89,30 @@ class SACAgent:
     attributes) of five torch.nn networks 'actor', 'critic1', 'critic2', 'critic1_target', 'critic2_target' with the reference's layers
     (conv1 .. conv3, fc1, fc_mean / fc_log_std or fc2) whose tensors the agent then shares: training the agent trains them.  Without it
     the agent builds its own, in the reference's order, the targets loaded from the critics.
+    alpha: the reference's fixed temperature (0.2), or 'auto': the temperature is learnt (red_gym_amd.temperature.Temperature, from
+    init_alpha towards target_entropy, None: -action_dim, with Adam at alpha_lr) and lives on the device -- `temperature` is that object
+    and `alpha` its [1] fp64 tensor, which the target and the actor's loss of update k read before the temperature's step of update k
+    makes the next one; the step is captured with the rest.  With a number nothing of this exists (temperature is None).
     Attributes: actor, critics [2], targets [2]; actor_opt, critic_opts [2] (SacAdam; a critic's also moves its target); draws, the [1]
     int64 draw counter on the device; sample, the tensors of the batch the last update drew (sample['indices'] names the transitions)."""
 
     def __init__(self, action_dim=16, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, rows=256, cols=256, hidden=512,
-                 on=255.0, device='cuda', networks=None):
+                 on=255.0, device='cuda', networks=None, target_entropy=None, alpha_lr=3e-4, init_alpha=0.2):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ValueError('SACAgent: device %s: there is no CPU path' % (self.device,))
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
-        self.action_dim, self.gamma, self.tau, self.alpha = int(action_dim), float(gamma), float(tau), float(alpha)
+        self.action_dim, self.gamma, self.tau = int(action_dim), float(gamma), float(tau)
+        self.temperature = None
+        if isinstance(alpha, str):
+            if alpha != 'auto':
+                raise ValueError('SACAgent: alpha %r: a number, or \'auto\' for a learnt temperature' % (alpha,))
+            self.temperature = Temperature(init_alpha=init_alpha, target_entropy=-float(self.action_dim) if target_entropy is None else target_entropy,
+                                           lr=alpha_lr, device=self.device)
+            self.alpha = self.temperature.alpha
+        else:
+            self.alpha = float(alpha)
         self.rows, self.cols, self.hidden, self.on = int(rows), int(cols), int(hidden), float(on)
         self.width = feature_width(self.rows, self.cols)
         if networks is None:
@@ -183,6 +197,8 @@ class SACAgent:
         new_a, logp = actor.sample(frames, s_idx, eps_new)                       # :564-568
         _, qn = twin_q([c.trunk(frames, s_idx) for c in critics], new_a, *_heads(critics), dense=True)
         _, g_logp, g_qn = actor_loss(logp, qn, self.alpha, loss=losses[0:1])
+        if self.temperature is not None:
+            self.temperature.step(logp)                                          # alpha of the NEXT update; this one's is read above
         self.actor_opt.zero_grad()
         torch.autograd.backward((logp, qn), (g_logp, g_qn))
         self.actor_opt.step()                                                    # :570-572
@@ -224,8 +240,10 @@ class SACAgent:
     # ---- the captured update
     def _graph_key(self, replay, n):
         opts = self.optimizers().values()
-        return (id(replay), replay.generation, replay.steps, replay.eng.B, replay._seed(None), n,
-                tuple((o.lr, o.betas, o.eps, o.tau) for o in opts))
+        key = (id(replay), replay.generation, replay.steps, replay.eng.B, replay._seed(None), n,
+               tuple((o.lr, o.betas, o.eps, o.tau) for o in opts))
+        t = self.temperature
+        return key if t is None else key + ((t.lr, t.betas, t.eps, t.target_entropy),)
 
     def capture_update(self, replay, batch_size=64, draws=True):
         """Captures the whole of update(replay, batch_size) -- the sample and the advance of the draw counter, both forward and
@@ -261,7 +279,8 @@ class SACAgent:
         """Replays the update captured for the ring and batch size of the last capture_update: one host call.  eps = (eps_next,
         eps_new) are copied into the static draws first; without them the graph draws by itself.  Returns the static [3] loss tensor
         (read it before the next replay).  The update is captured again first -- `recaptured` says so, `captures` counts -- when the
-        ring was installed anew (its old tensors are freed), or an optimizer's lr, betas, eps or tau, or the env's seed has changed:
+        ring was installed anew (its old tensors are freed), or an optimizer's (or the temperature's) lr, betas, eps, tau or target
+        entropy, or the env's seed has changed:
         a captured launch keeps the addresses and scalars it was captured with."""
         if self._g_key is None:
             raise ValueError('SACAgent: no update is captured (capture_update(replay, batch_size))')
@@ -301,11 +320,13 @@ class SACAgent:
 
     def state_dict(self):
         """The five networks under the reference's keys, the three optimizers in torch.optim.Adam's format (SacAdam.state_dict) and
-        the draw counter (copies; synchronises)."""
+        the draw counter, and under 'temperature' the learnt temperature's state where there is one (copies; synchronises)."""
         sd = {name: {_key(k): p.detach().clone() for k, p in net.named_parameters()} for name, net in self.modules().items()}
         for name, opt in self.optimizers().items():
             sd[name + '_optimizer'] = opt.state_dict()
         sd['draws'] = int(self.draws.item())
+        if self.temperature is not None:
+            sd['temperature'] = self.temperature.state_dict()
         return sd
 
     def load_state_dict(self, sd):
@@ -315,3 +336,5 @@ class SACAgent:
         for name, opt in self.optimizers().items():
             opt.load_state_dict(sd[name + '_optimizer'])
         self.draws.fill_(int(sd['draws']))
+        if self.temperature is not None:
+            self.temperature.load_state_dict(sd['temperature'])

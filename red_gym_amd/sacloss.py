@@ -6,11 +6,10 @@ these kernels repeats bit for bit and a captured one replays.  Neither function 
 tensors, which the caller hands on with torch.autograd.backward((q,), (grad_q,)) and torch.autograd.backward((log_prob, min_q),
 (grad_log_prob, grad_min_q)), and nothing here calls .item().  There is no CPU path and no torch fallback: the kernels of libf110_hip.so
 do the work."""
-import math
-
 import torch
 
 from . import _lib
+from .temperature import alpha_argument
 
 MAX_ROWS = 2 ** 24
 
@@ -61,6 +60,8 @@ def actor_loss(logp, qn, alpha, loss=None):
     """f110_sac_actor_loss: (loss [1] fp32, grad_logp [n] of logp's dtype, grad_qn [n] fp32) for logp [n] (or [n, 1]) fp64 or fp32, as
     the policy head returns it, and qn [n] fp32 (twin_q's qmin): loss = mean(alpha * logp - qn) summed in the contract's order,
     grad_logp = alpha / n and grad_qn = -1 / n, which for n a power of two are autograd's gradients of that expression bit for bit.
+    alpha: a finite number, or a [1] fp64 tensor on logp's device (Temperature.alpha): the kernel then reads it there
+    (f110_sac_actor_loss_alpha_dev) and divides alpha / n on the device, with the same bits.
     loss: a [1] fp32 tensor to write into.  One launch on the current stream, no synchronisation."""
     who = 'actor_loss'
     logp = _rows(who, 'logp', logp, dtypes=(torch.float64, torch.float32))
@@ -68,12 +69,16 @@ def actor_loss(logp, qn, alpha, loss=None):
     qn = _rows(who, 'qn', qn, n)
     if qn.device != dev:
         raise ValueError('%s: logp and qn must be on one device' % who)
-    if not isinstance(alpha, (int, float)) or not math.isfinite(alpha):
-        raise ValueError('%s: alpha %r must be finite' % (who, alpha))
+    alpha, alpha_dev = alpha_argument(who, alpha, dev)
     loss = _loss(who, loss, 1, dev)
     g_logp = torch.empty((n,), dtype=logp.dtype, device=dev)
     g_qn = torch.empty((n,), dtype=torch.float32, device=dev)
+    lib = _lib.load()
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().f110_sac_actor_loss(logp.data_ptr(), int(logp.dtype == torch.float64), qn.data_ptr(), float(alpha), n, loss.data_ptr(),
-                                                   g_logp.data_ptr(), g_qn.data_ptr(), _lib.stream(dev)))
+        if alpha_dev is None:
+            _lib.check(lib.f110_sac_actor_loss(logp.data_ptr(), int(logp.dtype == torch.float64), qn.data_ptr(), alpha, n, loss.data_ptr(),
+                                               g_logp.data_ptr(), g_qn.data_ptr(), _lib.stream(dev)))
+        else:
+            _lib.check(lib.f110_sac_actor_loss_alpha_dev(logp.data_ptr(), int(logp.dtype == torch.float64), qn.data_ptr(), alpha_dev.data_ptr(), n,
+                                                         loss.data_ptr(), g_logp.data_ptr(), g_qn.data_ptr(), _lib.stream(dev)))
     return loss, g_logp, g_qn
