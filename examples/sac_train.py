@@ -1,5 +1,5 @@
 """The training loop of the reference's RL consumer (main(), src/SAL.py:975-1019) for many envs at once, everything on the GPU:
-    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps] [auto]
+    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps] [auto] [device]
     select_action (the policy on the shaper's bitmap) -> path_actions (SAL's action decode and MPC step, which also hands the raw
     action to the ring) -> step (scan, shaper, the ring's push) -> after update_after steps, every update_every steps, one SACAgent
     update replayed from a graph: the batch is drawn on the device, the losses stay there.  The episodes are kept on the GPU too
@@ -8,7 +8,9 @@
 The defaults are small, so that it finishes in seconds; the reference's are batch 64, update_after 1000, update_every 50, max_steps
 2000.  The loss
 tensor is read (one synchronisation) only where it is printed.  With a trailing `auto` the temperature is learnt on the device
-(SACAgent(alpha='auto'): its step is part of the replayed graph) and alpha is printed beside the losses.  At the end the actor is saved under the reference's keys, as main()
+(SACAgent(alpha='auto'): its step is part of the replayed graph) and alpha is printed beside the losses.  With a trailing `device`
+the policy's Gaussian draws are made on the device (SACAgent(draws='device'): NumPy's Philox normals per env and call, the fills part of
+the replayed graph, the counters part of state_dict()) and the number of calls per stream is printed at the end.  At the end the actor is saved under the reference's keys, as main()
 saves sac_actor.pth."""
 import os
 import sys
@@ -21,7 +23,7 @@ from red_gym_amd.episodes import REASONS
 arg = lambda i, default: int(sys.argv[i]) if len(sys.argv) > i else default  # noqa: E731
 B, STEPS, BATCH, UPDATE_AFTER, UPDATE_EVERY, MAX_STEPS = arg(1, 64), arg(2, 48), arg(3, 64), arg(4, 16), arg(5, 4), arg(6, 12)
 AD = 16
-AUTO = len(sys.argv) > 7 and sys.argv[7] == 'auto'
+AUTO, DEVICE = 'auto' in sys.argv[7:], 'device' in sys.argv[7:]
 env = F110VecEnv(B, map=workload.EXAMPLE_MAP, num_agents=1, autoreset=True)
 env.shape_rewards()
 env.follow_paths()
@@ -29,7 +31,8 @@ env.record_replay(capacity=16 * B, action_dim=AD)
 env.track_episodes(MAX_STEPS + torch.arange(B, dtype=torch.int32) % 4)   # staggered: envs spawned together do not end together
 dev, cfg = env.device, env.eng.shaper.cfg
 torch.manual_seed(0)
-agent = SACAgent(action_dim=AD, rows=cfg.rows, cols=cfg.cols, device=dev, **(dict(alpha='auto') if AUTO else {}))
+agent = SACAgent(action_dim=AD, rows=cfg.rows, cols=cfg.cols, device=dev, **(dict(alpha='auto') if AUTO else {}),
+                 **(dict(draws='device', seed=0) if DEVICE else {}))
 raw = torch.zeros((B, AD), dtype=torch.float64, device=dev)                    # the policy's action, written in place
 obs, reward, done, info = env.reset(torch.as_tensor(workload.spawn_poses(B, 1), device=dev))
 total = torch.zeros((B,), dtype=torch.float64, device=dev)
@@ -54,6 +57,8 @@ for step in range(1, STEPS + 1):
             printed = count
 print('%d steps of %d envs, %d updates of batch %d, captures %d; %d of %d transitions valid; mean reward per step %.4f' % (
     STEPS, B, updates, BATCH, agent.captures, len(env.replay), env.replay.steps * B, float(total.mean()) / STEPS))
+if DEVICE:
+    print('draws made on the device: calls (acting, next_action, new_action, unused) %s' % agent.source.calls())
 s = env.episodes.summary(last=100)
 print('episodes: %d finished; the last %d: mean return %.3f, mean length %.1f; done %.0f %%, limit %.0f %%, reset %.0f %%'
       % (s['count'], s['n'], s['mean_return'], s['mean_length'], 100 * s['done'], 100 * s['limit'], 100 * s['reset']))

@@ -1073,6 +1073,50 @@ int f110_qhead_forward_alpha_dev(const f110_qhead_config *cfg, const f110_qhead_
 int f110_sac_actor_loss_alpha_dev(const void *logp, int32_t logp_fp64, const float *qn, const double *alpha, int64_t n, float *loss,
                                   void *grad_logp, float *grad_qn, void *stream);
 
+/* The policy's Gaussian draws: the eps of f110_policyhead_forward (Actor.sample's normal.rsample(), src/SAL.py:414-421) made on the
+ * device, so that the one random input of acting and of an update is the library's own, named by numbers a checkpoint can hold.
+ * One draw is named by five numbers -- seed (64 bits), stream (64 bits; an agent uses 0 for acting, 1 for an update's next_action and
+ * 2 for its new_action), call t (64 bits), row r (64 bits) and column j < A -- and its value is
+ *     float32( numpy.random.Generator( numpy.random.Philox(key=[seed, stream], counter=[0, j, r, t]) ).standard_normal() )
+ * the FIRST fp64 normal of that generator, rounded once to fp32 (ties to even): NumPy's bits, compared with == and no tolerance.
+ * Restated (checked on NumPy 2.2.6):
+ *   bit generator  Philox4x64-10: multipliers 0xD2E7470EE14C6C93 (word 0) and 0xCA5A826395121157 (word 2), Weyl increments of the
+ *                  key 0x9E3779B97F4A7C15 and 0xBB67AE8584CAA73B, ten rounds.  NumPy increments the counter BEFORE it produces a
+ *                  block: the first four raw words are the block of counter [1, j, r, t], the next four of [2, j, r, t].  Word 0 of
+ *                  the counter so belongs to the element's own block count, and two elements' streams never overlap.
+ *   normal         random_standard_normal's 256-layer ziggurat: one raw word per trial (index, sign, 52-bit magnitude; accepted by
+ *                  one table compare in 98.5 % of the elements), one more for a wedge test (against exp() of the device's library:
+ *                  a decision, and the one place where a library rounding could show), two per tail trial (|x| > 3.6541528853610088,
+ *                  log1p as glibc rounds it).  About 1.5 % of the elements take two to four words; a handful in 65 536 take five or
+ *                  more and cross into the second block.
+ *   cost           an element computes a whole block of four words and, on the common path, uses one; the other three are thrown
+ *                  away.  That is the price of lane independence: a row's draws are the same alone, among 65 536, and whatever was
+ *                  drawn before.
+ * The state is 64 bytes of caller-owned device memory: seed, one call counter per stream, padding (zeros).  The host writes a fresh
+ * one; f110_gauss_fill reads seed and t = calls[stream] ON THE DEVICE and, with advance nonzero, a one-lane kernel behind the fill
+ * adds 1 to calls[stream] -- the pattern of f110_replay_sample's draw counter and of f110_adam_step's state -- so a captured fill
+ * replays with a fresh t.  f110_gauss_fill_at is the same kernel with seed, stream and t by value, for callers that keep their own
+ * counter.  out [n, A] fp32, contiguous; rows NULL: row i is i, else an int64 [n] device array of row ids (their 64 bits as they
+ * stand).  One lane per element, a grid-stride walk beyond 2 048 workgroups of 256; stores are 16 bytes wide where out is 16-byte
+ * aligned.  Both launch on `hip_stream` of the calling thread's current device: no allocation, no synchronisation, no atomics, no LDS.
+ * F110_E_INVALID, before any launch, naming the culprit: a null state (f110_gauss_fill) or out; a state or rows not 8-byte aligned;
+ * stream outside 0 .. F110_GAUSS_STREAMS - 1; n < 1; A outside 1 .. F110_GAUSS_MAX_COLUMNS (the policy head's action_dim limit);
+ * n * A above 2^31; out not 4-byte aligned; and a wrong device as f110_policyhead_forward refuses it (state, rows, out).
+ * f110_gauss_state_bytes: sizeof(f110_gauss_state), 64.
+ * (The struct carries a tag for the reason f110_temperature_state does: it is mirrored as _lib.GAUSS_STRUCTS and
+ * tests/test_gauss_cpu.py checks its fields, size and offsets by the C compiler.) */
+#define F110_GAUSS_STREAMS 4
+#define F110_GAUSS_MAX_COLUMNS 32
+typedef struct f110_gauss_state {   /* on the device; 64 bytes */
+    uint64_t seed;
+    uint64_t calls[F110_GAUSS_STREAMS]; /* calls[s]: the t of the next f110_gauss_fill of stream s */
+    uint64_t reserved[3];           /* 0 */
+} f110_gauss_state;
+int64_t f110_gauss_state_bytes(void);
+int f110_gauss_fill(f110_gauss_state *state, int32_t stream, int64_t n, int32_t A, const int64_t *rows, float *out, int32_t advance,
+                    void *hip_stream);
+int f110_gauss_fill_at(uint64_t seed, int32_t stream, uint64_t t, int64_t n, int32_t A, const int64_t *rows, float *out, void *hip_stream);
+
 /* ---- function-level entry points (parity tests; all pointers dev) ---- */
 /* ScanSimulator2D.scan(pose, None): n poses [n,3] -> [n,num_beams] (noise off).
  * scans_f32 / lookups may be NULL; lookups [n] is overwritten-by-accumulation like

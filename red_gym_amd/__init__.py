@@ -41,6 +41,9 @@ def __getattr__(name):
     if name == 'Temperature':
         from .temperature import Temperature
         return Temperature
+    if name == 'GaussianSource':
+        from .gauss import GaussianSource
+        return GaussianSource
     if name in ('EpisodeTracker', 'DONE', 'LIMIT', 'RESET'):
         from . import episodes
         return getattr(episodes, name)

@@ -204,6 +204,18 @@ class TemperatureState(C.Structure):
 # the header's tagged typedefs (a struct that nests another by value); tests/test_temperature_cpu.py checks them against the compiler
 TEMPERATURE_STRUCTS = {'f110_adam_state': AdamState, 'f110_temperature_config': TemperatureConfig, 'f110_temperature_state': TemperatureState}
 
+# f110_gauss_state: the policy's Gaussian draws.  The state lives on the device; the mirror is here so that gauss.py writes a fresh
+# one through it and reads its offsets.  A tagged typedef like the temperature's; tests/test_gauss_cpu.py checks it against the compiler.
+F110_GAUSS_STREAMS = 4
+F110_GAUSS_MAX_COLUMNS = 32
+
+
+class GaussState(C.Structure):
+    _fields_ = [('seed', C.c_uint64), ('calls', C.c_uint64 * F110_GAUSS_STREAMS), ('reserved', C.c_uint64 * 3)]
+
+
+GAUSS_STRUCTS = {'f110_gauss_state': GaussState}
+
 # every typedef struct of include/f110_hip.h but f110_adam_state (device-resident; F110_ADAM_STATE_BYTES is its size)
 STRUCTS = {
     'f110_config': Config, 'f110_buffers': Buffers, 'f110_progress_buffers': ProgressBuffers,
@@ -333,6 +345,9 @@ SYMBOLS = {
     'f110_temperature_step': [_VP, _VP, _I32, _I64, _VP, _D, _VP],
     'f110_qhead_forward_alpha_dev': [C.POINTER(QheadConfig), C.POINTER(QheadCritics), _VP, _I64, _VP, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP],
     'f110_sac_actor_loss_alpha_dev': [_VP, _I32, _VP, _VP, _I64, _VP, _VP, _VP, _VP],
+    'f110_gauss_state_bytes': [],
+    'f110_gauss_fill': [_VP, _I32, _I64, _I32, _VP, _VP, _I32, _VP],
+    'f110_gauss_fill_at': [C.c_uint64, _I32, C.c_uint64, _I64, _I32, _VP, _VP, _VP],
     'f110_replay_pack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_replay_unpack': [_VP, _I64, _I32, _I32, _VP, _VP],
     'f110_profile_begin': [_VP, _I32],
@@ -359,6 +374,7 @@ RESTYPES = {
     'f110_last_error': C.c_char_p,
     'f110_destroy': None, 'f110_graph_destroy': None, 'f110_bitmap_destroy': None,
     'f110_pack_env_size': _I64, 'f110_adam_state_bytes': _I64, 'f110_temperature_state_bytes': _I64,
+    'f110_gauss_state_bytes': _I64,
     'f110_pure_pursuit_workspace': _I64, 'f110_bitconv_workspace': _I64, 'f110_featconv_workspace': _I64,
     'f110_dense_workspace': _I64, 'f110_policyhead_workspace': _I64, 'f110_qhead_workspace': _I64,
 }

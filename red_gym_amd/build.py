@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-UNITS = ['f110_handle', 'f110_maps', 'f110_noise_abi', 'f110_step', 'f110_consumers', 'f110_bitconv_abi', 'f110_policy_abi', 'f110_featconv_abi', 'f110_dense_abi', 'f110_bitmap_abi']
+UNITS = ['f110_handle', 'f110_maps', 'f110_noise_abi', 'f110_step', 'f110_consumers', 'f110_bitconv_abi', 'f110_policy_abi', 'f110_gauss_abi', 'f110_featconv_abi', 'f110_dense_abi', 'f110_bitmap_abi']
 HEADERS = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + [os.path.join(os.path.dirname(HERE), 'include', 'f110_hip.h')]
 LIB = os.path.join(HERE, 'libf110_hip.so')
 OBJ_DIR = os.path.join(HERE, 'build')

@@ -11,6 +11,7 @@
 //   f110_bitconv_abi.hip the policy's first layers from bits, stateless: bit convolution, policy stem
 //   f110_policy_abi.hip the policy's and the critics' tails, stateless: policy head, critic head, the parameter update (Adam and
 //                       the soft update of the targets), the two losses of a SAC update and the learnt entropy temperature
+//   f110_gauss_abi.hip  the policy's Gaussian draws, stateless but for the caller's 64-byte state: NumPy's Philox normals per element
 //   f110_featconv_abi.hip the trunk's dense convolutions (conv2, conv3), stateless: forward, grad_x, grad_weight / grad_bias
 //   f110_dense_abi.hip  the dense layer fc1, stateless: forward, grad_x, grad_weight, grad_bias
 //   f110_bitmap_abi.hip the scan's consumers with no handle: scan -> bitmap (its own f110_bitmap object), occupancy grid

@@ -8,6 +8,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .gauss import GaussianSource
 
 MAX_IN_FEATURES, MAX_ACTION_DIM = 4096, 32
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
@@ -179,7 +180,9 @@ class PolicyHead(torch.nn.Module):
     def sample(self, h, eps=None, generator=None, dtype=torch.float64, out=None):
         """Actor.sample(evaluate=False) on features h [n, in_features]: (action, log_prob, mean, log_std) of sample_actions.  eps:
         the [n, action_dim] fp32 draws; None draws them with torch.randn on h's device (from `generator` when given), so the
-        random numbers stay torch's."""
+        random numbers stay torch's; a gauss.GaussianSource draws them on the device from its stream 0, rows 0 .. n-1, and advances it."""
+        if isinstance(eps, GaussianSource):
+            eps = eps.normal(h.shape[0], self.fc_mean.out_features)
         if eps is None:
             if not torch.is_tensor(h) or h.dim() != 2:
                 raise ValueError('PolicyHead.sample: h must be [n, in_features]')

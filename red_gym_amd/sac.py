@@ -13,6 +13,7 @@ import torch
 
 from .dense import Dense
 from .featconv import Trunk
+from .gauss import GaussianSource
 from .optim import SacAdam
 from .policyhead import PolicyHead, sample_actions
 from .qhead import QHead, td_target, twin_q
@@ -93,11 +94,17 @@ class SACAgent:
     init_alpha towards target_entropy, None: -action_dim, with Adam at alpha_lr) and lives on the device -- `temperature` is that object
     and `alpha` its [1] fp64 tensor, which the target and the actor's loss of update k read before the temperature's step of update k
     makes the next one; the step is captured with the rest.  With a number nothing of this exists (temperature is None).
+    draws: where the Gaussian draws of Actor.sample come from when no eps is passed.  'torch': torch.randn, as before.  'device':
+    red_gym_amd.gauss.GaussianSource(seed) -- `source` is that object -- whose stream 0 serves select_action (row = the env: `index`
+    where one is given, so an env's noise is the same alone and in the batch), stream 1 an update's next_action and stream 2 its
+    new_action (row = the batch row); each call that draws advances its stream's counter on the device, the fills and their advances
+    are captured with the update, and state_dict() holds the seed and the counters, so a loaded agent continues to the same bits.  An
+    eps that is passed wins and advances nothing, and so does evaluate=True.  With 'torch' nothing of this exists (source is None).
     Attributes: actor, critics [2], targets [2]; actor_opt, critic_opts [2] (SacAdam; a critic's also moves its target); draws, the [1]
     int64 draw counter on the device; sample, the tensors of the batch the last update drew (sample['indices'] names the transitions)."""
 
     def __init__(self, action_dim=16, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, rows=256, cols=256, hidden=512,
-                 on=255.0, device='cuda', networks=None, target_entropy=None, alpha_lr=3e-4, init_alpha=0.2):
+                 on=255.0, device='cuda', networks=None, target_entropy=None, alpha_lr=3e-4, init_alpha=0.2, draws='torch', seed=0):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ValueError('SACAgent: device %s: there is no CPU path' % (self.device,))
@@ -113,6 +120,9 @@ class SACAgent:
             self.alpha = self.temperature.alpha
         else:
             self.alpha = float(alpha)
+        if draws not in ('torch', 'device'):
+            raise ValueError('SACAgent: draws %r: \'torch\' or \'device\'' % (draws,))
+        self.source = GaussianSource(seed, self.device) if draws == 'device' else None
         self.rows, self.cols, self.hidden, self.on = int(rows), int(cols), int(hidden), float(on)
         self.width = feature_width(self.rows, self.cols)
         if networks is None:
@@ -159,14 +169,16 @@ class SACAgent:
         """select_action (src/SAL.py:499-519) for a batch of envs under no_grad -> the fp64 [n, action_dim] action that
         F110VecEnv.path_actions and replay_action take: tanh(mean) with evaluate, else a sample.  frames: the env's uint8 bitmaps [n,
         rows, cols] or their bits [m, rows, words] int64 (info['lidar_bitmap'] either way); index: rows of `frames` to act on (None:
-        all).  eps: the [n, action_dim] fp32 draws (None: torch.randn); out: a [n, action_dim] fp64 tensor that receives the action, a
-        static buffer that path_actions or a captured step reads.  A row's action does not depend on the batch around it."""
+        all).  eps: the [n, action_dim] fp32 draws (None: torch.randn, or stream 0 of `source` with the envs' numbers as rows); out: a
+        [n, action_dim] fp64 tensor that receives the action, a static buffer that path_actions or a captured step reads.  A row's action does not depend on the batch around it."""
         with torch.no_grad():
             h = self.actor.features(frames, index)
             if evaluate:
                 head = self.actor.head
                 return sample_actions(h, head.fc_mean.weight, head.fc_mean.bias, head.fc_log_std.weight, head.fc_log_std.bias, eps=None,
                                       dtype=torch.float64, out=out)[0]
+            if eps is None and self.source is not None:
+                eps = self.source.normal(h.shape[0], self.action_dim, stream=0, rows=index)
             return self.actor.head.sample(h, eps=eps, dtype=torch.float64, out=out)[0]
 
     # ---- learning
@@ -183,6 +195,10 @@ class SACAgent:
     def _update(self, frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, losses):
         """:544-580 on one batch; the three losses go to `losses` [3] (actor, critic1, critic2), which is returned."""
         actor, critics, targets = self.actor, self.critics, self.targets
+        if eps_next is None and self.source is not None:
+            n = int(s_idx.shape[0])
+            eps_next = self.source.normal(n, self.action_dim, stream=1)
+            eps_new = self.source.normal(n, self.action_dim, stream=2)
         with torch.no_grad():                                                    # :544-549
             next_a, next_logp = actor.sample(frames, ns_idx, eps_next)
             tv = td_target([t.trunk(frames, ns_idx) for t in targets], next_a, next_logp, r, d, *_heads(targets), self.gamma, self.alpha, dense=True)
@@ -243,14 +259,16 @@ class SACAgent:
         key = (id(replay), replay.generation, replay.steps, replay.eng.B, replay._seed(None), n,
                tuple((o.lr, o.betas, o.eps, o.tau) for o in opts))
         t = self.temperature
-        return key if t is None else key + ((t.lr, t.betas, t.eps, t.target_entropy),)
+        key = key if t is None else key + ((t.lr, t.betas, t.eps, t.target_entropy),)
+        return key if self.source is None else key + (('source', self.source.state.data_ptr()),)
 
     def capture_update(self, replay, batch_size=64, draws=True):
         """Captures the whole of update(replay, batch_size) -- the sample and the advance of the draw counter, both forward and
         backward passes, the losses, the three optimizer steps -- in one torch.cuda.graph on a side stream.  A capture executes
         nothing: no parameter, moment or counter moves.  The batch, the two draws and the losses live in static tensors (the losses:
         the tensor update_graph returns, the same across re-captures); .grad is dropped inside the capture, so the gradients live in the
-        graph's pool.  draws=True records the two torch.randn calls inside the graph (the framework's graph-safe generator); draws=False
+        graph's pool.  draws=True records the two draws inside the graph (torch.randn of the framework's graph-safe generator, or the
+        two fills of `source` and the advances of their counters); draws=False
         captures the variant that reads the static draws update_graph(eps=...) fills.  update_graph captures what it needs by itself;
         calling this first only moves the cost."""
         self._check_replay(replay)
@@ -320,13 +338,16 @@ class SACAgent:
 
     def state_dict(self):
         """The five networks under the reference's keys, the three optimizers in torch.optim.Adam's format (SacAdam.state_dict) and
-        the draw counter, and under 'temperature' the learnt temperature's state where there is one (copies; synchronises)."""
+        the draw counter, under 'temperature' the learnt temperature's state where there is one and under 'source' the seed and the
+        call counters of the device's draws where it makes them (copies; synchronises)."""
         sd = {name: {_key(k): p.detach().clone() for k, p in net.named_parameters()} for name, net in self.modules().items()}
         for name, opt in self.optimizers().items():
             sd[name + '_optimizer'] = opt.state_dict()
         sd['draws'] = int(self.draws.item())
         if self.temperature is not None:
             sd['temperature'] = self.temperature.state_dict()
+        if self.source is not None:
+            sd['source'] = self.source.state_dict()
         return sd
 
     def load_state_dict(self, sd):
@@ -338,3 +359,5 @@ class SACAgent:
         self.draws.fill_(int(sd['draws']))
         if self.temperature is not None:
             self.temperature.load_state_dict(sd['temperature'])
+        if self.source is not None:
+            self.source.load_state_dict(sd['source'])
