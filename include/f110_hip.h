@@ -319,6 +319,29 @@ int f110_set_scan_stages(f110_handle *h, const char *spec);
 int f110_set_scan_order(f110_handle *h, const int32_t *order_dev);
 int f110_launch_epoch(f110_handle *h, int64_t *epoch);
 
+/* The form of the step's scan (performance only; results do not depend on it).  Besides the classic form -- two cars per
+ * workgroup sharing one 1 024-slot LDS copy of the map's distance LUT -- every install of map slot 0 builds two COMPACT forms (two more cell
+ * tables: 2 x the cell table's bytes, 10 MB at 1 600 x 1 600), S = 256 and 512: an LDS image of the LUT's first S - 2 ranks and a cell table in which every cell of a higher rank carries the far
+ * marker (such cells take the second table, as cells beyond the classic image always did).  A compact form runs workgroups of
+ * one wave, each with its own image.  It applies to the step's scan on a single map whose origin is unrotated and whose
+ * resolution is a power of two; the rule that picks it (scan_compact_choice in csrc/f110_scan_plan.h) reads, per form, the
+ * share of free cells behind its marker among the cells a car can reach, averaged over the cars (scan_reach_shares, same
+ * file): the free cells 8-connected to the car's spawn cell.  Until those shares are learnt the scan keeps the classic form.
+ * The environment variable F110_SCAN_FORM = classic | compact256 | compact512, read once per process, overrides the rule where
+ * the form applies (tests, A/B runs).
+ * f110_scan_form_learn(h, poses_dev, stream): learns the shares from poses_dev = dev [num_envs * num_agents][3] (x, y, yaw),
+ * the spawn poses of a reset of ALL envs; call it beside that reset (red_gym_amd.Engine.reset does).  Unlike f110_reset it
+ * SYNCHRONISES `stream`, copies the poses and map slot 0's cell table to the host, allocates there (4 bytes per map cell) and
+ * floods the cars' free components -- tens of ms on a 1 600 x 1 600 map.  It does all that once per map install and only
+ * where the answer is used: it returns at once on a handle the rule cannot route (several agents per env, fewer than 32 768
+ * cars, a map per env, a rotated origin or a resolution that is not 2^k), under F110_SCAN_FORM, when the shares are known,
+ * and on a stream that is being captured.  Learning moves the launch epoch.  Never calling it is safe: the classic form.
+ * f110_scan_form_info: *form = the S a step of n_cars cars launches now (0: classic); out_share[4] = the shares for S = 256 and
+ * 512 over ALL free cells of map slot 0, recorded at install (1.0 each where the compact tables were not built: a table beyond
+ * 64 MB, a failed allocation, a slot other than 0), then the learnt ones (-1.0 each while not learnt). */
+int f110_scan_form_learn(f110_handle *h, const double *poses_dev, void *stream);
+int f110_scan_form_info(f110_handle *h, int32_t n_cars, int32_t *form, double *out_share);
+
 /* The step as a HIP graph the library builds itself, for callers without a capturing framework and as the reference
  * point for framework captures: F110_GRAPH_NODES = one kernel node per kernel of f110_step(actions_dev), chained
  * (hipGraphAddKernelNode); F110_GRAPH_CAPTURE = the same launches captured on a private non-blocking stream.

@@ -160,6 +160,17 @@ struct f110_handle {
         DevBuf<double> d_lut, d_lut_lds, d_dt;
         MapDev dev;                   // host copy of d_maps[slot]
         bool used = false, ident = false, pow2 = false;
+        // compact forms (f110_map.h LUT_COMPACT), when they were built: their tables and, per form, the share of the map's
+        // free cells whose code lies behind its far marker (plan_scan's eligibility rule reads it)
+        DevBuf<uint16_t> d_cells_c[N_COMPACT];
+        DevBuf<double> d_lut_lds_c[N_COMPACT];
+        bool compact = false;
+        double compact_out[N_COMPACT] = {1.0, 1.0};
+        // the same shares over the free cells a car can REACH (8-connected to its spawn cell), averaged over the cars, learnt at
+        // the first reset of all envs after the install (learn_reach, f110_step.hip): what the rule reads.  The open ground
+        // around a track may be most of the map's free cells and holds next to no car
+        bool reach_known = false;
+        double reach_out[N_COMPACT] = {1.0, 1.0};
     };
     MapSlot slots[F110_MAX_MAPS];
     DevBuf<MapDev> d_maps;            // dev [F110_MAX_MAPS] descriptors read by scan_kernel

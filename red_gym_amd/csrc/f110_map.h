@@ -33,6 +33,17 @@ constexpr unsigned LDS_RANKS = LUT_LDS - 2;
 constexpr unsigned OFF_FAR = 8 * SLOT_FAR;
 constexpr unsigned CODE_ESC = 65535;                    // second table: read the fp64 table instead
 __host__ __device__ inline unsigned cell_code(unsigned rank) { return rank < LDS_RANKS ? 8u * (rank + 1u) : OFF_FAR; }
+// Compact forms (one-wave workgroups, f110_scan_plan.h): an LDS image of S slots -- the first S - 1 slots of the classic image
+// (dt[-1,-1] and ranks 0 .. S-3), then the far marker -- and a cell table of its own in which every code at or beyond the
+// marker's slot IS the marker's offset.  Same strips, same border; a cell behind the marker takes the second table as ever, so
+// only the share of look-ups on that rare path differs.  A map sized for its road rarely needs more than a few hundred ranks,
+// and 2 KB instead of 8 KB per LUT copy is what lets every wave own one.
+constexpr int N_COMPACT = 2;
+constexpr int LUT_COMPACT[N_COMPACT] = {256, 512};
+__host__ __device__ constexpr unsigned compact_off_far(int S) { return 8u * (unsigned)(S - 1); }
+__host__ __device__ constexpr unsigned compact_code(unsigned code, int S) { return code < compact_off_far(S) ? code : compact_off_far(S); }
+__host__ __device__ constexpr int compact_index(int S) { return S == 256 ? 0 : S == 512 ? 1 : -1; }
+static_assert(compact_index(LUT_COMPACT[0]) == 0 && compact_index(LUT_COMPACT[1]) == 1, "compact_index names LUT_COMPACT's entries");
 // geometry of the padded strip table
 __host__ __device__ inline int map_rows_padded(int H) { return ((H + 2 + 7) >> 3) << 3; }
 __host__ __device__ inline size_t map_cells(int H, int W) { return (size_t)((W >> 3) + 2) * map_rows_padded(H) * 8; } // strip 0 only holds the left border column
@@ -50,6 +61,8 @@ struct MapDev {
     int H, W;
     double res, rinv, ox, oy, oc, os, wres, hres, oob; // oob = dt[H-1][W-1]
     unsigned lut_len;       // entries of lut
+    const uint16_t *cells_c[N_COMPACT];  // compact cell tables (layout and size of `cells`) for S = LUT_COMPACT[i], or NULL
+    const double *lut_lds_c[N_COMPACT];  // [S] their LDS images
 };
 
 } // namespace f110

@@ -170,6 +170,30 @@ static __global__ __launch_bounds__(256) void map_fill_border_kernel(uint16_t *c
     cells_far[i] = 0;
 }
 
+// The compact cell tables from the classic one (both pipelines end with the classic table on the device), element by element:
+// borders and padding keep code 0.  counts[0] += free cells (a code above rank 0's: the distance is not 0), counts[1 + i] +=
+// those of them whose code lies at or beyond the marker of LUT_COMPACT[i].
+static __global__ __launch_bounds__(256) void map_compact_kernel(const uint16_t *cells, size_t n, uint16_t *out0, uint16_t *out1,
+                                                                 unsigned *counts)
+{
+    __shared__ unsigned s_cnt[1 + N_COMPACT];
+    if (threadIdx.x < 1 + N_COMPACT) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const unsigned code = cells[i];
+        out0[i] = (uint16_t)compact_code(code, LUT_COMPACT[0]);
+        out1[i] = (uint16_t)compact_code(code, LUT_COMPACT[1]);
+        if (code > cell_code(0)) {
+            atomicAdd(&s_cnt[0], 1u);
+            if (code >= compact_off_far(LUT_COMPACT[0])) atomicAdd(&s_cnt[1], 1u);
+            if (code >= compact_off_far(LUT_COMPACT[1])) atomicAdd(&s_cnt[2], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 1 + N_COMPACT && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
+}
+
 // lut[rank] = resolution * sqrt(d2) for every distinct d2 with rank < n_lut
 static __global__ __launch_bounds__(256) void map_lut_kernel(const unsigned *bits, int n_words, const unsigned *word_prefix, double res,
                                                       double *lut, unsigned n_lut)

@@ -2,14 +2,50 @@
 #include "f110_handle.h"
 #include "f110_mapgen.h"
 
+// The compact forms of a map (f110_map.h) beside its classic tables, derived from them on the device.  They are an extra: a
+// table beyond COMPACT_MAX_BYTES, or an allocation or copy that fails, leaves the slot with the classic form alone.  Cost: two
+// more cell tables, 2 x cells_bytes (10 MB at 1 600 x 1 600), for slot 0 only.
+constexpr size_t COMPACT_MAX_BYTES = (size_t)64 << 20;
+static void build_compact(f110_handle::MapSlot &ns)
+{
+    const size_t n = ns.d_cells.size();
+    if (n * sizeof(uint16_t) > COMPACT_MAX_BYTES) return;
+    DevBuf<uint16_t> cells[N_COMPACT];
+    DevBuf<double> img[N_COMPACT];
+    DevBuf<unsigned> counts;
+    double classic[LUT_COMPACT[N_COMPACT - 1]];
+    unsigned cnt[1 + N_COMPACT] = {};
+    bool ok = counts.alloc(1 + N_COMPACT) == hipSuccess && hipMemset(counts.get(), 0, sizeof(cnt)) == hipSuccess &&
+              hipMemcpy(classic, ns.d_lut_lds.get(), sizeof(classic), hipMemcpyDeviceToHost) == hipSuccess;
+    for (int i = 0; ok && i < N_COMPACT; i++) {
+        std::vector<double> v(classic, classic + LUT_COMPACT[i]);
+        v.back() = -0.0; // the far marker
+        ok = cells[i].alloc(n) == hipSuccess && img[i].upload(v.data(), v.size()) == hipSuccess;
+    }
+    if (ok) {
+        hipLaunchKernelGGL(map_compact_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, ns.d_cells.get(), n,
+                           cells[0].get(), cells[1].get(), counts.get());
+        ok = hipGetLastError() == hipSuccess && hipMemcpy(cnt, counts.get(), sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); return; }
+    for (int i = 0; i < N_COMPACT; i++) {
+        ns.d_cells_c[i] = std::move(cells[i]);
+        ns.d_lut_lds_c[i] = std::move(img[i]);
+        ns.compact_out[i] = cnt[0] ? (double)cnt[1 + i] / (double)cnt[0] : 0.0;
+    }
+    ns.compact = true;
+}
+
 // Both pipelines end here.  `ns` holds the complete tables of the new map; until the descriptor is on the device nothing of the
 // slot has changed, so a failed install leaves the slot, its descriptor and the handle's flags as they were.  Then the slot takes
 // the new tables over (its old ones are freed: the pipelines synchronised the device before building), with new flags and epoch.
 static int commit_map(f110_handle *h, int slot, f110_handle::MapSlot &&ns, int H, int W, double res, double ox, double oy, double oc,
                       double os, double oob)
 {
+    if (slot == 0) build_compact(ns); // (the forms apply to a single map only; a handle that goes on to a map per env keeps slot 0's)
     MapDev &m = ns.dev;
     memset(&m, 0, sizeof(m));
+    for (int i = 0; i < N_COMPACT; i++) { m.cells_c[i] = ns.d_cells_c[i].get(); m.lut_lds_c[i] = ns.d_lut_lds_c[i].get(); }
     m.cells = ns.d_cells.get(); m.cells_far = ns.d_cells_far.get(); m.lut = ns.d_lut.get(); m.lut_lds = ns.d_lut_lds.get(); m.dt = ns.d_dt.get();
     m.H = H; m.W = W; m.strip_bytes = (unsigned)map_rows_padded(H) * 16u; m.cells_bytes = (unsigned)(ns.d_cells.size() * sizeof(uint16_t));
     m.res = res; m.rinv = 1.0 / res;

@@ -22,13 +22,15 @@ struct MapView {
     int H, W;
     double res, rinv, ox, oy, oc, os, wres, hres;
     double nox, noy; // -ox * rinv, -oy * rinv (exact when rinv is a power of two)
-    F110_BOUNDS_ONLY(uint32_t *err = nullptr; unsigned cells_bytes = 0;)
-    __device__ void init(const MapDev &m)
+    F110_BOUNDS_ONLY(uint32_t *err = nullptr; unsigned cells_bytes = 0; unsigned off_far = OFF_FAR;)
+    // cells: the table the march reads, m.cells or one of m.cells_c (same layout and size); off_far: its far marker's code
+    __device__ void init(const MapDev &m, const uint16_t *cells, unsigned far_code)
     {
-        F110_BOUNDS_ONLY(cells_bytes = m.cells_bytes;)
-        cells_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(m.cells), 0, (int)m.cells_bytes, 0x00020000);
-        cells_words.x = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)m.cells);
-        cells_words.y = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)m.cells >> 32) & 0xffffu);
+        F110_BOUNDS_ONLY(cells_bytes = m.cells_bytes; off_far = far_code;)
+        (void)far_code;
+        cells_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(cells), 0, (int)m.cells_bytes, 0x00020000);
+        cells_words.x = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)cells);
+        cells_words.y = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)cells >> 32) & 0xffffu);
         cells_words.z = __builtin_amdgcn_readfirstlane(m.cells_bytes); cells_words.w = __builtin_amdgcn_readfirstlane(0x00020000u);
         row_bias = m.strip_bytes + 16u; strip_m16 = m.strip_bytes - 16u; desc = &m; H = m.H; W = m.W; res = m.res; rinv = m.rinv;
         ox = m.ox; oy = m.oy; oc = m.oc; os = m.os; wres = m.wres; hres = m.hres;
@@ -114,8 +116,8 @@ __device__ inline double dist_lookup(const MapView &m, const double *lds_lut, do
     unsigned code = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(m.cells_rsrc, (int)off, 0, 0);
 #if defined(F110_BOUNDS)
     F110_BCHK(off + 2u <= m.cells_bytes, BT_LUT_CODE, m.err);
-    F110_BCHK(code <= OFF_FAR && (code & 7u) == 0u, BT_LUT_CODE, m.err);
-    code = code <= OFF_FAR ? (code & ~7u) : 0u;
+    F110_BCHK(code <= m.off_far && (code & 7u) == 0u, BT_LUT_CODE, m.err); // (a compact table: nothing behind ITS marker)
+    code = code <= m.off_far ? (code & ~7u) : 0u;
 #endif
     // the loaded value IS the LDS byte offset of the distance: one ds_read_b64
     double d = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(lds_lut) + code);
@@ -466,13 +468,20 @@ static_assert(sizeof(ScanArgs) <= 4096, "kernarg segment size");
 // SM 0: ScanSimulator2D.scan(pose, None); 1: the scan of a step (noise, iTTC flag; env_kernel follows); 2: the same with
 // ordinary instead of streaming stores for the fp32 scan (launches of more than ~300 000 cars, see emit).
 constexpr int SCAN_MIN_WAVES = 8; // waves per SIMD: the kernel is held to their 80-SGPR budget (see the wave -> car mapping)
-template <bool IDENT, bool POW2, int SM>
+// LUTN: slots of the LDS image.  LUT_LDS is the classic form; LUT_COMPACT[i] the compact one (f110_scan_plan.h): always
+// launched as workgroups of one wave, reading the map's compact cell table and image.  The march statements are the same:
+// they see another descriptor and a shorter LUT at LDS address 0.
+static_assert(N_COMPACT == SCAN_COMPACT_N && LUT_COMPACT[0] == SCAN_COMPACT_S[0] && LUT_COMPACT[1] == SCAN_COMPACT_S[1],
+              "the plan's compact sizes are the map tables'");
+template <bool IDENT, bool POW2, int SM, int LUTN = LUT_LDS>
 __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(ScanArgs a)
 {
     constexpr bool STEP = SM >= 1;
+    constexpr bool COMPACT = LUTN != LUT_LDS;
+    static_assert(!COMPACT || (compact_index(LUTN) >= 0 && STEP && IDENT && POW2), "compact forms: the step's scan, kind 3");
     // ONE LDS object, the LUT first: march_ident_pow2 addresses the LUT by the cell codes alone, i.e. the LUT sits at LDS
     // address 0 (the kernel has no other LDS variable; every parity test would fail otherwise)
-    __shared__ struct __attribute__((aligned(16))) { double lut[LUT_LDS]; int chunk0[MAX_CHUNKS]; } s_mem;
+    __shared__ struct __attribute__((aligned(16))) { double lut[LUTN]; int chunk0[MAX_CHUNKS]; } s_mem;
     double *const s_lut = s_mem.lut;
     int *const s_chunk0 = s_mem.chunk0;
     // the same argument block addressed through the kernarg segment (ScanArgs is the only kernel argument): rarely
@@ -484,7 +493,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
 #endif
     const int nb = a.scan.nb;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int wg_single = rare->wg_single;
+    const int wg_single = COMPACT ? 1 : rare->wg_single;
     const int wid = wg_single ? (int)blockIdx.x : (int)blockIdx.x * SCAN_WAVES + wave; // wave-uniform (scalar)
     // wave -> (car, part of its beam queue).  Kept to one extra argument and shifts: this kernel sits at
     // the 80-SGPR budget of 8 waves/SIMD, and a scalar spilled inside the refill loop costs ~3 % of the launch.
@@ -513,18 +522,19 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
 #endif
     const MapDev &md = a.maps[map_slot];
     {   // LDS image of the LUT prepared by the host (slot 0 = dt[-1,-1], last slot = the far marker): 16-B copies
-        const double2 *src = reinterpret_cast<const double2 *>(md.lut_lds);
+        const double2 *src = reinterpret_cast<const double2 *>(COMPACT ? md.lut_lds_c[compact_index(LUTN) & 1] : md.lut_lds);
         double2 *dst = reinterpret_cast<double2 *>(s_lut);
-        for (int i = threadIdx.x; i < LUT_LDS / 2; i += SCAN_THREADS) dst[i] = src[i];
+        for (int i = threadIdx.x; i < LUTN / 2; i += SCAN_THREADS) dst[i] = src[i];
         if (SCAN_WAVES > 1 && wg_single) // (a lone wave copies the other waves' shares too)
             for (int k = 1; k < SCAN_WAVES; k++)
-                for (int i = threadIdx.x + k * WAVE; i < LUT_LDS / 2; i += SCAN_THREADS) dst[i] = src[i];
+                for (int i = threadIdx.x + k * WAVE; i < LUTN / 2; i += SCAN_THREADS) dst[i] = src[i];
     }
     static_assert(MAX_CHUNKS <= WAVE, "one pass of one wave stages the chunk table");
     if ((int)threadIdx.x < ((nb + 63) >> 6)) s_chunk0[threadIdx.x] = a.chunk_beam0[threadIdx.x];
     __syncthreads();
     MapView mv;
-    mv.init(md);
+    if (COMPACT) mv.init(md, md.cells_c[compact_index(LUTN) & 1], compact_off_far(LUTN));
+    else mv.init(md, md.cells, OFF_FAR);
     F110_BOUNDS_ONLY(mv.err = rare->dev_err;)
     if (car >= a.n_cars) return;
     car = car_c; // (from here on the car's index in the shard)

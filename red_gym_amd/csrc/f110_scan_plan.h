@@ -4,6 +4,7 @@
 #include "../../include/f110_hip.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -104,6 +105,94 @@ inline std::vector<StageSpec> scan_stage_list(const std::vector<StageSpec> &over
     return stv;
 }
 
+// The compact form of the step's scan: workgroups of ONE wave, each with its own LDS copy of a LUT image of S slots instead of
+// LUT_LDS (f110_map.h: the cells behind slot S - 1 carry the far marker in a cell table of their own and take the rare path).
+// A map whose road is a few dozen cells wide has a few hundred distinct distances, so the short image loses next to nothing
+// there, and a slot of the CU is free again when ONE car is done instead of two.
+constexpr int SCAN_COMPACT_N = 2;
+constexpr int SCAN_COMPACT_S[SCAN_COMPACT_N] = {256, 512};
+// The rule's constants, all MEASURED (profiles/r24_scan_compact.txt, MI355X).
+//  CAP: a compact form is chosen while the share of the cars' reachable free cells behind its marker is UNDER it.  With no cell
+//   behind the marker (example_map) the forms are 2.3 - 2.6 % faster than the classic one at 65 536 cars; every cell behind it
+//   parks its ray until the next refill, and the bundled tracks re-installed at 0.0625 m lose 5 % at a share of 0.027 (S = 512),
+//   15 % at 0.06 - 0.08 and 53 % at 0.29 (S = 256): about 2 - 2.8 % per 0.01 of share, break-even near 0.01.  0.004 keeps the
+//   interpolated cost (1.1 %) under half the gain.
+//  MIN_CARS: below 32 768 cars the one-wave groups lose (4 096: +1 %, 8 192: +0.6 .. 1.2 %, 16 384: +0.3 .. 0.9 % with S = 256).
+//  One agent per env only: 16 384 x 2 measured 1 % slower with S = 256 (its tail of split cars is twice as long).
+// F110_SCAN_FORM forces a form for tests and A/B runs.
+constexpr double SCAN_COMPACT_CAP = 0.004;
+constexpr int SCAN_COMPACT_MIN_CARS = 32768;
+
+// The smallest S whose share of reachable free cells outside the image is under the cap, or 0 = the classic form.
+// out_share[i]: that share for SCAN_COMPACT_S[i].
+inline int scan_compact_choice(const double *out_share, int n_cars, int agents, double cap = SCAN_COMPACT_CAP,
+                               int min_cars = SCAN_COMPACT_MIN_CARS)
+{
+    if (n_cars < min_cars || agents != 1) return 0;
+    for (int i = 0; i < SCAN_COMPACT_N; i++)
+        if (out_share[i] < cap) return SCAN_COMPACT_S[i];
+    return 0;
+}
+
+// The shares scan_compact_choice reads, from a map's cell codes and the cars' spawn poses.  A ray only crosses free cells and
+// a car that leaves its free component has collided, so until the next reset a car's look-ups stay inside the free cells
+// 8-connected to its spawn cell.  share[i] = the MEAN OVER THE CARS of (cells of the car's component whose code is at or
+// beyond off_far[i]) / (cells of the component): the expected fraction of look-ups behind the marker of SCAN_COMPACT_S[i] if a
+// car's look-ups are spread over its component.  A car off the map or on a cell that is not free never marches and counts 0;
+// a handful of cars jittered off a track weigh what they are.  (The share over ALL free cells of a map cannot serve: the open
+// ground around a track may be most of them and holds next to no car.)
+//   code_at(r, c): the classic cell code of map cell (r, c), 0 <= r < H, 0 <= c < W; free: code > code_zero (distance not 0)
+//   poses: n_cars x (x, y, .), pose_stride doubles apart; cell = floor((x - ox) * rinv), floor((y - oy) * rinv) (origin unrotated)
+template <typename CodeAt>
+void scan_reach_shares(int H, int W, CodeAt code_at, unsigned code_zero, const unsigned *off_far, const double *poses,
+                       int pose_stride, int n_cars, double ox, double oy, double rinv, double *share)
+{
+    std::vector<int> label((size_t)H * W, 0);            // 0: not visited, k > 0: component k - 1
+    std::vector<double> comp_share;                      // [component][SCAN_COMPACT_N]
+    std::vector<int> stack;
+    double sum[SCAN_COMPACT_N] = {};
+    for (int i = 0; i < n_cars; i++) {
+        const double qx = std::floor((poses[(size_t)i * pose_stride] - ox) * rinv), qy = std::floor((poses[(size_t)i * pose_stride + 1] - oy) * rinv);
+        if (!(qx >= 0 && qx < W && qy >= 0 && qy < H)) continue; // (a NaN pose fails the test too)
+        const int r0 = (int)qy, c0 = (int)qx;
+        if (!(code_at(r0, c0) > code_zero)) continue;
+        int &l0 = label[(size_t)r0 * W + c0];
+        if (!l0) {   // a component no earlier car stood in: flood fill it
+            const int id = (int)(comp_share.size() / SCAN_COMPACT_N) + 1;
+            size_t n_free = 0, n_out[SCAN_COMPACT_N] = {};
+            l0 = id;
+            stack.push_back(r0 * W + c0);
+            while (!stack.empty()) {
+                const int at = stack.back(), r = at / W, c = at % W;
+                stack.pop_back();
+                const unsigned code = code_at(r, c);
+                n_free++;
+                for (int k = 0; k < SCAN_COMPACT_N; k++) n_out[k] += code >= off_far[k];
+                for (int dr = -1; dr <= 1; dr++)
+                    for (int dc = -1; dc <= 1; dc++) {
+                        const int rr = r + dr, cc = c + dc;
+                        if (rr < 0 || rr >= H || cc < 0 || cc >= W || label[(size_t)rr * W + cc] || !(code_at(rr, cc) > code_zero)) continue;
+                        label[(size_t)rr * W + cc] = id;
+                        stack.push_back(rr * W + cc);
+                    }
+            }
+            for (int k = 0; k < SCAN_COMPACT_N; k++) comp_share.push_back((double)n_out[k] / (double)n_free);
+        }
+        for (int k = 0; k < SCAN_COMPACT_N; k++) sum[k] += comp_share[(size_t)(label[(size_t)r0 * W + c0] - 1) * SCAN_COMPACT_N + k];
+    }
+    for (int k = 0; k < SCAN_COMPACT_N; k++) share[k] = n_cars > 0 ? sum[k] / (double)n_cars : 1.0;
+}
+
+// F110_SCAN_FORM: "classic" -> 0, "compact256" -> 256, "compact512" -> 512; unset or anything else -> -1 (the rule decides)
+inline int scan_form_override(const char *v)
+{
+    if (!v) return -1;
+    if (!strcmp(v, "classic")) return 0;
+    if (!strcmp(v, "compact256")) return 256;
+    if (!strcmp(v, "compact512")) return 512;
+    return -1;
+}
+
 struct ScanPlanIn {
     int n_cars, agents, num_beams;      // of the whole scan: the shard's cars, or f110_scan's poses (one agent each)
     const std::vector<StageSpec> *stages; // f110_set_scan_stages override (empty: the built-in choice)
@@ -111,6 +200,7 @@ struct ScanPlanIn {
     const char *stores;                 // F110_SCAN_STORES: "plain", anything else (streaming stores) or NULL (unset)
     bool multi, wg_single;              // the scan reads a map per env; neighbouring cars on different maps (f110_assign_maps)
     int kind;                           // AND over the used map slots of their kinds (ScanLaunch::kind)
+    int compact = 0;                    // S of the compact form the map offers and the rule (or the override) chose, 0: classic
 };
 
 struct ScanLaunch {
@@ -121,6 +211,7 @@ struct ScanLaunch {
     int grid, block;
     bool wg_single, order, events;      // workgroups of one wave; f110_set_scan_order applies (not on a map per env: a
                                         // workgroup stages one LUT); carries the event pair
+    int lut;                            // 0: the classic instantiation (LUT_LDS slots); S: the compact one of S slots
 };
 
 // The launches of one scan in launch order, or an error code (message through fail) where they would break what scan_kernel
@@ -139,7 +230,9 @@ int plan_scan(const ScanPlanIn &in, EnvKind env_kind, std::vector<ScanLaunch> &o
         if (split)
             for (e1 = e0 + 1; e1 < num_envs && env_kind(e1) == l.kind; e1++) {}
         l.car_base = e0 * in.agents; l.n_cars = (e1 - e0) * in.agents;
-        l.wg_single = in.multi && in.wg_single; l.order = in.step && !in.multi; l.events = in.step && e0 == 0;
+        // the compact form: the step's scan of a single map, origin unrotated and resolution 2^k (the written-out march)
+        l.lut = in.step && !in.multi && in.kind == 3 ? in.compact : 0;
+        l.wg_single = (in.multi && in.wg_single) || l.lut != 0; l.order = in.step && !in.multi; l.events = in.step && e0 == 0;
         const std::vector<StageSpec> stv = scan_stage_list(*in.stages, l.n_cars, in.agents, in.num_beams);
         // what the kernel assumes about the stage list, checked here where a mistake costs an error code instead of a
         // wave -> car mapping that runs off the argument block

@@ -96,6 +96,75 @@ static int check_scan_args(const ScanArgs &a, const char *who)
 #define SCAN_KERNELS(SM) {(const void *)&scan_kernel<false, false, SM>, (const void *)&scan_kernel<true, false, SM>, \
                           (const void *)&scan_kernel<false, true, SM>, (const void *)&scan_kernel<true, true, SM>}
 static const void *const scan_kernels[3][4] = {SCAN_KERNELS(0), SCAN_KERNELS(1), SCAN_KERNELS(2)};
+// the compact forms (kind 3, the step's scan only) by [compact_index(S)][SM - 1]
+static const void *const scan_kernels_compact[N_COMPACT][2] = {
+    {(const void *)&scan_kernel<true, true, 1, LUT_COMPACT[0]>, (const void *)&scan_kernel<true, true, 2, LUT_COMPACT[0]>},
+    {(const void *)&scan_kernel<true, true, 1, LUT_COMPACT[1]>, (const void *)&scan_kernel<true, true, 2, LUT_COMPACT[1]>}};
+
+// The form of the step's scan on the handle's single map: what F110_SCAN_FORM forces (read once per process; tests and A/B
+// runs), else what the eligibility rule picks from the map's recorded shares.  A map without compact tables stays classic
+// whatever is asked.  The inputs only change with the map, whose install moves f110_launch_epoch.
+static int scan_form_forced() { static const int forced = scan_form_override(getenv("F110_SCAN_FORM")); return forced; }
+static int scan_form(const f110_handle *h, int n_cars)
+{
+    const int forced = scan_form_forced();
+    const f110_handle::MapSlot &m = h->slots[0];
+    if (!m.compact || h->multi || !(h->ident && h->pow2)) return 0;
+    if (forced >= 0) return forced;
+    return m.reach_known ? scan_compact_choice(m.reach_out, n_cars, h->cfg.num_agents) : 0;
+}
+
+// The shares the rule reads (scan_reach_shares, f110_scan_plan.h), learnt from the spawn poses of a reset of all envs: once per
+// map install, and only where the answer is used -- a handle the rule can route, no override.  An explicit call, not a part of
+// f110_reset: it synchronises the stream, copies the poses and the cell table to the host and floods the cars' free components
+// there (tens of ms on a 1 600 x 1 600 map), none of which f110_reset may do.  Anything that fails here (a stream being
+// captured, host memory) leaves the shares unlearnt, i.e. the classic form.
+extern "C" int f110_scan_form_learn(f110_handle *h, const double *poses_dev, void *stream)
+{
+    if (!h || !poses_dev) return fail(F110_E_INVALID, "f110_scan_form_learn: null argument");
+    if (!h->has_map) return fail(F110_E_NOMAP, "Map is not set for scan simulator.");
+    f110_handle::MapSlot &m = h->slots[0];
+    const int N = h->cfg.num_envs * h->cfg.num_agents;
+    const double none[N_COMPACT] = {}; // (a handle on which not even a map without a cell behind the markers would be routed: nothing to learn)
+    if (!m.compact || m.reach_known || h->multi || !(h->ident && h->pow2) || scan_form_forced() >= 0 ||
+        scan_compact_choice(none, N, h->cfg.num_agents) == 0)
+        return F110_OK;
+    if (int rc = check_device(h, "f110_scan_form_learn")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return F110_OK; }
+    if (cap != hipStreamCaptureStatusNone) return F110_OK;
+    try {
+        std::vector<double> poses((size_t)N * 3);
+        std::vector<uint16_t> cells(m.d_cells.size());
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy(poses.data(), poses_dev, poses.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cells.data(), m.d_cells.get(), cells.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        const MapDev &d = m.dev;
+        const int Hp = map_rows_padded(d.H);
+        const unsigned off_far[N_COMPACT] = {compact_off_far(LUT_COMPACT[0]), compact_off_far(LUT_COMPACT[1])};
+        scan_reach_shares(d.H, d.W, [&](int r, int c) { return (unsigned)cells[cell_elem(r, c, Hp)]; }, cell_code(0), off_far,
+                          poses.data(), 3, N, d.ox, d.oy, d.rinv, m.reach_out);
+    } catch (const std::bad_alloc &) {
+        return F110_OK;
+    }
+    m.reach_known = true;
+    h->epoch++; // the form of the next launches may differ from the one a captured step froze
+    return F110_OK;
+}
+
+extern "C" int f110_scan_form_info(f110_handle *h, int32_t n_cars, int32_t *form, double *out_share)
+{
+    if (!h || !form || !out_share || n_cars < 1) return fail(F110_E_INVALID, "f110_scan_form_info: bad arguments");
+    if (!h->has_map) return fail(F110_E_NOMAP, "Map is not set for scan simulator.");
+    const f110_handle::MapSlot &m = h->slots[0];
+    *form = scan_form(h, n_cars);
+    for (int i = 0; i < N_COMPACT; i++) {
+        out_share[i] = m.compact ? m.compact_out[i] : 1.0;
+        out_share[N_COMPACT + i] = m.reach_known ? m.reach_out[i] : -1.0;
+    }
+    return F110_OK;
+}
 
 // The scan of `a` -- the step's when a.state is set, else f110_scan's -- as f110_scan_plan.h plans it.  ev0 / ev1 (measurement
 // aid, may be null) ride on the step's first launch: start / stop events attached to the dispatch itself, which costs less than
@@ -109,6 +178,7 @@ static int run_scan(const f110_handle *h, const ScanArgs &a, const Sink &k, hipE
     ScanPlanIn in;
     in.n_cars = a.n_cars; in.agents = a.agents; in.num_beams = a.scan.nb; in.stages = &h->stages; in.step = a.state != nullptr;
     in.stores = stores_env; in.multi = a.env_map != nullptr; in.wg_single = h->wg_single; in.kind = h->ident | h->pow2 << 1;
+    in.compact = in.step && !in.multi ? scan_form(h, a.n_cars) : 0;
     std::vector<ScanLaunch> plan;
     if (int rc = plan_scan(in, [h](int env) { const f110_handle::MapSlot &m = h->slots[h->h_env_map[env]]; return m.ident | m.pow2 << 1; }, plan))
         return rc;
@@ -116,7 +186,16 @@ static int run_scan(const f110_handle *h, const ScanArgs &a, const Sink &k, hipE
         ScanArgs s = a;
         s.car_base = l.car_base; s.n_cars = l.n_cars; s.wg_single = l.wg_single; s.order = l.order ? h->scan_order : nullptr;
         s.n_stages = l.n_stages; memcpy(s.stage_cars, l.stage_cars, sizeof(s.stage_cars)); memcpy(s.stage_log2w, l.stage_log2w, sizeof(s.stage_log2w));
-        if (int rc = emit(k, scan_kernels[l.sm][l.kind], dim3(l.grid), dim3(l.block), 0, s, l.events ? ev0 : nullptr,
+        const void *func = scan_kernels[l.sm][l.kind];
+        if (l.lut) {
+            // the compact instantiation dereferences the map's compact tables without a test of its own
+            const int ci = compact_index(l.lut);
+            const MapDev &m = h->slots[0].dev;
+            if (ci < 0 || l.sm < 1 || l.kind != 3 || !m.cells_c[ci] || !m.lut_lds_c[ci])
+                return fail(F110_E_INVALID, "scan launch: compact form %d without its tables (kind %d, sm %d)", l.lut, l.kind, l.sm);
+            func = scan_kernels_compact[ci][l.sm - 1];
+        }
+        if (int rc = emit(k, func, dim3(l.grid), dim3(l.block), 0, s, l.events ? ev0 : nullptr,
                           l.events ? ev1 : nullptr))
             return rc;
     }

@@ -502,6 +502,10 @@ class Engine(object):
         if self._noise_floor > 0:
             self._set_noise_floor(0)       # cars at row 0 again: the rows below the floor are produced anew
         self.ready_noise(may_raise_floor=False)
+        if mask is None and not self._in_capture:
+            # a reset of all envs: the scan's form may follow where the cars stand (returns at once unless this handle can be
+            # routed and the map's shares are not known yet; then it synchronises, once per map install)
+            _lib.check(self.lib.f110_scan_form_learn(self._h, _ptr(poses), self._stream()))
         _lib.check(self.lib.f110_reset(self._h, _ptr(poses), _ptr(mask), self._stream()))
         self.host_steps_bound += 1
         self._keep = (poses, mask)  # keep inputs alive until the stream has consumed them
@@ -741,6 +745,15 @@ class Engine(object):
         e = C.c_int64(0)
         _lib.check(self.lib.f110_launch_epoch(self._h, C.byref(e)))
         return e.value
+
+    def scan_form(self, n_cars=None):
+        """(S, shares): the form the step's scan of n_cars cars (default: the engine's) launches -- 0 classic, 256 / 512 compact
+        -- and the shares of free cells behind the 256- and the 512-slot marker: over the whole map, then over the cells the
+        cars can reach (-1.0 until a reset of all envs has learnt them; f110_scan_form_info)."""
+        form, share = C.c_int32(0), (C.c_double * 4)()
+        n = self.N if n_cars is None else int(n_cars)
+        _lib.check(self.lib.f110_scan_form_info(self._h, n, C.byref(form), share))
+        return form.value, tuple(share)
 
     # ------------------------------------------------------------------ measurement aid
     def profile_begin(self, max_launches, every=1):
