@@ -341,6 +341,13 @@ int f110_launch_epoch(f110_handle *h, int64_t *epoch);
  * 64 MB, a failed allocation, a slot other than 0), then the learnt ones (-1.0 each while not learnt). */
 int f110_scan_form_learn(f110_handle *h, const double *poses_dev, void *stream);
 int f110_scan_form_info(f110_handle *h, int32_t n_cars, int32_t *form, double *out_share);
+/* The fp32 rows of the step's scan (performance only).  The compact form of 256 slots leaves 2 816 B of a workgroup's share of
+ * the LDS idle; with an fp32 output it stages the results of the last 11 of a wave's 64-beam chunks there and writes them out
+ * as whole chunks when its march has ended, instead of one scattered dword per finished beam (scan_rowbuf_plan in
+ * csrc/f110_scan_plan.h).  The environment variable F110_SCAN_ROWS = lds | direct, read once per process, overrides the rule
+ * (tests, A/B runs); neither value changes which form is launched.
+ * f110_scan_rows_info: *lds = 1 where a step of n_cars cars with an fp32 output stages its rows now, else 0. */
+int f110_scan_rows_info(f110_handle *h, int32_t n_cars, int32_t *lds);
 
 /* The step as a HIP graph the library builds itself, for callers without a capturing framework and as the reference
  * point for framework captures: F110_GRAPH_NODES = one kernel node per kernel of f110_step(actions_dev), chained

@@ -5,6 +5,8 @@
 #include "f110_map.h"
 #include "f110_scan_plan.h"
 
+#include <type_traits>
+
 #pragma clang fp contract(off)
 
 namespace f110 {
@@ -462,8 +464,8 @@ static_assert(sizeof(ScanArgs) <= 4096, "kernarg segment size");
 
 // One wavefront per car.  Lanes own rays; a finished ray idles (its lookups return 0.0) until at least REFILL_MIN_IDLE lanes are idle, then every idle
 // lane (a) finishes its previous beam -- noise, iTTC candidate test, fp32/fp64 store --
-// and (b) takes the next beam of the car.  No LDS staging of the scan: the only LDS
-// use is the 8 KiB distance LUT shared by the workgroup, so occupancy is register-bound.
+// and (b) takes the next beam of the car.  No LDS staging of the scan but ROWBUF's (below): the only other LDS
+// use is the distance LUT shared by the workgroup (8 KiB in the classic form), so occupancy is register-bound.
 // STEP: full env step (noise + iTTC + state update); false: ScanSimulator2D.scan(pose, None).
 // SM 0: ScanSimulator2D.scan(pose, None); 1: the scan of a step (noise, iTTC flag; env_kernel follows); 2: the same with
 // ordinary instead of streaming stores for the fp32 scan (launches of more than ~300 000 cars, see emit).
@@ -473,17 +475,27 @@ constexpr int SCAN_MIN_WAVES = 8; // waves per SIMD: the kernel is held to their
 // they see another descriptor and a shorter LUT at LDS address 0.
 static_assert(N_COMPACT == SCAN_COMPACT_N && LUT_COMPACT[0] == SCAN_COMPACT_S[0] && LUT_COMPACT[1] == SCAN_COMPACT_S[1],
               "the plan's compact sizes are the map tables'");
-template <bool IDENT, bool POW2, int SM, int LUTN = LUT_LDS>
+// ROWBUF (LUTN == 256 only): the fp32 results of the wave's last SCAN_ROWBUF_CHUNKS chunk positions are staged in LDS behind
+// the LUT and the chunk table and written out as whole chunks when the march has ended (f110_scan_plan.h: scan_rowbuf_plan).
+template <int LUTN> struct __attribute__((aligned(16))) ScanLds { double lut[LUTN]; int chunk0[MAX_CHUNKS]; };
+template <int LUTN> struct __attribute__((aligned(16))) ScanLdsRows { double lut[LUTN]; int chunk0[MAX_CHUNKS]; float rows[SCAN_ROWBUF_CHUNKS * 64]; };
+static_assert(sizeof(ScanLds<SCAN_ROWBUF_LUT>) == SCAN_ROWBUF_BASE && sizeof(ScanLdsRows<SCAN_ROWBUF_LUT>) <= SCAN_LDS_PER_GROUP,
+              "32 one-wave workgroups with a row buffer each fit a CU's LDS");
+template <bool DIRECT> struct EmitTag { static constexpr bool direct = DIRECT; };
+template <bool IDENT, bool POW2, int SM, int LUTN = LUT_LDS, bool ROWBUF = false>
 __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(ScanArgs a)
 {
     constexpr bool STEP = SM >= 1;
     constexpr bool COMPACT = LUTN != LUT_LDS;
     static_assert(!COMPACT || (compact_index(LUTN) >= 0 && STEP && IDENT && POW2), "compact forms: the step's scan, kind 3");
+    static_assert(!ROWBUF || LUTN == SCAN_ROWBUF_LUT, "the row buffer: the compact form of 256 slots");
     // ONE LDS object, the LUT first: march_ident_pow2 addresses the LUT by the cell codes alone, i.e. the LUT sits at LDS
     // address 0 (the kernel has no other LDS variable; every parity test would fail otherwise)
-    __shared__ struct __attribute__((aligned(16))) { double lut[LUTN]; int chunk0[MAX_CHUNKS]; } s_mem;
+    __shared__ typename std::conditional<ROWBUF, ScanLdsRows<LUTN>, ScanLds<LUTN>>::type s_mem;
     double *const s_lut = s_mem.lut;
     int *const s_chunk0 = s_mem.chunk0;
+    float *s_rows = nullptr;
+    if constexpr (ROWBUF) s_rows = s_mem.rows;
     // the same argument block addressed through the kernarg segment (ScanArgs is the only kernel argument): rarely
     // needed fields are re-read through it where they are used instead of being held in SGPRs for the whole kernel
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -539,10 +551,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
     if (car >= a.n_cars) return;
     car = car_c; // (from here on the car's index in the shard)
     // this wave's slice of the car's beam queue: chunk positions part, part+wpc, ...
-    const int nch = (nb + 63) >> 6;
-    const int my_chunks = nch > part ? (nch - part + wpc - 1) >> lg : 0;
-    const int owns_last = my_chunks > 0 && ((nch - 1) & (wpc - 1)) == part;
-    const int nbl = my_chunks * 64 - (owns_last ? nch * 64 - nb : 0); // beams of this wave
+    const int nbl = scan_rowbuf_plan(nb, lg, part).nbl; // beams of this wave
     if (a.reset_only && !a.pending_reset[env_c]) return; // (car == car_c here: the waves past the last car have left)
 
     const double px = a.pose_src[(size_t)car * a.pose_stride];
@@ -578,7 +587,12 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
 
     // finishing stage of one beam: clamp (laser_models.py:143-144), noise (:450-452),
     // stores, iTTC (:189-217).  nzv: noise of the beam, loaded by the caller ahead of time.
-    auto emit = [&](int i, double tot, double nzv) {
+    // ROWBUF: the refill passes `i` = beam | queue position << 12 (both below 4 096) and the beams at or behind the wave's
+    // first staged position go to the row buffer; tag.direct (the d0 loop below): a plain beam, always stored directly.
+    auto emit = [&](auto tag, int i, double tot, double nzv) {
+        constexpr bool STAGING = ROWBUF && !decltype(tag)::direct;
+        int kq = 0;
+        if (STAGING) { kq = i >> 12; i &= 4095; }
 #if defined(F110_BOUNDS)
         F110_BCHK((unsigned)i < (unsigned)nb, BT_SCAN_STORE, rare->dev_err);
         if ((unsigned)i >= (unsigned)nb) return;
@@ -593,9 +607,26 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
         // partial lines reach the HBM un-merged; 65 536: 0.683 / 0.654, 262 144: 2.476 / 2.459 -- so the host picks the
         // instantiation by the launch's size.  A run-time flag tested here costs 3.4 % of the launch.)
         if (o32) {
-            float *q = reinterpret_cast<float *>(reinterpret_cast<char *>(o32) + (size_t)((unsigned)i * 4u));
-            if (SM == 2) *q = (float)v;
-            else __builtin_nontemporal_store((float)v, q);
+            bool staged = false;
+            if (STAGING) {
+                int n = nbl;
+                asm volatile("" : "+s"(n)); // (the first staged position is formed here, not held in a scalar register across the march)
+                const int k0 = scan_rowbuf_k0(n);
+                staged = kq >= k0;
+                if (staged) {
+                    unsigned off = scan_rowbuf_offset(kq, k0);
+#if defined(F110_BOUNDS)
+                    F110_BCHK(off < (unsigned)(SCAN_ROWBUF_CHUNKS * 256) && ((kq ^ i) & 63) == 0, BT_SCAN_STORE, rare->dev_err);
+                    if (off >= (unsigned)(SCAN_ROWBUF_CHUNKS * 256)) off = 0u;
+#endif
+                    *reinterpret_cast<float *>(reinterpret_cast<char *>(s_rows) + off) = (float)v;
+                }
+            }
+            if (!staged) {
+                float *q = reinterpret_cast<float *>(reinterpret_cast<char *>(o32) + (size_t)((unsigned)i * 4u));
+                if (SM == 2) *q = (float)v;
+                else __builtin_nontemporal_store((float)v, q);
+            }
         }
         if (o64) {
             double *q64 = reinterpret_cast<double *>(reinterpret_cast<char *>(o64) + (size_t)((unsigned)i * 8u));
@@ -640,7 +671,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
             F110_BCHK((unsigned)i < (unsigned)nb, BT_NOISE_BEAM, rare->dev_err);
             if ((unsigned)i >= (unsigned)nb) i = 0;
 #endif
-            emit(i, d0, STEP ? ns[i] : 0.0);
+            emit(EmitTag<true>(), i, d0, STEP ? ns[i] : 0.0);
         }
     } else {
         const double td = (double)a.scan.theta_dis;
@@ -708,7 +739,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
                 if ((unsigned)ti >= (unsigned)a.scan.cs_len) ti = 0;
 #endif
                 const double2 cs = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(a.scan.cs) + (size_t)((unsigned)ti * 16u)); // second round trip, overlapped with emit()
-                if (beam >= 0) emit(beam, total, nzv);
+                if (beam >= 0) emit(EmitTag<false>(), beam, total, nzv);
                 beam = -1;
                 c = cs.x; // (every idle lane: one that takes no beam never marches again, and the far look-ups are finished above)
                 s = cs.y;
@@ -716,7 +747,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
                     x = px + d0 * c;
                     y = py + d0 * s;
                     total = d0;
-                    beam = b;
+                    beam = ROWBUF ? b | (k << 12) : b;
                     nz = nsv;
                     active = true;
                 }
@@ -768,6 +799,23 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
                 }
                 nact = __popcll(vote(active));
             } while (nact > go);
+        }
+        // ---- the staged chunks, whole: slot t holds queue position j0 + t, lane l its beam chunk start + l.  Every beam of the
+        // wave has been emitted (the loop ends when no ray marches and none is left to take), and a workgroup is one wave: its
+        // own LDS writes are ordered before these reads without a barrier.
+        if (ROWBUF && o32) {
+            const ScanRowbufPlan rp = scan_rowbuf_plan(nb, lg, part);
+            for (int t = 0; t < rp.n_slots; t++) {
+                F110_BCHK(((rp.j0 + t) << lg) + part < MAX_CHUNKS, BT_CHUNK_ORDER, rare->dev_err);
+                const int i = s_chunk0[(((rp.j0 + t) << lg) + part) & (MAX_CHUNKS - 1)] + lane;
+                const float f = s_rows[t * 64 + lane];
+                if (i < nb) {
+                    F110_BCHK(i >= 0 && t < SCAN_ROWBUF_CHUNKS, BT_SCAN_STORE, rare->dev_err);
+                    float *q = reinterpret_cast<float *>(reinterpret_cast<char *>(o32) + (size_t)((unsigned)i * 4u));
+                    if (SM == 2) *q = f;
+                    else __builtin_nontemporal_store(f, q);
+                }
+            }
         }
     }
     const ScanArgs *ra = rare;

@@ -183,6 +183,60 @@ void scan_reach_shares(int H, int W, CodeAt code_at, unsigned code_zero, const u
     for (int k = 0; k < SCAN_COMPACT_N; k++) share[k] = n_cars > 0 ? sum[k] / (double)n_cars : 1.0;
 }
 
+// The row buffer of the compact form with S = 256 (scan_kernel<.., 256, true>).  Its workgroup of one wave uses 2 304 B of LDS for
+// the LUT image and the chunk table; with 32 workgroups on a CU, SCAN_LDS_PER_GROUP are there for each, and the rest holds a
+// fixed set of the wave's 64-beam chunks as fp32: the LAST SCAN_ROWBUF_CHUNKS positions of its queue (the short rays; the
+// long rays of the first positions keep the direct store).  A finished beam of a staged chunk is written to LDS instead of to
+// its scattered dword of the row, and the wave writes the staged chunks out as whole 256-B pieces once its march has ended.
+// Nothing moves: no slot is re-bound, no counter kept (profiles/r25_scan_rowbuf.txt).
+constexpr int SCAN_LDS_PER_CU = 163840, SCAN_GROUPS_PER_CU = 32;
+constexpr int SCAN_LDS_PER_GROUP = SCAN_LDS_PER_CU / SCAN_GROUPS_PER_CU;                        // 5 120 B
+constexpr int SCAN_ROWBUF_LUT = 256;                                                             // the form that has the room
+constexpr int SCAN_ROWBUF_BASE = SCAN_ROWBUF_LUT * 8 + MAX_CHUNKS * 4;                           // LUT image + chunk table
+constexpr int SCAN_ROWBUF_CHUNKS = (SCAN_LDS_PER_GROUP - SCAN_ROWBUF_BASE) / (64 * 4);           // 11 chunks = 704 beams
+static_assert(SCAN_ROWBUF_CHUNKS >= 1 && SCAN_ROWBUF_BASE + SCAN_ROWBUF_CHUNKS * 256 <= SCAN_LDS_PER_GROUP, "row buffer within a group's LDS");
+
+#if defined(__HIPCC__)
+#define F110_PLAN_HD __host__ __device__
+#else
+#define F110_PLAN_HD
+#endif
+// The slice of a car's beam queue that wave `part` of 2^lg marches -- chunk positions part, part + 2^lg, ... of the
+// ceil(nb / 64) chunks, wave-local position j = 0 .. my_chunks - 1 -- and what of it is staged: positions j0 .. my_chunks - 1
+// in slots 0 .. n_slots - 1 (slot = j - j0).  nbl: beams of the wave (the car's last chunk may be short).
+struct ScanRowbufPlan { int my_chunks, nbl, j0, n_slots; };
+F110_PLAN_HD inline ScanRowbufPlan scan_rowbuf_plan(int nb, int lg, int part)
+{
+    const int wpc = 1 << lg, nch = (nb + 63) >> 6;
+    ScanRowbufPlan p;
+    p.my_chunks = nch > part ? (nch - part + wpc - 1) >> lg : 0;
+    const int owns_last = p.my_chunks > 0 && ((nch - 1) & (wpc - 1)) == part;
+    p.nbl = p.my_chunks * 64 - (owns_last ? nch * 64 - nb : 0);
+    p.j0 = p.my_chunks > SCAN_ROWBUF_CHUNKS ? p.my_chunks - SCAN_ROWBUF_CHUNKS : 0;
+    p.n_slots = p.my_chunks - p.j0;
+    return p;
+}
+// First staged position of the wave's queue (64 * j0) from its beam count alone: what scan_kernel recomputes where it needs it.
+F110_PLAN_HD inline int scan_rowbuf_k0(int nbl)
+{
+    const int k0 = ((nbl + 63) & ~63) - SCAN_ROWBUF_CHUNKS * 64;
+    return k0 > 0 ? k0 : 0;
+}
+// Byte offset in the row buffer of queue position k >= k0.  The beam at position k is chunk start + (k & 63) and chunk starts
+// are multiples of 64 (set_beam_order), so this is slot (k >> 6) - j0, dword (beam & 63): (j - j0) * 256 + (beam & 63) * 4.
+F110_PLAN_HD inline unsigned scan_rowbuf_offset(int k, int k0) { return (unsigned)(k - k0) * 4u; }
+// F110_SCAN_ROWS: "lds" -> 1, "direct" -> 0; unset or anything else -> -1 (the rule decides)
+inline int scan_rows_override(const char *v)
+{
+    if (!v) return -1;
+    if (!strcmp(v, "lds")) return 1;
+    if (!strcmp(v, "direct")) return 0;
+    return -1;
+}
+// The rule: rows are staged exactly when the compact form of 256 slots is launched with an fp32 output (measured:
+// profiles/r25_scan_rowbuf.txt).  S = 512 has 768 B to spare and the classic form none.
+inline bool scan_rowbuf_choice(int lut, bool has_f32, int forced) { return lut == SCAN_ROWBUF_LUT && has_f32 && forced != 0; }
+
 // F110_SCAN_FORM: "classic" -> 0, "compact256" -> 256, "compact512" -> 512; unset or anything else -> -1 (the rule decides)
 inline int scan_form_override(const char *v)
 {
@@ -201,6 +255,8 @@ struct ScanPlanIn {
     bool multi, wg_single;              // the scan reads a map per env; neighbouring cars on different maps (f110_assign_maps)
     int kind;                           // AND over the used map slots of their kinds (ScanLaunch::kind)
     int compact = 0;                    // S of the compact form the map offers and the rule (or the override) chose, 0: classic
+    bool out_f32 = false;               // the scan writes an fp32 row
+    int rows = -1;                      // scan_rows_override(F110_SCAN_ROWS)
 };
 
 struct ScanLaunch {
@@ -212,6 +268,7 @@ struct ScanLaunch {
     bool wg_single, order, events;      // workgroups of one wave; f110_set_scan_order applies (not on a map per env: a
                                         // workgroup stages one LUT); carries the event pair
     int lut;                            // 0: the classic instantiation (LUT_LDS slots); S: the compact one of S slots
+    bool rowbuf;                        // the instantiation that stages fp32 rows in LDS (scan_rowbuf_choice)
 };
 
 // The launches of one scan in launch order, or an error code (message through fail) where they would break what scan_kernel
@@ -232,6 +289,7 @@ int plan_scan(const ScanPlanIn &in, EnvKind env_kind, std::vector<ScanLaunch> &o
         l.car_base = e0 * in.agents; l.n_cars = (e1 - e0) * in.agents;
         // the compact form: the step's scan of a single map, origin unrotated and resolution 2^k (the written-out march)
         l.lut = in.step && !in.multi && in.kind == 3 ? in.compact : 0;
+        l.rowbuf = scan_rowbuf_choice(l.lut, in.out_f32, in.rows);
         l.wg_single = (in.multi && in.wg_single) || l.lut != 0; l.order = in.step && !in.multi; l.events = in.step && e0 == 0;
         const std::vector<StageSpec> stv = scan_stage_list(*in.stages, l.n_cars, in.agents, in.num_beams);
         // what the kernel assumes about the stage list, checked here where a mistake costs an error code instead of a

@@ -755,6 +755,12 @@ class Engine(object):
         _lib.check(self.lib.f110_scan_form_info(self._h, n, C.byref(form), share))
         return form.value, tuple(share)
 
+    def scan_rows(self, n_cars=None):
+        """True where the step's scan of n_cars cars (default: the engine's) stages its fp32 rows in LDS (f110_scan_rows_info)."""
+        lds = C.c_int32(0)
+        _lib.check(self.lib.f110_scan_rows_info(self._h, self.N if n_cars is None else int(n_cars), C.byref(lds)))
+        return bool(lds.value)
+
     # ------------------------------------------------------------------ measurement aid
     def profile_begin(self, max_launches, every=1):
         """hipEvent pairs on the scan dispatch of every `every`-th step from now on (f110_profile_begin / _every)."""
