@@ -1,5 +1,5 @@
 """The training loop of the reference's RL consumer (main(), src/SAL.py:975-1019) for many envs at once, everything on the GPU:
-    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps] [auto] [device]
+    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps] [nstep] [auto] [device]
     select_action (the policy on the shaper's bitmap) -> path_actions (SAL's action decode and MPC step, which also hands the raw
     action to the ring) -> step (scan, shaper, the ring's push) -> after update_after steps, every update_every steps, one SACAgent
     update replayed from a graph: the batch is drawn on the device, the losses stay there.  The episodes are kept on the GPU too
@@ -11,7 +11,9 @@ tensor is read (one synchronisation) only where it is printed.  With a trailing 
 (SACAgent(alpha='auto'): its step is part of the replayed graph) and alpha is printed beside the losses.  With a trailing `device`
 the policy's Gaussian draws are made on the device (SACAgent(draws='device'): NumPy's Philox normals per env and call, the fills part of
 the replayed graph, the counters part of state_dict()) and the number of calls per stream is printed at the end.  At the end the actor is saved under the reference's keys, as main()
-saves sac_actor.pth."""
+saves sac_actor.pth.  With nstep > 1 (a seventh number) the targets are built on truncated n-step returns walked through the ring on
+the device (SACAgent(nstep=k)), and the mean span of the last sampled batch is printed beside the losses: below k where episodes end,
+resets intervene or the newest push cuts a walk short."""
 import os
 import sys
 import tempfile
@@ -23,6 +25,7 @@ from red_gym_amd.episodes import REASONS
 arg = lambda i, default: int(sys.argv[i]) if len(sys.argv) > i else default  # noqa: E731
 B, STEPS, BATCH, UPDATE_AFTER, UPDATE_EVERY, MAX_STEPS = arg(1, 64), arg(2, 48), arg(3, 64), arg(4, 16), arg(5, 4), arg(6, 12)
 AD = 16
+NSTEP = int(sys.argv[7]) if len(sys.argv) > 7 and sys.argv[7].isdigit() else 1
 AUTO, DEVICE = 'auto' in sys.argv[7:], 'device' in sys.argv[7:]
 env = F110VecEnv(B, map=workload.EXAMPLE_MAP, num_agents=1, autoreset=True)
 env.shape_rewards()
@@ -32,7 +35,7 @@ env.track_episodes(MAX_STEPS + torch.arange(B, dtype=torch.int32) % 4)   # stagg
 dev, cfg = env.device, env.eng.shaper.cfg
 torch.manual_seed(0)
 agent = SACAgent(action_dim=AD, rows=cfg.rows, cols=cfg.cols, device=dev, **(dict(alpha='auto') if AUTO else {}),
-                 **(dict(draws='device', seed=0) if DEVICE else {}))
+                 **(dict(draws='device', seed=0) if DEVICE else {}), nstep=NSTEP)
 raw = torch.zeros((B, AD), dtype=torch.float64, device=dev)                    # the policy's action, written in place
 obs, reward, done, info = env.reset(torch.as_tensor(workload.spawn_poses(B, 1), device=dev))
 total = torch.zeros((B,), dtype=torch.float64, device=dev)
@@ -47,8 +50,9 @@ for step in range(1, STEPS + 1):
         losses = agent.update_graph()
         updates += 1
         if updates % 4 == 1:
-            print('step %3d, update %2d: losses (actor, critic 1, critic 2) %s%s' % (step, updates, ' '.join('%.6f' % v for v in losses.tolist()),
-                                                                                      ', alpha %.9f' % agent.alpha.item() if AUTO else ''))
+            print('step %3d, update %2d: losses (actor, critic 1, critic 2) %s%s%s' % (
+                step, updates, ' '.join('%.6f' % v for v in losses.tolist()), ', alpha %.9f' % agent.alpha.item() if AUTO else '',
+                ', mean span %.3f of %d' % (agent.sample['span'].double().mean().item(), NSTEP) if NSTEP > 1 else ''))
             count = int(info['episodes_finished'].item())
             rec = {k: v.tolist() for k, v in env.episodes.finished(last=min(count - printed, 4)).items()}   # (a few of the new ones)
             for i in range(len(rec['env'])):

@@ -648,6 +648,36 @@ int f110_replay_locate(f110_handle *h, const int64_t *indices, int32_t n, int64_
  * allocation, no synchronisation.  The handle keeps no draw counter: f110_replay_draw's first_draw stays the caller's host value. */
 int f110_replay_sample(f110_handle *h, uint64_t seed, uint64_t *counter, int32_t n, int64_t *indices, int64_t *s_frame, int64_t *ns_frame,
                        float *a, double *r, uint8_t *d, uint8_t *ok, void *stream);
+/* N-step returns: the truncated, uncorrected n-step return of a stored transition, walked through the ring on the device (the
+ * reference has one-step targets only).  For index = step slot * B + env, c0 is the push f110_replay_locate resolves it to.  The
+ * span is the largest m, 1 <= m <= nstep, such that every push c0 .. c0 + m - 1 is stored (c0 + m - 1 <= count - 1; a push after a
+ * stored push is still in the ring, newer pushes are overwritten later than older ones), each of them has valid[(c0 + k) % T][env]
+ * != 0, and none of c0 .. c0 + m - 2 has done = 1: the walk stops behind a terminal step, in front of an invalid slot (a reset, an
+ * env a masked reset left alone, a chain break at chain_start) and at the newest push.  The episode tracker's LIMIT step is stored
+ * valid with d = 0 and the reset behind it is invalid, so a span ends ON the LIMIT step and bootstraps from the frame after it.
+ * Per row:
+ *   ns_frame  the row of the frame tensor, viewed as [(T + 1) * B, rows, words], that holds the frame after push c0 + m - 1:
+ *             ((c0 + m - 1) % (T + 1)) * B + env (step slots wrap at T, frame slots at T + 1)
+ *   ret       R = r_0; g = gamma; for k = 1 .. m - 1: R = R + g * r_k; g = g * gamma -- fp64, every product and every sum rounded
+ *             on its own (no fused multiply-add)
+ *   discount  g as it stands behind the loop: gamma for m = 1, gamma^m by running products (not pow) otherwise
+ *   d         done of push c0 + m - 1;  span = m (int32)
+ * A row the locate refuses (an index outside 0 .. T * B - 1, a slot no push has reached, an invalid transition) is the zero
+ * transition: ns_frame = -1, ret = 0, d = 0, span = 0 and discount = gamma; f110_replay_sample_nstep also returns s_frame = -1,
+ * a zero action and ok = 0 for it.  With nstep = 1 every output of every row equals f110_replay_locate's / f110_replay_sample's
+ * (ret = r), and discount holds gamma's bits in every row.
+ * f110_replay_nstep: for n indices the caller names (dev int64), one lane per index; one launch.
+ * f110_replay_sample_nstep: f110_replay_sample -- the same draws from the caller's device counter, the same one-lane advance
+ * behind it -- with the walk in the same kernel; a captured call replays with fresh draws.  Two launches.
+ * Both read count on the device, allocate nothing, do not synchronise and use no atomics; all arrays dev, discount and ret [n]
+ * fp64, span [n] int32.  F110_E_INVALID without a launch for nstep outside 1 .. F110_REPLAY_MAX_NSTEP, a gamma that is not
+ * finite, n < 0 or a NULL array.  Kernels of their own: the one-step entries above keep their code and bits. */
+#define F110_REPLAY_MAX_NSTEP 64
+int f110_replay_nstep(f110_handle *h, const int64_t *indices, int32_t n, int32_t nstep, double gamma, int64_t *ns_frame, double *ret, uint8_t *d,
+                      double *discount, int32_t *span, void *stream);
+int f110_replay_sample_nstep(f110_handle *h, uint64_t seed, uint64_t *counter, int32_t n, int32_t nstep, double gamma, int64_t *indices,
+                             int64_t *s_frame, int64_t *ns_frame, float *a, double *ret, uint8_t *d, uint8_t *ok, double *discount, int32_t *span,
+                             void *stream);
 
 /* Episodes: the episode of the reference's training loop (src/SAL.py:986-1015: `obs = env.reset(); ep_reward = 0; for st in
  * range(max_steps): ...; ep_reward += reward; if done: break; print(f"Episode {ep} Reward={ep_reward:.2f}")`) for every env, on
@@ -1102,6 +1132,16 @@ int f110_qhead_forward_alpha_dev(const f110_qhead_config *cfg, const f110_qhead_
                                  float *target, void *stream);
 int f110_sac_actor_loss_alpha_dev(const void *logp, int32_t logp_fp64, const float *qn, const double *alpha, int64_t n, float *loss,
                                   void *grad_logp, float *grad_qn, void *stream);
+/* f110_qhead_forward_rows: f110_qhead_forward -- the same kernel, the same numerics -- with a discount per row in gamma's place, for
+ * targets built on n-step returns (f110_replay_sample_nstep's ret, d and discount): discount [n] dev fp64, and the target's second
+ * line is tv = reward + ((1.0 - done) * discount[b]) * tq.  Where discount[b] holds gamma's bits the row's target is the by-value
+ * entry's, bit for bit.  One entry serves both temperature modes: alpha_dev non-NULL (dev fp64 [1]) is read on the device and wins;
+ * NULL: `alpha` by value, which must then be finite.  The values of discount cannot be checked on the host; a null discount where a
+ * target is asked for, and one on a wrong device, are refused, everything else as f110_qhead_forward refuses it.  The backward pass
+ * does not read the target. */
+int f110_qhead_forward_rows(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const double *reward,
+                            const uint8_t *done, const void *next_log_prob, const double *discount, double alpha, const double *alpha_dev,
+                            float *q, float *qmin, float *target, void *stream);
 
 /* The policy's Gaussian draws: the eps of f110_policyhead_forward (Actor.sample's normal.rsample(), src/SAL.py:414-421) made on the
  * device, so that the one random input of acting and of an update is the library's own, named by numbers a checkpoint can hold.

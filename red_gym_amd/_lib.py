@@ -94,6 +94,7 @@ class ReplayConfig(C.Structure):
 
 REPLAY_FIELDS = ['frames', 'actions', 'rewards', 'dones', 'valid', 'count', 'chain_start', 't_seen', 'last_valid', 'action_in']
 F110_REPLAY_TRIES = 64
+F110_REPLAY_MAX_NSTEP = 64
 
 
 class ReplayBuffers(C.Structure):
@@ -308,6 +309,8 @@ SYMBOLS = {
     'f110_replay_gather': [_VP, _VP, _I32, _VP, _VP, _I32, _D, _VP, _VP, _VP, _VP, _VP],
     'f110_replay_locate': [_VP, _VP, _I32, _VP, _VP, _VP],
     'f110_replay_sample': [_VP, C.c_uint64, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_replay_nstep': [_VP, _VP, _I32, _I32, _D, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_replay_sample_nstep': [_VP, C.c_uint64, _VP, _I32, _I32, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_episodes_validate': [C.POINTER(EpisodesConfig)],
     'f110_episodes_install': [_VP, C.POINTER(EpisodesConfig)],
     'f110_episodes_bind': [_VP, C.POINTER(EpisodesBuffers)],
@@ -348,6 +351,7 @@ SYMBOLS = {
     'f110_temperature_step': [_VP, _VP, _I32, _I64, _VP, _D, _VP],
     'f110_qhead_forward_alpha_dev': [C.POINTER(QheadConfig), C.POINTER(QheadCritics), _VP, _I64, _VP, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP],
     'f110_sac_actor_loss_alpha_dev': [_VP, _I32, _VP, _VP, _I64, _VP, _VP, _VP, _VP],
+    'f110_qhead_forward_rows': [C.POINTER(QheadConfig), C.POINTER(QheadCritics), _VP, _I64, _VP, _VP, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP],
     'f110_gauss_state_bytes': [],
     'f110_gauss_fill': [_VP, _I32, _I64, _I32, _VP, _VP, _I32, _VP],
     'f110_gauss_fill_at': [C.c_uint64, _I32, C.c_uint64, _I64, _I32, _VP, _VP, _VP],

@@ -813,6 +813,58 @@ extern "C" int f110_replay_sample(f110_handle *h, uint64_t seed, uint64_t *count
     return F110_OK;
 }
 
+// what both n-step entries ask of their scalars
+static int replay_nstep_scalars(const char *who, int32_t n, int32_t nstep, double gamma)
+{
+    if (n < 0) return fail(F110_E_INVALID, "%s: n=%d", who, n);
+    if (nstep < 1 || nstep > F110_REPLAY_MAX_NSTEP) return fail(F110_E_INVALID, "%s: nstep %d (1..%d)", who, nstep, F110_REPLAY_MAX_NSTEP);
+    if (!std::isfinite(gamma)) return fail(F110_E_INVALID, "%s: gamma is not finite", who);
+    return F110_OK;
+}
+
+extern "C" int f110_replay_nstep(f110_handle *h, const int64_t *indices, int32_t n, int32_t nstep, double gamma, int64_t *ns_frame, double *ret,
+                                 uint8_t *d_out, double *discount, int32_t *span, void *stream)
+{
+    const char *who = "f110_replay_nstep";
+    if (!h) return fail(F110_E_INVALID, "%s: null handle", who);
+    ReplayNstepArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = replay_ready(h, who, a.ring)) return rc;
+    if (int rc = replay_nstep_scalars(who, n, nstep, gamma)) return rc;
+    if (!indices || !ns_frame || !ret || !d_out || !discount || !span) return fail(F110_E_INVALID, "%s: null argument", who);
+    if (n == 0) return F110_OK;
+    a.idx_in = (const long long *)indices; a.n = n; a.nstep = nstep; a.gamma = gamma;
+    a.ns_frame = (long long *)ns_frame; a.ret = ret; a.d = d_out; a.discount = discount; a.span = span;
+    hipLaunchKernelGGL(replay_nstep_kernel, dim3((unsigned)((n + REPLAY_THREADS - 1) / REPLAY_THREADS)), dim3(REPLAY_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_replay_sample_nstep(f110_handle *h, uint64_t seed, uint64_t *counter, int32_t n, int32_t nstep, double gamma, int64_t *indices,
+                                        int64_t *s_frame, int64_t *ns_frame, float *a_out, double *ret, uint8_t *d_out, uint8_t *ok, double *discount,
+                                        int32_t *span, void *stream)
+{
+    const char *who = "f110_replay_sample_nstep";
+    if (!h) return fail(F110_E_INVALID, "%s: null handle", who);
+    ReplayNstepArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = replay_ready(h, who, a.ring)) return rc;
+    if (int rc = replay_nstep_scalars(who, n, nstep, gamma)) return rc;
+    if (!counter || !indices || !s_frame || !ns_frame || !a_out || !ret || !d_out || !ok || !discount || !span)
+        return fail(F110_E_INVALID, "%s: null argument", who);
+    if ((uintptr_t)counter % 8) return fail(F110_E_INVALID, "%s: the counter is not 8-byte aligned", who);
+    if (n == 0) return F110_OK;
+    a.seed = seed; a.counter = (const unsigned long long *)counter; a.n = n; a.nstep = nstep; a.gamma = gamma;
+    a.idx = (long long *)indices; a.s_frame = (long long *)s_frame; a.ns_frame = (long long *)ns_frame;
+    a.a = a_out; a.ret = ret; a.d = d_out; a.ok = ok; a.discount = discount; a.span = span;
+    hipLaunchKernelGGL(replay_sample_nstep_kernel, dim3((unsigned)((n + REPLAY_THREADS - 1) / REPLAY_THREADS)), dim3(REPLAY_THREADS), 0, (hipStream_t)stream,
+                       a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(replay_counter_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long *)counter, (unsigned long long)n);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
 // ---------------------------------------------------------------- episodes
 // What install refuses, on the struct alone (no handle, no device).
 extern "C" int f110_episodes_validate(const f110_episodes_config *cfg)

@@ -96,10 +96,12 @@ static int qhead_critics(const char *who, const f110_qhead_config *cfg, const f1
     return F110_OK;
 }
 
-// both forward entry points; alpha_dev: where the target's alpha is read on the device, NULL: `alpha`
+// the forward entry points; alpha_dev: where the target's alpha is read on the device, NULL: `alpha`; by_row: the target's discount is
+// read per row from discount_dev [n], else `gamma`
 static int qhead_forward(const char *who, const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n,
                          const double *reward, const uint8_t *done, const void *next_log_prob, double gamma, double alpha, bool by_pointer,
-                         const double *alpha_dev, float *q, float *qmin, float *target, void *stream)
+                         const double *alpha_dev, float *q, float *qmin, float *target, void *stream, bool by_row = false,
+                         const double *discount_dev = nullptr)
 {
     if (int rc = f110_qhead_validate(cfg)) return rc;
     if (n < 0 || n > QH_MAX_ROWS) return fail(F110_E_INVALID, "%s: n=%lld rows (0..%lld)", who, (long long)n, (long long)QH_MAX_ROWS);
@@ -108,15 +110,17 @@ static int qhead_forward(const char *who, const f110_qhead_config *cfg, const f1
     if (target && (!reward || !done || !next_log_prob)) return fail(F110_E_INVALID, "%s: a target needs reward, done and next_log_prob", who);
     if (target && (!std::isfinite(gamma) || !std::isfinite(alpha))) return fail(F110_E_INVALID, "%s: gamma or alpha is not finite", who);
     if (target && by_pointer && !alpha_dev) return fail(F110_E_INVALID, "%s: null alpha", who);
+    if (target && by_row && !discount_dev) return fail(F110_E_INVALID, "%s: null discount", who);
     QheadForwardPlan plan = qhead_forward_plan(*cfg, n);
     QheadArgs &a = plan.a;
     std::vector<DevicePtr> ptrs = {{"action", action}, {"q", q}};
     if (int rc = qhead_critics(who, cfg, p, a, ptrs)) return rc;
     if (target) { ptrs.push_back({"reward", reward}); ptrs.push_back({"done", done}); ptrs.push_back({"next_log_prob", next_log_prob}); ptrs.push_back({"target", target}); }
     if (target && by_pointer) ptrs.push_back({"alpha", alpha_dev});
+    if (target && by_row) ptrs.push_back({"discount", discount_dev});
     if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
     a.action = action; a.q = q; a.qmin = qmin; a.target = target;
-    if (target) { a.reward = reward; a.done = done; a.nlp = next_log_prob; a.gamma = gamma; a.alpha = alpha; a.alpha_dev = by_pointer ? alpha_dev : nullptr; }
+    if (target) { a.reward = reward; a.done = done; a.nlp = next_log_prob; a.gamma = gamma; a.alpha = alpha; a.alpha_dev = by_pointer ? alpha_dev : nullptr; a.discount_dev = by_row ? discount_dev : nullptr; }
     F110_LAUNCH(qhead_forward_kernel, plan.l, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return F110_OK;
@@ -134,6 +138,16 @@ extern "C" int f110_qhead_forward_alpha_dev(const f110_qhead_config *cfg, const 
                                             float *q, float *qmin, float *target, void *stream)
 {
     return qhead_forward("f110_qhead_forward_alpha_dev", cfg, p, action, n, reward, done, next_log_prob, gamma, 0.0, true, alpha, q, qmin, target, stream);
+}
+
+extern "C" int f110_qhead_forward_rows(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const double *reward,
+                                       const uint8_t *done, const void *next_log_prob, const double *discount, double alpha, const double *alpha_dev,
+                                       float *q, float *qmin, float *target, void *stream)
+{
+    // (gamma is unused; 0.0 passes the finiteness check.  A non-null alpha_dev wins, and `alpha` is then not looked at)
+    const bool by_pointer = alpha_dev != nullptr;
+    return qhead_forward("f110_qhead_forward_rows", cfg, p, action, n, reward, done, next_log_prob, 0.0, by_pointer ? 0.0 : alpha, by_pointer, alpha_dev, q,
+                         qmin, target, stream, true, discount);
 }
 
 extern "C" int f110_qhead_backward(const f110_qhead_config *cfg, const f110_qhead_critics *p, const void *action, int64_t n, const float *q,

@@ -153,7 +153,8 @@ static __global__ __launch_bounds__(QH_THREADS) void qhead_forward_kernel(QheadA
                     const double lp = a.act_fp64 ? reinterpret_cast<const double *>(a.nlp)[row] : (double)reinterpret_cast<const float *>(a.nlp)[row];
                     const double alpha = a.alpha_dev ? *a.alpha_dev : a.alpha;      // (uniform in the launch)
                     const double tq = (double)qm - alpha * lp;
-                    const double keep = (1.0 - (double)a.done[row]) * a.gamma;
+                    const double gamma = a.discount_dev ? a.discount_dev[row] : a.gamma;  // (the branch is uniform in the launch)
+                    const double keep = (1.0 - (double)a.done[row]) * gamma;
                     a.target[row] = (float)(a.reward[row] + keep * tq);
                 }
             }

@@ -39,6 +39,7 @@ struct QheadArgs {
     void *grad_action;
     float *partial;                 // workspace [C][slices][H (A + 2) + 1]
     const double *alpha_dev;        // forward, f110_qhead_forward_alpha_dev: the target's alpha is read here; NULL: `alpha` above
+    const double *discount_dev;     // forward, f110_qhead_forward_rows: [n], row b's discount in gamma's place; NULL: `gamma` above
 };
 
 // floats of one (critic, slice) in the workspace: grad_w_act [H][A], grad_b1 [H], grad_w2 [H], grad_b2

@@ -14,6 +14,10 @@
 //   replay_sample_kernel   one lane per draw: the draw, the locate and the gather's tail in one, from a draw counter that lives on the
 //                          device (the caller's), so that a captured sample replays with fresh draws
 //   replay_counter_advance_kernel  one lane: counter += n, behind the sample
+//   replay_nstep_kernel    one lane per index: the truncated n-step return of the transition (replay_walk: up to nstep - 1 dependent
+//                          loads of valid, reward and done, one step slot = n_envs cells apart), for indices the caller names
+//   replay_sample_nstep_kernel  one lane per draw: replay_sample_kernel with the walk behind the locate; both are kernels of their
+//                          own beside the one-step ones, which keep their code
 #pragma once
 #include "../../include/f110_hip.h" // F110_REPLAY_TRIES
 #include "f110_bounds.h"
@@ -193,6 +197,20 @@ struct ReplaySampleArgs {
     uint8_t *d, *ok;                // [n]
 };
 
+struct ReplayNstepArgs {
+    ReplayRing ring;
+    unsigned long long seed;           // the sample form: as ReplaySampleArgs
+    const unsigned long long *counter; // [1]
+    const long long *idx_in;           // [n] the form that takes its indices from the caller
+    int n, nstep;                      // 1 <= nstep <= F110_REPLAY_MAX_NSTEP
+    double gamma;
+    long long *idx, *s_frame, *ns_frame; // [n]; idx and s_frame: the sample form only
+    float *a;                          // [n, action_dim], the sample form only
+    double *ret, *discount;            // [n]
+    uint8_t *d, *ok;                   // [n]; ok: the sample form only
+    int *span;                         // [n]
+};
+
 struct ReplayGatherArgs {
     ReplayRing ring;
     const long long *idx;           // [n]
@@ -347,6 +365,101 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_sample_kernel(Re
     a.r[i] = ok ? g.rewards[id] : 0.0;
     a.d[i] = ok ? g.dones[id] : (uint8_t)0;
     a.ok[i] = ok ? 1 : 0;
+}
+
+// The truncated n-step return of the transition replay_resolve gave as (ok, push c0, env); the contract is include/f110_hip.h's.
+// span m = the pushes c0 .. c0 + m - 1 walked: the walk goes on to push c = c0 + m while m < nstep, push c - 1 was not done, c is
+// stored (c <= count - 1: it is then still in the ring, because c0 is the newest push of its slot and so is every later one) and
+// valid.  ret = r_0 + g r_1 + ..., g the running product of gamma, every product and sum rounded on its own in fp64 (this file
+// compiles with contraction off); discount = g behind the last step (gamma for m = 1); d = done of push c0 + m - 1, and ns_frame
+// the row of its frame after in the frame tensor viewed as [(steps + 1) * n_envs, rows, words].  A refused row is the zero transition
+// with discount = gamma.  The two moduli differ: step slots wrap at `steps`, frame slots at `steps + 1`.
+__device__ inline void replay_walk(const ReplayRing &g, bool ok, long long c0, int env, int nstep, double gamma, long long &ns_frame, double &ret,
+                                   double &discount, uint8_t &d, int &span)
+{
+    ns_frame = -1;
+    ret = 0.0;
+    discount = gamma;
+    d = 0;
+    span = 0;
+    if (!ok) return;
+    const long long count = *g.count;
+    const long long s0 = c0 % g.steps;
+    F110_BCHK(c0 >= 1 && c0 <= count - 1 && s0 >= 0 && s0 < g.steps && env >= 0 && env < g.n_envs, BT_REPLAY, g.dev_err);
+    const size_t cell0 = (size_t)s0 * (size_t)g.n_envs + (size_t)env;
+    double R = g.rewards[cell0], gk = gamma;
+    uint8_t dn = g.dones[cell0];
+    int m = 1;
+    while (m < nstep && dn == 0) {
+        const long long c = c0 + m;
+        if (c > count - 1) break;                       // the newest push ends the span
+        const long long ss = c % g.steps;
+        F110_BCHK(ss >= 0 && ss < g.steps, BT_REPLAY, g.dev_err);
+        const size_t cell = (size_t)ss * (size_t)g.n_envs + (size_t)env;
+        if (g.valid[cell] == 0) break;                  // a reset, an env not stepped, a chain break: the span ends in front of it
+        R = R + gk * g.rewards[cell];
+        gk = gk * gamma;
+        dn = g.dones[cell];
+        m++;
+    }
+    const long long fs = (c0 + m - 1) % (g.steps + 1);
+    F110_BCHK(fs >= 0 && fs <= g.steps, BT_REPLAY, g.dev_err);
+    ns_frame = fs * g.n_envs + env;
+    ret = R;
+    discount = gk;
+    d = dn;
+    span = m;
+}
+
+// one lane per index: the walk from the transition the caller names
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_nstep_kernel(ReplayNstepArgs a)
+{
+    const ReplayRing &g = a.ring;
+    const int i = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (i >= a.n) return;
+    long long c = 0;
+    int env = 0;
+    const bool ok = replay_resolve(g, a.idx_in[i], c, env);
+    long long ns_frame;
+    double ret, discount;
+    uint8_t d;
+    int span;
+    replay_walk(g, ok, c, env, a.nstep, a.gamma, ns_frame, ret, discount, d, span);
+    a.ns_frame[i] = ns_frame;
+    a.ret[i] = ret;
+    a.discount[i] = discount;
+    a.d[i] = d;
+    a.span[i] = span;
+}
+
+// one lane per draw: replay_sample_kernel's draw, frame before and action, then the walk for the frame after, the return, done, the
+// discount and the span.  Every lane reads the counter; nothing in this launch writes it.
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_sample_nstep_kernel(ReplayNstepArgs a)
+{
+    const ReplayRing &g = a.ring;
+    const int i = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (i >= a.n) return;
+    const unsigned long long first = *a.counter;
+    const long long id = replay_pick(g, a.seed, first + (unsigned long long)i);
+    long long c = 0;
+    int env = 0;
+    const bool ok = replay_resolve(g, id, c, env);
+    F110_BCHK(!ok || (id >= 0 && id < g.steps * g.n_envs), BT_REPLAY, g.dev_err);
+    a.idx[i] = id;
+    a.s_frame[i] = ok ? ((c - 1) % (g.steps + 1)) * g.n_envs + env : -1;
+    for (int k = 0; k < g.action_dim; k++)
+        a.a[(size_t)i * (size_t)g.action_dim + (size_t)k] = ok ? g.actions[(size_t)id * (size_t)g.action_dim + (size_t)k] : 0.0f;
+    a.ok[i] = ok ? 1 : 0;
+    long long ns_frame;
+    double ret, discount;
+    uint8_t d;
+    int span;
+    replay_walk(g, ok, c, env, a.nstep, a.gamma, ns_frame, ret, discount, d, span);
+    a.ns_frame[i] = ns_frame;
+    a.ret[i] = ret;
+    a.discount[i] = discount;
+    a.d[i] = d;
+    a.span[i] = span;
 }
 
 static __global__ void replay_counter_advance_kernel(unsigned long long *counter, unsigned long long n)

@@ -62,7 +62,12 @@ def _launch_forward(cfg, pres, w1s, b1s, w2s, b2s, F, action, target_inputs=None
     reward, done, nlp, gamma, alpha = target_inputs if target_inputs is not None else (None, None, None, 0.0, 0.0)
     p = _critics_struct(pres, w1s, b1s, w2s, b2s, F)
     with torch.cuda.device(dev):
-        if torch.is_tensor(alpha):                      # the [1] fp64 device tensor td_target has checked
+        if torch.is_tensor(gamma):                      # the [n] fp64 device tensor td_target has checked: a discount per row
+            by_dev = torch.is_tensor(alpha)
+            _lib.check(lib.f110_qhead_forward_rows(C.byref(cfg), C.byref(p), action.data_ptr(), n, _ptr(reward), _ptr(done), _ptr(nlp), gamma.data_ptr(),
+                                                   0.0 if by_dev else float(alpha), alpha.data_ptr() if by_dev else None, q.data_ptr(), qmin.data_ptr(),
+                                                   _ptr(target), _lib.stream(dev)))
+        elif torch.is_tensor(alpha):                    # the [1] fp64 device tensor td_target has checked
             _lib.check(lib.f110_qhead_forward_alpha_dev(C.byref(cfg), C.byref(p), action.data_ptr(), n, _ptr(reward), _ptr(done), _ptr(nlp),
                                                         float(gamma), alpha.data_ptr(), q.data_ptr(), qmin.data_ptr(), _ptr(target), _lib.stream(dev)))
         else:
@@ -244,8 +249,10 @@ def td_target(feats, next_action, next_log_prob, reward, done, fc1s, fc2s, gamma
     next_log_prob), the last two lines in fp64 and rounded once.  feats, fc1s, fc2s as twin_q's, of the TARGET critics on the next
     state; next_action [n, A] and next_log_prob [n] or [n, 1] of one dtype (fp64 or fp32: the policy head's outputs); reward [n] fp64
     and done [n] uint8 or bool as the ring's sample() returns them.  alpha: a finite number, or a [1] fp64 tensor on the action's
-    device (Temperature.alpha), which the kernel then reads there (f110_qhead_forward_alpha_dev).  C GEMMs plus one launch; dense,
-    segment: as twin_q's."""
+    device (Temperature.alpha), which the kernel then reads there (f110_qhead_forward_alpha_dev).  gamma: a finite number, or an [n]
+    fp64 tensor on the action's device that holds a discount per row (ReplayBuffer.sample_frames_dev's with nstep > 1, beside a reward
+    that is the n-step return): row b's target then takes gamma[b] in gamma's place (f110_qhead_forward_rows, with either kind of
+    alpha); ValueError for another dtype, shape or device.  C GEMMs plus one launch; dense, segment: as twin_q's."""
     who = 'td_target'
     nc, F, A = _linears(who, fc1s, fc2s, feats, next_action)
     n, dev = int(next_action.shape[0]), next_action.device
@@ -258,7 +265,11 @@ def td_target(feats, next_action, next_log_prob, reward, done, fc1s, fc2s, gamma
     import math
     if torch.is_tensor(alpha):
         alpha = alpha_argument(who, alpha, dev)[1]
-    if not (math.isfinite(gamma) and (torch.is_tensor(alpha) or math.isfinite(alpha))):
+    if torch.is_tensor(gamma):
+        if gamma.dtype != torch.float64 or tuple(gamma.shape) != (n,) or gamma.device != dev:
+            raise ValueError('%s: a gamma per row must be a fp64 [%d] tensor on the action\'s device' % (who, n))
+        gamma = gamma.detach().contiguous()
+    if not ((torch.is_tensor(gamma) or math.isfinite(gamma)) and (torch.is_tensor(alpha) or math.isfinite(alpha))):
         raise ValueError('%s: gamma and alpha must be finite' % who)
     with torch.no_grad():
         cfg = validate(fc1s[0].out_features, A, nc, F + A, next_action.dtype == torch.float64)

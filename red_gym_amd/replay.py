@@ -12,6 +12,7 @@ from .consumer import Consumer
 
 DEFAULTS = dict(capacity=1000000, steps=None, action_dim=16)
 TRIES = _lib.F110_REPLAY_TRIES
+MAX_NSTEP = _lib.F110_REPLAY_MAX_NSTEP
 
 
 def make_config(num_envs=1, **cfg):
@@ -72,7 +73,7 @@ def unpack_bitmaps(packed, cols):
 
 
 class ReplayBuffer(Consumer):
-    """The replay buffer of one Engine (f110_replay_install / _bind / _update / _draw / _gather / _locate / _sample).  The ring lives in `buf`:
+    """The replay buffer of one Engine (f110_replay_install / _bind / _update / _draw / _gather / _locate / _sample / _nstep / _sample_nstep).  The ring lives in `buf`:
     frames [T + 1, B, rows, words] int64 (bit-packed), actions [T, B, action_dim] fp32, rewards [T, B] fp64, dones and valid
     [T, B] uint8, count and chain_start [1] int64, t_seen [B] fp64, last_valid [B] uint8 and action_in [B, action_dim] fp32 (what
     the next push stores: F110VecEnv.replay_action).  A transition is named by index = step slot * B + env.  The ring is no part
@@ -194,14 +195,57 @@ class ReplayBuffer(Consumer):
         idx, _ = self.draw(batch_size, seed)
         return self.sample_at(idx, dtype, scale)
 
-    def frames_at(self, indices):
+    def _nstep(self, nstep, gamma):
+        """(nstep, gamma) as the n-step entries take them; ValueError for nstep outside 1 .. MAX_NSTEP, a gamma that is no finite
+        number, and a missing gamma where nstep > 1 (with nstep = 1 no product is formed and gamma only fills `discount`)."""
+        import math
+        if isinstance(nstep, bool) or not isinstance(nstep, int) or not 1 <= nstep <= MAX_NSTEP:
+            raise ValueError('replay: nstep %r (an int in 1..%d)' % (nstep, MAX_NSTEP))
+        if gamma is None and nstep > 1:
+            raise ValueError('replay: nstep = %d needs a gamma' % nstep)
+        if gamma is None:
+            gamma = 1.0
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma):
+            raise ValueError('replay: gamma %r is no finite number' % (gamma,))
+        return nstep, float(gamma)
+
+    def nstep_at(self, indices, nstep, gamma):
+        """f110_replay_nstep: the truncated n-step return of the transitions `indices` [n], walked through the ring on the device
+        (include/f110_hip.h has the contract).  Returns (ns_idx, ret, d, discount, span): ns_idx [n] int64 the row of frames_at's
+        frame tensor that holds the frame after the span's last step, ret [n] fp64 = r_0 + gamma r_1 + ... over the span, d [n] uint8
+        the done of its last step, discount [n] fp64 = gamma^span by running products (what the bootstrap is multiplied with) and
+        span [n] int32, at most nstep: a span ends behind a terminal step, in front of an invalid transition and at the newest push.
+        -1, 0, 0, gamma, 0 where frames_at gives a zero transition.  Device tensors, no synchronisation."""
+        if not self.on:
+            raise ValueError('replay: the buffer is off (record_replay())')
+        nstep, gamma = self._nstep(nstep, gamma)
+        eng = self.eng
+        idx = torch.as_tensor(indices).to(device=eng.device, dtype=torch.int64).contiguous().reshape(-1)
+        n = idx.shape[0]
+        ns_idx = torch.empty((n,), dtype=torch.int64, device=eng.device)
+        ret, discount = torch.empty((n,), dtype=torch.float64, device=eng.device), torch.empty((n,), dtype=torch.float64, device=eng.device)
+        d, span = torch.empty((n,), dtype=torch.uint8, device=eng.device), torch.empty((n,), dtype=torch.int32, device=eng.device)
+        with torch.cuda.device(eng.device):
+            _lib.check(eng.lib.f110_replay_nstep(eng._h, idx.data_ptr(), n, nstep, gamma, ns_idx.data_ptr(), ret.data_ptr(), d.data_ptr(),
+                                                 discount.data_ptr(), span.data_ptr(), eng._stream()))
+        self._keep_nstep = idx   # (kept until the next call: the stream may not have read it yet)
+        return ns_idx, ret, d, discount, span
+
+    def frames_at(self, indices, nstep=1, gamma=None):
         """The transitions `indices` [n] without unpacking an image, for consumers that read bits (red_gym_amd.bitconv).
         Returns (frames, s_idx, ns_idx, a, r, d, ok): frames is the ring's frame tensor viewed as [(T + 1) * B, rows, words]
         int64 (a view, no copy: it changes with the next push), s_idx and ns_idx [n] int64 its rows that hold the frame before
         and the frame after (f110_replay_locate; -1 for both where sample_at gives zeros), and a, r, d, ok exactly what
-        sample_at(indices) returns.  Device tensors, no synchronisation."""
+        sample_at(indices) returns.  Device tensors, no synchronisation.
+        nstep > 1 (gamma is then required): the same tuple with r = the n-step return and ns_idx and d those of the span's end, as
+        nstep_at(indices, nstep, gamma) gives them, and its discount and span appended."""
         if not self.on:
             raise ValueError('replay: the buffer is off (record_replay())')
+        nstep, gamma = self._nstep(nstep, gamma)
+        if nstep > 1:
+            frames, s_idx, _, a, _, _, ok = self.frames_at(indices)
+            ns_idx, ret, d, discount, span = self.nstep_at(self._keep, nstep, gamma)
+            return frames, s_idx, ns_idx, a, ret, d, ok, discount, span
         eng = self.eng
         idx = torch.as_tensor(indices).to(device=eng.device, dtype=torch.int64).contiguous().reshape(-1)
         n = idx.shape[0]
@@ -226,7 +270,7 @@ class ReplayBuffer(Consumer):
         idx, _ = self.draw(batch_size, seed)
         return self.frames_at(idx)
 
-    def sample_frames_dev(self, batch_size, counter, seed=None, out=None):
+    def sample_frames_dev(self, batch_size, counter, seed=None, out=None, nstep=1, gamma=None):
         """f110_replay_sample: batch_size transitions drawn from a draw counter that lives on the device, in one kernel.  counter: a
         [1] int64 tensor on the env's device (the bits of the library's uint64; start it at 0) that the caller owns; the call draws
         draw numbers counter .. counter + batch_size - 1 of the stream `seed` (default: the env's) exactly as draw() would with
@@ -234,33 +278,48 @@ class ReplayBuffer(Consumer):
         call, so a captured call replays with fresh draws.  The host counter of draw(), sample() and sample_frames() does not move.
         Returns (frames, s_idx, ns_idx, a, r, d, ok, indices): the first seven what frames_at(indices) returns.  out: a dict with
         the static tensors 'indices', 's_idx', 'ns_idx' [n] int64, 'a' [n, action_dim] fp32, 'r' [n] fp64, 'd' and 'ok' [n] uint8
-        to write into (sample_out() allocates one); the same tensors are then returned.  Device tensors, no synchronisation."""
+        to write into (sample_out() allocates one); the same tensors are then returned.  Device tensors, no synchronisation.
+        nstep > 1 (gamma is then required): f110_replay_sample_nstep, the same draws with the n-step walk in the same kernel.  The
+        tuple is the same with r = the n-step return and ns_idx and d those of the span's end, and 'discount' [n] fp64 and 'span' [n]
+        int32 appended (out then holds those two as well: sample_out(n, nstep)); everything behind the indices is what
+        nstep_at(indices, nstep, gamma) and frames_at(indices) give."""
         if not self.on:
             raise ValueError('replay: the buffer is off (record_replay())')
+        nstep, gamma = self._nstep(nstep, gamma)
         eng, n = self.eng, int(batch_size)
         if not torch.is_tensor(counter) or counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != torch.device(eng.device):
             raise ValueError('replay: counter must be a [1] int64 tensor on %s' % (eng.device,))
-        o = self.sample_out(n) if out is None else out
-        shapes = self._sample_shapes(n)
+        o = self.sample_out(n, nstep) if out is None else out
+        shapes = self._sample_shapes(n, nstep)
         for k, (shape, dt) in shapes.items():
             t = o.get(k)
             if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != torch.device(eng.device) or not t.is_contiguous():
                 raise ValueError('replay: out[%r] must be a contiguous %s tensor of shape %s on %s' % (k, dt, shape, eng.device))
+        T, B = self.cfg.steps, eng.B
+        frames = self.buf['frames'].view((T + 1) * B, self.rows, words(self.cols))
+        if nstep > 1:
+            with torch.cuda.device(eng.device):
+                _lib.check(eng.lib.f110_replay_sample_nstep(eng._h, self._seed(seed), counter.data_ptr(), n, nstep, gamma, o['indices'].data_ptr(),
+                                                            o['s_idx'].data_ptr(), o['ns_idx'].data_ptr(), o['a'].data_ptr(), o['r'].data_ptr(),
+                                                            o['d'].data_ptr(), o['ok'].data_ptr(), o['discount'].data_ptr(), o['span'].data_ptr(),
+                                                            eng._stream()))
+            return frames, o['s_idx'], o['ns_idx'], o['a'], o['r'], o['d'], o['ok'], o['indices'], o['discount'], o['span']
         with torch.cuda.device(eng.device):
             _lib.check(eng.lib.f110_replay_sample(eng._h, self._seed(seed), counter.data_ptr(), n, o['indices'].data_ptr(), o['s_idx'].data_ptr(),
                                                   o['ns_idx'].data_ptr(), o['a'].data_ptr(), o['r'].data_ptr(), o['d'].data_ptr(), o['ok'].data_ptr(),
                                                   eng._stream()))
-        T, B = self.cfg.steps, eng.B
-        frames = self.buf['frames'].view((T + 1) * B, self.rows, words(self.cols))
         return frames, o['s_idx'], o['ns_idx'], o['a'], o['r'], o['d'], o['ok'], o['indices']
 
-    def _sample_shapes(self, n):
-        return {'indices': ((n,), torch.int64), 's_idx': ((n,), torch.int64), 'ns_idx': ((n,), torch.int64),
-                'a': ((n, self.cfg.action_dim), torch.float32), 'r': ((n,), torch.float64), 'd': ((n,), torch.uint8), 'ok': ((n,), torch.uint8)}
+    def _sample_shapes(self, n, nstep=1):
+        shapes = {'indices': ((n,), torch.int64), 's_idx': ((n,), torch.int64), 'ns_idx': ((n,), torch.int64),
+                  'a': ((n, self.cfg.action_dim), torch.float32), 'r': ((n,), torch.float64), 'd': ((n,), torch.uint8), 'ok': ((n,), torch.uint8)}
+        if nstep > 1:
+            shapes.update({'discount': ((n,), torch.float64), 'span': ((n,), torch.int32)})
+        return shapes
 
-    def sample_out(self, batch_size):
-        """The tensors sample_frames_dev writes, newly allocated: what its `out` takes."""
-        return {k: torch.empty(shape, dtype=dt, device=self.eng.device) for k, (shape, dt) in self._sample_shapes(int(batch_size)).items()}
+    def sample_out(self, batch_size, nstep=1):
+        """The tensors sample_frames_dev writes, newly allocated: what its `out` takes ('discount' and 'span' with nstep > 1 only)."""
+        return {k: torch.empty(shape, dtype=dt, device=self.eng.device) for k, (shape, dt) in self._sample_shapes(int(batch_size), int(nstep)).items()}
 
     def bytes_held(self):
         return sum(self.buf[k].numel() * self.buf[k].element_size() for k in ('frames', 'actions', 'rewards', 'dones', 'valid'))

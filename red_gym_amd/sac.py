@@ -17,6 +17,7 @@ from .gauss import GaussianSource
 from .optim import SacAdam
 from .policyhead import PolicyHead, sample_actions
 from .qhead import QHead, td_target, twin_q
+from .replay import MAX_NSTEP
 from .sacloss import actor_loss, critic_loss
 from .temperature import Temperature
 
@@ -100,17 +101,27 @@ class SACAgent:
     new_action (row = the batch row); each call that draws advances its stream's counter on the device, the fills and their advances
     are captured with the update, and state_dict() holds the seed and the counters, so a loaded agent continues to the same bits.  An
     eps that is passed wins and advances nothing, and so does evaluate=True.  With 'torch' nothing of this exists (source is None).
+    nstep: 1 is the reference's one-step target.  k > 1 (up to replay.MAX_NSTEP): the updates that draw from a ring -- update,
+    capture_update, update_graph -- draw with the n-step walk (ReplayBuffer.sample_frames_dev(nstep=k, gamma=gamma)) and the target is
+    tv = R + (1 - d) * gamma^m * (min Q'(s_m, a') - alpha * logp'), R = r_0 + gamma r_1 + ... + gamma^(m - 1) r_(m - 1) over a span of m
+    <= k stored steps that ends behind a terminal step, in front of a reset and at the newest push; the discount arrives per row.  This
+    is the UNCORRECTED n-step return: no importance weights for the off-policy steps inside the span and no entropy bonus on the
+    intermediate steps -- the entropy term enters through the bootstrap only, as in the common implementations.  nstep is
+    configuration, not state: state_dict() does not hold it.  With nstep = 1 nothing changes: the same launches, graph key and bits.
     Attributes: actor, critics [2], targets [2]; actor_opt, critic_opts [2] (SacAdam; a critic's also moves its target); draws, the [1]
     int64 draw counter on the device; sample, the tensors of the batch the last update drew (sample['indices'] names the transitions)."""
 
     def __init__(self, action_dim=16, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, rows=256, cols=256, hidden=512,
-                 on=255.0, device='cuda', networks=None, target_entropy=None, alpha_lr=3e-4, init_alpha=0.2, draws='torch', seed=0):
+                 on=255.0, device='cuda', networks=None, target_entropy=None, alpha_lr=3e-4, init_alpha=0.2, draws='torch', seed=0, nstep=1):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ValueError('SACAgent: device %s: there is no CPU path' % (self.device,))
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
         self.action_dim, self.gamma, self.tau = int(action_dim), float(gamma), float(tau)
+        if isinstance(nstep, bool) or not isinstance(nstep, int) or not 1 <= nstep <= MAX_NSTEP:
+            raise ValueError('SACAgent: nstep %r: an int in 1..%d' % (nstep, MAX_NSTEP))
+        self.nstep = nstep
         self.temperature = None
         if isinstance(alpha, str):
             if alpha != 'auto':
@@ -192,8 +203,9 @@ class SACAgent:
                 raise ValueError('SACAgent: eps_next and eps_new must be fp32 [%d, %d] on %s' % (n, self.action_dim, self.device))
         return eps[0], eps[1]
 
-    def _update(self, frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, losses):
-        """:544-580 on one batch; the three losses go to `losses` [3] (actor, critic1, critic2), which is returned."""
+    def _update(self, frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, losses, discount=None):
+        """:544-580 on one batch; the three losses go to `losses` [3] (actor, critic1, critic2), which is returned.  discount: [n] fp64,
+        the target's discount per row (r is then the n-step return); None: gamma."""
         actor, critics, targets = self.actor, self.critics, self.targets
         if eps_next is None and self.source is not None:
             n = int(s_idx.shape[0])
@@ -201,7 +213,8 @@ class SACAgent:
             eps_new = self.source.normal(n, self.action_dim, stream=2)
         with torch.no_grad():                                                    # :544-549
             next_a, next_logp = actor.sample(frames, ns_idx, eps_next)
-            tv = td_target([t.trunk(frames, ns_idx) for t in targets], next_a, next_logp, r, d, *_heads(targets), self.gamma, self.alpha, dense=True)
+            tv = td_target([t.trunk(frames, ns_idx) for t in targets], next_a, next_logp, r, d, *_heads(targets), self.gamma if discount is None else discount,
+                           self.alpha, dense=True)
         q, _ = twin_q([c.trunk(frames, s_idx) for c in critics], a, *_heads(critics), dense=True)     # :551-552, a as the ring stores it (fp32)
         grad_q = torch.empty_like(q)
         critic_loss(q[0], q[1], tv, loss=losses[1:3], grad=grad_q)               # :553-554
@@ -223,12 +236,15 @@ class SACAgent:
     def update_batch(self, batch, eps=None):
         """One update on a batch that is given, not drawn: a dict with 'frames' [m, rows, words] int64, 's_idx' and 'ns_idx' [n] int64
         rows of it (-1: a zero frame), 'a' [n, action_dim] fp32, 'r' [n] fp64 and 'd' [n] uint8, as ReplayBuffer.sample_frames returns
-        them.  eps = (eps_next, eps_new), fp32 [n, action_dim], replace the two torch.randn draws.  Returns the new [3] fp32 loss tensor
+        them.  An optional 'discount' [n] fp64 is the target's discount per row in gamma's place ('r' is then the n-step return and
+        'ns_idx', 'd' those of the span's end, as ReplayBuffer.frames_at with nstep > 1 returns them); without it gamma, whatever the agent's nstep.
+        eps = (eps_next, eps_new), fp32 [n, action_dim], replace the two torch.randn draws.  Returns the new [3] fp32 loss tensor
         (actor, critic1, critic2) on the device; no synchronisation."""
         n = int(batch['s_idx'].shape[0])
         eps_next, eps_new = self._eps(eps, n)
         losses = torch.empty((3,), dtype=torch.float32, device=self.device)
-        return self._update(batch['frames'], batch['s_idx'], batch['ns_idx'], batch['a'], batch['r'], batch['d'], eps_next, eps_new, losses)
+        return self._update(batch['frames'], batch['s_idx'], batch['ns_idx'], batch['a'], batch['r'], batch['d'], eps_next, eps_new, losses,
+                            batch.get('discount'))
 
     def _check_replay(self, replay):
         if not replay.on:
@@ -249,9 +265,16 @@ class SACAgent:
         eps_next, eps_new = self._eps(eps, n)
         if check and len(replay) < n:
             return torch.zeros((3,), dtype=torch.float32, device=self.device)
-        self.sample = replay.sample_out(n)
-        frames, s_idx, ns_idx, a, r, d, _, _ = replay.sample_frames_dev(n, self.draws, out=self.sample)
-        return self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, torch.empty((3,), dtype=torch.float32, device=self.device))
+        self.sample = replay.sample_out(n, self.nstep)
+        frames, s_idx, ns_idx, a, r, d, discount = self._draw(replay, n, self.sample)
+        return self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, torch.empty((3,), dtype=torch.float32, device=self.device), discount)
+
+    def _draw(self, replay, n, out):
+        """The batch of an update drawn into `out` with the agent's draw counter -> (frames, s_idx, ns_idx, a, r, d, discount or None)."""
+        if self.nstep == 1:
+            return replay.sample_frames_dev(n, self.draws, out=out)[:6] + (None,)
+        got = replay.sample_frames_dev(n, self.draws, out=out, nstep=self.nstep, gamma=self.gamma)
+        return got[:6] + (got[8],)
 
     # ---- the captured update
     def _graph_key(self, replay, n):
@@ -260,6 +283,7 @@ class SACAgent:
                tuple((o.lr, o.betas, o.eps, o.tau) for o in opts))
         t = self.temperature
         key = key if t is None else key + ((t.lr, t.betas, t.eps, t.target_entropy),)
+        key = key if self.nstep == 1 else key + (('nstep', self.nstep, self.gamma),)
         return key if self.source is None else key + (('source', self.source.state.data_ptr()),)
 
     def capture_update(self, replay, batch_size=64, draws=True):
@@ -277,7 +301,7 @@ class SACAgent:
         if key != self._g_key:
             self._graphs = {}
             self._g_key, self._g_replay = key, replay
-            self._g_sample = replay.sample_out(n)
+            self._g_sample = replay.sample_out(n, self.nstep)
             self._g_eps = [torch.zeros((n, self.action_dim), dtype=torch.float32, device=dev) for _ in range(2)]
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(dev)
@@ -285,9 +309,9 @@ class SACAgent:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.stream(side), torch.cuda.graph(g, stream=side):
             self.zero_grad(set_to_none=True)
-            frames, s_idx, ns_idx, a, r, d, _, _ = replay.sample_frames_dev(n, self.draws, out=self._g_sample)
+            frames, s_idx, ns_idx, a, r, d, discount = self._draw(replay, n, self._g_sample)
             eps_next, eps_new = (None, None) if draws else self._g_eps
-            self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, self._g_losses)
+            self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, self._g_losses, discount)
         cur.wait_stream(side)
         self._graphs[bool(draws)] = g
         self.captures += 1
@@ -298,7 +322,7 @@ class SACAgent:
         eps_new) are copied into the static draws first; without them the graph draws by itself.  Returns the static [3] loss tensor
         (read it before the next replay).  The update is captured again first -- `recaptured` says so, `captures` counts -- when the
         ring was installed anew (its old tensors are freed), or an optimizer's (or the temperature's) lr, betas, eps, tau or target
-        entropy, or the env's seed has changed:
+        entropy, the env's seed, or nstep (and, with nstep > 1, gamma, which the walk takes by value) has changed:
         a captured launch keeps the addresses and scalars it was captured with."""
         if self._g_key is None:
             raise ValueError('SACAgent: no update is captured (capture_update(replay, batch_size))')
