@@ -1,5 +1,5 @@
 """The training loop of the reference's RL consumer (main(), src/SAL.py:975-1019) for many envs at once, everything on the GPU:
-    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps] [nstep] [auto] [device]
+    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps] [nstep] [auto] [device] [per]
     select_action (the policy on the shaper's bitmap) -> path_actions (SAL's action decode and MPC step, which also hands the raw
     action to the ring) -> step (scan, shaper, the ring's push) -> after update_after steps, every update_every steps, one SACAgent
     update replayed from a graph: the batch is drawn on the device, the losses stay there.  The episodes are kept on the GPU too
@@ -13,7 +13,10 @@ the policy's Gaussian draws are made on the device (SACAgent(draws='device'): Nu
 the replayed graph, the counters part of state_dict()) and the number of calls per stream is printed at the end.  At the end the actor is saved under the reference's keys, as main()
 saves sac_actor.pth.  With nstep > 1 (a seventh number) the targets are built on truncated n-step returns walked through the ring on
 the device (SACAgent(nstep=k)), and the mean span of the last sampled batch is printed beside the losses: below k where episodes end,
-resets intervene or the newest push cuts a walk short."""
+resets intervene or the newest push cuts a walk short.  With a trailing `per` the ring keeps priorities (record_replay(priorities=True): an
+exact integer sum tree on the device) and the agent draws in proportion to them, weighs the critics' loss and writes the new TD errors
+back, all inside the replayed graph (SACAgent(per=True)); the mean importance weight of the last batch and beta are printed beside the
+losses."""
 import os
 import sys
 import tempfile
@@ -26,16 +29,16 @@ arg = lambda i, default: int(sys.argv[i]) if len(sys.argv) > i else default  # n
 B, STEPS, BATCH, UPDATE_AFTER, UPDATE_EVERY, MAX_STEPS = arg(1, 64), arg(2, 48), arg(3, 64), arg(4, 16), arg(5, 4), arg(6, 12)
 AD = 16
 NSTEP = int(sys.argv[7]) if len(sys.argv) > 7 and sys.argv[7].isdigit() else 1
-AUTO, DEVICE = 'auto' in sys.argv[7:], 'device' in sys.argv[7:]
+AUTO, DEVICE, PER = 'auto' in sys.argv[7:], 'device' in sys.argv[7:], 'per' in sys.argv[7:]
 env = F110VecEnv(B, map=workload.EXAMPLE_MAP, num_agents=1, autoreset=True)
 env.shape_rewards()
 env.follow_paths()
-env.record_replay(capacity=16 * B, action_dim=AD)
+env.record_replay(capacity=16 * B, action_dim=AD, priorities=True if PER else None)
 env.track_episodes(MAX_STEPS + torch.arange(B, dtype=torch.int32) % 4)   # staggered: envs spawned together do not end together
 dev, cfg = env.device, env.eng.shaper.cfg
 torch.manual_seed(0)
 agent = SACAgent(action_dim=AD, rows=cfg.rows, cols=cfg.cols, device=dev, **(dict(alpha='auto') if AUTO else {}),
-                 **(dict(draws='device', seed=0) if DEVICE else {}), nstep=NSTEP)
+                 **(dict(draws='device', seed=0) if DEVICE else {}), nstep=NSTEP, per=PER)
 raw = torch.zeros((B, AD), dtype=torch.float64, device=dev)                    # the policy's action, written in place
 obs, reward, done, info = env.reset(torch.as_tensor(workload.spawn_poses(B, 1), device=dev))
 total = torch.zeros((B,), dtype=torch.float64, device=dev)
@@ -50,9 +53,10 @@ for step in range(1, STEPS + 1):
         losses = agent.update_graph()
         updates += 1
         if updates % 4 == 1:
-            print('step %3d, update %2d: losses (actor, critic 1, critic 2) %s%s%s' % (
+            print('step %3d, update %2d: losses (actor, critic 1, critic 2) %s%s%s%s' % (
                 step, updates, ' '.join('%.6f' % v for v in losses.tolist()), ', alpha %.9f' % agent.alpha.item() if AUTO else '',
-                ', mean span %.3f of %d' % (agent.sample['span'].double().mean().item(), NSTEP) if NSTEP > 1 else ''))
+                ', mean span %.3f of %d' % (agent.sample['span'].double().mean().item(), NSTEP) if NSTEP > 1 else '',
+                ', mean weight %.4f, beta %.6f' % (agent.sample['weight'].mean().item(), env.replay.priorities.beta) if PER else ''))
             count = int(info['episodes_finished'].item())
             rec = {k: v.tolist() for k, v in env.episodes.finished(last=min(count - printed, 4)).items()}   # (a few of the new ones)
             for i in range(len(rec['env'])):

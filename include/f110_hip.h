@@ -679,6 +679,86 @@ int f110_replay_sample_nstep(f110_handle *h, uint64_t seed, uint64_t *counter, i
                              int64_t *s_frame, int64_t *ns_frame, float *a, double *ret, uint8_t *d, uint8_t *ok, double *discount, int32_t *span,
                              void *stream);
 
+/* Prioritized replay (Schaul et al., "Prioritized Experience Replay"; the reference draws uniformly): an exact integer sum tree over
+ * the ring's transitions, on the device, opt-in.  Without f110_priority_install nothing here launches and f110_replay_update's launch
+ * sequence is unchanged.
+ * The tree.  Leaves: uint32 leaf[L], L = T * B, leaf position = the transition index step slot * B + env; 0 = never drawn.  Above them
+ * levels of fanout 64 (a wave): level 1 has ceil(L / 64) uint64 nodes, level k + 1 has ceil(count_k / 64), until a level has at most
+ * 64 nodes: the top.  No root is stored; the total is the sum of the top level, formed by the wave that needs it.  With L <= 64 there
+ * is no node and the leaves are the top.  All nodes live in one array uint64 node[f110_priority_node_words(L)], level 1 first (-1 for
+ * an L outside 1 .. F110_PRIORITY_MAX_LEAVES).  After every entry point below has run, every node equals the sum of its (up to 64)
+ * children.  Words are integers and sums are exact, so the result of every entry is the same in every run and in any order of rows;
+ * the integer atomics used by the set do not change that.
+ * A word: q = clamp(llrint(p * 2^F110_PRIORITY_SHIFT), 1, 2^32 - 1) with p = pow(double(td) + eps, exponent), one fp64 pow of the
+ * device library (`exponent` is PER's alpha; the name keeps it apart from SAC's temperature); a td that is NaN or +inf gives 2^32 - 1.
+ * At exponent == 1 p is the sum double(td) + eps itself, without the pow (the library's is within an ulp, not exact there), so the word
+ * is rint((td + eps) * 2^16) exactly, ties to even.
+ * State: f110_priority_state, 64 bytes on the device, the caller's: qmax (the word a new transition enters with; start at 1 <<
+ * F110_PRIORITY_SHIFT = priority 1.0), beta, beta_step, beta_end (fp64), reserved words 0.
+ * Stateless entries (leaf, node dev; no handle, no allocation, no synchronisation, capturable):
+ * f110_ptree_rebuild: every level from the leaves, one launch per level.
+ * f110_ptree_set: leaf[idx[i]] = q[i] for the rows with 0 <= idx[i] < L (others are skipped); where several rows name one leaf it
+ *   becomes the MAXIMUM of their q; every ancestor is fixed.  Two launches whatever L: the first takes the old word out of each named
+ *   leaf (atomicExch to 0; the lane that got it subtracts it from every ancestor with 64-bit atomicAdd), the second raises the leaf
+ *   (atomicMax; a lane that raised it adds the difference to every ancestor, and the raises of one leaf telescope to its final word).
+ * f110_ptree_pick: n draws, one wave each.  Draw j (counted from first_draw) takes z = splitmix64(seed + 0x9E3779B97F4A7C15 * (1 + j *
+ *   F110_REPLAY_TRIES)) -- attempt 0 of f110_replay_draw's draw j -- and u = mulhi64(z, total).  From the top level down the lanes load
+ *   the current node's children (0 beyond the end), form the inclusive prefix sum across lanes, the first child whose prefix exceeds u is
+ *   taken, its exclusive prefix is subtracted from u.  At the leaves this gives idx_out[j] and q_out[j] = leaf[idx] > 0; total == 0 gives
+ *   -1 and 0.  The result equals searchsorted(cumsum(leaf), u, 'right') over the flat leaves.
+ * On the handle, behind an installed and bound replay ring (L = T * B):
+ * f110_priority_install: cfg = {exponent in [0, 8], eps >= 0 and finite}; NULL removes the feature.  f110_priority_bind: leaf [L]
+ *   uint32, node [f110_priority_node_words(L)] uint64 (may be NULL while that is 0), state (8-byte aligned).  f110_replay_install
+ *   (removal included) removes the priorities too.  Install, removal and bind move the launch epoch.
+ * f110_priority_reset: leaf = valid[index] ? qmax : 0 for every index, then the rebuild.
+ * f110_replay_update, while priorities are bound: between the push and the advance of count (so it reads the same count) the row of
+ *   step slot count % T gets leaf = valid ? qmax : 0 and every node whose children changed is recomputed -- one launch of one wave per
+ *   level-1 node the row touches (with B % 64 != 0 the row shares its first or last one with the neighbouring rows), and with more
+ *   than one level one launch of one workgroup for the levels above.  Captured with the push.
+ * f110_priority_sample: f110_replay_sample_nstep with f110_ptree_pick's draw (first_draw = counter[0]) in place of the uniform one:
+ *   for the indices it returns every ring output is what f110_replay_nstep / f110_replay_locate give (nstep = 1: the one-step values);
+ *   prio [n] uint32 = the drawn leaf's word.  A second launch of one workgroup forms qmin = the minimum of prio over the rows with ok
+ *   and weight[i] = ok ? float(pow(double(qmin) / double(prio[i]), beta)) : 0, then adds n to the counter and sets beta = min(beta_end,
+ *   beta + beta_step).  That is the importance weight (N * P(i))^-beta divided by the batch's maximum: P(i) = prio[i] / total, so N and
+ *   the total cancel in the ratio.  The weights use the beta read before its advance; rows with prio == qmin are exactly 1.0f and beta
+ *   = 0 gives all ones.  Two launches.
+ * f110_priority_update: q = the word of td[i] (above) for the rows with ok[i], an index inside the ring and valid[idx] != 0, applied
+ *   with f110_ptree_set's rule; other rows are skipped and have q_out = 0 (q_out may be NULL).  qmax is raised to the largest q
+ *   applied.  f110_priority_set: the same with the words given (for tests and for loading).  Two launches each.
+ * F110_E_INVALID before any launch, naming the culprit: a NULL array, n < 0, a misaligned counter or state, exponent outside [0, 8],
+ * eps negative or not finite, L outside its limits, and the wrong device as f110_replay_update refuses it. */
+#define F110_PRIORITY_SHIFT 16
+#define F110_PRIORITY_MAX_LEAVES (1ll << 31)
+#define F110_PRIORITY_STATE_BYTES 64
+typedef struct f110_priority_config {
+    double exponent;            /* PER's alpha: priority = (|td| + eps)^exponent */
+    double eps;
+} f110_priority_config;
+typedef struct f110_priority_state { /* on the device; 64 bytes */
+    uint32_t qmax;              /* the word of a new transition */
+    uint32_t reserved0;
+    double beta, beta_step, beta_end;
+    uint64_t reserved[4];
+} f110_priority_state;
+typedef struct f110_priority_buffers {
+    uint32_t *leaf;             /* [T * B] */
+    uint64_t *node;             /* [f110_priority_node_words(T * B)] */
+    f110_priority_state *state;
+} f110_priority_buffers;
+int64_t f110_priority_node_words(int64_t L);
+int f110_ptree_rebuild(const uint32_t *leaf, uint64_t *node, int64_t L, void *stream);
+int f110_ptree_set(uint32_t *leaf, uint64_t *node, int64_t L, const int64_t *idx, const uint32_t *q, int32_t n, void *stream);
+int f110_ptree_pick(const uint32_t *leaf, const uint64_t *node, int64_t L, uint64_t seed, uint64_t first_draw, int32_t n, int64_t *idx_out,
+                    uint32_t *q_out, void *stream);
+int f110_priority_install(f110_handle *h, const f110_priority_config *cfg);
+int f110_priority_bind(f110_handle *h, const f110_priority_buffers *bufs);
+int f110_priority_reset(f110_handle *h, void *stream);
+int f110_priority_sample(f110_handle *h, uint64_t seed, uint64_t *counter, int32_t n, int32_t nstep, double gamma, int64_t *indices,
+                         int64_t *s_frame, int64_t *ns_frame, float *a, double *ret, uint8_t *d, uint8_t *ok, double *discount, int32_t *span,
+                         uint32_t *prio, float *weight, void *stream);
+int f110_priority_update(f110_handle *h, const int64_t *idx, const uint8_t *ok, const float *td, int32_t n, uint32_t *q_out, void *stream);
+int f110_priority_set(f110_handle *h, const int64_t *idx, const uint32_t *q, int32_t n, void *stream);
+
 /* Episodes: the episode of the reference's training loop (src/SAL.py:986-1015: `obs = env.reset(); ep_reward = 0; for st in
  * range(max_steps): ...; ep_reward += reward; if done: break; print(f"Episode {ep} Reward={ep_reward:.2f}")`) for every env, on
  * the device behind the step: the return and the length of the running episode, a step limit per env, and a log of the finished
@@ -1074,6 +1154,14 @@ int f110_soft_update(const f110_adam_tensor *table, int32_t n_tensors, double ta
 int f110_sac_critic_loss(const float *q1, const float *q2, const float *tv, int64_t n, float *loss, float *grad_q1, float *grad_q2, void *stream);
 int f110_sac_actor_loss(const void *logp, int32_t logp_fp64, const float *qn, double alpha, int64_t n, float *loss, void *grad_logp,
                         float *grad_qn, void *stream);
+/* f110_sac_critic_loss_weighted: the critic loss under per-row importance weights w [n] fp32 (f110_priority_sample's), a kernel of its
+ * own: the unweighted entry keeps its code and bits.  e = double(q_c[i]) - double(tv[i]); t_i = double(w[i]) * (e * e) -- the square
+ * first, every product rounded on its own; the sum order, the division by n and the rounding exactly as above.  grad_q_c[i] = ((q_c[i] -
+ * tv[i]) * k) * w[i] in fp32, k = float(2.0 / double(n)).  td_out [n] fp32 (may be NULL) = fmaxf(fabsf(q1[i] - tv[i]), fabsf(q2[i] -
+ * tv[i])): what f110_priority_update takes.  With w = 1 everywhere the loss and both gradients are f110_sac_critic_loss's bits.  Refused
+ * as that entry refuses, and for a NULL w. */
+int f110_sac_critic_loss_weighted(const float *q1, const float *q2, const float *tv, const float *w, int64_t n, float *loss, float *grad_q1,
+                                  float *grad_q2, float *td_out, void *stream);
 
 /* The entropy temperature of SAC, learnt on the device: log_alpha moves by Adam towards a target entropy (the usual default is
  * -action_dim), and alpha = exp(log_alpha) lives in device memory where the two kernels that consume it read it, so a captured update

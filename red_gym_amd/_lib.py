@@ -217,6 +217,29 @@ class GaussState(C.Structure):
 
 GAUSS_STRUCTS = {'f110_gauss_state': GaussState}
 
+# f110_priority_config, f110_priority_state, f110_priority_buffers: prioritized replay (tagged typedefs like the temperature's;
+# tests/test_priority_cpu.py checks them against the compiler).  The state lives on the device: priority.py writes a fresh one through
+# the mirror.
+F110_PRIORITY_SHIFT = 16
+F110_PRIORITY_MAX_LEAVES = 1 << 31
+F110_PRIORITY_STATE_BYTES = 64
+
+
+class PriorityConfig(C.Structure):
+    _fields_ = [('exponent', C.c_double), ('eps', C.c_double)]
+
+
+class PriorityState(C.Structure):
+    _fields_ = [('qmax', C.c_uint32), ('reserved0', C.c_uint32), ('beta', C.c_double), ('beta_step', C.c_double), ('beta_end', C.c_double),
+                ('reserved', C.c_uint64 * 4)]
+
+
+class PriorityBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ('leaf', 'node', 'state')]
+
+
+PRIORITY_STRUCTS = {'f110_priority_config': PriorityConfig, 'f110_priority_state': PriorityState, 'f110_priority_buffers': PriorityBuffers}
+
 # every typedef struct of include/f110_hip.h but f110_adam_state (device-resident; F110_ADAM_STATE_BYTES is its size)
 STRUCTS = {
     'f110_config': Config, 'f110_buffers': Buffers, 'f110_progress_buffers': ProgressBuffers,
@@ -311,6 +334,16 @@ SYMBOLS = {
     'f110_replay_sample': [_VP, C.c_uint64, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_replay_nstep': [_VP, _VP, _I32, _I32, _D, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_replay_sample_nstep': [_VP, C.c_uint64, _VP, _I32, _I32, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_priority_node_words': [_I64],
+    'f110_ptree_rebuild': [_VP, _VP, _I64, _VP],
+    'f110_ptree_set': [_VP, _VP, _I64, _VP, _VP, _I32, _VP],
+    'f110_ptree_pick': [_VP, _VP, _I64, C.c_uint64, C.c_uint64, _I32, _VP, _VP, _VP],
+    'f110_priority_install': [_VP, _VP],
+    'f110_priority_bind': [_VP, _VP],
+    'f110_priority_reset': [_VP, _VP],
+    'f110_priority_sample': [_VP, C.c_uint64, _VP, _I32, _I32, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_priority_update': [_VP, _VP, _VP, _VP, _I32, _VP, _VP],
+    'f110_priority_set': [_VP, _VP, _VP, _I32, _VP],
     'f110_episodes_validate': [C.POINTER(EpisodesConfig)],
     'f110_episodes_install': [_VP, C.POINTER(EpisodesConfig)],
     'f110_episodes_bind': [_VP, C.POINTER(EpisodesBuffers)],
@@ -346,6 +379,7 @@ SYMBOLS = {
     'f110_soft_update': [C.POINTER(AdamTensor), _I32, _D, _VP],
     'f110_sac_critic_loss': [_VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP],
     'f110_sac_actor_loss': [_VP, _I32, _VP, _D, _I64, _VP, _VP, _VP, _VP],
+    'f110_sac_critic_loss_weighted': [_VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP],
     'f110_temperature_validate': [_VP],
     'f110_temperature_state_bytes': [],
     'f110_temperature_step': [_VP, _VP, _I32, _I64, _VP, _D, _VP],
@@ -381,7 +415,7 @@ RESTYPES = {
     'f110_last_error': C.c_char_p,
     'f110_destroy': None, 'f110_graph_destroy': None, 'f110_bitmap_destroy': None,
     'f110_pack_env_size': _I64, 'f110_adam_state_bytes': _I64, 'f110_temperature_state_bytes': _I64,
-    'f110_gauss_state_bytes': _I64,
+    'f110_gauss_state_bytes': _I64, 'f110_priority_node_words': _I64,
     'f110_pure_pursuit_workspace': _I64, 'f110_bitconv_workspace': _I64, 'f110_featconv_workspace': _I64,
     'f110_dense_workspace': _I64, 'f110_policyhead_workspace': _I64, 'f110_qhead_workspace': _I64,
 }

@@ -7,7 +7,7 @@
 //   f110_noise_abi.hip  lidar noise: slots, ring, generators, per-env mode
 //   f110_step.hip       launch policy of the scan, the step, hipGraphs, measurement aid, function-level entry points
 //   f110_consumers.hip  the callers either side of the step, on the handle: pure-pursuit planner, progress tracker, reward shaper,
-//                       path follower, replay buffer, episode tracker
+//                       path follower, replay buffer and its priority tree, episode tracker
 //   f110_bitconv_abi.hip the policy's first layers from bits, stateless: bit convolution, policy stem
 //   f110_policy_abi.hip the policy's and the critics' tails, stateless: policy head, critic head, the parameter update (Adam and
 //                       the soft update of the targets), the two losses of a SAC update and the learnt entropy temperature

@@ -5,6 +5,7 @@
 #include "f110_shaping.h"
 #include "f110_pathfollow.h"
 #include "f110_replay.h"
+#include "f110_priority.h"
 #include "f110_episodes.h"
 
 // ---------------------------------------------------------------- planner
@@ -688,11 +689,13 @@ extern "C" int f110_replay_install(f110_handle *h, const f110_replay_config *cfg
     if (!cfg) { // removes the buffer (the ring is the caller's)
         if (!r.on) return F110_OK;
         r.on = false; r.bound = false;
+        h->priority.on = false; h->priority.bound = false; // the tree is over this ring's transitions
         h->epoch++;
         return F110_OK;
     }
     if (int rc = f110_replay_validate(cfg, h->shaping.on ? &h->shaping.cfg : nullptr, h->cfg.num_envs)) return rc;
     if (int rc = clock_usable(h, "f110_replay_install")) return rc;
+    h->priority.on = false; h->priority.bound = false;
     r.cfg = *cfg; r.rows = h->shaping.cfg.rows; r.cols = h->shaping.cfg.cols;
     r.on = true; r.bound = false; // the ring's shape may have changed: bind again
     h->epoch++;
@@ -726,6 +729,8 @@ static int replay_ready(const f110_handle *h, const char *who, ReplayRing &g)
     return F110_OK;
 }
 
+static int priority_push(const f110_handle *h, const ReplayRing &g, hipStream_t stream);
+
 extern "C" int f110_replay_update(f110_handle *h, void *stream)
 {
     if (!h) return fail(F110_E_INVALID, "f110_replay_update: null handle");
@@ -740,6 +745,8 @@ extern "C" int f110_replay_update(f110_handle *h, void *stream)
     a.t_seen = r.bufs.t_seen; a.last_valid = r.bufs.last_valid;
     hipLaunchKernelGGL(replay_push_kernel, dim3((unsigned)a.ring.n_envs), dim3(REPLAY_THREADS), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
+    if (h->priority.on && h->priority.bound)
+        if (int rc = priority_push(h, a.ring, (hipStream_t)stream)) return rc;
     hipLaunchKernelGGL(replay_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a.ring.count);
     HIP_TRY(hipGetLastError());
     return F110_OK;
@@ -863,6 +870,218 @@ extern "C" int f110_replay_sample_nstep(f110_handle *h, uint64_t seed, uint64_t 
     hipLaunchKernelGGL(replay_counter_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long *)counter, (unsigned long long)n);
     HIP_TRY(hipGetLastError());
     return F110_OK;
+}
+
+// ---------------------------------------------------------------- prioritized replay: the tree alone, then on the handle
+static PriorityTree priority_tree(const uint32_t *leaf, const uint64_t *node, int64_t L, uint32_t *dev_err)
+{
+    PriorityTree t;
+    t.leaf = const_cast<uint32_t *>(leaf); t.node = (unsigned long long *)const_cast<uint64_t *>(node); t.lay = priority_layout(L); t.dev_err = dev_err;
+    return t;
+}
+
+// every level from the leaves, bottom up: one launch per level
+static int priority_rebuild(const PriorityTree &t, hipStream_t stream)
+{
+    for (int lev = 1; lev <= t.lay.levels; lev++) {
+        const long long waves = t.lay.count[lev - 1], per = PT_THREADS / 64;
+        hipLaunchKernelGGL(ptree_level_kernel, dim3((unsigned)((waves + per - 1) / per)), dim3(PT_THREADS), 0, stream, t, lev);
+        HIP_TRY(hipGetLastError());
+    }
+    return F110_OK;
+}
+
+// the set's two launches: every named leaf cleared, then raised
+static int priority_apply(const PrioritySetArgs &a, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((a.n + PT_THREADS - 1) / PT_THREADS));
+    hipLaunchKernelGGL(ptree_clear_kernel, grid, dim3(PT_THREADS), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ptree_raise_kernel, grid, dim3(PT_THREADS), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int64_t f110_priority_node_words(int64_t L) { return priority_node_words(L); }
+
+extern "C" int f110_ptree_rebuild(const uint32_t *leaf, uint64_t *node, int64_t L, void *stream)
+{
+    const char *who = "f110_ptree_rebuild";
+    if (int rc = priority_tree_check(who, leaf, node, L)) return rc;
+    const PriorityTree t = priority_tree(leaf, node, L, nullptr);
+    if (t.lay.levels == 0) return F110_OK;
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, {{"leaf", leaf}, {"node", node}})) return rc;
+    return priority_rebuild(t, (hipStream_t)stream);
+}
+
+extern "C" int f110_ptree_set(uint32_t *leaf, uint64_t *node, int64_t L, const int64_t *idx, const uint32_t *q, int32_t n, void *stream)
+{
+    const char *who = "f110_ptree_set";
+    if (int rc = priority_tree_check(who, leaf, node, L)) return rc;
+    if (n < 0) return fail(F110_E_INVALID, "%s: n=%d", who, n);
+    if (!idx) return fail(F110_E_INVALID, "%s: null idx", who);
+    if (!q) return fail(F110_E_INVALID, "%s: null q", who);
+    if (n == 0) return F110_OK;
+    std::vector<DevicePtr> ptrs = {{"leaf", leaf}, {"idx", idx}, {"q", q}};
+    if (node) ptrs.push_back({"node", node});
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
+    PrioritySetArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tree = priority_tree(leaf, node, L, nullptr); a.idx = (const long long *)idx; a.q_in = q; a.n = n;
+    return priority_apply(a, (hipStream_t)stream);
+}
+
+extern "C" int f110_ptree_pick(const uint32_t *leaf, const uint64_t *node, int64_t L, uint64_t seed, uint64_t first_draw, int32_t n, int64_t *idx_out,
+                               uint32_t *q_out, void *stream)
+{
+    const char *who = "f110_ptree_pick";
+    if (int rc = priority_tree_check(who, leaf, node, L)) return rc;
+    if (n < 0) return fail(F110_E_INVALID, "%s: n=%d", who, n);
+    if (!idx_out) return fail(F110_E_INVALID, "%s: null idx_out", who);
+    if (!q_out) return fail(F110_E_INVALID, "%s: null q_out", who);
+    if (n == 0) return F110_OK;
+    std::vector<DevicePtr> ptrs = {{"leaf", leaf}, {"idx_out", idx_out}, {"q_out", q_out}};
+    if (node) ptrs.push_back({"node", node});
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
+    const int per = PT_THREADS / 64;
+    hipLaunchKernelGGL(ptree_pick_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(PT_THREADS), 0, (hipStream_t)stream,
+                       priority_tree(leaf, node, L, nullptr), (unsigned long long)seed, (unsigned long long)first_draw, (int)n, (long long *)idx_out, q_out);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_priority_install(f110_handle *h, const f110_priority_config *cfg)
+{
+    const char *who = "f110_priority_install";
+    if (!h) return fail(F110_E_INVALID, "%s: null handle", who);
+    f110_handle::Priority &p = h->priority;
+    if (!cfg) { // removes the feature (the tree is the caller's)
+        if (!p.on) return F110_OK;
+        p.on = false; p.bound = false;
+        h->epoch++;
+        return F110_OK;
+    }
+    if (int rc = priority_config_check(who, cfg)) return rc;
+    if (!h->replay.on) return fail(F110_E_INVALID, "%s: no replay buffer is installed (f110_replay_install)", who);
+    const long long L = (long long)h->replay.cfg.steps * (long long)h->cfg.num_envs;
+    if (!priority_leaves_ok(L)) return fail(F110_E_INVALID, "%s: a ring of %lld transitions (1..%lld)", who, L, (long long)F110_PRIORITY_MAX_LEAVES);
+    p.cfg = *cfg;
+    p.on = true; p.bound = false;
+    h->epoch++;
+    return F110_OK;
+}
+
+extern "C" int f110_priority_bind(f110_handle *h, const f110_priority_buffers *b)
+{
+    const char *who = "f110_priority_bind";
+    if (!h || !b) return fail(F110_E_INVALID, "%s: null argument", who);
+    if (!h->priority.on || !h->replay.on) return fail(F110_E_INVALID, "%s: no priorities are installed (f110_priority_install)", who);
+    const long long L = (long long)h->replay.cfg.steps * (long long)h->cfg.num_envs;
+    if (int rc = priority_tree_check(who, b->leaf, b->node, L)) return rc;
+    if (!b->state) return fail(F110_E_INVALID, "%s: null state", who);
+    if ((uintptr_t)b->state % 8) return fail(F110_E_INVALID, "%s: state is not 8-byte aligned", who);
+    h->priority.bufs = *b;
+    h->priority.bound = true;
+    h->epoch++;
+    return F110_OK;
+}
+
+// `who` may run: priorities are installed and bound behind a ring that is
+static int priority_ready(const f110_handle *h, const char *who, ReplayRing &g, PriorityTree &t)
+{
+    const f110_handle::Priority &p = h->priority;
+    if (!p.on) return fail(F110_E_INVALID, "%s: no priorities are installed (f110_priority_install)", who);
+    if (!p.bound) return fail(F110_E_UNBOUND, "%s: f110_priority_bind has not been called", who);
+    if (int rc = replay_ready(h, who, g)) return rc;
+    t = priority_tree(p.bufs.leaf, p.bufs.node, g.steps * (long long)g.n_envs, h->d_err.get());
+    return F110_OK;
+}
+
+static int priority_push(const f110_handle *h, const ReplayRing &g, hipStream_t stream)
+{
+    PriorityPushArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tree = priority_tree(h->priority.bufs.leaf, h->priority.bufs.node, g.steps * (long long)g.n_envs, g.dev_err);
+    a.valid = g.valid; a.count = g.count; a.steps = g.steps; a.n_envs = g.n_envs; a.qmax = &h->priority.bufs.state->qmax;
+    const int waves = g.n_envs / PT_FANOUT + 2, per = PT_THREADS / 64;      // level-1 nodes a row of n_envs leaves can touch
+    hipLaunchKernelGGL(priority_push_kernel, dim3((unsigned)((waves + per - 1) / per)), dim3(PT_THREADS), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    if (a.tree.lay.levels >= 2) {
+        hipLaunchKernelGGL(priority_upper_kernel, dim3(1), dim3(PT_THREADS), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return F110_OK;
+}
+
+extern "C" int f110_priority_reset(f110_handle *h, void *stream)
+{
+    const char *who = "f110_priority_reset";
+    if (!h) return fail(F110_E_INVALID, "%s: null handle", who);
+    ReplayRing g;
+    PriorityTree t;
+    if (int rc = priority_ready(h, who, g, t)) return rc;
+    hipLaunchKernelGGL(priority_fill_kernel, dim3((unsigned)((t.lay.leaves + PT_THREADS - 1) / PT_THREADS)), dim3(PT_THREADS), 0, (hipStream_t)stream, t,
+                       (const uint8_t *)g.valid, (const uint32_t *)&h->priority.bufs.state->qmax);
+    HIP_TRY(hipGetLastError());
+    return priority_rebuild(t, (hipStream_t)stream);
+}
+
+extern "C" int f110_priority_sample(f110_handle *h, uint64_t seed, uint64_t *counter, int32_t n, int32_t nstep, double gamma, int64_t *indices,
+                                    int64_t *s_frame, int64_t *ns_frame, float *a_out, double *ret, uint8_t *d_out, uint8_t *ok, double *discount,
+                                    int32_t *span, uint32_t *prio, float *weight, void *stream)
+{
+    const char *who = "f110_priority_sample";
+    if (!h) return fail(F110_E_INVALID, "%s: null handle", who);
+    PrioritySampleArgs p;
+    memset(&p, 0, sizeof(p));
+    if (int rc = priority_ready(h, who, p.s.ring, p.tree)) return rc;
+    if (int rc = replay_nstep_scalars(who, n, nstep, gamma)) return rc;
+    if (!counter || !indices || !s_frame || !ns_frame || !a_out || !ret || !d_out || !ok || !discount || !span || !prio || !weight)
+        return fail(F110_E_INVALID, "%s: null argument", who);
+    if ((uintptr_t)counter % 8) return fail(F110_E_INVALID, "%s: the counter is not 8-byte aligned", who);
+    if (n == 0) return F110_OK;
+    ReplayNstepArgs &a = p.s;
+    a.seed = seed; a.counter = (const unsigned long long *)counter; a.n = n; a.nstep = nstep; a.gamma = gamma;
+    a.idx = (long long *)indices; a.s_frame = (long long *)s_frame; a.ns_frame = (long long *)ns_frame;
+    a.a = a_out; a.ret = ret; a.d = d_out; a.ok = ok; a.discount = discount; a.span = span;
+    p.prio = prio;
+    const int per = PT_THREADS / 64;
+    hipLaunchKernelGGL(priority_sample_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(PT_THREADS), 0, (hipStream_t)stream, p);
+    HIP_TRY(hipGetLastError());
+    PriorityWeightArgs w;
+    w.prio = prio; w.ok = ok; w.weight = weight; w.n = n; w.counter = (unsigned long long *)counter; w.state = h->priority.bufs.state;
+    hipLaunchKernelGGL(priority_weight_kernel, dim3(1), dim3(PT_THREADS), 0, (hipStream_t)stream, w);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+// f110_priority_update (td) and f110_priority_set (q): the set's rule on the rows with ok whose transition is valid
+static int priority_write(f110_handle *h, const char *who, const int64_t *idx, const uint8_t *ok, const float *td, const uint32_t *q, int32_t n,
+                          uint32_t *q_out, void *stream)
+{
+    if (!h) return fail(F110_E_INVALID, "%s: null handle", who);
+    PrioritySetArgs a;
+    memset(&a, 0, sizeof(a));
+    ReplayRing g;
+    if (int rc = priority_ready(h, who, g, a.tree)) return rc;
+    if (n < 0) return fail(F110_E_INVALID, "%s: n=%d", who, n);
+    if (!idx) return fail(F110_E_INVALID, "%s: null idx", who);
+    if (td ? !ok : !q) return fail(F110_E_INVALID, "%s: null %s", who, td ? "ok" : "q");
+    if (n == 0) return F110_OK;
+    a.idx = (const long long *)idx; a.ok = ok; a.q_in = q; a.td = td; a.valid = g.valid; a.n = n;
+    a.exponent = h->priority.cfg.exponent; a.eps = h->priority.cfg.eps; a.q_out = q_out; a.qmax = &h->priority.bufs.state->qmax;
+    return priority_apply(a, (hipStream_t)stream);
+}
+
+extern "C" int f110_priority_update(f110_handle *h, const int64_t *idx, const uint8_t *ok, const float *td, int32_t n, uint32_t *q_out, void *stream)
+{
+    if (h && !td) return fail(F110_E_INVALID, "f110_priority_update: null td");   // (without it the call would read as the set's)
+    return priority_write(h, "f110_priority_update", idx, ok, td, nullptr, n, q_out, stream);
+}
+
+extern "C" int f110_priority_set(f110_handle *h, const int64_t *idx, const uint32_t *q, int32_t n, void *stream)
+{
+    return priority_write(h, "f110_priority_set", idx, nullptr, nullptr, q, n, nullptr, stream);
 }
 
 // ---------------------------------------------------------------- episodes

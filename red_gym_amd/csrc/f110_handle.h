@@ -138,6 +138,13 @@ struct f110_handle {
         int rows = 0, cols = 0;
         f110_replay_buffers bufs;
     } replay;
+    // prioritized replay (f110_priority_install / _bind, f110_consumers.hip) behind the ring above: the configuration and the
+    // caller's tree; f110_replay_install switches it off
+    struct Priority {
+        bool on = false, bound = false;
+        f110_priority_config cfg;
+        f110_priority_buffers bufs;
+    } priority;
     // episode tracker (f110_episodes_install / _bind / _update, f110_consumers.hip): the configuration and the caller's arrays
     struct Episodes {
         bool on = false, bound = false;

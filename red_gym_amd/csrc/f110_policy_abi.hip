@@ -314,6 +314,25 @@ extern "C" int f110_sac_critic_loss(const float *q1, const float *q2, const floa
     return F110_OK;
 }
 
+extern "C" int f110_sac_critic_loss_weighted(const float *q1, const float *q2, const float *tv, const float *w, int64_t n, float *loss,
+                                             float *grad_q1, float *grad_q2, float *td_out, void *stream)
+{
+    const char *who = "f110_sac_critic_loss_weighted";
+    if (int rc = sacloss_rows(who, n)) return rc;
+    if (!q1 || !q2 || !tv || !loss) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if (!w) return fail(F110_E_INVALID, "%s: null w", who);
+    std::vector<DevicePtr> ptrs = {{"q1", q1}, {"q2", q2}, {"tv", tv}, {"w", w}, {"loss", loss}};
+    if (grad_q1) ptrs.push_back({"grad_q1", grad_q1});
+    if (grad_q2) ptrs.push_back({"grad_q2", grad_q2});
+    if (td_out) ptrs.push_back({"td_out", td_out});
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
+    SaclossPlan p = sacloss_plan(n, false, false, 0.0);
+    p.a.q1 = q1; p.a.q2 = q2; p.a.tv = tv; p.a.w = w; p.a.loss = loss; p.a.grad_q1 = grad_q1; p.a.grad_q2 = grad_q2; p.a.td_out = td_out;
+    F110_LAUNCH(sac_critic_loss_weighted_kernel, p.l, (hipStream_t)stream, p.a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
 // both actor-loss entry points; alpha_dev: where alpha is read on the device, NULL: `alpha`
 static int sac_actor_loss(const char *who, const void *logp, int32_t logp_fp64, const float *qn, double alpha, bool by_pointer, const double *alpha_dev,
                           int64_t n, float *loss, void *grad_logp, float *grad_qn, void *stream)

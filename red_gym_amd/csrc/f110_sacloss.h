@@ -62,6 +62,39 @@ static __global__ __launch_bounds__(SL_THREADS) void sac_critic_loss_kernel(Sacl
     }
 }
 
+// The critic loss under importance weights (prioritized replay): t_i = double(w[i]) * (e * e), grad_q_c[i] = ((q_c[i] - tv[i]) * k2n) * w[i],
+// td_out[i] = max |q_c[i] - tv[i]| in fp32.  The same chains, tree and division; a kernel of its own beside the unweighted one.
+static __global__ __launch_bounds__(SL_THREADS) void sac_critic_loss_weighted_kernel(SaclossArgs a)
+{
+    __shared__ double s1[SL_THREADS], s2[SL_THREADS];
+    const int tid = threadIdx.x;
+    for (long long i = (long long)blockIdx.x * SL_THREADS + tid; i < a.n; i += (long long)gridDim.x * SL_THREADS) {
+        const float tv = a.tv[i], w = a.w[i];
+        const float d1 = a.q1[i] - tv, d2 = a.q2[i] - tv;
+        if (a.grad_q1) { const float g = d1 * a.k2n; a.grad_q1[i] = g * w; }
+        if (a.grad_q2) { const float g = d2 * a.k2n; a.grad_q2[i] = g * w; }
+        if (a.td_out) a.td_out[i] = fmaxf(fabsf(d1), fabsf(d2));
+    }
+    if (blockIdx.x != 0) return;
+    double c1 = 0.0, c2 = 0.0;
+    for (long long i = tid; i < a.n; i += SL_THREADS) {
+        const double tv = (double)a.tv[i], w = (double)a.w[i];
+        const double e1 = (double)a.q1[i] - tv, e2 = (double)a.q2[i] - tv;
+        const double x1 = e1 * e1, x2 = e2 * e2;
+        const double t1 = w * x1, t2 = w * x2;
+        c1 = c1 + t1;
+        c2 = c2 + t2;
+    }
+    s1[tid] = c1;
+    s2[tid] = c2;
+    sacloss_tree(s1, tid);
+    sacloss_tree(s2, tid);
+    if (tid == 0) {
+        a.loss[0] = (float)(s1[0] / (double)a.n);
+        a.loss[1] = (float)(s2[0] / (double)a.n);
+    }
+}
+
 template <bool F64> static __global__ __launch_bounds__(SL_THREADS) void sac_actor_loss_kernel(SaclossArgs a)
 {
     __shared__ double s[SL_THREADS];

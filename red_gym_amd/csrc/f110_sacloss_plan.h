@@ -30,6 +30,8 @@ struct SaclossArgs {
     float *grad_qn;                 // [n] or NULL
     const double *alpha_dev;        // actor loss, f110_sac_actor_loss_alpha_dev: alpha is read here and alpha / n formed on the device;
                                     // NULL (every other entry): alpha, glp64 and glp32 above
+    const float *w;                 // f110_sac_critic_loss_weighted: [n] the rows' importance weights
+    float *td_out;                  // the same entry: [n] max |q_c - tv| or NULL
 };
 
 // One launch of sac_critic_loss_kernel (inst 0) or sac_actor_loss_kernel (inst 1 + logp_fp64) on 1 <= n <= SL_MAX_ROWS rows.  The

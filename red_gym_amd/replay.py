@@ -77,12 +77,14 @@ class ReplayBuffer(Consumer):
     frames [T + 1, B, rows, words] int64 (bit-packed), actions [T, B, action_dim] fp32, rewards [T, B] fp64, dones and valid
     [T, B] uint8, count and chain_start [1] int64, t_seen [B] fp64, last_valid [B] uint8 and action_in [B, action_dim] fp32 (what
     the next push stores: F110VecEnv.replay_action).  A transition is named by index = step slot * B + env.  The ring is no part
-    of state_dict(): save() / load() hand it over explicitly."""
+    of state_dict(): save() / load() hand it over explicitly.  `priorities` is the ring's PriorityTree (red_gym_amd.priority) while
+    record_replay(..., priorities=...) is on, else None: sample_priority_dev draws from it, save() and load() carry its leaves and state."""
     NAME = 'replay'
     INFO = {'replay_count': 'count', 'replay_valid': 'last_valid'}
     STATE = {}
     RING = ('frames', 'actions', 'rewards', 'dones', 'valid', 'count', 'chain_start', 't_seen')
     cfg, rows, cols, _draws = None, 0, 0, 0
+    priorities = None               # the PriorityTree while record_replay(priorities=...) is on (red_gym_amd.priority)
     generation = 0                  # installs made: a graph captured on the ring of an earlier one holds freed addresses (SACAgent)
 
     steps = property(lambda self: self.cfg.steps)
@@ -97,6 +99,7 @@ class ReplayBuffer(Consumer):
         rows, cols = eng.shaper.cfg.rows, eng.shaper.cfg.cols
         T, B, ad = c.steps, eng.B, c.action_dim
         self.buf, self.info = None, {}          # (the old ring goes before the new one is allocated)
+        self.priorities = None                  # (the library drops the priorities with the ring they were built over)
         try:
             with torch.cuda.device(eng.device):
                 z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=eng.device)  # noqa: E731
@@ -118,7 +121,19 @@ class ReplayBuffer(Consumer):
         if self.on:
             _lib.check(self.eng.lib.f110_replay_install(self.eng._h, None))
             torch.cuda.synchronize(self.eng.device)   # an enqueued push may still write the ring
-        self.cfg, self.on, self.buf, self.info = None, False, None, {}
+        self.cfg, self.on, self.buf, self.info, self.priorities = None, False, None, {}, None
+
+    def set_priorities(self, priorities):
+        """Switches prioritized replay on over the ring as it stands (True or a dict of red_gym_amd.priority.DEFAULTS' keys: every valid
+        transition enters with the word of priority 1.0), or off (None or False: no launch remains)."""
+        if not self.on:
+            raise ValueError('replay: the buffer is off (record_replay())')
+        if self.priorities is not None:
+            self.priorities.remove()
+            self.priorities = None
+        if priorities is not None and priorities is not False:
+            from .priority import PriorityTree
+            self.priorities = PriorityTree(self, priorities)
 
     def restart(self):
         """Breaks the chain of frames: the next push stores a frame and an invalid transition; what is stored stays."""
@@ -130,7 +145,10 @@ class ReplayBuffer(Consumer):
 
     def save(self):
         """The ring and its counter as a dict of new tensors (gigabytes at the reference's capacity)."""
-        return {k: self.buf[k].clone() for k in self.RING}
+        d = {k: self.buf[k].clone() for k in self.RING}
+        if self.priorities is not None:
+            d.update(self.priorities.save())    # (the leaves and the state; the nodes are rebuilt on load)
+        return d
 
     def load(self, d):
         """Restores what save() returned into a ring of the same shape; ValueError otherwise.  The chain of frames is restored
@@ -140,6 +158,8 @@ class ReplayBuffer(Consumer):
                 raise ValueError('replay: the saved ring does not fit (%s)' % k)
         for k in self.RING:
             self.buf[k].copy_(d[k])
+        if self.priorities is not None:
+            self.priorities.load(d)             # (a dict that carries no priorities resets the tree over the restored ring)
 
     def __len__(self):
         """Valid transitions held (one small reduction and one synchronisation: not for the step path)."""
@@ -310,16 +330,47 @@ class ReplayBuffer(Consumer):
                                                   eng._stream()))
         return frames, o['s_idx'], o['ns_idx'], o['a'], o['r'], o['d'], o['ok'], o['indices']
 
-    def _sample_shapes(self, n, nstep=1):
+    def sample_priority_dev(self, batch_size, counter, seed=None, out=None, nstep=1, gamma=None):
+        """f110_priority_sample: sample_frames_dev with draws in proportion to the transitions' priority words (record_replay(...,
+        priorities=...)), from the caller's device counter, in two launches.  Returns the n-step form's tuple whatever nstep is --
+        (frames, s_idx, ns_idx, a, r, d, ok, indices, discount, span) -- with prio [n] int32 (the bits of the drawn uint32 words) and
+        weight [n] fp32 appended: the importance weights (N P(i))^-beta over the batch's maximum, exactly 1.0 on the rows of the
+        smallest word and 0 where ok is 0, for the beta the tree held before this call moved it on.  out: sample_out(n, nstep,
+        priorities=True).  Device tensors, no synchronisation; a captured call replays with fresh draws."""
+        if not self.on or self.priorities is None:
+            raise ValueError('replay: priorities are off (record_replay(..., priorities=True))')
+        nstep, gamma = self._nstep(nstep, gamma)
+        eng, n = self.eng, int(batch_size)
+        if not torch.is_tensor(counter) or counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != torch.device(eng.device):
+            raise ValueError('replay: counter must be a [1] int64 tensor on %s' % (eng.device,))
+        o = self.sample_out(n, nstep, priorities=True) if out is None else out
+        for k, (shape, dt) in self._sample_shapes(n, nstep, True).items():
+            t = o.get(k)
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != torch.device(eng.device) or not t.is_contiguous():
+                raise ValueError('replay: out[%r] must be a contiguous %s tensor of shape %s on %s' % (k, dt, shape, eng.device))
+        T, B = self.cfg.steps, eng.B
+        frames = self.buf['frames'].view((T + 1) * B, self.rows, words(self.cols))
+        with torch.cuda.device(eng.device):
+            _lib.check(eng.lib.f110_priority_sample(eng._h, self._seed(seed), counter.data_ptr(), n, nstep, gamma, o['indices'].data_ptr(),
+                                                    o['s_idx'].data_ptr(), o['ns_idx'].data_ptr(), o['a'].data_ptr(), o['r'].data_ptr(),
+                                                    o['d'].data_ptr(), o['ok'].data_ptr(), o['discount'].data_ptr(), o['span'].data_ptr(),
+                                                    o['prio'].data_ptr(), o['weight'].data_ptr(), eng._stream()))
+        return frames, o['s_idx'], o['ns_idx'], o['a'], o['r'], o['d'], o['ok'], o['indices'], o['discount'], o['span'], o['prio'], o['weight']
+
+    def _sample_shapes(self, n, nstep=1, priorities=False):
         shapes = {'indices': ((n,), torch.int64), 's_idx': ((n,), torch.int64), 'ns_idx': ((n,), torch.int64),
                   'a': ((n, self.cfg.action_dim), torch.float32), 'r': ((n,), torch.float64), 'd': ((n,), torch.uint8), 'ok': ((n,), torch.uint8)}
-        if nstep > 1:
+        if nstep > 1 or priorities:
             shapes.update({'discount': ((n,), torch.float64), 'span': ((n,), torch.int32)})
+        if priorities:
+            shapes.update({'prio': ((n,), torch.int32), 'weight': ((n,), torch.float32)})
         return shapes
 
-    def sample_out(self, batch_size, nstep=1):
-        """The tensors sample_frames_dev writes, newly allocated: what its `out` takes ('discount' and 'span' with nstep > 1 only)."""
-        return {k: torch.empty(shape, dtype=dt, device=self.eng.device) for k, (shape, dt) in self._sample_shapes(int(batch_size), int(nstep)).items()}
+    def sample_out(self, batch_size, nstep=1, priorities=False):
+        """The tensors sample_frames_dev writes, newly allocated: what its `out` takes ('discount' and 'span' with nstep > 1 only).
+        priorities=True: what sample_priority_dev writes ('discount' and 'span' whatever nstep is, 'prio' and 'weight')."""
+        return {k: torch.empty(shape, dtype=dt, device=self.eng.device)
+                for k, (shape, dt) in self._sample_shapes(int(batch_size), int(nstep), bool(priorities)).items()}
 
     def bytes_held(self):
         return sum(self.buf[k].numel() * self.buf[k].element_size() for k in ('frames', 'actions', 'rewards', 'dones', 'valid'))

@@ -108,11 +108,17 @@ class SACAgent:
     is the UNCORRECTED n-step return: no importance weights for the off-policy steps inside the span and no entropy bonus on the
     intermediate steps -- the entropy term enters through the bootstrap only, as in the common implementations.  nstep is
     configuration, not state: state_dict() does not hold it.  With nstep = 1 nothing changes: the same launches, graph key and bits.
+    per: True -- prioritized replay (Schaul et al.) on a ring with record_replay(..., priorities=...): update, capture_update and
+    update_graph draw with ReplayBuffer.sample_priority_dev (which composes with nstep), the critics' loss takes the batch's importance
+    weights (sacloss.critic_loss(weight=...)) and the priorities of the drawn transitions are written back right behind it from max(|q1
+    - tv|, |q2 - tv|) (PriorityTree.update), all captured with the rest; the actor's loss stays unweighted.  ValueError from those three
+    on a ring without priorities.  False, the default, changes nothing: the same launches, graph key and bits, on any ring.
     Attributes: actor, critics [2], targets [2]; actor_opt, critic_opts [2] (SacAdam; a critic's also moves its target); draws, the [1]
     int64 draw counter on the device; sample, the tensors of the batch the last update drew (sample['indices'] names the transitions)."""
 
     def __init__(self, action_dim=16, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, rows=256, cols=256, hidden=512,
-                 on=255.0, device='cuda', networks=None, target_entropy=None, alpha_lr=3e-4, init_alpha=0.2, draws='torch', seed=0, nstep=1):
+                 on=255.0, device='cuda', networks=None, target_entropy=None, alpha_lr=3e-4, init_alpha=0.2, draws='torch', seed=0, nstep=1,
+                 per=False):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ValueError('SACAgent: device %s: there is no CPU path' % (self.device,))
@@ -122,6 +128,7 @@ class SACAgent:
         if isinstance(nstep, bool) or not isinstance(nstep, int) or not 1 <= nstep <= MAX_NSTEP:
             raise ValueError('SACAgent: nstep %r: an int in 1..%d' % (nstep, MAX_NSTEP))
         self.nstep = nstep
+        self.per = bool(per)
         self.temperature = None
         if isinstance(alpha, str):
             if alpha != 'auto':
@@ -203,9 +210,10 @@ class SACAgent:
                 raise ValueError('SACAgent: eps_next and eps_new must be fp32 [%d, %d] on %s' % (n, self.action_dim, self.device))
         return eps[0], eps[1]
 
-    def _update(self, frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, losses, discount=None):
+    def _update(self, frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, losses, discount=None, weight=None, writeback=None):
         """:544-580 on one batch; the three losses go to `losses` [3] (actor, critic1, critic2), which is returned.  discount: [n] fp64,
-        the target's discount per row (r is then the n-step return); None: gamma."""
+        the target's discount per row (r is then the n-step return); None: gamma.  weight: [n] fp32 importance weights of the critics'
+        loss; writeback = (priorities, indices, ok): the tree that then takes the rows' new TD errors."""
         actor, critics, targets = self.actor, self.critics, self.targets
         if eps_next is None and self.source is not None:
             n = int(s_idx.shape[0])
@@ -217,7 +225,13 @@ class SACAgent:
                            self.alpha, dense=True)
         q, _ = twin_q([c.trunk(frames, s_idx) for c in critics], a, *_heads(critics), dense=True)     # :551-552, a as the ring stores it (fp32)
         grad_q = torch.empty_like(q)
-        critic_loss(q[0], q[1], tv, loss=losses[1:3], grad=grad_q)               # :553-554
+        if weight is None:
+            critic_loss(q[0], q[1], tv, loss=losses[1:3], grad=grad_q)           # :553-554
+        else:
+            td = torch.empty((int(s_idx.shape[0]),), dtype=torch.float32, device=self.device)
+            critic_loss(q[0], q[1], tv, loss=losses[1:3], grad=grad_q, weight=weight, td=td)
+            if writeback is not None:
+                writeback[0].update(writeback[1], writeback[2], td)
         for opt in self.critic_opts:
             opt.zero_grad()
         torch.autograd.backward((q,), (grad_q,))
@@ -233,18 +247,26 @@ class SACAgent:
         self.actor_opt.step()                                                    # :570-572
         return losses
 
-    def update_batch(self, batch, eps=None):
+    def update_batch(self, batch, eps=None, replay=None):
         """One update on a batch that is given, not drawn: a dict with 'frames' [m, rows, words] int64, 's_idx' and 'ns_idx' [n] int64
         rows of it (-1: a zero frame), 'a' [n, action_dim] fp32, 'r' [n] fp64 and 'd' [n] uint8, as ReplayBuffer.sample_frames returns
         them.  An optional 'discount' [n] fp64 is the target's discount per row in gamma's place ('r' is then the n-step return and
         'ns_idx', 'd' those of the span's end, as ReplayBuffer.frames_at with nstep > 1 returns them); without it gamma, whatever the agent's nstep.
+        An optional 'weight' [n] fp32 weighs the critics' loss row by row (ReplayBuffer.sample_priority_dev's importance weights); with
+        'indices' [n] int64 and 'ok' [n] uint8 beside it and `replay` (a ring with priorities) the rows' new priorities are written back
+        as update() does with per=True; without them nothing is written back.
         eps = (eps_next, eps_new), fp32 [n, action_dim], replace the two torch.randn draws.  Returns the new [3] fp32 loss tensor
         (actor, critic1, critic2) on the device; no synchronisation."""
         n = int(batch['s_idx'].shape[0])
         eps_next, eps_new = self._eps(eps, n)
         losses = torch.empty((3,), dtype=torch.float32, device=self.device)
+        weight, writeback = batch.get('weight'), None
+        if weight is not None and replay is not None and 'indices' in batch and 'ok' in batch:
+            if replay.priorities is None:
+                raise ValueError('SACAgent: the ring has no priorities (record_replay(..., priorities=True))')
+            writeback = (replay.priorities, batch['indices'], batch['ok'])
         return self._update(batch['frames'], batch['s_idx'], batch['ns_idx'], batch['a'], batch['r'], batch['d'], eps_next, eps_new, losses,
-                            batch.get('discount'))
+                            batch.get('discount'), weight, writeback)
 
     def _check_replay(self, replay):
         if not replay.on:
@@ -252,6 +274,8 @@ class SACAgent:
         if (replay.rows, replay.cols, replay.action_dim) != (self.rows, self.cols, self.action_dim) or replay.eng.device != self.device:
             raise ValueError('SACAgent: the ring holds %d x %d images and %d action values on %s; the agent takes %d x %d and %d on %s'
                              % (replay.rows, replay.cols, replay.action_dim, replay.eng.device, self.rows, self.cols, self.action_dim, self.device))
+        if self.per and replay.priorities is None:
+            raise ValueError('SACAgent: per=True, but the ring has no priorities (record_replay(..., priorities=True))')
 
     def update(self, replay, batch_size=64, eps=None, check=False):
         """SACAgent.update (src/SAL.py:521-580) from the ring `replay` (F110VecEnv.replay): batch_size transitions drawn on the
@@ -265,12 +289,22 @@ class SACAgent:
         eps_next, eps_new = self._eps(eps, n)
         if check and len(replay) < n:
             return torch.zeros((3,), dtype=torch.float32, device=self.device)
-        self.sample = replay.sample_out(n, self.nstep)
-        frames, s_idx, ns_idx, a, r, d, discount = self._draw(replay, n, self.sample)
-        return self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, torch.empty((3,), dtype=torch.float32, device=self.device), discount)
+        self.sample = replay.sample_out(n, self.nstep, priorities=self.per)
+        frames, s_idx, ns_idx, a, r, d, discount, weight, writeback = self._draw(replay, n, self.sample)
+        return self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, torch.empty((3,), dtype=torch.float32, device=self.device), discount,
+                            weight, writeback)
 
     def _draw(self, replay, n, out):
-        """The batch of an update drawn into `out` with the agent's draw counter -> (frames, s_idx, ns_idx, a, r, d, discount or None)."""
+        """The batch of an update drawn into `out` with the agent's draw counter -> (frames, s_idx, ns_idx, a, r, d, discount or None,
+        weight or None, writeback or None): the last two with per=True only."""
+        if self.per:
+            got = replay.sample_priority_dev(n, self.draws, out=out, nstep=self.nstep, gamma=self.gamma)
+            # (with nstep = 1 the target takes gamma by value, as without priorities: got[8] holds its bits in every row)
+            return got[:6] + (None if self.nstep == 1 else got[8], got[11], (replay.priorities, got[7], got[6]))
+        got = self._draw_uniform(replay, n, out)
+        return got + (None, None)
+
+    def _draw_uniform(self, replay, n, out):
         if self.nstep == 1:
             return replay.sample_frames_dev(n, self.draws, out=out)[:6] + (None,)
         got = replay.sample_frames_dev(n, self.draws, out=out, nstep=self.nstep, gamma=self.gamma)
@@ -284,6 +318,9 @@ class SACAgent:
         t = self.temperature
         key = key if t is None else key + ((t.lr, t.betas, t.eps, t.target_entropy),)
         key = key if self.nstep == 1 else key + (('nstep', self.nstep, self.gamma),)
+        if self.per:                                # (a ring that lost its priorities: another key, and the capture refuses it)
+            p = replay.priorities
+            key = key + (('per', self.gamma) + ((None,) if p is None else (p.leaf.data_ptr(), p.state.data_ptr())),)
         return key if self.source is None else key + (('source', self.source.state.data_ptr()),)
 
     def capture_update(self, replay, batch_size=64, draws=True):
@@ -301,7 +338,7 @@ class SACAgent:
         if key != self._g_key:
             self._graphs = {}
             self._g_key, self._g_replay = key, replay
-            self._g_sample = replay.sample_out(n, self.nstep)
+            self._g_sample = replay.sample_out(n, self.nstep, priorities=self.per)
             self._g_eps = [torch.zeros((n, self.action_dim), dtype=torch.float32, device=dev) for _ in range(2)]
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(dev)
@@ -309,9 +346,9 @@ class SACAgent:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.stream(side), torch.cuda.graph(g, stream=side):
             self.zero_grad(set_to_none=True)
-            frames, s_idx, ns_idx, a, r, d, discount = self._draw(replay, n, self._g_sample)
+            frames, s_idx, ns_idx, a, r, d, discount, weight, writeback = self._draw(replay, n, self._g_sample)
             eps_next, eps_new = (None, None) if draws else self._g_eps
-            self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, self._g_losses, discount)
+            self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, self._g_losses, discount, weight, writeback)
         cur.wait_stream(side)
         self._graphs[bool(draws)] = g
         self.captures += 1

@@ -33,12 +33,15 @@ def _loss(who, loss, k, dev):
     return loss
 
 
-def critic_loss(q1, q2, tv, loss=None, grad=None):
+def critic_loss(q1, q2, tv, loss=None, grad=None, weight=None, td=None):
     """f110_sac_critic_loss: (loss [2] fp32, grad_q1 [n], grad_q2 [n] fp32) for q1, q2, tv [n] (or [n, 1]) fp32 on one GPU: loss[c] =
     mean((q_c - tv) ** 2) summed in the contract's order, grad_q_c = (q_c - tv) * float(2 / n), which for n a power of two is autograd's
     gradient of F.mse_loss(q_c, tv) bit for bit.  loss: a [2] fp32 tensor to write into (a slice of the agent's [3]); grad: a [2, n] fp32
     tensor whose rows receive the two gradients (twin_q returns q as such a tensor: one backward call takes it whole).  One launch on the
-    current stream, no synchronisation."""
+    current stream, no synchronisation.
+    weight: [n] fp32 importance weights (ReplayBuffer.sample_priority_dev's) -- f110_sac_critic_loss_weighted, a kernel of its own: loss[c]
+    = mean(weight * (q_c - tv) ** 2) in the same order and grad_q_c = ((q_c - tv) * float(2 / n)) * weight; td: an [n] fp32 tensor that
+    then receives max(|q1 - tv|, |q2 - tv|), what PriorityTree.update takes (td needs a weight; ones give the unweighted bits)."""
     who = 'critic_loss'
     q1 = _rows(who, 'q1', q1)
     n, dev = int(q1.shape[0]), q1.device
@@ -50,6 +53,18 @@ def critic_loss(q1, q2, tv, loss=None, grad=None):
         grad = torch.empty((2, n), dtype=torch.float32, device=dev)
     elif not torch.is_tensor(grad) or grad.dtype != torch.float32 or tuple(grad.shape) != (2, n) or grad.device != dev or not grad.is_contiguous():
         raise ValueError('%s: grad must be a contiguous fp32 [2, %d] tensor on %s' % (who, n, dev))
+    if weight is None and td is not None:
+        raise ValueError('%s: td is written by the weighted kernel only (give weight)' % who)
+    if weight is not None:
+        weight = _rows(who, 'weight', weight, n)
+        if weight.device != dev:
+            raise ValueError('%s: weight must be on %s' % (who, dev))
+        if td is not None and (not torch.is_tensor(td) or td.dtype != torch.float32 or tuple(td.shape) != (n,) or td.device != dev or not td.is_contiguous()):
+            raise ValueError('%s: td must be a contiguous fp32 [%d] tensor on %s' % (who, n, dev))
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().f110_sac_critic_loss_weighted(q1.data_ptr(), q2.data_ptr(), tv.data_ptr(), weight.data_ptr(), n, loss.data_ptr(),
+                                                                 grad[0].data_ptr(), grad[1].data_ptr(), _lib.ptr(td), _lib.stream(dev)))
+        return loss, grad[0], grad[1]
     with torch.cuda.device(dev):
         _lib.check(_lib.load().f110_sac_critic_loss(q1.data_ptr(), q2.data_ptr(), tv.data_ptr(), n, loss.data_ptr(), grad[0].data_ptr(),
                                                     grad[1].data_ptr(), _lib.stream(dev)))

@@ -221,7 +221,7 @@ class F110VecEnv(object):
         return out.view(self.num_envs, self.num_agents, 2)
 
     # ------------------------------------------------------------------ replay buffer
-    def record_replay(self, capacity=None, steps=None, action_dim=16):
+    def record_replay(self, capacity=None, steps=None, action_dim=16, priorities=None):
         """Switches the replay buffer on: the ReplayBuffer of the reference's RL consumer (src/SAL.py:447-463) and the push of
         its training loop (:996-1001) on the GPU.  `capacity` counts transitions as the reference's does: the ring has steps =
         capacity // num_envs step slots for all envs (or give `steps` itself; at least 2).  From then on reset, step, step_graph
@@ -238,13 +238,22 @@ class F110VecEnv(object):
         not part of state_dict().  env.replay.sample(batch_size) returns (s, a, r, ns, d, ok) on the device.
         record_replay(None) or record_replay(False) switches it off and frees the ring: no launch, no allocation, no info key
         remains.  ValueError while shape_rewards() is off; switching the shaper off, or installing it again with another image
-        size, removes the buffer too."""
+        size, removes the buffer too.
+        priorities: None (the default: uniform draws, nothing more is launched), True or a dict of exponent=0.6, eps=1e-6, beta=0.4,
+        beta_end=1.0, beta_updates=100000 -- prioritized replay (red_gym_amd.priority): an exact integer sum tree over the ring on the
+        device, exposed as env.replay.priorities.  Every push then gives its transitions the largest priority seen so far,
+        env.replay.sample_priority_dev draws in proportion to (|td| + eps)^exponent and returns importance weights for beta, which goes
+        from `beta` to `beta_end` in `beta_updates` samples, and env.replay.priorities.update writes new TD errors back."""
         if not capacity and steps is None:
             self.eng.replay.remove()
             return
         if not self.eng.shaper.on:
             raise ValueError('record_replay: the reward shaper is off (shape_rewards())')
+        if priorities is not None and priorities is not False:
+            from .priority import make_options
+            make_options(priorities)            # (refused before the ring is replaced)
         self.eng.replay.install(capacity=None if capacity is True else capacity, steps=steps, action_dim=action_dim)
+        self.eng.replay.set_priorities(priorities)
 
     @property
     def replay(self):
