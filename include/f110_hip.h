@@ -321,7 +321,7 @@ int f110_launch_epoch(f110_handle *h, int64_t *epoch);
 
 /* The form of the step's scan (performance only; results do not depend on it).  Besides the classic form -- two cars per
  * workgroup sharing one 1 024-slot LDS copy of the map's distance LUT -- every install of map slot 0 builds two COMPACT forms (two more cell
- * tables: 2 x the cell table's bytes, 10 MB at 1 600 x 1 600), S = 256 and 512: an LDS image of the LUT's first S - 2 ranks and a cell table in which every cell of a higher rank carries the far
+ * tables and the byte table of f110_scan_codes_info: 2.5 x the cell table's bytes, 13 MB at 1 600 x 1 600), S = 256 and 512: an LDS image of the LUT's first S - 2 ranks and a cell table in which every cell of a higher rank carries the far
  * marker (such cells take the second table, as cells beyond the classic image always did).  A compact form runs workgroups of
  * one wave, each with its own image.  It applies to the step's scan on a single map whose origin is unrotated and whose
  * resolution is a power of two; the rule that picks it (scan_compact_choice in csrc/f110_scan_plan.h) reads, per form, the
@@ -348,6 +348,13 @@ int f110_scan_form_info(f110_handle *h, int32_t n_cars, int32_t *form, double *o
  * (tests, A/B runs); neither value changes which form is launched.
  * f110_scan_rows_info: *lds = 1 where a step of n_cars cars with an fp32 output stages its rows now, else 0. */
 int f110_scan_rows_info(f110_handle *h, int32_t n_cars, int32_t *lds);
+/* The cell codes of the step's scan (performance only).  The codes of the compact form of 256 slots are multiples of 8 below
+ * 2 048, so every install of map slot 0 also builds that form's table as BYTES (the slot, code >> 3) in strips of 16 columns:
+ * half the cell table's bytes more, and a 128-byte line then holds 8 rows x 16 columns of cells instead of 8 x 8.  The launch
+ * that stages its rows in LDS (above) reads that table.  The environment variable F110_SCAN_CODES = byte | word, read once per
+ * process, overrides the rule (tests, A/B runs); neither value changes the form or where the rows are staged.
+ * f110_scan_codes_info: *bytes = 1 where a step of n_cars cars with an fp32 output reads byte codes now, else 0. */
+int f110_scan_codes_info(f110_handle *h, int32_t n_cars, int32_t *bytes);
 
 /* The step as a HIP graph the library builds itself, for callers without a capturing framework and as the reference
  * point for framework captures: F110_GRAPH_NODES = one kernel node per kernel of f110_step(actions_dev), chained

@@ -1,7 +1,12 @@
 // f110_map.h -- the cell-table format of a map, shared by the host code that builds the tables (f110_maps.hip), the device
 // pipeline that builds them (f110_mapgen.h) and the scan that reads them (f110_scan.h).  No kernels.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#else // a plain host compile (tests/test_scan_bytes_cpu.py holds the layout functions): the qualifiers say nothing there
+#define __host__
+#define __device__
+#endif
 #include <stddef.h>
 #include <stdint.h>
 
@@ -49,6 +54,23 @@ __host__ __device__ inline int map_rows_padded(int H) { return ((H + 2 + 7) >> 3
 __host__ __device__ inline size_t map_cells(int H, int W) { return (size_t)((W >> 3) + 2) * map_rows_padded(H) * 8; } // strip 0 only holds the left border column
 // element index of map cell (r, c), -1 <= r <= H, -1 <= c <= W
 __host__ __device__ inline size_t cell_elem(int r, int c, int Hp) { return ((size_t)((c >> 3) + 1) * Hp + (size_t)(r + 1)) * 8 + (size_t)(c & 7); }
+// Byte table of the compact form of 256 slots.  Its codes are multiples of 8 below 2 048 -- 8 bits of information -- so the cell
+// holds the SLOT, compact_code(code, 256) >> 3 (0: the border / dt[-1,-1], 255: the far marker), and the march shifts it back
+// into the LDS byte offset.  Strips of 16 columns, 16 bytes per row inside a strip, so strip_bytes = Hp * 16 is the u16
+// table's and a 128-B line holds 8 rows x 16 columns: map cell (r, c) at [(c >> 4) + 1][r + 1][c & 15], byte offset
+// (c >> 4) * (strip_bytes - 16) + c + (r << 4) + strip_bytes + 16.  Border and padding hold 0 as in the u16 tables.
+__host__ __device__ constexpr unsigned byte_code(unsigned code) { return compact_code(code, LUT_COMPACT[0]) >> 3; }
+__host__ __device__ inline size_t map_cells_b(int H, int W) { return (size_t)((W >> 4) + 2) * map_rows_padded(H) * 16; } // strip 0 only holds the left border column
+__host__ __device__ inline size_t cell_elem_b(int r, int c, int Hp) { return ((size_t)((c >> 4) + 1) * Hp + (size_t)(r + 1)) * 16 + (size_t)(c & 15); }
+// the u16 table's element of the cell that byte element i stands for (border, padding and the columns past W included: the u16
+// table's padding holds 0 too), or (size_t)-1 where the u16 table has no such element (strips past its last one)
+__host__ __device__ inline size_t cell_elem_of_byte(size_t i, int Hp, int W)
+{
+    const size_t strip = i / ((size_t)Hp * 16), row = i / 16 % (size_t)Hp, col = i % 16;
+    const long long c = ((long long)strip - 1) * 16 + (long long)col; // -16 .. 16 * ((W >> 4) + 1) - 1
+    if (c < -1 || c > W) return (size_t)-1;                           // outside the border columns: padding
+    return ((size_t)((c >> 3) + 1) * Hp + row) * 8 + (size_t)(c & 7);
+}
 
 struct MapDev {
     const uint16_t *cells;  // padded strips [(W >> 3) + 2][Hp][8] of LDS byte offsets
@@ -63,6 +85,8 @@ struct MapDev {
     unsigned lut_len;       // entries of lut
     const uint16_t *cells_c[N_COMPACT];  // compact cell tables (layout and size of `cells`) for S = LUT_COMPACT[i], or NULL
     const double *lut_lds_c[N_COMPACT];  // [S] their LDS images
+    const uint8_t *cells_b;              // byte table of cells_c[0] (16-column strips, map_cells_b elements), or NULL
+    unsigned cells_b_bytes;
 };
 
 } // namespace f110

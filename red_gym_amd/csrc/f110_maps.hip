@@ -4,13 +4,15 @@
 
 // The compact forms of a map (f110_map.h) beside its classic tables, derived from them on the device.  They are an extra: a
 // table beyond COMPACT_MAX_BYTES, or an allocation or copy that fails, leaves the slot with the classic form alone.  Cost: two
-// more cell tables, 2 x cells_bytes (10 MB at 1 600 x 1 600), for slot 0 only.
+// more cell tables and the byte table of the 256-slot one (half a table), 2.5 x cells_bytes (13 MB at 1 600 x 1 600), for
+// slot 0 only.
 constexpr size_t COMPACT_MAX_BYTES = (size_t)64 << 20;
-static void build_compact(f110_handle::MapSlot &ns)
+static void build_compact(f110_handle::MapSlot &ns, int H, int W)
 {
-    const size_t n = ns.d_cells.size();
+    const size_t n = ns.d_cells.size(), n_b = map_cells_b(H, W);
     if (n * sizeof(uint16_t) > COMPACT_MAX_BYTES) return;
     DevBuf<uint16_t> cells[N_COMPACT];
+    DevBuf<uint8_t> cells_b;
     DevBuf<double> img[N_COMPACT];
     DevBuf<unsigned> counts;
     double classic[LUT_COMPACT[N_COMPACT - 1]];
@@ -27,12 +29,18 @@ static void build_compact(f110_handle::MapSlot &ns)
                            cells[0].get(), cells[1].get(), counts.get());
         ok = hipGetLastError() == hipSuccess && hipMemcpy(cnt, counts.get(), sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess;
     }
+    if (ok && (ok = cells_b.alloc(n_b) == hipSuccess)) {
+        hipLaunchKernelGGL(map_bytes_kernel, dim3((unsigned)((n_b + 255) / 256)), dim3(256), 0, nullptr, ns.d_cells.get(),
+                           map_rows_padded(H), W, cells_b.get(), n_b);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    }
     if (!ok) { (void)hipGetLastError(); return; }
     for (int i = 0; i < N_COMPACT; i++) {
         ns.d_cells_c[i] = std::move(cells[i]);
         ns.d_lut_lds_c[i] = std::move(img[i]);
         ns.compact_out[i] = cnt[0] ? (double)cnt[1 + i] / (double)cnt[0] : 0.0;
     }
+    ns.d_cells_b = std::move(cells_b);
     ns.compact = true;
 }
 
@@ -42,10 +50,11 @@ static void build_compact(f110_handle::MapSlot &ns)
 static int commit_map(f110_handle *h, int slot, f110_handle::MapSlot &&ns, int H, int W, double res, double ox, double oy, double oc,
                       double os, double oob)
 {
-    if (slot == 0) build_compact(ns); // (the forms apply to a single map only; a handle that goes on to a map per env keeps slot 0's)
+    if (slot == 0) build_compact(ns, H, W); // (the forms apply to a single map only; a handle that goes on to a map per env keeps slot 0's)
     MapDev &m = ns.dev;
     memset(&m, 0, sizeof(m));
     for (int i = 0; i < N_COMPACT; i++) { m.cells_c[i] = ns.d_cells_c[i].get(); m.lut_lds_c[i] = ns.d_lut_lds_c[i].get(); }
+    m.cells_b = ns.d_cells_b.get(); m.cells_b_bytes = (unsigned)ns.d_cells_b.size();
     m.cells = ns.d_cells.get(); m.cells_far = ns.d_cells_far.get(); m.lut = ns.d_lut.get(); m.lut_lds = ns.d_lut_lds.get(); m.dt = ns.d_dt.get();
     m.H = H; m.W = W; m.strip_bytes = (unsigned)map_rows_padded(H) * 16u; m.cells_bytes = (unsigned)(ns.d_cells.size() * sizeof(uint16_t));
     m.res = res; m.rinv = 1.0 / res;
@@ -239,8 +248,9 @@ static int check_map_args(f110_handle *h, const void *p, int H, int W, double re
 {
     if (!h || !p) return fail(F110_E_INVALID, "%s: null argument", who);
     if (H < 1 || W < 1 || (int64_t)(H + 10) * (W + 10) > (int64_t)1 << 30 || H + 10 >= (1 << 20)) return fail(F110_E_INVALID, "%s: bad map size %dx%d", who, H, W);
-    // cell_offset and the march loops multiply (c >> 3) by strip_bytes - 16 as signed 24-bit operands (v_mad_i32_i24)
-    if (16 * (int64_t)map_rows_padded(H) - 16 >= (int64_t)1 << 23 || (W >> 3) >= (1 << 23))
+    // cell_offset and the march loops multiply (c >> 3) by strip_bytes - 16 as signed 24-bit operands (v_mad_i32_i24); the
+    // byte table's (c >> 4) by the same strip_bytes - 16
+    if (16 * (int64_t)map_rows_padded(H) - 16 >= (int64_t)1 << 23 || (W >> 3) >= (1 << 23) || (W >> 4) >= (1 << 23))
         return fail(F110_E_INVALID, "%s: map size %dx%d outside the 24-bit strip addressing (height <= 524286, width < 2^26)", who, H, W);
     if (!(res > 0) || !std::isfinite(res)) return fail(F110_E_INVALID, "%s: bad resolution %g", who, res);
     return F110_OK;

@@ -25,18 +25,29 @@ struct MapView {
     double res, rinv, ox, oy, oc, os, wres, hres;
     double nox, noy; // -ox * rinv, -oy * rinv (exact when rinv is a power of two)
     F110_BOUNDS_ONLY(uint32_t *err = nullptr; unsigned cells_bytes = 0; unsigned off_far = OFF_FAR;)
-    // cells: the table the march reads, m.cells or one of m.cells_c (same layout and size); off_far: its far marker's code
-    __device__ void init(const MapDev &m, const uint16_t *cells, unsigned far_code)
+    // cells: the table the march reads, m.cells or one of m.cells_c (same layout and size) or m.cells_b (bytes, 16-column strips);
+    // bytes: its size; off_far: its far marker's code
+    __device__ void init(const MapDev &m, const void *cells, unsigned bytes, unsigned far_code)
     {
-        F110_BOUNDS_ONLY(cells_bytes = m.cells_bytes; off_far = far_code;)
+        F110_BOUNDS_ONLY(cells_bytes = bytes; off_far = far_code;)
         (void)far_code;
-        cells_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(cells), 0, (int)m.cells_bytes, 0x00020000);
+        cells_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(cells), 0, (int)bytes, 0x00020000);
         cells_words.x = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)cells);
         cells_words.y = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)cells >> 32) & 0xffffu);
-        cells_words.z = __builtin_amdgcn_readfirstlane(m.cells_bytes); cells_words.w = __builtin_amdgcn_readfirstlane(0x00020000u);
+        cells_words.z = __builtin_amdgcn_readfirstlane(bytes); cells_words.w = __builtin_amdgcn_readfirstlane(0x00020000u);
         row_bias = m.strip_bytes + 16u; strip_m16 = m.strip_bytes - 16u; desc = &m; H = m.H; W = m.W; res = m.res; rinv = m.rinv;
         ox = m.ox; oy = m.oy; oc = m.oc; os = m.os; wres = m.wres; hres = m.hres;
         nox = -m.ox * m.rinv; noy = -m.oy * m.rinv;
+    }
+    // The byte table (m.cells_b, 16-column strips) behind a descriptor that starts row_bias = strip_bytes + 16 bytes INTO the
+    // table and is that much shorter: the +1 strip and the +1 border row of a cell's offset are in the base, so the march forms
+    // (c >> 4) * (strip_bytes - 16) + c + (r << 4) with one shift-add for row and column together.  The addresses are the same.
+    // What lies in front of the new base is strip 0 (columns -16 .. -1) and the border row of strip 1: border cells only, whose
+    // offsets are now negative, i.e. out of range, and read as 0 -- the slot they hold.
+    __device__ void init_bytes(const MapDev &m, unsigned far_code)
+    {
+        init(m, m.cells_b + (m.strip_bytes + 16u), m.cells_b_bytes - (m.strip_bytes + 16u), far_code);
+        F110_BOUNDS_ONLY(cells_bytes = m.cells_b_bytes;)
     }
 };
 
@@ -89,7 +100,9 @@ __device__ inline void cell_index(const MapView &m, double x, double y, int &ci,
     }
 }
 
-// byte offset of the cell under (column ci, row ri) in the strip table: both clamped onto the border
+// byte offset of the cell under (column ci, row ri) in the strip table: both clamped onto the border.  BYTES: in the byte table
+// of 16-column strips (f110_map.h: cell_elem_b), (c >> 4) * (S - 16) + c -- the column is added, not shift-added
+template <bool BYTES = false>
 __device__ inline unsigned cell_offset(const MapView &m, int ci, int ri)
 {
     const int cc = med3_i32(ci, -1, m.W);      // column -1..W (both ends are border cells)
@@ -100,6 +113,7 @@ __device__ inline unsigned cell_offset(const MapView &m, int ci, int ri)
     // into a trailing add.  (c >> 3) * S + (c & 7) * 2 == (c >> 3) * (S - 16) + c * 2: no masking of the column bits needed
     unsigned row16;
     asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(row16) : "v"(rr), "s"(m.row_bias));
+    if (BYTES) return (unsigned)(__mul24(cc >> 4, (int)m.strip_m16) + (int)(((unsigned)rr << 4) + (unsigned)cc)); // (against init_bytes' base)
     unsigned rc;
     asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(rc) : "v"(cc), "v"(row16));
     return (unsigned)(__mul24(cc >> 3, (int)m.strip_m16) + (int)rc);
@@ -108,16 +122,18 @@ __device__ inline unsigned cell_offset(const MapView &m, int ci, int ri)
 // One table look-up (laser_models.py:56-104 distance_transform): the value of the cell under (x, y), or -0.0 when the cell
 // carries the far marker (dist_lookup_far finishes those).  The caller runs it under the EXEC mask of the rays that are
 // still marching: a finished ray issues nothing.
-template <bool IDENT, bool POW2>
+template <bool IDENT, bool POW2, bool BYTES = false>
 __device__ inline double dist_lookup(const MapView &m, const double *lds_lut, double x, double y)
 {
     int ci, ri;
     cell_index<IDENT, POW2>(m, x, y, ci, ri);
-    const unsigned off = cell_offset(m, ci, ri);
-    // buffer load: 32-bit per-lane offset against a scalar descriptor
-    unsigned code = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(m.cells_rsrc, (int)off, 0, 0);
+    const unsigned off = cell_offset<BYTES>(m, ci, ri);
+    // buffer load: 32-bit per-lane offset against a scalar descriptor (BYTES: the cell holds the slot, 8 bytes each)
+    unsigned code = BYTES ? (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(m.cells_rsrc, (int)off, 0, 0) << 3
+                          : (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(m.cells_rsrc, (int)off, 0, 0);
 #if defined(F110_BOUNDS)
-    F110_BCHK(off + 2u <= m.cells_bytes, BT_LUT_CODE, m.err);
+    // the offset inside the table (BYTES: counted from the table's start, where init_bytes' descriptor starts row_bias later)
+    F110_BCHK(BYTES ? off + m.row_bias < m.cells_bytes : off + 2u <= m.cells_bytes, BT_LUT_CODE, m.err);
     F110_BCHK(code <= m.off_far && (code & 7u) == 0u, BT_LUT_CODE, m.err); // (a compact table: nothing behind ITS marker)
     code = code <= m.off_far ? (code & ~7u) : 0u;
 #endif
@@ -205,50 +221,73 @@ __device__ inline int beam_theta_index(unsigned long long T0, double t0w, int b,
 //   am: in, the rays marching; out, the rays still marching.  nlook += look-ups made.  d: every lane's last table value.
 // The loads and their waits are inside the statement (the compiler does not count an asm load).  The LDS LUT must sit at LDS
 // address 0 (scan_kernel checks it).
+// BYTES (the byte table of 16-column strips behind MapView::init_bytes' descriptor): the strip is c >> 4, ONE shift-add forms
+// (r << 4) + c (the constant is in the descriptor's base), the load is buffer_load_ubyte and one v_lshlrev_b32 turns the slot
+// into the LDS byte offset: 19 VALU as before.  The statements' texts differ in exactly those lines (the macros below).
+#define F110_MARCH_CELL_WORD_CLAMPED(strip, row, col) \
+        "v_lshl_add_u32 " row ", " row ", 4, %[rb]\n\t" \
+        "v_ashrrev_i32 " strip ", 3, " col "\n\t" \
+        "v_lshl_add_u32 " row ", " col ", 1, " row "\n\t"
+#define F110_MARCH_CELL_WORD_FAST(strip, row, col) \
+        "v_ashrrev_i32 " strip ", 3, " col "\n\t" \
+        "v_lshl_add_u32 " row ", " row ", 4, %[rb]\n\t" \
+        "v_lshl_add_u32 " row ", " col ", 1, " row "\n\t"
+#define F110_MARCH_CELL_BYTE(strip, row, col) \
+        "v_ashrrev_i32 " strip ", 4, " col "\n\t" \
+        "v_lshl_add_u32 " row ", " row ", 4, " col "\n\t"
+#define F110_MARCH_LOAD_WORD(code) \
+        "buffer_load_ushort " code ", " code ", %[rsrc], 0 offen\n\t" \
+        "s_waitcnt vmcnt(0)\n\t"
+#define F110_MARCH_LOAD_BYTE(code) \
+        "buffer_load_ubyte " code ", " code ", %[rsrc], 0 offen\n\t" \
+        "s_waitcnt vmcnt(0)\n\t" \
+        "v_lshlrev_b32 " code ", 3, " code "\n\t"
+template <bool BYTES = false>
 __device__ inline void march_ident_pow2(const MapView &m, double &x, double &y, double &total, double &d, double c, double s,
                                         double eps, double max_range, unsigned long long &am, int go, unsigned &nlook, int &nact)
 {
     unsigned long long sx;
     double q0, q1;
     int t0, t1, t2;
-    asm volatile(
-        "s_mov_b64 %[sx], exec\n\t"
-        "s_mov_b64 exec, %[am]\n"
-        "1:\n\t"
-        "s_add_u32 %[nl], %[nl], %[na]\n\t"
-        "v_fma_f64 %[q0], %[rinv], %[x], %[nox]\n\t"
-        "v_fma_f64 %[q1], %[rinv], %[y], %[noy]\n\t"
-        "v_floor_f64 %[q0], %[q0]\n\t"
-        "v_floor_f64 %[q1], %[q1]\n\t"
-        "v_cvt_i32_f64 %[t0], %[q0]\n\t"
-        "v_cvt_i32_f64 %[t1], %[q1]\n\t"
-        "v_med3_i32 %[t0], %[t0], -1, %[W]\n\t"
-        "v_med3_i32 %[t1], %[t1], -1, %[H]\n\t"
-        "v_lshl_add_u32 %[t1], %[t1], 4, %[rb]\n\t"
-        "v_ashrrev_i32 %[t2], 3, %[t0]\n\t"
-        "v_lshl_add_u32 %[t1], %[t0], 1, %[t1]\n\t"
-        "v_mad_i32_i24 %[t2], %[t2], %[sm], %[t1]\n\t"
-        "buffer_load_ushort %[t2], %[t2], %[rsrc], 0 offen\n\t"
-        "s_waitcnt vmcnt(0)\n\t"
-        "ds_read_b64 %[d], %[t2]\n\t"
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "v_add_f64 %[tot], %[tot], %[d]\n\t"
-        "v_mul_f64 %[q0], %[c], %[d]\n\t"
-        "v_mul_f64 %[q1], %[s], %[d]\n\t"
-        "v_add_f64 %[x], %[x], %[q0]\n\t"
-        "v_add_f64 %[y], %[y], %[q1]\n\t"
-        "v_cmpx_lt_f64 vcc, %[eps], %[d]\n\t"
-        "v_cmpx_ge_f64 vcc, %[mr], %[tot]\n\t"
-        "s_bcnt1_i32_b64 %[na], exec\n\t"
-        "s_cmp_gt_i32 %[na], %[go]\n\t"
-        "s_cbranch_scc1 1b\n\t"
-        "s_mov_b64 %[am], exec\n\t"
-        "s_mov_b64 exec, %[sx]"
-        : [x] "+v"(x), [y] "+v"(y), [tot] "+v"(total), [d] "+v"(d), [am] "+s"(am), [nl] "+s"(nlook), [na] "+s"(nact),
-          [sx] "=&s"(sx), [q0] "=&v"(q0), [q1] "=&v"(q1), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2)
-        : [c] "v"(c), [s] "v"(s), [nox] "v"(m.nox), [noy] "v"(m.noy), [rinv] "s"(m.rinv), [W] "s"(m.W), [H] "s"(m.H),
-          [rb] "s"(m.row_bias), [sm] "s"(m.strip_m16), [rsrc] "s"(m.cells_words), [eps] "s"(eps), [mr] "s"(max_range), [go] "s"(go)
-        : "vcc", "scc", "memory");
+#define F110_MARCH_CLAMPED(CELL, LOAD) \
+    asm volatile( \
+        "s_mov_b64 %[sx], exec\n\t" \
+        "s_mov_b64 exec, %[am]\n" \
+        "1:\n\t" \
+        "s_add_u32 %[nl], %[nl], %[na]\n\t" \
+        "v_fma_f64 %[q0], %[rinv], %[x], %[nox]\n\t" \
+        "v_fma_f64 %[q1], %[rinv], %[y], %[noy]\n\t" \
+        "v_floor_f64 %[q0], %[q0]\n\t" \
+        "v_floor_f64 %[q1], %[q1]\n\t" \
+        "v_cvt_i32_f64 %[t0], %[q0]\n\t" \
+        "v_cvt_i32_f64 %[t1], %[q1]\n\t" \
+        "v_med3_i32 %[t0], %[t0], -1, %[W]\n\t" \
+        "v_med3_i32 %[t1], %[t1], -1, %[H]\n\t" \
+        CELL("%[t2]", "%[t1]", "%[t0]") \
+        "v_mad_i32_i24 %[t2], %[t2], %[sm], %[t1]\n\t" \
+        LOAD("%[t2]") \
+        "ds_read_b64 %[d], %[t2]\n\t" \
+        "s_waitcnt lgkmcnt(0)\n\t" \
+        "v_add_f64 %[tot], %[tot], %[d]\n\t" \
+        "v_mul_f64 %[q0], %[c], %[d]\n\t" \
+        "v_mul_f64 %[q1], %[s], %[d]\n\t" \
+        "v_add_f64 %[x], %[x], %[q0]\n\t" \
+        "v_add_f64 %[y], %[y], %[q1]\n\t" \
+        "v_cmpx_lt_f64 vcc, %[eps], %[d]\n\t" \
+        "v_cmpx_ge_f64 vcc, %[mr], %[tot]\n\t" \
+        "s_bcnt1_i32_b64 %[na], exec\n\t" \
+        "s_cmp_gt_i32 %[na], %[go]\n\t" \
+        "s_cbranch_scc1 1b\n\t" \
+        "s_mov_b64 %[am], exec\n\t" \
+        "s_mov_b64 exec, %[sx]" \
+        : [x] "+v"(x), [y] "+v"(y), [tot] "+v"(total), [d] "+v"(d), [am] "+s"(am), [nl] "+s"(nlook), [na] "+s"(nact), \
+          [sx] "=&s"(sx), [q0] "=&v"(q0), [q1] "=&v"(q1), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2) \
+        : [c] "v"(c), [s] "v"(s), [nox] "v"(m.nox), [noy] "v"(m.noy), [rinv] "s"(m.rinv), [W] "s"(m.W), [H] "s"(m.H), \
+          [rb] "s"(m.row_bias), [sm] "s"(m.strip_m16), [rsrc] "s"(m.cells_words), [eps] "s"(eps), [mr] "s"(max_range), [go] "s"(go) \
+        : "vcc", "scc", "memory")
+    if constexpr (BYTES) F110_MARCH_CLAMPED(F110_MARCH_CELL_BYTE, F110_MARCH_LOAD_BYTE);
+    else F110_MARCH_CLAMPED(F110_MARCH_CELL_WORD_CLAMPED, F110_MARCH_LOAD_WORD);
+#undef F110_MARCH_CLAMPED
 }
 
 // The same loop for a car that is not absurdly far from its map (scan_kernel decides per car: |cell coordinates of the car| +
@@ -262,49 +301,60 @@ __device__ inline void march_ident_pow2(const MapView &m, double &x, double &y, 
 //    unsigned values), which the descriptor's range check answers with 0 = the border's code; the columns in between lie in the
 //    border strips.  That needs (c >> 3) * strip_bytes below 2^31, which the limit guarantees.  (The row still needs its clamp:
 //    a row beyond the strip would land in the neighbouring strip.)
+// BYTES, the same two arguments for strips of 16 columns and init_bytes' descriptor, which starts strip_bytes + 16 into the
+// table (16 VALU: the shift-add that joins row and column pays for the shift that turns the slot into the LDS offset, in v61):
+//  * counted from the table's start the offset is ((c >> 4) + 1) * strip_bytes + (r + 1) * 16 + (c & 15) with the row clamped,
+//    so a column outside [-16, 16 * ((W >> 4) + 1)) -- a fortiori one outside [-16, 16 * ((W >> 4) + 1) + 16) -- has strip index
+//    (c >> 4) + 1 below 0 or at or above the table's (W >> 4) + 2 strips: against the descriptor an offset that is negative
+//    (wraps to 2^31 or more) or at or beyond its bytes.  The columns in between that are no map cell lie in strip 0 (negative
+//    too: in front of the descriptor) or in the last strip's padding, which holds 0;
+//  * the descriptor's range check answers 0 for those offsets, the slot of the border; 0 << 3 is its code.  The limit keeps
+//    ((c >> 4) + 1) * strip_bytes below 2^31 and c >> 4 inside the multiply's 24 bits.
 // 16 VALU + 6 SALU per iteration.  The magic sums and the products live in v[60:63]: an asm operand cannot name the low dword
 // of a register pair, so the statement uses those four registers by name and declares them clobbered.
+template <bool BYTES = false>
 __device__ inline void march_ident_pow2_fast(const MapView &m, double &x, double &y, double &total, double &d, double c, double s,
                                              double eps, double max_range, unsigned long long &am, int go, unsigned &nlook, int &nact)
 {
     unsigned long long sx;
-    asm volatile(
-        "s_mov_b64 %[sx], exec\n\t"
-        "s_mov_b64 exec, %[am]\n"
-        "1:\n\t"
-        "s_add_u32 %[nl], %[nl], %[na]\n\t"
-        "v_fma_f64 v[60:61], %[rinv], %[x], %[nox]\n\t"
-        "v_fma_f64 v[62:63], %[rinv], %[y], %[noy]\n\t"
-        "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 2\n\t"      // f64 rounding: toward -inf
-        "v_add_f64 v[60:61], v[60:61], %[magic]\n\t"
-        "v_add_f64 v[62:63], v[62:63], %[magic]\n\t"
-        "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 0\n\t"      // back to nearest-even
-        "v_med3_i32 v62, v62, -1, %[H]\n\t"
-        "v_ashrrev_i32 v61, 3, v60\n\t"
-        "v_lshl_add_u32 v62, v62, 4, %[rb]\n\t"
-        "v_lshl_add_u32 v62, v60, 1, v62\n\t"
-        "v_mad_i32_i24 v61, v61, %[sm], v62\n\t"
-        "buffer_load_ushort v61, v61, %[rsrc], 0 offen\n\t"
-        "s_waitcnt vmcnt(0)\n\t"
-        "ds_read_b64 %[d], v61\n\t"
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "v_add_f64 %[tot], %[tot], %[d]\n\t"
-        "v_mul_f64 v[60:61], %[c], %[d]\n\t"
-        "v_mul_f64 v[62:63], %[s], %[d]\n\t"
-        "v_add_f64 %[x], %[x], v[60:61]\n\t"
-        "v_add_f64 %[y], %[y], v[62:63]\n\t"
-        "v_cmpx_lt_f64 vcc, %[eps], %[d]\n\t"
-        "v_cmpx_ge_f64 vcc, %[mr], %[tot]\n\t"
-        "s_bcnt1_i32_b64 %[na], exec\n\t"
-        "s_cmp_gt_i32 %[na], %[go]\n\t"
-        "s_cbranch_scc1 1b\n\t"
-        "s_mov_b64 %[am], exec\n\t"
-        "s_mov_b64 exec, %[sx]"
-        : [x] "+v"(x), [y] "+v"(y), [tot] "+v"(total), [d] "+v"(d), [am] "+s"(am), [nl] "+s"(nlook), [na] "+s"(nact), [sx] "=&s"(sx)
-        : [c] "v"(c), [s] "v"(s), [nox] "v"(m.nox), [noy] "v"(m.noy), [rinv] "s"(m.rinv), [H] "s"(m.H),
-          [rb] "s"(m.row_bias), [sm] "s"(m.strip_m16), [rsrc] "s"(m.cells_words), [eps] "s"(eps), [mr] "s"(max_range), [go] "s"(go),
-          [magic] "s"(6755399441055744.0)
-        : "vcc", "scc", "memory", "v60", "v61", "v62", "v63");
+#define F110_MARCH_FAST(CELL, LOAD) \
+    asm volatile( \
+        "s_mov_b64 %[sx], exec\n\t" \
+        "s_mov_b64 exec, %[am]\n" \
+        "1:\n\t" \
+        "s_add_u32 %[nl], %[nl], %[na]\n\t" \
+        "v_fma_f64 v[60:61], %[rinv], %[x], %[nox]\n\t" \
+        "v_fma_f64 v[62:63], %[rinv], %[y], %[noy]\n\t" \
+        "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 2\n\t"      /* f64 rounding: toward -inf */ \
+        "v_add_f64 v[60:61], v[60:61], %[magic]\n\t" \
+        "v_add_f64 v[62:63], v[62:63], %[magic]\n\t" \
+        "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 0\n\t"      /* back to nearest-even */ \
+        "v_med3_i32 v62, v62, -1, %[H]\n\t" \
+        CELL("v61", "v62", "v60") \
+        "v_mad_i32_i24 v61, v61, %[sm], v62\n\t" \
+        LOAD("v61") \
+        "ds_read_b64 %[d], v61\n\t" \
+        "s_waitcnt lgkmcnt(0)\n\t" \
+        "v_add_f64 %[tot], %[tot], %[d]\n\t" \
+        "v_mul_f64 v[60:61], %[c], %[d]\n\t" \
+        "v_mul_f64 v[62:63], %[s], %[d]\n\t" \
+        "v_add_f64 %[x], %[x], v[60:61]\n\t" \
+        "v_add_f64 %[y], %[y], v[62:63]\n\t" \
+        "v_cmpx_lt_f64 vcc, %[eps], %[d]\n\t" \
+        "v_cmpx_ge_f64 vcc, %[mr], %[tot]\n\t" \
+        "s_bcnt1_i32_b64 %[na], exec\n\t" \
+        "s_cmp_gt_i32 %[na], %[go]\n\t" \
+        "s_cbranch_scc1 1b\n\t" \
+        "s_mov_b64 %[am], exec\n\t" \
+        "s_mov_b64 exec, %[sx]" \
+        : [x] "+v"(x), [y] "+v"(y), [tot] "+v"(total), [d] "+v"(d), [am] "+s"(am), [nl] "+s"(nlook), [na] "+s"(nact), [sx] "=&s"(sx) \
+        : [c] "v"(c), [s] "v"(s), [nox] "v"(m.nox), [noy] "v"(m.noy), [rinv] "s"(m.rinv), [H] "s"(m.H), \
+          [rb] "s"(m.row_bias), [sm] "s"(m.strip_m16), [rsrc] "s"(m.cells_words), [eps] "s"(eps), [mr] "s"(max_range), [go] "s"(go), \
+          [magic] "s"(6755399441055744.0) \
+        : "vcc", "scc", "memory", "v60", "v61", "v62", "v63")
+    if constexpr (BYTES) F110_MARCH_FAST(F110_MARCH_CELL_BYTE, F110_MARCH_LOAD_BYTE);
+    else F110_MARCH_FAST(F110_MARCH_CELL_WORD_FAST, F110_MARCH_LOAD_WORD);
+#undef F110_MARCH_FAST
 }
 // The march for a map whose resolution is NOT a power of two (most F1TENTH maps: 0.05 m) and whose origin is not rotated, for
 // cars near their map (the same per-car test as above).  q = (x - ox) * (1 / res) is within ~2e-16 relative of the reference's
@@ -389,6 +439,12 @@ __device__ inline int march_ident_np_fast(const MapView &m, double &x, double &y
 // the largest |cell coordinate| a look-up of the fast march may have: (c >> 3) * strip_bytes stays below 2^31 with room to
 // spare, and far inside the magic number's 2^31 (a NaN or infinite pose fails the test and takes the clamped loop)
 __device__ inline double march_fast_limit(const MapView &m) { return (double)((0x7fffffffu / (m.row_bias + 16u)) * 8u) - 64.0; }
+// the same for the byte table: (c >> 4) * strip_bytes below 2^31 and c >> 4 a signed 24-bit operand of the multiply-add
+__device__ inline double march_fast_limit_bytes(const MapView &m)
+{
+    const unsigned strips = 0x7fffffffu / (m.row_bias + 16u);
+    return (double)((strips < 0x7fffffu ? strips : 0x7fffffu) * 16u) - 64.0;
+}
 
 struct ScanArgs {
     const MapDev *maps;         // dev [K] map descriptors
@@ -482,13 +538,15 @@ template <int LUTN> struct __attribute__((aligned(16))) ScanLdsRows { double lut
 static_assert(sizeof(ScanLds<SCAN_ROWBUF_LUT>) == SCAN_ROWBUF_BASE && sizeof(ScanLdsRows<SCAN_ROWBUF_LUT>) <= SCAN_LDS_PER_GROUP,
               "32 one-wave workgroups with a row buffer each fit a CU's LDS");
 template <bool DIRECT> struct EmitTag { static constexpr bool direct = DIRECT; };
-template <bool IDENT, bool POW2, int SM, int LUTN = LUT_LDS, bool ROWBUF = false>
+// BYTES (LUTN == 256 only): the march reads the map's byte table (f110_map.h: cell_elem_b) instead of cells_c[0].
+template <bool IDENT, bool POW2, int SM, int LUTN = LUT_LDS, bool ROWBUF = false, bool BYTES = false>
 __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(ScanArgs a)
 {
     constexpr bool STEP = SM >= 1;
     constexpr bool COMPACT = LUTN != LUT_LDS;
     static_assert(!COMPACT || (compact_index(LUTN) >= 0 && STEP && IDENT && POW2), "compact forms: the step's scan, kind 3");
     static_assert(!ROWBUF || LUTN == SCAN_ROWBUF_LUT, "the row buffer: the compact form of 256 slots");
+    static_assert(!BYTES || LUTN == LUT_COMPACT[0], "byte cell codes: the compact form of 256 slots");
     // ONE LDS object, the LUT first: march_ident_pow2 addresses the LUT by the cell codes alone, i.e. the LUT sits at LDS
     // address 0 (the kernel has no other LDS variable; every parity test would fail otherwise)
     __shared__ typename std::conditional<ROWBUF, ScanLdsRows<LUTN>, ScanLds<LUTN>>::type s_mem;
@@ -545,8 +603,9 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
     if ((int)threadIdx.x < ((nb + 63) >> 6)) s_chunk0[threadIdx.x] = a.chunk_beam0[threadIdx.x];
     __syncthreads();
     MapView mv;
-    if (COMPACT) mv.init(md, md.cells_c[compact_index(LUTN) & 1], compact_off_far(LUTN));
-    else mv.init(md, md.cells, OFF_FAR);
+    if (BYTES) mv.init_bytes(md, compact_off_far(LUTN));
+    else if (COMPACT) mv.init(md, md.cells_c[compact_index(LUTN) & 1], md.cells_bytes, compact_off_far(LUTN));
+    else mv.init(md, md.cells, md.cells_bytes, OFF_FAR);
     F110_BOUNDS_ONLY(mv.err = rare->dev_err;)
     if (car >= a.n_cars) return;
     car = car_c; // (from here on the car's index in the shard)
@@ -660,7 +719,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
 
     // ---- ray march (laser_models.py:107-186) -------------------------------------
     // The first table read of every beam is at the car itself (:129): done once.
-    double d0 = dist_lookup<IDENT, POW2>(mv, s_lut, px, py);
+    double d0 = dist_lookup<IDENT, POW2, BYTES>(mv, s_lut, px, py);
     if (__builtin_expect(is_far_marker(d0), 0)) d0 = dist_lookup_far<IDENT, POW2>(mv, px, py); // (wave-uniform: every lane reads the car's own cell)
     unsigned nlook = (unsigned)nbl; // the reference reads the table once per beam before marching
     if (!(d0 > eps && d0 <= max_range)) {
@@ -686,7 +745,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
         // (wave-uniform) may this car's rays take the fast march?  Every look-up lies within max_range of the car.
         bool fast = false;
         if (IDENT) {
-            const double reach = max_range * mv.rinv + 2.0, lim = march_fast_limit(mv);
+            const double reach = max_range * mv.rinv + 2.0, lim = BYTES ? march_fast_limit_bytes(mv) : march_fast_limit(mv);
             const double q0x = POW2 ? __builtin_fma(px, mv.rinv, mv.nox) : (px - mv.ox) * mv.rinv;
             const double q0y = POW2 ? __builtin_fma(py, mv.rinv, mv.noy) : (py - mv.oy) * mv.rinv;
             fast = fabs(q0x) + reach < lim && fabs(q0y) + reach < lim;
@@ -761,8 +820,8 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
 #if !defined(F110_BOUNDS)
             if (IDENT && POW2) {
                 unsigned long long am = vote(active);
-                if (fast) march_ident_pow2_fast(mv, x, y, total, d, c, s, eps, max_range, am, go, nlook, nact);
-                else march_ident_pow2(mv, x, y, total, d, c, s, eps, max_range, am, go, nlook, nact);
+                if (fast) march_ident_pow2_fast<BYTES>(mv, x, y, total, d, c, s, eps, max_range, am, go, nlook, nact);
+                else march_ident_pow2<BYTES>(mv, x, y, total, d, c, s, eps, max_range, am, go, nlook, nact);
                 active = ((am >> lane) & 1ull) != 0ull;
                 continue;
             }
@@ -774,7 +833,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
                     nlook += (unsigned)nact;
                     bool act = __builtin_amdgcn_inverse_ballot_w64(am);
                     if (act) {
-                        d = dist_lookup<IDENT, POW2>(mv, s_lut, x, y);
+                        d = dist_lookup<IDENT, POW2, BYTES>(mv, s_lut, x, y);
                         total += d;
                         x += d * c;
                         y += d * s;
@@ -791,7 +850,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
             do {
                 nlook += (unsigned)nact;
                 if (active) {
-                    d = dist_lookup<IDENT, POW2>(mv, s_lut, x, y);
+                    d = dist_lookup<IDENT, POW2, BYTES>(mv, s_lut, x, y);
                     total += d;
                     x += d * c;
                     y += d * s;

@@ -237,6 +237,20 @@ inline int scan_rows_override(const char *v)
 // profiles/r25_scan_rowbuf.txt).  S = 512 has 768 B to spare and the classic form none.
 inline bool scan_rowbuf_choice(int lut, bool has_f32, int forced) { return lut == SCAN_ROWBUF_LUT && has_f32 && forced != 0; }
 
+// Byte cell codes (f110_map.h: cell_elem_b; scan_kernel<.., 256, true, true>): the march of the compact form of 256 slots reads
+// its codes from a table of bytes in 16-column strips, twice the cells per cache line (profiles/r26_scan_bytes.txt).
+// F110_SCAN_CODES: "byte" -> 1, "word" -> 0; unset or anything else -> -1 (the rule decides)
+inline int scan_codes_override(const char *v)
+{
+    if (!v) return -1;
+    if (!strcmp(v, "byte")) return 1;
+    if (!strcmp(v, "word")) return 0;
+    return -1;
+}
+// The rule: bytes exactly where the row buffer is launched (the one instantiation of the 256-slot form the default run uses;
+// every code of that form is below slot 256 by construction, so nothing else has to hold).
+inline bool scan_codes_choice(int lut, bool rowbuf, int forced) { return lut == SCAN_ROWBUF_LUT && rowbuf && forced != 0; }
+
 // F110_SCAN_FORM: "classic" -> 0, "compact256" -> 256, "compact512" -> 512; unset or anything else -> -1 (the rule decides)
 inline int scan_form_override(const char *v)
 {
@@ -257,6 +271,7 @@ struct ScanPlanIn {
     int compact = 0;                    // S of the compact form the map offers and the rule (or the override) chose, 0: classic
     bool out_f32 = false;               // the scan writes an fp32 row
     int rows = -1;                      // scan_rows_override(F110_SCAN_ROWS)
+    int codes = -1;                     // scan_codes_override(F110_SCAN_CODES)
 };
 
 struct ScanLaunch {
@@ -269,6 +284,7 @@ struct ScanLaunch {
                                         // workgroup stages one LUT); carries the event pair
     int lut;                            // 0: the classic instantiation (LUT_LDS slots); S: the compact one of S slots
     bool rowbuf;                        // the instantiation that stages fp32 rows in LDS (scan_rowbuf_choice)
+    bool bytes;                         // the instantiation that reads the byte cell table (scan_codes_choice)
 };
 
 // The launches of one scan in launch order, or an error code (message through fail) where they would break what scan_kernel
@@ -290,6 +306,7 @@ int plan_scan(const ScanPlanIn &in, EnvKind env_kind, std::vector<ScanLaunch> &o
         // the compact form: the step's scan of a single map, origin unrotated and resolution 2^k (the written-out march)
         l.lut = in.step && !in.multi && in.kind == 3 ? in.compact : 0;
         l.rowbuf = scan_rowbuf_choice(l.lut, in.out_f32, in.rows);
+        l.bytes = scan_codes_choice(l.lut, l.rowbuf, in.codes);
         l.wg_single = (in.multi && in.wg_single) || l.lut != 0; l.order = in.step && !in.multi; l.events = in.step && e0 == 0;
         const std::vector<StageSpec> stv = scan_stage_list(*in.stages, l.n_cars, in.agents, in.num_beams);
         // what the kernel assumes about the stage list, checked here where a mistake costs an error code instead of a

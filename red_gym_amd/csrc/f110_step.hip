@@ -103,6 +103,9 @@ static const void *const scan_kernels_compact[N_COMPACT][2] = {
 // the compact form of 256 slots with fp32 rows staged in LDS (ScanLaunch::rowbuf) by [SM - 1]
 static const void *const scan_kernels_rowbuf[2] = {(const void *)&scan_kernel<true, true, 1, SCAN_ROWBUF_LUT, true>,
                                                    (const void *)&scan_kernel<true, true, 2, SCAN_ROWBUF_LUT, true>};
+// the same reading the byte cell table (ScanLaunch::bytes) by [SM - 1]
+static const void *const scan_kernels_bytes[2] = {(const void *)&scan_kernel<true, true, 1, SCAN_ROWBUF_LUT, true, true>,
+                                                  (const void *)&scan_kernel<true, true, 2, SCAN_ROWBUF_LUT, true, true>};
 
 // The form of the step's scan on the handle's single map: what F110_SCAN_FORM forces (read once per process; tests and A/B
 // runs), else what the eligibility rule picks from the map's recorded shares.  A map without compact tables stays classic
@@ -167,6 +170,17 @@ extern "C" int f110_scan_rows_info(f110_handle *h, int32_t n_cars, int32_t *lds)
     return F110_OK;
 }
 
+// F110_SCAN_CODES = byte | word (read once per process; tests and A/B runs) over the rule scan_codes_choice
+static int scan_codes_forced() { static const int forced = scan_codes_override(getenv("F110_SCAN_CODES")); return forced; }
+
+extern "C" int f110_scan_codes_info(f110_handle *h, int32_t n_cars, int32_t *bytes)
+{
+    if (!h || !bytes || n_cars < 1) return fail(F110_E_INVALID, "f110_scan_codes_info: bad arguments");
+    if (!h->has_map) return fail(F110_E_NOMAP, "Map is not set for scan simulator.");
+    *bytes = scan_codes_choice(scan_form(h, n_cars), scan_rowbuf_choice(scan_form(h, n_cars), true, scan_rows_forced()), scan_codes_forced());
+    return F110_OK;
+}
+
 extern "C" int f110_scan_form_info(f110_handle *h, int32_t n_cars, int32_t *form, double *out_share)
 {
     if (!h || !form || !out_share || n_cars < 1) return fail(F110_E_INVALID, "f110_scan_form_info: bad arguments");
@@ -193,7 +207,7 @@ static int run_scan(const f110_handle *h, const ScanArgs &a, const Sink &k, hipE
     in.n_cars = a.n_cars; in.agents = a.agents; in.num_beams = a.scan.nb; in.stages = &h->stages; in.step = a.state != nullptr;
     in.stores = stores_env; in.multi = a.env_map != nullptr; in.wg_single = h->wg_single; in.kind = h->ident | h->pow2 << 1;
     in.compact = in.step && !in.multi ? scan_form(h, a.n_cars) : 0;
-    in.out_f32 = a.out_f32 != nullptr; in.rows = scan_rows_forced();
+    in.out_f32 = a.out_f32 != nullptr; in.rows = scan_rows_forced(); in.codes = scan_codes_forced();
     std::vector<ScanLaunch> plan;
     if (int rc = plan_scan(in, [h](int env) { const f110_handle::MapSlot &m = h->slots[h->h_env_map[env]]; return m.ident | m.pow2 << 1; }, plan))
         return rc;
@@ -208,7 +222,10 @@ static int run_scan(const f110_handle *h, const ScanArgs &a, const Sink &k, hipE
             const MapDev &m = h->slots[0].dev;
             if (ci < 0 || l.sm < 1 || l.kind != 3 || !m.cells_c[ci] || !m.lut_lds_c[ci])
                 return fail(F110_E_INVALID, "scan launch: compact form %d without its tables (kind %d, sm %d)", l.lut, l.kind, l.sm);
-            func = l.rowbuf ? scan_kernels_rowbuf[l.sm - 1] : scan_kernels_compact[ci][l.sm - 1];
+            // ... nor the byte instantiation the byte table
+            if (l.bytes && (!l.rowbuf || l.lut != SCAN_ROWBUF_LUT || !m.cells_b || !m.cells_b_bytes))
+                return fail(F110_E_INVALID, "scan launch: byte cell codes without their table (form %d, rows %d)", l.lut, (int)l.rowbuf);
+            func = l.bytes ? scan_kernels_bytes[l.sm - 1] : l.rowbuf ? scan_kernels_rowbuf[l.sm - 1] : scan_kernels_compact[ci][l.sm - 1];
         }
         if (int rc = emit(k, func, dim3(l.grid), dim3(l.block), 0, s, l.events ? ev0 : nullptr,
                           l.events ? ev1 : nullptr))

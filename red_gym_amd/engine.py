@@ -761,6 +761,12 @@ class Engine(object):
         _lib.check(self.lib.f110_scan_rows_info(self._h, self.N if n_cars is None else int(n_cars), C.byref(lds)))
         return bool(lds.value)
 
+    def scan_codes(self, n_cars=None):
+        """True where the step's scan of n_cars cars (default: the engine's) reads byte cell codes (f110_scan_codes_info)."""
+        b = C.c_int32(0)
+        _lib.check(self.lib.f110_scan_codes_info(self._h, self.N if n_cars is None else int(n_cars), C.byref(b)))
+        return bool(b.value)
+
     # ------------------------------------------------------------------ measurement aid
     def profile_begin(self, max_launches, every=1):
         """hipEvent pairs on the scan dispatch of every `every`-th step from now on (f110_profile_begin / _every)."""

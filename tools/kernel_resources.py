@@ -1,6 +1,7 @@
 """Compiles the library with -Rpass-analysis=kernel-resource-usage and prints one line per kernel:
     python tools/kernel_resources.py [filter] [-- extra hipcc flags]
-(VGPRs, SGPRs, spills, scratch, occupancy in waves per SIMD, LDS bytes).  Works without a GPU."""
+(VGPRs, SGPRs, spills, scratch, occupancy in waves per SIMD, LDS bytes).  Works without a GPU.  The filter is a piece of the
+demangled name: "scan_kernel" lists every instantiation, "256, true, true" the 256-slot form with staged rows and byte codes."""
 import os
 import re
 import subprocess

@@ -4,7 +4,8 @@ unset: staged in LDS wherever the compact form of 256 slots runs), on a bundled 
 compact forms apply to power-of-two resolutions only; the bundled tracks but example_map are 0.05 m):
     F110_SCAN_FORM=compact256 python tools/scan_forms.py maps/berlin [--envs B] [--agents A] [--res 0.0625]
     F110_SCAN_FORM=compact256 F110_SCAN_ROWS=direct python tools/scan_forms.py     (compact256 has two columns: lds | direct)
-Prints one line: map, form launched, how its fp32 rows are stored, the map's shares of free cells behind the 256- and 512-slot images, ms/step, scan ms."""
+    F110_SCAN_FORM=compact256 F110_SCAN_CODES=word python tools/scan_forms.py      (and, with its rows in LDS, byte | word cell codes)
+Prints one line: map, form launched, how its fp32 rows are stored, which cell table its march reads, the map's shares of free cells behind the 256- and 512-slot images, ms/step, scan ms."""
 import argparse
 import os
 import sys
@@ -59,7 +60,8 @@ ms, n = env.eng.profile_end()
 lk = env.eng.t['lookups'].to(torch.int64).sum().item() / (a.steps * B * A)
 form, share = env.eng.scan_form()
 rows = 'lds' if env.eng.scan_rows() else 'direct'
-print('%-12s res %.4f %6d x %d  asked %-10s form %3d  rows %-6s (asked %s)  out256 %.4f out512 %.4f reach256 %.4f reach512 %.4f  ms/step %.4f scan_ms %.4f '
-      'lookups/car-step %.0f' % (a.map, res, B, A, os.environ.get('F110_SCAN_FORM', '-'), form, rows, os.environ.get('F110_SCAN_ROWS', '-'), share[0], share[1], share[2], share[3],
+codes = 'byte' if env.eng.scan_codes() else 'word'
+print('%-12s res %.4f %6d x %d  asked %-10s form %3d  rows %-6s (asked %s)  codes %-4s (asked %s)  out256 %.4f out512 %.4f reach256 %.4f reach512 %.4f  ms/step %.4f scan_ms %.4f '
+      'lookups/car-step %.0f' % (a.map, res, B, A, os.environ.get('F110_SCAN_FORM', '-'), form, rows, os.environ.get('F110_SCAN_ROWS', '-'), codes, os.environ.get('F110_SCAN_CODES', '-'), share[0], share[1], share[2], share[3],
                                  dt_s / a.steps * 1e3, ms / n, lk), flush=True)
 env.close()
