@@ -685,6 +685,31 @@ int f110_replay_nstep(f110_handle *h, const int64_t *indices, int32_t n, int32_t
 int f110_replay_sample_nstep(f110_handle *h, uint64_t seed, uint64_t *counter, int32_t n, int32_t nstep, double gamma, int64_t *indices,
                              int64_t *s_frame, int64_t *ns_frame, float *a, double *ret, uint8_t *d, uint8_t *ok, double *discount, int32_t *span,
                              void *stream);
+/* Frame stacks: the last `stack` frames of one env as rows of the frame tensor, walked backwards through the ring on the device
+ * (the mirror of the n-step walk; the reference feeds its policy one frame).  No frame is stored twice and none is copied: a
+ * stack is `stack` row numbers into the tensor f110_replay_locate's rows point into.
+ * Input.  frame_rows[i] is a row of the frame tensor viewed as [(T + 1) * B, rows, words] -- what f110_replay_locate, _sample,
+ * _nstep, _sample_nstep and f110_priority_sample write into s_frame / ns_frame: slot = row / B, env = row % B, and the push it stands
+ * for is the newest push c <= count - 1 with c % (T + 1) == slot (unique among the T + 1 live frames).  count is read on the device.
+ * Link.  Push p of env e links frame p to frame p - 1 iff p >= max(count - T, 0) (its step slot is still the ring's) and
+ * valid[p % T][e] != 0 (push 0 has no frame before it and is never valid).
+ * Output.  rows_out[i][0] = frame_rows[i]; for j = 1 .. stack - 1, rows_out[i][j] = ((c - j) % (T + 1)) * B + e as long as the
+ * pushes c, c - 1, ..., c - j + 1 all link; beyond that the oldest row reached is repeated (Gym's FrameStack: an episode's first
+ * observation fills the stack).  depth[i] = the number of distinct frames reached, 1 .. stack.  A row outside 0 .. (T + 1) * B - 1
+ * (-1 is the conventional one) or one whose slot no push has written gives -1 in every column and depth = 0.  A stack so ends in
+ * front of a reset, at an env a masked reset left alone, at a chain break (chain_start) and at the ring's oldest frame; it never
+ * crosses an episode: the terminal step's frame stacks over its episode, the spawn frame behind it over itself.
+ * Latest mode.  frame_rows == NULL: n must equal B and row i is env i's newest frame (c = count - 1), the stack a policy acts on;
+ * with count = 0 every column is -1 and depth 0.  No host value changes from call to call: a captured call replays correctly.
+ * For a one-step transition that the locate accepts, stack(ns_frame)[1:] == stack(s_frame)[:-1] wherever depth(s_frame) = stack.
+ * A stack computed at learning time can be shorter than the one the actor saw: only for the stack - 1 oldest pushes of the ring,
+ * whose predecessors are overwritten.  depth shows it; nothing corrects it.
+ * One launch, one lane per row, at most stack - 1 loads of valid; no atomics, no allocation, no synchronisation.  rows_out [n,
+ * stack] dev int64, depth [n] dev int32.  F110_E_INVALID without a launch for stack outside 1 .. F110_REPLAY_MAX_STACK, n < 0,
+ * latest mode with n != B, a NULL output, no bound ring and the wrong device, as f110_replay_nstep refuses it.  stack = 1 copies
+ * the rows (only the range checks apply). */
+#define F110_REPLAY_MAX_STACK 8
+int f110_replay_stack(f110_handle *h, const int64_t *frame_rows, int32_t n, int32_t stack, int64_t *rows_out, int32_t *depth, void *stream);
 
 /* Prioritized replay (Schaul et al., "Prioritized Experience Replay"; the reference draws uniformly): an exact integer sum tree over
  * the ring's transitions, on the device, opt-in.  Without f110_priority_install nothing here launches and f110_replay_update's launch
@@ -868,6 +893,27 @@ int f110_bitconv_forward_u8(const f110_bitconv_config *cfg, const uint8_t *image
                             const float *weight, const float *bias, float *out, void *stream);
 int f110_bitconv_backward(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int64_t n,
                           const float *grad_out, float *grad_weight, float *grad_bias, float *workspace, void *stream);
+/* The same layer on a stack of frames: nn.Conv2d(stack, C, kernel, stride) whose input channels are `stack` frames of the frame
+ * tensor (f110_replay_stack's rows), still from bits.  cfg is f110_bitconv_config unchanged; frames is the packed form only (there
+ * is no _u8 entry); index [n, stack] dev int64 is required: channel j of sample i is frame index[i][j], an entry outside 0 ..
+ * n_frames - 1 reads a frame of zeros, repeats are allowed.  weight and grad_weight are [channels, stack, kernel, kernel].
+ * Forward numerics, in fp32: acc = 0; for the frames j major, then ky, then kx minor: acc = acc + w[c][j][ky][kx] if that tap of
+ * frame index[i][j] is set; out = (acc * on) + bias[c]; then the relu.  With stack = 1 this is f110_bitconv_forward's contract, so
+ * its bits.  One launch per group of samples, as f110_bitconv_forward.
+ * f110_bitconv_backward_stack: grad_weight[:, j] is, bit for bit, what f110_bitconv_backward returns for the index column
+ * index[:, j], and grad_bias its grad_bias -- that fixes every summation order.  It is built as a loop over the columns on
+ * f110_bitconv_backward's own kernels: one launch that transposes the index into the workspace, then per column the partial sums
+ * and a reduction that writes with the [channels, stack, kernel, kernel] stride (1 + 2 * stack launches; grad_out is read once per
+ * column).  workspace: 16-byte aligned, f110_bitconv_workspace_stack bytes (0 for an invalid configuration, a stack outside its
+ * range or n < 1).  No allocation, no synchronisation, no atomics.
+ * F110_E_INVALID for stack outside 1 .. F110_BITCONV_MAX_STACK, a NULL index and whatever f110_bitconv_validate and the one-frame
+ * entries refuse. */
+#define F110_BITCONV_MAX_STACK 8
+int f110_bitconv_forward_stack(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int32_t stack,
+                               int64_t n, const float *weight, const float *bias, float *out, void *stream);
+int64_t f110_bitconv_workspace_stack(const f110_bitconv_config *cfg, int32_t stack, int64_t n);
+int f110_bitconv_backward_stack(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int32_t stack,
+                                int64_t n, const float *grad_out, float *grad_weight, float *grad_bias, float *workspace, void *stream);
 
 /* Policy stem for acting: relu(conv2(relu(conv1(x)))) of the reference's Actor and Critic (src/SAL.py:397-398, 405-406, 429-430,
  * 436-437; conv2 = nn.Conv2d(16, 32, kernel_size=4, stride=2)) from bits in one kernel.  The first layer's activations never

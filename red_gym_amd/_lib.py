@@ -95,6 +95,7 @@ class ReplayConfig(C.Structure):
 REPLAY_FIELDS = ['frames', 'actions', 'rewards', 'dones', 'valid', 'count', 'chain_start', 't_seen', 'last_valid', 'action_in']
 F110_REPLAY_TRIES = 64
 F110_REPLAY_MAX_NSTEP = 64
+F110_REPLAY_MAX_STACK = 8
 
 
 class ReplayBuffers(C.Structure):
@@ -120,6 +121,9 @@ class EpisodesBuffers(C.Structure):
 class BitconvConfig(C.Structure):
     _fields_ = [('rows', C.c_int32), ('cols', C.c_int32), ('kernel', C.c_int32), ('stride', C.c_int32),
                 ('channels', C.c_int32), ('relu', C.c_int32), ('on', C.c_float)]
+
+
+F110_BITCONV_MAX_STACK = 8          # input channels of the stacked first convolution (f110_bitconv_forward_stack)
 
 
 # f110_bitconv2_config: the policy stem (conv1 + relu + conv2) from bits, forward only (stateless)
@@ -335,6 +339,7 @@ SYMBOLS = {
     'f110_replay_sample': [_VP, C.c_uint64, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_replay_nstep': [_VP, _VP, _I32, _I32, _D, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_replay_sample_nstep': [_VP, C.c_uint64, _VP, _I32, _I32, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_replay_stack': [_VP, _VP, _I32, _I32, _VP, _VP, _VP],
     'f110_priority_node_words': [_I64],
     'f110_ptree_rebuild': [_VP, _VP, _I64, _VP],
     'f110_ptree_set': [_VP, _VP, _I64, _VP, _VP, _I32, _VP],
@@ -355,6 +360,9 @@ SYMBOLS = {
     'f110_bitconv_forward': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP],
     'f110_bitconv_forward_u8': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP],
     'f110_bitconv_backward': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP],
+    'f110_bitconv_forward_stack': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I32, _I64, _VP, _VP, _VP, _VP],
+    'f110_bitconv_workspace_stack': [C.POINTER(BitconvConfig), _I32, _I64],
+    'f110_bitconv_backward_stack': [C.POINTER(BitconvConfig), _VP, _I64, _VP, _I32, _I64, _VP, _VP, _VP, _VP, _VP],
     'f110_bitconv2_validate': [C.POINTER(Bitconv2Config)],
     'f110_bitconv2_forward': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_bitconv2_forward_u8': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
@@ -417,7 +425,7 @@ RESTYPES = {
     'f110_destroy': None, 'f110_graph_destroy': None, 'f110_bitmap_destroy': None,
     'f110_pack_env_size': _I64, 'f110_adam_state_bytes': _I64, 'f110_temperature_state_bytes': _I64,
     'f110_gauss_state_bytes': _I64, 'f110_priority_node_words': _I64,
-    'f110_pure_pursuit_workspace': _I64, 'f110_bitconv_workspace': _I64, 'f110_featconv_workspace': _I64,
+    'f110_pure_pursuit_workspace': _I64, 'f110_bitconv_workspace': _I64, 'f110_bitconv_workspace_stack': _I64, 'f110_featconv_workspace': _I64,
     'f110_dense_workspace': _I64, 'f110_policyhead_workspace': _I64, 'f110_qhead_workspace': _I64,
 }
 

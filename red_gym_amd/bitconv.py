@@ -11,6 +11,7 @@ import torch
 from . import _lib
 
 MAX_KERNEL, MAX_CHANNELS = 8, 64
+MAX_STACK = _lib.F110_BITCONV_MAX_STACK                         # input channels of conv_bits: frames of a stack
 MAX_KERNEL2, MAX_STEM_CHANNELS, MAX_STEM_WIDTH = 4, 16, 64     # conv_bits2: kernel2, the first layer's channels and output width
 
 
@@ -110,6 +111,62 @@ class _ConvBits(torch.autograd.Function):
         return None, (gw if ctx.needs_input_grad[1] else None), gb, None, None, None, None
 
 
+class _ConvBitsStack(torch.autograd.Function):
+    """conv_bits on a stack: f110_bitconv_forward_stack / f110_bitconv_backward_stack (packed frames, index [n, k])."""
+
+    @staticmethod
+    def forward(ctx, frames, weight, bias, index, cfg):
+        lib = _lib.load()
+        dev = frames.device
+        n, k = int(index.shape[0]), int(index.shape[1])
+        oh, ow = output_size(cfg.rows, cfg.cols, cfg.kernel, cfg.stride)
+        out = torch.empty((n, cfg.channels, oh, ow), dtype=torch.float32, device=dev)
+        w = weight.detach().contiguous()
+        b = None if bias is None else bias.detach().contiguous()
+        with torch.cuda.device(dev):
+            _lib.check(lib.f110_bitconv_forward_stack(C.byref(cfg), frames.data_ptr(), frames.shape[0], index.data_ptr(), k, n, w.data_ptr(),
+                                                      _lib.ptr(b), out.data_ptr(), _lib.stream(dev)))
+        ctx.cfg, ctx.has_bias = cfg, bias is not None
+        ctx.save_for_backward(frames, index, out if cfg.relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        frames, index, out = ctx.saved_tensors
+        cfg, dev = ctx.cfg, grad_out.device
+        n, k = int(index.shape[0]), int(index.shape[1])
+        if out is not None:
+            grad_out = grad_out * (out > 0)           # relu: the kernel takes grad_out already masked
+        g = grad_out.to(torch.float32).contiguous()
+        gw = torch.empty((cfg.channels, k, cfg.kernel, cfg.kernel), dtype=torch.float32, device=dev)
+        gb = torch.empty((cfg.channels,), dtype=torch.float32, device=dev) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        if n == 0:
+            return None, (gw.zero_() if ctx.needs_input_grad[1] else None), (None if gb is None else gb.zero_()), None, None
+        nbytes = lib.f110_bitconv_workspace_stack(C.byref(cfg), k, n)
+        assert nbytes >= 4 * cfg.channels * (cfg.kernel * cfg.kernel + 1) + 8 * k * n and nbytes % 4 == 0
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.f110_bitconv_backward_stack(C.byref(cfg), frames.data_ptr(), frames.shape[0], index.data_ptr(), k, n, g.data_ptr(),
+                                                       gw.data_ptr(), _lib.ptr(gb), ws.data_ptr(), _lib.stream(dev)))
+        return None, (gw if ctx.needs_input_grad[1] else None), gb, None, None
+
+
+def _conv_bits_stack(frames, weight, bias, stride, on, relu, index, cols):
+    """conv_bits for a weight [C, k, K, K] with k > 1: the checks, then _ConvBitsStack."""
+    who = 'conv_bits'
+    ch, k, ks = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
+    if k > MAX_STACK:
+        raise ValueError('%s: %d input channels (a stack has 1..%d frames)' % (who, k, MAX_STACK))
+    if frames.dtype != torch.int64:
+        raise ValueError('%s: a stack of frames is read from packed int64 frames (the replay ring\'s), not %s' % (who, frames.dtype))
+    _, rows, cols = _frames_kind(who, frames, cols)
+    if not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 2 or index.shape[1] != k or index.device != frames.device:
+        raise ValueError('%s: a weight of %d input channels needs an int64 index [n, %d] on the frames\' device' % (who, k, k))
+    cfg = validate(rows, cols, ks, stride, ch, on, relu)
+    return _ConvBitsStack.apply(frames.contiguous(), weight, bias, index.contiguous(), cfg)
+
+
 def conv_bits(frames, weight, bias=None, stride=1, on=1.0, relu=False, index=None, cols=None):
     """nn.Conv2d(1, C, kernel, stride) on images of two values, from their bits.
     frames: int64 [m, rows, words] device tensor in the replay ring's format (replay.pack_bitmaps, ReplayBuffer.sample_frames)
@@ -119,11 +176,19 @@ def conv_bits(frames, weight, bias=None, stride=1, on=1.0, relu=False, index=Non
     zeros; repeats are allowed.
     Returns [n, C, OH, OW] fp32 on the caller's current stream, without synchronising: out = on * sum of the weights under set
     pixels + bias, the taps added in the order ky major, kx minor (csrc/f110_bitconv.h).  Differentiable in weight and bias;
-    frames are data.  ValueError for what f110_bitconv_validate refuses and for a dtype / shape mismatch."""
+    frames are data.  ValueError for what f110_bitconv_validate refuses and for a dtype / shape mismatch.
+    A stack of frames: weight [C, k, K, K] with 1 < k <= MAX_STACK is nn.Conv2d(k, C, K, stride) whose input channel j of sample i is
+    frame index[i, j]; index int64 [n, k] is then required (ReplayBuffer.stack_rows gives it) and frames are the packed form.  The
+    frames are added j major, then ky, kx; grad_weight[:, j] is bit for bit what the one-frame call gives for index[:, j]."""
     if not torch.is_tensor(frames) or not torch.is_tensor(weight):
         raise ValueError('conv_bits: frames and weight must be tensors')
     if not frames.is_cuda or weight.device != frames.device:
         raise ValueError('conv_bits: frames and weight must be on the same GPU')
+    if weight.dtype == torch.float32 and weight.dim() == 4 and weight.shape[1] > 1 and weight.shape[2] == weight.shape[3]:
+        if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (int(weight.shape[0]),)
+                                 or bias.device != frames.device):
+            raise ValueError('conv_bits: bias must be fp32 [%d] on the frames\' device' % int(weight.shape[0]))
+        return _conv_bits_stack(frames, weight, bias, stride, on, relu, index, cols)
     if weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[1] != 1 or weight.shape[2] != weight.shape[3]:
         raise ValueError('conv_bits: weight must be fp32 [C, 1, k, k], not %s %s' % (weight.dtype, tuple(weight.shape)))
     ch, k = int(weight.shape[0]), int(weight.shape[2])
@@ -131,6 +196,8 @@ def conv_bits(frames, weight, bias=None, stride=1, on=1.0, relu=False, index=Non
         raise ValueError('conv_bits: bias must be fp32 [%d] on the frames\' device' % ch)
     u8, rows, cols = _frames_kind('conv_bits', frames, cols)
     cfg = validate(rows, cols, k, stride, ch, on, relu)
+    if torch.is_tensor(index) and index.dim() == 2 and index.shape[1] == 1:
+        index = index[:, 0]                           # a stack of one frame: the one-frame entry, the same bits
     index, n = _index_arg('conv_bits', index, frames)
     return _ConvBits.apply(frames.contiguous(), weight, bias, index, cfg, n, u8)
 
@@ -224,22 +291,29 @@ def _plain_conv(who, conv, name, in_channels, wrong_in):
 class BitConv2d(torch.nn.Module):
     """nn.Conv2d(1, out_channels, kernel_size, stride) on two-valued images, computed by conv_bits.  Its parameters have the
     names and shapes of nn.Conv2d's (weight [C, 1, k, k], bias [C]), so state dicts pass between the two in both directions.
-    forward(frames, index=None): frames uint8 [n, rows, cols], or int64 packed [m, rows, words] when `cols` was given."""
+    forward(frames, index=None): frames uint8 [n, rows, cols], or int64 packed [m, rows, words] when `cols` was given.
+    in_channels = k > 1: nn.Conv2d(k, ...) on stacks of k packed frames, forward(frames, index [n, k]) (conv_bits)."""
 
-    def __init__(self, out_channels, kernel_size, stride=1, bias=True, on=1.0, relu=False, cols=None, device=None):
+    def __init__(self, out_channels, kernel_size, stride=1, bias=True, on=1.0, relu=False, cols=None, device=None, in_channels=1):
         super().__init__()
         k = int(kernel_size)
-        ref = torch.nn.Conv2d(1, int(out_channels), k, int(stride), bias=bias, device=device)   # (for its initialisation)
+        if isinstance(in_channels, bool) or not isinstance(in_channels, int) or not 1 <= in_channels <= MAX_STACK:
+            raise ValueError('BitConv2d: in_channels %r (an int in 1..%d: the frames of a stack)' % (in_channels, MAX_STACK))
+        ref = torch.nn.Conv2d(in_channels, int(out_channels), k, int(stride), bias=bias, device=device)   # (for its initialisation)
         self.weight = ref.weight
         self.register_parameter('bias', ref.bias)
         self.kernel_size, self.stride, self.on, self.relu, self.cols = k, int(stride), float(on), bool(relu), cols
         validate(k, k, k, self.stride, int(out_channels), self.on)
 
     @classmethod
-    def from_conv(cls, conv, on=1.0, relu=False, cols=None):
+    def from_conv(cls, conv, on=1.0, relu=False, cols=None, in_channels=1):
         """A BitConv2d that shares the parameters of `conv` (the same tensors: training one trains the other).  ValueError
-        unless it is an nn.Conv2d(1, C, k, stride) with a square kernel and stride, no padding, dilation or groups."""
-        k, s = _plain_conv('BitConv2d.from_conv', conv, '', 1, 'in_channels = %d (a bitmap has one channel)')
+        unless it is an nn.Conv2d(in_channels, C, k, stride) with a square kernel and stride, no padding, dilation or groups;
+        in_channels: 1, a bitmap's one channel, or the frames of a stack, 2..MAX_STACK, which the caller names."""
+        if isinstance(in_channels, bool) or not isinstance(in_channels, int) or not 1 <= in_channels <= MAX_STACK:
+            raise ValueError('BitConv2d.from_conv: in_channels %r (an int in 1..%d: the frames of a stack)' % (in_channels, MAX_STACK))
+        wrong = 'in_channels = %d (a bitmap has one channel)' if in_channels == 1 else 'in_channels = %%d (the stack has %d frames)' % in_channels
+        k, s = _plain_conv('BitConv2d.from_conv', conv, '', in_channels, wrong)
         validate(k, k, k, s, conv.out_channels, on)
         m = cls.__new__(cls)
         torch.nn.Module.__init__(m)
@@ -253,7 +327,8 @@ class BitConv2d(torch.nn.Module):
                          cols=None if frames.dtype == torch.uint8 else self.cols)
 
     def extra_repr(self):
-        return '1, %d, kernel_size=%d, stride=%d, on=%g, relu=%s' % (self.weight.shape[0], self.kernel_size, self.stride, self.on, self.relu)
+        return '%d, %d, kernel_size=%d, stride=%d, on=%g, relu=%s' % (self.weight.shape[1], self.weight.shape[0], self.kernel_size, self.stride, self.on,
+                                                                       self.relu)
 
 
 def _plain_conv2(who, conv2, in_channels):

@@ -9,6 +9,10 @@
 //   bitconv_backward_kernel  stage 1 of grad_weight / grad_bias: a workgroup walks tiles g, g + G, ... (G fixed by the shape), a
 //                            lane owns one tap, a wave one row of the tile, and sums grad_out * bit in a fixed order
 //   bitconv_reduce_kernel    stage 2: the G partials of every element summed in a fixed order, times `on`
+//   bitconv_forward_stack_kernel  the layer with `stack` input channels, each a frame named by index [n, stack]: the masks of all
+//                            frames of a tile go to LDS, then chunks of BCS_CHUNK channels accumulate over the frames in registers
+//   bitconv_index_columns_kernel, bitconv_reduce_stack_kernel  the stacked backward is the one-frame backward per index column: the
+//                            index transposed once, and stage 2 written with the [C, stack, K, K] stride
 // Forward numerics (the contract of include/f110_hip.h): acc = 0; taps ky major, kx minor: acc = fma(w, bit, acc) with bit 0.0 or
 // 1.0 -- w * bit is exact, so this is acc + w for a set tap and acc for a clear one, rounded once per tap; out = (acc * on) + bias.
 // Limits, BitconvArgs and the host's checks and launch plans are in f110_bitconv_plan.h (f110_bitconv_abi.hip launches them); it
@@ -221,6 +225,98 @@ static __global__ __launch_bounds__(BC_THREADS) void bitconv_reduce_kernel(const
     const float v = (s[0] + s[1]) + (s[2] + s[3]);
     if (is_w) grad_weight[o] = v * on;
     else if (grad_bias) grad_bias[o - nw] = v;
+}
+
+// ---------------------------------------------------------------- the same layer on a stack of frames
+// grid as bitconv_forward_kernel; weight [C, stack, K, K], index [n, stack].  Pass 1: for every frame of the stack the tile is staged
+// and each lane keeps its window's mask in LDS (masks[j][tid]: its own entry, so pass 2 needs no barrier).  Pass 2: per chunk of
+// BCS_CHUNK channels one accumulator per channel in registers; for the frames in order the mask is expanded once to bit[K * K]
+// (constant indices only) and every channel of the chunk adds its K * K taps, the weights wave-uniform.  Per channel that is the
+// contract's order -- j major, ky, kx minor -- and with stack = 1 the one-frame kernel's chain of fmas.
+template <int K>
+static __global__ __launch_bounds__(BC_THREADS) void bitconv_forward_stack_kernel(BitconvStackArgs s, const float *__restrict__ weight,
+                                                                                 const float *__restrict__ bias, float *__restrict__ out)
+{
+    __shared__ uint64_t lds[BC_LROWS * BC_LWORDS];
+    __shared__ uint64_t masks[F110_BITCONV_MAX_STACK * BC_THREADS];
+    const BitconvArgs &a = s.a;
+    const f110_bitconv_config &c = a.cfg;
+    const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
+    BitconvTile t = bitconv_tile(a, a.first * ((long long)a.tiles_x * a.tiles_y) + (long long)blockIdx.x);
+    const int oy = t.oy0 + ty, ox = t.ox0 + tx;
+    const bool in = oy < a.OH && ox < a.OW;
+    for (int j = 0; j < s.stack; j++) {
+        const long long src = s.index[(size_t)t.i * (size_t)s.stack + (size_t)j];
+        t.src = src >= 0 && src < a.n_frames ? src : -1;
+        bitconv_stage<false>(a, t, lds, tid);
+        __syncthreads();
+        masks[j * BC_THREADS + tid] = in ? bitconv_mask<K>(lds, t, c.stride, ty, tx) : 0ull;
+        __syncthreads();
+    }
+    if (!in) return;
+    const size_t plane = (size_t)a.OH * (size_t)a.OW;
+    float *o = out + (size_t)t.i * (size_t)c.channels * plane + (size_t)oy * (size_t)a.OW + (size_t)ox;
+    for (int c0 = 0; c0 < c.channels; c0 += BCS_CHUNK) {
+        float acc[BCS_CHUNK];
+#pragma unroll
+        for (int q = 0; q < BCS_CHUNK; q++) acc[q] = 0.0f;
+        for (int j = 0; j < s.stack; j++) {
+            const uint64_t m = masks[j * BC_THREADS + tid];
+            float bit[K * K];
+#pragma unroll
+            for (int k = 0; k < K * K; k++) bit[k] = (m >> k) & 1ull ? 1.0f : 0.0f;
+#pragma unroll
+            for (int q = 0; q < BCS_CHUNK; q++) {
+                const int ch = min(c0 + q, c.channels - 1);    // (a channel beyond C repeats the last one; it is not written)
+                const float *w = weight + ((size_t)ch * (size_t)s.stack + (size_t)j) * (size_t)(K * K);   // wave-uniform: scalar loads
+#pragma unroll
+                for (int k = 0; k < K * K; k++) acc[q] = __builtin_fmaf(w[k], bit[k], acc[q]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < BCS_CHUNK; q++) {
+            const int ch = c0 + q;
+            if (ch < c.channels) {
+                float v = acc[q] * c.on;
+                v = v + (bias ? bias[ch] : 0.0f);
+                if (c.relu) v = v < 0.0f ? 0.0f : v;
+                o[(size_t)ch * plane] = v;
+            }
+        }
+    }
+}
+
+// one lane per entry: index [n, stack] -> columns [stack, n], so that f110_bitconv_backward's kernels read column j as their index
+static __global__ __launch_bounds__(BC_THREADS) void bitconv_index_columns_kernel(const long long *__restrict__ index, long long n, int stack,
+                                                                                 long long *__restrict__ columns)
+{
+    const long long o = (long long)blockIdx.x * BC_THREADS + threadIdx.x;
+    if (o >= n * stack) return;
+    const long long j = o / n, i = o - j * n;
+    columns[o] = index[i * stack + j];
+}
+
+// bitconv_reduce_kernel's sums in its order, written into column j of grad_weight [C, stack, kk]; the bias (the same for every
+// column: it does not depend on the frames) where the caller passes it
+static __global__ __launch_bounds__(BC_THREADS) void bitconv_reduce_stack_kernel(const float *ws, int G, int nw, int C, float on, int kk, int stack, int j,
+                                                                                float *grad_weight, float *grad_bias)
+{
+    const int o = blockIdx.x * BC_THREADS + threadIdx.x;
+    if (o >= nw + C) return;
+    const bool is_w = o < nw;
+    const float *p = is_w ? ws + o : ws + (size_t)G * (size_t)nw + (size_t)(o - nw);
+    const size_t step = is_w ? (size_t)nw : (size_t)C;
+    float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int g = 0; g < G; g += 4) {
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            if (g + q < G) s[q] = s[q] + p[(size_t)(g + q) * step];
+    }
+    const float v = (s[0] + s[1]) + (s[2] + s[3]);
+    if (is_w) {
+        const int ch = o / kk, k = o - ch * kk;
+        grad_weight[((size_t)ch * (size_t)stack + (size_t)j) * (size_t)kk + (size_t)k] = v * on;
+    } else if (grad_bias) grad_bias[o - nw] = v;
 }
 
 } // namespace f110

@@ -74,6 +74,66 @@ extern "C" int f110_bitconv_backward(const f110_bitconv_config *cfg, const uint6
     return F110_OK;
 }
 
+// ---------------------------------------------------------------- the same layer on a stack of frames
+extern "C" int f110_bitconv_forward_stack(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int32_t stack,
+                                          int64_t n, const float *weight, const float *bias, float *out, void *stream)
+{
+    const char *who = "f110_bitconv_forward_stack";
+    if (int rc = f110_bitconv_validate(cfg)) return rc;
+    if (int rc = bitconv_stack_check(stack, who)) return rc;
+    if (n < 0 || n_frames < 0) return fail(F110_E_INVALID, "%s: n=%lld samples of %lld frames", who, (long long)n, (long long)n_frames);
+    if (!index) return fail(F110_E_INVALID, "%s: null index (a stack names its frames)", who);
+    if (n == 0) return F110_OK;
+    if (!weight || !out || (n_frames > 0 && !frames)) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if ((uintptr_t)frames % 8) return fail(F110_E_INVALID, "%s: frames must be 8-byte aligned", who);
+    BitconvStackForwardPlan p = bitconv_forward_stack_plan(*cfg, stack, n);
+    BitconvStackArgs &s = p.s;
+    s.a.frames = frames; s.a.n_frames = n_frames; s.index = (const long long *)index;
+    for (const BitconvGroup &g : p.groups) {
+        s.a.first = g.first; p.l.gx = g.grid;
+#define BITCONV_FWDS(K) F110_LAUNCH((bitconv_forward_stack_kernel<K>), p.l, (hipStream_t)stream, s, weight, bias, out)
+        BITCONV_BY_KERNEL(p.l.inst, BITCONV_FWDS)
+#undef BITCONV_FWDS
+        HIP_TRY(hipGetLastError());
+    }
+    return F110_OK;
+}
+
+extern "C" int64_t f110_bitconv_workspace_stack(const f110_bitconv_config *cfg, int32_t stack, int64_t n)
+{
+    if (n < 1 || stack < 1 || stack > F110_BITCONV_MAX_STACK || f110_bitconv_validate(cfg) != F110_OK) return 0;
+    return bitconv_stack_workspace_bytes(*cfg, stack, n);
+}
+
+extern "C" int f110_bitconv_backward_stack(const f110_bitconv_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int32_t stack,
+                                           int64_t n, const float *grad_out, float *grad_weight, float *grad_bias, float *workspace, void *stream)
+{
+    const char *who = "f110_bitconv_backward_stack";
+    if (int rc = f110_bitconv_validate(cfg)) return rc;
+    if (int rc = bitconv_stack_check(stack, who)) return rc;
+    if (n < 1 || n > (1ll << 31) || n_frames < 0) return fail(F110_E_INVALID, "%s: n=%lld samples of %lld frames", who, (long long)n, (long long)n_frames);
+    if (!index) return fail(F110_E_INVALID, "%s: null index (a stack names its frames)", who);
+    if (!grad_out || !grad_weight || !workspace || (n_frames > 0 && !frames)) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if ((uintptr_t)frames % 8 || (uintptr_t)workspace % 16) return fail(F110_E_INVALID, "%s: frames must be 8-byte and the workspace 16-byte aligned", who);
+    BitconvStackBackwardPlan p = bitconv_backward_stack_plan(*cfg, stack, n);
+    long long *columns = reinterpret_cast<long long *>(reinterpret_cast<char *>(workspace) + p.index_offset);
+    F110_LAUNCH(bitconv_index_columns_kernel, p.columns, (hipStream_t)stream, (const long long *)index, (long long)n, (int)stack, columns);
+    HIP_TRY(hipGetLastError());
+    BitconvArgs &a = p.one.a;
+    a.frames = frames; a.n_frames = n_frames; a.grad_out = grad_out; a.ws = workspace;
+    for (int j = 0; j < stack; j++) {
+        a.index = columns + (size_t)j * (size_t)n;
+#define BITCONV_BWD(K) F110_LAUNCH((bitconv_backward_kernel<K>), p.one.partials, (hipStream_t)stream, a)
+        BITCONV_BY_KERNEL(p.one.partials.inst, BITCONV_BWD)
+#undef BITCONV_BWD
+        HIP_TRY(hipGetLastError());
+        F110_LAUNCH(bitconv_reduce_stack_kernel, p.one.reduce, (hipStream_t)stream, (const float *)workspace, a.G, p.one.nw, cfg->channels, cfg->on,
+                    cfg->kernel * cfg->kernel, (int)stack, j, grad_weight, j == 0 ? grad_bias : (float *)nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    return F110_OK;
+}
+
 // ---------------------------------------------------------------- policy stem: conv1 + relu + conv2 from bits
 extern "C" int f110_bitconv2_validate(const f110_bitconv2_config *cfg) { return bitconv2_check(cfg, "f110_bitconv2_validate"); }
 

@@ -106,6 +106,55 @@ inline BitconvBackwardPlan bitconv_backward_plan(const f110_bitconv_config &c, i
     return p;
 }
 
+// ---------------------------------------------------------------- the same layer on a stack of frames
+constexpr int BCS_CHUNK = 4;                  // channels whose accumulators a lane of the stacked forward keeps at once: their
+                                              // K * K weights each are wave-uniform and share the scalar registers (8 or 16 spill)
+
+struct BitconvStackArgs {
+    BitconvArgs a;                  // as the one-frame launch, with a.index = NULL: the frames are named by `index` below
+    const long long *index;         // [n, stack]: frame of channel j of sample i
+    int stack;                      // 1 .. F110_BITCONV_MAX_STACK
+};
+
+inline int bitconv_stack_check(int32_t stack, const char *who)
+{
+    if (stack < 1 || stack > F110_BITCONV_MAX_STACK) return fail(F110_E_INVALID, "%s: stack %d (1..%d)", who, stack, F110_BITCONV_MAX_STACK);
+    return F110_OK;
+}
+
+// f110_bitconv_forward_stack on n >= 1 samples: bitconv_forward_stack_kernel<K>, l.inst = K, once per group as the one-frame forward
+struct BitconvStackForwardPlan { BitconvStackArgs s; Launch l; std::vector<BitconvGroup> groups; };
+
+inline BitconvStackForwardPlan bitconv_forward_stack_plan(const f110_bitconv_config &c, int stack, int64_t n)
+{
+    const BitconvForwardPlan one = bitconv_forward_plan(c, false, n);
+    BitconvStackForwardPlan p;
+    p.s.a = one.a; p.s.index = nullptr; p.s.stack = stack;
+    p.l = one.l; p.l.inst = c.kernel;
+    p.groups = one.groups;
+    return p;
+}
+
+// f110_bitconv_backward_stack: the workspace is f110_bitconv_backward's partial sums (rounded up to 16 bytes), then the index
+// transposed to [stack, n] int64; bitconv_index_columns_kernel fills the latter (one lane per entry), then per column j the one-frame
+// plan's partials launch on column j and bitconv_reduce_stack_kernel (the one-frame reduce's grid) into grad_weight[:, j]
+inline int64_t bitconv_stack_partial_bytes(const f110_bitconv_config &c, int64_t n) { return (bitconv_workspace_bytes(c, n) + 15) / 16 * 16; }
+inline int64_t bitconv_stack_workspace_bytes(const f110_bitconv_config &c, int stack, int64_t n)
+{
+    return bitconv_stack_partial_bytes(c, n) + (int64_t)stack * n * (int64_t)sizeof(int64_t);
+}
+
+struct BitconvStackBackwardPlan { BitconvBackwardPlan one; Launch columns; int64_t index_offset; };
+
+inline BitconvStackBackwardPlan bitconv_backward_stack_plan(const f110_bitconv_config &c, int stack, int64_t n)
+{
+    BitconvStackBackwardPlan p;
+    p.one = bitconv_backward_plan(c, n);
+    p.columns = {(unsigned)(((int64_t)stack * n + BC_THREADS - 1) / BC_THREADS), 1, 1, (unsigned)BC_THREADS, 0, 0};
+    p.index_offset = bitconv_stack_partial_bytes(c, n);
+    return p;
+}
+
 // ---------------------------------------------------------------- policy stem: conv1 + relu + conv2 from bits
 constexpr int BC2_MAX_K2 = 4, BC2_MAX_C1 = 16, BC2_MAX_C2 = 64, BC2_MAX_OW1 = 64;
 constexpr int BC2_KSTEPS = BC2_MAX_C1 * BC2_MAX_K2 * BC2_MAX_K2 / 4;     // 64 steps of 4 at most

@@ -872,6 +872,25 @@ extern "C" int f110_replay_sample_nstep(f110_handle *h, uint64_t seed, uint64_t 
     return F110_OK;
 }
 
+extern "C" int f110_replay_stack(f110_handle *h, const int64_t *frame_rows, int32_t n, int32_t stack, int64_t *rows_out, int32_t *depth, void *stream)
+{
+    const char *who = "f110_replay_stack";
+    if (!h) return fail(F110_E_INVALID, "%s: null handle", who);
+    ReplayStackArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = replay_ready(h, who, a.ring)) return rc;
+    if (n < 0) return fail(F110_E_INVALID, "%s: n=%d", who, n);
+    if (stack < 1 || stack > F110_REPLAY_MAX_STACK) return fail(F110_E_INVALID, "%s: stack %d (1..%d)", who, stack, F110_REPLAY_MAX_STACK);
+    if (!frame_rows && n != a.ring.n_envs)
+        return fail(F110_E_INVALID, "%s: n=%d rows without frame_rows (the newest frame of each of the %d envs)", who, n, a.ring.n_envs);
+    if (!rows_out || !depth) return fail(F110_E_INVALID, "%s: null argument", who);
+    if (n == 0) return F110_OK;
+    a.rows_in = (const long long *)frame_rows; a.n = n; a.stack = stack; a.rows_out = (long long *)rows_out; a.depth = depth;
+    hipLaunchKernelGGL(replay_stack_kernel, dim3((unsigned)((n + REPLAY_THREADS - 1) / REPLAY_THREADS)), dim3(REPLAY_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
 // ---------------------------------------------------------------- prioritized replay: the tree alone, then on the handle
 static PriorityTree priority_tree(const uint32_t *leaf, const uint64_t *node, int64_t L, uint32_t *dev_err)
 {

@@ -18,6 +18,8 @@
 //                          loads of valid, reward and done, one step slot = n_envs cells apart), for indices the caller names
 //   replay_sample_nstep_kernel  one lane per draw: replay_sample_kernel with the walk behind the locate; both are kernels of their
 //                          own beside the one-step ones, which keep their code
+//   replay_stack_kernel    one lane per frame row: the rows of the env's previous stack - 1 frames, walked backwards while the pushes
+//                          between them link (up to stack - 1 loads of valid); the oldest row reached fills the rest
 #pragma once
 #include "../../include/f110_hip.h" // F110_REPLAY_TRIES
 #include "f110_bounds.h"
@@ -460,6 +462,72 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_sample_nstep_ker
     a.discount[i] = discount;
     a.d[i] = d;
     a.span[i] = span;
+}
+
+struct ReplayStackArgs {
+    ReplayRing ring;
+    const long long *rows_in;       // [n] rows of the frame tensor, or NULL: row i = env i's newest frame (n = n_envs)
+    int n, stack;                   // 1 <= stack <= F110_REPLAY_MAX_STACK
+    long long *rows_out;            // [n, stack]
+    int *depth;                     // [n]
+};
+
+// one lane per row: the backward walk, the mirror of replay_walk (the contract is include/f110_hip.h's "Frame stacks").  Frame row
+// -> the push c that wrote it (the newest one of its frame slot), then the frames c - 1, c - 2, ... of the same env while push c - j
+// + 1 links: it is still in the ring (>= count - steps; >= 1, because push 0 has no frame before it) and valid.  The loads of valid
+// do not depend on one another; frame slots wrap at steps + 1, step slots at steps.
+static __global__ __launch_bounds__(REPLAY_THREADS) void replay_stack_kernel(ReplayStackArgs a)
+{
+    const ReplayRing &g = a.ring;
+    const int i = blockIdx.x * REPLAY_THREADS + threadIdx.x;
+    if (i >= a.n) return;
+    const long long count = *g.count, F = g.steps + 1;
+    long long c = 0;
+    int env = 0;
+    bool ok = count >= 1;
+    if (a.rows_in) {
+        const long long row = a.rows_in[i];
+        ok = ok && row >= 0 && row < F * g.n_envs;
+        if (ok) {
+            const long long slot = row / g.n_envs;
+            env = (int)(row - slot * g.n_envs);
+            ok = slot <= count - 1;                       // a slot no push has written
+            c = count - 1 - (count - 1 - slot) % F;       // the newest push that went to this frame slot
+        }
+    } else {
+        env = i;
+        c = count - 1;
+        ok = ok && env < g.n_envs;
+    }
+    long long *o = a.rows_out + (size_t)i * (size_t)a.stack;
+    if (!ok) {
+        for (int j = 0; j < a.stack; j++) o[j] = -1;
+        a.depth[i] = 0;
+        return;
+    }
+    F110_BCHK(c >= 0 && c <= count - 1 && c >= count - F && env >= 0 && env < g.n_envs, BT_REPLAY, g.dev_err);
+    const long long oldest = count - g.steps;             // the oldest push whose step slot is still the ring's
+    long long row = (c % F) * g.n_envs + env;
+    int depth = 1;
+    bool linked = true;
+    o[0] = row;
+    for (int j = 1; j < a.stack; j++) {
+        const long long p = c - j + 1;                    // the push that links frame c - j + 1 to frame c - j
+        linked = linked && p >= 1 && p >= oldest;
+        if (linked) {
+            const long long ss = p % g.steps;
+            F110_BCHK(ss >= 0 && ss < g.steps, BT_REPLAY, g.dev_err);
+            linked = g.valid[(size_t)ss * (size_t)g.n_envs + (size_t)env] != 0;
+        }
+        if (linked) {
+            const long long fs = (p - 1) % F;
+            F110_BCHK(fs >= 0 && fs <= g.steps, BT_REPLAY, g.dev_err);
+            row = fs * g.n_envs + env;
+            depth++;
+        }
+        o[j] = row;
+    }
+    a.depth[i] = depth;
 }
 
 static __global__ void replay_counter_advance_kernel(unsigned long long *counter, unsigned long long n)

@@ -150,11 +150,14 @@ class Trunk(torch.nn.Module):
     forward(frames, index=None) -> [n, Co * OH * OW] takes one of two paths: while torch.is_grad_enabled() and one of the six
     parameters requires grad, conv_bits(relu) -> conv_feat(relu) -> conv_feat(relu), differentiable; otherwise conv_bits2 ->
     conv_feat(relu).  Both add conv2 in the same order, so the two paths return the same bits: the features a policy acts on are
-    the features it learns from."""
+    the features it learns from.
+    stack = k > 1: conv1 is nn.Conv2d(k, 16, 8, 4) on stacks of k packed frames and forward takes index [n, k]
+    (ReplayBuffer.stack_rows).  Both paths are then conv_bits -> conv_feat -> conv_feat (there is no stacked fused stem), still the
+    same bits; acting writes conv1's activations to memory."""
 
-    def __init__(self, on=1.0, cols=None, device=None):
+    def __init__(self, on=1.0, cols=None, device=None, stack=1):
         super().__init__()
-        self.conv1 = BitConv2d(16, 8, 4, on=on, relu=True, cols=cols, device=device)
+        self.conv1 = BitConv2d(16, 8, 4, on=on, relu=True, cols=cols, device=device, in_channels=stack)
         self.conv2 = FeatConv2d(16, 32, 4, 2, relu=True, device=device)
         self.conv3 = FeatConv2d(32, 32, 3, 1, relu=True, device=device)
         self._check()
@@ -171,23 +174,25 @@ class Trunk(torch.nn.Module):
         validate2(big, big, k1, c1.stride, c1.weight.shape[0], k2, c2.stride, c2.weight.shape[0], c1.on)
 
     @classmethod
-    def from_convs(cls, conv1, conv2, conv3, on=1.0, cols=None):
+    def from_convs(cls, conv1, conv2, conv3, on=1.0, cols=None, stack=1):
         """A trunk that shares the parameters of an existing network's three nn.Conv2d (the same tensors: training one trains the
         other).  ValueError where BitConv2d.from_conv or FeatConv2d.from_conv raises, for channel counts that do not chain, and
-        for a conv2 the fused stem refuses."""
+        for a conv2 the fused stem refuses.  stack = k: conv1 must be an nn.Conv2d(k, ...); the trunk then reads stacks of k frames."""
         m = cls.__new__(cls)
         torch.nn.Module.__init__(m)
-        m.conv1 = BitConv2d.from_conv(conv1, on=on, relu=True, cols=cols)
+        m.conv1 = BitConv2d.from_conv(conv1, on=on, relu=True, cols=cols, in_channels=stack)
         m.conv2 = FeatConv2d.from_conv(conv2, relu=True)
         m.conv3 = FeatConv2d.from_conv(conv3, relu=True)
         m._check()
         return m
 
+    stack = property(lambda self: int(self.conv1.weight.shape[1]))
+
     def forward(self, frames, index=None):
         c1, c2, c3 = self.conv1, self.conv2, self.conv3
         cols = None if frames.dtype == torch.uint8 else c1.cols
         params = (c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias)
-        if torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in params):
+        if self.stack > 1 or (torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in params)):
             a1 = conv_bits(frames, c1.weight, c1.bias, stride=c1.stride, on=c1.on, relu=True, index=index, cols=cols)
             a2 = conv_feat(a1, c2.weight, c2.bias, stride=c2.stride, relu=True)
         else:

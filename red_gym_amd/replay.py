@@ -13,6 +13,7 @@ from .consumer import Consumer
 DEFAULTS = dict(capacity=1000000, steps=None, action_dim=16)
 TRIES = _lib.F110_REPLAY_TRIES
 MAX_NSTEP = _lib.F110_REPLAY_MAX_NSTEP
+MAX_STACK = _lib.F110_REPLAY_MAX_STACK
 
 
 def make_config(num_envs=1, **cfg):
@@ -73,7 +74,7 @@ def unpack_bitmaps(packed, cols):
 
 
 class ReplayBuffer(Consumer):
-    """The replay buffer of one Engine (f110_replay_install / _bind / _update / _draw / _gather / _locate / _sample / _nstep / _sample_nstep).  The ring lives in `buf`:
+    """The replay buffer of one Engine (f110_replay_install / _bind / _update / _draw / _gather / _locate / _sample / _nstep / _sample_nstep / _stack).  The ring lives in `buf`:
     frames [T + 1, B, rows, words] int64 (bit-packed), actions [T, B, action_dim] fp32, rewards [T, B] fp64, dones and valid
     [T, B] uint8, count and chain_start [1] int64, t_seen [B] fp64, last_valid [B] uint8 and action_in [B, action_dim] fp32 (what
     the next push stores: F110VecEnv.replay_action).  A transition is named by index = step slot * B + env.  The ring is no part
@@ -251,17 +252,93 @@ class ReplayBuffer(Consumer):
         self._keep_nstep = idx   # (kept until the next call: the stream may not have read it yet)
         return ns_idx, ret, d, discount, span
 
-    def frames_at(self, indices, nstep=1, gamma=None):
+    @staticmethod
+    def _stack(stack):
+        """`stack` as the walk takes it; ValueError unless it is an int in 1 .. MAX_STACK."""
+        if isinstance(stack, bool) or not isinstance(stack, int) or not 1 <= stack <= MAX_STACK:
+            raise ValueError('replay: stack %r (an int in 1..%d)' % (stack, MAX_STACK))
+        return stack
+
+    def _walk_back(self, rows, n, stack, stack_rows, depth):
+        eng = self.eng
+        with torch.cuda.device(eng.device):
+            _lib.check(eng.lib.f110_replay_stack(eng._h, _lib.ptr(rows), n, stack, stack_rows.data_ptr(), depth.data_ptr(), eng._stream()))
+
+    def stack_rows(self, rows, stack):
+        """f110_replay_stack: the last `stack` frames of the env behind each of the frame rows `rows` [n] (rows of frames_at's frame
+        tensor: an s_idx or ns_idx), walked backwards through the ring on the device (include/f110_hip.h "Frame stacks").  Returns
+        (stack_rows [n, stack] int64, depth [n] int32): column 0 is `rows`, column j the row of the frame j pushes earlier while the
+        pushes between them belong to one episode and are still stored, else the oldest row reached, repeated; depth counts the
+        distinct frames, 1 .. stack.  -1 in every column and depth 0 for a row outside the tensor (-1) or one no push has written.
+        A stack at learning time can be shorter than the one the policy acted on, for the stack - 1 oldest pushes of the ring only
+        (their predecessors are overwritten); depth shows it.  Device tensors, no synchronisation; stack in 1 .. MAX_STACK."""
+        if not self.on:
+            raise ValueError('replay: the buffer is off (record_replay())')
+        stack = self._stack(stack)
+        eng = self.eng
+        r = torch.as_tensor(rows).to(device=eng.device, dtype=torch.int64).contiguous().reshape(-1)
+        n = r.shape[0]
+        out = torch.empty((n, stack), dtype=torch.int64, device=eng.device)
+        depth = torch.empty((n,), dtype=torch.int32, device=eng.device)
+        if n:
+            self._walk_back(r, n, stack, out, depth)
+        self._keep_stack = r   # (kept until the next call: the stream may not have read it yet)
+        return out, depth
+
+    def stack_latest(self, stack, out=None):
+        """f110_replay_stack's latest mode: stack_rows of every env's newest frame (the bitmap its last step returned), [B, stack]
+        int64 and depth [B] int32 -- the stack a policy acts on.  Nothing crosses from the host that changes from call to call, so
+        a captured call follows the ring.  An empty ring gives -1 and depth 0.  out: (stack_rows, depth) tensors to write into."""
+        if not self.on:
+            raise ValueError('replay: the buffer is off (record_replay())')
+        stack = self._stack(stack)
+        eng, B = self.eng, self.eng.B
+        if out is None:
+            out = (torch.empty((B, stack), dtype=torch.int64, device=eng.device), torch.empty((B,), dtype=torch.int32, device=eng.device))
+        rows, depth = out
+        for t, shape, dt in ((rows, (B, stack), torch.int64), (depth, (B,), torch.int32)):
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != torch.device(eng.device) or not t.is_contiguous():
+                raise ValueError('replay: out must be contiguous (%s [%d, %d], int32 [%d]) tensors on %s' % (torch.int64, B, stack, B, eng.device))
+        self._walk_back(None, B, stack, rows, depth)
+        return rows, depth
+
+    def frame_view(self):
+        """The ring's frame tensor viewed as [(T + 1) * B, rows, words] int64: what the rows of frames_at, stack_rows and
+        stack_latest point into (a view, no copy: it changes with the next push)."""
+        return self.buf['frames'].view((self.cfg.steps + 1) * self.eng.B, self.rows, words(self.cols))
+
+    def _stacked(self, res, stack, o=None):
+        """`res` (a tuple whose positions 1 and 2 are s_idx and ns_idx [n]) with those two replaced by their [n, stack] stacks.  The
+        two are walked in one launch where they are the halves of one tensor (o['pair'], sample_out(stack=k)); -> (tuple, depth
+        [2, n] int32: of s_idx, of ns_idx)."""
+        n = int(res[1].shape[0])
+        if o is not None:
+            pair, both, depth = o['pair'], o['stacks'], o['depth']
+        else:
+            pair = torch.stack((res[1], res[2]))
+            both = torch.empty((2, n, stack), dtype=torch.int64, device=pair.device)
+            depth = torch.empty((2, n), dtype=torch.int32, device=pair.device)
+            self._keep_pair = pair
+        if n:
+            self._walk_back(pair, 2 * n, stack, both, depth)
+        return (res[0], both[0], both[1]) + tuple(res[3:]), depth
+
+    def frames_at(self, indices, nstep=1, gamma=None, stack=1):
         """The transitions `indices` [n] without unpacking an image, for consumers that read bits (red_gym_amd.bitconv).
         Returns (frames, s_idx, ns_idx, a, r, d, ok): frames is the ring's frame tensor viewed as [(T + 1) * B, rows, words]
         int64 (a view, no copy: it changes with the next push), s_idx and ns_idx [n] int64 its rows that hold the frame before
         and the frame after (f110_replay_locate; -1 for both where sample_at gives zeros), and a, r, d, ok exactly what
         sample_at(indices) returns.  Device tensors, no synchronisation.
         nstep > 1 (gamma is then required): the same tuple with r = the n-step return and ns_idx and d those of the span's end, as
-        nstep_at(indices, nstep, gamma) gives them, and its discount and span appended."""
+        nstep_at(indices, nstep, gamma) gives them, and its discount and span appended.
+        stack > 1: positions 1 and 2 are the [n, stack] stacks of s_idx and ns_idx (stack_rows; column 0 is what stack = 1 returns,
+        with nstep > 1 ns_idx is the span's end), and depth [2, n] int32 -- of s_idx, of ns_idx -- is appended."""
         if not self.on:
             raise ValueError('replay: the buffer is off (record_replay())')
         nstep, gamma = self._nstep(nstep, gamma)
+        if self._stack(stack) > 1:
+            res, depth = self._stacked(self.frames_at(indices, nstep, gamma), stack)
+            return res + (depth,)
         if nstep > 1:
             frames, s_idx, _, a, _, _, ok = self.frames_at(indices)
             ns_idx, ret, d, discount, span = self.nstep_at(self._keep, nstep, gamma)
@@ -290,7 +367,7 @@ class ReplayBuffer(Consumer):
         idx, _ = self.draw(batch_size, seed)
         return self.frames_at(idx)
 
-    def sample_frames_dev(self, batch_size, counter, seed=None, out=None, nstep=1, gamma=None):
+    def sample_frames_dev(self, batch_size, counter, seed=None, out=None, nstep=1, gamma=None, stack=1):
         """f110_replay_sample: batch_size transitions drawn from a draw counter that lives on the device, in one kernel.  counter: a
         [1] int64 tensor on the env's device (the bits of the library's uint64; start it at 0) that the caller owns; the call draws
         draw numbers counter .. counter + batch_size - 1 of the stream `seed` (default: the env's) exactly as draw() would with
@@ -302,19 +379,23 @@ class ReplayBuffer(Consumer):
         nstep > 1 (gamma is then required): f110_replay_sample_nstep, the same draws with the n-step walk in the same kernel.  The
         tuple is the same with r = the n-step return and ns_idx and d those of the span's end, and 'discount' [n] fp64 and 'span' [n]
         int32 appended (out then holds those two as well: sample_out(n, nstep)); everything behind the indices is what
-        nstep_at(indices, nstep, gamma) and frames_at(indices) give."""
+        nstep_at(indices, nstep, gamma) and frames_at(indices) give.
+        stack > 1: the sample kernels are untouched and one launch of the walk (stack_rows) runs behind them: positions 1 and 2 of
+        the tuple are then the [n, stack] stacks of s_idx and ns_idx ('s_stack', 'ns_stack' of out) and 'depth' [2, n] int32 (of
+        s_idx, of ns_idx) is appended; out: sample_out(n, nstep, stack=k), whose 's_idx' and 'ns_idx' are the halves of one tensor."""
         if not self.on:
             raise ValueError('replay: the buffer is off (record_replay())')
         nstep, gamma = self._nstep(nstep, gamma)
+        stack = self._stack(stack)
         eng, n = self.eng, int(batch_size)
         if not torch.is_tensor(counter) or counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != torch.device(eng.device):
             raise ValueError('replay: counter must be a [1] int64 tensor on %s' % (eng.device,))
-        o = self.sample_out(n, nstep) if out is None else out
-        shapes = self._sample_shapes(n, nstep)
-        for k, (shape, dt) in shapes.items():
-            t = o.get(k)
-            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != torch.device(eng.device) or not t.is_contiguous():
-                raise ValueError('replay: out[%r] must be a contiguous %s tensor of shape %s on %s' % (k, dt, shape, eng.device))
+        o = self.sample_out(n, nstep, stack=stack) if out is None else out
+        self._check_out(o, n, nstep, False, stack)
+        if stack > 1:
+            res, depth = self._stacked(self.sample_frames_dev(n, counter, seed, {k: v for k, v in o.items() if k not in self.STACK_KEYS}, nstep, gamma),
+                                       stack, o)
+            return res + (depth,)
         T, B = self.cfg.steps, eng.B
         frames = self.buf['frames'].view((T + 1) * B, self.rows, words(self.cols))
         if nstep > 1:
@@ -330,24 +411,41 @@ class ReplayBuffer(Consumer):
                                                   eng._stream()))
         return frames, o['s_idx'], o['ns_idx'], o['a'], o['r'], o['d'], o['ok'], o['indices']
 
-    def sample_priority_dev(self, batch_size, counter, seed=None, out=None, nstep=1, gamma=None):
+    STACK_KEYS = ('pair', 'stacks', 's_stack', 'ns_stack', 'depth')
+
+    def _check_out(self, o, n, nstep, priorities, stack):
+        dev = torch.device(self.eng.device)
+        for k, (shape, dt) in self._sample_shapes(n, nstep, priorities, stack).items():
+            t = o.get(k)
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError('replay: out[%r] must be a contiguous %s tensor of shape %s on %s' % (k, dt, shape, dev))
+        if stack > 1 and (o['s_idx'].data_ptr() != o['pair'].data_ptr() or o['ns_idx'].data_ptr() != o['pair'][1].data_ptr()
+                          or o['s_stack'].data_ptr() != o['stacks'].data_ptr() or o['ns_stack'].data_ptr() != o['stacks'][1].data_ptr()):
+            raise ValueError("replay: out['s_idx'] / out['ns_idx'] and out['s_stack'] / out['ns_stack'] must be the halves of out['pair'] and "
+                             "out['stacks'] (sample_out(..., stack=k))")
+
+    def sample_priority_dev(self, batch_size, counter, seed=None, out=None, nstep=1, gamma=None, stack=1):
         """f110_priority_sample: sample_frames_dev with draws in proportion to the transitions' priority words (record_replay(...,
         priorities=...)), from the caller's device counter, in two launches.  Returns the n-step form's tuple whatever nstep is --
         (frames, s_idx, ns_idx, a, r, d, ok, indices, discount, span) -- with prio [n] int32 (the bits of the drawn uint32 words) and
         weight [n] fp32 appended: the importance weights (N P(i))^-beta over the batch's maximum, exactly 1.0 on the rows of the
         smallest word and 0 where ok is 0, for the beta the tree held before this call moved it on.  out: sample_out(n, nstep,
-        priorities=True).  Device tensors, no synchronisation; a captured call replays with fresh draws."""
+        priorities=True).  Device tensors, no synchronisation; a captured call replays with fresh draws.
+        stack > 1: as sample_frames_dev -- positions 1 and 2 are the stacks, depth [2, n] is appended (out: sample_out(n, nstep,
+        priorities=True, stack=k))."""
         if not self.on or self.priorities is None:
             raise ValueError('replay: priorities are off (record_replay(..., priorities=True))')
         nstep, gamma = self._nstep(nstep, gamma)
+        stack = self._stack(stack)
         eng, n = self.eng, int(batch_size)
         if not torch.is_tensor(counter) or counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != torch.device(eng.device):
             raise ValueError('replay: counter must be a [1] int64 tensor on %s' % (eng.device,))
-        o = self.sample_out(n, nstep, priorities=True) if out is None else out
-        for k, (shape, dt) in self._sample_shapes(n, nstep, True).items():
-            t = o.get(k)
-            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != torch.device(eng.device) or not t.is_contiguous():
-                raise ValueError('replay: out[%r] must be a contiguous %s tensor of shape %s on %s' % (k, dt, shape, eng.device))
+        o = self.sample_out(n, nstep, priorities=True, stack=stack) if out is None else out
+        self._check_out(o, n, nstep, True, stack)
+        if stack > 1:
+            res, depth = self._stacked(self.sample_priority_dev(n, counter, seed, {k: v for k, v in o.items() if k not in self.STACK_KEYS}, nstep, gamma),
+                                       stack, o)
+            return res + (depth,)
         T, B = self.cfg.steps, eng.B
         frames = self.buf['frames'].view((T + 1) * B, self.rows, words(self.cols))
         with torch.cuda.device(eng.device):
@@ -357,20 +455,29 @@ class ReplayBuffer(Consumer):
                                                     o['prio'].data_ptr(), o['weight'].data_ptr(), eng._stream()))
         return frames, o['s_idx'], o['ns_idx'], o['a'], o['r'], o['d'], o['ok'], o['indices'], o['discount'], o['span'], o['prio'], o['weight']
 
-    def _sample_shapes(self, n, nstep=1, priorities=False):
+    def _sample_shapes(self, n, nstep=1, priorities=False, stack=1):
         shapes = {'indices': ((n,), torch.int64), 's_idx': ((n,), torch.int64), 'ns_idx': ((n,), torch.int64),
                   'a': ((n, self.cfg.action_dim), torch.float32), 'r': ((n,), torch.float64), 'd': ((n,), torch.uint8), 'ok': ((n,), torch.uint8)}
         if nstep > 1 or priorities:
             shapes.update({'discount': ((n,), torch.float64), 'span': ((n,), torch.int32)})
         if priorities:
             shapes.update({'prio': ((n,), torch.int32), 'weight': ((n,), torch.float32)})
+        if stack > 1:
+            shapes.update({'pair': ((2, n), torch.int64), 'stacks': ((2, n, stack), torch.int64), 's_stack': ((n, stack), torch.int64),
+                           'ns_stack': ((n, stack), torch.int64), 'depth': ((2, n), torch.int32)})
         return shapes
 
-    def sample_out(self, batch_size, nstep=1, priorities=False):
+    def sample_out(self, batch_size, nstep=1, priorities=False, stack=1):
         """The tensors sample_frames_dev writes, newly allocated: what its `out` takes ('discount' and 'span' with nstep > 1 only).
-        priorities=True: what sample_priority_dev writes ('discount' and 'span' whatever nstep is, 'prio' and 'weight')."""
-        return {k: torch.empty(shape, dtype=dt, device=self.eng.device)
-                for k, (shape, dt) in self._sample_shapes(int(batch_size), int(nstep), bool(priorities)).items()}
+        priorities=True: what sample_priority_dev writes ('discount' and 'span' whatever nstep is, 'prio' and 'weight').
+        stack > 1: 's_stack' and 'ns_stack' [n, stack] int64 and 'depth' [2, n] int32 as well; 's_idx' / 'ns_idx' are then the halves of
+        'pair' [2, n] and the two stacks the halves of 'stacks' [2, n, stack], so that one launch of the walk serves both."""
+        stack = self._stack(stack)
+        shapes = self._sample_shapes(int(batch_size), int(nstep), bool(priorities), stack)
+        o = {k: torch.empty(shape, dtype=dt, device=self.eng.device) for k, (shape, dt) in shapes.items() if stack == 1 or k not in ('s_idx', 'ns_idx', 's_stack', 'ns_stack')}
+        if stack > 1:
+            o['s_idx'], o['ns_idx'], o['s_stack'], o['ns_stack'] = o['pair'][0], o['pair'][1], o['stacks'][0], o['stacks'][1]
+        return o
 
     def bytes_held(self):
         return sum(self.buf[k].numel() * self.buf[k].element_size() for k in ('frames', 'actions', 'rewards', 'dones', 'valid'))

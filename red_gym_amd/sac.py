@@ -17,7 +17,7 @@ from .gauss import GaussianSource
 from .optim import SacAdam
 from .policyhead import PolicyHead, sample_actions
 from .qhead import QHead, td_target, twin_q
-from .replay import MAX_NSTEP
+from .replay import MAX_NSTEP, MAX_STACK
 from .sacloss import actor_loss, critic_loss
 from .temperature import Temperature
 
@@ -47,13 +47,14 @@ class Actor(torch.nn.Module):
         self.trunk, self.fc1, self.head = trunk, fc1, head
 
     @classmethod
-    def new(cls, width, hidden, action_dim, on, cols, device):
-        return cls(Trunk(on=on, cols=cols, device=device), Dense(width, hidden, relu=True, device=device), PolicyHead(hidden, action_dim, device=device))
+    def new(cls, width, hidden, action_dim, on, cols, device, stack=1):
+        return cls(Trunk(on=on, cols=cols, device=device, stack=stack), Dense(width, hidden, relu=True, device=device),
+                   PolicyHead(hidden, action_dim, device=device))
 
     @classmethod
-    def sharing(cls, m, on, cols):
+    def sharing(cls, m, on, cols, stack=1):
         """On the tensors of a torch.nn network with the reference's attributes conv1 .. conv3, fc1, fc_mean, fc_log_std."""
-        return cls(Trunk.from_convs(m.conv1, m.conv2, m.conv3, on=on, cols=cols), Dense.from_linear(m.fc1, relu=True),
+        return cls(Trunk.from_convs(m.conv1, m.conv2, m.conv3, on=on, cols=cols, stack=stack), Dense.from_linear(m.fc1, relu=True),
                    PolicyHead.from_linears(m.fc_mean, m.fc_log_std))
 
     def features(self, frames, index=None):
@@ -72,12 +73,12 @@ class Critic(torch.nn.Module):
         self.trunk, self.head = trunk, head
 
     @classmethod
-    def new(cls, width, hidden, action_dim, on, cols, device):
-        return cls(Trunk(on=on, cols=cols, device=device), QHead(width, action_dim, hidden, device=device, dense=True))
+    def new(cls, width, hidden, action_dim, on, cols, device, stack=1):
+        return cls(Trunk(on=on, cols=cols, device=device, stack=stack), QHead(width, action_dim, hidden, device=device, dense=True))
 
     @classmethod
-    def sharing(cls, m, on, cols):
-        return cls(Trunk.from_convs(m.conv1, m.conv2, m.conv3, on=on, cols=cols), QHead.from_linears(m.fc1, m.fc2, dense=True))
+    def sharing(cls, m, on, cols, stack=1):
+        return cls(Trunk.from_convs(m.conv1, m.conv2, m.conv3, on=on, cols=cols, stack=stack), QHead.from_linears(m.fc1, m.fc2, dense=True))
 
 
 def _heads(nets):
@@ -113,12 +114,17 @@ class SACAgent:
     weights (sacloss.critic_loss(weight=...)) and the priorities of the drawn transitions are written back right behind it from max(|q1
     - tv|, |q2 - tv|) (PriorityTree.update), all captured with the rest; the actor's loss stays unweighted.  ValueError from those three
     on a ring without priorities.  False, the default, changes nothing: the same launches, graph key and bits, on any ring.
+    stack: 1 is the reference's one frame.  k > 1 (up to replay.MAX_STACK): every network's conv1 has k input channels, the last k
+    frames of the env (ReplayBuffer.stack_rows: repeated at an episode's start, never across a reset); update, capture_update and
+    update_graph draw with stack=k, update_batch takes 's_idx' / 'ns_idx' as [n, k], and act_from acts on the ring's newest stacks.
+    Shared networks must have a conv1 of k input channels (ValueError otherwise).  stack is configuration, not state.  With stack = 1
+    nothing changes: the same launches, graph key and bits.
     Attributes: actor, critics [2], targets [2]; actor_opt, critic_opts [2] (SacAdam; a critic's also moves its target); draws, the [1]
     int64 draw counter on the device; sample, the tensors of the batch the last update drew (sample['indices'] names the transitions)."""
 
     def __init__(self, action_dim=16, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, rows=256, cols=256, hidden=512,
                  on=255.0, device='cuda', networks=None, target_entropy=None, alpha_lr=3e-4, init_alpha=0.2, draws='torch', seed=0, nstep=1,
-                 per=False):
+                 per=False, stack=1):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ValueError('SACAgent: device %s: there is no CPU path' % (self.device,))
@@ -129,6 +135,9 @@ class SACAgent:
             raise ValueError('SACAgent: nstep %r: an int in 1..%d' % (nstep, MAX_NSTEP))
         self.nstep = nstep
         self.per = bool(per)
+        if isinstance(stack, bool) or not isinstance(stack, int) or not 1 <= stack <= MAX_STACK:
+            raise ValueError('SACAgent: stack %r: an int in 1..%d' % (stack, MAX_STACK))
+        self.stack = stack
         self.temperature = None
         if isinstance(alpha, str):
             if alpha != 'auto':
@@ -144,7 +153,7 @@ class SACAgent:
         self.rows, self.cols, self.hidden, self.on = int(rows), int(cols), int(hidden), float(on)
         self.width = feature_width(self.rows, self.cols)
         if networks is None:
-            make = lambda cls: cls.new(self.width, self.hidden, self.action_dim, self.on, self.cols, self.device)  # noqa: E731
+            make = lambda cls: cls.new(self.width, self.hidden, self.action_dim, self.on, self.cols, self.device, self.stack)  # noqa: E731
             self.actor = make(Actor)
             self.critics = [make(Critic), make(Critic)]
             self.targets = [make(Critic), make(Critic)]
@@ -152,9 +161,9 @@ class SACAgent:
                 t.load_state_dict(c.state_dict())
         else:
             get = networks.__getitem__ if isinstance(networks, dict) else lambda name: getattr(networks, name)  # noqa: E731
-            self.actor = Actor.sharing(get('actor'), self.on, self.cols)
-            self.critics = [Critic.sharing(get(n), self.on, self.cols) for n in ('critic1', 'critic2')]
-            self.targets = [Critic.sharing(get(n), self.on, self.cols) for n in ('critic1_target', 'critic2_target')]
+            self.actor = Actor.sharing(get('actor'), self.on, self.cols, self.stack)
+            self.critics = [Critic.sharing(get(n), self.on, self.cols, self.stack) for n in ('critic1', 'critic2')]
+            self.targets = [Critic.sharing(get(n), self.on, self.cols, self.stack) for n in ('critic1_target', 'critic2_target')]
         fc1 = self.actor.fc1.weight
         if tuple(fc1.shape) != (self.hidden, self.width) or self.actor.head.fc_mean.out_features != self.action_dim:
             raise ValueError('SACAgent: the actor\'s fc1 is %s and its action has %d values; rows, cols, hidden and action_dim say %s and %d'
@@ -198,6 +207,23 @@ class SACAgent:
             if eps is None and self.source is not None:
                 eps = self.source.normal(h.shape[0], self.action_dim, stream=0, rows=index)
             return self.actor.head.sample(h, eps=eps, dtype=torch.float64, out=out)[0]
+
+    def act_from(self, replay, evaluate=False, out=None, eps=None):
+        """select_action on what the ring `replay` (F110VecEnv.replay) holds as every env's newest frames: ReplayBuffer.stack_latest(stack)
+        over the ring's own frame tensor, nothing is copied or unpacked.  Row i is env i (so are the rows of the device's draws).  With
+        stack = 1 this is select_action(info['lidar_bitmap']) of the step that made the last push, bit for bit.  An env whose ring is
+        empty acts on frames of zeros.  evaluate, out, eps: as select_action."""
+        self._check_replay(replay)
+        rows, _ = replay.stack_latest(self.stack)
+        with torch.no_grad():
+            h = self.actor.features(replay.frame_view(), rows[:, 0] if self.stack == 1 else rows)
+            head = self.actor.head
+            if evaluate:
+                return sample_actions(h, head.fc_mean.weight, head.fc_mean.bias, head.fc_log_std.weight, head.fc_log_std.bias, eps=None,
+                                      dtype=torch.float64, out=out)[0]
+            if eps is None and self.source is not None:
+                eps = self.source.normal(h.shape[0], self.action_dim, stream=0, rows=None)
+            return head.sample(h, eps=eps, dtype=torch.float64, out=out)[0]
 
     # ---- learning
     def _eps(self, eps, n):
@@ -250,7 +276,7 @@ class SACAgent:
     def update_batch(self, batch, eps=None, replay=None):
         """One update on a batch that is given, not drawn: a dict with 'frames' [m, rows, words] int64, 's_idx' and 'ns_idx' [n] int64
         rows of it (-1: a zero frame), 'a' [n, action_dim] fp32, 'r' [n] fp64 and 'd' [n] uint8, as ReplayBuffer.sample_frames returns
-        them.  An optional 'discount' [n] fp64 is the target's discount per row in gamma's place ('r' is then the n-step return and
+        them; with stack = k > 1 's_idx' and 'ns_idx' are [n, k] (ReplayBuffer.frames_at(..., stack=k)).  An optional 'discount' [n] fp64 is the target's discount per row in gamma's place ('r' is then the n-step return and
         'ns_idx', 'd' those of the span's end, as ReplayBuffer.frames_at with nstep > 1 returns them); without it gamma, whatever the agent's nstep.
         An optional 'weight' [n] fp32 weighs the critics' loss row by row (ReplayBuffer.sample_priority_dev's importance weights); with
         'indices' [n] int64 and 'ok' [n] uint8 beside it and `replay` (a ring with priorities) the rows' new priorities are written back
@@ -289,16 +315,19 @@ class SACAgent:
         eps_next, eps_new = self._eps(eps, n)
         if check and len(replay) < n:
             return torch.zeros((3,), dtype=torch.float32, device=self.device)
-        self.sample = replay.sample_out(n, self.nstep, priorities=self.per)
+        self.sample = replay.sample_out(n, self.nstep, priorities=self.per, **self._stack_kw())
         frames, s_idx, ns_idx, a, r, d, discount, weight, writeback = self._draw(replay, n, self.sample)
         return self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, torch.empty((3,), dtype=torch.float32, device=self.device), discount,
                             weight, writeback)
+
+    def _stack_kw(self):
+        return {} if self.stack == 1 else dict(stack=self.stack)
 
     def _draw(self, replay, n, out):
         """The batch of an update drawn into `out` with the agent's draw counter -> (frames, s_idx, ns_idx, a, r, d, discount or None,
         weight or None, writeback or None): the last two with per=True only."""
         if self.per:
-            got = replay.sample_priority_dev(n, self.draws, out=out, nstep=self.nstep, gamma=self.gamma)
+            got = replay.sample_priority_dev(n, self.draws, out=out, nstep=self.nstep, gamma=self.gamma, **self._stack_kw())
             # (with nstep = 1 the target takes gamma by value, as without priorities: got[8] holds its bits in every row)
             return got[:6] + (None if self.nstep == 1 else got[8], got[11], (replay.priorities, got[7], got[6]))
         got = self._draw_uniform(replay, n, out)
@@ -306,8 +335,8 @@ class SACAgent:
 
     def _draw_uniform(self, replay, n, out):
         if self.nstep == 1:
-            return replay.sample_frames_dev(n, self.draws, out=out)[:6] + (None,)
-        got = replay.sample_frames_dev(n, self.draws, out=out, nstep=self.nstep, gamma=self.gamma)
+            return replay.sample_frames_dev(n, self.draws, out=out, **self._stack_kw())[:6] + (None,)
+        got = replay.sample_frames_dev(n, self.draws, out=out, nstep=self.nstep, gamma=self.gamma, **self._stack_kw())
         return got[:6] + (got[8],)
 
     # ---- the captured update
@@ -318,6 +347,7 @@ class SACAgent:
         t = self.temperature
         key = key if t is None else key + ((t.lr, t.betas, t.eps, t.target_entropy),)
         key = key if self.nstep == 1 else key + (('nstep', self.nstep, self.gamma),)
+        key = key if self.stack == 1 else key + (('stack', self.stack),)
         if self.per:                                # (a ring that lost its priorities: another key, and the capture refuses it)
             p = replay.priorities
             key = key + (('per', self.gamma) + ((None,) if p is None else (p.leaf.data_ptr(), p.state.data_ptr())),)
@@ -338,7 +368,7 @@ class SACAgent:
         if key != self._g_key:
             self._graphs = {}
             self._g_key, self._g_replay = key, replay
-            self._g_sample = replay.sample_out(n, self.nstep, priorities=self.per)
+            self._g_sample = replay.sample_out(n, self.nstep, priorities=self.per, **self._stack_kw())
             self._g_eps = [torch.zeros((n, self.action_dim), dtype=torch.float32, device=dev) for _ in range(2)]
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(dev)
