@@ -931,7 +931,17 @@ int f110_bitconv_backward_stack(const f110_bitconv_config *cfg, const uint64_t *
  * f110_bitconv2_validate: host only.  F110_E_INVALID for what f110_bitconv_validate refuses in the first layer's fields, for
  * channels outside 1..16, kernel2 outside 1..4, stride2 outside 1..kernel2, channels2 outside 1..64, for OH1 or OW1 below
  * kernel2, and for a first layer's output wider than 64 (OW1 > 64: the kernel works on whole rows of it and has no halo in x;
- * any number of rows is accepted). */
+ * any number of rows is accepted).
+ * f110_bitconv2_forward_stack: the stem on a stack of frames, for acting with f110_replay_stack's rows: the composition of the two
+ * contracts above.  Layer 1 is the contract of f110_bitconv_forward_stack unchanged (packed frames only, there is no _u8 entry;
+ * index [n, stack] dev int64 is required, an entry outside 0 .. n_frames - 1 reads a frame of zeros, repeats are allowed; w1
+ * [channels, stack, kernel, kernel]; acc = 0; for the frames j major, then ky, then kx minor: acc = fmaf(w1[c][j][ky][kx], bit ? 1.0f
+ * : 0.0f, acc); a1 = (acc * on) + b1[c] (+ 0.0f for NULL), then the relu -- `on`, the bias and the relu once, after the last frame);
+ * layer 2 is the contract of f110_bitconv2_forward on that a1.  So its output is, bit for bit, f110_bitconv2_forward's layer 2 on
+ * f110_bitconv_forward_stack's output, and with stack = 1 f110_bitconv2_forward's own.  One kernel, one launch for any n; the first
+ * layer's activations and the running sums over the frames live in LDS; the launch geometry does not depend on `stack`.
+ * F110_E_INVALID for stack outside 1 .. F110_BITCONV_MAX_STACK, a NULL index, n < 1, a null frames, w1, w2 or out, and whatever
+ * f110_bitconv2_validate refuses: every configuration it accepts is accepted at every stack. */
 typedef struct {
     int32_t rows, cols;         /* the image */
     int32_t kernel, stride;     /* layer 1, as f110_bitconv_config */
@@ -947,6 +957,8 @@ int f110_bitconv2_forward(const f110_bitconv2_config *cfg, const uint64_t *frame
                           const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream);
 int f110_bitconv2_forward_u8(const f110_bitconv2_config *cfg, const uint8_t *images, int64_t n_frames, const int64_t *index, int64_t n,
                              const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream);
+int f110_bitconv2_forward_stack(const f110_bitconv2_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int32_t stack,
+                                int64_t n, const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream);
 
 /* Dense convolution of fp32 feature maps, forward and backward: conv2 = nn.Conv2d(16, 32, 4, 2) and conv3 = nn.Conv2d(32, 32, 3, 1)
  * of the reference's Actor and Critic (src/SAL.py:398-399, 406-407, 430-431, 437-438) with their ReLU, on the fp32 matrix cores.

@@ -366,6 +366,7 @@ SYMBOLS = {
     'f110_bitconv2_validate': [C.POINTER(Bitconv2Config)],
     'f110_bitconv2_forward': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_bitconv2_forward_u8': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
+    'f110_bitconv2_forward_stack': [C.POINTER(Bitconv2Config), _VP, _I64, _VP, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _VP],
     'f110_featconv_validate': [C.POINTER(FeatconvConfig)],
     'f110_featconv_workspace': [C.POINTER(FeatconvConfig), _I64],
     'f110_featconv_forward': [C.POINTER(FeatconvConfig), _VP, _I64, _VP, _VP, _VP, _VP],

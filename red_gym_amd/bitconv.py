@@ -240,34 +240,56 @@ def conv_bits2(frames, w1, b1, w2, b2, stride1=1, stride2=1, on=1.0, relu1=True,
     through conv_bits and torch's conv2d: BitConvStem chooses).  Always the fused kernel, on the caller's current stream,
     without synchronising.  Numerics: the first layer exactly as conv_bits, the second acc = fma(w2[co][ci][ky][kx], a1, acc)
     for ci major, ky, kx minor from 0, + b2 -- a function of the bits and the four tensors alone (include/f110_hip.h).
-    ValueError for what f110_bitconv2_validate refuses and for a dtype / shape mismatch."""
+    ValueError for what f110_bitconv2_validate refuses and for a dtype / shape mismatch.
+    A stack of frames: w1 [C1, k, k1, k1] with 1 < k <= MAX_STACK selects f110_bitconv2_forward_stack, the same kernel with conv_bits'
+    stacked first layer (frames j major, then ky, kx; `on`, b1 and relu1 once, after the last frame): packed int64 frames and an int64
+    index [n, k] are then required, as for conv_bits.  The result is bit for bit conv_feat's of conv_bits' stacked output; an index
+    [n, 1] with a w1 of one input channel goes to the one-frame entry."""
     who = 'conv_bits2'
     if not torch.is_tensor(frames) or not torch.is_tensor(w1) or not torch.is_tensor(w2):
         raise ValueError('%s: frames, w1 and w2 must be tensors' % who)
     if not frames.is_cuda or w1.device != frames.device or w2.device != frames.device:
         raise ValueError('%s: frames, w1 and w2 must be on the same GPU' % who)
-    if w1.dtype != torch.float32 or w1.dim() != 4 or w1.shape[1] != 1 or w1.shape[2] != w1.shape[3]:
-        raise ValueError('%s: w1 must be fp32 [C1, 1, k1, k1], not %s %s' % (who, w1.dtype, tuple(w1.shape)))
-    c1, k1 = int(w1.shape[0]), int(w1.shape[2])
+    if w1.dtype != torch.float32 or w1.dim() != 4 or w1.shape[1] < 1 or w1.shape[2] != w1.shape[3]:
+        raise ValueError('%s: w1 must be fp32 [C1, 1, k1, k1] or [C1, k, k1, k1], not %s %s' % (who, w1.dtype, tuple(w1.shape)))
+    c1, k, k1 = int(w1.shape[0]), int(w1.shape[1]), int(w1.shape[2])
     if w2.dtype != torch.float32 or w2.dim() != 4 or w2.shape[1] != c1 or w2.shape[2] != w2.shape[3]:
         raise ValueError('%s: w2 must be fp32 [C2, %d, k2, k2], not %s %s' % (who, c1, w2.dtype, tuple(w2.shape)))
     c2, k2 = int(w2.shape[0]), int(w2.shape[2])
     for name, b, ch in (('b1', b1, c1), ('b2', b2, c2)):
         if b is not None and (not torch.is_tensor(b) or b.dtype != torch.float32 or tuple(b.shape) != (ch,) or b.device != frames.device):
             raise ValueError('%s: %s must be fp32 [%d] on the frames\' device' % (who, name, ch))
+    if k > 1:                                         # a stack of frames: the checks of _conv_bits_stack
+        if k > MAX_STACK:
+            raise ValueError('%s: %d input channels (a stack has 1..%d frames)' % (who, k, MAX_STACK))
+        if frames.dtype != torch.int64:
+            raise ValueError('%s: a stack of frames is read from packed int64 frames (the replay ring\'s), not %s' % (who, frames.dtype))
     u8, rows, cols = _frames_kind(who, frames, cols)
+    if k > 1 and (not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 2 or index.shape[1] != k or index.device != frames.device):
+        raise ValueError('%s: a w1 of %d input channels needs an int64 index [n, %d] on the frames\' device' % (who, k, k))
     cfg = validate2(rows, cols, k1, stride1, c1, k2, stride2, c2, on, relu1, relu2)
-    index, n = _index_arg(who, index, frames)
+    if k > 1:
+        index, n = index.contiguous(), int(index.shape[0])
+    else:
+        if torch.is_tensor(index) and index.dim() == 2 and index.shape[1] == 1:
+            index = index[:, 0]                       # a stack of one frame: the one-frame entry, the same bits
+        index, n = _index_arg(who, index, frames)
     lib = _lib.load()
     dev = frames.device
     frames = frames.contiguous()
     tensors = [None if t is None else t.detach().contiguous() for t in (w1, b1, w2, b2)]
     oh2, ow2 = output_size2(rows, cols, k1, stride1, k2, stride2)
     out = torch.empty((n, c2, oh2, ow2), dtype=torch.float32, device=dev)
-    fn = lib.f110_bitconv2_forward_u8 if u8 else lib.f110_bitconv2_forward
     with torch.cuda.device(dev):
-        _lib.check(fn(C.byref(cfg), frames.data_ptr(), frames.shape[0], _lib.ptr(index), n, *[_lib.ptr(t) for t in tensors], out.data_ptr(),
-                      _lib.stream(dev)))
+        if k > 1 and n == 0:
+            pass                                      # (the stacked entry takes n >= 1)
+        elif k > 1:
+            _lib.check(lib.f110_bitconv2_forward_stack(C.byref(cfg), frames.data_ptr(), frames.shape[0], index.data_ptr(), k, n,
+                                                       *[_lib.ptr(t) for t in tensors], out.data_ptr(), _lib.stream(dev)))
+        else:
+            fn = lib.f110_bitconv2_forward_u8 if u8 else lib.f110_bitconv2_forward
+            _lib.check(fn(C.byref(cfg), frames.data_ptr(), frames.shape[0], _lib.ptr(index), n, *[_lib.ptr(t) for t in tensors], out.data_ptr(),
+                          _lib.stream(dev)))
     return out
 
 
@@ -343,11 +365,13 @@ class BitConvStem(torch.nn.Module):
     four parameters requires grad, conv_bits(relu=True) -> F.conv2d -> relu, differentiable as before; otherwise (acting, the
     no_grad block of an update) conv_bits2, the fused kernel, whose result has no grad_fn.  The two paths agree to fp32
     rounding, not bit for bit: torch picks conv2's summation order on the first, the second adds in the order of the contract
-    (include/f110_hip.h)."""
+    (include/f110_hip.h).
+    in_channels = k > 1: conv1 is nn.Conv2d(k, ...) on stacks of k packed frames, forward(frames, index [n, k]); the same two paths,
+    conv_bits on the stack with gradients and the stacked fused kernel without."""
 
-    def __init__(self, channels1=16, kernel1=8, stride1=4, channels2=32, kernel2=4, stride2=2, on=1.0, cols=None, device=None):
+    def __init__(self, channels1=16, kernel1=8, stride1=4, channels2=32, kernel2=4, stride2=2, on=1.0, cols=None, device=None, in_channels=1):
         super().__init__()
-        self.conv1 = BitConv2d(channels1, kernel1, stride1, on=on, relu=True, cols=cols, device=device)
+        self.conv1 = BitConv2d(channels1, kernel1, stride1, on=on, relu=True, cols=cols, device=device, in_channels=in_channels)
         self.conv2 = torch.nn.Conv2d(int(channels1), int(channels2), int(kernel2), int(stride2), device=device)
         self._check()
 
@@ -358,11 +382,12 @@ class BitConvStem(torch.nn.Module):
         validate2(big, big, k1, self.conv1.stride, self.conv1.weight.shape[0], k2, s2, self.conv2.out_channels, self.conv1.on)
 
     @classmethod
-    def from_convs(cls, conv1, conv2, on=1.0, cols=None):
+    def from_convs(cls, conv1, conv2, on=1.0, cols=None, in_channels=1):
         """A stem that shares the parameters of an nn.Conv2d pair (the same tensors: training one trains the other).  ValueError
         where BitConv2d.from_conv raises for conv1, and for a conv2 with padding, dilation, groups, a non-square kernel or stride,
-        or in_channels != conv1.out_channels, or sizes the fused kernel refuses."""
-        first = BitConv2d.from_conv(conv1, on=on, relu=True, cols=cols)
+        or in_channels != conv1.out_channels, or sizes the fused kernel refuses.  in_channels = k: conv1 must be an nn.Conv2d(k, ...);
+        the stem then reads stacks of k frames."""
+        first = BitConv2d.from_conv(conv1, on=on, relu=True, cols=cols, in_channels=in_channels)
         _plain_conv2('BitConvStem.from_convs', conv2, conv1.out_channels)
         m = cls.__new__(cls)
         torch.nn.Module.__init__(m)

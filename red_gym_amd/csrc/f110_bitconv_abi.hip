@@ -166,3 +166,21 @@ extern "C" int f110_bitconv2_forward_u8(const f110_bitconv2_config *cfg, const u
 {
     return bitconv2_forward("f110_bitconv2_forward_u8", cfg, images, true, n_frames, index, n, w1, b1, w2, b2, out, (hipStream_t)stream);
 }
+
+extern "C" int f110_bitconv2_forward_stack(const f110_bitconv2_config *cfg, const uint64_t *frames, int64_t n_frames, const int64_t *index, int32_t stack,
+                                           int64_t n, const float *w1, const float *b1, const float *w2, const float *b2, float *out, void *stream)
+{
+    const char *who = "f110_bitconv2_forward_stack";
+    if (int rc = f110_bitconv2_validate(cfg)) return rc;
+    if (int rc = bitconv_stack_check(stack, who)) return rc;
+    if (n < 1 || n_frames < 0) return fail(F110_E_INVALID, "%s: n=%lld samples of %lld frames", who, (long long)n, (long long)n_frames);
+    if (!index) return fail(F110_E_INVALID, "%s: null index (a stack names its frames)", who);
+    if (!w1 || !w2 || !out || !frames) return fail(F110_E_INVALID, "%s: null pointer", who);
+    if ((uintptr_t)frames % 8) return fail(F110_E_INVALID, "%s: frames must be 8-byte aligned", who);
+    Bitconv2StackPlan p = bitconv2_forward_stack_plan(*cfg, stack, n);
+    Bitconv2StackArgs &s = p.s;
+    s.a.l1.frames = frames; s.a.l1.n_frames = n_frames; s.index = (const long long *)index;
+    F110_LAUNCH(bitconv2_forward_stack_kernel, p.l, (hipStream_t)stream, s, w1, b1, w2, b2, out);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}

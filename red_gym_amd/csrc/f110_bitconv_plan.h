@@ -237,4 +237,25 @@ inline Bitconv2Plan bitconv2_forward_plan(const f110_bitconv2_config &c, bool u8
     return p;
 }
 
+// ---------------------------------------------------------------- the stem on a stack of frames
+struct Bitconv2StackArgs {
+    Bitconv2Args a;                 // as the one-frame launch, with a.l1.index = NULL and a.u8 = 0: the frames are named by `index` below
+    const long long *index;         // [n, stack]: frame of channel j of sample i
+    int stack;                      // 1 .. F110_BITCONV_MAX_STACK
+};
+
+// f110_bitconv2_forward_stack on n >= 1 samples: one launch of bitconv2_forward_stack_kernel.  The frames of a stack pass through the
+// one-frame kernel's `words` one after the other and the running sums live in a1 itself, so the LDS, and with it the bands, are the
+// one-frame plan's at every stack: nothing that plan accepts is refused here.
+struct Bitconv2StackPlan { Bitconv2StackArgs s; Launch l; };
+
+inline Bitconv2StackPlan bitconv2_forward_stack_plan(const f110_bitconv2_config &c, int stack, int64_t n)
+{
+    const Bitconv2Plan one = bitconv2_forward_plan(c, false, n);
+    Bitconv2StackPlan p;
+    p.s.a = one.a; p.s.index = nullptr; p.s.stack = stack;
+    p.l = one.l;
+    return p;
+}
+
 } // namespace f110

@@ -152,8 +152,9 @@ class Trunk(torch.nn.Module):
     conv_feat(relu).  Both add conv2 in the same order, so the two paths return the same bits: the features a policy acts on are
     the features it learns from.
     stack = k > 1: conv1 is nn.Conv2d(k, 16, 8, 4) on stacks of k packed frames and forward takes index [n, k]
-    (ReplayBuffer.stack_rows).  Both paths are then conv_bits -> conv_feat -> conv_feat (there is no stacked fused stem), still the
-    same bits; acting writes conv1's activations to memory."""
+    (ReplayBuffer.stack_rows).  The two paths are the same: conv_bits on the stack with gradients, conv_bits2 on the stack (the stacked
+    fused stem, f110_bitconv2_forward_stack) without, so acting writes no conv1 activations to memory at any stack.  Both add the
+    frames j major, then ky, kx, and conv2 in the same order, so they still return the same bits."""
 
     def __init__(self, on=1.0, cols=None, device=None, stack=1):
         super().__init__()
@@ -192,7 +193,7 @@ class Trunk(torch.nn.Module):
         c1, c2, c3 = self.conv1, self.conv2, self.conv3
         cols = None if frames.dtype == torch.uint8 else c1.cols
         params = (c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias)
-        if self.stack > 1 or (torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in params)):
+        if torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in params):
             a1 = conv_bits(frames, c1.weight, c1.bias, stride=c1.stride, on=c1.on, relu=True, index=index, cols=cols)
             a2 = conv_feat(a1, c2.weight, c2.bias, stride=c2.stride, relu=True)
         else:
