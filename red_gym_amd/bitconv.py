@@ -71,19 +71,27 @@ def output_size2(rows, cols, kernel, stride, kernel2, stride2):
 
 
 class _ConvBits(torch.autograd.Function):
+    """conv_bits on checked arguments.  A weight [C, 1, K, K] goes to the one-frame entries (f110_bitconv_forward[_u8] /
+    f110_bitconv_backward; index [n] or None), one of k > 1 input channels to f110_bitconv_forward_stack / f110_bitconv_backward_stack
+    (packed frames, index [n, k])."""
+
     @staticmethod
     def forward(ctx, frames, weight, bias, index, cfg, n, u8):
         lib = _lib.load()
         dev = frames.device
+        k = int(weight.shape[1])
         oh, ow = output_size(cfg.rows, cfg.cols, cfg.kernel, cfg.stride)
         out = torch.empty((n, cfg.channels, oh, ow), dtype=torch.float32, device=dev)
         w = weight.detach().contiguous()
         b = None if bias is None else bias.detach().contiguous()
-        fn = lib.f110_bitconv_forward_u8 if u8 else lib.f110_bitconv_forward
+        tail = (n, w.data_ptr(), _lib.ptr(b), out.data_ptr(), _lib.stream(dev))
         with torch.cuda.device(dev):
-            _lib.check(fn(C.byref(cfg), frames.data_ptr(), frames.shape[0], _lib.ptr(index), n, w.data_ptr(), _lib.ptr(b), out.data_ptr(),
-                          _lib.stream(dev)))
-        ctx.cfg, ctx.n, ctx.u8, ctx.has_bias = cfg, n, u8, bias is not None
+            if k == 1:
+                fn = lib.f110_bitconv_forward_u8 if u8 else lib.f110_bitconv_forward
+                _lib.check(fn(C.byref(cfg), frames.data_ptr(), frames.shape[0], _lib.ptr(index), *tail))
+            else:
+                _lib.check(lib.f110_bitconv_forward_stack(C.byref(cfg), frames.data_ptr(), frames.shape[0], index.data_ptr(), k, *tail))
+        ctx.cfg, ctx.n, ctx.u8, ctx.k, ctx.has_bias = cfg, n, u8, k, bias is not None
         ctx.save_for_backward(frames, index, out if cfg.relu else None)
         return out
 
@@ -92,79 +100,27 @@ class _ConvBits(torch.autograd.Function):
         from .replay import pack_bitmaps
         lib = _lib.load()
         frames, index, out = ctx.saved_tensors
-        cfg, n = ctx.cfg, ctx.n
+        cfg, n, k = ctx.cfg, ctx.n, ctx.k
         dev = grad_out.device
         if out is not None:
             grad_out = grad_out * (out > 0)           # relu: the kernel takes grad_out already masked
         g = grad_out.to(torch.float32).contiguous()
         if ctx.u8:
             frames = pack_bitmaps(frames)             # the backward kernel reads bits (1/8 of the bytes, once per update)
-        kk = cfg.kernel * cfg.kernel
-        gw = torch.empty((cfg.channels, 1, cfg.kernel, cfg.kernel), dtype=torch.float32, device=dev)
-        gb = torch.empty((cfg.channels,), dtype=torch.float32, device=dev) if ctx.has_bias and ctx.needs_input_grad[2] else None
-        nbytes = lib.f110_bitconv_workspace(C.byref(cfg), n)
-        assert nbytes >= 4 * cfg.channels * (kk + 1)
-        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.f110_bitconv_backward(C.byref(cfg), frames.data_ptr(), frames.shape[0], _lib.ptr(index), n, g.data_ptr(), gw.data_ptr(),
-                                                 _lib.ptr(gb), ws.data_ptr(), _lib.stream(dev)))
-        return None, (gw if ctx.needs_input_grad[1] else None), gb, None, None, None, None
-
-
-class _ConvBitsStack(torch.autograd.Function):
-    """conv_bits on a stack: f110_bitconv_forward_stack / f110_bitconv_backward_stack (packed frames, index [n, k])."""
-
-    @staticmethod
-    def forward(ctx, frames, weight, bias, index, cfg):
-        lib = _lib.load()
-        dev = frames.device
-        n, k = int(index.shape[0]), int(index.shape[1])
-        oh, ow = output_size(cfg.rows, cfg.cols, cfg.kernel, cfg.stride)
-        out = torch.empty((n, cfg.channels, oh, ow), dtype=torch.float32, device=dev)
-        w = weight.detach().contiguous()
-        b = None if bias is None else bias.detach().contiguous()
-        with torch.cuda.device(dev):
-            _lib.check(lib.f110_bitconv_forward_stack(C.byref(cfg), frames.data_ptr(), frames.shape[0], index.data_ptr(), k, n, w.data_ptr(),
-                                                      _lib.ptr(b), out.data_ptr(), _lib.stream(dev)))
-        ctx.cfg, ctx.has_bias = cfg, bias is not None
-        ctx.save_for_backward(frames, index, out if cfg.relu else None)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        lib = _lib.load()
-        frames, index, out = ctx.saved_tensors
-        cfg, dev = ctx.cfg, grad_out.device
-        n, k = int(index.shape[0]), int(index.shape[1])
-        if out is not None:
-            grad_out = grad_out * (out > 0)           # relu: the kernel takes grad_out already masked
-        g = grad_out.to(torch.float32).contiguous()
         gw = torch.empty((cfg.channels, k, cfg.kernel, cfg.kernel), dtype=torch.float32, device=dev)
         gb = torch.empty((cfg.channels,), dtype=torch.float32, device=dev) if ctx.has_bias and ctx.needs_input_grad[2] else None
-        if n == 0:
-            return None, (gw.zero_() if ctx.needs_input_grad[1] else None), (None if gb is None else gb.zero_()), None, None
-        nbytes = lib.f110_bitconv_workspace_stack(C.byref(cfg), k, n)
-        assert nbytes >= 4 * cfg.channels * (cfg.kernel * cfg.kernel + 1) + 8 * k * n and nbytes % 4 == 0
+        if n == 0 and k > 1:                          # (the stacked entry takes n >= 1)
+            return None, (gw.zero_() if ctx.needs_input_grad[1] else None), (None if gb is None else gb.zero_()), None, None, None, None
+        nbytes = lib.f110_bitconv_workspace(C.byref(cfg), n) if k == 1 else lib.f110_bitconv_workspace_stack(C.byref(cfg), k, n)
+        assert nbytes >= 4 * cfg.channels * (cfg.kernel * cfg.kernel + 1) + (8 * k * n if k > 1 else 0) and nbytes % 4 == 0
         ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        tail = (n, g.data_ptr(), gw.data_ptr(), _lib.ptr(gb), ws.data_ptr(), _lib.stream(dev))
         with torch.cuda.device(dev):
-            _lib.check(lib.f110_bitconv_backward_stack(C.byref(cfg), frames.data_ptr(), frames.shape[0], index.data_ptr(), k, n, g.data_ptr(),
-                                                       gw.data_ptr(), _lib.ptr(gb), ws.data_ptr(), _lib.stream(dev)))
-        return None, (gw if ctx.needs_input_grad[1] else None), gb, None, None
-
-
-def _conv_bits_stack(frames, weight, bias, stride, on, relu, index, cols):
-    """conv_bits for a weight [C, k, K, K] with k > 1: the checks, then _ConvBitsStack."""
-    who = 'conv_bits'
-    ch, k, ks = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
-    if k > MAX_STACK:
-        raise ValueError('%s: %d input channels (a stack has 1..%d frames)' % (who, k, MAX_STACK))
-    if frames.dtype != torch.int64:
-        raise ValueError('%s: a stack of frames is read from packed int64 frames (the replay ring\'s), not %s' % (who, frames.dtype))
-    _, rows, cols = _frames_kind(who, frames, cols)
-    if not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 2 or index.shape[1] != k or index.device != frames.device:
-        raise ValueError('%s: a weight of %d input channels needs an int64 index [n, %d] on the frames\' device' % (who, k, k))
-    cfg = validate(rows, cols, ks, stride, ch, on, relu)
-    return _ConvBitsStack.apply(frames.contiguous(), weight, bias, index.contiguous(), cfg)
+            if k == 1:
+                _lib.check(lib.f110_bitconv_backward(C.byref(cfg), frames.data_ptr(), frames.shape[0], _lib.ptr(index), *tail))
+            else:
+                _lib.check(lib.f110_bitconv_backward_stack(C.byref(cfg), frames.data_ptr(), frames.shape[0], index.data_ptr(), k, *tail))
+        return None, (gw if ctx.needs_input_grad[1] else None), gb, None, None, None, None
 
 
 def conv_bits(frames, weight, bias=None, stride=1, on=1.0, relu=False, index=None, cols=None):
@@ -180,26 +136,43 @@ def conv_bits(frames, weight, bias=None, stride=1, on=1.0, relu=False, index=Non
     A stack of frames: weight [C, k, K, K] with 1 < k <= MAX_STACK is nn.Conv2d(k, C, K, stride) whose input channel j of sample i is
     frame index[i, j]; index int64 [n, k] is then required (ReplayBuffer.stack_rows gives it) and frames are the packed form.  The
     frames are added j major, then ky, kx; grad_weight[:, j] is bit for bit what the one-frame call gives for index[:, j]."""
+    who = 'conv_bits'
     if not torch.is_tensor(frames) or not torch.is_tensor(weight):
         raise ValueError('conv_bits: frames and weight must be tensors')
     if not frames.is_cuda or weight.device != frames.device:
         raise ValueError('conv_bits: frames and weight must be on the same GPU')
-    if weight.dtype == torch.float32 and weight.dim() == 4 and weight.shape[1] > 1 and weight.shape[2] == weight.shape[3]:
-        if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (int(weight.shape[0]),)
-                                 or bias.device != frames.device):
-            raise ValueError('conv_bits: bias must be fp32 [%d] on the frames\' device' % int(weight.shape[0]))
-        return _conv_bits_stack(frames, weight, bias, stride, on, relu, index, cols)
-    if weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[1] != 1 or weight.shape[2] != weight.shape[3]:
+    if weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[1] < 1 or weight.shape[2] != weight.shape[3]:
         raise ValueError('conv_bits: weight must be fp32 [C, 1, k, k], not %s %s' % (weight.dtype, tuple(weight.shape)))
-    ch, k = int(weight.shape[0]), int(weight.shape[2])
+    ch, k, ks = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
     if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (ch,) or bias.device != frames.device):
         raise ValueError('conv_bits: bias must be fp32 [%d] on the frames\' device' % ch)
-    u8, rows, cols = _frames_kind('conv_bits', frames, cols)
-    cfg = validate(rows, cols, k, stride, ch, on, relu)
-    if torch.is_tensor(index) and index.dim() == 2 and index.shape[1] == 1:
-        index = index[:, 0]                           # a stack of one frame: the one-frame entry, the same bits
-    index, n = _index_arg('conv_bits', index, frames)
+    u8, rows, cols = _stack_frames(who, 'weight', k, frames, index, cols)
+    cfg = validate(rows, cols, ks, stride, ch, on, relu)
+    index, n = _stack_index(who, k, index, frames)
     return _ConvBits.apply(frames.contiguous(), weight, bias, index, cfg, n, u8)
+
+
+def _stack_frames(who, what, k, frames, index, cols):
+    """(u8, rows, cols) of `frames` for `who` as _frames_kind gives them, after the checks of a first layer of k input channels
+    (`what`: its weight's name): beyond one, a stack of at most MAX_STACK packed frames named by an index [n, k]."""
+    if k > MAX_STACK:
+        raise ValueError('%s: %d input channels (a stack has 1..%d frames)' % (who, k, MAX_STACK))
+    if k > 1 and frames.dtype != torch.int64:
+        raise ValueError('%s: a stack of frames is read from packed int64 frames (the replay ring\'s), not %s' % (who, frames.dtype))
+    kind = _frames_kind(who, frames, cols)
+    if k > 1 and (not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 2 or index.shape[1] != k or index.device != frames.device):
+        raise ValueError('%s: a %s of %d input channels needs an int64 index [n, %d] on the frames\' device' % (who, what, k, k))
+    return kind
+
+
+def _stack_index(who, k, index, frames):
+    """(index, n) for `who` once _stack_frames has passed: the [n, k] index of a stack made contiguous, or what _index_arg gives
+    for one frame per sample -- an index [n, 1] is then a stack of one frame: the one-frame entry, the same bits."""
+    if k > 1:
+        return index.contiguous(), int(index.shape[0])
+    if torch.is_tensor(index) and index.dim() == 2 and index.shape[1] == 1:
+        index = index[:, 0]
+    return _index_arg(who, index, frames)
 
 
 def _frames_kind(who, frames, cols):
@@ -259,21 +232,9 @@ def conv_bits2(frames, w1, b1, w2, b2, stride1=1, stride2=1, on=1.0, relu1=True,
     for name, b, ch in (('b1', b1, c1), ('b2', b2, c2)):
         if b is not None and (not torch.is_tensor(b) or b.dtype != torch.float32 or tuple(b.shape) != (ch,) or b.device != frames.device):
             raise ValueError('%s: %s must be fp32 [%d] on the frames\' device' % (who, name, ch))
-    if k > 1:                                         # a stack of frames: the checks of _conv_bits_stack
-        if k > MAX_STACK:
-            raise ValueError('%s: %d input channels (a stack has 1..%d frames)' % (who, k, MAX_STACK))
-        if frames.dtype != torch.int64:
-            raise ValueError('%s: a stack of frames is read from packed int64 frames (the replay ring\'s), not %s' % (who, frames.dtype))
-    u8, rows, cols = _frames_kind(who, frames, cols)
-    if k > 1 and (not torch.is_tensor(index) or index.dtype != torch.int64 or index.dim() != 2 or index.shape[1] != k or index.device != frames.device):
-        raise ValueError('%s: a w1 of %d input channels needs an int64 index [n, %d] on the frames\' device' % (who, k, k))
+    u8, rows, cols = _stack_frames(who, 'w1', k, frames, index, cols)
     cfg = validate2(rows, cols, k1, stride1, c1, k2, stride2, c2, on, relu1, relu2)
-    if k > 1:
-        index, n = index.contiguous(), int(index.shape[0])
-    else:
-        if torch.is_tensor(index) and index.dim() == 2 and index.shape[1] == 1:
-            index = index[:, 0]                       # a stack of one frame: the one-frame entry, the same bits
-        index, n = _index_arg(who, index, frames)
+    index, n = _stack_index(who, k, index, frames)
     lib = _lib.load()
     dev = frames.device
     frames = frames.contiguous()
@@ -310,6 +271,12 @@ def _plain_conv(who, conv, name, in_channels, wrong_in):
     return ks[0], st[0]
 
 
+def _stack_channels(who, in_channels):
+    """ValueError from `who` unless in_channels is an int in 1..MAX_STACK."""
+    if isinstance(in_channels, bool) or not isinstance(in_channels, int) or not 1 <= in_channels <= MAX_STACK:
+        raise ValueError('%s: in_channels %r (an int in 1..%d: the frames of a stack)' % (who, in_channels, MAX_STACK))
+
+
 class BitConv2d(torch.nn.Module):
     """nn.Conv2d(1, out_channels, kernel_size, stride) on two-valued images, computed by conv_bits.  Its parameters have the
     names and shapes of nn.Conv2d's (weight [C, 1, k, k], bias [C]), so state dicts pass between the two in both directions.
@@ -319,8 +286,7 @@ class BitConv2d(torch.nn.Module):
     def __init__(self, out_channels, kernel_size, stride=1, bias=True, on=1.0, relu=False, cols=None, device=None, in_channels=1):
         super().__init__()
         k = int(kernel_size)
-        if isinstance(in_channels, bool) or not isinstance(in_channels, int) or not 1 <= in_channels <= MAX_STACK:
-            raise ValueError('BitConv2d: in_channels %r (an int in 1..%d: the frames of a stack)' % (in_channels, MAX_STACK))
+        _stack_channels('BitConv2d', in_channels)
         ref = torch.nn.Conv2d(in_channels, int(out_channels), k, int(stride), bias=bias, device=device)   # (for its initialisation)
         self.weight = ref.weight
         self.register_parameter('bias', ref.bias)
@@ -332,8 +298,7 @@ class BitConv2d(torch.nn.Module):
         """A BitConv2d that shares the parameters of `conv` (the same tensors: training one trains the other).  ValueError
         unless it is an nn.Conv2d(in_channels, C, k, stride) with a square kernel and stride, no padding, dilation or groups;
         in_channels: 1, a bitmap's one channel, or the frames of a stack, 2..MAX_STACK, which the caller names."""
-        if isinstance(in_channels, bool) or not isinstance(in_channels, int) or not 1 <= in_channels <= MAX_STACK:
-            raise ValueError('BitConv2d.from_conv: in_channels %r (an int in 1..%d: the frames of a stack)' % (in_channels, MAX_STACK))
+        _stack_channels('BitConv2d.from_conv', in_channels)
         wrong = 'in_channels = %d (a bitmap has one channel)' if in_channels == 1 else 'in_channels = %%d (the stack has %d frames)' % in_channels
         k, s = _plain_conv('BitConv2d.from_conv', conv, '', in_channels, wrong)
         validate(k, k, k, s, conv.out_channels, on)

@@ -8,10 +8,10 @@
 //                            per row, once) and expands it to 0.0 / 1.0; per channel one fma per tap with the weight wave-uniform
 //   bitconv_backward_kernel  stage 1 of grad_weight / grad_bias: a workgroup walks tiles g, g + G, ... (G fixed by the shape), a
 //                            lane owns one tap, a wave one row of the tile, and sums grad_out * bit in a fixed order
-//   bitconv_reduce_kernel    stage 2: the G partials of every element summed in a fixed order, times `on`
+//   bitconv_reduce_kernel<false>  stage 2: the G partials of every element summed in a fixed order, times `on`
 //   bitconv_forward_stack_kernel  the layer with `stack` input channels, each a frame named by index [n, stack]: the masks of all
 //                            frames of a tile go to LDS, then chunks of BCS_CHUNK channels accumulate over the frames in registers
-//   bitconv_index_columns_kernel, bitconv_reduce_stack_kernel  the stacked backward is the one-frame backward per index column: the
+//   bitconv_index_columns_kernel, bitconv_reduce_kernel<true>  the stacked backward is the one-frame backward per index column: the
 //                            index transposed once, and stage 2 written with the [C, stack, K, K] stride
 // Forward numerics (the contract of include/f110_hip.h): acc = 0; taps ky major, kx minor: acc = fma(w, bit, acc) with bit 0.0 or
 // 1.0 -- w * bit is exact, so this is acc + w for a set tap and acc for a clear one, rounded once per tap; out = (acc * on) + bias.
@@ -207,9 +207,12 @@ static __global__ __launch_bounds__(BC_THREADS) void bitconv_backward_kernel(Bit
         wsb[c0 + tid] = ((bred[tid] + bred[BC_CHUNK + tid]) + bred[2 * BC_CHUNK + tid]) + bred[3 * BC_CHUNK + tid];
 }
 
-// one lane per element of grad_weight (nw = C * kernel^2 of them) and of grad_bias (C): the G partials as four interleaved sums
+// one lane per element of grad_weight (nw = C * kernel^2 of them) and of grad_bias (C): the G partials as four interleaved sums.
+// <false>: grad_weight [C, kk] (kk, stack and j are not read).  <true>: the same sums into column j of grad_weight [C, stack, kk];
+// the bias (the same for every column: it does not depend on the frames) where the caller passes it.
+template <bool STACK>
 static __global__ __launch_bounds__(BC_THREADS) void bitconv_reduce_kernel(const float *ws, int G, int nw, int C, float on,
-                                                                          float *grad_weight, float *grad_bias)
+                                                                          float *grad_weight, float *grad_bias, int kk, int stack, int j)
 {
     const int o = blockIdx.x * BC_THREADS + threadIdx.x;
     if (o >= nw + C) return;
@@ -223,8 +226,14 @@ static __global__ __launch_bounds__(BC_THREADS) void bitconv_reduce_kernel(const
             if (g + q < G) s[q] = s[q] + p[(size_t)(g + q) * step];
     }
     const float v = (s[0] + s[1]) + (s[2] + s[3]);
-    if (is_w) grad_weight[o] = v * on;
-    else if (grad_bias) grad_bias[o - nw] = v;
+    if (is_w) {
+        size_t at = (size_t)o;
+        if constexpr (STACK) {
+            const int ch = o / kk, k = o - ch * kk;
+            at = ((size_t)ch * (size_t)stack + (size_t)j) * (size_t)kk + (size_t)k;
+        }
+        grad_weight[at] = v * on;
+    } else if (grad_bias) grad_bias[o - nw] = v;
 }
 
 // ---------------------------------------------------------------- the same layer on a stack of frames
@@ -294,29 +303,6 @@ static __global__ __launch_bounds__(BC_THREADS) void bitconv_index_columns_kerne
     if (o >= n * stack) return;
     const long long j = o / n, i = o - j * n;
     columns[o] = index[i * stack + j];
-}
-
-// bitconv_reduce_kernel's sums in its order, written into column j of grad_weight [C, stack, kk]; the bias (the same for every
-// column: it does not depend on the frames) where the caller passes it
-static __global__ __launch_bounds__(BC_THREADS) void bitconv_reduce_stack_kernel(const float *ws, int G, int nw, int C, float on, int kk, int stack, int j,
-                                                                                float *grad_weight, float *grad_bias)
-{
-    const int o = blockIdx.x * BC_THREADS + threadIdx.x;
-    if (o >= nw + C) return;
-    const bool is_w = o < nw;
-    const float *p = is_w ? ws + o : ws + (size_t)G * (size_t)nw + (size_t)(o - nw);
-    const size_t step = is_w ? (size_t)nw : (size_t)C;
-    float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int g = 0; g < G; g += 4) {
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            if (g + q < G) s[q] = s[q] + p[(size_t)(g + q) * step];
-    }
-    const float v = (s[0] + s[1]) + (s[2] + s[3]);
-    if (is_w) {
-        const int ch = o / kk, k = o - ch * kk;
-        grad_weight[((size_t)ch * (size_t)stack + (size_t)j) * (size_t)kk + (size_t)k] = v * on;
-    } else if (grad_bias) grad_bias[o - nw] = v;
 }
 
 } // namespace f110

@@ -24,6 +24,11 @@ constexpr int BC_CHUNK = 16;                  // channels one workgroup of the b
 constexpr int BC_MAX_PARTIALS = 1024;         // G at most
 constexpr long long BC_FORWARD_GROUP = 1ll << 23; // workgroups of one forward launch at most: a launch has fewer than 2^32 threads
 
+// STEP(K) for a kernel size K in 1..BC_MAX_K that is known when the code runs: the kernels are instantiated per size
+#define BITCONV_BY_KERNEL(K, STEP) \
+    switch (K) { case 1: STEP(1); break; case 2: STEP(2); break; case 3: STEP(3); break; case 4: STEP(4); break; \
+                 case 5: STEP(5); break; case 6: STEP(6); break; case 7: STEP(7); break; default: STEP(8); break; }
+
 struct BitconvArgs {
     f110_bitconv_config cfg;
     const uint64_t *frames;         // [n_frames, rows, W], or
@@ -89,8 +94,8 @@ inline BitconvForwardPlan bitconv_forward_plan(const f110_bitconv_config &c, boo
     return p;
 }
 
-// f110_bitconv_backward: bitconv_backward_kernel<K> (inst = K) on (G, chunks of channels), then bitconv_reduce_kernel over the nw
-// weights and C biases
+// f110_bitconv_backward: bitconv_backward_kernel<K> (inst = K) on (G, chunks of channels), then bitconv_reduce_kernel<false> over the
+// nw weights and C biases
 struct BitconvBackwardPlan { BitconvArgs a; Launch partials, reduce; int nw; };
 
 inline BitconvBackwardPlan bitconv_backward_plan(const f110_bitconv_config &c, int64_t n)
@@ -137,7 +142,7 @@ inline BitconvStackForwardPlan bitconv_forward_stack_plan(const f110_bitconv_con
 
 // f110_bitconv_backward_stack: the workspace is f110_bitconv_backward's partial sums (rounded up to 16 bytes), then the index
 // transposed to [stack, n] int64; bitconv_index_columns_kernel fills the latter (one lane per entry), then per column j the one-frame
-// plan's partials launch on column j and bitconv_reduce_stack_kernel (the one-frame reduce's grid) into grad_weight[:, j]
+// plan's partials launch on column j and bitconv_reduce_kernel<true> (the one-frame reduce's grid) into grad_weight[:, j]
 inline int64_t bitconv_stack_partial_bytes(const f110_bitconv_config &c, int64_t n) { return (bitconv_workspace_bytes(c, n) + 15) / 16 * 16; }
 inline int64_t bitconv_stack_workspace_bytes(const f110_bitconv_config &c, int stack, int64_t n)
 {
@@ -222,7 +227,7 @@ inline size_t bitconv2_geometry(const f110_bitconv2_config &c, Bitconv2Args &a)
     return bitconv2_lds(c, a.BR, a.XW, a.ksteps, &a.koff_off, &a.a1_off);
 }
 
-// f110_bitconv2_forward[_u8] on n >= 1 samples: one launch of bitconv2_forward_kernel (a workgroup walks items grid apart, so one
+// f110_bitconv2_forward[_u8] on n >= 1 samples: one launch of bitconv2_forward_kernel<false> (a workgroup walks items grid apart, so one
 // launch serves any n; its LDS stays below the 64 KiB every kernel may ask for)
 struct Bitconv2Plan { Bitconv2Args a; Launch l; };
 
@@ -244,7 +249,7 @@ struct Bitconv2StackArgs {
     int stack;                      // 1 .. F110_BITCONV_MAX_STACK
 };
 
-// f110_bitconv2_forward_stack on n >= 1 samples: one launch of bitconv2_forward_stack_kernel.  The frames of a stack pass through the
+// f110_bitconv2_forward_stack on n >= 1 samples: one launch of bitconv2_forward_kernel<true>.  The frames of a stack pass through the
 // one-frame kernel's `words` one after the other and the running sums live in a1 itself, so the LDS, and with it the bands, are the
 // one-frame plan's at every stack: nothing that plan accepts is refused here.
 struct Bitconv2StackPlan { Bitconv2StackArgs s; Launch l; };

@@ -1,4 +1,4 @@
-"""The checker of the stacked fused stem (csrc/f110_bitconv2.h bitconv2_forward_stack_kernel; f110_bitconv2_forward_stack's contract in
+"""The checker of the stacked fused stem (csrc/f110_bitconv2.h bitconv2_forward_kernel<true>; f110_bitconv2_forward_stack's contract in
 include/f110_hip.h), NumPy only.  The contract is the composition of two existing ones, and so is the checker: the stacked first layer
 of stack_cases.forward_stack (frames j major, then ky, kx; `on`, bias and relu once, after the last frame), then the fma chain of
 bitconv2_cases.accumulate2 / finish2.  Nothing is restated here."""

@@ -1,4 +1,4 @@
-"""Times the stacked fused stem (csrc/f110_bitconv2.h bitconv2_forward_stack_kernel; conv_bits2 with a w1 [16, k, 8, 8]) at SAL's shape
+"""Times the stacked fused stem (csrc/f110_bitconv2.h bitconv2_forward_kernel<true>; conv_bits2 with a w1 [16, k, 8, 8]) at SAL's shape
 (256 x 256, conv1 8 / 4 / 16, conv2 4 / 2 / 32) beside the path it replaces for acting, conv_bits(relu) -> conv_feat(relu), in one
 process, alternating, with events on the stream, the median of 20 after warm-up (tools/time_update.py's harness), two rounds:
     python tools/time_stem_stack.py [--batches 64,4096,65536] [--stacks 1,2,4] [--envs 65536] [--skip stem,act]
