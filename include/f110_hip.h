@@ -321,7 +321,7 @@ int f110_launch_epoch(f110_handle *h, int64_t *epoch);
 
 /* The form of the step's scan (performance only; results do not depend on it).  Besides the classic form -- two cars per
  * workgroup sharing one 1 024-slot LDS copy of the map's distance LUT -- every install of map slot 0 builds two COMPACT forms (two more cell
- * tables and the byte table of f110_scan_codes_info: 2.5 x the cell table's bytes, 13 MB at 1 600 x 1 600), S = 256 and 512: an LDS image of the LUT's first S - 2 ranks and a cell table in which every cell of a higher rank carries the far
+ * tables, 2 x the cell table's bytes, and the row-padded byte table of f110_scan_codes_info / f110_scan_pad_rows), S = 256 and 512: an LDS image of the LUT's first S - 2 ranks and a cell table in which every cell of a higher rank carries the far
  * marker (such cells take the second table, as cells beyond the classic image always did).  A compact form runs workgroups of
  * one wave, each with its own image.  It applies to the step's scan on a single map whose origin is unrotated and whose
  * resolution is a power of two; the rule that picks it (scan_compact_choice in csrc/f110_scan_plan.h) reads, per form, the
@@ -355,6 +355,13 @@ int f110_scan_rows_info(f110_handle *h, int32_t n_cars, int32_t *lds);
  * process, overrides the rule (tests, A/B runs); neither value changes the form or where the rows are staged.
  * f110_scan_codes_info: *bytes = 1 where a step of n_cars cars with an fp32 output reads byte codes now, else 0. */
 int f110_scan_codes_info(f110_handle *h, int32_t n_cars, int32_t *bytes);
+/* The byte table is ROW-PADDED: every strip carries P rows of 0 above its first and below its last border row, P the smallest
+ * multiple of 8 that is >= ceil(max_range / resolution) + 2, so that the march of a car standing on the map clamps no row
+ * (every look-up of a ray lies within max_range of its car).  Its bytes are those of a map of H + 2 P rows -- example_map:
+ * 4.2 MB at P = 488 -- and count toward the compact tables' 64 MB limit; a map whose padded table does not fit gets none and
+ * reads word codes.
+ * f110_scan_pad_rows: *rows = P of map slot 0's byte table, or -1 where the map has none. */
+int f110_scan_pad_rows(f110_handle *h, int32_t *rows);
 
 /* The step as a HIP graph the library builds itself, for callers without a capturing framework and as the reference
  * point for framework captures: F110_GRAPH_NODES = one kernel node per kernel of f110_step(actions_dev), chained

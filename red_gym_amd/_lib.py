@@ -303,6 +303,7 @@ SYMBOLS = {
     'f110_scan_form_learn': [_VP, _VP, _VP],
     'f110_scan_rows_info': [_VP, _I32, C.POINTER(C.c_int32)],
     'f110_scan_codes_info': [_VP, _I32, C.POINTER(C.c_int32)],
+    'f110_scan_pad_rows': [_VP, C.POINTER(C.c_int32)],
     'f110_graph_create': [_VP, _VP, _I32, C.POINTER(_VP)],
     'f110_graph_launch': [_VP, _VP],
     'f110_graph_info': [_VP, C.POINTER(C.c_int32), C.c_char_p],

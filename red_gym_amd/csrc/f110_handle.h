@@ -171,7 +171,8 @@ struct f110_handle {
         // free cells whose code lies behind its far marker (plan_scan's eligibility rule reads it)
         DevBuf<uint16_t> d_cells_c[N_COMPACT];
         DevBuf<double> d_lut_lds_c[N_COMPACT];
-        DevBuf<uint8_t> d_cells_b;    // byte table of d_cells_c[0] (f110_map.h: cell_elem_b), built with the compact forms
+        DevBuf<uint8_t> d_cells_b;    // row-padded byte table of d_cells_c[0] (f110_map.h: cell_elem_bp), built with the
+        int pad_rows = 0;             // compact forms where it fits (map_bytes_fit), and its P
         bool compact = false;
         double compact_out[N_COMPACT] = {1.0, 1.0};
         // the same shares over the free cells a car can REACH (8-connected to its spawn cell), averaged over the cars, learnt at

@@ -7,6 +7,7 @@
 #define __host__
 #define __device__
 #endif
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -72,6 +73,44 @@ __host__ __device__ inline size_t cell_elem_of_byte(size_t i, int Hp, int W)
     return ((size_t)((c >> 3) + 1) * Hp + row) * 8 + (size_t)(c & 7);
 }
 
+// The byte table as the device holds it: ROW-PADDED.  Every strip carries P rows of 0 above the border row -1 and at least P
+// below the border row H, P = map_pad_rows(max_range / resolution): the smallest multiple of 8 that is >= ceil(reach) + 2.
+// Every look-up of a ray lies within max_range of its car, so for a car standing on rows -1 .. H no row a march can form
+// leaves [-1 - P, H + P] -- its own strip -- and the fast march needs no clamp of the row (f110_scan.h: march_ident_pow2_fast).
+// The layout is the one above for a map of H + 2 P rows with row r stored at r + P: cell_elem_b(r + P, c, map_rows_b(H, P)).
+// P is a multiple of 8, so the padded rows stay a multiple of 8 and (r + 1 + P) = (r + 1) mod 8: a 128-B line holds the very
+// 8 x 16 cells it held without the padding.
+constexpr size_t COMPACT_MAX_BYTES = (size_t)64 << 20;  // the largest table a compact form (and the padded byte table) may be
+constexpr int MAP_PAD_ROWS_MAX = 1 << 20;
+// P for reach = max_range / resolution in cells, or -1 where there is none (a reach that is not finite, negative or absurd)
+__host__ __device__ inline int map_pad_rows(double reach)
+{
+    if (!(reach >= 0.0) || !(reach < (double)MAP_PAD_ROWS_MAX)) return -1;
+    return (((int)ceil(reach) + 2 + 7) >> 3) << 3;
+}
+__host__ __device__ inline int map_rows_b(int H, int P) { return map_rows_padded(H + 2 * P); }
+__host__ __device__ inline size_t map_cells_bp(int H, int W, int P) { return map_cells_b(H + 2 * P, W); }
+__host__ __device__ inline size_t cell_elem_bp(int r, int c, int H, int P) { return cell_elem_b(r + P, c, map_rows_b(H, P)); }
+// the bytes in front of strip 1, map row 0 -- where the march's descriptor starts (MapView::init_bytes)
+__host__ __device__ inline size_t map_bytes_skip(int H, int P) { return (size_t)map_rows_b(H, P) * 16 + 16 * (size_t)(1 + P); }
+// the size rule: the padded table counts toward the compact tables' limit, and its strip must stay a signed 24-bit operand
+// of the march's multiply-add.  Where it fails no byte table is built and the launch reads word codes.
+__host__ __device__ inline bool map_bytes_fit(int H, int W, int P)
+{
+    return P >= 0 && (long long)H + 2ll * P + 10 < (1ll << 19) && map_cells_bp(H, W, P) <= COMPACT_MAX_BYTES;
+}
+// cell_elem_of_byte for the padded table: byte row `row` stands for the u16 table's row `row - P` (its r + 1); the padding
+// rows have no u16 element
+__host__ __device__ inline size_t cell_elem_of_byte_padded(size_t i, int H, int W, int P)
+{
+    const int Hb = map_rows_b(H, P), Hp = map_rows_padded(H);
+    const size_t strip = i / ((size_t)Hb * 16), col = i % 16;
+    const long long row = (long long)(i / 16 % (size_t)Hb) - P;      // the u16 table's row index, r + 1
+    const long long c = ((long long)strip - 1) * 16 + (long long)col;
+    if (c < -1 || c > W || row < 0 || row >= Hp) return (size_t)-1;
+    return ((size_t)((c >> 3) + 1) * Hp + (size_t)row) * 8 + (size_t)(c & 7);
+}
+
 struct MapDev {
     const uint16_t *cells;  // padded strips [(W >> 3) + 2][Hp][8] of LDS byte offsets
     const uint16_t *cells_far; // same layout: rank (<= 65534) of the cells marked OFF_FAR, 65535 = fp64 table
@@ -85,8 +124,10 @@ struct MapDev {
     unsigned lut_len;       // entries of lut
     const uint16_t *cells_c[N_COMPACT];  // compact cell tables (layout and size of `cells`) for S = LUT_COMPACT[i], or NULL
     const double *lut_lds_c[N_COMPACT];  // [S] their LDS images
-    const uint8_t *cells_b;              // byte table of cells_c[0] (16-column strips, map_cells_b elements), or NULL
+    const uint8_t *cells_b;              // row-padded byte table of cells_c[0] (16-column strips, map_cells_bp elements), or NULL
     unsigned cells_b_bytes;
+    unsigned strip_bytes_b;              // its strip: map_rows_b(H, pad_rows) * 16 (the u16 tables keep strip_bytes)
+    unsigned pad_rows;                   // its P
 };
 
 } // namespace f110

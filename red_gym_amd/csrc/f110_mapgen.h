@@ -194,13 +194,14 @@ static __global__ __launch_bounds__(256) void map_compact_kernel(const uint16_t 
     if (threadIdx.x < 1 + N_COMPACT && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
 }
 
-// The byte table of the compact form of 256 slots (f110_map.h: cell_elem_b) from the classic table, element by element: the
-// slot of the cell the element stands for, 0 (the border's) for the padding the u16 table has no element for.
-static __global__ __launch_bounds__(256) void map_bytes_kernel(const uint16_t *cells, int Hp, int W, uint8_t *out, size_t n_b)
+// The row-padded byte table of the compact form of 256 slots (f110_map.h: cell_elem_bp) from the classic table, element by
+// element: the slot of the cell the element stands for, 0 (the border's) for the P padding rows above and below and for the
+// padding the u16 table has no element for.
+static __global__ __launch_bounds__(256) void map_bytes_kernel(const uint16_t *cells, int H, int W, int P, uint8_t *out, size_t n_b)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_b) return;
-    const size_t e = cell_elem_of_byte(i, Hp, W);
+    const size_t e = cell_elem_of_byte_padded(i, H, W, P);
     out[i] = e == (size_t)-1 ? (uint8_t)0 : (uint8_t)byte_code(cells[e]);
 }
 

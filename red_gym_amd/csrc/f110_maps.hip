@@ -4,13 +4,18 @@
 
 // The compact forms of a map (f110_map.h) beside its classic tables, derived from them on the device.  They are an extra: a
 // table beyond COMPACT_MAX_BYTES, or an allocation or copy that fails, leaves the slot with the classic form alone.  Cost: two
-// more cell tables and the byte table of the 256-slot one (half a table), 2.5 x cells_bytes (13 MB at 1 600 x 1 600), for
-// slot 0 only.
-constexpr size_t COMPACT_MAX_BYTES = (size_t)64 << 20;
-static void build_compact(f110_handle::MapSlot &ns, int H, int W)
+// more cell tables and the byte table of the 256-slot one (half a table plus its padding rows), for slot 0 only.
+// The byte table is ROW-PADDED (f110_map.h: map_pad_rows) for `reach` = the handle's max_range in cells, which is fixed for
+// the handle's life: P rows of 0 above and below every strip, so that the fast march needs no clamp of the row.  It is an
+// extra of the extra: where the padded table does not fit (map_bytes_fit) the compact forms are built without it and the
+// launch of the 256-slot form reads word codes.
+static void build_compact(f110_handle::MapSlot &ns, int H, int W, double reach)
 {
-    const size_t n = ns.d_cells.size(), n_b = map_cells_b(H, W);
+    const size_t n = ns.d_cells.size();
     if (n * sizeof(uint16_t) > COMPACT_MAX_BYTES) return;
+    const int P = map_pad_rows(reach);
+    const bool bytes = map_bytes_fit(H, W, P);
+    const size_t n_b = bytes ? map_cells_bp(H, W, P) : 0;
     DevBuf<uint16_t> cells[N_COMPACT];
     DevBuf<uint8_t> cells_b;
     DevBuf<double> img[N_COMPACT];
@@ -29,11 +34,12 @@ static void build_compact(f110_handle::MapSlot &ns, int H, int W)
                            cells[0].get(), cells[1].get(), counts.get());
         ok = hipGetLastError() == hipSuccess && hipMemcpy(cnt, counts.get(), sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess;
     }
-    if (ok && (ok = cells_b.alloc(n_b) == hipSuccess)) {
+    if (ok && bytes && (ok = cells_b.alloc(n_b) == hipSuccess)) {
         hipLaunchKernelGGL(map_bytes_kernel, dim3((unsigned)((n_b + 255) / 256)), dim3(256), 0, nullptr, ns.d_cells.get(),
-                           map_rows_padded(H), W, cells_b.get(), n_b);
-        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+                           H, W, P, cells_b.get(), n_b);
+        ok = hipGetLastError() == hipSuccess;
     }
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
     if (!ok) { (void)hipGetLastError(); return; }
     for (int i = 0; i < N_COMPACT; i++) {
         ns.d_cells_c[i] = std::move(cells[i]);
@@ -41,6 +47,7 @@ static void build_compact(f110_handle::MapSlot &ns, int H, int W)
         ns.compact_out[i] = cnt[0] ? (double)cnt[1 + i] / (double)cnt[0] : 0.0;
     }
     ns.d_cells_b = std::move(cells_b);
+    ns.pad_rows = bytes ? P : 0;
     ns.compact = true;
 }
 
@@ -50,11 +57,12 @@ static void build_compact(f110_handle::MapSlot &ns, int H, int W)
 static int commit_map(f110_handle *h, int slot, f110_handle::MapSlot &&ns, int H, int W, double res, double ox, double oy, double oc,
                       double os, double oob)
 {
-    if (slot == 0) build_compact(ns, H, W); // (the forms apply to a single map only; a handle that goes on to a map per env keeps slot 0's)
+    if (slot == 0) build_compact(ns, H, W, h->cfg.max_range * (1.0 / res)); // (the forms apply to a single map only; a handle that goes on to a map per env keeps slot 0's)
     MapDev &m = ns.dev;
     memset(&m, 0, sizeof(m));
     for (int i = 0; i < N_COMPACT; i++) { m.cells_c[i] = ns.d_cells_c[i].get(); m.lut_lds_c[i] = ns.d_lut_lds_c[i].get(); }
     m.cells_b = ns.d_cells_b.get(); m.cells_b_bytes = (unsigned)ns.d_cells_b.size();
+    m.pad_rows = (unsigned)ns.pad_rows; m.strip_bytes_b = m.cells_b ? (unsigned)map_rows_b(H, ns.pad_rows) * 16u : 0u;
     m.cells = ns.d_cells.get(); m.cells_far = ns.d_cells_far.get(); m.lut = ns.d_lut.get(); m.lut_lds = ns.d_lut_lds.get(); m.dt = ns.d_dt.get();
     m.H = H; m.W = W; m.strip_bytes = (unsigned)map_rows_padded(H) * 16u; m.cells_bytes = (unsigned)(ns.d_cells.size() * sizeof(uint16_t));
     m.res = res; m.rinv = 1.0 / res;

@@ -24,7 +24,7 @@ struct MapView {
     int H, W;
     double res, rinv, ox, oy, oc, os, wres, hres;
     double nox, noy; // -ox * rinv, -oy * rinv (exact when rinv is a power of two)
-    F110_BOUNDS_ONLY(uint32_t *err = nullptr; unsigned cells_bytes = 0; unsigned off_far = OFF_FAR;)
+    F110_BOUNDS_ONLY(uint32_t *err = nullptr; unsigned cells_bytes = 0; unsigned off_far = OFF_FAR; unsigned cells_skip = 0;)
     // cells: the table the march reads, m.cells or one of m.cells_c (same layout and size) or m.cells_b (bytes, 16-column strips);
     // bytes: its size; off_far: its far marker's code
     __device__ void init(const MapDev &m, const void *cells, unsigned bytes, unsigned far_code)
@@ -39,15 +39,19 @@ struct MapView {
         ox = m.ox; oy = m.oy; oc = m.oc; os = m.os; wres = m.wres; hres = m.hres;
         nox = -m.ox * m.rinv; noy = -m.oy * m.rinv;
     }
-    // The byte table (m.cells_b, 16-column strips) behind a descriptor that starts row_bias = strip_bytes + 16 bytes INTO the
-    // table and is that much shorter: the +1 strip and the +1 border row of a cell's offset are in the base, so the march forms
-    // (c >> 4) * (strip_bytes - 16) + c + (r << 4) with one shift-add for row and column together.  The addresses are the same.
-    // What lies in front of the new base is strip 0 (columns -16 .. -1) and the border row of strip 1: border cells only, whose
-    // offsets are now negative, i.e. out of range, and read as 0 -- the slot they hold.
+    // The row-padded byte table (m.cells_b, 16-column strips of strip_bytes_b bytes, row r stored at r + P: f110_map.h) behind a
+    // descriptor that starts at strip 1, map row 0 -- skip = strip_bytes_b + 16 * (1 + P) bytes INTO the table -- and is that
+    // much shorter: the +1 strip, the +1 border row and the P padding rows of a cell's offset are in the base, so the march
+    // forms (c >> 4) * (strip_bytes_b - 16) + c + (r << 4) with one shift-add for row and column together.  What lies in front
+    // of the new base is strip 0 (columns -16 .. -1) and the padding and border rows of strip 1: bytes that hold 0, whose
+    // offsets are now negative, i.e. out of range, and read as 0 -- the slot they hold.  row_bias and strip_m16 are the byte
+    // table's here; the second table (dist_lookup_far) keeps the u16 tables' geometry, which it reads from the descriptor.
     __device__ void init_bytes(const MapDev &m, unsigned far_code)
     {
-        init(m, m.cells_b + (m.strip_bytes + 16u), m.cells_b_bytes - (m.strip_bytes + 16u), far_code);
-        F110_BOUNDS_ONLY(cells_bytes = m.cells_b_bytes;)
+        const unsigned skip = m.strip_bytes_b + 16u * (1u + m.pad_rows);
+        init(m, m.cells_b + skip, m.cells_b_bytes - skip, far_code);
+        row_bias = m.strip_bytes_b + 16u; strip_m16 = m.strip_bytes_b - 16u;
+        F110_BOUNDS_ONLY(cells_bytes = m.cells_b_bytes; cells_skip = skip;)
     }
 };
 
@@ -102,8 +106,9 @@ __device__ inline void cell_index(const MapView &m, double x, double y, int &ci,
 
 // byte offset of the cell under (column ci, row ri) in the strip table: both clamped onto the border.  BYTES: in the byte table
 // of 16-column strips (f110_map.h: cell_elem_b), (c >> 4) * (S - 16) + c -- the column is added, not shift-added
+// (row_bias, strip_m16: of the table the offset is for -- MapView's, except for the second table under the byte march)
 template <bool BYTES = false>
-__device__ inline unsigned cell_offset(const MapView &m, int ci, int ri)
+__device__ inline unsigned cell_offset(const MapView &m, int ci, int ri, unsigned row_bias, unsigned strip_m16)
 {
     const int cc = med3_i32(ci, -1, m.W);      // column -1..W (both ends are border cells)
     const int rr = med3_i32(ri, -1, m.H);      // row -1..H
@@ -112,12 +117,14 @@ __device__ inline unsigned cell_offset(const MapView &m, int ci, int ri)
     // so no add is spent on the padding and the offset never goes negative; asm so that the constant is not re-associated
     // into a trailing add.  (c >> 3) * S + (c & 7) * 2 == (c >> 3) * (S - 16) + c * 2: no masking of the column bits needed
     unsigned row16;
-    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(row16) : "v"(rr), "s"(m.row_bias));
-    if (BYTES) return (unsigned)(__mul24(cc >> 4, (int)m.strip_m16) + (int)(((unsigned)rr << 4) + (unsigned)cc)); // (against init_bytes' base)
+    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(row16) : "v"(rr), "s"(row_bias));
+    if (BYTES) return (unsigned)(__mul24(cc >> 4, (int)strip_m16) + (int)(((unsigned)rr << 4) + (unsigned)cc)); // (against init_bytes' base)
     unsigned rc;
     asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(rc) : "v"(cc), "v"(row16));
-    return (unsigned)(__mul24(cc >> 3, (int)m.strip_m16) + (int)rc);
+    return (unsigned)(__mul24(cc >> 3, (int)strip_m16) + (int)rc);
 }
+template <bool BYTES = false>
+__device__ inline unsigned cell_offset(const MapView &m, int ci, int ri) { return cell_offset<BYTES>(m, ci, ri, m.row_bias, m.strip_m16); }
 
 // One table look-up (laser_models.py:56-104 distance_transform): the value of the cell under (x, y), or -0.0 when the cell
 // carries the far marker (dist_lookup_far finishes those).  The caller runs it under the EXEC mask of the rays that are
@@ -132,8 +139,9 @@ __device__ inline double dist_lookup(const MapView &m, const double *lds_lut, do
     unsigned code = BYTES ? (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(m.cells_rsrc, (int)off, 0, 0) << 3
                           : (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(m.cells_rsrc, (int)off, 0, 0);
 #if defined(F110_BOUNDS)
-    // the offset inside the table (BYTES: counted from the table's start, where init_bytes' descriptor starts row_bias later)
-    F110_BCHK(BYTES ? off + m.row_bias < m.cells_bytes : off + 2u <= m.cells_bytes, BT_LUT_CODE, m.err);
+    // the offset inside the table (BYTES: counted from the table's start, where init_bytes' descriptor starts cells_skip later;
+    // the border row and column lie in front of it and wrap back)
+    F110_BCHK(BYTES ? off + m.cells_skip < m.cells_bytes : off + 2u <= m.cells_bytes, BT_LUT_CODE, m.err);
     F110_BCHK(code <= m.off_far && (code & 7u) == 0u, BT_LUT_CODE, m.err); // (a compact table: nothing behind ITS marker)
     code = code <= m.off_far ? (code & ~7u) : 0u;
 #endif
@@ -144,14 +152,17 @@ __device__ inline double dist_lookup(const MapView &m, const double *lds_lut, do
 }
 
 // the rare path behind the far marker: the cell's full rank from the second table, then the global LUT or the fp64 table
-template <bool IDENT, bool POW2>
+// (BYTES: the view's geometry is the byte table's; the u16 tables' strip is re-read from the descriptor here)
+template <bool IDENT, bool POW2, bool BYTES = false>
 __device__ inline double dist_lookup_far(const MapView &m, double x, double y)
 {
     int ci, ri;
     cell_index<IDENT, POW2>(m, x, y, ci, ri);
-    unsigned off = cell_offset(m, ci, ri);
+    unsigned off = 0;
+    if (!BYTES) off = cell_offset(m, ci, ri);
     const MapDev *dp = m.desc;
     asm volatile("" : "+s"(dp)); // opaque: the loads below stay here instead of being hoisted to the kernel entry
+    if (BYTES) { const unsigned sb = dp->strip_bytes; off = cell_offset(m, ci, ri, sb + 16u, sb - 16u); }
 #if defined(F110_BOUNDS)
     F110_BCHK(off + 2u <= dp->cells_bytes, BT_CELLS_FAR, m.err);
     if (off + 2u > dp->cells_bytes) off = 0u;
@@ -300,24 +311,31 @@ __device__ inline void march_ident_pow2(const MapView &m, double &x, double &y, 
 //  * no clamp of the COLUMN: a column outside [-8, W + 8) forms an offset outside the table (negative ones wrap to large
 //    unsigned values), which the descriptor's range check answers with 0 = the border's code; the columns in between lie in the
 //    border strips.  That needs (c >> 3) * strip_bytes below 2^31, which the limit guarantees.  (The row still needs its clamp:
-//    a row beyond the strip would land in the neighbouring strip.)
-// BYTES, the same two arguments for strips of 16 columns and init_bytes' descriptor, which starts strip_bytes + 16 into the
-// table (16 VALU: the shift-add that joins row and column pays for the shift that turns the slot into the LDS offset, in v61):
-//  * counted from the table's start the offset is ((c >> 4) + 1) * strip_bytes + (r + 1) * 16 + (c & 15) with the row clamped,
-//    so a column outside [-16, 16 * ((W >> 4) + 1)) -- a fortiori one outside [-16, 16 * ((W >> 4) + 1) + 16) -- has strip index
-//    (c >> 4) + 1 below 0 or at or above the table's (W >> 4) + 2 strips: against the descriptor an offset that is negative
-//    (wraps to 2^31 or more) or at or beyond its bytes.  The columns in between that are no map cell lie in strip 0 (negative
-//    too: in front of the descriptor) or in the last strip's padding, which holds 0;
+//    a row beyond the strip would land in the neighbouring strip.)  16 VALU + 6 SALU per iteration.
+// BYTES: the row-padded byte table (f110_map.h: P = pad_rows zero rows above row -1 and below row H of every 16-column strip,
+// S = strip_bytes_b) behind init_bytes' descriptor, which starts at strip 1, map row 0.  NEITHER coordinate is clamped; the
+// offset the statement forms is (c >> 4) * S + r * 16 + (c & 15).  scan_kernel takes this march only for a car whose own row
+// lies in [-1, H] (and whose reach the table was padded for), so every row r of a look-up lies in [-1 - P, H + P]:
+//  * rows: the table stores row r of a strip at r + 1 + P in 0 .. H + 2 P + 1 < S / 16, so r * 16 + (c & 15) stays inside
+//    [-16 (1 + P), S - 16 (1 + P)) and the look-up never leaves the strip of its column.  Rows -1 - P .. -1 and H .. H + P
+//    are the strip's own padding and border rows, which hold 0; in strip 1 the rows below 0 lie in front of the descriptor
+//    (a negative offset, out of range), in later strips they are the strip's first rows, ordinary bytes that hold 0;
+//  * columns, as before: a column outside [-16, 16 * ((W >> 4) + 1)) has strip index (c >> 4) + 1 below 0 or at or above the
+//    table's (W >> 4) + 2 strips -- against the descriptor an offset that is negative (wraps to 2^31 or more) or at or beyond
+//    its bytes, ((W >> 4) + 1) * S - 16 (1 + P).  The columns in between that are no map cell lie in strip 0 (negative too) or
+//    in the last strip's padding columns, which hold 0;
 //  * the descriptor's range check answers 0 for those offsets, the slot of the border; 0 << 3 is its code.  The limit keeps
-//    ((c >> 4) + 1) * strip_bytes below 2^31 and c >> 4 inside the multiply's 24 bits.
-// 16 VALU + 6 SALU per iteration.  The magic sums and the products live in v[60:63]: an asm operand cannot name the low dword
+//    ((c >> 4) + 1) * S below 2^31 and c >> 4 inside the multiply's 24 bits.
+// 15 VALU + 6 SALU per iteration, one buffer_load_ubyte, one ds_read_b64 (tests/test_scan_rowpad_cpu.py replays the offset
+// arithmetic over every such row and column).  A car standing off those rows takes the clamped twin above.
+// The magic sums and the products live in v[60:63]: an asm operand cannot name the low dword
 // of a register pair, so the statement uses those four registers by name and declares them clobbered.
 template <bool BYTES = false>
 __device__ inline void march_ident_pow2_fast(const MapView &m, double &x, double &y, double &total, double &d, double c, double s,
                                              double eps, double max_range, unsigned long long &am, int go, unsigned &nlook, int &nact)
 {
     unsigned long long sx;
-#define F110_MARCH_FAST(CELL, LOAD) \
+#define F110_MARCH_FAST(ROW, CELL, LOAD, GEOM) \
     asm volatile( \
         "s_mov_b64 %[sx], exec\n\t" \
         "s_mov_b64 exec, %[am]\n" \
@@ -329,7 +347,7 @@ __device__ inline void march_ident_pow2_fast(const MapView &m, double &x, double
         "v_add_f64 v[60:61], v[60:61], %[magic]\n\t" \
         "v_add_f64 v[62:63], v[62:63], %[magic]\n\t" \
         "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 0\n\t"      /* back to nearest-even */ \
-        "v_med3_i32 v62, v62, -1, %[H]\n\t" \
+        ROW \
         CELL("v61", "v62", "v60") \
         "v_mad_i32_i24 v61, v61, %[sm], v62\n\t" \
         LOAD("v61") \
@@ -348,12 +366,16 @@ __device__ inline void march_ident_pow2_fast(const MapView &m, double &x, double
         "s_mov_b64 %[am], exec\n\t" \
         "s_mov_b64 exec, %[sx]" \
         : [x] "+v"(x), [y] "+v"(y), [tot] "+v"(total), [d] "+v"(d), [am] "+s"(am), [nl] "+s"(nlook), [na] "+s"(nact), [sx] "=&s"(sx) \
-        : [c] "v"(c), [s] "v"(s), [nox] "v"(m.nox), [noy] "v"(m.noy), [rinv] "s"(m.rinv), [H] "s"(m.H), \
-          [rb] "s"(m.row_bias), [sm] "s"(m.strip_m16), [rsrc] "s"(m.cells_words), [eps] "s"(eps), [mr] "s"(max_range), [go] "s"(go), \
+        : [c] "v"(c), [s] "v"(s), [nox] "v"(m.nox), [noy] "v"(m.noy), [rinv] "s"(m.rinv), GEOM \
+          [sm] "s"(m.strip_m16), [rsrc] "s"(m.cells_words), [eps] "s"(eps), [mr] "s"(max_range), [go] "s"(go), \
           [magic] "s"(6755399441055744.0) \
         : "vcc", "scc", "memory", "v60", "v61", "v62", "v63")
-    if constexpr (BYTES) F110_MARCH_FAST(F110_MARCH_CELL_BYTE, F110_MARCH_LOAD_BYTE);
-    else F110_MARCH_FAST(F110_MARCH_CELL_WORD_FAST, F110_MARCH_LOAD_WORD);
+#define F110_MARCH_ROW_CLAMP "v_med3_i32 v62, v62, -1, %[H]\n\t"
+#define F110_MARCH_GEOM_WORD [H] "s"(m.H), [rb] "s"(m.row_bias),
+    if constexpr (BYTES) F110_MARCH_FAST("", F110_MARCH_CELL_BYTE, F110_MARCH_LOAD_BYTE, );
+    else F110_MARCH_FAST(F110_MARCH_ROW_CLAMP, F110_MARCH_CELL_WORD_FAST, F110_MARCH_LOAD_WORD, F110_MARCH_GEOM_WORD);
+#undef F110_MARCH_GEOM_WORD
+#undef F110_MARCH_ROW_CLAMP
 #undef F110_MARCH_FAST
 }
 // The march for a map whose resolution is NOT a power of two (most F1TENTH maps: 0.05 m) and whose origin is not rotated, for
@@ -720,7 +742,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
     // ---- ray march (laser_models.py:107-186) -------------------------------------
     // The first table read of every beam is at the car itself (:129): done once.
     double d0 = dist_lookup<IDENT, POW2, BYTES>(mv, s_lut, px, py);
-    if (__builtin_expect(is_far_marker(d0), 0)) d0 = dist_lookup_far<IDENT, POW2>(mv, px, py); // (wave-uniform: every lane reads the car's own cell)
+    if (__builtin_expect(is_far_marker(d0), 0)) d0 = dist_lookup_far<IDENT, POW2, BYTES>(mv, px, py); // (wave-uniform: every lane reads the car's own cell)
     unsigned nlook = (unsigned)nbl; // the reference reads the table once per beam before marching
     if (!(d0 > eps && d0 <= max_range)) {
         for (int k = lane; k < nbl; k += WAVE) {
@@ -749,6 +771,9 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
             const double q0x = POW2 ? __builtin_fma(px, mv.rinv, mv.nox) : (px - mv.ox) * mv.rinv;
             const double q0y = POW2 ? __builtin_fma(py, mv.rinv, mv.noy) : (py - mv.oy) * mv.rinv;
             fast = fabs(q0x) + reach < lim && fabs(q0y) + reach < lim;
+            // the byte march clamps no row: the car's own row in -1 .. H, and the table padded for this reach (it is, by
+            // construction: the install pads for the handle's max_range).  Any other car takes the clamped twin.
+            if (BYTES) fast = fast && q0y >= -1.0 && q0y < (double)(mv.H + 1) && reach <= (double)md.pad_rows;
         }
         int next = 0;           // wave-uniform: next unassigned slot of the beam order
         bool active = false;
@@ -763,7 +788,7 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void scan_kernel(Scan
                 const bool farp = !active && is_far_marker(d);
                 if (__builtin_expect(vote(farp) != 0ull, 0)) {
                     if (farp) {
-                        d = dist_lookup_far<IDENT, POW2>(mv, x, y);
+                        d = dist_lookup_far<IDENT, POW2, BYTES>(mv, x, y);
                         total += d;
                         x += d * c;
                         y += d * s;

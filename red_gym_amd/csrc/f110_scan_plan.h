@@ -250,6 +250,9 @@ inline int scan_codes_override(const char *v)
 // The rule: bytes exactly where the row buffer is launched (the one instantiation of the 256-slot form the default run uses;
 // every code of that form is below slot 256 by construction, so nothing else has to hold).
 inline bool scan_codes_choice(int lut, bool rowbuf, int forced) { return lut == SCAN_ROWBUF_LUT && rowbuf && forced != 0; }
+// `forced` as the rule may see it: a map without the byte table (the row-padded table did not fit the compact tables' limit,
+// f110_map.h: map_bytes_fit) reads word codes whatever the override says
+inline int scan_codes_available(bool has_table, int forced) { return has_table ? forced : 0; }
 
 // F110_SCAN_FORM: "classic" -> 0, "compact256" -> 256, "compact512" -> 512; unset or anything else -> -1 (the rule decides)
 inline int scan_form_override(const char *v)

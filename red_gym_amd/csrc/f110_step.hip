@@ -171,13 +171,23 @@ extern "C" int f110_scan_rows_info(f110_handle *h, int32_t n_cars, int32_t *lds)
 }
 
 // F110_SCAN_CODES = byte | word (read once per process; tests and A/B runs) over the rule scan_codes_choice
+// ... where slot 0 has its row-padded byte table (scan_codes_available: a map whose padded table did not fit reads word codes)
 static int scan_codes_forced() { static const int forced = scan_codes_override(getenv("F110_SCAN_CODES")); return forced; }
+static int scan_codes_of(const f110_handle *h) { return scan_codes_available(h->slots[0].dev.cells_b != nullptr, scan_codes_forced()); }
 
 extern "C" int f110_scan_codes_info(f110_handle *h, int32_t n_cars, int32_t *bytes)
 {
     if (!h || !bytes || n_cars < 1) return fail(F110_E_INVALID, "f110_scan_codes_info: bad arguments");
     if (!h->has_map) return fail(F110_E_NOMAP, "Map is not set for scan simulator.");
-    *bytes = scan_codes_choice(scan_form(h, n_cars), scan_rowbuf_choice(scan_form(h, n_cars), true, scan_rows_forced()), scan_codes_forced());
+    *bytes = scan_codes_choice(scan_form(h, n_cars), scan_rowbuf_choice(scan_form(h, n_cars), true, scan_rows_forced()), scan_codes_of(h));
+    return F110_OK;
+}
+
+extern "C" int f110_scan_pad_rows(f110_handle *h, int32_t *rows)
+{
+    if (!h || !rows) return fail(F110_E_INVALID, "f110_scan_pad_rows: bad arguments");
+    if (!h->has_map) return fail(F110_E_NOMAP, "Map is not set for scan simulator.");
+    *rows = h->slots[0].dev.cells_b ? (int32_t)h->slots[0].dev.pad_rows : -1;
     return F110_OK;
 }
 
@@ -207,7 +217,7 @@ static int run_scan(const f110_handle *h, const ScanArgs &a, const Sink &k, hipE
     in.n_cars = a.n_cars; in.agents = a.agents; in.num_beams = a.scan.nb; in.stages = &h->stages; in.step = a.state != nullptr;
     in.stores = stores_env; in.multi = a.env_map != nullptr; in.wg_single = h->wg_single; in.kind = h->ident | h->pow2 << 1;
     in.compact = in.step && !in.multi ? scan_form(h, a.n_cars) : 0;
-    in.out_f32 = a.out_f32 != nullptr; in.rows = scan_rows_forced(); in.codes = scan_codes_forced();
+    in.out_f32 = a.out_f32 != nullptr; in.rows = scan_rows_forced(); in.codes = scan_codes_of(h);
     std::vector<ScanLaunch> plan;
     if (int rc = plan_scan(in, [h](int env) { const f110_handle::MapSlot &m = h->slots[h->h_env_map[env]]; return m.ident | m.pow2 << 1; }, plan))
         return rc;
@@ -222,9 +232,10 @@ static int run_scan(const f110_handle *h, const ScanArgs &a, const Sink &k, hipE
             const MapDev &m = h->slots[0].dev;
             if (ci < 0 || l.sm < 1 || l.kind != 3 || !m.cells_c[ci] || !m.lut_lds_c[ci])
                 return fail(F110_E_INVALID, "scan launch: compact form %d without its tables (kind %d, sm %d)", l.lut, l.kind, l.sm);
-            // ... nor the byte instantiation the byte table
-            if (l.bytes && (!l.rowbuf || l.lut != SCAN_ROWBUF_LUT || !m.cells_b || !m.cells_b_bytes))
-                return fail(F110_E_INVALID, "scan launch: byte cell codes without their table (form %d, rows %d)", l.lut, (int)l.rowbuf);
+            // ... nor the byte instantiation the byte table, whose fast march relies on the table's padding rows
+            if (l.bytes && (!l.rowbuf || l.lut != SCAN_ROWBUF_LUT || !m.cells_b || !m.pad_rows ||
+                            m.cells_b_bytes != map_cells_bp(m.H, m.W, (int)m.pad_rows) || m.strip_bytes_b != (unsigned)map_rows_b(m.H, (int)m.pad_rows) * 16u))
+                return fail(F110_E_INVALID, "scan launch: byte cell codes without their padded table (form %d, rows %d)", l.lut, (int)l.rowbuf);
             func = l.bytes ? scan_kernels_bytes[l.sm - 1] : l.rowbuf ? scan_kernels_rowbuf[l.sm - 1] : scan_kernels_compact[ci][l.sm - 1];
         }
         if (int rc = emit(k, func, dim3(l.grid), dim3(l.block), 0, s, l.events ? ev0 : nullptr,

@@ -767,6 +767,12 @@ class Engine(object):
         _lib.check(self.lib.f110_scan_codes_info(self._h, self.N if n_cars is None else int(n_cars), C.byref(b)))
         return bool(b.value)
 
+    def scan_pad_rows(self):
+        """The padding rows P of the map's byte cell table (f110_scan_pad_rows), or -1 where the map has no byte table."""
+        p = C.c_int32(0)
+        _lib.check(self.lib.f110_scan_pad_rows(self._h, C.byref(p)))
+        return int(p.value)
+
     # ------------------------------------------------------------------ measurement aid
     def profile_begin(self, max_launches, every=1):
         """hipEvent pairs on the scan dispatch of every `every`-th step from now on (f110_profile_begin / _every)."""
