@@ -1,5 +1,5 @@
 """The training loop of the reference's RL consumer (main(), src/SAL.py:975-1019) for many envs at once, everything on the GPU:
-    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps] [nstep] [auto] [device] [per] [stack3]
+    python examples/sac_train.py [envs] [steps] [batch] [update_after] [update_every] [max_steps] [nstep] [auto] [device] [per] [stack3] [clip10]
     select_action (the policy on the shaper's bitmap) -> path_actions (SAL's action decode and MPC step, which also hands the raw
     action to the ring) -> step (scan, shaper, the ring's push) -> after update_after steps, every update_every steps, one SACAgent
     update replayed from a graph: the batch is drawn on the device, the losses stay there.  The episodes are kept on the GPU too
@@ -19,7 +19,9 @@ back, all inside the replayed graph (SACAgent(per=True)); the mean importance we
 losses.  With a trailing `stack3` (any count up to 8) the networks see the last three frames of an env (SACAgent(stack=3): conv1 has three
 input channels, read as three rows of the ring's frame tensor, no frame is stored twice): the policy acts on the ring's newest stacks
 (act_from) and the mean depth of the last batch's stacks is printed beside the losses -- below 3 at the start of an episode, where the
-first frame fills the stack."""
+first frame fills the stack.  With a trailing `clip10` (any positive number, or `clipinf` for the non-finite guard alone) every
+optimizer clips the global norm of its network's gradients at 10 on the device and skips a step whose norm is not finite
+(SACAgent(max_grad_norm=10)): the three norms (actor, critic 1, critic 2) and the skipped-step counters are printed beside the losses."""
 import os
 import sys
 import tempfile
@@ -34,6 +36,7 @@ AD = 16
 NSTEP = int(sys.argv[7]) if len(sys.argv) > 7 and sys.argv[7].isdigit() else 1
 AUTO, DEVICE, PER = 'auto' in sys.argv[7:], 'device' in sys.argv[7:], 'per' in sys.argv[7:]
 STACK = ([int(a[5:]) for a in sys.argv[7:] if a.startswith('stack') and a[5:].isdigit()] + [0])[0]      # 0: not asked for
+CLIP = ([float(a[4:]) for a in sys.argv[7:] if a.startswith('clip') and a[4:]] + [None])[0]               # None: not asked for
 env = F110VecEnv(B, map=workload.EXAMPLE_MAP, num_agents=1, autoreset=True)
 env.shape_rewards()
 env.follow_paths()
@@ -42,7 +45,8 @@ env.track_episodes(MAX_STEPS + torch.arange(B, dtype=torch.int32) % 4)   # stagg
 dev, cfg = env.device, env.eng.shaper.cfg
 torch.manual_seed(0)
 agent = SACAgent(action_dim=AD, rows=cfg.rows, cols=cfg.cols, device=dev, **(dict(alpha='auto') if AUTO else {}),
-                 **(dict(draws='device', seed=0) if DEVICE else {}), nstep=NSTEP, per=PER, **(dict(stack=STACK) if STACK else {}))
+                 **(dict(draws='device', seed=0) if DEVICE else {}), nstep=NSTEP, per=PER, **(dict(stack=STACK) if STACK else {}),
+                 max_grad_norm=CLIP)
 raw = torch.zeros((B, AD), dtype=torch.float64, device=dev)                    # the policy's action, written in place
 obs, reward, done, info = env.reset(torch.as_tensor(workload.spawn_poses(B, 1), device=dev))
 total = torch.zeros((B,), dtype=torch.float64, device=dev)
@@ -60,11 +64,13 @@ for step in range(1, STEPS + 1):
         losses = agent.update_graph()
         updates += 1
         if updates % 4 == 1:
-            print('step %3d, update %2d: losses (actor, critic 1, critic 2) %s%s%s%s%s' % (
+            print('step %3d, update %2d: losses (actor, critic 1, critic 2) %s%s%s%s%s%s' % (
                 step, updates, ' '.join('%.6f' % v for v in losses.tolist()), ', alpha %.9f' % agent.alpha.item() if AUTO else '',
                 ', mean span %.3f of %d' % (agent.sample['span'].double().mean().item(), NSTEP) if NSTEP > 1 else '',
                 ', mean weight %.4f, beta %.6f' % (agent.sample['weight'].mean().item(), env.replay.priorities.beta) if PER else '',
-                ', mean depth %.3f of %d' % (agent.sample['depth'].double().mean().item(), STACK) if STACK > 1 else ''))
+                ', mean depth %.3f of %d' % (agent.sample['depth'].double().mean().item(), STACK) if STACK > 1 else '',
+                ', gradient norms %s clipped at %g, steps skipped %s' % (' '.join('%.4g' % v for v in agent.grad_stats()['norm'].tolist()), CLIP,
+                                                                        agent.grad_stats()['steps_skipped'].tolist()) if CLIP else ''))
             count = int(info['episodes_finished'].item())
             rec = {k: v.tolist() for k, v in env.episodes.finished(last=min(count - printed, 4)).items()}   # (a few of the new ones)
             for i in range(len(rec['env'])):

@@ -1207,6 +1207,61 @@ int f110_adam_step(const f110_adam_config *cfg, const f110_adam_tensor *table, i
                    void *stream);
 int f110_soft_update(const f110_adam_tensor *table, int32_t n_tensors, double tau, void *stream);
 
+/* Gradient clipping: the global L2 norm of the gradients of one optimizer step, the clip coefficient and a non-finite guard, formed on
+ * the device in a fixed order and consumed by the Adam pass while g is in a register.  Opt-in: f110_adam_step keeps its launches, its
+ * kernels and its bits.  One step is f110_adam_gradnorm (per call of up to F110_ADAM_MAX_TENSORS tensors), then f110_adam_clip once,
+ * then f110_adam_step_clipped (per call); all launch on `stream` of the calling thread's current device, no allocation, no
+ * synchronisation, no atomics.  The step covers the tensors that have a gradient, in table order, in chunks of F110_ADAM_CHUNK elements
+ * partitioned exactly as f110_adam_step partitions them (tensor i owns ceil(n_i / F110_ADAM_CHUNK) chunks; an empty tensor none); the
+ * chunks are numbered consecutively over the whole step, across calls: a further call takes chunk_base = the chunks of the calls before it.
+ * Numerics, bit for bit, every + one fp64 addition, nothing contracted:
+ *   chunk partial P_c   a chunk is 1 024 quads of four consecutive elements.  Chain l (0 <= l < 256) takes the elements j of the chunk
+ *                       with (j >> 2) & 255 == l, j ascending: S_l = S_l + double(g_j) * double(g_j) from 0.0 (the product of two fp32
+ *                       values is exact in fp64); a chain without an element is 0.0.  Then for s = 128, 64, .., 1: S_l = S_l + S_(l + s)
+ *                       for every l < s (the tree of the losses above), and P_c = S_0.  The membership is by element index, not by
+ *                       access width: a tensor on the 4-byte path gives the same P_c.
+ *   step sum S          chain l over the partials c = l mod 256, c ascending, from 0.0; the same tree.  finite = (S < +inf), false for
+ *                       NaN.  Finite fp32 inputs cannot overflow: at most 2^31 elements a tensor, each term <= 1.2e77.
+ *   norm, coefficient   norm = sqrt(S), correctly rounded (0.0 for S = 0); c = max_norm / (norm + 1e-6), one fp64 addition and one IEEE
+ *                       division (torch.nn.utils.clip_grad_norm_'s formula); coef = (c < 1.0) ? float(c) : 1.0f.  max_norm = +inf is
+ *                       allowed and gives coef = 1.0f always: the guard alone.
+ *   decision            skip = !finite (the guard is on whenever clipping is in use); clipped = !skip && coef < 1.0f, after rounding.
+ *                       On a skip the state holds sumsq = norm = +inf and coef = 1.0f, whatever NaN the sum was (a NaN's payload is
+ *                       no part of the contract, in a partial neither).  steps_clipped += clipped; steps_skipped += skip.
+ *   element             gc = g * coef, one fp32 multiplication, then the lines d .. p' of f110_adam_step's contract with gc in g's
+ *                       place; with coef == 1.0f this is the unclipped step bit for bit.  g itself is NOT written (torch's
+ *                       clip_grad_norm_ scales .grad in place; this saves a pass of stores).
+ *   skipped step        p, m, v and the Adam state (t, pow1, pow2, k2, a) keep their bits: the advance in front of the step returns at
+ *                       once.  The target is still moved from the unchanged p, as for a parameter without a gradient.
+ * f110_adam_gradnorm: one workgroup of 256 per chunk writes partials[chunk_base + c] (dev fp64 [partials_len]) for the table's chunks
+ * c; it reads g and n of each tensor and nothing else (p, m, v, target are ignored), with 16-byte loads where g is 16-byte aligned and
+ * 4-byte loads otherwise.
+ * f110_adam_clip: one workgroup of 256 on partials[0 .. n_chunks) forms S, norm, coef and skip, advances the two counters and writes
+ * *clip (dev) with plain stores from one lane.  n_chunks = 0 gives S = 0.  A fresh clip state is all zero bytes.
+ * f110_adam_step_clipped: f110_adam_step -- the same arguments, refusals and partition -- with an advance launch that returns at once
+ * when clip->skip is set and update kernels of their own that read coef and skip from *clip; skip is tested in a wave-uniform branch
+ * around the Adam half, the target half is untouched.
+ * F110_E_INVALID, before any launch, naming the culprit: what f110_adam_step refuses (gradnorm: of n_tensors, table, n and g alone);
+ * a null partials or clip; chunk_base < 0; a table whose chunks do not fit partials_len behind chunk_base; n_chunks < 0; max_norm NaN
+ * or <= 0; partials or clip not 8-byte aligned; and partials or clip on a wrong device as f110_policyhead_forward refuses it.
+ * f110_adam_clip_state_bytes: sizeof(f110_adam_clip_state), F110_ADAM_CLIP_STATE_BYTES.
+ * (The struct carries a tag, as the temperature's: it lives on the device, _lib.ADAM_CLIP_STRUCTS mirrors it and
+ * tests/test_clip_cpu.py checks its fields, size and offsets by the C compiler.) */
+#define F110_ADAM_CLIP_STATE_BYTES 64
+typedef struct f110_adam_clip_state {   /* on the device; 64 bytes */
+    double sumsq, norm;             /* S and sqrt(S) of the last step (+inf on a skip) */
+    float coef;                     /* what the step multiplied g by */
+    int32_t skip;                   /* 1: the last step was skipped */
+    int64_t steps_clipped, steps_skipped;
+    int64_t reserved[3];            /* 0 */
+} f110_adam_clip_state;
+int64_t f110_adam_clip_state_bytes(void);
+int f110_adam_gradnorm(const f110_adam_tensor *table, int32_t n_tensors, int64_t chunk_base, double *partials, int64_t partials_len,
+                       void *stream);
+int f110_adam_clip(const double *partials, int64_t n_chunks, double max_norm, f110_adam_clip_state *clip, void *stream);
+int f110_adam_step_clipped(const f110_adam_config *cfg, const f110_adam_tensor *table, int32_t n_tensors, f110_adam_state *state,
+                           const f110_adam_clip_state *clip, double lr, void *stream);
+
 /* The two losses of SACAgent.update (src/SAL.py:553-554, :568) and their gradients with respect to the arrays given, one launch each,
  * stateless (all arrays dev, n rows, 1 <= n <= 2^24; launches on `stream` of the calling thread's current device, no allocation, no
  * synchronisation, no atomics).  Neither knows of autograd: the caller hands the gradients to the layers behind q, log_prob and min_q.

@@ -189,6 +189,18 @@ class AdamTensor(C.Structure):
 F110_ADAM_CHUNK = 4096
 F110_ADAM_MAX_TENSORS = 64
 F110_ADAM_STATE_BYTES = 32          # f110_adam_state: int64 t, double pow1, pow2, float k2, a
+F110_ADAM_CLIP_STATE_BYTES = 64
+
+
+# f110_adam_clip_state: the norm, the coefficient and the guard of a clipped step.  It lives on the device (a fresh one is zero bytes);
+# a tagged typedef like the temperature's, mirrored here so that optim.py reads its offsets; tests/test_clip_cpu.py checks it against
+# the compiler.
+class AdamClipState(C.Structure):
+    _fields_ = [('sumsq', C.c_double), ('norm', C.c_double), ('coef', C.c_float), ('skip', C.c_int32),
+                ('steps_clipped', C.c_int64), ('steps_skipped', C.c_int64), ('reserved', C.c_int64 * 3)]
+
+
+ADAM_CLIP_STRUCTS = {'f110_adam_clip_state': AdamClipState}
 
 
 # f110_temperature_config, f110_temperature_state: the entropy temperature learnt on the device.  The state lives on the device and
@@ -388,6 +400,10 @@ SYMBOLS = {
     'f110_adam_state_bytes': [],
     'f110_adam_step': [C.POINTER(AdamConfig), C.POINTER(AdamTensor), _I32, _VP, _D, _VP],
     'f110_soft_update': [C.POINTER(AdamTensor), _I32, _D, _VP],
+    'f110_adam_clip_state_bytes': [],
+    'f110_adam_gradnorm': [C.POINTER(AdamTensor), _I32, _I64, _VP, _I64, _VP],
+    'f110_adam_clip': [_VP, _I64, _D, _VP, _VP],
+    'f110_adam_step_clipped': [C.POINTER(AdamConfig), C.POINTER(AdamTensor), _I32, _VP, _VP, _D, _VP],
     'f110_sac_critic_loss': [_VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP],
     'f110_sac_actor_loss': [_VP, _I32, _VP, _D, _I64, _VP, _VP, _VP, _VP],
     'f110_sac_critic_loss_weighted': [_VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP],
@@ -425,7 +441,7 @@ SYMBOLS = {
 RESTYPES = {
     'f110_last_error': C.c_char_p,
     'f110_destroy': None, 'f110_graph_destroy': None, 'f110_bitmap_destroy': None,
-    'f110_pack_env_size': _I64, 'f110_adam_state_bytes': _I64, 'f110_temperature_state_bytes': _I64,
+    'f110_pack_env_size': _I64, 'f110_adam_state_bytes': _I64, 'f110_adam_clip_state_bytes': _I64, 'f110_temperature_state_bytes': _I64,
     'f110_gauss_state_bytes': _I64, 'f110_priority_node_words': _I64,
     'f110_pure_pursuit_workspace': _I64, 'f110_bitconv_workspace': _I64, 'f110_bitconv_workspace_stack': _I64, 'f110_featconv_workspace': _I64,
     'f110_dense_workspace': _I64, 'f110_policyhead_workspace': _I64, 'f110_qhead_workspace': _I64,

@@ -61,8 +61,9 @@ static_assert(sizeof(AdamEntry) == 48 && sizeof(AdamTable) + sizeof(void *) <= 4
 
 using AdamState = f110_adam_state;
 
-// sqrt of x in (0, 1], correctly rounded whatever the library's own last bit: Tuckerman's test (y is the rounded root exactly when
-// y * pred(y) < x <= y * succ(y)), each product's sign taken from one fma, which is exact in sign.
+// sqrt of a normal positive x (the step's 1 - pow2 in (0, 1]; the sum of squares of f110_adam_clip.h, at least 2^-298 and 2^287 a tensor),
+// correctly rounded whatever the library's own last bit: Tuckerman's test (y is the rounded root exactly when y * pred(y) < x <= y *
+// succ(y)), each product's sign taken from one fma, which is exact in sign while y * y stays clear of the overflow and denormal ranges.
 __device__ inline double adam_sqrt_rn(double x)
 {
     double y = sqrt(x);

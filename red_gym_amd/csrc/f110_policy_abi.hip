@@ -3,6 +3,7 @@
 #include "f110_policyhead.h"
 #include "f110_qhead.h"
 #include "f110_adam.h"
+#include "f110_adam_clip.h"
 #include "f110_sacloss.h"
 #include "f110_temperature.h"
 
@@ -246,32 +247,47 @@ static int adam_table(const char *who, const f110_adam_tensor *table, int n_tens
     return F110_OK;
 }
 
-extern "C" int f110_adam_step(const f110_adam_config *cfg, const f110_adam_tensor *table, int32_t n_tensors, f110_adam_state *state, double lr,
-                              void *stream)
+// f110_adam_step (clip NULL: the launches it always made) and f110_adam_step_clipped
+static int adam_step(const char *who, const f110_adam_config *cfg, const f110_adam_tensor *table, int32_t n_tensors, f110_adam_state *state,
+                     const f110_adam_clip_state *clip, bool clipped, double lr, void *stream)
 {
-    const char *who = "f110_adam_step";
     if (int rc = adam_scalar_checks(who, cfg, cfg && cfg->with_target)) return rc;
     if (!state) return fail(F110_E_INVALID, "%s: null state", who);
     if ((uintptr_t)state % 8) return fail(F110_E_INVALID, "%s: the state is not 8-byte aligned", who);
+    if (clipped && !clip) return fail(F110_E_INVALID, "%s: null clip", who);
+    if (clipped && (uintptr_t)clip % 8) return fail(F110_E_INVALID, "%s: clip is not 8-byte aligned", who);
     if (!std::isfinite(lr)) return fail(F110_E_INVALID, "%s: lr is not finite", who);
     const bool target = cfg->with_target != 0;
     AdamTable tab;
     uint32_t grid = 0;
     std::vector<DevicePtr> ptrs = {{"state", state}};
+    if (clipped) ptrs.push_back({"clip", clip});
     if (int rc = adam_table(who, table, n_tensors, true, target, tab, &grid, ptrs)) return rc;
     if (int rc = check_device_pointers(who, (hipStream_t)stream, ptrs)) return rc;
     tab.c1 = (float)(1.0 - cfg->beta1); tab.c2 = (float)(1.0 - cfg->beta2); tab.b2 = (float)cfg->beta2; tab.eps = (float)cfg->eps;
     tab.tau = target ? (float)cfg->tau : 0.0f;
     hipStream_t s = (hipStream_t)stream;
     if (cfg->advance) {
-        hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, s, state, cfg->beta1, cfg->beta2, lr);
+        if (clipped) hipLaunchKernelGGL(adam_advance_clip_kernel, dim3(1), dim3(64), 0, s, state, clip, cfg->beta1, cfg->beta2, lr);
+        else hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, s, state, cfg->beta1, cfg->beta2, lr);
         HIP_TRY(hipGetLastError());
     }
     if (grid == 0) return F110_OK;
-    if (target) hipLaunchKernelGGL((adam_kernel<true, true>), dim3(grid), dim3(AD_THREADS), 0, s, tab, (const AdamState *)state);
-    else hipLaunchKernelGGL((adam_kernel<true, false>), dim3(grid), dim3(AD_THREADS), 0, s, tab, (const AdamState *)state);
+    if (clipped) {
+        if (target) hipLaunchKernelGGL((adam_clipped_kernel<true>), dim3(grid), dim3(AD_THREADS), 0, s, tab, (const AdamState *)state, clip);
+        else hipLaunchKernelGGL((adam_clipped_kernel<false>), dim3(grid), dim3(AD_THREADS), 0, s, tab, (const AdamState *)state, clip);
+    } else {
+        if (target) hipLaunchKernelGGL((adam_kernel<true, true>), dim3(grid), dim3(AD_THREADS), 0, s, tab, (const AdamState *)state);
+        else hipLaunchKernelGGL((adam_kernel<true, false>), dim3(grid), dim3(AD_THREADS), 0, s, tab, (const AdamState *)state);
+    }
     HIP_TRY(hipGetLastError());
     return F110_OK;
+}
+
+extern "C" int f110_adam_step(const f110_adam_config *cfg, const f110_adam_tensor *table, int32_t n_tensors, f110_adam_state *state, double lr,
+                              void *stream)
+{
+    return adam_step("f110_adam_step", cfg, table, n_tensors, state, nullptr, false, lr, stream);
 }
 
 extern "C" int f110_soft_update(const f110_adam_tensor *table, int32_t n_tensors, double tau, void *stream)
@@ -288,6 +304,55 @@ extern "C" int f110_soft_update(const f110_adam_tensor *table, int32_t n_tensors
     hipLaunchKernelGGL((adam_kernel<false, true>), dim3(grid), dim3(AD_THREADS), 0, (hipStream_t)stream, tab, (const AdamState *)nullptr);
     HIP_TRY(hipGetLastError());
     return F110_OK;
+}
+
+// ---------------------------------------------------------------- gradient clipping: the global norm, the coefficient, the guard
+extern "C" int64_t f110_adam_clip_state_bytes(void) { return (int64_t)sizeof(f110_adam_clip_state); }
+
+extern "C" int f110_adam_gradnorm(const f110_adam_tensor *table, int32_t n_tensors, int64_t chunk_base, double *partials, int64_t partials_len,
+                                  void *stream)
+{
+    const char *who = "f110_adam_gradnorm";
+    if (int rc = adam_gradnorm_check(who, chunk_base, partials, partials_len, -1)) return rc;
+    if (n_tensors < 0 || n_tensors > AD_MAX_T) return fail(F110_E_INVALID, "%s: n_tensors %d (0..%d a call)", who, n_tensors, AD_MAX_T);
+    if (n_tensors > 0 && !table) return fail(F110_E_INVALID, "%s: null table", who);
+    AdamTable tab;
+    memset(&tab, 0, sizeof(tab));
+    tab.n_tensors = n_tensors;
+    int64_t chunks = 0;
+    for (int i = 0; i < n_tensors; i++) {
+        const f110_adam_tensor &t = table[i];
+        if (t.n < 0 || t.n > ((int64_t)1 << 31)) return fail(F110_E_INVALID, "%s: tensor %d: n %lld (0..2^31)", who, i, (long long)t.n);
+        if (t.n > 0) {
+            if (!t.g) return fail(F110_E_INVALID, "%s: tensor %d: null g", who, i);
+            if ((uintptr_t)t.g % 4) return fail(F110_E_INVALID, "%s: tensor %d: g is not 4-byte aligned", who, i);
+            tab.t[i].g = t.g; tab.t[i].n = (uint32_t)t.n; tab.t[i].vec = (uintptr_t)t.g % 16 == 0;
+            chunks += adam_chunks(t.n);
+        }
+        tab.chunk_end[i] = (uint32_t)chunks;
+    }
+    if (int rc = adam_gradnorm_check(who, chunk_base, partials, partials_len, chunks)) return rc;
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, {{"partials", partials}})) return rc;
+    if (chunks == 0) return F110_OK;
+    hipLaunchKernelGGL(adam_gradnorm_kernel, dim3((uint32_t)chunks), dim3(AC_THREADS), 0, (hipStream_t)stream, tab, partials + chunk_base);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_adam_clip(const double *partials, int64_t n_chunks, double max_norm, f110_adam_clip_state *clip, void *stream)
+{
+    const char *who = "f110_adam_clip";
+    if (int rc = adam_clip_check(who, partials, n_chunks, max_norm, clip)) return rc;
+    if (int rc = check_device_pointers(who, (hipStream_t)stream, {{"partials", partials}, {"clip", clip}})) return rc;
+    hipLaunchKernelGGL(adam_clip_kernel, dim3(1), dim3(AC_THREADS), 0, (hipStream_t)stream, partials, (long long)n_chunks, max_norm, clip);
+    HIP_TRY(hipGetLastError());
+    return F110_OK;
+}
+
+extern "C" int f110_adam_step_clipped(const f110_adam_config *cfg, const f110_adam_tensor *table, int32_t n_tensors, f110_adam_state *state,
+                                      const f110_adam_clip_state *clip, double lr, void *stream)
+{
+    return adam_step("f110_adam_step_clipped", cfg, table, n_tensors, state, clip, true, lr, stream);
 }
 
 // ---------------------------------------------------------------- the two losses of a SAC update and their gradients

@@ -105,9 +105,18 @@ class SacAdam:
     launch in front of each step, so a step captured in a torch.cuda.graph replays; `lr` is a host scalar of each launch, settable
     between eager steps and frozen in a captured one.
     ValueError for non-fp32, non-contiguous, CPU, mixed-device or aliased tensors, a targets list of another length or other shapes,
-    and for what f110_adam_validate refuses (betas outside [0, 1), eps <= 0, tau outside [0, 1])."""
+    and for what f110_adam_validate refuses (betas outside [0, 1), eps <= 0, tau outside [0, 1]).
+    max_grad_norm: None -- every launch as above, nothing of what follows exists.  A positive float or float('inf'): each step first
+    forms the global L2 norm of all the .grad tensors on the device (f110_adam_gradnorm, f110_adam_clip: fp64, a fixed order; the
+    contract "Gradient clipping" of include/f110_hip.h), then steps with g * coef, coef = min(1, max_grad_norm / (norm + 1e-6)) as
+    torch.nn.utils.clip_grad_norm_ forms it, and SKIPS the step when the norm is inf or NaN: parameters, moments and the step counter
+    keep their bits, the targets still move.  float('inf') is the guard alone.  Two launches more per 64 tensors.  Unlike torch's
+    function this does NOT write the scaled gradient back to .grad.  max_grad_norm is a host scalar of the launch like lr: settable
+    between eager steps, frozen under capture.  clip_state: an int64 [8] device tensor that then holds the f110_adam_clip_state
+    (None: the optimizer allocates one); clip_stats() reads it.  max_grad_norm and the counters are configuration and diagnostics,
+    not state: state_dict() and load_state_dict() do not know them."""
 
-    def __init__(self, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, targets=None, tau=0.005):
+    def __init__(self, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, targets=None, tau=0.005, max_grad_norm=None, clip_state=None):
         who = 'SacAdam'
         self.params = _tensor_list(who, 'params', params)
         dev = _check(who, 'params', self.params)
@@ -136,6 +145,46 @@ class SacAdam:
         assert _lib.load().f110_adam_state_bytes() == _lib.F110_ADAM_STATE_BYTES
         self._state = torch.zeros((_lib.F110_ADAM_STATE_BYTES // 8,), dtype=torch.int64, device=dev)   # f110_adam_state
         self._set_state(0)
+        self._max_grad_norm, self._partials, self._clip = None, None, None
+        if max_grad_norm is None:
+            if clip_state is not None:
+                raise ValueError('%s: clip_state without max_grad_norm' % who)
+            return
+        self._max_grad_norm = self._checked_norm(max_grad_norm)
+        assert _lib.load().f110_adam_clip_state_bytes() == _lib.F110_ADAM_CLIP_STATE_BYTES == C.sizeof(_lib.AdamClipState)
+        words = _lib.F110_ADAM_CLIP_STATE_BYTES // 8
+        if clip_state is None:
+            clip_state = torch.zeros((words,), dtype=torch.int64, device=dev)
+        elif (not torch.is_tensor(clip_state) or clip_state.dtype != torch.int64 or tuple(clip_state.shape) != (words,)
+              or clip_state.device != dev or not clip_state.is_contiguous()):
+            raise ValueError('%s: clip_state must be a contiguous int64 [%d] tensor on %s' % (who, words, dev))
+        self._clip = clip_state                                        # f110_adam_clip_state
+        self._partials = torch.zeros((max(1, sum((p.numel() + CHUNK - 1) // CHUNK for p in self.params)),), dtype=torch.float64, device=dev)
+
+    # ---- gradient clipping
+    @staticmethod
+    def _checked_norm(value):
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or math.isnan(value) or not value > 0:
+            raise ValueError('SacAdam: max_grad_norm %r: a positive number or float(\'inf\')' % (value,))
+        return float(value)
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        if self._clip is None or value is None:
+            raise ValueError('SacAdam: max_grad_norm is switched on or off at construction only (it owns device buffers); its value may change')
+        self._max_grad_norm = self._checked_norm(value)
+
+    def clip_stats(self):
+        """(norm, coef, skip, steps_clipped, steps_skipped) of the last step as the device holds them (synchronises): the twin of
+        device_state().  norm is inf on a skipped step.  ValueError without max_grad_norm."""
+        if self._clip is None:
+            raise ValueError('SacAdam.clip_stats: the optimizer was built without max_grad_norm')
+        host = _lib.AdamClipState.from_buffer_copy(self._clip.cpu().numpy().tobytes())
+        return float(host.norm), float(host.coef), bool(host.skip), int(host.steps_clipped), int(host.steps_skipped)
 
     # ---- the device state
     def _set_state(self, t):
@@ -169,7 +218,9 @@ class SacAdam:
     def step(self):
         """One Adam step of every parameter that has a .grad, from the .grad tensors as they are now (autograd may have put them
         anywhere), and the soft update of every target.  A parameter whose .grad is None is left untouched, with its moments; its
-        target is still moved.  Launches on the current stream: one state advance, one update kernel per 64 tensors."""
+        target is still moved.  Launches on the current stream: one state advance, one update kernel per 64 tensors; with
+        max_grad_norm in front of them one norm kernel per 64 tensors and the one-workgroup clip kernel.  When no parameter has a
+        .grad nothing of the step is launched and the clip state is left alone."""
         who = 'SacAdam.step'
         lib, dev = _lib.load(), self.device
         m0, v0 = self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
@@ -188,9 +239,18 @@ class SacAdam:
         with torch.cuda.device(dev):
             stream = _lib.stream(dev)
             first = True
+            if self._clip is not None and with_grad:
+                partials, base = self._partials.data_ptr(), 0
+                for table, n in _launches(with_grad):                  # chunks numbered over the whole step, across calls
+                    _lib.check(lib.f110_adam_gradnorm(table, n, base, partials, self._partials.numel(), stream))
+                    base += sum((e.n + CHUNK - 1) // CHUNK for e in table)
+                _lib.check(lib.f110_adam_clip(partials, base, self._max_grad_norm, self._clip.data_ptr(), stream))
             for table, n in _launches(with_grad):
                 cfg = self._config(first)                              # the first launch of the step advances the state
-                _lib.check(lib.f110_adam_step(C.byref(cfg), table, n, self._state.data_ptr(), self.lr, stream))
+                if self._clip is None:
+                    _lib.check(lib.f110_adam_step(C.byref(cfg), table, n, self._state.data_ptr(), self.lr, stream))
+                else:
+                    _lib.check(lib.f110_adam_step_clipped(C.byref(cfg), table, n, self._state.data_ptr(), self._clip.data_ptr(), self.lr, stream))
                 first = False
         if without:
             _soft_update(dev, without, self.tau)

@@ -119,12 +119,21 @@ class SACAgent:
     update_graph draw with stack=k, update_batch takes 's_idx' / 'ns_idx' as [n, k], and act_from acts on the ring's newest stacks.
     Shared networks must have a conv1 of k input channels (ValueError otherwise).  stack is configuration, not state.  With stack = 1
     nothing changes: the same launches, graph key and bits.
+    max_grad_norm: None, or a positive number or float('inf') that every one of the three SacAdam takes as its max_grad_norm: each
+    optimizer clips the global L2 norm of ITS network's gradients on the device, as torch.nn.utils.clip_grad_norm_(net.parameters(),
+    max_grad_norm) per network would, and skips its step when that norm is inf or NaN (parameters, moments and step counter keep
+    their bits; a critic's target still moves).  float('inf') is the guard alone.  .grad is not rewritten.  The three clip states are
+    the rows (actor, critic1, critic2) of ONE [3, 8] int64 tensor `clip_states`; grad_stats() returns views of it, nothing
+    synchronises, and a replayed graph leaves fresh values there.  The Temperature's one-parameter step is NOT clipped or guarded.
+    max_grad_norm is configuration, not state: state_dict() does not hold it, nor the counters.  It may be changed (not switched on
+    or off) after construction; a captured update is then captured again.  With None nothing changes: the same launches, graph key
+    and bits.
     Attributes: actor, critics [2], targets [2]; actor_opt, critic_opts [2] (SacAdam; a critic's also moves its target); draws, the [1]
     int64 draw counter on the device; sample, the tensors of the batch the last update drew (sample['indices'] names the transitions)."""
 
     def __init__(self, action_dim=16, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, rows=256, cols=256, hidden=512,
                  on=255.0, device='cuda', networks=None, target_entropy=None, alpha_lr=3e-4, init_alpha=0.2, draws='torch', seed=0, nstep=1,
-                 per=False, stack=1):
+                 per=False, stack=1, max_grad_norm=None):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ValueError('SACAgent: device %s: there is no CPU path' % (self.device,))
@@ -171,8 +180,13 @@ class SACAgent:
         for p in self.modules()['actor'].parameters():
             if p.device != self.device:
                 raise ValueError('SACAgent: the networks are on %s, not on %s' % (p.device, self.device))
-        self.actor_opt = SacAdam(self.actor, lr=actor_lr)
-        self.critic_opts = [SacAdam(c, lr=critic_lr, targets=t, tau=self.tau) for c, t in zip(self.critics, self.targets)]
+        self.clip_states = None
+        clip = [{}, {}, {}]
+        if max_grad_norm is not None:
+            self.clip_states = torch.zeros((len(OPTIMIZERS), 8), dtype=torch.int64, device=self.device)       # f110_adam_clip_state each
+            clip = [dict(max_grad_norm=max_grad_norm, clip_state=row) for row in self.clip_states]
+        self.actor_opt = SacAdam(self.actor, lr=actor_lr, **clip[0])
+        self.critic_opts = [SacAdam(c, lr=critic_lr, targets=t, tau=self.tau, **kw) for c, t, kw in zip(self.critics, self.targets, clip[1:])]
         self.draws = torch.zeros((1,), dtype=torch.int64, device=self.device)
         self.sample = None
         # the captured update
@@ -190,6 +204,25 @@ class SACAgent:
     def zero_grad(self, set_to_none=True):
         for opt in self.optimizers().values():
             opt.zero_grad(set_to_none)
+
+    @property
+    def max_grad_norm(self):
+        return self.actor_opt.max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        for opt in self.optimizers().values():
+            opt.max_grad_norm = value
+
+    def grad_stats(self):
+        """The last update's clipping per network (rows: actor, critic1, critic2) as views of `clip_states`, on the device, without a
+        synchronisation: 'sumsq' and 'norm' [3] fp64 (inf on a skipped step), 'coef' [3] fp32, 'skip' [3] int32, 'steps_clipped' and
+        'steps_skipped' [3] int64.  ValueError without max_grad_norm."""
+        if self.clip_states is None:
+            raise ValueError('SACAgent: the agent was built without max_grad_norm')
+        s = self.clip_states
+        f64, f32, i32 = s.view(torch.float64), s.view(torch.float32), s.view(torch.int32)
+        return dict(sumsq=f64[:, 0], norm=f64[:, 1], coef=f32[:, 4], skip=i32[:, 5], steps_clipped=s[:, 3], steps_skipped=s[:, 4])
 
     # ---- acting
     def select_action(self, frames, index=None, evaluate=False, out=None, eps=None):
@@ -348,6 +381,7 @@ class SACAgent:
         key = key if t is None else key + ((t.lr, t.betas, t.eps, t.target_entropy),)
         key = key if self.nstep == 1 else key + (('nstep', self.nstep, self.gamma),)
         key = key if self.stack == 1 else key + (('stack', self.stack),)
+        key = key if self.clip_states is None else key + (('max_grad_norm', self.max_grad_norm),)
         if self.per:                                # (a ring that lost its priorities: another key, and the capture refuses it)
             p = replay.priorities
             key = key + (('per', self.gamma) + ((None,) if p is None else (p.leaf.data_ptr(), p.state.data_ptr())),)
