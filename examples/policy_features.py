@@ -49,7 +49,8 @@ for k in range(STEPS):
     obs, reward, done, info = env.step(env.path_actions(raw))
 print('acting: lidar_bitmap %s %s -> features %s %s' % (tuple(info['lidar_bitmap'].shape), info['lidar_bitmap'].dtype, tuple(feats.shape), feats.dtype))
 n = 64
-frames, s_idx, ns_idx, a, r, d, ok = env.replay.sample_frames(n)
+batch = env.replay.sample_frames(n)
+frames, s_idx, ns_idx, r, ok = (batch[k] for k in ('frames', 's_idx', 'ns_idx', 'r', 'ok'))
 f_s, f_ns = learn_layer(frames, index=s_idx), learn_layer(frames, index=ns_idx)
 loss = ((f_s.mean(dim=(1, 2, 3)) - r.float()) ** 2).mean() + f_ns.mean()
 loss.backward()

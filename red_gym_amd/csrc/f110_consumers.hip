@@ -829,6 +829,22 @@ static int replay_nstep_scalars(const char *who, int32_t n, int32_t nstep, doubl
     return F110_OK;
 }
 
+// The sample form of ReplayNstepArgs (its ring is the caller's): the scalars and pointers checked, then filled in.  What
+// f110_replay_sample_nstep and f110_priority_sample share.
+static int replay_sample_nstep_args(const char *who, ReplayNstepArgs &a, uint64_t seed, uint64_t *counter, int32_t n, int32_t nstep, double gamma,
+                                    int64_t *indices, int64_t *s_frame, int64_t *ns_frame, float *a_out, double *ret, uint8_t *d_out, uint8_t *ok,
+                                    double *discount, int32_t *span)
+{
+    if (int rc = replay_nstep_scalars(who, n, nstep, gamma)) return rc;
+    if (!counter || !indices || !s_frame || !ns_frame || !a_out || !ret || !d_out || !ok || !discount || !span)
+        return fail(F110_E_INVALID, "%s: null argument", who);
+    if ((uintptr_t)counter % 8) return fail(F110_E_INVALID, "%s: the counter is not 8-byte aligned", who);
+    a.seed = seed; a.counter = (const unsigned long long *)counter; a.n = n; a.nstep = nstep; a.gamma = gamma;
+    a.idx = (long long *)indices; a.s_frame = (long long *)s_frame; a.ns_frame = (long long *)ns_frame;
+    a.a = a_out; a.ret = ret; a.d = d_out; a.ok = ok; a.discount = discount; a.span = span;
+    return F110_OK;
+}
+
 extern "C" int f110_replay_nstep(f110_handle *h, const int64_t *indices, int32_t n, int32_t nstep, double gamma, int64_t *ns_frame, double *ret,
                                  uint8_t *d_out, double *discount, int32_t *span, void *stream)
 {
@@ -856,14 +872,8 @@ extern "C" int f110_replay_sample_nstep(f110_handle *h, uint64_t seed, uint64_t 
     ReplayNstepArgs a;
     memset(&a, 0, sizeof(a));
     if (int rc = replay_ready(h, who, a.ring)) return rc;
-    if (int rc = replay_nstep_scalars(who, n, nstep, gamma)) return rc;
-    if (!counter || !indices || !s_frame || !ns_frame || !a_out || !ret || !d_out || !ok || !discount || !span)
-        return fail(F110_E_INVALID, "%s: null argument", who);
-    if ((uintptr_t)counter % 8) return fail(F110_E_INVALID, "%s: the counter is not 8-byte aligned", who);
+    if (int rc = replay_sample_nstep_args(who, a, seed, counter, n, nstep, gamma, indices, s_frame, ns_frame, a_out, ret, d_out, ok, discount, span)) return rc;
     if (n == 0) return F110_OK;
-    a.seed = seed; a.counter = (const unsigned long long *)counter; a.n = n; a.nstep = nstep; a.gamma = gamma;
-    a.idx = (long long *)indices; a.s_frame = (long long *)s_frame; a.ns_frame = (long long *)ns_frame;
-    a.a = a_out; a.ret = ret; a.d = d_out; a.ok = ok; a.discount = discount; a.span = span;
     hipLaunchKernelGGL(replay_sample_nstep_kernel, dim3((unsigned)((n + REPLAY_THREADS - 1) / REPLAY_THREADS)), dim3(REPLAY_THREADS), 0, (hipStream_t)stream,
                        a);
     HIP_TRY(hipGetLastError());
@@ -1054,15 +1064,9 @@ extern "C" int f110_priority_sample(f110_handle *h, uint64_t seed, uint64_t *cou
     PrioritySampleArgs p;
     memset(&p, 0, sizeof(p));
     if (int rc = priority_ready(h, who, p.s.ring, p.tree)) return rc;
-    if (int rc = replay_nstep_scalars(who, n, nstep, gamma)) return rc;
-    if (!counter || !indices || !s_frame || !ns_frame || !a_out || !ret || !d_out || !ok || !discount || !span || !prio || !weight)
-        return fail(F110_E_INVALID, "%s: null argument", who);
-    if ((uintptr_t)counter % 8) return fail(F110_E_INVALID, "%s: the counter is not 8-byte aligned", who);
+    if (!prio || !weight) return fail(F110_E_INVALID, "%s: null argument", who);
+    if (int rc = replay_sample_nstep_args(who, p.s, seed, counter, n, nstep, gamma, indices, s_frame, ns_frame, a_out, ret, d_out, ok, discount, span)) return rc;
     if (n == 0) return F110_OK;
-    ReplayNstepArgs &a = p.s;
-    a.seed = seed; a.counter = (const unsigned long long *)counter; a.n = n; a.nstep = nstep; a.gamma = gamma;
-    a.idx = (long long *)indices; a.s_frame = (long long *)s_frame; a.ns_frame = (long long *)ns_frame;
-    a.a = a_out; a.ret = ret; a.d = d_out; a.ok = ok; a.discount = discount; a.span = span;
     p.prio = prio;
     const int per = PT_THREADS / 64;
     hipLaunchKernelGGL(priority_sample_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(PT_THREADS), 0, (hipStream_t)stream, p);

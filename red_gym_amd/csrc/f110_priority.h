@@ -270,19 +270,10 @@ static __global__ __launch_bounds__(PT_THREADS) void priority_sample_kernel(Prio
         a.a[(size_t)i * (size_t)g.action_dim + (size_t)k] = ok ? g.actions[(size_t)id * (size_t)g.action_dim + (size_t)k] : 0.0f;
     if (lane != 0) return;
     a.idx[i] = id;
-    a.s_frame[i] = ok ? ((c - 1) % (g.steps + 1)) * g.n_envs + env : -1;
+    a.s_frame[i] = replay_frame_before(g, ok, c, env);
     a.ok[i] = ok ? 1 : 0;
     p.prio[i] = q;
-    long long ns_frame;
-    double ret, discount;
-    uint8_t d;
-    int span;
-    replay_walk(g, ok, c, env, a.nstep, a.gamma, ns_frame, ret, discount, d, span);
-    a.ns_frame[i] = ns_frame;
-    a.ret[i] = ret;
-    a.discount[i] = discount;
-    a.d[i] = d;
-    a.span[i] = span;
+    replay_walk_store(a, i, ok, c, env);
 }
 
 struct PriorityWeightArgs {

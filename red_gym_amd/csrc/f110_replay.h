@@ -332,6 +332,13 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_gather_kernel(Re
     }
 }
 
+// The row of the frame tensor viewed as [(steps + 1) * n_envs, rows, words] that holds the frame before push `c` of `env`, as
+// replay_resolve gave them; -1 for a refused transition.
+__device__ inline long long replay_frame_before(const ReplayRing &g, bool ok, long long c, int env)
+{
+    return ok ? ((c - 1) % (g.steps + 1)) * g.n_envs + env : -1;
+}
+
 // one lane per index: the rows of the frame tensor viewed as [(steps + 1) * n_envs, rows, words] that hold the transition's frame
 // before and its frame after, -1 for both where the gather would write zeros
 static __global__ __launch_bounds__(REPLAY_THREADS) void replay_locate_kernel(ReplayRing g, const long long *idx, int n, long long *s_frame, long long *ns_frame)
@@ -341,7 +348,7 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_locate_kernel(Re
     long long c = 0;
     int env = 0;
     const bool ok = replay_resolve(g, idx[i], c, env);
-    s_frame[i] = ok ? ((c - 1) % (g.steps + 1)) * g.n_envs + env : -1;
+    s_frame[i] = replay_frame_before(g, ok, c, env);
     ns_frame[i] = ok ? (c % (g.steps + 1)) * g.n_envs + env : -1;
 }
 
@@ -360,7 +367,7 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_sample_kernel(Re
     const bool ok = replay_resolve(g, id, c, env);
     F110_BCHK(!ok || (id >= 0 && id < g.steps * g.n_envs), BT_REPLAY, g.dev_err);
     a.idx[i] = id;
-    a.s_frame[i] = ok ? ((c - 1) % (g.steps + 1)) * g.n_envs + env : -1;
+    a.s_frame[i] = replay_frame_before(g, ok, c, env);
     a.ns_frame[i] = ok ? (c % (g.steps + 1)) * g.n_envs + env : -1;
     for (int k = 0; k < g.action_dim; k++)
         a.a[(size_t)i * (size_t)g.action_dim + (size_t)k] = ok ? g.actions[(size_t)id * (size_t)g.action_dim + (size_t)k] : 0.0f;
@@ -413,6 +420,21 @@ __device__ inline void replay_walk(const ReplayRing &g, bool ok, long long c0, i
     span = m;
 }
 
+// The walk from (ok, push c, env), stored as row i: what every kernel with the walk ends in.
+__device__ inline void replay_walk_store(const ReplayNstepArgs &a, int i, bool ok, long long c, int env)
+{
+    long long ns_frame;
+    double ret, discount;
+    uint8_t d;
+    int span;
+    replay_walk(a.ring, ok, c, env, a.nstep, a.gamma, ns_frame, ret, discount, d, span);
+    a.ns_frame[i] = ns_frame;
+    a.ret[i] = ret;
+    a.discount[i] = discount;
+    a.d[i] = d;
+    a.span[i] = span;
+}
+
 // one lane per index: the walk from the transition the caller names
 static __global__ __launch_bounds__(REPLAY_THREADS) void replay_nstep_kernel(ReplayNstepArgs a)
 {
@@ -422,16 +444,7 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_nstep_kernel(Rep
     long long c = 0;
     int env = 0;
     const bool ok = replay_resolve(g, a.idx_in[i], c, env);
-    long long ns_frame;
-    double ret, discount;
-    uint8_t d;
-    int span;
-    replay_walk(g, ok, c, env, a.nstep, a.gamma, ns_frame, ret, discount, d, span);
-    a.ns_frame[i] = ns_frame;
-    a.ret[i] = ret;
-    a.discount[i] = discount;
-    a.d[i] = d;
-    a.span[i] = span;
+    replay_walk_store(a, i, ok, c, env);
 }
 
 // one lane per draw: replay_sample_kernel's draw, frame before and action, then the walk for the frame after, the return, done, the
@@ -448,20 +461,11 @@ static __global__ __launch_bounds__(REPLAY_THREADS) void replay_sample_nstep_ker
     const bool ok = replay_resolve(g, id, c, env);
     F110_BCHK(!ok || (id >= 0 && id < g.steps * g.n_envs), BT_REPLAY, g.dev_err);
     a.idx[i] = id;
-    a.s_frame[i] = ok ? ((c - 1) % (g.steps + 1)) * g.n_envs + env : -1;
+    a.s_frame[i] = replay_frame_before(g, ok, c, env);
     for (int k = 0; k < g.action_dim; k++)
         a.a[(size_t)i * (size_t)g.action_dim + (size_t)k] = ok ? g.actions[(size_t)id * (size_t)g.action_dim + (size_t)k] : 0.0f;
     a.ok[i] = ok ? 1 : 0;
-    long long ns_frame;
-    double ret, discount;
-    uint8_t d;
-    int span;
-    replay_walk(g, ok, c, env, a.nstep, a.gamma, ns_frame, ret, discount, d, span);
-    a.ns_frame[i] = ns_frame;
-    a.ret[i] = ret;
-    a.discount[i] = discount;
-    a.d[i] = d;
-    a.span[i] = span;
+    replay_walk_store(a, i, ok, c, env);
 }
 
 struct ReplayStackArgs {

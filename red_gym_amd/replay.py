@@ -73,6 +73,35 @@ def unpack_bitmaps(packed, cols):
     return out
 
 
+def sample_fields(n, action_dim, nstep=1, priorities=False, stack=1):
+    """THE FIELD TABLE of a batch of n transitions: name -> (shape, dtype).  frames_at, sample_frames, sample_frames_dev and
+    sample_priority_dev return a dict of these fields plus 'frames' (ReplayBuffer.frame_view()); sample_out allocates them, and the
+    device entries' `out` takes them.  A pure function: no ring, no device.
+      indices [n] int64         the transitions (step slot * B + env; -1: none was found)
+      s_idx, ns_idx [n] int64   rows of 'frames' that hold the frame before and the frame after (-1 for both: a zero transition)
+      a [n, action_dim] fp32, r [n] fp64, d [n] uint8, ok [n] uint8    as sample_at returns them
+    with nstep > 1, and always from the priority draw (r is then the n-step return, ns_idx and d those of the span's end):
+      discount [n] fp64, span [n] int32      as nstep_at returns them
+    from the priority draw only:
+      prio [n] int32            the bits of the drawn uint32 priority words
+      weight [n] fp32           the importance weights (N P(i))^-beta over the batch's maximum, 0 where ok is 0
+    with stack > 1 (s_idx and ns_idx stay [n]: they are column 0 of the stacks):
+      s_stack, ns_stack [n, stack] int64     stack_rows of s_idx and of ns_idx
+      depth [2, n] int32        of s_idx, of ns_idx
+      pair [2, n], stacks [2, n, stack] int64    storage: s_idx / ns_idx and s_stack / ns_stack are their halves, so that one
+                                launch of the walk serves both"""
+    shapes = {'indices': ((n,), torch.int64), 's_idx': ((n,), torch.int64), 'ns_idx': ((n,), torch.int64),
+              'a': ((n, action_dim), torch.float32), 'r': ((n,), torch.float64), 'd': ((n,), torch.uint8), 'ok': ((n,), torch.uint8)}
+    if nstep > 1 or priorities:
+        shapes.update({'discount': ((n,), torch.float64), 'span': ((n,), torch.int32)})
+    if priorities:
+        shapes.update({'prio': ((n,), torch.int32), 'weight': ((n,), torch.float32)})
+    if stack > 1:
+        shapes.update({'pair': ((2, n), torch.int64), 'stacks': ((2, n, stack), torch.int64), 's_stack': ((n, stack), torch.int64),
+                       'ns_stack': ((n, stack), torch.int64), 'depth': ((2, n), torch.int32)})
+    return shapes
+
+
 class ReplayBuffer(Consumer):
     """The replay buffer of one Engine (f110_replay_install / _bind / _update / _draw / _gather / _locate / _sample / _nstep / _sample_nstep / _stack).  The ring lives in `buf`:
     frames [T + 1, B, rows, words] int64 (bit-packed), actions [T, B, action_dim] fp32, rewards [T, B] fp64, dones and valid
@@ -127,8 +156,7 @@ class ReplayBuffer(Consumer):
     def set_priorities(self, priorities):
         """Switches prioritized replay on over the ring as it stands (True or a dict of red_gym_amd.priority.DEFAULTS' keys: every valid
         transition enters with the word of priority 1.0), or off (None or False: no launch remains)."""
-        if not self.on:
-            raise ValueError('replay: the buffer is off (record_replay())')
+        self._require_on()
         if self.priorities is not None:
             self.priorities.remove()
             self.priorities = None
@@ -166,6 +194,16 @@ class ReplayBuffer(Consumer):
         """Valid transitions held (one small reduction and one synchronisation: not for the step path)."""
         return int(self.buf['valid'].sum().item()) if self.on else 0
 
+    def _require_on(self, priorities=False):
+        if priorities and (not self.on or self.priorities is None):
+            raise ValueError('replay: priorities are off (record_replay(..., priorities=True))')
+        if not self.on:
+            raise ValueError('replay: the buffer is off (record_replay())')
+
+    def _indices(self, x):
+        """Indices or frame rows as the kernels read them: [n] int64, contiguous, on the env's device."""
+        return torch.as_tensor(x).to(device=self.eng.device, dtype=torch.int64).contiguous().reshape(-1)
+
     def _seed(self, seed):
         if seed is None:
             seed = self.eng.seed
@@ -188,12 +226,11 @@ class ReplayBuffer(Consumer):
         """f110_replay_gather for the transitions `indices` [n] (step slot * B + env; -1 or an invalid one: zeros and ok = 0).
         Returns (s, a, r, ns, d, ok): s and ns uint8 [n, rows, cols], or with dtype=torch.float32 fp32 [n, 1, rows, cols] =
         pixel * scale; a [n, action_dim] fp32, r [n] fp64, d [n] and ok [n] uint8.  Device tensors, no synchronisation."""
-        if not self.on:
-            raise ValueError('replay: the buffer is off (record_replay())')
+        self._require_on()
         if dtype not in (torch.uint8, torch.float32):
             raise ValueError('replay: dtype must be torch.uint8 or torch.float32')
         eng = self.eng
-        idx = torch.as_tensor(indices).to(device=eng.device, dtype=torch.int64).contiguous().reshape(-1)
+        idx = self._indices(indices)
         n = idx.shape[0]
         f32 = dtype == torch.float32
         shape = (n, 1, self.rows, self.cols) if f32 else (n, self.rows, self.cols)
@@ -211,8 +248,7 @@ class ReplayBuffer(Consumer):
         """batch_size transitions drawn uniformly over the valid ones, as sample_at returns them.  `seed` defaults to the
         env's; the host keeps the draw counter, so two calls never reuse draws.  A draw that found no valid transition in TRIES
         attempts (an empty buffer is one case) has ok = 0 and zeros."""
-        if not self.on:
-            raise ValueError('replay: the buffer is off (record_replay())')
+        self._require_on()
         idx, _ = self.draw(batch_size, seed)
         return self.sample_at(idx, dtype, scale)
 
@@ -237,11 +273,10 @@ class ReplayBuffer(Consumer):
         the done of its last step, discount [n] fp64 = gamma^span by running products (what the bootstrap is multiplied with) and
         span [n] int32, at most nstep: a span ends behind a terminal step, in front of an invalid transition and at the newest push.
         -1, 0, 0, gamma, 0 where frames_at gives a zero transition.  Device tensors, no synchronisation."""
-        if not self.on:
-            raise ValueError('replay: the buffer is off (record_replay())')
+        self._require_on()
         nstep, gamma = self._nstep(nstep, gamma)
         eng = self.eng
-        idx = torch.as_tensor(indices).to(device=eng.device, dtype=torch.int64).contiguous().reshape(-1)
+        idx = self._indices(indices)
         n = idx.shape[0]
         ns_idx = torch.empty((n,), dtype=torch.int64, device=eng.device)
         ret, discount = torch.empty((n,), dtype=torch.float64, device=eng.device), torch.empty((n,), dtype=torch.float64, device=eng.device)
@@ -272,11 +307,10 @@ class ReplayBuffer(Consumer):
         distinct frames, 1 .. stack.  -1 in every column and depth 0 for a row outside the tensor (-1) or one no push has written.
         A stack at learning time can be shorter than the one the policy acted on, for the stack - 1 oldest pushes of the ring only
         (their predecessors are overwritten); depth shows it.  Device tensors, no synchronisation; stack in 1 .. MAX_STACK."""
-        if not self.on:
-            raise ValueError('replay: the buffer is off (record_replay())')
+        self._require_on()
         stack = self._stack(stack)
         eng = self.eng
-        r = torch.as_tensor(rows).to(device=eng.device, dtype=torch.int64).contiguous().reshape(-1)
+        r = self._indices(rows)
         n = r.shape[0]
         out = torch.empty((n, stack), dtype=torch.int64, device=eng.device)
         depth = torch.empty((n,), dtype=torch.int32, device=eng.device)
@@ -289,8 +323,7 @@ class ReplayBuffer(Consumer):
         """f110_replay_stack's latest mode: stack_rows of every env's newest frame (the bitmap its last step returned), [B, stack]
         int64 and depth [B] int32 -- the stack a policy acts on.  Nothing crosses from the host that changes from call to call, so
         a captured call follows the ring.  An empty ring gives -1 and depth 0.  out: (stack_rows, depth) tensors to write into."""
-        if not self.on:
-            raise ValueError('replay: the buffer is off (record_replay())')
+        self._require_on()
         stack = self._stack(stack)
         eng, B = self.eng, self.eng.B
         if out is None:
@@ -307,65 +340,80 @@ class ReplayBuffer(Consumer):
         stack_latest point into (a view, no copy: it changes with the next push)."""
         return self.buf['frames'].view((self.cfg.steps + 1) * self.eng.B, self.rows, words(self.cols))
 
-    def _stacked(self, res, stack, o=None):
-        """`res` (a tuple whose positions 1 and 2 are s_idx and ns_idx [n]) with those two replaced by their [n, stack] stacks.  The
-        two are walked in one launch where they are the halves of one tensor (o['pair'], sample_out(stack=k)); -> (tuple, depth
-        [2, n] int32: of s_idx, of ns_idx)."""
-        n = int(res[1].shape[0])
-        if o is not None:
-            pair, both, depth = o['pair'], o['stacks'], o['depth']
-        else:
-            pair = torch.stack((res[1], res[2]))
-            both = torch.empty((2, n, stack), dtype=torch.int64, device=pair.device)
-            depth = torch.empty((2, n), dtype=torch.int32, device=pair.device)
-            self._keep_pair = pair
+    def _stacked(self, b, stack):
+        """The one launch of the walk over b['pair'] (s_idx above ns_idx) into b['stacks'] and b['depth']."""
+        n = int(b['pair'].shape[1])
         if n:
-            self._walk_back(pair, 2 * n, stack, both, depth)
-        return (res[0], both[0], both[1]) + tuple(res[3:]), depth
+            self._walk_back(b['pair'], 2 * n, stack, b['stacks'], b['depth'])
 
     def frames_at(self, indices, nstep=1, gamma=None, stack=1):
         """The transitions `indices` [n] without unpacking an image, for consumers that read bits (red_gym_amd.bitconv).
-        Returns (frames, s_idx, ns_idx, a, r, d, ok): frames is the ring's frame tensor viewed as [(T + 1) * B, rows, words]
-        int64 (a view, no copy: it changes with the next push), s_idx and ns_idx [n] int64 its rows that hold the frame before
-        and the frame after (f110_replay_locate; -1 for both where sample_at gives zeros), and a, r, d, ok exactly what
-        sample_at(indices) returns.  Device tensors, no synchronisation.
-        nstep > 1 (gamma is then required): the same tuple with r = the n-step return and ns_idx and d those of the span's end, as
-        nstep_at(indices, nstep, gamma) gives them, and its discount and span appended.
-        stack > 1: positions 1 and 2 are the [n, stack] stacks of s_idx and ns_idx (stack_rows; column 0 is what stack = 1 returns,
-        with nstep > 1 ns_idx is the span's end), and depth [2, n] int32 -- of s_idx, of ns_idx -- is appended."""
-        if not self.on:
-            raise ValueError('replay: the buffer is off (record_replay())')
+        Returns the batch as a dict: the fields of sample_fields(n, action_dim, nstep, stack=stack) -- the table is there -- and
+        'frames', the ring's frame tensor as frame_view() gives it (a view, no copy: it changes with the next push).  s_idx and
+        ns_idx are f110_replay_locate's, and a, r, d, ok exactly what sample_at(indices) returns.  Device tensors, no synchronisation.
+        nstep > 1 (gamma is then required): r, ns_idx, d, discount and span are what nstep_at(indices, nstep, gamma) gives.
+        stack > 1: s_stack, ns_stack and depth are stack_rows of s_idx and of ns_idx (with nstep > 1 ns_idx is the span's end)."""
+        self._require_on()
         nstep, gamma = self._nstep(nstep, gamma)
-        if self._stack(stack) > 1:
-            res, depth = self._stacked(self.frames_at(indices, nstep, gamma), stack)
-            return res + (depth,)
-        if nstep > 1:
-            frames, s_idx, _, a, _, _, ok = self.frames_at(indices)
-            ns_idx, ret, d, discount, span = self.nstep_at(self._keep, nstep, gamma)
-            return frames, s_idx, ns_idx, a, ret, d, ok, discount, span
+        stack = self._stack(stack)
         eng = self.eng
-        idx = torch.as_tensor(indices).to(device=eng.device, dtype=torch.int64).contiguous().reshape(-1)
+        idx = self._indices(indices)
         n = idx.shape[0]
         s_idx = torch.empty((n,), dtype=torch.int64, device=eng.device)
         ns_idx = torch.empty((n,), dtype=torch.int64, device=eng.device)
         with torch.cuda.device(eng.device):
             _lib.check(eng.lib.f110_replay_locate(eng._h, idx.data_ptr(), n, s_idx.data_ptr(), ns_idx.data_ptr(), eng._stream()))
-        self._keep = idx
+        self._keep = idx   # (kept until the next call: the stream may not have read it yet)
         T, B = self.cfg.steps, eng.B
         found = s_idx >= 0
         at = torch.where(found, idx, torch.zeros_like(idx))
         a = torch.where(found[:, None], self.buf['actions'].view(T * B, -1)[at], torch.zeros((), dtype=torch.float32, device=eng.device))
         r = torch.where(found, self.buf['rewards'].view(-1)[at], torch.zeros((), dtype=torch.float64, device=eng.device))
         d = torch.where(found, self.buf['dones'].view(-1)[at], torch.zeros((), dtype=torch.uint8, device=eng.device))
-        frames = self.buf['frames'].view((T + 1) * B, self.rows, words(self.cols))
-        return frames, s_idx, ns_idx, a, r, d, found.to(torch.uint8)
+        b = dict(frames=self.frame_view(), indices=idx, s_idx=s_idx, ns_idx=ns_idx, a=a, r=r, d=d, ok=found.to(torch.uint8))
+        if nstep > 1:
+            b['ns_idx'], b['r'], b['d'], b['discount'], b['span'] = self.nstep_at(idx, nstep, gamma)
+        if stack > 1:
+            b['pair'] = self._keep_pair = torch.stack((b['s_idx'], b['ns_idx']))
+            b['stacks'] = torch.empty((2, n, stack), dtype=torch.int64, device=eng.device)
+            b['depth'] = torch.empty((2, n), dtype=torch.int32, device=eng.device)
+            b['s_stack'], b['ns_stack'] = b['stacks'][0], b['stacks'][1]
+            self._stacked(b, stack)
+        return b
 
     def sample_frames(self, batch_size, seed=None):
         """batch_size transitions drawn as sample() draws them (the same draw counter), returned as frames_at returns them."""
-        if not self.on:
-            raise ValueError('replay: the buffer is off (record_replay())')
+        self._require_on()
         idx, _ = self.draw(batch_size, seed)
         return self.frames_at(idx)
+
+    def _sample_dev(self, batch_size, counter, seed, out, nstep, gamma, stack, priorities):
+        """What sample_frames_dev and sample_priority_dev share: the inputs checked, `out` picked or checked, the one library call of the
+        combination (f110_priority_sample with priorities, else f110_replay_sample_nstep with nstep > 1, else f110_replay_sample)
+        and, with stack > 1, the one launch of the walk over out['pair'] behind it.  Returns a NEW dict -- out's own tensors and
+        'frames' -- and leaves `out` as it was: a caller keeps `out` across re-installs of the ring, and a frame view stored there
+        would pin the old ring's memory."""
+        self._require_on(priorities)
+        nstep, gamma = self._nstep(nstep, gamma)
+        stack = self._stack(stack)
+        eng, n = self.eng, int(batch_size)
+        if not torch.is_tensor(counter) or counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != torch.device(eng.device):
+            raise ValueError('replay: counter must be a [1] int64 tensor on %s' % (eng.device,))
+        o = self.sample_out(n, nstep, priorities, stack) if out is None else out
+        self._check_out(o, n, nstep, priorities, stack)
+        draw = (eng._h, self._seed(seed), counter.data_ptr(), n)
+        ptr = lambda *keys: tuple(o[k].data_ptr() for k in keys)  # noqa: E731
+        batch = ptr('indices', 's_idx', 'ns_idx', 'a', 'r', 'd', 'ok')
+        with torch.cuda.device(eng.device):
+            if priorities:
+                _lib.check(eng.lib.f110_priority_sample(*draw, nstep, gamma, *batch, *ptr('discount', 'span', 'prio', 'weight'), eng._stream()))
+            elif nstep > 1:
+                _lib.check(eng.lib.f110_replay_sample_nstep(*draw, nstep, gamma, *batch, *ptr('discount', 'span'), eng._stream()))
+            else:
+                _lib.check(eng.lib.f110_replay_sample(*draw, *batch, eng._stream()))
+        if stack > 1:
+            self._stacked(o, stack)
+        return dict(o, frames=self.frame_view())
 
     def sample_frames_dev(self, batch_size, counter, seed=None, out=None, nstep=1, gamma=None, stack=1):
         """f110_replay_sample: batch_size transitions drawn from a draw counter that lives on the device, in one kernel.  counter: a
@@ -373,45 +421,21 @@ class ReplayBuffer(Consumer):
         draw numbers counter .. counter + batch_size - 1 of the stream `seed` (default: the env's) exactly as draw() would with
         that counter, and a one-lane kernel behind it adds batch_size.  Nothing crosses from the host that changes from call to
         call, so a captured call replays with fresh draws.  The host counter of draw(), sample() and sample_frames() does not move.
-        Returns (frames, s_idx, ns_idx, a, r, d, ok, indices): the first seven what frames_at(indices) returns.  out: a dict with
-        the static tensors 'indices', 's_idx', 'ns_idx' [n] int64, 'a' [n, action_dim] fp32, 'r' [n] fp64, 'd' and 'ok' [n] uint8
-        to write into (sample_out() allocates one); the same tensors are then returned.  Device tensors, no synchronisation.
-        nstep > 1 (gamma is then required): f110_replay_sample_nstep, the same draws with the n-step walk in the same kernel.  The
-        tuple is the same with r = the n-step return and ns_idx and d those of the span's end, and 'discount' [n] fp64 and 'span' [n]
-        int32 appended (out then holds those two as well: sample_out(n, nstep)); everything behind the indices is what
-        nstep_at(indices, nstep, gamma) and frames_at(indices) give.
-        stack > 1: the sample kernels are untouched and one launch of the walk (stack_rows) runs behind them: positions 1 and 2 of
-        the tuple are then the [n, stack] stacks of s_idx and ns_idx ('s_stack', 'ns_stack' of out) and 'depth' [2, n] int32 (of
-        s_idx, of ns_idx) is appended; out: sample_out(n, nstep, stack=k), whose 's_idx' and 'ns_idx' are the halves of one tensor."""
-        if not self.on:
-            raise ValueError('replay: the buffer is off (record_replay())')
-        nstep, gamma = self._nstep(nstep, gamma)
-        stack = self._stack(stack)
-        eng, n = self.eng, int(batch_size)
-        if not torch.is_tensor(counter) or counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != torch.device(eng.device):
-            raise ValueError('replay: counter must be a [1] int64 tensor on %s' % (eng.device,))
-        o = self.sample_out(n, nstep, stack=stack) if out is None else out
-        self._check_out(o, n, nstep, False, stack)
-        if stack > 1:
-            res, depth = self._stacked(self.sample_frames_dev(n, counter, seed, {k: v for k, v in o.items() if k not in self.STACK_KEYS}, nstep, gamma),
-                                       stack, o)
-            return res + (depth,)
-        T, B = self.cfg.steps, eng.B
-        frames = self.buf['frames'].view((T + 1) * B, self.rows, words(self.cols))
-        if nstep > 1:
-            with torch.cuda.device(eng.device):
-                _lib.check(eng.lib.f110_replay_sample_nstep(eng._h, self._seed(seed), counter.data_ptr(), n, nstep, gamma, o['indices'].data_ptr(),
-                                                            o['s_idx'].data_ptr(), o['ns_idx'].data_ptr(), o['a'].data_ptr(), o['r'].data_ptr(),
-                                                            o['d'].data_ptr(), o['ok'].data_ptr(), o['discount'].data_ptr(), o['span'].data_ptr(),
-                                                            eng._stream()))
-            return frames, o['s_idx'], o['ns_idx'], o['a'], o['r'], o['d'], o['ok'], o['indices'], o['discount'], o['span']
-        with torch.cuda.device(eng.device):
-            _lib.check(eng.lib.f110_replay_sample(eng._h, self._seed(seed), counter.data_ptr(), n, o['indices'].data_ptr(), o['s_idx'].data_ptr(),
-                                                  o['ns_idx'].data_ptr(), o['a'].data_ptr(), o['r'].data_ptr(), o['d'].data_ptr(), o['ok'].data_ptr(),
-                                                  eng._stream()))
-        return frames, o['s_idx'], o['ns_idx'], o['a'], o['r'], o['d'], o['ok'], o['indices']
+        Returns the batch as a dict (sample_fields has the table): everything but 'indices' is what frames_at(indices, nstep, gamma,
+        stack) returns.  out: a dict of the static tensors to write into (sample_out(n, nstep, stack=stack) allocates one); the
+        returned dict is a new one that holds the same tensors and 'frames', `out` itself is not changed.  Device tensors, no
+        synchronisation.
+        nstep > 1 (gamma is then required): f110_replay_sample_nstep, the same draws with the n-step walk in the same kernel.
+        stack > 1: the sample kernels are untouched and one launch of the walk (stack_rows) runs behind them."""
+        return self._sample_dev(batch_size, counter, seed, out, nstep, gamma, stack, False)
 
-    STACK_KEYS = ('pair', 'stacks', 's_stack', 'ns_stack', 'depth')
+    def sample_priority_dev(self, batch_size, counter, seed=None, out=None, nstep=1, gamma=None, stack=1):
+        """f110_priority_sample: sample_frames_dev with draws in proportion to the transitions' priority words (record_replay(...,
+        priorities=...)), from the caller's device counter, in two launches.  The batch holds 'discount' and 'span' whatever nstep
+        is, and 'prio' and 'weight' (sample_fields(..., priorities=True)): the weights are exactly 1.0 on the rows of the smallest
+        word, for the beta the tree held before this call moved it on.  out: sample_out(n, nstep, priorities=True, stack=stack).
+        Device tensors, no synchronisation; a captured call replays with fresh draws."""
+        return self._sample_dev(batch_size, counter, seed, out, nstep, gamma, stack, True)
 
     def _check_out(self, o, n, nstep, priorities, stack):
         dev = torch.device(self.eng.device)
@@ -424,54 +448,13 @@ class ReplayBuffer(Consumer):
             raise ValueError("replay: out['s_idx'] / out['ns_idx'] and out['s_stack'] / out['ns_stack'] must be the halves of out['pair'] and "
                              "out['stacks'] (sample_out(..., stack=k))")
 
-    def sample_priority_dev(self, batch_size, counter, seed=None, out=None, nstep=1, gamma=None, stack=1):
-        """f110_priority_sample: sample_frames_dev with draws in proportion to the transitions' priority words (record_replay(...,
-        priorities=...)), from the caller's device counter, in two launches.  Returns the n-step form's tuple whatever nstep is --
-        (frames, s_idx, ns_idx, a, r, d, ok, indices, discount, span) -- with prio [n] int32 (the bits of the drawn uint32 words) and
-        weight [n] fp32 appended: the importance weights (N P(i))^-beta over the batch's maximum, exactly 1.0 on the rows of the
-        smallest word and 0 where ok is 0, for the beta the tree held before this call moved it on.  out: sample_out(n, nstep,
-        priorities=True).  Device tensors, no synchronisation; a captured call replays with fresh draws.
-        stack > 1: as sample_frames_dev -- positions 1 and 2 are the stacks, depth [2, n] is appended (out: sample_out(n, nstep,
-        priorities=True, stack=k))."""
-        if not self.on or self.priorities is None:
-            raise ValueError('replay: priorities are off (record_replay(..., priorities=True))')
-        nstep, gamma = self._nstep(nstep, gamma)
-        stack = self._stack(stack)
-        eng, n = self.eng, int(batch_size)
-        if not torch.is_tensor(counter) or counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != torch.device(eng.device):
-            raise ValueError('replay: counter must be a [1] int64 tensor on %s' % (eng.device,))
-        o = self.sample_out(n, nstep, priorities=True, stack=stack) if out is None else out
-        self._check_out(o, n, nstep, True, stack)
-        if stack > 1:
-            res, depth = self._stacked(self.sample_priority_dev(n, counter, seed, {k: v for k, v in o.items() if k not in self.STACK_KEYS}, nstep, gamma),
-                                       stack, o)
-            return res + (depth,)
-        T, B = self.cfg.steps, eng.B
-        frames = self.buf['frames'].view((T + 1) * B, self.rows, words(self.cols))
-        with torch.cuda.device(eng.device):
-            _lib.check(eng.lib.f110_priority_sample(eng._h, self._seed(seed), counter.data_ptr(), n, nstep, gamma, o['indices'].data_ptr(),
-                                                    o['s_idx'].data_ptr(), o['ns_idx'].data_ptr(), o['a'].data_ptr(), o['r'].data_ptr(),
-                                                    o['d'].data_ptr(), o['ok'].data_ptr(), o['discount'].data_ptr(), o['span'].data_ptr(),
-                                                    o['prio'].data_ptr(), o['weight'].data_ptr(), eng._stream()))
-        return frames, o['s_idx'], o['ns_idx'], o['a'], o['r'], o['d'], o['ok'], o['indices'], o['discount'], o['span'], o['prio'], o['weight']
-
     def _sample_shapes(self, n, nstep=1, priorities=False, stack=1):
-        shapes = {'indices': ((n,), torch.int64), 's_idx': ((n,), torch.int64), 'ns_idx': ((n,), torch.int64),
-                  'a': ((n, self.cfg.action_dim), torch.float32), 'r': ((n,), torch.float64), 'd': ((n,), torch.uint8), 'ok': ((n,), torch.uint8)}
-        if nstep > 1 or priorities:
-            shapes.update({'discount': ((n,), torch.float64), 'span': ((n,), torch.int32)})
-        if priorities:
-            shapes.update({'prio': ((n,), torch.int32), 'weight': ((n,), torch.float32)})
-        if stack > 1:
-            shapes.update({'pair': ((2, n), torch.int64), 'stacks': ((2, n, stack), torch.int64), 's_stack': ((n, stack), torch.int64),
-                           'ns_stack': ((n, stack), torch.int64), 'depth': ((2, n), torch.int32)})
-        return shapes
+        return sample_fields(n, self.cfg.action_dim, nstep, priorities, stack)
 
     def sample_out(self, batch_size, nstep=1, priorities=False, stack=1):
-        """The tensors sample_frames_dev writes, newly allocated: what its `out` takes ('discount' and 'span' with nstep > 1 only).
-        priorities=True: what sample_priority_dev writes ('discount' and 'span' whatever nstep is, 'prio' and 'weight').
-        stack > 1: 's_stack' and 'ns_stack' [n, stack] int64 and 'depth' [2, n] int32 as well; 's_idx' / 'ns_idx' are then the halves of
-        'pair' [2, n] and the two stacks the halves of 'stacks' [2, n, stack], so that one launch of the walk serves both."""
+        """The tensors sample_frames_dev writes, newly allocated: what its `out` takes (sample_fields(batch_size, action_dim, nstep,
+        priorities, stack); priorities=True: what sample_priority_dev writes).  With stack > 1 's_idx' / 'ns_idx' are the halves of
+        'pair' and the two stacks the halves of 'stacks'."""
         stack = self._stack(stack)
         shapes = self._sample_shapes(int(batch_size), int(nstep), bool(priorities), stack)
         o = {k: torch.empty(shape, dtype=dt, device=self.eng.device) for k, (shape, dt) in shapes.items() if stack == 1 or k not in ('s_idx', 'ns_idx', 's_stack', 'ns_stack')}

@@ -116,7 +116,8 @@ class SACAgent:
     on a ring without priorities.  False, the default, changes nothing: the same launches, graph key and bits, on any ring.
     stack: 1 is the reference's one frame.  k > 1 (up to replay.MAX_STACK): every network's conv1 has k input channels, the last k
     frames of the env (ReplayBuffer.stack_rows: repeated at an episode's start, never across a reset); update, capture_update and
-    update_graph draw with stack=k, update_batch takes 's_idx' / 'ns_idx' as [n, k], and act_from acts on the ring's newest stacks.
+    update_graph draw with stack=k and read the batch's 's_stack' / 'ns_stack', update_batch takes those (or 's_idx' / 'ns_idx' as
+    [n, k]), and act_from acts on the ring's newest stacks.
     Shared networks must have a conv1 of k input channels (ValueError otherwise).  stack is configuration, not state.  With stack = 1
     nothing changes: the same launches, graph key and bits.
     max_grad_norm: None, or a positive number or float('inf') that every one of the three SacAdam takes as its max_grad_norm: each
@@ -232,14 +233,18 @@ class SACAgent:
         all).  eps: the [n, action_dim] fp32 draws (None: torch.randn, or stream 0 of `source` with the envs' numbers as rows); out: a
         [n, action_dim] fp64 tensor that receives the action, a static buffer that path_actions or a captured step reads.  A row's action does not depend on the batch around it."""
         with torch.no_grad():
-            h = self.actor.features(frames, index)
-            if evaluate:
-                head = self.actor.head
-                return sample_actions(h, head.fc_mean.weight, head.fc_mean.bias, head.fc_log_std.weight, head.fc_log_std.bias, eps=None,
-                                      dtype=torch.float64, out=out)[0]
-            if eps is None and self.source is not None:
-                eps = self.source.normal(h.shape[0], self.action_dim, stream=0, rows=index)
-            return self.actor.head.sample(h, eps=eps, dtype=torch.float64, out=out)[0]
+            return self._act(self.actor.features(frames, index), index, evaluate, out, eps)
+
+    def _act(self, h, rows, evaluate, out, eps):
+        """The actor's tail on the features h, under the caller's no_grad: tanh(mean) with evaluate, else a sample whose draws, where
+        none are passed, are the device's for the rows `rows` (None: row i is env i)."""
+        head = self.actor.head
+        if evaluate:
+            return sample_actions(h, head.fc_mean.weight, head.fc_mean.bias, head.fc_log_std.weight, head.fc_log_std.bias, eps=None,
+                                  dtype=torch.float64, out=out)[0]
+        if eps is None and self.source is not None:
+            eps = self.source.normal(h.shape[0], self.action_dim, stream=0, rows=rows)
+        return head.sample(h, eps=eps, dtype=torch.float64, out=out)[0]
 
     def act_from(self, replay, evaluate=False, out=None, eps=None):
         """select_action on what the ring `replay` (F110VecEnv.replay) holds as every env's newest frames: ReplayBuffer.stack_latest(stack)
@@ -249,14 +254,7 @@ class SACAgent:
         self._check_replay(replay)
         rows, _ = replay.stack_latest(self.stack)
         with torch.no_grad():
-            h = self.actor.features(replay.frame_view(), rows[:, 0] if self.stack == 1 else rows)
-            head = self.actor.head
-            if evaluate:
-                return sample_actions(h, head.fc_mean.weight, head.fc_mean.bias, head.fc_log_std.weight, head.fc_log_std.bias, eps=None,
-                                      dtype=torch.float64, out=out)[0]
-            if eps is None and self.source is not None:
-                eps = self.source.normal(h.shape[0], self.action_dim, stream=0, rows=None)
-            return head.sample(h, eps=eps, dtype=torch.float64, out=out)[0]
+            return self._act(self.actor.features(replay.frame_view(), rows[:, 0] if self.stack == 1 else rows), None, evaluate, out, eps)
 
     # ---- learning
     def _eps(self, eps, n):
@@ -269,28 +267,32 @@ class SACAgent:
                 raise ValueError('SACAgent: eps_next and eps_new must be fp32 [%d, %d] on %s' % (n, self.action_dim, self.device))
         return eps[0], eps[1]
 
-    def _update(self, frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, losses, discount=None, weight=None, writeback=None):
-        """:544-580 on one batch; the three losses go to `losses` [3] (actor, critic1, critic2), which is returned.  discount: [n] fp64,
-        the target's discount per row (r is then the n-step return); None: gamma.  weight: [n] fp32 importance weights of the critics'
-        loss; writeback = (priorities, indices, ok): the tree that then takes the rows' new TD errors."""
+    def _update(self, batch, eps_next, eps_new, losses, writeback=None):
+        """:544-580 on one batch, a dict under the names of replay.sample_fields; the three losses go to `losses` [3] (actor, critic1,
+        critic2), which is returned.  The frame rows are 's_stack' / 'ns_stack' where the batch has them, else 's_idx' / 'ns_idx'.
+        'discount': [n] fp64, the target's discount per row ('r' is then the n-step return); without it gamma.  'weight': [n] fp32
+        importance weights of the critics' loss; writeback: the PriorityTree that then takes the new TD errors of the rows 'indices'
+        with 'ok'."""
         actor, critics, targets = self.actor, self.critics, self.targets
+        frames, a, discount, weight = batch['frames'], batch['a'], batch.get('discount'), batch.get('weight')
+        s_idx, ns_idx = batch.get('s_stack', batch['s_idx']), batch.get('ns_stack', batch['ns_idx'])
+        n = int(s_idx.shape[0])
         if eps_next is None and self.source is not None:
-            n = int(s_idx.shape[0])
             eps_next = self.source.normal(n, self.action_dim, stream=1)
             eps_new = self.source.normal(n, self.action_dim, stream=2)
         with torch.no_grad():                                                    # :544-549
             next_a, next_logp = actor.sample(frames, ns_idx, eps_next)
-            tv = td_target([t.trunk(frames, ns_idx) for t in targets], next_a, next_logp, r, d, *_heads(targets), self.gamma if discount is None else discount,
-                           self.alpha, dense=True)
+            tv = td_target([t.trunk(frames, ns_idx) for t in targets], next_a, next_logp, batch['r'], batch['d'], *_heads(targets),
+                           self.gamma if discount is None else discount, self.alpha, dense=True)
         q, _ = twin_q([c.trunk(frames, s_idx) for c in critics], a, *_heads(critics), dense=True)     # :551-552, a as the ring stores it (fp32)
         grad_q = torch.empty_like(q)
         if weight is None:
             critic_loss(q[0], q[1], tv, loss=losses[1:3], grad=grad_q)           # :553-554
         else:
-            td = torch.empty((int(s_idx.shape[0]),), dtype=torch.float32, device=self.device)
+            td = torch.empty((n,), dtype=torch.float32, device=self.device)
             critic_loss(q[0], q[1], tv, loss=losses[1:3], grad=grad_q, weight=weight, td=td)
             if writeback is not None:
-                writeback[0].update(writeback[1], writeback[2], td)
+                writeback.update(batch['indices'], batch['ok'], td)
         for opt in self.critic_opts:
             opt.zero_grad()
         torch.autograd.backward((q,), (grad_q,))
@@ -309,7 +311,8 @@ class SACAgent:
     def update_batch(self, batch, eps=None, replay=None):
         """One update on a batch that is given, not drawn: a dict with 'frames' [m, rows, words] int64, 's_idx' and 'ns_idx' [n] int64
         rows of it (-1: a zero frame), 'a' [n, action_dim] fp32, 'r' [n] fp64 and 'd' [n] uint8, as ReplayBuffer.sample_frames returns
-        them; with stack = k > 1 's_idx' and 'ns_idx' are [n, k] (ReplayBuffer.frames_at(..., stack=k)).  An optional 'discount' [n] fp64 is the target's discount per row in gamma's place ('r' is then the n-step return and
+        them; with stack = k > 1 the frame rows are 's_stack' and 'ns_stack' [n, k] (ReplayBuffer.frames_at(..., stack=k)), or 's_idx'
+        and 'ns_idx' themselves given as [n, k].  An optional 'discount' [n] fp64 is the target's discount per row in gamma's place ('r' is then the n-step return and
         'ns_idx', 'd' those of the span's end, as ReplayBuffer.frames_at with nstep > 1 returns them); without it gamma, whatever the agent's nstep.
         An optional 'weight' [n] fp32 weighs the critics' loss row by row (ReplayBuffer.sample_priority_dev's importance weights); with
         'indices' [n] int64 and 'ok' [n] uint8 beside it and `replay` (a ring with priorities) the rows' new priorities are written back
@@ -319,13 +322,13 @@ class SACAgent:
         n = int(batch['s_idx'].shape[0])
         eps_next, eps_new = self._eps(eps, n)
         losses = torch.empty((3,), dtype=torch.float32, device=self.device)
-        weight, writeback = batch.get('weight'), None
-        if weight is not None and replay is not None and 'indices' in batch and 'ok' in batch:
+        writeback = None
+        if batch.get('weight') is not None and replay is not None and 'indices' in batch and 'ok' in batch:
             if replay.priorities is None:
                 raise ValueError('SACAgent: the ring has no priorities (record_replay(..., priorities=True))')
-            writeback = (replay.priorities, batch['indices'], batch['ok'])
-        return self._update(batch['frames'], batch['s_idx'], batch['ns_idx'], batch['a'], batch['r'], batch['d'], eps_next, eps_new, losses,
-                            batch.get('discount'), weight, writeback)
+            writeback = replay.priorities
+        # (a 'discount' the caller supplies is used as it is, whatever the agent's nstep: only _draw drops one)
+        return self._update(batch, eps_next, eps_new, losses, writeback)
 
     def _check_replay(self, replay):
         if not replay.on:
@@ -348,29 +351,20 @@ class SACAgent:
         eps_next, eps_new = self._eps(eps, n)
         if check and len(replay) < n:
             return torch.zeros((3,), dtype=torch.float32, device=self.device)
-        self.sample = replay.sample_out(n, self.nstep, priorities=self.per, **self._stack_kw())
-        frames, s_idx, ns_idx, a, r, d, discount, weight, writeback = self._draw(replay, n, self.sample)
-        return self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, torch.empty((3,), dtype=torch.float32, device=self.device), discount,
-                            weight, writeback)
-
-    def _stack_kw(self):
-        return {} if self.stack == 1 else dict(stack=self.stack)
+        self.sample = replay.sample_out(n, self.nstep, self.per, self.stack)
+        batch, writeback = self._draw(replay, n, self.sample)
+        return self._update(batch, eps_next, eps_new, torch.empty((3,), dtype=torch.float32, device=self.device), writeback)
 
     def _draw(self, replay, n, out):
-        """The batch of an update drawn into `out` with the agent's draw counter -> (frames, s_idx, ns_idx, a, r, d, discount or None,
-        weight or None, writeback or None): the last two with per=True only."""
-        if self.per:
-            got = replay.sample_priority_dev(n, self.draws, out=out, nstep=self.nstep, gamma=self.gamma, **self._stack_kw())
-            # (with nstep = 1 the target takes gamma by value, as without priorities: got[8] holds its bits in every row)
-            return got[:6] + (None if self.nstep == 1 else got[8], got[11], (replay.priorities, got[7], got[6]))
-        got = self._draw_uniform(replay, n, out)
-        return got + (None, None)
-
-    def _draw_uniform(self, replay, n, out):
+        """The batch of an update drawn into `out` with the agent's draw counter -> (batch, writeback): the batch as the ring returns
+        it (a new dict: `out` gains nothing), writeback the ring's PriorityTree with per=True, else None."""
+        draw = replay.sample_priority_dev if self.per else replay.sample_frames_dev
+        batch = draw(n, self.draws, out=out, nstep=self.nstep, gamma=self.gamma, stack=self.stack)
         if self.nstep == 1:
-            return replay.sample_frames_dev(n, self.draws, out=out, **self._stack_kw())[:6] + (None,)
-        got = replay.sample_frames_dev(n, self.draws, out=out, nstep=self.nstep, gamma=self.gamma, **self._stack_kw())
-        return got[:6] + (got[8],)
+            # the target takes gamma BY VALUE, as it always has with nstep = 1 (the same launches, graph key and bits): the
+            # 'discount' column the priority draw wrote, gamma's bits in every row, is not handed on
+            batch.pop('discount', None)
+        return batch, replay.priorities if self.per else None
 
     # ---- the captured update
     def _graph_key(self, replay, n):
@@ -402,7 +396,7 @@ class SACAgent:
         if key != self._g_key:
             self._graphs = {}
             self._g_key, self._g_replay = key, replay
-            self._g_sample = replay.sample_out(n, self.nstep, priorities=self.per, **self._stack_kw())
+            self._g_sample = replay.sample_out(n, self.nstep, self.per, self.stack)
             self._g_eps = [torch.zeros((n, self.action_dim), dtype=torch.float32, device=dev) for _ in range(2)]
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(dev)
@@ -410,9 +404,9 @@ class SACAgent:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.stream(side), torch.cuda.graph(g, stream=side):
             self.zero_grad(set_to_none=True)
-            frames, s_idx, ns_idx, a, r, d, discount, weight, writeback = self._draw(replay, n, self._g_sample)
+            batch, writeback = self._draw(replay, n, self._g_sample)
             eps_next, eps_new = (None, None) if draws else self._g_eps
-            self._update(frames, s_idx, ns_idx, a, r, d, eps_next, eps_new, self._g_losses, discount, weight, writeback)
+            self._update(batch, eps_next, eps_new, self._g_losses, writeback)
         cur.wait_stream(side)
         self._graphs[bool(draws)] = g
         self.captures += 1

@@ -416,7 +416,8 @@ def test_closed_loop_from_bitmap_and_ring_to_features(assets):
 
     def check_ring(what):
         s, a, r, ns, d, ok = env.replay.sample_at(all_idx)
-        frames, s_idx, ns_idx, a2, r2, d2, ok2 = env.replay.frames_at(all_idx)
+        at = env.replay.frames_at(all_idx)
+        frames, s_idx, ns_idx, a2, r2, d2, ok2 = (at[k] for k in ('frames', 's_idx', 'ns_idx', 'a', 'r', 'd', 'ok'))
         assert frames.data_ptr() == env.replay.buf['frames'].data_ptr() and tuple(frames.shape) == ((T + 1) * B, rows, 2)
         for x, y in ((a, a2), (r, r2), (d, d2), (ok, ok2)):
             assert x.dtype == y.dtype and torch.equal(x, y), what
@@ -455,7 +456,8 @@ def test_closed_loop_from_bitmap_and_ring_to_features(assets):
     check_ring('after step_graph')
     # the same draws as sample(): sample_frames moves the one draw counter
     first = env.replay._draws
-    frames, s_idx, ns_idx, a, r, d, ok = env.replay.sample_frames(64, seed=5)
+    batch = env.replay.sample_frames(64, seed=5)
+    frames, s_idx, ns_idx, a, r, d, ok = (batch[k] for k in ('frames', 's_idx', 'ns_idx', 'a', 'r', 'd', 'ok'))
     drawn = gk.to_host(env.replay._keep)
     want_idx, want_ok, _ = rc.draw(gk.to_host(env.replay.buf['valid']), int(env.replay.buf['count']), 5, first, 64)
     assert np.array_equal(drawn, want_idx) and np.array_equal(gk.to_host(ok), want_ok) and env.replay._draws == first + 64

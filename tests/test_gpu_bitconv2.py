@@ -346,7 +346,8 @@ def test_closed_loop_from_bitmap_and_ring_to_features(assets):
             assert 2 * sum(bool((im == 255).any() and (im == 0).any()) for im in bitmap) >= B
             checked += 1
     first = env.replay._draws
-    frames, s_idx, ns_idx, a, r, d, ok = env.replay.sample_frames(32, seed=5)
+    batch = env.replay.sample_frames(32, seed=5)
+    frames, s_idx, ns_idx, a, r, d, ok = (batch[k] for k in ('frames', 's_idx', 'ns_idx', 'a', 'r', 'd', 'ok'))
     s2 = env.replay.sample_at(torch.as_tensor(gk.to_host(env.replay._keep), device=env.device))
     assert env.replay._draws == first + 32 and int(ok.sum()) > 0
     with torch.no_grad():

@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 
 G = nc.GAMMA
 WALK = ('ns_frame', 'ret', 'd', 'discount', 'span')
+FIELDS = ('s_idx', 'ns_idx', 'a', 'r', 'd', 'ok')                    # of every batch, beside 'frames' and 'indices'
 
 
 def _ring(assets, ring, rows=40, cols=30):
@@ -72,14 +73,17 @@ def test_nstep_at_equals_the_checker_at_every_index(assets, name):
         assert [t.dtype for t in got] == [torch.int64, torch.float64, torch.uint8, torch.float64, torch.int32]
         _assert_walk(got, want, (name, nstep))
     # nstep = 1: what frames_at gives, and gamma's bits in every row
-    frames, s_idx, ns_idx, a, r, d, ok = rp.frames_at(idx)
+    plain = rp.frames_at(idx)
+    assert sorted(plain) == sorted(('frames', 'indices') + FIELDS)
+    frames, s_idx, ns_idx, a, r, d, ok = (plain[k] for k in ('frames',) + FIELDS)
     one = rp.nstep_at(idx, 1, G)
     assert torch.equal(one[0], ns_idx) and _bits_equal(one[1], gk.to_host(r)) and torch.equal(one[2], d) and torch.equal((one[4] > 0).to(torch.uint8), ok)
     assert _bits_equal(one[3], np.full(len(idx), G))
     # frames_at(nstep=3): frames_at's frame before, action and ok beside nstep_at's walk
     got = rp.frames_at(idx, nstep=3, gamma=G)
-    assert len(got) == 9 and got[0].data_ptr() == frames.data_ptr() and torch.equal(got[1], s_idx) and torch.equal(got[3], a) and torch.equal(got[6], ok)
-    _assert_walk((got[2], got[4], got[5], got[7], got[8]), nc.walk(valid, dones, rewards, count, idx, 3, G), (name, 'frames_at'))
+    assert sorted(got) == sorted(('frames', 'indices', 'discount', 'span') + FIELDS)
+    assert got['frames'].data_ptr() == frames.data_ptr() and torch.equal(got['s_idx'], s_idx) and torch.equal(got['a'], a) and torch.equal(got['ok'], ok)
+    _assert_walk((got['ns_idx'], got['r'], got['d'], got['discount'], got['span']), nc.walk(valid, dones, rewards, count, idx, 3, G), (name, 'frames_at'))
     assert env.eng.device_errors() == 0
     env.close()
 
@@ -89,13 +93,13 @@ def _assert_sample(rp, ring, got, want_idx, nstep):
     the rest `==` frames_at(indices)."""
     import torch
     valid, dones, rewards, count = ring
-    frames, s_idx, ns_idx, a, r, d, ok, idx, discount, span = got
+    frames, s_idx, ns_idx, a, r, d, ok, idx, discount, span = (got[k] for k in ('frames',) + FIELDS + ('indices', 'discount', 'span'))
     assert np.array_equal(gk.to_host(idx), want_idx)
     _assert_walk((ns_idx, r, d, discount, span), nc.walk(valid, dones, rewards, count, want_idx, nstep, G), 'sample')
     again = rp.nstep_at(idx, nstep, G)
     assert all(torch.equal(x, y) for x, y in zip((ns_idx, r, d, discount, span), again))
     one = rp.frames_at(idx)
-    assert frames.data_ptr() == one[0].data_ptr() and torch.equal(s_idx, one[1]) and torch.equal(a, one[3]) and torch.equal(ok, one[6])
+    assert frames.data_ptr() == one['frames'].data_ptr() and torch.equal(s_idx, one['s_idx']) and torch.equal(a, one['a']) and torch.equal(ok, one['ok'])
 
 
 def test_sample_nstep_continues_one_stream_of_draws(assets):
@@ -107,18 +111,18 @@ def test_sample_nstep_continues_one_stream_of_draws(assets):
     counter = torch.zeros((1,), dtype=torch.int64, device=env.device)
     first = rp.sample_frames_dev(5, counter, seed=seed, nstep=3, gamma=G)
     second = rp.sample_frames_dev(7, counter, seed=seed, nstep=3, gamma=G)
-    assert len(first) == 10 and int(counter) == 12
+    assert sorted(first) == sorted(('frames', 'indices', 'discount', 'span') + FIELDS) and int(counter) == 12
     _assert_sample(rp, ring, first, rc.draw(valid, count, seed, 0, 5)[0], 3)
     _assert_sample(rp, ring, second, rc.draw(valid, count, seed, 5, 7)[0], 3)
-    # the one-step call at the same draw numbers draws the same transitions, and returns its seven tensors and the indices as before
+    # the one-step call at the same draw numbers draws the same transitions, and returns its seven fields and the indices as before
     counter.zero_()
     plain = rp.sample_frames_dev(5, counter, seed=seed)
-    assert len(plain) == 8 and torch.equal(plain[7], first[7]) and torch.equal(plain[1], first[1]) and int(counter) == 5
+    assert sorted(plain) == sorted(('frames', 'indices') + FIELDS) and torch.equal(plain['indices'], first['indices']) and torch.equal(plain['s_idx'], first['s_idx']) and int(counter) == 5
     # out=: with nstep > 1 the two extra tensors are required, written and returned
     out = rp.sample_out(7, 3)
     assert sorted(out) == sorted(list(rp.sample_out(7)) + ['discount', 'span']) and 'discount' not in rp.sample_out(7, 1)
     got = rp.sample_frames_dev(7, counter, seed=seed, out=out, nstep=3, gamma=G)
-    assert got[8] is out['discount'] and got[9] is out['span'] and got[4] is out['r'] and int(counter) == 12
+    assert got['discount'] is out['discount'] and got['span'] is out['span'] and got['r'] is out['r'] and 'frames' not in out and int(counter) == 12
     _assert_sample(rp, ring, got, rc.draw(valid, count, seed, 5, 7)[0], 3)
     assert env.eng.device_errors() == 0
     env.close()
@@ -169,7 +173,8 @@ def test_the_empty_ring_gives_zero_transitions(assets):
     out = env.replay.sample_out(9, 3)
     for t in out.values():
         t.fill_(3)
-    frames, s_idx, ns_idx, a, r, d, ok, idx, discount, span = env.replay.sample_frames_dev(9, counter, out=out, nstep=3, gamma=G)
+    got = env.replay.sample_frames_dev(9, counter, out=out, nstep=3, gamma=G)
+    s_idx, ns_idx, a, r, d, ok, idx, discount, span = (got[k] for k in FIELDS + ('indices', 'discount', 'span'))
     assert all((gk.to_host(t) == -1).all() for t in (idx, s_idx, ns_idx)) and not any(gk.to_host(t).any() for t in (a, r, d, ok, span))
     assert _bits_equal(discount, np.full(9, G)) and int(counter) == 9 and env.eng.device_errors() == 0
     env.close()
@@ -327,7 +332,8 @@ def test_nstep_3_is_update_batch_on_a_batch_assembled_by_hand(assets):
     l3 = three.update(env.replay, n, eps=eps)
     s = three.sample
     assert sorted(s) == sorted(list(env.replay.sample_out(n)) + ['discount', 'span'])
-    frames, s_idx, _, a, _, _, ok = env.replay.frames_at(s['indices'])
+    one_step = env.replay.frames_at(s['indices'])
+    frames, s_idx, a, ok = (one_step[k] for k in ('frames', 's_idx', 'a', 'ok'))
     ns_idx, ret, d, discount, span = env.replay.nstep_at(s['indices'], 3, three.gamma)
     assert bool(ok.all()) and bool((span > 1).any()) and torch.equal(span, s['span']) and torch.equal(ret, s['r']) and torch.equal(discount, s['discount'])
     lh = by_hand.update_batch(dict(frames=frames, s_idx=s_idx, ns_idx=ns_idx, a=a, r=ret, d=d, discount=discount), eps=eps)

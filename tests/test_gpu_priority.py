@@ -224,18 +224,21 @@ def _spread_words(env, seed=9):
     return leaf, node
 
 
+BATCH = ('frames', 's_idx', 'ns_idx', 'a', 'r', 'd', 'ok', 'indices', 'discount', 'span', 'prio', 'weight')   # the priority draw's, whatever nstep is
+
+
 def _assert_sample(env, got, leaf, node, first, n, nstep):
     import torch
     rp = env.replay
-    frames, s_idx, ns_idx, a, r, d, ok, idx, discount, span, prio, weight = got
+    frames, s_idx, ns_idx, a, r, d, ok, idx, discount, span, prio, weight = (got[k] for k in BATCH)
     want_idx, want_q, _ = pc.pick(leaf, node, SEED, first, n)
     assert np.array_equal(gk.to_host(idx), want_idx) and np.array_equal(_u32(prio), want_q)
     walk = rp.nstep_at(idx, nstep, G)
     assert all(torch.equal(x, y) for x, y in zip((ns_idx, r, d, discount, span), walk))
     one = rp.frames_at(idx)
-    assert frames.data_ptr() == one[0].data_ptr() and torch.equal(s_idx, one[1]) and torch.equal(a, one[3]) and torch.equal(ok, one[6])
+    assert frames.data_ptr() == one['frames'].data_ptr() and torch.equal(s_idx, one['s_idx']) and torch.equal(a, one['a']) and torch.equal(ok, one['ok'])
     if nstep == 1:
-        assert torch.equal(ns_idx, one[2]) and torch.equal(r.view(torch.int64), one[4].view(torch.int64)) and torch.equal(d, one[5])
+        assert torch.equal(ns_idx, one['ns_idx']) and torch.equal(r.view(torch.int64), one['r'].view(torch.int64)) and torch.equal(d, one['d'])
     return want_q
 
 
@@ -248,10 +251,10 @@ def test_sample_equals_the_checkers_pick_and_the_ring(assets, nstep):
     counter = torch.zeros((1,), dtype=torch.int64, device=env.device)
     first = rp.sample_priority_dev(64, counter, seed=SEED, nstep=nstep, gamma=G)
     second = rp.sample_priority_dev(200, counter, seed=SEED, nstep=nstep, gamma=G)
-    assert len(first) == 12 and int(counter) == 264 and first[10].dtype == torch.int32 and first[11].dtype == torch.float32
+    assert sorted(first) == sorted(BATCH) and int(counter) == 264 and first['prio'].dtype == torch.int32 and first['weight'].dtype == torch.float32
     _assert_sample(env, first, leaf, node, 0, 64, nstep)
     _assert_sample(env, second, leaf, node, 64, 200, nstep)
-    assert bool(first[6].all()) and (nstep == 1 or bool((first[9] > 1).any()))
+    assert bool(first['ok'].all()) and (nstep == 1 or bool((first['span'] > 1).any()))
     assert sorted(rp.sample_out(8, nstep, priorities=True)) == sorted(list(rp.sample_out(8, 3)) + ['prio', 'weight'])
     with pytest.raises(ValueError):
         rp.sample_priority_dev(8, counter, out=rp.sample_out(8, 3))
@@ -282,7 +285,7 @@ def test_a_captured_sample_replays_as_three_eager_ones(assets):
     eager = []
     for k in range(3):
         got = rp.sample_priority_dev(n, counter, seed=SEED, nstep=3, gamma=G)
-        eager.append([t.clone() for t in got[1:]])
+        eager.append({k: got[k].clone() for k in BATCH[1:]})
         assert int(counter) == (k + 1) * n and p.beta == want_beta[k]
     counter.zero_()
     p.set_beta(0.4)
@@ -298,10 +301,10 @@ def test_a_captured_sample_replays_as_three_eager_ones(assets):
     for k in range(3):
         graph.replay()
         torch.cuda.synchronize()
-        assert all(torch.equal(x, y) for x, y in zip(got[1:], eager[k])), k
+        assert sorted(got) == sorted(BATCH) and all(torch.equal(got[f], eager[k][f]) for f in BATCH[1:]), k
         assert int(counter) == (k + 1) * n and p.beta == want_beta[k]
         _assert_sample(env, got, leaf, node, k * n, n, 3)
-    assert not torch.equal(eager[0][6], eager[1][6]) and not torch.equal(eager[0][10], eager[1][10])     # other draws, other weights
+    assert not torch.equal(eager[0]['indices'], eager[1]['indices']) and not torch.equal(eager[0]['weight'], eager[1]['weight'])     # other draws, other weights
     assert env.eng.device_errors() == 0
     env.close()
 
@@ -323,7 +326,7 @@ def test_importance_weights(assets):
     for beta in (0.4, 1.0, 0.0):
         p.set_beta(beta)
         got = rp.sample_priority_dev(n, counter, seed=SEED, nstep=1, gamma=G)
-        ok, idx, prio, w = gk.to_host(got[6]), gk.to_host(got[7]), _u32(got[10]), gk.to_host(got[11])
+        ok, idx, prio, w = gk.to_host(got['ok']), gk.to_host(got['indices']), _u32(got['prio']), gk.to_host(got['weight'])
         assert (ok == 0).sum() >= 5 and (idx[ok == 0] == stale).all() and (ok != 0).sum() >= 100
         qmin = prio[ok != 0].min()
         assert w.dtype == np.float32 and (w[ok == 0] == 0.0).all() and (w[(ok != 0) & (prio == qmin)] == 1.0).all() and ((ok != 0) & (prio == qmin)).any()

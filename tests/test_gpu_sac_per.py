@@ -86,7 +86,9 @@ def test_first_update_is_update_batch_by_hand_and_the_tree_is_the_checkers(asset
     p.rebuild()
     assert _same_tree(_tree(env), before)
     counter = torch.zeros((1,), dtype=torch.int64, device=env.device)
-    frames, s_idx, ns_idx, a, r, d, ok_t, indices, discount, span, prio, weight = rp.sample_priority_dev(n, counter, nstep=nstep, gamma=per.gamma)
+    got = rp.sample_priority_dev(n, counter, nstep=nstep, gamma=per.gamma)
+    frames, s_idx, ns_idx, a, r, d, ok_t, indices, discount, span, prio, weight = (
+        got[k] for k in ('frames', 's_idx', 'ns_idx', 'a', 'r', 'd', 'ok', 'indices', 'discount', 'span', 'prio', 'weight'))
     assert all(torch.equal(x, s[k]) for k, x in dict(indices=indices, s_idx=s_idx, ns_idx=ns_idx, a=a, r=r, d=d, weight=weight, prio=prio, span=span).items())
     batch = dict(frames=frames, s_idx=s_idx, ns_idx=ns_idx, a=a, r=r, d=d, weight=weight, indices=indices, ok=ok_t)
     if nstep > 1:
@@ -155,7 +157,8 @@ def test_equal_priorities_are_the_unweighted_update(assets):
         lp = per.update(rp, n, eps=eps)
         s = per.sample
         assert bool((s['weight'] == 1.0).all()) and bool((s['prio'] == pc.ONE).all()) and bool(s['ok'].all())
-        frames, s_idx, ns_idx, a, r, d, ok = rp.frames_at(s['indices'])
+        at = rp.frames_at(s['indices'])
+        frames, s_idx, ns_idx, a, r, d, ok = (at[k] for k in ('frames', 's_idx', 'ns_idx', 'a', 'r', 'd', 'ok'))
         lh = plain.update_batch(dict(frames=frames, s_idx=s_idx, ns_idx=ns_idx, a=a, r=r, d=d), eps=eps)
         assert _same_bits(lp, lh) and _differing(_snapshot(per), _snapshot(plain)) == [], u
         leaf, node, state = _tree(env)

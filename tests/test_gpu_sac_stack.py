@@ -127,7 +127,9 @@ def test_stack_3_is_update_batch_on_a_batch_assembled_by_hand(assets):
     l3 = three.update(env.replay, n, eps=eps)
     s = three.sample
     assert sorted(s) == sorted(env.replay.sample_out(n, stack=K))
-    frames, s_stack, ns_stack, a, r, d, ok, depth = env.replay.frames_at(s['indices'], stack=K)
+    at = env.replay.frames_at(s['indices'], stack=K)
+    frames, s_stack, ns_stack, a, r, d, ok, depth = (at[k] for k in ('frames', 's_stack', 'ns_stack', 'a', 'r', 'd', 'ok', 'depth'))
+    assert torch.equal(at['s_idx'], s_stack[:, 0]) and torch.equal(at['ns_idx'], ns_stack[:, 0])
     assert bool(ok.all()) and tuple(s_stack.shape) == (n, K) and torch.equal(s_stack, s['s_stack']) and torch.equal(ns_stack, s['ns_stack'])
     assert torch.equal(depth, s['depth']) and bool((depth < K).any()) and bool((depth == K).any())
     assert torch.equal(s['s_idx'], s_stack[:, 0]) and torch.equal(s['ns_idx'], ns_stack[:, 0])

@@ -38,11 +38,12 @@ def _ring(assets, rows=40, cols=30):
 def _assert_is_frames_at(rp, got, want_idx):
     """got: sample_frames_dev's result; every output but the indices `==` frames_at(indices)."""
     import torch
-    frames, idx = got[0], got[7]
+    frames, idx = got['frames'], got['indices']
     assert np.array_equal(gk.to_host(idx), want_idx)
     want = rp.frames_at(idx)
-    assert frames.data_ptr() == want[0].data_ptr() and frames.shape == want[0].shape
-    for name, g, w in zip(NAMES, got[1:7], want[1:]):
+    assert frames.data_ptr() == want['frames'].data_ptr() and frames.shape == want['frames'].shape
+    for name in NAMES:
+        g, w = got[name], want[name]
         assert g.dtype == w.dtype and g.shape == w.shape and torch.equal(g, w), name
 
 
@@ -57,11 +58,11 @@ def test_two_calls_continue_one_stream_of_draws(assets):
     _assert_is_frames_at(rp, first, rc.draw(pattern, c['count'], c['seed'], 0, 5)[0])
     _assert_is_frames_at(rp, second, rc.draw(pattern, c['count'], c['seed'], 5, 7)[0])
     assert int(counter) == 12
-    assert gk.to_host(first[6]).all() and gk.to_host(second[6]).all() and (gk.to_host(first[1]) >= 0).all() and gk.to_host(second[3]).any()
-    idx = np.concatenate([gk.to_host(first[7]), gk.to_host(second[7])])
+    assert gk.to_host(first['ok']).all() and gk.to_host(second['ok']).all() and (gk.to_host(first['s_idx']) >= 0).all() and gk.to_host(second['a']).any()
+    idx = np.concatenate([gk.to_host(first['indices']), gk.to_host(second['indices'])])
     assert pattern[idx // c['B'], idx % c['B']].all()                                  # no drawn index is invalid
     # the stored action names its env: a[., 0] = 16 env + 1000 k
-    assert np.array_equal(gk.to_host(second[3])[:, 0] % 1000, 16.0 * (gk.to_host(second[7]) % c['B']))
+    assert np.array_equal(gk.to_host(second['a'])[:, 0] % 1000, 16.0 * (gk.to_host(second['indices']) % c['B']))
     # the host counter of draw() has not moved, and draw() does not move the device counter
     assert rp._draws == host_before
     again, _ = rp.draw(5, seed=c['seed'])
@@ -70,7 +71,7 @@ def test_two_calls_continue_one_stream_of_draws(assets):
     out = rp.sample_out(7)
     counter.fill_(-3)
     got = rp.sample_frames_dev(7, counter, seed=c['seed'], out=out)
-    assert all(got[1 + k] is out[name] for k, name in enumerate(NAMES)) and got[7] is out['indices']
+    assert all(got[name] is out[name] for name in NAMES) and got['indices'] is out['indices'] and 'frames' not in out
     _assert_is_frames_at(rp, got, rc.draw(pattern, c['count'], c['seed'], 2 ** 64 - 3, 7)[0])
     assert int(counter) == 4
     for bad in (lambda: rp.sample_frames_dev(5, counter.int()), lambda: rp.sample_frames_dev(5, counter.cpu()),
@@ -90,11 +91,12 @@ def test_the_empty_ring(assets):
     out = env.replay.sample_out(9)
     for t in out.values():
         t.fill_(3)
-    frames, s_idx, ns_idx, a, r, d, ok, idx = env.replay.sample_frames_dev(9, counter, out=out)
+    got = env.replay.sample_frames_dev(9, counter, out=out)
+    s_idx, ns_idx, a, r, d, ok, idx = (got[k] for k in NAMES + ('indices',))
     assert (gk.to_host(idx) == -1).all() and (gk.to_host(s_idx) == -1).all() and (gk.to_host(ns_idx) == -1).all()
     assert not gk.to_host(ok).any() and not gk.to_host(a).any() and not gk.to_host(r).any() and not gk.to_host(d).any() and int(counter) == 9
     env.step(torch.zeros((c['B'], 1, 2), dtype=torch.float64, device=env.device))      # one frame, no transition yet
-    assert not gk.to_host(env.replay.sample_frames_dev(9, counter)[6]).any() and int(counter) == 18
+    assert not gk.to_host(env.replay.sample_frames_dev(9, counter)['ok']).any() and int(counter) == 18
     assert env.eng.device_errors() == 0
     env.close()
 

@@ -17,6 +17,8 @@ from test_gpu_nstep import _ring
 pytestmark = pytest.mark.gpu
 
 G = nc.GAMMA
+BASE = ('frames', 'indices', 's_idx', 'ns_idx', 'a', 'r', 'd', 'ok')  # of every batch
+STACKED = ('pair', 'stacks', 's_stack', 'ns_stack', 'depth')            # what stack > 1 adds
 
 
 def _raw_stack(env, rows, n, k):
@@ -53,7 +55,8 @@ def test_stack_rows_equal_the_checker_at_every_row(assets, name):
         l_rows, l_depth = rp.stack_latest(k)
         assert np.array_equal(gk.to_host(l_rows), latest['rows']) and np.array_equal(gk.to_host(l_depth), latest['depth'])
     # the invariant, on the device's own locate: stack(ns)[1:] == stack(s)[:-1] where the stack of s is full
-    frames, s_idx, ns_idx, a, r, d, ok = rp.frames_at(nc.all_indices(T, B))
+    plain = rp.frames_at(nc.all_indices(T, B))
+    frames, s_idx, ns_idx, ok = (plain[f] for f in ('frames', 's_idx', 'ns_idx', 'ok'))
     keep = ok.bool()
     s4, ds = rp.stack_rows(s_idx[keep], 4)
     ns4, dns = rp.stack_rows(ns_idx[keep], 4)
@@ -61,10 +64,12 @@ def test_stack_rows_equal_the_checker_at_every_row(assets, name):
     assert torch.equal(ns4[full][:, 1:], s4[full][:, :-1]) and torch.equal(dns, torch.clamp(ds + 1, max=4)) and bool(keep.any())
     # frames_at(stack=k): the stacks of its own s_idx / ns_idx, everything else unchanged
     got = rp.frames_at(nc.all_indices(T, B), stack=3)
-    assert len(got) == 8 and got[0].data_ptr() == frames.data_ptr() and all(torch.equal(x, y) for x, y in zip(got[3:7], (a, r, d, ok)))
-    for pos, idx in ((1, s_idx), (2, ns_idx)):
+    assert sorted(got) == sorted(BASE + STACKED) and got['frames'].data_ptr() == frames.data_ptr()
+    assert all(torch.equal(got[f], plain[f]) for f in ('a', 'r', 'd', 'ok'))
+    for pos, (name, col0, idx) in enumerate((('s_stack', 's_idx', s_idx), ('ns_stack', 'ns_idx', ns_idx))):
         want_rows, want_depth = rp.stack_rows(idx, 3)
-        assert torch.equal(got[pos], want_rows) and torch.equal(got[pos][:, 0], idx) and torch.equal(got[7][pos - 1], want_depth)
+        assert torch.equal(got[name], want_rows) and torch.equal(got[name][:, 0], idx) and torch.equal(got['depth'][pos], want_depth)
+        assert torch.equal(got[col0], idx) and torch.equal(got[col0], got[name][:, 0])
     assert env.eng.device_errors() == 0
     env.close()
 
@@ -205,19 +210,20 @@ def test_the_newest_stacks_follow_a_mirror_through_a_scripted_run(assets, how):
 
 # ---------------------------------------------------------------------------------------------- behind the samples
 def _assert_stacks(rp, ring, got, k, nstep):
-    """got: a sampling call's tuple with stack = k: positions 1 and 2 `==` the checker's stacks of the rows the plain call gives for the
-    same indices, and `==` stack_rows of them; depth is appended."""
+    """got: a sampling call's batch with stack = k: 's_stack' and 'ns_stack' `==` the checker's stacks of the rows the plain call gives for
+    the same indices, and `==` stack_rows of them; 's_idx' and 'ns_idx' are those rows, column 0 of the stacks; 'depth' is beside them."""
     import torch
     valid, dones, rewards, count = ring
-    idx = got[7]
+    idx = got['indices']
     plain = rp.frames_at(idx, nstep=nstep, gamma=G if nstep > 1 else None)
-    depth = got[-1]
-    for pos in (1, 2):
-        want = sc.stack(valid, count, gk.to_host(plain[pos]), k)
-        assert np.array_equal(gk.to_host(got[pos]), want['rows']) and np.array_equal(gk.to_host(depth[pos - 1]), want['depth'])
-        again = rp.stack_rows(plain[pos], k)
-        assert torch.equal(got[pos], again[0]) and torch.equal(depth[pos - 1], again[1]) and torch.equal(got[pos][:, 0], plain[pos])
-    assert all(torch.equal(x, y) for x, y in zip(got[3:7], plain[3:7]))
+    depth = got['depth']
+    for pos, (name, col0) in enumerate((('s_stack', 's_idx'), ('ns_stack', 'ns_idx'))):
+        want = sc.stack(valid, count, gk.to_host(plain[col0]), k)
+        assert np.array_equal(gk.to_host(got[name]), want['rows']) and np.array_equal(gk.to_host(depth[pos]), want['depth'])
+        again = rp.stack_rows(plain[col0], k)
+        assert torch.equal(got[name], again[0]) and torch.equal(depth[pos], again[1]) and torch.equal(got[name][:, 0], plain[col0])
+        assert torch.equal(got[col0], plain[col0]) and torch.equal(got[col0], got[name][:, 0])
+    assert all(torch.equal(got[f], plain[f]) for f in ('a', 'r', 'd', 'ok'))
 
 
 def test_a_captured_walk_behind_a_captured_sample(assets):
@@ -241,21 +247,21 @@ def test_a_captured_walk_behind_a_captured_sample(assets):
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     assert int(counter) == 0 and (gk.to_host(out['indices']) == -5).all() and (gk.to_host(out['stacks']) == -5).all()
-    assert len(got) == 9 and got[1].data_ptr() == out['s_stack'].data_ptr() and got[2].data_ptr() == out['ns_stack'].data_ptr() and got[8] is out['depth']
+    assert sorted(got) == sorted(BASE + STACKED) and 'frames' not in out and all(got[f] is out[f] for f in out)
     depths = set()
     for u in range(3):
         graph.replay()
         torch.cuda.synchronize()
         want_idx, want_ok, _ = rc.draw(valid, count, seed, u * n, n)
-        assert want_ok.all() and np.array_equal(gk.to_host(got[7]), want_idx) and int(counter) == (u + 1) * n
+        assert want_ok.all() and np.array_equal(gk.to_host(got['indices']), want_idx) and int(counter) == (u + 1) * n
         _assert_stacks(rp, ring, got, k, 1)
         assert torch.equal(out['s_idx'], out['s_stack'][:, 0]) and torch.equal(out['ns_idx'], out['ns_stack'][:, 0])
-        depths.update(gk.to_host(got[8]).reshape(-1).tolist())
+        depths.update(gk.to_host(got['depth']).reshape(-1).tolist())
     assert depths == {1, 2, 3, 4} and env.eng.device_errors() == 0
     # uncaptured, without out=: the same draws at the same counter
     counter.zero_()
     fresh = rp.sample_frames_dev(n, counter, seed=seed, stack=k)
-    assert np.array_equal(gk.to_host(fresh[7]), rc.draw(valid, count, seed, 0, n)[0])
+    assert np.array_equal(gk.to_host(fresh['indices']), rc.draw(valid, count, seed, 0, n)[0])
     _assert_stacks(rp, ring, fresh, k, 1)
     env.close()
 
@@ -268,14 +274,14 @@ def test_the_stacks_of_the_nstep_and_the_prioritized_sample(assets):
     rp, seed, n, k = env.replay, rc.DRAW_CASE['seed'], 64, 3
     counter = torch.zeros((1,), dtype=torch.int64, device=env.device)
     got = rp.sample_frames_dev(n, counter, seed=seed, nstep=3, gamma=G, stack=k)
-    assert len(got) == 11 and int(counter) == n and bool((got[9] > 1).any())
+    assert sorted(got) == sorted(BASE + ('discount', 'span') + STACKED) and int(counter) == n and bool((got['span'] > 1).any())
     _assert_stacks(rp, ring, got, k, 3)
-    at = rp.frames_at(got[7], nstep=3, gamma=G, stack=k)
-    assert len(at) == 10 and torch.equal(at[1], got[1]) and torch.equal(at[2], got[2]) and torch.equal(at[9], got[10])
+    at = rp.frames_at(got['indices'], nstep=3, gamma=G, stack=k)
+    assert sorted(at) == sorted(got) and all(torch.equal(at[f], got[f]) for f in ('s_stack', 'ns_stack', 'depth', 's_idx', 'ns_idx'))
     rp.set_priorities(True)
     for nstep in (1, 3):
         got = rp.sample_priority_dev(n, counter, seed=seed, nstep=nstep, gamma=G, stack=k)
-        assert len(got) == 13 and bool(got[6].all())
+        assert sorted(got) == sorted(BASE + ('discount', 'span', 'prio', 'weight') + STACKED) and bool(got['ok'].all())
         _assert_stacks(rp, ring, got, k, nstep)
         plain = rp.sample_out(n, nstep, priorities=True, stack=k)
         assert sorted(plain) == sorted(list(rp.sample_out(n, nstep, priorities=True)) + ['pair', 'stacks', 's_stack', 'ns_stack', 'depth'])

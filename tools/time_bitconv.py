@@ -52,11 +52,13 @@ if 'ring' in SECTIONS or 'backward' in SECTIONS:
     assert bool(rp.sample_at(idx)[5].all())
 
     def ours():
-        frames, s_idx, ns_idx, a, r, d, ok = rp.frames_at(idx)
+        at = rp.frames_at(idx)
+        frames, s_idx = at['frames'], at['s_idx']
         return conv_bits(frames, w, b, stride=STRIDE, on=255.0 * SCALE, cols=COLS, index=s_idx)
 
     def ours_both():
-        frames, s_idx, ns_idx, a, r, d, ok = rp.frames_at(idx)
+        at = rp.frames_at(idx)
+        frames, s_idx, ns_idx = at['frames'], at['s_idx'], at['ns_idx']
         return (conv_bits(frames, w, b, stride=STRIDE, on=255.0 * SCALE, cols=COLS, index=s_idx),
                 conv_bits(frames, w, b, stride=STRIDE, on=255.0 * SCALE, cols=COLS, index=ns_idx))
 
@@ -77,7 +79,8 @@ if 'ring' in SECTIONS or 'backward' in SECTIONS:
                 'write of one out tensor alone (fill_)': (lambda o=torch.empty((n, CH, OH, OW), device='cuda'): o.fill_(1.0))}, N, 5, 3, name='ring  ')
 
     if 'backward' in SECTIONS:
-        frames, s_idx, _, _, _, _, _ = rp.frames_at(idx)
+        at = rp.frames_at(idx)
+        frames, s_idx = at['frames'], at['s_idx']
         s32 = rp.sample_at(idx, dtype=torch.float32, scale=SCALE)[0]
         g = torch.randn((n, CH, OH, OW), device='cuda')
         wg = w.clone().requires_grad_()

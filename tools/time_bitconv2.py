@@ -79,7 +79,8 @@ def section(title, n, src, kw):
 for sec in SECTIONS:
     if sec == 'ring':
         idx, _ = rp.draw(4096, seed=1)
-        frames, s_idx = rp.frames_at(idx)[:2]
+        at = rp.frames_at(idx)
+        frames, s_idx = at['frames'], at['s_idx']
         section('4096 samples of the ring', 4096, frames, dict(cols=COLS, index=s_idx))
     elif sec.startswith('u8_'):
         n = int(sec[3:])
