@@ -62,10 +62,11 @@ class PackedRacelines(object):
 
 class ProgressTracker(Consumer):
     """The progress tracker of one Engine (f110_progress_install / _bind / _update).  The outputs live in `buf` (tensors [B, A]:
-    s, d, heading_error, delta, progress, s_prev, seg, seen), allocated and bound by the first install and kept from then on;
-    `lap_length` is the tensor [B] of every env's lap length."""
+    s, d, heading_error, delta, progress, s_prev, seg, seen -- and lap_length [B], every env's lap length, which the host fills at
+    an install and no kernel reads), allocated and bound by the first install and kept from then on; `lap_length` is that tensor."""
     NAME = 'progress'
-    INFO = {'frenet_s': 's', 'frenet_d': 'd', 'heading_error': 'heading_error', 'progress': 'progress', 'progress_delta': 'delta'}
+    INFO = {'frenet_s': 's', 'frenet_d': 'd', 'heading_error': 'heading_error', 'progress': 'progress', 'progress_delta': 'delta',
+            'lap_length': 'lap_length'}
     STATE = {'progress': 'progress', 's_prev': 's_prev', 'seen': 'seen'}
     DTYPES = {'s': torch.float64, 'd': torch.float64, 'heading_error': torch.float64, 'delta': torch.float64,
               'progress': torch.float64, 's_prev': torch.float64, 'seg': torch.int32, 'seen': torch.uint8}
@@ -90,12 +91,14 @@ class ProgressTracker(Consumer):
                                 for a in (pk.xy, pk.offsets, pk.len, pk.cum, pk.psi, pk.lap_length, assign)]
         _lib.check(eng.lib.f110_progress_install(eng._h, xy, offsets, pk.K, *tables, int(bool(grid))))
         if self.buf is None:
-            self._bind({k: torch.zeros((eng.B, eng.A), dtype=dt, device=eng.device) for k, dt in self.DTYPES.items()},
-                       _lib.ProgressBuffers)
+            buf = {k: torch.zeros((eng.B, eng.A), dtype=dt, device=eng.device) for k, dt in self.DTYPES.items()}
+            buf['lap_length'] = torch.zeros((eng.B,), dtype=torch.float64, device=eng.device)
+            self._bind(buf, _lib.ProgressBuffers)
+            self.lap_length = buf['lap_length']
         else:
             self.restart()
         lap = pk.lap_length[assign] if assign is not None else np.full(eng.B, pk.lap_length[0])
-        self.lap_length = self.info['lap_length'] = torch.as_tensor(lap, device=eng.device)
+        self.lap_length.copy_(torch.as_tensor(lap))
         self.on = True
 
     def remove(self):

@@ -47,6 +47,14 @@ def same(got, want):
     return _host(got).shape == _host(want).shape and differing(got, want) == 0
 
 
+def equal(got, want):
+    """`==` at the array's own width: the same dtype and shape, bit patterns for floats, values for the integers."""
+    got, want = np.asarray(got), np.asarray(want)
+    if got.dtype != want.dtype or got.shape != want.shape:
+        return False
+    return same(got, want) if got.dtype.kind == 'f' else bool((got == want).all())
+
+
 class Guarded:
     """count elements of `dtype` (fp32 unless given) with GUARD elements of `fill` either side, the first `off` elements past a
     16-byte boundary; through matrix() a [rows, cols] view whose rows lie ld apart, with `fill` between the rows.  `fill` may be

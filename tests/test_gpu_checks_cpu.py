@@ -78,6 +78,16 @@ def test_bits_differing_and_same():
         gk.bits(np.zeros(3, np.int32))
 
 
+def test_equal_wants_dtype_shape_and_every_bit():
+    zeros, nans = np.array([0.0, -0.0]), np.array([np.nan, 1.0])
+    assert gk.equal(zeros, zeros.copy()) and not gk.equal(zeros, zeros[::-1]) and gk.equal(nans, nans.copy())
+    assert not gk.equal(zeros, zeros.astype(np.float32)) and not gk.equal(zeros.astype(np.float32), zeros)     # (no cast either way)
+    ints = np.array([1, 2, 3], np.int32)
+    assert gk.equal(ints, ints.copy()) and not gk.equal(ints, ints.astype(np.int64)) and not gk.equal(ints, np.array([1, 2, 4], np.int32))
+    assert not gk.equal(ints, ints.reshape(3, 1)) and not gk.equal(ints, ints.astype(np.float64))
+    assert gk.equal(np.array([True, False]), np.array([True, False])) and not gk.equal(np.array([1, 0], np.uint8), np.array([True, False]))
+
+
 def test_to_device_copies():
     assert gk.to_device(None) is None
     a = np.arange(4, dtype=np.float32)
